@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MicroMix mgemm hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -503,16 +503,43 @@ def compact_line(r, details_path=None):
     return line
 
 
+DUMP_ROWS = 1024       # rows of the [M, N] product stored in full by --dump-outputs (16 MiB as float32)
+DUMP_SEED = 0
+
+
+def dump_outputs(directory, out):
+    """--dump-outputs: what the timed path returned in its last step -- the bf16 [M, N] product of `mixedgemm.matmul` (with --gpus N > 1
+    the all-reduced product of the sharded layer) -- as .npy files, 16 MiB in all:
+      out_rows.npy     float32 [DUMP_ROWS, N]: a fixed sample of rows (seeded choice, ascending), every element exact
+      out_row_sum.npy  float64 [M]: the sum of every row of the full product
+      out_col_sum.npy  float64 [N]: the sum of every column of the full product
+    The two sums are taken on the host in float64 over the bf16 values, so they are the same from run to run and a difference
+    anywhere in the product shows in them.  `out` is a host tensor."""
+    import torch
+    d = out.to(torch.float32).numpy()
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(d.shape[0], size=min(DUMP_ROWS, d.shape[0]), replace=False))
+    os.makedirs(directory, exist_ok=True)
+    arrays = {"out_rows": np.ascontiguousarray(d[rows]), "out_row_sum": d.astype(np.float64).sum(1),
+              "out_col_sum": d.astype(np.float64).sum(0)}
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps (one GEMM launch each); ms_per_step is their mean")
     ap.add_argument("--warmup", type=int, default=50)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's output to DIR/*.npy (see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="headline GEMM only (profiling runs)")
     ap.add_argument("--details", default=os.path.join("gpurun_out", "bench_details.json"),
                     help="file for the full result (every note / kernel name / per-case dictionary); the printed line carries numbers only")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args, sys.argv[1:]))
 
@@ -639,6 +666,8 @@ def main():
         step()
     barrier()
     dt = time.perf_counter() - t0
+    # the last timed step's product, copied to the host before anything else writes into `out`
+    last_out = out.cpu() if args.dump_outputs and rank == 0 else None
     extra_launch = "K stream launches"
     # the same K steps once more as ONE hipGraph replay, timed the same way (auxiliary figure: which of the two modes is
     # faster differs between devices of the pool -- graph 55.6 vs stream 53.9 us on one box, 54 vs 57-60 on another -- so
@@ -1100,6 +1129,9 @@ def main():
             details = args.details
         except OSError as e:
             print(f"[bench] could not write the details file ({e})", file=sys.stderr)
+        if last_out is not None:
+            names = dump_outputs(args.dump_outputs, last_out)
+            print(f"[bench] wrote {', '.join(n + '.npy' for n in names)} to {args.dump_outputs}", file=sys.stderr)
         print(compact_line(result, details), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -112,3 +112,34 @@ def test_describe_names_the_product_kernels_and_ignores_retired_switches():
     d = run()
     assert "mm::g256::mx_gemm256_kernel<true,false> x 256" in d[0] and "g256::" in d[1] and "mx_gemm256_act_kernel x 1792" in d[2]
     assert run(MICROMIX_GEMM_W1="1", MICROMIX_GEMM_PERSIST="1") == d
+
+
+def test_dump_outputs_writes_a_fixed_float_sample(tmp_path):
+    """--dump-outputs: float32 / float64 .npy files under the 64 MB cap, the same sampled rows every run, and sums over the whole product
+    (a change in a row the sample leaves out still shows)"""
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(3)
+    out = torch.randn((bench.M, bench.N), generator=g).to(torch.bfloat16)
+    names = bench.dump_outputs(str(tmp_path / "a"), out)
+    assert names == ["out_col_sum", "out_row_sum", "out_rows"]
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(os.path.getsize(tmp_path / "a" / f"{n}.npy") for n in names) <= 64 * 2 ** 20
+    full = out.float().numpy()
+    rows = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(bench.M, bench.DUMP_ROWS, replace=False))
+    assert got["out_rows"].shape == (bench.DUMP_ROWS, bench.N) and np.array_equal(got["out_rows"], full[rows])
+    assert np.array_equal(got["out_row_sum"], full.astype(np.float64).sum(1))
+    assert np.array_equal(got["out_col_sum"], full.astype(np.float64).sum(0))
+    bench.dump_outputs(str(tmp_path / "b"), out)
+    assert all(np.array_equal(got[n], np.load(tmp_path / "b" / f"{n}.npy")) for n in names)
+    other = out.clone()
+    other[int(np.setdiff1d(np.arange(bench.M), rows)[0]), 7] += 1.0
+    bench.dump_outputs(str(tmp_path / "c"), other)
+    assert not np.array_equal(got["out_row_sum"], np.load(tmp_path / "c" / "out_row_sum.npy"))
+
+
+def test_steps_below_one_are_refused():
+    import subprocess
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert p.returncode == 2 and "--steps must be at least 1" in p.stderr

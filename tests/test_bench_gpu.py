@@ -46,3 +46,34 @@ def test_bench_line_is_short_and_complete():
     assert d["n_gpus"] == 1 and d["roofline"]["frac"] > 0.2 and d["cpu_baseline"]["value"] > 0
     assert set(d["mixed"]) >= {"q_o_all_fp4", "q_o_3072_896_128", "down_12288_1024_1024"} and d["roofline"]["zero_operands"]["kernel_us"] > 0
     assert "power" in d and "llama_layer" in d and "quantizers" in d
+
+
+def test_dump_outputs_are_the_timed_product(tmp_path):
+    """--dump-outputs after the timed steps: the last step's [M, N] product, equal from run to run (fixed inputs), and equal to the same
+    GEMM computed again in this process on the bench's inputs; `steps` and `ms_per_step` in the line are the timed steps'"""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+    from micromix_amd import mixedgemm
+    dumps = []
+    for run in ("a", "b"):
+        d = str(tmp_path / run)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "1", "--no-extras",
+                            "--details", str(tmp_path / f"details_{run}.json"), "--dump-outputs", d],
+                           capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+        line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
+        assert line["steps"] == 7 and line["ms_per_step"] > 0
+        dumps.append({n: np.load(os.path.join(d, f"{n}.npy")) for n in ("out_rows", "out_row_sum", "out_col_sum")})
+    for n in dumps[0]:
+        assert dumps[0][n].dtype in (np.float32, np.float64) and np.array_equal(dumps[0][n], dumps[1][n]), n
+    dev = torch.device("cuda:0")
+    x, w, idx = (t.to(dev) for t in bench.synth_inputs())
+    a = mixedgemm.reorder_quantize_x(x, idx, *bench.SPLIT)
+    b = mixedgemm.reorder_quantize_w4(w, idx, *bench.SPLIT)
+    want = mixedgemm.matmul(a[0], b[0], a[1], b[1], a[2], b[2], a[3], b[3], a[4], b[4], a[5], b[5]).cpu()
+    bench.dump_outputs(str(tmp_path / "here"), want)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], np.load(tmp_path / "here" / f"{n}.npy")), n
