@@ -294,6 +294,43 @@ int mm_rmsnorm_qlinear_decode(const void *X_bf16, const void *norm_weight_bf16, 
                               const uint8_t *BS, const uint8_t *BO, const uint8_t *SFBN, const uint8_t *SFBS, const uint8_t *SFBO, int M, int N,
                               int KN, int KS, int KO, int wmode, int flags, const void *bias_bf16, void *D_bf16, mm_stream_t stream);
 
+/*
+ * Paged KV cache for decode (version >= 600).  The reference's vendored FlashInfer layout and parameter convention
+ * (flashinfer/page.cuh:15,75-103, quantization.cuh:60-80), head_dim 128, any page size P >= 1, 64-bit offsets throughout:
+ *   MM_KV_INT4  kv_data uint8 [max_pages, L, 2, Hkv, P, 64]: index 0 of the third dim is K, 1 is V; byte j of a row holds element 2j in
+ *               its low nibble and 2j + 1 in its high nibble.  kv_param fp16 [max_pages, L, 2, Hkv, P, 2] = (scale, zero) per token and
+ *               head; value = code * scale - zero.
+ *   MM_KV_BF16  kv_data bf16 [max_pages, L, 2, Hkv, P, 128]; kv_param unused (NULL)
+ * Page table (int32, device): kv_indptr [B + 1] and kv_indices [nnz] list sequence b's pages in order; last_page_len [B] in 1..P; a
+ * sequence without pages has length 0.  The table already counts the tokens being appended.  Page indices outside [0, max_pages) are
+ * skipped (nothing read or written for their tokens).
+ *
+ * mm_kv_append: k, v bf16 [T, Hkv, 128]; append_indptr [B + 1] splits the T tokens among the sequences (arange(B + 1) for one decode
+ *   token each); sequence b's tokens go to its last append_indptr[b + 1] - append_indptr[b] positions (page.cuh:180-188).  Int4: each
+ *   (token, head) row of 128 values is quantized as quantize_int_group(x, 4, 128) (model/qLlamaLayer.py:13-23) in fp32 with fp16
+ *   parameters, round-half-even throughout:
+ *     s = fp16(max(max - min, 1e-5) / 15);  base = clamp(rint(-min / s), 0, 15);  code = clamp(rint(x / s) + base, 0, 15);
+ *     zero = fp16(base * s)     (correctly rounded divides; fp16 conversions saturate to +-65504; finite inputs)
+ *   A row that does not straddle zero keeps the reference's behaviour: base clamps to 0 and the top codes clip.  Bf16: a copy.
+ *   Nothing outside the target slots is written.
+ * mm_paged_decode: one query token per sequence, q bf16 [B, Hq, 128], Hq = g * Hkv with g <= 16; query head h attends kv head h / g
+ *   (HF repeat_kv) over every cached token (no mask); softmax in fp32 with sm_scale (<= 0: 1 / sqrt(128)); o bf16 [B, Hq, 128], rounded
+ *   once; a sequence of length 0 gives o = 0.  Split-KV: the tokens are cut into chunks chosen from (B, Hkv, max_seq_len) alone, so a
+ *   captured graph stays valid while the sequences grow up to max_seq_len (longer sequences are still attended in full, by the last
+ *   chunk).  With more than one chunk the partials go to `workspace` (mm_paged_decode_workspace_bytes, 16-byte aligned, not shared
+ *   with a concurrent call) and a second launch merges them; with one chunk (workspace_bytes() == 0) one launch writes o.
+ * Null pointers and bad sizes: MM_ERR_BAD_ARG; head_dim != 128 or g > 16: MM_ERR_UNSUPPORTED; both without device work.
+ */
+enum mm_kv_dtype { MM_KV_INT4 = 0, MM_KV_BF16 = 1 };
+int mm_kv_append(void *kv_data, void *kv_param, int kv_dtype, int max_pages, int num_layers, int layer, int num_kv_heads, int page_size,
+                 int head_dim, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_len, int batch,
+                 const void *k_bf16, const void *v_bf16, const int32_t *append_indptr, int num_tokens, mm_stream_t stream);
+size_t mm_paged_decode_workspace_bytes(int batch, int num_qo_heads, int num_kv_heads, int max_seq_len);
+int mm_paged_decode(const void *q_bf16, const void *kv_data, const void *kv_param, int kv_dtype, int max_pages, int num_layers, int layer,
+                    int num_kv_heads, int page_size, int head_dim, const int32_t *kv_indptr, const int32_t *kv_indices,
+                    const int32_t *last_page_len, int batch, int num_qo_heads, int max_seq_len, float sm_scale, void *workspace,
+                    size_t workspace_bytes, void *o_bf16, mm_stream_t stream);
+
 /* Which kernel(s) and how many workgroups mm_matmul / mm_matmul_ws launch for this problem on the CURRENT device (the same
  * decision code as the launcher; workspace_bytes = 0 means "no workspace", i.e. never split-K).  Returns a string in a
  * thread-local buffer, valid until the calling thread's next call.  Used by bench.py to name the kernel it timed. */

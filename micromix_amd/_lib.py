@@ -20,6 +20,7 @@ EXPORTS = (
     "mm_matmul_ws", "mm_matmul_workspace_bytes", "mm_matmul_ws_reset",
     "mm_gate_up_activate", "mm_gate_up_activate_decode", "mm_rmsnorm_gate_up_activate_decode", "mm_rmsnorm_gate_up_activate_decode_supported", "mm_gate_up_activate_decode_supported", "mm_down_activate_decode", "mm_down_activate_decode_supported", "mm_down_activate_decode_supported_w", "mm_gate_up_activate_workspace_bytes", "mm_gate_up_activate_describe", "mm_rmsnorm_quantize", "mm_qlinear_decode", "mm_qlinear_decode_supported", "mm_qlinear_decode_supported_w", "mm_rmsnorm_qlinear_decode", "mm_rmsnorm_qlinear_decode_supported", "mm_rmsnorm_qlinear_decode_supported_w", "mm_matmul_grouped", "mm_reorder_quantize_grouped",
     "mm_matmul_describe", "mm_test_function", "mm_diag_set_kernel_events",
+    "mm_kv_append", "mm_paged_decode_workspace_bytes", "mm_paged_decode",
 )
 # every symbol include/micromix_diag.h declares (libmicromix_diag.so: hardware probes for tests/tools, never used by the ops)
 DIAG_LIB_PATH = os.environ.get("MICROMIX_DIAG_LIB") or os.path.join(_PKG, "lib", "libmicromix_diag.so")
@@ -32,6 +33,7 @@ MM_ROUND_PER_SEGMENT, MM_ROUND_ONCE, MM_SPLIT_K_ALWAYS, MM_WS_TICKETS_ZEROED, MM
 MM_WS_TICKET_BYTES = 4096
 MM_RMS_REFERENCE, MM_RMS_NO_INTEGER_ROUND = 0, 1
 MM_NORM_NO_INTEGER_ROUND = 0x100
+MM_KV_INT4, MM_KV_BF16 = 0, 1
 
 class MMGroup(ctypes.Structure):
     """mm_group of include/micromix_hip.h"""
@@ -134,6 +136,12 @@ def load():
         lib.mm_diag_set_clock_buffer.argtypes = [vp]
     lib.mm_diag_set_kernel_events.restype = i
     lib.mm_diag_set_kernel_events.argtypes = [vp, vp]
+    lib.mm_kv_append.restype = i
+    lib.mm_kv_append.argtypes = [vp, vp] + [i] * 7 + [vp] * 3 + [i, vp, vp, vp, i, vp]
+    lib.mm_paged_decode_workspace_bytes.restype = sz
+    lib.mm_paged_decode_workspace_bytes.argtypes = [i] * 4
+    lib.mm_paged_decode.restype = i
+    lib.mm_paged_decode.argtypes = [vp, vp, vp] + [i] * 7 + [vp] * 3 + [i, i, i, ctypes.c_float, vp, sz, vp, vp]
     _lib = lib
     return lib
 

@@ -179,4 +179,13 @@ size_t mx_gemm_workspace_bytes(int M, int N, const int K[3], bool w4, bool force
 bool mx_gemm_small_m_uses_tiles(int M, int N, const int K[3], bool w4, size_t ws_bytes, bool force_split);
 const char *describe_mx_gemm256(int M, int N, const int K[3], bool w4, size_t ws_bytes, bool force_split, bool tickets_zeroed);   // thread-local buffer  // 0 when mm_matmul would not split K for this shape
 
+// paged KV cache (kv_cache.hip)
+void kv_decode_split(int B, int Hkv, int max_seq_len, int *nc, int *chunk);     // chunks of mm_paged_decode (host-known values only)
+hipError_t launch_kv_append(void *kv_data, void *kv_param, bool int4, const int *kv_indptr, const int *kv_indices, const int *last_page_len,
+                            int B, const void *k, const void *v, const int *append_indptr, int T, int max_pages, int L, int layer, int Hkv,
+                            int P, hipStream_t stream);
+hipError_t launch_paged_decode(const void *q, const void *kv_data, const void *kv_param, bool int4, const int *kv_indptr, const int *kv_indices,
+                               const int *last_page_len, int B, int Hq, int Hkv, int max_pages, int L, int layer, int P, int max_seq_len,
+                               float sm_scale, void *ws, void *o, hipStream_t stream);
+
 }  // namespace mm

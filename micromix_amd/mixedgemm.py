@@ -19,7 +19,8 @@ Differences from the reference, all deliberate:
     downproj_quantize_w / _w4 (W, KN, KS, KO)         -> (WN, WS, WO, SFWN, SFWS, SFWO)
     rmsnorm_quantize_x(X, W, eps, reorder_index, KN, KS, KO) -> (XN, XS, XO, SFXN, SFXS, SFXO)    (section 8f rank 2)
 The remaining exports of the reference module (FlashInfer KV ops) are outside the hot path; they raise
-NotImplementedError.
+NotImplementedError.  The paged KV cache itself is `kv_append` / `paged_decode` below (GQA, bf16 q,
+quantizes K/V itself; micromix_amd/kvcache.py wraps them), on the reference's FlashInfer layout.
 """
 from __future__ import annotations
 
@@ -28,7 +29,8 @@ import torch
 from . import _lib
 
 __all__ = ["test_function", "matmul", "gate_up_activate", "interleave_gate_up", "reorder_quantize_x", "reorder_quantize_w", "reorder_quantize_w4", "activate_quantize_x",
-           "downproj_quantize_w", "downproj_quantize_w4", "rmsnorm_quantize_x", "qlinear_decode", "qlinear_decode_supported", "matmul_grouped", "reorder_quantize_x_grouped"]
+           "downproj_quantize_w", "downproj_quantize_w4", "rmsnorm_quantize_x", "qlinear_decode", "qlinear_decode_supported", "matmul_grouped", "reorder_quantize_x_grouped",
+           "kv_append", "paged_decode", "paged_decode_workspace_bytes"]
 
 
 def test_function():
@@ -817,3 +819,122 @@ def rmsnorm_quantize_x(X, W, eps, reorder_index, KN, KS, KO, *, integer_round=Tr
 
 for _n in ("batch_decode_i4", "batch_decode_f16", "init_kv_i4", "init_kv_f16", "append_kv_i4", "append_kv_f16"):
     globals()[_n] = _not_on_path(_n)
+
+
+# ---- paged KV cache (include/micromix_hip.h, mm_kv_append / mm_paged_decode; micromix_amd/kvcache.py is the small cache object) ----
+
+def _kv_geometry(kv_data, kv_param, index):
+    """(dtype code, max_pages, L, Hkv, P) of a cache; int4: uint8 [max_pages, L, 2, Hkv, P, 64] + fp16 params [..., P, 2],
+    bf16: bf16 [max_pages, L, 2, Hkv, P, 128] and kv_param None."""
+    if kv_param is None:
+        if not _ok(kv_data, torch.bfloat16, index):
+            _check_tensor(kv_data, "kv_data", torch.bfloat16)
+            raise RuntimeError(f"kv_data must be on cuda:{index}")
+        if kv_data.dim() != 6 or kv_data.size(2) != 2 or kv_data.size(5) != 128:
+            raise RuntimeError("bf16 kv_data must be [max_pages, L, 2, Hkv, P, 128]")
+        kind = _lib.MM_KV_BF16
+    else:
+        if not (_ok(kv_data, torch.uint8, index) and _ok(kv_param, torch.float16, index)):
+            _check_tensor(kv_data, "kv_data", torch.uint8)
+            _check_tensor(kv_param, "kv_param", torch.float16, kv_data.device)
+            raise RuntimeError(f"kv_data / kv_param must be on cuda:{index}")
+        if kv_data.dim() != 6 or kv_data.size(2) != 2 or kv_data.size(5) != 64:
+            raise RuntimeError("int4 kv_data must be [max_pages, L, 2, Hkv, P, 64] uint8")
+        if tuple(kv_param.shape) != tuple(kv_data.shape[:5]) + (2,):
+            raise RuntimeError("kv_param must be [max_pages, L, 2, Hkv, P, 2] fp16, matching kv_data")
+        kind = _lib.MM_KV_INT4
+    max_pages, L, _, Hkv, P, _ = kv_data.shape
+    return kind, max_pages, L, Hkv, P
+
+
+def _page_table(kv_indptr, kv_indices, last_page_len, dev):
+    for n, t in (("kv_indptr", kv_indptr), ("kv_indices", kv_indices), ("last_page_len", last_page_len)):
+        if not _ok(t, torch.int32, dev.index):
+            _check_tensor(t, n, torch.int32, dev)
+    B = last_page_len.numel()
+    if kv_indptr.numel() != B + 1:
+        raise RuntimeError("kv_indptr must have B + 1 entries (B = last_page_len.numel())")
+    return B
+
+
+def kv_append(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, k, v, append_indptr, layer_idx):
+    """Write T new tokens' K and V (bf16 [T, Hkv, 128]) into layer `layer_idx` of a paged cache, in place.
+
+    Not an export of the reference module (its append_kv_i4 / _f16 take K/V already quantized and one head count).  The page table
+    (kv_indptr [B + 1], kv_indices, last_page_len [B], int32) already counts the new tokens; append_indptr [B + 1] splits the T tokens
+    among the sequences, each sequence's go to its last positions.  kv_param None: bf16 cache (a copy); otherwise int4 codes + fp16
+    (scale, zero) by the rule of quantize_int_group(x, 4, 128) (include/micromix_hip.h).  Runs on the current stream, capture-safe.
+    """
+    lib = _lib.load()
+    if not (isinstance(kv_data, torch.Tensor) and kv_data.is_cuda):
+        _check_tensor(kv_data, "kv_data", torch.uint8 if kv_param is not None else torch.bfloat16)
+    dev = kv_data.device
+    kind, max_pages, L, Hkv, P = _kv_geometry(kv_data, kv_param, dev.index)
+    B = _page_table(kv_indptr, kv_indices, last_page_len, dev)
+    if not _ok(append_indptr, torch.int32, dev.index):
+        _check_tensor(append_indptr, "append_indptr", torch.int32, dev)
+    for n, t in (("k", k), ("v", v)):
+        if not _ok(t, torch.bfloat16, dev.index):
+            _check_tensor(t, n, torch.bfloat16, dev)
+    if k.dim() != 3 or k.shape != v.shape or k.size(1) != Hkv or k.size(2) != 128:
+        raise RuntimeError(f"k and v must both be [T, {Hkv}, 128] bf16")
+    if append_indptr.numel() != B + 1:
+        raise RuntimeError("append_indptr must have B + 1 entries")
+    layer_idx = int(layer_idx)
+    if not 0 <= layer_idx < L:
+        raise RuntimeError(f"layer_idx {layer_idx} outside the cache's {L} layers")
+    with _on_device(dev.index):
+        st = lib.mm_kv_append(_ptr(kv_data), _ptr(kv_param) if kv_param is not None else None, kind, max_pages, L, layer_idx, Hkv, P, 128,
+                              _ptr(kv_indptr), _ptr(kv_indices), _ptr(last_page_len), B, _ptr(k), _ptr(v), _ptr(append_indptr),
+                              k.size(0), _stream_ptr(dev))
+    if st:
+        _lib.check(st, "kv_append")
+
+
+def paged_decode_workspace_bytes(B, Hq, Hkv, max_seq_len):
+    """bytes of fp32 scratch paged_decode needs for this bound (0: one launch, no workspace)"""
+    return int(_lib.load().mm_paged_decode_workspace_bytes(int(B), int(Hq), int(Hkv), int(max_seq_len)))
+
+
+def paged_decode(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, max_seq_len, sm_scale=None, workspace=None):
+    """Single-token GQA attention over layer `layer_idx` of a paged cache: q bf16 [B, Hq, 128] -> o bf16 [B, Hq, 128].
+
+    Query head h reads kv head h // (Hq / Hkv) (HF repeat_kv), every cached token, softmax in fp32 with sm_scale (default 1/sqrt(128));
+    a sequence of length 0 gives zeros.  `max_seq_len` bounds the sequence lengths; the split over the tokens depends on it (and B,
+    Hq, Hkv) only, so a captured graph stays valid while the sequences grow up to it.  `workspace` (uint8 / any device tensor of at
+    least paged_decode_workspace_bytes(...) bytes) is allocated here when None -- pass one when capturing a graph.
+    """
+    lib = _lib.load()
+    if not (isinstance(q, torch.Tensor) and q.is_cuda and _ok(q, torch.bfloat16, q.get_device())):
+        _check_tensor(q, "q", torch.bfloat16)
+    dev = q.device
+    kind, max_pages, L, Hkv, P = _kv_geometry(kv_data, kv_param, dev.index)
+    B = _page_table(kv_indptr, kv_indices, last_page_len, dev)
+    if q.dim() != 3 or q.size(0) != B or q.size(2) != 128:
+        raise RuntimeError(f"q must be [B = {B}, Hq, 128] bf16")
+    Hq = q.size(1)
+    if Hq % Hkv:
+        raise RuntimeError(f"the {Hq} query heads are not a multiple of the cache's {Hkv} kv heads")
+    layer_idx, max_seq_len = int(layer_idx), int(max_seq_len)
+    if not 0 <= layer_idx < L:
+        raise RuntimeError(f"layer_idx {layer_idx} outside the cache's {L} layers")
+    if max_seq_len < 0:
+        raise RuntimeError("max_seq_len must be >= 0")
+    need = paged_decode_workspace_bytes(B, Hq, Hkv, max_seq_len) if B else 0
+    if need and workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+    if need and (not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or workspace.device != dev
+                 or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need):
+        raise RuntimeError(f"workspace must be a contiguous device tensor of at least {need} bytes on {dev}")
+    o = torch.empty((B, Hq, 128), dtype=torch.bfloat16, device=dev)
+    scale = float(sm_scale) if sm_scale is not None else 128 ** -0.5
+    if not scale > 0:
+        raise ValueError("sm_scale must be positive")
+    with _on_device(dev.index):
+        st = lib.mm_paged_decode(_ptr(q), _ptr(kv_data), _ptr(kv_param) if kv_param is not None else None, kind, max_pages, L, layer_idx,
+                                 Hkv, P, 128, _ptr(kv_indptr), _ptr(kv_indices), _ptr(last_page_len), B, Hq, max_seq_len, scale,
+                                 _ptr(workspace) if need else None, workspace.numel() * workspace.element_size() if need else 0,
+                                 _ptr(o), _stream_ptr(dev))
+    if st:
+        _lib.check(st, "paged_decode")
+    return o
