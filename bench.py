@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MicroMix mgemm hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full] [--details FILE]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run measures the headline figure and nothing else: inputs and operands, W warm-up steps, the settle phase below, the K
+timed steps, the --dump-outputs files if asked for, and the JSON line.  Everything listed under "The line also carries" (and the
+hipGraph replay, `graph_launch_ms_per_step`) is measured only with --full, which also writes the details file (--details,
+default build/bench_details.json).  The headline `value` and `ms_per_step` are the same steps, measured the same way, in both.
 
 Workload (BASELINE.json configs[1]): ONE mixed-MX GEMM, M = N = K = 4096, all-MXFP8 activations
 (p8_num = 4096), weights pre-packed the way QLinearLayer deploys them (MXFP4, "w4" mode:
@@ -16,7 +21,7 @@ the ramp.  So, independent of --warmup, an UNTIMED settle phase of back-to-back 
 `prewarm_s` in the line) runs right before the timed region, and every kernel time quoted below is taken in that
 same regime.
 
-The line also carries
+The line also carries (with --full)
   * `roofline`   : the GEMM kernel's per-launch duration from HIP events attached to each dispatch, against the dense
                    MFMA peak of the operand precision (MI355X_MICROARCH.md: fp8 operands ~5.03 PF, fp6/fp4 ~10.07 PF);
   * `mixed`      : the same for the mixed (p4, p6, p8) splits of SURVEY.md section 8d, each against its per-precision
@@ -30,13 +35,13 @@ The line also carries
                    1400 W cap: its time is set by energy, see DESIGN.md section 4.2);
   * `roofline.zero_operands`: context for that -- the SAME launch on operands whose codes are all zero (same instructions, same
                    traffic, multipliers barely switching): kernel time, power and clock when the cap does not bite.  Never `value`.
-`value` is always the K stream launches' figure (the same launch mode `roofline.kernel_us` is measured in); the hipGraph replay of
-the same K launches is reported beside it as `graph_launch_ms_per_step`.
+`value` is always the K stream launches' figure (the same launch mode `roofline.kernel_us` is measured in); with --full the hipGraph
+replay of the same K launches is reported beside it as `graph_launch_ms_per_step`.
 With --gpus N > 1 (one process per GPU, RCCL): the north-star tensor-parallel path -- each rank holds a 128-aligned K-shard of
 every reordered segment (weights AND activation columns), computes a partial [M, N] product and the partials are summed with
 one RCCL all-reduce on the bf16 output.  Total work is fixed ("scaling": "strong"); `value` is 2*M*N*K*steps / max-over-ranks
-time; `tp` splits a step into `gemm_us` and `allreduce_us` (events on the compute stream) and lists the payload and the
-per-rank roofline; `tp_mlp` times the Megatron pairing (gate/up column-parallel -> down row-parallel, ONE all-reduce per MLP).
+time.  With --full, `tp` splits a step into `gemm_us` and `allreduce_us` (events on the compute stream) and lists the payload and
+the per-rank roofline, and `tp_mlp` times the Megatron pairing (gate/up column-parallel -> down row-parallel, ONE all-reduce per MLP).
 """
 from __future__ import annotations
 
@@ -526,20 +531,35 @@ def dump_outputs(directory, out):
     return sorted(arrays)
 
 
-def main():
+DETAILS_DEFAULT = os.path.join("build", "bench_details.json")     # relative to the repository root; --full only
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200, help="timed steps (one GEMM launch each); ms_per_step is their mean")
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the last step's output to DIR/*.npy (see dump_outputs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline GEMM only (profiling runs)")
-    ap.add_argument("--details", default=os.path.join("gpurun_out", "bench_details.json"),
-                    help="file for the full result (every note / kernel name / per-case dictionary); the printed line carries numbers only")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: hipGraph replay, roofline, mixed splits, small-M and "
+                         "decode launches, quantizers, QLinearLayer and Llama layer, power, CPU baseline (with --gpus N > 1: the "
+                         "GEMM / all-reduce split, row-parallel and MLP figures)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: the headline GEMM and its roofline only (profiling runs)")
+    ap.add_argument("--details", default=None,
+                    help=f"file for the full result (every note / kernel name / per-case dictionary); the printed line carries numbers "
+                         f"only.  Default: none for a plain run, {DETAILS_DEFAULT} with --full")
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.details is None and args.full:
+        args.details = DETAILS_DEFAULT
+    return args
+
+
+def main():
+    args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args, sys.argv[1:]))
 
@@ -634,11 +654,11 @@ def main():
     for _ in range(args.warmup):
         step()
     barrier()
-    # The same K steps are also captured as ONE hipGraph holding K GEMM launches (single GPU) and replayed after the timed
+    # With --full the same K steps are also captured as ONE hipGraph holding K GEMM launches (single GPU) and replayed after the timed
     # region as an auxiliary figure (consecutive launches from a stream leave a ~4 us gap at every kernel boundary, a graph about
     # half of that on most boxes: tools/graph_gap.py).  Capture happens here, outside any timed region; MICROMIX_BENCH_GRAPH=0 skips it.
     graph = None
-    if world == 1 and os.environ.get("MICROMIX_BENCH_GRAPH", "1") != "0":
+    if args.full and world == 1 and os.environ.get("MICROMIX_BENCH_GRAPH", "1") != "0":
         try:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
@@ -654,7 +674,7 @@ def main():
             print(f"[bench] hipGraph capture failed ({e}); timing stream launches", file=sys.stderr)
             graph = None
     power = {}
-    sampler = sample_power(power) if rank == 0 and world == 1 else None
+    sampler = sample_power(power) if args.full and rank == 0 and world == 1 else None
     prewarm_s = settle(step)
     if sampler is not None:
         sampler.join(timeout=25)
@@ -706,7 +726,7 @@ def main():
     if power:
         result["power"] = dict(power, sampled="rocm-smi during the settle phase (back-to-back GEMM launches)")
 
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         traffic = load_traffic()
         kus = kernel_us(step, args.steps)
         achieved = flop / (kus * 1e-6) / 1e12
@@ -746,7 +766,7 @@ def main():
                 "power": pz, "note": "same launch, all-zero operand codes: not power-capped (context for `power` / `frac`; never `value`)"}
             del az, bz
             settle(step, 0.5)      # back to the bench data's clock / power state for what follows
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         # ---- mixed splits against their per-precision rooflines (t* = sum_seg 2*M*N*K_seg / peak(seg)) ----
         mixed = {}
         for name, mm_, nn_, kk_, split, *wm in MIXED:
@@ -1050,7 +1070,7 @@ def main():
         result["llama_layer"] = llama_layer(dev, lib, mixedgemm, x, args.steps)
         if not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(x_cpu, w_cpu, idx_cpu)
-    if world > 1:
+    if args.full and world > 1:
         # ---- GEMM and all-reduce separately (events on the compute stream; the all-reduce is waited for on that stream) ----
         ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.steps)]
         for e0, e1, e2 in ev:
@@ -1121,14 +1141,15 @@ def main():
     if rank == 0:
         result.update(extra)
         details = None
-        try:
-            dpath = args.details if os.path.isabs(args.details) else os.path.join(ROOT, args.details)
-            os.makedirs(os.path.dirname(dpath), exist_ok=True)
-            with open(dpath, "w") as f:
-                json.dump(result, f, indent=1)
-            details = args.details
-        except OSError as e:
-            print(f"[bench] could not write the details file ({e})", file=sys.stderr)
+        if args.details:
+            try:
+                dpath = args.details if os.path.isabs(args.details) else os.path.join(ROOT, args.details)
+                os.makedirs(os.path.dirname(dpath), exist_ok=True)
+                with open(dpath, "w") as f:
+                    json.dump(result, f, indent=1)
+                details = args.details
+            except OSError as e:
+                print(f"[bench] could not write the details file ({e})", file=sys.stderr)
         if last_out is not None:
             names = dump_outputs(args.dump_outputs, last_out)
             print(f"[bench] wrote {', '.join(n + '.npy' for n in names)} to {args.dump_outputs}", file=sys.stderr)

@@ -139,6 +139,16 @@ def test_dump_outputs_writes_a_fixed_float_sample(tmp_path):
     assert not np.array_equal(got["out_row_sum"], np.load(tmp_path / "c" / "out_row_sum.npy"))
 
 
+def test_plain_run_is_lean_and_full_is_opt_in():
+    """without --full a run measures the headline steps only and writes no details file; --full brings both back"""
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not plain.full and plain.details is None and plain.dump_outputs is None
+    full = bench.parse_args(["--full", "--steps", "20"])
+    assert full.full and full.details == bench.DETAILS_DEFAULT and not full.no_extras and not full.no_cpu_baseline
+    assert bench.parse_args(["--full", "--details", "elsewhere.json"]).details == "elsewhere.json"
+    assert bench.parse_args(["--details", "d.json"]).details == "d.json"
+
+
 def test_steps_below_one_are_refused():
     import subprocess
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300, cwd=ROOT)

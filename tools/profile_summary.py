@@ -5,7 +5,7 @@ root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 prof = os.path.join(root, "gpurun_out", f"profiles_{tag}")   # merged back by gpurun; copy into profiles/ afterwards
 os.makedirs(prof, exist_ok=True)
 lines = []
-CMD = "python3 bench.py --steps 20 --warmup 5"
+CMD = "python3 bench.py --full --steps 20 --warmup 5"
 for f in glob.glob(out + "/trace/*/*_kernel_stats.csv"):
     rows = list(csv.DictReader(open(f)))
     with open(os.path.join(prof, f"{tag}_bench_kernel_stats.csv"), "w") as g:
