@@ -331,6 +331,32 @@ int mm_paged_decode(const void *q_bf16, const void *kv_data, const void *kv_para
                     const int32_t *last_page_len, int batch, int num_qo_heads, int max_seq_len, float sm_scale, void *workspace,
                     size_t workspace_bytes, void *o_bf16, mm_stream_t stream);
 
+/*
+ * Causal multi-token attention over the paged KV cache (version >= 610): prompt ingestion, chunked prefill, a new turn over a cached
+ * conversation, speculative verification.  Cache layout, page table, head rules (head_dim 128, Hq = g * Hkv with g <= 16, query head h
+ * reads kv head h / g) and sm_scale as mm_paged_decode.
+ * mm_paged_prefill: q bf16 [T, Hq, 128]; qo_indptr [B + 1] (int32, device) splits the T query tokens among the sequences, the same
+ *   array and convention as mm_kv_append's append_indptr (qo_indptr[B] = T).  The mask is causal and aligned bottom-right (FlashInfer
+ *   prefill.cuh:192,207): sequence b holds len_b tokens (from the page table, which already counts the new ones) and
+ *   n_b = qo_indptr[b + 1] - qo_indptr[b]; its j-th query token sits at position p = len_b - n_b + j and attends cache positions
+ *   0..p.  A query with p < 0 (a table that does not count the tokens) gives o = 0, and so does a length-0 sequence.  Softmax in fp32;
+ *   o bf16 [T, Hq, 128], rounded once.  With n_b = 1 for every b it computes what mm_paged_decode computes (within rounding).
+ *   Int4 cache: p.V runs on bf16 MFMA operands, bf16(p * scale_v) times the codes, so |o - exact| stays within 2 bf16 ulps plus
+ *   2^-8 max|V| of the attended tokens.
+ *   The grid and the workspace depend only on (T, B, Hq, Hkv, max_seq_len), so one captured graph of mm_kv_append + mm_paged_prefill
+ *   stays valid across later steps with the same T while the sequences stay within max_seq_len (longer ones are still attended in
+ *   full).  With more than one kv chunk the partials go to `workspace` (mm_paged_prefill_workspace_bytes, 16-byte aligned, not shared
+ *   with a concurrent call) and a second launch merges them; workspace_bytes() == 0 means one launch and no workspace.
+ * Null pointers, bad sizes, Hq not a multiple of Hkv, negative T or max_seq_len, or a missing, small or misaligned workspace:
+ * MM_ERR_BAD_ARG; head_dim != 128 or g > 16: MM_ERR_UNSUPPORTED; T = 0 or B = 0: MM_OK; all without device work.
+ */
+size_t mm_paged_prefill_workspace_bytes(int num_tokens, int batch, int num_qo_heads, int num_kv_heads, int max_seq_len);
+int mm_paged_prefill(const void *q_bf16, const int32_t *qo_indptr, int num_tokens, const void *kv_data, const void *kv_param,
+                     int kv_dtype, int max_pages, int num_layers, int layer, int num_kv_heads, int page_size, int head_dim,
+                     const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_len, int batch,
+                     int num_qo_heads, int max_seq_len, float sm_scale, void *workspace, size_t workspace_bytes,
+                     void *o_bf16, mm_stream_t stream);
+
 /* Which kernel(s) and how many workgroups mm_matmul / mm_matmul_ws launch for this problem on the CURRENT device (the same
  * decision code as the launcher; workspace_bytes = 0 means "no workspace", i.e. never split-K).  Returns a string in a
  * thread-local buffer, valid until the calling thread's next call.  Used by bench.py to name the kernel it timed. */

@@ -29,7 +29,7 @@ static bool split_ok(int K, int KN, int KS, int KO) {
 
 extern "C" {
 
-int mm_version(void) { return 600; /* 0.6.0: + mm_kv_append, mm_paged_decode(_workspace_bytes), enum mm_kv_dtype (paged int4 / bf16 KV cache); 0.5.1: + mm_rmsnorm_gate_up_activate_decode(_supported), mm_gate_up_activate_decode_supported; mm_gate_up_activate(_decode) one launch at decode sizes; 0.5.0: + the *_supported_w queries (weight mode); 0.4.0: + mm_rmsnorm_qlinear_decode(_supported) (0.3.0: + mm_gate_up_activate(_decode), mm_down_activate_decode, mm_matmul_ws_reset; 0.2.0: diagnostics moved to libmicromix_diag.so, + mm_test_function) */ }
+int mm_version(void) { return 610; /* 0.6.1: + mm_paged_prefill(_workspace_bytes) (causal multi-token attention over the paged KV cache); 0.6.0: + mm_kv_append, mm_paged_decode(_workspace_bytes), enum mm_kv_dtype (paged int4 / bf16 KV cache); 0.5.1: + mm_rmsnorm_gate_up_activate_decode(_supported), mm_gate_up_activate_decode_supported; mm_gate_up_activate(_decode) one launch at decode sizes; 0.5.0: + the *_supported_w queries (weight mode); 0.4.0: + mm_rmsnorm_qlinear_decode(_supported) (0.3.0: + mm_gate_up_activate(_decode), mm_down_activate_decode, mm_matmul_ws_reset; 0.2.0: diagnostics moved to libmicromix_diag.so, + mm_test_function) */ }
 
 const char *mm_test_function(void) { return "Hello from test_function!"; /* bindings.cpp:700 */ }
 
@@ -627,6 +627,32 @@ int mm_paged_decode(const void *q_bf16, const void *kv_data, const void *kv_para
                                            num_qo_heads, num_kv_heads, max_pages, num_layers, layer, page_size, max_seq_len,
                                            sm_scale > 0.0f ? sm_scale : 0.08838834764831845f, workspace, o_bf16, (hipStream_t)stream);
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_paged_decode");
+}
+
+size_t mm_paged_prefill_workspace_bytes(int num_tokens, int batch, int num_qo_heads, int num_kv_heads, int max_seq_len) {
+    if (num_tokens <= 0 || batch <= 0 || batch > 65535 || num_kv_heads <= 0 || num_kv_heads > 65535 || num_qo_heads <= 0 ||
+        max_seq_len < 0 || num_qo_heads % num_kv_heads || num_qo_heads / num_kv_heads > 16)
+        return 0;
+    return mm::kv_prefill_workspace_bytes(num_tokens, batch, num_qo_heads, num_kv_heads, max_seq_len);
+}
+
+int mm_paged_prefill(const void *q_bf16, const int32_t *qo_indptr, int num_tokens, const void *kv_data, const void *kv_param, int kv_dtype,
+                     int max_pages, int num_layers, int layer, int num_kv_heads, int page_size, int head_dim, const int32_t *kv_indptr,
+                     const int32_t *kv_indices, const int32_t *last_page_len, int batch, int num_qo_heads, int max_seq_len, float sm_scale,
+                     void *workspace, size_t workspace_bytes, void *o_bf16, mm_stream_t stream) {
+    if (int st = kv_geometry(kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size, head_dim, batch)) return st;
+    if (num_qo_heads <= 0 || num_qo_heads % num_kv_heads || max_seq_len < 0 || num_tokens < 0) return MM_ERR_BAD_ARG;
+    if (num_qo_heads / num_kv_heads > 16) return MM_ERR_UNSUPPORTED;
+    if (num_tokens == 0 || batch == 0) return MM_OK;
+    if (!q_bf16 || !qo_indptr || !kv_data || (kv_dtype == MM_KV_INT4 && !kv_param) || !kv_indptr || !kv_indices || !last_page_len || !o_bf16)
+        return MM_ERR_BAD_ARG;
+    const size_t need = mm_paged_prefill_workspace_bytes(num_tokens, batch, num_qo_heads, num_kv_heads, max_seq_len);
+    if (need && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15))) return MM_ERR_BAD_ARG;
+    hipError_t e = mm::launch_paged_prefill(q_bf16, qo_indptr, num_tokens, kv_data, kv_param, kv_dtype == MM_KV_INT4, kv_indptr, kv_indices,
+                                            last_page_len, batch, num_qo_heads, num_kv_heads, max_pages, num_layers, layer, page_size,
+                                            max_seq_len, sm_scale > 0.0f ? sm_scale : 0.08838834764831845f, workspace, o_bf16,
+                                            (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_paged_prefill");
 }
 
 int mm_diag_set_kernel_events(void *start_event, void *stop_event) {

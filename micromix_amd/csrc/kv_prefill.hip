@@ -1,0 +1,447 @@
+// Causal multi-token attention over the paged int4 / bf16 KV cache (include/micromix_hip.h, mm_paged_prefill).  Same cache layout,
+// page table and head rules as mm_paged_decode (kv_cache.hip); the queries q [T, Hq, 128] are split among the sequences by qo_indptr
+// (the append_indptr of mm_kv_append), and the mask is causal, aligned bottom-right: query j of sequence b sits at position
+// p = len_b - n_b + j and attends cache positions 0..p.
+//
+// One workgroup (4 waves) per (query tile of one sequence, kv head, kv chunk).  Its 64 MFMA rows are (token, head) pairs over the g
+// query heads of the kv head: BQ = 64 / g tokens x g heads (row r = token r / g, head r % g), 16 rows per wave, so each K/V byte is
+// staged once per query tile.  Per 64-token kv tile:
+//   staging  all 256 threads load the tile's K rows into LDS as stored, and V transposed ([dim][token], bf16: the int4 codes as exact
+//            bf16 integers), plus per-token (scale, zero) of K and V; the next tile's global loads are issued before this tile's math
+//   scores   S^T = K q^T, v_mfma_f32_16x16x32_bf16 with A = K (int4: 16 + code, exact), B = q (kept in registers), so a lane holds 16
+//            scores of ONE query row; int4: s = sk (q.(16 + c)) - (16 sk + zk) sum(q)
+//   softmax  online, fp32, log2 domain; the row max over the 4 lanes of a row; the causal mask only on tiles that cross the diagonal
+//   p.V      O^T += V^T P^T on the MFMA: B = bf16(p * s_v) (int4) or bf16(p) (bf16 cache) straight from the score registers, A = the
+//            transposed V image; int4 subtracts sum(p z_v) once at the end in fp32
+// Split-KV: the kv range is cut into chunks chosen from host values only (kv_prefill_split); with more than one chunk each workgroup
+// writes (m, l, o) partials and a merge launch combines them.  The tile -> (sequence, tile of it) map needs no host knowledge of
+// qo_indptr: sequence b owns tiles [qo_indptr[b] / BQ + b, qo_indptr[b + 1] / BQ + b + 1), which hold its ceil(n_b / BQ) tiles;
+// the surplus workgroups exit.
+#include <hip/hip_runtime.h>
+#include <hip/hip_fp16.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "mx_kernels.h"
+
+namespace {
+
+typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
+typedef unsigned v4u __attribute__((ext_vector_type(4)));
+typedef unsigned v2u __attribute__((ext_vector_type(2)));
+typedef float v4f __attribute__((ext_vector_type(4)));
+
+constexpr int HD = 128;              // head_dim
+constexpr int ROWS = 64;             // MFMA rows (token, head) per workgroup
+constexpr int KT = 64;               // kv tokens per tile
+constexpr int NT = 256;              // threads per workgroup
+constexpr int KSTR4 = 64 + 16;       // LDS row stride of an int4 K row (bytes)
+constexpr int KSTR16 = 256 + 16;     // LDS row stride of a bf16 K row (bytes)
+constexpr int VSTR = 2 * KT + 8;     // LDS row stride of the transposed V image (bytes)
+
+__device__ inline float bf16f(uint32_t bits16) { return __uint_as_float(bits16 << 16); }
+
+__device__ inline uint16_t f2bf_rne(float f) {    // finite inputs
+    const uint32_t u = __float_as_uint(f);
+    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+
+__device__ inline uint32_t pack_bf(float lo, float hi) { return (uint32_t)f2bf_rne(lo) | ((uint32_t)f2bf_rne(hi) << 16); }
+
+__device__ inline int seq_len(const int *kv_indptr, const int *last_page_len, int b, int P) {
+    const int np = kv_indptr[b + 1] - kv_indptr[b];
+    return np > 0 ? (np - 1) * P + min(max(last_page_len[b], 0), P) : 0;    // clamped: a bad entry never reads past the page list
+}
+
+// row index (in rows of one token-head) of K (kv = 0) or V (kv = 1) of `page`, `slot`
+__device__ inline int64_t kv_row(int page, int L, int layer, int kv, int Hkv, int h, int P, int slot) {
+    return ((((int64_t)page * L + layer) * 2 + kv) * Hkv + h) * P + slot;
+}
+
+// 8 int4 codes (one dword, element 2j in the low nibble of byte j) -> 8 bf16 values 16 + code (exact), MFMA operand order
+__device__ inline v8bf codes_to_bf16(uint32_t w) {
+    const uint32_t lo = w & 0x0f0f0f0fu, hi = (w >> 4) & 0x0f0f0f0fu;
+    v4u r;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        const uint32_t sel = 0x0c000c00u | ((4u + m) << 16) | (uint32_t)m;  // byte0 = lo.byte m, byte2 = hi.byte m, bytes 1, 3 = 0
+        r[m] = (__builtin_amdgcn_perm(hi, lo, sel) << 3) | 0x41804180u;    // bf16 0x4180 | c << 3 = 16 + c
+    }
+    return __builtin_bit_cast(v8bf, r);
+}
+
+struct PrefillArgs {
+    const uint16_t *q;
+    const int *qo_indptr;
+    const uint8_t *kv_data;
+    const __half *kv_param;
+    const int *kv_indptr, *kv_indices, *last_page_len;
+    float *ws;                 // partials: o [tiles, Hkv, nc, 64, 128], then (m, l) [tiles, Hkv, nc, 64, 2]
+    uint16_t *o;
+    int T, max_pages, L, layer, Hkv, P, B, Hq, g, bq, tiles, nc, chunk;
+    float scale_log2;          // sm_scale * log2(e)
+};
+
+// (sequence, tile of it, its token count) of workgroup tile index i; false for a surplus tile
+__device__ inline bool tile_of(const PrefillArgs &a, int i, int &b, int &j, int &q0, int &n) {
+    int lo = 0, hi = a.B;                         // the largest b with start(b) = qo_indptr[b] / bq + b <= i
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (min(max(a.qo_indptr[mid], 0), a.T) / a.bq + mid <= i) lo = mid; else hi = mid;
+    }
+    b = lo;
+    q0 = min(max(a.qo_indptr[b], 0), a.T);
+    n = min(max(a.qo_indptr[b + 1], 0), a.T) - q0;
+    j = i - (q0 / a.bq + b);
+    return n > 0 && j * a.bq < n;
+}
+
+template <bool INT4>
+__global__ __launch_bounds__(NT) void paged_prefill_kernel(const PrefillArgs a) {
+    constexpr int KSTR = INT4 ? KSTR4 : KSTR16;
+    __shared__ __attribute__((aligned(16))) uint8_t s_k[KT * KSTR];
+    __shared__ __attribute__((aligned(16))) uint8_t s_vt[HD * VSTR];
+    __shared__ __attribute__((aligned(16))) float s_par[5][KT];      // per token: K scale, K offset, K bias (0 / -inf), V scale, V zero
+    float *s_ks = s_par[0], *s_kc = s_par[1], *s_kb = s_par[2], *s_vs = s_par[3], *s_vz = s_par[4];
+
+    const int tile = a.tiles - 1 - (int)blockIdx.x;      // the last tiles of a sequence carry the most work: they start first
+    const int kvh = blockIdx.y, chunk = blockIdx.z;
+    int b, j, q0, n;
+    if (!tile_of(a, tile, b, j, q0, n)) return;
+    const int tid = threadIdx.x, wave = tid >> 6, l = tid & 63, c = l & 15, kq = l >> 4;
+    const int g = a.g, P = a.P;
+    const int len = seq_len(a.kv_indptr, a.last_page_len, b, P);
+    const int *pages = a.kv_indices + a.kv_indptr[b];
+    const int ntok = min(a.bq, n - j * a.bq);             // query tokens of this tile
+    const int pos0 = len - n + j * a.bq;                   // position of its first token
+    const int pmax = pos0 + ntok - 1;                      // the last position any row attends
+    const int t0 = chunk * a.chunk;
+    const int t1 = chunk == a.nc - 1 ? len : min(len, t0 + a.chunk);   // the last chunk runs to the end, whatever max_seq_len said
+    const int kend = min(t1, pmax + 1);
+
+    // ---- this lane's query row: (token r / g, head r % g); q as the MFMA B operand, dims 32 kq + 8 s + e in step s
+    const int row = 16 * wave + c, rt = row / g, rh = row - rt * g;
+    const bool rvalid = rt < ntok;
+    const int prow = rvalid ? pos0 + rt : -1;             // -1: attends nothing (also a query whose position is negative)
+    const int64_t qrow = (int64_t)(q0 + j * a.bq + rt) * a.Hq + (int64_t)kvh * g + rh;
+    v8bf qb[4];
+    float sq = 0.0f;
+    {
+        const v4u *qp = (const v4u *)(a.q + (rvalid ? qrow : 0) * HD + 32 * kq);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const v4u w = rvalid ? qp[s] : v4u{0, 0, 0, 0};
+            qb[s] = __builtin_bit_cast(v8bf, w);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) sq += bf16f(w[e] & 0xffffu) + bf16f(w[e] >> 16);
+        }
+    }
+    sq += __shfl_xor(sq, 16);
+    sq += __shfl_xor(sq, 32);
+    // rows of this wave: first / last position (wave-uniform)
+    const int wr0 = 16 * wave, wt0 = wr0 / g, wt1 = min((wr0 + 15) / g, ntok - 1);
+    const bool wactive = wt0 < ntok;
+    const int wpmin = pos0 + wt0, wpmax = pos0 + wt1;
+
+    float m = -INFINITY, lsum = 0.0f, pz = 0.0f;
+    v4f o[8];
+#pragma unroll
+    for (int dt = 0; dt < 8; ++dt) o[dt] = v4f{0.0f, 0.0f, 0.0f, 0.0f};
+
+    // ---- staging: thread (tg, dg) owns tokens 4 tg .. 4 tg + 3 of the tile: V dims 8 dg .. 8 dg + 7 of each, the K bytes of token
+    // 4 tg + (dg >> 2) part dg & 3, and (dg == 0) the K params / (dg == 1) the V params of its four tokens
+    const int tg = tid & 15, dg = tid >> 4, uk = dg >> 2, kpart = dg & 3;
+    v4u kreg[INT4 ? 1 : 4];
+    v4u vreg[4];                // int4: .x holds the token's 8 codes; bf16: the 8 values
+    uint32_t preg[4];
+    bool okreg[4];
+    auto load = [&](int kt) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int t = kt + 4 * tg + u;
+            const int page = t < len ? pages[t / P] : -1;
+            const bool ok = page >= 0 && page < a.max_pages;
+            okreg[u] = ok;
+            const int64_t rk = ok ? kv_row(page, a.L, a.layer, 0, a.Hkv, kvh, P, t % P) : 0;
+            const int64_t rv = rk + (int64_t)a.Hkv * P;
+            if (INT4) {
+                vreg[u].x = ok ? *(const uint32_t *)(a.kv_data + rv * (HD / 2) + 4 * dg) : 0u;
+                if (u == uk) kreg[0] = ok ? *(const v4u *)(a.kv_data + rk * (HD / 2) + 16 * kpart) : v4u{0, 0, 0, 0};
+                if (dg < 2) preg[u] = ok ? *(const uint32_t *)(a.kv_param + (dg ? rv : rk) * 2) : 0u;
+            } else {
+                vreg[u] = ok ? *(const v4u *)(a.kv_data + rv * (HD * 2) + 16 * dg) : v4u{0, 0, 0, 0};
+                if (u == uk) {
+#pragma unroll
+                    for (int s = 0; s < 4; ++s)
+                        kreg[s] = ok ? *(const v4u *)(a.kv_data + rk * (HD * 2) + 64 * kpart + 16 * s) : v4u{0, 0, 0, 0};
+                }
+            }
+        }
+    };
+    auto store = [&]() {
+        if (INT4) {
+            *(v4u *)(s_k + (4 * tg + uk) * KSTR + 16 * kpart) = kreg[0];
+            float f[4][8];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const uint32_t w = vreg[u].x, lo = w & 0x0f0f0f0fu, hi = (w >> 4) & 0x0f0f0f0fu;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    f[u][2 * e] = (float)((lo >> (8 * e)) & 0xffu);
+                    f[u][2 * e + 1] = (float)((hi >> (8 * e)) & 0xffu);
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                v2u w;
+                w.x = __builtin_amdgcn_perm(__float_as_uint(f[1][e]), __float_as_uint(f[0][e]), 0x07060302u);   // exact: small integers
+                w.y = __builtin_amdgcn_perm(__float_as_uint(f[3][e]), __float_as_uint(f[2][e]), 0x07060302u);
+                *(v2u *)(s_vt + (8 * dg + e) * VSTR + 8 * tg) = w;
+            }
+            if (dg < 2) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const float s = __half2float(__ushort_as_half((unsigned short)(preg[u] & 0xffffu)));
+                    const float z = __half2float(__ushort_as_half((unsigned short)(preg[u] >> 16)));
+                    const int t = 4 * tg + u;
+                    if (dg == 0) {
+                        s_ks[t] = okreg[u] ? s * a.scale_log2 : 0.0f;
+                        s_kc[t] = okreg[u] ? (16.0f * s + z) * a.scale_log2 : 0.0f;
+                        s_kb[t] = okreg[u] ? 0.0f : -INFINITY;
+                    } else {
+                        s_vs[t] = okreg[u] ? s : 0.0f;
+                        s_vz[t] = okreg[u] ? z : 0.0f;
+                    }
+                }
+            }
+        } else {
+#pragma unroll
+            for (int s = 0; s < 4; ++s) *(v4u *)(s_k + (4 * tg + uk) * KSTR + 64 * kpart + 16 * s) = kreg[s];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int sh = 16 * (e & 1);
+                v2u w;
+                w.x = ((vreg[0][e >> 1] >> sh) & 0xffffu) | (((vreg[1][e >> 1] >> sh) & 0xffffu) << 16);
+                w.y = ((vreg[2][e >> 1] >> sh) & 0xffffu) | (((vreg[3][e >> 1] >> sh) & 0xffffu) << 16);
+                *(v2u *)(s_vt + (8 * dg + e) * VSTR + 8 * tg) = w;
+            }
+            if (dg == 0) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) s_kb[4 * tg + u] = okreg[u] ? 0.0f : -INFINITY;
+            }
+        }
+    };
+
+    if (t0 < kend) load(t0);
+    for (int kt = t0; kt < kend; kt += KT) {
+        __syncthreads();                                   // the previous tile's LDS reads are done
+        store();
+        __syncthreads();
+        if (kt + KT < kend) load(kt + KT);                 // in flight during this tile's math
+        if (!wactive || kt > wpmax) continue;              // every row of this wave is masked on this tile
+
+        // ---- scores S^T: lane (c, kq) holds rows' scores of tokens kt + 16 blk + 4 kq + r for its row
+        float sc[4][4];
+#pragma unroll
+        for (int blk = 0; blk < 4; ++blk) {
+            v4f d = {0.0f, 0.0f, 0.0f, 0.0f};
+            const int tl = 16 * blk + 4 * kq;
+            if (INT4) {
+                const v4u kc = *(const v4u *)(s_k + (16 * blk + c) * KSTR + 16 * kq);
+#pragma unroll
+                for (int s = 0; s < 4; ++s) d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(codes_to_bf16(kc[s]), qb[s], d, 0, 0, 0);
+                const v4f ks = *(const v4f *)(s_ks + tl), kcs = *(const v4f *)(s_kc + tl), kb = *(const v4f *)(s_kb + tl);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) sc[blk][r] = ks[r] * d[r] - kcs[r] * sq + kb[r];
+            } else {
+                const v4u *kr = (const v4u *)(s_k + (16 * blk + c) * KSTR + 64 * kq);
+#pragma unroll
+                for (int s = 0; s < 4; ++s) d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8bf, kr[s]), qb[s], d, 0, 0, 0);
+                const v4f kb = *(const v4f *)(s_kb + tl);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) sc[blk][r] = d[r] * a.scale_log2 + kb[r];
+            }
+        }
+        if (kt + KT - 1 > wpmin) {                         // the tile crosses the diagonal of some row of this wave
+#pragma unroll
+            for (int blk = 0; blk < 4; ++blk)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (kt + 16 * blk + 4 * kq + r > prow) sc[blk][r] = -INFINITY;
+        }
+        // ---- online softmax (log2 domain)
+        float mt = -INFINITY;
+#pragma unroll
+        for (int blk = 0; blk < 4; ++blk)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) mt = fmaxf(mt, sc[blk][r]);
+        mt = fmaxf(mt, __shfl_xor(mt, 16));
+        mt = fmaxf(mt, __shfl_xor(mt, 32));
+        const float mn = fmaxf(m, mt), mb = mn == -INFINITY ? 0.0f : mn, alpha = exp2f(m - mb);
+        m = mn;
+        float p[4][4], ps = 0.0f;
+#pragma unroll
+        for (int blk = 0; blk < 4; ++blk)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                p[blk][r] = exp2f(sc[blk][r] - mb);
+                ps += p[blk][r];
+            }
+        lsum = lsum * alpha + ps;
+#pragma unroll
+        for (int dt = 0; dt < 8; ++dt) o[dt] *= alpha;
+        // ---- p.V: k step ks covers tokens 32 ks + {4 kq + e, 16 + 4 kq + e}, e = 0..3
+        if (INT4) pz *= alpha;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            v4u pb;
+            if (INT4) {
+                const v4f vs0 = *(const v4f *)(s_vs + 32 * ks + 4 * kq), vs1 = *(const v4f *)(s_vs + 32 * ks + 16 + 4 * kq);
+                const v4f vz0 = *(const v4f *)(s_vz + 32 * ks + 4 * kq), vz1 = *(const v4f *)(s_vz + 32 * ks + 16 + 4 * kq);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) pz += p[2 * ks][r] * vz0[r] + p[2 * ks + 1][r] * vz1[r];
+                pb.x = pack_bf(p[2 * ks][0] * vs0[0], p[2 * ks][1] * vs0[1]);
+                pb.y = pack_bf(p[2 * ks][2] * vs0[2], p[2 * ks][3] * vs0[3]);
+                pb.z = pack_bf(p[2 * ks + 1][0] * vs1[0], p[2 * ks + 1][1] * vs1[1]);
+                pb.w = pack_bf(p[2 * ks + 1][2] * vs1[2], p[2 * ks + 1][3] * vs1[3]);
+            } else {
+                pb.x = pack_bf(p[2 * ks][0], p[2 * ks][1]);
+                pb.y = pack_bf(p[2 * ks][2], p[2 * ks][3]);
+                pb.z = pack_bf(p[2 * ks + 1][0], p[2 * ks + 1][1]);
+                pb.w = pack_bf(p[2 * ks + 1][2], p[2 * ks + 1][3]);
+            }
+            const v8bf pbf = __builtin_bit_cast(v8bf, pb);
+#pragma unroll
+            for (int dt = 0; dt < 8; ++dt) {
+                const uint8_t *vr = s_vt + (16 * dt + c) * VSTR + 2 * (32 * ks + 4 * kq);
+                v4u va;
+                const v2u a0 = *(const v2u *)vr, a1 = *(const v2u *)(vr + 32);
+                va.x = a0.x; va.y = a0.y; va.z = a1.x; va.w = a1.y;
+                o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8bf, va), pbf, o[dt], 0, 0, 0);
+            }
+        }
+    }
+
+    // ---- row totals: l and sum(p z) over the 4 lanes of a row; o^T lane (c, kq) holds row c, dims 16 dt + 4 kq + r
+    lsum += __shfl_xor(lsum, 16);
+    lsum += __shfl_xor(lsum, 32);
+    if (INT4) {
+        pz += __shfl_xor(pz, 16);
+        pz += __shfl_xor(pz, 32);
+    }
+    if (!rvalid) return;
+    if (a.nc == 1) {
+        const float inv = lsum > 0.0f ? 1.0f / lsum : 0.0f;
+        uint16_t *orow = a.o + qrow * HD + 4 * kq;
+#pragma unroll
+        for (int dt = 0; dt < 8; ++dt) {
+            v2u w;
+            w.x = pack_bf((o[dt][0] - pz) * inv, (o[dt][1] - pz) * inv);
+            w.y = pack_bf((o[dt][2] - pz) * inv, (o[dt][3] - pz) * inv);
+            *(v2u *)(orow + 16 * dt) = w;
+        }
+    } else {
+        const int64_t part = (((int64_t)tile * a.Hkv + kvh) * a.nc + chunk) * ROWS + row;
+        float *op = a.ws + part * HD + 4 * kq;
+#pragma unroll
+        for (int dt = 0; dt < 8; ++dt) *(v4f *)(op + 16 * dt) = o[dt] - pz;
+        if (kq == 0) *(float2 *)(a.ws + (int64_t)a.tiles * a.Hkv * a.nc * ROWS * HD + part * 2) = make_float2(m, lsum);
+    }
+}
+
+// combines the nc chunk partials of the rows of one (tile, kv head); a chunk without attended tokens has m = -inf and l = 0
+__global__ __launch_bounds__(NT) void paged_prefill_merge_kernel(const PrefillArgs a) {
+    const int tile = blockIdx.x, kvh = blockIdx.y;
+    int b, j, q0, n;
+    if (!tile_of(a, tile, b, j, q0, n)) return;
+    const int rows = min(a.bq, n - j * a.bq) * a.g;
+    const int64_t first = ((int64_t)tile * a.Hkv + kvh) * a.nc * ROWS;     // part index of chunk 0, row 0; chunk stride ROWS
+    const float *ml = a.ws + (int64_t)a.tiles * a.Hkv * a.nc * ROWS * HD;
+    for (int idx = threadIdx.x; idx < rows * (HD / 4); idx += NT) {
+        const int row = idx / (HD / 4), d = 4 * (idx % (HD / 4));
+        float M = -INFINITY;
+        for (int c = 0; c < a.nc; ++c) M = fmaxf(M, ml[(first + (int64_t)c * ROWS + row) * 2]);
+        float ls = 0.0f;
+        v4f acc = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (M != -INFINITY) {
+            for (int c = 0; c < a.nc; ++c) {
+                const int64_t part = first + (int64_t)c * ROWS + row;
+                const float f = exp2f(ml[part * 2] - M);
+                ls += f * ml[part * 2 + 1];
+                acc += f * *(const v4f *)(a.ws + part * HD + d);
+            }
+        }
+        const float inv = ls > 0.0f ? 1.0f / ls : 0.0f;
+        const int rt = row / a.g, rh = row - rt * a.g;
+        const int64_t qrow = (int64_t)(q0 + j * a.bq + rt) * a.Hq + (int64_t)kvh * a.g + rh;
+        v2u w;
+        w.x = pack_bf(acc[0] * inv, acc[1] * inv);
+        w.y = pack_bf(acc[2] * inv, acc[3] * inv);
+        *(v2u *)(a.o + qrow * HD + d) = w;
+    }
+}
+
+}  // namespace
+
+namespace mm {
+
+void kv_prefill_split(int T, int B, int Hq, int Hkv, int max_seq_len, int *tiles, int *nc, int *chunk) {
+    // tiles: an upper bound on sum ceil(n_b / BQ), BQ = 64 / g query tokens per tile.  Chunks: enough workgroups for four per CU of
+    // the 256 on an MI355X, chunks of at least 256 tokens; host-known values only, so a captured graph stays valid while the
+    // sequences grow up to max_seq_len
+    const int g = Hkv > 0 && Hq >= Hkv ? Hq / Hkv : 1;
+    const int bq = ROWS / (g > 0 && g <= ROWS ? g : 1);
+    *tiles = T / bq + B;
+    const long long work = (long long)(*tiles > 0 ? *tiles : 1) * (Hkv > 0 ? Hkv : 1);
+    const long long want = work >= 1024 ? 1 : (1024 + work - 1) / work;
+    const int most = (max_seq_len + 255) / 256;
+    int n = want < most ? (int)want : most;
+    if (n < 1) n = 1;
+    int cl = (max_seq_len + n - 1) / n;
+    cl = (cl + KT - 1) / KT * KT;
+    if (cl < KT) cl = KT;
+    *chunk = cl;
+    *nc = max_seq_len > 0 ? (max_seq_len + cl - 1) / cl : 1;
+}
+
+size_t kv_prefill_workspace_bytes(int T, int B, int Hq, int Hkv, int max_seq_len) {
+    int tiles, nc, chunk;
+    kv_prefill_split(T, B, Hq, Hkv, max_seq_len, &tiles, &nc, &chunk);
+    return nc > 1 ? (size_t)tiles * Hkv * nc * ROWS * (HD + 2) * sizeof(float) : 0;
+}
+
+hipError_t launch_paged_prefill(const void *q, const int *qo_indptr, int T, const void *kv_data, const void *kv_param, bool int4,
+                                const int *kv_indptr, const int *kv_indices, const int *last_page_len, int B, int Hq, int Hkv, int max_pages,
+                                int L, int layer, int P, int max_seq_len, float sm_scale, void *ws, void *o, hipStream_t stream) {
+    PrefillArgs a;
+    a.q = (const uint16_t *)q;
+    a.qo_indptr = qo_indptr;
+    a.kv_data = (const uint8_t *)kv_data;
+    a.kv_param = (const __half *)kv_param;
+    a.kv_indptr = kv_indptr;
+    a.kv_indices = kv_indices;
+    a.last_page_len = last_page_len;
+    a.ws = (float *)ws;
+    a.o = (uint16_t *)o;
+    a.T = T;
+    a.max_pages = max_pages;
+    a.L = L;
+    a.layer = layer;
+    a.Hkv = Hkv;
+    a.P = P;
+    a.B = B;
+    a.Hq = Hq;
+    a.g = Hq / Hkv;
+    a.bq = ROWS / a.g;
+    kv_prefill_split(T, B, Hq, Hkv, max_seq_len, &a.tiles, &a.nc, &a.chunk);
+    a.scale_log2 = sm_scale * 1.4426950408889634f;
+    const dim3 grid(a.tiles, Hkv, a.nc);
+    if (int4) paged_prefill_kernel<true><<<grid, NT, 0, stream>>>(a);
+    else paged_prefill_kernel<false><<<grid, NT, 0, stream>>>(a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || a.nc == 1) return e;
+    paged_prefill_merge_kernel<<<dim3(a.tiles, Hkv), NT, 0, stream>>>(a);
+    return hipGetLastError();
+}
+
+}  // namespace mm

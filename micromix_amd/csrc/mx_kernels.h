@@ -187,5 +187,11 @@ hipError_t launch_kv_append(void *kv_data, void *kv_param, bool int4, const int 
 hipError_t launch_paged_decode(const void *q, const void *kv_data, const void *kv_param, bool int4, const int *kv_indptr, const int *kv_indices,
                                const int *last_page_len, int B, int Hq, int Hkv, int max_pages, int L, int layer, int P, int max_seq_len,
                                float sm_scale, void *ws, void *o, hipStream_t stream);
+// causal multi-token attention over the paged cache (kv_prefill.hip)
+void kv_prefill_split(int T, int B, int Hq, int Hkv, int max_seq_len, int *tiles, int *nc, int *chunk);   // host-known values only
+size_t kv_prefill_workspace_bytes(int T, int B, int Hq, int Hkv, int max_seq_len);
+hipError_t launch_paged_prefill(const void *q, const int *qo_indptr, int T, const void *kv_data, const void *kv_param, bool int4,
+                                const int *kv_indptr, const int *kv_indices, const int *last_page_len, int B, int Hq, int Hkv, int max_pages,
+                                int L, int layer, int P, int max_seq_len, float sm_scale, void *ws, void *o, hipStream_t stream);
 
 }  // namespace mm

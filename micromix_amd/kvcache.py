@@ -6,7 +6,12 @@
         cache.append(layer, k, v)          # k, v bf16 [T, Hkv, 128], T = the tokens extend() announced
         o = cache.attend(layer, q)         # q bf16 [B, Hq, 128] -> o bf16 [B, Hq, 128]
 
-The page table lives in device tensors of fixed capacity that `extend` rewrites in place, so `append` + `attend` captured once into a
+    cache.extend([300, 512, 5])            # several tokens per sequence: a prompt, a chunk of one, a speculative draft
+    for layer in range(32):
+        cache.append(layer, k, v)          # k, v bf16 [T, Hkv, 128], T = 817
+        o = cache.attend_new(layer, q)     # q bf16 [T, Hq, 128] -> o bf16 [T, Hq, 128], causal over each sequence's cache
+
+The page table lives in device tensors of fixed capacity that `extend` rewrites in place, so `append` + `attend` (or `attend_new`) captured once into a
 hipGraph replay correctly after later `extend` calls, as long as T stays the same and the sequences stay within the captured
 `max_seq_len`.  The allocator is a free list: no eviction, no prefix sharing.
 """
@@ -47,6 +52,7 @@ class PagedKVCache:
         self.append_indptr = torch.zeros((batch + 1,), **i32)
         self.num_new_tokens = 0
         self._workspace = None
+        self._prefill_workspace = None
         self._retired = []
 
     def _upload(self, new):
@@ -105,3 +111,19 @@ class PagedKVCache:
             self._workspace = torch.empty((need,), dtype=torch.uint8, device=self.device)
         return mixedgemm.paged_decode(q, self.kv_data, self.kv_param, self.kv_indptr, self.kv_indices, self.last_page_len, layer, bound,
                                       sm_scale=sm_scale, workspace=self._workspace if need else None)
+
+    def attend_new(self, layer, q, max_seq_len=None, sm_scale=None):
+        """Causal attention of the tokens the last `extend()` announced: q (bf16 [num_new_tokens, Hq, 128], sequence by sequence) over
+        `layer`, each new token attending its sequence's cache up to and including itself.  Call it after `append` of the same layer.
+        max_seq_len as in `attend`."""
+        if q.dim() != 3 or q.size(0) != self.num_new_tokens:
+            raise RuntimeError(f"attend_new expects the {self.num_new_tokens} tokens announced by extend(), got q of shape {tuple(q.shape)}")
+        bound = max(self.seq_lens) if max_seq_len is None else int(max_seq_len)
+        need = mixedgemm.paged_prefill_workspace_bytes(self.num_new_tokens, self.batch, q.size(1), self.num_kv_heads, bound)
+        if need and (self._prefill_workspace is None or self._prefill_workspace.numel() < need):
+            if self._prefill_workspace is not None:
+                self._retired.append(self._prefill_workspace)      # a graph captured earlier may still point at it
+            self._prefill_workspace = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        return mixedgemm.paged_prefill(q, self.kv_data, self.kv_param, self.kv_indptr, self.kv_indices, self.last_page_len,
+                                       self.append_indptr, layer, bound, sm_scale=sm_scale,
+                                       workspace=self._prefill_workspace if need else None)

@@ -19,7 +19,7 @@ Differences from the reference, all deliberate:
     downproj_quantize_w / _w4 (W, KN, KS, KO)         -> (WN, WS, WO, SFWN, SFWS, SFWO)
     rmsnorm_quantize_x(X, W, eps, reorder_index, KN, KS, KO) -> (XN, XS, XO, SFXN, SFXS, SFXO)    (section 8f rank 2)
 The remaining exports of the reference module (FlashInfer KV ops) are outside the hot path; they raise
-NotImplementedError.  The paged KV cache itself is `kv_append` / `paged_decode` below (GQA, bf16 q,
+NotImplementedError.  The paged KV cache itself is `kv_append` / `paged_decode` / `paged_prefill` below (GQA, bf16 q,
 quantizes K/V itself; micromix_amd/kvcache.py wraps them), on the reference's FlashInfer layout.
 """
 from __future__ import annotations
@@ -30,7 +30,7 @@ from . import _lib
 
 __all__ = ["test_function", "matmul", "gate_up_activate", "interleave_gate_up", "reorder_quantize_x", "reorder_quantize_w", "reorder_quantize_w4", "activate_quantize_x",
            "downproj_quantize_w", "downproj_quantize_w4", "rmsnorm_quantize_x", "qlinear_decode", "qlinear_decode_supported", "matmul_grouped", "reorder_quantize_x_grouped",
-           "kv_append", "paged_decode", "paged_decode_workspace_bytes"]
+           "kv_append", "paged_decode", "paged_decode_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes"]
 
 
 def test_function():
@@ -937,4 +937,60 @@ def paged_decode(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, lay
                                  _ptr(o), _stream_ptr(dev))
     if st:
         _lib.check(st, "paged_decode")
+    return o
+
+
+def paged_prefill_workspace_bytes(T, B, Hq, Hkv, max_seq_len):
+    """bytes of fp32 scratch paged_prefill needs for T query tokens over B sequences within max_seq_len (0: one launch, no workspace)"""
+    return int(_lib.load().mm_paged_prefill_workspace_bytes(int(T), int(B), int(Hq), int(Hkv), int(max_seq_len)))
+
+
+def paged_prefill(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, qo_indptr, layer_idx, max_seq_len, sm_scale=None,
+                  workspace=None):
+    """Causal GQA attention of T new query tokens over layer `layer_idx` of a paged cache: q bf16 [T, Hq, 128] -> o bf16 [T, Hq, 128].
+
+    qo_indptr (int32 [B + 1], qo_indptr[B] = T) splits the queries among the sequences, as kv_append's append_indptr does; pass the
+    same array.  The page table already counts the new tokens, and the mask is aligned bottom-right: sequence b's j-th new token sits
+    at position len_b - n_b + j and attends positions 0 .. that one.  Softmax in fp32 with sm_scale (default 1/sqrt(128)).
+    `max_seq_len` bounds the sequence lengths; the grid and the split over the tokens depend on it (and T, B, Hq, Hkv) only, so a
+    captured graph stays valid over later steps with the same T.  `workspace` (any contiguous device tensor of at least
+    paged_prefill_workspace_bytes(...) bytes) is allocated here when None -- pass one when capturing a graph.
+    """
+    lib = _lib.load()
+    if not (isinstance(q, torch.Tensor) and q.is_cuda and _ok(q, torch.bfloat16, q.get_device())):
+        _check_tensor(q, "q", torch.bfloat16)
+    dev = q.device
+    kind, max_pages, L, Hkv, P = _kv_geometry(kv_data, kv_param, dev.index)
+    B = _page_table(kv_indptr, kv_indices, last_page_len, dev)
+    if not _ok(qo_indptr, torch.int32, dev.index):
+        _check_tensor(qo_indptr, "qo_indptr", torch.int32, dev)
+    if qo_indptr.numel() != B + 1:
+        raise RuntimeError("qo_indptr must have B + 1 entries (B = last_page_len.numel())")
+    if q.dim() != 3 or q.size(2) != 128:
+        raise RuntimeError("q must be [T, Hq, 128] bf16, T = qo_indptr[-1]")
+    T, Hq = q.size(0), q.size(1)
+    if Hq % Hkv:
+        raise RuntimeError(f"the {Hq} query heads are not a multiple of the cache's {Hkv} kv heads")
+    layer_idx, max_seq_len = int(layer_idx), int(max_seq_len)
+    if not 0 <= layer_idx < L:
+        raise RuntimeError(f"layer_idx {layer_idx} outside the cache's {L} layers")
+    if max_seq_len < 0:
+        raise RuntimeError("max_seq_len must be >= 0")
+    need = paged_prefill_workspace_bytes(T, B, Hq, Hkv, max_seq_len) if B and T else 0
+    if need and workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+    if need and (not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or workspace.device != dev
+                 or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need):
+        raise RuntimeError(f"workspace must be a contiguous device tensor of at least {need} bytes on {dev}")
+    o = torch.empty((T, Hq, 128), dtype=torch.bfloat16, device=dev)
+    scale = float(sm_scale) if sm_scale is not None else 128 ** -0.5
+    if not scale > 0:
+        raise ValueError("sm_scale must be positive")
+    with _on_device(dev.index):
+        st = lib.mm_paged_prefill(_ptr(q), _ptr(qo_indptr), T, _ptr(kv_data), _ptr(kv_param) if kv_param is not None else None, kind,
+                                  max_pages, L, layer_idx, Hkv, P, 128, _ptr(kv_indptr), _ptr(kv_indices), _ptr(last_page_len), B, Hq,
+                                  max_seq_len, scale, _ptr(workspace) if need else None,
+                                  workspace.numel() * workspace.element_size() if need else 0, _ptr(o), _stream_ptr(dev))
+    if st:
+        _lib.check(st, "paged_prefill")
     return o
