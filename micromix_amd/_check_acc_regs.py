@@ -20,7 +20,7 @@ def agprs(line):
     return out
 
 
-EXPECTED_KERNELS = 12   # mx_gemm256.hip -- g256: 2 + 2 grouped + 1 fused gate/up; g128: 2 + 2 split-K + 2 grouped + 1 fused gate/up
+EXPECTED_KERNELS = 13   # mx_gemm256.hip -- g256: 2 + 2 grouped + 1 fused gate/up + 1 tile-major tail; g128: 2 + 2 split-K + 2 grouped + 1 fused gate/up
 EXPECTED_SMALL = 4      # mx_gemm_tiles_small.hip -- g64: 2 + 2 grouped (the 4-wave tiles leave their accumulators to the compiler)
 
 

@@ -404,8 +404,19 @@ const char *describe_mx_gemm256(int M, int N, const int K[3], bool w4, size_t ws
     return buf;
 }
 
+// The 256-row tiles with fp4 weights end with the tile-major tail (mx_gemm_tile.inc, run_tail) when it applies: bf16 output and at
+// least two slabs in the last (fp8 x fp4) segment.  The "w" mode (fp8 / fp6 weights) keeps the old path: its kernel already sits at
+// the 128-VGPR limit, and its fp8 x fp8 stage (66 KiB) leaves no third stage to free.
+static bool g256_tail(const GemmArgs &a, bool w4) { return w4 && !a.out_f32 && (a.K[2] >> 7) >= 2; }
+
+static hipError_t launch_g256(const GemmArgs &a, bool w4, int wgs, DynamicLdsOnce *done, hipStream_t stream) {
+    if (g256_tail(a, w4)) return launch_tile(g256::mx_gemm256_kernel<true, false, true>, done[2], g256::Lds<true>::TOTAL, wgs, g256::NT, a, stream);
+    if (w4) return launch_tile(g256::mx_gemm256_kernel<true, false>, done[0], g256::Lds<true>::TOTAL, wgs, g256::NT, a, stream);
+    return launch_tile(g256::mx_gemm256_kernel<false, false>, done[1], g256::Lds<false>::TOTAL, wgs, g256::NT, a, stream);
+}
+
 hipError_t launch_mx_gemm256(const GemmArgs &a, bool w4, hipStream_t stream) {
-    static DynamicLdsOnce done[12];
+    static DynamicLdsOnce done[12], done256[3];
     const TilePlan p = plan_tiles(a.M, a.N, a.K, w4, a.ws != nullptr, a.ws_bytes, a.force_split != 0, a.tickets_zeroed != 0);
     switch (p.kind) {
         case TK_SPLITK: {
@@ -459,15 +470,12 @@ hipError_t launch_mx_gemm256(const GemmArgs &a, bool w4, hipStream_t stream) {
             lo.n_tiles = p.tn - c;
             hi.n_tile0 = p.tn - c;
             hi.n_tiles = c;
-            hipError_t e = w4 ? launch_tile(g256::mx_gemm256_kernel<true, false>, done[0], g256::Lds<true>::TOTAL, p.tm256 * (p.tn - c), g256::NT, lo, stream)
-                           : launch_tile(g256::mx_gemm256_kernel<false, false>, done[1], g256::Lds<false>::TOTAL, p.tm256 * (p.tn - c), g256::NT, lo, stream);
+            hipError_t e = launch_g256(lo, w4, p.tm256 * (p.tn - c), done256, stream);
             if (e != hipSuccess) return e;
             return w4 ? launch_tile(g128::mx_gemm256_kernel<true, false>, done[2], g128::Lds<true>::TOTAL, p.tm128 * c, g128::NT, hi, stream)
                       : launch_tile(g128::mx_gemm256_kernel<false, false>, done[3], g128::Lds<false>::TOTAL, p.tm128 * c, g128::NT, hi, stream);
         }
-        case TK_G256:
-            if (w4) return launch_tile(g256::mx_gemm256_kernel<true, false>, done[0], g256::Lds<true>::TOTAL, p.tiles256, g256::NT, a, stream);
-            return launch_tile(g256::mx_gemm256_kernel<false, false>, done[1], g256::Lds<false>::TOTAL, p.tiles256, g256::NT, a, stream);
+        case TK_G256: return launch_g256(a, w4, p.tiles256, done256, stream);
         default:
             if (w4) return launch_tile(g128::mx_gemm256_kernel<true, false>, done[2], g128::Lds<true>::TOTAL, p.tiles128, g128::NT, a, stream);
             return launch_tile(g128::mx_gemm256_kernel<false, false>, done[3], g128::Lds<false>::TOTAL, p.tiles128, g128::NT, a, stream);

@@ -896,6 +896,172 @@ __device__ __forceinline__ void wait_slabs(const D &dma) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Tile-major tail (the TAIL kernels: 256 x 256 tile, fp4 weights, bf16 output, no split-K, no fused activation; the last segment).
+// Before: every CU ran its K loop to the end and then stored its 128 KiB at once; that write-out (~5 us at 4096^3, the HBM write
+// rate with every CU storing, matrix pipe idle) was ~10 % of the launch.  Here the last TWO slabs of the launch, both resident in
+// LDS once the last DMA has landed, are computed tile by tile so that finished output tiles leave while the MFMAs of the others
+// still run.  The wave's 2 x 4 accumulator tiles go in four groups (tm, tn pair): per group eight MFMAs -- the four K steps of the
+// two slabs on both tiles, alternating between the tiles so that no MFMA waits for the one before it; every accumulator receives
+// its K steps in the order the slab-major loop gives them, so the sums are bit for bit the same.  Between those eight MFMAs runs
+// the PREVIOUS group's epilogue: the rounding of write_tile (bf16, + bias, bf16) into a wave-private [32 rows][64 features] image,
+// then 16-byte row-contiguous write-through stores of whole 128-byte lines.  The images live in the third stage of the ring,
+// which held slab count - 3 and is free from the barrier of that slab on.  The fragments of a group are read from LDS when the
+// group starts (the loop's two full fragment sets would not fit next to a second set for the next group).
+// ---------------------------------------------------------------------------------------------------------
+constexpr int TAIL_EP = 192;   // row pitch of a tail image: 48 dwords = 16 mod 32 banks, so the two rows a 32-lane half writes per
+                               // ds_write_b32 fall on disjoint banks, and rows two apart start 32 banks apart (the row reads)
+template <class G, class FX, class FW>
+struct TailTM {
+    using XF = typename Frag<G::XEL>::type;
+    using WF = typename Frag<G::WEL>::type;
+    static_assert(TM == 2 && TN == 4 && G::KSTEPS == 2 && G::NSTAGE == 3, "the tail is written out for the 256 x 256 tile on a three-stage 128-deep ring");
+    // byte arithmetic: 8 waves x 32 rows x 192 B = 48 KiB of images in one 50 KiB stage (fp8 x fp4: 32 + 16 + 2 KiB)
+    static_assert((NT / 64) * 32 * TAIL_EP <= G::STAGE, "the tail images fit in the stage the tail frees");
+    const GemmArgs &a;
+    const uint8_t *sa, *sb;      // stages of slab count - 2 and count - 1
+    uint8_t *img;                // this wave's image
+    const FX &fx;
+    const FW &fw;
+    Scales<G::KD> sca, scb;
+    float bias[TN];
+    int m0w, n0w;                // first token / feature of the wave's block
+    int lane, li, hi;
+    unsigned sel;
+    XF xs[4];                    // the four K steps of the group's activation fragment (tm)
+    WF ws[2][4];                 // ... and of its two weight fragments
+
+    template <int TM_>
+    __device__ __forceinline__ void load_x() {
+        xs[0] = load_frag<G::XEL, G::KD, 0>(sa, fx, TM_);
+        xs[1] = load_frag<G::XEL, G::KD, 1>(sa, fx, TM_);
+        xs[2] = load_frag<G::XEL, G::KD, 0>(sb, fx, TM_);
+        xs[3] = load_frag<G::XEL, G::KD, 1>(sb, fx, TM_);
+    }
+    template <int TN_>
+    __device__ __forceinline__ void load_w(WF (&w)[4]) {
+        w[0] = load_frag<G::WEL, G::KD, 0>(sa + G::OFF_W, fw, TN_);
+        w[1] = load_frag<G::WEL, G::KD, 1>(sa + G::OFF_W, fw, TN_);
+        w[2] = load_frag<G::WEL, G::KD, 0>(sb + G::OFF_W, fw, TN_);
+        w[3] = load_frag<G::WEL, G::KD, 1>(sb + G::OFF_W, fw, TN_);
+    }
+    // MFMA I of group (TM_, P): K step I >> 1 on tile J = I & 1 of the pair
+    template <int TM_, int P, int I>
+    __device__ __forceinline__ void mfma() {
+        constexpr int J = I & 1, H = I >> 1, TN_ = 2 * P + J;
+        const Scales<G::KD> &sc = H < 2 ? sca : scb;
+        mfma_tile<TN_ * TM + TM_, G::XEL, G::WEL, (H & 1), true>(xs[H], ws[J][H], sc.x[0][TM_], sc.w[0][TN_]);
+    }
+    // (v0, v1) = this lane's feature at tokens t, t + 1 -> features (li & ~1, li | 1) at token t + (lane & 1): write_tile's pair_to_token
+    __device__ __forceinline__ unsigned pair_to_token(float v0, float v1, float b) const {
+        unsigned out = 0;
+        MM_DEVICE_ONLY(
+            unsigned p;
+            asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(p) : "v"(v0), "v"(v1));
+            if (a.bias != nullptr) {
+                const float r0 = __uint_as_float(p << 16) + b, r1 = __uint_as_float(p & 0xFFFF0000u) + b;
+                asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(p) : "v"(r0), "v"(r1));
+            }
+            const unsigned other = (unsigned)__builtin_amdgcn_mov_dpp((int)p, 0xB1, 0xF, 0xF, true);   // quad_perm [1,0,3,2]
+            out = __builtin_amdgcn_perm(other, p, sel);)
+        return out;
+    }
+    // chunk C of group (TM_, P)'s rounding: registers 4q .. 4q + 3 (tokens 8q + 4hi + 0..3) of tile J = C >> 2, q = C & 3
+    template <int TM_, int P, int C>
+    __device__ __forceinline__ void round_chunk() {
+        constexpr int J = C >> 2, Q = C & 3, T = (2 * P + J) * TM + TM_;
+        if constexpr (C == 0) acc_settle();   // the group's last MFMA issued one MFMA ago at least; 18 wait states before a VALU read
+        const float v0 = acc_read<16 * T + 4 * Q>(), v1 = acc_read<16 * T + 4 * Q + 1>();
+        const float v2 = acc_read<16 * T + 4 * Q + 2>(), v3 = acc_read<16 * T + 4 * Q + 3>();
+        uint8_t *wr = img + (4 * hi + (lane & 1)) * TAIL_EP + (li & ~1) * 2 + J * 64;
+        *reinterpret_cast<unsigned *>(wr + (8 * Q) * TAIL_EP) = pair_to_token(v0, v1, bias[2 * P + J]);
+        *reinterpret_cast<unsigned *>(wr + (8 * Q + 2) * TAIL_EP) = pair_to_token(v2, v3, bias[2 * P + J]);
+    }
+    // the image of group (TM_, P) to D: four wave instructions of eight 128-byte rows (write_tile's TN = 2 row mapping)
+    template <int TM_, int P>
+    __device__ __forceinline__ void store_group() {
+        const int rgrp = ((0x96 >> ((lane >> 2) & 7)) & 1) + 2 * hi, ridx = ((lane >> 3) & 3) * 4 + (lane & 3);
+        const bool vec_ok = (a.N & 7) == 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int rowl = 8 * j + (rgrp & 1) + 4 * (rgrp >> 1) + 2 * (ridx >> 3), ch = ridx & 7;
+            const uint4 v = *reinterpret_cast<const uint4 *>(img + rowl * TAIL_EP + ch * 16);
+            const int m = m0w + TM_ * 32 + rowl, n = n0w + P * 64 + ch * 8;
+            if (m < a.M) {
+                uint16_t *dst = a.D + (size_t)m * a.N + n;
+                if (vec_ok && n + 7 < a.N) {
+                    typedef unsigned v4u __attribute__((ext_vector_type(4)));
+                    [[maybe_unused]] const v4u vv = {v.x, v.y, v.z, v.w};
+                    MM_DEVICE_ONLY(asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(dst), "v"(vv) : "memory");)
+                } else {
+                    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                    for (int e = 0; e < 8; ++e)
+                        if (n + e < a.N) dst[e] = (uint16_t)(w[e >> 1] >> (16 * (e & 1)));
+                }
+            }
+        }
+    }
+    // group GI = (tm, tn pair) = (GI >> 1, GI & 1): its fragments, its eight MFMAs with group GI - 1's rounding between them, then
+    // group GI - 1's stores.  GI = 4: the last group's rounding and stores, nothing left to hide them behind.
+    template <int GI, int I = 0>
+    __device__ __forceinline__ void mfmas_with_rounding() {
+        if constexpr (I < 8) {
+            mfma<(GI >> 1), (GI & 1), I>();
+            if constexpr (GI > 0) round_chunk<((GI - 1) >> 1), ((GI - 1) & 1), I>();
+            mfmas_with_rounding<GI, I + 1>();
+        }
+    }
+    template <int GI>
+    __device__ __forceinline__ void group() {
+        if constexpr (GI < 4) {
+            constexpr int TM_ = GI >> 1, P = GI & 1;
+            if constexpr (P == 0) load_x<TM_>();
+            load_w<2 * P>(ws[0]);
+            load_w<2 * P + 1>(ws[1]);
+            mfmas_with_rounding<GI>();
+        } else {
+#if MM_CLOCKS
+            // loop end of the TAIL kernels: the last MFMA is issued (raw stamps; tile_body makes them relative to its start)
+            if (a.clock_out != nullptr && mm_tid() == 0) {
+                a.clock_out[4 * blockIdx.x] = __builtin_amdgcn_s_memtime();
+                a.clock_out[4 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
+            }
+#endif
+            round_chunk<1, 1, 0>(); round_chunk<1, 1, 1>(); round_chunk<1, 1, 2>(); round_chunk<1, 1, 3>();
+            round_chunk<1, 1, 4>(); round_chunk<1, 1, 5>(); round_chunk<1, 1, 6>(); round_chunk<1, 1, 7>();
+        }
+        if constexpr (GI > 0) store_group<((GI - 1) >> 1), ((GI - 1) & 1)>();
+        if constexpr (GI < 4) group<GI + 1>();
+    }
+};
+
+// The tail itself: called in place of the loop's last two iterations.  On entry stage c2 holds slab count - 2 (complete), stage c1
+// slab count - 1 (in flight), stage cf nothing that any wave still reads.
+template <class G, class FX, class FW>
+__device__ __forceinline__ void run_tail(const GemmArgs &a, int m0, int n0, uint8_t *smem, int c2, int c1, int cf, const Scales<G::KD> &sca,
+                                         const FX &fx, const FW &fw, int gx, int gw) {
+    const int lane = mm_tid() & 63, wave = __builtin_amdgcn_readfirstlane(mm_tid() >> 6);
+    const int wm = wave >> 1, wn = wave & 1, li = lane & 31, kb = lane >> 5;
+    wait_vmcnt<0>();       // this thread's share of slab count - 1 has landed ...
+    barrier_lds_only();    // ... and every thread's
+    TailTM<G, FX, FW> t{a, smem + c2 * G::STAGE, smem + c1 * G::STAGE, smem + cf * G::STAGE + wave * (32 * TAIL_EP), fx, fw};
+    t.sca = sca;
+    load_scales<G>(t.scb, t.sb, gx, gw, li, kb);
+    t.m0w = m0 + wm * (TM * 32);
+    t.n0w = n0 + wn * (TN * 32);
+    t.lane = lane;
+    t.li = li;
+    t.hi = lane >> 5;
+    t.sel = (lane & 1) ? 0x03020706u : 0x05040100u;
+#pragma unroll
+    for (int tn = 0; tn < TN; ++tn) {
+        const int n = t.n0w + tn * 32 + li;
+        t.bias[tn] = (a.bias != nullptr && n < a.N) ? bf16_bits_to_f32(a.bias[n]) : 0.0f;
+    }
+    t.template group<0>();
+}
+
 // Chaining.  A segment's successor: while segment A walks its last slabs it requests the first `pref` slabs of segment B
 // (pref = min(B's stages, B's slabs); 0 = no chaining), so that B starts with slab 0 in LDS, certified by A's last barrier, and
 // slabs 1 .. pref-1 in flight -- exactly the state B's own prologue would have produced, minus the prologue.  Without it a segment
@@ -918,11 +1084,13 @@ __device__ __forceinline__ void wait_slabs(const D &dma) {
 // accumulators between two segments); unchained it sits between the issue of the first DMAs and the wait for them.
 // Returns the ring position after the last slab (where a same-geometry successor's slab 0 lies).
 // CH = false: no successor (nx is ignored) and never chained in.
-template <class G, bool CH, class NX, class PRE>
+// TAIL: the last segment of a TAIL kernel (count >= 2, no successor): the last two slabs run tile-major and write the output (run_tail).
+template <class G, bool CH, class NX, class PRE, bool TAIL = false>
 __device__ __forceinline__ int run_slabs_big(const GemmArgs &a, int Q, int nslab128, int first128, int count, int m0, int n0,
                                              uint8_t *smem, PRE pre, int pref_in, int cur0, const NX &nxd, int nx_pref) {
     constexpr int XEL = G::XEL, WEL = G::WEL, KD = G::KD;
     constexpr bool SAME = CH && (KD == NX::KD), DIFF = CH && (KD != NX::KD);
+    static_assert(!TAIL || G::NSTAGE == 3, "the tail runs on a three-stage ring");
     static_assert(!SAME || (NX::STAGE == G::STAGE && NX::NPIECES == SlabDma<G>::NPIECES), "a same-geometry successor continues the ring");
     const int lane = mm_tid() & 63, wave = __builtin_amdgcn_readfirstlane(mm_tid() >> 6);
     const int wm = wave >> 1, wn = wave & 1;
@@ -986,7 +1154,7 @@ __device__ __forceinline__ int run_slabs_big(const GemmArgs &a, int Q, int nslab
 #pragma unroll
     for (int i = 0; i < MM_PRESSURE; ++i) { keep_[i] = lane * (i + 3); MM_DEVICE_ONLY(asm volatile("" : "+v"(keep_[i]));) }
 #endif
-    for (int s = 0; s < count; ++s) {
+    for (int s = 0; s < (TAIL ? count - 2 : count); ++s) {
         const int nxt = next_of(cur);
         uint8_t *st_cur = stage_at(cur);
         uint8_t *st_nxt = stage_at(nxt);
@@ -1027,17 +1195,22 @@ __device__ __forceinline__ int run_slabs_big(const GemmArgs &a, int Q, int nslab
 #pragma unroll
     for (int i = 0; i < MM_PRESSURE; ++i) { MM_DEVICE_ONLY(asm volatile("" ::"v"(keep_[i]));) }
 #endif
+    if constexpr (TAIL) {
+        // slab count - 2 is in stage cur, count - 1 in the next; the third held count - 3 (or nothing when count = 2)
+        run_tail<G>(a, m0, n0, smem, cur, next_of(cur), next_of(next_of(cur)), sc, fx, fw, gx, gw);
+    }
     return cur;
 }
 
-template <class G, bool CH, class NX, class PRE>
+template <class G, bool CH, class NX, class PRE, bool TAIL = false>
 __device__ __forceinline__ int run_slabs(Acc &acc, const GemmArgs &a, int Q, int nslab128, int first128, int count, int m0, int n0,
                                          uint8_t *smem, PRE pre, int pref_in, int cur0, const NX &nxd, int nx_pref) {
     if constexpr (SMALL) {
+        static_assert(!TAIL, "the tail belongs to the 8-wave pipeline");
         run_slabs_small<G>(acc, a, Q, nslab128, first128, count, m0, n0, smem, pre);
         return 0;
     } else {
-        return run_slabs_big<G, CH, NX>(a, Q, nslab128, first128, count, m0, n0, smem, pre, pref_in, cur0, nxd, nx_pref);
+        return run_slabs_big<G, CH, NX, PRE, TAIL>(a, Q, nslab128, first128, count, m0, n0, smem, pre, pref_in, cur0, nxd, nx_pref);
     }
 }
 
@@ -1100,11 +1273,13 @@ __device__ __forceinline__ void run_segment(Acc &acc, const GemmArgs &a, int nsl
 
 // The three segments of one tile in a row, chained where the geometry allows (Segs::CHAIN, see "Chaining" above run_slabs_big): the fp4 segment hands
 // over to the first 128-deep segment that exists, S hands over to O.  `round_acc` = the rounding between two segments.
-template <bool W4, class RND>
+// TAIL: the O segment (n2s >= 2, the launcher's rule) ends with the tile-major tail, which writes the output (run_tail).
+template <bool W4, bool TAIL, class RND>
 __device__ __forceinline__ void run_all_segments(Acc &acc, const GemmArgs &a, int n0s, int n1s, int n2s, int m0, int n0, uint8_t *smem,
                                                  RND round_acc) {
     using SG = Segs<W4>;
     using DmaSO = typename SG::DmaSO;
+    static_assert(!TAIL || SG::CHAIN, "the tail is built into the chained segment sequence of the 256-row tile");
     auto nothing = [] {};
     if constexpr (!SG::CHAIN) {
         if (n0s) run_segment<W4, 0>(acc, a, n0s, 0, n0s, m0, n0, smem, nothing);
@@ -1160,7 +1335,7 @@ __device__ __forceinline__ void run_all_segments(Acc &acc, const GemmArgs &a, in
         }
         if (n2s) {
             if (any && pref == 0) barrier_lds_only();
-            run_slabs<typename SG::O, true>(acc, a, 2, n2s, 0, n2s, m0, n0, smem, pre, pref, pref ? cur : 0, d2, 0);
+            run_slabs<typename SG::O, true, DmaSO, decltype(pre), TAIL>(acc, a, 2, n2s, 0, n2s, m0, n0, smem, pre, pref, pref ? cur : 0, d2, 0);
         }
     }
 }
@@ -1689,8 +1864,10 @@ __device__ __forceinline__ void split_tile_reduce(const GemmArgs &a, const int b
 // (blockIdx.x % 8) all walk the same K range when splits is a multiple of 8, so each L2 holds one K slice of X and W.
 // `bid` = index of this workgroup among the workgroups of problem `a` (its block index, or the block index minus the first block
 // of the group in a grouped launch)
-template <bool W4, bool SPLITK, bool ACT = false>
+// TAIL: the tile-major tail writes the output under the last slabs' MFMAs (run_tail; bf16 output, the launcher's rule)
+template <bool W4, bool SPLITK, bool ACT = false, bool TAIL = false>
 __device__ __forceinline__ void tile_body(const GemmArgs &a, const int bid) {
+    static_assert(!TAIL || (!SPLITK && !ACT), "the tail replaces the plain bf16 epilogue only");
     extern __shared__ __attribute__((aligned(128))) uint8_t smem[];   // 128: FragOfsC relies on it
     Acc acc;   // empty for the 8-wave tiles (their accumulators are the AGPRs a[0 : NACC-1])
 
@@ -1797,7 +1974,20 @@ __device__ __forceinline__ void tile_body(const GemmArgs &a, const int bid) {
 #else
         const int lm0 = m0, ln0 = n0;
 #endif
-        run_all_segments<W4>(acc, a, n0s, n1s, n2s, lm0, ln0, smem, round_acc);
+        run_all_segments<W4, TAIL>(acc, a, n0s, n1s, n2s, lm0, ln0, smem, round_acc);
+        if constexpr (TAIL) {
+#if MM_CLOCKS
+            // run_tail stamped its loop end (the last MFMA) as raw counters; its stores are the last it issued
+            if (stamp && mm_tid() == 0) {
+                a.clock_out[4 * bid] -= t0;
+                a.clock_out[4 * bid + 1] -= r0;
+                a.clock_out[4 * bid + 2] = r0;
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's stores have left
+                a.clock_out[4 * bid + 3] = __builtin_amdgcn_s_memrealtime() - r0;
+            }
+#endif
+            return;
+        }
         __syncthreads();  // every wave is done with the operand stages: LDS is reused for the transpose (no DMA is in flight here)
         if constexpr (SMALL) {
             if (mm_tid() >= NT) return;   // the loader waves have no accumulators
@@ -1829,6 +2019,15 @@ template <bool W4, bool SPLITK>
 __global__ void __launch_bounds__(NTHREADS) mx_gemm256_kernel(GemmArgs a) {
     tile_body<W4, SPLITK>(a, blockIdx.x);
 }
+#if MM_WM == 4 && MM_TM == 2
+// fp4 weights, no split-K, bf16 output, at least two slabs in the O segment: the tile-major tail (run_tail).  An overload with a
+// third parameter: mx_gemm256_kernel<true, false, true>, while the two-parameter kernels keep their names.
+template <bool W4, bool SPLITK, bool TAIL>
+__global__ void __launch_bounds__(NTHREADS) mx_gemm256_kernel(GemmArgs a) {
+    static_assert(W4 && !SPLITK && TAIL, "the tail kernel exists for fp4 weights without split-K");
+    tile_body<W4, SPLITK, false, TAIL>(a, blockIdx.x);
+}
+#endif
 #if MM_WM == 4 && MM_TN == 4
 // fp4 weights, no split-K, the fused gate / up epilogue (write_tile_act)
 __global__ void __launch_bounds__(NTHREADS) mx_gemm256_act_kernel(GemmArgs a) {
