@@ -181,7 +181,8 @@ const char *mm_matmul_describe(int M, int N, int KN, int KS, int KO, int wmode, 
     if (M <= 64 && !mm::mx_gemm_small_m_uses_tiles(M, N, K, weights_fp4(wmode, KS, KO), workspace_bytes, (flags & MM_SPLIT_K_ALWAYS) != 0))
         return mm::mx_gemm_stream_supported(M, N, K, weights_fp4(wmode, KS, KO)) ? "mm::stream::mx_gemm_stream_kernel (weight streaming, M <= 64)"
                                                                          : "mm::skinny::mx_gemm_skinny*_kernel (weight streaming, M <= 64)";
-    return mm::describe_mx_gemm256(M, N, K, weights_fp4(wmode, KS, KO), workspace_bytes, (flags & MM_SPLIT_K_ALWAYS) != 0, (flags & MM_WS_TICKETS_ZEROED) != 0);
+    return mm::describe_mx_gemm256(M, N, K, weights_fp4(wmode, KS, KO), workspace_bytes, (flags & MM_SPLIT_K_ALWAYS) != 0, (flags & MM_WS_TICKETS_ZEROED) != 0,
+                                   (flags & MM_OUT_F32) != 0);
 }
 
 int mm_matmul(const uint8_t *AN, const uint8_t *BN, const uint8_t *AS, const uint8_t *BS, const uint8_t *AO,

@@ -26,6 +26,7 @@
 //  * with tokens on MFMA rows the accumulator has the feature index on the lane, so the epilogue transposes
 //    each wave's tile through LDS (free at that point) and stores whole 256-byte rows.
 #include "mx_gemm_prelude.h"
+#include <string.h>
 
 namespace mm {
 
@@ -382,8 +383,16 @@ bool mx_gemm_small_m_uses_tiles(int M, int N, const int K[3], bool w4, size_t ws
     return need > 0 && need <= ws_bytes;
 }
 
-const char *describe_mx_gemm256(int M, int N, const int K[3], bool w4, size_t ws_bytes, bool force_split, bool tickets_zeroed) {
-    static thread_local char buf[192];
+// The 256-row tiles walk a launch that is ONE fp8 x fp4 segment (K[0] = K[1] = 0: nothing is chained in) of at least two slabs with
+// the ping-pong K loop (mx_gemm_tile.inc, run_pingpong) in front of the tail: fp4 weights, bf16 output, no split-K (the callers of
+// launch_g256 never split).  Mixed splits, the "w" mode, fp32 output, the fused gate / up and the grouped kernels and the 128-row
+// tiles keep the lock-step loop.  -DMM_PINGPONG=0 restores that selection everywhere (A/B builds of one tree).
+static bool g256_pingpong(int K0, int K1, int K2, bool w4, bool out_f32) {
+    return MM_PINGPONG && w4 && !out_f32 && K0 == 0 && K1 == 0 && (K2 >> 7) >= 2;
+}
+
+const char *describe_mx_gemm256(int M, int N, const int K[3], bool w4, size_t ws_bytes, bool force_split, bool tickets_zeroed, bool out_f32) {
+    static thread_local char buf[224];
     const TilePlan p = plan_tiles(M, N, K, w4, ws_bytes > 0, ws_bytes, force_split, tickets_zeroed);
     const char *w = w4 ? "true" : "false";
     switch (p.kind) {
@@ -401,6 +410,10 @@ const char *describe_mx_gemm256(int M, int N, const int K[3], bool w4, size_t ws
             break;
         default: snprintf(buf, sizeof(buf), "mm::g128::mx_gemm256_kernel<%s,false> x %d workgroups (128x256 tiles)", w, p.tiles128); break;
     }
+    if ((p.kind == TK_G256 || p.kind == TK_G256_TAIL) && g256_pingpong(K[0], K[1], K[2], w4, out_f32)) {
+        const size_t n = strlen(buf);
+        snprintf(buf + n, sizeof(buf) - n, ", ping-pong K loop");
+    }
     return buf;
 }
 
@@ -410,13 +423,17 @@ const char *describe_mx_gemm256(int M, int N, const int K[3], bool w4, size_t ws
 static bool g256_tail(const GemmArgs &a, bool w4) { return w4 && !a.out_f32 && (a.K[2] >> 7) >= 2; }
 
 static hipError_t launch_g256(const GemmArgs &a, bool w4, int wgs, DynamicLdsOnce *done, hipStream_t stream) {
+#if MM_PINGPONG
+    if (g256_pingpong(a.K[0], a.K[1], a.K[2], w4, a.out_f32 != 0))
+        return launch_tile(g256::mx_gemm256_kernel<true, false, true, true>, done[3], g256::Lds<true>::TOTAL, wgs, g256::NT, a, stream);
+#endif
     if (g256_tail(a, w4)) return launch_tile(g256::mx_gemm256_kernel<true, false, true>, done[2], g256::Lds<true>::TOTAL, wgs, g256::NT, a, stream);
     if (w4) return launch_tile(g256::mx_gemm256_kernel<true, false>, done[0], g256::Lds<true>::TOTAL, wgs, g256::NT, a, stream);
     return launch_tile(g256::mx_gemm256_kernel<false, false>, done[1], g256::Lds<false>::TOTAL, wgs, g256::NT, a, stream);
 }
 
 hipError_t launch_mx_gemm256(const GemmArgs &a, bool w4, hipStream_t stream) {
-    static DynamicLdsOnce done[12], done256[3];
+    static DynamicLdsOnce done[12], done256[4];
     const TilePlan p = plan_tiles(a.M, a.N, a.K, w4, a.ws != nullptr, a.ws_bytes, a.force_split != 0, a.tickets_zeroed != 0);
     switch (p.kind) {
         case TK_SPLITK: {

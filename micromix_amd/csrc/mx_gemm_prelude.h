@@ -15,6 +15,9 @@
 #define MM_PRIO 1        // s_setprio for waves 4-7 of the 8-wave tiles (mx_gemm_tile.inc, tile_body); 0 = none
 #endif
 #include "mx_instrument.h"   // MM_DBG ablation switches and MM_CLOCKS: constant 0 unless built with -DMM_INSTRUMENT
+#ifndef MM_PINGPONG
+#define MM_PINGPONG 1  // the ping-pong K loop for one-segment fp8 x fp4 launches on the 256-row tile (mx_gemm_tile.inc, run_pingpong); 0 = lock-step loop
+#endif
 #ifndef MM_CHAIN
 #define MM_CHAIN 1  // chained segment hand-over on the 256-row tile (mx_gemm_tile.inc); 0 = every segment's own prologue (A/B builds)
 #endif

@@ -1341,6 +1341,150 @@ __device__ __forceinline__ void run_all_segments(Acc &acc, const GemmArgs &a, in
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Ping-pong K loop (the PP kernel: 256 x 256 tile, fp4 weights, bf16 output, a launch that is ONE fp8 x fp4 segment of >= 2 slabs,
+// nothing chained in; the launcher's rule, g256_pingpong).  In run_slabs_big all eight waves run their MFMAs, reach the barrier and
+// wait for their post-barrier fragment reads at the same time, so every SIMD's matrix pipe runs dry around each rendezvous (19 % of
+// the loop with no DMA at all, profiles/r06_delivery.txt).  Here the two waves of a SIMD (w and w + 4) take turns:
+//   G0 = waves 0-3, G1 = waves 4-7.  The loop is a chain of PERIODS, each ending in one workgroup barrier; in every period one
+//   group is in its COMPUTE phase (the 16 MFMAs of one slab, both K steps, back to back from a fragment set already in registers)
+//   and the other in its MEMORY phase (the ds_reads of its next slab's fragments and scales into that same set, and its own DMA
+//   pieces of the slab two ahead).  G1 runs exactly one period behind G0.  Slab s lives in stage s % 3:
+//     period 2s:     G0 memory(s)   G1 compute(s - 1)      G0 requests its pieces of slab s + 2 into stage (s + 2) % 3
+//     period 2s + 1: G0 compute(s)  G1 memory(s)           G1 requests its pieces of slab s + 2
+//   Stage (s + 2) % 3 held slab s - 1, last read by G1 in period 2s - 1 (lgkmcnt(0) in front of that barrier).  Slab s + 1 must be
+//   complete before G0 reads it in period 2s + 2: both groups certify it with a counted vmcnt in front of the barrier that ends
+//   period 2s + 1 -- G0 at the end of compute(s) (its pieces of s + 1 went out in period 2s - 2), G1 at the end of memory(s), right
+//   after issuing its pieces of s + 2 (its pieces of s + 1 went out in period 2s - 1).  The scale pieces are issued by waves 0 and 1,
+//   both in G0, so G1's count has no scale piece in it.  Never vmcnt(0) inside the loop.
+// Every accumulator still receives its K steps slab by slab, step 0 before step 1: the sums are bit for bit those of run_slabs_big.
+// Barriers (P = count - 2 ping-pong slabs): the prologue's one, then per group P memory + P compute phases and ONE extra period --
+// G1's first (period 0, it has no compute(-1)), G0's last (period 2P, G1 computes slab count - 3 while G0 only waits) -- both only
+// when P > 0: 1 + 2P + (P > 0) barriers per wave in each group, then run_tail's own.  count = 2: no ping-pong period; count = 3: one
+// slab, periods 0-2.  After the last one the state is exactly what run_tail documents: slab count - 2 complete in its stage (certified
+// at the end of period 2P - 1, or by the prologue when P = 0), slab count - 1 requested, the stage of slab count - 3 free.
+// MM_PP_CPIECES = c (0-2): the first c DMA pieces of a wave's share of a slab go out in its compute phase, one after every second
+// MFMA, instead of in its memory phase.  MM_PP_FLIP = 1: the computing wave of a SIMD at priority 1 (set and reset at the compute
+// phase's edges) instead of the static priority 1 of waves 4-7 (tile_body).
+// Register hazard: a memory phase overwrites the srcA / srcB fragment registers that the same wave's MFMAs read in the previous
+// period.  The gfx950 hazard table has a write-after-read entry for an MFMA's srcC only (the accumulators: AGPRs that no ds_read
+// writes), none for srcA / srcB, which the MFMA reads at issue; and a barrier lies between the last MFMA and the first such read,
+// which goes to step 0's fragments, read by MFMAs eight MFMAs earlier still.  (run_slabs_big overwrites set 0 after a barrier in the
+// same way.)
+// ---------------------------------------------------------------------------------------------------------
+#ifndef MM_PP_CPIECES
+#define MM_PP_CPIECES 0
+#endif
+#ifndef MM_PP_FLIP
+#define MM_PP_FLIP 0
+#endif
+template <class G>
+struct PingPong {
+    using D = SlabDma<G>;
+    static constexpr int XEL = G::XEL, WEL = G::WEL, KD = G::KD, CP = MM_PP_CPIECES;
+    static_assert(G::KSTEPS == 2 && G::NSTAGE == 3 && TM == 2 && TN == 4, "the ping-pong loop is written for the 256 x 256 tile on a three-stage 128-deep ring");
+    static_assert(D::SFW <= 4, "the scale pieces are issued by waves of G0 only (G1's vmcnt counts none)");
+    static_assert(CP >= 0 && CP <= 2 && CP < D::XP, "compute-phase pieces are activation pieces");
+    using XF = typename Frag<XEL>::type;
+    using WF = typename Frag<WEL>::type;
+    const D &dma;
+    const FragOfsOf<G, XEL> &fx;
+    const FragOfsOf<G, WEL> &fw;
+    int gx, gw, li, kb;
+    XF x[2][TM];        // one slab's fragments, both K steps: 32 + 32 VGPRs (run_slabs_big's x0 / x1 / w0 / w1)
+    WF w[2][TN];
+    Scales<KD> sc;
+
+    template <int H>
+    __device__ __forceinline__ void read_step(const uint8_t *st) {
+#pragma unroll
+        for (int t = 0; t < TM; ++t) x[H][t] = load_frag<XEL, KD, H>(st, fx, t);
+#pragma unroll
+        for (int t = 0; t < TN; ++t) w[H][t] = load_frag<WEL, KD, H>(st + G::OFF_W, fw, t);
+    }
+    template <int P = CP>
+    __device__ __forceinline__ void mem_pieces(int slab, uint8_t *stage) const {
+        if constexpr (P < D::NPIECES) {
+            dma.template piece<P>(slab, stage);
+            mem_pieces<P + 1>(slab, stage);
+        }
+    }
+    // memory phase: slab `st`'s fragments and scales (step 0 first), then this wave's memory-phase pieces of slab `ahead`
+    __device__ __forceinline__ void memory(const uint8_t *st, int ahead, uint8_t *st_ahead) {
+        read_step<0>(st);
+        read_step<1>(st);
+        load_scales<G>(sc, st, gx, gw, li, kb);
+        mem_pieces(ahead, st_ahead);
+        // the scale shifts stay in this phase, behind the DMA issue (hipcc would sink them behind the barrier, to the head of the
+        // compute phase)
+        MM_DEVICE_ONLY(asm volatile("" : "+v"(sc.x[0][0]), "+v"(sc.x[0][1]), "+v"(sc.w[0][0]), "+v"(sc.w[0][1]), "+v"(sc.w[0][2]),
+                                    "+v"(sc.w[0][3]));)
+    }
+    // compute phase: MFMA I = K step I >> 3 on tile I & 7 (run_slabs_big's order), compute-phase piece J after MFMA 2J + 1
+    template <int I = 0>
+    __device__ __forceinline__ void compute(int ahead, uint8_t *st_ahead) const {
+        if constexpr (I < 16) {
+            constexpr int H = I >> 3, P = I & 7, tn = P / TM, tm = P % TM;
+            mfma_tile<tn * TM + tm, XEL, WEL, H>(x[H][tm], w[H][tn], sc.x[0][tm], sc.w[0][tn]);
+            if constexpr ((I & 1) && (I >> 1) < CP) dma.template piece<(I >> 1)>(ahead, st_ahead);
+            compute<I + 1>(ahead, st_ahead);
+        }
+    }
+};
+
+template <class G>
+__device__ __forceinline__ void run_pingpong(const GemmArgs &a, int count, int m0, int n0, uint8_t *smem) {
+    using D = SlabDma<G>;
+    const int lane = mm_tid() & 63, wave = __builtin_amdgcn_readfirstlane(mm_tid() >> 6);
+    const int wm = wave >> 1, wn = wave & 1, li = lane & 31, kb = lane >> 5;
+    const bool g1 = wave >= NT / 128;     // wave-uniform: waves 4-7
+    D dma;
+    init_slab_dma<G>(dma, a, 2, m0, n0, count, 0, wave);
+    auto stage_at = [&](int i) { return smem + i * G::STAGE; };
+    // prologue: slabs 0 and 1 (count >= 2), wait for slab 0 only
+    dma.all(0, stage_at(0));
+    dma.all(1, stage_at(1));
+    wait_slabs<1>(dma);
+    barrier_lds_only();
+    FragOfsOf<G, G::XEL> fx;
+    FragOfsOf<G, G::WEL> fw;
+    fx.init(wm * (TM * 32) + li, kb);
+    fw.init(wn * (TN * 32) + li, kb);
+    const int gx = ((m0 & 127) >> 5) + wm * TM, gw = ((n0 & 127) >> 5) + wn * TN;
+    PingPong<G> pp{dma, fx, fw, gx, gw, li, kb};
+#if MM_PP_FLIP && MM_PRIO
+    MM_DEVICE_ONLY(asm volatile("s_setprio 0");)   // (tile_body gave waves 4-7 the static priority)
+#endif
+    const int P = count - 2;
+    if (g1 && P > 0) barrier_lds_only();           // period 0: G1 has no compute(-1)
+    int st = 0;                                     // stage of slab s
+    for (int s = 0; s < P; ++s) {
+        const int sa = st == 0 ? 2 : st - 1;        // stage of slab s + 2 (= that of slab s - 1)
+        pp.memory(stage_at(st), s + 2, stage_at(sa));
+        // G1: its pieces of slab s + 1 have landed; those of s + 2 (memory phase, issued just now) may stay in flight
+        if (g1) wait_vmcnt<D::NPIECES - 1 - PingPong<G>::CP>();
+        barrier_lds_only();
+#if MM_PP_FLIP
+        MM_DEVICE_ONLY(asm volatile("s_setprio 1");)
+#endif
+        pp.compute(s + 2, stage_at(sa));
+#if MM_PP_FLIP
+        MM_DEVICE_ONLY(asm volatile("s_setprio 0");)
+#endif
+        // G0: its pieces of slab s + 1 have landed; all of s + 2 may stay in flight
+        if (!g1) wait_slabs<1>(dma);
+        MM_DEVICE_ONLY(__builtin_amdgcn_sched_barrier(0);)   // the MFMAs are issued before the wave waits at the barrier
+        barrier_lds_only();
+        st = st == 2 ? 0 : st + 1;
+    }
+    if (!g1 && P > 0) barrier_lds_only();          // period 2P: G1 computes slab count - 3, G0 waits
+    // stage st holds slab count - 2 (complete), the next one count - 1 (requested), the third count - 3 (free)
+    const int c1 = st == 2 ? 0 : st + 1, cf = c1 == 2 ? 0 : c1 + 1;
+    Scales<G::KD> sca;
+    load_scales<G>(sca, stage_at(st), gx, gw, li, kb);
+    run_tail<G>(a, m0, n0, smem, st, c1, cf, sca, fx, fw, gx, gw);
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Epilogue of one tile: the accumulators (AGPRs a[0 : NACC-1] of the 8-wave tiles, `acc` of the 4-wave tiles) as bf16 (+ bias)
 // to D.  Every wave of the caller is past its last read of the operand stages (LDS is reused for the transposes).
 // ---------------------------------------------------------------------------------------------------------
@@ -1865,9 +2009,11 @@ __device__ __forceinline__ void split_tile_reduce(const GemmArgs &a, const int b
 // `bid` = index of this workgroup among the workgroups of problem `a` (its block index, or the block index minus the first block
 // of the group in a grouped launch)
 // TAIL: the tile-major tail writes the output under the last slabs' MFMAs (run_tail; bf16 output, the launcher's rule)
-template <bool W4, bool SPLITK, bool ACT = false, bool TAIL = false>
+// PP: the launch is one fp8 x fp4 segment of >= 2 slabs (K[0] = K[1] = 0), walked by the ping-pong loop (run_pingpong) into the tail
+template <bool W4, bool SPLITK, bool ACT = false, bool TAIL = false, bool PP = false>
 __device__ __forceinline__ void tile_body(const GemmArgs &a, const int bid) {
     static_assert(!TAIL || (!SPLITK && !ACT), "the tail replaces the plain bf16 epilogue only");
+    static_assert(!PP || (W4 && TAIL), "the ping-pong loop hands over to the tile-major tail");
     extern __shared__ __attribute__((aligned(128))) uint8_t smem[];   // 128: FragOfsC relies on it
     Acc acc;   // empty for the 8-wave tiles (their accumulators are the AGPRs a[0 : NACC-1])
 
@@ -1974,7 +2120,8 @@ __device__ __forceinline__ void tile_body(const GemmArgs &a, const int bid) {
 #else
         const int lm0 = m0, ln0 = n0;
 #endif
-        run_all_segments<W4, TAIL>(acc, a, n0s, n1s, n2s, lm0, ln0, smem, round_acc);
+        if constexpr (PP) run_pingpong<typename Segs<W4>::O>(a, n2s, lm0, ln0, smem);
+        else run_all_segments<W4, TAIL>(acc, a, n0s, n1s, n2s, lm0, ln0, smem, round_acc);
         if constexpr (TAIL) {
 #if MM_CLOCKS
             // run_tail stamped its loop end (the last MFMA) as raw counters; its stores are the last it issued
@@ -2026,6 +2173,13 @@ template <bool W4, bool SPLITK, bool TAIL>
 __global__ void __launch_bounds__(NTHREADS) mx_gemm256_kernel(GemmArgs a) {
     static_assert(W4 && !SPLITK && TAIL, "the tail kernel exists for fp4 weights without split-K");
     tile_body<W4, SPLITK, false, TAIL>(a, blockIdx.x);
+}
+// ... and, when the launch is one fp8 x fp4 segment (K[0] = K[1] = 0), the ping-pong K loop in front of the tail (run_pingpong):
+// mx_gemm256_kernel<true, false, true, true>
+template <bool W4, bool SPLITK, bool TAIL, bool PP>
+__global__ void __launch_bounds__(NTHREADS) mx_gemm256_kernel(GemmArgs a) {
+    static_assert(W4 && !SPLITK && TAIL && PP, "the ping-pong kernel exists for fp4 weights without split-K, with the tail");
+    tile_body<W4, SPLITK, false, TAIL, PP>(a, blockIdx.x);
 }
 #endif
 #if MM_WM == 4 && MM_TN == 4

@@ -177,7 +177,7 @@ hipError_t launch_gate_up_act_stream_decode(const void *X, const int16_t *idx, c
 hipError_t launch_mx_gemm_skinny_grouped(const GroupedGemmArgs &ga, int max_m, bool w4, hipStream_t stream);
 size_t mx_gemm_workspace_bytes(int M, int N, const int K[3], bool w4, bool force, bool tickets_zeroed);
 bool mx_gemm_small_m_uses_tiles(int M, int N, const int K[3], bool w4, size_t ws_bytes, bool force_split);
-const char *describe_mx_gemm256(int M, int N, const int K[3], bool w4, size_t ws_bytes, bool force_split, bool tickets_zeroed);   // thread-local buffer  // 0 when mm_matmul would not split K for this shape
+const char *describe_mx_gemm256(int M, int N, const int K[3], bool w4, size_t ws_bytes, bool force_split, bool tickets_zeroed, bool out_f32 = false);   // thread-local buffer  // 0 when mm_matmul would not split K for this shape
 
 // paged KV cache (kv_cache.hip)
 void kv_decode_split(int B, int Hkv, int max_seq_len, int *nc, int *chunk);     // chunks of mm_paged_decode (host-known values only)
