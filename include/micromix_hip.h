@@ -311,7 +311,8 @@ int mm_rmsnorm_qlinear_decode(const void *X_bf16, const void *norm_weight_bf16, 
  *   parameters, round-half-even throughout:
  *     s = fp16(max(max - min, 1e-5) / 15);  base = clamp(rint(-min / s), 0, 15);  code = clamp(rint(x / s) + base, 0, 15);
  *     zero = fp16(base * s)     (correctly rounded divides; fp16 conversions saturate to +-65504; finite inputs)
- *   A row that does not straddle zero keeps the reference's behaviour: base clamps to 0 and the top codes clip.  Bf16: a copy.
+ *   A row that does not straddle zero keeps the reference's behaviour: base clamps to 0 and the top codes clip.  zero >= 0 always; a
+ *   zero of value 0 is stored as +0.0 (0x0000), never -0.0, also where rint(-min / s) is -0.0.  Bf16: a copy.
  *   Nothing outside the target slots is written.
  * mm_paged_decode: one query token per sequence, q bf16 [B, Hq, 128], Hq = g * Hkv with g <= 16; query head h attends kv head h / g
  *   (HF repeat_kv) over every cached token (no mask); softmax in fp32 with sm_scale (<= 0: 1 / sqrt(128)); o bf16 [B, Hq, 128], rounded

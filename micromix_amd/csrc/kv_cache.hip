@@ -94,7 +94,7 @@ __global__ __launch_bounds__(128) void kv_append_kernel(uint8_t *__restrict__ kv
     kv_data[row * (HD / 2) + lane] = (uint8_t)((unsigned)c0 | ((unsigned)c1 << 4));
     if (lane == 0) {
         kv_param[row * 2] = __float2half_rn(s);
-        kv_param[row * 2 + 1] = sat_half(base * s);
+        kv_param[row * 2 + 1] = sat_half(fabsf(base * s));   // base = clamp(-0.0) has no defined sign: a zero `zero` is stored as +0.0
     }
 }
 

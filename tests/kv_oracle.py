@@ -1,7 +1,8 @@
 """Numpy oracle of the paged KV cache (include/micromix_hip.h, mm_kv_append / mm_paged_decode).
 
 quantize_row   the int4 rule: quantize_int_group(x, 4, 128) (model/qLlamaLayer.py:13-23) in fp32 with fp16 (scale, zero), round half
-               to even throughout, correctly rounded fp32 divides, fp16 conversions saturating at +-65504
+               to even throughout, correctly rounded fp32 divides, fp16 conversions saturating at +-65504; a `zero` parameter of
+               value 0 (rows with min >= -s / 2, where base = clamp(rint(-min / s)) can come out as -0.0) is +0.0
 append         the bytes mm_kv_append writes into a host copy of the cache (FlashInfer paged layout, page.cuh:75-103,180-188)
 attention      fp64 single-token GQA attention over the dequantized cache of one layer
 """
@@ -28,7 +29,7 @@ def quantize_row(x):
     sf = s.astype(np.float32)
     base = np.clip(np.rint(-mn / sf), 0, 15).astype(np.float32)
     codes = np.clip(np.rint(x / sf[..., None]) + base[..., None], 0, 15).astype(np.uint8)
-    zero = _f16(base * sf)
+    zero = np.abs(_f16(base * sf))                     # base * s >= 0; a zero is stored as +0.0, never -0.0
     return codes, s, zero
 
 
