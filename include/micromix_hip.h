@@ -358,6 +358,32 @@ int mm_paged_prefill(const void *q_bf16, const int32_t *qo_indptr, int num_token
                      int num_qo_heads, int max_seq_len, float sm_scale, void *workspace, size_t workspace_bytes,
                      void *o_bf16, mm_stream_t stream);
 
+/*
+ * RoPE + paged KV append in one launch (version >= 620): takes q | k | v as the fused q/k/v projection leaves them, leaves the rotated
+ * q ready for mm_paged_decode / mm_paged_prefill and the rotated K and the untouched V in the cache.  Cache layout, page table, head_dim
+ * 128 as above; no limit on g = Hq / Hkv.
+ * mm_rope_kv_append: q, k, v are three bf16 pointers that share one token stride, qkv_token_stride, in elements; within a token the
+ *   heads are contiguous ([Hq * 128], [Hkv * 128], [Hkv * 128]).  A packed [T, (Hq + 2 Hkv) * 128] projection is passed as base,
+ *   base + Hq * 128, base + (Hq + Hkv) * 128 with stride (Hq + 2 Hkv) * 128; three contiguous tensors with Hq = Hkv share a stride too.
+ *   cos, sin bf16 [T, 128] with row stride cs_token_stride (elements): row i belongs to flat token i (HF's position_embeddings,
+ *   flattened; rope scaling is the caller's).  RoPE is HF's apply_rotary_pos_emb in bf16 tensor arithmetic,
+ *   x * cos + rotate_half(x) * sin, every op rounded to bf16 -- for element d of a head row, in fp32, round to nearest even:
+ *     a = bf16(x[d] * cos[d]);  b = bf16((d < 64 ? -x[d + 64] : x[d - 64]) * sin[d]);  y[d] = bf16(a + b)       (finite inputs)
+ *   The rotated q of every one of the T tokens goes to q_out bf16 [T, Hq, 128], contiguous, whether or not the token's cache slot is
+ *   valid.  The rotated K and V are written exactly as mm_kv_append writes them: the same slot rule (append_indptr, a page table that
+ *   already counts the tokens), the same int4 rule or bf16 copy, the same guards, nothing outside the target slots.
+ *   q_out must not overlap q, k, v, cos or sin (other workgroups may still be reading them).  No workspace, no host reads of device
+ *   arrays: capture-safe like mm_kv_append.
+ * Null pointers, negative sizes, Hq not a multiple of Hkv, a stride smaller than the row it holds (Hq * 128, 128) or odd, a q / k / v /
+ * cos / sin / q_out pointer that is not 4-byte aligned, or tokens without a sequence (num_tokens > 0 with batch = 0): MM_ERR_BAD_ARG;
+ * head_dim != 128: MM_ERR_UNSUPPORTED; num_tokens = 0: MM_OK; all without device work.
+ */
+int mm_rope_kv_append(void *kv_data, void *kv_param, int kv_dtype, int max_pages, int num_layers, int layer, int num_kv_heads, int page_size,
+                      int head_dim, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_len, int batch,
+                      const void *q_bf16, const void *k_bf16, const void *v_bf16, int64_t qkv_token_stride, int num_qo_heads,
+                      const void *cos_bf16, const void *sin_bf16, int64_t cs_token_stride, const int32_t *append_indptr, int num_tokens,
+                      void *q_out_bf16, mm_stream_t stream);
+
 /* Which kernel(s) and how many workgroups mm_matmul / mm_matmul_ws launch for this problem on the CURRENT device (the same
  * decision code as the launcher; workspace_bytes = 0 means "no workspace", i.e. never split-K).  Returns a string in a
  * thread-local buffer, valid until the calling thread's next call.  Used by bench.py to name the kernel it timed. */

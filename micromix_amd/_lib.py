@@ -21,7 +21,7 @@ EXPORTS = (
     "mm_gate_up_activate", "mm_gate_up_activate_decode", "mm_rmsnorm_gate_up_activate_decode", "mm_rmsnorm_gate_up_activate_decode_supported", "mm_gate_up_activate_decode_supported", "mm_down_activate_decode", "mm_down_activate_decode_supported", "mm_down_activate_decode_supported_w", "mm_gate_up_activate_workspace_bytes", "mm_gate_up_activate_describe", "mm_rmsnorm_quantize", "mm_qlinear_decode", "mm_qlinear_decode_supported", "mm_qlinear_decode_supported_w", "mm_rmsnorm_qlinear_decode", "mm_rmsnorm_qlinear_decode_supported", "mm_rmsnorm_qlinear_decode_supported_w", "mm_matmul_grouped", "mm_reorder_quantize_grouped",
     "mm_matmul_describe", "mm_test_function", "mm_diag_set_kernel_events",
     "mm_kv_append", "mm_paged_decode_workspace_bytes", "mm_paged_decode",
-    "mm_paged_prefill_workspace_bytes", "mm_paged_prefill",
+    "mm_paged_prefill_workspace_bytes", "mm_paged_prefill", "mm_rope_kv_append",
 )
 # every symbol include/micromix_diag.h declares (libmicromix_diag.so: hardware probes for tests/tools, never used by the ops)
 DIAG_LIB_PATH = os.environ.get("MICROMIX_DIAG_LIB") or os.path.join(_PKG, "lib", "libmicromix_diag.so")
@@ -147,6 +147,8 @@ def load():
     lib.mm_paged_prefill_workspace_bytes.argtypes = [i] * 5
     lib.mm_paged_prefill.restype = i
     lib.mm_paged_prefill.argtypes = [vp, vp, i, vp, vp] + [i] * 7 + [vp] * 3 + [i, i, i, ctypes.c_float, vp, sz, vp, vp]
+    lib.mm_rope_kv_append.restype = i
+    lib.mm_rope_kv_append.argtypes = [vp, vp] + [i] * 7 + [vp] * 3 + [i, vp, vp, vp, ctypes.c_int64, i, vp, vp, ctypes.c_int64, vp, i, vp, vp]
     _lib = lib
     return lib
 

@@ -29,7 +29,7 @@ static bool split_ok(int K, int KN, int KS, int KO) {
 
 extern "C" {
 
-int mm_version(void) { return 610; /* 0.6.1: + mm_paged_prefill(_workspace_bytes) (causal multi-token attention over the paged KV cache); 0.6.0: + mm_kv_append, mm_paged_decode(_workspace_bytes), enum mm_kv_dtype (paged int4 / bf16 KV cache); 0.5.1: + mm_rmsnorm_gate_up_activate_decode(_supported), mm_gate_up_activate_decode_supported; mm_gate_up_activate(_decode) one launch at decode sizes; 0.5.0: + the *_supported_w queries (weight mode); 0.4.0: + mm_rmsnorm_qlinear_decode(_supported) (0.3.0: + mm_gate_up_activate(_decode), mm_down_activate_decode, mm_matmul_ws_reset; 0.2.0: diagnostics moved to libmicromix_diag.so, + mm_test_function) */ }
+int mm_version(void) { return 620; /* 0.6.2: + mm_rope_kv_append (RoPE + paged KV append in one launch, from the packed q | k | v projection); 0.6.1: + mm_paged_prefill(_workspace_bytes) (causal multi-token attention over the paged KV cache); 0.6.0: + mm_kv_append, mm_paged_decode(_workspace_bytes), enum mm_kv_dtype (paged int4 / bf16 KV cache); 0.5.1: + mm_rmsnorm_gate_up_activate_decode(_supported), mm_gate_up_activate_decode_supported; mm_gate_up_activate(_decode) one launch at decode sizes; 0.5.0: + the *_supported_w queries (weight mode); 0.4.0: + mm_rmsnorm_qlinear_decode(_supported) (0.3.0: + mm_gate_up_activate(_decode), mm_down_activate_decode, mm_matmul_ws_reset; 0.2.0: diagnostics moved to libmicromix_diag.so, + mm_test_function) */ }
 
 const char *mm_test_function(void) { return "Hello from test_function!"; /* bindings.cpp:700 */ }
 
@@ -603,6 +603,30 @@ int mm_kv_append(void *kv_data, void *kv_param, int kv_dtype, int max_pages, int
     hipError_t e = mm::launch_kv_append(kv_data, kv_param, kv_dtype == MM_KV_INT4, kv_indptr, kv_indices, last_page_len, batch, k_bf16, v_bf16,
                                         append_indptr, num_tokens, max_pages, num_layers, layer, num_kv_heads, page_size, (hipStream_t)stream);
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_kv_append");
+}
+
+int mm_rope_kv_append(void *kv_data, void *kv_param, int kv_dtype, int max_pages, int num_layers, int layer, int num_kv_heads, int page_size,
+                      int head_dim, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_len, int batch,
+                      const void *q_bf16, const void *k_bf16, const void *v_bf16, int64_t qkv_token_stride, int num_qo_heads,
+                      const void *cos_bf16, const void *sin_bf16, int64_t cs_token_stride, const int32_t *append_indptr, int num_tokens,
+                      void *q_out_bf16, mm_stream_t stream) {
+    if (int st = kv_geometry(kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size, head_dim, batch)) return st;
+    if (num_tokens < 0 || num_qo_heads <= 0 || num_qo_heads % num_kv_heads) return MM_ERR_BAD_ARG;
+    // a row of a token's q (the widest of the three) and of cos / sin must fit its stride; the kernel moves dwords
+    if (qkv_token_stride < (int64_t)num_qo_heads * 128 || cs_token_stride < 128 || (qkv_token_stride & 1) || (cs_token_stride & 1))
+        return MM_ERR_BAD_ARG;
+    if (num_tokens == 0) return MM_OK;
+    if (batch == 0) return MM_ERR_BAD_ARG;                    // tokens that belong to no sequence
+    if (!kv_data || (kv_dtype == MM_KV_INT4 && !kv_param) || !kv_indptr || !kv_indices || !last_page_len || !q_bf16 || !k_bf16 || !v_bf16 ||
+        !cos_bf16 || !sin_bf16 || !append_indptr || !q_out_bf16)
+        return MM_ERR_BAD_ARG;
+    if (((uintptr_t)q_bf16 | (uintptr_t)k_bf16 | (uintptr_t)v_bf16 | (uintptr_t)cos_bf16 | (uintptr_t)sin_bf16 | (uintptr_t)q_out_bf16) & 3)
+        return MM_ERR_BAD_ARG;
+    hipError_t e = mm::launch_rope_kv_append(kv_data, kv_param, kv_dtype == MM_KV_INT4, kv_indptr, kv_indices, last_page_len, batch, q_bf16,
+                                             k_bf16, v_bf16, qkv_token_stride, num_qo_heads, cos_bf16, sin_bf16, cs_token_stride,
+                                             append_indptr, num_tokens, q_out_bf16, max_pages, num_layers, layer, num_kv_heads, page_size,
+                                             (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_rope_kv_append");
 }
 
 size_t mm_paged_decode_workspace_bytes(int batch, int num_qo_heads, int num_kv_heads, int max_seq_len) {

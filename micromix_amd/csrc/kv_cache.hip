@@ -20,47 +20,20 @@
 #include <stdint.h>
 
 #include "mx_kernels.h"
+#include "mx_kv_append.h"
 
 namespace {
+
+using namespace mm::kva;      // HD, bf16f, f2bf_rne, seq_len, kv_row, append_row, store_row
 
 typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
 typedef float v4f __attribute__((ext_vector_type(4)));
 
-constexpr int HD = 128;            // head_dim
 constexpr int DEC_WAVES = 4;
 constexpr int TILE = 32;           // tokens per wave iteration
 
-__device__ inline float bf16f(uint32_t bits16) { return __uint_as_float(bits16 << 16); }
-
-__device__ inline uint16_t f2bf_rne(float f) {    // finite inputs
-    const uint32_t u = __float_as_uint(f);
-    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-
-__device__ inline __half sat_half(float x) { return __float2half_rn(fminf(fmaxf(x, -65504.0f), 65504.0f)); }
-
-// the sequence a flat index belongs to: the largest b with indptr[b] <= i (empty sequences are skipped over)
-__device__ inline int find_seq(const int *indptr, int B, int i) {
-    int lo = 0, hi = B;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (indptr[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-__device__ inline int seq_len(const int *kv_indptr, const int *last_page_len, int b, int P) {
-    const int np = kv_indptr[b + 1] - kv_indptr[b];
-    return np > 0 ? (np - 1) * P + min(max(last_page_len[b], 0), P) : 0;    // clamped: a bad entry never reads past the page list
-}
-
-// row index (in rows of one token-head) of K (kv = 0) or V (kv = 1) of `page`, `slot`
-__device__ inline int64_t kv_row(int page, int L, int layer, int kv, int Hkv, int h, int P, int slot) {
-    return ((((int64_t)page * L + layer) * 2 + kv) * Hkv + h) * P + slot;
-}
-
-// One workgroup per appended token and kv head; wave 0 writes K, wave 1 writes V.
+// One workgroup per appended token and kv head; wave 0 writes K, wave 1 writes V (the slot and the int4 rule: mx_kv_append.h).
 template <bool INT4>
 __global__ __launch_bounds__(128) void kv_append_kernel(uint8_t *__restrict__ kv_data, __half *__restrict__ kv_param,
                                                         const int *__restrict__ kv_indptr, const int *__restrict__ kv_indices,
@@ -68,34 +41,10 @@ __global__ __launch_bounds__(128) void kv_append_kernel(uint8_t *__restrict__ kv
                                                         const uint16_t *__restrict__ v, const int *__restrict__ append_indptr, int B,
                                                         int max_pages, int L, int layer, int Hkv, int P) {
     const int i = blockIdx.x, h = blockIdx.y, which = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int b = find_seq(append_indptr, B, i);
-    const int len = seq_len(kv_indptr, last_page_len, b, P);
-    const int pos = len - (append_indptr[b + 1] - append_indptr[b]) + (i - append_indptr[b]);
-    if (pos < 0 || pos >= len) return;                        // a table that does not count the appended tokens: nothing written
-    const int page = kv_indices[kv_indptr[b] + pos / P];
-    if (page < 0 || page >= max_pages) return;
-    const int64_t row = kv_row(page, L, layer, which, Hkv, h, P, pos % P);
+    const int64_t row = append_row(kv_indptr, kv_indices, last_page_len, append_indptr, B, i, max_pages, L, layer, which, Hkv, h, P);
+    if (row < 0) return;
     const uint32_t two = ((const uint32_t *)((which ? v : k) + ((int64_t)i * Hkv + h) * HD))[lane];   // elements 2 lane, 2 lane + 1
-    if (!INT4) {
-        ((uint32_t *)kv_data)[row * (HD / 2) + lane] = two;
-        return;
-    }
-    const float x0 = bf16f(two & 0xffffu), x1 = bf16f(two >> 16);
-    float mn = fminf(x0, x1), mx = fmaxf(x0, x1);
-#pragma unroll
-    for (int o = 32; o; o >>= 1) {
-        mn = fminf(mn, __shfl_xor(mn, o));
-        mx = fmaxf(mx, __shfl_xor(mx, o));
-    }
-    const float s = __half2float(sat_half(__fdiv_rn(fmaxf(mx - mn, 1e-5f), 15.0f)));
-    const float base = fminf(fmaxf(rintf(__fdiv_rn(-mn, s)), 0.0f), 15.0f);
-    const float c0 = fminf(fmaxf(rintf(__fdiv_rn(x0, s)) + base, 0.0f), 15.0f);
-    const float c1 = fminf(fmaxf(rintf(__fdiv_rn(x1, s)) + base, 0.0f), 15.0f);
-    kv_data[row * (HD / 2) + lane] = (uint8_t)((unsigned)c0 | ((unsigned)c1 << 4));
-    if (lane == 0) {
-        kv_param[row * 2] = __float2half_rn(s);
-        kv_param[row * 2 + 1] = sat_half(fabsf(base * s));   // base = clamp(-0.0) has no defined sign: a zero `zero` is stored as +0.0
-    }
+    store_row<INT4>(kv_data, kv_param, row, lane, two);
 }
 
 // 8 int4 codes (one dword, element 2j in the low nibble of byte j) -> 8 bf16 values 16 + code (exact), MFMA operand order

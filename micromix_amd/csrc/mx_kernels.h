@@ -187,6 +187,11 @@ hipError_t launch_kv_append(void *kv_data, void *kv_param, bool int4, const int 
 hipError_t launch_paged_decode(const void *q, const void *kv_data, const void *kv_param, bool int4, const int *kv_indptr, const int *kv_indices,
                                const int *last_page_len, int B, int Hq, int Hkv, int max_pages, int L, int layer, int P, int max_seq_len,
                                float sm_scale, void *ws, void *o, hipStream_t stream);
+// RoPE + append in one launch (rope_append.hip): q | k | v share the token stride qkv_stride, cos | sin the stride cs_stride (elements)
+hipError_t launch_rope_kv_append(void *kv_data, void *kv_param, bool int4, const int *kv_indptr, const int *kv_indices,
+                                 const int *last_page_len, int B, const void *q, const void *k, const void *v, int64_t qkv_stride, int Hq,
+                                 const void *cos, const void *sin, int64_t cs_stride, const int *append_indptr, int T, void *q_out,
+                                 int max_pages, int L, int layer, int Hkv, int P, hipStream_t stream);
 // causal multi-token attention over the paged cache (kv_prefill.hip)
 void kv_prefill_split(int T, int B, int Hq, int Hkv, int max_seq_len, int *tiles, int *nc, int *chunk);   // host-known values only
 size_t kv_prefill_workspace_bytes(int T, int B, int Hq, int Hkv, int max_seq_len);

@@ -5,6 +5,8 @@
     for layer in range(32):
         cache.append(layer, k, v)          # k, v bf16 [T, Hkv, 128], T = the tokens extend() announced
         o = cache.attend(layer, q)         # q bf16 [B, Hq, 128] -> o bf16 [B, Hq, 128]
+        # or, from the q | k | v projection before RoPE, with HF's bf16 cos / sin rows [T, 128]: one launch instead of RoPE + append
+        o = cache.attend(layer, cache.append_rope(layer, q, k, v, cos, sin))
 
     cache.extend([300, 512, 5])            # several tokens per sequence: a prompt, a chunk of one, a speculative draft
     for layer in range(32):
@@ -99,6 +101,15 @@ class PagedKVCache:
         if k.dim() != 3 or k.size(0) != self.num_new_tokens:
             raise RuntimeError(f"append expects the {self.num_new_tokens} tokens announced by extend(), got k of shape {tuple(k.shape)}")
         mixedgemm.kv_append(self.kv_data, self.kv_param, self.kv_indptr, self.kv_indices, self.last_page_len, k, v, self.append_indptr, layer)
+
+    def append_rope(self, layer, q, k, v, cos, sin):
+        """RoPE + `append` in one launch: rotates q and k (bf16 [T, H, 128] or [T, H * 128], e.g. the views FusedQLinear returns) by the
+        bf16 cos / sin rows of the announced tokens ([T, 128] or HF's [bsz, q_len, 128]), writes the rotated K and V of `layer` and returns
+        the rotated q, bf16 [T, Hq, 128], for `attend` / `attend_new`.  Bit-equal to HF's bf16 apply_rotary_pos_emb followed by `append`."""
+        if q.dim() not in (2, 3) or q.size(0) != self.num_new_tokens:
+            raise RuntimeError(f"append_rope expects the {self.num_new_tokens} tokens announced by extend(), got q of shape {tuple(q.shape)}")
+        return mixedgemm.rope_kv_append(self.kv_data, self.kv_param, self.kv_indptr, self.kv_indices, self.last_page_len, q, k, v, cos, sin,
+                                        self.append_indptr, layer)
 
     def attend(self, layer, q, max_seq_len=None, sm_scale=None):
         """Decode attention of q (bf16 [B, Hq, 128]) over `layer`.  max_seq_len defaults to the longest sequence now (host

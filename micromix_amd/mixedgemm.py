@@ -30,7 +30,7 @@ from . import _lib
 
 __all__ = ["test_function", "matmul", "gate_up_activate", "interleave_gate_up", "reorder_quantize_x", "reorder_quantize_w", "reorder_quantize_w4", "activate_quantize_x",
            "downproj_quantize_w", "downproj_quantize_w4", "rmsnorm_quantize_x", "qlinear_decode", "qlinear_decode_supported", "matmul_grouped", "reorder_quantize_x_grouped",
-           "kv_append", "paged_decode", "paged_decode_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes"]
+           "kv_append", "rope_kv_append", "paged_decode", "paged_decode_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes"]
 
 
 def test_function():
@@ -889,6 +889,80 @@ def kv_append(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, k, v, app
                               k.size(0), _stream_ptr(dev))
     if st:
         _lib.check(st, "kv_append")
+
+
+def _token_rows(t, name, heads):
+    """(heads, token stride in elements) of q / k / v given as [T, H, 128] or [T, H * 128] whose rows lie contiguous within a token.
+    Stride 0: any stride will do (at most one token); None: the tensor has to be copied (rows not contiguous, an odd stride, a
+    misaligned pointer)"""
+    if t.dim() == 3 and t.size(2) == 128:
+        H, inner = t.size(1), t.stride(2) == 1 and (t.size(1) == 1 or t.stride(1) == 128)
+    elif t.dim() == 2 and t.size(1) % 128 == 0 and t.size(1):
+        H, inner = t.size(1) // 128, t.stride(1) == 1
+    else:
+        raise RuntimeError(f"{name} must be [T, H, 128] or [T, H * 128] bf16")
+    if heads is not None and H != heads:
+        raise RuntimeError(f"{name} has {H} heads, the cache has {heads}")
+    stride = t.stride(0) if t.size(0) > 1 else 0
+    ok = inner and (stride == 0 or stride >= H * 128) and stride % 2 == 0 and t.data_ptr() % 4 == 0
+    return H, (stride if ok else None)
+
+
+def rope_kv_append(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, q, k, v, cos, sin, append_indptr, layer_idx):
+    """RoPE on q and k, then `kv_append` of (rotated k, v), in one launch; returns the rotated q, bf16 [T, Hq, 128] contiguous.
+
+    q, k, v: bf16 [T, H, 128] or [T, H * 128].  Views of one packed [T, (Hq + 2 Hkv) * 128] projection (what FusedQLinear returns) are
+    read in place; so are any three tensors with one common token stride.  Otherwise they are packed into one buffer first (one copy).
+    cos, sin: bf16 [T, 128], or HF's [1, T, 128] / [bsz, q_len, 128] (flattened): row i belongs to flat token i; a row stride is honoured.
+    RoPE is HF's apply_rotary_pos_emb in bf16 arithmetic, q * cos + rotate_half(q) * sin with every op rounded to bf16, bit for bit
+    (include/micromix_hip.h, mm_rope_kv_append).  The cache receives exactly what kv_append(rope(k), v) writes; q is rotated for every
+    token.  Page table and append_indptr as in `kv_append`.  Runs on the current stream, capture-safe.
+    """
+    lib = _lib.load()
+    if not (isinstance(kv_data, torch.Tensor) and kv_data.is_cuda):
+        _check_tensor(kv_data, "kv_data", torch.uint8 if kv_param is not None else torch.bfloat16)
+    dev = kv_data.device
+    kind, max_pages, L, Hkv, P = _kv_geometry(kv_data, kv_param, dev.index)
+    B = _page_table(kv_indptr, kv_indices, last_page_len, dev)
+    if not _ok(append_indptr, torch.int32, dev.index):
+        _check_tensor(append_indptr, "append_indptr", torch.int32, dev)
+    if append_indptr.numel() != B + 1:
+        raise RuntimeError("append_indptr must have B + 1 entries")
+    for n, t in (("q", q), ("k", k), ("v", v), ("cos", cos), ("sin", sin)):
+        if not (isinstance(t, torch.Tensor) and t.dtype is torch.bfloat16 and t.is_cuda and t.get_device() == dev.index):
+            _check_tensor(t, n, torch.bfloat16, dev)      # contiguity is not asked of these five
+    Hq, sq = _token_rows(q, "q", None)
+    _, sk = _token_rows(k, "k", Hkv)
+    _, sv = _token_rows(v, "v", Hkv)
+    T = q.size(0)
+    if k.size(0) != T or v.size(0) != T:
+        raise RuntimeError("q, k and v must hold the same T tokens")
+    if Hq % Hkv:
+        raise RuntimeError(f"the {Hq} query heads are not a multiple of the cache's {Hkv} kv heads")
+    strides = {sq, sk, sv} - {0}
+    if None in strides or len(strides) > 1 or max(strides, default=Hq * 128) < Hq * 128:
+        packed = torch.cat([q.reshape(T, Hq * 128), k.reshape(T, Hkv * 128), v.reshape(T, Hkv * 128)], dim=1)
+        q, k, v = packed[:, : Hq * 128], packed[:, Hq * 128: (Hq + Hkv) * 128], packed[:, (Hq + Hkv) * 128:]
+        strides = {(Hq + 2 * Hkv) * 128}
+    sq = max(strides, default=Hq * 128)
+    if cos.shape != sin.shape or cos.dim() not in (2, 3) or cos.size(-1) != 128 or cos.numel() != T * 128:
+        raise RuntimeError(f"cos and sin must both be [T = {T}, 128] (or [bsz, q_len, 128] with bsz * q_len = T) bf16")
+    cos, sin = cos.reshape(T, 128), sin.reshape(T, 128)
+    sc = cos.stride(0) if T > 1 else 128
+    if not (cos.stride(1) == 1 and sin.stride(1) == 1 and (T <= 1 or sin.stride(0) == sc) and sc >= 128 and sc % 2 == 0
+            and cos.data_ptr() % 4 == 0 and sin.data_ptr() % 4 == 0):
+        cos, sin, sc = cos.contiguous(), sin.contiguous(), 128
+    layer_idx = int(layer_idx)
+    if not 0 <= layer_idx < L:
+        raise RuntimeError(f"layer_idx {layer_idx} outside the cache's {L} layers")
+    q_rot = torch.empty((T, Hq, 128), dtype=torch.bfloat16, device=dev)
+    with _on_device(dev.index):
+        st = lib.mm_rope_kv_append(_ptr(kv_data), _ptr(kv_param) if kv_param is not None else None, kind, max_pages, L, layer_idx, Hkv, P, 128,
+                                   _ptr(kv_indptr), _ptr(kv_indices), _ptr(last_page_len), B, _ptr(q), _ptr(k), _ptr(v), sq, Hq,
+                                   _ptr(cos), _ptr(sin), sc, _ptr(append_indptr), T, _ptr(q_rot), _stream_ptr(dev))
+    if st:
+        _lib.check(st, "rope_kv_append")
+    return q_rot
 
 
 def paged_decode_workspace_bytes(B, Hq, Hkv, max_seq_len):
