@@ -384,6 +384,38 @@ int mm_rope_kv_append(void *kv_data, void *kv_param, int kv_dtype, int max_pages
                       const void *cos_bf16, const void *sin_bf16, int64_t cs_token_stride, const int32_t *append_indptr, int num_tokens,
                       void *q_out_bf16, mm_stream_t stream);
 
+/*
+ * Sparse MoE block around mm_reorder_quantize_grouped / mm_matmul_grouped (version >= 630): top-k routing of the gate logits, the
+ * dispatch plan, the row gather and the weighted combine (the reference's MixtralSparseMoeBlock.forward, qMixtralLayer.py:414-452,
+ * without its per-expert host loop).  T tokens, E experts, n = T * top_k (token, k-slot) pairs, pair p = t * top_k + j.
+ * Limits: 1 <= top_k <= 8, top_k <= E <= 64, n < 2^31, H a multiple of 8 (rows move as 16-byte vectors; bf16 row pointers 16-byte
+ * aligned): otherwise MM_ERR_UNSUPPORTED.  Null or misaligned pointers, negative sizes: MM_ERR_BAD_ARG.  T = 0 (or no rows, H = 0):
+ * MM_OK without device work.  All four run on `stream`, read nothing on the host, need no workspace and no zeroed state
+ * (capture-safe), use no atomic that could decide an order: two launches on the same input give the same bytes.
+ *
+ * mm_moe_route: logits bf16 [T, E] -> topk_ids int32 [T, top_k], topk_w bf16 [T, top_k].  The top_k largest logits in descending
+ *   order, equal logits (-0.0 = +0.0) in ascending expert index.  w_j = exp(l_j - m) / sum over the selected of exp(l_i - m) in fp32,
+ *   m the largest logit, rounded to bf16 to nearest even: softmax -> topk -> renormalise -> cast, always renormalised.
+ * mm_moe_plan: topk_ids -> expert_offsets int32 [E + 1], sorted_token int32 [n], slot_of int32 [T, top_k].  A stable counting sort
+ *   of the pairs by expert: expert e owns the slots [expert_offsets[e], expert_offsets[e + 1]), within an expert the slots run by
+ *   ascending pair (so by ascending token), sorted_token[s] is the token of slot s and slot_of[t, j] its inverse.  An id outside
+ *   [0, E) is not counted and gets slot_of = -1; the slots from expert_offsets[E] on, which no pair owns then, get sorted_token = -1.
+ * mm_moe_gather: x bf16 [T, H], sorted_token [num_rows] -> x_sorted bf16 [num_rows, H]: x_sorted[s] = x[sorted_token[s]]; a row
+ *   whose sorted_token lies outside [0, T) is left untouched.
+ * mm_moe_combine: y_sorted bf16 [n, H], topk_ids, topk_w, slot_of -> out bf16 [T, H].  Per token its top_k entries in ascending
+ *   expert id (equal ids: ascending k-slot): c = bf16(y_sorted[slot] * w) (the fp32 product of two bf16 values is exact), acc =
+ *   bf16(acc + c) from +0.0, every rounding to nearest even -- what zeros + index_add_ expert by expert gives.  Entries with
+ *   slot_of outside [0, n) are skipped; a token with none gets zeros.  Every row of out is written.
+ */
+int mm_moe_route(const void *logits_bf16, int num_tokens, int num_experts, int top_k, int32_t *topk_ids, void *topk_w_bf16,
+                 mm_stream_t stream);
+int mm_moe_plan(const int32_t *topk_ids, int num_tokens, int num_experts, int top_k, int32_t *expert_offsets, int32_t *sorted_token,
+                int32_t *slot_of, mm_stream_t stream);
+int mm_moe_gather(const void *x_bf16, const int32_t *sorted_token, int num_tokens, int num_rows, int hidden, void *x_sorted_bf16,
+                  mm_stream_t stream);
+int mm_moe_combine(const void *y_sorted_bf16, const int32_t *topk_ids, const void *topk_w_bf16, const int32_t *slot_of, int num_tokens,
+                   int top_k, int hidden, void *out_bf16, mm_stream_t stream);
+
 /* Which kernel(s) and how many workgroups mm_matmul / mm_matmul_ws launch for this problem on the CURRENT device (the same
  * decision code as the launcher; workspace_bytes = 0 means "no workspace", i.e. never split-K).  Returns a string in a
  * thread-local buffer, valid until the calling thread's next call.  Used by bench.py to name the kernel it timed. */

@@ -22,6 +22,7 @@ EXPORTS = (
     "mm_matmul_describe", "mm_test_function", "mm_diag_set_kernel_events",
     "mm_kv_append", "mm_paged_decode_workspace_bytes", "mm_paged_decode",
     "mm_paged_prefill_workspace_bytes", "mm_paged_prefill", "mm_rope_kv_append",
+    "mm_moe_route", "mm_moe_plan", "mm_moe_gather", "mm_moe_combine",
 )
 # every symbol include/micromix_diag.h declares (libmicromix_diag.so: hardware probes for tests/tools, never used by the ops)
 DIAG_LIB_PATH = os.environ.get("MICROMIX_DIAG_LIB") or os.path.join(_PKG, "lib", "libmicromix_diag.so")
@@ -149,6 +150,14 @@ def load():
     lib.mm_paged_prefill.argtypes = [vp, vp, i, vp, vp] + [i] * 7 + [vp] * 3 + [i, i, i, ctypes.c_float, vp, sz, vp, vp]
     lib.mm_rope_kv_append.restype = i
     lib.mm_rope_kv_append.argtypes = [vp, vp] + [i] * 7 + [vp] * 3 + [i, vp, vp, vp, ctypes.c_int64, i, vp, vp, ctypes.c_int64, vp, i, vp, vp]
+    lib.mm_moe_route.restype = i
+    lib.mm_moe_route.argtypes = [vp, i, i, i, vp, vp, vp]
+    lib.mm_moe_plan.restype = i
+    lib.mm_moe_plan.argtypes = [vp, i, i, i, vp, vp, vp, vp]
+    lib.mm_moe_gather.restype = i
+    lib.mm_moe_gather.argtypes = [vp, vp, i, i, i, vp, vp]
+    lib.mm_moe_combine.restype = i
+    lib.mm_moe_combine.argtypes = [vp, vp, vp, vp, i, i, i, vp, vp]
     _lib = lib
     return lib
 

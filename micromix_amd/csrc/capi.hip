@@ -29,7 +29,7 @@ static bool split_ok(int K, int KN, int KS, int KO) {
 
 extern "C" {
 
-int mm_version(void) { return 620; /* 0.6.2: + mm_rope_kv_append (RoPE + paged KV append in one launch, from the packed q | k | v projection); 0.6.1: + mm_paged_prefill(_workspace_bytes) (causal multi-token attention over the paged KV cache); 0.6.0: + mm_kv_append, mm_paged_decode(_workspace_bytes), enum mm_kv_dtype (paged int4 / bf16 KV cache); 0.5.1: + mm_rmsnorm_gate_up_activate_decode(_supported), mm_gate_up_activate_decode_supported; mm_gate_up_activate(_decode) one launch at decode sizes; 0.5.0: + the *_supported_w queries (weight mode); 0.4.0: + mm_rmsnorm_qlinear_decode(_supported) (0.3.0: + mm_gate_up_activate(_decode), mm_down_activate_decode, mm_matmul_ws_reset; 0.2.0: diagnostics moved to libmicromix_diag.so, + mm_test_function) */ }
+int mm_version(void) { return 630; /* 0.6.3: + mm_moe_route, mm_moe_plan, mm_moe_gather, mm_moe_combine (top-k routing, dispatch and combine of a sparse MoE block around mm_matmul_grouped); 0.6.2: + mm_rope_kv_append (RoPE + paged KV append in one launch, from the packed q | k | v projection); 0.6.1: + mm_paged_prefill(_workspace_bytes) (causal multi-token attention over the paged KV cache); 0.6.0: + mm_kv_append, mm_paged_decode(_workspace_bytes), enum mm_kv_dtype (paged int4 / bf16 KV cache); 0.5.1: + mm_rmsnorm_gate_up_activate_decode(_supported), mm_gate_up_activate_decode_supported; mm_gate_up_activate(_decode) one launch at decode sizes; 0.5.0: + the *_supported_w queries (weight mode); 0.4.0: + mm_rmsnorm_qlinear_decode(_supported) (0.3.0: + mm_gate_up_activate(_decode), mm_down_activate_decode, mm_matmul_ws_reset; 0.2.0: diagnostics moved to libmicromix_diag.so, + mm_test_function) */ }
 
 const char *mm_test_function(void) { return "Hello from test_function!"; /* bindings.cpp:700 */ }
 
@@ -678,6 +678,54 @@ int mm_paged_prefill(const void *q_bf16, const int32_t *qo_indptr, int num_token
                                             max_seq_len, sm_scale > 0.0f ? sm_scale : 0.08838834764831845f, workspace, o_bf16,
                                             (hipStream_t)stream);
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_paged_prefill");
+}
+
+// ---- sparse MoE block (moe.hip)
+static int moe_shape(int T, int E, int top_k) {
+    if (T < 0 || E < 0 || top_k < 0) return MM_ERR_BAD_ARG;
+    if (top_k < 1 || top_k > 8 || E < top_k || E > 64 || (int64_t)T * top_k > INT32_MAX) return MM_ERR_UNSUPPORTED;
+    return MM_OK;
+}
+
+int mm_moe_route(const void *logits_bf16, int num_tokens, int num_experts, int top_k, int32_t *topk_ids, void *topk_w_bf16,
+                 mm_stream_t stream) {
+    if (int st = moe_shape(num_tokens, num_experts, top_k)) return st;
+    if (num_tokens == 0) return MM_OK;
+    if (!logits_bf16 || !topk_ids || !topk_w_bf16) return MM_ERR_BAD_ARG;
+    hipError_t e = mm::launch_moe_route(logits_bf16, num_tokens, num_experts, top_k, topk_ids, topk_w_bf16, (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_moe_route");
+}
+
+int mm_moe_plan(const int32_t *topk_ids, int num_tokens, int num_experts, int top_k, int32_t *expert_offsets, int32_t *sorted_token,
+                int32_t *slot_of, mm_stream_t stream) {
+    if (int st = moe_shape(num_tokens, num_experts, top_k)) return st;
+    if (num_tokens == 0) return MM_OK;
+    if (!topk_ids || !expert_offsets || !sorted_token || !slot_of) return MM_ERR_BAD_ARG;
+    hipError_t e = mm::launch_moe_plan(topk_ids, num_tokens * top_k, num_experts, top_k, expert_offsets, sorted_token, slot_of,
+                                       (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_moe_plan");
+}
+
+int mm_moe_gather(const void *x_bf16, const int32_t *sorted_token, int num_tokens, int num_rows, int hidden, void *x_sorted_bf16,
+                  mm_stream_t stream) {
+    if (num_tokens < 0 || num_rows < 0 || hidden < 0) return MM_ERR_BAD_ARG;
+    if (hidden % 8) return MM_ERR_UNSUPPORTED;
+    if (num_tokens == 0 || num_rows == 0 || hidden == 0) return MM_OK;
+    if (!x_bf16 || !sorted_token || !x_sorted_bf16 || (((uintptr_t)x_bf16 | (uintptr_t)x_sorted_bf16) & 15)) return MM_ERR_BAD_ARG;
+    hipError_t e = mm::launch_moe_gather(x_bf16, sorted_token, num_tokens, num_rows, hidden, x_sorted_bf16, (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_moe_gather");
+}
+
+int mm_moe_combine(const void *y_sorted_bf16, const int32_t *topk_ids, const void *topk_w_bf16, const int32_t *slot_of, int num_tokens,
+                   int top_k, int hidden, void *out_bf16, mm_stream_t stream) {
+    if (num_tokens < 0 || top_k < 0 || hidden < 0) return MM_ERR_BAD_ARG;
+    if (top_k < 1 || top_k > 8 || hidden % 8 || (int64_t)num_tokens * top_k > INT32_MAX) return MM_ERR_UNSUPPORTED;
+    if (num_tokens == 0 || hidden == 0) return MM_OK;
+    if (!y_sorted_bf16 || !topk_ids || !topk_w_bf16 || !slot_of || !out_bf16 || (((uintptr_t)y_sorted_bf16 | (uintptr_t)out_bf16) & 15))
+        return MM_ERR_BAD_ARG;
+    hipError_t e = mm::launch_moe_combine(y_sorted_bf16, topk_ids, topk_w_bf16, slot_of, num_tokens, top_k, hidden, out_bf16,
+                                          (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_moe_combine");
 }
 
 int mm_diag_set_kernel_events(void *start_event, void *stop_event) {

@@ -192,6 +192,12 @@ hipError_t launch_rope_kv_append(void *kv_data, void *kv_param, bool int4, const
                                  const int *last_page_len, int B, const void *q, const void *k, const void *v, int64_t qkv_stride, int Hq,
                                  const void *cos, const void *sin, int64_t cs_stride, const int *append_indptr, int T, void *q_out,
                                  int max_pages, int L, int layer, int Hkv, int P, hipStream_t stream);
+// sparse MoE block around the grouped GEMMs (moe.hip): n = T * top_k pairs, H a multiple of 8, rows 16-byte aligned
+hipError_t launch_moe_route(const void *logits, int T, int E, int top_k, int *ids, void *w, hipStream_t stream);
+hipError_t launch_moe_plan(const int *ids, int n, int E, int top_k, int *offsets, int *sorted_token, int *slot_of, hipStream_t stream);
+hipError_t launch_moe_gather(const void *x, const int *sorted_token, int T, int n_rows, int H, void *x_sorted, hipStream_t stream);
+hipError_t launch_moe_combine(const void *y, const int *ids, const void *w, const int *slot_of, int T, int top_k, int H, void *out,
+                              hipStream_t stream);
 // causal multi-token attention over the paged cache (kv_prefill.hip)
 void kv_prefill_split(int T, int B, int Hq, int Hkv, int max_seq_len, int *tiles, int *nc, int *chunk);   // host-known values only
 size_t kv_prefill_workspace_bytes(int T, int B, int Hq, int Hkv, int max_seq_len);

@@ -30,7 +30,8 @@ from . import _lib
 
 __all__ = ["test_function", "matmul", "gate_up_activate", "interleave_gate_up", "reorder_quantize_x", "reorder_quantize_w", "reorder_quantize_w4", "activate_quantize_x",
            "downproj_quantize_w", "downproj_quantize_w4", "rmsnorm_quantize_x", "qlinear_decode", "qlinear_decode_supported", "matmul_grouped", "reorder_quantize_x_grouped",
-           "kv_append", "rope_kv_append", "paged_decode", "paged_decode_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes"]
+           "kv_append", "rope_kv_append", "paged_decode", "paged_decode_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes",
+           "moe_route", "moe_plan", "moe_gather", "moe_combine"]
 
 
 def test_function():
@@ -411,14 +412,15 @@ def reorder_quantize_x_grouped(Xs, reorder_indices, KN, KS, KO):
     return res
 
 
-def matmul_grouped(As, Bs, *, biases=None, rounding="reference"):
+def matmul_grouped(As, Bs, *, biases=None, rounding="reference", outs=None):
     """`[matmul(*interleave(A_g, B_g)) for g]` for groups that share N, the (KN, KS, KO) split and the weight mode -- MoE experts
     (the per-expert loop of qMixtralLayer.py:507-519) -- in as few launches as possible: groups of <= 64 token rows run 8 per
     launch.  As[g] = (AN, AS, AO, SFAN, SFAS, SFAO) as returned by reorder_quantize_x, Bs[g] = (BN, BS, BO, SFBN, SFBS, SFBO).
-    Returns the list of [M_g, N] bf16 outputs, bit-identical to the separate calls.  Not an export of the reference module."""
+    Returns the list of [M_g, N] bf16 outputs, bit-identical to the separate calls.  `outs`: one contiguous [M_g, N] bf16 tensor per
+    group to write into instead (row slices of one buffer, say); they are returned.  Not an export of the reference module."""
     lib = _lib.load()
-    if len(As) != len(Bs) or (biases is not None and len(biases) != len(As)):
-        raise ValueError("As, Bs (and biases) must have one entry per group")
+    if len(As) != len(Bs) or (biases is not None and len(biases) != len(As)) or (outs is not None and len(outs) != len(As)):
+        raise ValueError("As, Bs (and biases, outs) must have one entry per group")
     if not As:
         return []
     dev = As[0][0].device
@@ -434,7 +436,7 @@ def matmul_grouped(As, Bs, *, biases=None, rounding="reference"):
     if rounding not in ("reference", "fused"):
         raise ValueError("rounding must be 'reference' or 'fused'")
     arr = (_lib.MMGroup * len(As))()
-    outs = []
+    given, outs = outs, []
     for g, (A, B) in enumerate(zip(As, Bs)):
         for t in (*A, *B):
             if not _ok(t, u8, index):
@@ -450,7 +452,13 @@ def matmul_grouped(As, Bs, *, biases=None, rounding="reference"):
         bias = biases[g] if biases is not None else None
         if bias is not None and (not _ok(bias, torch.bfloat16, index) or bias.numel() != N):
             raise RuntimeError(f"group {g}: bias must be a bfloat16 tensor with N elements")
-        out = torch.empty((M, N), dtype=torch.bfloat16, device=dev)
+        if given is None:
+            out = torch.empty((M, N), dtype=torch.bfloat16, device=dev)
+        else:
+            out = given[g]
+            if not _ok(out, torch.bfloat16, index) or tuple(out.shape) != (M, N):
+                _check_tensor(out, f"outs[{g}]", torch.bfloat16, dev)
+                raise RuntimeError(f"group {g}: outs[{g}] must be [{M}, {N}] bf16")
         outs.append(out)
         e = arr[g]
         e.AN, e.AS, e.AO, e.SFAN, e.SFAS, e.SFAO = (_ptr(t) for t in A)
@@ -1068,3 +1076,113 @@ def paged_prefill(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, qo
     if st:
         _lib.check(st, "paged_prefill")
     return o
+
+
+# ---- sparse MoE block (include/micromix_hip.h, mm_moe_*; micromix_amd/moe.py assembles the block) ----
+
+def _moe_tensor(t, name, dtype, dev, shape=None):
+    if not _ok(t, dtype, dev.index):
+        _check_tensor(t, name, dtype, dev)
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise RuntimeError(f"{name} must be {list(shape)}, got {list(t.shape)}")
+    return t
+
+
+def moe_route(logits, top_k, *, topk_ids=None, topk_w=None):
+    """Top-k routing of the gate logits: logits bf16 [T, E] -> (topk_ids int32 [T, top_k], topk_w bf16 [T, top_k]).
+
+    Not an export of the reference module; the same numbers as its softmax(float) -> topk -> renormalise -> cast
+    (qMixtralLayer.py:422-426): the top_k largest logits in descending order, equal logits in ascending expert index (torch.topk
+    leaves ties unspecified), w_j = exp(l_j - max) / sum over the selected, in fp32, rounded to bf16.  1 <= top_k <= 8,
+    top_k <= E <= 64.  Outputs are allocated unless passed in.  Runs on the current stream, capture-safe.
+    """
+    lib = _lib.load()
+    if not (isinstance(logits, torch.Tensor) and logits.is_cuda and _ok(logits, torch.bfloat16, logits.get_device())):
+        _check_tensor(logits, "logits", torch.bfloat16)
+    if logits.dim() != 2:
+        raise RuntimeError("logits must be [T, E] bf16")
+    dev, (T, E), top_k = logits.device, logits.shape, int(top_k)
+    topk_ids = torch.empty((T, top_k), dtype=torch.int32, device=dev) if topk_ids is None else _moe_tensor(topk_ids, "topk_ids", torch.int32, dev, (T, top_k))
+    topk_w = torch.empty((T, top_k), dtype=torch.bfloat16, device=dev) if topk_w is None else _moe_tensor(topk_w, "topk_w", torch.bfloat16, dev, (T, top_k))
+    with _on_device(dev.index):
+        st = lib.mm_moe_route(_ptr(logits), T, E, top_k, _ptr(topk_ids), _ptr(topk_w), _stream_ptr(dev))
+    if st:
+        _lib.check(st, "moe_route")
+    return topk_ids, topk_w
+
+
+def moe_plan(topk_ids, num_experts, *, expert_offsets=None, sorted_token=None, slot_of=None):
+    """The dispatch plan of routed tokens: topk_ids int32 [T, top_k] -> (expert_offsets int32 [E + 1], sorted_token int32 [T * top_k],
+    slot_of int32 [T, top_k]), a stable counting sort of the (token, k-slot) pairs by expert.
+
+    Expert e owns the slots [expert_offsets[e], expert_offsets[e + 1]); within an expert the slots run by ascending token;
+    sorted_token[s] is the token of slot s, slot_of[t, j] the slot of token t's j-th choice.  An id outside [0, E) is not counted and
+    gets slot_of = -1; the slots left over then hold sorted_token = -1.  Deterministic; runs on the current stream, capture-safe.
+    """
+    lib = _lib.load()
+    if not (isinstance(topk_ids, torch.Tensor) and topk_ids.is_cuda and _ok(topk_ids, torch.int32, topk_ids.get_device())):
+        _check_tensor(topk_ids, "topk_ids", torch.int32)
+    if topk_ids.dim() != 2:
+        raise RuntimeError("topk_ids must be [T, top_k] int32")
+    dev, (T, top_k), E = topk_ids.device, topk_ids.shape, int(num_experts)
+    i32 = torch.int32
+    if expert_offsets is None:      # without tokens the entry does no device work: the offsets are all zero then
+        expert_offsets = (torch.empty if T else torch.zeros)((max(E, 0) + 1,), dtype=i32, device=dev)
+    else:
+        _moe_tensor(expert_offsets, "expert_offsets", i32, dev, (E + 1,))
+        if T == 0:
+            expert_offsets.zero_()
+    sorted_token = torch.empty((T * top_k,), dtype=i32, device=dev) if sorted_token is None else _moe_tensor(sorted_token, "sorted_token", i32, dev, (T * top_k,))
+    slot_of = torch.empty((T, top_k), dtype=i32, device=dev) if slot_of is None else _moe_tensor(slot_of, "slot_of", i32, dev, (T, top_k))
+    with _on_device(dev.index):
+        st = lib.mm_moe_plan(_ptr(topk_ids), T, E, top_k, _ptr(expert_offsets), _ptr(sorted_token), _ptr(slot_of), _stream_ptr(dev))
+    if st:
+        _lib.check(st, "moe_plan")
+    return expert_offsets, sorted_token, slot_of
+
+
+def moe_gather(x, sorted_token, *, out=None):
+    """x bf16 [T, H], sorted_token int32 [n_rows] -> x_sorted bf16 [n_rows, H] with x_sorted[s] = x[sorted_token[s]] (H a multiple
+    of 8).  A row whose sorted_token lies outside [0, T) is left as it was (uninitialised in an output allocated here).  Runs on the
+    current stream, capture-safe."""
+    lib = _lib.load()
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and _ok(x, torch.bfloat16, x.get_device())):
+        _check_tensor(x, "x", torch.bfloat16)
+    if x.dim() != 2:
+        raise RuntimeError("x must be [T, H] bf16")
+    dev, (T, H) = x.device, x.shape
+    _moe_tensor(sorted_token, "sorted_token", torch.int32, dev)
+    n_rows = sorted_token.numel()
+    out = torch.empty((n_rows, H), dtype=torch.bfloat16, device=dev) if out is None else _moe_tensor(out, "out", torch.bfloat16, dev, (n_rows, H))
+    with _on_device(dev.index):
+        st = lib.mm_moe_gather(_ptr(x), _ptr(sorted_token), T, n_rows, H, _ptr(out), _stream_ptr(dev))
+    if st:
+        _lib.check(st, "moe_gather")
+    return out
+
+
+def moe_combine(y_sorted, topk_ids, topk_w, slot_of, *, out=None):
+    """The weighted sum of every token's expert outputs: y_sorted bf16 [T * top_k, H] (rows in plan order), topk_ids int32, topk_w bf16,
+    slot_of int32, all [T, top_k] -> out bf16 [T, H].
+
+    Per token its entries are taken in ascending expert id, c = bf16(y * w), acc = bf16(acc + c) from +0.0: bit for bit what the
+    reference's zeros + index_add_ expert by expert leaves (qMixtralLayer.py:428-450), whatever order topk_ids lists the experts in.
+    Entries with slot_of = -1 are skipped; every row of out is written.  Runs on the current stream, capture-safe.
+    """
+    lib = _lib.load()
+    if not (isinstance(y_sorted, torch.Tensor) and y_sorted.is_cuda and _ok(y_sorted, torch.bfloat16, y_sorted.get_device())):
+        _check_tensor(y_sorted, "y_sorted", torch.bfloat16)
+    dev = y_sorted.device
+    _moe_tensor(topk_ids, "topk_ids", torch.int32, dev)
+    if topk_ids.dim() != 2 or y_sorted.dim() != 2 or y_sorted.size(0) != topk_ids.numel():
+        raise RuntimeError("topk_ids must be [T, top_k] and y_sorted [T * top_k, H]")
+    T, top_k = topk_ids.shape
+    H = y_sorted.size(1)
+    _moe_tensor(topk_w, "topk_w", torch.bfloat16, dev, (T, top_k))
+    _moe_tensor(slot_of, "slot_of", torch.int32, dev, (T, top_k))
+    out = torch.empty((T, H), dtype=torch.bfloat16, device=dev) if out is None else _moe_tensor(out, "out", torch.bfloat16, dev, (T, H))
+    with _on_device(dev.index):
+        st = lib.mm_moe_combine(_ptr(y_sorted), _ptr(topk_ids), _ptr(topk_w), _ptr(slot_of), T, top_k, H, _ptr(out), _stream_ptr(dev))
+    if st:
+        _lib.check(st, "moe_combine")
+    return out

@@ -1,0 +1,142 @@
+"""The sparse MoE block on the MI355X: micromix_amd.moe.SparseMoEBlock against the per-expert loop it replaces, and its four new kernels.
+
+    python tools/time_moe.py [out.txt]
+
+Mixtral-8x7B shapes (H 4096, I 14336, E 8, top_k 2; splits as tests/test_model_shapes_gpu.py), T = 1, 16, 128, 4096, one set of weights.
+1. The block (`SparseMoEBlock.forward`: one host sync) and the reference's loop (model/qMixtralLayer.py:414-452, 502-519) written with
+   this library's per-expert ops -- torch softmax / topk / one_hot / where, reorder_quantize_x, matmul, F.silu * , index_add_ -- once
+   with the reference's two torch.cuda.synchronize() per expert and once without them.  Time = device events around ITERS back-to-back
+   calls / ITERS, so host gaps between launches count, as they do for a model.
+2. moe_route, moe_plan, moe_gather, moe_combine alone: ten calls captured in one hipGraph (no host time), replay time / 10; their sum
+   as a share of the block's time; for gather and combine the bytes they move as TB/s and as a fraction of 8 TB/s.
+"""
+from __future__ import annotations
+
+import json
+import os
+import sys
+
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from micromix_amd import SparseMoEBlock, mixedgemm  # noqa: E402
+from micromix_amd.qlinear import QLinearLayer  # noqa: E402
+
+H, I, E, K = 4096, 14336, 8, 2
+SPLIT_H, SPLIT_I = (3584, 256, 256), (12544, 1024, 768)
+WARM = 3
+
+
+def timed(fn, iters):
+    for _ in range(WARM):
+        fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) * 1e3 / iters     # us
+
+
+def graph_time(fn, calls=10, iters=20):
+    """us per call of `fn` when `calls` of them replay as one hipGraph"""
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        fn()
+    torch.cuda.current_stream().wait_stream(s)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        for _ in range(calls):
+            fn()
+    return timed(graph.replay, iters) / calls
+
+
+def make_experts(dev):
+    g = torch.Generator(device=dev).manual_seed(0)
+    out = []
+    for e in range(E):
+        i1 = torch.randperm(H, generator=g, device=dev).to(torch.int16)
+        i2 = torch.randperm(I, generator=g, device=dev).to(torch.int16)
+        layers = []
+        for n, k, split, idx in ((I, H, SPLIT_H, i1), (I, H, SPLIT_H, i1), (H, I, SPLIT_I, i2)):
+            lin = torch.nn.Linear(k, n, bias=False, dtype=torch.bfloat16, device=dev)
+            lin.weight.data = (torch.randn((n, k), generator=g, device=dev) * 0.02).to(torch.bfloat16)
+            layers.append(QLinearLayer(lin, p8_num=split[2], p6_num=split[1], reorder_index=idx))
+            del lin
+        out.append(tuple(layers))
+    return out
+
+
+def reference_loop(x, gate_w, experts, syncs):
+    mm = lambda q, l: mixedgemm.matmul(q[0], l.BN, q[1], l.BS, q[2], l.BO, q[3], l.SFBN, q[4], l.SFBS, q[5], l.SFBO)
+    logits = F.linear(x, gate_w)
+    rw = F.softmax(logits, dim=1, dtype=torch.float)
+    rw, sel = torch.topk(rw, K, dim=-1)
+    rw = (rw / rw.sum(dim=-1, keepdim=True)).to(x.dtype)
+    final = torch.zeros_like(x)
+    mask = F.one_hot(sel, num_classes=E).permute(2, 1, 0)
+    for e, (w1, w3, w2) in enumerate(experts):
+        idx, top_x = torch.where(mask[e])
+        if top_x.numel() == 0:
+            continue
+        cur = x[None, top_x].reshape(-1, H)
+        q = mixedgemm.reorder_quantize_x(cur, w1.reorder_index, w1.p4_num, w1.p6_num, w1.p8_num)
+        if syncs:
+            torch.cuda.synchronize()
+        h = F.silu(mm(q, w1)) * mm(q, w3)
+        q = mixedgemm.reorder_quantize_x(h, w2.reorder_index, w2.p4_num, w2.p6_num, w2.p8_num)
+        if syncs:
+            torch.cuda.synchronize()
+        final.index_add_(0, top_x, mm(q, w2) * rw[top_x, idx, None])
+    return final
+
+
+def main():
+    dev = torch.device("cuda:0")
+    experts = make_experts(dev)
+    g = torch.Generator(device=dev).manual_seed(1)
+    gate_w = (torch.randn((E, H), generator=g, device=dev) * 0.05).to(torch.bfloat16)
+    block = SparseMoEBlock(gate_w, experts, K)
+    lines, rows = [], []
+    lines.append(f"{'T':>5} {'block us':>9} {'loop us':>9} {'loop + ref syncs us':>20} | {'route':>7} {'plan':>7} {'gather':>7} {'combine':>8} {'share':>6} |"
+                 f" {'gather TB/s (/8)':>17} {'combine TB/s (/8)':>18}   rows per expert")
+    for T in (1, 16, 128, 4096):
+        x = torch.randn((T, H), generator=g, device=dev).to(torch.bfloat16)
+        iters = 20 if T >= 4096 else 50
+        block_us = timed(lambda: block(x), iters)
+        loop_us = timed(lambda: reference_loop(x, gate_w, experts, False), iters)
+        loop_sync_us = timed(lambda: reference_loop(x, gate_w, experts, True), iters)
+        logits = F.linear(x, gate_w)
+        ids, w = mixedgemm.moe_route(logits, K)
+        off, tok, slot = mixedgemm.moe_plan(ids, E)
+        xs = mixedgemm.moe_gather(x, tok)
+        y = torch.randn((T * K, H), generator=g, device=dev).to(torch.bfloat16)
+        out = torch.empty((T, H), dtype=torch.bfloat16, device=dev)
+        us = dict(route=graph_time(lambda: mixedgemm.moe_route(logits, K, topk_ids=ids, topk_w=w)),
+                  plan=graph_time(lambda: mixedgemm.moe_plan(ids, E, expert_offsets=off, sorted_token=tok, slot_of=slot)),
+                  gather=graph_time(lambda: mixedgemm.moe_gather(x, tok, out=xs)),
+                  combine=graph_time(lambda: mixedgemm.moe_combine(y, ids, w, slot, out=out)))
+        share = sum(us.values()) / block_us
+        gb = 2 * T * K * H * 2 + 4 * T * K                    # every sorted row read and written, the token list
+        cb = T * K * H * 2 + T * H * 2 + T * K * 10           # every expert row read, every token row written, ids / weights / slots
+        counts = (off[1:] - off[:-1]).tolist()
+        rows.append(dict(T=T, block_us=round(block_us, 1), loop_us=round(loop_us, 1), loop_ref_syncs_us=round(loop_sync_us, 1),
+                         **{n + "_us": round(v, 2) for n, v in us.items()}, kernels_share=round(share, 4), gather_bytes=gb,
+                         gather_tbps=round(gb / us["gather"] / 1e6, 3), combine_bytes=cb, combine_tbps=round(cb / us["combine"] / 1e6, 3),
+                         rows_per_expert=counts))
+        lines.append(f"{T:5d} {block_us:9.1f} {loop_us:9.1f} {loop_sync_us:20.1f} | {us['route']:7.2f} {us['plan']:7.2f} {us['gather']:7.2f} "
+                     f"{us['combine']:8.2f} {share:6.3f} | {gb / us['gather'] / 1e6:9.2f} ({gb / us['gather'] / 8e6:5.3f}) "
+                     f"{cb / us['combine'] / 1e6:10.2f} ({cb / us['combine'] / 8e6:5.3f})   {counts}")
+    text = "\n".join(lines)
+    print(text)
+    print(json.dumps(rows))
+    if len(sys.argv) > 1:
+        with open(sys.argv[1], "w") as f:
+            f.write(f"# {torch.cuda.get_device_name(0)}, torch {torch.__version__}; Mixtral-8x7B shapes H {H} I {I} E {E} top_k {K}\n{text}\n{json.dumps(rows)}\n")
+
+
+if __name__ == "__main__":
+    main()
