@@ -584,24 +584,29 @@ int mm_matmul_grouped(const mm_group *groups, int ngroups, int N, int KN, int KS
     return st != MM_OK ? st : flush_big();
 }
 
-// ---- paged KV cache (kv_cache.hip)
-static int kv_geometry(int kv_dtype, int max_pages, int L, int layer, int Hkv, int P, int head_dim, int B) {
+// ---- paged KV cache (kv_cache.hip, rope_append.hip, kv_prefill.hip)
+// What every entry point shares: kv_geometry checks the numbers and fills the descriptor, kv_pointers checks what it points to (int4
+// needs its params).  Two steps: a call with nothing to do returns MM_OK between them, before any pointer is looked at.
+static int kv_geometry(const void *kv_data, const void *kv_param, int kv_dtype, int max_pages, int L, int layer, int Hkv, int P, int head_dim,
+                       const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_len, int B, mm::PagedKV *kv) {
     if ((kv_dtype != MM_KV_INT4 && kv_dtype != MM_KV_BF16) || max_pages <= 0 || L <= 0 || layer < 0 || layer >= L || Hkv <= 0 || Hkv > 65535 ||
         P <= 0 || B < 0 || B > 65535 || head_dim <= 0)
         return MM_ERR_BAD_ARG;
+    *kv = {(uint8_t *)kv_data, (uint16_t *)kv_param, kv_indptr, kv_indices, last_page_len, max_pages, L, layer, Hkv, P, B, kv_dtype == MM_KV_INT4};
     return head_dim == 128 ? MM_OK : MM_ERR_UNSUPPORTED;
 }
+static bool kv_pointers(const mm::PagedKV &kv) { return kv.data && (!kv.int4 || kv.param) && kv.indptr && kv.indices && kv.last_page_len; }
 
 int mm_kv_append(void *kv_data, void *kv_param, int kv_dtype, int max_pages, int num_layers, int layer, int num_kv_heads, int page_size,
                  int head_dim, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_len, int batch,
                  const void *k_bf16, const void *v_bf16, const int32_t *append_indptr, int num_tokens, mm_stream_t stream) {
-    if (int st = kv_geometry(kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size, head_dim, batch)) return st;
+    mm::PagedKV kv;
+    if (int st = kv_geometry(kv_data, kv_param, kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size, head_dim, kv_indptr, kv_indices,
+                             last_page_len, batch, &kv)) return st;
     if (num_tokens < 0) return MM_ERR_BAD_ARG;
     if (num_tokens == 0 || batch == 0) return MM_OK;
-    if (!kv_data || (kv_dtype == MM_KV_INT4 && !kv_param) || !kv_indptr || !kv_indices || !last_page_len || !k_bf16 || !v_bf16 || !append_indptr)
-        return MM_ERR_BAD_ARG;
-    hipError_t e = mm::launch_kv_append(kv_data, kv_param, kv_dtype == MM_KV_INT4, kv_indptr, kv_indices, last_page_len, batch, k_bf16, v_bf16,
-                                        append_indptr, num_tokens, max_pages, num_layers, layer, num_kv_heads, page_size, (hipStream_t)stream);
+    if (!kv_pointers(kv) || !k_bf16 || !v_bf16 || !append_indptr) return MM_ERR_BAD_ARG;
+    hipError_t e = mm::launch_kv_append(kv, k_bf16, v_bf16, append_indptr, num_tokens, (hipStream_t)stream);
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_kv_append");
 }
 
@@ -610,47 +615,42 @@ int mm_rope_kv_append(void *kv_data, void *kv_param, int kv_dtype, int max_pages
                       const void *q_bf16, const void *k_bf16, const void *v_bf16, int64_t qkv_token_stride, int num_qo_heads,
                       const void *cos_bf16, const void *sin_bf16, int64_t cs_token_stride, const int32_t *append_indptr, int num_tokens,
                       void *q_out_bf16, mm_stream_t stream) {
-    if (int st = kv_geometry(kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size, head_dim, batch)) return st;
+    mm::PagedKV kv;
+    if (int st = kv_geometry(kv_data, kv_param, kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size, head_dim, kv_indptr, kv_indices,
+                             last_page_len, batch, &kv)) return st;
     if (num_tokens < 0 || num_qo_heads <= 0 || num_qo_heads % num_kv_heads) return MM_ERR_BAD_ARG;
     // a row of a token's q (the widest of the three) and of cos / sin must fit its stride; the kernel moves dwords
     if (qkv_token_stride < (int64_t)num_qo_heads * 128 || cs_token_stride < 128 || (qkv_token_stride & 1) || (cs_token_stride & 1))
         return MM_ERR_BAD_ARG;
     if (num_tokens == 0) return MM_OK;
     if (batch == 0) return MM_ERR_BAD_ARG;                    // tokens that belong to no sequence
-    if (!kv_data || (kv_dtype == MM_KV_INT4 && !kv_param) || !kv_indptr || !kv_indices || !last_page_len || !q_bf16 || !k_bf16 || !v_bf16 ||
-        !cos_bf16 || !sin_bf16 || !append_indptr || !q_out_bf16)
-        return MM_ERR_BAD_ARG;
+    if (!kv_pointers(kv) || !q_bf16 || !k_bf16 || !v_bf16 || !cos_bf16 || !sin_bf16 || !append_indptr || !q_out_bf16) return MM_ERR_BAD_ARG;
     if (((uintptr_t)q_bf16 | (uintptr_t)k_bf16 | (uintptr_t)v_bf16 | (uintptr_t)cos_bf16 | (uintptr_t)sin_bf16 | (uintptr_t)q_out_bf16) & 3)
         return MM_ERR_BAD_ARG;
-    hipError_t e = mm::launch_rope_kv_append(kv_data, kv_param, kv_dtype == MM_KV_INT4, kv_indptr, kv_indices, last_page_len, batch, q_bf16,
-                                             k_bf16, v_bf16, qkv_token_stride, num_qo_heads, cos_bf16, sin_bf16, cs_token_stride,
-                                             append_indptr, num_tokens, q_out_bf16, max_pages, num_layers, layer, num_kv_heads, page_size,
-                                             (hipStream_t)stream);
+    hipError_t e = mm::launch_rope_kv_append(kv, q_bf16, k_bf16, v_bf16, qkv_token_stride, num_qo_heads, cos_bf16, sin_bf16, cs_token_stride,
+                                             append_indptr, num_tokens, q_out_bf16, (hipStream_t)stream);
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_rope_kv_append");
 }
 
 size_t mm_paged_decode_workspace_bytes(int batch, int num_qo_heads, int num_kv_heads, int max_seq_len) {
     if (batch <= 0 || num_kv_heads <= 0 || num_qo_heads <= 0 || max_seq_len < 0 || num_qo_heads % num_kv_heads) return 0;
-    int nc, chunk;
-    mm::kv_decode_split(batch, num_kv_heads, max_seq_len, &nc, &chunk);
-    return nc > 1 ? (size_t)batch * num_qo_heads * nc * (128 + 2) * sizeof(float) : 0;
+    return mm::kv_decode_workspace_bytes(batch, num_qo_heads, num_kv_heads, max_seq_len);
 }
 
 int mm_paged_decode(const void *q_bf16, const void *kv_data, const void *kv_param, int kv_dtype, int max_pages, int num_layers, int layer,
                     int num_kv_heads, int page_size, int head_dim, const int32_t *kv_indptr, const int32_t *kv_indices,
                     const int32_t *last_page_len, int batch, int num_qo_heads, int max_seq_len, float sm_scale, void *workspace,
                     size_t workspace_bytes, void *o_bf16, mm_stream_t stream) {
-    if (int st = kv_geometry(kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size, head_dim, batch)) return st;
+    mm::PagedKV kv;
+    if (int st = kv_geometry(kv_data, kv_param, kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size, head_dim, kv_indptr, kv_indices,
+                             last_page_len, batch, &kv)) return st;
     if (num_qo_heads <= 0 || num_qo_heads % num_kv_heads || max_seq_len < 0) return MM_ERR_BAD_ARG;
     if (num_qo_heads / num_kv_heads > 16) return MM_ERR_UNSUPPORTED;
     if (batch == 0) return MM_OK;
-    if (!q_bf16 || !kv_data || (kv_dtype == MM_KV_INT4 && !kv_param) || !kv_indptr || !kv_indices || !last_page_len || !o_bf16)
-        return MM_ERR_BAD_ARG;
+    if (!q_bf16 || !kv_pointers(kv) || !o_bf16) return MM_ERR_BAD_ARG;
     const size_t need = mm_paged_decode_workspace_bytes(batch, num_qo_heads, num_kv_heads, max_seq_len);
     if (need && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15))) return MM_ERR_BAD_ARG;
-    hipError_t e = mm::launch_paged_decode(q_bf16, kv_data, kv_param, kv_dtype == MM_KV_INT4, kv_indptr, kv_indices, last_page_len, batch,
-                                           num_qo_heads, num_kv_heads, max_pages, num_layers, layer, page_size, max_seq_len,
-                                           sm_scale > 0.0f ? sm_scale : 0.08838834764831845f, workspace, o_bf16, (hipStream_t)stream);
+    hipError_t e = mm::launch_paged_decode(kv, q_bf16, num_qo_heads, max_seq_len, sm_scale, workspace, o_bf16, (hipStream_t)stream);
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_paged_decode");
 }
 
@@ -665,17 +665,16 @@ int mm_paged_prefill(const void *q_bf16, const int32_t *qo_indptr, int num_token
                      int max_pages, int num_layers, int layer, int num_kv_heads, int page_size, int head_dim, const int32_t *kv_indptr,
                      const int32_t *kv_indices, const int32_t *last_page_len, int batch, int num_qo_heads, int max_seq_len, float sm_scale,
                      void *workspace, size_t workspace_bytes, void *o_bf16, mm_stream_t stream) {
-    if (int st = kv_geometry(kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size, head_dim, batch)) return st;
+    mm::PagedKV kv;
+    if (int st = kv_geometry(kv_data, kv_param, kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size, head_dim, kv_indptr, kv_indices,
+                             last_page_len, batch, &kv)) return st;
     if (num_qo_heads <= 0 || num_qo_heads % num_kv_heads || max_seq_len < 0 || num_tokens < 0) return MM_ERR_BAD_ARG;
     if (num_qo_heads / num_kv_heads > 16) return MM_ERR_UNSUPPORTED;
     if (num_tokens == 0 || batch == 0) return MM_OK;
-    if (!q_bf16 || !qo_indptr || !kv_data || (kv_dtype == MM_KV_INT4 && !kv_param) || !kv_indptr || !kv_indices || !last_page_len || !o_bf16)
-        return MM_ERR_BAD_ARG;
+    if (!q_bf16 || !qo_indptr || !kv_pointers(kv) || !o_bf16) return MM_ERR_BAD_ARG;
     const size_t need = mm_paged_prefill_workspace_bytes(num_tokens, batch, num_qo_heads, num_kv_heads, max_seq_len);
     if (need && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15))) return MM_ERR_BAD_ARG;
-    hipError_t e = mm::launch_paged_prefill(q_bf16, qo_indptr, num_tokens, kv_data, kv_param, kv_dtype == MM_KV_INT4, kv_indptr, kv_indices,
-                                            last_page_len, batch, num_qo_heads, num_kv_heads, max_pages, num_layers, layer, page_size,
-                                            max_seq_len, sm_scale > 0.0f ? sm_scale : 0.08838834764831845f, workspace, o_bf16,
+    hipError_t e = mm::launch_paged_prefill(kv, q_bf16, qo_indptr, num_tokens, num_qo_heads, max_seq_len, sm_scale, workspace, o_bf16,
                                             (hipStream_t)stream);
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_paged_prefill");
 }

@@ -20,53 +20,35 @@
 #include <stdint.h>
 
 #include "mx_kernels.h"
-#include "mx_kv_append.h"
+#include "mx_paged_kv.h"
 
 namespace {
 
-using namespace mm::kva;      // HD, bf16f, f2bf_rne, seq_len, kv_row, append_row, store_row
+using namespace mm::kv;       // the page-table walk, the append rule, the int4 decoding and the chunk merge
+using mm::PagedKV;
 
-typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
 typedef float v4f __attribute__((ext_vector_type(4)));
 
 constexpr int DEC_WAVES = 4;
 constexpr int TILE = 32;           // tokens per wave iteration
 
-// One workgroup per appended token and kv head; wave 0 writes K, wave 1 writes V (the slot and the int4 rule: mx_kv_append.h).
+// One workgroup per appended token and kv head; wave 0 writes K, wave 1 writes V (the slot and the int4 rule: mx_paged_kv.h).
 template <bool INT4>
-__global__ __launch_bounds__(128) void kv_append_kernel(uint8_t *__restrict__ kv_data, __half *__restrict__ kv_param,
-                                                        const int *__restrict__ kv_indptr, const int *__restrict__ kv_indices,
-                                                        const int *__restrict__ last_page_len, const uint16_t *__restrict__ k,
-                                                        const uint16_t *__restrict__ v, const int *__restrict__ append_indptr, int B,
-                                                        int max_pages, int L, int layer, int Hkv, int P) {
+__global__ __launch_bounds__(128) void kv_append_kernel(const PagedKV kv, const uint16_t *__restrict__ k, const uint16_t *__restrict__ v,
+                                                        const int *__restrict__ append_indptr) {
     const int i = blockIdx.x, h = blockIdx.y, which = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t row = append_row(kv_indptr, kv_indices, last_page_len, append_indptr, B, i, max_pages, L, layer, which, Hkv, h, P);
+    const int64_t row = append_row(kv, append_indptr, i, which, h);
     if (row < 0) return;
-    const uint32_t two = ((const uint32_t *)((which ? v : k) + ((int64_t)i * Hkv + h) * HD))[lane];   // elements 2 lane, 2 lane + 1
-    store_row<INT4>(kv_data, kv_param, row, lane, two);
-}
-
-// 8 int4 codes (one dword, element 2j in the low nibble of byte j) -> 8 bf16 values 16 + code (exact), MFMA operand order
-__device__ inline v8bf codes_to_bf16(uint32_t w) {
-    const uint32_t lo = w & 0x0f0f0f0fu, hi = (w >> 4) & 0x0f0f0f0fu;
-    v4u r;
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        const uint32_t sel = 0x0c000c00u | ((4u + m) << 16) | (uint32_t)m;  // byte0 = lo.byte m, byte2 = hi.byte m, bytes 1, 3 = 0
-        r[m] = (__builtin_amdgcn_perm(hi, lo, sel) << 3) | 0x41804180u;    // bf16 0x4180 | c << 3 = 16 + c
-    }
-    return __builtin_bit_cast(v8bf, r);
+    const uint32_t two = ((const uint32_t *)((which ? v : k) + ((int64_t)i * kv.Hkv + h) * HD))[lane];   // elements 2 lane, 2 lane + 1
+    store_row<INT4>(kv, row, lane, two);
 }
 
 struct DecodeArgs {
+    PagedKV kv;
     const uint16_t *q;
-    const uint8_t *kv_data;
-    const __half *kv_param;
-    const int *kv_indptr, *kv_indices, *last_page_len;
     float *ws;                 // partials: o [B, Hkv, nc, g, 128], then (m, l) [B, Hkv, nc, g, 2]
     uint16_t *o;
-    int max_pages, L, layer, Hkv, P, B, Hq, g, nc, chunk;
+    int Hq, g, nc, chunk;
     float scale_log2;          // sm_scale * log2(e)
 };
 
@@ -80,11 +62,12 @@ __global__ __launch_bounds__(256) void paged_decode_kernel(const DecodeArgs a) {
 
     const int chunk = blockIdx.x, kvh = blockIdx.y, b = blockIdx.z;
     const int wave = threadIdx.x >> 6, l = threadIdx.x & 63, c = l & 15, kq = l >> 4;
-    const int g = a.g, P = a.P;
-    const int len = seq_len(a.kv_indptr, a.last_page_len, b, P);
+    const PagedKV &kv = a.kv;
+    const int g = a.g;
+    const int len = seq_len(kv, b);
     const int t0 = chunk * a.chunk;
     const int t1 = chunk == a.nc - 1 ? len : min(len, t0 + a.chunk);   // the last chunk runs to the end, whatever max_seq_len said
-    const int *pages = a.kv_indices + a.kv_indptr[b];
+    const int *pages = kv.indices + kv.indptr[b];
 
     // q as the MFMA A operand: lane (c, kq) holds head c, dims 32 kq + 8 s + j in step s
     v8bf qa[4];
@@ -120,27 +103,25 @@ __global__ __launch_bounds__(256) void paged_decode_kernel(const DecodeArgs a) {
         float sc[2][4], sv[2], zv[2];                  // sv, zv: the V row's (scale, zero) of the token
 #pragma unroll
         for (int G = 0; G < 2; ++G) {
-            const int t = tb + 16 * G + c;
-            int page = t < t1 ? pages[t / P] : -1;
-            const bool ok = page >= 0 && page < a.max_pages;
-            const int64_t rk = ok ? kv_row(page, a.L, a.layer, 0, a.Hkv, kvh, P, t % P) : 0;
-            if (kq == 0) s_row[wave][16 * G + c] = ok ? rk + (int64_t)a.Hkv * P : -1;
+            int64_t rk;
+            const bool ok = k_row(kv, pages, tb + 16 * G + c, t1, kvh, rk);
+            if (kq == 0) s_row[wave][16 * G + c] = ok ? rk + v_offset(kv) : -1;
             v4f d = {0.0f, 0.0f, 0.0f, 0.0f};
             if (INT4) {
-                v4u kc = *(const v4u *)(a.kv_data + rk * (HD / 2) + 16 * kq);
-                const uint32_t pk = *(const uint32_t *)(a.kv_param + rk * 2);
-                const uint32_t pv = *(const uint32_t *)(a.kv_param + (rk + (int64_t)a.Hkv * P) * 2);
+                v4u kc = *(const v4u *)(kv.data + rk * (HD / 2) + 16 * kq);
+                const uint32_t pk = *(const uint32_t *)(kv.param + rk * 2);
+                const uint32_t pv = *(const uint32_t *)(kv.param + (rk + v_offset(kv)) * 2);
                 if (!ok) kc = v4u{0, 0, 0, 0};
-                const float sk = ok ? __half2float(__ushort_as_half((unsigned short)(pk & 0xffffu))) : 0.0f;
-                const float zk = ok ? __half2float(__ushort_as_half((unsigned short)(pk >> 16))) : 0.0f;
-                sv[G] = ok ? __half2float(__ushort_as_half((unsigned short)(pv & 0xffffu))) : 0.0f;
-                zv[G] = ok ? __half2float(__ushort_as_half((unsigned short)(pv >> 16))) : 0.0f;
+                // the conversions stay inside the selects: which of the products below the compiler fuses follows this shape
+                const float sk = ok ? scale_of(pk) : 0.0f, zk = ok ? zero_of(pk) : 0.0f;
+                sv[G] = ok ? scale_of(pv) : 0.0f;
+                zv[G] = ok ? zero_of(pv) : 0.0f;
 #pragma unroll
                 for (int s = 0; s < 4; ++s) d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[s], codes_to_bf16(kc[s]), d, 0, 0, 0);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) sc[G][r] = sk * d[r] - (16.0f * sk + zk) * sq[r];
             } else {
-                const v4u *kr = (const v4u *)(a.kv_data + rk * (HD * 2) + 64 * kq);
+                const v4u *kr = (const v4u *)(kv.data + rk * (HD * 2) + 64 * kq);
                 v4u kb[4];
 #pragma unroll
                 for (int s = 0; s < 4; ++s) kb[s] = ok ? kr[s] : v4u{0, 0, 0, 0};
@@ -183,7 +164,7 @@ __global__ __launch_bounds__(256) void paged_decode_kernel(const DecodeArgs a) {
         if (INT4) {
             uint32_t vc[8];
 #pragma unroll
-            for (int i = 0; i < 8; ++i) vc[i] = *(const uint32_t *)(a.kv_data + (rv[i] < 0 ? 0 : rv[i]) * (HD / 2) + 4 * dg);
+            for (int i = 0; i < 8; ++i) vc[i] = *(const uint32_t *)(kv.data + (rv[i] < 0 ? 0 : rv[i]) * (HD / 2) + 4 * dg);
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 if (rv[i] < 0) continue;
@@ -203,7 +184,7 @@ __global__ __launch_bounds__(256) void paged_decode_kernel(const DecodeArgs a) {
         } else {
             v4u vb[8];
 #pragma unroll
-            for (int i = 0; i < 8; ++i) vb[i] = *(const v4u *)(a.kv_data + (rv[i] < 0 ? 0 : rv[i]) * (HD * 2) + 16 * dg);
+            for (int i = 0; i < 8; ++i) vb[i] = *(const v4u *)(kv.data + (rv[i] < 0 ? 0 : rv[i]) * (HD * 2) + 16 * dg);
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 if (rv[i] < 0) continue;
@@ -279,41 +260,27 @@ __global__ __launch_bounds__(256) void paged_decode_kernel(const DecodeArgs a) {
         const int hq = kvh * g + h;
         if (single) {
             const float inv = ls > 0.0f ? 1.0f / ls : 0.0f;
-            const uint32_t packed = (uint32_t)f2bf_rne(o0 * inv) | ((uint32_t)f2bf_rne(o1 * inv) << 16);
-            *(uint32_t *)(a.o + ((int64_t)b * a.Hq + hq) * HD + d) = packed;
+            *(uint32_t *)(a.o + ((int64_t)b * a.Hq + hq) * HD + d) = pack_bf(o0 * inv, o1 * inv);
         } else {
-            const int64_t part = (((int64_t)b * a.Hkv + kvh) * a.nc + chunk) * g + h;
+            const int64_t part = (((int64_t)b * kv.Hkv + kvh) * a.nc + chunk) * g + h;
             *(float2 *)(a.ws + part * HD + d) = make_float2(o0, o1);
-            if (d == 0) *(float2 *)(a.ws + (int64_t)a.B * a.Hq * a.nc * HD + part * 2) = make_float2(M, ls);
+            if (d == 0) *(float2 *)(a.ws + (int64_t)kv.B * a.Hq * a.nc * HD + part * 2) = make_float2(M, ls);
         }
     }
 }
 
-// combines the nc chunk partials of one (sequence, query head); a chunk without tokens has m = -inf and l = 0
+// combines the nc chunk partials of one (sequence, query head)
 __global__ __launch_bounds__(64) void paged_decode_merge_kernel(const DecodeArgs a) {
     const int hq = blockIdx.x, b = blockIdx.y, kvh = hq / a.g, h = hq % a.g, d = 2 * threadIdx.x;
-    const int64_t first = (((int64_t)b * a.Hkv + kvh) * a.nc) * a.g + h;      // part index of chunk 0; chunk stride g
-    const float *ml = a.ws + (int64_t)a.B * a.Hq * a.nc * HD;
-    float M = -INFINITY;
-    for (int c = 0; c < a.nc; ++c) M = fmaxf(M, ml[(first + (int64_t)c * a.g) * 2]);
-    float ls = 0.0f, o0 = 0.0f, o1 = 0.0f;
-    if (M != -INFINITY) {
-        for (int c = 0; c < a.nc; ++c) {
-            const int64_t part = first + (int64_t)c * a.g;
-            const float f = exp2f(ml[part * 2] - M);
-            const float2 v = *(const float2 *)(a.ws + part * HD + d);
-            ls += f * ml[part * 2 + 1];
-            o0 += f * v.x;
-            o1 += f * v.y;
-        }
-    }
-    const float inv = ls > 0.0f ? 1.0f / ls : 0.0f;
-    *(uint32_t *)(a.o + ((int64_t)b * a.Hq + hq) * HD + d) = (uint32_t)f2bf_rne(o0 * inv) | ((uint32_t)f2bf_rne(o1 * inv) << 16);
+    const int64_t first = (((int64_t)b * a.kv.Hkv + kvh) * a.nc) * a.g + h;      // part index of chunk 0; chunk stride g
+    float o[2];
+    merge_chunks<2>(a.ws + (int64_t)a.kv.B * a.Hq * a.nc * HD, a.ws + d, first, a.g, a.nc, o);
+    *(uint32_t *)(a.o + ((int64_t)b * a.Hq + hq) * HD + d) = pack_bf(o[0], o[1]);
 }
 
 template <bool INT4>
 hipError_t launch_decode_g(const DecodeArgs &a, hipStream_t stream) {
-    const dim3 grid(a.nc, a.Hkv, a.B);
+    const dim3 grid(a.nc, a.kv.Hkv, a.kv.B);
     if (a.g <= 4) paged_decode_kernel<INT4, 4><<<grid, 256, 0, stream>>>(a);
     else if (a.g <= 8) paged_decode_kernel<INT4, 8><<<grid, 256, 0, stream>>>(a);
     else paged_decode_kernel<INT4, 16><<<grid, 256, 0, stream>>>(a);
@@ -324,59 +291,51 @@ hipError_t launch_decode_g(const DecodeArgs &a, hipStream_t stream) {
 
 namespace mm {
 
-void kv_decode_split(int B, int Hkv, int max_seq_len, int *nc, int *chunk) {
-    // enough workgroups for two per CU of the 256 on an MI355X, chunks of at least 256 tokens (two tiles per wave);
-    // host-known values only, so a captured graph stays valid while the sequences grow up to max_seq_len
-    const int work = B * Hkv > 0 ? B * Hkv : 1;
-    const int want = (512 + work - 1) / work;
+void kv_chunks(long long work, int target_workgroups, int max_seq_len, int round_to, int *nc, int *chunk) {
+    if (work < 1) work = 1;
+    const long long want = (target_workgroups + work - 1) / work;
     const int most = (max_seq_len + 255) / 256;
-    int n = want < most ? want : most;
+    int n = want < most ? (int)want : most;
     if (n < 1) n = 1;
     int cl = (max_seq_len + n - 1) / n;
-    cl = (cl + TILE * DEC_WAVES - 1) / (TILE * DEC_WAVES) * (TILE * DEC_WAVES);
-    if (cl < TILE * DEC_WAVES) cl = TILE * DEC_WAVES;
+    cl = (cl + round_to - 1) / round_to * round_to;
+    if (cl < round_to) cl = round_to;
     *chunk = cl;
     *nc = max_seq_len > 0 ? (max_seq_len + cl - 1) / cl : 1;
 }
 
-hipError_t launch_kv_append(void *kv_data, void *kv_param, bool int4, const int *kv_indptr, const int *kv_indices, const int *last_page_len,
-                            int B, const void *k, const void *v, const int *append_indptr, int T, int max_pages, int L, int layer, int Hkv,
-                            int P, hipStream_t stream) {
-    const dim3 grid(T, Hkv);
-    if (int4)
-        kv_append_kernel<true><<<grid, 128, 0, stream>>>((uint8_t *)kv_data, (__half *)kv_param, kv_indptr, kv_indices, last_page_len,
-                                                         (const uint16_t *)k, (const uint16_t *)v, append_indptr, B, max_pages, L, layer, Hkv, P);
-    else
-        kv_append_kernel<false><<<grid, 128, 0, stream>>>((uint8_t *)kv_data, nullptr, kv_indptr, kv_indices, last_page_len,
-                                                          (const uint16_t *)k, (const uint16_t *)v, append_indptr, B, max_pages, L, layer, Hkv, P);
+void kv_decode_split(int B, int Hkv, int max_seq_len, int *nc, int *chunk) {
+    // two workgroups per CU of the 256 on an MI355X; a chunk gives every wave whole tiles
+    kv_chunks((long long)B * Hkv, 512, max_seq_len, TILE * DEC_WAVES, nc, chunk);
+}
+
+size_t kv_decode_workspace_bytes(int B, int Hq, int Hkv, int max_seq_len) {
+    int nc, chunk;
+    kv_decode_split(B, Hkv, max_seq_len, &nc, &chunk);
+    return nc > 1 ? (size_t)B * Hq * nc * (HD + 2) * sizeof(float) : 0;     // DecodeArgs::ws
+}
+
+hipError_t launch_kv_append(const PagedKV &kv, const void *k, const void *v, const int *append_indptr, int T, hipStream_t stream) {
+    const dim3 grid(T, kv.Hkv);
+    if (kv.int4) kv_append_kernel<true><<<grid, 128, 0, stream>>>(kv, (const uint16_t *)k, (const uint16_t *)v, append_indptr);
+    else kv_append_kernel<false><<<grid, 128, 0, stream>>>(kv, (const uint16_t *)k, (const uint16_t *)v, append_indptr);
     return hipGetLastError();
 }
 
-hipError_t launch_paged_decode(const void *q, const void *kv_data, const void *kv_param, bool int4, const int *kv_indptr, const int *kv_indices,
-                               const int *last_page_len, int B, int Hq, int Hkv, int max_pages, int L, int layer, int P, int max_seq_len,
-                               float sm_scale, void *ws, void *o, hipStream_t stream) {
+hipError_t launch_paged_decode(const PagedKV &kv, const void *q, int Hq, int max_seq_len, float sm_scale, void *ws, void *o,
+                               hipStream_t stream) {
     DecodeArgs a;
+    a.kv = kv;
     a.q = (const uint16_t *)q;
-    a.kv_data = (const uint8_t *)kv_data;
-    a.kv_param = (const __half *)kv_param;
-    a.kv_indptr = kv_indptr;
-    a.kv_indices = kv_indices;
-    a.last_page_len = last_page_len;
     a.ws = (float *)ws;
     a.o = (uint16_t *)o;
-    a.max_pages = max_pages;
-    a.L = L;
-    a.layer = layer;
-    a.Hkv = Hkv;
-    a.P = P;
-    a.B = B;
     a.Hq = Hq;
-    a.g = Hq / Hkv;
-    kv_decode_split(B, Hkv, max_seq_len, &a.nc, &a.chunk);
-    a.scale_log2 = sm_scale * 1.4426950408889634f;
-    hipError_t e = int4 ? launch_decode_g<true>(a, stream) : launch_decode_g<false>(a, stream);
+    a.g = Hq / kv.Hkv;
+    kv_decode_split(kv.B, kv.Hkv, max_seq_len, &a.nc, &a.chunk);
+    a.scale_log2 = kv_scale_log2(sm_scale);
+    hipError_t e = kv.int4 ? launch_decode_g<true>(a, stream) : launch_decode_g<false>(a, stream);
     if (e != hipSuccess || a.nc == 1) return e;
-    paged_decode_merge_kernel<<<dim3(Hq, B), 64, 0, stream>>>(a);
+    paged_decode_merge_kernel<<<dim3(Hq, kv.B), 64, 0, stream>>>(a);
     return hipGetLastError();
 }
 

@@ -23,15 +23,16 @@
 #include <stdint.h>
 
 #include "mx_kernels.h"
+#include "mx_paged_kv.h"
 
 namespace {
 
-typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
+using namespace mm::kv;       // the page-table walk, the int4 decoding and the chunk merge
+using mm::PagedKV;
+
 typedef unsigned v2u __attribute__((ext_vector_type(2)));
 typedef float v4f __attribute__((ext_vector_type(4)));
 
-constexpr int HD = 128;              // head_dim
 constexpr int ROWS = 64;             // MFMA rows (token, head) per workgroup
 constexpr int KT = 64;               // kv tokens per tile
 constexpr int NT = 256;              // threads per workgroup
@@ -39,52 +40,19 @@ constexpr int KSTR4 = 64 + 16;       // LDS row stride of an int4 K row (bytes)
 constexpr int KSTR16 = 256 + 16;     // LDS row stride of a bf16 K row (bytes)
 constexpr int VSTR = 2 * KT + 8;     // LDS row stride of the transposed V image (bytes)
 
-__device__ inline float bf16f(uint32_t bits16) { return __uint_as_float(bits16 << 16); }
-
-__device__ inline uint16_t f2bf_rne(float f) {    // finite inputs
-    const uint32_t u = __float_as_uint(f);
-    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-
-__device__ inline uint32_t pack_bf(float lo, float hi) { return (uint32_t)f2bf_rne(lo) | ((uint32_t)f2bf_rne(hi) << 16); }
-
-__device__ inline int seq_len(const int *kv_indptr, const int *last_page_len, int b, int P) {
-    const int np = kv_indptr[b + 1] - kv_indptr[b];
-    return np > 0 ? (np - 1) * P + min(max(last_page_len[b], 0), P) : 0;    // clamped: a bad entry never reads past the page list
-}
-
-// row index (in rows of one token-head) of K (kv = 0) or V (kv = 1) of `page`, `slot`
-__device__ inline int64_t kv_row(int page, int L, int layer, int kv, int Hkv, int h, int P, int slot) {
-    return ((((int64_t)page * L + layer) * 2 + kv) * Hkv + h) * P + slot;
-}
-
-// 8 int4 codes (one dword, element 2j in the low nibble of byte j) -> 8 bf16 values 16 + code (exact), MFMA operand order
-__device__ inline v8bf codes_to_bf16(uint32_t w) {
-    const uint32_t lo = w & 0x0f0f0f0fu, hi = (w >> 4) & 0x0f0f0f0fu;
-    v4u r;
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        const uint32_t sel = 0x0c000c00u | ((4u + m) << 16) | (uint32_t)m;  // byte0 = lo.byte m, byte2 = hi.byte m, bytes 1, 3 = 0
-        r[m] = (__builtin_amdgcn_perm(hi, lo, sel) << 3) | 0x41804180u;    // bf16 0x4180 | c << 3 = 16 + c
-    }
-    return __builtin_bit_cast(v8bf, r);
-}
-
 struct PrefillArgs {
+    PagedKV kv;
     const uint16_t *q;
     const int *qo_indptr;
-    const uint8_t *kv_data;
-    const __half *kv_param;
-    const int *kv_indptr, *kv_indices, *last_page_len;
     float *ws;                 // partials: o [tiles, Hkv, nc, 64, 128], then (m, l) [tiles, Hkv, nc, 64, 2]
     uint16_t *o;
-    int T, max_pages, L, layer, Hkv, P, B, Hq, g, bq, tiles, nc, chunk;
+    int T, Hq, g, bq, tiles, nc, chunk;
     float scale_log2;          // sm_scale * log2(e)
 };
 
 // (sequence, tile of it, its token count) of workgroup tile index i; false for a surplus tile
 __device__ inline bool tile_of(const PrefillArgs &a, int i, int &b, int &j, int &q0, int &n) {
-    int lo = 0, hi = a.B;                         // the largest b with start(b) = qo_indptr[b] / bq + b <= i
+    int lo = 0, hi = a.kv.B;                         // the largest b with start(b) = qo_indptr[b] / bq + b <= i
     while (hi - lo > 1) {
         const int mid = (lo + hi) >> 1;
         if (min(max(a.qo_indptr[mid], 0), a.T) / a.bq + mid <= i) lo = mid; else hi = mid;
@@ -109,9 +77,10 @@ __global__ __launch_bounds__(NT) void paged_prefill_kernel(const PrefillArgs a) 
     int b, j, q0, n;
     if (!tile_of(a, tile, b, j, q0, n)) return;
     const int tid = threadIdx.x, wave = tid >> 6, l = tid & 63, c = l & 15, kq = l >> 4;
-    const int g = a.g, P = a.P;
-    const int len = seq_len(a.kv_indptr, a.last_page_len, b, P);
-    const int *pages = a.kv_indices + a.kv_indptr[b];
+    const PagedKV &kv = a.kv;
+    const int g = a.g;
+    const int len = seq_len(kv, b);
+    const int *pages = kv.indices + kv.indptr[b];
     const int ntok = min(a.bq, n - j * a.bq);             // query tokens of this tile
     const int pos0 = len - n + j * a.bq;                   // position of its first token
     const int pmax = pos0 + ntok - 1;                      // the last position any row attends
@@ -158,22 +127,19 @@ __global__ __launch_bounds__(NT) void paged_prefill_kernel(const PrefillArgs a) 
     auto load = [&](int kt) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            const int t = kt + 4 * tg + u;
-            const int page = t < len ? pages[t / P] : -1;
-            const bool ok = page >= 0 && page < a.max_pages;
-            okreg[u] = ok;
-            const int64_t rk = ok ? kv_row(page, a.L, a.layer, 0, a.Hkv, kvh, P, t % P) : 0;
-            const int64_t rv = rk + (int64_t)a.Hkv * P;
+            int64_t rk;
+            const bool ok = okreg[u] = k_row(kv, pages, kt + 4 * tg + u, len, kvh, rk);
+            const int64_t rv = rk + v_offset(kv);
             if (INT4) {
-                vreg[u].x = ok ? *(const uint32_t *)(a.kv_data + rv * (HD / 2) + 4 * dg) : 0u;
-                if (u == uk) kreg[0] = ok ? *(const v4u *)(a.kv_data + rk * (HD / 2) + 16 * kpart) : v4u{0, 0, 0, 0};
-                if (dg < 2) preg[u] = ok ? *(const uint32_t *)(a.kv_param + (dg ? rv : rk) * 2) : 0u;
+                vreg[u].x = ok ? *(const uint32_t *)(kv.data + rv * (HD / 2) + 4 * dg) : 0u;
+                if (u == uk) kreg[0] = ok ? *(const v4u *)(kv.data + rk * (HD / 2) + 16 * kpart) : v4u{0, 0, 0, 0};
+                if (dg < 2) preg[u] = ok ? *(const uint32_t *)(kv.param + (dg ? rv : rk) * 2) : 0u;
             } else {
-                vreg[u] = ok ? *(const v4u *)(a.kv_data + rv * (HD * 2) + 16 * dg) : v4u{0, 0, 0, 0};
+                vreg[u] = ok ? *(const v4u *)(kv.data + rv * (HD * 2) + 16 * dg) : v4u{0, 0, 0, 0};
                 if (u == uk) {
 #pragma unroll
                     for (int s = 0; s < 4; ++s)
-                        kreg[s] = ok ? *(const v4u *)(a.kv_data + rk * (HD * 2) + 64 * kpart + 16 * s) : v4u{0, 0, 0, 0};
+                        kreg[s] = ok ? *(const v4u *)(kv.data + rk * (HD * 2) + 64 * kpart + 16 * s) : v4u{0, 0, 0, 0};
                 }
             }
         }
@@ -201,8 +167,7 @@ __global__ __launch_bounds__(NT) void paged_prefill_kernel(const PrefillArgs a) 
             if (dg < 2) {
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
-                    const float s = __half2float(__ushort_as_half((unsigned short)(preg[u] & 0xffffu)));
-                    const float z = __half2float(__ushort_as_half((unsigned short)(preg[u] >> 16)));
+                    const float s = scale_of(preg[u]), z = zero_of(preg[u]);
                     const int t = 4 * tg + u;
                     if (dg == 0) {
                         s_ks[t] = okreg[u] ? s * a.scale_log2 : 0.0f;
@@ -341,42 +306,31 @@ __global__ __launch_bounds__(NT) void paged_prefill_kernel(const PrefillArgs a) 
             *(v2u *)(orow + 16 * dt) = w;
         }
     } else {
-        const int64_t part = (((int64_t)tile * a.Hkv + kvh) * a.nc + chunk) * ROWS + row;
+        const int64_t part = (((int64_t)tile * kv.Hkv + kvh) * a.nc + chunk) * ROWS + row;
         float *op = a.ws + part * HD + 4 * kq;
 #pragma unroll
         for (int dt = 0; dt < 8; ++dt) *(v4f *)(op + 16 * dt) = o[dt] - pz;
-        if (kq == 0) *(float2 *)(a.ws + (int64_t)a.tiles * a.Hkv * a.nc * ROWS * HD + part * 2) = make_float2(m, lsum);
+        if (kq == 0) *(float2 *)(a.ws + (int64_t)a.tiles * kv.Hkv * a.nc * ROWS * HD + part * 2) = make_float2(m, lsum);
     }
 }
 
-// combines the nc chunk partials of the rows of one (tile, kv head); a chunk without attended tokens has m = -inf and l = 0
+// combines the nc chunk partials of the rows of one (tile, kv head)
 __global__ __launch_bounds__(NT) void paged_prefill_merge_kernel(const PrefillArgs a) {
     const int tile = blockIdx.x, kvh = blockIdx.y;
     int b, j, q0, n;
     if (!tile_of(a, tile, b, j, q0, n)) return;
     const int rows = min(a.bq, n - j * a.bq) * a.g;
-    const int64_t first = ((int64_t)tile * a.Hkv + kvh) * a.nc * ROWS;     // part index of chunk 0, row 0; chunk stride ROWS
-    const float *ml = a.ws + (int64_t)a.tiles * a.Hkv * a.nc * ROWS * HD;
+    const int64_t first = ((int64_t)tile * a.kv.Hkv + kvh) * a.nc * ROWS;     // part index of chunk 0, row 0; chunk stride ROWS
+    const float *ml = a.ws + (int64_t)a.tiles * a.kv.Hkv * a.nc * ROWS * HD;
     for (int idx = threadIdx.x; idx < rows * (HD / 4); idx += NT) {
         const int row = idx / (HD / 4), d = 4 * (idx % (HD / 4));
-        float M = -INFINITY;
-        for (int c = 0; c < a.nc; ++c) M = fmaxf(M, ml[(first + (int64_t)c * ROWS + row) * 2]);
-        float ls = 0.0f;
-        v4f acc = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (M != -INFINITY) {
-            for (int c = 0; c < a.nc; ++c) {
-                const int64_t part = first + (int64_t)c * ROWS + row;
-                const float f = exp2f(ml[part * 2] - M);
-                ls += f * ml[part * 2 + 1];
-                acc += f * *(const v4f *)(a.ws + part * HD + d);
-            }
-        }
-        const float inv = ls > 0.0f ? 1.0f / ls : 0.0f;
+        float o[4];
+        merge_chunks<4>(ml, a.ws + d, first + row, ROWS, a.nc, o);
         const int rt = row / a.g, rh = row - rt * a.g;
         const int64_t qrow = (int64_t)(q0 + j * a.bq + rt) * a.Hq + (int64_t)kvh * a.g + rh;
         v2u w;
-        w.x = pack_bf(acc[0] * inv, acc[1] * inv);
-        w.y = pack_bf(acc[2] * inv, acc[3] * inv);
+        w.x = pack_bf(o[0], o[1]);
+        w.y = pack_bf(o[2], o[3]);
         *(v2u *)(a.o + qrow * HD + d) = w;
     }
 }
@@ -386,22 +340,10 @@ __global__ __launch_bounds__(NT) void paged_prefill_merge_kernel(const PrefillAr
 namespace mm {
 
 void kv_prefill_split(int T, int B, int Hq, int Hkv, int max_seq_len, int *tiles, int *nc, int *chunk) {
-    // tiles: an upper bound on sum ceil(n_b / BQ), BQ = 64 / g query tokens per tile.  Chunks: enough workgroups for four per CU of
-    // the 256 on an MI355X, chunks of at least 256 tokens; host-known values only, so a captured graph stays valid while the
-    // sequences grow up to max_seq_len
+    // tiles: an upper bound on sum ceil(n_b / BQ), BQ = 64 / g query tokens per tile.  Chunks: four workgroups per CU of the 256 on an MI355X
     const int g = Hkv > 0 && Hq >= Hkv ? Hq / Hkv : 1;
-    const int bq = ROWS / (g > 0 && g <= ROWS ? g : 1);
-    *tiles = T / bq + B;
-    const long long work = (long long)(*tiles > 0 ? *tiles : 1) * (Hkv > 0 ? Hkv : 1);
-    const long long want = work >= 1024 ? 1 : (1024 + work - 1) / work;
-    const int most = (max_seq_len + 255) / 256;
-    int n = want < most ? (int)want : most;
-    if (n < 1) n = 1;
-    int cl = (max_seq_len + n - 1) / n;
-    cl = (cl + KT - 1) / KT * KT;
-    if (cl < KT) cl = KT;
-    *chunk = cl;
-    *nc = max_seq_len > 0 ? (max_seq_len + cl - 1) / cl : 1;
+    *tiles = T / (ROWS / (g > 0 && g <= ROWS ? g : 1)) + B;
+    kv_chunks((long long)(*tiles > 0 ? *tiles : 1) * (Hkv > 0 ? Hkv : 1), 1024, max_seq_len, KT, nc, chunk);
 }
 
 size_t kv_prefill_workspace_bytes(int T, int B, int Hq, int Hkv, int max_seq_len) {
@@ -410,37 +352,26 @@ size_t kv_prefill_workspace_bytes(int T, int B, int Hq, int Hkv, int max_seq_len
     return nc > 1 ? (size_t)tiles * Hkv * nc * ROWS * (HD + 2) * sizeof(float) : 0;
 }
 
-hipError_t launch_paged_prefill(const void *q, const int *qo_indptr, int T, const void *kv_data, const void *kv_param, bool int4,
-                                const int *kv_indptr, const int *kv_indices, const int *last_page_len, int B, int Hq, int Hkv, int max_pages,
-                                int L, int layer, int P, int max_seq_len, float sm_scale, void *ws, void *o, hipStream_t stream) {
+hipError_t launch_paged_prefill(const PagedKV &kv, const void *q, const int *qo_indptr, int T, int Hq, int max_seq_len, float sm_scale,
+                                void *ws, void *o, hipStream_t stream) {
     PrefillArgs a;
+    a.kv = kv;
     a.q = (const uint16_t *)q;
     a.qo_indptr = qo_indptr;
-    a.kv_data = (const uint8_t *)kv_data;
-    a.kv_param = (const __half *)kv_param;
-    a.kv_indptr = kv_indptr;
-    a.kv_indices = kv_indices;
-    a.last_page_len = last_page_len;
     a.ws = (float *)ws;
     a.o = (uint16_t *)o;
     a.T = T;
-    a.max_pages = max_pages;
-    a.L = L;
-    a.layer = layer;
-    a.Hkv = Hkv;
-    a.P = P;
-    a.B = B;
     a.Hq = Hq;
-    a.g = Hq / Hkv;
+    a.g = Hq / kv.Hkv;
     a.bq = ROWS / a.g;
-    kv_prefill_split(T, B, Hq, Hkv, max_seq_len, &a.tiles, &a.nc, &a.chunk);
-    a.scale_log2 = sm_scale * 1.4426950408889634f;
-    const dim3 grid(a.tiles, Hkv, a.nc);
-    if (int4) paged_prefill_kernel<true><<<grid, NT, 0, stream>>>(a);
+    kv_prefill_split(T, kv.B, Hq, kv.Hkv, max_seq_len, &a.tiles, &a.nc, &a.chunk);
+    a.scale_log2 = kv_scale_log2(sm_scale);
+    const dim3 grid(a.tiles, kv.Hkv, a.nc);
+    if (kv.int4) paged_prefill_kernel<true><<<grid, NT, 0, stream>>>(a);
     else paged_prefill_kernel<false><<<grid, NT, 0, stream>>>(a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || a.nc == 1) return e;
-    paged_prefill_merge_kernel<<<dim3(a.tiles, Hkv), NT, 0, stream>>>(a);
+    paged_prefill_merge_kernel<<<dim3(a.tiles, kv.Hkv), NT, 0, stream>>>(a);
     return hipGetLastError();
 }
 

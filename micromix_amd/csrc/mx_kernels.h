@@ -179,19 +179,28 @@ size_t mx_gemm_workspace_bytes(int M, int N, const int K[3], bool w4, bool force
 bool mx_gemm_small_m_uses_tiles(int M, int N, const int K[3], bool w4, size_t ws_bytes, bool force_split);
 const char *describe_mx_gemm256(int M, int N, const int K[3], bool w4, size_t ws_bytes, bool force_split, bool tickets_zeroed, bool out_f32 = false);   // thread-local buffer  // 0 when mm_matmul would not split K for this shape
 
-// paged KV cache (kv_cache.hip)
-void kv_decode_split(int B, int Hkv, int max_seq_len, int *nc, int *chunk);     // chunks of mm_paged_decode (host-known values only)
-hipError_t launch_kv_append(void *kv_data, void *kv_param, bool int4, const int *kv_indptr, const int *kv_indices, const int *last_page_len,
-                            int B, const void *k, const void *v, const int *append_indptr, int T, int max_pages, int L, int layer, int Hkv,
-                            int P, hipStream_t stream);
-hipError_t launch_paged_decode(const void *q, const void *kv_data, const void *kv_param, bool int4, const int *kv_indptr, const int *kv_indices,
-                               const int *last_page_len, int B, int Hq, int Hkv, int max_pages, int L, int layer, int P, int max_seq_len,
-                               float sm_scale, void *ws, void *o, hipStream_t stream);
+// paged KV cache: one layer of a cache and the page table of its B sequences (layout: kv_cache.hip; device side: mx_paged_kv.h)
+struct PagedKV {
+    uint8_t *data;
+    uint16_t *param;           // int4 only: fp16 (scale, zero) per row
+    const int *indptr, *indices, *last_page_len;
+    int max_pages, L, layer, Hkv, P, B;
+    bool int4;
+};
+constexpr float KV_DEFAULT_SM_SCALE = 0.08838834764831845f;                // 1 / sqrt(128)
+inline float kv_scale_log2(float sm_scale) { return (sm_scale > 0.0f ? sm_scale : KV_DEFAULT_SM_SCALE) * 1.4426950408889634f; }
+// split-KV chunks, from host-known values only, so a captured graph stays valid while the sequences grow up to max_seq_len: enough
+// chunks of `work` items to reach target_workgroups, of at least 256 tokens each, the chunk length a multiple of round_to
+void kv_chunks(long long work, int target_workgroups, int max_seq_len, int round_to, int *nc, int *chunk);
+// append and single-token attention (kv_cache.hip)
+void kv_decode_split(int B, int Hkv, int max_seq_len, int *nc, int *chunk);
+size_t kv_decode_workspace_bytes(int B, int Hq, int Hkv, int max_seq_len);
+hipError_t launch_kv_append(const PagedKV &kv, const void *k, const void *v, const int *append_indptr, int T, hipStream_t stream);
+hipError_t launch_paged_decode(const PagedKV &kv, const void *q, int Hq, int max_seq_len, float sm_scale, void *ws, void *o,
+                               hipStream_t stream);
 // RoPE + append in one launch (rope_append.hip): q | k | v share the token stride qkv_stride, cos | sin the stride cs_stride (elements)
-hipError_t launch_rope_kv_append(void *kv_data, void *kv_param, bool int4, const int *kv_indptr, const int *kv_indices,
-                                 const int *last_page_len, int B, const void *q, const void *k, const void *v, int64_t qkv_stride, int Hq,
-                                 const void *cos, const void *sin, int64_t cs_stride, const int *append_indptr, int T, void *q_out,
-                                 int max_pages, int L, int layer, int Hkv, int P, hipStream_t stream);
+hipError_t launch_rope_kv_append(const PagedKV &kv, const void *q, const void *k, const void *v, int64_t qkv_stride, int Hq, const void *cos,
+                                 const void *sin, int64_t cs_stride, const int *append_indptr, int T, void *q_out, hipStream_t stream);
 // sparse MoE block around the grouped GEMMs (moe.hip): n = T * top_k pairs, H a multiple of 8, rows 16-byte aligned
 hipError_t launch_moe_route(const void *logits, int T, int E, int top_k, int *ids, void *w, hipStream_t stream);
 hipError_t launch_moe_plan(const int *ids, int n, int E, int top_k, int *offsets, int *sorted_token, int *slot_of, hipStream_t stream);
@@ -199,10 +208,9 @@ hipError_t launch_moe_gather(const void *x, const int *sorted_token, int T, int 
 hipError_t launch_moe_combine(const void *y, const int *ids, const void *w, const int *slot_of, int T, int top_k, int H, void *out,
                               hipStream_t stream);
 // causal multi-token attention over the paged cache (kv_prefill.hip)
-void kv_prefill_split(int T, int B, int Hq, int Hkv, int max_seq_len, int *tiles, int *nc, int *chunk);   // host-known values only
+void kv_prefill_split(int T, int B, int Hq, int Hkv, int max_seq_len, int *tiles, int *nc, int *chunk);
 size_t kv_prefill_workspace_bytes(int T, int B, int Hq, int Hkv, int max_seq_len);
-hipError_t launch_paged_prefill(const void *q, const int *qo_indptr, int T, const void *kv_data, const void *kv_param, bool int4,
-                                const int *kv_indptr, const int *kv_indices, const int *last_page_len, int B, int Hq, int Hkv, int max_pages,
-                                int L, int layer, int P, int max_seq_len, float sm_scale, void *ws, void *o, hipStream_t stream);
+hipError_t launch_paged_prefill(const PagedKV &kv, const void *q, const int *qo_indptr, int T, int Hq, int max_seq_len, float sm_scale,
+                                void *ws, void *o, hipStream_t stream);
 
 }  // namespace mm

@@ -1,6 +1,6 @@
 // RoPE + paged KV append in one launch (include/micromix_hip.h, mm_rope_kv_append): reads q | k | v as the fused q/k/v projection leaves
 // them (three pointers, one token stride), rotates q and K by the caller's bf16 cos / sin rows, writes the rotated q contiguous and the
-// rotated K and V into the cache by the slot rule and the int4 rule of mm_kv_append (mx_kv_append.h: the same code).
+// rotated K and V into the cache by the slot rule and the int4 rule of mm_kv_append (mx_paged_kv.h: the same code).
 //
 // RoPE is HF's apply_rotary_pos_emb in bf16 tensor arithmetic, x * cos + rotate_half(x) * sin with every op rounded to bf16:
 //   a = bf16(x[d] * cos[d]);  b = bf16((d < 64 ? -x[d + 64] : x[d - 64]) * sin[d]);  y[d] = bf16(a + b)
@@ -14,22 +14,21 @@
 #include <stdint.h>
 
 #include "mx_kernels.h"
-#include "mx_kv_append.h"
+#include "mx_paged_kv.h"
 
 namespace {
 
-using namespace mm::kva;
+using namespace mm::kv;
 
 constexpr int MAX_Q_WAVES = 6;     // query heads beyond these are taken in further rounds (no limit on g)
 
 struct RopeArgs {
-    uint8_t *kv_data;
-    __half *kv_param;
-    const int *kv_indptr, *kv_indices, *last_page_len, *append_indptr;
+    mm::PagedKV kv;
+    const int *append_indptr;
     const uint16_t *q, *k, *v, *cos, *sin;
     uint16_t *q_out;
     int64_t qkv_stride, cs_stride;     // elements per token
-    int B, max_pages, L, layer, Hkv, P, Hq, g;
+    int Hq, g;
 };
 
 // bf16(bf16(x * c) + bf16(r * s)) for one element
@@ -53,18 +52,16 @@ __global__ __launch_bounds__(64 * (2 + MAX_Q_WAVES)) void rope_kv_append_kernel(
     const int64_t in = (int64_t)i * a.qkv_stride;
     if (wave == 1) {                                          // V: as mm_kv_append
         const uint32_t two = ((const uint32_t *)(a.v + in + (int64_t)h * HD))[lane];
-        const int64_t row = append_row(a.kv_indptr, a.kv_indices, a.last_page_len, a.append_indptr, a.B, i, a.max_pages, a.L, a.layer, 1,
-                                       a.Hkv, h, a.P);
-        if (row >= 0) store_row<INT4>(a.kv_data, a.kv_param, row, lane, two);
+        const int64_t row = append_row(a.kv, a.append_indptr, i, 1, h);
+        if (row >= 0) store_row<INT4>(a.kv, row, lane, two);
         return;
     }
     const uint32_t cs = ((const uint32_t *)(a.cos + (int64_t)i * a.cs_stride))[lane];
     const uint32_t sn = ((const uint32_t *)(a.sin + (int64_t)i * a.cs_stride))[lane];
     if (wave == 0) {                                          // K
         const uint32_t two = rope_pair(((const uint32_t *)(a.k + in + (int64_t)h * HD))[lane], cs, sn, lane);
-        const int64_t row = append_row(a.kv_indptr, a.kv_indices, a.last_page_len, a.append_indptr, a.B, i, a.max_pages, a.L, a.layer, 0,
-                                       a.Hkv, h, a.P);
-        if (row >= 0) store_row<INT4>(a.kv_data, a.kv_param, row, lane, two);
+        const int64_t row = append_row(a.kv, a.append_indptr, i, 0, h);
+        if (row >= 0) store_row<INT4>(a.kv, row, lane, two);
         return;
     }
     // q: every token, whatever its cache slot
@@ -72,7 +69,9 @@ __global__ __launch_bounds__(64 * (2 + MAX_Q_WAVES)) void rope_kv_append_kernel(
     for (int j = wave - 2; j < a.g; j += nq) {
         const int hq = h * a.g + j;
         const uint32_t two = ((const uint32_t *)(a.q + in + (int64_t)hq * HD))[lane];
-        ((uint32_t *)(a.q_out + ((int64_t)i * a.Hq + hq) * HD))[lane] = rope_pair(two, cs, sn, lane);
+        // stored as a float: a store of an integer type here may alias the page table for all the compiler knows, and then wave 0 and
+        // wave 1 read the table (append_row) with vector loads instead of scalar ones (7 % of the launch at T = 4096)
+        ((float *)(a.q_out + ((int64_t)i * a.Hq + hq) * HD))[lane] = __uint_as_float(rope_pair(two, cs, sn, lane));
     }
 }
 
@@ -80,16 +79,10 @@ __global__ __launch_bounds__(64 * (2 + MAX_Q_WAVES)) void rope_kv_append_kernel(
 
 namespace mm {
 
-hipError_t launch_rope_kv_append(void *kv_data, void *kv_param, bool int4, const int *kv_indptr, const int *kv_indices,
-                                 const int *last_page_len, int B, const void *q, const void *k, const void *v, int64_t qkv_stride, int Hq,
-                                 const void *cos, const void *sin, int64_t cs_stride, const int *append_indptr, int T, void *q_out,
-                                 int max_pages, int L, int layer, int Hkv, int P, hipStream_t stream) {
+hipError_t launch_rope_kv_append(const PagedKV &kv, const void *q, const void *k, const void *v, int64_t qkv_stride, int Hq, const void *cos,
+                                 const void *sin, int64_t cs_stride, const int *append_indptr, int T, void *q_out, hipStream_t stream) {
     RopeArgs a;
-    a.kv_data = (uint8_t *)kv_data;
-    a.kv_param = (__half *)kv_param;
-    a.kv_indptr = kv_indptr;
-    a.kv_indices = kv_indices;
-    a.last_page_len = last_page_len;
+    a.kv = kv;
     a.append_indptr = append_indptr;
     a.q = (const uint16_t *)q;
     a.k = (const uint16_t *)k;
@@ -99,17 +92,11 @@ hipError_t launch_rope_kv_append(void *kv_data, void *kv_param, bool int4, const
     a.q_out = (uint16_t *)q_out;
     a.qkv_stride = qkv_stride;
     a.cs_stride = cs_stride;
-    a.B = B;
-    a.max_pages = max_pages;
-    a.L = L;
-    a.layer = layer;
-    a.Hkv = Hkv;
-    a.P = P;
     a.Hq = Hq;
-    a.g = Hq / Hkv;
-    const dim3 grid(T, Hkv);
+    a.g = Hq / kv.Hkv;
+    const dim3 grid(T, kv.Hkv);
     const int threads = 64 * (2 + (a.g < MAX_Q_WAVES ? a.g : MAX_Q_WAVES));
-    if (int4) rope_kv_append_kernel<true><<<grid, threads, 0, stream>>>(a);
+    if (kv.int4) rope_kv_append_kernel<true><<<grid, threads, 0, stream>>>(a);
     else rope_kv_append_kernel<false><<<grid, threads, 0, stream>>>(a);
     return hipGetLastError();
 }

@@ -865,6 +865,46 @@ def _page_table(kv_indptr, kv_indices, last_page_len, dev):
     return B
 
 
+def _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, q=None):
+    """The common checks of the four cache ops: (device, B, Hkv, the C arguments kv_data .. batch that every entry point takes in this
+    order).  The device is q's (bf16, contiguous); an append has no q and takes the cache's."""
+    if q is None:
+        if not (isinstance(kv_data, torch.Tensor) and kv_data.is_cuda):
+            _check_tensor(kv_data, "kv_data", torch.uint8 if kv_param is not None else torch.bfloat16)
+        dev = kv_data.device
+    else:
+        if not (isinstance(q, torch.Tensor) and q.is_cuda and _ok(q, torch.bfloat16, q.get_device())):
+            _check_tensor(q, "q", torch.bfloat16)
+        dev = q.device
+    kind, max_pages, L, Hkv, P = _kv_geometry(kv_data, kv_param, dev.index)
+    B = _page_table(kv_indptr, kv_indices, last_page_len, dev)
+    layer_idx = int(layer_idx)
+    if not 0 <= layer_idx < L:
+        raise RuntimeError(f"layer_idx {layer_idx} outside the cache's {L} layers")
+    return dev, B, Hkv, (_ptr(kv_data), _ptr(kv_param) if kv_param is not None else None, kind, max_pages, L, layer_idx, Hkv, P, 128,
+                         _ptr(kv_indptr), _ptr(kv_indices), _ptr(last_page_len), B)
+
+
+def _kv_workspace(workspace, need, dev):
+    """(the split-KV scratch, which the caller holds across the launch, its two C arguments): allocated when `need` bytes are wanted and
+    none was passed"""
+    if not need:
+        return None, (None, 0)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+    if (not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or workspace.device != dev
+            or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need):
+        raise RuntimeError(f"workspace must be a contiguous device tensor of at least {need} bytes on {dev}")
+    return workspace, (_ptr(workspace), workspace.numel() * workspace.element_size())
+
+
+def _sm_scale(sm_scale):
+    scale = float(sm_scale) if sm_scale is not None else 128 ** -0.5
+    if not scale > 0:
+        raise ValueError("sm_scale must be positive")
+    return scale
+
+
 def kv_append(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, k, v, append_indptr, layer_idx):
     """Write T new tokens' K and V (bf16 [T, Hkv, 128]) into layer `layer_idx` of a paged cache, in place.
 
@@ -874,11 +914,7 @@ def kv_append(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, k, v, app
     (scale, zero) by the rule of quantize_int_group(x, 4, 128) (include/micromix_hip.h).  Runs on the current stream, capture-safe.
     """
     lib = _lib.load()
-    if not (isinstance(kv_data, torch.Tensor) and kv_data.is_cuda):
-        _check_tensor(kv_data, "kv_data", torch.uint8 if kv_param is not None else torch.bfloat16)
-    dev = kv_data.device
-    kind, max_pages, L, Hkv, P = _kv_geometry(kv_data, kv_param, dev.index)
-    B = _page_table(kv_indptr, kv_indices, last_page_len, dev)
+    dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx)
     if not _ok(append_indptr, torch.int32, dev.index):
         _check_tensor(append_indptr, "append_indptr", torch.int32, dev)
     for n, t in (("k", k), ("v", v)):
@@ -888,13 +924,8 @@ def kv_append(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, k, v, app
         raise RuntimeError(f"k and v must both be [T, {Hkv}, 128] bf16")
     if append_indptr.numel() != B + 1:
         raise RuntimeError("append_indptr must have B + 1 entries")
-    layer_idx = int(layer_idx)
-    if not 0 <= layer_idx < L:
-        raise RuntimeError(f"layer_idx {layer_idx} outside the cache's {L} layers")
     with _on_device(dev.index):
-        st = lib.mm_kv_append(_ptr(kv_data), _ptr(kv_param) if kv_param is not None else None, kind, max_pages, L, layer_idx, Hkv, P, 128,
-                              _ptr(kv_indptr), _ptr(kv_indices), _ptr(last_page_len), B, _ptr(k), _ptr(v), _ptr(append_indptr),
-                              k.size(0), _stream_ptr(dev))
+        st = lib.mm_kv_append(*kv_args, _ptr(k), _ptr(v), _ptr(append_indptr), k.size(0), _stream_ptr(dev))
     if st:
         _lib.check(st, "kv_append")
 
@@ -927,11 +958,7 @@ def rope_kv_append(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, q, k
     token.  Page table and append_indptr as in `kv_append`.  Runs on the current stream, capture-safe.
     """
     lib = _lib.load()
-    if not (isinstance(kv_data, torch.Tensor) and kv_data.is_cuda):
-        _check_tensor(kv_data, "kv_data", torch.uint8 if kv_param is not None else torch.bfloat16)
-    dev = kv_data.device
-    kind, max_pages, L, Hkv, P = _kv_geometry(kv_data, kv_param, dev.index)
-    B = _page_table(kv_indptr, kv_indices, last_page_len, dev)
+    dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx)
     if not _ok(append_indptr, torch.int32, dev.index):
         _check_tensor(append_indptr, "append_indptr", torch.int32, dev)
     if append_indptr.numel() != B + 1:
@@ -960,14 +987,10 @@ def rope_kv_append(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, q, k
     if not (cos.stride(1) == 1 and sin.stride(1) == 1 and (T <= 1 or sin.stride(0) == sc) and sc >= 128 and sc % 2 == 0
             and cos.data_ptr() % 4 == 0 and sin.data_ptr() % 4 == 0):
         cos, sin, sc = cos.contiguous(), sin.contiguous(), 128
-    layer_idx = int(layer_idx)
-    if not 0 <= layer_idx < L:
-        raise RuntimeError(f"layer_idx {layer_idx} outside the cache's {L} layers")
     q_rot = torch.empty((T, Hq, 128), dtype=torch.bfloat16, device=dev)
     with _on_device(dev.index):
-        st = lib.mm_rope_kv_append(_ptr(kv_data), _ptr(kv_param) if kv_param is not None else None, kind, max_pages, L, layer_idx, Hkv, P, 128,
-                                   _ptr(kv_indptr), _ptr(kv_indices), _ptr(last_page_len), B, _ptr(q), _ptr(k), _ptr(v), sq, Hq,
-                                   _ptr(cos), _ptr(sin), sc, _ptr(append_indptr), T, _ptr(q_rot), _stream_ptr(dev))
+        st = lib.mm_rope_kv_append(*kv_args, _ptr(q), _ptr(k), _ptr(v), sq, Hq, _ptr(cos), _ptr(sin), sc, _ptr(append_indptr), T,
+                                   _ptr(q_rot), _stream_ptr(dev))
     if st:
         _lib.check(st, "rope_kv_append")
     return q_rot
@@ -987,36 +1010,21 @@ def paged_decode(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, lay
     least paged_decode_workspace_bytes(...) bytes) is allocated here when None -- pass one when capturing a graph.
     """
     lib = _lib.load()
-    if not (isinstance(q, torch.Tensor) and q.is_cuda and _ok(q, torch.bfloat16, q.get_device())):
-        _check_tensor(q, "q", torch.bfloat16)
-    dev = q.device
-    kind, max_pages, L, Hkv, P = _kv_geometry(kv_data, kv_param, dev.index)
-    B = _page_table(kv_indptr, kv_indices, last_page_len, dev)
+    dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, q)
     if q.dim() != 3 or q.size(0) != B or q.size(2) != 128:
         raise RuntimeError(f"q must be [B = {B}, Hq, 128] bf16")
     Hq = q.size(1)
     if Hq % Hkv:
         raise RuntimeError(f"the {Hq} query heads are not a multiple of the cache's {Hkv} kv heads")
-    layer_idx, max_seq_len = int(layer_idx), int(max_seq_len)
-    if not 0 <= layer_idx < L:
-        raise RuntimeError(f"layer_idx {layer_idx} outside the cache's {L} layers")
+    max_seq_len = int(max_seq_len)
     if max_seq_len < 0:
         raise RuntimeError("max_seq_len must be >= 0")
     need = paged_decode_workspace_bytes(B, Hq, Hkv, max_seq_len) if B else 0
-    if need and workspace is None:
-        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
-    if need and (not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or workspace.device != dev
-                 or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need):
-        raise RuntimeError(f"workspace must be a contiguous device tensor of at least {need} bytes on {dev}")
+    workspace, ws_args = _kv_workspace(workspace, need, dev)
     o = torch.empty((B, Hq, 128), dtype=torch.bfloat16, device=dev)
-    scale = float(sm_scale) if sm_scale is not None else 128 ** -0.5
-    if not scale > 0:
-        raise ValueError("sm_scale must be positive")
+    scale = _sm_scale(sm_scale)
     with _on_device(dev.index):
-        st = lib.mm_paged_decode(_ptr(q), _ptr(kv_data), _ptr(kv_param) if kv_param is not None else None, kind, max_pages, L, layer_idx,
-                                 Hkv, P, 128, _ptr(kv_indptr), _ptr(kv_indices), _ptr(last_page_len), B, Hq, max_seq_len, scale,
-                                 _ptr(workspace) if need else None, workspace.numel() * workspace.element_size() if need else 0,
-                                 _ptr(o), _stream_ptr(dev))
+        st = lib.mm_paged_decode(_ptr(q), *kv_args, Hq, max_seq_len, scale, *ws_args, _ptr(o), _stream_ptr(dev))
     if st:
         _lib.check(st, "paged_decode")
     return o
@@ -1039,11 +1047,7 @@ def paged_prefill(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, qo
     paged_prefill_workspace_bytes(...) bytes) is allocated here when None -- pass one when capturing a graph.
     """
     lib = _lib.load()
-    if not (isinstance(q, torch.Tensor) and q.is_cuda and _ok(q, torch.bfloat16, q.get_device())):
-        _check_tensor(q, "q", torch.bfloat16)
-    dev = q.device
-    kind, max_pages, L, Hkv, P = _kv_geometry(kv_data, kv_param, dev.index)
-    B = _page_table(kv_indptr, kv_indices, last_page_len, dev)
+    dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, q)
     if not _ok(qo_indptr, torch.int32, dev.index):
         _check_tensor(qo_indptr, "qo_indptr", torch.int32, dev)
     if qo_indptr.numel() != B + 1:
@@ -1053,26 +1057,15 @@ def paged_prefill(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, qo
     T, Hq = q.size(0), q.size(1)
     if Hq % Hkv:
         raise RuntimeError(f"the {Hq} query heads are not a multiple of the cache's {Hkv} kv heads")
-    layer_idx, max_seq_len = int(layer_idx), int(max_seq_len)
-    if not 0 <= layer_idx < L:
-        raise RuntimeError(f"layer_idx {layer_idx} outside the cache's {L} layers")
+    max_seq_len = int(max_seq_len)
     if max_seq_len < 0:
         raise RuntimeError("max_seq_len must be >= 0")
     need = paged_prefill_workspace_bytes(T, B, Hq, Hkv, max_seq_len) if B and T else 0
-    if need and workspace is None:
-        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
-    if need and (not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or workspace.device != dev
-                 or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need):
-        raise RuntimeError(f"workspace must be a contiguous device tensor of at least {need} bytes on {dev}")
+    workspace, ws_args = _kv_workspace(workspace, need, dev)
     o = torch.empty((T, Hq, 128), dtype=torch.bfloat16, device=dev)
-    scale = float(sm_scale) if sm_scale is not None else 128 ** -0.5
-    if not scale > 0:
-        raise ValueError("sm_scale must be positive")
+    scale = _sm_scale(sm_scale)
     with _on_device(dev.index):
-        st = lib.mm_paged_prefill(_ptr(q), _ptr(qo_indptr), T, _ptr(kv_data), _ptr(kv_param) if kv_param is not None else None, kind,
-                                  max_pages, L, layer_idx, Hkv, P, 128, _ptr(kv_indptr), _ptr(kv_indices), _ptr(last_page_len), B, Hq,
-                                  max_seq_len, scale, _ptr(workspace) if need else None,
-                                  workspace.numel() * workspace.element_size() if need else 0, _ptr(o), _stream_ptr(dev))
+        st = lib.mm_paged_prefill(_ptr(q), _ptr(qo_indptr), T, *kv_args, Hq, max_seq_len, scale, *ws_args, _ptr(o), _stream_ptr(dev))
     if st:
         _lib.check(st, "paged_prefill")
     return o
