@@ -85,6 +85,8 @@ class SparseMoEBlock(nn.Module):
     @torch.no_grad()
     def forward(self, hidden):
         shape, H, E = hidden.shape, self.hidden_dim, self.num_experts
+        if hidden.dim() < 1 or hidden.size(-1) != H:          # (a width that H divides would otherwise reshape into other tokens)
+            raise ValueError(f"hidden must be [.., H = {H}], got {tuple(shape)}")
         x = hidden.reshape(-1, H).contiguous()
         router_logits = F.linear(x, self.gate_weight, self.gate_bias)
         T = x.size(0)

@@ -162,3 +162,63 @@ def test_moe_status_codes_without_device_work():
     assert lib.mm_moe_combine(p, p, p, p, 4, 2, 64, z, z) == B and lib.mm_moe_combine(p, p, p, p, 4, 2, 64, 8, z) == B
     assert lib.mm_moe_gather(z, p, 4, 8, 64, p, z) == B and lib.mm_moe_gather(p, z, 4, 8, 64, p, z) == B
     assert lib.mm_moe_gather(p, p, 4, 8, 64, z, z) == B and lib.mm_moe_gather(8, p, 4, 8, 64, p, z) == B
+
+
+# ---- the edges of the routing rule (moe_oracle.route_edge_inputs) ---------------------------------------------------------------------
+def topk_set_is_unambiguous(bits, k):
+    """rows whose k-th and (k + 1)-th largest logits differ: there torch.topk has one possible set"""
+    s = -np.sort(-o.bf16_to_f32(bits).astype(np.float64), axis=1)
+    return s[:, k - 1] != s[:, k]
+
+
+@pytest.mark.parametrize("E,k", mo.ROUTE_EDGE_SHAPES)
+def test_route_oracle_at_the_edges(E, k):
+    """what the edge inputs are built to hold, in the oracle's own answer: at a tie the lower index wins (-0.0 = +0.0), a -inf expert is
+    picked only when fewer than k are finite, then the lowest such index with weight +0.0, and the far weights are normal bf16 numbers;
+    wherever the top-k set is unambiguous it is torch.topk's, with weights within 1 bf16 ulp of torch's chain"""
+    for T in mo.ROUTE_EDGE_TOKENS:
+        inputs = mo.route_edge_inputs(E, k, T)
+        assert list(inputs) == ["tie of 2 at k", "tie of 3 at k", "masked", "k - 1 finite", "far"]
+        for name, bits in inputs.items():
+            l = o.bf16_to_f32(bits).astype(np.float64)
+            assert bits.shape == (T, E) and not np.isnan(l).any()
+            ids, w_bits, w = mo.route(bits, k)
+            sel = np.take_along_axis(l, ids.astype(np.int64), axis=1)
+            assert (np.diff(sel, axis=1) <= 0).all() and all(len(set(r)) == k for r in ids.tolist()), name
+            if name.startswith("tie"):
+                n = int(name.split()[2])
+                zeros = 0
+                for t in range(T):
+                    tied = np.flatnonzero(l[t] == sel[t, k - 1])
+                    assert len(tied) == n and (l[t] > sel[t, k - 1]).sum() < k <= (l[t] >= sel[t, k - 1]).sum() - 1
+                    took = np.intersect1d(ids[t], tied)
+                    assert np.array_equal(took, tied[: len(took)]), (name, t)          # the lowest indices among the tied
+                    zeros += int(len(set(np.signbit(l[t, tied]).tolist())) == 2)
+                assert zeros >= T // 3, name                  # rows where -0.0 meets +0.0
+                assert not topk_set_is_unambiguous(bits, k).any()
+            if name == "masked":
+                assert np.isfinite(sel).all() and all(1 <= c <= E - k for c in np.isinf(l).sum(axis=1)), name
+            if name == "k - 1 finite":
+                assert (np.isfinite(l).sum(axis=1) == k - 1).all() and np.isfinite(sel[:, : k - 1]).all()
+                assert np.array_equal(ids[:, k - 1], np.argmax(np.isinf(l), axis=1))       # the first -inf expert
+                assert (w_bits[:, k - 1] == 0).all() and (w[:, k - 1] == 0).all()
+            if name == "far":
+                gaps = sel[:, :1] - sel[:, 1:]
+                assert set(np.unique(gaps).tolist()) <= set(mo.FAR_GAPS) and gaps.max() == 80.0 and gaps.min() == 20.0
+                assert (w > 2.0 ** -126).all() and ((w_bits & 0x7F80) != 0).all()         # normal bf16 numbers
+            clear = topk_set_is_unambiguous(bits, k)
+            if not clear.any():
+                continue
+            p = torch.softmax(t_from_bits(bits[clear], "cpu"), dim=1, dtype=torch.float)
+            tw, ti = torch.topk(p, k, dim=-1)
+            tw = (tw / tw.sum(dim=-1, keepdim=True)).to(torch.bfloat16)
+            assert np.array_equal(np.sort(ids[clear], axis=1), np.sort(ti.numpy(), axis=1)), f"{name}: top-k set"
+            want = np.zeros((int(clear.sum()), E), dtype=np.uint16)
+            np.put_along_axis(want, ti.numpy(), bits_from_t(tw), axis=1)
+            ulp = o.bf16_ulp_distance(w_bits[clear], np.take_along_axis(want, ids[clear].astype(np.int64), axis=1))
+            assert ulp.max() <= 1, f"{name}: torch's CPU chain is {ulp.max()} bf16 ulps from the oracle"
+
+
+def test_f64_to_bf16_gives_zero_for_zero():
+    x = np.array([0.0, 1.0, 0.0, 2.0 ** -126, 1.8e-35])
+    assert np.array_equal(mo.f64_to_bf16(x), np.array([0x0000, 0x3F80, 0x0000, 0x0080, 0x05BF], dtype=np.uint16))

@@ -51,6 +51,27 @@ def test_route_against_the_oracle(dev, E, k):
     assert differ <= 0.01 * total, (differ, total)
 
 
+@pytest.mark.parametrize("E,k", mo.ROUTE_EDGE_SHAPES)
+def test_route_at_the_edges(dev, E, k):
+    """moe_oracle.route_edge_inputs: a tie exactly at the k boundary among otherwise distinct logits (two and three experts, low, high
+    and mixed indices, -0.0 against +0.0) -- the lower index wins; experts masked with -inf; rows with k - 1 finite logits, where the
+    -inf pick has weight +0.0; weights down to e^-80.  ids equal to the oracle's, weights within 1 bf16 ulp, two launches bit-equal"""
+    for T in mo.ROUTE_EDGE_TOKENS:
+        for name, bits in mo.route_edge_inputs(E, k, T).items():
+            logits = t_from_bits(bits, dev)
+            ids, w = mixedgemm.moe_route(logits, k)
+            ids2, w2 = mixedgemm.moe_route(logits, k)
+            want_ids, want_w, _ = mo.route(bits, k)
+            assert np.array_equal(host(ids), want_ids), (name, T)
+            ulp = o.bf16_ulp_distance(bits_from_t(w), want_w)
+            print(f"route edge E={E} k={k} T={T} {name}: max {ulp.max()} ulp, {int((ulp != 0).sum())} of {ulp.size} differ")
+            assert ulp.max() <= 1, (name, T)
+            if name == "k - 1 finite":
+                assert (bits_from_t(w)[:, k - 1] == 0).all(), "the -inf pick must have weight +0.0"
+                assert np.isinf(o.bf16_to_f32(bits)[np.arange(T), host(ids)[:, k - 1]]).all()
+            assert np.array_equal(host(ids), host(ids2)) and np.array_equal(bits_from_t(w), bits_from_t(w2))
+
+
 # ---- plan -------------------------------------------------------------------------------------------------------------------------
 def plan_cases():
     rng = np.random.default_rng(7)
