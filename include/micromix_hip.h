@@ -416,6 +416,62 @@ int mm_moe_gather(const void *x_bf16, const int32_t *sorted_token, int num_token
 int mm_moe_combine(const void *y_sorted_bf16, const int32_t *topk_ids, const void *topk_w_bf16, const int32_t *slot_of, int num_tokens,
                    int top_k, int hidden, void *out_bf16, mm_stream_t stream);
 
+/*
+ * Device-sized grouped launches (version >= 640): the expert quantizer and the expert GEMM of a sparse MoE block with the row counts read
+ * from expert_offsets ON THE DEVICE, so that the block needs no copy to the host and can be captured in a hipGraph.  Both entries take
+ * no workspace, read no device data on the host, use no atomic to decide an order and give the same bytes on every launch; their
+ * grids depend on host values only.  E experts, 1 <= E <= 64 (else MM_ERR_UNSUPPORTED); n = num_rows rows ("slots") in plan order;
+ * expert e owns the slots [expert_offsets[e], expert_offsets[e + 1]) (mm_moe_plan's output).
+ *
+ * Data format -- one set of buffers per quantized operand for ALL experts:
+ *   packed segments  [n, Kseg / 2 | 3 Kseg / 4 | Kseg] row-major; expert e's rows are rows expert_offsets[e] .. of it: the bytes of
+ *                    the per-expert tensors of mm_reorder_quantize_grouped laid end to end.
+ *   scale tensors    the layout above is tiled per 128 rows OF A GROUP, so every expert has its own run of 128-row tiles (a tile of a
+ *                    segment is 128 * Kseg / 32 bytes).  Expert e's run starts at tile
+ *                        expert_offsets[e] / 128 + e            (integer division)
+ *                    and is ceil(M_e / 128) tiles long.  A pure function of expert_offsets[e]: no scan.  The runs are disjoint for any
+ *                    non-decreasing offsets, because floor(lo / 128) + ceil(M / 128) <= floor(hi / 128) + 1, and they lie inside
+ *                    n / 128 + E tiles: mm_moe_sf_bytes(n, E, Kseg) bytes is the allocation.  Inside its run an expert's scale bytes are
+ *                    those of its own [M_e, Kseg] scale tensor (mm_sf_offset from the run's first byte).
+ *   expert table     mm_moe_expert[E] in DEVICE memory (8-byte aligned), built once: the expert's reorder index (mm_moe_quantize reads
+ *                    only this), its packed weights and scales and an optional bias (mm_moe_matmul reads these).  One table per layer
+ *                    (w1, w3, w2).  The pointers must stay valid while launches that read the table run.
+ *
+ * mm_moe_quantize: for every slot s that an expert owns, quantizes row row_of_slot[s] of src (bf16 [src_rows, K]; row s itself when
+ *   row_of_slot is NULL) with that expert's reorder index, as mm_reorder_quantize does, into packed row s and the scale bytes of row
+ *   s - expert_offsets[e] of the expert's run.  With row_of_slot = mm_moe_plan's sorted_token this is mm_moe_gather folded in.  A slot
+ *   from expert_offsets[E] on, offsets that are not a plan's (decreasing, negative, past n), or a row index outside [0, src_rows) leave
+ *   that slot's outputs untouched; nothing is read or written out of bounds.  src and the packed outputs 16-byte aligned, scale tensors
+ *   4-byte aligned.  mode: MM_QUANT_MIXED or MM_QUANT_W4.
+ * mm_moe_matmul: D[slots of e] = the product mm_matmul_grouped computes for group e, on the same kernel family -- bit for bit when
+ *   K <= 512, for an expert of more than 64 rows, and whenever the two streaming launches split K over the same number of waves (4 when
+ *   ceil(N / 32) * groups >= CUs and the tier is above 16 rows, else 8; here tier and groups come from max_rows and min(E, n, 8), there
+ *   from the largest group and the number of groups of at most 64 rows in each launch); otherwise the fp32 partial sums of an expert of
+ *   at most 64 rows are added in another order.  The result depends on (max_rows, the expert's rows) alone.  A / SFA the buffers
+ *   mm_moe_quantize (MM_QUANT_MIXED) filled, weights and bias from the table, D bf16 [n, N].  max_rows is a host bound on any expert's rows that the
+ *   caller vouches for (a MoE block passes T: a token meets an expert at most once).  Experts of 1 .. 64 rows run in one launch of the
+ *   weight-streaming kernels (at the tier of min(max_rows, 64)), experts of more than 64 rows, when max_rows > 64, in one launch of the
+ *   tiled kernels whose grid is the host bound (n / bm + min(E, n)) * ceil(N / bn) on the sum of their tiles; an expert finds itself in
+ *   one launch and leaves the other at once.  An expert with more than max_rows rows is skipped whole: its D rows stay untouched.
+ *   KN + KS + KO == 0 writes zeros to the owned rows.  MM_OUT_F32 and shapes whose scale images do not fit the streaming kernels' LDS at some
+ *   tier up to min(max_rows, 64)'s (mm_moe_matmul_supported() == 0; the caller then takes mm_matmul_grouped): MM_ERR_UNSUPPORTED.
+ * Null or misaligned pointers, negative sizes: MM_ERR_BAD_ARG; a bad split: MM_ERR_BAD_SPLIT; n = 0: MM_OK; all without device work.
+ */
+typedef struct mm_moe_expert {
+    const int16_t *reorder_index;                 /* [K] */
+    const uint8_t *BN, *BS, *BO;                  /* packed weights [N, .] */
+    const uint8_t *SFBN, *SFBS, *SFBO;            /* their scales */
+    const void *bias_bf16;                        /* [N] or NULL */
+} mm_moe_expert;
+size_t mm_moe_sf_bytes(int num_rows, int num_experts, int Kseg);
+int mm_moe_quantize(const void *src_bf16, const int32_t *row_of_slot, const int32_t *expert_offsets, const mm_moe_expert *expert_table,
+                    int num_experts, int num_rows, int src_rows, int K, int KN, int KS, int KO, int mode, uint8_t *oN, uint8_t *oS,
+                    uint8_t *oO, uint8_t *sfN, uint8_t *sfS, uint8_t *sfO, mm_stream_t stream);
+int mm_moe_matmul_supported(int max_rows, int N, int KN, int KS, int KO, int wmode);
+int mm_moe_matmul(const uint8_t *AN, const uint8_t *AS, const uint8_t *AO, const uint8_t *SFAN, const uint8_t *SFAS, const uint8_t *SFAO,
+                  const int32_t *expert_offsets, const mm_moe_expert *expert_table, int num_experts, int num_rows, int max_rows, int N,
+                  int KN, int KS, int KO, int wmode, int flags, void *D_bf16, mm_stream_t stream);
+
 /* Which kernel(s) and how many workgroups mm_matmul / mm_matmul_ws launch for this problem on the CURRENT device (the same
  * decision code as the launcher; workspace_bytes = 0 means "no workspace", i.e. never split-K).  Returns a string in a
  * thread-local buffer, valid until the calling thread's next call.  Used by bench.py to name the kernel it timed. */

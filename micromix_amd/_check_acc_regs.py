@@ -20,8 +20,8 @@ def agprs(line):
     return out
 
 
-EXPECTED_KERNELS = 13   # mx_gemm256.hip -- g256: 2 + 2 grouped + 1 fused gate/up + 1 tile-major tail; g128: 2 + 2 split-K + 2 grouped + 1 fused gate/up
-EXPECTED_SMALL = 4      # mx_gemm_tiles_small.hip -- g64: 2 + 2 grouped (the 4-wave tiles leave their accumulators to the compiler)
+EXPECTED_KERNELS = 18   # mx_gemm256.hip -- every instantiation the build examines: g256: 2 + 2 grouped + 2 device-sized + fused gate/up + tile-major tail; g128: 2 + 2 split-K + 2 grouped + 2 device-sized + fused gate/up
+EXPECTED_SMALL = 6      # mx_gemm_tiles_small.hip -- g64: 2 + 2 grouped + 2 device-sized (the 4-wave tiles leave their accumulators to the compiler)
 
 
 def check(asm_text):
@@ -33,7 +33,7 @@ def check_counted(asm_text):
     """(violations, symbols of the kernels with asm-owned accumulators that were examined).  A caller must also require
     len(examined) >= EXPECTED_KERNELS: a name-mangling change would otherwise make the check pass with nothing examined."""
     bad, examined = [], []
-    for m in re.finditer(r"^(_ZN2mm\d(g(?:256|128|64|32n|32|16))(?:17|21|25)mx_gemm256_(?:grouped_|act_)?kernel\w*):[^\n]*\n(.*?)\.end_amdhsa_kernel",
+    for m in re.finditer(r"^(_ZN2mm\d(g(?:256|128|64|32n|32|16))(?:17|21|25)mx_gemm256_(?:grouped_|act_|moe_)?kernel\w*):[^\n]*\n(.*?)\.end_amdhsa_kernel",
                          asm_text, re.S | re.M):
         sym, ns, body = m.group(1), m.group(2), m.group(3)
         n = NACC[ns]
@@ -64,13 +64,14 @@ def check_counted(asm_text):
 # the model, so the scan is exact for straight-line code and silent across branches).
 # ---------------------------------------------------------------------------------------------------------
 STREAM_OWN = re.compile(r"^\s*(v_mfma_scale_f32_16x16x128_f8f6f4|v_accvgpr_read_b32|v_accvgpr_write_b32)\b")
-STREAM_KERNEL = re.compile(r"^(_ZN2mm6stream\d+(mx_gemm_stream_kernel|mx_gemm_stream_grouped_kernel|mx_qlinear_stream_kernel|mx_qlinear_stream_rms_kernel)I((?:Li\d+E)+)Lb[01]E\w*):[^\n]*\n(.*?)\.end_amdhsa_kernel",
+STREAM_KERNEL = re.compile(r"^(_ZN2mm6stream\d+(mx_gemm_stream_kernel|mx_gemm_stream_grouped_kernel|mx_gemm_stream_moe_kernel|mx_qlinear_stream_kernel|mx_qlinear_stream_rms_kernel)I((?:Li\d+E)+)Lb[01]E\w*):[^\n]*\n(.*?)\.end_amdhsa_kernel",
                            re.S | re.M)
 # ... and the launches with the activation inside (stream_body ACT: F = 4): mx_gemm_stream_act_kernel<T16 = 1, 2>,
 # mx_qlinear_stream_act_kernel<RMS>
 STREAM_ACT_KERNEL = re.compile(r"^(_ZN2mm6stream\d+(mx_gemm_stream_act_kernel|mx_qlinear_stream_act_kernel)I(?:Lb[01]|Li(\d+))EE\w*):[^\n]*\n(.*?)\.end_amdhsa_kernel",
                                re.S | re.M)
 EXPECTED_STREAM_KERNELS = 68   # 22 plain + 18 grouped + 16 with the quantizer inside + 8 with norm and quantizer inside + 4 with the activation inside
+EXPECTED_STREAM_MOE_KERNELS = 18      # ... and, counted by name on top of those, the device-sized launches: the 18 configurations of the grouped ones
 VMEM = re.compile(r"^\s*(buffer_|global_|scratch_|flat_)(load|store|atomic)")
 
 
@@ -192,7 +193,7 @@ def verify_pending(asm_text):
 # matching-precision 256-row kernel lost 2.3x that way (124 us against 53) while every numerical test stayed green.  The tile kernels
 # also may not own static LDS: FragOfsC (mx_gemm_tile.inc) relies on the dynamic LDS starting at byte 0.
 # ---------------------------------------------------------------------------------------------------------
-TILE_KERNEL = re.compile(r"mx_gemm256_(?:grouped_|act_)?kernel")
+TILE_KERNEL = re.compile(r"mx_gemm256_(?:grouped_|act_|moe_)?kernel")
 
 
 def check_scratch(asm_text):
@@ -237,6 +238,10 @@ def verify_stream(asm_text):
     if len(examined) < EXPECTED_STREAM_KERNELS:
         raise RuntimeError(f"accumulator-register check found {len(examined)} streaming kernels, expected >= {EXPECTED_STREAM_KERNELS} "
                            "(kernel names changed? update micromix_amd/_check_acc_regs.py)")
+    moe = [sym for sym in examined if "mx_gemm_stream_moe_kernel" in sym]
+    if len(moe) < EXPECTED_STREAM_MOE_KERNELS or len(examined) - len(moe) < EXPECTED_STREAM_KERNELS:
+        raise RuntimeError(f"accumulator-register check found {len(moe)} device-sized streaming kernels and {len(examined) - len(moe)} others, expected "
+                           f">= {EXPECTED_STREAM_MOE_KERNELS} and >= {EXPECTED_STREAM_KERNELS} (kernel names changed? update micromix_amd/_check_acc_regs.py)")
     return len(examined)
 
 

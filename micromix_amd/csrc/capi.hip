@@ -29,7 +29,7 @@ static bool split_ok(int K, int KN, int KS, int KO) {
 
 extern "C" {
 
-int mm_version(void) { return 630; /* 0.6.3: + mm_moe_route, mm_moe_plan, mm_moe_gather, mm_moe_combine (top-k routing, dispatch and combine of a sparse MoE block around mm_matmul_grouped); 0.6.2: + mm_rope_kv_append (RoPE + paged KV append in one launch, from the packed q | k | v projection); 0.6.1: + mm_paged_prefill(_workspace_bytes) (causal multi-token attention over the paged KV cache); 0.6.0: + mm_kv_append, mm_paged_decode(_workspace_bytes), enum mm_kv_dtype (paged int4 / bf16 KV cache); 0.5.1: + mm_rmsnorm_gate_up_activate_decode(_supported), mm_gate_up_activate_decode_supported; mm_gate_up_activate(_decode) one launch at decode sizes; 0.5.0: + the *_supported_w queries (weight mode); 0.4.0: + mm_rmsnorm_qlinear_decode(_supported) (0.3.0: + mm_gate_up_activate(_decode), mm_down_activate_decode, mm_matmul_ws_reset; 0.2.0: diagnostics moved to libmicromix_diag.so, + mm_test_function) */ }
+int mm_version(void) { return 640; /* 0.6.4: + mm_moe_quantize, mm_moe_matmul(_supported), mm_moe_sf_bytes (device-sized grouped launches: a hipGraph-capturable MoE block); 0.6.3: + mm_moe_route, mm_moe_plan, mm_moe_gather, mm_moe_combine (top-k routing, dispatch and combine of a sparse MoE block around mm_matmul_grouped); 0.6.2: + mm_rope_kv_append (RoPE + paged KV append in one launch, from the packed q | k | v projection); 0.6.1: + mm_paged_prefill(_workspace_bytes) (causal multi-token attention over the paged KV cache); 0.6.0: + mm_kv_append, mm_paged_decode(_workspace_bytes), enum mm_kv_dtype (paged int4 / bf16 KV cache); 0.5.1: + mm_rmsnorm_gate_up_activate_decode(_supported), mm_gate_up_activate_decode_supported; mm_gate_up_activate(_decode) one launch at decode sizes; 0.5.0: + the *_supported_w queries (weight mode); 0.4.0: + mm_rmsnorm_qlinear_decode(_supported) (0.3.0: + mm_gate_up_activate(_decode), mm_down_activate_decode, mm_matmul_ws_reset; 0.2.0: diagnostics moved to libmicromix_diag.so, + mm_test_function) */ }
 
 const char *mm_test_function(void) { return "Hello from test_function!"; /* bindings.cpp:700 */ }
 
@@ -725,6 +725,80 @@ int mm_moe_combine(const void *y_sorted_bf16, const int32_t *topk_ids, const voi
     hipError_t e = mm::launch_moe_combine(y_sorted_bf16, topk_ids, topk_w_bf16, slot_of, num_tokens, top_k, hidden, out_bf16,
                                           (hipStream_t)stream);
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_moe_combine");
+}
+
+// ---- device-sized grouped launches (reorder_quantize.hip, mx_gemm_stream.hip, mx_gemm_tile.inc: the *_moe_kernel)
+static_assert(sizeof(mm_moe_expert) == sizeof(mm::MoeExpert) && sizeof(mm_moe_expert) == 64, "the device table is read as mm::MoeExpert");
+
+size_t mm_moe_sf_bytes(int num_rows, int num_experts, int Kseg) {
+    if (num_rows < 0 || num_experts < 0 || Kseg < 0) return 0;
+    return mm::moe_sf_bytes(num_rows, num_experts, Kseg);
+}
+
+static int moe_groups(const int32_t *expert_offsets, const mm_moe_expert *expert_table, int E, int n, int max_rows, mm::MoeGroups *mg) {
+    if (E < 0 || n < 0) return MM_ERR_BAD_ARG;
+    if (E < 1 || E > 64) return MM_ERR_UNSUPPORTED;
+    *mg = {expert_offsets, reinterpret_cast<const mm::MoeExpert *>(expert_table), E, n, max_rows};
+    return MM_OK;
+}
+
+int mm_moe_quantize(const void *src_bf16, const int32_t *row_of_slot, const int32_t *expert_offsets, const mm_moe_expert *expert_table,
+                    int num_experts, int num_rows, int src_rows, int K, int KN, int KS, int KO, int mode, uint8_t *oN, uint8_t *oS, uint8_t *oO,
+                    uint8_t *sfN, uint8_t *sfS, uint8_t *sfO, mm_stream_t stream) {
+    mm::MoeGroups mg;
+    if (src_rows < 0 || K < 0) return MM_ERR_BAD_ARG;
+    if (int st = moe_groups(expert_offsets, expert_table, num_experts, num_rows, num_rows, &mg)) return st;
+    if (!split_ok(K, KN, KS, KO)) return MM_ERR_BAD_SPLIT;
+    if (K > 32768 || (mode != MM_QUANT_MIXED && mode != MM_QUANT_W4)) return MM_ERR_BAD_ARG;
+    if (num_rows == 0 || src_rows == 0) return MM_OK;
+    if (!src_bf16 || !expert_offsets || !expert_table || ((uintptr_t)src_bf16 & 15) || ((uintptr_t)expert_table & 7)) return MM_ERR_BAD_ARG;
+    if ((KN && (!oN || !sfN)) || (KS && (!oS || !sfS)) || (KO && (!oO || !sfO))) return MM_ERR_BAD_ARG;
+    // rows are stored in 16-byte pieces, scales as dwords
+    if ((((uintptr_t)oN | (uintptr_t)oS | (uintptr_t)oO) & 15) || (((uintptr_t)sfN | (uintptr_t)sfS | (uintptr_t)sfO) & 3)) return MM_ERR_BAD_ARG;
+    hipError_t e = mm::launch_moe_quantize(src_bf16, row_of_slot, mg, src_rows, K, KN, KS, KO, mode == MM_QUANT_W4, oN, oS, oO, sfN, sfS, sfO,
+                                           (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_moe_quantize");
+}
+
+int mm_moe_matmul_supported(int max_rows, int N, int KN, int KS, int KO, int wmode) {
+    if (max_rows < 1 || N < 1 || KN < 0 || KS < 0 || KO < 0 || (KN % 128) || (KS % 128) || (KO % 128)) return 0;
+    if (wmode != MM_W_MATCH && wmode != MM_W_FP4) return 0;
+    if (KN + KS + KO == 0) return 1;
+    const int K[3] = {KN, KS, KO};
+    return mm::mx_gemm_stream_moe_supported(max_rows, K) ? 1 : 0;
+}
+
+int mm_moe_matmul(const uint8_t *AN, const uint8_t *AS, const uint8_t *AO, const uint8_t *SFAN, const uint8_t *SFAS, const uint8_t *SFAO,
+                  const int32_t *expert_offsets, const mm_moe_expert *expert_table, int num_experts, int num_rows, int max_rows, int N, int KN,
+                  int KS, int KO, int wmode, int flags, void *D_bf16, mm_stream_t stream) {
+    mm::MoeGroups mg;
+    if (max_rows < 0 || N < 0 || KN < 0 || KS < 0 || KO < 0) return MM_ERR_BAD_ARG;
+    if (int st = moe_groups(expert_offsets, expert_table, num_experts, num_rows, max_rows, &mg)) return st;
+    if ((KN % 128) || (KS % 128) || (KO % 128)) return MM_ERR_BAD_SPLIT;
+    if (wmode != MM_W_MATCH && wmode != MM_W_FP4) return MM_ERR_BAD_ARG;
+    if (flags & MM_OUT_F32) return MM_ERR_UNSUPPORTED;    // fp32 partial sums come from mm_matmul only
+    if (num_rows == 0 || N == 0 || max_rows == 0) return MM_OK;
+    if (!expert_offsets || !expert_table || ((uintptr_t)expert_table & 7) || !D_bf16 || ((uintptr_t)D_bf16 & 1)) return MM_ERR_BAD_ARG;
+    if ((KN && (!AN || !SFAN)) || (KS && (!AS || !SFAS)) || (KO && (!AO || !SFAO))) return MM_ERR_BAD_ARG;
+    if (KN + KS + KO == 0) {   // no segment: every owned row is zero (gemm.cu:48-50); a kernel, see ws_reset_kernel
+        hipError_t e = mm::launch_moe_zero_rows(D_bf16, expert_offsets, num_experts, num_rows, N, (hipStream_t)stream);
+        return e == hipSuccess ? MM_OK : fail_hip(e, "mm_moe_matmul(zero)");
+    }
+    if (!mm_moe_matmul_supported(max_rows, N, KN, KS, KO, wmode)) return MM_ERR_UNSUPPORTED;
+    mm::GemmArgs a = {};
+    a.X[0] = AN; a.X[1] = AS; a.X[2] = AO;
+    a.SFX[0] = SFAN; a.SFX[1] = SFAS; a.SFX[2] = SFAO;
+    a.K[0] = KN; a.K[1] = KS; a.K[2] = KO;
+    a.N = N;
+    a.sfw_row_tiles = (N + 127) / 128;
+    a.round_per_segment = (flags & MM_ROUND_ONCE) ? 0 : 1;
+    a.D = (uint16_t *)D_bf16;
+    const bool w4 = weights_fp4(wmode, KS, KO);
+    // experts of 1 .. 64 rows on the weight-streaming kernels, larger ones on the tiled kernels: the kernel family mm_matmul_grouped
+    // gives each of them; an expert finds itself in one launch and returns at once from the other
+    hipError_t e = mm::launch_mx_gemm_stream_moe(a, mg, w4, (hipStream_t)stream);
+    if (e == hipSuccess && max_rows > 64) e = mm::launch_mx_gemm256_moe(a, mg, w4, (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_moe_matmul");
 }
 
 int mm_diag_set_kernel_events(void *start_event, void *stop_event) {

@@ -242,6 +242,14 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(const uint4 *y, const 
     }
 }
 
+// ---- zero rows (mm_moe_matmul without a segment) ------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void moe_zero_rows_kernel(uint16_t *D, const int *offsets, int E, int n, int N) {
+    const int owned = offsets[E];
+    if ((int)blockIdx.x >= owned || owned > n) return;
+    uint16_t *row = D + (int64_t)blockIdx.x * N;
+    for (int c = threadIdx.x; c < N; c += blockDim.x) row[c] = 0;
+}
+
 int row_threads(int V) { return V >= 256 ? 256 : (V + 63) / 64 * 64; }
 
 }  // namespace
@@ -280,6 +288,11 @@ hipError_t launch_moe_combine(const void *y, const int *ids, const void *w, cons
         case 7: moe_combine_kernel<7><<<T, threads, 0, stream>>>(y4, ids, w16, slot_of, n_rows, V, o4); break;
         default: moe_combine_kernel<8><<<T, threads, 0, stream>>>(y4, ids, w16, slot_of, n_rows, V, o4); break;
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_moe_zero_rows(void *D, const int *offsets, int E, int n, int N, hipStream_t stream) {
+    moe_zero_rows_kernel<<<n, 256, 0, stream>>>((uint16_t *)D, offsets, E, n, N);
     return hipGetLastError();
 }
 

@@ -586,4 +586,35 @@ hipError_t launch_mx_gemm256_grouped(GroupedTileArgs &ga, bool w4, hipStream_t s
     return launch_small_tile_grouped(64, w4, total, ga, stream);
 }
 
+// device-sized grouped launch of the tiled kernels: the groups' row counts are on the device, so the tile size comes from a host
+// bound on the sum of their tiles -- n / bm + min(E, n) row tiles, since sum ceil(M_e / bm) <= sum M_e / bm + the experts with rows --
+// by the rule of launch_mx_gemm256_grouped, and the grid is that bound
+hipError_t launch_mx_gemm256_moe(const GemmArgs &a, const MoeGroups &mg, bool w4, hipStream_t stream) {
+    const int cus = device_cus();
+    const int N = a.N, groups = mg.E < mg.n ? mg.E : mg.n;
+    auto tiles = [&](int bm, int bn) { return (long long)(mg.n / bm + groups) * ((N + bn - 1) / bn); };
+    const long long t128 = tiles(128, 256), t64 = tiles(128, 128), t32 = tiles(64, 128), t32n = tiles(64, 64);
+    int bm, bn;
+    if (t32n <= cus) { bm = 64; bn = 64; }
+    else if (t32 <= cus && 2 * t64 <= cus) { bm = 64; bn = 128; }
+    else if (2 * t128 <= cus && t64 <= cus) { bm = 128; bn = 128; }
+    else if (t128 <= cus) { bm = 128; bn = 256; }
+    else { bm = 256; bn = 256; }
+    const long long bound = tiles(bm, bn);
+    if (bound > INT32_MAX) return hipErrorInvalidValue;
+    const int total = (int)bound;
+    static DynamicLdsOnce done[4];
+    auto go = [&](auto kern, DynamicLdsOnce &d, int lds, int threads) -> hipError_t {
+        if (hipError_t e = d.ensure(reinterpret_cast<const void *>(kern), lds); e != hipSuccess) return e;
+        hipLaunchKernelGGL(kern, dim3(total), dim3(threads), lds, stream, a, mg);
+        return hipGetLastError();
+    };
+    if (bm == 64) return launch_small_tile_moe(bn == 64 ? 33 : 32, w4, total, a, mg, stream);
+    if (bm == 256) return w4 ? go(g256::mx_gemm256_moe_kernel<true>, done[0], g256::Lds<true>::TOTAL, g256::NT)
+                             : go(g256::mx_gemm256_moe_kernel<false>, done[1], g256::Lds<false>::TOTAL, g256::NT);
+    if (bn == 256) return w4 ? go(g128::mx_gemm256_moe_kernel<true>, done[2], g128::Lds<true>::TOTAL, g128::NT)
+                             : go(g128::mx_gemm256_moe_kernel<false>, done[3], g128::Lds<false>::TOTAL, g128::NT);
+    return launch_small_tile_moe(64, w4, total, a, mg, stream);
+}
+
 }  // namespace mm

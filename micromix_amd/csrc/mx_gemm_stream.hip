@@ -876,6 +876,35 @@ static hipError_t launch_grouped_one(const GroupedGemmArgs &ga, hipStream_t stre
     return hipGetLastError();
 }
 
+// Device-sized grouped launch (mm_moe_matmul): blockIdx.y is the expert; its row count and the bases of its rows in the packed buffers
+// come from the offsets on the device, its weights from the device table (moe_group_args).  An expert without rows, with more than 64
+// (the tiled launch's) or more than max_rows returns at once; the host picks T16 with 16 T16 >= min(max_rows, 64).
+template <int F, int T16, int D, int NW, bool W4>
+__global__ void __launch_bounds__(64 * NW) mx_gemm_stream_moe_kernel(GemmArgs a, MoeGroups mg) {
+    const int e = blockIdx.y;
+    const int lo = mg.offsets[e], M = mg.offsets[e + 1] - lo;
+    if (lo < 0 || M < 1 || M > 16 * T16 || M > mg.max_rows || M > mg.n - lo) return;
+    moe_group_args(a, mg, e, lo, M);
+    stream_body<F, T16, D, NW, W4>(a);
+}
+
+template <int F, int T16, int D, int NW, bool W4>
+static hipError_t launch_moe_one(const GemmArgs &a, const MoeGroups &mg, hipStream_t stream) {
+    const int present = (a.K[0] ? 1 : 0) + (a.K[1] ? 1 : 0) + (a.K[2] ? 1 : 0);
+    const int red_bytes = NW * (F * T16 >= 8 ? 1 : present) * F * T16 * 4 * 64 * (int)sizeof(float);
+    const int stage_bytes = NW * D * Ring<F, T16, W4>::SLOT + scale_images_bytes(F, T16, NW, (a.K[0] + a.K[1] + a.K[2]) >> 7, W4);
+    const int lds = red_bytes > stage_bytes ? red_bytes : stage_bytes;
+    if (lds > STREAM_LDS_MAX) return hipErrorInvalidValue;      // (mx_gemm_stream_moe_supported keeps callers away from this)
+    static DynamicLdsOnce once;
+    if (lds > 65536) {
+        hipError_t e = once.ensure(reinterpret_cast<const void *>(mx_gemm_stream_moe_kernel<F, T16, D, NW, W4>), STREAM_LDS_MAX);
+        if (e != hipSuccess) return e;
+    }
+    const int blocks = (a.N + 16 * F - 1) / (16 * F);
+    hipLaunchKernelGGL((mx_gemm_stream_moe_kernel<F, T16, D, NW, W4>), dim3(blocks, mg.E), dim3(64 * NW), lds, stream, a, mg);
+    return hipGetLastError();
+}
+
 // mm_qlinear_decode on the streaming kernel: the workgroup quantizes the M <= 8 rows itself (QUANT)
 template <int F, int D, int NW, bool W4>
 __global__ void __launch_bounds__(64 * NW) mx_qlinear_stream_kernel(GemmArgs a, dq::QuantIn qi, int qbytes) {
@@ -988,6 +1017,40 @@ hipError_t launch_mx_gemm_stream_grouped(const GroupedGemmArgs &ga, int max_m, b
         const int slabs = (ga.g[0].K[0] + ga.g[0].K[1] + ga.g[0].K[2]) >> 7;
         if (wide) return launch_grouped_one<2, 2, 2, 4, true>(ga, stream);
         return two_tile_fits(3, slabs) ? launch_grouped_one<1, 2, 3, 8, true>(ga, stream) : launch_grouped_one<1, 2, 2, 8, true>(ga, stream);
+    }
+    if (max_m <= 32) return wide ? MM_STREAM_G(2, 2, 3, 4) : MM_STREAM_G(1, 2, 3, 8);
+    if (max_m <= 48) return wide ? MM_STREAM_G(2, 3, 2, 4) : MM_STREAM_G(1, 3, 2, 8);
+    return wide ? MM_STREAM_G(2, 4, 2, 4) : MM_STREAM_G(1, 4, 2, 8);
+#undef MM_STREAM_G
+}
+
+// the device-sized grouped launch: the configurations of launch_mx_gemm_stream_grouped, chosen from host values only -- the tier from
+// max_rows, the groups that share the CUs counted as that launch counts them at its fullest, min(E, n, MM_MAX_GROUPS).  The host-sized
+// path takes both from the rows of each launch, so the two may run different configurations on the same rows.  F, T16 and D leave every
+// bit alone; NW does not once a launch has more than four slabs (K > 512): slab j is summed in wave j % NW and the waves in wave order.
+// An expert's rows therefore carry the bits mm_matmul_grouped gives them in a launch of the same NW (4 when `wide` and the tier is
+// above 16 rows, 8 otherwise), and the bits of every launch when K <= 512.
+// Supported where the host-sized path streams whatever its largest group of at most max_m rows is: every tier up to max_m's must fit
+// (a very long K fits the 64-row tier and not the 16-row one), so that no group is on the skinny kernel there and streamed here.
+bool mx_gemm_stream_moe_supported(int max_m, const int K[3]) {
+    max_m = max_m < 64 ? max_m : 64;
+    for (int tier = 16; tier < max_m; tier += 16)
+        if (!mx_gemm_stream_grouped_supported(tier, 1, 0, K)) return false;
+    return mx_gemm_stream_grouped_supported(max_m, 1, 0, K);
+}
+hipError_t launch_mx_gemm_stream_moe(const GemmArgs &a, const MoeGroups &mg, bool w4, hipStream_t stream) {
+    using namespace stream;
+    const int max_m = mg.max_rows < 64 ? mg.max_rows : 64;
+    int groups = mg.E < mg.n ? mg.E : mg.n;
+    groups = groups < MM_MAX_GROUPS ? groups : MM_MAX_GROUPS;
+    const bool wide = (a.N + 31) / 32 * groups >= device_cus();
+#define MM_STREAM_G(F_, T_, D_, NW_)                                                 \
+    (w4 ? launch_moe_one<F_, T_, D_, NW_, true>(a, mg, stream) : launch_moe_one<F_, T_, D_, NW_, false>(a, mg, stream))
+    if (max_m <= 16) return wide ? MM_STREAM_G(2, 1, 2, 8) : MM_STREAM_G(1, 1, 3, 8);
+    if (max_m <= 32 && w4) {
+        const int slabs = (a.K[0] + a.K[1] + a.K[2]) >> 7;
+        if (wide) return launch_moe_one<2, 2, 2, 4, true>(a, mg, stream);
+        return two_tile_fits(3, slabs) ? launch_moe_one<1, 2, 3, 8, true>(a, mg, stream) : launch_moe_one<1, 2, 2, 8, true>(a, mg, stream);
     }
     if (max_m <= 32) return wide ? MM_STREAM_G(2, 2, 3, 4) : MM_STREAM_G(1, 2, 3, 8);
     if (max_m <= 48) return wide ? MM_STREAM_G(2, 3, 2, 4) : MM_STREAM_G(1, 3, 2, 8);

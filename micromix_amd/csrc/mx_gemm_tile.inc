@@ -2200,5 +2200,24 @@ __global__ void __launch_bounds__(NTHREADS) mx_gemm256_grouped_kernel(GroupedTil
     tile_body<W4, false>(ga.g[g], (int)blockIdx.x - ga.first_block[g]);
 }
 
+// Device-sized grouped launch (mm_moe_matmul): the groups are the experts with 65 .. max_rows rows, their tile counts are worked out
+// from the offsets by every workgroup (a scalar walk over <= 64 experts), and the grid is a host bound on the sum; a workgroup past
+// the real total leaves before it touches memory.  The expert's argument block: moe_group_args.
+template <bool W4>
+__global__ void __launch_bounds__(NTHREADS) mx_gemm256_moe_kernel(GemmArgs a, MoeGroups mg) {
+    const int tiles_n = (a.N + BN - 1) / BN;
+    int bid = blockIdx.x, e = 0, lo = 0, M = 0;
+    for (; e < mg.E; ++e) {
+        lo = mg.offsets[e];
+        M = mg.offsets[e + 1] - lo;
+        const int t = (lo >= 0 && M > 64 && M <= mg.max_rows && M <= mg.n - lo) ? ((M + BM - 1) / BM) * tiles_n : 0;
+        if (bid < t) break;
+        bid -= t;
+    }
+    if (e >= mg.E) return;
+    moe_group_args(a, mg, e, lo, M);
+    tile_body<W4, false>(a, bid);
+}
+
 }  // namespace MM_NS
 #undef MM_SMALL

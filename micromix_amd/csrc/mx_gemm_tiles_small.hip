@@ -119,4 +119,23 @@ hipError_t launch_small_tile_grouped(int kind, bool w4, int total, const Grouped
     }
 }
 
+// device-sized grouped launch (launch_mx_gemm256_moe has chosen the tile and the grid bound `total`)
+hipError_t launch_small_tile_moe(int kind, bool w4, int total, const GemmArgs &a, const MoeGroups &mg, hipStream_t stream) {
+    static DynamicLdsOnce done[6];
+    auto go = [&](auto kern, DynamicLdsOnce &d, int lds, int threads) -> hipError_t {
+        if (hipError_t e = d.ensure(reinterpret_cast<const void *>(kern), lds); e != hipSuccess) return e;
+        hipLaunchKernelGGL(kern, dim3(total), dim3(threads), lds, stream, a, mg);
+        return hipGetLastError();
+    };
+    switch (kind) {
+        case 33: return w4 ? go(g32n::mx_gemm256_moe_kernel<true>, done[0], g32n::Lds<true>::TOTAL, g32n::NTHREADS)
+                           : go(g32n::mx_gemm256_moe_kernel<false>, done[1], g32n::Lds<false>::TOTAL, g32n::NTHREADS);
+        case 32: return w4 ? go(g32::mx_gemm256_moe_kernel<true>, done[2], g32::Lds<true>::TOTAL, g32::NTHREADS)
+                           : go(g32::mx_gemm256_moe_kernel<false>, done[3], g32::Lds<false>::TOTAL, g32::NTHREADS);
+        case 64: return w4 ? go(g64::mx_gemm256_moe_kernel<true>, done[4], g64::Lds<true>::TOTAL, g64::NT)
+                           : go(g64::mx_gemm256_moe_kernel<false>, done[5], g64::Lds<false>::TOTAL, g64::NT);
+        default: return hipErrorInvalidValue;
+    }
+}
+
 }  // namespace mm

@@ -132,6 +132,55 @@ struct GroupedQuantArgs {
 };
 hipError_t launch_reorder_quantize_grouped(const GroupedQuantArgs &ga, int max_rows, bool w4, hipStream_t stream);
 
+
+// Device-sized grouped launches (mm_moe_quantize / mm_moe_matmul, include/micromix_hip.h): the groups are the experts of a sparse MoE
+// block, their rows the slots [offsets[e], offsets[e + 1]) of buffers that hold all experts' rows in slot order.  What differs from
+// expert to expert and is known on the host sits in a device table (one MoeExpert = one mm_moe_expert, 64 bytes); the row counts are
+// read from `offsets` by every workgroup, so nothing is read back to the host and the grids depend on host values only.
+struct MoeExpert {
+    const int16_t *idx;        // reorder index (mm_moe_quantize)
+    const uint8_t *W[3];       // packed weights BN, BS, BO (mm_moe_matmul)
+    const uint8_t *SFW[3];     // their scales
+    const uint16_t *bias;      // optional [N] bf16
+};
+struct MoeGroups {
+    const int *offsets;        // [E + 1], device
+    const MoeExpert *table;    // [E], device
+    int E, n, max_rows;        // n: rows of the packed buffers; a group with more than max_rows rows is skipped
+};
+// first 128-row scale tile of expert e's run in a packed scale tensor: a function of offsets[e] alone (runs are disjoint because
+// floor(lo / 128) + ceil(M / 128) <= floor(hi / 128) + 1, and all lie inside n / 128 + E tiles)
+__host__ __device__ inline int moe_sf_tile(int lo, int e) { return (lo >> 7) + e; }
+inline size_t moe_sf_bytes(int n, int E, int Kseg) { return (size_t)(n / 128 + E) * 128u * (size_t)(Kseg / 32); }
+#if defined(__HIPCC__)
+// the argument block of expert e in a launch whose `a` carries the packed buffers (X, SFX, D) and what all experts share
+__device__ __forceinline__ void moe_group_args(GemmArgs &a, const MoeGroups &mg, int e, int lo, int M) {
+    const MoeExpert &x = mg.table[e];
+    const size_t tile = (size_t)moe_sf_tile(lo, e);
+    a.X[0] += (size_t)lo * (size_t)(a.K[0] >> 1);
+    a.X[1] += (size_t)lo * (size_t)((a.K[1] >> 2) * 3);
+    a.X[2] += (size_t)lo * (size_t)a.K[2];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        a.SFX[i] += tile * (size_t)(a.K[i] << 2);      // a 128-row tile of a segment's scales: 128 * Kseg / 32 bytes
+        a.W[i] = x.W[i];
+        a.SFW[i] = x.SFW[i];
+    }
+    a.bias = x.bias;
+    a.D += (size_t)lo * (size_t)a.N;
+    a.M = M;
+    a.sfx_row_tiles = (M + 127) >> 7;
+}
+#endif
+hipError_t launch_moe_quantize(const void *src, const int *row_of_slot, const MoeGroups &mg, int src_rows, int K, int KN, int KS, int KO,
+                               bool w4, uint8_t *oN, uint8_t *oS, uint8_t *oO, uint8_t *sfN, uint8_t *sfS, uint8_t *sfO, hipStream_t stream);
+bool mx_gemm_stream_moe_supported(int max_m, const int K[3]);
+// `a`: X / SFX / D the packed buffers, K, N, round_per_segment, sfw_row_tiles filled in; groups of 1 .. min(max_rows, 64) rows
+hipError_t launch_mx_gemm_stream_moe(const GemmArgs &a, const MoeGroups &mg, bool w4, hipStream_t stream);
+// ... groups of 65 .. max_rows rows on the tiled kernels
+hipError_t launch_mx_gemm256_moe(const GemmArgs &a, const MoeGroups &mg, bool w4, hipStream_t stream);
+hipError_t launch_moe_zero_rows(void *D, const int *offsets, int E, int n, int N, hipStream_t stream);
+
 hipError_t set_quant_clock_buffer(unsigned long long *buf);   // -DMM_INSTRUMENT only
 hipError_t launch_reorder_quantize(const void *src, int rows, int K, const int16_t *idx, int KN, int KS, int KO, bool w4,
                                    uint8_t *oN, uint8_t *oS, uint8_t *oO, uint8_t *sfN, uint8_t *sfS, uint8_t *sfO,

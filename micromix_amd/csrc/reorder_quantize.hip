@@ -27,12 +27,13 @@ namespace mm {
 __device__ unsigned long long *g_quant_clock = nullptr;
 #endif
 
-// rows first_row, first_row + row_stride, ... of one [rows, K] matrix (one workgroup's share)
+// rows first_row, first_row + row_stride, ... of one [rows, K] matrix (one workgroup's share); sf_row0: the row of the scale tensors
+// that row 0 of the matrix is (0 everywhere but in moe_quantize_kernel, whose pointers are those of ONE row)
 template <bool W4>
 __device__ __forceinline__ void reorder_quantize_body(const uint16_t *__restrict__ src, int rows, int K, const int16_t *__restrict__ idx,
                                                       int KN, int KS, int KO, uint8_t *__restrict__ oN, uint8_t *__restrict__ oS,
                                                       uint8_t *__restrict__ oO, uint8_t *__restrict__ sfN, uint8_t *__restrict__ sfS,
-                                                      uint8_t *__restrict__ sfO, int first_row, int row_stride) {
+                                                      uint8_t *__restrict__ sfO, int first_row, int row_stride, int sf_row0 = 0) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int G = (KN + KS + KO) >> 5;  // groups produced; K is the input row length (>= 32 * G)
     const int g = threadIdx.x;
@@ -123,7 +124,7 @@ __device__ __forceinline__ void reorder_quantize_body(const uint16_t *__restrict
             const uint32_t b2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)byte, 0xAA, 0xF, 0xF, false);
             const uint32_t b3 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)byte, 0xFF, 0xF, 0xF, false);
             if ((g & 3) == 0)
-                store_scale_dword(sf + sf_offset(r, j, kseg), byte | (b1 << 8) | (b2 << 16) | (b3 << 24));
+                store_scale_dword(sf + sf_offset(r + sf_row0, j, kseg), byte | (b1 << 8) | (b2 << 16) | (b3 << 24));
         }
 #if MM_CLOCKS
         if (ck != nullptr && threadIdx.x == 0 && r == first_row) ck[2] = __builtin_amdgcn_s_memrealtime();
@@ -163,6 +164,31 @@ __global__ void __launch_bounds__(MAXT) reorder_quantize_grouped_kernel(GroupedQ
     if ((int)blockIdx.x < q.rows)
         reorder_quantize_body<W4>(q.src, q.rows, ga.K, q.idx, ga.KN, ga.KS, ga.KO, q.o[0], q.o[1], q.o[2], q.sf[0], q.sf[1], q.sf[2],
                                   blockIdx.x, gridDim.x);
+}
+
+// Device-sized grouped launch (mm_moe_quantize): one workgroup per slot s of the packed buffers.  It finds the expert that owns the
+// slot among the <= 65 offsets (the number of offsets[i] <= s, i < E, less one: an empty expert shares its offset with the next one, and
+// the last of them is the owner), takes the row to read from row_of_slot (the gather of the MoE dispatch, folded in) or s itself, and
+// quantizes it with that expert's reorder index into packed row s and the expert's run of scale tiles (moe_sf_tile).  A slot that no
+// expert owns, offsets that are not those of a plan, or a source row outside [0, src_rows) leave the slot's outputs untouched; the
+// scale tile written is at most s / 128 + E - 1 whatever the offsets hold.
+template <bool W4, int MAXT>
+__global__ void __launch_bounds__(MAXT)
+moe_quantize_kernel(const uint16_t *__restrict__ src, const int *__restrict__ row_of_slot, MoeGroups mg, int src_rows, int K, int KN, int KS,
+                    int KO, uint8_t *oN, uint8_t *oS, uint8_t *oO, uint8_t *sfN, uint8_t *sfS, uint8_t *sfO) {
+    const int s = blockIdx.x;
+    int e = -1;
+    for (int i = 0; i < mg.E; ++i) e += mg.offsets[i] <= s ? 1 : 0;
+    if (e < 0) return;
+    const int lo = mg.offsets[e], hi = mg.offsets[e + 1];
+    if (lo < 0 || lo > s || s >= hi || hi > mg.n) return;
+    const int t = row_of_slot != nullptr ? row_of_slot[s] : s;
+    if (t < 0 || t >= src_rows) return;
+    const int r = s - lo;                                     // the row inside the expert's own [M_e, K] matrix
+    const size_t tile = (size_t)moe_sf_tile(lo, e) + (size_t)(r >> 7);
+    reorder_quantize_body<W4>(src + (size_t)t * K, 1, K, mg.table[e].idx, KN, KS, KO, oN + (size_t)s * (KN >> 1),
+                              oS + (size_t)s * (W4 ? KS >> 1 : (KS >> 2) * 3), oO + (size_t)s * (W4 ? KO >> 1 : KO),
+                              sfN + tile * (size_t)(KN << 2), sfS + tile * (size_t)(KS << 2), sfO + tile * (size_t)(KO << 2), 0, 1, r & 127);
 }
 
 #if MM_CLOCKS
@@ -212,6 +238,22 @@ hipError_t launch_reorder_quantize_grouped(const GroupedQuantArgs &ga, int max_r
     bx = bx < 1 ? 1 : bx;
     bx = max_rows < bx ? max_rows : bx;
     hipLaunchKernelGGL(kern, dim3(bx, ga.ngroups), dim3(threads), lds, stream, ga);
+    return hipGetLastError();
+}
+
+hipError_t launch_moe_quantize(const void *src, const int *row_of_slot, const MoeGroups &mg, int src_rows, int K, int KN, int KS, int KO,
+                               bool w4, uint8_t *oN, uint8_t *oS, uint8_t *oO, uint8_t *sfN, uint8_t *sfS, uint8_t *sfO, hipStream_t stream) {
+    if (mg.n == 0) return hipSuccess;
+    const int G = (KN + KS + KO) / 32, stagers = K / 32;
+    const int threads = ((G > stagers ? G : stagers) + 63) / 64 * 64;
+    const size_t lds = (size_t)K * 2 + (w4 ? 0 : (size_t)KS / 4 * 3 + KO);
+    auto kern = threads <= 256 ? (w4 ? moe_quantize_kernel<true, 256> : moe_quantize_kernel<false, 256>)
+                               : (w4 ? moe_quantize_kernel<true, 1024> : moe_quantize_kernel<false, 1024>);
+    static DynamicLdsOnce big_lds;
+    if (lds > 48 * 1024)
+        if (hipError_t e = big_lds.ensure(reinterpret_cast<const void *>(moe_quantize_kernel<false, 1024>), 96 * 1024); e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(mg.n), dim3(threads), lds, stream, (const uint16_t *)src, row_of_slot, mg, src_rows, K, KN, KS, KO, oN, oS,
+                       oO, sfN, sfS, sfO);
     return hipGetLastError();
 }
 

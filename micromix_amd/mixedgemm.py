@@ -31,7 +31,8 @@ from . import _lib
 __all__ = ["test_function", "matmul", "gate_up_activate", "interleave_gate_up", "reorder_quantize_x", "reorder_quantize_w", "reorder_quantize_w4", "activate_quantize_x",
            "downproj_quantize_w", "downproj_quantize_w4", "rmsnorm_quantize_x", "qlinear_decode", "qlinear_decode_supported", "matmul_grouped", "reorder_quantize_x_grouped",
            "kv_append", "rope_kv_append", "paged_decode", "paged_decode_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes",
-           "moe_route", "moe_plan", "moe_gather", "moe_combine"]
+           "moe_route", "moe_plan", "moe_gather", "moe_combine",
+           "moe_expert_table", "moe_sf_bytes", "moe_quantize", "moe_matmul", "moe_matmul_supported"]
 
 
 def test_function():
@@ -1178,4 +1179,139 @@ def moe_combine(y_sorted, topk_ids, topk_w, slot_of, *, out=None):
         st = lib.mm_moe_combine(_ptr(y_sorted), _ptr(topk_ids), _ptr(topk_w), _ptr(slot_of), T, top_k, H, _ptr(out), _stream_ptr(dev))
     if st:
         _lib.check(st, "moe_combine")
+    return out
+
+
+# ---- device-sized grouped launches: the expert quantizer and GEMM of a capturable MoE block (mm_moe_quantize / mm_moe_matmul) ----
+
+class MoEExpertTable:
+    """`mm_moe_expert[E]` in device memory (include/micromix_hip.h) with the tensors it points to kept alive.  `tensor` int64 [E, 8]:
+    per expert the addresses of (reorder_index, BN, BS, BO, SFBN, SFBS, SFBO, bias or 0).  Built once, by moe_expert_table."""
+    __slots__ = ("tensor", "E", "N", "K", "split", "wmode", "has_bias", "_keep")
+
+
+def moe_expert_table(reorder_indices, Bs, KN, KS, KO, biases=None):
+    """One table per layer of the experts: reorder_indices[e] int16 [K], Bs[e] = (BN, BS, BO, SFBN, SFBS, SFBO) as matmul_grouped takes
+    them, biases[e] bf16 [N] or None.  All experts share N, the (KN, KS, KO) split and the weight mode.  The addresses are copied to the
+    device here -- build the table once (SparseMoEBlock.__init__), never per call."""
+    E = len(Bs)
+    if not (1 <= E <= 64) or len(reorder_indices) != E or (biases is not None and len(biases) != E):
+        raise ValueError("1 <= E <= 64 experts, one reorder index (and bias entry) each")
+    KN, KS, KO = int(KN), int(KS), int(KO)
+    K = KN + KS + KO
+    if KN < 0 or KS < 0 or KO < 0 or KN % 128 or KS % 128 or KO % 128 or K == 0:
+        _lib.check(_lib.MM_ERR_BAD_SPLIT, "moe_expert_table")
+    dev = Bs[0][0].device
+    index, u8 = dev.index, torch.uint8
+    N = Bs[0][0].size(0)
+    same = Bs[0][1].size(1) == KS // 4 * 3 and Bs[0][2].size(1) == KO          # (as matmul_grouped tells the weight mode)
+    wmode = _lib.MM_W_MATCH if same else _lib.MM_W_FP4
+    wb = (KN // 2, KS // 4 * 3 if same else KS // 2, KO if same else KO // 2)
+    if tuple(tuple(t.shape) for t in Bs[0][:3]) != tuple((N, w) for w in wb):
+        raise RuntimeError("the packed weights of expert 0 do not match the split in either weight mode")
+    shapes = tuple(tuple(t.shape) for t in Bs[0])
+    rows, keep = [], []
+    for e, (idx, B) in enumerate(zip(reorder_indices, Bs)):
+        if not _ok(idx, torch.int16, index) or idx.numel() != K:
+            _check_tensor(idx, f"reorder_index[{e}]", torch.int16, dev)
+            raise RuntimeError(f"expert {e}: the reorder index must have {K} entries")
+        for t in B:
+            if not _ok(t, u8, index):
+                _check_tensor(t, f"expert {e} weight operand", u8, dev)
+        if tuple(tuple(t.shape) for t in B[:3]) != shapes[:3] or any(t.numel() < _sf_bytes_w(N, k) for t, k in zip(B[3:], (KN, KS, KO))):
+            raise RuntimeError(f"expert {e}: packed weights do not match N / split / weight mode of expert 0")
+        bias = biases[e] if biases is not None else None
+        if bias is not None and (not _ok(bias, torch.bfloat16, index) or bias.numel() != N):
+            raise RuntimeError(f"expert {e}: bias must be a bfloat16 tensor with N elements")
+        rows.append([idx.data_ptr()] + [t.data_ptr() if t.numel() else 0 for t in B] + [bias.data_ptr() if bias is not None else 0])
+        keep.append((idx, B, bias))
+    tab = MoEExpertTable()
+    tab.tensor = torch.tensor(rows, dtype=torch.int64).to(dev)
+    tab.E, tab.N, tab.K, tab.split, tab.wmode, tab._keep = E, N, K, (KN, KS, KO), wmode, keep
+    tab.has_bias = biases is not None and any(b is not None for b in biases)
+    return tab
+
+
+def moe_sf_bytes(n, E, Kseg):
+    """bytes of a packed scale tensor for n rows of E experts: n // 128 + E tiles of 128 rows (include/micromix_hip.h)"""
+    return (n // 128 + E) * 128 * (Kseg // 32)
+
+
+def moe_quantize(src, row_of_slot, expert_offsets, table, n=None, *, mode="x", out=None):
+    """The expert quantizer with the row counts read on the device: for every slot s that an expert owns (expert_offsets int32 [E + 1],
+    moe_plan's), row row_of_slot[s] of src bf16 [rows, K] -- row s itself with row_of_slot=None -- quantized with that expert's reorder
+    index (table: moe_expert_table).  Returns ONE 6-tuple (oN, oS, oO, sfN, sfS, sfO) for all experts: packed rows in slot order
+    [n, .], scale tensors of moe_sf_bytes(n, E, Kseg) bytes with expert e's run at tile expert_offsets[e] // 128 + e; bytes of slots and
+    tiles that no expert owns are left as they were.  n defaults to len(row_of_slot) (or src's rows).  mode "x" (mixed) or "w4".
+    Byte for byte reorder_quantize_x_grouped's per-expert tensors laid end to end.  No host sync; capture-safe."""
+    lib = _lib.load()
+    if not (isinstance(src, torch.Tensor) and src.is_cuda and _ok(src, torch.bfloat16, src.get_device())):
+        _check_tensor(src, "src", torch.bfloat16)
+    if src.dim() != 2:
+        raise RuntimeError("src must be [rows, K] bf16")
+    dev, (src_rows, K) = src.device, src.shape
+    if mode not in ("x", "w4"):
+        raise ValueError("mode must be 'x' or 'w4'")
+    w4 = mode == "w4"
+    E, (KN, KS, KO) = table.E, table.split
+    if K != table.K:
+        raise RuntimeError(f"src must be [rows, {table.K}]")
+    _moe_tensor(expert_offsets, "expert_offsets", torch.int32, dev, (E + 1,))
+    if row_of_slot is not None:
+        _moe_tensor(row_of_slot, "row_of_slot", torch.int32, dev)
+        n = row_of_slot.numel() if n is None else int(n)
+        if row_of_slot.numel() < n:
+            raise RuntimeError("row_of_slot must have n entries")
+    else:
+        n = src_rows if n is None else int(n)
+    u8 = torch.uint8
+    widths = (KN // 2, KS // 2 if w4 else KS // 4 * 3, KO // 2 if w4 else KO)
+    if out is None:
+        out = tuple(torch.empty((n, w), dtype=u8, device=dev) for w in widths) + \
+            tuple(torch.empty((moe_sf_bytes(n, E, k),), dtype=u8, device=dev) for k in (KN, KS, KO))
+    else:
+        for t, w in zip(out[:3], widths):
+            _moe_tensor(t, "packed output", u8, dev, (n, w))
+        for t, k in zip(out[3:], (KN, KS, KO)):
+            if _moe_tensor(t, "scale output", u8, dev).numel() < moe_sf_bytes(n, E, k):
+                raise RuntimeError("a scale output is smaller than moe_sf_bytes(n, E, Kseg)")
+    with _on_device(dev.index):
+        st = lib.mm_moe_quantize(_ptr(src), _ptr(row_of_slot) if row_of_slot is not None else None, _ptr(expert_offsets), _ptr(table.tensor), E, n,
+                                 src_rows, K, KN, KS, KO, _lib.MM_QUANT_W4 if w4 else _lib.MM_QUANT_MIXED, *(_ptr(t) for t in out), _stream_ptr(dev))
+    if st:
+        _lib.check(st, "moe_quantize")
+    return tuple(out)
+
+
+def moe_matmul_supported(max_rows, table):
+    """False where moe_matmul would answer "unsupported configuration" (very long K: take matmul_grouped there)"""
+    return bool(_lib.load().mm_moe_matmul_supported(int(max_rows), table.N, *table.split, table.wmode))
+
+
+def moe_matmul(A, expert_offsets, table, max_rows, *, rounding="reference", out=None):
+    """The expert GEMM with the row counts read on the device: A = moe_quantize's 6-tuple (mode "x"), out bf16 [n, N] with the rows of
+    expert e = matmul_grouped's output for that expert (bit for bit wherever both split K over the same number of waves, and always when
+    K <= 512: include/micromix_hip.h), weights and biases from `table`.  max_rows: a bound on any expert's
+    rows that the caller vouches for (T in a MoE block); an expert with more rows is skipped, its rows of `out` left as they were, as
+    are the rows from expert_offsets[E] on.  At most two launches, whatever E.  No host sync; capture-safe."""
+    lib = _lib.load()
+    if rounding not in ("reference", "fused"):
+        raise ValueError("rounding must be 'reference' or 'fused'")
+    dev = A[0].device
+    E, N, (KN, KS, KO) = table.E, table.N, table.split
+    n = A[0].size(0)
+    u8 = torch.uint8
+    for t, w in zip(A[:3], (KN // 2, KS // 4 * 3, KO)):
+        _moe_tensor(t, "activation segment", u8, dev, (n, w))
+    for t, k in zip(A[3:], (KN, KS, KO)):
+        if _moe_tensor(t, "activation scales", u8, dev).numel() < moe_sf_bytes(n, E, k):
+            raise RuntimeError("an activation scale tensor is smaller than moe_sf_bytes(n, E, Kseg)")
+    _moe_tensor(expert_offsets, "expert_offsets", torch.int32, dev, (E + 1,))
+    out = torch.empty((n, N), dtype=torch.bfloat16, device=dev) if out is None else _moe_tensor(out, "out", torch.bfloat16, dev, (n, N))
+    flags = _lib.MM_ROUND_PER_SEGMENT if rounding == "reference" else _lib.MM_ROUND_ONCE
+    with _on_device(dev.index):
+        st = lib.mm_moe_matmul(*(_ptr(t) for t in A), _ptr(expert_offsets), _ptr(table.tensor), E, n, int(max_rows), N, KN, KS, KO, table.wmode,
+                               flags, _ptr(out), _stream_ptr(dev))
+    if st:
+        _lib.check(st, "moe_matmul")
     return out

@@ -35,12 +35,18 @@ class SparseMoEBlock(nn.Module):
     quantized rows, so they share index and split (the reference quantizes once, with w1's, qMixtralLayer.py:507-510), and all experts
     share the splits and the weight mode (their reorder indices are their own).  1 <= top_k <= 8, top_k <= E <= 64.
 
-    `forward(hidden [.., H])` returns `(out [.., H], router_logits [T, E])` like the reference.  It reads the E + 1 expert offsets
-    back to the host once, because the grouped entries take host row counts: that copy is the block's single sync, and the block is
-    therefore NOT hipGraph-capturable (DESIGN.md 7e lists device-sized grouped launches as open).
+    `forward(hidden [.., H])` returns `(out [.., H], router_logits [T, E])` like the reference.  With the default `capturable=False` it
+    reads the E + 1 expert offsets back to the host once, because the grouped entries take host row counts: that copy is the block's
+    single sync, and in this mode the block is NOT hipGraph-capturable.  With `capturable=True` the expert quantizer and the expert GEMM
+    read the row counts from the offsets on the device (`mixedgemm.moe_quantize / moe_matmul`): about ten launches whatever
+    E is, no copy to the host, no per-expert Python loop, no allocation whose size depends on device data -- `forward` can be captured
+    once per token count T and replayed on any routing.  The arithmetic is the default mode's, expert by expert, on the same kernel
+    family; the bits are the default mode's wherever both modes split K over the same number of waves, and always when K <= 512 --
+    with a longer K an expert of at most 64 rows may differ in the order of its fp32 partial sums, because the default mode picks the
+    streaming configuration from the rows of each call and this mode from T ("Which bits").
     """
 
-    def __init__(self, gate_weight, experts, top_k, gate_bias=None):
+    def __init__(self, gate_weight, experts, top_k, gate_bias=None, capturable=False):
         super().__init__()
         if isinstance(gate_weight, nn.Module):
             gate_weight, gate_bias = gate_weight.weight, (gate_weight.bias if gate_bias is None else gate_bias)
@@ -81,6 +87,22 @@ class SparseMoEBlock(nn.Module):
         self._idx2 = [t[2].reorder_index for t in triples]
         self._B = [[tuple(getattr(layer, n) for n in _PACKED) for layer in col] for col in zip(*triples)]     # w1s, w3s, w2s
         self._bias = [[layer.bias for layer in col] if any(layer.bias is not None for layer in col) else None for col in zip(*triples)]
+        self.capturable = bool(capturable)
+        self._supported = {}
+        if self.capturable:      # the device tables of the three layers (mm_moe_expert[E]), built once; they keep their tensors alive
+            self._tables = [mixedgemm.moe_expert_table(idx, B, *split, biases=bias) for idx, B, split, bias in
+                            zip((self._idx1, self._idx1, self._idx2), self._B, (self.split1, self.split1, self.split2), self._bias)]
+
+    def _device_sized(self, T):
+        """whether the expert GEMMs take device row counts at this T (asked once per T: very long K does not fit the streaming kernels'
+        LDS, and the block then takes the host-sized path, which a capture cannot contain)"""
+        ok = self._supported.get(T)
+        if ok is None:
+            ok = self._supported[T] = all(mixedgemm.moe_matmul_supported(T, t) for t in self._tables)
+        if not ok and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"SparseMoEBlock(capturable=True): moe_matmul does not support these experts at T = {T} (K too long for the "
+                               "weight-streaming kernels); the block would read the expert offsets on the host, which cannot be captured")
+        return ok
 
     @torch.no_grad()
     def forward(self, hidden):
@@ -94,6 +116,16 @@ class SparseMoEBlock(nn.Module):
             return hidden.new_zeros(shape), router_logits
         ids, w = mixedgemm.moe_route(router_logits, self.top_k)
         offsets, sorted_token, slot_of = mixedgemm.moe_plan(ids, E)
+        if self.capturable and self._device_sized(T):
+            # row counts stay on the device; a token meets an expert at most once, so no expert has more than T rows
+            t1, t3, t2 = self._tables
+            q1 = mixedgemm.moe_quantize(x, sorted_token, offsets, t1)          # the row gather is the quantizer's
+            a = mixedgemm.moe_matmul(q1, offsets, t1, T, rounding=self.rounding)
+            b = mixedgemm.moe_matmul(q1, offsets, t3, T, rounding=self.rounding)
+            h = F.silu(a) * b
+            q2 = mixedgemm.moe_quantize(h, None, offsets, t2)
+            y = mixedgemm.moe_matmul(q2, offsets, t2, T, rounding=self.rounding)
+            return mixedgemm.moe_combine(y, ids, w, slot_of).reshape(shape), router_logits
         xs = mixedgemm.moe_gather(x, sorted_token)
         off = offsets.tolist()                                # the block's single sync: the grouped entries take host row counts
         rows = lambda t: [t[off[e]:off[e + 1]] for e in range(E)]     # an expert without tokens is a group with M = 0

@@ -1,6 +1,7 @@
 """The sparse MoE block on the MI355X: micromix_amd.moe.SparseMoEBlock against the per-expert loop it replaces, and its four new kernels.
 
     python tools/time_moe.py [out.txt]
+    python tools/time_moe.py device [out.txt]     the capturable block (device-sized grouped launches), see device_main
 
 Mixtral-8x7B shapes (H 4096, I 14336, E 8, top_k 2; splits as tests/test_model_shapes_gpu.py), T = 1, 16, 128, 4096, one set of weights.
 1. The block (`SparseMoEBlock.forward`: one host sync) and the reference's loop (model/qMixtralLayer.py:414-452, 502-519) written with
@@ -138,5 +139,73 @@ def main():
             f.write(f"# {torch.cuda.get_device_name(0)}, torch {torch.__version__}; Mixtral-8x7B shapes H {H} I {I} E {E} top_k {K}\n{text}\n{json.dumps(rows)}\n")
 
 
+def device_main(out_path):
+    """SparseMoEBlock(capturable=True) against the default block (which is the parent's, line for line), one box, one run:
+    per T the default block eager, the capturable block eager, both three times in alternation (the spread of each is printed), the
+    capturable block as ONE graph replay, and the two new entries against the grouped calls they replace, each as ten calls in one
+    graph (no host time): gather + grouped quantizer against moe_quantize, matmul_grouped against moe_matmul for w1 (N = I) and w2
+    (N = H).  The possible costs of the device-sized form on their own: moe_matmul with max_rows = 64 on offsets whose groups all
+    exceed 64 rows is the streaming launch in which every group exits; the tiled launch's grid bound against the tiles that exist."""
+    dev = torch.device("cuda:0")
+    experts = make_experts(dev)
+    g = torch.Generator(device=dev).manual_seed(1)
+    gate_w = (torch.randn((E, H), generator=g, device=dev) * 0.05).to(torch.bfloat16)
+    plain, capt = SparseMoEBlock(gate_w, experts, K), SparseMoEBlock(gate_w, experts, K, capturable=True)
+    lines, rows = [], []
+    for T in (1, 16, 128, 4096):
+        x = torch.randn((T, H), generator=g, device=dev).to(torch.bfloat16)
+        iters = 20 if T >= 4096 else 50
+        same = torch.equal(plain(x)[0], capt(x)[0])      # (DESIGN.md 7e "Which bits": not on every routing once K > 512)
+        eager = {"default": [], "capturable": []}
+        for _ in range(3):
+            eager["default"].append(timed(lambda: plain(x), iters))
+            eager["capturable"].append(timed(lambda: capt(x), iters))
+        replay = graph_time(lambda: capt(x), calls=1, iters=iters)
+        ids, w = mixedgemm.moe_route(F.linear(x, gate_w), K)
+        off, tok, slot = mixedgemm.moe_plan(ids, E)
+        o = off.tolist()
+        n = T * K
+        cut = lambda t: [t[o[e]:o[e + 1]] for e in range(E)]
+        t1, t3, t2 = capt._tables
+        xs = mixedgemm.moe_gather(x, tok)
+        q1 = mixedgemm.moe_quantize(x, tok, off, t1)
+        q1g = mixedgemm.reorder_quantize_x_grouped(cut(xs), plain._idx1, *SPLIT_H)
+        a, y = torch.empty((n, I), dtype=torch.bfloat16, device=dev), torch.empty((n, H), dtype=torch.bfloat16, device=dev)
+        hbuf = torch.randn((n, I), generator=g, device=dev).to(torch.bfloat16)
+        q2 = mixedgemm.moe_quantize(hbuf, None, off, t2)
+        q2g = mixedgemm.reorder_quantize_x_grouped(cut(hbuf), plain._idx2, *SPLIT_I)
+        us = {
+            "gather + quantize_grouped (H)": graph_time(lambda: mixedgemm.reorder_quantize_x_grouped(cut(mixedgemm.moe_gather(x, tok, out=xs)), plain._idx1, *SPLIT_H)),
+            "moe_quantize (H, gather inside)": graph_time(lambda: mixedgemm.moe_quantize(x, tok, off, t1, out=q1)),
+            "quantize_grouped (I)": graph_time(lambda: mixedgemm.reorder_quantize_x_grouped(cut(hbuf), plain._idx2, *SPLIT_I)),
+            "moe_quantize (I)": graph_time(lambda: mixedgemm.moe_quantize(hbuf, None, off, t2, out=q2)),
+            "matmul_grouped w1": graph_time(lambda: mixedgemm.matmul_grouped(q1g, plain._B[0], outs=cut(a))),
+            "moe_matmul w1": graph_time(lambda: mixedgemm.moe_matmul(q1, off, t1, T, out=a)),
+            "matmul_grouped w2": graph_time(lambda: mixedgemm.matmul_grouped(q2g, plain._B[2], outs=cut(y))),
+            "moe_matmul w2": graph_time(lambda: mixedgemm.moe_matmul(q2, off, t2, T, out=y)),
+        }
+        if min(c for c in (o[e + 1] - o[e] for e in range(E))) > 64:
+            us["moe_matmul w1, max_rows 64: the streaming launch, every group exits"] = graph_time(lambda: mixedgemm.moe_matmul(q1, off, t1, 64, out=a))
+        counts = [o[e + 1] - o[e] for e in range(E)]
+        sp = lambda v: f"{min(v):8.1f} .. {max(v):8.1f}"
+        lines.append(f"T = {T}: rows per expert {counts}; the two blocks' outputs are {'bit-equal' if same else 'NOT bit-equal'}")
+        lines.append(f"  default block, eager      {sp(eager['default'])} us (three runs in alternation)")
+        lines.append(f"  capturable block, eager   {sp(eager['capturable'])} us")
+        lines.append(f"  capturable block, one graph replay {replay:8.1f} us")
+        lines += [f"  {k:<72} {v:9.2f} us" for k, v in us.items()]
+        rows.append(dict(T=T, rows_per_expert=counts, default_eager_us=[round(v, 1) for v in eager["default"]],
+                         capturable_eager_us=[round(v, 1) for v in eager["capturable"]], capturable_replay_us=round(replay, 1),
+                         entries_us={k: round(v, 2) for k, v in us.items()}))
+    text = "\n".join(lines)
+    print(text)
+    print(json.dumps(rows))
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(f"# {torch.cuda.get_device_name(0)}, torch {torch.__version__}; Mixtral-8x7B shapes H {H} I {I} E {E} top_k {K}\n{text}\n{json.dumps(rows)}\n")
+
+
 if __name__ == "__main__":
-    main()
+    if len(sys.argv) > 1 and sys.argv[1] == "device":
+        device_main(sys.argv[2] if len(sys.argv) > 2 else None)
+    else:
+        main()
