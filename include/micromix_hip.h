@@ -443,6 +443,16 @@ int mm_moe_combine(const void *y_sorted_bf16, const int32_t *topk_ids, const voi
  *   from expert_offsets[E] on, offsets that are not a plan's (decreasing, negative, past n), or a row index outside [0, src_rows) leave
  *   that slot's outputs untouched; nothing is read or written out of bounds.  src and the packed outputs 16-byte aligned, scale tensors
  *   4-byte aligned.  mode: MM_QUANT_MIXED or MM_QUANT_W4.
+ * mm_moe_activate_quantize (version >= 650): the activation of the expert MLP computed while the quantizer stages the row.  a, b bf16
+ *   [n, K] with rows in slot order (the experts' two up-projections).  For every slot s that an expert owns, in mm_moe_quantize's sense,
+ *       h[s, c] = bf16( float(bf16( silu(a[s, c]) )) * float(b[s, c]) ),     silu(x) = x * rcp(1 + exp2(-x log2 e)) in fp32,
+ *   both roundings to nearest even -- torch's bf16 `silu(a) * b`, which rounds twice, except where the hardware exp2 / rcp (about one
+ *   fp32 ulp each) move silu across a bf16 rounding boundary: fewer than 1 element in 1 000 differs from the correctly rounded result,
+ *   none by more than 3 bf16 ulps (1 ulp when b = 1).  Row h[s, :] is then quantized exactly as mm_moe_quantize(h, NULL, ..,
+ *   MM_QUANT_MIXED) would: the same six buffers, byte for byte, which mm_moe_matmul consumes.  h_out_bf16, when not NULL, also receives
+ *   the bf16 row, unreordered ([n, K]; it must not overlap a or b).  A slot no expert owns, offsets that are not a plan's or a slot from
+ *   expert_offsets[E] on leave every output of that slot untouched, h_out included; the scale tile written is at most s / 128 + E - 1.
+ *   a, b, h_out and the packed outputs 16-byte aligned, scale tensors 4-byte aligned.  One launch, no workspace.
  * mm_moe_matmul: D[slots of e] = the product mm_matmul_grouped computes for group e, on the same kernel family -- bit for bit when
  *   K <= 512, for an expert of more than 64 rows, and whenever the two streaming launches split K over the same number of waves (4 when
  *   ceil(N / 32) * groups >= CUs and the tier is above 16 rows, else 8; here tier and groups come from max_rows and min(E, n, 8), there
@@ -467,6 +477,9 @@ size_t mm_moe_sf_bytes(int num_rows, int num_experts, int Kseg);
 int mm_moe_quantize(const void *src_bf16, const int32_t *row_of_slot, const int32_t *expert_offsets, const mm_moe_expert *expert_table,
                     int num_experts, int num_rows, int src_rows, int K, int KN, int KS, int KO, int mode, uint8_t *oN, uint8_t *oS,
                     uint8_t *oO, uint8_t *sfN, uint8_t *sfS, uint8_t *sfO, mm_stream_t stream);
+int mm_moe_activate_quantize(const void *a_bf16, const void *b_bf16, const int32_t *expert_offsets, const mm_moe_expert *expert_table,
+                             int num_experts, int num_rows, int K, int KN, int KS, int KO, uint8_t *oN, uint8_t *oS, uint8_t *oO,
+                             uint8_t *sfN, uint8_t *sfS, uint8_t *sfO, void *h_out_bf16, mm_stream_t stream);
 int mm_moe_matmul_supported(int max_rows, int N, int KN, int KS, int KO, int wmode);
 int mm_moe_matmul(const uint8_t *AN, const uint8_t *AS, const uint8_t *AO, const uint8_t *SFAN, const uint8_t *SFAS, const uint8_t *SFAO,
                   const int32_t *expert_offsets, const mm_moe_expert *expert_table, int num_experts, int num_rows, int max_rows, int N,

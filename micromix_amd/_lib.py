@@ -23,7 +23,7 @@ EXPORTS = (
     "mm_kv_append", "mm_paged_decode_workspace_bytes", "mm_paged_decode",
     "mm_paged_prefill_workspace_bytes", "mm_paged_prefill", "mm_rope_kv_append",
     "mm_moe_route", "mm_moe_plan", "mm_moe_gather", "mm_moe_combine",
-    "mm_moe_sf_bytes", "mm_moe_quantize", "mm_moe_matmul_supported", "mm_moe_matmul",
+    "mm_moe_sf_bytes", "mm_moe_quantize", "mm_moe_activate_quantize", "mm_moe_matmul_supported", "mm_moe_matmul",
 )
 # every symbol include/micromix_diag.h declares (libmicromix_diag.so: hardware probes for tests/tools, never used by the ops)
 DIAG_LIB_PATH = os.environ.get("MICROMIX_DIAG_LIB") or os.path.join(_PKG, "lib", "libmicromix_diag.so")
@@ -163,6 +163,8 @@ def load():
     lib.mm_moe_sf_bytes.argtypes = [i, i, i]
     lib.mm_moe_quantize.restype = i
     lib.mm_moe_quantize.argtypes = [vp] * 4 + [i] * 8 + [vp] * 7
+    lib.mm_moe_activate_quantize.restype = i
+    lib.mm_moe_activate_quantize.argtypes = [vp] * 4 + [i] * 6 + [vp] * 8
     lib.mm_moe_matmul_supported.restype = i
     lib.mm_moe_matmul_supported.argtypes = [i] * 6
     lib.mm_moe_matmul.restype = i

@@ -29,7 +29,7 @@ static bool split_ok(int K, int KN, int KS, int KO) {
 
 extern "C" {
 
-int mm_version(void) { return 640; /* 0.6.4: + mm_moe_quantize, mm_moe_matmul(_supported), mm_moe_sf_bytes (device-sized grouped launches: a hipGraph-capturable MoE block); 0.6.3: + mm_moe_route, mm_moe_plan, mm_moe_gather, mm_moe_combine (top-k routing, dispatch and combine of a sparse MoE block around mm_matmul_grouped); 0.6.2: + mm_rope_kv_append (RoPE + paged KV append in one launch, from the packed q | k | v projection); 0.6.1: + mm_paged_prefill(_workspace_bytes) (causal multi-token attention over the paged KV cache); 0.6.0: + mm_kv_append, mm_paged_decode(_workspace_bytes), enum mm_kv_dtype (paged int4 / bf16 KV cache); 0.5.1: + mm_rmsnorm_gate_up_activate_decode(_supported), mm_gate_up_activate_decode_supported; mm_gate_up_activate(_decode) one launch at decode sizes; 0.5.0: + the *_supported_w queries (weight mode); 0.4.0: + mm_rmsnorm_qlinear_decode(_supported) (0.3.0: + mm_gate_up_activate(_decode), mm_down_activate_decode, mm_matmul_ws_reset; 0.2.0: diagnostics moved to libmicromix_diag.so, + mm_test_function) */ }
+int mm_version(void) { return 650; /* 0.6.5: + mm_moe_activate_quantize (silu(a) * b computed while the expert quantizer stages the row: the activation of a capturable MoE block in one launch); 0.6.4: + mm_moe_quantize, mm_moe_matmul(_supported), mm_moe_sf_bytes (device-sized grouped launches: a hipGraph-capturable MoE block); 0.6.3: + mm_moe_route, mm_moe_plan, mm_moe_gather, mm_moe_combine (top-k routing, dispatch and combine of a sparse MoE block around mm_matmul_grouped); 0.6.2: + mm_rope_kv_append (RoPE + paged KV append in one launch, from the packed q | k | v projection); 0.6.1: + mm_paged_prefill(_workspace_bytes) (causal multi-token attention over the paged KV cache); 0.6.0: + mm_kv_append, mm_paged_decode(_workspace_bytes), enum mm_kv_dtype (paged int4 / bf16 KV cache); 0.5.1: + mm_rmsnorm_gate_up_activate_decode(_supported), mm_gate_up_activate_decode_supported; mm_gate_up_activate(_decode) one launch at decode sizes; 0.5.0: + the *_supported_w queries (weight mode); 0.4.0: + mm_rmsnorm_qlinear_decode(_supported) (0.3.0: + mm_gate_up_activate(_decode), mm_down_activate_decode, mm_matmul_ws_reset; 0.2.0: diagnostics moved to libmicromix_diag.so, + mm_test_function) */ }
 
 const char *mm_test_function(void) { return "Hello from test_function!"; /* bindings.cpp:700 */ }
 
@@ -758,6 +758,23 @@ int mm_moe_quantize(const void *src_bf16, const int32_t *row_of_slot, const int3
     hipError_t e = mm::launch_moe_quantize(src_bf16, row_of_slot, mg, src_rows, K, KN, KS, KO, mode == MM_QUANT_W4, oN, oS, oO, sfN, sfS, sfO,
                                            (hipStream_t)stream);
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_moe_quantize");
+}
+
+int mm_moe_activate_quantize(const void *a_bf16, const void *b_bf16, const int32_t *expert_offsets, const mm_moe_expert *expert_table,
+                             int num_experts, int num_rows, int K, int KN, int KS, int KO, uint8_t *oN, uint8_t *oS, uint8_t *oO, uint8_t *sfN,
+                             uint8_t *sfS, uint8_t *sfO, void *h_out_bf16, mm_stream_t stream) {
+    mm::MoeGroups mg;
+    if (K < 0) return MM_ERR_BAD_ARG;
+    if (int st = moe_groups(expert_offsets, expert_table, num_experts, num_rows, num_rows, &mg)) return st;
+    if (!split_ok(K, KN, KS, KO)) return MM_ERR_BAD_SPLIT;
+    if (K > 32768) return MM_ERR_BAD_ARG;
+    if (num_rows == 0) return MM_OK;
+    if (!a_bf16 || !b_bf16 || !expert_offsets || !expert_table || ((uintptr_t)expert_table & 7)) return MM_ERR_BAD_ARG;
+    if (((uintptr_t)a_bf16 | (uintptr_t)b_bf16 | (uintptr_t)h_out_bf16) & 15) return MM_ERR_BAD_ARG;
+    if ((KN && (!oN || !sfN)) || (KS && (!oS || !sfS)) || (KO && (!oO || !sfO))) return MM_ERR_BAD_ARG;
+    if ((((uintptr_t)oN | (uintptr_t)oS | (uintptr_t)oO) & 15) || (((uintptr_t)sfN | (uintptr_t)sfS | (uintptr_t)sfO) & 3)) return MM_ERR_BAD_ARG;
+    hipError_t e = mm::launch_moe_activate_quantize(a_bf16, b_bf16, h_out_bf16, mg, K, KN, KS, KO, oN, oS, oO, sfN, sfS, sfO, (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_moe_activate_quantize");
 }
 
 int mm_moe_matmul_supported(int max_rows, int N, int KN, int KS, int KO, int wmode) {

@@ -92,6 +92,21 @@ __device__ __forceinline__ float silu_mul(float x, float b) {
 #endif
 }
 
+// The MoE experts' activation (mm_moe_activate_quantize): the bf16 bits of bf16(bf16(silu(x)) * b), both roundings to nearest even --
+// what torch's bf16 `F.silu(a) * b` rounds (the reference's act_fn(w1(x)) * w3(x)), where silu_mul above keeps one fp32 value.
+// silu(x) = x * rcp(1 + exp2(-x log2 e)) with the same hardware exp2 / rcp.  v_rcp_f32 gives 0 for a result below 2^-126 and v_exp_f32
+// overflows from 2^128 on, which would turn silu(x) into -0 for every x < -87.3 although it is a nonzero bf16 down to x = -96: there
+// (t > 64, where 1 + 2^t == 2^t in fp32 anyway) the exponential is taken 2^64 smaller and the product scaled back by a multiply,
+// which rounds into the denormals as any fp32 multiply does.
+__device__ __forceinline__ uint32_t silu_mul_bf16(float x, float b) {
+    const float t = x * -1.4426950408889634f;
+    const bool far = t > 64.0f;
+    const float ex = __builtin_amdgcn_exp2f(far ? t - 64.0f : t);
+    float s = x * __builtin_amdgcn_rcpf(far ? ex : 1.0f + ex);
+    s = far ? s * 0x1p-64f : s;
+    return f32_to_bf16_bits(bf16_bits_to_f32(f32_to_bf16_bits(s)) * b);
+}
+
 // eight bf16 (one 16-byte chunk) -> fp32
 __device__ __forceinline__ void unpack8(const uint4 t, float *f) {
     const uint32_t w[4] = {t.x, t.y, t.z, t.w};

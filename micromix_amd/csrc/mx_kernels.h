@@ -174,6 +174,9 @@ __device__ __forceinline__ void moe_group_args(GemmArgs &a, const MoeGroups &mg,
 #endif
 hipError_t launch_moe_quantize(const void *src, const int *row_of_slot, const MoeGroups &mg, int src_rows, int K, int KN, int KS, int KO,
                                bool w4, uint8_t *oN, uint8_t *oS, uint8_t *oO, uint8_t *sfN, uint8_t *sfS, uint8_t *sfO, hipStream_t stream);
+// a, b bf16 [n, K] in slot order; h_out bf16 [n, K] or nullptr; mixed mode only
+hipError_t launch_moe_activate_quantize(const void *a, const void *b, void *h_out, const MoeGroups &mg, int K, int KN, int KS, int KO, uint8_t *oN,
+                                        uint8_t *oS, uint8_t *oO, uint8_t *sfN, uint8_t *sfS, uint8_t *sfO, hipStream_t stream);
 bool mx_gemm_stream_moe_supported(int max_m, const int K[3]);
 // `a`: X / SFX / D the packed buffers, K, N, round_per_segment, sfw_row_tiles filled in; groups of 1 .. min(max_rows, 64) rows
 hipError_t launch_mx_gemm_stream_moe(const GemmArgs &a, const MoeGroups &mg, bool w4, hipStream_t stream);

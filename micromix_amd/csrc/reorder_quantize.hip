@@ -16,6 +16,7 @@
 //  * all scale arithmetic is integer/exponent arithmetic (no log2/ceil/ldexp/divide); the element conversion is
 //    one hardware MX-converter instruction per 2 (fp4/fp8) or 32 (fp6) elements.
 #include "mx_common.h"
+#include "mx_direct_convert.h"
 #include "mx_group_convert.h"
 #include "mx_instrument.h"
 #include "mx_kernels.h"
@@ -27,13 +28,57 @@ namespace mm {
 __device__ unsigned long long *g_quant_clock = nullptr;
 #endif
 
+// How a row reaches its LDS image, 16 bytes (eight bf16) per lane and step.  load() issues the global loads of chunk c of row r (grow:
+// that row of src; zeros past the row's end) into a Regs, of which the body keeps four in flight; chunk() turns a Regs into the eight
+// bf16 to stage; keep() runs once the row's chunks are in LDS, for a hook that also stores what it staged.  chunk() and keep() are
+// called only for chunks of the row.  StageLoad, the plain load, is what every quantizer but moe_activate_quantize_kernel stages with.
+struct StageLoad {
+    typedef uint4 Regs;
+    __device__ __forceinline__ Regs load(const uint4 *__restrict__ grow, int, int, int c, bool in_row) const {
+        uint4 t = make_uint4(0u, 0u, 0u, 0u);
+        if (in_row) t = grow[c];
+        return t;
+    }
+    __device__ __forceinline__ uint4 chunk(Regs &t, int, int, int) const { return t; }
+    __device__ __forceinline__ void keep(const Regs &, int, int, int) const {}
+};
+// The staged row is computed: src is a, and h = bf16(bf16(silu(a)) * b) from the same row of b (silu_mul_bf16, mx_direct_convert.h),
+// 4 + 4 loads in flight per lane; with h_out the eight bf16 are also stored, unreordered -- after all four chunks are computed, so
+// that no chunk's arithmetic waits behind a store.
+struct StageSiluMul {
+    struct Regs { uint4 a, b; };
+    const uint16_t *__restrict__ b;     // [rows, K]
+    uint16_t *__restrict__ h_out;       // [rows, K] or nullptr
+    __device__ __forceinline__ Regs load(const uint4 *__restrict__ grow, int r, int K, int c, bool in_row) const {
+        Regs t = {make_uint4(0u, 0u, 0u, 0u), make_uint4(0u, 0u, 0u, 0u)};
+        if (in_row) {
+            t.a = grow[c];
+            t.b = reinterpret_cast<const uint4 *>(b + (size_t)r * K)[c];
+        }
+        return t;
+    }
+    __device__ __forceinline__ uint4 chunk(Regs &t, int, int, int) const {
+        float x[8], y[8];
+        unpack8(t.a, x);
+        unpack8(t.b, y);
+        uint32_t w[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) w[k] = silu_mul_bf16(x[2 * k], y[2 * k]) | (silu_mul_bf16(x[2 * k + 1], y[2 * k + 1]) << 16);
+        return t.a = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+    __device__ __forceinline__ void keep(const Regs &t, int r, int K, int c) const {
+        if (h_out != nullptr) reinterpret_cast<uint4 *>(h_out + (size_t)r * K)[c] = t.a;
+    }
+};
+
 // rows first_row, first_row + row_stride, ... of one [rows, K] matrix (one workgroup's share); sf_row0: the row of the scale tensors
-// that row 0 of the matrix is (0 everywhere but in moe_quantize_kernel, whose pointers are those of ONE row)
-template <bool W4>
+// that row 0 of the matrix is (0 everywhere but in the moe kernels, whose pointers are those of ONE row)
+template <bool W4, class Stage = StageLoad>
 __device__ __forceinline__ void reorder_quantize_body(const uint16_t *__restrict__ src, int rows, int K, const int16_t *__restrict__ idx,
                                                       int KN, int KS, int KO, uint8_t *__restrict__ oN, uint8_t *__restrict__ oS,
                                                       uint8_t *__restrict__ oO, uint8_t *__restrict__ sfN, uint8_t *__restrict__ sfS,
-                                                      uint8_t *__restrict__ sfO, int first_row, int row_stride, int sf_row0 = 0) {
+                                                      uint8_t *__restrict__ sfO, int first_row, int row_stride, int sf_row0 = 0,
+                                                      const Stage hook = Stage()) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int G = (KN + KS + KO) >> 5;  // groups produced; K is the input row length (>= 32 * G)
     const int g = threadIdx.x;
@@ -67,21 +112,24 @@ __device__ __forceinline__ void reorder_quantize_body(const uint16_t *__restrict
     unsigned long long *ck = g_quant_clock != nullptr ? g_quant_clock + 4 * (size_t)blockIdx.x : nullptr;
     if (ck != nullptr && threadIdx.x == 0) ck[0] = __builtin_amdgcn_s_memrealtime();
 #endif
-    uint4 stage[4];
+    typename Stage::Regs stage[4];
     int r = first_row;
     if (r < rows) {
         const uint4 *grow = reinterpret_cast<const uint4 *>(src + (size_t)r * K);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int c = threadIdx.x + i * blockDim.x;
-            uint4 t = make_uint4(0u, 0u, 0u, 0u);
-            if (c < nchunk) t = grow[c];
-            stage[i] = t;
+            stage[i] = hook.load(grow, r, K, c, c < nchunk);
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int c = threadIdx.x + i * blockDim.x;
-            if (c < nchunk) reinterpret_cast<uint4 *>(smem)[swizzle_chunk(c)] = stage[i];
+            if (c < nchunk) reinterpret_cast<uint4 *>(smem)[swizzle_chunk(c)] = hook.chunk(stage[i], r, K, c);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int c = threadIdx.x + i * blockDim.x;
+            if (c < nchunk) hook.keep(stage[i], r, K, c);
         }
     }
     __syncthreads();
@@ -95,9 +143,7 @@ __device__ __forceinline__ void reorder_quantize_body(const uint16_t *__restrict
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int c = threadIdx.x + i * blockDim.x;
-                uint4 t = make_uint4(0u, 0u, 0u, 0u);
-                if (c < nchunk) t = grow[c];
-                stage[i] = t;
+                stage[i] = hook.load(grow, rn, K, c, c < nchunk);
             }
         }
         if (active) {
@@ -135,7 +181,12 @@ __device__ __forceinline__ void reorder_quantize_body(const uint16_t *__restrict
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int c = threadIdx.x + i * blockDim.x;
-                if (c < nchunk) reinterpret_cast<uint4 *>(smem)[swizzle_chunk(c)] = stage[i];
+                if (c < nchunk) reinterpret_cast<uint4 *>(smem)[swizzle_chunk(c)] = hook.chunk(stage[i], rn, K, c);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int c = threadIdx.x + i * blockDim.x;
+                if (c < nchunk) hook.keep(stage[i], rn, K, c);
             }
         }
         __syncthreads();
@@ -189,6 +240,26 @@ moe_quantize_kernel(const uint16_t *__restrict__ src, const int *__restrict__ ro
     reorder_quantize_body<W4>(src + (size_t)t * K, 1, K, mg.table[e].idx, KN, KS, KO, oN + (size_t)s * (KN >> 1),
                               oS + (size_t)s * (W4 ? KS >> 1 : (KS >> 2) * 3), oO + (size_t)s * (W4 ? KO >> 1 : KO),
                               sfN + tile * (size_t)(KN << 2), sfS + tile * (size_t)(KS << 2), sfO + tile * (size_t)(KO << 2), 0, 1, r & 127);
+}
+
+// mm_moe_activate_quantize: moe_quantize_kernel<false> on a row that is computed while it is staged -- slot s of a and b gives
+// h = bf16(bf16(silu(a)) * b), which goes to h_out (when given) and through the expert's reorder index into packed row s and the
+// expert's run of scale tiles.  The same walk over the offsets and the same guards: a slot no expert owns is left untouched, h_out too.
+template <int MAXT>
+__global__ void __launch_bounds__(MAXT)
+moe_activate_quantize_kernel(const uint16_t *__restrict__ a, const uint16_t *__restrict__ b, uint16_t *__restrict__ h_out, MoeGroups mg, int K,
+                             int KN, int KS, int KO, uint8_t *oN, uint8_t *oS, uint8_t *oO, uint8_t *sfN, uint8_t *sfS, uint8_t *sfO) {
+    const int s = blockIdx.x;
+    int e = -1;
+    for (int i = 0; i < mg.E; ++i) e += mg.offsets[i] <= s ? 1 : 0;
+    if (e < 0) return;
+    const int lo = mg.offsets[e], hi = mg.offsets[e + 1];
+    if (lo < 0 || lo > s || s >= hi || hi > mg.n) return;
+    const int r = s - lo;
+    const size_t tile = (size_t)moe_sf_tile(lo, e) + (size_t)(r >> 7), row = (size_t)s * K;
+    reorder_quantize_body<false>(a + row, 1, K, mg.table[e].idx, KN, KS, KO, oN + (size_t)s * (KN >> 1), oS + (size_t)s * ((KS >> 2) * 3),
+                                 oO + (size_t)s * KO, sfN + tile * (size_t)(KN << 2), sfS + tile * (size_t)(KS << 2), sfO + tile * (size_t)(KO << 2),
+                                 0, 1, r & 127, StageSiluMul{b + row, h_out != nullptr ? h_out + row : nullptr});
 }
 
 #if MM_CLOCKS
@@ -254,6 +325,21 @@ hipError_t launch_moe_quantize(const void *src, const int *row_of_slot, const Mo
         if (hipError_t e = big_lds.ensure(reinterpret_cast<const void *>(moe_quantize_kernel<false, 1024>), 96 * 1024); e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(mg.n), dim3(threads), lds, stream, (const uint16_t *)src, row_of_slot, mg, src_rows, K, KN, KS, KO, oN, oS,
                        oO, sfN, sfS, sfO);
+    return hipGetLastError();
+}
+
+hipError_t launch_moe_activate_quantize(const void *a, const void *b, void *h_out, const MoeGroups &mg, int K, int KN, int KS, int KO, uint8_t *oN,
+                                        uint8_t *oS, uint8_t *oO, uint8_t *sfN, uint8_t *sfS, uint8_t *sfO, hipStream_t stream) {
+    if (mg.n == 0) return hipSuccess;
+    const int G = (KN + KS + KO) / 32, stagers = K / 32;
+    const int threads = ((G > stagers ? G : stagers) + 63) / 64 * 64;
+    const size_t lds = (size_t)K * 2 + (size_t)KS / 4 * 3 + KO;
+    auto kern = threads <= 256 ? moe_activate_quantize_kernel<256> : moe_activate_quantize_kernel<1024>;
+    static DynamicLdsOnce big_lds;
+    if (lds > 48 * 1024)
+        if (hipError_t e = big_lds.ensure(reinterpret_cast<const void *>(moe_activate_quantize_kernel<1024>), 96 * 1024); e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(mg.n), dim3(threads), lds, stream, (const uint16_t *)a, (const uint16_t *)b, (uint16_t *)h_out, mg, K, KN, KS, KO,
+                       oN, oS, oO, sfN, sfS, sfO);
     return hipGetLastError();
 }
 

@@ -32,7 +32,7 @@ __all__ = ["test_function", "matmul", "gate_up_activate", "interleave_gate_up", 
            "downproj_quantize_w", "downproj_quantize_w4", "rmsnorm_quantize_x", "qlinear_decode", "qlinear_decode_supported", "matmul_grouped", "reorder_quantize_x_grouped",
            "kv_append", "rope_kv_append", "paged_decode", "paged_decode_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes",
            "moe_route", "moe_plan", "moe_gather", "moe_combine",
-           "moe_expert_table", "moe_sf_bytes", "moe_quantize", "moe_matmul", "moe_matmul_supported"]
+           "moe_expert_table", "moe_sf_bytes", "moe_quantize", "moe_activate_quantize", "moe_matmul", "moe_matmul_supported"]
 
 
 def test_function():
@@ -1280,6 +1280,47 @@ def moe_quantize(src, row_of_slot, expert_offsets, table, n=None, *, mode="x", o
                                  src_rows, K, KN, KS, KO, _lib.MM_QUANT_W4 if w4 else _lib.MM_QUANT_MIXED, *(_ptr(t) for t in out), _stream_ptr(dev))
     if st:
         _lib.check(st, "moe_quantize")
+    return tuple(out)
+
+
+def moe_activate_quantize(a, b, expert_offsets, table, *, out=None, h_out=None):
+    """The experts' activation and the quantizer of their down-projection in one launch: a, b bf16 [n, K] in slot order (the outputs of
+    moe_matmul for w1 and w3), and for every slot s that an expert owns h[s] = bf16(bf16(silu(a[s])) * b[s]) -- torch's bf16
+    `F.silu(a) * b` except where the device exp2 / rcp move a value across a bf16 rounding boundary (include/micromix_hip.h) --
+    quantized as moe_quantize(h, None, expert_offsets, table) would.  Returns that 6-tuple, byte for byte; `out=` takes a 6-tuple to
+    fill.  h_out: None, or a bf16 [n, K] tensor (not a or b) that also receives h.  Slots no expert owns are left as they were in
+    every output.  Mixed mode only.  No host sync, no allocation sized by device data; capture-safe."""
+    lib = _lib.load()
+    if not (isinstance(a, torch.Tensor) and a.is_cuda and _ok(a, torch.bfloat16, a.get_device())):
+        _check_tensor(a, "a", torch.bfloat16)
+    if a.dim() != 2:
+        raise RuntimeError("a must be [n, K] bf16")
+    dev, (n, K) = a.device, a.shape
+    _moe_tensor(b, "b", torch.bfloat16, dev, (n, K))
+    E, (KN, KS, KO) = table.E, table.split
+    if K != table.K:
+        raise RuntimeError(f"a and b must be [n, {table.K}]")
+    _moe_tensor(expert_offsets, "expert_offsets", torch.int32, dev, (E + 1,))
+    if h_out is not None:
+        _moe_tensor(h_out, "h_out", torch.bfloat16, dev, (n, K))
+        if h_out.data_ptr() in (a.data_ptr(), b.data_ptr()) and n:
+            raise RuntimeError("h_out must not be a or b")
+    u8 = torch.uint8
+    widths = (KN // 2, KS // 4 * 3, KO)
+    if out is None:
+        out = tuple(torch.empty((n, w), dtype=u8, device=dev) for w in widths) + \
+            tuple(torch.empty((moe_sf_bytes(n, E, k),), dtype=u8, device=dev) for k in (KN, KS, KO))
+    else:
+        for t, w in zip(out[:3], widths):
+            _moe_tensor(t, "packed output", u8, dev, (n, w))
+        for t, k in zip(out[3:], (KN, KS, KO)):
+            if _moe_tensor(t, "scale output", u8, dev).numel() < moe_sf_bytes(n, E, k):
+                raise RuntimeError("a scale output is smaller than moe_sf_bytes(n, E, Kseg)")
+    with _on_device(dev.index):
+        st = lib.mm_moe_activate_quantize(_ptr(a), _ptr(b), _ptr(expert_offsets), _ptr(table.tensor), E, n, K, KN, KS, KO, *(_ptr(t) for t in out),
+                                          _ptr(h_out) if h_out is not None else None, _stream_ptr(dev))
+    if st:
+        _lib.check(st, "moe_activate_quantize")
     return tuple(out)
 
 

@@ -44,9 +44,16 @@ class SparseMoEBlock(nn.Module):
     family; the bits are the default mode's wherever both modes split K over the same number of waves, and always when K <= 512 --
     with a longer K an expert of at most 64 rows may differ in the order of its fp32 partial sums, because the default mode picks the
     streaming configuration from the rows of each call and this mode from T ("Which bits").
+
+    `fused_activation=True` (only with `capturable=True`, else ValueError) replaces the two torch launches of `F.silu(a) * b` and the
+    quantizer behind them by one launch, `mixedgemm.moe_activate_quantize`, wherever the block takes the device-sized path (where it
+    falls back to the host-sized path, the activation is torch's as before).  Which bits that gives: routing, plan, both
+    up-projections, the down-projection GEMM and the combine are the capturable block's, unchanged; `h` is the device formula's,
+    bf16(bf16(x * rcp(1 + exp2(-x log2 e))) * b), which equals torch's `F.silu(a) * b` except where the device `exp2` / `rcp` moves a
+    value across a bf16 rounding boundary (fewer than 1 element in 1 000, none by more than 3 bf16 ulps).
     """
 
-    def __init__(self, gate_weight, experts, top_k, gate_bias=None, capturable=False):
+    def __init__(self, gate_weight, experts, top_k, gate_bias=None, capturable=False, fused_activation=False):
         super().__init__()
         if isinstance(gate_weight, nn.Module):
             gate_weight, gate_bias = gate_weight.weight, (gate_weight.bias if gate_bias is None else gate_bias)
@@ -88,6 +95,9 @@ class SparseMoEBlock(nn.Module):
         self._B = [[tuple(getattr(layer, n) for n in _PACKED) for layer in col] for col in zip(*triples)]     # w1s, w3s, w2s
         self._bias = [[layer.bias for layer in col] if any(layer.bias is not None for layer in col) else None for col in zip(*triples)]
         self.capturable = bool(capturable)
+        self.fused_activation = bool(fused_activation)
+        if self.fused_activation and not self.capturable:
+            raise ValueError("fused_activation=True needs capturable=True: the fused activation exists for the device-sized launches only")
         self._supported = {}
         if self.capturable:      # the device tables of the three layers (mm_moe_expert[E]), built once; they keep their tensors alive
             self._tables = [mixedgemm.moe_expert_table(idx, B, *split, biases=bias) for idx, B, split, bias in
@@ -122,8 +132,11 @@ class SparseMoEBlock(nn.Module):
             q1 = mixedgemm.moe_quantize(x, sorted_token, offsets, t1)          # the row gather is the quantizer's
             a = mixedgemm.moe_matmul(q1, offsets, t1, T, rounding=self.rounding)
             b = mixedgemm.moe_matmul(q1, offsets, t3, T, rounding=self.rounding)
-            h = F.silu(a) * b
-            q2 = mixedgemm.moe_quantize(h, None, offsets, t2)
+            if self.fused_activation:
+                q2 = mixedgemm.moe_activate_quantize(a, b, offsets, t2)
+            else:
+                h = F.silu(a) * b
+                q2 = mixedgemm.moe_quantize(h, None, offsets, t2)
             y = mixedgemm.moe_matmul(q2, offsets, t2, T, rounding=self.rounding)
             return mixedgemm.moe_combine(y, ids, w, slot_of).reshape(shape), router_logits
         xs = mixedgemm.moe_gather(x, sorted_token)

@@ -2,6 +2,7 @@
 
     python tools/time_moe.py [out.txt]
     python tools/time_moe.py device [out.txt]     the capturable block (device-sized grouped launches), see device_main
+    python tools/time_moe.py activate [out.txt]   the fused silu * mul + expert quantizer (fused_activation=True), see activate_main
 
 Mixtral-8x7B shapes (H 4096, I 14336, E 8, top_k 2; splits as tests/test_model_shapes_gpu.py), T = 1, 16, 128, 4096, one set of weights.
 1. The block (`SparseMoEBlock.forward`: one host sync) and the reference's loop (model/qMixtralLayer.py:414-452, 502-519) written with
@@ -204,8 +205,70 @@ def device_main(out_path):
             f.write(f"# {torch.cuda.get_device_name(0)}, torch {torch.__version__}; Mixtral-8x7B shapes H {H} I {I} E {E} top_k {K}\n{text}\n{json.dumps(rows)}\n")
 
 
+def activate_main(out_path):
+    """mixedgemm.moe_activate_quantize against the three launches it replaces (F.silu, *, moe_quantize), and
+    SparseMoEBlock(capturable=True, fused_activation=True) against the capturable block (the parent's, line for line), one box, one
+    run.  Per T: the three launches and the one, ten calls per hipGraph (no host time), three runs each in alternation (their spread is
+    printed); the fused op's rate on its own 2 n I 2 input bytes as TB/s and as a fraction of 8 TB/s -- at T = 4 096 ten replays of
+    0.47 GB exceed the 256 MiB Infinity Cache, so that one is an HBM rate; both blocks eager, three runs each in alternation, and each as
+    ONE graph replay; and how many elements of h differ between the two (the device exp2 / rcp against torch's)."""
+    dev = torch.device("cuda:0")
+    experts = make_experts(dev)
+    g = torch.Generator(device=dev).manual_seed(1)
+    gate_w = (torch.randn((E, H), generator=g, device=dev) * 0.05).to(torch.bfloat16)
+    capt = SparseMoEBlock(gate_w, experts, K, capturable=True)
+    fused = SparseMoEBlock(gate_w, experts, K, capturable=True, fused_activation=True)
+    lines, rows = [], []
+    for T in (1, 16, 128, 4096):
+        x = torch.randn((T, H), generator=g, device=dev).to(torch.bfloat16)
+        iters = 20 if T >= 4096 else 50
+        n = T * K
+        ids, w = mixedgemm.moe_route(F.linear(x, gate_w), K)
+        off, tok, slot = mixedgemm.moe_plan(ids, E)
+        t1, t3, t2 = capt._tables
+        q1 = mixedgemm.moe_quantize(x, tok, off, t1)
+        a, b = mixedgemm.moe_matmul(q1, off, t1, T), mixedgemm.moe_matmul(q1, off, t3, T)      # the op's real inputs
+        h = torch.empty_like(a)
+        q2 = mixedgemm.moe_activate_quantize(a, b, off, t2, h_out=h)
+        differ = int((h.view(torch.int16) != (F.silu(a) * b).view(torch.int16)).sum())
+        q3 = tuple(torch.empty_like(t) for t in q2)
+        three = lambda: mixedgemm.moe_quantize(F.silu(a) * b, None, off, t2, out=q3)
+        one = lambda: mixedgemm.moe_activate_quantize(a, b, off, t2, out=q2)
+        op = {"three launches": [], "one launch": []}
+        eager = {"capturable": [], "fused": []}
+        for _ in range(3):
+            op["three launches"].append(graph_time(three))
+            op["one launch"].append(graph_time(one))
+        for _ in range(3):
+            eager["capturable"].append(timed(lambda: capt(x), iters))
+            eager["fused"].append(timed(lambda: fused(x), iters))
+        replay = {"capturable": graph_time(lambda: capt(x), calls=1, iters=iters), "fused": graph_time(lambda: fused(x), calls=1, iters=iters)}
+        in_bytes = 2 * n * I * 2
+        best = min(op["one launch"])
+        sp = lambda v: f"{min(v):8.1f} .. {max(v):8.1f}"
+        lines.append(f"T = {T} (n = {n}): {differ} of {n * I} elements of h differ from torch's F.silu(a) * b")
+        lines.append(f"  F.silu, *, moe_quantize (ten per graph)     {sp(op['three launches'])} us (three runs in alternation)")
+        lines.append(f"  moe_activate_quantize (ten per graph)       {sp(op['one launch'])} us: {in_bytes / best / 1e6:6.2f} TB/s on its {in_bytes / 1e6:.1f} MB of "
+                     f"input, {in_bytes / best / 8e6:5.3f} of 8 TB/s")
+        lines.append(f"  capturable block, eager                     {sp(eager['capturable'])} us")
+        lines.append(f"  capturable block, fused activation, eager   {sp(eager['fused'])} us")
+        lines.append(f"  one graph replay: capturable {replay['capturable']:8.1f} us, fused {replay['fused']:8.1f} us")
+        rows.append(dict(T=T, h_elements_differing=differ, three_launches_us=[round(v, 2) for v in op["three launches"]],
+                         one_launch_us=[round(v, 2) for v in op["one launch"]], input_bytes=in_bytes, input_tbps=round(in_bytes / best / 1e6, 3),
+                         capturable_eager_us=[round(v, 1) for v in eager["capturable"]], fused_eager_us=[round(v, 1) for v in eager["fused"]],
+                         replay_us={k: round(v, 1) for k, v in replay.items()}))
+    text = "\n".join(lines)
+    print(text)
+    print(json.dumps(rows))
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(f"# {torch.cuda.get_device_name(0)}, torch {torch.__version__}; Mixtral-8x7B shapes H {H} I {I} E {E} top_k {K}\n{text}\n{json.dumps(rows)}\n")
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "device":
         device_main(sys.argv[2] if len(sys.argv) > 2 else None)
+    elif len(sys.argv) > 1 and sys.argv[1] == "activate":
+        activate_main(sys.argv[2] if len(sys.argv) > 2 else None)
     else:
         main()
