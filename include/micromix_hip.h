@@ -140,6 +140,39 @@ int mm_rmsnorm_quantize(const void *X_bf16, const void *W_bf16, float eps, int r
                         uint8_t *sfO, mm_stream_t stream);
 
 /*
+ * mm_add_rmsnorm_quantize (version >= 660): mm_rmsnorm_quantize with the residual add of a decoder layer in front of the norm.
+ *   s[i] = bf16_rne(f32(x[i]) + f32(r[i]))   one IEEE fp32 add of the widened values, rounded to nearest even; subnormals kept;
+ *                                            every NaN result (inf - inf, a NaN operand) is 0x7FC0 -- torch's bf16 `x + r`, bit for bit wherever that is a number
+ * s is written to S_out_bf16 [rows, K] (the new residual stream) and normalised and quantized: the six outputs are byte for byte
+ * mm_rmsnorm_quantize applied to s, same summation order, integer rounding and flags.  The add happens while the row is staged, so s
+ * costs one write and no extra read.  Every row count runs the kernels that stage the row through registers (mm_rmsnorm_quantize
+ * takes an LDS-DMA kernel for small row counts, which cannot add on the way).
+ *   R_bf16 [rows, K]; S_out_bf16 must not overlap X_bf16 or R_bf16 (MM_ERR_BAD_ARG before any launch); X, R, S_out and W 16-byte
+ *   aligned (MM_ERR_BAD_ARG).  Everything else -- statuses included -- as mm_rmsnorm_quantize; rows == 0 is MM_OK with nothing written.
+ */
+int mm_add_rmsnorm_quantize(const void *X_bf16, const void *R_bf16, void *S_out_bf16, const void *W_bf16, float eps, int rows, int K,
+                            const int16_t *reorder_index, int KN, int KS, int KO, int flags, uint8_t *oN, uint8_t *oS, uint8_t *oO,
+                            uint8_t *sfN, uint8_t *sfS, uint8_t *sfO, mm_stream_t stream);
+
+/*
+ * The decode launches with the same add in front of their norm (version >= 660): mm_rmsnorm_qlinear_decode /
+ * mm_rmsnorm_gate_up_activate_decode on s = X + R, arguments as theirs plus R_bf16 and S_out_bf16 ([M, K]).  Every workgroup forms s for
+ * itself (the add is deterministic) and exactly one workgroup of the grid stores it to S_out.  D (the six buffers) are bit-identical
+ * to mm_add_rmsnorm_quantize followed by mm_matmul (mm_gate_up_activate).  Supported exactly where the plain forms are
+ * (mm_rmsnorm_qlinear_decode_supported_w / mm_rmsnorm_gate_up_activate_decode_supported).  S_out must not overlap X or R -- every
+ * workgroup re-reads both -- and R, S_out are 16-byte aligned like X: MM_ERR_BAD_ARG before any launch; M == 0 is MM_OK.
+ */
+int mm_add_rmsnorm_qlinear_decode(const void *X_bf16, const void *R_bf16, void *S_out_bf16, const void *norm_weight_bf16, float eps,
+                                  const int16_t *reorder_index, const uint8_t *BN, const uint8_t *BS, const uint8_t *BO, const uint8_t *SFBN,
+                                  const uint8_t *SFBS, const uint8_t *SFBO, int M, int N, int KN, int KS, int KO, int wmode, int flags,
+                                  const void *bias_bf16, void *D_bf16, mm_stream_t stream);
+int mm_add_rmsnorm_gate_up_activate_decode(const void *X_bf16, const void *R_bf16, void *S_out_bf16, const void *norm_weight_bf16, float eps,
+                                           const int16_t *reorder_index, const uint8_t *BN, const uint8_t *BS, const uint8_t *BO,
+                                           const uint8_t *SFBN, const uint8_t *SFBS, const uint8_t *SFBO, int M, int I, int KN, int KS, int KO,
+                                           int DN, int DS, int DO, int flags, uint8_t *oN, uint8_t *oS, uint8_t *oO, uint8_t *sfN, uint8_t *sfS,
+                                           uint8_t *sfO, void *workspace, size_t workspace_bytes, mm_stream_t stream);
+
+/*
  * Three-segment mixed-precision block-scaled GEMM:
  *   D[m,n] = bf16( sum over segments, blocks b:  2^(sfa[m,b]-127) * 2^(sfb[n,b]-127) * sum_{k in b} a[m,k]*b[n,k] ) (+ bias[n])
  *   A segments: AN [M,KN/2] fp4, AS [M,3KS/4] fp6(E3M2), AO [M,KO] fp8(E4M3)

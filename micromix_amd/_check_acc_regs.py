@@ -64,13 +64,14 @@ def check_counted(asm_text):
 # the model, so the scan is exact for straight-line code and silent across branches).
 # ---------------------------------------------------------------------------------------------------------
 STREAM_OWN = re.compile(r"^\s*(v_mfma_scale_f32_16x16x128_f8f6f4|v_accvgpr_read_b32|v_accvgpr_write_b32)\b")
-STREAM_KERNEL = re.compile(r"^(_ZN2mm6stream\d+(mx_gemm_stream_kernel|mx_gemm_stream_grouped_kernel|mx_gemm_stream_moe_kernel|mx_qlinear_stream_kernel|mx_qlinear_stream_rms_kernel)I((?:Li\d+E)+)Lb[01]E\w*):[^\n]*\n(.*?)\.end_amdhsa_kernel",
+STREAM_KERNEL = re.compile(r"^(_ZN2mm6stream\d+(mx_gemm_stream_kernel|mx_gemm_stream_grouped_kernel|mx_gemm_stream_moe_kernel|mx_qlinear_stream_kernel|mx_qlinear_stream_rms_kernel|mx_qlinear_stream_add_kernel)I((?:Li\d+E)+)Lb[01]E\w*):[^\n]*\n(.*?)\.end_amdhsa_kernel",
                            re.S | re.M)
 # ... and the launches with the activation inside (stream_body ACT: F = 4): mx_gemm_stream_act_kernel<T16 = 1, 2>,
 # mx_qlinear_stream_act_kernel<RMS>
-STREAM_ACT_KERNEL = re.compile(r"^(_ZN2mm6stream\d+(mx_gemm_stream_act_kernel|mx_qlinear_stream_act_kernel)I(?:Lb[01]|Li(\d+))EE\w*):[^\n]*\n(.*?)\.end_amdhsa_kernel",
+STREAM_ACT_KERNEL = re.compile(r"^(_ZN2mm6stream\d+(mx_gemm_stream_act_kernel|mx_qlinear_stream_act_kernel|mx_qlinear_stream_act_add_kernel)I(?:Lb[01]|Li(\d+))EE\w*):[^\n]*\n(.*?)\.end_amdhsa_kernel",
                                re.S | re.M)
 EXPECTED_STREAM_KERNELS = 68   # 22 plain + 18 grouped + 16 with the quantizer inside + 8 with norm and quantizer inside + 4 with the activation inside
+EXPECTED_STREAM_ADD_KERNELS = 9        # ... and, counted by name as well: the norm variants with the residual add in front (8 + the one with the activation inside)
 EXPECTED_STREAM_MOE_KERNELS = 18      # ... and, counted by name on top of those, the device-sized launches: the 18 configurations of the grouped ones
 VMEM = re.compile(r"^\s*(buffer_|global_|scratch_|flat_)(load|store|atomic)")
 
@@ -238,11 +239,16 @@ def verify_stream(asm_text):
     if len(examined) < EXPECTED_STREAM_KERNELS:
         raise RuntimeError(f"accumulator-register check found {len(examined)} streaming kernels, expected >= {EXPECTED_STREAM_KERNELS} "
                            "(kernel names changed? update micromix_amd/_check_acc_regs.py)")
+    add = [sym for sym in examined if "mx_qlinear_stream_add_kernel" in sym or "mx_qlinear_stream_act_add_kernel" in sym]
+    if len(add) < EXPECTED_STREAM_ADD_KERNELS:
+        raise RuntimeError(f"accumulator-register check found {len(add)} streaming kernels with the residual add, expected >= {EXPECTED_STREAM_ADD_KERNELS} "
+                           "(kernel names changed? update micromix_amd/_check_acc_regs.py)")
+    examined = [sym for sym in examined if sym not in add]
     moe = [sym for sym in examined if "mx_gemm_stream_moe_kernel" in sym]
     if len(moe) < EXPECTED_STREAM_MOE_KERNELS or len(examined) - len(moe) < EXPECTED_STREAM_KERNELS:
         raise RuntimeError(f"accumulator-register check found {len(moe)} device-sized streaming kernels and {len(examined) - len(moe)} others, expected "
                            f">= {EXPECTED_STREAM_MOE_KERNELS} and >= {EXPECTED_STREAM_KERNELS} (kernel names changed? update micromix_amd/_check_acc_regs.py)")
-    return len(examined)
+    return len(examined) + len(add)
 
 
 # tile kernels with asm-owned accumulators per translation unit

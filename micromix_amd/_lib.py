@@ -18,7 +18,7 @@ EXPORTS = (
     "mm_sf_bytes_x", "mm_sf_bytes_w", "mm_sf_offset",
     "mm_reorder_quantize", "mm_reorder_quantize_gather", "mm_activate_quantize", "mm_downproj_quantize", "mm_matmul",
     "mm_matmul_ws", "mm_matmul_workspace_bytes", "mm_matmul_ws_reset",
-    "mm_gate_up_activate", "mm_gate_up_activate_decode", "mm_rmsnorm_gate_up_activate_decode", "mm_rmsnorm_gate_up_activate_decode_supported", "mm_gate_up_activate_decode_supported", "mm_down_activate_decode", "mm_down_activate_decode_supported", "mm_down_activate_decode_supported_w", "mm_gate_up_activate_workspace_bytes", "mm_gate_up_activate_describe", "mm_rmsnorm_quantize", "mm_qlinear_decode", "mm_qlinear_decode_supported", "mm_qlinear_decode_supported_w", "mm_rmsnorm_qlinear_decode", "mm_rmsnorm_qlinear_decode_supported", "mm_rmsnorm_qlinear_decode_supported_w", "mm_matmul_grouped", "mm_reorder_quantize_grouped",
+    "mm_gate_up_activate", "mm_gate_up_activate_decode", "mm_rmsnorm_gate_up_activate_decode", "mm_rmsnorm_gate_up_activate_decode_supported", "mm_gate_up_activate_decode_supported", "mm_down_activate_decode", "mm_down_activate_decode_supported", "mm_down_activate_decode_supported_w", "mm_gate_up_activate_workspace_bytes", "mm_gate_up_activate_describe", "mm_rmsnorm_quantize", "mm_add_rmsnorm_quantize", "mm_add_rmsnorm_qlinear_decode", "mm_add_rmsnorm_gate_up_activate_decode", "mm_qlinear_decode", "mm_qlinear_decode_supported", "mm_qlinear_decode_supported_w", "mm_rmsnorm_qlinear_decode", "mm_rmsnorm_qlinear_decode_supported", "mm_rmsnorm_qlinear_decode_supported_w", "mm_matmul_grouped", "mm_reorder_quantize_grouped",
     "mm_matmul_describe", "mm_test_function", "mm_diag_set_kernel_events",
     "mm_kv_append", "mm_paged_decode_workspace_bytes", "mm_paged_decode",
     "mm_paged_prefill_workspace_bytes", "mm_paged_prefill", "mm_rope_kv_append",
@@ -91,6 +91,12 @@ def load():
     lib.mm_matmul.argtypes = [vp] * 12 + [i] * 7 + [vp, vp, vp]
     lib.mm_rmsnorm_quantize.restype = i
     lib.mm_rmsnorm_quantize.argtypes = [vp, vp, ctypes.c_float, i, i, vp, i, i, i, i] + [vp] * 7
+    lib.mm_add_rmsnorm_quantize.restype = i
+    lib.mm_add_rmsnorm_quantize.argtypes = [vp, vp, vp, vp, ctypes.c_float, i, i, vp, i, i, i, i] + [vp] * 7
+    lib.mm_add_rmsnorm_qlinear_decode.restype = i
+    lib.mm_add_rmsnorm_qlinear_decode.argtypes = [vp, vp, vp, vp, ctypes.c_float] + [vp] * 7 + [i] * 7 + [vp, vp, vp]
+    lib.mm_add_rmsnorm_gate_up_activate_decode.restype = i
+    lib.mm_add_rmsnorm_gate_up_activate_decode.argtypes = [vp, vp, vp, vp, ctypes.c_float] + [vp] * 7 + [i] * 9 + [vp] * 7 + [ctypes.c_size_t, vp]
     lib.mm_qlinear_decode.restype = i
     lib.mm_qlinear_decode.argtypes = [vp] * 8 + [i] * 7 + [vp, vp, vp]
     lib.mm_qlinear_decode_supported.restype = i

@@ -29,7 +29,7 @@ static bool split_ok(int K, int KN, int KS, int KO) {
 
 extern "C" {
 
-int mm_version(void) { return 650; /* 0.6.5: + mm_moe_activate_quantize (silu(a) * b computed while the expert quantizer stages the row: the activation of a capturable MoE block in one launch); 0.6.4: + mm_moe_quantize, mm_moe_matmul(_supported), mm_moe_sf_bytes (device-sized grouped launches: a hipGraph-capturable MoE block); 0.6.3: + mm_moe_route, mm_moe_plan, mm_moe_gather, mm_moe_combine (top-k routing, dispatch and combine of a sparse MoE block around mm_matmul_grouped); 0.6.2: + mm_rope_kv_append (RoPE + paged KV append in one launch, from the packed q | k | v projection); 0.6.1: + mm_paged_prefill(_workspace_bytes) (causal multi-token attention over the paged KV cache); 0.6.0: + mm_kv_append, mm_paged_decode(_workspace_bytes), enum mm_kv_dtype (paged int4 / bf16 KV cache); 0.5.1: + mm_rmsnorm_gate_up_activate_decode(_supported), mm_gate_up_activate_decode_supported; mm_gate_up_activate(_decode) one launch at decode sizes; 0.5.0: + the *_supported_w queries (weight mode); 0.4.0: + mm_rmsnorm_qlinear_decode(_supported) (0.3.0: + mm_gate_up_activate(_decode), mm_down_activate_decode, mm_matmul_ws_reset; 0.2.0: diagnostics moved to libmicromix_diag.so, + mm_test_function) */ }
+int mm_version(void) { return 660; /* 0.6.6: + mm_add_rmsnorm_quantize, mm_add_rmsnorm_qlinear_decode, mm_add_rmsnorm_gate_up_activate_decode (the residual add in front of the norm, s = x + r, computed while the quantizer stages the row; s leaves as the new residual stream); 0.6.5: + mm_moe_activate_quantize (silu(a) * b computed while the expert quantizer stages the row: the activation of a capturable MoE block in one launch); 0.6.4: + mm_moe_quantize, mm_moe_matmul(_supported), mm_moe_sf_bytes (device-sized grouped launches: a hipGraph-capturable MoE block); 0.6.3: + mm_moe_route, mm_moe_plan, mm_moe_gather, mm_moe_combine (top-k routing, dispatch and combine of a sparse MoE block around mm_matmul_grouped); 0.6.2: + mm_rope_kv_append (RoPE + paged KV append in one launch, from the packed q | k | v projection); 0.6.1: + mm_paged_prefill(_workspace_bytes) (causal multi-token attention over the paged KV cache); 0.6.0: + mm_kv_append, mm_paged_decode(_workspace_bytes), enum mm_kv_dtype (paged int4 / bf16 KV cache); 0.5.1: + mm_rmsnorm_gate_up_activate_decode(_supported), mm_gate_up_activate_decode_supported; mm_gate_up_activate(_decode) one launch at decode sizes; 0.5.0: + the *_supported_w queries (weight mode); 0.4.0: + mm_rmsnorm_qlinear_decode(_supported) (0.3.0: + mm_gate_up_activate(_decode), mm_down_activate_decode, mm_matmul_ws_reset; 0.2.0: diagnostics moved to libmicromix_diag.so, + mm_test_function) */ }
 
 const char *mm_test_function(void) { return "Hello from test_function!"; /* bindings.cpp:700 */ }
 
@@ -113,6 +113,29 @@ int mm_rmsnorm_quantize(const void *X_bf16, const void *W_bf16, float eps, int r
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_rmsnorm_quantize");
 }
 
+// [a, a + na) and [b, b + nb) share a byte
+static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+
+int mm_add_rmsnorm_quantize(const void *X_bf16, const void *R_bf16, void *S_out_bf16, const void *W_bf16, float eps, int rows, int K,
+                            const int16_t *reorder_index, int KN, int KS, int KO, int flags, uint8_t *oN, uint8_t *oS, uint8_t *oO,
+                            uint8_t *sfN, uint8_t *sfS, uint8_t *sfO, mm_stream_t stream) {
+    if (!split_ok(K, KN, KS, KO)) return MM_ERR_BAD_SPLIT;
+    if (rows < 0 || K > 32768) return MM_ERR_BAD_ARG;
+    if (rows == 0) return MM_OK;
+    if (!X_bf16 || !R_bf16 || !S_out_bf16 || !W_bf16 || !reorder_index) return MM_ERR_BAD_ARG;
+    if ((KN && (!oN || !sfN)) || (KS && (!oS || !sfS)) || (KO && (!oO || !sfO))) return MM_ERR_BAD_ARG;
+    // rows travel in 16-byte pieces; K % 128 == 0 keeps every row of an aligned tensor aligned
+    if (((uintptr_t)X_bf16 & 15) || ((uintptr_t)R_bf16 & 15) || ((uintptr_t)S_out_bf16 & 15) || ((uintptr_t)W_bf16 & 15)) return MM_ERR_BAD_ARG;
+    const size_t bytes = (size_t)rows * (size_t)K * 2u;
+    if (ranges_overlap(S_out_bf16, bytes, X_bf16, bytes) || ranges_overlap(S_out_bf16, bytes, R_bf16, bytes)) return MM_ERR_BAD_ARG;
+    hipError_t e = mm::launch_add_rmsnorm_quantize(X_bf16, R_bf16, S_out_bf16, W_bf16, eps, rows, K, reorder_index, KN, KS, KO,
+                                                   !(flags & MM_RMS_NO_INTEGER_ROUND), oN, oS, oO, sfN, sfS, sfO, (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_add_rmsnorm_quantize");
+}
+
 // (the five-argument queries answer for the matching-precision weight mode, whose ring / reduction tail is the larger one: what they
 // accept launches in either mode; the _w forms take the weight mode and accept the long-K fp4 shapes the 48 KB tail leaves room for)
 int mm_qlinear_decode_supported_w(int M, int N, int KN, int KS, int KO, int wmode) {
@@ -167,6 +190,36 @@ int mm_rmsnorm_qlinear_decode(const void *X_bf16, const void *norm_weight_bf16, 
     hipError_t e = mm::launch_qlinear_decode(X_bf16, reorder_index, W, SFW, M, N, K, weights_fp4(wmode, KS, KO),
                                              (flags & MM_ROUND_ONCE) ? 0 : 1, bias_bf16, D_bf16, (hipStream_t)stream, norm);
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_rmsnorm_qlinear_decode");
+}
+
+// S_out of the add_ decode entries: non-null, 16-byte aligned like R, and clear of X and R -- every workgroup re-reads both while
+// workgroup 0 writes S_out, so an in-place update would race
+static bool residual_ok(const void *X, const void *R, const void *S_out, int M, int K) {
+    if (!R || !S_out || ((uintptr_t)R & 15) || ((uintptr_t)S_out & 15)) return false;
+    const size_t bytes = (size_t)M * (size_t)K * 2u;
+    return !ranges_overlap(S_out, bytes, X, bytes) && !ranges_overlap(S_out, bytes, R, bytes);
+}
+
+int mm_add_rmsnorm_qlinear_decode(const void *X_bf16, const void *R_bf16, void *S_out_bf16, const void *norm_weight_bf16, float eps,
+                                  const int16_t *reorder_index, const uint8_t *BN, const uint8_t *BS, const uint8_t *BO, const uint8_t *SFBN,
+                                  const uint8_t *SFBS, const uint8_t *SFBO, int M, int N, int KN, int KS, int KO, int wmode, int flags,
+                                  const void *bias_bf16, void *D_bf16, mm_stream_t stream) {
+    if (M < 0 || N < 0 || KN < 0 || KS < 0 || KO < 0) return MM_ERR_BAD_ARG;
+    if ((KN % 128) || (KS % 128) || (KO % 128) || KN + KS + KO == 0) return MM_ERR_BAD_SPLIT;
+    if (wmode != MM_W_MATCH && wmode != MM_W_FP4) return MM_ERR_BAD_ARG;
+    if (flags & ~(MM_ROUND_ONCE | MM_NORM_NO_INTEGER_ROUND)) return MM_ERR_BAD_ARG;
+    if (M == 0 || N == 0) return MM_OK;
+    if (!mm_rmsnorm_qlinear_decode_supported_w(M, N, KN, KS, KO, wmode)) return MM_ERR_UNSUPPORTED;
+    if (!X_bf16 || !norm_weight_bf16 || !reorder_index || !D_bf16) return MM_ERR_BAD_ARG;
+    if (((uintptr_t)X_bf16 & 15) || ((uintptr_t)norm_weight_bf16 & 15)) return MM_ERR_BAD_ARG;
+    if (!residual_ok(X_bf16, R_bf16, S_out_bf16, M, KN + KS + KO)) return MM_ERR_BAD_ARG;
+    if ((KN && (!BN || !SFBN)) || (KS && (!BS || !SFBS)) || (KO && (!BO || !SFBO))) return MM_ERR_BAD_ARG;
+    const uint8_t *W[3] = {BN, BS, BO}, *SFW[3] = {SFBN, SFBS, SFBO};
+    const int K[3] = {KN, KS, KO};
+    const mm::NormArgs norm = {norm_weight_bf16, eps, (flags & MM_NORM_NO_INTEGER_ROUND) ? 0 : 1, R_bf16, S_out_bf16};
+    hipError_t e = mm::launch_qlinear_decode(X_bf16, reorder_index, W, SFW, M, N, K, weights_fp4(wmode, KS, KO),
+                                             (flags & MM_ROUND_ONCE) ? 0 : 1, bias_bf16, D_bf16, (hipStream_t)stream, norm);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_add_rmsnorm_qlinear_decode");
 }
 
 size_t mm_matmul_workspace_bytes(int M, int N, int KN, int KS, int KO, int wmode, int flags) {
@@ -418,6 +471,39 @@ int mm_rmsnorm_gate_up_activate_decode(const void *X_bf16, const void *norm_weig
     hipError_t e = mm::launch_direct_quantize(workspace, (const uint16_t *)workspace + 128, M, DN, DS, DO, 3, oN, oS, oO, sfN, sfS, sfO,
                                               (hipStream_t)stream);
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_rmsnorm_gate_up_activate_decode");
+}
+
+int mm_add_rmsnorm_gate_up_activate_decode(const void *X_bf16, const void *R_bf16, void *S_out_bf16, const void *norm_weight_bf16, float eps,
+                                           const int16_t *reorder_index, const uint8_t *BN, const uint8_t *BS, const uint8_t *BO,
+                                           const uint8_t *SFBN, const uint8_t *SFBS, const uint8_t *SFBO, int M, int I, int KN, int KS, int KO,
+                                           int DN, int DS, int DO, int flags, uint8_t *oN, uint8_t *oS, uint8_t *oO, uint8_t *sfN, uint8_t *sfS,
+                                           uint8_t *sfO, void *workspace, size_t workspace_bytes, mm_stream_t stream) {
+    if (M < 0 || I < 0 || KN < 0 || KS < 0 || KO < 0) return MM_ERR_BAD_ARG;
+    if ((KN % 128) || (KS % 128) || (KO % 128) || KN + KS + KO == 0) return MM_ERR_BAD_SPLIT;
+    if (!split_ok(DN + DS + DO, DN, DS, DO) || DN + DS + DO != I) return MM_ERR_BAD_SPLIT;
+    if (flags & ~(MM_ROUND_ONCE | MM_NORM_NO_INTEGER_ROUND)) return MM_ERR_BAD_ARG;
+    if (M == 0) return MM_OK;
+    const int Kin[3] = {KN, KS, KO};
+    if (!mm_rmsnorm_gate_up_activate_decode_supported(M, I, KN, KS, KO)) return MM_ERR_UNSUPPORTED;
+    if (!X_bf16 || !norm_weight_bf16 || !reorder_index || ((uintptr_t)X_bf16 & 15) || ((uintptr_t)norm_weight_bf16 & 15)) return MM_ERR_BAD_ARG;
+    if (!residual_ok(X_bf16, R_bf16, S_out_bf16, M, KN + KS + KO)) return MM_ERR_BAD_ARG;
+    if ((KN && (!BN || !SFBN)) || (KS && (!BS || !SFBS)) || (KO && (!BO || !SFBO))) return MM_ERR_BAD_ARG;
+    if ((DN && (!oN || !sfN)) || (DS && (!oS || !sfS)) || (DO && (!oO || !sfO))) return MM_ERR_BAD_ARG;
+    if (mm::gate_up_act_stream_supported(M, 2 * I, Kin, true, true)) {
+        const mm::GemmArgs a = act_stream_args(BN, BS, BO, SFBN, SFBS, SFBO, M, I, KN, KS, KO, DN, DS, DO, flags, oN, oS, oO, sfN, sfS, sfO);
+        const mm::NormArgs norm = {norm_weight_bf16, eps, (flags & MM_NORM_NO_INTEGER_ROUND) ? 0 : 1, R_bf16, S_out_bf16};
+        hipError_t e = mm::launch_gate_up_act_stream_decode(X_bf16, reorder_index, a, (hipStream_t)stream, norm);
+        return e == hipSuccess ? MM_OK : fail_hip(e, "mm_add_rmsnorm_gate_up_activate_decode");
+    }
+    // two launches: add + norm + quantize + gate | up GEMM into the scratch, then the activation quantizer on it (the same bytes)
+    const int N = 2 * I;
+    if (!workspace || workspace_bytes < (size_t)M * N * sizeof(uint16_t) || ((uintptr_t)workspace & 15)) return MM_ERR_BAD_ARG;
+    const int st = mm_add_rmsnorm_qlinear_decode(X_bf16, R_bf16, S_out_bf16, norm_weight_bf16, eps, reorder_index, BN, BS, BO, SFBN, SFBS, SFBO, M, N,
+                                                 KN, KS, KO, MM_W_FP4, flags, nullptr, workspace, stream);
+    if (st != MM_OK) return st;
+    hipError_t e = mm::launch_direct_quantize(workspace, (const uint16_t *)workspace + 128, M, DN, DS, DO, 3, oN, oS, oO, sfN, sfS, sfO,
+                                              (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_add_rmsnorm_gate_up_activate_decode");
 }
 
 int mm_down_activate_decode_supported_w(int M, int N, int DN, int DS, int DO, int wmode) {

@@ -30,6 +30,12 @@ struct QuantIn {
     const uint16_t *norm_w; // [K] bf16, or null: no norm
     float eps;
     int int_round;          // the reference's round() before the conversion (0: MM_RMS_NO_INTEGER_ROUND)
+    // The residual add in front of the norm (the ADD forms of the two row-staging phases; mm_add_rmsnorm_qlinear_decode): what is staged,
+    // summed and quantized is s = bf16(X + R) (add_bf16x8, mx_rms_convert.h).  Every workgroup forms s for itself -- the add is
+    // deterministic, so all of them quantize the same bits -- and workgroup 0 alone stores it to S_out, which therefore may not overlap
+    // X or R: the other workgroups are still reading them.
+    const uint16_t *R;      // [M, K] bf16 (ADD only)
+    uint16_t *S_out;        // [M, K] bf16 (ADD only)
 };
 constexpr int EARLY_RL = 2;      // 16-byte chunks of the rows per thread (M K / 8 <= NT * EARLY_RL follows from early_fits)
 constexpr int EARLY_WL = 2;      // with the norm: 16-byte chunks of the weight vector per thread (K / 8 <= NT * EARLY_WL)
@@ -265,7 +271,8 @@ struct NoHook { __device__ __forceinline__ void operator()() const {} };
 // work per lane does not halve, so pairs lose wherever they double the passes (q/o at M = 4: 6.4 -> 7.3 us, M = 8: 8.5 -> 9.9) and win
 // where they do not (M = 1, 2).  Both paths in one kernel cost the larger one's registers: kernels at one workgroup per CU anyway take 0,
 // the norm's 32-feature streaming kernel 2 (its register count decides between one and two workgroups per CU).
-template <int NT, bool RMS = false, int LPG = 0, class Hook = NoHook>
+// ADD: the rows staged are X + R (QuantIn::R / S_out); a template parameter for the same reason as RMS.
+template <int NT, bool RMS = false, int LPG = 0, bool ADD = false, class Hook = NoHook>
 __device__ __forceinline__ LdsMap quantize_rows_to_lds(const QuantIn &a, uint8_t *smem, Hook staged = Hook()) {
     const int Kt = a.K[0] + a.K[1] + a.K[2], Gt = Kt >> 5;
     const int gN = a.K[0] >> 5, gS = a.K[1] >> 5;
@@ -300,6 +307,17 @@ __device__ __forceinline__ LdsMap quantize_rows_to_lds(const QuantIn &a, uint8_t
             else if constexpr (LPG != 2) load_ix(a.idx, t0 % Gt, ix);
         }
         const uint4 *grow = reinterpret_cast<const uint4 *>(a.X + (size_t)r0 * Kt);
+        if constexpr (ADD) {
+            static_assert(!ADD || RMS, "the residual add belongs to the norm");
+            const uint4 *rrow = reinterpret_cast<const uint4 *>(a.R + (size_t)r0 * Kt);
+            uint4 *srow = reinterpret_cast<uint4 *>(a.S_out + (size_t)r0 * Kt);
+            const bool writer = blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0;
+            for (int c = threadIdx.x; c < nr * (Kt >> 3); c += NT) {
+                const uint4 s = add_bf16x8(grow[c], rrow[c]);
+                reinterpret_cast<uint4 *>(stage)[c] = s;
+                if (writer) srow[c] = s;
+            }
+        } else
         for (int c = threadIdx.x; c < nr * (Kt >> 3); c += NT) reinterpret_cast<uint4 *>(stage)[c] = grow[c];
         if constexpr (rms) if (r0 == 0)
             for (int c = threadIdx.x; c < (Kt >> 3); c += NT) reinterpret_cast<uint4 *>(wvec)[c] = reinterpret_cast<const uint4 *>(a.norm_w)[c];
@@ -398,7 +416,7 @@ __device__ __forceinline__ void wait_vmcnt_range(int n) {
 }
 __device__ __forceinline__ void wait_vmcnt(int n) { wait_vmcnt_range<0, 63>(n < 0 ? 0 : (n > 63 ? 63 : n)); }
 __host__ __device__ inline bool early_fits(int M, int Kt, int NT, int npass) { return 2 * (size_t)M * (size_t)(Kt >> 5) <= (size_t)NT * npass; }
-template <int NT, bool RMS, int NPASS, class Request, class Landed>
+template <int NT, bool RMS, int NPASS, bool ADD = false, class Request, class Landed>
 __device__ __forceinline__ LdsMap quantize_rows_early(const QuantIn &a, uint8_t *smem, Request request, Landed landed) {
     const int Kt = a.K[0] + a.K[1] + a.K[2], Gt = Kt >> 5;
     const int gN = a.K[0] >> 5, gS = a.K[1] >> 5;
@@ -443,6 +461,16 @@ __device__ __forceinline__ LdsMap quantize_rows_early(const QuantIn &a, uint8_t 
         const int c = row_chunk(k);
         rq[k] = gload16(grow + (c >= 0 ? c : chunks - 1));       // (nothing to load: the last chunk again, not stored)
     }
+    // ADD: the same chunks of the residual beside them (RL more loads in front of the caller's requests, certified by the same wait)
+    static_assert(!ADD || RMS, "the residual add belongs to the norm");
+    [[maybe_unused]] dq_v4u rres[ADD ? RL : 1];
+    if constexpr (ADD) {
+#pragma unroll
+        for (int k = 0; k < RL; ++k) {
+            const int c = row_chunk(k);
+            rres[k] = gload16(reinterpret_cast<const uint4 *>(a.R) + (c >= 0 ? c : chunks - 1));
+        }
+    }
     if constexpr (rms) {                                                                                   // (see the wait below)
 #pragma unroll
         for (int k = 0; k < WL; ++k) {
@@ -462,6 +490,17 @@ __device__ __forceinline__ LdsMap quantize_rows_early(const QuantIn &a, uint8_t 
     if constexpr (rms) {
 #pragma unroll
         for (int k = 0; k < WL; ++k) { MM_DQ_DEVICE_ONLY(asm volatile("" : "+v"(wq[k]));) }
+    }
+    if constexpr (ADD) {      // rq becomes the sum: what is staged, what the partial sums below read, and -- from workgroup 0 -- S_out
+        const bool writer = blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0;
+#pragma unroll
+        for (int k = 0; k < RL; ++k) {
+            MM_DQ_DEVICE_ONLY(asm volatile("" : "+v"(rres[k]));)
+            const uint4 s = add_bf16x8(make_uint4(rq[k][0], rq[k][1], rq[k][2], rq[k][3]), make_uint4(rres[k][0], rres[k][1], rres[k][2], rres[k][3]));
+            rq[k] = dq_v4u{s.x, s.y, s.z, s.w};
+            const int c = row_chunk(k);
+            if (writer && c >= 0) reinterpret_cast<uint4 *>(a.S_out)[c] = s;
+        }
     }
 #pragma unroll
     for (int k = 0; k < RL; ++k) {

@@ -231,7 +231,7 @@ template <int NW> constexpr int EARLY_NPASS = NW <= 4 ? 2 : 1;
 // arithmetic of direct_quantize.hip), quantizes the group as mm_activate_quantize does and writes the consumer's (down_proj's) operand
 // bytes and scale byte -- a.act_o / a.act_sf / a.act_K -- instead of D.  The same bytes as GEMM -> mm_activate_quantize, one launch less,
 // and down_proj becomes a plain mm_matmul (M = 1: 7.3 us against 9.2 for mm_down_activate_decode).
-template <int F, int T16, int D, int NW, bool W4, bool QUANT = false, bool RMS = false, bool ACT = false>
+template <int F, int T16, int D, int NW, bool W4, bool QUANT = false, bool RMS = false, bool ACT = false, bool ADD = false>
 __device__ __forceinline__ void stream_body(const GemmArgs &a, const dq::QuantIn &qi = dq::QuantIn(), int qbytes = 0) {
     static_assert(T16 <= 4, "64 token rows: row groups 0 and 1 of the activation scale atoms, both in the 8 bytes a lane loads");
     static_assert(!QUANT || T16 == 1, "M <= 8");
@@ -489,10 +489,10 @@ __device__ __forceinline__ void stream_body(const GemmArgs &a, const dq::QuantIn
         if (!RMS && qi.mode == 1 && qi.early) L = dq::activate_rows_early<NT>(qi, smem_all, prime, [] {});
         else if (!RMS && qi.mode == 1) L = dq::activate_rows_to_lds<NT>(qi, smem_all, [&]() { prime(); });
         // (the ring's first slabs stay in front of the wait: from the landed hook as well, fused gate + up at M = 1 11.9 -> 12.4 us)
-        else if (qi.early) L = dq::quantize_rows_early<NT, RMS, EARLY_NPASS<NW>>(qi, smem_all, prime, scales);
+        else if (qi.early) L = dq::quantize_rows_early<NT, RMS, EARLY_NPASS<NW>, ADD>(qi, smem_all, prime, scales);
         // (whatever fits one pass of lane pairs went the early way: the staged path runs one lane per group -- except in the norm's
         // eight-wave 32-feature kernel, whose register count decides between one and two workgroups per CU)
-        else L = dq::quantize_rows_to_lds<NT, RMS, (RMS && NW == 8 && F == 2) ? 2 : 1>(qi, smem_all, [&]() { prime(); });
+        else L = dq::quantize_rows_to_lds<NT, RMS, (RMS && NW == 8 && F == 2) ? 2 : 1, ADD>(qi, smem_all, [&]() { prime(); });
         const int rr = li < a.M ? li : 0;
         qx[0] = L.opN + rr * L.pN + 16 * h;
         qx[1] = L.opS + rr * L.pS + 24 * h;
@@ -920,16 +920,26 @@ __global__ void __launch_bounds__(64 * NW) mx_qlinear_stream_rms_kernel(GemmArgs
     stream_body<F, 1, D, NW, W4, true, true>(a, qi, qbytes);
 }
 
+// ... and the residual add in front of that norm (mm_add_rmsnorm_qlinear_decode; dq::QuantIn::R / S_out): kernels of their own again
+template <int F, int D, int NW, bool W4>
+__global__ void __launch_bounds__(64 * NW) mx_qlinear_stream_add_kernel(GemmArgs a, dq::QuantIn qi, int qbytes) {
+    stream_body<F, 1, D, NW, W4, true, true, false, true>(a, qi, qbytes);
+}
+
 // ... and with the activation inside (ACT, see stream_body): the fused gate | up weight, 64 rows (32 gate + 32 up) x 4 waves
 template <bool RMS>
 __global__ void __launch_bounds__(256) mx_qlinear_stream_act_kernel(GemmArgs a, dq::QuantIn qi, int qbytes) {
     stream_body<4, 1, 2, 4, true, true, RMS, true>(a, qi, qbytes);
 }
+template <bool ADD>      // (mm_add_rmsnorm_gate_up_activate_decode: norm and residual add; instantiated with true only)
+__global__ void __launch_bounds__(256) mx_qlinear_stream_act_add_kernel(GemmArgs a, dq::QuantIn qi, int qbytes) {
+    stream_body<4, 1, 2, 4, true, true, true, true, ADD>(a, qi, qbytes);
+}
 template <int T16>
 __global__ void __launch_bounds__(256) mx_gemm_stream_act_kernel(GemmArgs a) { stream_body<4, T16, 2, 4, true, false, false, true>(a); }
 constexpr int ACT_GROUP_BYTES = 16 * 32 * 4;       // the 32 values of a group for up to 16 tokens, behind the reduction image
 
-template <int F, int D, int NW, bool W4, bool RMS = false, bool ACT = false>
+template <int F, int D, int NW, bool W4, bool RMS = false, bool ACT = false, bool ADD = false>
 static hipError_t launch_quant(const GemmArgs &a, dq::QuantIn qi, hipStream_t stream) {
     static_assert(!ACT || (F == 4 && D == 2 && NW == 4 && W4), "mx_qlinear_stream_act_kernel");
     if constexpr (ACT && !RMS) {
@@ -938,6 +948,10 @@ static hipError_t launch_quant(const GemmArgs &a, dq::QuantIn qi, hipStream_t st
     if constexpr (!ACT && !RMS && ((F == 4 && D == 2 && NW == 4) || (F == 2 && D == 2 && NW == 8) || (F == 1 && NW == 8 && (D == 3 || D == 4)))) {
         if (qi.norm_w != nullptr) return launch_quant<F, D, NW, W4, true>(a, qi, stream);      // (the configurations the default dispatch uses)
     }
+    if constexpr (RMS && !ADD) {      // (every norm variant has its variant with the residual add)
+        if (qi.R != nullptr) return launch_quant<F, D, NW, W4, true, ACT, true>(a, qi, stream);
+    }
+    if (!ADD && qi.R != nullptr) return hipErrorInvalidValue;
     if (!RMS && qi.norm_w != nullptr) return hipErrorInvalidValue;       // (a kernel-developer override picked a configuration without a norm variant)
     const int present = (a.K[0] ? 1 : 0) + (a.K[1] ? 1 : 0) + (a.K[2] ? 1 : 0);
     const size_t Kt = (size_t)a.K[0] + a.K[1] + a.K[2];
@@ -965,7 +979,9 @@ static hipError_t launch_quant(const GemmArgs &a, dq::QuantIn qi, hipStream_t st
     if (lds > LDS_WG) return hipErrorInvalidValue;      // (every mode: the supported() predicates keep callers away from this)
     static DynamicLdsOnce once;
     auto kern = [] {
-        if constexpr (ACT) return mx_qlinear_stream_act_kernel<RMS>;
+        if constexpr (ACT && ADD) return mx_qlinear_stream_act_add_kernel<true>;
+        else if constexpr (ADD) return mx_qlinear_stream_add_kernel<F, D, NW, W4>;
+        else if constexpr (ACT) return mx_qlinear_stream_act_kernel<RMS>;
         else if constexpr (RMS) return mx_qlinear_stream_rms_kernel<F, D, NW, W4>;
         else return mx_qlinear_stream_kernel<F, D, NW, W4>;
     }();
@@ -1109,6 +1125,8 @@ hipError_t launch_qlinear_stream(const void *X, const int16_t *idx, const uint8_
     qi.norm_w = (const uint16_t *)norm.weight;
     qi.eps = norm.eps;
     qi.int_round = norm.int_round;
+    qi.R = (const uint16_t *)norm.res;
+    qi.S_out = (uint16_t *)norm.s_out;
     for (int g = 0; g < 3; ++g) {
         a.W[g] = W[g];
         a.SFW[g] = SFW[g];
@@ -1185,6 +1203,8 @@ hipError_t launch_gate_up_act_stream_decode(const void *X, const int16_t *idx, c
     qi.norm_w = (const uint16_t *)norm.weight;
     qi.eps = norm.eps;
     qi.int_round = norm.int_round;
+    qi.R = (const uint16_t *)norm.res;
+    qi.S_out = (uint16_t *)norm.s_out;
     for (int g = 0; g < 3; ++g) qi.K[g] = a.K[g];
     return launch_quant<4, 2, 4, true, false, true>(a, qi, stream);
 }

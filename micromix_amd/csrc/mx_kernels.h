@@ -43,8 +43,8 @@ struct DynamicLdsOnce {
 struct OccupancyCache {
     struct Entry { const void *kernel; int dev, threads; size_t lds; int per_cu; };
     static int get(int slot, const void *kernel, int threads, size_t lds) {
-        static thread_local Entry last[8] = {};
-        Entry &e = last[slot & 7];
+        static thread_local Entry last[16] = {};
+        Entry &e = last[slot & 15];
         const int dev = current_device();
         if (e.kernel == kernel && e.dev == dev && e.threads == threads && e.lds == lds && e.per_cu > 0) return e.per_cu;
         int per_cu = 0;
@@ -194,9 +194,15 @@ hipError_t launch_direct_quantize(const void *A, const void *B, int rows, int KN
 hipError_t launch_rmsnorm_quantize(const void *src, const void *weight, float eps, int rows, int K, const int16_t *idx, int KN,
                                    int KS, int KO, bool integer_round, uint8_t *oN, uint8_t *oS, uint8_t *oO, uint8_t *sfN,
                                    uint8_t *sfS, uint8_t *sfO, hipStream_t stream);
+// ... of s = src + res (bf16, one rounding), which is also written to s_out (mm_add_rmsnorm_quantize)
+hipError_t launch_add_rmsnorm_quantize(const void *src, const void *res, void *s_out, const void *weight, float eps, int rows, int K,
+                                       const int16_t *idx, int KN, int KS, int KO, bool integer_round, uint8_t *oN, uint8_t *oS, uint8_t *oO,
+                                       uint8_t *sfN, uint8_t *sfS, uint8_t *sfO, hipStream_t stream);
 // RMSNorm in front of the quantization of the decode launches (mm_rmsnorm_qlinear_decode): weight == nullptr means no norm
-struct NormArgs { const void *weight; float eps; int int_round; };
-constexpr NormArgs NO_NORM = {nullptr, 0.0f, 1};
+// res / s_out (both or neither; with weight only): the residual add in front of the norm -- the rows are X + res, and one workgroup
+// of the launch writes them to s_out (mm_add_rmsnorm_qlinear_decode)
+struct NormArgs { const void *weight; float eps; int int_round; const void *res; void *s_out; };
+constexpr NormArgs NO_NORM = {nullptr, 0.0f, 1, nullptr, nullptr};
 int qlinear_decode_supported(int M, int N, const int K[3], bool rms = false, bool w4 = false);
 hipError_t launch_qlinear_decode(const void *X, const int16_t *idx, const uint8_t *const W[3], const uint8_t *const SFW[3],
                                  int M, int N, const int K[3], bool w4, int round_per_segment, const void *bias, void *D,

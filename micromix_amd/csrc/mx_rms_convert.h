@@ -67,6 +67,20 @@ __device__ __forceinline__ float rms_scale(uint32_t (&v)[16], uint32_t amax, int
         return __uint_as_float((uint32_t)(127 + e) << 23);
     }
 }
+// The residual add in front of the norm (mm_add_rmsnorm_quantize and the add_ decode launches): s = bf16_rne(f32(x) + f32(r)) per element,
+// an IEEE fp32 add of the widened values (exact up to its one rounding; subnormals kept) and one rounding to nearest even -- the rule of
+// torch's bf16 `x + r` wherever that is a number; every NaN (inf - inf, a NaN operand) is the one pattern 0x7FC0 (torch's own differs
+// between its conversions).
+__device__ __forceinline__ uint32_t add_bf16x2(uint32_t x, uint32_t r) {
+    float lo = bf16_bits_to_f32(x & 0xFFFFu) + bf16_bits_to_f32(r & 0xFFFFu);
+    float hi = __uint_as_float(x & 0xFFFF0000u) + __uint_as_float(r & 0xFFFF0000u);
+    lo = lo != lo ? __uint_as_float(0x7FC00000u) : lo;
+    hi = hi != hi ? __uint_as_float(0x7FC00000u) : hi;
+    return pack_bf16x2(lo, hi);
+}
+__device__ __forceinline__ uint4 add_bf16x8(const uint4 x, const uint4 r) {
+    return make_uint4(add_bf16x2(x.x, r.x), add_bf16x2(x.y, r.y), add_bf16x2(x.z, r.z), add_bf16x2(x.w, r.w));
+}
 // the sum of squares of one of the reference's group threads: elements 8 (i T + t) + j, i = 0 .. 3, j = 0 .. 7, one after the other
 // (rmsnorm.cu:143-160; `chunk(q)` returns 16-byte chunk q of the row as four dwords)
 template <class Chunk>

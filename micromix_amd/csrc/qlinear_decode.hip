@@ -97,6 +97,8 @@ struct Args {
     const uint16_t *norm_w; // RMSNorm in front of the quantization (null: none), see dq::QuantIn
     float eps;
     int int_round;
+    const uint16_t *res;    // the residual add in front of the norm (ADD kernels only), see dq::QuantIn::R / S_out
+    uint16_t *s_out;
 };
 
 // this wave's slabs of one segment; xl = LDS base of the segment's quantized rows (pitch xp bytes), sl = LDS base of the
@@ -246,31 +248,34 @@ struct SegPrefetch {
 __device__ __forceinline__ void wait_all_loads() { MM_QD_DEVICE_ONLY(asm volatile("s_waitcnt vmcnt(0)" ::: "memory");) }
 
 using dq::LdsMap;
-template <bool RMS, int LPG>
+template <bool RMS, int LPG, bool ADD>
 __device__ __forceinline__ LdsMap quantize_rows_to_lds(const Args &a, uint8_t *smem) {
     dq::QuantIn q;
     q.X = a.X; q.idx = a.idx; q.M = a.M; q.stage_rows = a.stage_rows;
     q.K[0] = a.K[0]; q.K[1] = a.K[1]; q.K[2] = a.K[2];
     q.mode = 0; q.early = 0;
     q.norm_w = a.norm_w; q.eps = a.eps; q.int_round = a.int_round;
-    return dq::quantize_rows_to_lds<NT, RMS, LPG>(q, smem);
+    q.R = a.res; q.S_out = a.s_out;
+    return dq::quantize_rows_to_lds<NT, RMS, LPG, ADD>(q, smem);
 }
 // ... with `request()` (vector-memory instructions the compiler does not track) called from the phase's hook, once the first batch of
 // rows is staged
-template <bool RMS, int LPG, class Request>
+template <bool RMS, int LPG, bool ADD, class Request>
 __device__ __forceinline__ LdsMap quantize_rows_to_lds(const Args &a, uint8_t *smem, Request request) {
     dq::QuantIn q;
     q.X = a.X; q.idx = a.idx; q.M = a.M; q.stage_rows = a.stage_rows;
     q.K[0] = a.K[0]; q.K[1] = a.K[1]; q.K[2] = a.K[2];
     q.mode = 0; q.early = 0;
     q.norm_w = a.norm_w; q.eps = a.eps; q.int_round = a.int_round;
-    return dq::quantize_rows_to_lds<NT, RMS, LPG>(q, smem, [&]() { request(); });
+    q.R = a.res; q.S_out = a.s_out;
+    return dq::quantize_rows_to_lds<NT, RMS, LPG, ADD>(q, smem, [&]() { request(); });
 }
 
 // LPG: lanes per reordered group in the quantization phase (dq::quantize_rows_to_lds): 2 when the launch's (row, group, half) slots fit
 // one pass of the workgroup (M <= 2 at K = 4096), else 1 -- kernels of their own: with both paths in one kernel the one-lane path ran
 // 0.3 - 2 us slower than alone (q | k | v with the norm at M = 8: 16.1 -> 18.1 us)
-template <bool W4, bool RMS = false, int LPG = 1>
+// ADD: the residual add in front of the norm (mm_add_rmsnorm_qlinear_decode), kernels of their own as RMS
+template <bool W4, bool RMS = false, int LPG = 1, bool ADD = false>
 __global__ void __launch_bounds__(NT) qlinear_decode_kernel(Args a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];   // [row stage | opN | opS | opO | scales]
     __shared__ float red[3][NW][4][64];      // per segment and wave: accumulator registers 0 .. 3 (token rows 0 .. 7)
@@ -284,8 +289,8 @@ __global__ void __launch_bounds__(NT) qlinear_decode_kernel(Args a) {
         pfS.request(a.W[1], a.SFW[1], a.K[1] >> 7, a.N, n0, a.sfw_row_tiles);
         pfO.request(a.W[2], a.SFW[2], a.K[2] >> 7, a.N, n0, a.sfw_row_tiles);
     };
-    if constexpr (PF && MM_DECODE_PREFETCH == 2) L = quantize_rows_to_lds<RMS, LPG>(a, smem, request);
-    else L = quantize_rows_to_lds<RMS, LPG>(a, smem);
+    if constexpr (PF && MM_DECODE_PREFETCH == 2) L = quantize_rows_to_lds<RMS, LPG, ADD>(a, smem, request);
+    else L = quantize_rows_to_lds<RMS, LPG, ADD>(a, smem);
     if constexpr (PF && MM_DECODE_PREFETCH == 1) request();
     const uint8_t *opN = L.opN, *opS = L.opS, *opO = L.opO, *scales = L.scales;
     const int pN = L.pN, pS = L.pS, pO = L.pO, Gt = L.Gt, gN = L.gN, gS = L.gS;
@@ -471,7 +476,8 @@ __device__ __forceinline__ void run_segment16(v4f &acc, const uint8_t *xl, int x
     }
 }
 
-template <bool W4, bool RMS = false, int LPG = 1>
+// ADD: the residual add in front of the norm (mm_add_rmsnorm_qlinear_decode), kernels of their own as RMS
+template <bool W4, bool RMS = false, int LPG = 1, bool ADD = false>
 __global__ void __launch_bounds__(NT) qlinear_decode16_kernel(Args a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     __shared__ float red[3][NW][4][64];        // the waves' partial sums of N, S, O side by side: ONE barrier (round 6; was two per segment)
@@ -485,8 +491,8 @@ __global__ void __launch_bounds__(NT) qlinear_decode16_kernel(Args a) {
         pfS.request(a.W[1], a.SFW[1], a.K[1] >> 7, a.N, n0, a.sfw_row_tiles);
         pfO.request(a.W[2], a.SFW[2], a.K[2] >> 7, a.N, n0, a.sfw_row_tiles);
     };
-    if constexpr (PF && MM_DECODE_PREFETCH == 2) L = quantize_rows_to_lds<RMS, LPG>(a, smem, request);
-    else L = quantize_rows_to_lds<RMS, LPG>(a, smem);
+    if constexpr (PF && MM_DECODE_PREFETCH == 2) L = quantize_rows_to_lds<RMS, LPG, ADD>(a, smem, request);
+    else L = quantize_rows_to_lds<RMS, LPG, ADD>(a, smem);
     if constexpr (PF && MM_DECODE_PREFETCH == 1) request();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nseg[3] = {a.K[0] >> 7, a.K[1] >> 7, a.K[2] >> 7};
@@ -611,6 +617,10 @@ hipError_t launch_qlinear_decode(const void *X, const int16_t *idx, const uint8_
     a.norm_w = (const uint16_t *)norm.weight;
     a.eps = norm.eps;
     a.int_round = norm.int_round;
+    a.res = (const uint16_t *)norm.res;
+    a.s_out = (uint16_t *)norm.s_out;
+    const bool add = norm.res != nullptr;
+    if (add && !rms) return hipErrorInvalidValue;
     a.X = (const uint16_t *)X;
     a.idx = idx;
     for (int i = 0; i < 3; ++i) {
@@ -634,14 +644,16 @@ hipError_t launch_qlinear_decode(const void *X, const int16_t *idx, const uint8_
     const bool pairs = 2 * (size_t)stage_rows * (Kt / 32) <= (size_t)NT;
     auto pick = [&](auto lpg_) {
         constexpr int L = decltype(lpg_)::value;
+        if (add) return f16 ? (w4 ? qlinear_decode16_kernel<true, true, L, true> : qlinear_decode16_kernel<false, true, L, true>)
+                            : (w4 ? qlinear_decode_kernel<true, true, L, true> : qlinear_decode_kernel<false, true, L, true>);
         return rms ? (f16 ? (w4 ? qlinear_decode16_kernel<true, true, L> : qlinear_decode16_kernel<false, true, L>)
                           : (w4 ? qlinear_decode_kernel<true, true, L> : qlinear_decode_kernel<false, true, L>))
                    : (f16 ? (w4 ? qlinear_decode16_kernel<true, false, L> : qlinear_decode16_kernel<false, false, L>)
                           : (w4 ? qlinear_decode_kernel<true, false, L> : qlinear_decode_kernel<false, false, L>));
     };
     auto kern = pairs ? pick(std::integral_constant<int, 2>{}) : pick(std::integral_constant<int, 1>{});
-    static DynamicLdsOnce done[16];
-    if (hipError_t e = done[(pairs ? 8 : 0) + (rms ? 4 : 0) + (f16 ? 2 : 0) + (w4 ? 0 : 1)].ensure(reinterpret_cast<const void *>(kern), (int)DECODE_LDS_MAX); e != hipSuccess)
+    static DynamicLdsOnce done[32];
+    if (hipError_t e = done[(add ? 16 : 0) + (pairs ? 8 : 0) + (rms ? 4 : 0) + (f16 ? 2 : 0) + (w4 ? 0 : 1)].ensure(reinterpret_cast<const void *>(kern), (int)DECODE_LDS_MAX); e != hipSuccess)
         return e;
     const int feat = f16 ? BN16 : BN;
     int blocks = (N + feat - 1) / feat;

@@ -31,6 +31,12 @@
 #include "mx_rms_convert.h"
 #include "mx_kernels.h"
 
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MM_RMS_SCHED_BARRIER() __builtin_amdgcn_sched_barrier(0)
+#else
+#define MM_RMS_SCHED_BARRIER() do { } while (0)
+#endif
+
 namespace mm {
 
 //   then convert_group<EL> into global memory (fp4: 16 bytes per lane, whole lines as they are) or into the LDS image of the row's
@@ -50,16 +56,53 @@ __device__ __forceinline__ uint32_t rms_group(const uint8_t *__restrict__ row, c
     return (uint32_t)(e + 127);
 }
 
+// How a row's 16-byte chunks reach the staging registers (in the spirit of StageLoad / StageSiluMul, reorder_quantize.hip).  load() issues
+// the global loads of chunk c = cu + g of row r (grow: that row of src; cu: the workgroup-uniform part of c, g: the thread), chunk() turns
+// the registers into the eight bf16 that are staged and summed, keep() runs once per staged chunk for a hook that also stores what it
+// staged.  RowLoad, the plain load, is what mm_rmsnorm_quantize stages with.
+// (The hook is the kernel's last argument and its type a template parameter: the instantiations with RowLoad are mm_rmsnorm_quantize's
+// kernels as they were, register for register; what the residual costs lives in the RowAddResidual instantiations alone.)
+struct RowLoad {
+    typedef uint4 Regs;
+    static constexpr int WAVES_PER_SIMD = 0;      // the products kernel's __launch_bounds__: no bound
+    __device__ __forceinline__ Regs load(const uint4 *__restrict__ grow, int, int, int c, int, int) const { return grow[c]; }
+    __device__ __forceinline__ uint4 chunk(Regs &t) const { return t; }
+    __device__ __forceinline__ void keep(const Regs &, int, int, int, int) const {}
+};
+// mm_add_rmsnorm_quantize: the staged row is s = bf16(x + res) (add_bf16x8, mx_rms_convert.h); the chunk of `res` travels beside the
+// chunk of x, the packed sums go to LDS and into the sum of squares, and leave once for s_out -- the new residual stream.  A row
+// belongs to one workgroup and a chunk to one thread, so every byte of s_out is written exactly once.
+// (Addresses as uniform base + the thread's 16 g bytes: with one 64-bit address per chunk and tensor in registers the two-group kernel,
+// 248 registers with the plain load, spilled 50 of them.)
+struct RowAddResidual {
+    struct Regs { uint4 x, r; };
+    // the products kernel at three waves per SIMD, as with the plain load (158 VGPRs there; the second chunk in flight per lane made it
+    // 170 with the integer rounding, two over the 168 that three waves leave each other)
+    static constexpr int WAVES_PER_SIMD = 3;
+    const uint16_t *__restrict__ res;   // [rows, K]
+    uint16_t *__restrict__ s_out;       // [rows, K]
+    __device__ __forceinline__ Regs load(const uint4 *__restrict__ grow, int r, int K, int, int cu, int g) const {
+        Regs t;
+        t.x = (grow + cu)[g];
+        t.r = (reinterpret_cast<const uint4 *>(res + (size_t)r * K) + cu)[g];
+        return t;
+    }
+    __device__ __forceinline__ uint4 chunk(Regs &t) const { return t.x = add_bf16x8(t.x, t.r); }
+    __device__ __forceinline__ void keep(const Regs &t, int r, int K, int cu, int g) const {
+        (reinterpret_cast<uint4 *>(s_out + (size_t)r * K) + cu)[g] = t.x;
+    }
+};
+
 // GPT = groups per thread.  8192 < K <= 16384: one (K / 32 <= 512 threads).  16384 < K <= 32768: TWO -- thread g plays the reference's group
 // threads t = g and g + 512 one after the other, with their indices and norm weights in 2 x 32 registers.  (Rounds 1-5 ran that range with
 // 1024 threads, i.e. 128 registers per lane, which this kernel does not fit in: it spilled 12-13 registers, reloaded inside the row
 // loop.  Round 6: no kernel of the library may use scratch -- 512 threads have 256 registers each.)
-template <bool INT_ROUND, int GPT>
+template <bool INT_ROUND, int GPT, class Stage = RowLoad>
 __global__ void __launch_bounds__(512)
 rmsnorm_quantize_kernel(const uint16_t *__restrict__ src, const uint16_t *__restrict__ weight, float eps, int rows, int K,
                         const int16_t *__restrict__ idx, int KN, int KS, int KO, uint8_t *__restrict__ oN,
                         uint8_t *__restrict__ oS, uint8_t *__restrict__ oO, uint8_t *__restrict__ sfN,
-                        uint8_t *__restrict__ sfS, uint8_t *__restrict__ sfO) {
+                        uint8_t *__restrict__ sfS, uint8_t *__restrict__ sfO, const Stage hook) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];  // [K bf16 row][P floats of partial sums]
     const int T = K >> 5;  // the reference's group threads = stager threads: group thread t stages chunks t, T + t, 2T + t, 3T + t
     const int g = threadIdx.x, NTH = (int)blockDim.x;
@@ -120,7 +163,11 @@ rmsnorm_quantize_kernel(const uint16_t *__restrict__ src, const uint16_t *__rest
     // the gather), and stored to LDS -- squares summed on the way -- after the barrier that ends the current row.
     // GPT = 2 fetches each row when it needs it (2 x 4 chunks: the registers go to the second group's indices and weights)
     constexpr bool PREFETCH = GPT == 1;
-    uint4 stage[GPT][4];
+    // (... all 2 x 4 chunks at once with the plain load.  A hook with two loads per chunk takes them in pairs of chunks, each pair staged and
+    // summed before the next is requested: beside 2 x 32 registers of indices and weights the kernel has no room for more in flight --
+    // 248 registers with the plain load -- and the order of the sum is the same, chunk after chunk)
+    constexpr bool IN_PAIRS = !PREFETCH && sizeof(typename Stage::Regs) > sizeof(uint4);
+    typename Stage::Regs stage[IN_PAIRS ? 1 : GPT][IN_PAIRS ? 2 : 4];
     auto fetch = [&](int r) {
         if (r < rows) {
             const uint4 *grow = reinterpret_cast<const uint4 *>(src + (size_t)r * K);
@@ -128,34 +175,50 @@ rmsnorm_quantize_kernel(const uint16_t *__restrict__ src, const uint16_t *__rest
             for (int u = 0; u < GPT; ++u)
                 if (active[u]) {
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) stage[u][i] = grow[i * T + g + u * NTH];
+                    for (int i = 0; i < 4; ++i) stage[u][i] = hook.load(grow, r, K, i * T + g + u * NTH, i * T + u * NTH, g);
                 }
         }
     };
+    // chunk i of group thread t_u: staged, its squares added to `sum`
+    auto stage_chunk = [&](typename Stage::Regs &t, int u, int i, int r, float &sum) {
+        const uint4 q = hook.chunk(t);
+        reinterpret_cast<uint4 *>(smem)[swizzle_chunk(i * T + g + u * NTH)] = q;
+        const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float a = bf16_bits_to_f32(w[k] & 0xFFFFu), b = bf16_bits_to_f32(w[k] >> 16);
+            sum = __builtin_fmaf(a, a, sum);  // a*a is exact: the fused and the unfused forms round identically
+            sum = __builtin_fmaf(b, b, sum);
+        }
+        hook.keep(t, r, K, i * T + u * NTH, g);
+    };
     // (the partial sum of group thread t_u, in the reference's order: its four chunks one after the other)
-    auto stage_and_sum = [&](int u) -> float {
+    auto stage_and_sum = [&](int u, int r) -> float {
         float sum = 0.0f;
         if (active[u]) {
+            if constexpr (IN_PAIRS) {
+                const uint4 *grow = reinterpret_cast<const uint4 *>(src + (size_t)r * K);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                reinterpret_cast<uint4 *>(smem)[swizzle_chunk(i * T + g + u * NTH)] = stage[u][i];
-                const uint32_t w[4] = {stage[u][i].x, stage[u][i].y, stage[u][i].z, stage[u][i].w};
+                for (int i0 = 0; i0 < 4; i0 += 2) {
+                    MM_RMS_SCHED_BARRIER();      // (or the scheduler requests the next pair in front of this one's sums)
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float a = bf16_bits_to_f32(w[k] & 0xFFFFu), b = bf16_bits_to_f32(w[k] >> 16);
-                    sum = __builtin_fmaf(a, a, sum);  // a*a is exact: the fused and the unfused forms round identically
-                    sum = __builtin_fmaf(b, b, sum);
+                    for (int i = 0; i < 2; ++i) stage[0][i] = hook.load(grow, r, K, (i0 + i) * T + g + u * NTH, (i0 + i) * T + u * NTH, g);
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) stage_chunk(stage[0][i], u, i0 + i, r, sum);
                 }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) stage_chunk(stage[u][i], u, i, r, sum);
             }
         }
         return sum;
     };
     if constexpr (PREFETCH) fetch(blockIdx.x);
     for (int r = blockIdx.x; r < rows; r += gridDim.x) {
-        if constexpr (!PREFETCH) fetch(r);
+        if constexpr (!PREFETCH && !IN_PAIRS) fetch(r);
         float sum[GPT];
 #pragma unroll
-        for (int u = 0; u < GPT; ++u) sum[u] = stage_and_sum(u);
+        for (int u = 0; u < GPT; ++u) sum[u] = stage_and_sum(u, r);
         if constexpr (PREFETCH) fetch(r + gridDim.x);
         // part[t] for t < T, zeros up to P (P <= 2 * GPT * NTH: group threads past T contribute the zero padding)
 #pragma unroll
@@ -195,13 +258,13 @@ rmsnorm_quantize_kernel(const uint16_t *__restrict__ src, const uint16_t *__rest
 // K <= 8192: the row is staged as fp32 products x * w (see the header).  LDS: [plane A: K floats' first halves][plane B][P partial sums];
 // element c = 8q + e lives at byte (e < 4 ? 0 : 2K) + 16 q' + 4(e & 3), q' = swizzle_chunk(q) (mx_group_convert.h), so chunk q's two
 // halves are two conflict-free 16-byte writes.
-template <bool INT_ROUND>
-// (167 VGPRs: six workgroups per CU.  Bounding it to 128 for eight -- __launch_bounds__(256, 4) -- spills 38 registers: 14.4 -> 25.9 us.)
-__global__ void __launch_bounds__(256)
+template <bool INT_ROUND, class Stage = RowLoad>
+// (167 VGPRs when this was measured, 158 with the current toolchain: six workgroups per CU either way.  Bounding it to 128 for eight -- __launch_bounds__(256, 4) -- spills 38 registers: 14.4 -> 25.9 us.)
+__global__ void __launch_bounds__(256, Stage::WAVES_PER_SIMD)
 rmsnorm_quantize_products_kernel(const uint16_t *__restrict__ src, const uint16_t *__restrict__ weight, float eps, int rows, int K,
                                  const int16_t *__restrict__ idx, int KN, int KS, int KO, uint8_t *__restrict__ oN,
                                  uint8_t *__restrict__ oS, uint8_t *__restrict__ oO, uint8_t *__restrict__ sfN,
-                                 uint8_t *__restrict__ sfS, uint8_t *__restrict__ sfO) {
+                                 uint8_t *__restrict__ sfS, uint8_t *__restrict__ sfO, const Stage hook) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int T = K >> 5;
     const int g = threadIdx.x;
@@ -239,20 +302,21 @@ rmsnorm_quantize_products_kernel(const uint16_t *__restrict__ src, const uint16_
     else if (g < gN + gS) { seg = 1; j = g - gN; kseg = KS; }
     else { seg = 2; j = g - gN - gS; kseg = KO; }
 
-    uint4 stage[4];
+    typename Stage::Regs stage[4];
     auto fetch = [&](int r) {
         if (active && r < rows) {
             const uint4 *grow = reinterpret_cast<const uint4 *>(src + (size_t)r * K);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) stage[i] = grow[i * T + g];
+            for (int i = 0; i < 4; ++i) stage[i] = hook.load(grow, r, K, i * T + g, i * T, g);
         }
     };
-    auto stage_and_sum = [&]() -> float {
+    auto stage_and_sum = [&](int r) -> float {
         float sum = 0.0f;
         if (active) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const uint32_t x[4] = {stage[i].x, stage[i].y, stage[i].z, stage[i].w};
+                const uint4 sq = hook.chunk(stage[i]);
+                const uint32_t x[4] = {sq.x, sq.y, sq.z, sq.w};
                 const uint32_t w[4] = {wch[i].x, wch[i].y, wch[i].z, wch[i].w};
                 float pr[8];
 #pragma unroll
@@ -267,12 +331,14 @@ rmsnorm_quantize_products_kernel(const uint16_t *__restrict__ src, const uint16_
                 reinterpret_cast<float4 *>(smem)[q] = make_float4(pr[0], pr[1], pr[2], pr[3]);
                 reinterpret_cast<float4 *>(smem + planeB)[q] = make_float4(pr[4], pr[5], pr[6], pr[7]);
             }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) hook.keep(stage[i], r, K, i * T, g);
         }
         return sum;
     };
     fetch(blockIdx.x);
     for (int r = blockIdx.x; r < rows; r += gridDim.x) {
-        const float sum = stage_and_sum();
+        const float sum = stage_and_sum(r);
         fetch(r + gridDim.x);
         part[g] = sum;              // threads T.. contribute the zero padding (P < 2 * blockDim.x)
         if (g + (int)blockDim.x < P) part[g + blockDim.x] = 0.0f;
@@ -561,7 +627,39 @@ hipError_t launch_rmsnorm_quantize(const void *src, const void *weight, float ep
     int blocks = cus * per_cu;
     blocks = rows < blocks ? rows : blocks;
     MM_LAUNCH(kern, dim3(blocks), dim3(threads), lds, stream, (const uint16_t *)src, (const uint16_t *)weight, eps, rows,
-                       K, idx, KN, KS, KO, oN, oS, oO, sfN, sfS, sfO);
+                       K, idx, KN, KS, KO, oN, oS, oO, sfN, sfS, sfO, RowLoad());
+    return hipGetLastError();
+}
+
+// mm_add_rmsnorm_quantize: the two kernels that stage the row through registers, at every row count -- the LDS-DMA ring moves global
+// memory straight to LDS and cannot add on the way.  Grid as above: CUs x occupancy workgroups striding over the rows.
+hipError_t launch_add_rmsnorm_quantize(const void *src, const void *res, void *s_out, const void *weight, float eps, int rows, int K,
+                                       const int16_t *idx, int KN, int KS, int KO, bool integer_round, uint8_t *oN, uint8_t *oS, uint8_t *oO,
+                                       uint8_t *sfN, uint8_t *sfS, uint8_t *sfO, hipStream_t stream) {
+    if (rows == 0) return hipSuccess;
+    const int T = K / 32;
+    const int groups_per_thread = T > 512 ? 2 : 1;
+    const int threads = ((T + groups_per_thread - 1) / groups_per_thread + 63) / 64 * 64;
+    int P = 64;
+    while (P < T) P <<= 1;
+    const bool products = threads <= 256;
+    const int pslots = P > groups_per_thread * threads ? P : groups_per_thread * threads;
+    const size_t lds = (size_t)K * (products ? 4 : 2) + (size_t)pslots * 4 + (size_t)KS / 4 * 3 + KO;
+    using Add = RowAddResidual;
+    auto kern = products ? (integer_round ? rmsnorm_quantize_products_kernel<true, Add> : rmsnorm_quantize_products_kernel<false, Add>)
+              : groups_per_thread == 1 ? (integer_round ? rmsnorm_quantize_kernel<true, 1, Add> : rmsnorm_quantize_kernel<false, 1, Add>)
+                               : (integer_round ? rmsnorm_quantize_kernel<true, 2, Add> : rmsnorm_quantize_kernel<false, 2, Add>);
+    static DynamicLdsOnce attr[6];
+    if (lds > 48 * 1024) {
+        const int which = (products ? 0 : groups_per_thread == 1 ? 1 : 2) * 2 + (integer_round ? 1 : 0);
+        if (hipError_t e = attr[which].ensure(reinterpret_cast<const void *>(kern), 104 * 1024); e != hipSuccess) return e;
+    }
+    // (slots of its own: a layer stack alternates this launch with mm_rmsnorm_quantize's)
+    const int per_cu = OccupancyCache::get(integer_round ? 8 : 9, reinterpret_cast<const void *>(kern), threads, lds);
+    int blocks = device_cus() * per_cu;
+    blocks = rows < blocks ? rows : blocks;
+    MM_LAUNCH(kern, dim3(blocks), dim3(threads), lds, stream, (const uint16_t *)src, (const uint16_t *)weight, eps, rows, K, idx, KN, KS, KO,
+              oN, oS, oO, sfN, sfS, sfO, Add{(const uint16_t *)res, (uint16_t *)s_out});
     return hipGetLastError();
 }
 

@@ -544,6 +544,26 @@ def gate_up_activate_decode_supported(M, I, KN, KS, KO):
     return int(_lib.load().mm_gate_up_activate_decode_supported(int(M), int(I), int(KN), int(KS), int(KO)))
 
 
+def _residual_operands(X, residual, out_sum, index):
+    """the residual and the tensor that receives X + residual, checked (the library itself refuses an out_sum that overlaps either input)"""
+    if not _ok(residual, torch.bfloat16, index) or tuple(residual.shape) != tuple(X.shape):
+        _check_tensor(residual, "residual", torch.bfloat16, X.device)
+        raise RuntimeError("residual must have X's shape")
+    if out_sum is None:
+        out_sum = torch.empty_like(X)
+    elif not _ok(out_sum, torch.bfloat16, index) or tuple(out_sum.shape) != tuple(X.shape):
+        _check_tensor(out_sum, "out_sum", torch.bfloat16, X.device)
+        raise RuntimeError("out_sum must have X's shape")
+    return out_sum
+
+
+def add_rmsnorm_gate_up_activate_decode(X, residual, norm_weight, eps, reorder_index, B, DN, DS, DO, *, rounding="reference", integer_round=True,
+                                        out_sum=None):
+    """`rmsnorm_gate_up_activate_decode` on s = X + residual (torch's bf16 add), the add inside the launch: returns (s, down_proj's six
+    operands).  Bit-identical to `add_rmsnorm_quantize_x` -> `gate_up_activate`; supported where the plain form is."""
+    return _rmsnorm_gate_up_activate_decode(X, norm_weight, eps, reorder_index, B, DN, DS, DO, rounding, integer_round, residual, out_sum)
+
+
 def rmsnorm_gate_up_activate_decode(X, norm_weight, eps, reorder_index, B, DN, DS, DO, *, rounding="reference", integer_round=True):
     """`gate_up_activate(rmsnorm_quantize_x(X, norm_weight, eps, reorder_index, KN, KS, KO), B, DN, DS, DO)` for decode-sized batches: the
     post-attention RMSNorm, the quantization of x, the gate | up GEMM on the interleaved weight B, silu(gate) * up and the quantization for
@@ -551,6 +571,10 @@ def rmsnorm_gate_up_activate_decode(X, norm_weight, eps, reorder_index, B, DN, D
     fastest form).  Returns
     down_proj's activation operands (oN, oS, oO, sfN, sfS, sfO): `matmul` them with the packed down_proj weight.  Same bytes as the
     three-op form.  Not an export of the reference module."""
+    return _rmsnorm_gate_up_activate_decode(X, norm_weight, eps, reorder_index, B, DN, DS, DO, rounding, integer_round, None, None)
+
+
+def _rmsnorm_gate_up_activate_decode(X, norm_weight, eps, reorder_index, B, DN, DS, DO, rounding, integer_round, residual, out_sum):
     lib = _lib.load()
     dev = X.device
     index = dev.index
@@ -558,6 +582,8 @@ def rmsnorm_gate_up_activate_decode(X, norm_weight, eps, reorder_index, B, DN, D
         _check_tensor(X, "X", torch.bfloat16)
         _check_tensor(norm_weight, "norm_weight", torch.bfloat16, dev)
         _check_tensor(reorder_index, "reorder_index", torch.int16, dev)
+    if residual is not None:
+        out_sum = _residual_operands(X, residual, out_sum, index)
     for t in B:
         if not _ok(t, torch.uint8, index):
             _check_tensor(t, "operand", torch.uint8, dev)
@@ -584,13 +610,16 @@ def rmsnorm_gate_up_activate_decode(X, norm_weight, eps, reorder_index, B, DN, D
     sfS = torch.empty((_sf_bytes_x(M, DS),), dtype=u8, device=dev)
     sfO = torch.empty((_sf_bytes_x(M, DO),), dtype=u8, device=dev)
     ws = torch.empty((M * N2 * 2,), dtype=u8, device=dev)      # (scratch of the two-launch form; stream-ordered, from the caching allocator)
+    tail = (_ptr(reorder_index), _ptr(B[0]), _ptr(B[1]), _ptr(B[2]), _ptr(B[3]), _ptr(B[4]), _ptr(B[5]), M, I, KN, KS, KO, DN, DS, DO, flags, _ptr(oN),
+            _ptr(oS), _ptr(oO), _ptr(sfN), _ptr(sfS), _ptr(sfO), _ptr(ws), ws.numel(), _stream_ptr(dev))
     with _on_device(index):
-        st = lib.mm_rmsnorm_gate_up_activate_decode(_ptr(X), _ptr(norm_weight), float(eps), _ptr(reorder_index), _ptr(B[0]), _ptr(B[1]), _ptr(B[2]),
-                                                    _ptr(B[3]), _ptr(B[4]), _ptr(B[5]), M, I, KN, KS, KO, DN, DS, DO, flags, _ptr(oN), _ptr(oS),
-                                                    _ptr(oO), _ptr(sfN), _ptr(sfS), _ptr(sfO), _ptr(ws), ws.numel(), _stream_ptr(dev))
+        if residual is None:
+            st = lib.mm_rmsnorm_gate_up_activate_decode(_ptr(X), _ptr(norm_weight), float(eps), *tail)
+        else:
+            st = lib.mm_add_rmsnorm_gate_up_activate_decode(_ptr(X), _ptr(residual), _ptr(out_sum), _ptr(norm_weight), float(eps), *tail)
     if st:
-        _lib.check(st, "rmsnorm_gate_up_activate_decode")
-    return oN, oS, oO, sfN, sfS, sfO
+        _lib.check(st, "rmsnorm_gate_up_activate_decode" if residual is None else "add_rmsnorm_gate_up_activate_decode")
+    return (oN, oS, oO, sfN, sfS, sfO) if residual is None else (out_sum, oN, oS, oO, sfN, sfS, sfO)
 
 
 def down_activate_decode_supported(M, N, DN, DS, DO, weight_mode="w4"):
@@ -688,14 +717,30 @@ def rmsnorm_qlinear_decode_supported(M, N, KN, KS, KO, weight_mode="w4"):
     return int(_lib.load().mm_rmsnorm_qlinear_decode_supported_w(int(M), int(N), int(KN), int(KS), int(KO), _wmode_of(weight_mode)))
 
 
+def add_rmsnorm_qlinear_decode(X, residual, norm_weight, eps, reorder_index, BN, BS, BO, SFBN, SFBS, SFBO, KN, KS, KO, *, bias=None,
+                               rounding="reference", integer_round=True, out=None, out_sum=None):
+    """`rmsnorm_qlinear_decode` on s = X + residual (torch's bf16 add), the add inside the launch: returns (s, D).  Bit-identical to
+    `add_rmsnorm_quantize_x` followed by `matmul`; supported where the plain form is (`rmsnorm_qlinear_decode_supported`)."""
+    return _rmsnorm_qlinear_decode(X, norm_weight, eps, reorder_index, BN, BS, BO, SFBN, SFBS, SFBO, KN, KS, KO, bias, rounding, integer_round, out,
+                                   residual, out_sum)
+
+
 def rmsnorm_qlinear_decode(X, norm_weight, eps, reorder_index, BN, BS, BO, SFBN, SFBS, SFBO, KN, KS, KO, *, bias=None, rounding="reference",
                            integer_round=True, out=None):
     """rmsnorm_quantize_x + matmul (+ bias) as ONE launch for M <= 8 rows: what a decoder layer of the reference runs in front of
     q/k/v and gate/up (qLlamaLayer.py: input_layernorm / post_attention_layernorm fused into the quantizer, rmsnorm.cu:95-352, then
     qLinearLayer.py:58-74).  Bit-identical to `rmsnorm_quantize_x` followed by `matmul`.  X [M, K] bf16, norm_weight [K] bf16."""
+    return _rmsnorm_qlinear_decode(X, norm_weight, eps, reorder_index, BN, BS, BO, SFBN, SFBS, SFBO, KN, KS, KO, bias, rounding, integer_round, out,
+                                   None, None)
+
+
+def _rmsnorm_qlinear_decode(X, norm_weight, eps, reorder_index, BN, BS, BO, SFBN, SFBS, SFBO, KN, KS, KO, bias, rounding, integer_round, out,
+                            residual, out_sum):
     lib = _lib.load()
     dev = X.device
     index = dev.index
+    if residual is not None:
+        out_sum = _residual_operands(X, residual, out_sum, index)
     if not (X.is_cuda and _ok(X, torch.bfloat16, index) and _ok(reorder_index, torch.int16, index) and _ok(norm_weight, torch.bfloat16, index)):
         _check_tensor(X, "X", torch.bfloat16)
         _check_tensor(norm_weight, "norm_weight", torch.bfloat16, dev)
@@ -723,13 +768,16 @@ def rmsnorm_qlinear_decode(X, norm_weight, eps, reorder_index, BN, BS, BO, SFBN,
         raise RuntimeError("bias must have N elements")
     if out is None:
         out = torch.empty((M, N), dtype=torch.bfloat16, device=dev)
+    tail = (_ptr(reorder_index), _ptr(BN), _ptr(BS), _ptr(BO), _ptr(SFBN), _ptr(SFBS), _ptr(SFBO), M, N, KN, KS, KO, wmode, flags,
+            _ptr(bias) if bias is not None else None, _ptr(out), _stream_ptr(dev))
     with _on_device(index):
-        st = lib.mm_rmsnorm_qlinear_decode(_ptr(X), _ptr(norm_weight), float(eps), _ptr(reorder_index), _ptr(BN), _ptr(BS), _ptr(BO), _ptr(SFBN),
-                                           _ptr(SFBS), _ptr(SFBO), M, N, KN, KS, KO, wmode, flags, _ptr(bias) if bias is not None else None,
-                                           _ptr(out), _stream_ptr(dev))
+        if residual is None:
+            st = lib.mm_rmsnorm_qlinear_decode(_ptr(X), _ptr(norm_weight), float(eps), *tail)
+        else:
+            st = lib.mm_add_rmsnorm_qlinear_decode(_ptr(X), _ptr(residual), _ptr(out_sum), _ptr(norm_weight), float(eps), *tail)
     if st:
-        _lib.check(st, "rmsnorm_qlinear_decode")
-    return out
+        _lib.check(st, "rmsnorm_qlinear_decode" if residual is None else "add_rmsnorm_qlinear_decode")
+    return out if residual is None else (out_sum, out)
 
 
 def _direct(src_a, src_b, KN, KS, KO, mode, what):
@@ -824,6 +872,50 @@ def rmsnorm_quantize_x(X, W, eps, reorder_index, KN, KS, KO, *, integer_round=Tr
     if st:
         _lib.check(st, "rmsnorm_bf16_mixed")
     return oN, oS, oO, sfN, sfS, sfO
+
+
+def add_rmsnorm_quantize_x(x, residual, weight, eps, reorder_index, KN, KS, KO, out_sum=None, *, integer_round=True):
+    """The residual add of a decoder layer fused into `rmsnorm_quantize_x`: s = x + residual (torch's bf16 add, bit for bit), then
+    RMSNorm(s; weight, eps) -> reorder -> mixed quantize, one kernel that reads x and residual once and writes s once.
+
+    x, residual [M, K] bf16 -> (s, XN, XS, XO, SFXN, SFXS, SFXO): s [M, K] bf16 is the new residual stream, the rest is byte for byte
+    `rmsnorm_quantize_x(s, weight, eps, reorder_index, KN, KS, KO)`.  `out_sum`: a [M, K] bf16 tensor to receive s; it must not
+    overlap x or residual (the library refuses an overlap).  Not an export of the reference module: its layers add in torch
+    (model/qLlamaLayer.py:127-148)."""
+    lib = _lib.load()
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and isinstance(residual, torch.Tensor) and isinstance(weight, torch.Tensor)
+            and isinstance(reorder_index, torch.Tensor) and _ok(x, torch.bfloat16, x.get_device()) and _ok(residual, torch.bfloat16, x.get_device())
+            and _ok(weight, torch.bfloat16, x.get_device()) and _ok(reorder_index, torch.int16, x.get_device())):
+        _check_tensor(x, "x", torch.bfloat16)
+        _check_tensor(residual, "residual", torch.bfloat16, x.device)
+        _check_tensor(weight, "weight", torch.bfloat16, x.device)
+        _check_tensor(reorder_index, "reorder_index", torch.int16, x.device)
+    if x.dim() != 2 or tuple(residual.shape) != tuple(x.shape):
+        raise RuntimeError("x and residual must be 2-D [rows, K] of equal shape")
+    KN, KS, KO = int(KN), int(KS), int(KO)
+    rows, K = x.shape
+    if (KN < 0 or KS < 0 or KO < 0 or KN % 128 or KS % 128 or KO % 128 or KN + KS + KO != K or reorder_index.numel() != K
+            or weight.numel() != K):
+        _lib.check(_lib.MM_ERR_BAD_SPLIT, "rmsnorm_bf16_mixed")
+    dev, u8 = x.device, torch.uint8
+    if out_sum is None:
+        out_sum = torch.empty((rows, K), dtype=torch.bfloat16, device=dev)
+    elif not _ok(out_sum, torch.bfloat16, x.get_device()) or tuple(out_sum.shape) != (rows, K):
+        _check_tensor(out_sum, "out_sum", torch.bfloat16, dev)
+        raise RuntimeError("out_sum must be [rows, K]")
+    oN = torch.empty((rows, KN // 2), dtype=u8, device=dev)
+    oS = torch.empty((rows, KS // 4 * 3), dtype=u8, device=dev)
+    oO = torch.empty((rows, KO), dtype=u8, device=dev)
+    sfN = torch.empty((_sf_bytes_x(rows, KN),), dtype=u8, device=dev)
+    sfS = torch.empty((_sf_bytes_x(rows, KS),), dtype=u8, device=dev)
+    sfO = torch.empty((_sf_bytes_x(rows, KO),), dtype=u8, device=dev)
+    with _on_device(dev.index):
+        st = lib.mm_add_rmsnorm_quantize(_ptr(x), _ptr(residual), _ptr(out_sum), _ptr(weight), float(eps), rows, K, _ptr(reorder_index),
+                                         KN, KS, KO, _lib.MM_RMS_REFERENCE if integer_round else _lib.MM_RMS_NO_INTEGER_ROUND,
+                                         _ptr(oN), _ptr(oS), _ptr(oO), _ptr(sfN), _ptr(sfS), _ptr(sfO), _stream_ptr(dev))
+    if st:
+        _lib.check(st, "add_rmsnorm_quantize_x")
+    return out_sum, oN, oS, oO, sfN, sfS, sfO
 
 
 for _n in ("batch_decode_i4", "batch_decode_f16", "init_kv_i4", "init_kv_f16", "append_kv_i4", "append_kv_f16"):

@@ -76,8 +76,9 @@ class _DecodePlan:
         return out
 
 
-    def run_two_op(self, x2d, bias, norm=None):
-        """quantize (norm = (weight, eps): rmsnorm_quantize_x instead of reorder_quantize_x) + matmul, the split-K scratch from the plan"""
+    def run_two_op(self, x2d, bias, norm=None, residual=None):
+        """quantize (norm = (weight, eps): rmsnorm_quantize_x instead of reorder_quantize_x) + matmul, the split-K scratch from the plan.
+        `residual` (with norm): the quantizer is add_rmsnorm_quantize_x on x2d + residual, and the sum comes back next to the output"""
         m = x2d.size(0)
         kn, ks, ko = self.split
         sizes = (m * (kn // 2), m * (ks // 4 * 3), m * ko, mixedgemm._sf_bytes_x(m, kn), mixedgemm._sf_bytes_x(m, ks),
@@ -93,7 +94,7 @@ class _DecodePlan:
             ws_bytes = self.ws_bytes[m] = self.lib.mm_matmul_workspace_bytes(m, self.n, kn, ks, ko, self.wmode, wflags) if m > 32 else 0
         if torch.cuda.current_device() != self.index:
             with torch.cuda.device(self.index):
-                return self.run_two_op(x2d, bias, norm)
+                return self.run_two_op(x2d, bias, norm, residual)
         # one scratch tensor for the quantizer outputs; it is released at return, which is safe because the caching allocator only
         # hands the block to later work on the same stream.  The split-K workspace is the stream's persistent one.
         scratch = torch.empty((total,), dtype=torch.uint8, device=self.device)
@@ -105,6 +106,10 @@ class _DecodePlan:
         idx, bn, bs, bo, sfbn, sfbs, sfbo = self.args
         if norm is None:
             st = self.lib.mm_reorder_quantize(x2d.data_ptr(), m, self.k, idx, kn, ks, ko, 0, *q, stream)
+        elif residual is not None:
+            s = torch.empty((m, self.k), dtype=torch.bfloat16, device=self.device)
+            st = self.lib.mm_add_rmsnorm_quantize(x2d.data_ptr(), residual.data_ptr(), s.data_ptr(), norm[0].data_ptr(), float(norm[1]), m, self.k,
+                                                  idx, kn, ks, ko, 0, *q, stream)
         else:
             st = self.lib.mm_rmsnorm_quantize(x2d.data_ptr(), norm[0].data_ptr(), float(norm[1]), m, self.k, idx, kn, ks, ko, 0, *q, stream)
         if st == 0:
@@ -113,7 +118,7 @@ class _DecodePlan:
                                        ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, stream)
         if st:
             _lib.check(st, "QLinearLayer.forward")
-        return out
+        return out if residual is None else (out, s)
 
 
 def _forward(layer, x):
@@ -151,12 +156,15 @@ def _plan_of(layer):
     return plan
 
 
-def _forward_norm(layer, x, norm_weight, eps):
+def _forward_norm(layer, x, norm_weight, eps, residual=None):
     """RMSNorm(x; norm_weight, eps) -> layer: the reference's caller pattern `layer(rmsnorm_quantize_x(x, w, eps, idx, p4, p6, p8))`
     (model/qLlamaLayer.py: input_layernorm -> q/k/v, post_attention_layernorm -> gate/up; bindings.cpp:257-303).  At decode sizes where
     it is faster the norm, the quantization and the GEMM are ONE launch (`mixedgemm.rmsnorm_qlinear_decode`); the bytes are the same.
     x: [bsz, q_len, K], or [tokens, K] (the Mixtral caller's 2-D form: bsz comes back as None).  The same checks, the same empty-batch
-    answer and the same per-layer plan (split-K workspace included) as `_forward`."""
+    answer and the same per-layer plan (split-K workspace included) as `_forward`.
+    `residual` (same shape as x): the layer runs on RMSNorm(s), s = x + residual, and s comes back as a fourth value, [m, K].  Where the
+    two-launch form runs, the add is inside the quantizer (`mixedgemm.add_rmsnorm_quantize_x`); where the one-launch decode form runs,
+    inside that launch (`mixedgemm.add_rmsnorm_qlinear_decode`): no launch and no pass of its own either way, and the same bits."""
     if x.dim() == 3:
         bsz, q_len, k = x.shape
     elif x.dim() == 2:
@@ -169,8 +177,11 @@ def _forward_norm(layer, x, norm_weight, eps):
         raise TypeError(f"input must be a bfloat16 tensor [bsz, q_len, {plan.k}] on {plan.device}")
     if norm_weight.dtype is not torch.bfloat16 or norm_weight.device != plan.device or norm_weight.numel() != plan.k:
         raise TypeError(f"norm_weight must be a bfloat16 tensor [{plan.k}] on {plan.device}")
+    if residual is not None and (residual.dtype is not torch.bfloat16 or residual.device != plan.device or tuple(residual.shape) != tuple(x.shape)):
+        raise TypeError("residual must be a bfloat16 tensor of x's shape on its device")
     if m == 0:
-        return torch.empty((0, plan.n), dtype=torch.bfloat16, device=plan.device), bsz, q_len
+        y = torch.empty((0, plan.n), dtype=torch.bfloat16, device=plan.device)
+        return (y, bsz, q_len) if residual is None else (y, bsz, q_len, torch.empty((0, k), dtype=torch.bfloat16, device=plan.device))
     x2d = x.reshape(m, k).contiguous()
     norm_weight = norm_weight.contiguous()
     bias = layer.bias
@@ -178,9 +189,17 @@ def _forward_norm(layer, x, norm_weight, eps):
         bias = bias.to(x.device)
     if _DECODE_FUSED and m <= 8 and plan.norm_wins(m):
         split = plan.split
-        return mixedgemm.rmsnorm_qlinear_decode(x2d, norm_weight, eps, layer.reorder_index, layer.BN, layer.BS, layer.BO, layer.SFBN, layer.SFBS,
-                                                layer.SFBO, *split, bias=bias, rounding=getattr(layer, "rounding", "reference")), bsz, q_len
-    return plan.run_two_op(x2d, bias, norm=(norm_weight, eps)), bsz, q_len
+        if residual is None:
+            return mixedgemm.rmsnorm_qlinear_decode(x2d, norm_weight, eps, layer.reorder_index, layer.BN, layer.BS, layer.BO, layer.SFBN, layer.SFBS,
+                                                    layer.SFBO, *split, bias=bias, rounding=getattr(layer, "rounding", "reference")), bsz, q_len
+        s, y = mixedgemm.add_rmsnorm_qlinear_decode(x2d, residual.reshape(m, k).contiguous(), norm_weight, eps, layer.reorder_index, layer.BN, layer.BS,
+                                                    layer.BO, layer.SFBN, layer.SFBS, layer.SFBO, *split, bias=bias,
+                                                    rounding=getattr(layer, "rounding", "reference"))
+        return y, bsz, q_len, s
+    if residual is None:
+        return plan.run_two_op(x2d, bias, norm=(norm_weight, eps)), bsz, q_len
+    y, s = plan.run_two_op(x2d, bias, norm=(norm_weight, eps), residual=residual.reshape(m, k).contiguous())
+    return y, bsz, q_len, s
 
 
 def find_qlinear_layers(module, name=""):
@@ -238,10 +257,12 @@ class QLinearLayer(nn.Module):
         return y.reshape(bsz, q_len, y.size(-1)) if bsz is not None else y.reshape(q_len, y.size(-1))
 
     @torch.no_grad()
-    def forward_norm(self, x, norm_weight, eps):
-        """layer(RMSNorm(x)): x [bsz, q_len, K] bf16 -> [bsz, q_len, N]; see _forward_norm"""
-        y, bsz, q_len = _forward_norm(self, x, norm_weight, eps)
-        return y.reshape(bsz, q_len, y.size(-1)) if bsz is not None else y.reshape(q_len, y.size(-1))
+    def forward_norm(self, x, norm_weight, eps, residual=None):
+        """layer(RMSNorm(x)): x [bsz, q_len, K] bf16 -> [bsz, q_len, N]; see _forward_norm.  With `residual` (x's shape):
+        (layer(RMSNorm(x + residual)), x + residual) -- the sum, in x's shape, is the layer's new residual stream"""
+        y, bsz, q_len, *s = _forward_norm(self, x, norm_weight, eps, residual)
+        y = y.reshape(bsz, q_len, y.size(-1)) if bsz is not None else y.reshape(q_len, y.size(-1))
+        return y if residual is None else (y, s[0].reshape(x.shape))
 
 
 class FusedQLinear(nn.Module):
@@ -291,12 +312,15 @@ class FusedQLinear(nn.Module):
         return tuple(t.reshape(bsz, q_len, t.size(-1)) for t in y.split(self.splits, dim=1))
 
     @torch.no_grad()
-    def forward_norm(self, x, norm_weight, eps):
-        """the fused layers on RMSNorm(x) (input_layernorm -> q | k | v as one launch at decode sizes); see _forward_norm"""
-        y, bsz, q_len = _forward_norm(self, x, norm_weight, eps)
+    def forward_norm(self, x, norm_weight, eps, residual=None):
+        """the fused layers on RMSNorm(x) (input_layernorm -> q | k | v as one launch at decode sizes); see _forward_norm.  With
+        `residual` (x's shape): (the per-layer outputs of RMSNorm(x + residual), x + residual)"""
+        y, bsz, q_len, *s = _forward_norm(self, x, norm_weight, eps, residual)
         if bsz is None:
-            return tuple(t.reshape(q_len, t.size(-1)) for t in y.split(self.splits, dim=1))
-        return tuple(t.reshape(bsz, q_len, t.size(-1)) for t in y.split(self.splits, dim=1))
+            ys = tuple(t.reshape(q_len, t.size(-1)) for t in y.split(self.splits, dim=1))
+        else:
+            ys = tuple(t.reshape(bsz, q_len, t.size(-1)) for t in y.split(self.splits, dim=1))
+        return ys if residual is None else (ys, s[0].reshape(x.shape))
 
 
 class FusedMLP(nn.Module):
@@ -331,33 +355,54 @@ class FusedMLP(nn.Module):
             self.register_buffer("D_" + name, t)
 
     @torch.no_grad()
-    def forward(self, x, norm_weight=None, eps=1e-5):
+    def forward(self, x, norm_weight=None, eps=1e-5, residual=None):
         """`norm_weight` given: the MLP of RMSNorm(x) (post_attention_layernorm fused into the quantizer, as the reference's
-        rmsnorm_quantize_x caller does); at M = 1 the norm, the quantization and the gate | up GEMM are one launch"""
+        rmsnorm_quantize_x caller does); at M = 1 the norm, the quantization and the gate | up GEMM are one launch.
+        `residual` (x's shape, needs norm_weight): returns (the MLP of RMSNorm(s), s), s = x + residual in x's shape -- the same
+        dispatch with the add_ form of whichever launch holds the norm, so no launch and no pass over the rows is added"""
         lead = x.shape[:-1]
         x2 = x.reshape(-1, self.hidden).contiguous()
         gu = (self.GU_BN, self.GU_BS, self.GU_BO, self.GU_SFBN, self.GU_SFBS, self.GU_SFBO)
         m = x2.size(0)
         down = (self.D_BN, self.D_BS, self.D_BO, self.D_SFBN, self.D_SFBS, self.D_SFBO)
+        r2 = None
+        if residual is not None:
+            if norm_weight is None:
+                raise ValueError("residual needs norm_weight: the add is fused into the norm's quantizer")
+            if residual.dtype is not torch.bfloat16 or residual.device != x.device or tuple(residual.shape) != tuple(x.shape):
+                raise TypeError("residual must be a bfloat16 tensor of x's shape on its device")
+            r2 = residual.reshape(-1, self.hidden).contiguous()
+        done = lambda y, s=None: y.reshape(*lead, self.hidden) if r2 is None else (y.reshape(*lead, self.hidden), s.reshape(x.shape))
         # (a wide layer: gate_up_activate is ONE launch at M <= 16 -- then the fused pairs below, whose workgroups all repeat the
         # quantization, only win at M <= 2)
         pair_rows = 2 if mixedgemm.gate_up_activate_decode_supported(1, self.inter, *self.in_split) == 2 else 4
         if norm_weight is not None:
+            s = None
             if m <= 2 and mixedgemm.rmsnorm_gate_up_activate_decode_supported(m, self.inter, *self.in_split) == 2:
                 # round 6: norm, quantization, gate | up GEMM, silu * up and the quantization for down_proj in ONE launch; down_proj a plain GEMM
-                qh = mixedgemm.rmsnorm_gate_up_activate_decode(x2, norm_weight, eps, self.reorder_index, gu, *self.down_split, rounding=self.rounding)
+                if r2 is None:
+                    qh = mixedgemm.rmsnorm_gate_up_activate_decode(x2, norm_weight, eps, self.reorder_index, gu, *self.down_split, rounding=self.rounding)
+                else:
+                    s, *qh = mixedgemm.add_rmsnorm_gate_up_activate_decode(x2, r2, norm_weight, eps, self.reorder_index, gu, *self.down_split,
+                                                                           rounding=self.rounding)
                 y = mixedgemm.matmul(qh[0], self.D_BN, qh[1], self.D_BS, qh[2], self.D_BO, qh[3], self.D_SFBN, qh[4], self.D_SFBS, qh[5],
                                      self.D_SFBO, rounding=self.rounding)
-                return y.reshape(*lead, self.hidden)
+                return done(y, s)
             if m <= pair_rows and mixedgemm.rmsnorm_qlinear_decode_supported(m, 2 * self.inter, *self.in_split) == 2 \
                     and mixedgemm.down_activate_decode_supported(m, self.hidden, *self.down_split) == 2:
-                gub = mixedgemm.rmsnorm_qlinear_decode(x2, norm_weight, eps, self.reorder_index, *gu, *self.in_split, rounding=self.rounding)
-                return mixedgemm.down_activate_decode(gub, down, *self.down_split, rounding=self.rounding).reshape(*lead, self.hidden)
-            qx = mixedgemm.rmsnorm_quantize_x(x2, norm_weight, eps, self.reorder_index, *self.in_split)
+                if r2 is None:
+                    gub = mixedgemm.rmsnorm_qlinear_decode(x2, norm_weight, eps, self.reorder_index, *gu, *self.in_split, rounding=self.rounding)
+                else:
+                    s, gub = mixedgemm.add_rmsnorm_qlinear_decode(x2, r2, norm_weight, eps, self.reorder_index, *gu, *self.in_split, rounding=self.rounding)
+                return done(mixedgemm.down_activate_decode(gub, down, *self.down_split, rounding=self.rounding), s)
+            if r2 is None:
+                qx = mixedgemm.rmsnorm_quantize_x(x2, norm_weight, eps, self.reorder_index, *self.in_split)
+            else:
+                s, *qx = mixedgemm.add_rmsnorm_quantize_x(x2, r2, norm_weight, eps, self.reorder_index, *self.in_split)
             qh = mixedgemm.gate_up_activate(qx, gu, *self.down_split, rounding=self.rounding)
             y = mixedgemm.matmul(qh[0], self.D_BN, qh[1], self.D_BS, qh[2], self.D_BO, qh[3], self.D_SFBN, qh[4], self.D_SFBS, qh[5],
                                  self.D_SFBO, rounding=self.rounding)
-            return y.reshape(*lead, self.hidden)
+            return done(y, s)
         if m <= 2 and mixedgemm.gate_up_activate_decode_supported(m, self.inter, *self.in_split) == 2:
             qh = mixedgemm.gate_up_activate_decode(x2, self.reorder_index, gu, *self.down_split, rounding=self.rounding)      # ONE launch (round 6)
             y = mixedgemm.matmul(qh[0], self.D_BN, qh[1], self.D_BS, qh[2], self.D_BO, qh[3], self.D_SFBN, qh[4], self.D_SFBS, qh[5],
