@@ -22,10 +22,25 @@ static int fail_hip(hipError_t e, const char *where) {
 // fp4 in both modes, so it takes the fp4-weight kernels too (the matching-precision 256 x 256 kernel sits at its register limit).
 static bool weights_fp4(int wmode, int KS, int KO) { return wmode == MM_W_FP4 || (KS == 0 && KO == 0); }
 
-static bool split_ok(int K, int KN, int KS, int KO) {
-    return KN >= 0 && KS >= 0 && KO >= 0 && (KN % 128) == 0 && (KS % 128) == 0 && (KO % 128) == 0 && KN + KS + KO == K &&
-           K > 0;
+// a decode split is well-formed: three non-negative multiples of 128, not all zero
+static bool decode_split_ok(const int K[3]) {
+    return K[0] >= 0 && K[1] >= 0 && K[2] >= 0 && (K[0] % 128) == 0 && (K[1] % 128) == 0 && (K[2] % 128) == 0 && K[0] + K[1] + K[2] > 0;
 }
+
+// ... and adds up to a K given separately
+static bool split_ok(int K, int KN, int KS, int KO) {
+    const int Kseg[3] = {KN, KS, KO};
+    return decode_split_ok(Kseg) && KN + KS + KO == K;
+}
+
+// every non-empty segment has its data and its scale pointer
+struct Ptr3 { const uint8_t *p[3]; };
+static bool segments_ok(const int K[3], const Ptr3 &data, const Ptr3 &sf) {
+    return !((K[0] && (!data.p[0] || !sf.p[0])) || (K[1] && (!data.p[1] || !sf.p[1])) || (K[2] && (!data.p[2] || !sf.p[2])));
+}
+
+// which of its extern "C" entries a shared body serves: the pointers cannot tell (a null norm weight is an error of the norm entries)
+enum Variant { PLAIN, NORM, ADD_NORM };
 
 extern "C" {
 
@@ -58,7 +73,8 @@ int mm_reorder_quantize(const void *src_bf16, int rows, int K, const int16_t *re
     if (rows < 0 || K > 32768 || (mode != MM_QUANT_MIXED && mode != MM_QUANT_W4)) return MM_ERR_BAD_ARG;
     if (rows == 0) return MM_OK;
     if (!src_bf16 || !reorder_index) return MM_ERR_BAD_ARG;
-    if ((KN && (!oN || !sfN)) || (KS && (!oS || !sfS)) || (KO && (!oO || !sfO))) return MM_ERR_BAD_ARG;
+    const int Kseg[3] = {KN, KS, KO};
+    if (!segments_ok(Kseg, {oN, oS, oO}, {sfN, sfS, sfO})) return MM_ERR_BAD_ARG;
     hipError_t e = mm::launch_reorder_quantize(src_bf16, rows, K, reorder_index, KN, KS, KO, mode == MM_QUANT_W4, oN, oS,
                                                oO, sfN, sfS, sfO, (hipStream_t)stream);
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_reorder_quantize");
@@ -71,7 +87,8 @@ int mm_reorder_quantize_gather(const void *src_bf16, int rows, int K_in, const i
     if (rows < 0 || K_in > 32768 || (mode != MM_QUANT_MIXED && mode != MM_QUANT_W4)) return MM_ERR_BAD_ARG;
     if (rows == 0) return MM_OK;
     if (!src_bf16 || !index) return MM_ERR_BAD_ARG;
-    if ((KN && (!oN || !sfN)) || (KS && (!oS || !sfS)) || (KO && (!oO || !sfO))) return MM_ERR_BAD_ARG;
+    const int Kseg[3] = {KN, KS, KO};
+    if (!segments_ok(Kseg, {oN, oS, oO}, {sfN, sfS, sfO})) return MM_ERR_BAD_ARG;
     hipError_t e = mm::launch_reorder_quantize(src_bf16, rows, K_in, index, KN, KS, KO, mode == MM_QUANT_W4, oN, oS, oO,
                                                sfN, sfS, sfO, (hipStream_t)stream);
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_reorder_quantize_gather");
@@ -83,7 +100,8 @@ int mm_activate_quantize(const void *A_bf16, const void *B_bf16, int rows, int K
     if (rows < 0) return MM_ERR_BAD_ARG;
     if (rows == 0) return MM_OK;
     if (!A_bf16 || !B_bf16) return MM_ERR_BAD_ARG;
-    if ((KN && (!oN || !sfN)) || (KS && (!oS || !sfS)) || (KO && (!oO || !sfO))) return MM_ERR_BAD_ARG;
+    const int Kseg[3] = {KN, KS, KO};
+    if (!segments_ok(Kseg, {oN, oS, oO}, {sfN, sfS, sfO})) return MM_ERR_BAD_ARG;
     hipError_t e = mm::launch_direct_quantize(A_bf16, B_bf16, rows, KN, KS, KO, 0, oN, oS, oO, sfN, sfS, sfO, (hipStream_t)stream);
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_activate_quantize");
 }
@@ -94,23 +112,11 @@ int mm_downproj_quantize(const void *W_bf16, int rows, int KN, int KS, int KO, i
     if (rows < 0 || (mode != MM_QUANT_MIXED && mode != MM_QUANT_W4)) return MM_ERR_BAD_ARG;
     if (rows == 0) return MM_OK;
     if (!W_bf16) return MM_ERR_BAD_ARG;
-    if ((KN && (!oN || !sfN)) || (KS && (!oS || !sfS)) || (KO && (!oO || !sfO))) return MM_ERR_BAD_ARG;
+    const int Kseg[3] = {KN, KS, KO};
+    if (!segments_ok(Kseg, {oN, oS, oO}, {sfN, sfS, sfO})) return MM_ERR_BAD_ARG;
     hipError_t e = mm::launch_direct_quantize(W_bf16, nullptr, rows, KN, KS, KO, mode == MM_QUANT_W4 ? 2 : 1, oN, oS, oO, sfN, sfS,
                                               sfO, (hipStream_t)stream);
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_downproj_quantize");
-}
-
-int mm_rmsnorm_quantize(const void *X_bf16, const void *W_bf16, float eps, int rows, int K, const int16_t *reorder_index, int KN,
-                        int KS, int KO, int flags, uint8_t *oN, uint8_t *oS, uint8_t *oO, uint8_t *sfN, uint8_t *sfS,
-                        uint8_t *sfO, mm_stream_t stream) {
-    if (!split_ok(K, KN, KS, KO)) return MM_ERR_BAD_SPLIT;
-    if (rows < 0 || K > 32768) return MM_ERR_BAD_ARG;
-    if (rows == 0) return MM_OK;
-    if (!X_bf16 || !W_bf16 || !reorder_index) return MM_ERR_BAD_ARG;
-    if ((KN && (!oN || !sfN)) || (KS && (!oS || !sfS)) || (KO && (!oO || !sfO))) return MM_ERR_BAD_ARG;
-    hipError_t e = mm::launch_rmsnorm_quantize(X_bf16, W_bf16, eps, rows, K, reorder_index, KN, KS, KO,
-                                               !(flags & MM_RMS_NO_INTEGER_ROUND), oN, oS, oO, sfN, sfS, sfO, (hipStream_t)stream);
-    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_rmsnorm_quantize");
 }
 
 // [a, a + na) and [b, b + nb) share a byte
@@ -119,107 +125,111 @@ static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
     return x < y + nb && y < x + na;
 }
 
-int mm_add_rmsnorm_quantize(const void *X_bf16, const void *R_bf16, void *S_out_bf16, const void *W_bf16, float eps, int rows, int K,
-                            const int16_t *reorder_index, int KN, int KS, int KO, int flags, uint8_t *oN, uint8_t *oS, uint8_t *oO,
-                            uint8_t *sfN, uint8_t *sfS, uint8_t *sfO, mm_stream_t stream) {
-    if (!split_ok(K, KN, KS, KO)) return MM_ERR_BAD_SPLIT;
-    if (rows < 0 || K > 32768) return MM_ERR_BAD_ARG;
-    if (rows == 0) return MM_OK;
-    if (!X_bf16 || !R_bf16 || !S_out_bf16 || !W_bf16 || !reorder_index) return MM_ERR_BAD_ARG;
-    if ((KN && (!oN || !sfN)) || (KS && (!oS || !sfS)) || (KO && (!oO || !sfO))) return MM_ERR_BAD_ARG;
-    // rows travel in 16-byte pieces; K % 128 == 0 keeps every row of an aligned tensor aligned
-    if (((uintptr_t)X_bf16 & 15) || ((uintptr_t)R_bf16 & 15) || ((uintptr_t)S_out_bf16 & 15) || ((uintptr_t)W_bf16 & 15)) return MM_ERR_BAD_ARG;
-    const size_t bytes = (size_t)rows * (size_t)K * 2u;
-    if (ranges_overlap(S_out_bf16, bytes, X_bf16, bytes) || ranges_overlap(S_out_bf16, bytes, R_bf16, bytes)) return MM_ERR_BAD_ARG;
-    hipError_t e = mm::launch_add_rmsnorm_quantize(X_bf16, R_bf16, S_out_bf16, W_bf16, eps, rows, K, reorder_index, KN, KS, KO,
-                                                   !(flags & MM_RMS_NO_INTEGER_ROUND), oN, oS, oO, sfN, sfS, sfO, (hipStream_t)stream);
-    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_add_rmsnorm_quantize");
-}
-
-// (the five-argument queries answer for the matching-precision weight mode, whose ring / reduction tail is the larger one: what they
-// accept launches in either mode; the _w forms take the weight mode and accept the long-K fp4 shapes the 48 KB tail leaves room for)
-int mm_qlinear_decode_supported_w(int M, int N, int KN, int KS, int KO, int wmode) {
-    if (N < 0 || KN < 0 || KS < 0 || KO < 0 || (KN % 128) || (KS % 128) || (KO % 128) || KN + KS + KO == 0 || KN + KS + KO > 32768) return 0;
-    if (wmode != MM_W_MATCH && wmode != MM_W_FP4) return 0;
-    const int K[3] = {KN, KS, KO};
-    return mm::qlinear_decode_supported(M, N, K, false, weights_fp4(wmode, KS, KO));
-}
-int mm_qlinear_decode_supported(int M, int N, int KN, int KS, int KO) { return mm_qlinear_decode_supported_w(M, N, KN, KS, KO, (KS | KO) ? MM_W_MATCH : MM_W_FP4); }
-
-int mm_qlinear_decode(const void *X_bf16, const int16_t *reorder_index, const uint8_t *BN, const uint8_t *BS, const uint8_t *BO,
-                      const uint8_t *SFBN, const uint8_t *SFBS, const uint8_t *SFBO, int M, int N, int KN, int KS, int KO,
-                      int wmode, int flags, const void *bias_bf16, void *D_bf16, mm_stream_t stream) {
-    if (M < 0 || N < 0 || KN < 0 || KS < 0 || KO < 0) return MM_ERR_BAD_ARG;
-    if ((KN % 128) || (KS % 128) || (KO % 128) || KN + KS + KO == 0) return MM_ERR_BAD_SPLIT;
-    if (wmode != MM_W_MATCH && wmode != MM_W_FP4) return MM_ERR_BAD_ARG;
-    if (flags & MM_OUT_F32) return MM_ERR_UNSUPPORTED;    // fp32 partial sums come from mm_matmul only
-    if (M == 0 || N == 0) return MM_OK;
-    if (!mm_qlinear_decode_supported_w(M, N, KN, KS, KO, wmode)) return MM_ERR_UNSUPPORTED;
-    if (!X_bf16 || !reorder_index || !D_bf16) return MM_ERR_BAD_ARG;
-    if ((KN && (!BN || !SFBN)) || (KS && (!BS || !SFBS)) || (KO && (!BO || !SFBO))) return MM_ERR_BAD_ARG;
-    const uint8_t *W[3] = {BN, BS, BO}, *SFW[3] = {SFBN, SFBS, SFBO};
-    const int K[3] = {KN, KS, KO};
-    hipError_t e = mm::launch_qlinear_decode(X_bf16, reorder_index, W, SFW, M, N, K, weights_fp4(wmode, KS, KO),
-                                             (flags & MM_ROUND_ONCE) ? 0 : 1, bias_bf16, D_bf16, (hipStream_t)stream);
-    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_qlinear_decode");
-}
-
-int mm_rmsnorm_qlinear_decode_supported_w(int M, int N, int KN, int KS, int KO, int wmode) {
-    if (N < 0 || KN < 0 || KS < 0 || KO < 0 || (KN % 128) || (KS % 128) || (KO % 128) || KN + KS + KO == 0 || KN + KS + KO > 32768) return 0;
-    if (wmode != MM_W_MATCH && wmode != MM_W_FP4) return 0;
-    const int K[3] = {KN, KS, KO};
-    return mm::qlinear_decode_supported(M, N, K, true, weights_fp4(wmode, KS, KO));
-}
-int mm_rmsnorm_qlinear_decode_supported(int M, int N, int KN, int KS, int KO) { return mm_rmsnorm_qlinear_decode_supported_w(M, N, KN, KS, KO, (KS | KO) ? MM_W_MATCH : MM_W_FP4); }
-
-int mm_rmsnorm_qlinear_decode(const void *X_bf16, const void *norm_weight_bf16, float eps, const int16_t *reorder_index, const uint8_t *BN,
-                              const uint8_t *BS, const uint8_t *BO, const uint8_t *SFBN, const uint8_t *SFBS, const uint8_t *SFBO, int M, int N,
-                              int KN, int KS, int KO, int wmode, int flags, const void *bias_bf16, void *D_bf16, mm_stream_t stream) {
-    if (M < 0 || N < 0 || KN < 0 || KS < 0 || KO < 0) return MM_ERR_BAD_ARG;
-    if ((KN % 128) || (KS % 128) || (KO % 128) || KN + KS + KO == 0) return MM_ERR_BAD_SPLIT;
-    if (wmode != MM_W_MATCH && wmode != MM_W_FP4) return MM_ERR_BAD_ARG;
-    if (flags & ~(MM_ROUND_ONCE | MM_NORM_NO_INTEGER_ROUND)) return MM_ERR_BAD_ARG;
-    if (M == 0 || N == 0) return MM_OK;
-    if (!mm_rmsnorm_qlinear_decode_supported_w(M, N, KN, KS, KO, wmode)) return MM_ERR_UNSUPPORTED;
-    if (!X_bf16 || !norm_weight_bf16 || !reorder_index || !D_bf16) return MM_ERR_BAD_ARG;
-    if (((uintptr_t)X_bf16 & 15) || ((uintptr_t)norm_weight_bf16 & 15)) return MM_ERR_BAD_ARG;      // rows and weights are staged in 16-byte pieces
-    if ((KN && (!BN || !SFBN)) || (KS && (!BS || !SFBS)) || (KO && (!BO || !SFBO))) return MM_ERR_BAD_ARG;
-    const uint8_t *W[3] = {BN, BS, BO}, *SFW[3] = {SFBN, SFBS, SFBO};
-    const int K[3] = {KN, KS, KO};
-    const mm::NormArgs norm = {norm_weight_bf16, eps, (flags & MM_NORM_NO_INTEGER_ROUND) ? 0 : 1};
-    hipError_t e = mm::launch_qlinear_decode(X_bf16, reorder_index, W, SFW, M, N, K, weights_fp4(wmode, KS, KO),
-                                             (flags & MM_ROUND_ONCE) ? 0 : 1, bias_bf16, D_bf16, (hipStream_t)stream, norm);
-    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_rmsnorm_qlinear_decode");
-}
-
-// S_out of the add_ decode entries: non-null, 16-byte aligned like R, and clear of X and R -- every workgroup re-reads both while
-// workgroup 0 writes S_out, so an in-place update would race
+// S_out of the add_ entries: non-null, 16-byte aligned like R, and clear of X and R -- every workgroup of the decode launches re-reads
+// both while workgroup 0 writes S_out, so an in-place update would race
 static bool residual_ok(const void *X, const void *R, const void *S_out, int M, int K) {
     if (!R || !S_out || ((uintptr_t)R & 15) || ((uintptr_t)S_out & 15)) return false;
     const size_t bytes = (size_t)M * (size_t)K * 2u;
     return !ranges_overlap(S_out, bytes, X, bytes) && !ranges_overlap(S_out, bytes, R, bytes);
 }
 
+// mm_rmsnorm_quantize (NORM) and mm_add_rmsnorm_quantize (ADD_NORM)
+static int rmsnorm_quantize_entry(Variant v, const void *X_bf16, const void *R_bf16, void *S_out_bf16, const void *W_bf16, float eps, int rows, int K,
+                                  const int16_t *reorder_index, int KN, int KS, int KO, int flags, uint8_t *oN, uint8_t *oS, uint8_t *oO,
+                                  uint8_t *sfN, uint8_t *sfS, uint8_t *sfO, mm_stream_t stream) {
+    if (!split_ok(K, KN, KS, KO)) return MM_ERR_BAD_SPLIT;
+    if (rows < 0 || K > 32768) return MM_ERR_BAD_ARG;
+    if (rows == 0) return MM_OK;
+    if (!X_bf16 || !W_bf16 || !reorder_index) return MM_ERR_BAD_ARG;
+    const int Kseg[3] = {KN, KS, KO};
+    if (!segments_ok(Kseg, {oN, oS, oO}, {sfN, sfS, sfO})) return MM_ERR_BAD_ARG;
+    const bool int_round = !(flags & MM_RMS_NO_INTEGER_ROUND);
+    if (v == NORM) {    // (mm_rmsnorm_quantize asks no alignment of X and W)
+        hipError_t e = mm::launch_rmsnorm_quantize(X_bf16, W_bf16, eps, rows, K, reorder_index, KN, KS, KO, int_round, oN, oS, oO, sfN, sfS, sfO,
+                                                   (hipStream_t)stream);
+        return e == hipSuccess ? MM_OK : fail_hip(e, "mm_rmsnorm_quantize");
+    }
+    // rows travel in 16-byte pieces; K % 128 == 0 keeps every row of an aligned tensor aligned
+    if (((uintptr_t)X_bf16 & 15) || ((uintptr_t)W_bf16 & 15) || !residual_ok(X_bf16, R_bf16, S_out_bf16, rows, K)) return MM_ERR_BAD_ARG;
+    hipError_t e = mm::launch_add_rmsnorm_quantize(X_bf16, R_bf16, S_out_bf16, W_bf16, eps, rows, K, reorder_index, KN, KS, KO, int_round, oN, oS, oO,
+                                                   sfN, sfS, sfO, (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_add_rmsnorm_quantize");
+}
+
+int mm_rmsnorm_quantize(const void *X_bf16, const void *W_bf16, float eps, int rows, int K, const int16_t *reorder_index, int KN,
+                        int KS, int KO, int flags, uint8_t *oN, uint8_t *oS, uint8_t *oO, uint8_t *sfN, uint8_t *sfS,
+                        uint8_t *sfO, mm_stream_t stream) {
+    return rmsnorm_quantize_entry(NORM, X_bf16, nullptr, nullptr, W_bf16, eps, rows, K, reorder_index, KN, KS, KO, flags, oN, oS, oO, sfN, sfS, sfO,
+                                  stream);
+}
+
+int mm_add_rmsnorm_quantize(const void *X_bf16, const void *R_bf16, void *S_out_bf16, const void *W_bf16, float eps, int rows, int K,
+                            const int16_t *reorder_index, int KN, int KS, int KO, int flags, uint8_t *oN, uint8_t *oS, uint8_t *oO,
+                            uint8_t *sfN, uint8_t *sfS, uint8_t *sfO, mm_stream_t stream) {
+    return rmsnorm_quantize_entry(ADD_NORM, X_bf16, R_bf16, S_out_bf16, W_bf16, eps, rows, K, reorder_index, KN, KS, KO, flags, oN, oS, oO, sfN, sfS,
+                                  sfO, stream);
+}
+
+// (the five-argument queries answer for the matching-precision weight mode, whose ring / reduction tail is the larger one: what they
+// accept launches in either mode; the _w forms take the weight mode and accept the long-K fp4 shapes the 48 KB tail leaves room for)
+static int decode_supported_w(int M, int N, int KN, int KS, int KO, int wmode, bool rms) {
+    const int K[3] = {KN, KS, KO};
+    if (N < 0 || !decode_split_ok(K) || KN + KS + KO > 32768) return 0;
+    if (wmode != MM_W_MATCH && wmode != MM_W_FP4) return 0;
+    return mm::qlinear_decode_supported(M, N, K, rms, weights_fp4(wmode, KS, KO));
+}
+int mm_qlinear_decode_supported_w(int M, int N, int KN, int KS, int KO, int wmode) { return decode_supported_w(M, N, KN, KS, KO, wmode, false); }
+int mm_qlinear_decode_supported(int M, int N, int KN, int KS, int KO) { return decode_supported_w(M, N, KN, KS, KO, (KS | KO) ? MM_W_MATCH : MM_W_FP4, false); }
+int mm_rmsnorm_qlinear_decode_supported_w(int M, int N, int KN, int KS, int KO, int wmode) { return decode_supported_w(M, N, KN, KS, KO, wmode, true); }
+int mm_rmsnorm_qlinear_decode_supported(int M, int N, int KN, int KS, int KO) { return decode_supported_w(M, N, KN, KS, KO, (KS | KO) ? MM_W_MATCH : MM_W_FP4, true); }
+
+static mm::NormArgs norm_args(const void *weight, float eps, int flags, const void *res = nullptr, void *s_out = nullptr) {
+    return {weight, eps, (flags & MM_NORM_NO_INTEGER_ROUND) ? 0 : 1, res, s_out};
+}
+
+// mm_qlinear_decode (PLAIN, norm = mm::NO_NORM), mm_rmsnorm_qlinear_decode (NORM) and mm_add_rmsnorm_qlinear_decode (ADD_NORM: norm.res / norm.s_out)
+static int qlinear_decode_entry(Variant v, const void *X_bf16, const mm::NormArgs &norm, const int16_t *reorder_index, const Ptr3 &B, const Ptr3 &SFB,
+                                int M, int N, int KN, int KS, int KO, int wmode, int flags, const void *bias_bf16, void *D_bf16, mm_stream_t stream) {
+    static const char *const name[] = {"mm_qlinear_decode", "mm_rmsnorm_qlinear_decode", "mm_add_rmsnorm_qlinear_decode"};
+    const int K[3] = {KN, KS, KO};
+    if (M < 0 || N < 0 || KN < 0 || KS < 0 || KO < 0) return MM_ERR_BAD_ARG;
+    if (!decode_split_ok(K)) return MM_ERR_BAD_SPLIT;
+    if (wmode != MM_W_MATCH && wmode != MM_W_FP4) return MM_ERR_BAD_ARG;
+    if (v == PLAIN) {   // mm_qlinear_decode: fp32 partial sums come from mm_matmul only; it ignores every other unknown bit
+        if (flags & MM_OUT_F32) return MM_ERR_UNSUPPORTED;
+    } else if (flags & ~(MM_ROUND_ONCE | MM_NORM_NO_INTEGER_ROUND)) return MM_ERR_BAD_ARG;     // the norm entries refuse any unknown bit
+    if (M == 0 || N == 0) return MM_OK;
+    if (!decode_supported_w(M, N, KN, KS, KO, wmode, v != PLAIN)) return MM_ERR_UNSUPPORTED;
+    if (!X_bf16 || !reorder_index || !D_bf16) return MM_ERR_BAD_ARG;
+    // the norm entries stage rows and weights in 16-byte pieces; mm_qlinear_decode asks no alignment of X
+    if (v != PLAIN && (!norm.weight || ((uintptr_t)X_bf16 & 15) || ((uintptr_t)norm.weight & 15))) return MM_ERR_BAD_ARG;
+    if (v == ADD_NORM && !residual_ok(X_bf16, norm.res, norm.s_out, M, KN + KS + KO)) return MM_ERR_BAD_ARG;
+    if (!segments_ok(K, B, SFB)) return MM_ERR_BAD_ARG;
+    hipError_t e = mm::launch_qlinear_decode(X_bf16, reorder_index, B.p, SFB.p, M, N, K, weights_fp4(wmode, KS, KO), (flags & MM_ROUND_ONCE) ? 0 : 1,
+                                             bias_bf16, D_bf16, (hipStream_t)stream, norm);
+    return e == hipSuccess ? MM_OK : fail_hip(e, name[v]);
+}
+
+int mm_qlinear_decode(const void *X_bf16, const int16_t *reorder_index, const uint8_t *BN, const uint8_t *BS, const uint8_t *BO,
+                      const uint8_t *SFBN, const uint8_t *SFBS, const uint8_t *SFBO, int M, int N, int KN, int KS, int KO,
+                      int wmode, int flags, const void *bias_bf16, void *D_bf16, mm_stream_t stream) {
+    return qlinear_decode_entry(PLAIN, X_bf16, mm::NO_NORM, reorder_index, {BN, BS, BO}, {SFBN, SFBS, SFBO}, M, N, KN, KS, KO, wmode, flags, bias_bf16,
+                                D_bf16, stream);
+}
+
+int mm_rmsnorm_qlinear_decode(const void *X_bf16, const void *norm_weight_bf16, float eps, const int16_t *reorder_index, const uint8_t *BN,
+                              const uint8_t *BS, const uint8_t *BO, const uint8_t *SFBN, const uint8_t *SFBS, const uint8_t *SFBO, int M, int N,
+                              int KN, int KS, int KO, int wmode, int flags, const void *bias_bf16, void *D_bf16, mm_stream_t stream) {
+    return qlinear_decode_entry(NORM, X_bf16, norm_args(norm_weight_bf16, eps, flags), reorder_index, {BN, BS, BO}, {SFBN, SFBS, SFBO}, M, N, KN, KS, KO,
+                                wmode, flags, bias_bf16, D_bf16, stream);
+}
+
 int mm_add_rmsnorm_qlinear_decode(const void *X_bf16, const void *R_bf16, void *S_out_bf16, const void *norm_weight_bf16, float eps,
                                   const int16_t *reorder_index, const uint8_t *BN, const uint8_t *BS, const uint8_t *BO, const uint8_t *SFBN,
                                   const uint8_t *SFBS, const uint8_t *SFBO, int M, int N, int KN, int KS, int KO, int wmode, int flags,
                                   const void *bias_bf16, void *D_bf16, mm_stream_t stream) {
-    if (M < 0 || N < 0 || KN < 0 || KS < 0 || KO < 0) return MM_ERR_BAD_ARG;
-    if ((KN % 128) || (KS % 128) || (KO % 128) || KN + KS + KO == 0) return MM_ERR_BAD_SPLIT;
-    if (wmode != MM_W_MATCH && wmode != MM_W_FP4) return MM_ERR_BAD_ARG;
-    if (flags & ~(MM_ROUND_ONCE | MM_NORM_NO_INTEGER_ROUND)) return MM_ERR_BAD_ARG;
-    if (M == 0 || N == 0) return MM_OK;
-    if (!mm_rmsnorm_qlinear_decode_supported_w(M, N, KN, KS, KO, wmode)) return MM_ERR_UNSUPPORTED;
-    if (!X_bf16 || !norm_weight_bf16 || !reorder_index || !D_bf16) return MM_ERR_BAD_ARG;
-    if (((uintptr_t)X_bf16 & 15) || ((uintptr_t)norm_weight_bf16 & 15)) return MM_ERR_BAD_ARG;
-    if (!residual_ok(X_bf16, R_bf16, S_out_bf16, M, KN + KS + KO)) return MM_ERR_BAD_ARG;
-    if ((KN && (!BN || !SFBN)) || (KS && (!BS || !SFBS)) || (KO && (!BO || !SFBO))) return MM_ERR_BAD_ARG;
-    const uint8_t *W[3] = {BN, BS, BO}, *SFW[3] = {SFBN, SFBS, SFBO};
-    const int K[3] = {KN, KS, KO};
-    const mm::NormArgs norm = {norm_weight_bf16, eps, (flags & MM_NORM_NO_INTEGER_ROUND) ? 0 : 1, R_bf16, S_out_bf16};
-    hipError_t e = mm::launch_qlinear_decode(X_bf16, reorder_index, W, SFW, M, N, K, weights_fp4(wmode, KS, KO),
-                                             (flags & MM_ROUND_ONCE) ? 0 : 1, bias_bf16, D_bf16, (hipStream_t)stream, norm);
-    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_add_rmsnorm_qlinear_decode");
+    return qlinear_decode_entry(ADD_NORM, X_bf16, norm_args(norm_weight_bf16, eps, flags, R_bf16, S_out_bf16), reorder_index, {BN, BS, BO},
+                                {SFBN, SFBS, SFBO}, M, N, KN, KS, KO, wmode, flags, bias_bf16, D_bf16, stream);
 }
 
 size_t mm_matmul_workspace_bytes(int M, int N, int KN, int KS, int KO, int wmode, int flags) {
@@ -229,8 +239,8 @@ size_t mm_matmul_workspace_bytes(int M, int N, int KN, int KS, int KO, int wmode
 }
 
 const char *mm_matmul_describe(int M, int N, int KN, int KS, int KO, int wmode, int flags, size_t workspace_bytes) {
-    if (M <= 0 || N <= 0 || KN < 0 || KS < 0 || KO < 0 || (KN % 128) || (KS % 128) || (KO % 128) || KN + KS + KO == 0) return "none";
     const int K[3] = {KN, KS, KO};
+    if (M <= 0 || N <= 0 || !decode_split_ok(K)) return "none";
     if (M <= 64 && !mm::mx_gemm_small_m_uses_tiles(M, N, K, weights_fp4(wmode, KS, KO), workspace_bytes, (flags & MM_SPLIT_K_ALWAYS) != 0))
         return mm::mx_gemm_stream_supported(M, N, K, weights_fp4(wmode, KS, KO)) ? "mm::stream::mx_gemm_stream_kernel (weight streaming, M <= 64)"
                                                                          : "mm::skinny::mx_gemm_skinny*_kernel (weight streaming, M <= 64)";
@@ -257,9 +267,8 @@ int mm_matmul_ws(const uint8_t *AN, const uint8_t *BN, const uint8_t *AS, const 
     if (!D_bf16) return MM_ERR_BAD_ARG;
     const bool out_f32 = (flags & MM_OUT_F32) != 0;
     if (out_f32 && (!(flags & MM_ROUND_ONCE) || bias_bf16)) return MM_ERR_BAD_ARG;   // fp32 partial sums: no chain rounding, no bias
-    if ((KN && (!AN || !BN || !SFAN || !SFBN)) || (KS && (!AS || !BS || !SFAS || !SFBS)) ||
-        (KO && (!AO || !BO || !SFAO || !SFBO)))
-        return MM_ERR_BAD_ARG;
+    const int K[3] = {KN, KS, KO};
+    if (!segments_ok(K, {AN, AS, AO}, {SFAN, SFAS, SFAO}) || !segments_ok(K, {BN, BS, BO}, {SFBN, SFBS, SFBO})) return MM_ERR_BAD_ARG;
     if (KN + KS + KO == 0) {  // reference: C = zeros, no segment runs (gemm.cu:48-50)
         hipError_t e = hipMemsetAsync(D_bf16, 0, (size_t)M * N * (out_f32 ? 4 : 2), (hipStream_t)stream);
         return e == hipSuccess ? MM_OK : fail_hip(e, "mm_matmul(memset)");
@@ -338,16 +347,15 @@ int mm_gate_up_activate(const uint8_t *AN, const uint8_t *BN, const uint8_t *AS,
                         const uint8_t *SFAO, const uint8_t *SFBO, int M, int I, int KN, int KS, int KO, int DN, int DS, int DO,
                         int flags, uint8_t *oN, uint8_t *oS, uint8_t *oO, uint8_t *sfN, uint8_t *sfS, uint8_t *sfO, void *workspace,
                         size_t workspace_bytes, mm_stream_t stream) {
+    const int Kin[3] = {KN, KS, KO}, Kd[3] = {DN, DS, DO};
     if (M < 0 || I < 0 || KN < 0 || KS < 0 || KO < 0) return MM_ERR_BAD_ARG;
-    if ((KN % 128) || (KS % 128) || (KO % 128) || KN + KS + KO == 0) return MM_ERR_BAD_SPLIT;
-    if (!split_ok(DN + DS + DO, DN, DS, DO) || DN + DS + DO != I) return MM_ERR_BAD_SPLIT;
+    if (!decode_split_ok(Kin)) return MM_ERR_BAD_SPLIT;
+    if (!split_ok(I, DN, DS, DO)) return MM_ERR_BAD_SPLIT;
     if (flags & ~MM_ROUND_ONCE) return MM_ERR_BAD_ARG;
     if (M == 0) return MM_OK;
-    if ((KN && (!AN || !BN || !SFAN || !SFBN)) || (KS && (!AS || !BS || !SFAS || !SFBS)) || (KO && (!AO || !BO || !SFAO || !SFBO)))
-        return MM_ERR_BAD_ARG;
-    if ((DN && (!oN || !sfN)) || (DS && (!oS || !sfS)) || (DO && (!oO || !sfO))) return MM_ERR_BAD_ARG;
+    if (!segments_ok(Kin, {AN, AS, AO}, {SFAN, SFAS, SFAO}) || !segments_ok(Kin, {BN, BS, BO}, {SFBN, SFBS, SFBO})) return MM_ERR_BAD_ARG;
+    if (!segments_ok(Kd, {oN, oS, oO}, {sfN, sfS, sfO})) return MM_ERR_BAD_ARG;
     const int N = 2 * I;
-    const int Kin[3] = {KN, KS, KO};
     if (!mm::mx_gemm_act_supported(M, N) && mm::gate_up_act_stream_supported(M, N, Kin, false, false)) {
         // M <= 16 on a wide layer (round 6): ONE weight-streaming launch with the activation inside -- no scratch, the same bytes
         mm::GemmArgs a = act_stream_args(BN, BS, BO, SFBN, SFBS, SFBO, M, I, KN, KS, KO, DN, DS, DO, flags, oN, oS, oO, sfN, sfS, sfO);
@@ -395,82 +403,70 @@ int mm_gate_up_activate(const uint8_t *AN, const uint8_t *BN, const uint8_t *AS,
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_gate_up_activate");
 }
 
+// 2: ONE launch and expected to be the fastest way through the MLP's first half (M <= 2: at M = 3, 4 every workgroup repeating the
+// quantization loses to mm_rmsnorm_quantize / mm_reorder_quantize -> mm_gate_up_activate, itself one launch at M <= 16 --
+// tools/time_mlp_decode.py: Llama-3-8B MLP at M = 1 / 2 / 4 23.1 / 25.3 / 36.9 us against 26.3 / 26.7 / 27.2); 1: runs; 0: cannot
+static int gate_up_decode_supported(int M, int I, int KN, int KS, int KO, bool rms) {
+    const int Kin[3] = {KN, KS, KO};
+    if (M < 1 || I < 128 || (I % 128) || !decode_split_ok(Kin)) return 0;
+    if (mm::gate_up_act_stream_supported(M, 2 * I, Kin, true, rms)) return M <= 2 ? 2 : 1;
+    return decode_supported_w(M, 2 * I, KN, KS, KO, MM_W_FP4, rms) ? 1 : 0;
+}
+int mm_rmsnorm_gate_up_activate_decode_supported(int M, int I, int KN, int KS, int KO) { return gate_up_decode_supported(M, I, KN, KS, KO, true); }
+int mm_gate_up_activate_decode_supported(int M, int I, int KN, int KS, int KO) { return gate_up_decode_supported(M, I, KN, KS, KO, false); }
+
+// mm_gate_up_activate_decode (PLAIN, norm = mm::NO_NORM), mm_rmsnorm_gate_up_activate_decode (NORM) and mm_add_rmsnorm_gate_up_activate_decode
+// (ADD_NORM: norm.res / norm.s_out)
+static int gate_up_decode_entry(Variant v, const void *X_bf16, const mm::NormArgs &norm, const int16_t *reorder_index, const Ptr3 &B, const Ptr3 &SFB,
+                                int M, int I, int KN, int KS, int KO, int DN, int DS, int DO, int flags, uint8_t *oN, uint8_t *oS, uint8_t *oO,
+                                uint8_t *sfN, uint8_t *sfS, uint8_t *sfO, void *workspace, size_t workspace_bytes, mm_stream_t stream) {
+    static const char *const name[] = {"mm_gate_up_activate_decode", "mm_rmsnorm_gate_up_activate_decode", "mm_add_rmsnorm_gate_up_activate_decode"};
+    const int Kin[3] = {KN, KS, KO}, Kd[3] = {DN, DS, DO};
+    if (M < 0 || I < 0 || KN < 0 || KS < 0 || KO < 0) return MM_ERR_BAD_ARG;
+    if (!decode_split_ok(Kin)) return MM_ERR_BAD_SPLIT;
+    if (!split_ok(I, DN, DS, DO)) return MM_ERR_BAD_SPLIT;
+    if (flags & ~(v == PLAIN ? MM_ROUND_ONCE : MM_ROUND_ONCE | MM_NORM_NO_INTEGER_ROUND)) return MM_ERR_BAD_ARG;
+    if (M == 0) return MM_OK;
+    const int N = 2 * I;
+    // mm_gate_up_activate_decode asks what its two-launch form needs; the norm entries ask their own query (I >= 128, either form)
+    if (!(v == PLAIN ? decode_supported_w(M, N, KN, KS, KO, MM_W_FP4, false) : gate_up_decode_supported(M, I, KN, KS, KO, true))) return MM_ERR_UNSUPPORTED;
+    // M <= 4 on a wide layer (round 6): (norm,) quantization, GEMM, silu(gate) * up and the consumer's quantization in ONE launch
+    const bool one_launch = mm::gate_up_act_stream_supported(M, N, Kin, true, v != PLAIN);
+    if (!X_bf16 || !reorder_index || !segments_ok(Kin, B, SFB) || !segments_ok(Kd, {oN, oS, oO}, {sfN, sfS, sfO})) return MM_ERR_BAD_ARG;
+    // mm_gate_up_activate_decode asks the alignment of X in its one-launch form only (its other form is mm_qlinear_decode, which asks none)
+    if ((v != PLAIN || one_launch) && ((uintptr_t)X_bf16 & 15)) return MM_ERR_BAD_ARG;
+    if (v != PLAIN && (!norm.weight || ((uintptr_t)norm.weight & 15))) return MM_ERR_BAD_ARG;
+    if (v == ADD_NORM && !residual_ok(X_bf16, norm.res, norm.s_out, M, KN + KS + KO)) return MM_ERR_BAD_ARG;
+    if (one_launch) {
+        const mm::GemmArgs a = act_stream_args(B.p[0], B.p[1], B.p[2], SFB.p[0], SFB.p[1], SFB.p[2], M, I, KN, KS, KO, DN, DS, DO, flags, oN, oS, oO, sfN,
+                                               sfS, sfO);
+        hipError_t e = mm::launch_gate_up_act_stream_decode(X_bf16, reorder_index, a, (hipStream_t)stream, norm);
+        return e == hipSuccess ? MM_OK : fail_hip(e, name[v]);
+    }
+    // two launches: (add + norm +) quantize + gate | up GEMM into the scratch (columns alternate 128 gate | 128 up), then the activation
+    // quantizer on that layout: the bytes of mm_reorder_quantize -> mm_gate_up_activate (tests/test_gate_up_gpu.py)
+    if (!workspace || workspace_bytes < (size_t)M * N * sizeof(uint16_t) || ((uintptr_t)workspace & 15)) return MM_ERR_BAD_ARG;
+    const int st = qlinear_decode_entry(v, X_bf16, norm, reorder_index, B, SFB, M, N, KN, KS, KO, MM_W_FP4, flags, nullptr, workspace, stream);
+    if (st != MM_OK) return st;
+    hipError_t e = mm::launch_direct_quantize(workspace, (const uint16_t *)workspace + 128, M, DN, DS, DO, 3, oN, oS, oO, sfN, sfS, sfO,
+                                              (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, name[v]);
+}
+
 int mm_gate_up_activate_decode(const void *X_bf16, const int16_t *reorder_index, const uint8_t *BN, const uint8_t *BS, const uint8_t *BO,
                                const uint8_t *SFBN, const uint8_t *SFBS, const uint8_t *SFBO, int M, int I, int KN, int KS, int KO, int DN,
                                int DS, int DO, int flags, uint8_t *oN, uint8_t *oS, uint8_t *oO, uint8_t *sfN, uint8_t *sfS, uint8_t *sfO,
                                void *workspace, size_t workspace_bytes, mm_stream_t stream) {
-    if (M < 0 || I < 0 || KN < 0 || KS < 0 || KO < 0) return MM_ERR_BAD_ARG;
-    if ((KN % 128) || (KS % 128) || (KO % 128) || KN + KS + KO == 0) return MM_ERR_BAD_SPLIT;
-    if (!split_ok(DN + DS + DO, DN, DS, DO) || DN + DS + DO != I) return MM_ERR_BAD_SPLIT;
-    if (flags & ~MM_ROUND_ONCE) return MM_ERR_BAD_ARG;
-    if (M == 0) return MM_OK;
-    const int N = 2 * I;
-    if (!mm_qlinear_decode_supported_w(M, N, KN, KS, KO, MM_W_FP4)) return MM_ERR_UNSUPPORTED;
-    if ((DN && (!oN || !sfN)) || (DS && (!oS || !sfS)) || (DO && (!oO || !sfO))) return MM_ERR_BAD_ARG;
-    const int Kin[3] = {KN, KS, KO};
-    if (mm::gate_up_act_stream_supported(M, N, Kin, true, false)) {
-        // M <= 4 on a wide layer (round 6): quantization, GEMM, silu(gate) * up and the consumer's quantization in ONE launch
-        if (!X_bf16 || !reorder_index || ((uintptr_t)X_bf16 & 15)) return MM_ERR_BAD_ARG;
-        if ((KN && (!BN || !SFBN)) || (KS && (!BS || !SFBS)) || (KO && (!BO || !SFBO))) return MM_ERR_BAD_ARG;
-        const mm::GemmArgs a = act_stream_args(BN, BS, BO, SFBN, SFBS, SFBO, M, I, KN, KS, KO, DN, DS, DO, flags, oN, oS, oO, sfN, sfS, sfO);
-        hipError_t e = mm::launch_gate_up_act_stream_decode(X_bf16, reorder_index, a, (hipStream_t)stream);
-        return e == hipSuccess ? MM_OK : fail_hip(e, "mm_gate_up_activate_decode");
-    }
-    if (!workspace || workspace_bytes < (size_t)M * N * sizeof(uint16_t) || ((uintptr_t)workspace & 15)) return MM_ERR_BAD_ARG;
-    // quantize + gate | up GEMM in one launch into the scratch (columns alternate 128 gate | 128 up), then the activation quantizer on
-    // that layout: the bytes of mm_reorder_quantize -> mm_gate_up_activate (tests/test_gate_up_gpu.py)
-    const int st = mm_qlinear_decode(X_bf16, reorder_index, BN, BS, BO, SFBN, SFBS, SFBO, M, N, KN, KS, KO, MM_W_FP4, flags, nullptr, workspace, stream);
-    if (st != MM_OK) return st;
-    hipError_t e = mm::launch_direct_quantize(workspace, (const uint16_t *)workspace + 128, M, DN, DS, DO, 3, oN, oS, oO, sfN, sfS, sfO,
-                                              (hipStream_t)stream);
-    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_gate_up_activate_decode");
-}
-
-// 2: ONE launch and expected to be the fastest way through the MLP's first half (M <= 2: at M = 3, 4 every workgroup repeating the
-// quantization loses to mm_rmsnorm_quantize / mm_reorder_quantize -> mm_gate_up_activate, itself one launch at M <= 16 --
-// tools/time_mlp_decode.py: Llama-3-8B MLP at M = 1 / 2 / 4 23.1 / 25.3 / 36.9 us against 26.3 / 26.7 / 27.2); 1: runs; 0: cannot
-int mm_rmsnorm_gate_up_activate_decode_supported(int M, int I, int KN, int KS, int KO) {
-    if (M < 1 || I < 128 || (I % 128) || KN < 0 || KS < 0 || KO < 0 || (KN % 128) || (KS % 128) || (KO % 128) || KN + KS + KO == 0) return 0;
-    const int Kin[3] = {KN, KS, KO};
-    if (mm::gate_up_act_stream_supported(M, 2 * I, Kin, true, true)) return M <= 2 ? 2 : 1;
-    return mm_rmsnorm_qlinear_decode_supported_w(M, 2 * I, KN, KS, KO, MM_W_FP4) ? 1 : 0;
-}
-int mm_gate_up_activate_decode_supported(int M, int I, int KN, int KS, int KO) {
-    if (M < 1 || I < 128 || (I % 128) || KN < 0 || KS < 0 || KO < 0 || (KN % 128) || (KS % 128) || (KO % 128) || KN + KS + KO == 0) return 0;
-    const int Kin[3] = {KN, KS, KO};
-    if (mm::gate_up_act_stream_supported(M, 2 * I, Kin, true, false)) return M <= 2 ? 2 : 1;
-    return mm_qlinear_decode_supported_w(M, 2 * I, KN, KS, KO, MM_W_FP4) ? 1 : 0;
+    return gate_up_decode_entry(PLAIN, X_bf16, mm::NO_NORM, reorder_index, {BN, BS, BO}, {SFBN, SFBS, SFBO}, M, I, KN, KS, KO, DN, DS, DO, flags, oN, oS,
+                                oO, sfN, sfS, sfO, workspace, workspace_bytes, stream);
 }
 
 int mm_rmsnorm_gate_up_activate_decode(const void *X_bf16, const void *norm_weight_bf16, float eps, const int16_t *reorder_index, const uint8_t *BN,
                                        const uint8_t *BS, const uint8_t *BO, const uint8_t *SFBN, const uint8_t *SFBS, const uint8_t *SFBO, int M,
                                        int I, int KN, int KS, int KO, int DN, int DS, int DO, int flags, uint8_t *oN, uint8_t *oS, uint8_t *oO,
                                        uint8_t *sfN, uint8_t *sfS, uint8_t *sfO, void *workspace, size_t workspace_bytes, mm_stream_t stream) {
-    if (M < 0 || I < 0 || KN < 0 || KS < 0 || KO < 0) return MM_ERR_BAD_ARG;
-    if ((KN % 128) || (KS % 128) || (KO % 128) || KN + KS + KO == 0) return MM_ERR_BAD_SPLIT;
-    if (!split_ok(DN + DS + DO, DN, DS, DO) || DN + DS + DO != I) return MM_ERR_BAD_SPLIT;
-    if (flags & ~(MM_ROUND_ONCE | MM_NORM_NO_INTEGER_ROUND)) return MM_ERR_BAD_ARG;
-    if (M == 0) return MM_OK;
-    const int Kin[3] = {KN, KS, KO};
-    if (!mm_rmsnorm_gate_up_activate_decode_supported(M, I, KN, KS, KO)) return MM_ERR_UNSUPPORTED;
-    if (!X_bf16 || !norm_weight_bf16 || !reorder_index || ((uintptr_t)X_bf16 & 15) || ((uintptr_t)norm_weight_bf16 & 15)) return MM_ERR_BAD_ARG;
-    if ((KN && (!BN || !SFBN)) || (KS && (!BS || !SFBS)) || (KO && (!BO || !SFBO))) return MM_ERR_BAD_ARG;
-    if ((DN && (!oN || !sfN)) || (DS && (!oS || !sfS)) || (DO && (!oO || !sfO))) return MM_ERR_BAD_ARG;
-    if (mm::gate_up_act_stream_supported(M, 2 * I, Kin, true, true)) {
-        const mm::GemmArgs a = act_stream_args(BN, BS, BO, SFBN, SFBS, SFBO, M, I, KN, KS, KO, DN, DS, DO, flags, oN, oS, oO, sfN, sfS, sfO);
-        const mm::NormArgs norm = {norm_weight_bf16, eps, (flags & MM_NORM_NO_INTEGER_ROUND) ? 0 : 1};
-        hipError_t e = mm::launch_gate_up_act_stream_decode(X_bf16, reorder_index, a, (hipStream_t)stream, norm);
-        return e == hipSuccess ? MM_OK : fail_hip(e, "mm_rmsnorm_gate_up_activate_decode");
-    }
-    // two launches: norm + quantize + gate | up GEMM into the scratch, then the activation quantizer on it (the same bytes)
-    const int N = 2 * I;
-    if (!workspace || workspace_bytes < (size_t)M * N * sizeof(uint16_t) || ((uintptr_t)workspace & 15)) return MM_ERR_BAD_ARG;
-    const int st = mm_rmsnorm_qlinear_decode(X_bf16, norm_weight_bf16, eps, reorder_index, BN, BS, BO, SFBN, SFBS, SFBO, M, N, KN, KS, KO, MM_W_FP4,
-                                             flags, nullptr, workspace, stream);
-    if (st != MM_OK) return st;
-    hipError_t e = mm::launch_direct_quantize(workspace, (const uint16_t *)workspace + 128, M, DN, DS, DO, 3, oN, oS, oO, sfN, sfS, sfO,
-                                              (hipStream_t)stream);
-    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_rmsnorm_gate_up_activate_decode");
+    return gate_up_decode_entry(NORM, X_bf16, norm_args(norm_weight_bf16, eps, flags), reorder_index, {BN, BS, BO}, {SFBN, SFBS, SFBO}, M, I, KN, KS, KO,
+                                DN, DS, DO, flags, oN, oS, oO, sfN, sfS, sfO, workspace, workspace_bytes, stream);
 }
 
 int mm_add_rmsnorm_gate_up_activate_decode(const void *X_bf16, const void *R_bf16, void *S_out_bf16, const void *norm_weight_bf16, float eps,
@@ -478,38 +474,14 @@ int mm_add_rmsnorm_gate_up_activate_decode(const void *X_bf16, const void *R_bf1
                                            const uint8_t *SFBN, const uint8_t *SFBS, const uint8_t *SFBO, int M, int I, int KN, int KS, int KO,
                                            int DN, int DS, int DO, int flags, uint8_t *oN, uint8_t *oS, uint8_t *oO, uint8_t *sfN, uint8_t *sfS,
                                            uint8_t *sfO, void *workspace, size_t workspace_bytes, mm_stream_t stream) {
-    if (M < 0 || I < 0 || KN < 0 || KS < 0 || KO < 0) return MM_ERR_BAD_ARG;
-    if ((KN % 128) || (KS % 128) || (KO % 128) || KN + KS + KO == 0) return MM_ERR_BAD_SPLIT;
-    if (!split_ok(DN + DS + DO, DN, DS, DO) || DN + DS + DO != I) return MM_ERR_BAD_SPLIT;
-    if (flags & ~(MM_ROUND_ONCE | MM_NORM_NO_INTEGER_ROUND)) return MM_ERR_BAD_ARG;
-    if (M == 0) return MM_OK;
-    const int Kin[3] = {KN, KS, KO};
-    if (!mm_rmsnorm_gate_up_activate_decode_supported(M, I, KN, KS, KO)) return MM_ERR_UNSUPPORTED;
-    if (!X_bf16 || !norm_weight_bf16 || !reorder_index || ((uintptr_t)X_bf16 & 15) || ((uintptr_t)norm_weight_bf16 & 15)) return MM_ERR_BAD_ARG;
-    if (!residual_ok(X_bf16, R_bf16, S_out_bf16, M, KN + KS + KO)) return MM_ERR_BAD_ARG;
-    if ((KN && (!BN || !SFBN)) || (KS && (!BS || !SFBS)) || (KO && (!BO || !SFBO))) return MM_ERR_BAD_ARG;
-    if ((DN && (!oN || !sfN)) || (DS && (!oS || !sfS)) || (DO && (!oO || !sfO))) return MM_ERR_BAD_ARG;
-    if (mm::gate_up_act_stream_supported(M, 2 * I, Kin, true, true)) {
-        const mm::GemmArgs a = act_stream_args(BN, BS, BO, SFBN, SFBS, SFBO, M, I, KN, KS, KO, DN, DS, DO, flags, oN, oS, oO, sfN, sfS, sfO);
-        const mm::NormArgs norm = {norm_weight_bf16, eps, (flags & MM_NORM_NO_INTEGER_ROUND) ? 0 : 1, R_bf16, S_out_bf16};
-        hipError_t e = mm::launch_gate_up_act_stream_decode(X_bf16, reorder_index, a, (hipStream_t)stream, norm);
-        return e == hipSuccess ? MM_OK : fail_hip(e, "mm_add_rmsnorm_gate_up_activate_decode");
-    }
-    // two launches: add + norm + quantize + gate | up GEMM into the scratch, then the activation quantizer on it (the same bytes)
-    const int N = 2 * I;
-    if (!workspace || workspace_bytes < (size_t)M * N * sizeof(uint16_t) || ((uintptr_t)workspace & 15)) return MM_ERR_BAD_ARG;
-    const int st = mm_add_rmsnorm_qlinear_decode(X_bf16, R_bf16, S_out_bf16, norm_weight_bf16, eps, reorder_index, BN, BS, BO, SFBN, SFBS, SFBO, M, N,
-                                                 KN, KS, KO, MM_W_FP4, flags, nullptr, workspace, stream);
-    if (st != MM_OK) return st;
-    hipError_t e = mm::launch_direct_quantize(workspace, (const uint16_t *)workspace + 128, M, DN, DS, DO, 3, oN, oS, oO, sfN, sfS, sfO,
-                                              (hipStream_t)stream);
-    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_add_rmsnorm_gate_up_activate_decode");
+    return gate_up_decode_entry(ADD_NORM, X_bf16, norm_args(norm_weight_bf16, eps, flags, R_bf16, S_out_bf16), reorder_index, {BN, BS, BO},
+                                {SFBN, SFBS, SFBO}, M, I, KN, KS, KO, DN, DS, DO, flags, oN, oS, oO, sfN, sfS, sfO, workspace, workspace_bytes, stream);
 }
 
 int mm_down_activate_decode_supported_w(int M, int N, int DN, int DS, int DO, int wmode) {
-    if (M < 1 || N < 1 || DN < 0 || DS < 0 || DO < 0 || (DN % 128) || (DS % 128) || (DO % 128) || DN + DS + DO == 0) return 0;
-    if (wmode != MM_W_MATCH && wmode != MM_W_FP4) return 0;
     const int K[3] = {DN, DS, DO};
+    if (M < 1 || N < 1 || !decode_split_ok(K)) return 0;
+    if (wmode != MM_W_MATCH && wmode != MM_W_FP4) return 0;
     if (!mm::down_activate_stream_supported(M, N, K, weights_fp4(wmode, DS, DO))) return 0;
     return M <= 2 ? 2 : 1;      // every workgroup repeats silu * up + the quantization: one pass of its threads up to M = 2 at I = 14336
 }
@@ -518,16 +490,16 @@ int mm_down_activate_decode_supported(int M, int N, int DN, int DS, int DO) { re
 int mm_down_activate_decode(const void *GU_bf16, const uint8_t *BN, const uint8_t *BS, const uint8_t *BO, const uint8_t *SFBN, const uint8_t *SFBS,
                             const uint8_t *SFBO, int M, int N, int DN, int DS, int DO, int wmode, int flags, const void *bias_bf16, void *D_bf16,
                             mm_stream_t stream) {
+    const int K[3] = {DN, DS, DO};
     if (M < 0 || N < 0 || DN < 0 || DS < 0 || DO < 0) return MM_ERR_BAD_ARG;
-    if ((DN % 128) || (DS % 128) || (DO % 128) || DN + DS + DO == 0) return MM_ERR_BAD_SPLIT;
+    if (!decode_split_ok(K)) return MM_ERR_BAD_SPLIT;
     if (wmode != MM_W_MATCH && wmode != MM_W_FP4) return MM_ERR_BAD_ARG;
     if (flags & ~MM_ROUND_ONCE) return MM_ERR_BAD_ARG;
     if (M == 0 || N == 0) return MM_OK;
     if (!mm_down_activate_decode_supported_w(M, N, DN, DS, DO, wmode)) return MM_ERR_UNSUPPORTED;
     if (!GU_bf16 || !D_bf16 || ((uintptr_t)GU_bf16 & 15)) return MM_ERR_BAD_ARG;
-    if ((DN && (!BN || !SFBN)) || (DS && (!BS || !SFBS)) || (DO && (!BO || !SFBO))) return MM_ERR_BAD_ARG;
     const uint8_t *W[3] = {BN, BS, BO}, *SFW[3] = {SFBN, SFBS, SFBO};
-    const int K[3] = {DN, DS, DO};
+    if (!segments_ok(K, {BN, BS, BO}, {SFBN, SFBS, SFBO})) return MM_ERR_BAD_ARG;
     hipError_t e = mm::launch_down_activate_stream(GU_bf16, W, SFW, M, N, K, weights_fp4(wmode, DS, DO), (flags & MM_ROUND_ONCE) ? 0 : 1, bias_bf16, D_bf16,
                                                    (hipStream_t)stream);
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_down_activate_decode");
@@ -546,12 +518,12 @@ int mm_reorder_quantize_grouped(const mm_quant_group *groups, int ngroups, int K
     if (!split_ok(K, KN, KS, KO)) return MM_ERR_BAD_SPLIT;
     if (mode != MM_QUANT_MIXED && mode != MM_QUANT_W4) return MM_ERR_BAD_ARG;
     if (K > 32768) return MM_ERR_BAD_ARG;
+    const int Kseg[3] = {KN, KS, KO};
     for (int i = 0; i < ngroups; ++i) {
         const mm_quant_group &g = groups[i];
         if (g.rows < 0) return MM_ERR_BAD_ARG;
         if (g.rows == 0) continue;
-        if (!g.src_bf16 || !g.reorder_index || (KN && (!g.oN || !g.sfN)) || (KS && (!g.oS || !g.sfS)) || (KO && (!g.oO || !g.sfO)))
-            return MM_ERR_BAD_ARG;
+        if (!g.src_bf16 || !g.reorder_index || !segments_ok(Kseg, {g.oN, g.oS, g.oO}, {g.sfN, g.sfS, g.sfO})) return MM_ERR_BAD_ARG;
     }
     mm::GroupedQuantArgs ga;
     ga.K = K; ga.KN = KN; ga.KS = KS; ga.KO = KO;
@@ -588,12 +560,12 @@ int mm_matmul_grouped(const mm_group *groups, int ngroups, int N, int KN, int KS
     if (wmode != MM_W_MATCH && wmode != MM_W_FP4) return MM_ERR_BAD_ARG;
     if (flags & MM_OUT_F32) return MM_ERR_UNSUPPORTED;    // fp32 partial sums come from mm_matmul only
     if (ngroups == 0 || N == 0) return MM_OK;
+    const int Ks[3] = {KN, KS, KO};
     for (int i = 0; i < ngroups; ++i) {
         const mm_group &g = groups[i];
         if (g.M < 0) return MM_ERR_BAD_ARG;
         if (g.M == 0) continue;
-        if (!g.D || (KN && (!g.AN || !g.BN || !g.SFAN || !g.SFBN)) || (KS && (!g.AS || !g.BS || !g.SFAS || !g.SFBS)) ||
-            (KO && (!g.AO || !g.BO || !g.SFAO || !g.SFBO)))
+        if (!g.D || !segments_ok(Ks, {g.AN, g.AS, g.AO}, {g.SFAN, g.SFAS, g.SFAO}) || !segments_ok(Ks, {g.BN, g.BS, g.BO}, {g.SFBN, g.SFBS, g.SFBO}))
             return MM_ERR_BAD_ARG;
     }
     // groups of at most 64 token rows share launches of the weight-streaming kernels, larger groups launches of the tiled
@@ -633,7 +605,6 @@ int mm_matmul_grouped(const mm_group *groups, int ngroups, int N, int KN, int KS
     auto flush_small = [&]() -> int {
         if (nsmall == 0) return MM_OK;
         small.ngroups = nsmall;
-        const int Ks[3] = {KN, KS, KO};
         hipError_t e = mm::mx_gemm_stream_grouped_supported(max_m, nsmall, N, Ks)
                            ? mm::launch_mx_gemm_stream_grouped(small, max_m, weights_fp4(wmode, KS, KO), (hipStream_t)stream)
                            : mm::launch_mx_gemm_skinny_grouped(small, max_m, weights_fp4(wmode, KS, KO), (hipStream_t)stream);
@@ -838,7 +809,8 @@ int mm_moe_quantize(const void *src_bf16, const int32_t *row_of_slot, const int3
     if (K > 32768 || (mode != MM_QUANT_MIXED && mode != MM_QUANT_W4)) return MM_ERR_BAD_ARG;
     if (num_rows == 0 || src_rows == 0) return MM_OK;
     if (!src_bf16 || !expert_offsets || !expert_table || ((uintptr_t)src_bf16 & 15) || ((uintptr_t)expert_table & 7)) return MM_ERR_BAD_ARG;
-    if ((KN && (!oN || !sfN)) || (KS && (!oS || !sfS)) || (KO && (!oO || !sfO))) return MM_ERR_BAD_ARG;
+    const int Kseg[3] = {KN, KS, KO};
+    if (!segments_ok(Kseg, {oN, oS, oO}, {sfN, sfS, sfO})) return MM_ERR_BAD_ARG;
     // rows are stored in 16-byte pieces, scales as dwords
     if ((((uintptr_t)oN | (uintptr_t)oS | (uintptr_t)oO) & 15) || (((uintptr_t)sfN | (uintptr_t)sfS | (uintptr_t)sfO) & 3)) return MM_ERR_BAD_ARG;
     hipError_t e = mm::launch_moe_quantize(src_bf16, row_of_slot, mg, src_rows, K, KN, KS, KO, mode == MM_QUANT_W4, oN, oS, oO, sfN, sfS, sfO,
@@ -857,7 +829,8 @@ int mm_moe_activate_quantize(const void *a_bf16, const void *b_bf16, const int32
     if (num_rows == 0) return MM_OK;
     if (!a_bf16 || !b_bf16 || !expert_offsets || !expert_table || ((uintptr_t)expert_table & 7)) return MM_ERR_BAD_ARG;
     if (((uintptr_t)a_bf16 | (uintptr_t)b_bf16 | (uintptr_t)h_out_bf16) & 15) return MM_ERR_BAD_ARG;
-    if ((KN && (!oN || !sfN)) || (KS && (!oS || !sfS)) || (KO && (!oO || !sfO))) return MM_ERR_BAD_ARG;
+    const int Kseg[3] = {KN, KS, KO};
+    if (!segments_ok(Kseg, {oN, oS, oO}, {sfN, sfS, sfO})) return MM_ERR_BAD_ARG;
     if ((((uintptr_t)oN | (uintptr_t)oS | (uintptr_t)oO) & 15) || (((uintptr_t)sfN | (uintptr_t)sfS | (uintptr_t)sfO) & 3)) return MM_ERR_BAD_ARG;
     hipError_t e = mm::launch_moe_activate_quantize(a_bf16, b_bf16, h_out_bf16, mg, K, KN, KS, KO, oN, oS, oO, sfN, sfS, sfO, (hipStream_t)stream);
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_moe_activate_quantize");
@@ -882,7 +855,8 @@ int mm_moe_matmul(const uint8_t *AN, const uint8_t *AS, const uint8_t *AO, const
     if (flags & MM_OUT_F32) return MM_ERR_UNSUPPORTED;    // fp32 partial sums come from mm_matmul only
     if (num_rows == 0 || N == 0 || max_rows == 0) return MM_OK;
     if (!expert_offsets || !expert_table || ((uintptr_t)expert_table & 7) || !D_bf16 || ((uintptr_t)D_bf16 & 1)) return MM_ERR_BAD_ARG;
-    if ((KN && (!AN || !SFAN)) || (KS && (!AS || !SFAS)) || (KO && (!AO || !SFAO))) return MM_ERR_BAD_ARG;
+    const int K[3] = {KN, KS, KO};
+    if (!segments_ok(K, {AN, AS, AO}, {SFAN, SFAS, SFAO})) return MM_ERR_BAD_ARG;
     if (KN + KS + KO == 0) {   // no segment: every owned row is zero (gemm.cu:48-50); a kernel, see ws_reset_kernel
         hipError_t e = mm::launch_moe_zero_rows(D_bf16, expert_offsets, num_experts, num_rows, N, (hipStream_t)stream);
         return e == hipSuccess ? MM_OK : fail_hip(e, "mm_moe_matmul(zero)");

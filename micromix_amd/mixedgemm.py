@@ -7,6 +7,9 @@ Same function names, argument order, keyword names, return tuples, dtypes and sh
     reorder_quantize_x(X, reorder_index, KN, KS, KO)  -> (XN, XS, XO, SFXN, SFXS, SFXO)
     reorder_quantize_w(W, reorder_index, KN, KS, KO)  -> (WN, WS, WO, SFWN, SFWS, SFWO)
     reorder_quantize_w4(W, reorder_index, KN, KS, KO) -> (WN, WS, WO, SFWN, SFWS, SFWO)
+    activate_quantize_x(A, B, KN, KS, KO)             -> (XN, XS, XO, SFXN, SFXS, SFXO)   (section 8f rank 1)
+    downproj_quantize_w / _w4 (W, KN, KS, KO)         -> (WN, WS, WO, SFWN, SFWS, SFWO)
+    rmsnorm_quantize_x(X, W, eps, reorder_index, KN, KS, KO) -> (XN, XS, XO, SFXN, SFXS, SFXO)    (section 8f rank 2)
 
 Differences from the reference, all deliberate:
   * kernels are queued on torch's CURRENT stream of the tensors' device (the reference uses
@@ -15,9 +18,6 @@ Differences from the reference, all deliberate:
     (bindings.cpp:134-148); bad splits still raise RuntimeError("Value error in run_...");
   * inputs are validated (dtype/device/contiguity) instead of being reinterpreted blindly;
   * `matmul` takes optional keyword-only `bias` and `rounding` arguments (extensions).
-    activate_quantize_x(A, B, KN, KS, KO)             -> (XN, XS, XO, SFXN, SFXS, SFXO)   (section 8f rank 1)
-    downproj_quantize_w / _w4 (W, KN, KS, KO)         -> (WN, WS, WO, SFWN, SFWS, SFWO)
-    rmsnorm_quantize_x(X, W, eps, reorder_index, KN, KS, KO) -> (XN, XS, XO, SFXN, SFXS, SFXO)    (section 8f rank 2)
 The remaining exports of the reference module (FlashInfer KV ops) are outside the hot path; they raise
 NotImplementedError.  The paged KV cache itself is `kv_append` / `paged_decode` / `paged_prefill` below (GQA, bf16 q,
 quantizes K/V itself; micromix_amd/kvcache.py wraps them), on the reference's FlashInfer layout.
@@ -75,6 +75,37 @@ def _sf_bytes_w(n, k):   # bindings.cpp:170-172 (rows padded to 128)
     return (n + 127) // 128 * 128 * (k // 32)
 
 
+def _check_split(KN, KS, KO, K, what):
+    """the reference's "Value error in run_<what>" unless (KN, KS, KO) are non-negative multiples of 128 that add up to K (K None: to
+    anything but 0)"""
+    if KN < 0 or KS < 0 or KO < 0 or KN % 128 or KS % 128 or KO % 128 or (KN + KS + KO != K if K is not None else KN + KS + KO == 0):
+        _lib.check(_lib.MM_ERR_BAD_SPLIT, what)
+
+
+def _round_flags(rounding, integer_round=True):
+    if rounding not in ("reference", "fused"):
+        raise ValueError("rounding must be 'reference' or 'fused'")
+    return (_lib.MM_ROUND_PER_SEGMENT if rounding == "reference" else _lib.MM_ROUND_ONCE) | (0 if integer_round else _lib.MM_NORM_NO_INTEGER_ROUND)
+
+
+def _weight_mode(B, N, KN, KS, KO, split_name="(KN, KS, KO)"):
+    """the weight mode of packed weights B = (BN, BS, BO, ...) of N rows, read off their widths: matching precision or all fp4"""
+    same = B[1].size(1) == KS // 4 * 3 and B[2].size(1) == KO
+    w4 = B[1].size(1) == KS // 2 and B[2].size(1) == KO // 2
+    if B[0].size(1) != KN // 2 or not (same or w4) or B[1].size(0) != N or B[2].size(0) != N:
+        raise RuntimeError(f"packed weights do not match {split_name}")
+    return _lib.MM_W_MATCH if same else _lib.MM_W_FP4
+
+
+def _check_weight_scales(SF, N, KN, KS, KO, names=None):
+    """the scale tensors SF of N rows hold enough bytes; names: say which one does not"""
+    if SF[0].numel() < _sf_bytes_w(N, KN) or SF[1].numel() < _sf_bytes_w(N, KS) or SF[2].numel() < _sf_bytes_w(N, KO):
+        for n, t, k in zip(names or (), SF, (KN, KS, KO)):
+            if t.numel() < _sf_bytes_w(N, k):
+                raise RuntimeError(f"{n} holds {t.numel()} scale bytes, needs at least {_sf_bytes_w(N, k)}")
+        raise RuntimeError("weight scale tensors are too small")
+
+
 class _on_device:
     """`with torch.cuda.device(d)` only when d is not already current (saves ~2 us per call)."""
     __slots__ = ("idx", "prev")
@@ -105,19 +136,17 @@ def _quantize(src, reorder_index, KN, KS, KO, mode, what, gather_subset=False):
         raise RuntimeError("input must be 2-D [rows, K]")
     KN, KS, KO = int(KN), int(KS), int(KO)
     rows, K = src.shape
-    if reorder_index.numel() != KN + KS + KO:
+    if reorder_index.numel() != KN + KS + KO or (gather_subset and (K % 128 or KN + KS + KO > K)):
         _lib.check(_lib.MM_ERR_BAD_SPLIT, what)
-    if KN < 0 or KS < 0 or KO < 0 or KN % 128 or KS % 128 or KO % 128 or K % 128:
-        _lib.check(_lib.MM_ERR_BAD_SPLIT, what)
-    if (KN + KS + KO != K) if not gather_subset else (KN + KS + KO > K or KN + KS + KO == 0):
-        _lib.check(_lib.MM_ERR_BAD_SPLIT, what)
+    if KN < 0 or KS < 0 or KO < 0 or KN % 128 or KS % 128 or KO % 128 or (KN + KS + KO == 0 if gather_subset else KN + KS + KO != K):
+        _check_split(KN, KS, KO, None if gather_subset else K, what)
     dev = src.device
     w4 = mode == "w4"
+    sf_bytes = _sf_bytes_x if mode == "x" else _sf_bytes_w
     u8 = torch.uint8
     oN = torch.empty((rows, KN // 2), dtype=u8, device=dev)
     oS = torch.empty((rows, KS // 2 if w4 else KS // 4 * 3), dtype=u8, device=dev)
     oO = torch.empty((rows, KO // 2 if w4 else KO), dtype=u8, device=dev)
-    sf_bytes = _sf_bytes_x if mode == "x" else _sf_bytes_w
     sfN = torch.empty((sf_bytes(rows, KN),), dtype=u8, device=dev)
     sfS = torch.empty((sf_bytes(rows, KS),), dtype=u8, device=dev)
     sfO = torch.empty((sf_bytes(rows, KO),), dtype=u8, device=dev)
@@ -226,11 +255,8 @@ def matmul(AN, BN, AS, BS, AO, BO, SFAN, SFBN, SFAS, SFBS, SFAO, SFBO, *, bias=N
         raise RuntimeError("AS and AO must be [M, bytes]")
     if (SFAN.numel() < _sf_bytes_w(M, KN) or SFAS.numel() < _sf_bytes_w(M, KS) or SFAO.numel() < _sf_bytes_w(M, KO)
             or SFBN.numel() < _sf_bytes_w(N, KN) or SFBS.numel() < _sf_bytes_w(N, KS) or SFBO.numel() < _sf_bytes_w(N, KO)):
-        for n, t, need in (("SFAN", SFAN, _sf_bytes_w(M, KN)), ("SFAS", SFAS, _sf_bytes_w(M, KS)),
-                           ("SFAO", SFAO, _sf_bytes_w(M, KO)), ("SFBN", SFBN, _sf_bytes_w(N, KN)),
-                           ("SFBS", SFBS, _sf_bytes_w(N, KS)), ("SFBO", SFBO, _sf_bytes_w(N, KO))):
-            if t.numel() < need:
-                raise RuntimeError(f"{n} holds {t.numel()} scale bytes, needs at least {need}")
+        _check_weight_scales((SFAN, SFAS, SFAO), M, KN, KS, KO, ("SFAN", "SFAS", "SFAO"))
+        _check_weight_scales((SFBN, SFBS, SFBO), N, KN, KS, KO, ("SFBN", "SFBS", "SFBO"))
     if rounding == "reference":
         flags = _lib.MM_ROUND_PER_SEGMENT
     elif rounding == "fused":
@@ -345,16 +371,16 @@ def gate_up_activate(A, B, DN, DS, DO, *, rounding="reference"):
     if A[1].size(0) != M or A[2].size(0) != M:
         raise RuntimeError("AS and AO must be [M, bytes]")
     if DN < 0 or DS < 0 or DO < 0 or DN % 128 or DS % 128 or DO % 128 or DN + DS + DO != I:
-        _lib.check(_lib.MM_ERR_BAD_SPLIT, "activate_quantize_x")
-    for n, t, need in (("SFAN", A[3], _sf_bytes_w(M, KN)), ("SFAS", A[4], _sf_bytes_w(M, KS)), ("SFAO", A[5], _sf_bytes_w(M, KO)),
-                       ("SFBN", B[3], _sf_bytes_w(N2, KN)), ("SFBS", B[4], _sf_bytes_w(N2, KS)), ("SFBO", B[5], _sf_bytes_w(N2, KO))):
-        if t.numel() < need:
-            raise RuntimeError(f"{n} holds {t.numel()} scale bytes, needs at least {need}")
+        _check_split(DN, DS, DO, I, "activate_quantize_x")
+    if A[3].numel() < _sf_bytes_w(M, KN) or A[4].numel() < _sf_bytes_w(M, KS) or A[5].numel() < _sf_bytes_w(M, KO):
+        _check_weight_scales(A[3:], M, KN, KS, KO, ("SFAN", "SFAS", "SFAO"))
+    if B[3].numel() < _sf_bytes_w(N2, KN) or B[4].numel() < _sf_bytes_w(N2, KS) or B[5].numel() < _sf_bytes_w(N2, KO):
+        _check_weight_scales(B[3:], N2, KN, KS, KO, ("SFBN", "SFBS", "SFBO"))
     for t in (*A, *B):
         if t.data_ptr() & 15 and t.numel():
             raise RuntimeError("operands must be 16-byte aligned")
     if rounding not in ("reference", "fused"):
-        raise ValueError("rounding must be 'reference' or 'fused'")
+        _round_flags(rounding)
     flags = _lib.MM_ROUND_PER_SEGMENT if rounding == "reference" else _lib.MM_ROUND_ONCE
     oN = torch.empty((M, DN // 2), dtype=u8, device=dev)
     oS = torch.empty((M, DS // 4 * 3), dtype=u8, device=dev)
@@ -388,7 +414,7 @@ def reorder_quantize_x_grouped(Xs, reorder_indices, KN, KS, KO):
     index = dev.index
     K = Xs[0].size(1)
     if KN < 0 or KS < 0 or KO < 0 or KN % 128 or KS % 128 or KO % 128 or KN + KS + KO != K:
-        _lib.check(_lib.MM_ERR_BAD_SPLIT, "reorder_quantize_x")
+        _check_split(KN, KS, KO, K, "reorder_quantize_x")
     arr = (_lib.MMQuantGroup * len(Xs))()
     res = []
     u8 = torch.uint8
@@ -433,9 +459,9 @@ def matmul_grouped(As, Bs, *, biases=None, rounding="reference", outs=None):
     same = As[0][1].size(1) == BS0.size(1) and As[0][2].size(1) == BO0.size(1)
     wmode = _lib.MM_W_MATCH if same else _lib.MM_W_FP4
     wb = (KN // 2, KS // 4 * 3 if same else KS // 2, KO if same else KO // 2)
-    flags = _lib.MM_ROUND_PER_SEGMENT if rounding == "reference" else _lib.MM_ROUND_ONCE
     if rounding not in ("reference", "fused"):
-        raise ValueError("rounding must be 'reference' or 'fused'")
+        _round_flags(rounding)
+    flags = _lib.MM_ROUND_PER_SEGMENT if rounding == "reference" else _lib.MM_ROUND_ONCE
     arr = (_lib.MMGroup * len(As))()
     given, outs = outs, []
     for g, (A, B) in enumerate(zip(As, Bs)):
@@ -492,45 +518,7 @@ def gate_up_activate_decode(X, reorder_index, B, DN, DS, DO, *, rounding="refere
     instead of three: reorder + quantize + the gate | up GEMM as one launch (`qlinear_decode` on the interleaved weight B), then
     silu(gate) * up + the quantization for down_proj.  X [M, K] bf16 with M <= 8 and `qlinear_decode_supported(M, 2 I, KN, KS, KO)`;
     (KN, KS, KO) are read off B.  Same bytes as the three-launch form.  Not an export of the reference module."""
-    lib = _lib.load()
-    dev = X.device
-    index = dev.index
-    if not (X.is_cuda and _ok(X, torch.bfloat16, index) and _ok(reorder_index, torch.int16, index)):
-        _check_tensor(X, "X", torch.bfloat16)
-        _check_tensor(reorder_index, "reorder_index", torch.int16, dev)
-    for t in B:
-        if not _ok(t, torch.uint8, index):
-            _check_tensor(t, "operand", torch.uint8, dev)
-    M, K = X.shape
-    N2 = B[0].size(0)
-    KN, KS, KO = B[0].size(1) * 2, B[1].size(1) * 2, B[2].size(1) * 2
-    I = N2 // 2
-    DN, DS, DO = int(DN), int(DS), int(DO)
-    if N2 % 256 or K != KN + KS + KO or reorder_index.numel() != K or B[1].size(0) != N2 or B[2].size(0) != N2:
-        raise RuntimeError("B must be an interleaved fp4 gate/up weight (interleave_gate_up) whose split adds up to X's columns")
-    if DN < 0 or DS < 0 or DO < 0 or DN % 128 or DS % 128 or DO % 128 or DN + DS + DO != I:
-        _lib.check(_lib.MM_ERR_BAD_SPLIT, "activate_quantize_x")
-    for n, t, need in (("SFBN", B[3], _sf_bytes_w(N2, KN)), ("SFBS", B[4], _sf_bytes_w(N2, KS)), ("SFBO", B[5], _sf_bytes_w(N2, KO))):
-        if t.numel() < need:
-            raise RuntimeError(f"{n} holds {t.numel()} scale bytes, needs at least {need}")
-    if rounding not in ("reference", "fused"):
-        raise ValueError("rounding must be 'reference' or 'fused'")
-    flags = _lib.MM_ROUND_PER_SEGMENT if rounding == "reference" else _lib.MM_ROUND_ONCE
-    u8 = torch.uint8
-    oN = torch.empty((M, DN // 2), dtype=u8, device=dev)
-    oS = torch.empty((M, DS // 4 * 3), dtype=u8, device=dev)
-    oO = torch.empty((M, DO), dtype=u8, device=dev)
-    sfN = torch.empty((_sf_bytes_x(M, DN),), dtype=u8, device=dev)
-    sfS = torch.empty((_sf_bytes_x(M, DS),), dtype=u8, device=dev)
-    sfO = torch.empty((_sf_bytes_x(M, DO),), dtype=u8, device=dev)
-    ws = torch.empty((M * N2 * 2,), dtype=u8, device=dev)      # stream-ordered scratch from the caching allocator
-    with _on_device(index):
-        st = lib.mm_gate_up_activate_decode(_ptr(X), _ptr(reorder_index), _ptr(B[0]), _ptr(B[1]), _ptr(B[2]), _ptr(B[3]), _ptr(B[4]), _ptr(B[5]),
-                                            M, I, KN, KS, KO, DN, DS, DO, flags, _ptr(oN), _ptr(oS), _ptr(oO), _ptr(sfN), _ptr(sfS), _ptr(sfO),
-                                            _ptr(ws), ws.numel(), _stream_ptr(dev))
-    if st:
-        _lib.check(st, "gate_up_activate_decode")
-    return oN, oS, oO, sfN, sfS, sfO
+    return _gate_up_activate_decode(False, X, None, 0.0, reorder_index, B, DN, DS, DO, rounding, True)[1:]
 
 
 def rmsnorm_gate_up_activate_decode_supported(M, I, KN, KS, KO):
@@ -561,7 +549,8 @@ def add_rmsnorm_gate_up_activate_decode(X, residual, norm_weight, eps, reorder_i
                                         out_sum=None):
     """`rmsnorm_gate_up_activate_decode` on s = X + residual (torch's bf16 add), the add inside the launch: returns (s, down_proj's six
     operands).  Bit-identical to `add_rmsnorm_quantize_x` -> `gate_up_activate`; supported where the plain form is."""
-    return _rmsnorm_gate_up_activate_decode(X, norm_weight, eps, reorder_index, B, DN, DS, DO, rounding, integer_round, residual, out_sum)
+    res = _gate_up_activate_decode(True, X, norm_weight, eps, reorder_index, B, DN, DS, DO, rounding, integer_round, residual, out_sum)
+    return res if residual is not None else res[1:]      # (no residual: the plain norm form and its six operands, as ever)
 
 
 def rmsnorm_gate_up_activate_decode(X, norm_weight, eps, reorder_index, B, DN, DS, DO, *, rounding="reference", integer_round=True):
@@ -571,16 +560,19 @@ def rmsnorm_gate_up_activate_decode(X, norm_weight, eps, reorder_index, B, DN, D
     fastest form).  Returns
     down_proj's activation operands (oN, oS, oO, sfN, sfS, sfO): `matmul` them with the packed down_proj weight.  Same bytes as the
     three-op form.  Not an export of the reference module."""
-    return _rmsnorm_gate_up_activate_decode(X, norm_weight, eps, reorder_index, B, DN, DS, DO, rounding, integer_round, None, None)
+    return _gate_up_activate_decode(True, X, norm_weight, eps, reorder_index, B, DN, DS, DO, rounding, integer_round)[1:]
 
 
-def _rmsnorm_gate_up_activate_decode(X, norm_weight, eps, reorder_index, B, DN, DS, DO, rounding, integer_round, residual, out_sum):
+def _gate_up_activate_decode(norm, X, norm_weight, eps, reorder_index, B, DN, DS, DO, rounding, integer_round, residual=None, out_sum=None):
+    """shared body of gate_up_activate_decode (norm False), rmsnorm_gate_up_activate_decode and add_rmsnorm_gate_up_activate_decode
+    (residual given): (out_sum or None, oN, oS, oO, sfN, sfS, sfO).  `norm` says which form runs, never norm_weight: None there is an error"""
     lib = _lib.load()
     dev = X.device
     index = dev.index
-    if not (X.is_cuda and _ok(X, torch.bfloat16, index) and _ok(reorder_index, torch.int16, index) and _ok(norm_weight, torch.bfloat16, index)):
+    if not (X.is_cuda and _ok(X, torch.bfloat16, index) and _ok(reorder_index, torch.int16, index) and (not norm or _ok(norm_weight, torch.bfloat16, index))):
         _check_tensor(X, "X", torch.bfloat16)
-        _check_tensor(norm_weight, "norm_weight", torch.bfloat16, dev)
+        if norm:
+            _check_tensor(norm_weight, "norm_weight", torch.bfloat16, dev)
         _check_tensor(reorder_index, "reorder_index", torch.int16, dev)
     if residual is not None:
         out_sum = _residual_operands(X, residual, out_sum, index)
@@ -592,16 +584,17 @@ def _rmsnorm_gate_up_activate_decode(X, norm_weight, eps, reorder_index, B, DN, 
     KN, KS, KO = B[0].size(1) * 2, B[1].size(1) * 2, B[2].size(1) * 2
     I = N2 // 2
     DN, DS, DO = int(DN), int(DS), int(DO)
-    if N2 % 256 or K != KN + KS + KO or reorder_index.numel() != K or norm_weight.numel() != K or B[1].size(0) != N2 or B[2].size(0) != N2:
+    if N2 % 256 or K != KN + KS + KO or reorder_index.numel() != K or (norm and norm_weight.numel() != K) or B[1].size(0) != N2 or B[2].size(0) != N2:
         raise RuntimeError("B must be an interleaved fp4 gate/up weight (interleave_gate_up) whose split adds up to X's columns")
     if DN < 0 or DS < 0 or DO < 0 or DN % 128 or DS % 128 or DO % 128 or DN + DS + DO != I:
-        _lib.check(_lib.MM_ERR_BAD_SPLIT, "activate_quantize_x")
-    for n, t, need in (("SFBN", B[3], _sf_bytes_w(N2, KN)), ("SFBS", B[4], _sf_bytes_w(N2, KS)), ("SFBO", B[5], _sf_bytes_w(N2, KO))):
-        if t.numel() < need:
-            raise RuntimeError(f"{n} holds {t.numel()} scale bytes, needs at least {need}")
+        _check_split(DN, DS, DO, I, "activate_quantize_x")
+    if B[3].numel() < _sf_bytes_w(N2, KN) or B[4].numel() < _sf_bytes_w(N2, KS) or B[5].numel() < _sf_bytes_w(N2, KO):
+        _check_weight_scales(B[3:], N2, KN, KS, KO, ("SFBN", "SFBS", "SFBO"))
     if rounding not in ("reference", "fused"):
-        raise ValueError("rounding must be 'reference' or 'fused'")
-    flags = (_lib.MM_ROUND_PER_SEGMENT if rounding == "reference" else _lib.MM_ROUND_ONCE) | (0 if integer_round else _lib.MM_NORM_NO_INTEGER_ROUND)
+        _round_flags(rounding)
+    flags = _lib.MM_ROUND_PER_SEGMENT if rounding == "reference" else _lib.MM_ROUND_ONCE
+    if not integer_round:
+        flags |= _lib.MM_NORM_NO_INTEGER_ROUND
     u8 = torch.uint8
     oN = torch.empty((M, DN // 2), dtype=u8, device=dev)
     oS = torch.empty((M, DS // 4 * 3), dtype=u8, device=dev)
@@ -613,13 +606,16 @@ def _rmsnorm_gate_up_activate_decode(X, norm_weight, eps, reorder_index, B, DN, 
     tail = (_ptr(reorder_index), _ptr(B[0]), _ptr(B[1]), _ptr(B[2]), _ptr(B[3]), _ptr(B[4]), _ptr(B[5]), M, I, KN, KS, KO, DN, DS, DO, flags, _ptr(oN),
             _ptr(oS), _ptr(oO), _ptr(sfN), _ptr(sfS), _ptr(sfO), _ptr(ws), ws.numel(), _stream_ptr(dev))
     with _on_device(index):
-        if residual is None:
-            st = lib.mm_rmsnorm_gate_up_activate_decode(_ptr(X), _ptr(norm_weight), float(eps), *tail)
+        if not norm:
+            st, what = lib.mm_gate_up_activate_decode(_ptr(X), *tail), "gate_up_activate_decode"
+        elif residual is None:
+            st, what = lib.mm_rmsnorm_gate_up_activate_decode(_ptr(X), _ptr(norm_weight), float(eps), *tail), "rmsnorm_gate_up_activate_decode"
         else:
-            st = lib.mm_add_rmsnorm_gate_up_activate_decode(_ptr(X), _ptr(residual), _ptr(out_sum), _ptr(norm_weight), float(eps), *tail)
+            st, what = lib.mm_add_rmsnorm_gate_up_activate_decode(_ptr(X), _ptr(residual), _ptr(out_sum), _ptr(norm_weight), float(eps), *tail), \
+                "add_rmsnorm_gate_up_activate_decode"
     if st:
-        _lib.check(st, "rmsnorm_gate_up_activate_decode" if residual is None else "add_rmsnorm_gate_up_activate_decode")
-    return (oN, oS, oO, sfN, sfS, sfO) if residual is None else (out_sum, oN, oS, oO, sfN, sfS, sfO)
+        _lib.check(st, what)
+    return out_sum, oN, oS, oO, sfN, sfS, sfO
 
 
 def down_activate_decode_supported(M, N, DN, DS, DO, weight_mode="w4"):
@@ -647,14 +643,13 @@ def down_activate_decode(GU, B, DN, DS, DO, *, bias=None, rounding="reference"):
     if I2 != 2 * I or I % 128 or DN % 128 or DS % 128 or DO % 128:
         _lib.check(_lib.MM_ERR_BAD_SPLIT, "activate_quantize_x")
     same = B[1].size(1) == DS // 4 * 3 and B[2].size(1) == DO
-    w4 = B[1].size(1) == DS // 2 and B[2].size(1) == DO // 2
-    if B[0].size(1) != DN // 2 or not (same or w4) or B[1].size(0) != N or B[2].size(0) != N:
-        raise RuntimeError("packed weights do not match (DN, DS, DO)")
+    if B[0].size(1) != DN // 2 or not (same or (B[1].size(1) == DS // 2 and B[2].size(1) == DO // 2)) or B[1].size(0) != N or B[2].size(0) != N:
+        _weight_mode(B, N, DN, DS, DO, "(DN, DS, DO)")
     wmode = _lib.MM_W_MATCH if same else _lib.MM_W_FP4
     if B[3].numel() < _sf_bytes_w(N, DN) or B[4].numel() < _sf_bytes_w(N, DS) or B[5].numel() < _sf_bytes_w(N, DO):
-        raise RuntimeError("weight scale tensors are too small")
+        _check_weight_scales(B[3:], N, DN, DS, DO)
     if rounding not in ("reference", "fused"):
-        raise ValueError("rounding must be 'reference' or 'fused'")
+        _round_flags(rounding)
     flags = _lib.MM_ROUND_PER_SEGMENT if rounding == "reference" else _lib.MM_ROUND_ONCE
     if bias is not None and (not _ok(bias, torch.bfloat16, index) or bias.numel() != N):
         _check_tensor(bias, "bias", torch.bfloat16, dev)
@@ -674,42 +669,7 @@ def qlinear_decode(X, reorder_index, BN, BS, BO, SFBN, SFBS, SFBO, KN, KS, KO, *
     Not an export of the reference module: it is what the reference's forward computes, fused for decode, and bit-identical
     to the two-op path.  X [M, K] bf16; B / SFB are the layer's packed weights; returns [M, N] bf16.
     """
-    lib = _lib.load()
-    dev = X.device
-    index = dev.index
-    if not (X.is_cuda and _ok(X, torch.bfloat16, index) and _ok(reorder_index, torch.int16, index)):
-        _check_tensor(X, "X", torch.bfloat16)
-        _check_tensor(reorder_index, "reorder_index", torch.int16, dev)
-    for n, t in (("BN", BN), ("BS", BS), ("BO", BO), ("SFBN", SFBN), ("SFBS", SFBS), ("SFBO", SFBO)):
-        if not _ok(t, torch.uint8, index):
-            _check_tensor(t, n, torch.uint8, dev)
-    KN, KS, KO = int(KN), int(KS), int(KO)
-    M, K = X.shape
-    N = BN.size(0)
-    if K != KN + KS + KO or reorder_index.numel() != K:
-        _lib.check(_lib.MM_ERR_BAD_SPLIT, "reorder_quantize_x")
-    same = BS.size(1) == KS // 4 * 3 and BO.size(1) == KO
-    w4 = BS.size(1) == KS // 2 and BO.size(1) == KO // 2
-    if BN.size(1) != KN // 2 or not (same or w4) or BS.size(0) != N or BO.size(0) != N:
-        raise RuntimeError("packed weights do not match (KN, KS, KO)")
-    wmode = _lib.MM_W_MATCH if same else _lib.MM_W_FP4
-    if (SFBN.numel() < _sf_bytes_w(N, KN) or SFBS.numel() < _sf_bytes_w(N, KS) or SFBO.numel() < _sf_bytes_w(N, KO)):
-        raise RuntimeError("weight scale tensors are too small")
-    flags = _lib.MM_ROUND_PER_SEGMENT if rounding == "reference" else _lib.MM_ROUND_ONCE
-    if rounding not in ("reference", "fused"):
-        raise ValueError("rounding must be 'reference' or 'fused'")
-    if bias is not None and (not _ok(bias, torch.bfloat16, index) or bias.numel() != N):
-        _check_tensor(bias, "bias", torch.bfloat16, dev)
-        raise RuntimeError("bias must have N elements")
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.bfloat16, device=dev)
-    with _on_device(index):
-        st = lib.mm_qlinear_decode(_ptr(X), _ptr(reorder_index), _ptr(BN), _ptr(BS), _ptr(BO), _ptr(SFBN), _ptr(SFBS), _ptr(SFBO),
-                                   M, N, KN, KS, KO, wmode, flags, _ptr(bias) if bias is not None else None, _ptr(out),
-                                   _stream_ptr(dev))
-    if st:
-        _lib.check(st, "qlinear_decode")
-    return out
+    return _qlinear_decode(False, X, None, 0.0, reorder_index, BN, BS, BO, SFBN, SFBS, SFBO, KN, KS, KO, bias, rounding, True, out)[1]
 
 
 def rmsnorm_qlinear_decode_supported(M, N, KN, KS, KO, weight_mode="w4"):
@@ -721,8 +681,9 @@ def add_rmsnorm_qlinear_decode(X, residual, norm_weight, eps, reorder_index, BN,
                                rounding="reference", integer_round=True, out=None, out_sum=None):
     """`rmsnorm_qlinear_decode` on s = X + residual (torch's bf16 add), the add inside the launch: returns (s, D).  Bit-identical to
     `add_rmsnorm_quantize_x` followed by `matmul`; supported where the plain form is (`rmsnorm_qlinear_decode_supported`)."""
-    return _rmsnorm_qlinear_decode(X, norm_weight, eps, reorder_index, BN, BS, BO, SFBN, SFBS, SFBO, KN, KS, KO, bias, rounding, integer_round, out,
-                                   residual, out_sum)
+    res = _qlinear_decode(True, X, norm_weight, eps, reorder_index, BN, BS, BO, SFBN, SFBS, SFBO, KN, KS, KO, bias, rounding, integer_round, out, residual,
+                          out_sum)
+    return res if residual is not None else res[1]      # (no residual: the plain norm form and its one tensor, as ever)
 
 
 def rmsnorm_qlinear_decode(X, norm_weight, eps, reorder_index, BN, BS, BO, SFBN, SFBS, SFBO, KN, KS, KO, *, bias=None, rounding="reference",
@@ -730,20 +691,22 @@ def rmsnorm_qlinear_decode(X, norm_weight, eps, reorder_index, BN, BS, BO, SFBN,
     """rmsnorm_quantize_x + matmul (+ bias) as ONE launch for M <= 8 rows: what a decoder layer of the reference runs in front of
     q/k/v and gate/up (qLlamaLayer.py: input_layernorm / post_attention_layernorm fused into the quantizer, rmsnorm.cu:95-352, then
     qLinearLayer.py:58-74).  Bit-identical to `rmsnorm_quantize_x` followed by `matmul`.  X [M, K] bf16, norm_weight [K] bf16."""
-    return _rmsnorm_qlinear_decode(X, norm_weight, eps, reorder_index, BN, BS, BO, SFBN, SFBS, SFBO, KN, KS, KO, bias, rounding, integer_round, out,
-                                   None, None)
+    return _qlinear_decode(True, X, norm_weight, eps, reorder_index, BN, BS, BO, SFBN, SFBS, SFBO, KN, KS, KO, bias, rounding, integer_round, out)[1]
 
 
-def _rmsnorm_qlinear_decode(X, norm_weight, eps, reorder_index, BN, BS, BO, SFBN, SFBS, SFBO, KN, KS, KO, bias, rounding, integer_round, out,
-                            residual, out_sum):
+def _qlinear_decode(norm, X, norm_weight, eps, reorder_index, BN, BS, BO, SFBN, SFBS, SFBO, KN, KS, KO, bias, rounding, integer_round, out,
+                    residual=None, out_sum=None):
+    """shared body of qlinear_decode (norm False), rmsnorm_qlinear_decode and add_rmsnorm_qlinear_decode (residual given):
+    (out_sum or None, out).  `norm` says which form runs, never norm_weight: None there is an error"""
     lib = _lib.load()
     dev = X.device
     index = dev.index
     if residual is not None:
         out_sum = _residual_operands(X, residual, out_sum, index)
-    if not (X.is_cuda and _ok(X, torch.bfloat16, index) and _ok(reorder_index, torch.int16, index) and _ok(norm_weight, torch.bfloat16, index)):
+    if not (X.is_cuda and _ok(X, torch.bfloat16, index) and _ok(reorder_index, torch.int16, index) and (not norm or _ok(norm_weight, torch.bfloat16, index))):
         _check_tensor(X, "X", torch.bfloat16)
-        _check_tensor(norm_weight, "norm_weight", torch.bfloat16, dev)
+        if norm:
+            _check_tensor(norm_weight, "norm_weight", torch.bfloat16, dev)
         _check_tensor(reorder_index, "reorder_index", torch.int16, dev)
     for n, t in (("BN", BN), ("BS", BS), ("BO", BO), ("SFBN", SFBN), ("SFBS", SFBS), ("SFBO", SFBO)):
         if not _ok(t, torch.uint8, index):
@@ -751,17 +714,17 @@ def _rmsnorm_qlinear_decode(X, norm_weight, eps, reorder_index, BN, BS, BO, SFBN
     KN, KS, KO = int(KN), int(KS), int(KO)
     M, K = X.shape
     N = BN.size(0)
-    if K != KN + KS + KO or reorder_index.numel() != K or norm_weight.numel() != K:
-        _lib.check(_lib.MM_ERR_BAD_SPLIT, "rmsnorm_quantize_x")
+    if K != KN + KS + KO or reorder_index.numel() != K or (norm and norm_weight.numel() != K):
+        _lib.check(_lib.MM_ERR_BAD_SPLIT, "rmsnorm_quantize_x" if norm else "reorder_quantize_x")
+    # (hot-path rule, here as in every wrapper: the tests inline, the helpers -- which raise -- only once one of them failed)
     same = BS.size(1) == KS // 4 * 3 and BO.size(1) == KO
-    w4 = BS.size(1) == KS // 2 and BO.size(1) == KO // 2
-    if BN.size(1) != KN // 2 or not (same or w4) or BS.size(0) != N or BO.size(0) != N:
-        raise RuntimeError("packed weights do not match (KN, KS, KO)")
+    if BN.size(1) != KN // 2 or not (same or (BS.size(1) == KS // 2 and BO.size(1) == KO // 2)) or BS.size(0) != N or BO.size(0) != N:
+        _weight_mode((BN, BS, BO), N, KN, KS, KO)
     wmode = _lib.MM_W_MATCH if same else _lib.MM_W_FP4
-    if (SFBN.numel() < _sf_bytes_w(N, KN) or SFBS.numel() < _sf_bytes_w(N, KS) or SFBO.numel() < _sf_bytes_w(N, KO)):
-        raise RuntimeError("weight scale tensors are too small")
+    if SFBN.numel() < _sf_bytes_w(N, KN) or SFBS.numel() < _sf_bytes_w(N, KS) or SFBO.numel() < _sf_bytes_w(N, KO):
+        _check_weight_scales((SFBN, SFBS, SFBO), N, KN, KS, KO)
     if rounding not in ("reference", "fused"):
-        raise ValueError("rounding must be 'reference' or 'fused'")
+        _round_flags(rounding)
     flags = (_lib.MM_ROUND_PER_SEGMENT if rounding == "reference" else _lib.MM_ROUND_ONCE) | (0 if integer_round else _lib.MM_NORM_NO_INTEGER_ROUND)
     if bias is not None and (not _ok(bias, torch.bfloat16, index) or bias.numel() != N):
         _check_tensor(bias, "bias", torch.bfloat16, dev)
@@ -771,13 +734,16 @@ def _rmsnorm_qlinear_decode(X, norm_weight, eps, reorder_index, BN, BS, BO, SFBN
     tail = (_ptr(reorder_index), _ptr(BN), _ptr(BS), _ptr(BO), _ptr(SFBN), _ptr(SFBS), _ptr(SFBO), M, N, KN, KS, KO, wmode, flags,
             _ptr(bias) if bias is not None else None, _ptr(out), _stream_ptr(dev))
     with _on_device(index):
-        if residual is None:
-            st = lib.mm_rmsnorm_qlinear_decode(_ptr(X), _ptr(norm_weight), float(eps), *tail)
+        if not norm:
+            st, what = lib.mm_qlinear_decode(_ptr(X), *tail), "qlinear_decode"
+        elif residual is None:
+            st, what = lib.mm_rmsnorm_qlinear_decode(_ptr(X), _ptr(norm_weight), float(eps), *tail), "rmsnorm_qlinear_decode"
         else:
-            st = lib.mm_add_rmsnorm_qlinear_decode(_ptr(X), _ptr(residual), _ptr(out_sum), _ptr(norm_weight), float(eps), *tail)
+            st, what = lib.mm_add_rmsnorm_qlinear_decode(_ptr(X), _ptr(residual), _ptr(out_sum), _ptr(norm_weight), float(eps), *tail), \
+                "add_rmsnorm_qlinear_decode"
     if st:
-        _lib.check(st, "rmsnorm_qlinear_decode" if residual is None else "add_rmsnorm_qlinear_decode")
-    return out if residual is None else (out_sum, out)
+        _lib.check(st, what)
+    return out_sum, out
 
 
 def _direct(src_a, src_b, KN, KS, KO, mode, what):
@@ -792,14 +758,14 @@ def _direct(src_a, src_b, KN, KS, KO, mode, what):
         raise RuntimeError("inputs must be 2-D [rows, K] of equal shape")
     rows, K = src_a.shape
     if KN < 0 or KS < 0 or KO < 0 or KN % 128 or KS % 128 or KO % 128 or KN + KS + KO != K:
-        _lib.check(_lib.MM_ERR_BAD_SPLIT, what)
+        _check_split(KN, KS, KO, K, what)
     dev = src_a.device
-    u8 = torch.uint8
     w4 = mode == "w4"
+    u8 = torch.uint8
     oN = torch.empty((rows, KN // 2), dtype=u8, device=dev)
     oS = torch.empty((rows, KS // 2 if w4 else KS // 4 * 3), dtype=u8, device=dev)
     oO = torch.empty((rows, KO // 2 if w4 else KO), dtype=u8, device=dev)
-    sfN = torch.empty((_sf_bytes_x(rows, KN),), dtype=u8, device=dev)    # (rows/128+1)*128 rows for all three ops
+    sfN = torch.empty((_sf_bytes_x(rows, KN),), dtype=u8, device=dev)
     sfS = torch.empty((_sf_bytes_x(rows, KS),), dtype=u8, device=dev)
     sfO = torch.empty((_sf_bytes_x(rows, KO),), dtype=u8, device=dev)
     with _on_device(dev.index):
@@ -844,34 +810,7 @@ def rmsnorm_quantize_x(X, W, eps, reorder_index, KN, KS, KO, *, integer_round=Tr
     `integer_round=True` (default) reproduces the reference, which rounds the scaled value to an integer before the element
     conversion (rmsnorm.cu:262-267); `False` drops that step.
     """
-    lib = _lib.load()
-    if not (isinstance(X, torch.Tensor) and X.is_cuda and isinstance(W, torch.Tensor) and isinstance(reorder_index, torch.Tensor)
-            and _ok(X, torch.bfloat16, X.get_device()) and _ok(W, torch.bfloat16, X.get_device())
-            and _ok(reorder_index, torch.int16, X.get_device())):
-        _check_tensor(X, "X", torch.bfloat16)
-        _check_tensor(W, "W", torch.bfloat16, X.device)
-        _check_tensor(reorder_index, "reorder_index", torch.int16, X.device)
-    if X.dim() != 2:
-        raise RuntimeError("X must be 2-D [rows, K]")
-    KN, KS, KO = int(KN), int(KS), int(KO)
-    rows, K = X.shape
-    if (KN < 0 or KS < 0 or KO < 0 or KN % 128 or KS % 128 or KO % 128 or KN + KS + KO != K or reorder_index.numel() != K
-            or W.numel() != K):
-        _lib.check(_lib.MM_ERR_BAD_SPLIT, "rmsnorm_bf16_mixed")    # bindings.cpp:298 "Value error in run_rmsnorm_bf16_mixed"
-    dev, u8 = X.device, torch.uint8
-    oN = torch.empty((rows, KN // 2), dtype=u8, device=dev)
-    oS = torch.empty((rows, KS // 4 * 3), dtype=u8, device=dev)
-    oO = torch.empty((rows, KO), dtype=u8, device=dev)
-    sfN = torch.empty((_sf_bytes_x(rows, KN),), dtype=u8, device=dev)
-    sfS = torch.empty((_sf_bytes_x(rows, KS),), dtype=u8, device=dev)
-    sfO = torch.empty((_sf_bytes_x(rows, KO),), dtype=u8, device=dev)
-    with _on_device(dev.index):
-        st = lib.mm_rmsnorm_quantize(_ptr(X), _ptr(W), float(eps), rows, K, _ptr(reorder_index), KN, KS, KO,
-                                     _lib.MM_RMS_REFERENCE if integer_round else _lib.MM_RMS_NO_INTEGER_ROUND,
-                                     _ptr(oN), _ptr(oS), _ptr(oO), _ptr(sfN), _ptr(sfS), _ptr(sfO), _stream_ptr(dev))
-    if st:
-        _lib.check(st, "rmsnorm_bf16_mixed")
-    return oN, oS, oO, sfN, sfS, sfO
+    return _rmsnorm_quantize_x(False, X, W, eps, reorder_index, KN, KS, KO, integer_round)[1:]
 
 
 def add_rmsnorm_quantize_x(x, residual, weight, eps, reorder_index, KN, KS, KO, out_sum=None, *, integer_round=True):
@@ -882,39 +821,51 @@ def add_rmsnorm_quantize_x(x, residual, weight, eps, reorder_index, KN, KS, KO, 
     `rmsnorm_quantize_x(s, weight, eps, reorder_index, KN, KS, KO)`.  `out_sum`: a [M, K] bf16 tensor to receive s; it must not
     overlap x or residual (the library refuses an overlap).  Not an export of the reference module: its layers add in torch
     (model/qLlamaLayer.py:127-148)."""
+    return _rmsnorm_quantize_x(True, x, weight, eps, reorder_index, KN, KS, KO, integer_round, residual, out_sum)
+
+
+def _rmsnorm_quantize_x(add, X, W, eps, reorder_index, KN, KS, KO, integer_round, residual=None, out_sum=None):
+    """shared body of rmsnorm_quantize_x and add_rmsnorm_quantize_x (add True: a residual of None is an error; its errors call the operands x / weight):
+    (out_sum or None, oN, oS, oO, sfN, sfS, sfO)"""
     lib = _lib.load()
-    if not (isinstance(x, torch.Tensor) and x.is_cuda and isinstance(residual, torch.Tensor) and isinstance(weight, torch.Tensor)
-            and isinstance(reorder_index, torch.Tensor) and _ok(x, torch.bfloat16, x.get_device()) and _ok(residual, torch.bfloat16, x.get_device())
-            and _ok(weight, torch.bfloat16, x.get_device()) and _ok(reorder_index, torch.int16, x.get_device())):
-        _check_tensor(x, "x", torch.bfloat16)
-        _check_tensor(residual, "residual", torch.bfloat16, x.device)
-        _check_tensor(weight, "weight", torch.bfloat16, x.device)
-        _check_tensor(reorder_index, "reorder_index", torch.int16, x.device)
-    if x.dim() != 2 or tuple(residual.shape) != tuple(x.shape):
-        raise RuntimeError("x and residual must be 2-D [rows, K] of equal shape")
+    if not (isinstance(X, torch.Tensor) and X.is_cuda and (not add or isinstance(residual, torch.Tensor)) and isinstance(W, torch.Tensor)
+            and isinstance(reorder_index, torch.Tensor) and _ok(X, torch.bfloat16, X.get_device()) and (not add or _ok(residual, torch.bfloat16, X.get_device()))
+            and _ok(W, torch.bfloat16, X.get_device()) and _ok(reorder_index, torch.int16, X.get_device())):
+        _check_tensor(X, "x" if add else "X", torch.bfloat16)
+        if add:
+            _check_tensor(residual, "residual", torch.bfloat16, X.device)
+        _check_tensor(W, "weight" if add else "W", torch.bfloat16, X.device)
+        _check_tensor(reorder_index, "reorder_index", torch.int16, X.device)
+    if X.dim() != 2 or (add and tuple(residual.shape) != tuple(X.shape)):
+        raise RuntimeError("x and residual must be 2-D [rows, K] of equal shape" if add else "X must be 2-D [rows, K]")
     KN, KS, KO = int(KN), int(KS), int(KO)
-    rows, K = x.shape
-    if (KN < 0 or KS < 0 or KO < 0 or KN % 128 or KS % 128 or KO % 128 or KN + KS + KO != K or reorder_index.numel() != K
-            or weight.numel() != K):
-        _lib.check(_lib.MM_ERR_BAD_SPLIT, "rmsnorm_bf16_mixed")
-    dev, u8 = x.device, torch.uint8
-    if out_sum is None:
+    rows, K = X.shape
+    if reorder_index.numel() != K or W.numel() != K:
+        _lib.check(_lib.MM_ERR_BAD_SPLIT, "rmsnorm_bf16_mixed")    # bindings.cpp:298 "Value error in run_rmsnorm_bf16_mixed"
+    if KN < 0 or KS < 0 or KO < 0 or KN % 128 or KS % 128 or KO % 128 or KN + KS + KO != K:
+        _check_split(KN, KS, KO, K, "rmsnorm_bf16_mixed")
+    dev = X.device
+    if add and out_sum is None:
         out_sum = torch.empty((rows, K), dtype=torch.bfloat16, device=dev)
-    elif not _ok(out_sum, torch.bfloat16, x.get_device()) or tuple(out_sum.shape) != (rows, K):
+    elif add and (not _ok(out_sum, torch.bfloat16, X.get_device()) or tuple(out_sum.shape) != (rows, K)):
         _check_tensor(out_sum, "out_sum", torch.bfloat16, dev)
         raise RuntimeError("out_sum must be [rows, K]")
+    u8 = torch.uint8
     oN = torch.empty((rows, KN // 2), dtype=u8, device=dev)
     oS = torch.empty((rows, KS // 4 * 3), dtype=u8, device=dev)
     oO = torch.empty((rows, KO), dtype=u8, device=dev)
     sfN = torch.empty((_sf_bytes_x(rows, KN),), dtype=u8, device=dev)
     sfS = torch.empty((_sf_bytes_x(rows, KS),), dtype=u8, device=dev)
     sfO = torch.empty((_sf_bytes_x(rows, KO),), dtype=u8, device=dev)
+    tail = (float(eps), rows, K, _ptr(reorder_index), KN, KS, KO, _lib.MM_RMS_REFERENCE if integer_round else _lib.MM_RMS_NO_INTEGER_ROUND,
+            _ptr(oN), _ptr(oS), _ptr(oO), _ptr(sfN), _ptr(sfS), _ptr(sfO), _stream_ptr(dev))
     with _on_device(dev.index):
-        st = lib.mm_add_rmsnorm_quantize(_ptr(x), _ptr(residual), _ptr(out_sum), _ptr(weight), float(eps), rows, K, _ptr(reorder_index),
-                                         KN, KS, KO, _lib.MM_RMS_REFERENCE if integer_round else _lib.MM_RMS_NO_INTEGER_ROUND,
-                                         _ptr(oN), _ptr(oS), _ptr(oO), _ptr(sfN), _ptr(sfS), _ptr(sfO), _stream_ptr(dev))
+        if add:
+            st = lib.mm_add_rmsnorm_quantize(_ptr(X), _ptr(residual), _ptr(out_sum), _ptr(W), *tail)
+        else:
+            st = lib.mm_rmsnorm_quantize(_ptr(X), _ptr(W), *tail)
     if st:
-        _lib.check(st, "add_rmsnorm_quantize_x")
+        _lib.check(st, "add_rmsnorm_quantize_x" if add else "rmsnorm_bf16_mixed")
     return out_sum, oN, oS, oO, sfN, sfS, sfO
 
 
@@ -1291,8 +1242,7 @@ def moe_expert_table(reorder_indices, Bs, KN, KS, KO, biases=None):
         raise ValueError("1 <= E <= 64 experts, one reorder index (and bias entry) each")
     KN, KS, KO = int(KN), int(KS), int(KO)
     K = KN + KS + KO
-    if KN < 0 or KS < 0 or KO < 0 or KN % 128 or KS % 128 or KO % 128 or K == 0:
-        _lib.check(_lib.MM_ERR_BAD_SPLIT, "moe_expert_table")
+    _check_split(KN, KS, KO, None, "moe_expert_table")
     dev = Bs[0][0].device
     index, u8 = dev.index, torch.uint8
     N = Bs[0][0].size(0)
@@ -1329,6 +1279,20 @@ def moe_sf_bytes(n, E, Kseg):
     return (n // 128 + E) * 128 * (Kseg // 32)
 
 
+def _moe_outputs(out, n, E, widths, split, dev):
+    """the 6-tuple a MoE quantizer fills: allocated, or the caller's `out` checked"""
+    u8 = torch.uint8
+    if out is None:
+        return tuple(torch.empty((n, w), dtype=u8, device=dev) for w in widths) + \
+            tuple(torch.empty((moe_sf_bytes(n, E, k),), dtype=u8, device=dev) for k in split)
+    for t, w in zip(out[:3], widths):
+        _moe_tensor(t, "packed output", u8, dev, (n, w))
+    for t, k in zip(out[3:], split):
+        if _moe_tensor(t, "scale output", u8, dev).numel() < moe_sf_bytes(n, E, k):
+            raise RuntimeError("a scale output is smaller than moe_sf_bytes(n, E, Kseg)")
+    return out
+
+
 def moe_quantize(src, row_of_slot, expert_offsets, table, n=None, *, mode="x", out=None):
     """The expert quantizer with the row counts read on the device: for every slot s that an expert owns (expert_offsets int32 [E + 1],
     moe_plan's), row row_of_slot[s] of src bf16 [rows, K] -- row s itself with row_of_slot=None -- quantized with that expert's reorder
@@ -1356,17 +1320,7 @@ def moe_quantize(src, row_of_slot, expert_offsets, table, n=None, *, mode="x", o
             raise RuntimeError("row_of_slot must have n entries")
     else:
         n = src_rows if n is None else int(n)
-    u8 = torch.uint8
-    widths = (KN // 2, KS // 2 if w4 else KS // 4 * 3, KO // 2 if w4 else KO)
-    if out is None:
-        out = tuple(torch.empty((n, w), dtype=u8, device=dev) for w in widths) + \
-            tuple(torch.empty((moe_sf_bytes(n, E, k),), dtype=u8, device=dev) for k in (KN, KS, KO))
-    else:
-        for t, w in zip(out[:3], widths):
-            _moe_tensor(t, "packed output", u8, dev, (n, w))
-        for t, k in zip(out[3:], (KN, KS, KO)):
-            if _moe_tensor(t, "scale output", u8, dev).numel() < moe_sf_bytes(n, E, k):
-                raise RuntimeError("a scale output is smaller than moe_sf_bytes(n, E, Kseg)")
+    out = _moe_outputs(out, n, E, (KN // 2, KS // 2 if w4 else KS // 4 * 3, KO // 2 if w4 else KO), (KN, KS, KO), dev)
     with _on_device(dev.index):
         st = lib.mm_moe_quantize(_ptr(src), _ptr(row_of_slot) if row_of_slot is not None else None, _ptr(expert_offsets), _ptr(table.tensor), E, n,
                                  src_rows, K, KN, KS, KO, _lib.MM_QUANT_W4 if w4 else _lib.MM_QUANT_MIXED, *(_ptr(t) for t in out), _stream_ptr(dev))
@@ -1397,17 +1351,7 @@ def moe_activate_quantize(a, b, expert_offsets, table, *, out=None, h_out=None):
         _moe_tensor(h_out, "h_out", torch.bfloat16, dev, (n, K))
         if h_out.data_ptr() in (a.data_ptr(), b.data_ptr()) and n:
             raise RuntimeError("h_out must not be a or b")
-    u8 = torch.uint8
-    widths = (KN // 2, KS // 4 * 3, KO)
-    if out is None:
-        out = tuple(torch.empty((n, w), dtype=u8, device=dev) for w in widths) + \
-            tuple(torch.empty((moe_sf_bytes(n, E, k),), dtype=u8, device=dev) for k in (KN, KS, KO))
-    else:
-        for t, w in zip(out[:3], widths):
-            _moe_tensor(t, "packed output", u8, dev, (n, w))
-        for t, k in zip(out[3:], (KN, KS, KO)):
-            if _moe_tensor(t, "scale output", u8, dev).numel() < moe_sf_bytes(n, E, k):
-                raise RuntimeError("a scale output is smaller than moe_sf_bytes(n, E, Kseg)")
+    out = _moe_outputs(out, n, E, (KN // 2, KS // 4 * 3, KO), (KN, KS, KO), dev)
     with _on_device(dev.index):
         st = lib.mm_moe_activate_quantize(_ptr(a), _ptr(b), _ptr(expert_offsets), _ptr(table.tensor), E, n, K, KN, KS, KO, *(_ptr(t) for t in out),
                                           _ptr(h_out) if h_out is not None else None, _stream_ptr(dev))
@@ -1429,7 +1373,8 @@ def moe_matmul(A, expert_offsets, table, max_rows, *, rounding="reference", out=
     are the rows from expert_offsets[E] on.  At most two launches, whatever E.  No host sync; capture-safe."""
     lib = _lib.load()
     if rounding not in ("reference", "fused"):
-        raise ValueError("rounding must be 'reference' or 'fused'")
+        _round_flags(rounding)
+    flags = _lib.MM_ROUND_PER_SEGMENT if rounding == "reference" else _lib.MM_ROUND_ONCE
     dev = A[0].device
     E, N, (KN, KS, KO) = table.E, table.N, table.split
     n = A[0].size(0)
@@ -1441,7 +1386,6 @@ def moe_matmul(A, expert_offsets, table, max_rows, *, rounding="reference", out=
             raise RuntimeError("an activation scale tensor is smaller than moe_sf_bytes(n, E, Kseg)")
     _moe_tensor(expert_offsets, "expert_offsets", torch.int32, dev, (E + 1,))
     out = torch.empty((n, N), dtype=torch.bfloat16, device=dev) if out is None else _moe_tensor(out, "out", torch.bfloat16, dev, (n, N))
-    flags = _lib.MM_ROUND_PER_SEGMENT if rounding == "reference" else _lib.MM_ROUND_ONCE
     with _on_device(dev.index):
         st = lib.mm_moe_matmul(*(_ptr(t) for t in A), _ptr(expert_offsets), _ptr(table.tensor), E, n, int(max_rows), N, KN, KS, KO, table.wmode,
                                flags, _ptr(out), _stream_ptr(dev))

@@ -188,14 +188,10 @@ def _forward_norm(layer, x, norm_weight, eps, residual=None):
     if bias is not None and bias.device != x.device:
         bias = bias.to(x.device)
     if _DECODE_FUSED and m <= 8 and plan.norm_wins(m):
-        split = plan.split
-        if residual is None:
-            return mixedgemm.rmsnorm_qlinear_decode(x2d, norm_weight, eps, layer.reorder_index, layer.BN, layer.BS, layer.BO, layer.SFBN, layer.SFBS,
-                                                    layer.SFBO, *split, bias=bias, rounding=getattr(layer, "rounding", "reference")), bsz, q_len
-        s, y = mixedgemm.add_rmsnorm_qlinear_decode(x2d, residual.reshape(m, k).contiguous(), norm_weight, eps, layer.reorder_index, layer.BN, layer.BS,
-                                                    layer.BO, layer.SFBN, layer.SFBS, layer.SFBO, *split, bias=bias,
-                                                    rounding=getattr(layer, "rounding", "reference"))
-        return y, bsz, q_len, s
+        s, y = mixedgemm._qlinear_decode(True, x2d, norm_weight, eps, layer.reorder_index, layer.BN, layer.BS, layer.BO, layer.SFBN, layer.SFBS, layer.SFBO,
+                                         *plan.split, bias, getattr(layer, "rounding", "reference"), True, None,
+                                         None if residual is None else residual.reshape(m, k).contiguous())
+        return (y, bsz, q_len) if residual is None else (y, bsz, q_len, s)
     if residual is None:
         return plan.run_two_op(x2d, bias, norm=(norm_weight, eps)), bsz, q_len
     y, s = plan.run_two_op(x2d, bias, norm=(norm_weight, eps), residual=residual.reshape(m, k).contiguous())
@@ -376,29 +372,18 @@ class FusedMLP(nn.Module):
         # (a wide layer: gate_up_activate is ONE launch at M <= 16 -- then the fused pairs below, whose workgroups all repeat the
         # quantization, only win at M <= 2)
         pair_rows = 2 if mixedgemm.gate_up_activate_decode_supported(1, self.inter, *self.in_split) == 2 else 4
-        if norm_weight is not None:
-            s = None
+        if norm_weight is not None:       # (the private bodies: the plain form without r2, the add_ form with it; s is None without)
             if m <= 2 and mixedgemm.rmsnorm_gate_up_activate_decode_supported(m, self.inter, *self.in_split) == 2:
                 # round 6: norm, quantization, gate | up GEMM, silu * up and the quantization for down_proj in ONE launch; down_proj a plain GEMM
-                if r2 is None:
-                    qh = mixedgemm.rmsnorm_gate_up_activate_decode(x2, norm_weight, eps, self.reorder_index, gu, *self.down_split, rounding=self.rounding)
-                else:
-                    s, *qh = mixedgemm.add_rmsnorm_gate_up_activate_decode(x2, r2, norm_weight, eps, self.reorder_index, gu, *self.down_split,
-                                                                           rounding=self.rounding)
+                s, *qh = mixedgemm._gate_up_activate_decode(True, x2, norm_weight, eps, self.reorder_index, gu, *self.down_split, self.rounding, True, r2)
                 y = mixedgemm.matmul(qh[0], self.D_BN, qh[1], self.D_BS, qh[2], self.D_BO, qh[3], self.D_SFBN, qh[4], self.D_SFBS, qh[5],
                                      self.D_SFBO, rounding=self.rounding)
                 return done(y, s)
             if m <= pair_rows and mixedgemm.rmsnorm_qlinear_decode_supported(m, 2 * self.inter, *self.in_split) == 2 \
                     and mixedgemm.down_activate_decode_supported(m, self.hidden, *self.down_split) == 2:
-                if r2 is None:
-                    gub = mixedgemm.rmsnorm_qlinear_decode(x2, norm_weight, eps, self.reorder_index, *gu, *self.in_split, rounding=self.rounding)
-                else:
-                    s, gub = mixedgemm.add_rmsnorm_qlinear_decode(x2, r2, norm_weight, eps, self.reorder_index, *gu, *self.in_split, rounding=self.rounding)
+                s, gub = mixedgemm._qlinear_decode(True, x2, norm_weight, eps, self.reorder_index, *gu, *self.in_split, None, self.rounding, True, None, r2)
                 return done(mixedgemm.down_activate_decode(gub, down, *self.down_split, rounding=self.rounding), s)
-            if r2 is None:
-                qx = mixedgemm.rmsnorm_quantize_x(x2, norm_weight, eps, self.reorder_index, *self.in_split)
-            else:
-                s, *qx = mixedgemm.add_rmsnorm_quantize_x(x2, r2, norm_weight, eps, self.reorder_index, *self.in_split)
+            s, *qx = mixedgemm._rmsnorm_quantize_x(r2 is not None, x2, norm_weight, eps, self.reorder_index, *self.in_split, True, r2)
             qh = mixedgemm.gate_up_activate(qx, gu, *self.down_split, rounding=self.rounding)
             y = mixedgemm.matmul(qh[0], self.D_BN, qh[1], self.D_BS, qh[2], self.D_BO, qh[3], self.D_SFBN, qh[4], self.D_SFBS, qh[5],
                                  self.D_SFBO, rounding=self.rounding)
