@@ -498,6 +498,22 @@ int mm_moe_combine(const void *y_sorted_bf16, const int32_t *topk_ids, const voi
  *   one launch and leaves the other at once.  An expert with more than max_rows rows is skipped whole: its D rows stay untouched.
  *   KN + KS + KO == 0 writes zeros to the owned rows.  MM_OUT_F32 and shapes whose scale images do not fit the streaming kernels' LDS at some
  *   tier up to min(max_rows, 64)'s (mm_moe_matmul_supported() == 0; the caller then takes mm_matmul_grouped): MM_ERR_UNSUPPORTED.
+ * mm_moe_gate_up_activate (detect it by the symbol; mm_version stays 660): both up-projections, the activation and the quantizer of the
+ *   down-projection in ONE launch of the tiled kernels.  A / SFA the buffers mm_moe_quantize (MM_QUANT_MIXED) filled with w1's split
+ *   (KN, KS, KO).  gate_up_table: per expert the fp4-packed weight of N = 2 I rows whose gate half is w1 and whose up half is w3, both
+ *   with their rows in the order of the expert's w2 reorder index (row j = row idx2[j]) and then interleaved per 128 rows as
+ *   mm_gate_up_activate takes them; no bias.  (DN, DS, DO) is w2's split of the I features.  For every slot s that an expert with
+ *   1 .. max_rows rows owns,
+ *       h[s, j] = bf16( float(bf16( silu(a[s, idx2[j]]) )) * float(b[s, idx2[j]]) )
+ *   with a, b the bf16 rows that the tiled kernels without split-K give the expert for w1 and w3 (mm_moe_matmul's own rows for an
+ *   expert of more than 64 rows; below that mm_moe_matmul streams the weights and may add its fp32 partial sums in another order),
+ *   quantized into packed row s and the expert's run of scale tiles: for owned rows byte for byte the six buffers that
+ *   mm_moe_activate_quantize(a, b, ..) with w2's table fills.  The scale bytes of rows past M_e inside the expert's own tiles are
+ *   unspecified (whole 512-byte atoms are written); everything outside the experts' rows and runs keeps its bytes; an expert above
+ *   max_rows, or one whose offsets are negative, decreasing or past n, is skipped whole.  The grid is the host bound
+ *   (n / bm + min(E, n)) * (2 I / 256): 128-row tiles while that fits one round of workgroups, else 256-row tiles
+ *   (mm_moe_gate_up_activate_describe).  flags: MM_ROUND_ONCE or 0.  I and DN, DS, DO multiples of 128; the packed outputs and the
+ *   scale tensors 16-byte aligned.  mm_moe_gate_up_activate_supported: 0 for max_rows < 1, a bad split, or weights that are not fp4.
  * Null or misaligned pointers, negative sizes: MM_ERR_BAD_ARG; a bad split: MM_ERR_BAD_SPLIT; n = 0: MM_OK; all without device work.
  */
 typedef struct mm_moe_expert {
@@ -517,6 +533,12 @@ int mm_moe_matmul_supported(int max_rows, int N, int KN, int KS, int KO, int wmo
 int mm_moe_matmul(const uint8_t *AN, const uint8_t *AS, const uint8_t *AO, const uint8_t *SFAN, const uint8_t *SFAS, const uint8_t *SFAO,
                   const int32_t *expert_offsets, const mm_moe_expert *expert_table, int num_experts, int num_rows, int max_rows, int N,
                   int KN, int KS, int KO, int wmode, int flags, void *D_bf16, mm_stream_t stream);
+int mm_moe_gate_up_activate_supported(int max_rows, int I, int KN, int KS, int KO, int DN, int DS, int DO, int wmode);
+const char *mm_moe_gate_up_activate_describe(int num_experts, int num_rows, int I);
+int mm_moe_gate_up_activate(const uint8_t *AN, const uint8_t *AS, const uint8_t *AO, const uint8_t *SFAN, const uint8_t *SFAS, const uint8_t *SFAO,
+                            const int32_t *expert_offsets, const mm_moe_expert *gate_up_table, int num_experts, int num_rows, int max_rows, int I,
+                            int KN, int KS, int KO, int DN, int DS, int DO, int flags, uint8_t *oN, uint8_t *oS, uint8_t *oO, uint8_t *sfN,
+                            uint8_t *sfS, uint8_t *sfO, mm_stream_t stream);
 
 /* Which kernel(s) and how many workgroups mm_matmul / mm_matmul_ws launch for this problem on the CURRENT device (the same
  * decision code as the launcher; workspace_bytes = 0 means "no workspace", i.e. never split-K).  Returns a string in a

@@ -20,7 +20,7 @@ def agprs(line):
     return out
 
 
-EXPECTED_KERNELS = 18   # mx_gemm256.hip -- every instantiation the build examines: g256: 2 + 2 grouped + 2 device-sized + fused gate/up + tile-major tail; g128: 2 + 2 split-K + 2 grouped + 2 device-sized + fused gate/up
+EXPECTED_KERNELS = 20   # mx_gemm256.hip -- every instantiation the build examines: g256: 2 + 2 grouped + 2 device-sized + fused gate/up + device-sized fused gate/up + tile-major tail; g128: 2 + 2 split-K + 2 grouped + 2 device-sized + fused gate/up + device-sized fused gate/up
 EXPECTED_SMALL = 6      # mx_gemm_tiles_small.hip -- g64: 2 + 2 grouped + 2 device-sized (the 4-wave tiles leave their accumulators to the compiler)
 
 
@@ -33,7 +33,7 @@ def check_counted(asm_text):
     """(violations, symbols of the kernels with asm-owned accumulators that were examined).  A caller must also require
     len(examined) >= EXPECTED_KERNELS: a name-mangling change would otherwise make the check pass with nothing examined."""
     bad, examined = [], []
-    for m in re.finditer(r"^(_ZN2mm\d(g(?:256|128|64|32n|32|16))(?:17|21|25)mx_gemm256_(?:grouped_|act_|moe_)?kernel\w*):[^\n]*\n(.*?)\.end_amdhsa_kernel",
+    for m in re.finditer(r"^(_ZN2mm\d(g(?:256|128|64|32n|32|16))(?:17|21|25)mx_gemm256_(?:grouped_|act_|moe_|moe_act_)?kernel\w*):[^\n]*\n(.*?)\.end_amdhsa_kernel",
                          asm_text, re.S | re.M):
         sym, ns, body = m.group(1), m.group(2), m.group(3)
         n = NACC[ns]
@@ -194,7 +194,7 @@ def verify_pending(asm_text):
 # matching-precision 256-row kernel lost 2.3x that way (124 us against 53) while every numerical test stayed green.  The tile kernels
 # also may not own static LDS: FragOfsC (mx_gemm_tile.inc) relies on the dynamic LDS starting at byte 0.
 # ---------------------------------------------------------------------------------------------------------
-TILE_KERNEL = re.compile(r"mx_gemm256_(?:grouped_|act_|moe_)?kernel")
+TILE_KERNEL = re.compile(r"mx_gemm256_(?:grouped_|act_|moe_|moe_act_)?kernel")
 
 
 def check_scratch(asm_text):

@@ -24,6 +24,7 @@ EXPORTS = (
     "mm_paged_prefill_workspace_bytes", "mm_paged_prefill", "mm_rope_kv_append",
     "mm_moe_route", "mm_moe_plan", "mm_moe_gather", "mm_moe_combine",
     "mm_moe_sf_bytes", "mm_moe_quantize", "mm_moe_activate_quantize", "mm_moe_matmul_supported", "mm_moe_matmul",
+    "mm_moe_gate_up_activate_supported", "mm_moe_gate_up_activate_describe", "mm_moe_gate_up_activate",
 )
 # every symbol include/micromix_diag.h declares (libmicromix_diag.so: hardware probes for tests/tools, never used by the ops)
 DIAG_LIB_PATH = os.environ.get("MICROMIX_DIAG_LIB") or os.path.join(_PKG, "lib", "libmicromix_diag.so")
@@ -175,6 +176,12 @@ def load():
     lib.mm_moe_matmul_supported.argtypes = [i] * 6
     lib.mm_moe_matmul.restype = i
     lib.mm_moe_matmul.argtypes = [vp] * 8 + [i] * 9 + [vp, vp]
+    lib.mm_moe_gate_up_activate_supported.restype = i
+    lib.mm_moe_gate_up_activate_supported.argtypes = [i] * 9
+    lib.mm_moe_gate_up_activate_describe.restype = ctypes.c_char_p
+    lib.mm_moe_gate_up_activate_describe.argtypes = [i] * 3
+    lib.mm_moe_gate_up_activate.restype = i
+    lib.mm_moe_gate_up_activate.argtypes = [vp] * 8 + [i] * 11 + [vp] * 7
     _lib = lib
     return lib
 

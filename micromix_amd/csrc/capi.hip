@@ -878,6 +878,49 @@ int mm_moe_matmul(const uint8_t *AN, const uint8_t *AS, const uint8_t *AO, const
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_moe_matmul");
 }
 
+// ---- w1 | w3, silu * mul and w2's quantizer in one device-sized launch (mx_gemm_tile.inc: mx_gemm256_moe_act_kernel)
+int mm_moe_gate_up_activate_supported(int max_rows, int I, int KN, int KS, int KO, int DN, int DS, int DO, int wmode) {
+    const int Kin[3] = {KN, KS, KO};
+    if (max_rows < 1 || I < 128 || !decode_split_ok(Kin) || !split_ok(I, DN, DS, DO)) return 0;
+    if (wmode != MM_W_MATCH && wmode != MM_W_FP4) return 0;
+    return weights_fp4(wmode, KS, KO) ? 1 : 0;      // the fused epilogue exists for fp4 weights
+}
+
+const char *mm_moe_gate_up_activate_describe(int num_experts, int num_rows, int I) {
+    if (num_experts < 1 || num_experts > 64 || num_rows < 1 || I < 128 || (I % 128)) return "none";
+    return mm::describe_mx_gemm256_moe_act(num_experts, num_rows, 2 * I);
+}
+
+int mm_moe_gate_up_activate(const uint8_t *AN, const uint8_t *AS, const uint8_t *AO, const uint8_t *SFAN, const uint8_t *SFAS, const uint8_t *SFAO,
+                            const int32_t *expert_offsets, const mm_moe_expert *gate_up_table, int num_experts, int num_rows, int max_rows, int I,
+                            int KN, int KS, int KO, int DN, int DS, int DO, int flags, uint8_t *oN, uint8_t *oS, uint8_t *oO, uint8_t *sfN,
+                            uint8_t *sfS, uint8_t *sfO, mm_stream_t stream) {
+    mm::MoeGroups mg;
+    const int Kin[3] = {KN, KS, KO}, Kd[3] = {DN, DS, DO};
+    if (max_rows < 1 || I < 0 || KN < 0 || KS < 0 || KO < 0) return MM_ERR_BAD_ARG;
+    if (int st = moe_groups(expert_offsets, gate_up_table, num_experts, num_rows, max_rows, &mg)) return st;
+    if (!decode_split_ok(Kin) || !split_ok(I, DN, DS, DO)) return MM_ERR_BAD_SPLIT;
+    if (flags & ~MM_ROUND_ONCE) return MM_ERR_BAD_ARG;
+    if (num_rows == 0) return MM_OK;
+    if (!expert_offsets || !gate_up_table || ((uintptr_t)gate_up_table & 7)) return MM_ERR_BAD_ARG;
+    if (!segments_ok(Kin, {AN, AS, AO}, {SFAN, SFAS, SFAO}) || !segments_ok(Kd, {oN, oS, oO}, {sfN, sfS, sfO})) return MM_ERR_BAD_ARG;
+    // rows leave in 16-byte pieces, scale atoms 16 bytes per lane
+    if ((((uintptr_t)oN | (uintptr_t)oS | (uintptr_t)oO) & 15) || (((uintptr_t)sfN | (uintptr_t)sfS | (uintptr_t)sfO) & 15)) return MM_ERR_BAD_ARG;
+    mm::GemmArgs a = {};
+    a.X[0] = AN; a.X[1] = AS; a.X[2] = AO;
+    a.SFX[0] = SFAN; a.SFX[1] = SFAS; a.SFX[2] = SFAO;
+    a.K[0] = KN; a.K[1] = KS; a.K[2] = KO;
+    a.N = 2 * I;
+    a.sfw_row_tiles = (2 * I + 127) / 128;
+    a.round_per_segment = (flags & MM_ROUND_ONCE) ? 0 : 1;
+    a.act = 1;
+    a.act_K[0] = DN; a.act_K[1] = DS; a.act_K[2] = DO;
+    a.act_o[0] = oN; a.act_o[1] = oS; a.act_o[2] = oO;
+    a.act_sf[0] = sfN; a.act_sf[1] = sfS; a.act_sf[2] = sfO;
+    hipError_t e = mm::launch_mx_gemm256_moe_act(a, mg, (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_moe_gate_up_activate");
+}
+
 int mm_diag_set_kernel_events(void *start_event, void *stop_event) {
     g_ev.start = (hipEvent_t)start_event;
     g_ev.stop = (hipEvent_t)stop_event;

@@ -617,4 +617,39 @@ hipError_t launch_mx_gemm256_moe(const GemmArgs &a, const MoeGroups &mg, bool w4
     return launch_small_tile_moe(64, w4, total, a, mg, stream);
 }
 
+// device-sized grouped launch with the fused gate / up epilogue (mm_moe_gate_up_activate): 256-feature tiles only, every expert of
+// 1 .. max_rows rows in ONE grid.  The grid is the host bound of launch_mx_gemm256_moe on the experts' row tiles; 128-row tiles while
+// that bound fits one round of workgroups (plan_act's rule applied to the bound), 256-row tiles otherwise; no tail balancing, no split-K.
+static bool moe_act_use128(int E, int n, int N, long long *bound) {
+    const int groups = E < n ? E : n;
+    const long long t128 = (long long)(n / 128 + groups) * (N / 256), t256 = (long long)(n / 256 + groups) * (N / 256);
+    const bool use128 = t128 <= device_cus();
+    *bound = use128 ? t128 : t256;
+    return use128;
+}
+
+const char *describe_mx_gemm256_moe_act(int E, int n, int N) {
+    static thread_local char buf[160];
+    long long bound;
+    const bool use128 = moe_act_use128(E, n, N, &bound);
+    snprintf(buf, sizeof(buf), "mm::%s::mx_gemm256_moe_act_kernel x %lld workgroups (%s tiles, fused silu*up + quantize)", use128 ? "g128" : "g256", bound,
+             use128 ? "128x256" : "256x256");
+    return buf;
+}
+
+hipError_t launch_mx_gemm256_moe_act(const GemmArgs &a, const MoeGroups &mg, hipStream_t stream) {
+    if (a.N <= 0 || (a.N % 256) || mg.E < 1 || mg.n < 1) return hipErrorInvalidValue;
+    long long bound;
+    const bool use128 = moe_act_use128(mg.E, mg.n, a.N, &bound);
+    if (bound > INT32_MAX) return hipErrorInvalidValue;
+    static DynamicLdsOnce done[2];
+    auto go = [&](auto kern, DynamicLdsOnce &d, int lds, int threads) -> hipError_t {
+        if (hipError_t e = d.ensure(reinterpret_cast<const void *>(kern), lds); e != hipSuccess) return e;
+        hipLaunchKernelGGL(kern, dim3((int)bound), dim3(threads), lds, stream, a, mg);
+        return hipGetLastError();
+    };
+    return use128 ? go(g128::mx_gemm256_moe_act_kernel, done[1], g128::Lds<true>::TOTAL, g128::NT)
+                  : go(g256::mx_gemm256_moe_act_kernel, done[0], g256::Lds<true>::TOTAL, g256::NT);
+}
+
 }  // namespace mm

@@ -23,6 +23,7 @@
 #endif
 #include "mx_common.h"
 #include "mx_direct_convert.h"
+#include "mx_group_convert.h"
 #include "mx_kernels.h"
 
 namespace mm {

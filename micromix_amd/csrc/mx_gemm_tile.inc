@@ -1672,7 +1672,11 @@ __device__ __forceinline__ void write_tile(const GemmArgs &a, Acc &acc, const in
 // The consumer's segments are multiples of 128 columns, so a tile's 128 features lie in ONE of them: format and destination are
 // workgroup-uniform.  No bias (gate_proj / up_proj have none in the models of BASELINE.json).
 // ---------------------------------------------------------------------------------------------------------
+// BF16H (the MoE experts, mx_gemm256_moe_act_kernel): h is the bf16 value bf16(bf16(silu(gate)) * up) (silu_mul_bf16) and its groups are
+// quantized by the reorder quantizer's arithmetic on bf16 pairs (finish_group, mx_group_convert.h) -- the bytes of
+// mm_moe_activate_quantize, whose reorder index the packed weight's row order has taken in.
 #if MM_WM == 4 && MM_TN == 4
+template <bool BF16H = false>
 __device__ __forceinline__ void write_tile_act(const GemmArgs &a, const int m0, const int n0, uint8_t *smem) {
     constexpr int EP = 320;
     constexpr int IMG = (NT / 64) * 32 * EP;            // the eight bf16 images
@@ -1687,7 +1691,13 @@ __device__ __forceinline__ void write_tile_act(const GemmArgs &a, const int m0, 
     const int KN = a.act_K[0], KS = a.act_K[1];
     const int seg = __builtin_amdgcn_readfirstlane(f0 < KN ? 0 : (f0 < KN + KS ? 1 : 2));
     const int fo = f0 - (seg == 0 ? 0 : seg == 1 ? KN : KN + KS);        // first feature inside the segment: a multiple of 128
-    const int kseg = a.act_K[seg];
+    // (BF16H: `a` is the expert's own copy of the argument block, in registers -- selects, since an index that is not a constant would
+    // send the whole block to scratch.    // Every value goes through readfirstlane (they are uniform) before the select: a select between loads from the block would be
+    // folded back into one load at a computed address.)
+    int kseg;
+    if constexpr (BF16H)
+        kseg = seg == 0 ? __builtin_amdgcn_readfirstlane(KN) : (seg == 1 ? __builtin_amdgcn_readfirstlane(KS) : __builtin_amdgcn_readfirstlane(a.act_K[2]));
+    else kseg = a.act_K[seg];
     [[maybe_unused]] const unsigned sel = (lane & 1) ? 0x03020706u : 0x05040100u;   // as write_tile
     // A: this lane writes rows 8 g + 4 hi + (lane & 1) and that + 2: row & 3 = (lane & 1) and (lane & 1) + 2
     const int col = (li & 6) << 1, ch = li >> 3;
@@ -1712,6 +1722,33 @@ __device__ __forceinline__ void write_tile_act(const GemmArgs &a, const int m0, 
     auto quantize_slice = [&](int tm) {
         const int row_t = (wave >> 1) * (TM * 32) + tm * 32 + rr;        // row inside the tile
         const int m = m0 + row_t;
+        uint32_t byte;
+        if constexpr (BF16H) {
+            uint32_t hv[16], amax = 0;     // hv[i] = {element 2 i, element 2 i + 1} as bf16 bits; amax: the larger magnitude bits of either half
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                float x[8], b[8];
+                unpack8(*reinterpret_cast<const uint4 *>(gate + ((c ^ sw) << 4)), x);
+                unpack8(*reinterpret_cast<const uint4 *>(up + ((c ^ sw) << 4)), b);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const uint32_t lo16 = silu_mul_bf16(x[2 * k], b[2 * k]), hi16 = silu_mul_bf16(x[2 * k + 1], b[2 * k + 1]);
+                    hv[4 * c + k] = lo16 | (hi16 << 16);
+                    const uint32_t ml = lo16 & 0x7FFFu, mh = hi16 & 0x7FFFu;
+                    amax = amax > ml ? amax : ml;
+                    amax = amax > mh ? amax : mh;
+                }
+            }
+            if (seg == 0) {
+                uint8_t *dst = a.act_o[0] + (size_t)m * (size_t)(kseg >> 1) + (fo >> 1) + g * 16;
+                if (m < a.M) byte = finish_group<EL_FP4, true>(hv, amax, dst);
+                else byte = 127u;
+            } else if (seg == 1) {
+                byte = finish_group<EL_FP6>(hv, amax, codes + q * 96 + g * 24);
+            } else {
+                byte = finish_group<EL_FP8>(hv, amax, codes + q * 128 + g * 32);
+            }
+        } else {
         float v[32];
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -1721,7 +1758,6 @@ __device__ __forceinline__ void write_tile_act(const GemmArgs &a, const int m0, 
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[8 * c + e] = silu_mul(x[e], b[e]);
         }
-        uint32_t byte;
         if (seg == 0) {
             // (rows past M: the store is skipped, the group is still quantized -- its scale byte goes into the atom's padding)
             uint8_t *dst = a.act_o[0] + (size_t)m * (size_t)(kseg >> 1) + (fo >> 1) + g * 16;
@@ -1731,6 +1767,7 @@ __device__ __forceinline__ void write_tile_act(const GemmArgs &a, const int m0, 
             byte = quantize32<EL_FP6>(v, codes + q * 96 + g * 24);
         } else {
             byte = quantize32<EL_FP8>(v, codes + q * 128 + g * 32);
+        }
         }
         // C: the quad's four scale bytes -> one dword of the row's SF entry (layout: mx_common.h sf_offset)
         const uint32_t b1 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)byte, 0x55, 0xF, 0xF, false);
@@ -1795,7 +1832,18 @@ __device__ __forceinline__ void write_tile_act(const GemmArgs &a, const int m0, 
         const int atom = lane >> 5;
         if (atom * 128 < BM && m0 + atom * 128 < a.M) {
             const uint4 sv = *reinterpret_cast<const uint4 *>(sfst + lane * 16);
-            uint8_t *dst = a.act_sf[seg] + ((size_t)((m0 >> 7) + atom) * (size_t)(kseg >> 7) + (size_t)(fo >> 7)) * 512u + (lane & 31) * 16;
+            uint8_t *act_sf;
+            if constexpr (BF16H) {
+                auto uniform = [](uint8_t *p) {
+                    const unsigned long long v = (unsigned long long)p;
+                    const unsigned lo32 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v), hi32 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+                    return (uint8_t *)(((unsigned long long)hi32 << 32) | lo32);
+                };
+                uint8_t *const sf0 = uniform(a.act_sf[0]), *const sf1 = uniform(a.act_sf[1]), *const sf2 = uniform(a.act_sf[2]);
+                act_sf = seg == 0 ? sf0 : (seg == 1 ? sf1 : sf2);
+            }
+            else act_sf = a.act_sf[seg];
+            uint8_t *dst = act_sf + ((size_t)((m0 >> 7) + atom) * (size_t)(kseg >> 7) + (size_t)(fo >> 7)) * 512u + (lane & 31) * 16;
             store16<true>(dst, sv.x, sv.y, sv.z, sv.w);
         }
     }
@@ -2010,7 +2058,8 @@ __device__ __forceinline__ void split_tile_reduce(const GemmArgs &a, const int b
 // of the group in a grouped launch)
 // TAIL: the tile-major tail writes the output under the last slabs' MFMAs (run_tail; bf16 output, the launcher's rule)
 // PP: the launch is one fp8 x fp4 segment of >= 2 slabs (K[0] = K[1] = 0), walked by the ping-pong loop (run_pingpong) into the tail
-template <bool W4, bool SPLITK, bool ACT = false, bool TAIL = false, bool PP = false>
+// BF16H: the fused gate / up epilogue in the MoE experts' bits (write_tile_act)
+template <bool W4, bool SPLITK, bool ACT = false, bool TAIL = false, bool PP = false, bool BF16H = false>
 __device__ __forceinline__ void tile_body(const GemmArgs &a, const int bid) {
     static_assert(!TAIL || (!SPLITK && !ACT), "the tail replaces the plain bf16 epilogue only");
     static_assert(!PP || (W4 && TAIL), "the ping-pong loop hands over to the tile-major tail");
@@ -2149,7 +2198,7 @@ __device__ __forceinline__ void tile_body(const GemmArgs &a, const int bid) {
         }
 #endif
 #if MM_WM == 4 && MM_TN == 4
-        if constexpr (ACT) write_tile_act(a, m0, n0, smem);
+        if constexpr (ACT) write_tile_act<BF16H>(a, m0, n0, smem);
         else
 #endif
             write_tile(a, acc, m0, n0, smem);
@@ -2218,6 +2267,27 @@ __global__ void __launch_bounds__(NTHREADS) mx_gemm256_moe_kernel(GemmArgs a, Mo
     moe_group_args(a, mg, e, lo, M);
     tile_body<W4, false>(a, bid);
 }
+
+#if MM_WM == 4 && MM_TN == 4
+// mm_moe_gate_up_activate: the walk of mx_gemm256_moe_kernel, but EVERY expert of 1 .. max_rows rows gets row tiles (one of at most 64
+// rows runs on this tile with its missing rows masked, as write_tile_act masks the rows past a.M), the weight is the expert's packed
+// w1 | w3 (fp4, N = 2 I rows in w2's reordered feature order, interleaved per 128) and the epilogue is write_tile_act in the MoE block's
+// bits.  A workgroup past the real total, or one whose expert's offsets are negative, decreasing or past n, leaves before it touches memory.
+__global__ void __launch_bounds__(NTHREADS) mx_gemm256_moe_act_kernel(GemmArgs a, MoeGroups mg) {
+    const int tiles_n = (a.N + BN - 1) / BN;
+    int bid = blockIdx.x, e = 0, lo = 0, M = 0;
+    for (; e < mg.E; ++e) {
+        lo = mg.offsets[e];
+        M = mg.offsets[e + 1] - lo;
+        const int t = (lo >= 0 && M >= 1 && M <= mg.max_rows && M <= mg.n - lo) ? ((M + BM - 1) / BM) * tiles_n : 0;
+        if (bid < t) break;
+        bid -= t;
+    }
+    if (e >= mg.E) return;
+    moe_group_args<true>(a, mg, e, lo, M);
+    tile_body<true, false, true, false, false, true>(a, bid);
+}
+#endif
 
 }  // namespace MM_NS
 #undef MM_SMALL

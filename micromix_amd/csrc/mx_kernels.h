@@ -154,6 +154,9 @@ __host__ __device__ inline int moe_sf_tile(int lo, int e) { return (lo >> 7) + e
 inline size_t moe_sf_bytes(int n, int E, int Kseg) { return (size_t)(n / 128 + E) * 128u * (size_t)(Kseg / 32); }
 #if defined(__HIPCC__)
 // the argument block of expert e in a launch whose `a` carries the packed buffers (X, SFX, D) and what all experts share
+// ACT (mm_moe_gate_up_activate): `a` also carries the packed outputs of the fused gate / up epilogue, act_o / act_sf, which advance to
+// the expert's rows and to its run of scale tiles by the rule of X / SFX -- the layout mm_moe_quantize writes and mm_moe_matmul reads
+template <bool ACT = false>
 __device__ __forceinline__ void moe_group_args(GemmArgs &a, const MoeGroups &mg, int e, int lo, int M) {
     const MoeExpert &x = mg.table[e];
     const size_t tile = (size_t)moe_sf_tile(lo, e);
@@ -170,6 +173,13 @@ __device__ __forceinline__ void moe_group_args(GemmArgs &a, const MoeGroups &mg,
     a.D += (size_t)lo * (size_t)a.N;
     a.M = M;
     a.sfx_row_tiles = (M + 127) >> 7;
+    if constexpr (ACT) {
+        a.act_o[0] += (size_t)lo * (size_t)(a.act_K[0] >> 1);
+        a.act_o[1] += (size_t)lo * (size_t)((a.act_K[1] >> 2) * 3);
+        a.act_o[2] += (size_t)lo * (size_t)a.act_K[2];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) a.act_sf[i] += tile * (size_t)(a.act_K[i] << 2);
+    }
 }
 #endif
 hipError_t launch_moe_quantize(const void *src, const int *row_of_slot, const MoeGroups &mg, int src_rows, int K, int KN, int KS, int KO,
@@ -182,6 +192,10 @@ bool mx_gemm_stream_moe_supported(int max_m, const int K[3]);
 hipError_t launch_mx_gemm_stream_moe(const GemmArgs &a, const MoeGroups &mg, bool w4, hipStream_t stream);
 // ... groups of 65 .. max_rows rows on the tiled kernels
 hipError_t launch_mx_gemm256_moe(const GemmArgs &a, const MoeGroups &mg, bool w4, hipStream_t stream);
+// ... every group of 1 .. max_rows rows on the 256-feature tiles with the fused gate / up epilogue (mm_moe_gate_up_activate): fp4 weights
+// of N = 2 I interleaved rows, `a` as above plus act_K / act_o / act_sf (the packed buffers of the consumer's operand); no D
+hipError_t launch_mx_gemm256_moe_act(const GemmArgs &a, const MoeGroups &mg, hipStream_t stream);
+const char *describe_mx_gemm256_moe_act(int E, int n, int N);
 hipError_t launch_moe_zero_rows(void *D, const int *offsets, int E, int n, int N, hipStream_t stream);
 
 hipError_t set_quant_clock_buffer(unsigned long long *buf);   // -DMM_INSTRUMENT only

@@ -32,7 +32,8 @@ __all__ = ["test_function", "matmul", "gate_up_activate", "interleave_gate_up", 
            "downproj_quantize_w", "downproj_quantize_w4", "rmsnorm_quantize_x", "qlinear_decode", "qlinear_decode_supported", "matmul_grouped", "reorder_quantize_x_grouped",
            "kv_append", "rope_kv_append", "paged_decode", "paged_decode_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes",
            "moe_route", "moe_plan", "moe_gather", "moe_combine",
-           "moe_expert_table", "moe_sf_bytes", "moe_quantize", "moe_activate_quantize", "moe_matmul", "moe_matmul_supported"]
+           "moe_expert_table", "moe_sf_bytes", "moe_quantize", "moe_activate_quantize", "moe_matmul", "moe_matmul_supported",
+           "permute_packed_rows", "moe_gate_up_table", "moe_gate_up_activate", "moe_gate_up_activate_supported"]
 
 
 def test_function():
@@ -1392,3 +1393,121 @@ def moe_matmul(A, expert_offsets, table, max_rows, *, rounding="reference", out=
     if st:
         _lib.check(st, "moe_matmul")
     return out
+
+
+# ---- w1 | w3, silu * mul and w2's quantizer in one expert launch (mm_moe_gate_up_activate) ----
+
+def permute_packed_rows(packed6, perm):
+    """Rows of a packed weight (BN, BS, BO, SFBN, SFBS, SFBO) in another order: row j of the result is row perm[j] of the input.
+
+    Weights are quantized per output row, so this is a pure byte shuffle, equal byte for byte to quantizing the row-permuted weight:
+    the packed codes move as rows; a scale tensor is tiled per 128 rows, and inside a tile's 512-byte atom of one 128-column slab row
+    r sits at (r & 31) * 16 + ((r >> 5) & 3) * 4 (sf_offset, csrc/mx_common.h).  The row count must be a multiple of 128 (whole scale
+    tiles) and perm a permutation of it.  Plain torch on any device, CPU tensors included; returns new tensors."""
+    n = packed6[0].size(0)
+    perm = torch.as_tensor(perm).to(device=packed6[0].device, dtype=torch.long).reshape(-1)
+    if n % 128 or perm.numel() != n or (n and not torch.equal(torch.sort(perm).values, torch.arange(n, device=perm.device))):
+        raise ValueError("permute_packed_rows: the rows must be a multiple of 128 and perm a permutation of them")
+    out = [t.index_select(0, perm) if t.numel() else t.clone() for t in packed6[:3]]
+    for t in packed6[3:]:
+        if t.numel() == 0:
+            out.append(t.clone())
+            continue
+        if t.numel() % (n * 4):
+            raise ValueError("permute_packed_rows: a scale tensor is not whole 128-row tiles of these rows")
+        atoms = t.numel() // (n * 4)                                  # 128-column slabs of the segment
+        rows = t.reshape(n // 128, atoms, 32, 4, 4).permute(0, 3, 2, 1, 4).reshape(n, atoms * 4)        # [row, its scale bytes]
+        rows = rows.index_select(0, perm)
+        out.append(rows.reshape(n // 128, 4, 32, atoms, 4).permute(0, 3, 2, 1, 4).reshape(-1).contiguous())
+    return tuple(out)
+
+
+def moe_gate_up_table(reorder_indices1, w1s, w3s, reorder_indices2, split1, split2, *, biases1=None, biases3=None):
+    """The device table of `moe_gate_up_activate`: per expert ONE packed fp4 weight of N = 2 I rows made from w1s[e] and w3s[e] (the
+    6-tuples moe_expert_table takes).  Row j of the gate half is w1 row reorder_indices2[e][j], row j of the up half is w3 row
+    reorder_indices2[e][j] -- the expert's w2 reorder index moves into the weight, because the fused epilogue quantizes 128 consecutive
+    features into one segment of w2's K split -- and the halves are interleaved per 128 rows (interleave_gate_up).  reorder_indices1[e]
+    is the index of the first quantizer (w1's), split1 / split2 the (KN, KS, KO) splits of w1 and of w2.  Returns a MoEExpertTable with
+    N = 2 I and no bias whose weights are NEW tensors that it keeps alive: while the originals stay in use elsewhere, the memory held
+    for w1 / w3 doubles.  Raises ValueError for biases on w1 / w3, weights that are not fp4 (MM_W_FP4), I not a multiple of 128 or an
+    entry of split2 that is not a multiple of 128 (or split2 not adding up to I)."""
+    E = len(w1s)
+    if not (1 <= E <= 64) or len(w3s) != E or len(reorder_indices1) != E or len(reorder_indices2) != E:
+        raise ValueError("moe_gate_up_table: 1 <= E <= 64 experts with w1, w3 and both reorder indices each")
+    if any(b is not None for bs in (biases1, biases3) if bs is not None for b in bs):
+        raise ValueError("moe_gate_up_table: w1 / w3 must have no bias (the fused epilogue adds none)")
+    KN, KS, KO = (int(k) for k in split1)
+    split2 = tuple(int(k) for k in split2)
+    I = w1s[0][0].size(0)
+    if I < 128 or I % 128:
+        raise ValueError(f"moe_gate_up_table: I = {I} must be a multiple of 128")
+    if len(split2) != 3 or any(k < 0 or k % 128 for k in split2) or sum(split2) != I:
+        raise ValueError(f"moe_gate_up_table: split2 = {split2} must be three non-negative multiples of 128 that add up to I = {I}")
+    fp4 = ((I, KN // 2), (I, KS // 2), (I, KO // 2))
+    Bs = []
+    for e in range(E):
+        for name, B in (("w1", w1s[e]), ("w3", w3s[e])):
+            if tuple(tuple(t.shape) for t in B[:3]) != fp4:
+                raise ValueError(f"moe_gate_up_table: expert {e}: {name} must be fp4 weights (MM_W_FP4) of [{I}, .] rows matching split1")
+            if any(t.numel() < _sf_bytes_w(I, k) for t, k in zip(B[3:], (KN, KS, KO))):
+                raise ValueError(f"moe_gate_up_table: expert {e}: a scale tensor of {name} holds fewer than _sf_bytes_w(I, Kseg) bytes")
+        idx2 = reorder_indices2[e]
+        if idx2.numel() != I:
+            raise ValueError(f"moe_gate_up_table: expert {e}: w2's reorder index must have I = {I} entries")
+        whole = lambda B: tuple(B[:3]) + tuple(t.reshape(-1)[:_sf_bytes_w(I, k)] for t, k in zip(B[3:], (KN, KS, KO)))
+        Bs.append(interleave_gate_up(permute_packed_rows(whole(w1s[e]), idx2), permute_packed_rows(whole(w3s[e]), idx2)))
+    tab = moe_expert_table(reorder_indices1, Bs, KN, KS, KO)
+    tab.wmode = _lib.MM_W_FP4              # (moe_expert_table cannot tell the modes apart when KS = KO = 0)
+    return tab
+
+
+def _gate_up_split2(table, split2):
+    DN, DS, DO = (int(k) for k in split2)
+    if table.N % 256:
+        raise RuntimeError("table must be a moe_gate_up_table (N = 2 I, I a multiple of 128)")
+    _check_split(DN, DS, DO, table.N // 2, "moe_gate_up_activate")
+    return DN, DS, DO
+
+
+def moe_gate_up_activate_supported(max_rows, table, split2):
+    """False where moe_gate_up_activate would refuse: max_rows < 1, a bad split, or a table whose weights are not fp4"""
+    I = table.N // 2
+    return table.N % 256 == 0 and bool(_lib.load().mm_moe_gate_up_activate_supported(int(max_rows), I, *table.split, *(int(k) for k in split2), table.wmode))
+
+
+def moe_gate_up_activate_describe(table, n, split2=None):
+    """which kernel family and how many workgroups moe_gate_up_activate launches for n rows on the current device"""
+    return _lib.load().mm_moe_gate_up_activate_describe(table.E, int(n), table.N // 2).decode()
+
+
+def moe_gate_up_activate(A, expert_offsets, table, max_rows, split2, *, rounding="reference", out=None):
+    """Both up-projections of the experts, silu * mul and the quantizer of their down-projection in ONE launch: A = moe_quantize's
+    6-tuple (mode "x", w1's split), table = moe_gate_up_table(..), split2 = w2's (KN, KS, KO).  Returns the 6-tuple that moe_matmul
+    takes for w2 -- for every slot an expert of 1 .. max_rows rows owns byte for byte what
+    `moe_activate_quantize(moe_matmul(A, .., w1), moe_matmul(A, .., w3), offsets, w2's table)` gives wherever moe_matmul runs the
+    expert on the tiled kernels (more than 64 rows; below that it may add its fp32 partial sums in another order, include/micromix_hip.h).
+    Scale bytes of rows past an expert's last inside its own 128-row tiles are unspecified; everything else outside the experts' rows
+    and runs, and the rows of an expert above max_rows, are left as they were.  `out=` takes a 6-tuple to fill.  No host sync, no
+    allocation sized by device data; capture-safe."""
+    lib = _lib.load()
+    if rounding not in ("reference", "fused"):
+        _round_flags(rounding)
+    flags = _lib.MM_ROUND_PER_SEGMENT if rounding == "reference" else _lib.MM_ROUND_ONCE
+    dev = A[0].device
+    E, (KN, KS, KO) = table.E, table.split
+    DN, DS, DO = _gate_up_split2(table, split2)
+    n = A[0].size(0)
+    u8 = torch.uint8
+    for t, w in zip(A[:3], (KN // 2, KS // 4 * 3, KO)):
+        _moe_tensor(t, "activation segment", u8, dev, (n, w))
+    for t, k in zip(A[3:], (KN, KS, KO)):
+        if _moe_tensor(t, "activation scales", u8, dev).numel() < moe_sf_bytes(n, E, k):
+            raise RuntimeError("an activation scale tensor is smaller than moe_sf_bytes(n, E, Kseg)")
+    _moe_tensor(expert_offsets, "expert_offsets", torch.int32, dev, (E + 1,))
+    out = _moe_outputs(out, n, E, (DN // 2, DS // 4 * 3, DO), (DN, DS, DO), dev)
+    with _on_device(dev.index):
+        st = lib.mm_moe_gate_up_activate(*(_ptr(t) for t in A), _ptr(expert_offsets), _ptr(table.tensor), E, n, int(max_rows), table.N // 2, KN, KS, KO,
+                                         DN, DS, DO, flags, *(_ptr(t) for t in out), _stream_ptr(dev))
+    if st:
+        _lib.check(st, "moe_gate_up_activate")
+    return tuple(out)

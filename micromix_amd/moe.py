@@ -51,9 +51,19 @@ class SparseMoEBlock(nn.Module):
     up-projections, the down-projection GEMM and the combine are the capturable block's, unchanged; `h` is the device formula's,
     bf16(bf16(x * rcp(1 + exp2(-x log2 e))) * b), which equals torch's `F.silu(a) * b` except where the device `exp2` / `rcp` moves a
     value across a bf16 rounding boundary (fewer than 1 element in 1 000, none by more than 3 bf16 ulps).
+
+    `fused_gate_up` (only with `capturable=True`, else ValueError; default False) replaces both up-projection GEMMs and the activation
+    quantizer -- three launches -- by one, `mixedgemm.moe_gate_up_activate`: the tiled expert GEMM over the packed w1 | w3 weight with
+    silu * mul and w2's quantizer in its epilogue.  `True` takes it at every T on the device-sized path; an int takes it from that many
+    tokens on and the existing path below (below about 128 rows per expert the streaming kernels move the weight bytes faster than a
+    128-row tile; the launch won from T = 128 on where it was measured, DESIGN.md 7e, and nothing is measured below, so the integer has no
+    default).  It needs fp4 weights, no bias on w1 / w3 and a w2 split in 128s
+    (ValueError at construction otherwise), and it keeps a second, row-permuted copy of w1 and w3: their memory doubles.  The bits are
+    `fused_activation`'s for every expert of more than 64 rows; a smaller expert runs on the tiled kernels here and on the streaming
+    kernels there, which may add the fp32 partial sums in another order.
     """
 
-    def __init__(self, gate_weight, experts, top_k, gate_bias=None, capturable=False, fused_activation=False):
+    def __init__(self, gate_weight, experts, top_k, gate_bias=None, capturable=False, fused_activation=False, fused_gate_up=False):
         super().__init__()
         if isinstance(gate_weight, nn.Module):
             gate_weight, gate_bias = gate_weight.weight, (gate_weight.bias if gate_bias is None else gate_bias)
@@ -98,7 +108,16 @@ class SparseMoEBlock(nn.Module):
         self.fused_activation = bool(fused_activation)
         if self.fused_activation and not self.capturable:
             raise ValueError("fused_activation=True needs capturable=True: the fused activation exists for the device-sized launches only")
+        # the token count from which forward takes the one-launch w1 | w3 path: None = never
+        self._gate_up_from = None if fused_gate_up is False else (1 if fused_gate_up is True else int(fused_gate_up))
+        if self._gate_up_from is not None and not self.capturable:
+            raise ValueError("fused_gate_up needs capturable=True: the fused expert launch exists for the device-sized launches only")
+        if self._gate_up_from is not None and self._gate_up_from < 1:
+            raise ValueError("fused_gate_up must be True, False or a token count >= 1")
         self._supported = {}
+        if self._gate_up_from is not None:      # the packed w1 | w3 table: a second copy of both weights, rows in w2's reordered order
+            self._gate_up_table = mixedgemm.moe_gate_up_table(self._idx1, self._B[0], self._B[1], self._idx2, self.split1, self.split2,
+                                                              biases1=self._bias[0], biases3=self._bias[1])
         if self.capturable:      # the device tables of the three layers (mm_moe_expert[E]), built once; they keep their tensors alive
             self._tables = [mixedgemm.moe_expert_table(idx, B, *split, biases=bias) for idx, B, split, bias in
                             zip((self._idx1, self._idx1, self._idx2), self._B, (self.split1, self.split1, self.split2), self._bias)]
@@ -130,6 +149,10 @@ class SparseMoEBlock(nn.Module):
             # row counts stay on the device; a token meets an expert at most once, so no expert has more than T rows
             t1, t3, t2 = self._tables
             q1 = mixedgemm.moe_quantize(x, sorted_token, offsets, t1)          # the row gather is the quantizer's
+            if self._gate_up_from is not None and T >= self._gate_up_from:
+                q2 = mixedgemm.moe_gate_up_activate(q1, offsets, self._gate_up_table, T, self.split2, rounding=self.rounding)
+                y = mixedgemm.moe_matmul(q2, offsets, t2, T, rounding=self.rounding)
+                return mixedgemm.moe_combine(y, ids, w, slot_of).reshape(shape), router_logits
             a = mixedgemm.moe_matmul(q1, offsets, t1, T, rounding=self.rounding)
             b = mixedgemm.moe_matmul(q1, offsets, t3, T, rounding=self.rounding)
             if self.fused_activation:

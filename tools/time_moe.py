@@ -3,6 +3,7 @@
     python tools/time_moe.py [out.txt]
     python tools/time_moe.py device [out.txt]     the capturable block (device-sized grouped launches), see device_main
     python tools/time_moe.py activate [out.txt]   the fused silu * mul + expert quantizer (fused_activation=True), see activate_main
+    python tools/time_moe.py gate_up [out.txt]    w1 | w3, silu * mul and w2's quantizer in one launch (fused_gate_up=True), see gate_up_main
 
 Mixtral-8x7B shapes (H 4096, I 14336, E 8, top_k 2; splits as tests/test_model_shapes_gpu.py), T = 1, 16, 128, 4096, one set of weights.
 1. The block (`SparseMoEBlock.forward`: one host sync) and the reference's loop (model/qMixtralLayer.py:414-452, 502-519) written with
@@ -265,10 +266,68 @@ def activate_main(out_path):
             f.write(f"# {torch.cuda.get_device_name(0)}, torch {torch.__version__}; Mixtral-8x7B shapes H {H} I {I} E {E} top_k {K}\n{text}\n{json.dumps(rows)}\n")
 
 
+def gate_up_main(out_path):
+    """mixedgemm.moe_gate_up_activate against the three launches it replaces -- two moe_matmul and moe_activate_quantize, the parent's
+    code, never the code under test -- and SparseMoEBlock(capturable=True, fused_gate_up=True) against fused_activation=True, at
+    T = 128, 1 024 and 4 096 on one box in one run.  Ten calls per hipGraph (no host time), three runs each in alternation so that the
+    spread is seen; both blocks as ONE graph replay, three runs in alternation.  The bar at T = 4 096: the one launch is faster than the
+    three by more than the spread between the runs."""
+    dev = torch.device("cuda:0")
+    experts = make_experts(dev)
+    g = torch.Generator(device=dev).manual_seed(1)
+    gate_w = (torch.randn((E, H), generator=g, device=dev) * 0.05).to(torch.bfloat16)
+    old = SparseMoEBlock(gate_w, experts, K, capturable=True, fused_activation=True)
+    new = SparseMoEBlock(gate_w, experts, K, capturable=True, fused_gate_up=True)
+    lines, rows = [], []
+    for T in (128, 1024, 4096):
+        x = torch.randn((T, H), generator=g, device=dev).to(torch.bfloat16)
+        iters = 20 if T >= 1024 else 50
+        n = T * K
+        ids, w = mixedgemm.moe_route(F.linear(x, gate_w), K)
+        off, tok, slot = mixedgemm.moe_plan(ids, E)
+        t1, t3, t2 = old._tables
+        q1 = mixedgemm.moe_quantize(x, tok, off, t1)
+        a, b = mixedgemm.moe_matmul(q1, off, t1, T), mixedgemm.moe_matmul(q1, off, t3, T)
+        q2 = mixedgemm.moe_activate_quantize(a, b, off, t2)
+        q3 = mixedgemm.moe_gate_up_activate(q1, off, new._gate_up_table, T, SPLIT_I)
+        counts = (off[1:] - off[:-1]).tolist()
+        same = all(torch.equal(u[:n], v[:n]) for u, v in zip(q2[:3], q3[:3]))
+
+        def three():
+            mixedgemm.moe_matmul(q1, off, t1, T, out=a)
+            mixedgemm.moe_matmul(q1, off, t3, T, out=b)
+            mixedgemm.moe_activate_quantize(a, b, off, t2, out=q2)
+        one = lambda: mixedgemm.moe_gate_up_activate(q1, off, new._gate_up_table, T, SPLIT_I, out=q3)
+        op = {"three": [], "one": []}
+        replay = {"fused_activation": [], "fused_gate_up": []}
+        for _ in range(3):
+            op["three"].append(graph_time(three))
+            op["one"].append(graph_time(one))
+        for _ in range(3):
+            replay["fused_activation"].append(graph_time(lambda: old(x), calls=1, iters=iters))
+            replay["fused_gate_up"].append(graph_time(lambda: new(x), calls=1, iters=iters))
+        sp = lambda v: f"{min(v):8.1f} .. {max(v):8.1f}"
+        spread = max(max(v) - min(v) for v in op.values())
+        lines.append(f"T = {T} (n = {n}, rows per expert {counts}): {mixedgemm.moe_gate_up_activate_describe(new._gate_up_table, n)}; packed bytes equal: {same}")
+        lines.append(f"  two moe_matmul + moe_activate_quantize (ten per graph)   {sp(op['three'])} us (three runs in alternation)")
+        lines.append(f"  moe_gate_up_activate (ten per graph)                     {sp(op['one'])} us; gain {min(op['three']) - max(op['one']):8.1f} us worst case against a spread of {spread:.1f} us")
+        lines.append(f"  one graph replay of the block: fused_activation {sp(replay['fused_activation'])} us, fused_gate_up {sp(replay['fused_gate_up'])} us")
+        rows.append(dict(T=T, rows_per_expert=counts, three_launches_us=[round(v, 2) for v in op["three"]], one_launch_us=[round(v, 2) for v in op["one"]],
+                         packed_bytes_equal=same, replay_us={k: [round(u, 1) for u in v] for k, v in replay.items()}))
+    text = "\n".join(lines)
+    print(text)
+    print(json.dumps(rows))
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(f"# {torch.cuda.get_device_name(0)}, torch {torch.__version__}; Mixtral-8x7B shapes H {H} I {I} E {E} top_k {K}\n{text}\n{json.dumps(rows)}\n")
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "device":
         device_main(sys.argv[2] if len(sys.argv) > 2 else None)
     elif len(sys.argv) > 1 and sys.argv[1] == "activate":
         activate_main(sys.argv[2] if len(sys.argv) > 2 else None)
+    elif len(sys.argv) > 1 and sys.argv[1] == "gate_up":
+        gate_up_main(sys.argv[2] if len(sys.argv) > 2 else None)
     else:
         main()
