@@ -392,6 +392,33 @@ int mm_paged_prefill(const void *q_bf16, const int32_t *qo_indptr, int num_token
                      void *o_bf16, mm_stream_t stream);
 
 /*
+ * Sliding-window attention over the paged KV cache (detect the four entries by their symbols; mm_version stays 660).  `window` = W >= 1
+ * is HF's sliding_window: the query at position p attends positions max(0, p - W + 1) .. p, W tokens with itself -- in decode
+ * p = len_b - 1, in prefill p = len_b - n_b + j (bottom-right, as above).  W = 0: no window, the same launches and the same bits as
+ * mm_paged_decode / mm_paged_prefill; W < 0: MM_ERR_BAD_ARG.  Everything else -- arguments, sm_scale, head rules, both cache kinds, a
+ * length-0 sequence, negative positions, statuses -- as the un-windowed entry of the same name.
+ *   Only the kv tiles that hold a window are visited (decode: from token max(0, len_b - W) on; prefill: per query tile, from the
+ *   window start of its first token rounded down to 64), and the split-KV chunks are laid over that span, not over the sequence:
+ *   over min(max_seq_len, W) tokens in decode and min(max_seq_len, W + 64 / g + 62) in prefill.  So the grid and the
+ *   workspace depend on the old host values plus W (the *_window_workspace_bytes queries), one captured graph stays valid while the
+ *   sequences grow -- past max_seq_len too, the cost staying that of W tokens -- and W >= max_seq_len gives the un-windowed split.
+ *   The page-table entry of a token below every window is never read (prefill: read and its token masked), and a page index outside [0, max_pages) masks its
+ *   tokens as everywhere else, so the pages that lie wholly below every window may be released and reused: put -1 in their entries and
+ *   keep the entries, so that positions do not move (PagedKVCache(window=W) does this).
+ */
+size_t mm_paged_decode_window_workspace_bytes(int batch, int num_qo_heads, int num_kv_heads, int max_seq_len, int window);
+int mm_paged_decode_window(const void *q_bf16, const void *kv_data, const void *kv_param, int kv_dtype, int max_pages, int num_layers,
+                           int layer, int num_kv_heads, int page_size, int head_dim, const int32_t *kv_indptr, const int32_t *kv_indices,
+                           const int32_t *last_page_len, int batch, int num_qo_heads, int max_seq_len, float sm_scale, void *workspace,
+                           size_t workspace_bytes, void *o_bf16, mm_stream_t stream, int window);
+size_t mm_paged_prefill_window_workspace_bytes(int num_tokens, int batch, int num_qo_heads, int num_kv_heads, int max_seq_len, int window);
+int mm_paged_prefill_window(const void *q_bf16, const int32_t *qo_indptr, int num_tokens, const void *kv_data, const void *kv_param,
+                            int kv_dtype, int max_pages, int num_layers, int layer, int num_kv_heads, int page_size, int head_dim,
+                            const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_len, int batch,
+                            int num_qo_heads, int max_seq_len, float sm_scale, void *workspace, size_t workspace_bytes,
+                            void *o_bf16, mm_stream_t stream, int window);
+
+/*
  * RoPE + paged KV append in one launch (version >= 620): takes q | k | v as the fused q/k/v projection leaves them, leaves the rotated
  * q ready for mm_paged_decode / mm_paged_prefill and the rotated K and the untouched V in the cache.  Cache layout, page table, head_dim
  * 128 as above; no limit on g = Hq / Hkv.

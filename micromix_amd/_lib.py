@@ -22,6 +22,7 @@ EXPORTS = (
     "mm_matmul_describe", "mm_test_function", "mm_diag_set_kernel_events",
     "mm_kv_append", "mm_paged_decode_workspace_bytes", "mm_paged_decode",
     "mm_paged_prefill_workspace_bytes", "mm_paged_prefill", "mm_rope_kv_append",
+    "mm_paged_decode_window_workspace_bytes", "mm_paged_decode_window", "mm_paged_prefill_window_workspace_bytes", "mm_paged_prefill_window",
     "mm_moe_route", "mm_moe_plan", "mm_moe_gather", "mm_moe_combine",
     "mm_moe_sf_bytes", "mm_moe_quantize", "mm_moe_activate_quantize", "mm_moe_matmul_supported", "mm_moe_matmul",
     "mm_moe_gate_up_activate_supported", "mm_moe_gate_up_activate_describe", "mm_moe_gate_up_activate",
@@ -156,6 +157,14 @@ def load():
     lib.mm_paged_prefill_workspace_bytes.argtypes = [i] * 5
     lib.mm_paged_prefill.restype = i
     lib.mm_paged_prefill.argtypes = [vp, vp, i, vp, vp] + [i] * 7 + [vp] * 3 + [i, i, i, ctypes.c_float, vp, sz, vp, vp]
+    lib.mm_paged_decode_window_workspace_bytes.restype = sz
+    lib.mm_paged_decode_window_workspace_bytes.argtypes = [i] * 5
+    lib.mm_paged_decode_window.restype = i
+    lib.mm_paged_decode_window.argtypes = lib.mm_paged_decode.argtypes + [i]
+    lib.mm_paged_prefill_window_workspace_bytes.restype = sz
+    lib.mm_paged_prefill_window_workspace_bytes.argtypes = [i] * 6
+    lib.mm_paged_prefill_window.restype = i
+    lib.mm_paged_prefill_window.argtypes = lib.mm_paged_prefill.argtypes + [i]
     lib.mm_rope_kv_append.restype = i
     lib.mm_rope_kv_append.argtypes = [vp, vp] + [i] * 7 + [vp] * 3 + [i, vp, vp, vp, ctypes.c_int64, i, vp, vp, ctypes.c_int64, vp, i, vp, vp]
     lib.mm_moe_route.restype = i

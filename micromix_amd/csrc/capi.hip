@@ -689,51 +689,77 @@ int mm_rope_kv_append(void *kv_data, void *kv_param, int kv_dtype, int max_pages
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_rope_kv_append");
 }
 
+// the un-windowed entry points are the windowed ones at window = 0
+size_t mm_paged_decode_window_workspace_bytes(int batch, int num_qo_heads, int num_kv_heads, int max_seq_len, int window) {
+    if (batch <= 0 || num_kv_heads <= 0 || num_qo_heads <= 0 || max_seq_len < 0 || window < 0 || num_qo_heads % num_kv_heads) return 0;
+    return mm::kv_decode_workspace_bytes(batch, num_qo_heads, num_kv_heads, max_seq_len, window);
+}
+
 size_t mm_paged_decode_workspace_bytes(int batch, int num_qo_heads, int num_kv_heads, int max_seq_len) {
-    if (batch <= 0 || num_kv_heads <= 0 || num_qo_heads <= 0 || max_seq_len < 0 || num_qo_heads % num_kv_heads) return 0;
-    return mm::kv_decode_workspace_bytes(batch, num_qo_heads, num_kv_heads, max_seq_len);
+    return mm_paged_decode_window_workspace_bytes(batch, num_qo_heads, num_kv_heads, max_seq_len, 0);
+}
+
+int mm_paged_decode_window(const void *q_bf16, const void *kv_data, const void *kv_param, int kv_dtype, int max_pages, int num_layers, int layer,
+                           int num_kv_heads, int page_size, int head_dim, const int32_t *kv_indptr, const int32_t *kv_indices,
+                           const int32_t *last_page_len, int batch, int num_qo_heads, int max_seq_len, float sm_scale, void *workspace,
+                           size_t workspace_bytes, void *o_bf16, mm_stream_t stream, int window) {
+    mm::PagedKV kv;
+    if (int st = kv_geometry(kv_data, kv_param, kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size, head_dim, kv_indptr, kv_indices,
+                             last_page_len, batch, &kv)) return st;
+    if (num_qo_heads <= 0 || num_qo_heads % num_kv_heads || max_seq_len < 0 || window < 0) return MM_ERR_BAD_ARG;
+    if (num_qo_heads / num_kv_heads > 16) return MM_ERR_UNSUPPORTED;
+    if (batch == 0) return MM_OK;
+    if (!q_bf16 || !kv_pointers(kv) || !o_bf16) return MM_ERR_BAD_ARG;
+    const size_t need = mm_paged_decode_window_workspace_bytes(batch, num_qo_heads, num_kv_heads, max_seq_len, window);
+    if (need && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15))) return MM_ERR_BAD_ARG;
+    hipError_t e = mm::launch_paged_decode(kv, q_bf16, num_qo_heads, max_seq_len, window, sm_scale, workspace, o_bf16, (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, window ? "mm_paged_decode_window" : "mm_paged_decode");
 }
 
 int mm_paged_decode(const void *q_bf16, const void *kv_data, const void *kv_param, int kv_dtype, int max_pages, int num_layers, int layer,
                     int num_kv_heads, int page_size, int head_dim, const int32_t *kv_indptr, const int32_t *kv_indices,
                     const int32_t *last_page_len, int batch, int num_qo_heads, int max_seq_len, float sm_scale, void *workspace,
                     size_t workspace_bytes, void *o_bf16, mm_stream_t stream) {
-    mm::PagedKV kv;
-    if (int st = kv_geometry(kv_data, kv_param, kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size, head_dim, kv_indptr, kv_indices,
-                             last_page_len, batch, &kv)) return st;
-    if (num_qo_heads <= 0 || num_qo_heads % num_kv_heads || max_seq_len < 0) return MM_ERR_BAD_ARG;
-    if (num_qo_heads / num_kv_heads > 16) return MM_ERR_UNSUPPORTED;
-    if (batch == 0) return MM_OK;
-    if (!q_bf16 || !kv_pointers(kv) || !o_bf16) return MM_ERR_BAD_ARG;
-    const size_t need = mm_paged_decode_workspace_bytes(batch, num_qo_heads, num_kv_heads, max_seq_len);
-    if (need && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15))) return MM_ERR_BAD_ARG;
-    hipError_t e = mm::launch_paged_decode(kv, q_bf16, num_qo_heads, max_seq_len, sm_scale, workspace, o_bf16, (hipStream_t)stream);
-    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_paged_decode");
+    return mm_paged_decode_window(q_bf16, kv_data, kv_param, kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size, head_dim, kv_indptr,
+                                  kv_indices, last_page_len, batch, num_qo_heads, max_seq_len, sm_scale, workspace, workspace_bytes, o_bf16, stream, 0);
+}
+
+size_t mm_paged_prefill_window_workspace_bytes(int num_tokens, int batch, int num_qo_heads, int num_kv_heads, int max_seq_len, int window) {
+    if (num_tokens <= 0 || batch <= 0 || batch > 65535 || num_kv_heads <= 0 || num_kv_heads > 65535 || num_qo_heads <= 0 ||
+        max_seq_len < 0 || window < 0 || num_qo_heads % num_kv_heads || num_qo_heads / num_kv_heads > 16)
+        return 0;
+    return mm::kv_prefill_workspace_bytes(num_tokens, batch, num_qo_heads, num_kv_heads, max_seq_len, window);
 }
 
 size_t mm_paged_prefill_workspace_bytes(int num_tokens, int batch, int num_qo_heads, int num_kv_heads, int max_seq_len) {
-    if (num_tokens <= 0 || batch <= 0 || batch > 65535 || num_kv_heads <= 0 || num_kv_heads > 65535 || num_qo_heads <= 0 ||
-        max_seq_len < 0 || num_qo_heads % num_kv_heads || num_qo_heads / num_kv_heads > 16)
-        return 0;
-    return mm::kv_prefill_workspace_bytes(num_tokens, batch, num_qo_heads, num_kv_heads, max_seq_len);
+    return mm_paged_prefill_window_workspace_bytes(num_tokens, batch, num_qo_heads, num_kv_heads, max_seq_len, 0);
+}
+
+int mm_paged_prefill_window(const void *q_bf16, const int32_t *qo_indptr, int num_tokens, const void *kv_data, const void *kv_param, int kv_dtype,
+                            int max_pages, int num_layers, int layer, int num_kv_heads, int page_size, int head_dim, const int32_t *kv_indptr,
+                            const int32_t *kv_indices, const int32_t *last_page_len, int batch, int num_qo_heads, int max_seq_len,
+                            float sm_scale, void *workspace, size_t workspace_bytes, void *o_bf16, mm_stream_t stream, int window) {
+    mm::PagedKV kv;
+    if (int st = kv_geometry(kv_data, kv_param, kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size, head_dim, kv_indptr, kv_indices,
+                             last_page_len, batch, &kv)) return st;
+    if (num_qo_heads <= 0 || num_qo_heads % num_kv_heads || max_seq_len < 0 || num_tokens < 0 || window < 0) return MM_ERR_BAD_ARG;
+    if (num_qo_heads / num_kv_heads > 16) return MM_ERR_UNSUPPORTED;
+    if (num_tokens == 0 || batch == 0) return MM_OK;
+    if (!q_bf16 || !qo_indptr || !kv_pointers(kv) || !o_bf16) return MM_ERR_BAD_ARG;
+    const size_t need = mm_paged_prefill_window_workspace_bytes(num_tokens, batch, num_qo_heads, num_kv_heads, max_seq_len, window);
+    if (need && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15))) return MM_ERR_BAD_ARG;
+    hipError_t e = mm::launch_paged_prefill(kv, q_bf16, qo_indptr, num_tokens, num_qo_heads, max_seq_len, window, sm_scale, workspace, o_bf16,
+                                            (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, window ? "mm_paged_prefill_window" : "mm_paged_prefill");
 }
 
 int mm_paged_prefill(const void *q_bf16, const int32_t *qo_indptr, int num_tokens, const void *kv_data, const void *kv_param, int kv_dtype,
                      int max_pages, int num_layers, int layer, int num_kv_heads, int page_size, int head_dim, const int32_t *kv_indptr,
                      const int32_t *kv_indices, const int32_t *last_page_len, int batch, int num_qo_heads, int max_seq_len, float sm_scale,
                      void *workspace, size_t workspace_bytes, void *o_bf16, mm_stream_t stream) {
-    mm::PagedKV kv;
-    if (int st = kv_geometry(kv_data, kv_param, kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size, head_dim, kv_indptr, kv_indices,
-                             last_page_len, batch, &kv)) return st;
-    if (num_qo_heads <= 0 || num_qo_heads % num_kv_heads || max_seq_len < 0 || num_tokens < 0) return MM_ERR_BAD_ARG;
-    if (num_qo_heads / num_kv_heads > 16) return MM_ERR_UNSUPPORTED;
-    if (num_tokens == 0 || batch == 0) return MM_OK;
-    if (!q_bf16 || !qo_indptr || !kv_pointers(kv) || !o_bf16) return MM_ERR_BAD_ARG;
-    const size_t need = mm_paged_prefill_workspace_bytes(num_tokens, batch, num_qo_heads, num_kv_heads, max_seq_len);
-    if (need && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15))) return MM_ERR_BAD_ARG;
-    hipError_t e = mm::launch_paged_prefill(kv, q_bf16, qo_indptr, num_tokens, num_qo_heads, max_seq_len, sm_scale, workspace, o_bf16,
-                                            (hipStream_t)stream);
-    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_paged_prefill");
+    return mm_paged_prefill_window(q_bf16, qo_indptr, num_tokens, kv_data, kv_param, kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size,
+                                   head_dim, kv_indptr, kv_indices, last_page_len, batch, num_qo_heads, max_seq_len, sm_scale, workspace,
+                                   workspace_bytes, o_bf16, stream, 0);
 }
 
 // ---- sparse MoE block (moe.hip)

@@ -14,6 +14,9 @@
 //   p.V     VALU, fp32: a lane owns 8 dims of 8 tokens of the tile, acc[h][8] += (p s_v)[h] * code  (minus sum(p z_v) once at the end)
 // The waves merge through LDS; with one chunk the workgroup writes o, otherwise (m, l, o) partials that mm_paged_decode's merge kernel
 // combines.
+// Sliding window (mm_paged_decode_window, the WINDOW kernels): the walk starts at token max(0, len - W) instead of at token 0 and the
+// chunks are laid over the W tokens from there, so a long sequence costs its window; the un-windowed kernels are the WINDOW = false
+// instantiations, instruction for instruction what they were.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <math.h>
@@ -50,9 +53,13 @@ struct DecodeArgs {
     uint16_t *o;
     int Hq, g, nc, chunk;
     float scale_log2;          // sm_scale * log2(e)
+    int window;                // WINDOW kernels: the query attends its last `window` >= 1 tokens (itself included)
 };
 
-template <bool INT4, int GP>
+// WINDOW: the workgroups of sequence b walk [lo_b, len_b), lo_b = max(0, len_b - window), chunk c from lo_b + c * chunk on.  The tiles
+// start at lo_b itself -- a lane addresses its token's row on its own, so a tile need not start on a multiple of 32 -- and no token
+// below the window is ever looked at: no compare, no page-table read, the span exactly min(len_b, window) tokens
+template <bool INT4, int GP, bool WINDOW>
 __global__ __launch_bounds__(256) void paged_decode_kernel(const DecodeArgs a) {
     __shared__ float s_p[DEC_WAVES][TILE][16];        // (p * scale) of the tile, [token][head]
     __shared__ float s_alpha[DEC_WAVES][16];
@@ -65,7 +72,7 @@ __global__ __launch_bounds__(256) void paged_decode_kernel(const DecodeArgs a) {
     const PagedKV &kv = a.kv;
     const int g = a.g;
     const int len = seq_len(kv, b);
-    const int t0 = chunk * a.chunk;
+    const int t0 = (WINDOW ? window_begin(len - 1, a.window) : 0) + chunk * a.chunk;
     const int t1 = chunk == a.nc - 1 ? len : min(len, t0 + a.chunk);   // the last chunk runs to the end, whatever max_seq_len said
     const int *pages = kv.indices + kv.indptr[b];
 
@@ -278,12 +285,12 @@ __global__ __launch_bounds__(64) void paged_decode_merge_kernel(const DecodeArgs
     *(uint32_t *)(a.o + ((int64_t)b * a.Hq + hq) * HD + d) = pack_bf(o[0], o[1]);
 }
 
-template <bool INT4>
+template <bool INT4, bool WINDOW>
 hipError_t launch_decode_g(const DecodeArgs &a, hipStream_t stream) {
     const dim3 grid(a.nc, a.kv.Hkv, a.kv.B);
-    if (a.g <= 4) paged_decode_kernel<INT4, 4><<<grid, 256, 0, stream>>>(a);
-    else if (a.g <= 8) paged_decode_kernel<INT4, 8><<<grid, 256, 0, stream>>>(a);
-    else paged_decode_kernel<INT4, 16><<<grid, 256, 0, stream>>>(a);
+    if (a.g <= 4) paged_decode_kernel<INT4, 4, WINDOW><<<grid, 256, 0, stream>>>(a);
+    else if (a.g <= 8) paged_decode_kernel<INT4, 8, WINDOW><<<grid, 256, 0, stream>>>(a);
+    else paged_decode_kernel<INT4, 16, WINDOW><<<grid, 256, 0, stream>>>(a);
     return hipGetLastError();
 }
 
@@ -304,14 +311,18 @@ void kv_chunks(long long work, int target_workgroups, int max_seq_len, int round
     *nc = max_seq_len > 0 ? (max_seq_len + cl - 1) / cl : 1;
 }
 
-void kv_decode_split(int B, int Hkv, int max_seq_len, int *nc, int *chunk) {
-    // two workgroups per CU of the 256 on an MI355X; a chunk gives every wave whole tiles
-    kv_chunks((long long)B * Hkv, 512, max_seq_len, TILE * DEC_WAVES, nc, chunk);
+int kv_window_span(int max_seq_len, int window, int slack) {
+    return window > 0 && (long long)window + slack < max_seq_len ? window + slack : max_seq_len;
 }
 
-size_t kv_decode_workspace_bytes(int B, int Hq, int Hkv, int max_seq_len) {
+void kv_decode_split(int B, int Hkv, int max_seq_len, int window, int *nc, int *chunk) {
+    // two workgroups per CU of the 256 on an MI355X; a chunk gives every wave whole tiles.  A window's range is the window: no slack
+    kv_chunks((long long)B * Hkv, 512, kv_window_span(max_seq_len, window, 0), TILE * DEC_WAVES, nc, chunk);
+}
+
+size_t kv_decode_workspace_bytes(int B, int Hq, int Hkv, int max_seq_len, int window) {
     int nc, chunk;
-    kv_decode_split(B, Hkv, max_seq_len, &nc, &chunk);
+    kv_decode_split(B, Hkv, max_seq_len, window, &nc, &chunk);
     return nc > 1 ? (size_t)B * Hq * nc * (HD + 2) * sizeof(float) : 0;     // DecodeArgs::ws
 }
 
@@ -322,7 +333,7 @@ hipError_t launch_kv_append(const PagedKV &kv, const void *k, const void *v, con
     return hipGetLastError();
 }
 
-hipError_t launch_paged_decode(const PagedKV &kv, const void *q, int Hq, int max_seq_len, float sm_scale, void *ws, void *o,
+hipError_t launch_paged_decode(const PagedKV &kv, const void *q, int Hq, int max_seq_len, int window, float sm_scale, void *ws, void *o,
                                hipStream_t stream) {
     DecodeArgs a;
     a.kv = kv;
@@ -331,9 +342,11 @@ hipError_t launch_paged_decode(const PagedKV &kv, const void *q, int Hq, int max
     a.o = (uint16_t *)o;
     a.Hq = Hq;
     a.g = Hq / kv.Hkv;
-    kv_decode_split(kv.B, kv.Hkv, max_seq_len, &a.nc, &a.chunk);
+    kv_decode_split(kv.B, kv.Hkv, max_seq_len, window, &a.nc, &a.chunk);
     a.scale_log2 = kv_scale_log2(sm_scale);
-    hipError_t e = kv.int4 ? launch_decode_g<true>(a, stream) : launch_decode_g<false>(a, stream);
+    a.window = window;
+    hipError_t e = window > 0 ? (kv.int4 ? launch_decode_g<true, true>(a, stream) : launch_decode_g<false, true>(a, stream))
+                              : (kv.int4 ? launch_decode_g<true, false>(a, stream) : launch_decode_g<false, false>(a, stream));
     if (e != hipSuccess || a.nc == 1) return e;
     paged_decode_merge_kernel<<<dim3(Hq, kv.B), 64, 0, stream>>>(a);
     return hipGetLastError();

@@ -17,6 +17,10 @@
 // writes (m, l, o) partials and a merge launch combines them.  The tile -> (sequence, tile of it) map needs no host knowledge of
 // qo_indptr: sequence b owns tiles [qo_indptr[b] / BQ + b, qo_indptr[b + 1] / BQ + b + 1), which hold its ceil(n_b / BQ) tiles;
 // the surplus workgroups exit.
+// Sliding window (mm_paged_prefill_window, the WINDOW kernels): a query at position p attends max(0, p - W + 1) .. p.  A query tile's
+// walk starts at the kv tile that holds its first token's window start, its chunks are laid over the W + BQ + 62 tokens from there, a
+// wave skips the tiles below all its rows' windows, and the lower-edge compare runs only on the tiles that cross one.  The un-windowed
+// kernels are the WINDOW = false instantiations, instruction for instruction what they were.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <math.h>
@@ -48,6 +52,7 @@ struct PrefillArgs {
     uint16_t *o;
     int T, Hq, g, bq, tiles, nc, chunk;
     float scale_log2;          // sm_scale * log2(e)
+    int window;                // WINDOW kernels: a query at position p attends positions max(0, p - window + 1) .. p
 };
 
 // (sequence, tile of it, its token count) of workgroup tile index i; false for a surplus tile
@@ -64,7 +69,10 @@ __device__ inline bool tile_of(const PrefillArgs &a, int i, int &b, int &j, int 
     return n > 0 && j * a.bq < n;
 }
 
-template <bool INT4>
+// WINDOW: a query tile walks the kv tiles from the window of its first token on (rounded down to KT), chunk c from there + c * chunk;
+// a wave skips the tiles that lie below the windows of all its rows and compares against the lower edge only on the tiles that cross
+// one of them -- both wave-uniform, like the diagonal's gate
+template <bool INT4, bool WINDOW>
 __global__ __launch_bounds__(NT) void paged_prefill_kernel(const PrefillArgs a) {
     constexpr int KSTR = INT4 ? KSTR4 : KSTR16;
     __shared__ __attribute__((aligned(16))) uint8_t s_k[KT * KSTR];
@@ -84,7 +92,7 @@ __global__ __launch_bounds__(NT) void paged_prefill_kernel(const PrefillArgs a) 
     const int ntok = min(a.bq, n - j * a.bq);             // query tokens of this tile
     const int pos0 = len - n + j * a.bq;                   // position of its first token
     const int pmax = pos0 + ntok - 1;                      // the last position any row attends
-    const int t0 = chunk * a.chunk;
+    const int t0 = (WINDOW ? window_begin(max(pos0, -1), a.window) & ~(KT - 1) : 0) + chunk * a.chunk;
     const int t1 = chunk == a.nc - 1 ? len : min(len, t0 + a.chunk);   // the last chunk runs to the end, whatever max_seq_len said
     const int kend = min(t1, pmax + 1);
 
@@ -204,6 +212,7 @@ __global__ __launch_bounds__(NT) void paged_prefill_kernel(const PrefillArgs a) 
         __syncthreads();
         if (kt + KT < kend) load(kt + KT);                 // in flight during this tile's math
         if (!wactive || kt > wpmax) continue;              // every row of this wave is masked on this tile
+        if (WINDOW && wpmin - (kt + KT - 1) >= a.window) continue;   // ... it lies below the windows of all of them
 
         // ---- scores S^T: lane (c, kq) holds rows' scores of tokens kt + 16 blk + 4 kq + r for its row
         float sc[4][4];
@@ -233,6 +242,13 @@ __global__ __launch_bounds__(NT) void paged_prefill_kernel(const PrefillArgs a) 
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
                     if (kt + 16 * blk + 4 * kq + r > prow) sc[blk][r] = -INFINITY;
+        }
+        if (WINDOW && wpmax - kt >= a.window) {            // the tile crosses the lower edge of some row's window
+#pragma unroll
+            for (int blk = 0; blk < 4; ++blk)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (prow - (kt + 16 * blk + 4 * kq + r) >= a.window) sc[blk][r] = -INFINITY;
         }
         // ---- online softmax (log2 domain)
         float mt = -INFINITY;
@@ -339,21 +355,25 @@ __global__ __launch_bounds__(NT) void paged_prefill_merge_kernel(const PrefillAr
 
 namespace mm {
 
-void kv_prefill_split(int T, int B, int Hq, int Hkv, int max_seq_len, int *tiles, int *nc, int *chunk) {
+void kv_prefill_split(int T, int B, int Hq, int Hkv, int max_seq_len, int window, int *tiles, int *nc, int *chunk) {
     // tiles: an upper bound on sum ceil(n_b / BQ), BQ = 64 / g query tokens per tile.  Chunks: four workgroups per CU of the 256 on an MI355X
     const int g = Hkv > 0 && Hq >= Hkv ? Hq / Hkv : 1;
-    *tiles = T / (ROWS / (g > 0 && g <= ROWS ? g : 1)) + B;
-    kv_chunks((long long)(*tiles > 0 ? *tiles : 1) * (Hkv > 0 ? Hkv : 1), 1024, max_seq_len, KT, nc, chunk);
+    const int bq = ROWS / (g > 0 && g <= ROWS ? g : 1);
+    *tiles = T / bq + B;
+    // a window: a query tile walks from the kv tile that holds the window's start of its first token (at most KT - 1 tokens below it)
+    // to its last token's position, bq - 1 above the first's
+    kv_chunks((long long)(*tiles > 0 ? *tiles : 1) * (Hkv > 0 ? Hkv : 1), 1024, kv_window_span(max_seq_len, window, bq - 1 + KT - 1), KT, nc,
+              chunk);
 }
 
-size_t kv_prefill_workspace_bytes(int T, int B, int Hq, int Hkv, int max_seq_len) {
+size_t kv_prefill_workspace_bytes(int T, int B, int Hq, int Hkv, int max_seq_len, int window) {
     int tiles, nc, chunk;
-    kv_prefill_split(T, B, Hq, Hkv, max_seq_len, &tiles, &nc, &chunk);
+    kv_prefill_split(T, B, Hq, Hkv, max_seq_len, window, &tiles, &nc, &chunk);
     return nc > 1 ? (size_t)tiles * Hkv * nc * ROWS * (HD + 2) * sizeof(float) : 0;
 }
 
-hipError_t launch_paged_prefill(const PagedKV &kv, const void *q, const int *qo_indptr, int T, int Hq, int max_seq_len, float sm_scale,
-                                void *ws, void *o, hipStream_t stream) {
+hipError_t launch_paged_prefill(const PagedKV &kv, const void *q, const int *qo_indptr, int T, int Hq, int max_seq_len, int window,
+                                float sm_scale, void *ws, void *o, hipStream_t stream) {
     PrefillArgs a;
     a.kv = kv;
     a.q = (const uint16_t *)q;
@@ -364,11 +384,15 @@ hipError_t launch_paged_prefill(const PagedKV &kv, const void *q, const int *qo_
     a.Hq = Hq;
     a.g = Hq / kv.Hkv;
     a.bq = ROWS / a.g;
-    kv_prefill_split(T, kv.B, Hq, kv.Hkv, max_seq_len, &a.tiles, &a.nc, &a.chunk);
+    kv_prefill_split(T, kv.B, Hq, kv.Hkv, max_seq_len, window, &a.tiles, &a.nc, &a.chunk);
     a.scale_log2 = kv_scale_log2(sm_scale);
+    a.window = window;
     const dim3 grid(a.tiles, kv.Hkv, a.nc);
-    if (kv.int4) paged_prefill_kernel<true><<<grid, NT, 0, stream>>>(a);
-    else paged_prefill_kernel<false><<<grid, NT, 0, stream>>>(a);
+    if (window > 0) {
+        if (kv.int4) paged_prefill_kernel<true, true><<<grid, NT, 0, stream>>>(a);
+        else paged_prefill_kernel<false, true><<<grid, NT, 0, stream>>>(a);
+    } else if (kv.int4) paged_prefill_kernel<true, false><<<grid, NT, 0, stream>>>(a);
+    else paged_prefill_kernel<false, false><<<grid, NT, 0, stream>>>(a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || a.nc == 1) return e;
     paged_prefill_merge_kernel<<<dim3(a.tiles, kv.Hkv), NT, 0, stream>>>(a);

@@ -264,11 +264,16 @@ inline float kv_scale_log2(float sm_scale) { return (sm_scale > 0.0f ? sm_scale 
 // split-KV chunks, from host-known values only, so a captured graph stays valid while the sequences grow up to max_seq_len: enough
 // chunks of `work` items to reach target_workgroups, of at least 256 tokens each, the chunk length a multiple of round_to
 void kv_chunks(long long work, int target_workgroups, int max_seq_len, int round_to, int *nc, int *chunk);
+// Sliding window (window >= 1; 0: none): a query attends its last `window` positions, itself included.  The kernels walk only the
+// tiles that hold them, and the chunks are laid over that span -- at most window + slack tokens, slack being what a kernel's range
+// gains by starting on a tile edge and by the query tile's rows (prefill; decode starts at the window itself: none) -- so the grid
+// still depends on host values only, and a window that reaches max_seq_len gives the split of no window
+int kv_window_span(int max_seq_len, int window, int slack);
 // append and single-token attention (kv_cache.hip)
-void kv_decode_split(int B, int Hkv, int max_seq_len, int *nc, int *chunk);
-size_t kv_decode_workspace_bytes(int B, int Hq, int Hkv, int max_seq_len);
+void kv_decode_split(int B, int Hkv, int max_seq_len, int window, int *nc, int *chunk);
+size_t kv_decode_workspace_bytes(int B, int Hq, int Hkv, int max_seq_len, int window);
 hipError_t launch_kv_append(const PagedKV &kv, const void *k, const void *v, const int *append_indptr, int T, hipStream_t stream);
-hipError_t launch_paged_decode(const PagedKV &kv, const void *q, int Hq, int max_seq_len, float sm_scale, void *ws, void *o,
+hipError_t launch_paged_decode(const PagedKV &kv, const void *q, int Hq, int max_seq_len, int window, float sm_scale, void *ws, void *o,
                                hipStream_t stream);
 // RoPE + append in one launch (rope_append.hip): q | k | v share the token stride qkv_stride, cos | sin the stride cs_stride (elements)
 hipError_t launch_rope_kv_append(const PagedKV &kv, const void *q, const void *k, const void *v, int64_t qkv_stride, int Hq, const void *cos,
@@ -280,9 +285,9 @@ hipError_t launch_moe_gather(const void *x, const int *sorted_token, int T, int 
 hipError_t launch_moe_combine(const void *y, const int *ids, const void *w, const int *slot_of, int T, int top_k, int H, void *out,
                               hipStream_t stream);
 // causal multi-token attention over the paged cache (kv_prefill.hip)
-void kv_prefill_split(int T, int B, int Hq, int Hkv, int max_seq_len, int *tiles, int *nc, int *chunk);
-size_t kv_prefill_workspace_bytes(int T, int B, int Hq, int Hkv, int max_seq_len);
-hipError_t launch_paged_prefill(const PagedKV &kv, const void *q, const int *qo_indptr, int T, int Hq, int max_seq_len, float sm_scale,
-                                void *ws, void *o, hipStream_t stream);
+void kv_prefill_split(int T, int B, int Hq, int Hkv, int max_seq_len, int window, int *tiles, int *nc, int *chunk);
+size_t kv_prefill_workspace_bytes(int T, int B, int Hq, int Hkv, int max_seq_len, int window);
+hipError_t launch_paged_prefill(const PagedKV &kv, const void *q, const int *qo_indptr, int T, int Hq, int max_seq_len, int window,
+                                float sm_scale, void *ws, void *o, hipStream_t stream);
 
 }  // namespace mm

@@ -75,6 +75,9 @@ __device__ inline bool k_row(const PagedKV &kv, const int *pages, int t, int end
     return ok;
 }
 
+// the first position of a window of W >= 1 tokens that ends at position p (HF's sliding_window: max(0, p - W + 1)); p >= -1
+__device__ inline int window_begin(int p, int W) { return p >= W ? p - W + 1 : 0; }
+
 // the K (which = 0) or V (which = 1) row of appended token i, head h; -1: nothing is written for this token
 __device__ inline int64_t append_row(const PagedKV &kv, const int *append_indptr, int i, int which, int h) {
     const int b = find_seq(append_indptr, kv.B, i);

@@ -15,7 +15,18 @@
 
 The page table lives in device tensors of fixed capacity that `extend` rewrites in place, so `append` + `attend` (or `attend_new`) captured once into a
 hipGraph replay correctly after later `extend` calls, as long as T stays the same and the sequences stay within the captured
-`max_seq_len`.  The allocator is a free list: no eviction, no prefix sharing.
+`max_seq_len`.  The allocator is a free list; no prefix sharing.
+
+    cache = PagedKVCache(..., window=4096)  # HF's sliding_window: a token attends the last 4096 positions, its own included
+
+With a window, `attend` / `attend_new` visit only the tiles that hold it, and `extend` evicts: every page whose positions all lie below
+what the announced tokens can attend -- below len_b - n_b - W + 1, len_b counting the n_b new tokens (for n_b = 0: below len_b - W, what
+a decode query at the last position attends) -- returns to the free list, and its entry in `kv_indices` becomes -1.  The entry stays, so
+positions, `seq_lens` and the append slots do not move; a sequence holds at most ceil((W + n_b) / P) + 1 pages, whatever its length,
+and a long chat costs the window, not the history.  Without a window nothing is evicted.  `release=False` keeps the pages (the mask
+alone), for callers who share pages between sequences.  The page table itself still grows by one entry per page_size tokens:
+`max_seq_len` sizes `kv_indices` for batch * ceil(max_seq_len / P) entries up front; past its capacity the tensor is replaced by a
+larger one, and a graph captured before that has to be captured again.
 """
 from __future__ import annotations
 
@@ -27,9 +38,13 @@ HEAD_DIM = 128
 
 
 class PagedKVCache:
-    def __init__(self, num_layers, num_kv_heads, page_size, max_pages, batch, kind="int4", device="cuda"):
+    def __init__(self, num_layers, num_kv_heads, page_size, max_pages, batch, kind="int4", device="cuda", window=None, release=True, max_seq_len=None):
         if kind not in ("int4", "bf16"):
             raise ValueError("kind must be 'int4' or 'bf16'")
+        self.window = 0 if window is None else int(window)
+        if self.window < 0:
+            raise ValueError("window must be None, 0 (no window) or a positive token count")
+        self.release = bool(release) and self.window > 0
         if min(num_layers, num_kv_heads, page_size, max_pages, batch) <= 0:
             raise ValueError("num_layers, num_kv_heads, page_size, max_pages and batch must be positive")
         dev = torch.device(device)
@@ -45,11 +60,13 @@ class PagedKVCache:
             self.kv_data = torch.zeros(shape + (HEAD_DIM,), dtype=torch.bfloat16, device=dev)
             self.kv_param = None
         self._free = list(range(max_pages - 1, -1, -1))        # pop() hands out low page numbers first
-        self._pages = [[] for _ in range(batch)]
+        self._pages = [[] for _ in range(batch)]                # -1: a page released below the window; its entry keeps its place
+        self._released = [0] * batch                            # leading entries of _pages[b] that are -1
         self.seq_lens = [0] * batch
         i32 = dict(dtype=torch.int32, device=dev)
         self.kv_indptr = torch.zeros((batch + 1,), **i32)
-        self.kv_indices = torch.zeros((max_pages,), **i32)     # capacity: every page, so the tensor never moves
+        # capacity: every page, so the tensor never moves -- unless released entries (which keep their place) outgrow it
+        self.kv_indices = torch.zeros((max(max_pages, batch * -(-int(max_seq_len or 0) // page_size)),), **i32)
         self.last_page_len = torch.zeros((batch,), **i32)
         self.append_indptr = torch.zeros((batch + 1,), **i32)
         self.num_new_tokens = 0
@@ -68,6 +85,9 @@ class PagedKVCache:
         for n in new:
             app.append(app[-1] + n)
         self.kv_indptr.copy_(torch.tensor(indptr, dtype=torch.int32))
+        if len(indices) > self.kv_indices.numel():
+            self._retired.append(self.kv_indices)          # a graph captured earlier may still point at it
+            self.kv_indices = torch.zeros((2 * len(indices),), dtype=torch.int32, device=self.device)
         if indices:
             self.kv_indices[: len(indices)].copy_(torch.tensor(indices, dtype=torch.int32))
         self.last_page_len.copy_(torch.tensor(last, dtype=torch.int32))
@@ -82,8 +102,17 @@ class PagedKVCache:
         if len(new) != self.batch or min(new) < 0:
             raise ValueError(f"need {self.batch} non-negative token counts")
         need = [-(-(self.seq_lens[b] + n) // self.page_size) - len(self._pages[b]) for b, n in enumerate(new)]
-        if sum(need) > len(self._free):
-            raise RuntimeError(f"out of pages: {sum(need)} needed, {len(self._free)} free")
+        # pages wholly below the lowest position the announced tokens attend (n = 0: a decode query at the last position)
+        drop = [max(self._released[b], min((self.seq_lens[b] + n - max(n, 1) - self.window + 1) // self.page_size, len(self._pages[b])))
+                if self.release else 0 for b, n in enumerate(new)]
+        freed = sum(drop[b] - self._released[b] for b in range(self.batch))
+        if sum(need) > len(self._free) + freed:
+            raise RuntimeError(f"out of pages: {sum(need)} needed, {len(self._free) + freed} free")
+        for b in range(self.batch):                              # releases first: another sequence's new tokens may take these pages
+            for i in range(self._released[b], drop[b]):
+                self._free.append(self._pages[b][i])
+                self._pages[b][i] = -1
+            self._released[b] = drop[b]
         for b, n in enumerate(new):
             self._pages[b] += [self._free.pop() for _ in range(need[b])]
             self.seq_lens[b] += n
@@ -91,8 +120,9 @@ class PagedKVCache:
 
     def reset(self, seq):
         """Empty sequence `seq` and return its pages to the free list (outside graph capture)."""
-        self._free += reversed(self._pages[seq])
+        self._free += [p for p in reversed(self._pages[seq]) if p >= 0]      # a released entry's page is in the list already
         self._pages[seq] = []
+        self._released[seq] = 0
         self.seq_lens[seq] = 0
         self._upload([0] * self.batch)
 
@@ -115,13 +145,13 @@ class PagedKVCache:
         """Decode attention of q (bf16 [B, Hq, 128]) over `layer`.  max_seq_len defaults to the longest sequence now (host
         bookkeeping, no device sync); under graph capture pass the bound the replays will stay within."""
         bound = max(self.seq_lens) if max_seq_len is None else int(max_seq_len)
-        need = mixedgemm.paged_decode_workspace_bytes(self.batch, q.size(1), self.num_kv_heads, bound)
+        need = mixedgemm.paged_decode_workspace_bytes(self.batch, q.size(1), self.num_kv_heads, bound, self.window)
         if need and (self._workspace is None or self._workspace.numel() < need):
             if self._workspace is not None:
                 self._retired.append(self._workspace)      # a graph captured earlier may still point at it
             self._workspace = torch.empty((need,), dtype=torch.uint8, device=self.device)
         return mixedgemm.paged_decode(q, self.kv_data, self.kv_param, self.kv_indptr, self.kv_indices, self.last_page_len, layer, bound,
-                                      sm_scale=sm_scale, workspace=self._workspace if need else None)
+                                      sm_scale=sm_scale, workspace=self._workspace if need else None, window=self.window)
 
     def attend_new(self, layer, q, max_seq_len=None, sm_scale=None):
         """Causal attention of the tokens the last `extend()` announced: q (bf16 [num_new_tokens, Hq, 128], sequence by sequence) over
@@ -130,11 +160,11 @@ class PagedKVCache:
         if q.dim() != 3 or q.size(0) != self.num_new_tokens:
             raise RuntimeError(f"attend_new expects the {self.num_new_tokens} tokens announced by extend(), got q of shape {tuple(q.shape)}")
         bound = max(self.seq_lens) if max_seq_len is None else int(max_seq_len)
-        need = mixedgemm.paged_prefill_workspace_bytes(self.num_new_tokens, self.batch, q.size(1), self.num_kv_heads, bound)
+        need = mixedgemm.paged_prefill_workspace_bytes(self.num_new_tokens, self.batch, q.size(1), self.num_kv_heads, bound, self.window)
         if need and (self._prefill_workspace is None or self._prefill_workspace.numel() < need):
             if self._prefill_workspace is not None:
                 self._retired.append(self._prefill_workspace)      # a graph captured earlier may still point at it
             self._prefill_workspace = torch.empty((need,), dtype=torch.uint8, device=self.device)
         return mixedgemm.paged_prefill(q, self.kv_data, self.kv_param, self.kv_indptr, self.kv_indices, self.last_page_len,
                                        self.append_indptr, layer, bound, sm_scale=sm_scale,
-                                       workspace=self._prefill_workspace if need else None)
+                                       workspace=self._prefill_workspace if need else None, window=self.window)

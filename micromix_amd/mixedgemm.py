@@ -1041,20 +1041,35 @@ def rope_kv_append(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, q, k
     return q_rot
 
 
-def paged_decode_workspace_bytes(B, Hq, Hkv, max_seq_len):
-    """bytes of fp32 scratch paged_decode needs for this bound (0: one launch, no workspace)"""
-    return int(_lib.load().mm_paged_decode_workspace_bytes(int(B), int(Hq), int(Hkv), int(max_seq_len)))
+def _window(window):
+    """HF's sliding_window as the C ABI takes it: None or 0 is no window (the un-windowed entry points), W >= 1 a window of W tokens"""
+    window = 0 if window is None else int(window)
+    if window < 0:
+        raise ValueError("window must be None, 0 (no window) or a positive token count")
+    return window
 
 
-def paged_decode(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, max_seq_len, sm_scale=None, workspace=None):
+def paged_decode_workspace_bytes(B, Hq, Hkv, max_seq_len, window=None):
+    """bytes of fp32 scratch paged_decode needs for this bound and window (0: one launch, no workspace)"""
+    window = _window(window)
+    if not window:
+        return int(_lib.load().mm_paged_decode_workspace_bytes(int(B), int(Hq), int(Hkv), int(max_seq_len)))
+    return int(_lib.load().mm_paged_decode_window_workspace_bytes(int(B), int(Hq), int(Hkv), int(max_seq_len), window))
+
+
+def paged_decode(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, max_seq_len, sm_scale=None, workspace=None, *,
+                 window=None):
     """Single-token GQA attention over layer `layer_idx` of a paged cache: q bf16 [B, Hq, 128] -> o bf16 [B, Hq, 128].
 
     Query head h reads kv head h // (Hq / Hkv) (HF repeat_kv), every cached token, softmax in fp32 with sm_scale (default 1/sqrt(128));
     a sequence of length 0 gives zeros.  `max_seq_len` bounds the sequence lengths; the split over the tokens depends on it (and B,
     Hq, Hkv) only, so a captured graph stays valid while the sequences grow up to it.  `workspace` (uint8 / any device tensor of at
     least paged_decode_workspace_bytes(...) bytes) is allocated here when None -- pass one when capturing a graph.
+    `window` = W (HF's sliding_window; None or 0: none): the query attends the last W tokens of its sequence, its own included.  Only
+    these tokens are read, the split is laid over W tokens, and page-table entries below the window may be -1.
     """
     lib = _lib.load()
+    window = _window(window)
     dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, q)
     if q.dim() != 3 or q.size(0) != B or q.size(2) != 128:
         raise RuntimeError(f"q must be [B = {B}, Hq, 128] bf16")
@@ -1064,24 +1079,31 @@ def paged_decode(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, lay
     max_seq_len = int(max_seq_len)
     if max_seq_len < 0:
         raise RuntimeError("max_seq_len must be >= 0")
-    need = paged_decode_workspace_bytes(B, Hq, Hkv, max_seq_len) if B else 0
+    need = paged_decode_workspace_bytes(B, Hq, Hkv, max_seq_len, window) if B else 0
     workspace, ws_args = _kv_workspace(workspace, need, dev)
     o = torch.empty((B, Hq, 128), dtype=torch.bfloat16, device=dev)
     scale = _sm_scale(sm_scale)
     with _on_device(dev.index):
-        st = lib.mm_paged_decode(_ptr(q), *kv_args, Hq, max_seq_len, scale, *ws_args, _ptr(o), _stream_ptr(dev))
+        if window:
+            st = lib.mm_paged_decode_window(_ptr(q), *kv_args, Hq, max_seq_len, scale, *ws_args, _ptr(o), _stream_ptr(dev), window)
+        else:
+            st = lib.mm_paged_decode(_ptr(q), *kv_args, Hq, max_seq_len, scale, *ws_args, _ptr(o), _stream_ptr(dev))
     if st:
         _lib.check(st, "paged_decode")
     return o
 
 
-def paged_prefill_workspace_bytes(T, B, Hq, Hkv, max_seq_len):
-    """bytes of fp32 scratch paged_prefill needs for T query tokens over B sequences within max_seq_len (0: one launch, no workspace)"""
-    return int(_lib.load().mm_paged_prefill_workspace_bytes(int(T), int(B), int(Hq), int(Hkv), int(max_seq_len)))
+def paged_prefill_workspace_bytes(T, B, Hq, Hkv, max_seq_len, window=None):
+    """bytes of fp32 scratch paged_prefill needs for T query tokens over B sequences within max_seq_len, under `window` (0: one launch,
+    no workspace)"""
+    window = _window(window)
+    if not window:
+        return int(_lib.load().mm_paged_prefill_workspace_bytes(int(T), int(B), int(Hq), int(Hkv), int(max_seq_len)))
+    return int(_lib.load().mm_paged_prefill_window_workspace_bytes(int(T), int(B), int(Hq), int(Hkv), int(max_seq_len), window))
 
 
 def paged_prefill(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, qo_indptr, layer_idx, max_seq_len, sm_scale=None,
-                  workspace=None):
+                  workspace=None, *, window=None):
     """Causal GQA attention of T new query tokens over layer `layer_idx` of a paged cache: q bf16 [T, Hq, 128] -> o bf16 [T, Hq, 128].
 
     qo_indptr (int32 [B + 1], qo_indptr[B] = T) splits the queries among the sequences, as kv_append's append_indptr does; pass the
@@ -1090,8 +1112,11 @@ def paged_prefill(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, qo
     `max_seq_len` bounds the sequence lengths; the grid and the split over the tokens depend on it (and T, B, Hq, Hkv) only, so a
     captured graph stays valid over later steps with the same T.  `workspace` (any contiguous device tensor of at least
     paged_prefill_workspace_bytes(...) bytes) is allocated here when None -- pass one when capturing a graph.
+    `window` = W (HF's sliding_window; None or 0: none): the token at position p attends positions max(0, p - W + 1) .. p; the kv tiles
+    below a query tile's windows are not read, and page-table entries below every window may be -1.
     """
     lib = _lib.load()
+    window = _window(window)
     dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, q)
     if not _ok(qo_indptr, torch.int32, dev.index):
         _check_tensor(qo_indptr, "qo_indptr", torch.int32, dev)
@@ -1105,12 +1130,16 @@ def paged_prefill(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, qo
     max_seq_len = int(max_seq_len)
     if max_seq_len < 0:
         raise RuntimeError("max_seq_len must be >= 0")
-    need = paged_prefill_workspace_bytes(T, B, Hq, Hkv, max_seq_len) if B and T else 0
+    need = paged_prefill_workspace_bytes(T, B, Hq, Hkv, max_seq_len, window) if B and T else 0
     workspace, ws_args = _kv_workspace(workspace, need, dev)
     o = torch.empty((T, Hq, 128), dtype=torch.bfloat16, device=dev)
     scale = _sm_scale(sm_scale)
     with _on_device(dev.index):
-        st = lib.mm_paged_prefill(_ptr(q), _ptr(qo_indptr), T, *kv_args, Hq, max_seq_len, scale, *ws_args, _ptr(o), _stream_ptr(dev))
+        if window:
+            st = lib.mm_paged_prefill_window(_ptr(q), _ptr(qo_indptr), T, *kv_args, Hq, max_seq_len, scale, *ws_args, _ptr(o),
+                                             _stream_ptr(dev), window)
+        else:
+            st = lib.mm_paged_prefill(_ptr(q), _ptr(qo_indptr), T, *kv_args, Hq, max_seq_len, scale, *ws_args, _ptr(o), _stream_ptr(dev))
     if st:
         _lib.check(st, "paged_prefill")
     return o
