@@ -2,15 +2,12 @@
 // workgroup quantizes the M <= 8 activation rows into LDS by itself -- reorder + per-32 absmax + UE8M0 scale + MXFP4/6/8 codes,
 // reorder.cu:94-269 per group, through the shared quantize_group of mx_group_convert.h: the bytes of reorder_quantize_x.
 #pragma once
+#include "mx_buffer_ops.h"   // MM_DEVICE_ONLY, wait_vmcnt<N>
 #include "mx_group_convert.h"
 #include "mx_direct_convert.h"
 #include "mx_rms_convert.h"
 
-#if defined(__HIP_DEVICE_COMPILE__)
-#define MM_DQ_SCHED_BARRIER() __builtin_amdgcn_sched_barrier(0)
-#else
-#define MM_DQ_SCHED_BARRIER() do { } while (0)
-#endif
+#define MM_DQ_SCHED_BARRIER() do { MM_DEVICE_ONLY(__builtin_amdgcn_sched_barrier(0);) } while (0)
 
 namespace mm {
 namespace dq {
@@ -389,15 +386,10 @@ __device__ __forceinline__ LdsMap quantize_rows_to_lds(const QuantIn &a, uint8_t
 // requested ~1 us earlier than from the hook of quantize_rows_to_lds, which has to wait for the staged rows first.
 // Preconditions (QuantIn::early, set by the launcher: early_fits): stage_rows >= M and at most NPASS (row, group, half) slots per thread,
 // 2 M K / 32 <= NPASS NT -- which bounds the rows at EARLY_RL and the norm's weight vector at EARLY_WL 16-byte chunks per thread and pass.
-#if defined(__HIP_DEVICE_COMPILE__)
-#define MM_DQ_DEVICE_ONLY(...) __VA_ARGS__
-#else
-#define MM_DQ_DEVICE_ONLY(...)
-#endif
 typedef unsigned dq_v4u __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ dq_v4u gload16(const void *p) {
     dq_v4u d = {0u, 0u, 0u, 0u};
-    MM_DQ_DEVICE_ONLY(asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(d) : "v"(p) : "memory");)
+    MM_DEVICE_ONLY(asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(d) : "v"(p) : "memory");)
     return d;
 }
 // NPASS: slots per thread.  1 on the eight-wave kernels, whose register count decides how many workgroups a CU holds; 2 on the four-wave
@@ -407,7 +399,7 @@ __device__ __forceinline__ dq_v4u gload16(const void *p) {
 template <int LO, int HI>
 __device__ __forceinline__ void wait_vmcnt_range(int n) {
     if constexpr (LO == HI) {
-        MM_DQ_DEVICE_ONLY(asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LO) : "memory");)
+        mm::wait_vmcnt<LO>();
     } else {
         constexpr int MID = (LO + HI) / 2;
         if (n <= MID) wait_vmcnt_range<LO, MID>(n);
@@ -484,18 +476,18 @@ __device__ __forceinline__ LdsMap quantize_rows_early(const QuantIn &a, uint8_t 
     // for every wave's.  Here this wave's loads are home and every other wave's have long been issued.
     landed();
 #pragma unroll
-    for (int p = 0; p < NPASS; ++p) { MM_DQ_DEVICE_ONLY(asm volatile("" : "+v"(iq[p][0]), "+v"(iq[p][1]));) }
+    for (int p = 0; p < NPASS; ++p) { MM_DEVICE_ONLY(asm volatile("" : "+v"(iq[p][0]), "+v"(iq[p][1]));) }
 #pragma unroll
-    for (int k = 0; k < RL; ++k) { MM_DQ_DEVICE_ONLY(asm volatile("" : "+v"(rq[k]));) }
+    for (int k = 0; k < RL; ++k) { MM_DEVICE_ONLY(asm volatile("" : "+v"(rq[k]));) }
     if constexpr (rms) {
 #pragma unroll
-        for (int k = 0; k < WL; ++k) { MM_DQ_DEVICE_ONLY(asm volatile("" : "+v"(wq[k]));) }
+        for (int k = 0; k < WL; ++k) { MM_DEVICE_ONLY(asm volatile("" : "+v"(wq[k]));) }
     }
     if constexpr (ADD) {      // rq becomes the sum: what is staged, what the partial sums below read, and -- from workgroup 0 -- S_out
         const bool writer = blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0;
 #pragma unroll
         for (int k = 0; k < RL; ++k) {
-            MM_DQ_DEVICE_ONLY(asm volatile("" : "+v"(rres[k]));)
+            MM_DEVICE_ONLY(asm volatile("" : "+v"(rres[k]));)
             const uint4 s = add_bf16x8(make_uint4(rq[k][0], rq[k][1], rq[k][2], rq[k][3]), make_uint4(rres[k][0], rres[k][1], rres[k][2], rres[k][3]));
             rq[k] = dq_v4u{s.x, s.y, s.z, s.w};
             const int c = row_chunk(k);
@@ -606,7 +598,7 @@ __device__ __forceinline__ LdsMap activate_rows_to_lds(const QuantIn &a, uint8_t
         }
         if (t == (int)threadIdx.x) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) { MM_DQ_DEVICE_ONLY(asm volatile("" : "+v"(xa[i].x), "+v"(xa[i].y), "+v"(xb[i].x), "+v"(xb[i].y));) }   // the loads have landed
+            for (int i = 0; i < 4; ++i) { MM_DEVICE_ONLY(asm volatile("" : "+v"(xa[i].x), "+v"(xa[i].y), "+v"(xb[i].x), "+v"(xb[i].y));) }   // the loads have landed
             request();
         }
         if (live) {
@@ -665,7 +657,7 @@ __device__ __forceinline__ LdsMap activate_rows_early(const QuantIn &a, uint8_t 
     // for every wave's.  Here this wave's loads are home and every other wave's have long been issued.
     landed();
 #pragma unroll
-    for (int i = 0; i < 4; ++i) { MM_DQ_DEVICE_ONLY(asm volatile("" : "+v"(qa[i]), "+v"(qb[i]));) }
+    for (int i = 0; i < 4; ++i) { MM_DEVICE_ONLY(asm volatile("" : "+v"(qa[i]), "+v"(qb[i]));) }
     if (live) {
         float v[32];
 #pragma unroll

@@ -22,19 +22,12 @@
 #define MM_CHAIN 1  // chained segment hand-over on the 256-row tile (mx_gemm_tile.inc); 0 = every segment's own prologue (A/B builds)
 #endif
 #include "mx_common.h"
+#include "mx_buffer_ops.h"   // MM_DEVICE_ONLY, make_rsrc / make_brsrc, lds_address, dma16: once, for every tile namespace
 #include "mx_direct_convert.h"
 #include "mx_group_convert.h"
 #include "mx_kernels.h"
 
 namespace mm {
-
-// hipcc parses __device__ bodies in its host pass as well; gfx950 inline asm and target builtins only exist in
-// the device pass, so those few bodies are compiled for the device only.
-#if defined(__HIP_DEVICE_COMPILE__)
-#define MM_DEVICE_ONLY(...) __VA_ARGS__
-#else
-#define MM_DEVICE_ONLY(...)
-#endif
 
 // in-kernel split-K (split_tile_reduce): scope of the ticket atomics and cache-policy bits of the partial-sum traffic
 #define MM_SPLIT_SCOPE __HIP_MEMORY_SCOPE_AGENT

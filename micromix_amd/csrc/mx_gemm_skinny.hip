@@ -15,50 +15,13 @@
 #include <stdlib.h>
 
 #include "mx_common.h"
+#include "mx_buffer_ops.h"   // make_brsrc, slab_bytes, load_frag / load_frag16: the operands' descriptors and MFMA fragments
 #include "mx_kernels.h"
 
 namespace mm {
 namespace skinny {
 
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-
 constexpr int NT = 512, NW = 8, BN = 32;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const uint8_t *base, unsigned bytes) {
-    const unsigned long long v = (unsigned long long)base;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v);
-    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    const unsigned nb = __builtin_amdgcn_readfirstlane(bytes);
-    return __builtin_amdgcn_make_buffer_rsrc((void *)(((unsigned long long)hi << 32) | lo), 0, (int)nb, 0x00020000);
-}
-
-template <int EL> struct G { static constexpr int BYTES = EL == EL_FP8 ? 128 : (EL == EL_FP6 ? 96 : 64); };
-
-// One lane's fragment for MFMA step h of slab `slab`: row byte offset `rowoff` inside the descriptor, kb = lane >> 5.
-// Register layouts as in mx_gemm256.hip (fp8: two 16-element halves; fp4/fp6: block 2h + kb).
-template <int EL>
-__device__ __forceinline__ v8i load_frag(__amdgpu_buffer_rsrc_t rsrc, int rowoff, int slab, int h, int kb) {
-    const int so = slab * G<EL>::BYTES;
-    v8i r = {0, 0, 0, 0, 0, 0, 0, 0};
-    if constexpr (EL == EL_FP8) {
-        const v4i lo = __builtin_amdgcn_raw_buffer_load_b128(rsrc, rowoff + (4 * h + kb) * 16, so, 0);
-        const v4i hi = __builtin_amdgcn_raw_buffer_load_b128(rsrc, rowoff + (4 * h + 2 + kb) * 16, so, 0);
-        r = v8i{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    } else if constexpr (EL == EL_FP4) {
-        const v4i v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, rowoff + (2 * h + kb) * 16, so, 0);
-        r = v8i{v[0], v[1], v[2], v[3], 0, 0, 0, 0};
-    } else {
-        typedef int v2i __attribute__((ext_vector_type(2)));
-        const int o = rowoff + (2 * h + kb) * 24;
-        const v2i a = __builtin_amdgcn_raw_buffer_load_b64(rsrc, o, so, 0);
-        const v2i b = __builtin_amdgcn_raw_buffer_load_b64(rsrc, o + 8, so, 0);
-        const v2i c = __builtin_amdgcn_raw_buffer_load_b64(rsrc, o + 16, so, 0);
-        r = v8i{a[0], a[1], b[0], b[1], c[0], c[1], 0, 0};
-    }
-    return r;
-}
 
 // One segment: this wave's share of the slabs (slab = wave, wave + 8, ...), accumulated into acc[TM].
 template <int XEL, int WEL, int TM>
@@ -66,13 +29,13 @@ __device__ __forceinline__ void run_segment(v16f (&acc)[TM], const uint8_t *X, c
                                             const uint8_t *SFW, int nslab, int M, int N, int n0, int sfx_tiles, int sfw_tiles) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int li = lane & 31, kb = lane >> 5;
-    const int xrb = nslab * G<XEL>::BYTES, wrb = nslab * G<WEL>::BYTES;
+    const int xrb = nslab * slab_bytes<XEL>, wrb = nslab * slab_bytes<WEL>;
     int wrows = N - n0;
     wrows = wrows > BN ? BN : wrows;
-    const __amdgpu_buffer_rsrc_t rx = make_rsrc(X, (unsigned)M * (unsigned)xrb);
-    const __amdgpu_buffer_rsrc_t rw = make_rsrc(W + (size_t)n0 * wrb, (unsigned)wrows * (unsigned)wrb);
-    const __amdgpu_buffer_rsrc_t rsx = make_rsrc(SFX, (unsigned)sfx_tiles * (unsigned)nslab * 512u);
-    const __amdgpu_buffer_rsrc_t rsw = make_rsrc(SFW, (unsigned)sfw_tiles * (unsigned)nslab * 512u);
+    const __amdgpu_buffer_rsrc_t rx = make_brsrc(X, (unsigned)M * (unsigned)xrb);
+    const __amdgpu_buffer_rsrc_t rw = make_brsrc(W + (size_t)n0 * wrb, (unsigned)wrows * (unsigned)wrb);
+    const __amdgpu_buffer_rsrc_t rsx = make_brsrc(SFX, (unsigned)sfx_tiles * (unsigned)nslab * 512u);
+    const __amdgpu_buffer_rsrc_t rsw = make_brsrc(SFW, (unsigned)sfw_tiles * (unsigned)nslab * 512u);
     // scale dword of (row, slab): atom (row >> 7, slab) + (row & 31) * 16 + ((row >> 5) & 3) * 4
     const int n = n0 + li;
     const int sfw_off = (n >> 7) * nslab * 512 + (n & 31) * 16 + ((n >> 5) & 3) * 4;
@@ -222,33 +185,10 @@ __device__ __forceinline__ void skinny_body(const GemmArgs &a) {
 // 16-feature variant (v_mfma_scale_f32_16x16x128_f8f6f4, one MFMA per slab and 16-token tile): twice the workgroups for the same N.
 // Used while N/32 workgroups would leave half of the CUs idle: a workgroup's weight stream is latency bound (~25 GB/s per CU),
 // so for N <= 4096 the extra workgroups nearly halve the time of the long-K layers (down_proj).
-// Register layouts (tests/test_hw_gpu.py): lane l = (row/col l & 15, K block h = l >> 4); fp4/fp6 lanes hold the 32 elements of
-// block h, fp8 lanes hold K = 16h + [0,16) and 64 + 16h + [0,16); the scale byte of a lane belongs to block h.
+// Register layouts: load_frag16 (mx_buffer_ops.h); lane l = (row/col l & 15, K block h = l >> 4), the scale byte of a lane belongs to
+// block h.
 // ---------------------------------------------------------------------------------------------------------
-typedef float v4f __attribute__((ext_vector_type(4)));
 constexpr int BN16 = 16;
-
-template <int EL>
-__device__ __forceinline__ v8i load_frag16(__amdgpu_buffer_rsrc_t rsrc, int rowoff, int slab, int h) {
-    const int so = slab * G<EL>::BYTES;
-    v8i r = {0, 0, 0, 0, 0, 0, 0, 0};
-    if constexpr (EL == EL_FP8) {
-        const v4i lo = __builtin_amdgcn_raw_buffer_load_b128(rsrc, rowoff + h * 16, so, 0);
-        const v4i hi = __builtin_amdgcn_raw_buffer_load_b128(rsrc, rowoff + 64 + h * 16, so, 0);
-        r = v8i{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    } else if constexpr (EL == EL_FP4) {
-        const v4i v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, rowoff + h * 16, so, 0);
-        r = v8i{v[0], v[1], v[2], v[3], 0, 0, 0, 0};
-    } else {
-        typedef int v2i __attribute__((ext_vector_type(2)));
-        const int o = rowoff + h * 24;
-        const v2i a = __builtin_amdgcn_raw_buffer_load_b64(rsrc, o, so, 0);
-        const v2i b = __builtin_amdgcn_raw_buffer_load_b64(rsrc, o + 8, so, 0);
-        const v2i c = __builtin_amdgcn_raw_buffer_load_b64(rsrc, o + 16, so, 0);
-        r = v8i{a[0], a[1], b[0], b[1], c[0], c[1], 0, 0};
-    }
-    return r;
-}
 
 // T16 token tiles of 16 rows each (M <= 16 * T16)
 template <int XEL, int WEL, int T16>
@@ -256,13 +196,13 @@ __device__ __forceinline__ void run_segment16(v4f (&acc)[T16], const uint8_t *X,
                                               const uint8_t *SFW, int nslab, int M, int N, int n0, int sfx_tiles, int sfw_tiles) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int li = lane & 15, h = lane >> 4;
-    const int xrb = nslab * G<XEL>::BYTES, wrb = nslab * G<WEL>::BYTES;
+    const int xrb = nslab * slab_bytes<XEL>, wrb = nslab * slab_bytes<WEL>;
     int wrows = N - n0;
     wrows = wrows > BN16 ? BN16 : wrows;
-    const __amdgpu_buffer_rsrc_t rx = make_rsrc(X, (unsigned)M * (unsigned)xrb);
-    const __amdgpu_buffer_rsrc_t rw = make_rsrc(W + (size_t)n0 * wrb, (unsigned)wrows * (unsigned)wrb);
-    const __amdgpu_buffer_rsrc_t rsx = make_rsrc(SFX, (unsigned)sfx_tiles * (unsigned)nslab * 512u);
-    const __amdgpu_buffer_rsrc_t rsw = make_rsrc(SFW, (unsigned)sfw_tiles * (unsigned)nslab * 512u);
+    const __amdgpu_buffer_rsrc_t rx = make_brsrc(X, (unsigned)M * (unsigned)xrb);
+    const __amdgpu_buffer_rsrc_t rw = make_brsrc(W + (size_t)n0 * wrb, (unsigned)wrows * (unsigned)wrb);
+    const __amdgpu_buffer_rsrc_t rsx = make_brsrc(SFX, (unsigned)sfx_tiles * (unsigned)nslab * 512u);
+    const __amdgpu_buffer_rsrc_t rsw = make_brsrc(SFW, (unsigned)sfw_tiles * (unsigned)nslab * 512u);
     const int n = n0 + li;
     const int sfw_off = (n >> 7) * nslab * 512 + (n & 31) * 16 + ((n >> 5) & 3) * 4;
     int sfx_off[T16];

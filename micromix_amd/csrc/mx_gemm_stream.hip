@@ -40,24 +40,12 @@
 #include <utility>
 
 #include "mx_common.h"
+#include "mx_buffer_ops.h"   // make_rsrc, lds_address, dma16: the descriptor and the ring's buffer_load_dwordx4 ... lds
 #include "mx_decode_quant.h"
 #include "mx_kernels.h"
 
 namespace mm {
 namespace stream {
-
-// hipcc parses __device__ bodies in its host pass as well; gfx950 inline asm only exists in the device pass
-#if defined(__HIP_DEVICE_COMPILE__)
-#define MM_DEVICE_ONLY(...) __VA_ARGS__
-#else
-#define MM_DEVICE_ONLY(...)
-#endif
-
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v2i __attribute__((ext_vector_type(2)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef int rsrc_t __attribute__((ext_vector_type(4)));
 
 // kernel-developer ablations (tools/build_one_variant.sh): 1 no activation loads, 2 no scale loads, 4 no MFMAs, 8 no reduction / store,
 // 16 no weight loads
@@ -72,33 +60,9 @@ typedef int rsrc_t __attribute__((ext_vector_type(4)));
 // launches without the quantization that take their scales from scale images (see stream_body): one token tile, and two with fp4 weights
 __host__ __device__ constexpr bool scale_images_for(int T16, bool W4) { return T16 == 1 || (T16 == 2 && W4); }
 
-// 128-bit raw buffer descriptor {base_lo, base_hi(16 bits) | stride 0, num_records (bytes), flags}, every word provably
-// wave-uniform so that it can be bound to an "s" operand
-__device__ __forceinline__ rsrc_t make_rsrc(const uint8_t *base, unsigned bytes) {
-    const unsigned long long v = (unsigned long long)base;
-    rsrc_t r;
-    r[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)v);
-    r[1] = __builtin_amdgcn_readfirstlane((int)((unsigned)(v >> 32) & 0xFFFFu));
-    r[2] = __builtin_amdgcn_readfirstlane((int)bytes);
-    r[3] = 0x00020000;
-    return r;
-}
-
-// LDS byte address of a pointer into the workgroup's LDS (the low half of the flat address; see mx_gemm_tile.inc)
-__device__ __forceinline__ unsigned lds_address(const uint8_t *p) { return (unsigned)(unsigned long long)p; }
-
-// one buffer_load_dwordx4 ... lds: 64 lanes x 16 B -> LDS bytes [lds, lds + 1024) in lane order; per-lane source = base + voff + soff
-// (s_nop 4: SALU results may not be read by a VMEM instruction for 5 states; s_nop 0: one state between the M0 write and the DMA).
-// (The same tiles through registers -- buffer_load_dwordx4 into a register ring, ds_write_b128 in lane order when a slab is consumed --
-// measured the same times at 118 instead of 53 VGPRs: profiles/r04_stream_ablation.txt, section 6.)
-__device__ __forceinline__ void dma16(const rsrc_t &rsrc, int voff, int soff, unsigned lds) {
-    MM_DEVICE_ONLY(unsigned keep;
-                   asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-                                "buffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
-                                : "=&s"(keep)
-                                : "v"(voff), "s"(rsrc), "s"(lds), "s"(soff)
-                                : "memory");)
-}
+// The ring's tiles go global -> LDS by dma16 (mx_buffer_ops.h).  (The same tiles through registers -- buffer_load_dwordx4 into a
+// register ring, ds_write_b128 in lane order when a slab is consumed -- measured the same times at 118 instead of 53 VGPRs:
+// profiles/r04_stream_ablation.txt, section 6.)
 // 8 bytes per lane into registers, NOT tracked by the compiler (the counted waits below order it).  Lane-contiguous on purpose:
 // the same 512 bytes as one dword per lane at a stride of 8 bytes cost the launch 1.5-2.3 us (profiles/r04_stream_ablation.txt).
 __device__ __forceinline__ v2i load_atom(const rsrc_t &rsrc, int voff, int soff) {
@@ -116,8 +80,7 @@ __device__ __forceinline__ void wait_slot(Slot &q) {     // at most N vector-mem
     MM_DEVICE_ONLY(asm volatile("s_waitcnt vmcnt(%2)" : "+v"(q.sw), "+v"(q.sx) : "n"(N) : "memory");)
 }
 
-typedef int v6i __attribute__((ext_vector_type(6)));
-template <int EL> struct Frag;                                    // the registers a lane holds of a 128-deep operand row
+template <int EL> struct Frag;                                  // the registers a lane holds of a 128-deep operand row
 template <> struct Frag<0> { typedef v4i type; static constexpr int HW = HW_FP4; };
 template <> struct Frag<1> { typedef v6i type; static constexpr int HW = HW_BF6; };
 template <> struct Frag<2> { typedef v8i type; static constexpr int HW = HW_FP8; };

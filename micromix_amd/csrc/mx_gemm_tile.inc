@@ -23,12 +23,9 @@ constexpr int NACC = 16 * TM * TN; // accumulator registers per lane: a[0 : NACC
 // them and leave them to the compiler (MFMA builtin), which then sees no asm-owned AGPRs and gives the kernel the whole
 // 256-register budget of a 512-thread workgroup -- and cannot allocate a temporary on top of an accumulator it does not know
 // about (it did, see tools/check_acc_regs.py).
-typedef float v16f_t __attribute__((ext_vector_type(16)));
-typedef int v8i_t __attribute__((ext_vector_type(8)));
-typedef int v4i_sel __attribute__((ext_vector_type(4)));
 struct Acc {
 #if MM_SMALL
-    v16f_t t[TM * TN];
+    v16f t[TM * TN];
 #endif
 };
 constexpr int X_TILE = BM * 128;   // bytes, sized for fp8 / padded fp6
@@ -41,7 +38,7 @@ constexpr int LDS_BUDGET = MM_LDS_BUDGET;
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
 #if !(MM_DBG & 2048)   // ablation 2048: no waits for the DMA
-    MM_DEVICE_ONLY(asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");)
+    mm::wait_vmcnt<N>();
 #endif
 }
 // workgroup barrier that does NOT drain the DMA queue (a __syncthreads() would add vmcnt(0))
@@ -253,7 +250,6 @@ struct AccLoop {
     // the same write-through 20.2 / 24.7 / 39.1, 16 bytes write-through 20.2 / 24.8 / 39.0 (profiles/notes_r03.md section 19).
     static __device__ __forceinline__ void store(float *p) {
         static_assert(I % 4 == 0 && N % 4 == 0, "four accumulator registers per store");
-        typedef float v4f __attribute__((ext_vector_type(4)));
         [[maybe_unused]] const v4f v = {acc_read<I>(), acc_read<I + 1>(), acc_read<I + 2>(), acc_read<I + 3>()};
         MM_DEVICE_ONLY(asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(p + (I / 4) * NT * 4), "v"(v) : "memory");)
         AccLoop<I + 4, N>::store(p);
@@ -274,54 +270,16 @@ struct AccLoop<N, N> {
 // prefetch queue once per K slab (measured: the loop then runs at DMA latency, ~47 % MFMA utilisation).  With asm
 // the compiler does not see the LDS writes; ordering is ours: counted s_waitcnt vmcnt(N), then the workgroup
 // barrier, then the reads (all asm statements carry a "memory" clobber).
-typedef int rsrc_t __attribute__((ext_vector_type(4)));
-
-// 128-bit raw buffer descriptor {base_lo, base_hi(16 bits) | stride 0, num_records (bytes), flags}, every word made
-// provably wave-uniform so that it can be bound to an "s" operand.
-__device__ __forceinline__ rsrc_t make_rsrc(const uint8_t *base, unsigned bytes) {
-    const unsigned long long v = (unsigned long long)base;
-    rsrc_t r;
-    r[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)v);
-    r[1] = __builtin_amdgcn_readfirstlane((int)((unsigned)(v >> 32) & 0xFFFFu));
-    r[2] = __builtin_amdgcn_readfirstlane((int)bytes);
-    r[3] = 0x00020000;
-    return r;
-}
-
-// one buffer_load_dwordx4 ... lds: 64 lanes x 16 B -> LDS bytes [lds_addr, lds_addr + 1024) (M0 = wave-uniform base,
-// the hardware adds lane * 16); per-lane source = descriptor base + voff + soff.
-//   s_nop 4 : SALU/readfirstlane results (descriptor, soffset) may not be read by a VMEM instruction for 5 states
-//   s_nop 0 : one state between the M0 write and the LDS-DMA that reads it
-// M0 belongs to the compiler, so it is saved and restored inside the statement.
+// The descriptors (make_rsrc for the DMA; make_brsrc, compiler-visible, for the loads into registers of the 4-wave tiles,
+// run_slabs_small), lds_address and the DMA instruction itself are mm::'s, mx_buffer_ops.h.  Here only the "no DMA" ablation:
 __device__ __forceinline__ void dma16(const rsrc_t &rsrc, int voff, int soff, unsigned lds_addr) {
 #if (MM_DBG & 2)
     MM_DEVICE_ONLY(asm volatile("" ::"v"(voff), "s"(rsrc), "s"(lds_addr), "s"(soff));)
-    return;
+#else
+    mm::dma16(rsrc, voff, soff, lds_addr);
 #endif
-    MM_DEVICE_ONLY(unsigned keep;
-                   asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-                                "buffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
-                                : "=&s"(keep)
-                                : "v"(voff), "s"(rsrc), "s"(lds_addr), "s"(soff)
-                                : "memory");)
-}
-
-// The same descriptor as a compiler-visible buffer resource, for loads into registers (the 4-wave tiles, run_slabs_small)
-typedef int v4i_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_brsrc(const uint8_t *base, unsigned bytes) {
-    const unsigned long long v = (unsigned long long)base;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc((void *)(((unsigned long long)hi << 32) | lo), 0,
-                                             (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
 }
 constexpr int OOB = 1 << 30;   // added to a lane's byte offset it puts the lane past any descriptor: the load returns zero (not for free)
-
-// LDS byte address of a generic pointer into the workgroup's LDS: the low half of the flat address (the aperture base sits in
-// the high half).  Written as a truncation, not as an address-space cast: the cast carries a null test that hipcc (ROCm 7.2)
-// lowers to an illegal V_CMP against src_shared_base when it cannot prove the pointer wave-uniform.
-__device__ __forceinline__ unsigned lds_address(const uint8_t *p) {
-    return (unsigned)(unsigned long long)p;
-}
 
 // One operand of one segment: descriptor over the tile's rows (rows past the matrix edge read as zero and their
 // outputs are masked) and the per-lane offset of DMA piece 0; piece `it` adds it * ROWS_PER_IT * rowbytes.
@@ -375,13 +333,13 @@ struct OperandDma {
     }
     // the same piece through registers: load<IT> now, store<IT> (same LDS bytes as the DMA would write) when it has arrived
     template <int IT>
-    __device__ __forceinline__ v4i_t load(int slab128, int oob) const {
+    __device__ __forceinline__ v4i load(int slab128, int oob) const {
         return __builtin_amdgcn_raw_buffer_load_b128(brsrc, voff0 + IT * ROWS_PER_IT * rowbytes + oob,
                                                      __builtin_amdgcn_readfirstlane(slab128 * g128), 0);
     }
     template <int IT>
-    __device__ __forceinline__ void store(const v4i_t &v, uint8_t *lds_tile) const {
-        *reinterpret_cast<v4i_t *>(lds_tile + (IT * NT + (threadIdx.x & (NT - 1))) * 16) = v;
+    __device__ __forceinline__ void store(const v4i &v, uint8_t *lds_tile) const {
+        *reinterpret_cast<v4i *>(lds_tile + (IT * NT + (threadIdx.x & (NT - 1))) * 16) = v;
     }
 };
 
@@ -417,12 +375,12 @@ struct SfDma {
               __builtin_amdgcn_readfirstlane(lds_address(lds_sf) + R * 1024));
     }
     template <int R>
-    __device__ __forceinline__ v4i_t load(int slab128, int oob) const {
+    __device__ __forceinline__ v4i load(int slab128, int oob) const {
         return __builtin_amdgcn_raw_buffer_load_b128(brsrc, voff[R] + oob, __builtin_amdgcn_readfirstlane(slab128 * 512), 0);
     }
     template <int R>
-    __device__ __forceinline__ void store(const v4i_t &v, uint8_t *lds_sf) const {
-        *reinterpret_cast<v4i_t *>(lds_sf + R * 1024 + (threadIdx.x & 63) * 16) = v;
+    __device__ __forceinline__ void store(const v4i &v, uint8_t *lds_sf) const {
+        *reinterpret_cast<v4i *>(lds_sf + R * 1024 + (threadIdx.x & 63) * 16) = v;
     }
 };
 
@@ -550,7 +508,7 @@ struct SlabDmaT {
     // the register path of the 4-wave tiles: piece P of slab `slab` (zeros when the slab is past `count`; callers do not ask).
     // Every loader wave carries a scale piece (dealt by wave & 1 / wave & 3; with four loader waves the 128-deep geometry repeats each).
     template <int P>
-    __device__ __forceinline__ v4i_t load(int slab, int count) const {
+    __device__ __forceinline__ v4i load(int slab, int count) const {
         const int u = unit(slab), oob = slab < count ? 0 : OOB;
         if constexpr (P < XP) {
             return x.template load<P>(u, oob);
@@ -565,7 +523,7 @@ struct SlabDmaT {
         }
     }
     template <int P>
-    __device__ __forceinline__ void store(const v4i_t &v, uint8_t *stage) const {
+    __device__ __forceinline__ void store(const v4i &v, uint8_t *stage) const {
         if constexpr (P < XP) {
             x.template store<P>(v, stage);
         } else if constexpr (P < XP + WP) {
@@ -742,10 +700,10 @@ __device__ __forceinline__ void read_slab(SlabRegs<G> &r, const uint8_t *st, con
     }
 }
 template <int EL>
-__device__ __forceinline__ v8i_t widen_frag(const typename Frag<EL>::type &f) {
-    if constexpr (EL == EL_FP8) return v8i_t{f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7]};
-    else if constexpr (EL == EL_FP6) return v8i_t{f[0], f[1], f[2], f[3], f[4], f[5], 0, 0};
-    else return v8i_t{f[0], f[1], f[2], f[3], 0, 0, 0, 0};
+__device__ __forceinline__ v8i widen_frag(const typename Frag<EL>::type &f) {
+    if constexpr (EL == EL_FP8) return v8i{f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7]};
+    else if constexpr (EL == EL_FP6) return v8i{f[0], f[1], f[2], f[3], f[4], f[5], 0, 0};
+    else return v8i{f[0], f[1], f[2], f[3], 0, 0, 0, 0};
 }
 // the MFMAs of one slab on compiler-owned accumulators (4-wave tiles).  Scale bytes as in mfma_tile: the lane's scale dword is
 // already shifted by 8 * kb, step H takes byte 2 * (H & 1) of the 128-deep unit H >> 1.
@@ -768,7 +726,7 @@ __device__ __forceinline__ void mfma_slab(Acc &acc, const SlabRegs<G> &r) {
 }
 template <class G>
 struct SlabSlot {
-    v4i_t q[SlabDma<G>::NPIECES];
+    v4i q[SlabDma<G>::NPIECES];
     template <int P = 0>
     __device__ __forceinline__ void load(const SlabDma<G> &dma, int slab, int count) {
         if constexpr (P < SlabDma<G>::NPIECES) {
@@ -1921,7 +1879,7 @@ __device__ __forceinline__ void split_tile_reduce(const GemmArgs &a, const int b
             for (int t = 0; t < NF; ++t)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    const v4i_t v = {__float_as_int(acc.t[t][4 * g]), __float_as_int(acc.t[t][4 * g + 1]),
+                    const v4i v = {__float_as_int(acc.t[t][4 * g]), __float_as_int(acc.t[t][4 * g + 1]),
                                      __float_as_int(acc.t[t][4 * g + 2]), __float_as_int(acc.t[t][4 * g + 3])};
                     __builtin_amdgcn_raw_buffer_store_b128(v, rs, tofs + (4 * t + g) * (NT * 16), soff, AUX_SC);
                 }
@@ -2010,7 +1968,7 @@ __device__ __forceinline__ void split_tile_reduce(const GemmArgs &a, const int b
     };
     int cur_seg = (int)(a.slot_seg & 3ull);
     for (int sb = 0; sb < nslots; sb += B) {
-        v4i_t v[B][CHUNKS];
+        v4i v[B][CHUNKS];
 #pragma unroll
         for (int b = 0; b < B; ++b)
             if (sb + b < nslots) {

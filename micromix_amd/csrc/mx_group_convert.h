@@ -1,6 +1,7 @@
 // Shared by the quantizer kernels: one 32-element group (two bf16 per register) -> packed MX codes.
 #pragma once
 #include "mx_common.h"
+#include "mx_buffer_ops.h"   // MM_DEVICE_ONLY
 
 namespace mm {
 
@@ -13,9 +14,7 @@ typedef unsigned u6 __attribute__((ext_vector_type(6)));
 // two fp32 -> packed bf16 pair {lo, hi}, round to nearest even (v_cvt_pk_bf16_f32)
 __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
     uint32_t r = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-#endif
+    MM_DEVICE_ONLY(asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));)
     return r;
 }
 

@@ -18,52 +18,17 @@
 #include <type_traits>
 #include <utility>
 
+#include "mx_buffer_ops.h"   // make_brsrc / make_rsrc, slab_bytes, load_frag / load_frag16 (the weights' fragments), wait_vmcnt
 #include "mx_decode_quant.h"
 #include "mx_kernels.h"
 
 namespace mm {
 namespace decode {
 
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v2i __attribute__((ext_vector_type(2)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-
 constexpr int NT = 512, NW = 8, BN = 32;
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const uint8_t *base, unsigned bytes) {
-    const unsigned long long v = (unsigned long long)base;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v);
-    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    const unsigned nb = __builtin_amdgcn_readfirstlane(bytes);
-    return __builtin_amdgcn_make_buffer_rsrc((void *)(((unsigned long long)hi << 32) | lo), 0, (int)nb, 0x00020000);
-}
-
-template <int EL> struct G { static constexpr int BYTES = EL == EL_FP8 ? 128 : (EL == EL_FP6 ? 96 : 64); };
-
-// weight fragment from global memory (as mx_gemm_skinny.hip)
-template <int EL>
-__device__ __forceinline__ v8i load_wfrag(__amdgpu_buffer_rsrc_t rsrc, int rowoff, int slab, int h, int kb) {
-    const int so = slab * G<EL>::BYTES;
-    v8i r = {0, 0, 0, 0, 0, 0, 0, 0};
-    if constexpr (EL == EL_FP8) {
-        const v4i lo = __builtin_amdgcn_raw_buffer_load_b128(rsrc, rowoff + (4 * h + kb) * 16, so, 0);
-        const v4i hi = __builtin_amdgcn_raw_buffer_load_b128(rsrc, rowoff + (4 * h + 2 + kb) * 16, so, 0);
-        r = v8i{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    } else if constexpr (EL == EL_FP4) {
-        const v4i v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, rowoff + (2 * h + kb) * 16, so, 0);
-        r = v8i{v[0], v[1], v[2], v[3], 0, 0, 0, 0};
-    } else {
-        const int o = rowoff + (2 * h + kb) * 24;
-        const v2i a = __builtin_amdgcn_raw_buffer_load_b64(rsrc, o, so, 0);
-        const v2i b = __builtin_amdgcn_raw_buffer_load_b64(rsrc, o + 8, so, 0);
-        const v2i c = __builtin_amdgcn_raw_buffer_load_b64(rsrc, o + 16, so, 0);
-        r = v8i{a[0], a[1], b[0], b[1], c[0], c[1], 0, 0};
-    }
-    return r;
-}
-
-// activation fragment from the LDS copy of the quantized row (`p` = row base + slab * BYTES); same register layouts
+// activation fragment from the LDS copy of the quantized row (`p` = row base + slab * slab_bytes): the LDS-side twin of load_frag
+// (mx_buffer_ops.h), same register layouts
 template <int EL>
 __device__ __forceinline__ v8i lds_xfrag(const uint8_t *p, int h, int kb) {
     v8i r = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -109,11 +74,11 @@ __device__ __forceinline__ void run_segment(v16f &acc, const uint8_t *xl, int xp
                                             const uint8_t *SFW, int nslab, int M, int N, int n0, int sfw_tiles, int r0 = 0) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int li = lane & 31, kb = lane >> 5;
-    const int wrb = nslab * G<WEL>::BYTES;
+    const int wrb = nslab * slab_bytes<WEL>;
     int wrows = N - n0;
     wrows = wrows > BN ? BN : wrows;
-    const __amdgpu_buffer_rsrc_t rw = make_rsrc(W + (size_t)n0 * wrb, (unsigned)wrows * (unsigned)wrb);
-    const __amdgpu_buffer_rsrc_t rsw = make_rsrc(SFW, (unsigned)sfw_tiles * (unsigned)nslab * 512u);
+    const __amdgpu_buffer_rsrc_t rw = make_brsrc(W + (size_t)n0 * wrb, (unsigned)wrows * (unsigned)wrb);
+    const __amdgpu_buffer_rsrc_t rsw = make_brsrc(SFW, (unsigned)sfw_tiles * (unsigned)nslab * 512u);
     const int n = n0 + li;
     const int sfw_off = (n >> 7) * nslab * 512 + (n & 31) * 16 + ((n >> 5) & 3) * 4;
     const bool valid = li < M;   // MFMA rows = tokens; rows past M are zero
@@ -132,7 +97,7 @@ __device__ __forceinline__ void run_segment(v16f &acc, const uint8_t *xl, int xp
             if (s < nslab) {
                 swr[j] = __builtin_amdgcn_raw_buffer_load_b32(rsw, sfw_off, s * 512, 0);
 #pragma unroll
-                for (int h = 0; h < 2; ++h) wf[j][h] = load_wfrag<WEL>(rw, li * wrb, s, h, kb);
+                for (int h = 0; h < 2; ++h) wf[j][h] = load_frag<WEL>(rw, li * wrb, s, h, kb);
             }
         }
 #pragma unroll
@@ -147,7 +112,7 @@ __device__ __forceinline__ void run_segment(v16f &acc, const uint8_t *xl, int xp
                 if (valid) {
                     sx = (int)(*reinterpret_cast<const uint32_t *>(srow + 4 * s) >> sh);
 #pragma unroll
-                    for (int h = 0; h < 2; ++h) xf[h] = lds_xfrag<XEL>(xrow + s * G<XEL>::BYTES, h, kb);
+                    for (int h = 0; h < 2; ++h) xf[h] = lds_xfrag<XEL>(xrow + s * slab_bytes<XEL>, h, kb);
                 }
                 acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(xf[0], wf[j][0], acc, ElemTraits<XEL>::HW, ElemTraits<WEL>::HW, 0, sx, 0, sw);
                 acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(xf[1], wf[j][1], acc, ElemTraits<XEL>::HW, ElemTraits<WEL>::HW, 2, sx, 2, sw);
@@ -172,29 +137,14 @@ __device__ __forceinline__ void run_segment(v16f &acc, const uint8_t *xl, int xp
 //   Per segment the first PRE_R rounds (slabs w and w + 8 of wave w): at K = 4096 that is every slab of every split; a slab that does
 //   not exist for this wave requests nothing.
 // ---------------------------------------------------------------------------------------------------------
-typedef int rsrc4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ rsrc4_t make_rsrc4(const uint8_t *base, unsigned bytes) {
-    const unsigned long long v = (unsigned long long)base;
-    rsrc4_t r;
-    r[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)v);
-    r[1] = __builtin_amdgcn_readfirstlane((int)((unsigned)(v >> 32) & 0xFFFFu));
-    r[2] = __builtin_amdgcn_readfirstlane((int)bytes);
-    r[3] = 0x00020000;
-    return r;
-}
-#if defined(__HIP_DEVICE_COMPILE__)
-#define MM_QD_DEVICE_ONLY(...) __VA_ARGS__
-#else
-#define MM_QD_DEVICE_ONLY(...)
-#endif
-// (s_nop 4: SALU / readfirstlane results may not be read by a VMEM instruction for five wait states)
+// (the requests go through the raw descriptor, make_rsrc; s_nop 4: SALU / readfirstlane results may not be read by a VMEM instruction for five wait states)
 // `d` is read-write ("+v"): the destination IS the register that holds the caller's zero when the request is skipped (a wave-uniform
 // branch around the statement), so no copy of a pending register is ever needed where the two paths meet
-__device__ __forceinline__ void asm_load16(v4i &d, const rsrc4_t &rs, int voff, int soff) {
-    MM_QD_DEVICE_ONLY(asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %1, %2, %3 offen" : "+v"(d) : "v"(voff), "s"(rs), "s"(soff) : "memory");)
+__device__ __forceinline__ void asm_load16(v4i &d, const rsrc_t &rs, int voff, int soff) {
+    MM_DEVICE_ONLY(asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %1, %2, %3 offen" : "+v"(d) : "v"(voff), "s"(rs), "s"(soff) : "memory");)
 }
-__device__ __forceinline__ void asm_load4(int &d, const rsrc4_t &rs, int voff, int soff) {
-    MM_QD_DEVICE_ONLY(asm volatile("s_nop 4\n\tbuffer_load_dword %0, %1, %2, %3 offen" : "+v"(d) : "v"(voff), "s"(rs), "s"(soff) : "memory");)
+__device__ __forceinline__ void asm_load4(int &d, const rsrc_t &rs, int voff, int soff) {
+    MM_DEVICE_ONLY(asm volatile("s_nop 4\n\tbuffer_load_dword %0, %1, %2, %3 offen" : "+v"(d) : "v"(voff), "s"(rs), "s"(soff) : "memory");)
 }
 constexpr int PRE_R = 2;                // rounds of a segment (slabs w, w + 8 of wave w) that travel under the quantization phase
 template <int FEAT> struct PreSlab;     // the registers one request fills
@@ -222,8 +172,8 @@ struct SegPrefetch {
         int wrows = N - n0;
         wrows = wrows > FEAT ? FEAT : wrows;
         const int n = n0 + li, wrb = nslab * 64;
-        const rsrc4_t rw = make_rsrc4(W + (size_t)n0 * wrb, (unsigned)wrows * (unsigned)wrb);
-        const rsrc4_t rs = make_rsrc4(SFW, (unsigned)sfw_tiles * (unsigned)nslab * 512u);
+        const rsrc_t rw = make_rsrc(W + (size_t)n0 * wrb, (unsigned)wrows * (unsigned)wrb);
+        const rsrc_t rs = make_rsrc(SFW, (unsigned)sfw_tiles * (unsigned)nslab * 512u);
         const int sfw_off = (n >> 7) * nslab * 512 + (n & 31) * 16 + ((n >> 5) & 3) * 4;
         const int woff = li * wrb + hb * 16;
 #pragma unroll
@@ -240,12 +190,11 @@ struct SegPrefetch {
     __device__ __forceinline__ void landed() {
 #pragma unroll
         for (int j = 0; j < PRE_R; ++j) {
-            MM_QD_DEVICE_ONLY(asm volatile("" : "+v"(q[j].sw), "+v"(q[j].w[0]));)
-            if constexpr (FEAT == 32) { MM_QD_DEVICE_ONLY(asm volatile("" : "+v"(q[j].w[1]));) }
+            MM_DEVICE_ONLY(asm volatile("" : "+v"(q[j].sw), "+v"(q[j].w[0]));)
+            if constexpr (FEAT == 32) { MM_DEVICE_ONLY(asm volatile("" : "+v"(q[j].w[1]));) }
         }
     }
 };
-__device__ __forceinline__ void wait_all_loads() { MM_QD_DEVICE_ONLY(asm volatile("s_waitcnt vmcnt(0)" ::: "memory");) }
 
 using dq::LdsMap;
 template <bool RMS, int LPG, bool ADD>
@@ -308,7 +257,7 @@ __global__ void __launch_bounds__(NT) qlinear_decode_kernel(Args a) {
         int r0 = 0;
         if constexpr (PF) {
             if (n0 == (int)blockIdx.x * BN) {        // the block whose first slabs were requested under the quantization
-                wait_all_loads();
+                wait_vmcnt<0>();
                 pfN.landed(); pfS.landed(); pfO.landed();
                 const int wv = __builtin_amdgcn_readfirstlane(wave), li = lane & 31, kb = lane >> 5, sh = 8 * kb;
                 const bool valid = li < a.M;
@@ -327,7 +276,7 @@ __global__ void __launch_bounds__(NT) qlinear_decode_kernel(Args a) {
                             if (valid) {
                                 sx = (int)(*reinterpret_cast<const uint32_t *>(sl + rr * Gt + 4 * s) >> sh);
 #pragma unroll
-                                for (int h = 0; h < 2; ++h) xf[h] = lds_xfrag<XEL>(xl + rr * xp + s * G<XEL>::BYTES, h, kb);
+                                for (int h = 0; h < 2; ++h) xf[h] = lds_xfrag<XEL>(xl + rr * xp + s * slab_bytes<XEL>, h, kb);
                             }
                             const int sw = pf.q[j].sw >> sh;
                             const v4i a0 = pf.q[j].w[0], a1 = pf.q[j].w[1];
@@ -386,33 +335,12 @@ __global__ void __launch_bounds__(NT) qlinear_decode_kernel(Args a) {
 // 16-feature variant (v_mfma_scale_f32_16x16x128_f8f6f4: one MFMA per 128-deep slab, tokens on 16 rows): twice the workgroups
 // for the same N.  Used while N/32 workgroups would leave half of the CUs idle (N <= 4096 on 256 CUs), where a workgroup's
 // weight stream is latency bound (~25 GB/s per CU): down_proj at M = 1 14.8 -> ~10 us.
-// Register layouts (tests/test_hw_gpu.py): lane l = (row/col l & 15, K block h = l >> 4); fp4/fp6 lanes hold the 32 elements of
-// block h, fp8 lanes hold K = 16h + [0,16) and 64 + 16h + [0,16); the scale byte of a lane belongs to block h.
+// Register layouts: load_frag16 (mx_buffer_ops.h); lane l = (row/col l & 15, K block h = l >> 4), the scale byte of a lane belongs to
+// block h.
 // ---------------------------------------------------------------------------------------------------------
-typedef float v4f __attribute__((ext_vector_type(4)));
 constexpr int BN16 = 16;
 
-template <int EL>
-__device__ __forceinline__ v8i load_wfrag16(__amdgpu_buffer_rsrc_t rsrc, int rowoff, int slab, int h) {
-    const int so = slab * G<EL>::BYTES;
-    v8i r = {0, 0, 0, 0, 0, 0, 0, 0};
-    if constexpr (EL == EL_FP8) {
-        const v4i lo = __builtin_amdgcn_raw_buffer_load_b128(rsrc, rowoff + h * 16, so, 0);
-        const v4i hi = __builtin_amdgcn_raw_buffer_load_b128(rsrc, rowoff + 64 + h * 16, so, 0);
-        r = v8i{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    } else if constexpr (EL == EL_FP4) {
-        const v4i v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, rowoff + h * 16, so, 0);
-        r = v8i{v[0], v[1], v[2], v[3], 0, 0, 0, 0};
-    } else {
-        const int o = rowoff + h * 24;
-        const v2i a = __builtin_amdgcn_raw_buffer_load_b64(rsrc, o, so, 0);
-        const v2i b = __builtin_amdgcn_raw_buffer_load_b64(rsrc, o + 8, so, 0);
-        const v2i c = __builtin_amdgcn_raw_buffer_load_b64(rsrc, o + 16, so, 0);
-        r = v8i{a[0], a[1], b[0], b[1], c[0], c[1], 0, 0};
-    }
-    return r;
-}
-
+// the LDS-side twin of load_frag16
 template <int EL>
 __device__ __forceinline__ v8i lds_xfrag16(const uint8_t *p, int h) {
     v8i r = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -436,11 +364,11 @@ __device__ __forceinline__ void run_segment16(v4f &acc, const uint8_t *xl, int x
                                               const uint8_t *SFW, int nslab, int M, int N, int n0, int sfw_tiles, int r0 = 0) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int li = lane & 15, h = lane >> 4;
-    const int wrb = nslab * G<WEL>::BYTES;
+    const int wrb = nslab * slab_bytes<WEL>;
     int wrows = N - n0;
     wrows = wrows > BN16 ? BN16 : wrows;
-    const __amdgpu_buffer_rsrc_t rw = make_rsrc(W + (size_t)n0 * wrb, (unsigned)wrows * (unsigned)wrb);
-    const __amdgpu_buffer_rsrc_t rsw = make_rsrc(SFW, (unsigned)sfw_tiles * (unsigned)nslab * 512u);
+    const __amdgpu_buffer_rsrc_t rw = make_brsrc(W + (size_t)n0 * wrb, (unsigned)wrows * (unsigned)wrb);
+    const __amdgpu_buffer_rsrc_t rsw = make_brsrc(SFW, (unsigned)sfw_tiles * (unsigned)nslab * 512u);
     const int n = n0 + li;
     const int sfw_off = (n >> 7) * nslab * 512 + (n & 31) * 16 + ((n >> 5) & 3) * 4;
     const bool valid = li < M;
@@ -456,7 +384,7 @@ __device__ __forceinline__ void run_segment16(v4f &acc, const uint8_t *xl, int x
             const int s = s0 + j * NW;
             if (s < nslab) {
                 swr[j] = __builtin_amdgcn_raw_buffer_load_b32(rsw, sfw_off, s * 512, 0);
-                wf[j] = load_wfrag16<WEL>(rw, li * wrb, s, h);
+                wf[j] = load_frag16<WEL>(rw, li * wrb, s, h);
             }
         }
 #pragma unroll
@@ -467,7 +395,7 @@ __device__ __forceinline__ void run_segment16(v4f &acc, const uint8_t *xl, int x
                 v8i xf = {0, 0, 0, 0, 0, 0, 0, 0};
                 if (valid) {
                     sx = (int)(*reinterpret_cast<const uint32_t *>(srow + 4 * s) >> sh);
-                    xf = lds_xfrag16<XEL>(xrow + s * G<XEL>::BYTES, h);
+                    xf = lds_xfrag16<XEL>(xrow + s * slab_bytes<XEL>, h);
                 }
                 acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(xf, wf[j], acc, ElemTraits<XEL>::HW, ElemTraits<WEL>::HW, 0, sx, 0,
                                                                        swr[j] >> sh);
@@ -499,7 +427,7 @@ __global__ void __launch_bounds__(NT) qlinear_decode16_kernel(Args a) {
     v4f accN = {0, 0, 0, 0}, accS = {0, 0, 0, 0}, accO = {0, 0, 0, 0};
     int r0 = 0;
     if constexpr (PF) {
-        wait_all_loads();
+        wait_vmcnt<0>();
         pfN.landed(); pfS.landed(); pfO.landed();
         const int wv = __builtin_amdgcn_readfirstlane(wave), li = lane & 15, h = lane >> 4, sh = 8 * h;
         const bool valid = li < a.M;
@@ -515,7 +443,7 @@ __global__ void __launch_bounds__(NT) qlinear_decode16_kernel(Args a) {
                     v8i xf = {0, 0, 0, 0, 0, 0, 0, 0};
                     if (valid) {
                         sx = (int)(*reinterpret_cast<const uint32_t *>(sl + rr * L.Gt + 4 * s) >> sh);
-                        xf = lds_xfrag16<XEL>(xl + rr * xp + s * G<XEL>::BYTES, h);
+                        xf = lds_xfrag16<XEL>(xl + rr * xp + s * slab_bytes<XEL>, h);
                     }
                     const v4i a0 = pf.q[j].w[0];
                     const v8i w0 = {a0[0], a0[1], a0[2], a0[3], 0, 0, 0, 0};

@@ -27,15 +27,12 @@
 //   of K = 32768 would not fit the LDS).
 #include <stdlib.h>
 
+#include "mx_buffer_ops.h"   // MM_DEVICE_ONLY; make_rsrc, dma16, wait_vmcnt: the ring kernel's LDS-DMA
 #include "mx_group_convert.h"
 #include "mx_rms_convert.h"
 #include "mx_kernels.h"
 
-#if defined(__HIP_DEVICE_COMPILE__)
-#define MM_RMS_SCHED_BARRIER() __builtin_amdgcn_sched_barrier(0)
-#else
-#define MM_RMS_SCHED_BARRIER() do { } while (0)
-#endif
+#define MM_RMS_SCHED_BARRIER() do { MM_DEVICE_ONLY(__builtin_amdgcn_sched_barrier(0);) } while (0)
 
 namespace mm {
 
@@ -395,36 +392,8 @@ rmsnorm_quantize_products_kernel(const uint16_t *__restrict__ src, const uint16_
 // piece per step, when a wave issues both stores) travel on.  When the next row does not exist nothing was issued for it: vmcnt(0).
 // Every wave issues exactly four DMAs per row (rows of K <= 8192 are at most 16 pieces on at most 4 waves); a piece past the row's
 // end lies past the descriptor's range, fetches nothing and lands in a dump area of its own.
+// The descriptor, the DMA instruction and the counted wait are make_rsrc, dma16 and wait_vmcnt<N> of mx_buffer_ops.h.
 // ---------------------------------------------------------------------------------------------------------
-typedef int rms_rsrc_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ rms_rsrc_t rms_make_rsrc(const void *base, unsigned bytes) {
-    const unsigned long long v = (unsigned long long)base;
-    rms_rsrc_t r;
-    r[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)v);
-    r[1] = __builtin_amdgcn_readfirstlane((int)((unsigned)(v >> 32) & 0xFFFFu));
-    r[2] = __builtin_amdgcn_readfirstlane((int)bytes);
-    r[3] = 0x00020000;
-    return r;
-}
-// one buffer_load_dwordx4 ... lds: 64 lanes x 16 B -> LDS bytes [lds, lds + 1024) in lane order (M0 = wave-uniform base; the compiler
-// owns M0, so it is saved and restored; s_nop 4 / 0: SALU -> VMEM and M0 -> LDS-DMA wait states)
-__device__ __forceinline__ void rms_dma16(const rms_rsrc_t &rsrc, int voff, int soff, unsigned lds) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    unsigned keep;
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-                 "buffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(rsrc), "s"(lds), "s"(soff)
-                 : "memory");
-#endif
-}
-template <int N>
-__device__ __forceinline__ void rms_wait_vmcnt() {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-#endif
-}
-
 template <bool INT_ROUND, int R>
 __global__ void __launch_bounds__(256)
 rmsnorm_quantize_ring_kernel(const uint16_t *__restrict__ src, const uint16_t *__restrict__ weight, float eps, int rows, int K,
@@ -455,12 +424,12 @@ rmsnorm_quantize_ring_kernel(const uint16_t *__restrict__ src, const uint16_t *_
     // rows r0, r0 + stride, ...: DMA of the n-th of them into slot n % R
     const int stride = (int)gridDim.x;
     auto issue_row = [&](int r, int slot) {
-        const rms_rsrc_t rs = rms_make_rsrc(src + (size_t)r * K, (unsigned)K * 2u);
+        const rsrc_t rs = make_rsrc(src + (size_t)r * K, (unsigned)K * 2u);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int pc = wave + i * nw;                    // piece index (wave-uniform); past the row: nothing fetched, lands in the dump
             const bool real = pc < pieces;
-            rms_dma16(rs, real ? voff : 0x7FFFFF00, __builtin_amdgcn_readfirstlane(real ? pc * 1024 : 0),
+            dma16(rs, real ? voff : 0x7FFFFF00, __builtin_amdgcn_readfirstlane(real ? pc * 1024 : 0),
                       __builtin_amdgcn_readfirstlane(real ? lds0 + (unsigned)slot * (unsigned)slot_bytes + (unsigned)pc * 1024u
                                                           : lds0 + (unsigned)R * (unsigned)slot_bytes));
         }
@@ -479,10 +448,8 @@ rmsnorm_quantize_ring_kernel(const uint16_t *__restrict__ src, const uint16_t *_
         [[maybe_unused]] const uint4 *ip = reinterpret_cast<const uint4 *>(idx + (size_t)(active ? g : 0) * 32), *wp = reinterpret_cast<const uint4 *>(weight);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-#if defined(__HIP_DEVICE_COMPILE__)
-            asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(iq[i]) : "v"(ip + i) : "memory");
-            asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(wq[i]) : "v"(wp + (active ? i * T + g : 0)) : "memory");
-#endif
+            MM_DEVICE_ONLY(asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(iq[i]) : "v"(ip + i) : "memory");)
+            MM_DEVICE_ONLY(asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(wq[i]) : "v"(wp + (active ? i * T + g : 0)) : "memory");)
         }
     }
     int r = (int)blockIdx.x;
@@ -490,16 +457,12 @@ rmsnorm_quantize_ring_kernel(const uint16_t *__restrict__ src, const uint16_t *_
 #pragma unroll
     for (int n = 0; n < R - 1; ++n)
         if (r + n * stride < rows) { issue_row(r + n * stride, n); dmas += 4; }
-    if (dmas >= 12) rms_wait_vmcnt<12>();
-    else if (dmas == 8) rms_wait_vmcnt<8>();
-    else if (dmas == 4) rms_wait_vmcnt<4>();
-    else rms_wait_vmcnt<0>();
+    if (dmas >= 12) wait_vmcnt<12>();
+    else if (dmas == 8) wait_vmcnt<8>();
+    else if (dmas == 4) wait_vmcnt<4>();
+    else wait_vmcnt<0>();
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#if defined(__HIP_DEVICE_COMPILE__)
-        asm volatile("" : "+v"(iq[i]), "+v"(wq[i]));     // valid from here on
-#endif
-    }
+    for (int i = 0; i < 4; ++i) { MM_DEVICE_ONLY(asm volatile("" : "+v"(iq[i]), "+v"(wq[i]));) }     // valid from here on
     if (active) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) reinterpret_cast<v4u *>(wslot)[swizzle_chunk(i * T + g)] = wq[i];
@@ -529,9 +492,9 @@ rmsnorm_quantize_ring_kernel(const uint16_t *__restrict__ src, const uint16_t *_
     for (int it = 0; r < rows; r += stride, ++it) {
         // row r has landed (this wave's pieces; the barrier extends it to every wave's)
         // (the first R - 1 iterations: the rows requested by the prologue have no stores between them -- only the DMAs are counted)
-        if (r + (R - 2) * stride >= rows) rms_wait_vmcnt<0>();
-        else if (it < R - 1) rms_wait_vmcnt<4 * (R - 2)>();
-        else rms_wait_vmcnt<5 * (R - 2)>();
+        if (r + (R - 2) * stride >= rows) wait_vmcnt<0>();
+        else if (it < R - 1) wait_vmcnt<4 * (R - 2)>();
+        else wait_vmcnt<5 * (R - 2)>();
         __syncthreads();                                                                  // B1
         if (prev >= 0) store_code_image(image, bytesS, KO, oS, oO, prev);                 // the previous row's fp6 / fp8 codes leave
         {

@@ -87,6 +87,18 @@ def test_every_csrc_header_is_a_build_dependency():
     assert present <= listed, sorted(present - listed)
 
 
+def test_the_buffer_primitives_have_one_copy():
+    """the descriptor's flags word, the LDS-DMA statement, the device-pass-only macro and the builtin buffer resource each encode a
+    hardware rule; a fix to one of several copies would not reach the others, so each lives in one product file (mx_buffer_ops.h).
+    The hardware probes of diag.hip, written out on purpose, are in neither list."""
+    import re
+    from micromix_amd import build
+    text = {os.path.basename(f): open(os.path.join(build.CSRC, f)).read() for f in build.SOURCES + build.HEADERS}
+    for what, pattern in (("descriptor flags word", r"0x00020000"), ("LDS-DMA statement", r"offen lds"),
+                          ("device-pass-only macro", r"#\s*define\s+\w*DEVICE_ONLY\b"), ("builtin buffer resource", r"__builtin_amdgcn_make_buffer_rsrc")):
+        assert [f for f, t in sorted(text.items()) if re.search(pattern, t)] == ["mx_buffer_ops.h"], what
+
+
 STREAM_OK = ("_ZN2mm6stream21mx_gemm_stream_kernelILi2ELi1ELi2ELi8ELb1EEEvNS_8GemmArgsE: ; @x\n"
              "\tv_accvgpr_write_b32 a[0], 0\n"
              "\tbuffer_load_dwordx2 v[10:11], v17, s[8:11], s1 offen\n"
