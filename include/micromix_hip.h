@@ -334,6 +334,18 @@ int mm_rmsnorm_qlinear_decode(const void *X_bf16, const void *norm_weight_bf16, 
  *               its low nibble and 2j + 1 in its high nibble.  kv_param fp16 [max_pages, L, 2, Hkv, P, 2] = (scale, zero) per token and
  *               head; value = code * scale - zero.
  *   MM_KV_BF16  kv_data bf16 [max_pages, L, 2, Hkv, P, 128]; kv_param unused (NULL)
+ *   MM_KV_FP8_E4M3  (detect it with mm_kv_dtype_supported(3); mm_version stays 660)  kv_data uint8 [max_pages, L, 2, Hkv, P, 128]: OCP
+ *               e4m3fn codes, element j in byte j.  kv_param fp16 [max_pages, L, 2, Hkv, P, 2] = (scale, zero), the int4 layout, with
+ *               scale = 2^e and zero = +0.0, so value = decode(code) * scale - zero is the one dequantization rule of both kinds.
+ *               Row rule (one group per 128 values, K and V alike, finite inputs): amax = the largest magnitude of the row's bf16
+ *               values; e = the smallest integer in [-14, 15] with amax <= 448 * 2^e -- from amax's bf16 exponent field E and
+ *               mantissa M, e = clamp(E - 135 + (M > 96), -14, 15); an all-zero or denormal row gives -14.  Element rule:
+ *               code = e4m3fn(RNE(clamp(x * 2^-e, -448, 448))); the scaling is exact, the clamp (which acts only where e was clamped
+ *               at 15) comes first, -0.0 keeps its sign (0x80), and no code is 0x7F / 0xFF.  Every dequantized value is exactly a
+ *               bf16 number.  Half the bytes of bf16 (plus 4 parameter bytes per 128-byte row), relative error <= 2^-4 per value
+ *               that is normal in e4m3 at the row's scale.  Attention over it computes bit for bit what it computes over a bf16
+ *               cache holding the dequantized values.
+ * Code 2 is unassigned: MM_ERR_BAD_ARG.
  * Page table (int32, device): kv_indptr [B + 1] and kv_indices [nnz] list sequence b's pages in order; last_page_len [B] in 1..P; a
  * sequence without pages has length 0.  The table already counts the tokens being appended.  Page indices outside [0, max_pages) are
  * skipped (nothing read or written for their tokens).
@@ -345,7 +357,7 @@ int mm_rmsnorm_qlinear_decode(const void *X_bf16, const void *norm_weight_bf16, 
  *     s = fp16(max(max - min, 1e-5) / 15);  base = clamp(rint(-min / s), 0, 15);  code = clamp(rint(x / s) + base, 0, 15);
  *     zero = fp16(base * s)     (correctly rounded divides; fp16 conversions saturate to +-65504; finite inputs)
  *   A row that does not straddle zero keeps the reference's behaviour: base clamps to 0 and the top codes clip.  zero >= 0 always; a
- *   zero of value 0 is stored as +0.0 (0x0000), never -0.0, also where rint(-min / s) is -0.0.  Bf16: a copy.
+ *   zero of value 0 is stored as +0.0 (0x0000), never -0.0, also where rint(-min / s) is -0.0.  Bf16: a copy.  Fp8: the rule above.
  *   Nothing outside the target slots is written.
  * mm_paged_decode: one query token per sequence, q bf16 [B, Hq, 128], Hq = g * Hkv with g <= 16; query head h attends kv head h / g
  *   (HF repeat_kv) over every cached token (no mask); softmax in fp32 with sm_scale (<= 0: 1 / sqrt(128)); o bf16 [B, Hq, 128], rounded
@@ -355,7 +367,8 @@ int mm_rmsnorm_qlinear_decode(const void *X_bf16, const void *norm_weight_bf16, 
  *   with a concurrent call) and a second launch merges them; with one chunk (workspace_bytes() == 0) one launch writes o.
  * Null pointers and bad sizes: MM_ERR_BAD_ARG; head_dim != 128 or g > 16: MM_ERR_UNSUPPORTED; both without device work.
  */
-enum mm_kv_dtype { MM_KV_INT4 = 0, MM_KV_BF16 = 1 };
+enum mm_kv_dtype { MM_KV_INT4 = 0, MM_KV_BF16 = 1, MM_KV_FP8_E4M3 = 3 };
+int mm_kv_dtype_supported(int kv_dtype);   /* 1 for the codes above, 0 for every other value */
 int mm_kv_append(void *kv_data, void *kv_param, int kv_dtype, int max_pages, int num_layers, int layer, int num_kv_heads, int page_size,
                  int head_dim, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_len, int batch,
                  const void *k_bf16, const void *v_bf16, const int32_t *append_indptr, int num_tokens, mm_stream_t stream);
@@ -395,7 +408,7 @@ int mm_paged_prefill(const void *q_bf16, const int32_t *qo_indptr, int num_token
  * Sliding-window attention over the paged KV cache (detect the four entries by their symbols; mm_version stays 660).  `window` = W >= 1
  * is HF's sliding_window: the query at position p attends positions max(0, p - W + 1) .. p, W tokens with itself -- in decode
  * p = len_b - 1, in prefill p = len_b - n_b + j (bottom-right, as above).  W = 0: no window, the same launches and the same bits as
- * mm_paged_decode / mm_paged_prefill; W < 0: MM_ERR_BAD_ARG.  Everything else -- arguments, sm_scale, head rules, both cache kinds, a
+ * mm_paged_decode / mm_paged_prefill; W < 0: MM_ERR_BAD_ARG.  Everything else -- arguments, sm_scale, head rules, every cache kind, a
  * length-0 sequence, negative positions, statuses -- as the un-windowed entry of the same name.
  *   Only the kv tiles that hold a window are visited (decode: from token max(0, len_b - W) on; prefill: per query tile, from the
  *   window start of its first token rounded down to 64), and the split-KV chunks are laid over that span, not over the sequence:
@@ -431,7 +444,7 @@ int mm_paged_prefill_window(const void *q_bf16, const int32_t *qo_indptr, int nu
  *     a = bf16(x[d] * cos[d]);  b = bf16((d < 64 ? -x[d + 64] : x[d - 64]) * sin[d]);  y[d] = bf16(a + b)       (finite inputs)
  *   The rotated q of every one of the T tokens goes to q_out bf16 [T, Hq, 128], contiguous, whether or not the token's cache slot is
  *   valid.  The rotated K and V are written exactly as mm_kv_append writes them: the same slot rule (append_indptr, a page table that
- *   already counts the tokens), the same int4 rule or bf16 copy, the same guards, nothing outside the target slots.
+ *   already counts the tokens), the same int4 / fp8 rule or bf16 copy, the same guards, nothing outside the target slots.
  *   q_out must not overlap q, k, v, cos or sin (other workgroups may still be reading them).  No workspace, no host reads of device
  *   arrays: capture-safe like mm_kv_append.
  * Null pointers, negative sizes, Hq not a multiple of Hkv, a stride smaller than the row it holds (Hq * 128, 128) or odd, a q / k / v /

@@ -20,7 +20,7 @@ EXPORTS = (
     "mm_matmul_ws", "mm_matmul_workspace_bytes", "mm_matmul_ws_reset",
     "mm_gate_up_activate", "mm_gate_up_activate_decode", "mm_rmsnorm_gate_up_activate_decode", "mm_rmsnorm_gate_up_activate_decode_supported", "mm_gate_up_activate_decode_supported", "mm_down_activate_decode", "mm_down_activate_decode_supported", "mm_down_activate_decode_supported_w", "mm_gate_up_activate_workspace_bytes", "mm_gate_up_activate_describe", "mm_rmsnorm_quantize", "mm_add_rmsnorm_quantize", "mm_add_rmsnorm_qlinear_decode", "mm_add_rmsnorm_gate_up_activate_decode", "mm_qlinear_decode", "mm_qlinear_decode_supported", "mm_qlinear_decode_supported_w", "mm_rmsnorm_qlinear_decode", "mm_rmsnorm_qlinear_decode_supported", "mm_rmsnorm_qlinear_decode_supported_w", "mm_matmul_grouped", "mm_reorder_quantize_grouped",
     "mm_matmul_describe", "mm_test_function", "mm_diag_set_kernel_events",
-    "mm_kv_append", "mm_paged_decode_workspace_bytes", "mm_paged_decode",
+    "mm_kv_dtype_supported", "mm_kv_append", "mm_paged_decode_workspace_bytes", "mm_paged_decode",
     "mm_paged_prefill_workspace_bytes", "mm_paged_prefill", "mm_rope_kv_append",
     "mm_paged_decode_window_workspace_bytes", "mm_paged_decode_window", "mm_paged_prefill_window_workspace_bytes", "mm_paged_prefill_window",
     "mm_moe_route", "mm_moe_plan", "mm_moe_gather", "mm_moe_combine",
@@ -38,7 +38,7 @@ MM_ROUND_PER_SEGMENT, MM_ROUND_ONCE, MM_SPLIT_K_ALWAYS, MM_WS_TICKETS_ZEROED, MM
 MM_WS_TICKET_BYTES = 4096
 MM_RMS_REFERENCE, MM_RMS_NO_INTEGER_ROUND = 0, 1
 MM_NORM_NO_INTEGER_ROUND = 0x100
-MM_KV_INT4, MM_KV_BF16 = 0, 1
+MM_KV_INT4, MM_KV_BF16, MM_KV_FP8_E4M3 = 0, 1, 3      # 2 is unassigned
 
 class MMGroup(ctypes.Structure):
     """mm_group of include/micromix_hip.h"""
@@ -147,6 +147,8 @@ def load():
         lib.mm_diag_set_clock_buffer.argtypes = [vp]
     lib.mm_diag_set_kernel_events.restype = i
     lib.mm_diag_set_kernel_events.argtypes = [vp, vp]
+    lib.mm_kv_dtype_supported.restype = i
+    lib.mm_kv_dtype_supported.argtypes = [i]
     lib.mm_kv_append.restype = i
     lib.mm_kv_append.argtypes = [vp, vp] + [i] * 7 + [vp] * 3 + [i, vp, vp, vp, i, vp]
     lib.mm_paged_decode_workspace_bytes.restype = sz

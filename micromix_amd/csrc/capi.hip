@@ -643,16 +643,19 @@ int mm_matmul_grouped(const mm_group *groups, int ngroups, int N, int KN, int KS
 
 // ---- paged KV cache (kv_cache.hip, rope_append.hip, kv_prefill.hip)
 // What every entry point shares: kv_geometry checks the numbers and fills the descriptor, kv_pointers checks what it points to (int4
-// needs its params).  Two steps: a call with nothing to do returns MM_OK between them, before any pointer is looked at.
+// and fp8 need their params).  Two steps: a call with nothing to do returns MM_OK between them, before any pointer is looked at.
+static_assert(mm::KV_INT4 == MM_KV_INT4 && mm::KV_BF16 == MM_KV_BF16 && mm::KV_FP8 == MM_KV_FP8_E4M3, "PagedKV::kind holds mm_kv_dtype codes");
+int mm_kv_dtype_supported(int kv_dtype) { return kv_dtype == MM_KV_INT4 || kv_dtype == MM_KV_BF16 || kv_dtype == MM_KV_FP8_E4M3; }
+
 static int kv_geometry(const void *kv_data, const void *kv_param, int kv_dtype, int max_pages, int L, int layer, int Hkv, int P, int head_dim,
                        const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_len, int B, mm::PagedKV *kv) {
-    if ((kv_dtype != MM_KV_INT4 && kv_dtype != MM_KV_BF16) || max_pages <= 0 || L <= 0 || layer < 0 || layer >= L || Hkv <= 0 || Hkv > 65535 ||
+    if (!mm_kv_dtype_supported(kv_dtype) || max_pages <= 0 || L <= 0 || layer < 0 || layer >= L || Hkv <= 0 || Hkv > 65535 ||
         P <= 0 || B < 0 || B > 65535 || head_dim <= 0)
         return MM_ERR_BAD_ARG;
-    *kv = {(uint8_t *)kv_data, (uint16_t *)kv_param, kv_indptr, kv_indices, last_page_len, max_pages, L, layer, Hkv, P, B, kv_dtype == MM_KV_INT4};
+    *kv = {(uint8_t *)kv_data, (uint16_t *)kv_param, kv_indptr, kv_indices, last_page_len, max_pages, L, layer, Hkv, P, B, kv_dtype};
     return head_dim == 128 ? MM_OK : MM_ERR_UNSUPPORTED;
 }
-static bool kv_pointers(const mm::PagedKV &kv) { return kv.data && (!kv.int4 || kv.param) && kv.indptr && kv.indices && kv.last_page_len; }
+static bool kv_pointers(const mm::PagedKV &kv) { return kv.data && (kv.kind == mm::KV_BF16 || kv.param) && kv.indptr && kv.indices && kv.last_page_len; }
 
 int mm_kv_append(void *kv_data, void *kv_param, int kv_dtype, int max_pages, int num_layers, int layer, int num_kv_heads, int page_size,
                  int head_dim, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_len, int batch,

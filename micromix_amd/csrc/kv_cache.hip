@@ -1,17 +1,21 @@
-// Paged KV cache: append (int4 quantize or bf16 copy) and GQA split-KV decode attention (include/micromix_hip.h, mm_kv_append /
+// Paged KV cache: append (int4 or fp8 quantize, or bf16 copy) and GQA split-KV decode attention (include/micromix_hip.h, mm_kv_append /
 // mm_paged_decode).  Layout and parameter convention of the reference's vendored FlashInfer cache (flashinfer/page.cuh:15,75-103,
 // quantization.cuh:60-80); the quantization rule is quantize_int_group(x, 4, 128) (model/qLlamaLayer.py:13-23) with fp16 parameters.
 //
 //   kv_data  int4: uint8 [max_pages, L, 2, Hkv, P, 64]  (byte j = element 2j low nibble | element 2j+1 high nibble)
 //            bf16: bf16  [max_pages, L, 2, Hkv, P, 128]
-//   kv_param int4 only: fp16 [max_pages, L, 2, Hkv, P, 2] = (scale, zero);  value = code * scale - zero
+//            fp8:  uint8 [max_pages, L, 2, Hkv, P, 128] (OCP e4m3fn codes, element j in byte j)
+//   kv_param int4 and fp8: fp16 [max_pages, L, 2, Hkv, P, 2] = (scale, zero);  value = decode(code) * scale - zero
+//            (fp8: scale = 2^e, the smallest e in [-14, 15] with amax <= 448 * 2^e, and zero = +0.0)
 //
 // Decode: one workgroup (4 waves) per (sequence, kv head, chunk of tokens) handles all g = Hq / Hkv query heads of that kv head, so every
 // cache byte is read once.  Each wave walks 32-token tiles of the chunk:
 //   scores  one v_mfma_f32_16x16x32_bf16 chain per 16 tokens: A = q (16 head rows, g used), B = the K codes as bf16 (16 + code, exact),
-//           so q.k = s * (q.(16 + c)) - (16 s + z) * sum(q);  for the bf16 cache B is the K row itself
+//           so q.k = s * (q.(16 + c)) - (16 s + z) * sum(q);  for the bf16 cache B is the K row itself;  fp8: B = the codes widened to
+//           bf16 (exact, one v_cvt_scalef32_pk_bf16_fp8 per two), q.k = s * (q.code): the power-of-two s moves no rounding
 //   softmax online, in the log2 domain, the max across the tile's 16 token lanes, l and sum(p z) as per-lane partials
-//   p.V     VALU, fp32: a lane owns 8 dims of 8 tokens of the tile, acc[h][8] += (p s_v)[h] * code  (minus sum(p z_v) once at the end)
+//   p.V     VALU, fp32: a lane owns 8 dims of 8 tokens of the tile, acc[h][8] += (p s_v)[h] * code  (minus sum(p z_v) once at the end;
+//           fp8: the codes by v_cvt_pk_f32_fp8, no z)
 // The waves merge through LDS; with one chunk the workgroup writes o, otherwise (m, l, o) partials that mm_paged_decode's merge kernel
 // combines.
 // Sliding window (mm_paged_decode_window, the WINDOW kernels): the walk starts at token max(0, len - W) instead of at token 0 and the
@@ -36,14 +40,14 @@ constexpr int DEC_WAVES = 4;
 constexpr int TILE = 32;           // tokens per wave iteration
 
 // One workgroup per appended token and kv head; wave 0 writes K, wave 1 writes V (the slot and the int4 rule: mx_paged_kv.h).
-template <bool INT4>
+template <int KIND>
 __global__ __launch_bounds__(128) void kv_append_kernel(const PagedKV kv, const uint16_t *__restrict__ k, const uint16_t *__restrict__ v,
                                                         const int *__restrict__ append_indptr) {
     const int i = blockIdx.x, h = blockIdx.y, which = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t row = append_row(kv, append_indptr, i, which, h);
     if (row < 0) return;
     const uint32_t two = ((const uint32_t *)((which ? v : k) + ((int64_t)i * kv.Hkv + h) * HD))[lane];   // elements 2 lane, 2 lane + 1
-    store_row<INT4>(kv, row, lane, two);
+    store_row<KIND>(kv, row, lane, two);
 }
 
 struct DecodeArgs {
@@ -59,7 +63,7 @@ struct DecodeArgs {
 // WINDOW: the workgroups of sequence b walk [lo_b, len_b), lo_b = max(0, len_b - window), chunk c from lo_b + c * chunk on.  The tiles
 // start at lo_b itself -- a lane addresses its token's row on its own, so a tile need not start on a multiple of 32 -- and no token
 // below the window is ever looked at: no compare, no page-table read, the span exactly min(len_b, window) tokens
-template <bool INT4, int GP, bool WINDOW>
+template <int KIND, int GP, bool WINDOW>
 __global__ __launch_bounds__(256) void paged_decode_kernel(const DecodeArgs a) {
     __shared__ float s_p[DEC_WAVES][TILE][16];        // (p * scale) of the tile, [token][head]
     __shared__ float s_alpha[DEC_WAVES][16];
@@ -114,7 +118,7 @@ __global__ __launch_bounds__(256) void paged_decode_kernel(const DecodeArgs a) {
             const bool ok = k_row(kv, pages, tb + 16 * G + c, t1, kvh, rk);
             if (kq == 0) s_row[wave][16 * G + c] = ok ? rk + v_offset(kv) : -1;
             v4f d = {0.0f, 0.0f, 0.0f, 0.0f};
-            if (INT4) {
+            if (KIND == KV_INT4) {
                 v4u kc = *(const v4u *)(kv.data + rk * (HD / 2) + 16 * kq);
                 const uint32_t pk = *(const uint32_t *)(kv.param + rk * 2);
                 const uint32_t pv = *(const uint32_t *)(kv.param + (rk + v_offset(kv)) * 2);
@@ -127,6 +131,23 @@ __global__ __launch_bounds__(256) void paged_decode_kernel(const DecodeArgs a) {
                 for (int s = 0; s < 4; ++s) d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[s], codes_to_bf16(kc[s]), d, 0, 0, 0);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) sc[G][r] = sk * d[r] - (16.0f * sk + zk) * sq[r];
+            } else if (KIND == KV_FP8) {
+                const v4u *kr = (const v4u *)(kv.data + rk * HD + 32 * kq);      // dims 32 kq .. 32 kq + 31: step s is dwords 2 s, 2 s + 1
+                v4u kc[2];
+                kc[0] = ok ? kr[0] : v4u{0, 0, 0, 0};
+                kc[1] = ok ? kr[1] : v4u{0, 0, 0, 0};
+                const uint32_t pk = *(const uint32_t *)(kv.param + rk * 2);
+                const uint32_t pv = *(const uint32_t *)(kv.param + (rk + v_offset(kv)) * 2);
+                const float sk = ok ? scale_of(pk) : 0.0f;
+                sv[G] = ok ? scale_of(pv) : 0.0f;
+                zv[G] = 0.0f;
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    const v2u lo = fp8x4_to_bf16(kc[s >> 1][2 * (s & 1)]), hi = fp8x4_to_bf16(kc[s >> 1][2 * (s & 1) + 1]);
+                    d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[s], __builtin_bit_cast(v8bf, (v4u{lo.x, lo.y, hi.x, hi.y})), d, 0, 0, 0);
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) sc[G][r] = sk * d[r];
             } else {
                 const v4u *kr = (const v4u *)(kv.data + rk * (HD * 2) + 64 * kq);
                 v4u kb[4];
@@ -168,7 +189,7 @@ __global__ __launch_bounds__(256) void paged_decode_kernel(const DecodeArgs a) {
         int64_t rv[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) rv[i] = s_row[wave][4 * i + tq];
-        if (INT4) {
+        if (KIND == KV_INT4) {
             uint32_t vc[8];
 #pragma unroll
             for (int i = 0; i < 8; ++i) vc[i] = *(const uint32_t *)(kv.data + (rv[i] < 0 ? 0 : rv[i]) * (HD / 2) + 4 * dg);
@@ -181,6 +202,23 @@ __global__ __launch_bounds__(256) void paged_decode_kernel(const DecodeArgs a) {
                     cv[2 * j] = (float)((vc[i] >> (8 * j)) & 15u);
                     cv[2 * j + 1] = (float)((vc[i] >> (8 * j + 4)) & 15u);
                 }
+#pragma unroll
+                for (int h = 0; h < GP; ++h) {
+                    const float p = s_p[wave][4 * i + tq][h];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) acc[h][e] = fmaf(p, cv[e], acc[h][e]);
+                }
+            }
+        } else if (KIND == KV_FP8) {
+            v2u vc[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) vc[i] = *(const v2u *)(kv.data + (rv[i] < 0 ? 0 : rv[i]) * HD + 8 * dg);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                if (rv[i] < 0) continue;
+                float cv[8];
+                fp8x4_to_f32(vc[i].x, cv);
+                fp8x4_to_f32(vc[i].y, cv + 4);
 #pragma unroll
                 for (int h = 0; h < GP; ++h) {
                     const float p = s_p[wave][4 * i + tq][h];
@@ -285,12 +323,12 @@ __global__ __launch_bounds__(64) void paged_decode_merge_kernel(const DecodeArgs
     *(uint32_t *)(a.o + ((int64_t)b * a.Hq + hq) * HD + d) = pack_bf(o[0], o[1]);
 }
 
-template <bool INT4, bool WINDOW>
+template <int KIND, bool WINDOW>
 hipError_t launch_decode_g(const DecodeArgs &a, hipStream_t stream) {
     const dim3 grid(a.nc, a.kv.Hkv, a.kv.B);
-    if (a.g <= 4) paged_decode_kernel<INT4, 4, WINDOW><<<grid, 256, 0, stream>>>(a);
-    else if (a.g <= 8) paged_decode_kernel<INT4, 8, WINDOW><<<grid, 256, 0, stream>>>(a);
-    else paged_decode_kernel<INT4, 16, WINDOW><<<grid, 256, 0, stream>>>(a);
+    if (a.g <= 4) paged_decode_kernel<KIND, 4, WINDOW><<<grid, 256, 0, stream>>>(a);
+    else if (a.g <= 8) paged_decode_kernel<KIND, 8, WINDOW><<<grid, 256, 0, stream>>>(a);
+    else paged_decode_kernel<KIND, 16, WINDOW><<<grid, 256, 0, stream>>>(a);
     return hipGetLastError();
 }
 
@@ -328,8 +366,9 @@ size_t kv_decode_workspace_bytes(int B, int Hq, int Hkv, int max_seq_len, int wi
 
 hipError_t launch_kv_append(const PagedKV &kv, const void *k, const void *v, const int *append_indptr, int T, hipStream_t stream) {
     const dim3 grid(T, kv.Hkv);
-    if (kv.int4) kv_append_kernel<true><<<grid, 128, 0, stream>>>(kv, (const uint16_t *)k, (const uint16_t *)v, append_indptr);
-    else kv_append_kernel<false><<<grid, 128, 0, stream>>>(kv, (const uint16_t *)k, (const uint16_t *)v, append_indptr);
+    if (kv.kind == KV_INT4) kv_append_kernel<KV_INT4><<<grid, 128, 0, stream>>>(kv, (const uint16_t *)k, (const uint16_t *)v, append_indptr);
+    else if (kv.kind == KV_FP8) kv_append_kernel<KV_FP8><<<grid, 128, 0, stream>>>(kv, (const uint16_t *)k, (const uint16_t *)v, append_indptr);
+    else kv_append_kernel<KV_BF16><<<grid, 128, 0, stream>>>(kv, (const uint16_t *)k, (const uint16_t *)v, append_indptr);
     return hipGetLastError();
 }
 
@@ -345,8 +384,10 @@ hipError_t launch_paged_decode(const PagedKV &kv, const void *q, int Hq, int max
     kv_decode_split(kv.B, kv.Hkv, max_seq_len, window, &a.nc, &a.chunk);
     a.scale_log2 = kv_scale_log2(sm_scale);
     a.window = window;
-    hipError_t e = window > 0 ? (kv.int4 ? launch_decode_g<true, true>(a, stream) : launch_decode_g<false, true>(a, stream))
-                              : (kv.int4 ? launch_decode_g<true, false>(a, stream) : launch_decode_g<false, false>(a, stream));
+    hipError_t e;
+    if (kv.kind == KV_INT4) e = window > 0 ? launch_decode_g<KV_INT4, true>(a, stream) : launch_decode_g<KV_INT4, false>(a, stream);
+    else if (kv.kind == KV_FP8) e = window > 0 ? launch_decode_g<KV_FP8, true>(a, stream) : launch_decode_g<KV_FP8, false>(a, stream);
+    else e = window > 0 ? launch_decode_g<KV_BF16, true>(a, stream) : launch_decode_g<KV_BF16, false>(a, stream);
     if (e != hipSuccess || a.nc == 1) return e;
     paged_decode_merge_kernel<<<dim3(Hq, kv.B), 64, 0, stream>>>(a);
     return hipGetLastError();

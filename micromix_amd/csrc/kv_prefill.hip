@@ -1,4 +1,4 @@
-// Causal multi-token attention over the paged int4 / bf16 KV cache (include/micromix_hip.h, mm_paged_prefill).  Same cache layout,
+// Causal multi-token attention over the paged int4 / bf16 / fp8 KV cache (include/micromix_hip.h, mm_paged_prefill).  Same cache layout,
 // page table and head rules as mm_paged_decode (kv_cache.hip); the queries q [T, Hq, 128] are split among the sequences by qo_indptr
 // (the append_indptr of mm_kv_append), and the mask is causal, aligned bottom-right: query j of sequence b sits at position
 // p = len_b - n_b + j and attends cache positions 0..p.
@@ -13,6 +13,9 @@
 //   softmax  online, fp32, log2 domain; the row max over the 4 lanes of a row; the causal mask only on tiles that cross the diagonal
 //   p.V      O^T += V^T P^T on the MFMA: B = bf16(p * s_v) (int4) or bf16(p) (bf16 cache) straight from the score registers, A = the
 //            transposed V image; int4 subtracts sum(p z_v) once at the end in fp32
+//   fp8      staging widens the e4m3 codes of K and V to bf16 (exact), K into the bf16 kind's row layout and V into the same transposed
+//            image, so scores and p.V read LDS exactly as the bf16 kind does; s = sk (q.code), B = bf16(p * s_v), no z: the power-of-two
+//            scales move no rounding.  K is widened once per workgroup here, not once per wave at the MFMA operand as int4's nibbles are
 // Split-KV: the kv range is cut into chunks chosen from host values only (kv_prefill_split); with more than one chunk each workgroup
 // writes (m, l, o) partials and a merge launch combines them.  The tile -> (sequence, tile of it) map needs no host knowledge of
 // qo_indptr: sequence b owns tiles [qo_indptr[b] / BQ + b, qo_indptr[b + 1] / BQ + b + 1), which hold its ceil(n_b / BQ) tiles;
@@ -34,7 +37,6 @@ namespace {
 using namespace mm::kv;       // the page-table walk, the int4 decoding and the chunk merge
 using mm::PagedKV;
 
-typedef unsigned v2u __attribute__((ext_vector_type(2)));
 typedef float v4f __attribute__((ext_vector_type(4)));
 
 constexpr int ROWS = 64;             // MFMA rows (token, head) per workgroup
@@ -72,9 +74,10 @@ __device__ inline bool tile_of(const PrefillArgs &a, int i, int &b, int &j, int 
 // WINDOW: a query tile walks the kv tiles from the window of its first token on (rounded down to KT), chunk c from there + c * chunk;
 // a wave skips the tiles that lie below the windows of all its rows and compares against the lower edge only on the tiles that cross
 // one of them -- both wave-uniform, like the diagonal's gate
-template <bool INT4, bool WINDOW>
+template <int KIND, bool WINDOW>
 __global__ __launch_bounds__(NT) void paged_prefill_kernel(const PrefillArgs a) {
-    constexpr int KSTR = INT4 ? KSTR4 : KSTR16;
+    constexpr bool INT4 = KIND == KV_INT4, FP8 = KIND == KV_FP8;
+    constexpr int KSTR = INT4 ? KSTR4 : KSTR16;       // fp8: the bf16 layout, widened at staging
     __shared__ __attribute__((aligned(16))) uint8_t s_k[KT * KSTR];
     __shared__ __attribute__((aligned(16))) uint8_t s_vt[HD * VSTR];
     __shared__ __attribute__((aligned(16))) float s_par[5][KT];      // per token: K scale, K offset, K bias (0 / -inf), V scale, V zero
@@ -128,8 +131,8 @@ __global__ __launch_bounds__(NT) void paged_prefill_kernel(const PrefillArgs a) 
     // ---- staging: thread (tg, dg) owns tokens 4 tg .. 4 tg + 3 of the tile: V dims 8 dg .. 8 dg + 7 of each, the K bytes of token
     // 4 tg + (dg >> 2) part dg & 3, and (dg == 0) the K params / (dg == 1) the V params of its four tokens
     const int tg = tid & 15, dg = tid >> 4, uk = dg >> 2, kpart = dg & 3;
-    v4u kreg[INT4 ? 1 : 4];
-    v4u vreg[4];                // int4: .x holds the token's 8 codes; bf16: the 8 values
+    v4u kreg[INT4 ? 1 : FP8 ? 2 : 4];
+    v4u vreg[4];                // int4: .x holds the token's 8 codes; fp8: .x, .y; bf16: the 8 values
     uint32_t preg[4];
     bool okreg[4];
     auto load = [&](int kt) {
@@ -141,6 +144,15 @@ __global__ __launch_bounds__(NT) void paged_prefill_kernel(const PrefillArgs a) 
             if (INT4) {
                 vreg[u].x = ok ? *(const uint32_t *)(kv.data + rv * (HD / 2) + 4 * dg) : 0u;
                 if (u == uk) kreg[0] = ok ? *(const v4u *)(kv.data + rk * (HD / 2) + 16 * kpart) : v4u{0, 0, 0, 0};
+                if (dg < 2) preg[u] = ok ? *(const uint32_t *)(kv.param + (dg ? rv : rk) * 2) : 0u;
+            } else if (FP8) {
+                const v2u vc = ok ? *(const v2u *)(kv.data + rv * HD + 8 * dg) : v2u{0, 0};
+                vreg[u].x = vc.x;
+                vreg[u].y = vc.y;
+                if (u == uk) {
+                    kreg[0] = ok ? *(const v4u *)(kv.data + rk * HD + 32 * kpart) : v4u{0, 0, 0, 0};
+                    kreg[1] = ok ? *(const v4u *)(kv.data + rk * HD + 32 * kpart + 16) : v4u{0, 0, 0, 0};
+                }
                 if (dg < 2) preg[u] = ok ? *(const uint32_t *)(kv.param + (dg ? rv : rk) * 2) : 0u;
             } else {
                 vreg[u] = ok ? *(const v4u *)(kv.data + rv * (HD * 2) + 16 * dg) : v4u{0, 0, 0, 0};
@@ -187,6 +199,39 @@ __global__ __launch_bounds__(NT) void paged_prefill_kernel(const PrefillArgs a) 
                     }
                 }
             }
+        } else if (FP8) {
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {      // 8 codes -> 8 bf16, the bf16 kind's row
+                const v2u lo = fp8x4_to_bf16(kreg[s >> 1][2 * (s & 1)]), hi = fp8x4_to_bf16(kreg[s >> 1][2 * (s & 1) + 1]);
+                *(v4u *)(s_k + (4 * tg + uk) * KSTR + 64 * kpart + 16 * s) = v4u{lo.x, lo.y, hi.x, hi.y};
+            }
+            v4u vb[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const v2u lo = fp8x4_to_bf16(vreg[u].x), hi = fp8x4_to_bf16(vreg[u].y);
+                vb[u] = v4u{lo.x, lo.y, hi.x, hi.y};
+            }
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int sh = 16 * (e & 1);
+                v2u w;
+                w.x = ((vb[0][e >> 1] >> sh) & 0xffffu) | (((vb[1][e >> 1] >> sh) & 0xffffu) << 16);
+                w.y = ((vb[2][e >> 1] >> sh) & 0xffffu) | (((vb[3][e >> 1] >> sh) & 0xffffu) << 16);
+                *(v2u *)(s_vt + (8 * dg + e) * VSTR + 8 * tg) = w;
+            }
+            if (dg < 2) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const float s = scale_of(preg[u]);
+                    const int t = 4 * tg + u;
+                    if (dg == 0) {
+                        s_ks[t] = okreg[u] ? s * a.scale_log2 : 0.0f;
+                        s_kb[t] = okreg[u] ? 0.0f : -INFINITY;
+                    } else {
+                        s_vs[t] = okreg[u] ? s : 0.0f;
+                    }
+                }
+            }
         } else {
 #pragma unroll
             for (int s = 0; s < 4; ++s) *(v4u *)(s_k + (4 * tg + uk) * KSTR + 64 * kpart + 16 * s) = kreg[s];
@@ -227,6 +272,13 @@ __global__ __launch_bounds__(NT) void paged_prefill_kernel(const PrefillArgs a) 
                 const v4f ks = *(const v4f *)(s_ks + tl), kcs = *(const v4f *)(s_kc + tl), kb = *(const v4f *)(s_kb + tl);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) sc[blk][r] = ks[r] * d[r] - kcs[r] * sq + kb[r];
+            } else if (FP8) {
+                const v4u *kr = (const v4u *)(s_k + (16 * blk + c) * KSTR + 64 * kq);
+#pragma unroll
+                for (int s = 0; s < 4; ++s) d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8bf, kr[s]), qb[s], d, 0, 0, 0);
+                const v4f ks = *(const v4f *)(s_ks + tl), kb = *(const v4f *)(s_kb + tl);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) sc[blk][r] = ks[r] * d[r] + kb[r];
             } else {
                 const v4u *kr = (const v4u *)(s_k + (16 * blk + c) * KSTR + 64 * kq);
 #pragma unroll
@@ -281,6 +333,12 @@ __global__ __launch_bounds__(NT) void paged_prefill_kernel(const PrefillArgs a) 
                 const v4f vz0 = *(const v4f *)(s_vz + 32 * ks + 4 * kq), vz1 = *(const v4f *)(s_vz + 32 * ks + 16 + 4 * kq);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) pz += p[2 * ks][r] * vz0[r] + p[2 * ks + 1][r] * vz1[r];
+                pb.x = pack_bf(p[2 * ks][0] * vs0[0], p[2 * ks][1] * vs0[1]);
+                pb.y = pack_bf(p[2 * ks][2] * vs0[2], p[2 * ks][3] * vs0[3]);
+                pb.z = pack_bf(p[2 * ks + 1][0] * vs1[0], p[2 * ks + 1][1] * vs1[1]);
+                pb.w = pack_bf(p[2 * ks + 1][2] * vs1[2], p[2 * ks + 1][3] * vs1[3]);
+            } else if (FP8) {
+                const v4f vs0 = *(const v4f *)(s_vs + 32 * ks + 4 * kq), vs1 = *(const v4f *)(s_vs + 32 * ks + 16 + 4 * kq);
                 pb.x = pack_bf(p[2 * ks][0] * vs0[0], p[2 * ks][1] * vs0[1]);
                 pb.y = pack_bf(p[2 * ks][2] * vs0[2], p[2 * ks][3] * vs0[3]);
                 pb.z = pack_bf(p[2 * ks + 1][0] * vs1[0], p[2 * ks + 1][1] * vs1[1]);
@@ -389,10 +447,12 @@ hipError_t launch_paged_prefill(const PagedKV &kv, const void *q, const int *qo_
     a.window = window;
     const dim3 grid(a.tiles, kv.Hkv, a.nc);
     if (window > 0) {
-        if (kv.int4) paged_prefill_kernel<true, true><<<grid, NT, 0, stream>>>(a);
-        else paged_prefill_kernel<false, true><<<grid, NT, 0, stream>>>(a);
-    } else if (kv.int4) paged_prefill_kernel<true, false><<<grid, NT, 0, stream>>>(a);
-    else paged_prefill_kernel<false, false><<<grid, NT, 0, stream>>>(a);
+        if (kv.kind == KV_INT4) paged_prefill_kernel<KV_INT4, true><<<grid, NT, 0, stream>>>(a);
+        else if (kv.kind == KV_FP8) paged_prefill_kernel<KV_FP8, true><<<grid, NT, 0, stream>>>(a);
+        else paged_prefill_kernel<KV_BF16, true><<<grid, NT, 0, stream>>>(a);
+    } else if (kv.kind == KV_INT4) paged_prefill_kernel<KV_INT4, false><<<grid, NT, 0, stream>>>(a);
+    else if (kv.kind == KV_FP8) paged_prefill_kernel<KV_FP8, false><<<grid, NT, 0, stream>>>(a);
+    else paged_prefill_kernel<KV_BF16, false><<<grid, NT, 0, stream>>>(a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || a.nc == 1) return e;
     paged_prefill_merge_kernel<<<dim3(a.tiles, kv.Hkv), NT, 0, stream>>>(a);

@@ -252,12 +252,13 @@ bool mx_gemm_small_m_uses_tiles(int M, int N, const int K[3], bool w4, size_t ws
 const char *describe_mx_gemm256(int M, int N, const int K[3], bool w4, size_t ws_bytes, bool force_split, bool tickets_zeroed, bool out_f32 = false);   // thread-local buffer  // 0 when mm_matmul would not split K for this shape
 
 // paged KV cache: one layer of a cache and the page table of its B sequences (layout: kv_cache.hip; device side: mx_paged_kv.h)
+constexpr int KV_INT4 = 0, KV_BF16 = 1, KV_FP8 = 3;      // the codes of enum mm_kv_dtype (include/micromix_hip.h); 2 is unassigned
 struct PagedKV {
     uint8_t *data;
-    uint16_t *param;           // int4 only: fp16 (scale, zero) per row
+    uint16_t *param;           // int4 and fp8: fp16 (scale, zero) per row
     const int *indptr, *indices, *last_page_len;
     int max_pages, L, layer, Hkv, P, B;
-    bool int4;
+    int kind;                  // KV_INT4, KV_BF16 or KV_FP8
 };
 constexpr float KV_DEFAULT_SM_SCALE = 0.08838834764831845f;                // 1 / sqrt(128)
 inline float kv_scale_log2(float sm_scale) { return (sm_scale > 0.0f ? sm_scale : KV_DEFAULT_SM_SCALE) * 1.4426950408889634f; }

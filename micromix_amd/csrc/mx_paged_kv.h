@@ -1,7 +1,10 @@
 // Device side of the paged KV cache (PagedKV, mx_kernels.h), shared by kv_cache.hip, kv_prefill.hip and rope_append.hip: the page-table
-// walk (seq_len, kv_row, k_row), where an appended token's row lies and what is written there (append_row, store_row: the int4 rule of
-// include/micromix_hip.h, or a bf16 copy), the int4 decoding (codes_to_bf16, scale_of, zero_of) and the split-KV merge (merge_chunks).
+// walk (seq_len, kv_row, k_row), where an appended token's row lies and what is written there (append_row, store_row: the int4 rule or
+// the fp8 rule of include/micromix_hip.h, or a bf16 copy), the decoding (int4: codes_to_bf16; fp8: fp8x4_to_bf16, fp8x4_to_f32; both:
+// scale_of, zero_of) and the split-KV merge (merge_chunks).
 // One copy of each, so the kernels cannot drift apart.  In the append, a wave owns a (token, head) row, lane l its elements 2 l, 2 l + 1.
+// The fp8 kind (KV_FP8): OCP e4m3fn codes, element j in byte j, with the int4 kind's (scale, zero) pair per row, scale = 2^e and
+// zero = +0.0, so value = decode(code) * scale - zero holds for both.  e is the smallest integer in [-14, 15] with amax <= 448 * 2^e.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
@@ -15,8 +18,15 @@ namespace kv {
 
 typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
+typedef unsigned v2u __attribute__((ext_vector_type(2)));
+typedef __bf16 v2bf __attribute__((ext_vector_type(2)));
+typedef short v2s __attribute__((ext_vector_type(2)));
+typedef float v2f __attribute__((ext_vector_type(2)));
 
 constexpr int HD = 128;            // head_dim
+using mm::KV_INT4;
+using mm::KV_BF16;
+using mm::KV_FP8;
 
 __device__ inline float bf16f(uint32_t bits16) { return __uint_as_float(bits16 << 16); }
 
@@ -43,6 +53,21 @@ __device__ inline v8bf codes_to_bf16(uint32_t w) {
         r[m] = (__builtin_amdgcn_perm(hi, lo, sel) << 3) | 0x41804180u;    // bf16 0x4180 | c << 3 = 16 + c
     }
     return __builtin_bit_cast(v8bf, r);
+}
+
+// 4 e4m3 codes (one dword, element j in byte j) -> 4 bf16 values (exact: e4m3 has 3 mantissa bits), element j in half j.  The scale
+// operand is 1.0, so nothing depends on which way the converter applies it
+__device__ inline v2u fp8x4_to_bf16(uint32_t w) {
+    v2u r;
+    r.x = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, false));
+    r.y = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, true));
+    return r;
+}
+
+// 4 e4m3 codes -> 4 fp32 values
+__device__ inline void fp8x4_to_f32(uint32_t w, float *f) {
+    const v2f lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
+    f[0] = lo.x; f[1] = lo.y; f[2] = hi.x; f[3] = hi.y;
 }
 
 // the sequence a flat index belongs to: the largest b with indptr[b] <= i (empty sequences are skipped over)
@@ -90,10 +115,27 @@ __device__ inline int64_t append_row(const PagedKV &kv, const int *append_indptr
 }
 
 // the whole wave stores one row: `two` = this lane's elements 2 lane, 2 lane + 1 (bf16 bits)
-template <bool INT4>
+template <int KIND>
 __device__ inline void store_row(const PagedKV &kv, int64_t row, int lane, uint32_t two) {
-    if (!INT4) {
+    if (KIND == KV_BF16) {
         ((uint32_t *)kv.data)[row * (HD / 2) + lane] = two;
+        return;
+    }
+    if (KIND == KV_FP8) {
+        // bf16 magnitudes order as their bit patterns do, so amax, the exponent and the clamp are integer work: no divide, no log
+        uint32_t m0 = two & 0x7fffu, m1 = (two >> 16) & 0x7fffu;
+        uint32_t amax = max(m0, m1);
+#pragma unroll
+        for (int o = 32; o; o >>= 1) amax = max(amax, (uint32_t)__shfl_xor((int)amax, o));
+        // amax = 1.M * 2^(E - 127) <= 448 * 2^e = 1.75 * 2^(e + 8): e = E - 135, one more when M > 0.75 * 128
+        const int e = min(max((int)(amax >> 7) - 135 + ((amax & 127u) > 96u ? 1 : 0), -14), 15);
+        const uint32_t top = ((uint32_t)(135 + e) << 7) | 96u;               // 448 * 2^e as bf16 bits; only e = 15 (clamped) can exceed it
+        m0 = min(m0, top);
+        m1 = min(m1, top);
+        const uint32_t cl = (two & 0x80008000u) | m0 | (m1 << 16);           // the signs stay, -0.0 too
+        const v2s r = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(v2s{0, 0}, __builtin_bit_cast(v2bf, cl), __uint_as_float((uint32_t)(127 + e) << 23), false);
+        ((uint16_t *)kv.data)[row * (HD / 2) + lane] = (uint16_t)r.x;
+        if (lane == 0) ((uint32_t *)kv.param)[row] = (uint32_t)(15 + e) << 10;   // fp16 (2^e, +0.0)
         return;
     }
     const float x0 = bf16f(two & 0xffffu), x1 = bf16f(two >> 16);

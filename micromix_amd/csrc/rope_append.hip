@@ -1,6 +1,6 @@
 // RoPE + paged KV append in one launch (include/micromix_hip.h, mm_rope_kv_append): reads q | k | v as the fused q/k/v projection leaves
 // them (three pointers, one token stride), rotates q and K by the caller's bf16 cos / sin rows, writes the rotated q contiguous and the
-// rotated K and V into the cache by the slot rule and the int4 rule of mm_kv_append (mx_paged_kv.h: the same code).
+// rotated K and V into the cache by the slot rule and the int4 / fp8 rule of mm_kv_append (mx_paged_kv.h: the same code).
 //
 // RoPE is HF's apply_rotary_pos_emb in bf16 tensor arithmetic, x * cos + rotate_half(x) * sin with every op rounded to bf16:
 //   a = bf16(x[d] * cos[d]);  b = bf16((d < 64 ? -x[d + 64] : x[d - 64]) * sin[d]);  y[d] = bf16(a + b)
@@ -46,14 +46,14 @@ __device__ inline uint32_t rope_pair(uint32_t x, uint32_t cs, uint32_t sn, int l
     return rope_one(x & 0xffffu, r & 0xffffu, cs & 0xffffu, sn & 0xffffu) | (rope_one(x >> 16, r >> 16, cs >> 16, sn >> 16) << 16);
 }
 
-template <bool INT4>
+template <int KIND>
 __global__ __launch_bounds__(64 * (2 + MAX_Q_WAVES)) void rope_kv_append_kernel(const RopeArgs a) {
     const int i = blockIdx.x, h = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t in = (int64_t)i * a.qkv_stride;
     if (wave == 1) {                                          // V: as mm_kv_append
         const uint32_t two = ((const uint32_t *)(a.v + in + (int64_t)h * HD))[lane];
         const int64_t row = append_row(a.kv, a.append_indptr, i, 1, h);
-        if (row >= 0) store_row<INT4>(a.kv, row, lane, two);
+        if (row >= 0) store_row<KIND>(a.kv, row, lane, two);
         return;
     }
     const uint32_t cs = ((const uint32_t *)(a.cos + (int64_t)i * a.cs_stride))[lane];
@@ -61,7 +61,7 @@ __global__ __launch_bounds__(64 * (2 + MAX_Q_WAVES)) void rope_kv_append_kernel(
     if (wave == 0) {                                          // K
         const uint32_t two = rope_pair(((const uint32_t *)(a.k + in + (int64_t)h * HD))[lane], cs, sn, lane);
         const int64_t row = append_row(a.kv, a.append_indptr, i, 0, h);
-        if (row >= 0) store_row<INT4>(a.kv, row, lane, two);
+        if (row >= 0) store_row<KIND>(a.kv, row, lane, two);
         return;
     }
     // q: every token, whatever its cache slot
@@ -96,8 +96,9 @@ hipError_t launch_rope_kv_append(const PagedKV &kv, const void *q, const void *k
     a.g = Hq / kv.Hkv;
     const dim3 grid(T, kv.Hkv);
     const int threads = 64 * (2 + (a.g < MAX_Q_WAVES ? a.g : MAX_Q_WAVES));
-    if (kv.int4) rope_kv_append_kernel<true><<<grid, threads, 0, stream>>>(a);
-    else rope_kv_append_kernel<false><<<grid, threads, 0, stream>>>(a);
+    if (kv.kind == KV_INT4) rope_kv_append_kernel<KV_INT4><<<grid, threads, 0, stream>>>(a);
+    else if (kv.kind == KV_FP8) rope_kv_append_kernel<KV_FP8><<<grid, threads, 0, stream>>>(a);
+    else rope_kv_append_kernel<KV_BF16><<<grid, threads, 0, stream>>>(a);
     return hipGetLastError();
 }
 

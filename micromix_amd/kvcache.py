@@ -1,6 +1,6 @@
 """A small paged KV cache for decode on top of `mixedgemm.kv_append` / `mixedgemm.paged_decode`.
 
-    cache = PagedKVCache(num_layers=32, num_kv_heads=8, page_size=16, max_pages=4096, batch=4, kind="int4")
+    cache = PagedKVCache(num_layers=32, num_kv_heads=8, page_size=16, max_pages=4096, batch=4, kind="int4")   # or "bf16", "fp8_e4m3"
     cache.extend(1)                        # one new token per sequence: pages allocated, page table updated (host side, before a graph)
     for layer in range(32):
         cache.append(layer, k, v)          # k, v bf16 [T, Hkv, 128], T = the tokens extend() announced
@@ -12,6 +12,10 @@
     for layer in range(32):
         cache.append(layer, k, v)          # k, v bf16 [T, Hkv, 128], T = 817
         o = cache.attend_new(layer, q)     # q bf16 [T, Hq, 128] -> o bf16 [T, Hq, 128], causal over each sequence's cache
+
+`kind` is "int4" (the reference's --kv_cache rule: asymmetric, 16 levels per 128-value row), "bf16" (exact, two bytes per value) or
+"fp8_e4m3" (OCP e4m3fn codes with a power-of-two scale per row: half the bytes of bf16, relative error at most 2^-4 per value, and
+attention that equals, bit for bit, attention over a bf16 cache of the dequantized values).  Nothing else in the class depends on it.
 
 The page table lives in device tensors of fixed capacity that `extend` rewrites in place, so `append` + `attend` (or `attend_new`) captured once into a
 hipGraph replay correctly after later `extend` calls, as long as T stays the same and the sequences stay within the captured
@@ -39,8 +43,8 @@ HEAD_DIM = 128
 
 class PagedKVCache:
     def __init__(self, num_layers, num_kv_heads, page_size, max_pages, batch, kind="int4", device="cuda", window=None, release=True, max_seq_len=None):
-        if kind not in ("int4", "bf16"):
-            raise ValueError("kind must be 'int4' or 'bf16'")
+        if kind not in ("int4", "bf16", "fp8_e4m3"):
+            raise ValueError("kind must be 'int4', 'bf16' or 'fp8_e4m3'")
         self.window = 0 if window is None else int(window)
         if self.window < 0:
             raise ValueError("window must be None, 0 (no window) or a positive token count")
@@ -53,8 +57,8 @@ class PagedKVCache:
         self.num_layers, self.num_kv_heads, self.page_size, self.max_pages, self.batch = num_layers, num_kv_heads, page_size, max_pages, batch
         self.kind, self.device = kind, dev
         shape = (max_pages, num_layers, 2, num_kv_heads, page_size)
-        if kind == "int4":
-            self.kv_data = torch.zeros(shape + (HEAD_DIM // 2,), dtype=torch.uint8, device=dev)
+        if kind in ("int4", "fp8_e4m3"):      # int4: two codes per byte; fp8 (OCP e4m3fn): one; both with fp16 (scale, zero) per row
+            self.kv_data = torch.zeros(shape + (HEAD_DIM // 2 if kind == "int4" else HEAD_DIM,), dtype=torch.uint8, device=dev)
             self.kv_param = torch.zeros(shape + (2,), dtype=torch.float16, device=dev)
         else:
             self.kv_data = torch.zeros(shape + (HEAD_DIM,), dtype=torch.bfloat16, device=dev)

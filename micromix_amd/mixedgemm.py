@@ -876,28 +876,37 @@ for _n in ("batch_decode_i4", "batch_decode_f16", "init_kv_i4", "init_kv_f16", "
 
 # ---- paged KV cache (include/micromix_hip.h, mm_kv_append / mm_paged_decode; micromix_amd/kvcache.py is the small cache object) ----
 
+def _kv_bytes(kv_data):
+    """an fp8 cache held as torch.float8_e4m3fn, seen as the uint8 tensor the ops take: the same bytes, OCP e4m3fn codes"""
+    return kv_data.view(torch.uint8) if isinstance(kv_data, torch.Tensor) and kv_data.dtype is torch.float8_e4m3fn else kv_data
+
+
 def _kv_geometry(kv_data, kv_param, index):
-    """(dtype code, max_pages, L, Hkv, P) of a cache; int4: uint8 [max_pages, L, 2, Hkv, P, 64] + fp16 params [..., P, 2],
-    bf16: bf16 [max_pages, L, 2, Hkv, P, 128] and kv_param None."""
+    """(dtype code, max_pages, L, Hkv, P, kv_data as the C ABI takes it) of a cache, recognised by its shape; int4: uint8
+    [max_pages, L, 2, Hkv, P, 64] + fp16 params [..., P, 2]; fp8: uint8 (or torch.float8_e4m3fn, viewed as uint8) [max_pages, L, 2, Hkv,
+    P, 128] + the same fp16 params; bf16: bf16 [max_pages, L, 2, Hkv, P, 128] and kv_param None."""
     if kv_param is None:
         if not _ok(kv_data, torch.bfloat16, index):
             _check_tensor(kv_data, "kv_data", torch.bfloat16)
             raise RuntimeError(f"kv_data must be on cuda:{index}")
         if kv_data.dim() != 6 or kv_data.size(2) != 2 or kv_data.size(5) != 128:
-            raise RuntimeError("bf16 kv_data must be [max_pages, L, 2, Hkv, P, 128]")
+            raise RuntimeError("bf16 kv_data (kv_param None) must be [max_pages, L, 2, Hkv, P, 128]; an int4 cache ([..., 64] uint8) and an "
+                               "fp8 cache ([..., 128] uint8 / float8_e4m3fn) need their fp16 kv_param")
         kind = _lib.MM_KV_BF16
     else:
+        kv_data = _kv_bytes(kv_data)
         if not (_ok(kv_data, torch.uint8, index) and _ok(kv_param, torch.float16, index)):
             _check_tensor(kv_data, "kv_data", torch.uint8)
             _check_tensor(kv_param, "kv_param", torch.float16, kv_data.device)
             raise RuntimeError(f"kv_data / kv_param must be on cuda:{index}")
-        if kv_data.dim() != 6 or kv_data.size(2) != 2 or kv_data.size(5) != 64:
-            raise RuntimeError("int4 kv_data must be [max_pages, L, 2, Hkv, P, 64] uint8")
+        if kv_data.dim() != 6 or kv_data.size(2) != 2 or kv_data.size(5) not in (64, 128):
+            raise RuntimeError("kv_data with a kv_param must be [max_pages, L, 2, Hkv, P, 64] uint8 (int4) or [max_pages, L, 2, Hkv, P, 128] "
+                               "uint8 / float8_e4m3fn (fp8); a bf16 cache [max_pages, L, 2, Hkv, P, 128] takes kv_param None")
         if tuple(kv_param.shape) != tuple(kv_data.shape[:5]) + (2,):
             raise RuntimeError("kv_param must be [max_pages, L, 2, Hkv, P, 2] fp16, matching kv_data")
-        kind = _lib.MM_KV_INT4
+        kind = _lib.MM_KV_INT4 if kv_data.size(5) == 64 else _lib.MM_KV_FP8_E4M3
     max_pages, L, _, Hkv, P, _ = kv_data.shape
-    return kind, max_pages, L, Hkv, P
+    return kind, max_pages, L, Hkv, P, kv_data
 
 
 def _page_table(kv_indptr, kv_indices, last_page_len, dev):
@@ -913,6 +922,8 @@ def _page_table(kv_indptr, kv_indices, last_page_len, dev):
 def _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, q=None):
     """The common checks of the four cache ops: (device, B, Hkv, the C arguments kv_data .. batch that every entry point takes in this
     order).  The device is q's (bf16, contiguous); an append has no q and takes the cache's."""
+    if kv_param is not None:
+        kv_data = _kv_bytes(kv_data)
     if q is None:
         if not (isinstance(kv_data, torch.Tensor) and kv_data.is_cuda):
             _check_tensor(kv_data, "kv_data", torch.uint8 if kv_param is not None else torch.bfloat16)
@@ -921,7 +932,7 @@ def _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx,
         if not (isinstance(q, torch.Tensor) and q.is_cuda and _ok(q, torch.bfloat16, q.get_device())):
             _check_tensor(q, "q", torch.bfloat16)
         dev = q.device
-    kind, max_pages, L, Hkv, P = _kv_geometry(kv_data, kv_param, dev.index)
+    kind, max_pages, L, Hkv, P, kv_data = _kv_geometry(kv_data, kv_param, dev.index)
     B = _page_table(kv_indptr, kv_indices, last_page_len, dev)
     layer_idx = int(layer_idx)
     if not 0 <= layer_idx < L:
@@ -956,7 +967,8 @@ def kv_append(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, k, v, app
     Not an export of the reference module (its append_kv_i4 / _f16 take K/V already quantized and one head count).  The page table
     (kv_indptr [B + 1], kv_indices, last_page_len [B], int32) already counts the new tokens; append_indptr [B + 1] splits the T tokens
     among the sequences, each sequence's go to its last positions.  kv_param None: bf16 cache (a copy); otherwise int4 codes + fp16
-    (scale, zero) by the rule of quantize_int_group(x, 4, 128) (include/micromix_hip.h).  Runs on the current stream, capture-safe.
+    (scale, zero) by the rule of quantize_int_group(x, 4, 128), or -- kv_data [..., 128] uint8 / float8_e4m3fn -- e4m3 codes with a
+    power-of-two scale per row and zero = 0 (include/micromix_hip.h, MM_KV_FP8_E4M3).  Runs on the current stream, capture-safe.
     """
     lib = _lib.load()
     dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx)
@@ -1000,7 +1012,8 @@ def rope_kv_append(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, q, k
     cos, sin: bf16 [T, 128], or HF's [1, T, 128] / [bsz, q_len, 128] (flattened): row i belongs to flat token i; a row stride is honoured.
     RoPE is HF's apply_rotary_pos_emb in bf16 arithmetic, q * cos + rotate_half(q) * sin with every op rounded to bf16, bit for bit
     (include/micromix_hip.h, mm_rope_kv_append).  The cache receives exactly what kv_append(rope(k), v) writes; q is rotated for every
-    token.  Page table and append_indptr as in `kv_append`.  Runs on the current stream, capture-safe.
+    token.  Page table, append_indptr and the three cache kinds (int4, fp8 e4m3, bf16) as in `kv_append`.  Runs on the current stream,
+    capture-safe.
     """
     lib = _lib.load()
     dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx)
@@ -1067,6 +1080,8 @@ def paged_decode(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, lay
     least paged_decode_workspace_bytes(...) bytes) is allocated here when None -- pass one when capturing a graph.
     `window` = W (HF's sliding_window; None or 0: none): the query attends the last W tokens of its sequence, its own included.  Only
     these tokens are read, the split is laid over W tokens, and page-table entries below the window may be -1.
+    The cache is int4, fp8 (e4m3) or bf16, told apart as in `kv_append`; over an fp8 cache the result equals, bit for bit, that over a
+    bf16 cache holding the dequantized values.
     """
     lib = _lib.load()
     window = _window(window)
@@ -1114,6 +1129,7 @@ def paged_prefill(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, qo
     paged_prefill_workspace_bytes(...) bytes) is allocated here when None -- pass one when capturing a graph.
     `window` = W (HF's sliding_window; None or 0: none): the token at position p attends positions max(0, p - W + 1) .. p; the kv tiles
     below a query tile's windows are not read, and page-table entries below every window may be -1.
+    The cache is int4, fp8 (e4m3) or bf16, told apart as in `kv_append`; fp8 runs p.V on bf16(p * scale_v) times the codes, as int4.
     """
     lib = _lib.load()
     window = _window(window)
