@@ -458,6 +458,25 @@ int mm_rope_kv_append(void *kv_data, void *kv_param, int kv_dtype, int max_pages
                       void *q_out_bf16, mm_stream_t stream);
 
 /*
+ * Page copy of the paged KV cache (detect it by its symbol; mm_version stays 660): what a sequence needs before it writes into a partly
+ * filled page that it shares with another sequence (copy-on-write; PagedKVCache.fork / extend).  Cache layout and kinds as above.
+ * mm_kv_copy_pages: for pair i, for every (layer, K / V, kv head), token rows [0, r_i) of page src_pages[i] go to the same rows of page
+ *   dst_pages[i]: the code bytes (64 / 128 / 256 per row for int4 / fp8 / bf16) and, for int4 and fp8, the fp16 (scale, zero) dword of
+ *   each row.  r_i = rows[i] clamped to [0, P]; rows == NULL: r_i = P, whole pages.  Bytes only: nothing is dequantized or rounded
+ *   again, and nothing outside those rows of those destination pages is written.
+ *   A pair is skipped (nothing read or written) when either index lies outside [0, max_pages), when src == dst, or when r_i <= 0.
+ *   Preconditions: the destination pages are pairwise distinct, and no destination page is a source of the same call (the pairs are
+ *   copied concurrently).  src_pages, dst_pages and rows are device int32 arrays of num_pairs entries.  kv_data is 16-byte aligned and
+ *   kv_param 4-byte aligned.  No workspace, no host reads of device arrays: capture-safe like mm_kv_append.
+ * Null kv_data, null kv_param for int4 / fp8, misaligned kv_data / kv_param, null src_pages / dst_pages with num_pairs > 0, non-positive
+ * geometry, negative num_pairs, an unassigned kv_dtype (2 included): MM_ERR_BAD_ARG; head_dim != 128, or a page of 2^31 or more 16-byte
+ * vectors at the bf16 width (2 L Hkv P >= 2^27): MM_ERR_UNSUPPORTED; num_pairs == 0: MM_OK; all without device work.
+ */
+int mm_kv_copy_pages(void *kv_data, void *kv_param, int kv_dtype, int max_pages, int num_layers, int num_kv_heads, int page_size,
+                     int head_dim, const int32_t *src_pages, const int32_t *dst_pages, const int32_t *rows /* or NULL */, int num_pairs,
+                     mm_stream_t stream);
+
+/*
  * Sparse MoE block around mm_reorder_quantize_grouped / mm_matmul_grouped (version >= 630): top-k routing of the gate logits, the
  * dispatch plan, the row gather and the weighted combine (the reference's MixtralSparseMoeBlock.forward, qMixtralLayer.py:414-452,
  * without its per-expert host loop).  T tokens, E experts, n = T * top_k (token, k-slot) pairs, pair p = t * top_k + j.

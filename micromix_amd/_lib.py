@@ -21,7 +21,7 @@ EXPORTS = (
     "mm_gate_up_activate", "mm_gate_up_activate_decode", "mm_rmsnorm_gate_up_activate_decode", "mm_rmsnorm_gate_up_activate_decode_supported", "mm_gate_up_activate_decode_supported", "mm_down_activate_decode", "mm_down_activate_decode_supported", "mm_down_activate_decode_supported_w", "mm_gate_up_activate_workspace_bytes", "mm_gate_up_activate_describe", "mm_rmsnorm_quantize", "mm_add_rmsnorm_quantize", "mm_add_rmsnorm_qlinear_decode", "mm_add_rmsnorm_gate_up_activate_decode", "mm_qlinear_decode", "mm_qlinear_decode_supported", "mm_qlinear_decode_supported_w", "mm_rmsnorm_qlinear_decode", "mm_rmsnorm_qlinear_decode_supported", "mm_rmsnorm_qlinear_decode_supported_w", "mm_matmul_grouped", "mm_reorder_quantize_grouped",
     "mm_matmul_describe", "mm_test_function", "mm_diag_set_kernel_events",
     "mm_kv_dtype_supported", "mm_kv_append", "mm_paged_decode_workspace_bytes", "mm_paged_decode",
-    "mm_paged_prefill_workspace_bytes", "mm_paged_prefill", "mm_rope_kv_append",
+    "mm_paged_prefill_workspace_bytes", "mm_paged_prefill", "mm_rope_kv_append", "mm_kv_copy_pages",
     "mm_paged_decode_window_workspace_bytes", "mm_paged_decode_window", "mm_paged_prefill_window_workspace_bytes", "mm_paged_prefill_window",
     "mm_moe_route", "mm_moe_plan", "mm_moe_gather", "mm_moe_combine",
     "mm_moe_sf_bytes", "mm_moe_quantize", "mm_moe_activate_quantize", "mm_moe_matmul_supported", "mm_moe_matmul",
@@ -169,6 +169,8 @@ def load():
     lib.mm_paged_prefill_window.argtypes = lib.mm_paged_prefill.argtypes + [i]
     lib.mm_rope_kv_append.restype = i
     lib.mm_rope_kv_append.argtypes = [vp, vp] + [i] * 7 + [vp] * 3 + [i, vp, vp, vp, ctypes.c_int64, i, vp, vp, ctypes.c_int64, vp, i, vp, vp]
+    lib.mm_kv_copy_pages.restype = i
+    lib.mm_kv_copy_pages.argtypes = [vp, vp] + [i] * 6 + [vp] * 3 + [i, vp]
     lib.mm_moe_route.restype = i
     lib.mm_moe_route.argtypes = [vp, i, i, i, vp, vp, vp]
     lib.mm_moe_plan.restype = i

@@ -692,6 +692,21 @@ int mm_rope_kv_append(void *kv_data, void *kv_param, int kv_dtype, int max_pages
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_rope_kv_append");
 }
 
+int mm_kv_copy_pages(void *kv_data, void *kv_param, int kv_dtype, int max_pages, int num_layers, int num_kv_heads, int page_size,
+                     int head_dim, const int32_t *src_pages, const int32_t *dst_pages, const int32_t *rows, int num_pairs,
+                     mm_stream_t stream) {
+    mm::PagedKV kv;                                           // no layer (0) and no page table: every layer of the named pages
+    if (int st = kv_geometry(kv_data, kv_param, kv_dtype, max_pages, num_layers, 0, num_kv_heads, page_size, head_dim, nullptr, nullptr,
+                             nullptr, 0, &kv)) return st;
+    if (num_pairs < 0 || !kv.data || (kv.kind != mm::KV_BF16 && !kv.param)) return MM_ERR_BAD_ARG;
+    if (((uintptr_t)kv_data & 15) || ((uintptr_t)kv_param & 3)) return MM_ERR_BAD_ARG;
+    if ((int64_t)num_layers * num_kv_heads > INT32_MAX / 32 / page_size) return MM_ERR_UNSUPPORTED;   // 2 L Hkv P rows of up to 16 vectors
+    if (num_pairs == 0) return MM_OK;
+    if (!src_pages || !dst_pages) return MM_ERR_BAD_ARG;
+    hipError_t e = mm::launch_kv_copy_pages(kv, src_pages, dst_pages, rows, num_pairs, (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_kv_copy_pages");
+}
+
 // the un-windowed entry points are the windowed ones at window = 0
 size_t mm_paged_decode_window_workspace_bytes(int batch, int num_qo_heads, int num_kv_heads, int max_seq_len, int window) {
     if (batch <= 0 || num_kv_heads <= 0 || num_qo_heads <= 0 || max_seq_len < 0 || window < 0 || num_qo_heads % num_kv_heads) return 0;

@@ -279,6 +279,9 @@ hipError_t launch_paged_decode(const PagedKV &kv, const void *q, int Hq, int max
 // RoPE + append in one launch (rope_append.hip): q | k | v share the token stride qkv_stride, cos | sin the stride cs_stride (elements)
 hipError_t launch_rope_kv_append(const PagedKV &kv, const void *q, const void *k, const void *v, int64_t qkv_stride, int Hq, const void *cos,
                                  const void *sin, int64_t cs_stride, const int *append_indptr, int T, void *q_out, hipStream_t stream);
+// rows [0, rows[i]) of page src_pages[i] -> page dst_pages[i], every layer, K and V, every head (kv_copy.hip); kv.layer is 0
+hipError_t launch_kv_copy_pages(const PagedKV &kv, const int *src_pages, const int *dst_pages, const int *rows, int num_pairs,
+                                hipStream_t stream);
 // sparse MoE block around the grouped GEMMs (moe.hip): n = T * top_k pairs, H a multiple of 8, rows 16-byte aligned
 hipError_t launch_moe_route(const void *logits, int T, int E, int top_k, int *ids, void *w, hipStream_t stream);
 hipError_t launch_moe_plan(const int *ids, int n, int E, int top_k, int *offsets, int *sorted_token, int *slot_of, hipStream_t stream);

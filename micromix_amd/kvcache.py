@@ -19,7 +19,7 @@ attention that equals, bit for bit, attention over a bf16 cache of the dequantiz
 
 The page table lives in device tensors of fixed capacity that `extend` rewrites in place, so `append` + `attend` (or `attend_new`) captured once into a
 hipGraph replay correctly after later `extend` calls, as long as T stays the same and the sequences stay within the captured
-`max_seq_len`.  The allocator is a free list; no prefix sharing.
+`max_seq_len`.  The allocator is a free list with a reference count per page, so sequences can share pages (below).
 
     cache = PagedKVCache(..., window=4096)  # HF's sliding_window: a token attends the last 4096 positions, its own included
 
@@ -31,6 +31,24 @@ and a long chat costs the window, not the history.  Without a window nothing is 
 alone), for callers who share pages between sequences.  The page table itself still grows by one entry per page_size tokens:
 `max_seq_len` sizes `kv_indices` for batch * ceil(max_seq_len / P) entries up front; past its capacity the tensor is replaced by a
 larger one, and a graph captured before that has to be captured again.
+
+    cache.fork(0, 1)                        # sequence 1 = sequence 0, no byte copied: n samples of one prompt, beams, a shared system prompt
+    cache.fork(0, 2, length=21)             # ... or its first 21 tokens
+    cache.truncate(1, cache.seq_lens[1] - 3)   # drop the last 3 tokens: the rejected part of a speculative draft
+
+Sharing.  `fork` gives `dst` the page list of `src` and raises each page's count; `truncate`, `reset` and the window's release lower
+counts, and a page returns to the free list when its last owner lets go.  The rule: a page is written only by a sequence that is its
+sole owner.  The only page a sequence ever writes that may already hold tokens is its last one, so `extend` checks exactly that: a
+sequence about to receive tokens whose last page is partly filled (in its own view) and counted more than once first takes a fresh
+page, swaps it into its list and drops its reference to the old one; the rows it holds there, [0, seq_len % P), are copied by one
+`mixedgemm.kv_copy_pages` launch for all such sequences of the call (copy-on-write; on a CPU cache, by slice assignment), on the current
+stream before `extend` returns, so before any later `append`.  Full shared pages are never copied, and neither is anything when the
+other owners have let go in the meantime.  Tokens past a sequence's length on a page it owns alone are simply overwritten.
+With a window, a fork or truncate to `length` is refused (ValueError) when it would keep a released page inside the window of the shorter
+sequence -- unless released_pages * P <= max(0, length - W) -- because the -1 entries would silently mask tokens it must attend.
+Shared pages are listed once per owner, so the page table can outgrow `max_pages` entries; `max_seq_len` sizes it as above.
+Graphs captured earlier stay valid across `fork`, `truncate` and a copying `extend` (the tables are rewritten in place), replayed on a
+stream ordered after the `extend`.  `pages_in_use` is the number of pages off the free list.
 """
 from __future__ import annotations
 
@@ -66,6 +84,7 @@ class PagedKVCache:
         self._free = list(range(max_pages - 1, -1, -1))        # pop() hands out low page numbers first
         self._pages = [[] for _ in range(batch)]                # -1: a page released below the window; its entry keeps its place
         self._released = [0] * batch                            # leading entries of _pages[b] that are -1
+        self._ref = [0] * max_pages                             # entries of _pages that name the page; 0: the page is in _free, once
         self.seq_lens = [0] * batch
         i32 = dict(dtype=torch.int32, device=dev)
         self.kv_indptr = torch.zeros((batch + 1,), **i32)
@@ -98,10 +117,36 @@ class PagedKVCache:
         self.append_indptr.copy_(torch.tensor(app, dtype=torch.int32))
         self.num_new_tokens = app[-1]
 
+    @property
+    def pages_in_use(self):
+        return self.max_pages - len(self._free)
+
+    def _unref(self, page):
+        self._ref[page] -= 1
+        if self._ref[page] == 0:
+            self._free.append(page)
+
+    def _take(self):
+        page = self._free.pop()
+        self._ref[page] = 1
+        return page
+
+    def _copy_pages(self, pairs):
+        """rows [0, r) of page `old` -> page `new` for every (old, new, r): one launch on the current stream"""
+        if self.device.type == "cpu":                            # the host tests' path, and the copy rule in plain words
+            for old, new, r in pairs:
+                self.kv_data[new, :, :, :, :r] = self.kv_data[old, :, :, :, :r]
+                if self.kv_param is not None:
+                    self.kv_param[new, :, :, :, :r] = self.kv_param[old, :, :, :, :r]
+            return
+        src, dst, rows = (torch.tensor(c, dtype=torch.int32).to(self.device) for c in zip(*pairs))
+        mixedgemm.kv_copy_pages(self.kv_data, self.kv_param, src, dst, rows)
+
     def extend(self, new_tokens_per_seq):
         """Announce the next tokens: an int (the same count for every sequence) or one count per sequence.  Allocates pages and
         rewrites the page table in place (host -> device copies; call it outside graph capture).  The following `append` calls of
-        every layer take exactly sum(counts) tokens, sequence by sequence."""
+        every layer take exactly sum(counts) tokens, sequence by sequence.  A sequence whose partly filled last page is shared gets
+        its own copy first (the module docstring, "Sharing")."""
         new = [int(new_tokens_per_seq)] * self.batch if isinstance(new_tokens_per_seq, int) else [int(n) for n in new_tokens_per_seq]
         if len(new) != self.batch or min(new) < 0:
             raise ValueError(f"need {self.batch} non-negative token counts")
@@ -109,25 +154,85 @@ class PagedKVCache:
         # pages wholly below the lowest position the announced tokens attend (n = 0: a decode query at the last position)
         drop = [max(self._released[b], min((self.seq_lens[b] + n - max(n, 1) - self.window + 1) // self.page_size, len(self._pages[b])))
                 if self.release else 0 for b, n in enumerate(new)]
-        freed = sum(drop[b] - self._released[b] for b in range(self.batch))
-        if sum(need) > len(self._free) + freed:
-            raise RuntimeError(f"out of pages: {sum(need)} needed, {len(self._free) + freed} free")
+        # a dry run of the counts, in the order of the real one below: a released page is gained only when its last owner lets go,
+        # and of the sequences that share a partly filled last page all but the last to be served need a copy (and a page for it)
+        less, freed, cow = {}, 0, []
+        for b in range(self.batch):
+            for p in self._pages[b][self._released[b]:drop[b]]:
+                less[p] = less.get(p, 0) + 1
+                freed += self._ref[p] == less[p]
+        for b, n in enumerate(new):
+            if n and self.seq_lens[b] % self.page_size:
+                p = self._pages[b][-1]
+                if self._ref[p] - less.get(p, 0) > 1:
+                    less[p] = less.get(p, 0) + 1
+                    cow.append(b)
+        if sum(need) + len(cow) > len(self._free) + freed:
+            raise RuntimeError(f"out of pages: {sum(need) + len(cow)} needed, {len(self._free) + freed} free")
         for b in range(self.batch):                              # releases first: another sequence's new tokens may take these pages
             for i in range(self._released[b], drop[b]):
-                self._free.append(self._pages[b][i])
+                self._unref(self._pages[b][i])
                 self._pages[b][i] = -1
             self._released[b] = drop[b]
+        pairs = []
         for b, n in enumerate(new):
-            self._pages[b] += [self._free.pop() for _ in range(need[b])]
+            if b in cow:                                         # the sole-owner rule: its own copy of the rows it holds there
+                old, self._pages[b][-1] = self._pages[b][-1], self._take()
+                self._unref(old)
+                pairs.append((old, self._pages[b][-1], self.seq_lens[b] % self.page_size))
+            self._pages[b] += [self._take() for _ in range(need[b])]
             self.seq_lens[b] += n
         self._upload(new)
+        if pairs:
+            self._copy_pages(pairs)
+
+    def _shorten(self, seq, length):
+        """keep the first `length` tokens of `seq`: the pages wholly past them lose a reference"""
+        keep = -(-length // self.page_size)
+        for p in reversed(self._pages[seq][keep:]):
+            if p >= 0:                                           # a released entry's reference is gone already
+                self._unref(p)
+        del self._pages[seq][keep:]
+        self._released[seq] = min(self._released[seq], keep)
+        self.seq_lens[seq] = length
+
+    def _check_length(self, seq, length, what):
+        if not 0 <= length <= self.seq_lens[seq]:
+            raise ValueError(f"{what}: length {length} outside [0, {self.seq_lens[seq]}], the tokens sequence {seq} holds")
+        kept = min(self._released[seq], -(-length // self.page_size))
+        if kept * self.page_size > max(0, length - self.window):
+            raise ValueError(f"{what}: the first {kept} pages of sequence {seq} were released below its window; {length} tokens with a "
+                             f"window of {self.window} would attend tokens on them")
+
+    def fork(self, src, dst, length=None):
+        """Sequence `dst` becomes a copy of the first `length` tokens of `src` (default: all) without copying anything: `dst` is reset,
+        then lists the same pages, released entries included, and each page's count goes up.  length 0 is a reset.  ValueError for src == dst,
+        a length outside [0, seq_lens[src]] and a length that would put a released page inside the window (the module docstring).
+        Rewrites the page table on the device like `extend` (outside graph capture)."""
+        length = self.seq_lens[src] if length is None else int(length)
+        if src == dst:
+            raise ValueError("fork: src and dst are the same sequence")
+        self._check_length(src, length, "fork")
+        self._shorten(dst, 0)
+        self._pages[dst] = self._pages[src][: -(-length // self.page_size)]
+        for p in self._pages[dst]:
+            if p >= 0:
+                self._ref[p] += 1
+        self._released[dst] = min(self._released[src], len(self._pages[dst]))
+        self.seq_lens[dst] = length
+        self._upload([0] * self.batch)
+
+    def truncate(self, seq, length):
+        """Drop the tokens of `seq` at and past `length` (the rejected part of a speculative draft).  Nothing is copied; pages wholly
+        past `length` lose a reference.  ValueError as for `fork`.  Outside graph capture."""
+        length = int(length)
+        self._check_length(seq, length, "truncate")
+        self._shorten(seq, length)
+        self._upload([0] * self.batch)
 
     def reset(self, seq):
-        """Empty sequence `seq` and return its pages to the free list (outside graph capture)."""
-        self._free += [p for p in reversed(self._pages[seq]) if p >= 0]      # a released entry's page is in the list already
-        self._pages[seq] = []
-        self._released[seq] = 0
-        self.seq_lens[seq] = 0
+        """Empty sequence `seq`: its pages lose a reference, and those it owned alone return to the free list (outside graph capture)."""
+        self._shorten(seq, 0)
         self._upload([0] * self.batch)
 
     def append(self, layer, k, v):

@@ -30,7 +30,7 @@ from . import _lib
 
 __all__ = ["test_function", "matmul", "gate_up_activate", "interleave_gate_up", "reorder_quantize_x", "reorder_quantize_w", "reorder_quantize_w4", "activate_quantize_x",
            "downproj_quantize_w", "downproj_quantize_w4", "rmsnorm_quantize_x", "qlinear_decode", "qlinear_decode_supported", "matmul_grouped", "reorder_quantize_x_grouped",
-           "kv_append", "rope_kv_append", "paged_decode", "paged_decode_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes",
+           "kv_append", "rope_kv_append", "kv_copy_pages", "paged_decode", "paged_decode_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes",
            "moe_route", "moe_plan", "moe_gather", "moe_combine",
            "moe_expert_table", "moe_sf_bytes", "moe_quantize", "moe_activate_quantize", "moe_matmul", "moe_matmul_supported",
            "permute_packed_rows", "moe_gate_up_table", "moe_gate_up_activate", "moe_gate_up_activate_supported"]
@@ -985,6 +985,35 @@ def kv_append(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, k, v, app
         st = lib.mm_kv_append(*kv_args, _ptr(k), _ptr(v), _ptr(append_indptr), k.size(0), _stream_ptr(dev))
     if st:
         _lib.check(st, "kv_append")
+
+
+def kv_copy_pages(kv_data, kv_param, src_pages, dst_pages, rows=None):
+    """Copy token rows [0, rows[i]) of page src_pages[i] to page dst_pages[i] of a paged cache, for every layer, K and V, every head, in
+    place; returns None.  rows None: whole pages.  Bytes only (codes and, for int4 / fp8, the fp16 params): no dequantization.
+
+    src_pages, dst_pages, rows: int32 device tensors of one length.  A pair whose page index lies outside the cache, with src == dst or
+    with rows <= 0 is skipped; rows above the page size count as the page size.  The destination pages must be pairwise distinct and
+    none of them a source of the same call (include/micromix_hip.h, mm_kv_copy_pages).  What PagedKVCache.extend calls before a sequence
+    writes into a partly filled page it shares.  Runs on the current stream, capture-safe."""
+    lib = _lib.load()
+    if kv_param is not None:
+        kv_data = _kv_bytes(kv_data)
+    if not (isinstance(kv_data, torch.Tensor) and kv_data.is_cuda):
+        _check_tensor(kv_data, "kv_data", torch.uint8 if kv_param is not None else torch.bfloat16)
+    dev = kv_data.device
+    kind, max_pages, L, Hkv, P, kv_data = _kv_geometry(kv_data, kv_param, dev.index)
+    index = [("src_pages", src_pages), ("dst_pages", dst_pages)] + ([("rows", rows)] if rows is not None else [])
+    for n, t in index:
+        if not _ok(t, torch.int32, dev.index):
+            _check_tensor(t, n, torch.int32, dev)
+        if t.dim() != 1 or t.numel() != src_pages.numel():
+            raise RuntimeError("src_pages, dst_pages and rows must be one-dimensional and of one length")
+    with _on_device(dev.index):
+        st = lib.mm_kv_copy_pages(_ptr(kv_data), _ptr(kv_param) if kv_param is not None else None, kind, max_pages, L, Hkv, P, 128,
+                                  _ptr(src_pages), _ptr(dst_pages), _ptr(rows) if rows is not None else None, src_pages.numel(),
+                                  _stream_ptr(dev))
+    if st:
+        _lib.check(st, "kv_copy_pages")
 
 
 def _token_rows(t, name, heads):
