@@ -477,6 +477,40 @@ int mm_kv_copy_pages(void *kv_data, void *kv_param, int kv_dtype, int max_pages,
                      mm_stream_t stream);
 
 /*
+ * Shared-prefix decode over the paged KV cache (detect the two entries by their symbols; mm_version stays 660): mm_paged_decode for a
+ * batch in which groups of sequences hold a leading run of pages in common (n samples of one prompt, beams, a system prompt;
+ * PagedKVCache.fork).  The result is the same function as mm_paged_decode -- every sequence attends all of its own tokens -- within the
+ * same error budget (the sums run in another order, so not the same bits).  The shared tokens are walked once per slab of
+ * floor(16 / g) group members, whose queries fill the rows of one MFMA operand that g heads leave idle; every sequence's own tail is
+ * walked on its own.  q, the cache, the page table, head rules, sm_scale and o as mm_paged_decode.
+ *   group_indptr [batch + 1], group_members [batch], shared_len [batch]: int32 device arrays of fixed size, read by the kernels only,
+ *   so one captured graph stays valid while the sharing changes between replays.  Group j is
+ *   group_members[group_indptr[j] .. group_indptr[j + 1]); unused trailing groups are empty (group_indptr[j] = batch); group_members is
+ *   a permutation of 0 .. batch - 1.  shared_len[b] is the number of leading tokens sequence b has on the same pages as the other
+ *   members of its group: the same value for every member, at most every member's length, not necessarily a multiple of the page size
+ *   (right after a fork the partly filled last page is shared too).  A sequence that shares nothing is a group of one with shared_len 0.
+ *   The shared tokens are read through the page list of a slab's first member.
+ *   When the arrays break these rules the results of the affected sequences are unspecified, and nothing is read or written outside
+ *   the cache, the tables, the workspace and o: member indices outside [0, batch) are ignored, a walk never passes the length of the
+ *   sequence whose page list it reads, and page numbers outside [0, max_pages) are skipped as everywhere else.
+ *   max_shared_len bounds the shared counts and max_suffix_len the tails (length - shared count), each in [0, 2^29].  The two chunk
+ *   counts and the workspace size depend on (batch, Hq, Hkv, max_shared_len, max_suffix_len) alone; the last chunk of either range runs
+ *   to the real end, whatever the bound said.  The call always goes through `workspace` (mm_paged_decode_shared_workspace_bytes, never 0
+ *   for arguments the call accepts with batch > 0; 16-byte aligned, not shared with a concurrent call): three launches, prefix, tails,
+ *   merge.  No host read of a device array: capture-safe.
+ *   No sliding window here: every member's window begins at a different place, which is a different problem.
+ * Null pointers, bad sizes, Hq not a multiple of Hkv, a bound outside [0, 2^29], a missing, small or misaligned workspace:
+ * MM_ERR_BAD_ARG; head_dim != 128 or g > 16: MM_ERR_UNSUPPORTED; batch = 0: MM_OK; all without device work.
+ */
+size_t mm_paged_decode_shared_workspace_bytes(int batch, int num_qo_heads, int num_kv_heads, int max_shared_len, int max_suffix_len);
+int mm_paged_decode_shared(const void *q_bf16, const void *kv_data, const void *kv_param, int kv_dtype, int max_pages, int num_layers,
+                           int layer, int num_kv_heads, int page_size, int head_dim, const int32_t *kv_indptr, const int32_t *kv_indices,
+                           const int32_t *last_page_len, int batch, int num_qo_heads, const int32_t *group_indptr /* [batch + 1] */,
+                           const int32_t *group_members /* [batch] */, const int32_t *shared_len /* [batch], per sequence */,
+                           int max_shared_len, int max_suffix_len, float sm_scale, void *workspace, size_t workspace_bytes, void *o_bf16,
+                           mm_stream_t stream);
+
+/*
  * Sparse MoE block around mm_reorder_quantize_grouped / mm_matmul_grouped (version >= 630): top-k routing of the gate logits, the
  * dispatch plan, the row gather and the weighted combine (the reference's MixtralSparseMoeBlock.forward, qMixtralLayer.py:414-452,
  * without its per-expert host loop).  T tokens, E experts, n = T * top_k (token, k-slot) pairs, pair p = t * top_k + j.

@@ -23,6 +23,7 @@ EXPORTS = (
     "mm_kv_dtype_supported", "mm_kv_append", "mm_paged_decode_workspace_bytes", "mm_paged_decode",
     "mm_paged_prefill_workspace_bytes", "mm_paged_prefill", "mm_rope_kv_append", "mm_kv_copy_pages",
     "mm_paged_decode_window_workspace_bytes", "mm_paged_decode_window", "mm_paged_prefill_window_workspace_bytes", "mm_paged_prefill_window",
+    "mm_paged_decode_shared_workspace_bytes", "mm_paged_decode_shared",
     "mm_moe_route", "mm_moe_plan", "mm_moe_gather", "mm_moe_combine",
     "mm_moe_sf_bytes", "mm_moe_quantize", "mm_moe_activate_quantize", "mm_moe_matmul_supported", "mm_moe_matmul",
     "mm_moe_gate_up_activate_supported", "mm_moe_gate_up_activate_describe", "mm_moe_gate_up_activate",
@@ -171,6 +172,11 @@ def load():
     lib.mm_rope_kv_append.argtypes = [vp, vp] + [i] * 7 + [vp] * 3 + [i, vp, vp, vp, ctypes.c_int64, i, vp, vp, ctypes.c_int64, vp, i, vp, vp]
     lib.mm_kv_copy_pages.restype = i
     lib.mm_kv_copy_pages.argtypes = [vp, vp] + [i] * 6 + [vp] * 3 + [i, vp]
+    if hasattr(lib, "mm_paged_decode_shared"):         # detected by symbol: a library built before it lacks the pair
+        lib.mm_paged_decode_shared_workspace_bytes.restype = sz
+        lib.mm_paged_decode_shared_workspace_bytes.argtypes = [i] * 5
+        lib.mm_paged_decode_shared.restype = i
+        lib.mm_paged_decode_shared.argtypes = [vp, vp, vp] + [i] * 7 + [vp] * 3 + [i, i, vp, vp, vp, i, i, ctypes.c_float, vp, sz, vp, vp]
     lib.mm_moe_route.restype = i
     lib.mm_moe_route.argtypes = [vp, i, i, i, vp, vp, vp]
     lib.mm_moe_plan.restype = i

@@ -2,6 +2,7 @@
 #include "../../include/micromix_hip.h"
 #include "mx_common.h"
 #include "mx_kernels.h"
+#include "mx_kv_shared_host.h"
 
 #include <stdio.h>
 #include <string.h>
@@ -740,6 +741,29 @@ int mm_paged_decode(const void *q_bf16, const void *kv_data, const void *kv_para
                     size_t workspace_bytes, void *o_bf16, mm_stream_t stream) {
     return mm_paged_decode_window(q_bf16, kv_data, kv_param, kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size, head_dim, kv_indptr,
                                   kv_indices, last_page_len, batch, num_qo_heads, max_seq_len, sm_scale, workspace, workspace_bytes, o_bf16, stream, 0);
+}
+
+// shared-prefix decode: the sizes, the split and the workspace rules are mx_kv_shared_host.h's
+size_t mm_paged_decode_shared_workspace_bytes(int batch, int num_qo_heads, int num_kv_heads, int max_shared_len, int max_suffix_len) {
+    return mm::kv_shared_workspace_bytes(batch, num_qo_heads, num_kv_heads, max_shared_len, max_suffix_len);
+}
+
+int mm_paged_decode_shared(const void *q_bf16, const void *kv_data, const void *kv_param, int kv_dtype, int max_pages, int num_layers, int layer,
+                           int num_kv_heads, int page_size, int head_dim, const int32_t *kv_indptr, const int32_t *kv_indices,
+                           const int32_t *last_page_len, int batch, int num_qo_heads, const int32_t *group_indptr,
+                           const int32_t *group_members, const int32_t *shared_len, int max_shared_len, int max_suffix_len, float sm_scale,
+                           void *workspace, size_t workspace_bytes, void *o_bf16, mm_stream_t stream) {
+    mm::PagedKV kv;
+    if (int st = kv_geometry(kv_data, kv_param, kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size, head_dim, kv_indptr, kv_indices,
+                             last_page_len, batch, &kv)) return st;
+    if (int st = mm::kv_shared_sizes_status(batch, num_qo_heads, num_kv_heads, max_shared_len, max_suffix_len)) return st;
+    if (batch == 0) return MM_OK;
+    if (!q_bf16 || !kv_pointers(kv) || !o_bf16 || !group_indptr || !group_members || !shared_len) return MM_ERR_BAD_ARG;
+    const size_t need = mm::kv_shared_workspace_bytes(batch, num_qo_heads, num_kv_heads, max_shared_len, max_suffix_len);
+    if (int st = mm::kv_shared_workspace_status(workspace, workspace_bytes, need)) return st;
+    hipError_t e = mm::launch_paged_decode_shared(kv, q_bf16, num_qo_heads, group_indptr, group_members, shared_len, max_shared_len,
+                                                  max_suffix_len, sm_scale, workspace, o_bf16, (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_paged_decode_shared");
 }
 
 size_t mm_paged_prefill_window_workspace_bytes(int num_tokens, int batch, int num_qo_heads, int num_kv_heads, int max_seq_len, int window) {

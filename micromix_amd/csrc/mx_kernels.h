@@ -276,6 +276,10 @@ size_t kv_decode_workspace_bytes(int B, int Hq, int Hkv, int max_seq_len, int wi
 hipError_t launch_kv_append(const PagedKV &kv, const void *k, const void *v, const int *append_indptr, int T, hipStream_t stream);
 hipError_t launch_paged_decode(const PagedKV &kv, const void *q, int Hq, int max_seq_len, int window, float sm_scale, void *ws, void *o,
                                hipStream_t stream);
+// decode over sequences that share leading pages (kv_cache.hip; the host rules and the split: mx_kv_shared_host.h); ws always used
+hipError_t launch_paged_decode_shared(const PagedKV &kv, const void *q, int Hq, const int *group_indptr, const int *group_members,
+                                      const int *shared_len, int max_shared_len, int max_suffix_len, float sm_scale, void *ws, void *o,
+                                      hipStream_t stream);
 // RoPE + append in one launch (rope_append.hip): q | k | v share the token stride qkv_stride, cos | sin the stride cs_stride (elements)
 hipError_t launch_rope_kv_append(const PagedKV &kv, const void *q, const void *k, const void *v, int64_t qkv_stride, int Hq, const void *cos,
                                  const void *sin, int64_t cs_stride, const int *append_indptr, int T, void *q_out, hipStream_t stream);

@@ -49,6 +49,23 @@ sequence -- unless released_pages * P <= max(0, length - W) -- because the -1 en
 Shared pages are listed once per owner, so the page table can outgrow `max_pages` entries; `max_seq_len` sizes it as above.
 Graphs captured earlier stay valid across `fork`, `truncate` and a copying `extend` (the tables are rewritten in place), replayed on a
 stream ordered after the `extend`.  `pages_in_use` is the number of pages off the free list.
+
+    o = cache.attend(layer, q, shared=True)    # the same attention; tokens that forked sequences share are read once, not once each
+
+Shared-prefix decode.  `attend(shared=True)` calls `mixedgemm.paged_decode_shared`: the sequences of a group put their queries into the
+rows of one matrix operand -- 16 // (Hq // Hkv) sequences to a slab, 4 for Llama-3-8B -- and one walk over the tokens they share serves
+the slab; each sequence's own tail is walked as before and a merge launch combines the two.  The result is within the same budget as
+`attend()` but not the same bits (the sums run in another order).  The groups come from `share_groups()`, which every table change
+(`extend`, `fork`, `truncate`, `reset`) recomputes and writes, in place, into three int32 device tensors of fixed size made in
+`__init__` (`group_indptr` [B + 1], `group_members` [B], `shared_len` [B]): a graph captured with `shared=True` stays valid while groups
+form and dissolve.  `shared=True` always takes this path, also when nothing is shared -- then it costs three launches where `attend()`
+has one or two -- so a graph captured before the first fork needs no second capture.  `share_groups()` puts a sequence into the first
+group whose leader lists the same first page and gives the group the number of leading pages on which ALL its members agree (times the
+page size, capped at the shortest member): a beam tree whose branches share different depths gets the depth common to the whole tree,
+which is correct and not optimal; a caller who wants more passes its own groups to `mixedgemm.paged_decode_shared`.  A cache with a
+window refuses `shared=True` (ValueError): every member's window begins elsewhere.  `shared=False`, the default, is the call it was.
+Measured (Llama-3-8B heads): 1.2 x faster for 64 samples of a 4 096-token prompt, slower for 8 samples of it, for 64 samples
+of 1 024 tokens and when nothing is shared -- take it for many samples of a long prompt.
 """
 from __future__ import annotations
 
@@ -92,8 +109,13 @@ class PagedKVCache:
         self.kv_indices = torch.zeros((max(max_pages, batch * -(-int(max_seq_len or 0) // page_size)),), **i32)
         self.last_page_len = torch.zeros((batch,), **i32)
         self.append_indptr = torch.zeros((batch + 1,), **i32)
+        # the groups of attend(shared=True), one tensor so that a table change costs one more copy: views of fixed size and address
+        self._group_table = torch.tensor(list(range(batch + 1)) + list(range(batch)) + [0] * batch, **i32)   # nobody shares yet
+        self.group_indptr, self.group_members, self.shared_len = self._group_table.split([batch + 1, batch, batch])
+        self._max_shared = self._max_suffix = 0                 # the largest shared count and the longest tail now
         self.num_new_tokens = 0
         self._workspace = None
+        self._shared_workspace = None
         self._prefill_workspace = None
         self._retired = []
 
@@ -116,6 +138,41 @@ class PagedKVCache:
         self.last_page_len.copy_(torch.tensor(last, dtype=torch.int32))
         self.append_indptr.copy_(torch.tensor(app, dtype=torch.int32))
         self.num_new_tokens = app[-1]
+        groups, shared = self.share_groups()
+        gptr = [0]
+        for grp in groups:
+            gptr.append(gptr[-1] + len(grp))
+        gptr += [self.batch] * (self.batch + 1 - len(gptr))    # the unused trailing groups are empty
+        self._group_table.copy_(torch.tensor(gptr + [b for grp in groups for b in grp] + shared, dtype=torch.int32))
+        self._max_shared = max(shared)
+        self._max_suffix = max(n - c for n, c in zip(self.seq_lens, shared))
+
+    def share_groups(self):
+        """(groups, shared): the grouping `attend(shared=True)` uses, from the page lists alone (host only; works on a CPU cache).
+        groups: lists of sequence indices that together hold every sequence once; shared[b]: the leading tokens sequence b has on the
+        same pages as the rest of its group.  Sequences are taken in index order; b joins the first group whose leader (its first
+        member) lists the same page, a real one (>= 0), in entry 0, and opens a group otherwise.  A group shares
+        page_size * (leading entries on which all its members agree), capped at its shortest member's length; a group of one shares 0."""
+        groups = []
+        for b, pages in enumerate(self._pages):
+            for grp in groups:
+                lead = self._pages[grp[0]]
+                if pages and lead and pages[0] >= 0 and pages[0] == lead[0]:
+                    grp.append(b)
+                    break
+            else:
+                groups.append([b])
+        shared = [0] * self.batch
+        for grp in groups:
+            if len(grp) > 1:
+                lists = [self._pages[b] for b in grp]
+                n = 0
+                while n < min(map(len, lists)) and lists[0][n] >= 0 and all(x[n] == lists[0][n] for x in lists):
+                    n += 1
+                count = min(n * self.page_size, min(self.seq_lens[b] for b in grp))
+                for b in grp:
+                    shared[b] = count
+        return groups, shared
 
     @property
     def pages_in_use(self):
@@ -250,9 +307,26 @@ class PagedKVCache:
         return mixedgemm.rope_kv_append(self.kv_data, self.kv_param, self.kv_indptr, self.kv_indices, self.last_page_len, q, k, v, cos, sin,
                                         self.append_indptr, layer)
 
-    def attend(self, layer, q, max_seq_len=None, sm_scale=None):
+    def attend(self, layer, q, max_seq_len=None, sm_scale=None, *, shared=False, max_shared_len=None):
         """Decode attention of q (bf16 [B, Hq, 128]) over `layer`.  max_seq_len defaults to the longest sequence now (host
-        bookkeeping, no device sync); under graph capture pass the bound the replays will stay within."""
+        bookkeeping, no device sync); under graph capture pass the bound the replays will stay within.
+        shared=True: the same attention through `mixedgemm.paged_decode_shared` over the groups of `share_groups()` (the module
+        docstring, "Shared-prefix decode"), always, whether or not anything is shared.  Its two bounds default to host bookkeeping, the
+        largest shared count and the longest tail now; under capture pass max_seq_len, which then bounds the tails, and max_shared_len."""
+        if shared:
+            if self.window:
+                raise ValueError("attend(shared=True) has no sliding-window form: this cache was made with window="
+                                 f"{self.window}; use attend()")
+            most = self._max_shared if max_shared_len is None else int(max_shared_len)
+            tail = self._max_suffix if max_seq_len is None else int(max_seq_len)
+            need = mixedgemm.paged_decode_shared_workspace_bytes(self.batch, q.size(1), self.num_kv_heads, most, tail)
+            if need and (self._shared_workspace is None or self._shared_workspace.numel() < need):
+                if self._shared_workspace is not None:
+                    self._retired.append(self._shared_workspace)      # a graph captured earlier may still point at it
+                self._shared_workspace = torch.empty((need,), dtype=torch.uint8, device=self.device)
+            return mixedgemm.paged_decode_shared(q, self.kv_data, self.kv_param, self.kv_indptr, self.kv_indices, self.last_page_len, layer,
+                                                 self.group_indptr, self.group_members, self.shared_len, most, tail, sm_scale=sm_scale,
+                                                 workspace=self._shared_workspace if need else None)
         bound = max(self.seq_lens) if max_seq_len is None else int(max_seq_len)
         need = mixedgemm.paged_decode_workspace_bytes(self.batch, q.size(1), self.num_kv_heads, bound, self.window)
         if need and (self._workspace is None or self._workspace.numel() < need):

@@ -30,7 +30,7 @@ from . import _lib
 
 __all__ = ["test_function", "matmul", "gate_up_activate", "interleave_gate_up", "reorder_quantize_x", "reorder_quantize_w", "reorder_quantize_w4", "activate_quantize_x",
            "downproj_quantize_w", "downproj_quantize_w4", "rmsnorm_quantize_x", "qlinear_decode", "qlinear_decode_supported", "matmul_grouped", "reorder_quantize_x_grouped",
-           "kv_append", "rope_kv_append", "kv_copy_pages", "paged_decode", "paged_decode_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes",
+           "kv_append", "rope_kv_append", "kv_copy_pages", "paged_decode", "paged_decode_workspace_bytes", "paged_decode_shared", "paged_decode_shared_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes",
            "moe_route", "moe_plan", "moe_gather", "moe_combine",
            "moe_expert_table", "moe_sf_bytes", "moe_quantize", "moe_activate_quantize", "moe_matmul", "moe_matmul_supported",
            "permute_packed_rows", "moe_gate_up_table", "moe_gate_up_activate", "moe_gate_up_activate_supported"]
@@ -1135,6 +1135,69 @@ def paged_decode(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, lay
     if st:
         _lib.check(st, "paged_decode")
     return o
+
+
+def _shared_lib():
+    lib = _lib.load()
+    if not hasattr(lib, "mm_paged_decode_shared"):
+        raise _lib.MicroMixLibraryError("libmicromix_hip.so has no mm_paged_decode_shared: it was built before shared-prefix decode; "
+                                        "rebuild it with `python -m micromix_amd.build --force`")
+    return lib
+
+
+def paged_decode_shared_workspace_bytes(B, Hq, Hkv, max_shared_len, max_suffix_len):
+    """bytes of fp32 scratch paged_decode_shared needs for these bounds: the partials of its prefix and tail chunks (never 0 for B > 0
+    and sizes the call takes; 0 for sizes it refuses)"""
+    return int(_shared_lib().mm_paged_decode_shared_workspace_bytes(int(B), int(Hq), int(Hkv), int(max_shared_len), int(max_suffix_len)))
+
+
+def paged_decode_shared(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, group_indptr, group_members, shared_len,
+                        max_shared_len, max_suffix_len, sm_scale=None, workspace=None, *, out=None):
+    """`paged_decode` for a batch in which groups of sequences hold their leading pages in common: q bf16 [B, Hq, 128] -> o bf16
+    [B, Hq, 128], the same function (every sequence attends all of its tokens), within the same budget but not the same bits.
+
+    The shared tokens of a group are walked once per slab of 16 // (Hq // Hkv) members instead of once per member; each sequence's own
+    tail is walked as in `paged_decode`.  group_indptr [B + 1], group_members [B], shared_len [B]: int32 device tensors.  Group j is
+    group_members[group_indptr[j] : group_indptr[j + 1]], trailing unused groups are empty (group_indptr[j] = B), group_members is a
+    permutation of range(B), and shared_len[b] -- the same for every member of a group, at most each member's length, any value, not
+    only multiples of the page size -- counts the leading tokens b has on the same pages as its group (include/micromix_hip.h,
+    mm_paged_decode_shared, also for what happens when the tensors break the rules: wrong results for those sequences, no access outside
+    the tensors).  `PagedKVCache.share_groups()` derives one grouping from a page table; a caller who knows better (a beam tree whose
+    branches share different depths) passes its own.
+    `max_shared_len` bounds the shared counts, `max_suffix_len` the tails; the launches depend on them (and B, Hq, Hkv) only, so a
+    captured graph stays valid while lengths and groups change within them.  `workspace` (at least
+    paged_decode_shared_workspace_bytes(...) bytes; always needed) is allocated here when None -- pass one when capturing a graph.
+    `out`: a bf16 [B, Hq, 128] tensor to write instead of a new one.  No sliding window.
+    """
+    lib = _shared_lib()
+    dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, q)
+    if q.dim() != 3 or q.size(0) != B or q.size(2) != 128:
+        raise RuntimeError(f"q must be [B = {B}, Hq, 128] bf16")
+    Hq = q.size(1)
+    if Hq % Hkv:
+        raise RuntimeError(f"the {Hq} query heads are not a multiple of the cache's {Hkv} kv heads")
+    for n, t, size in (("group_indptr", group_indptr, B + 1), ("group_members", group_members, B), ("shared_len", shared_len, B)):
+        if not _ok(t, torch.int32, dev.index):
+            _check_tensor(t, n, torch.int32, dev)
+        if t.dim() != 1 or t.numel() != size:
+            raise RuntimeError(f"{n} must be a one-dimensional int32 tensor of {size} entries (B = {B})")
+    max_shared_len, max_suffix_len = int(max_shared_len), int(max_suffix_len)
+    if min(max_shared_len, max_suffix_len) < 0 or max(max_shared_len, max_suffix_len) > 1 << 29:
+        raise RuntimeError("max_shared_len and max_suffix_len must lie in [0, 2^29]")
+    need = paged_decode_shared_workspace_bytes(B, Hq, Hkv, max_shared_len, max_suffix_len) if B and Hq // Hkv <= 16 else 0
+    workspace, ws_args = _kv_workspace(workspace, need, dev)
+    if out is None:
+        out = torch.empty((B, Hq, 128), dtype=torch.bfloat16, device=dev)
+    elif not _ok(out, torch.bfloat16, dev.index) or tuple(out.shape) != (B, Hq, 128):
+        _check_tensor(out, "out", torch.bfloat16, dev)
+        raise RuntimeError(f"out must be [{B}, {Hq}, 128] bf16")
+    scale = _sm_scale(sm_scale)
+    with _on_device(dev.index):
+        st = lib.mm_paged_decode_shared(_ptr(q), *kv_args, Hq, _ptr(group_indptr), _ptr(group_members), _ptr(shared_len), max_shared_len,
+                                        max_suffix_len, scale, *ws_args, _ptr(out), _stream_ptr(dev))
+    if st:
+        _lib.check(st, "paged_decode_shared")
+    return out
 
 
 def paged_prefill_workspace_bytes(T, B, Hq, Hkv, max_seq_len, window=None):
