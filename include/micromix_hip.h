@@ -477,6 +477,48 @@ int mm_kv_copy_pages(void *kv_data, void *kv_param, int kv_dtype, int max_pages,
                      mm_stream_t stream);
 
 /*
+ * Tree-masked attention over the paged KV cache and keeping a path (detect the two entries by their symbols; mm_version stays 660):
+ * verifying a tree draft (Medusa, EAGLE, SpecInfer: candidate continuations that share ancestors) in one call, then keeping the accepted
+ * root-to-leaf path.  Cache layout, kinds and page table as above.
+ * mm_paged_prefill_tree: mm_paged_prefill (no window) with another mask among the tokens just appended.  tree_mask: uint64 [num_tokens]
+ *   on the device, 8-byte aligned, read by the kernel only (a captured graph replays with other trees written into it).  With
+ *   base_b = len_b - n_b, query token j of sequence b (row qo_indptr[b] + j, cache slot base_b + j) attends
+ *     every cache position < base_b: the committed tokens, all of them;
+ *     new slot base_b + i exactly when i <= j and bit i of tree_mask[qo_indptr[b] + j] is set.
+ *   Bits above j are ignored; bit j itself is honoured as given (a node usually attends itself: set it).  For a node, set the bits of
+ *   its ancestors among the new tokens and its own.  Words with bits 0 .. j set give the bits of mm_paged_prefill, not merely its budget.
+ *   A sequence with n_b > 64 ignores its words and is attended causally, exactly as mm_paged_prefill does, so one call can mix a prompt
+ *   chunk with tree drafts.  A row that attends nothing (base_b = 0 and no bit set, or p < 0 as above) gives o = 0.
+ *   Everything else -- head rules, sm_scale, the three kinds, split-KV, statuses, the grid and the workspace, whose size is
+ *   mm_paged_prefill_workspace_bytes of the same (T, B, Hq, Hkv, max_seq_len) -- as mm_paged_prefill; a null or misaligned tree_mask
+ *   (with T > 0 and B > 0): MM_ERR_BAD_ARG.  RoPE needs nothing new: mm_rope_kv_append takes a cos / sin row per token, the row of
+ *   position base_b + depth(node).
+ * mm_kv_move_rows: for sequence b, for the moves m in [move_indptr[b], move_indptr[b + 1]), for every (layer, K / V, kv head), the token
+ *   row at logical position src_pos[m] of b goes to logical position dst_pos[m] of b: the code bytes and, for int4 and fp8, the fp16
+ *   (scale, zero) dword.  Bytes only.  Position pos is row pos % P of page kv_indices[kv_indptr[b] + pos / P].
+ *   Within a sequence every source is read before any destination is written, so a destination may be another move's source, as
+ *   always happens when a path is packed down.  At most 64 moves per sequence are performed; entries of a sequence past its 64th are
+ *   skipped.  A move is skipped (nothing read or written) when src == dst, when a position is negative or past the pages the sequence
+ *   lists, or when a page index lies outside [0, max_pages).
+ *   Preconditions: the destination positions of a sequence are pairwise distinct, and the pages written are not listed by another
+ *   sequence that has moves in the same call.  move_indptr [batch + 1], src_pos, dst_pos [num_moves]: device int32.  kv_data is 16-byte
+ *   aligned and kv_param 4-byte aligned.  No workspace, no host reads of device arrays: capture-safe like mm_kv_append.
+ * Null kv_data, null kv_param for int4 / fp8, misaligned kv_data / kv_param, non-positive geometry, negative batch or num_moves, an
+ * unassigned kv_dtype (2 included), or (with work to do) a null kv_indptr / kv_indices / move_indptr / src_pos / dst_pos: MM_ERR_BAD_ARG;
+ * head_dim != 128, more than 65535 layers or 32767 kv heads: MM_ERR_UNSUPPORTED; num_moves == 0 or batch == 0: MM_OK; all without
+ * device work.
+ */
+int mm_paged_prefill_tree(const void *q_bf16, const int32_t *qo_indptr, int num_tokens, const void *kv_data, const void *kv_param,
+                          int kv_dtype, int max_pages, int num_layers, int layer, int num_kv_heads, int page_size, int head_dim,
+                          const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_len, int batch,
+                          int num_qo_heads, int max_seq_len, float sm_scale, void *workspace, size_t workspace_bytes,
+                          void *o_bf16, mm_stream_t stream, const uint64_t *tree_mask /* [num_tokens] */);
+int mm_kv_move_rows(void *kv_data, void *kv_param, int kv_dtype, int max_pages, int num_layers, int num_kv_heads, int page_size,
+                    int head_dim, const int32_t *kv_indptr, const int32_t *kv_indices, int batch,
+                    const int32_t *move_indptr /* [batch + 1] */, const int32_t *src_pos, const int32_t *dst_pos, int num_moves,
+                    mm_stream_t stream);
+
+/*
  * Shared-prefix decode over the paged KV cache (detect the two entries by their symbols; mm_version stays 660): mm_paged_decode for a
  * batch in which groups of sequences hold a leading run of pages in common (n samples of one prompt, beams, a system prompt;
  * PagedKVCache.fork).  The result is the same function as mm_paged_decode -- every sequence attends all of its own tokens -- within the

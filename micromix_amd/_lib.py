@@ -24,6 +24,7 @@ EXPORTS = (
     "mm_paged_prefill_workspace_bytes", "mm_paged_prefill", "mm_rope_kv_append", "mm_kv_copy_pages",
     "mm_paged_decode_window_workspace_bytes", "mm_paged_decode_window", "mm_paged_prefill_window_workspace_bytes", "mm_paged_prefill_window",
     "mm_paged_decode_shared_workspace_bytes", "mm_paged_decode_shared",
+    "mm_paged_prefill_tree", "mm_kv_move_rows",
     "mm_moe_route", "mm_moe_plan", "mm_moe_gather", "mm_moe_combine",
     "mm_moe_sf_bytes", "mm_moe_quantize", "mm_moe_activate_quantize", "mm_moe_matmul_supported", "mm_moe_matmul",
     "mm_moe_gate_up_activate_supported", "mm_moe_gate_up_activate_describe", "mm_moe_gate_up_activate",
@@ -177,6 +178,11 @@ def load():
         lib.mm_paged_decode_shared_workspace_bytes.argtypes = [i] * 5
         lib.mm_paged_decode_shared.restype = i
         lib.mm_paged_decode_shared.argtypes = [vp, vp, vp] + [i] * 7 + [vp] * 3 + [i, i, vp, vp, vp, i, i, ctypes.c_float, vp, sz, vp, vp]
+    if hasattr(lib, "mm_paged_prefill_tree"):          # detected by symbol, like the pair above
+        lib.mm_paged_prefill_tree.restype = i
+        lib.mm_paged_prefill_tree.argtypes = lib.mm_paged_prefill.argtypes + [vp]
+        lib.mm_kv_move_rows.restype = i
+        lib.mm_kv_move_rows.argtypes = [vp, vp] + [i] * 6 + [vp, vp, i] + [vp] * 3 + [i, vp]
     lib.mm_moe_route.restype = i
     lib.mm_moe_route.argtypes = [vp, i, i, i, vp, vp, vp]
     lib.mm_moe_plan.restype = i

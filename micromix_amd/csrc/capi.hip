@@ -708,6 +708,21 @@ int mm_kv_copy_pages(void *kv_data, void *kv_param, int kv_dtype, int max_pages,
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_kv_copy_pages");
 }
 
+int mm_kv_move_rows(void *kv_data, void *kv_param, int kv_dtype, int max_pages, int num_layers, int num_kv_heads, int page_size,
+                    int head_dim, const int32_t *kv_indptr, const int32_t *kv_indices, int batch, const int32_t *move_indptr,
+                    const int32_t *src_pos, const int32_t *dst_pos, int num_moves, mm_stream_t stream) {
+    mm::PagedKV kv;                                           // no layer (0) and no lengths: every layer, positions within the listed pages
+    if (int st = kv_geometry(kv_data, kv_param, kv_dtype, max_pages, num_layers, 0, num_kv_heads, page_size, head_dim, kv_indptr, kv_indices,
+                             nullptr, batch, &kv)) return st;
+    if (num_moves < 0 || !kv.data || (kv.kind != mm::KV_BF16 && !kv.param)) return MM_ERR_BAD_ARG;
+    if (((uintptr_t)kv_data & 15) || ((uintptr_t)kv_param & 3)) return MM_ERR_BAD_ARG;
+    if (num_layers > 65535 || num_kv_heads > 32767) return MM_ERR_UNSUPPORTED;   // the grid: (2 Hkv, L, B)
+    if (num_moves == 0 || batch == 0) return MM_OK;
+    if (!kv_indptr || !kv_indices || !move_indptr || !src_pos || !dst_pos) return MM_ERR_BAD_ARG;
+    hipError_t e = mm::launch_kv_move_rows(kv, move_indptr, src_pos, dst_pos, num_moves, (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_kv_move_rows");
+}
+
 // the un-windowed entry points are the windowed ones at window = 0
 size_t mm_paged_decode_window_workspace_bytes(int batch, int num_qo_heads, int num_kv_heads, int max_seq_len, int window) {
     if (batch <= 0 || num_kv_heads <= 0 || num_qo_heads <= 0 || max_seq_len < 0 || window < 0 || num_qo_heads % num_kv_heads) return 0;
@@ -777,10 +792,12 @@ size_t mm_paged_prefill_workspace_bytes(int num_tokens, int batch, int num_qo_he
     return mm_paged_prefill_window_workspace_bytes(num_tokens, batch, num_qo_heads, num_kv_heads, max_seq_len, 0);
 }
 
-int mm_paged_prefill_window(const void *q_bf16, const int32_t *qo_indptr, int num_tokens, const void *kv_data, const void *kv_param, int kv_dtype,
-                            int max_pages, int num_layers, int layer, int num_kv_heads, int page_size, int head_dim, const int32_t *kv_indptr,
-                            const int32_t *kv_indices, const int32_t *last_page_len, int batch, int num_qo_heads, int max_seq_len,
-                            float sm_scale, void *workspace, size_t workspace_bytes, void *o_bf16, mm_stream_t stream, int window) {
+// the body of the three prefill entries: `tree` says whether the call is mm_paged_prefill_tree (a null tree_mask is then an error)
+static int paged_prefill(const void *q_bf16, const int32_t *qo_indptr, int num_tokens, const void *kv_data, const void *kv_param, int kv_dtype,
+                         int max_pages, int num_layers, int layer, int num_kv_heads, int page_size, int head_dim, const int32_t *kv_indptr,
+                         const int32_t *kv_indices, const int32_t *last_page_len, int batch, int num_qo_heads, int max_seq_len,
+                         float sm_scale, void *workspace, size_t workspace_bytes, void *o_bf16, mm_stream_t stream, int window, bool tree,
+                         const uint64_t *tree_mask) {
     mm::PagedKV kv;
     if (int st = kv_geometry(kv_data, kv_param, kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size, head_dim, kv_indptr, kv_indices,
                              last_page_len, batch, &kv)) return st;
@@ -788,11 +805,31 @@ int mm_paged_prefill_window(const void *q_bf16, const int32_t *qo_indptr, int nu
     if (num_qo_heads / num_kv_heads > 16) return MM_ERR_UNSUPPORTED;
     if (num_tokens == 0 || batch == 0) return MM_OK;
     if (!q_bf16 || !qo_indptr || !kv_pointers(kv) || !o_bf16) return MM_ERR_BAD_ARG;
+    if (tree && (!tree_mask || ((uintptr_t)tree_mask & 7))) return MM_ERR_BAD_ARG;
     const size_t need = mm_paged_prefill_window_workspace_bytes(num_tokens, batch, num_qo_heads, num_kv_heads, max_seq_len, window);
     if (need && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15))) return MM_ERR_BAD_ARG;
-    hipError_t e = mm::launch_paged_prefill(kv, q_bf16, qo_indptr, num_tokens, num_qo_heads, max_seq_len, window, sm_scale, workspace, o_bf16,
-                                            (hipStream_t)stream);
-    return e == hipSuccess ? MM_OK : fail_hip(e, window ? "mm_paged_prefill_window" : "mm_paged_prefill");
+    hipError_t e = mm::launch_paged_prefill(kv, q_bf16, qo_indptr, num_tokens, num_qo_heads, max_seq_len, window, tree ? tree_mask : nullptr,
+                                            sm_scale, workspace, o_bf16, (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, tree ? "mm_paged_prefill_tree" : window ? "mm_paged_prefill_window" : "mm_paged_prefill");
+}
+
+int mm_paged_prefill_window(const void *q_bf16, const int32_t *qo_indptr, int num_tokens, const void *kv_data, const void *kv_param, int kv_dtype,
+                            int max_pages, int num_layers, int layer, int num_kv_heads, int page_size, int head_dim, const int32_t *kv_indptr,
+                            const int32_t *kv_indices, const int32_t *last_page_len, int batch, int num_qo_heads, int max_seq_len,
+                            float sm_scale, void *workspace, size_t workspace_bytes, void *o_bf16, mm_stream_t stream, int window) {
+    return paged_prefill(q_bf16, qo_indptr, num_tokens, kv_data, kv_param, kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size,
+                         head_dim, kv_indptr, kv_indices, last_page_len, batch, num_qo_heads, max_seq_len, sm_scale, workspace, workspace_bytes,
+                         o_bf16, stream, window, false, nullptr);
+}
+
+int mm_paged_prefill_tree(const void *q_bf16, const int32_t *qo_indptr, int num_tokens, const void *kv_data, const void *kv_param, int kv_dtype,
+                          int max_pages, int num_layers, int layer, int num_kv_heads, int page_size, int head_dim, const int32_t *kv_indptr,
+                          const int32_t *kv_indices, const int32_t *last_page_len, int batch, int num_qo_heads, int max_seq_len,
+                          float sm_scale, void *workspace, size_t workspace_bytes, void *o_bf16, mm_stream_t stream,
+                          const uint64_t *tree_mask) {
+    return paged_prefill(q_bf16, qo_indptr, num_tokens, kv_data, kv_param, kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size,
+                         head_dim, kv_indptr, kv_indices, last_page_len, batch, num_qo_heads, max_seq_len, sm_scale, workspace, workspace_bytes,
+                         o_bf16, stream, 0, true, tree_mask);
 }
 
 int mm_paged_prefill(const void *q_bf16, const int32_t *qo_indptr, int num_tokens, const void *kv_data, const void *kv_param, int kv_dtype,

@@ -24,6 +24,12 @@
 // walk starts at the kv tile that holds its first token's window start, its chunks are laid over the W + BQ + 62 tokens from there, a
 // wave skips the tiles below all its rows' windows, and the lower-edge compare runs only on the tiles that cross one.  The un-windowed
 // kernels are the WINDOW = false instantiations, instruction for instruction what they were.
+// Tree mask (mm_paged_prefill_tree, the TREE kernels): among the n_b <= 64 tokens a sequence has just appended, query j attends new
+// slot base_b + i (base_b = len_b - n_b) when i <= j and bit i of its word tree_mask[q0_b + j] is set, and every committed position
+// below base_b.  A lane owns one query row, so it holds one word, with the bits above j cleared: the triangle is then a special case
+// of the word, kend and the wave's skip stay what they are, and on the tiles that reach base_b the word's test stands where the
+// diagonal's compare stood -- same elements set to -inf for a chain's words, so the same bits as the TREE = false kernel.  A sequence
+// with n_b > 64 has no words and takes the diagonal (uniform over the workgroup).  TREE = false: the six kernels as they were.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <math.h>
@@ -55,6 +61,7 @@ struct PrefillArgs {
     int T, Hq, g, bq, tiles, nc, chunk;
     float scale_log2;          // sm_scale * log2(e)
     int window;                // WINDOW kernels: a query at position p attends positions max(0, p - window + 1) .. p
+    const uint64_t *tree;      // TREE kernels: one word per query token, [T]
 };
 
 // (sequence, tile of it, its token count) of workgroup tile index i; false for a surplus tile
@@ -74,7 +81,7 @@ __device__ inline bool tile_of(const PrefillArgs &a, int i, int &b, int &j, int 
 // WINDOW: a query tile walks the kv tiles from the window of its first token on (rounded down to KT), chunk c from there + c * chunk;
 // a wave skips the tiles that lie below the windows of all its rows and compares against the lower edge only on the tiles that cross
 // one of them -- both wave-uniform, like the diagonal's gate
-template <int KIND, bool WINDOW>
+template <int KIND, bool WINDOW, bool TREE = false>
 __global__ __launch_bounds__(NT) void paged_prefill_kernel(const PrefillArgs a) {
     constexpr bool INT4 = KIND == KV_INT4, FP8 = KIND == KV_FP8;
     constexpr int KSTR = INT4 ? KSTR4 : KSTR16;       // fp8: the bf16 layout, widened at staging
@@ -122,6 +129,11 @@ __global__ __launch_bounds__(NT) void paged_prefill_kernel(const PrefillArgs a) 
     const int wr0 = 16 * wave, wt0 = wr0 / g, wt1 = min((wr0 + 15) / g, ntok - 1);
     const bool wactive = wt0 < ntok;
     const int wpmin = pos0 + wt0, wpmax = pos0 + wt1;
+    // TREE: new slot i of the sequence is cache position base + i; this row is new token jt < 64 and keeps bits 0 .. jt of its word
+    const bool tree = TREE && n <= 64;
+    const int base = len - n, jt = j * a.bq + rt;
+    uint64_t word = 0;
+    if (TREE && tree && rvalid) word = a.tree[q0 + jt] & ((2ull << jt) - 1ull);
 
     float m = -INFINITY, lsum = 0.0f, pz = 0.0f;
     v4f o[8];
@@ -288,7 +300,17 @@ __global__ __launch_bounds__(NT) void paged_prefill_kernel(const PrefillArgs a) 
                 for (int r = 0; r < 4; ++r) sc[blk][r] = d[r] * a.scale_log2 + kb[r];
             }
         }
-        if (kt + KT - 1 > wpmin) {                         // the tile crosses the diagonal of some row of this wave
+        if (TREE && tree) {
+            if (kt + KT - 1 >= base) {                     // the tile holds new slots: the word decides, the diagonal is in it
+#pragma unroll
+                for (int blk = 0; blk < 4; ++blk)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int i = kt + 16 * blk + 4 * kq + r - base;      // committed (i < 0): kept; past the 64 slots: masked
+                        if (i >= 0 && !(i < 64 && ((word >> (i & 63)) & 1ull))) sc[blk][r] = -INFINITY;
+                    }
+            }
+        } else if (kt + KT - 1 > wpmin) {                  // the tile crosses the diagonal of some row of this wave
 #pragma unroll
             for (int blk = 0; blk < 4; ++blk)
 #pragma unroll
@@ -431,7 +453,7 @@ size_t kv_prefill_workspace_bytes(int T, int B, int Hq, int Hkv, int max_seq_len
 }
 
 hipError_t launch_paged_prefill(const PagedKV &kv, const void *q, const int *qo_indptr, int T, int Hq, int max_seq_len, int window,
-                                float sm_scale, void *ws, void *o, hipStream_t stream) {
+                                const void *tree_mask, float sm_scale, void *ws, void *o, hipStream_t stream) {
     PrefillArgs a;
     a.kv = kv;
     a.q = (const uint16_t *)q;
@@ -445,8 +467,13 @@ hipError_t launch_paged_prefill(const PagedKV &kv, const void *q, const int *qo_
     kv_prefill_split(T, kv.B, Hq, kv.Hkv, max_seq_len, window, &a.tiles, &a.nc, &a.chunk);
     a.scale_log2 = kv_scale_log2(sm_scale);
     a.window = window;
+    a.tree = (const uint64_t *)tree_mask;
     const dim3 grid(a.tiles, kv.Hkv, a.nc);
-    if (window > 0) {
+    if (tree_mask) {                                       // no window form (capi.hip passes window = 0)
+        if (kv.kind == KV_INT4) paged_prefill_kernel<KV_INT4, false, true><<<grid, NT, 0, stream>>>(a);
+        else if (kv.kind == KV_FP8) paged_prefill_kernel<KV_FP8, false, true><<<grid, NT, 0, stream>>>(a);
+        else paged_prefill_kernel<KV_BF16, false, true><<<grid, NT, 0, stream>>>(a);
+    } else if (window > 0) {
         if (kv.kind == KV_INT4) paged_prefill_kernel<KV_INT4, true><<<grid, NT, 0, stream>>>(a);
         else if (kv.kind == KV_FP8) paged_prefill_kernel<KV_FP8, true><<<grid, NT, 0, stream>>>(a);
         else paged_prefill_kernel<KV_BF16, true><<<grid, NT, 0, stream>>>(a);

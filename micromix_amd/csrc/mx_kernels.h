@@ -286,6 +286,10 @@ hipError_t launch_rope_kv_append(const PagedKV &kv, const void *q, const void *k
 // rows [0, rows[i]) of page src_pages[i] -> page dst_pages[i], every layer, K and V, every head (kv_copy.hip); kv.layer is 0
 hipError_t launch_kv_copy_pages(const PagedKV &kv, const int *src_pages, const int *dst_pages, const int *rows, int num_pairs,
                                 hipStream_t stream);
+// within sequence b, for moves m in [move_indptr[b], move_indptr[b + 1]): the token row at position src_pos[m] -> position dst_pos[m],
+// every layer, K and V, every head, all sources read before any destination is written (kv_move.hip); kv.layer is 0
+hipError_t launch_kv_move_rows(const PagedKV &kv, const int *move_indptr, const int *src_pos, const int *dst_pos, int num_moves,
+                               hipStream_t stream);
 // sparse MoE block around the grouped GEMMs (moe.hip): n = T * top_k pairs, H a multiple of 8, rows 16-byte aligned
 hipError_t launch_moe_route(const void *logits, int T, int E, int top_k, int *ids, void *w, hipStream_t stream);
 hipError_t launch_moe_plan(const int *ids, int n, int E, int top_k, int *offsets, int *sorted_token, int *slot_of, hipStream_t stream);
@@ -295,7 +299,8 @@ hipError_t launch_moe_combine(const void *y, const int *ids, const void *w, cons
 // causal multi-token attention over the paged cache (kv_prefill.hip)
 void kv_prefill_split(int T, int B, int Hq, int Hkv, int max_seq_len, int window, int *tiles, int *nc, int *chunk);
 size_t kv_prefill_workspace_bytes(int T, int B, int Hq, int Hkv, int max_seq_len, int window);
+// tree_mask: null, or the [T] words of mm_paged_prefill_tree (then window is 0)
 hipError_t launch_paged_prefill(const PagedKV &kv, const void *q, const int *qo_indptr, int T, int Hq, int max_seq_len, int window,
-                                float sm_scale, void *ws, void *o, hipStream_t stream);
+                                const void *tree_mask, float sm_scale, void *ws, void *o, hipStream_t stream);
 
 }  // namespace mm

@@ -30,7 +30,7 @@ from . import _lib
 
 __all__ = ["test_function", "matmul", "gate_up_activate", "interleave_gate_up", "reorder_quantize_x", "reorder_quantize_w", "reorder_quantize_w4", "activate_quantize_x",
            "downproj_quantize_w", "downproj_quantize_w4", "rmsnorm_quantize_x", "qlinear_decode", "qlinear_decode_supported", "matmul_grouped", "reorder_quantize_x_grouped",
-           "kv_append", "rope_kv_append", "kv_copy_pages", "paged_decode", "paged_decode_workspace_bytes", "paged_decode_shared", "paged_decode_shared_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes",
+           "kv_append", "rope_kv_append", "kv_copy_pages", "kv_move_rows", "paged_decode", "paged_decode_workspace_bytes", "paged_decode_shared", "paged_decode_shared_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes",
            "moe_route", "moe_plan", "moe_gather", "moe_combine",
            "moe_expert_table", "moe_sf_bytes", "moe_quantize", "moe_activate_quantize", "moe_matmul", "moe_matmul_supported",
            "permute_packed_rows", "moe_gate_up_table", "moe_gate_up_activate", "moe_gate_up_activate_supported"]
@@ -1016,6 +1016,50 @@ def kv_copy_pages(kv_data, kv_param, src_pages, dst_pages, rows=None):
         _lib.check(st, "kv_copy_pages")
 
 
+def _tree_lib():
+    lib = _lib.load()
+    if not hasattr(lib, "mm_paged_prefill_tree"):
+        raise _lib.MicroMixLibraryError("libmicromix_hip.so has no mm_paged_prefill_tree / mm_kv_move_rows: it was built before tree-masked "
+                                        "attention; rebuild it with `python -m micromix_amd.build --force`")
+    return lib
+
+
+def kv_move_rows(kv_data, kv_param, kv_indptr, kv_indices, move_indptr, src_pos, dst_pos):
+    """Within each sequence of a paged cache, move token rows from one logical position to another, for every layer, K and V, every
+    head, in place; returns None.  Bytes only (codes and, for int4 / fp8, the fp16 params): no dequantization.
+
+    Sequence b's moves are m in [move_indptr[b], move_indptr[b + 1]): the row at position src_pos[m] goes to position dst_pos[m], a
+    position being row pos % P of page kv_indices[kv_indptr[b] + pos // P].  All sources of a sequence are read before any of its
+    destinations is written, so a destination may be another move's source -- what packing the accepted path of a tree draft down to
+    contiguous positions needs (PagedKVCache.accept).  At most 64 moves per sequence are performed; a move with src == dst, a position
+    outside the pages the sequence lists or a page index outside the cache is skipped.  The destinations of a sequence must be pairwise
+    distinct, and no page written may be listed by another sequence with moves in the call (include/micromix_hip.h, mm_kv_move_rows).
+    move_indptr [B + 1], src_pos, dst_pos: int32 device tensors.  Runs on the current stream, capture-safe."""
+    lib = _tree_lib()
+    if kv_param is not None:
+        kv_data = _kv_bytes(kv_data)
+    if not (isinstance(kv_data, torch.Tensor) and kv_data.is_cuda):
+        _check_tensor(kv_data, "kv_data", torch.uint8 if kv_param is not None else torch.bfloat16)
+    dev = kv_data.device
+    kind, max_pages, L, Hkv, P, kv_data = _kv_geometry(kv_data, kv_param, dev.index)
+    for n, t in (("kv_indptr", kv_indptr), ("kv_indices", kv_indices), ("move_indptr", move_indptr), ("src_pos", src_pos), ("dst_pos", dst_pos)):
+        if not _ok(t, torch.int32, dev.index):
+            _check_tensor(t, n, torch.int32, dev)
+        if t.dim() != 1:
+            raise RuntimeError(f"{n} must be one-dimensional")
+    B = kv_indptr.numel() - 1
+    if B < 0 or move_indptr.numel() != B + 1:
+        raise RuntimeError("kv_indptr and move_indptr must both have B + 1 entries")
+    if src_pos.numel() != dst_pos.numel():
+        raise RuntimeError("src_pos and dst_pos must be of one length")
+    with _on_device(dev.index):
+        st = lib.mm_kv_move_rows(_ptr(kv_data), _ptr(kv_param) if kv_param is not None else None, kind, max_pages, L, Hkv, P, 128,
+                                 _ptr(kv_indptr), _ptr(kv_indices), B, _ptr(move_indptr), _ptr(src_pos), _ptr(dst_pos), src_pos.numel(),
+                                 _stream_ptr(dev))
+    if st:
+        _lib.check(st, "kv_move_rows")
+
+
 def _token_rows(t, name, heads):
     """(heads, token stride in elements) of q / k / v given as [T, H, 128] or [T, H * 128] whose rows lie contiguous within a token.
     Stride 0: any stride will do (at most one token); None: the tensor has to be copied (rows not contiguous, an odd stride, a
@@ -1210,7 +1254,7 @@ def paged_prefill_workspace_bytes(T, B, Hq, Hkv, max_seq_len, window=None):
 
 
 def paged_prefill(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, qo_indptr, layer_idx, max_seq_len, sm_scale=None,
-                  workspace=None, *, window=None):
+                  workspace=None, *, window=None, tree_mask=None):
     """Causal GQA attention of T new query tokens over layer `layer_idx` of a paged cache: q bf16 [T, Hq, 128] -> o bf16 [T, Hq, 128].
 
     qo_indptr (int32 [B + 1], qo_indptr[B] = T) splits the queries among the sequences, as kv_append's append_indptr does; pass the
@@ -1221,10 +1265,18 @@ def paged_prefill(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, qo
     paged_prefill_workspace_bytes(...) bytes) is allocated here when None -- pass one when capturing a graph.
     `window` = W (HF's sliding_window; None or 0: none): the token at position p attends positions max(0, p - W + 1) .. p; the kv tiles
     below a query tile's windows are not read, and page-table entries below every window may be -1.
+    `tree_mask` (int64 [T] device tensor, one word per query token; None: the causal mask): verification of a tree draft.  With
+    base_b = len_b - n_b, sequence b's j-th new token attends every position below base_b and new slot base_b + i exactly when i <= j
+    and bit i of its word is set (bits above j are ignored; set bit j for a token to attend itself).  A sequence with more than 64 new
+    tokens ignores its words and is attended causally.  Words (2 << j) - 1 give the bits of the causal call.  No window form: `window`
+    together with `tree_mask` is a ValueError.  The tensor is read by the kernel only, so a captured graph replays with other trees
+    written into it.  `PagedKVCache.tree_mask` builds the words from parent indices.
     The cache is int4, fp8 (e4m3) or bf16, told apart as in `kv_append`; fp8 runs p.V on bf16(p * scale_v) times the codes, as int4.
     """
-    lib = _lib.load()
+    lib = _lib.load() if tree_mask is None else _tree_lib()
     window = _window(window)
+    if window and tree_mask is not None:
+        raise ValueError("paged_prefill has no sliding-window form of the tree mask: pass window or tree_mask, not both")
     dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, q)
     if not _ok(qo_indptr, torch.int32, dev.index):
         _check_tensor(qo_indptr, "qo_indptr", torch.int32, dev)
@@ -1235,6 +1287,11 @@ def paged_prefill(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, qo
     T, Hq = q.size(0), q.size(1)
     if Hq % Hkv:
         raise RuntimeError(f"the {Hq} query heads are not a multiple of the cache's {Hkv} kv heads")
+    if tree_mask is not None:
+        if not _ok(tree_mask, torch.int64, dev.index):
+            _check_tensor(tree_mask, "tree_mask", torch.int64, dev)
+        if tree_mask.dim() != 1 or tree_mask.numel() != T:
+            raise RuntimeError(f"tree_mask must be a one-dimensional int64 tensor of T = {T} words")
     max_seq_len = int(max_seq_len)
     if max_seq_len < 0:
         raise RuntimeError("max_seq_len must be >= 0")
@@ -1243,7 +1300,10 @@ def paged_prefill(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, qo
     o = torch.empty((T, Hq, 128), dtype=torch.bfloat16, device=dev)
     scale = _sm_scale(sm_scale)
     with _on_device(dev.index):
-        if window:
+        if tree_mask is not None:
+            st = lib.mm_paged_prefill_tree(_ptr(q), _ptr(qo_indptr), T, *kv_args, Hq, max_seq_len, scale, *ws_args, _ptr(o),
+                                           _stream_ptr(dev), _ptr(tree_mask))
+        elif window:
             st = lib.mm_paged_prefill_window(_ptr(q), _ptr(qo_indptr), T, *kv_args, Hq, max_seq_len, scale, *ws_args, _ptr(o),
                                              _stream_ptr(dev), window)
         else:
