@@ -701,7 +701,9 @@ const char *mm_test_function(void);
 int mm_diag_set_kernel_events(void *start_event, void *stop_event);
 #ifdef MM_INSTRUMENT
 /* device buffer of 4 x 8 bytes per workgroup: {main-loop s_memtime delta, main-loop s_memrealtime delta, start tick,
- * end-of-epilogue tick delta} of every workgroup of the large-M GEMM (in-kernel clock = ratio x 100 MHz); NULL disables. */
+ * end-of-epilogue tick delta} of every workgroup of the large-M GEMM (in-kernel clock = ratio x 100 MHz); NULL disables.
+ * The ping-pong kernel also writes its head -- {shader cycles from the start stamp to wave 0's first DMA request, ... to its first
+ * MFMA} -- to row 2048 + workgroup when it has at most 2048 workgroups: give it a buffer of at least 4096 rows. */
 int mm_diag_set_clock_buffer(void *buf);
 /* device buffer of 4 x 8 bytes per workgroup of reorder_quantize_kernel: {start, row staged, first group stored, end} ticks */
 int mm_diag_set_quant_clock_buffer(void *buf);

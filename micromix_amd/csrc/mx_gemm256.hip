@@ -387,6 +387,8 @@ bool mx_gemm_small_m_uses_tiles(int M, int N, const int K[3], bool w4, size_t ws
 // the ping-pong K loop (mx_gemm_tile.inc, run_pingpong) in front of the tail: fp4 weights, bf16 output, no split-K (the callers of
 // launch_g256 never split).  Mixed splits, the "w" mode, fp32 output, the fused gate / up and the grouped kernels and the 128-row
 // tiles keep the lock-step loop.  -DMM_PINGPONG=0 restores that selection everywhere (A/B builds of one tree).
+// This kernel alone starts on accumulators that nothing has zeroed: its first K step writes them (srcC = 0), and it requests slab 0
+// before any other set-up, slab 1 behind a head barrier (run_pingpong, "The head").  Every other kernel zeroes in tile_body as before.
 static bool g256_pingpong(int K0, int K1, int K2, bool w4, bool out_f32) {
     return MM_PINGPONG && w4 && !out_f32 && K0 == 0 && K1 == 0 && (K2 >> 7) >= 2;
 }

@@ -172,13 +172,22 @@ template <class G, int EL> using FragOfsOf = std::conditional_t<G::XEL == EL_FP8
 // above it (used on the first MFMAs after a barrier: the matrix pipe gets work before the wave spends ~100 cycles
 // issuing the next fragments' ds_reads).  HSEL = op_sel_hi of both scale operands: the scale bytes 0/1 (HSEL = 0) or 2/3
 // (HSEL = 1) of the lane's scale dword, already shifted by 8 * kb, i.e. K block 2 * HSEL + kb of the 128-deep scale atom.
-template <int T, int XEL, int WEL, int HSEL, bool FENCE = false>
+// ZC: the tile's FIRST K step (the ping-pong kernel, which never zeroes its accumulators): srcC is the inline constant 0 and the
+// accumulator is only written.  0 + x in the matrix pipe is what accumulating onto a zeroed register gives, bit for bit.
+template <int T, int XEL, int WEL, int HSEL, bool FENCE = false, bool ZC = false>
 __device__ __forceinline__ void mfma_tile(const typename Frag<XEL>::type &x, const typename Frag<WEL>::type &w, int sx,
                                           int sw) {
     // s_nop 1: two wait states between a just-written source VGPR (a compiler v_mov assembling the tuple, the
     // scale shift) and the MFMA that reads it -- hipcc pads nothing inside or in front of an asm statement.
 #if !(MM_DBG & 1)
-    if constexpr (FENCE) {
+    if constexpr (ZC) {   // (always a fence: these are the first MFMAs behind a barrier)
+        MM_DEVICE_ONLY(asm volatile("s_nop 1\n\tv_mfma_scale_f32_32x32x64_f8f6f4 a[%c7:%c8], %0, %1, 0, %2, %3 "
+                                    "op_sel_hi:[%c4,%c4,0] cbsz:%c5 blgp:%c6"
+                                    :
+                                    : "v"(x), "v"(w), "v"(sx), "v"(sw), "i"(HSEL), "i"(ElemTraits<XEL>::HW),
+                                      "i"(ElemTraits<WEL>::HW), "i"(16 * T), "i"(16 * T + 15)
+                                    : MM_ACC, "memory");)
+    } else if constexpr (FENCE) {
         MM_DEVICE_ONLY(asm volatile("s_nop 1\n\tv_mfma_scale_f32_32x32x64_f8f6f4 a[%c7:%c8], %0, %1, a[%c7:%c8], %2, %3 "
                                     "op_sel_hi:[%c4,%c4,0] cbsz:%c5 blgp:%c6"
                                     :
@@ -869,7 +878,9 @@ __device__ __forceinline__ void wait_slabs(const D &dma) {
 // ---------------------------------------------------------------------------------------------------------
 constexpr int TAIL_EP = 192;   // row pitch of a tail image: 48 dwords = 16 mod 32 banks, so the two rows a 32-lane half writes per
                                // ds_write_b32 fall on disjoint banks, and rows two apart start 32 banks apart (the row reads)
-template <class G, class FX, class FW>
+// Z0: the tail is the tile's whole K loop (the ping-pong kernel at count = 2, which never zeroes its accumulators): the first K step of
+// every accumulator takes the constant 0 as srcC (mfma_tile's ZC).
+template <class G, class FX, class FW, bool Z0 = false>
 struct TailTM {
     using XF = typename Frag<G::XEL>::type;
     using WF = typename Frag<G::WEL>::type;
@@ -908,7 +919,7 @@ struct TailTM {
     __device__ __forceinline__ void mfma() {
         constexpr int J = I & 1, H = I >> 1, TN_ = 2 * P + J;
         const Scales<G::KD> &sc = H < 2 ? sca : scb;
-        mfma_tile<TN_ * TM + TM_, G::XEL, G::WEL, (H & 1), true>(xs[H], ws[J][H], sc.x[0][TM_], sc.w[0][TN_]);
+        mfma_tile<TN_ * TM + TM_, G::XEL, G::WEL, (H & 1), true, Z0 && H == 0>(xs[H], ws[J][H], sc.x[0][TM_], sc.w[0][TN_]);
     }
     // (v0, v1) = this lane's feature at tokens t, t + 1 -> features (li & ~1, li | 1) at token t + (lane & 1): write_tile's pair_to_token
     __device__ __forceinline__ unsigned pair_to_token(float v0, float v1, float b) const {
@@ -995,15 +1006,15 @@ struct TailTM {
 };
 
 // The tail itself: called in place of the loop's last two iterations.  On entry stage c2 holds slab count - 2 (complete), stage c1
-// slab count - 1 (in flight), stage cf nothing that any wave still reads.
-template <class G, class FX, class FW>
+// slab count - 1 (in flight), stage cf nothing that any wave still reads.  Z0: the accumulators are unwritten on entry (TailTM).
+template <class G, bool Z0 = false, class FX, class FW>
 __device__ __forceinline__ void run_tail(const GemmArgs &a, int m0, int n0, uint8_t *smem, int c2, int c1, int cf, const Scales<G::KD> &sca,
                                          const FX &fx, const FW &fw, int gx, int gw) {
     const int lane = mm_tid() & 63, wave = __builtin_amdgcn_readfirstlane(mm_tid() >> 6);
     const int wm = wave >> 1, wn = wave & 1, li = lane & 31, kb = lane >> 5;
     wait_vmcnt<0>();       // this thread's share of slab count - 1 has landed ...
     barrier_lds_only();    // ... and every thread's
-    TailTM<G, FX, FW> t{a, smem + c2 * G::STAGE, smem + c1 * G::STAGE, smem + cf * G::STAGE + wave * (32 * TAIL_EP), fx, fw};
+    TailTM<G, FX, FW, Z0> t{a, smem + c2 * G::STAGE, smem + c1 * G::STAGE, smem + cf * G::STAGE + wave * (32 * TAIL_EP), fx, fw};
     t.sca = sca;
     load_scales<G>(t.scb, t.sb, gx, gw, li, kb);
     t.m0w = m0 + wm * (TM * 32);
@@ -1315,11 +1326,26 @@ __device__ __forceinline__ void run_all_segments(Acc &acc, const GemmArgs &a, in
 //   after issuing its pieces of s + 2 (its pieces of s + 1 went out in period 2s - 1).  The scale pieces are issued by waves 0 and 1,
 //   both in G0, so G1's count has no scale piece in it.  Never vmcnt(0) inside the loop.
 // Every accumulator still receives its K steps slab by slab, step 0 before step 1: the sums are bit for bit those of run_slabs_big.
-// Barriers (P = count - 2 ping-pong slabs): the prologue's one, then per group P memory + P compute phases and ONE extra period --
-// G1's first (period 0, it has no compute(-1)), G0's last (period 2P, G1 computes slab count - 3 while G0 only waits) -- both only
-// when P > 0: 1 + 2P + (P > 0) barriers per wave in each group, then run_tail's own.  count = 2: no ping-pong period; count = 3: one
-// slab, periods 0-2.  After the last one the state is exactly what run_tail documents: slab count - 2 complete in its stage (certified
-// at the end of period 2P - 1, or by the prologue when P = 0), slab count - 1 requested, the stage of slab count - 3 free.
+// The head (round 18, profiles/r18_head.txt).  One tile per CU and one round of tiles per launch: nothing overlaps what a workgroup does
+// before its first MFMA, so that is kept to the requests and their latency.
+//   - The accumulators are never zeroed (128 v_accvgpr_write per wave, two waves per SIMD, used to stand in front of the first request).
+//     The first K step of every accumulator -- slab 0, step 0: the first eight MFMAs of each group's first compute phase, peeled out of
+//     the loop (compute<Z0>), or of the tail when count = 2 (run_tail<Z0>) -- takes the inline constant 0 as srcC and only writes the
+//     accumulator.  0 + x in the matrix pipe is what accumulating onto a zeroed register gives: the outputs keep their bits.
+//   - After the tile mapping a wave builds its DMA descriptors and issues its slab-0 pieces; the fragment offsets, gx / gw and the
+//     PingPong object follow behind that issue.  (The tail's bias loads stay in run_tail: they are vector-memory loads and would enter
+//     the vmcnt accounting of the loop.)
+//   - Slab 1 is requested behind the HEAD BARRIER, which every wave reaches when the memory pipe has taken its slab-0 pieces.  The pipe
+//     serves in issue order across waves (one 1 KiB piece per ~31 cycles), so without that barrier a wave that is ahead puts its slab-1
+//     pieces in front of the other waves' slab-0 pieces and the slab-0 certificate waits for up to 100 pieces instead of about 50.
+//     vmcnt accounting of the prologue: slab 0 (NPIECES or NPIECES - 1 per wave), head barrier, slab 1 (the same count), then
+//     wait_slabs<1> = at most one slab's worth outstanding = this wave's slab-0 pieces have landed, then the certificate barrier.
+// Barriers (P = count - 2 ping-pong slabs): the prologue's two (head barrier, slab-0 certificate), then per group P memory + P compute
+// phases and ONE extra period -- G1's first (period 0, it has no compute(-1)), G0's last (period 2P, G1 computes slab count - 3 while
+// G0 only waits) -- both only when P > 0: 2 + 2P + (P > 0) barriers per wave in each group, then run_tail's own.  count = 2: no
+// ping-pong period; count = 3: one slab, periods 0-2.  After the last one the state is exactly what run_tail documents: slab count - 2
+// complete in its stage (certified at the end of period 2P - 1, or by the prologue when P = 0), slab count - 1 requested, the stage of
+// slab count - 3 free.  -DMM_PP_HEAD_BARRIER=0 (A/B builds): slab 1 right behind the moved set-up, no head barrier.
 // MM_PP_CPIECES = c (0-2): the first c DMA pieces of a wave's share of a slab go out in its compute phase, one after every second
 // MFMA, instead of in its memory phase.  MM_PP_FLIP = 1: the computing wave of a SIMD at priority 1 (set and reset at the compute
 // phase's edges) instead of the static priority 1 of waves 4-7 (tile_body).
@@ -1334,6 +1360,9 @@ __device__ __forceinline__ void run_all_segments(Acc &acc, const GemmArgs &a, in
 #endif
 #ifndef MM_PP_FLIP
 #define MM_PP_FLIP 0
+#endif
+#ifndef MM_PP_HEAD_BARRIER
+#define MM_PP_HEAD_BARRIER 1
 #endif
 template <class G>
 struct PingPong {
@@ -1378,19 +1407,25 @@ struct PingPong {
                                     "+v"(sc.w[0][3]));)
     }
     // compute phase: MFMA I = K step I >> 3 on tile I & 7 (run_slabs_big's order), compute-phase piece J after MFMA 2J + 1
-    template <int I = 0>
+    // Z0: the group's first compute phase (slab 0).  Nothing has written the accumulators: the eight MFMAs of K step 0 take the
+    // constant 0 as srcC (mfma_tile's ZC).
+    template <bool Z0 = false, int I = 0>
     __device__ __forceinline__ void compute(int ahead, uint8_t *st_ahead) const {
         if constexpr (I < 16) {
             constexpr int H = I >> 3, P = I & 7, tn = P / TM, tm = P % TM;
-            mfma_tile<tn * TM + tm, XEL, WEL, H>(x[H][tm], w[H][tn], sc.x[0][tm], sc.w[0][tn]);
+            mfma_tile<tn * TM + tm, XEL, WEL, H, false, Z0 && H == 0>(x[H][tm], w[H][tn], sc.x[0][tm], sc.w[0][tn]);
             if constexpr ((I & 1) && (I >> 1) < CP) dma.template piece<(I >> 1)>(ahead, st_ahead);
-            compute<I + 1>(ahead, st_ahead);
+            compute<Z0, I + 1>(ahead, st_ahead);
         }
     }
 };
 
+// head stamps of the instrumented build (s_memtime, raw): this wave's first DMA request and its first MFMA; tile_body stores them
+struct HeadStamps {
+    unsigned long long dma = 0, mfma = 0;
+};
 template <class G>
-__device__ __forceinline__ void run_pingpong(const GemmArgs &a, int count, int m0, int n0, uint8_t *smem) {
+__device__ __forceinline__ void run_pingpong(const GemmArgs &a, int count, int m0, int n0, uint8_t *smem, [[maybe_unused]] HeadStamps &hs) {
     using D = SlabDma<G>;
     const int lane = mm_tid() & 63, wave = __builtin_amdgcn_readfirstlane(mm_tid() >> 6);
     const int wm = wave >> 1, wn = wave & 1, li = lane & 31, kb = lane >> 5;
@@ -1398,24 +1433,37 @@ __device__ __forceinline__ void run_pingpong(const GemmArgs &a, int count, int m
     D dma;
     init_slab_dma<G>(dma, a, 2, m0, n0, count, 0, wave);
     auto stage_at = [&](int i) { return smem + i * G::STAGE; };
-    // prologue: slabs 0 and 1 (count >= 2), wait for slab 0 only
+    // Head (round 18): the requests for slab 0 are the first thing a wave does -- the accumulators are never zeroed (compute<Z0>,
+    // run_tail<Z0>), and everything that does not go into a DMA instruction is worked out behind their issue, under their latency.
+#if MM_CLOCKS
+    hs.dma = __builtin_amdgcn_s_memtime();
+#endif
     dma.all(0, stage_at(0));
-    dma.all(1, stage_at(1));
-    wait_slabs<1>(dma);
-    barrier_lds_only();
+    // (the asm keeps hipcc from hoisting the set-up below, which hangs on li_, above the DMA issue)
+    int li_ = li;
+    MM_DEVICE_ONLY(asm volatile("" : "+v"(li_));)
     FragOfsOf<G, G::XEL> fx;
     FragOfsOf<G, G::WEL> fw;
-    fx.init(wm * (TM * 32) + li, kb);
-    fw.init(wn * (TN * 32) + li, kb);
+    fx.init(wm * (TM * 32) + li_, kb);
+    fw.init(wn * (TN * 32) + li_, kb);
     const int gx = ((m0 & 127) >> 5) + wm * TM, gw = ((n0 & 127) >> 5) + wn * TN;
     PingPong<G> pp{dma, fx, fw, gx, gw, li, kb};
 #if MM_PP_FLIP && MM_PRIO
     MM_DEVICE_ONLY(asm volatile("s_setprio 0");)   // (tile_body gave waves 4-7 the static priority)
 #endif
+    // Slab 1 goes out only when EVERY wave has handed its slab-0 pieces to the memory pipe, which serves them in issue order: the
+    // head barrier.  Without it a wave that is ahead (waves 4-7 win every issue arbitration) queues its slab-1 pieces in front of the
+    // other waves' slab-0 pieces, and the slab-0 certificate below waits for up to 100 pieces instead of about 50.
+#if MM_PP_HEAD_BARRIER
+    barrier_lds_only();
+#endif
+    dma.all(1, stage_at(1));
+    wait_slabs<1>(dma);                             // this wave's slab-0 pieces have landed; its slab-1 pieces may stay in flight
+    barrier_lds_only();
     const int P = count - 2;
-    if (g1 && P > 0) barrier_lds_only();           // period 0: G1 has no compute(-1)
-    int st = 0;                                     // stage of slab s
-    for (int s = 0; s < P; ++s) {
+    // one ping-pong slab of a group: memory(s), barrier, compute(s), barrier.  Z0: the group's first (s = 0), peeled out of the loop
+    // so that the loop's MFMAs all accumulate
+    auto slab = [&](auto z0, int s, int st) {
         const int sa = st == 0 ? 2 : st - 1;        // stage of slab s + 2 (= that of slab s - 1)
         pp.memory(stage_at(st), s + 2, stage_at(sa));
         // G1: its pieces of slab s + 1 have landed; those of s + 2 (memory phase, issued just now) may stay in flight
@@ -1424,7 +1472,10 @@ __device__ __forceinline__ void run_pingpong(const GemmArgs &a, int count, int m
 #if MM_PP_FLIP
         MM_DEVICE_ONLY(asm volatile("s_setprio 1");)
 #endif
-        pp.compute(s + 2, stage_at(sa));
+#if MM_CLOCKS
+        if constexpr (decltype(z0)::value) hs.mfma = __builtin_amdgcn_s_memtime();
+#endif
+        pp.template compute<decltype(z0)::value>(s + 2, stage_at(sa));
 #if MM_PP_FLIP
         MM_DEVICE_ONLY(asm volatile("s_setprio 0");)
 #endif
@@ -1432,9 +1483,22 @@ __device__ __forceinline__ void run_pingpong(const GemmArgs &a, int count, int m
         if (!g1) wait_slabs<1>(dma);
         MM_DEVICE_ONLY(__builtin_amdgcn_sched_barrier(0);)   // the MFMAs are issued before the wave waits at the barrier
         barrier_lds_only();
+    };
+    if (P == 0) {
+        // stage 0 holds slab 0 (complete), stage 1 slab 1 (requested), stage 2 nothing; the tail writes the accumulators first
+        Scales<G::KD> sca;
+        load_scales<G>(sca, stage_at(0), gx, gw, li, kb);
+        run_tail<G, true>(a, m0, n0, smem, 0, 1, 2, sca, fx, fw, gx, gw);
+        return;
+    }
+    if (g1) barrier_lds_only();                    // period 0: G1 has no compute(-1)
+    slab(std::true_type{}, 0, 0);
+    int st = 1;                                     // stage of slab s
+    for (int s = 1; s < P; ++s) {
+        slab(std::false_type{}, s, st);
         st = st == 2 ? 0 : st + 1;
     }
-    if (!g1 && P > 0) barrier_lds_only();          // period 2P: G1 computes slab count - 3, G0 waits
+    if (!g1) barrier_lds_only();                   // period 2P: G1 computes slab count - 3, G0 waits
     // stage st holds slab count - 2 (complete), the next one count - 1 (requested), the third count - 3 (free)
     const int c1 = st == 2 ? 0 : st + 1, cf = c1 == 2 ? 0 : c1 + 1;
     Scales<G::KD> sca;
@@ -2116,7 +2180,8 @@ __device__ __forceinline__ void tile_body(const GemmArgs &a, const int bid) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc.t[t][i] = 0.0f;
 #else
-        AccLoop<0, NACC>::zero();
+        // (the ping-pong kernel never zeroes: the first K step of every accumulator writes it, run_pingpong)
+        if constexpr (!PP) AccLoop<0, NACC>::zero();
 #endif
         // ablation 4096: every workgroup loads tile (0, 0)'s operands (all of L2's misses disappear, the L2 -> LDS traffic stays);
         // ablation 8192: every workgroup of an XCD loads the operands of the XCD's first tile
@@ -2127,7 +2192,8 @@ __device__ __forceinline__ void tile_body(const GemmArgs &a, const int bid) {
 #else
         const int lm0 = m0, ln0 = n0;
 #endif
-        if constexpr (PP) run_pingpong<typename Segs<W4>::O>(a, n2s, lm0, ln0, smem);
+        [[maybe_unused]] HeadStamps hs;
+        if constexpr (PP) run_pingpong<typename Segs<W4>::O>(a, n2s, lm0, ln0, smem, hs);
         else run_all_segments<W4, TAIL>(acc, a, n0s, n1s, n2s, lm0, ln0, smem, round_acc);
         if constexpr (TAIL) {
 #if MM_CLOCKS
@@ -2138,6 +2204,12 @@ __device__ __forceinline__ void tile_body(const GemmArgs &a, const int bid) {
                 a.clock_out[4 * bid + 2] = r0;
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's stores have left
                 a.clock_out[4 * bid + 3] = __builtin_amdgcn_s_memrealtime() - r0;
+                // the ping-pong kernel's head: shader cycles from the start stamp to wave 0's first DMA request and to its first
+                // MFMA, in row MM_HEAD_ROW0 + bid of the buffer (a launch of more workgroups than that leaves them out)
+                if (PP && bid < MM_HEAD_ROW0) {
+                    a.clock_out[4 * (MM_HEAD_ROW0 + bid)] = hs.dma - t0;
+                    a.clock_out[4 * (MM_HEAD_ROW0 + bid) + 1] = hs.mfma > t0 ? hs.mfma - t0 : 0;
+                }
             }
 #endif
             return;

@@ -12,6 +12,7 @@
 #define MM_DBG 0
 #endif
 #define MM_CLOCKS 1   // per-workgroup s_memtime / s_memrealtime stamps into GemmArgs::clock_out
+#define MM_HEAD_ROW0 2048   // first row (of 4 x 8 bytes) of the ping-pong kernel's head stamps: the buffer has >= 2 * MM_HEAD_ROW0 rows
 #else
 #ifdef MM_DBG
 #error "MM_DBG ablation switches need -DMM_INSTRUMENT (tools/build_variant.sh)"

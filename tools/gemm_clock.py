@@ -37,6 +37,12 @@ for split in SPLITS:
     lib.mm_diag_set_clock_buffer(None)
     kernel_us = e0.elapsed_time(e1) * 1e3
     c = clk.cpu().double()
+    head = c[2048:][c[2048:, 1] > 0][:256]   # the ping-pong kernel's head stamps (MM_HEAD_ROW0): wave 0's first DMA request, first MFMA
+    if len(head):
+        q = lambda v: f"median {v.median():.0f} (p10 {v.quantile(0.1):.0f} p90 {v.quantile(0.9):.0f})"
+        print(f"   head, shader cycles of wave 0 ({len(head)} workgroups): start -> first DMA {q(head[:, 0])}; "
+              f"first DMA -> first MFMA {q(head[:, 1] - head[:, 0])}; start -> first MFMA {q(head[:, 1])}")
+    c = c[:2048]
     c = c[c[:, 1] > 0][:256]     # the workgroups that ran (up to one round of them)
     cyc, ticks = c[:, 0], c[:, 1]
     ghz = (cyc / ticks * 0.1)
