@@ -233,6 +233,52 @@ int mm_add_rmsnorm_qlinear_decode(const void *X_bf16, const void *R_bf16, void *
                                 {SFBN, SFBS, SFBO}, M, N, KN, KS, KO, wmode, flags, bias_bf16, D_bf16, stream);
 }
 
+// The one place a GemmArgs is made: operands, shapes and flags.  Everything else starts at zero -- no workspace (mm_matmul_ws adds its
+// own), no fused epilogue (gemm_args_act adds it); the launchers fill in splits, tickets and tile columns.  X / SFX: null where the launch
+// quantizes its own rows.  M = 0: a device-sized grouped launch (every workgroup reads its group's rows).  hooks: the launch carries the
+// calling thread's diagnostics hooks (mm_diag_set_kernel_events / mm_diag_set_clock_buffer).
+static mm::GemmArgs gemm_args(const Ptr3 &X, const Ptr3 &SFX, const Ptr3 &W, const Ptr3 &SFW, int M, int N, const int K[3], int flags,
+                              const void *bias_bf16, void *D, bool hooks) {
+    mm::GemmArgs a = {};
+    for (int i = 0; i < 3; ++i) {
+        a.X[i] = X.p[i];
+        a.W[i] = W.p[i];
+        a.SFX[i] = SFX.p[i];
+        a.SFW[i] = SFW.p[i];
+        a.K[i] = K[i];
+    }
+    a.M = M;
+    a.N = N;
+    // the 128-row tiles that hold scales of real rows.  The reference allocates M/128 + 1 tiles (bindings.cpp:120) and never
+    // writes the last one when M % 128 == 0; counting only the written tiles keeps every kernel's scale reads inside ANY tensor
+    // that holds the scales of its M rows, whoever allocated it.
+    a.sfx_row_tiles = (M + 127) / 128;
+    a.sfw_row_tiles = (N + 127) / 128;
+    a.round_per_segment = (flags & MM_ROUND_ONCE) ? 0 : 1;
+    a.bias = (const uint16_t *)bias_bf16;
+    a.D = (uint16_t *)D;
+    a.out_f32 = (flags & MM_OUT_F32) ? 1 : 0;
+    if (hooks) {
+        a.clock_out = g_clock_buf;
+        a.ev_start = g_ev.start;
+        a.ev_stop = g_ev.stop;
+    }
+    return a;
+}
+// ... with the fused gate / up epilogue (GemmArgs::act): N = 2 I interleaved rows, no D; Kd, o, sf: the consumer GEMM's operand
+struct Out3 { uint8_t *p[3]; };
+static mm::GemmArgs gemm_args_act(const Ptr3 &X, const Ptr3 &SFX, const Ptr3 &W, const Ptr3 &SFW, int M, int I, const int K[3], int flags,
+                                  const int Kd[3], const Out3 &o, const Out3 &sf, bool hooks) {
+    mm::GemmArgs a = gemm_args(X, SFX, W, SFW, M, 2 * I, K, flags, nullptr, nullptr, hooks);
+    a.act = 1;
+    for (int i = 0; i < 3; ++i) {
+        a.act_K[i] = Kd[i];
+        a.act_o[i] = o.p[i];
+        a.act_sf[i] = sf.p[i];
+    }
+    return a;
+}
+
 size_t mm_matmul_workspace_bytes(int M, int N, int KN, int KS, int KO, int wmode, int flags) {
     if (M <= 0 || N <= 0 || KN < 0 || KS < 0 || KO < 0 || (KN % 128) || (KS % 128) || (KO % 128)) return 0;
     const int K[3] = {KN, KS, KO};
@@ -274,34 +320,11 @@ int mm_matmul_ws(const uint8_t *AN, const uint8_t *BN, const uint8_t *AS, const 
         hipError_t e = hipMemsetAsync(D_bf16, 0, (size_t)M * N * (out_f32 ? 4 : 2), (hipStream_t)stream);
         return e == hipSuccess ? MM_OK : fail_hip(e, "mm_matmul(memset)");
     }
-    mm::GemmArgs a;
-    a.X[0] = AN; a.X[1] = AS; a.X[2] = AO;
-    a.W[0] = BN; a.W[1] = BS; a.W[2] = BO;
-    a.SFX[0] = SFAN; a.SFX[1] = SFAS; a.SFX[2] = SFAO;
-    a.SFW[0] = SFBN; a.SFW[1] = SFBS; a.SFW[2] = SFBO;
-    a.K[0] = KN; a.K[1] = KS; a.K[2] = KO;
-    a.M = M; a.N = N;
-    // the 128-row tiles that hold scales of real rows.  The reference allocates M/128 + 1 tiles (bindings.cpp:120) and never
-    // writes the last one when M % 128 == 0; counting only the written tiles keeps every kernel's scale reads inside ANY tensor
-    // that holds the scales of its M rows, whoever allocated it.
-    a.sfx_row_tiles = (M + 127) / 128;
-    a.sfw_row_tiles = (N + 127) / 128;
-    a.round_per_segment = (flags & MM_ROUND_ONCE) ? 0 : 1;
-    a.bias = (const uint16_t *)bias_bf16;
-    a.D = (uint16_t *)D_bf16;
-    a.out_f32 = out_f32 ? 1 : 0;
-    a.act = 0;
-    a.clock_out = g_clock_buf;
-    a.ev_start = g_ev.start;
-    a.ev_stop = g_ev.stop;
+    mm::GemmArgs a = gemm_args({AN, AS, AO}, {SFAN, SFAS, SFAO}, {BN, BS, BO}, {SFBN, SFBS, SFBO}, M, N, K, flags, bias_bf16, D_bf16, true);
     a.ws = (float *)workspace;
     a.ws_bytes = workspace ? workspace_bytes : 0;
-    a.splits = 0;
-    a.tickets = nullptr;
     a.tickets_zeroed = (workspace && (flags & MM_WS_TICKETS_ZEROED)) ? 1 : 0;
-    a.n_tile0 = a.n_tiles = 0;
     a.force_split = (flags & MM_SPLIT_K_ALWAYS) ? 1 : 0;
-    a.split_first[0] = a.split_first[1] = a.split_first[2] = a.split_first[3] = 0;
     hipError_t e = mm::launch_mx_gemm(a, weights_fp4(wmode, KS, KO), (hipStream_t)stream);
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_matmul");
 }
@@ -324,23 +347,10 @@ const char *mm_gate_up_activate_describe(int M, int I) {
     return mm::describe_mx_gemm_act(M, 2 * I);
 }
 
-// the fused gate | up weight with the activation inside the weight-streaming launch (mx_gemm_stream.hip, ACT)
-static mm::GemmArgs act_stream_args(const uint8_t *BN, const uint8_t *BS, const uint8_t *BO, const uint8_t *SFBN, const uint8_t *SFBS, const uint8_t *SFBO,
-                                    int M, int I, int KN, int KS, int KO, int DN, int DS, int DO, int flags, uint8_t *oN, uint8_t *oS, uint8_t *oO,
-                                    uint8_t *sfN, uint8_t *sfS, uint8_t *sfO) {
-    mm::GemmArgs a = {};
-    a.W[0] = BN; a.W[1] = BS; a.W[2] = BO;
-    a.SFW[0] = SFBN; a.SFW[1] = SFBS; a.SFW[2] = SFBO;
-    a.K[0] = KN; a.K[1] = KS; a.K[2] = KO;
-    a.M = M; a.N = 2 * I;
-    a.sfx_row_tiles = 1;
-    a.sfw_row_tiles = (2 * I + 127) / 128;
-    a.round_per_segment = (flags & MM_ROUND_ONCE) ? 0 : 1;
-    a.act = 1;
-    a.act_K[0] = DN; a.act_K[1] = DS; a.act_K[2] = DO;
-    a.act_o[0] = oN; a.act_o[1] = oS; a.act_o[2] = oO;
-    a.act_sf[0] = sfN; a.act_sf[1] = sfS; a.act_sf[2] = sfO;
-    return a;
+// the fused gate | up weight with the activation inside the weight-streaming launch (mx_gemm_stream.hip, ACT): M <= 32, one scale tile
+static mm::GemmArgs act_stream_args(const Ptr3 &A, const Ptr3 &SFA, const Ptr3 &B, const Ptr3 &SFB, int M, int I, const int Kin[3], int flags,
+                                    const int Kd[3], const Out3 &o, const Out3 &sf) {
+    return gemm_args_act(A, SFA, B, SFB, M, I, Kin, flags, Kd, o, sf, false);
 }
 
 int mm_gate_up_activate(const uint8_t *AN, const uint8_t *BN, const uint8_t *AS, const uint8_t *BS, const uint8_t *AO,
@@ -359,9 +369,8 @@ int mm_gate_up_activate(const uint8_t *AN, const uint8_t *BN, const uint8_t *AS,
     const int N = 2 * I;
     if (!mm::mx_gemm_act_supported(M, N) && mm::gate_up_act_stream_supported(M, N, Kin, false, false)) {
         // M <= 16 on a wide layer (round 6): ONE weight-streaming launch with the activation inside -- no scratch, the same bytes
-        mm::GemmArgs a = act_stream_args(BN, BS, BO, SFBN, SFBS, SFBO, M, I, KN, KS, KO, DN, DS, DO, flags, oN, oS, oO, sfN, sfS, sfO);
-        a.X[0] = AN; a.X[1] = AS; a.X[2] = AO;
-        a.SFX[0] = SFAN; a.SFX[1] = SFAS; a.SFX[2] = SFAO;
+        const mm::GemmArgs a = act_stream_args({AN, AS, AO}, {SFAN, SFAS, SFAO}, {BN, BS, BO}, {SFBN, SFBS, SFBO}, M, I, Kin, flags, Kd, {oN, oS, oO},
+                                               {sfN, sfS, sfO});
         hipError_t e = mm::launch_gate_up_act_stream(a, (hipStream_t)stream);
         return e == hipSuccess ? MM_OK : fail_hip(e, "mm_gate_up_activate");
     }
@@ -376,30 +385,8 @@ int mm_gate_up_activate(const uint8_t *AN, const uint8_t *BN, const uint8_t *AS,
                                                   (hipStream_t)stream);
         return e == hipSuccess ? MM_OK : fail_hip(e, "mm_gate_up_activate");
     }
-    mm::GemmArgs a;
-    a.X[0] = AN; a.X[1] = AS; a.X[2] = AO;
-    a.W[0] = BN; a.W[1] = BS; a.W[2] = BO;
-    a.SFX[0] = SFAN; a.SFX[1] = SFAS; a.SFX[2] = SFAO;
-    a.SFW[0] = SFBN; a.SFW[1] = SFBS; a.SFW[2] = SFBO;
-    a.K[0] = KN; a.K[1] = KS; a.K[2] = KO;
-    a.M = M; a.N = N;
-    a.sfx_row_tiles = (M + 127) / 128;
-    a.sfw_row_tiles = (N + 127) / 128;
-    a.round_per_segment = (flags & MM_ROUND_ONCE) ? 0 : 1;
-    a.bias = nullptr;
-    a.D = nullptr;
-    a.out_f32 = 0;
-    a.act = 1;
-    a.act_K[0] = DN; a.act_K[1] = DS; a.act_K[2] = DO;
-    a.act_o[0] = oN; a.act_o[1] = oS; a.act_o[2] = oO;
-    a.act_sf[0] = sfN; a.act_sf[1] = sfS; a.act_sf[2] = sfO;
-    a.clock_out = g_clock_buf;
-    a.ev_start = g_ev.start;
-    a.ev_stop = g_ev.stop;
-    a.ws = nullptr; a.ws_bytes = 0; a.splits = 0; a.tickets = nullptr; a.tickets_zeroed = 0;
-    a.n_tile0 = a.n_tiles = 0;
-    a.force_split = 0;
-    a.split_first[0] = a.split_first[1] = a.split_first[2] = a.split_first[3] = 0;
+    const mm::GemmArgs a = gemm_args_act({AN, AS, AO}, {SFAN, SFAS, SFAO}, {BN, BS, BO}, {SFBN, SFBS, SFBO}, M, I, Kin, flags, Kd, {oN, oS, oO},
+                                         {sfN, sfS, sfO}, true);
     hipError_t e = mm::launch_mx_gemm_act(a, (hipStream_t)stream);
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_gate_up_activate");
 }
@@ -439,8 +426,7 @@ static int gate_up_decode_entry(Variant v, const void *X_bf16, const mm::NormArg
     if (v != PLAIN && (!norm.weight || ((uintptr_t)norm.weight & 15))) return MM_ERR_BAD_ARG;
     if (v == ADD_NORM && !residual_ok(X_bf16, norm.res, norm.s_out, M, KN + KS + KO)) return MM_ERR_BAD_ARG;
     if (one_launch) {
-        const mm::GemmArgs a = act_stream_args(B.p[0], B.p[1], B.p[2], SFB.p[0], SFB.p[1], SFB.p[2], M, I, KN, KS, KO, DN, DS, DO, flags, oN, oS, oO, sfN,
-                                               sfS, sfO);
+        const mm::GemmArgs a = act_stream_args({}, {}, B, SFB, M, I, Kin, flags, Kd, {oN, oS, oO}, {sfN, sfS, sfO});   // the launch quantizes X itself
         hipError_t e = mm::launch_gate_up_act_stream_decode(X_bf16, reorder_index, a, (hipStream_t)stream, norm);
         return e == hipSuccess ? MM_OK : fail_hip(e, name[v]);
     }
@@ -572,24 +558,7 @@ int mm_matmul_grouped(const mm_group *groups, int ngroups, int N, int KN, int KS
     // groups of at most 64 token rows share launches of the weight-streaming kernels, larger groups launches of the tiled
     // kernels (up to MM_MAX_GROUPS argument blocks per launch, carried in the kernel arguments)
     auto fill = [&](mm::GemmArgs &a, const mm_group &g) {
-        a.X[0] = g.AN; a.X[1] = g.AS; a.X[2] = g.AO;
-        a.W[0] = g.BN; a.W[1] = g.BS; a.W[2] = g.BO;
-        a.SFX[0] = g.SFAN; a.SFX[1] = g.SFAS; a.SFX[2] = g.SFAO;
-        a.SFW[0] = g.SFBN; a.SFW[1] = g.SFBS; a.SFW[2] = g.SFBO;
-        a.K[0] = KN; a.K[1] = KS; a.K[2] = KO;
-        a.M = g.M; a.N = N;
-        a.sfx_row_tiles = (g.M + 127) / 128;
-        a.sfw_row_tiles = (N + 127) / 128;
-        a.round_per_segment = (flags & MM_ROUND_ONCE) ? 0 : 1;
-        a.bias = (const uint16_t *)g.bias_bf16;
-        a.D = (uint16_t *)g.D;
-        a.out_f32 = 0;
-        a.act = 0;
-        a.clock_out = nullptr;
-        a.ev_start = a.ev_stop = nullptr;
-        a.ws = nullptr; a.ws_bytes = 0; a.splits = 0; a.force_split = 0; a.n_tile0 = a.n_tiles = 0;
-        a.tickets = nullptr; a.tickets_zeroed = 0;
-        a.split_first[0] = a.split_first[1] = a.split_first[2] = a.split_first[3] = 0;
+        a = gemm_args({g.AN, g.AS, g.AO}, {g.SFAN, g.SFAS, g.SFAO}, {g.BN, g.BS, g.BO}, {g.SFBN, g.SFBS, g.SFBO}, g.M, N, Ks, flags, g.bias_bf16, g.D, false);
     };
     if (KN + KS + KO == 0) {   // no segment: every output is zero (gemm.cu:48-50)
         for (int i = 0; i < ngroups; ++i)
@@ -967,14 +936,7 @@ int mm_moe_matmul(const uint8_t *AN, const uint8_t *AS, const uint8_t *AO, const
         return e == hipSuccess ? MM_OK : fail_hip(e, "mm_moe_matmul(zero)");
     }
     if (!mm_moe_matmul_supported(max_rows, N, KN, KS, KO, wmode)) return MM_ERR_UNSUPPORTED;
-    mm::GemmArgs a = {};
-    a.X[0] = AN; a.X[1] = AS; a.X[2] = AO;
-    a.SFX[0] = SFAN; a.SFX[1] = SFAS; a.SFX[2] = SFAO;
-    a.K[0] = KN; a.K[1] = KS; a.K[2] = KO;
-    a.N = N;
-    a.sfw_row_tiles = (N + 127) / 128;
-    a.round_per_segment = (flags & MM_ROUND_ONCE) ? 0 : 1;
-    a.D = (uint16_t *)D_bf16;
+    const mm::GemmArgs a = gemm_args({AN, AS, AO}, {SFAN, SFAS, SFAO}, {}, {}, 0, N, K, flags, nullptr, D_bf16, false);   // W, SFW, bias: the expert table's
     const bool w4 = weights_fp4(wmode, KS, KO);
     // experts of 1 .. 64 rows on the weight-streaming kernels, larger ones on the tiled kernels: the kernel family mm_matmul_grouped
     // gives each of them; an expert finds itself in one launch and returns at once from the other
@@ -1011,17 +973,7 @@ int mm_moe_gate_up_activate(const uint8_t *AN, const uint8_t *AS, const uint8_t 
     if (!segments_ok(Kin, {AN, AS, AO}, {SFAN, SFAS, SFAO}) || !segments_ok(Kd, {oN, oS, oO}, {sfN, sfS, sfO})) return MM_ERR_BAD_ARG;
     // rows leave in 16-byte pieces, scale atoms 16 bytes per lane
     if ((((uintptr_t)oN | (uintptr_t)oS | (uintptr_t)oO) & 15) || (((uintptr_t)sfN | (uintptr_t)sfS | (uintptr_t)sfO) & 15)) return MM_ERR_BAD_ARG;
-    mm::GemmArgs a = {};
-    a.X[0] = AN; a.X[1] = AS; a.X[2] = AO;
-    a.SFX[0] = SFAN; a.SFX[1] = SFAS; a.SFX[2] = SFAO;
-    a.K[0] = KN; a.K[1] = KS; a.K[2] = KO;
-    a.N = 2 * I;
-    a.sfw_row_tiles = (2 * I + 127) / 128;
-    a.round_per_segment = (flags & MM_ROUND_ONCE) ? 0 : 1;
-    a.act = 1;
-    a.act_K[0] = DN; a.act_K[1] = DS; a.act_K[2] = DO;
-    a.act_o[0] = oN; a.act_o[1] = oS; a.act_o[2] = oO;
-    a.act_sf[0] = sfN; a.act_sf[1] = sfS; a.act_sf[2] = sfO;
+    const mm::GemmArgs a = gemm_args_act({AN, AS, AO}, {SFAN, SFAS, SFAO}, {}, {}, 0, I, Kin, flags, Kd, {oN, oS, oO}, {sfN, sfS, sfO}, false);
     hipError_t e = mm::launch_mx_gemm256_moe_act(a, mg, (hipStream_t)stream);
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_moe_gate_up_activate");
 }

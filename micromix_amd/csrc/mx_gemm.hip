@@ -26,7 +26,7 @@
 //                                    and K is not split, for M <= 32 while they fit three rounds: mx_gemm_small_m_uses_tiles)
 //  * M  > 64 : mx_gemm256.hip     -- LDS-DMA pipelined 256x256 tiles when they fill the chip, else 128x256 / 128x128 tiles,
 //                                    64x128 / 64x64 / 32x64 tiles with loader and compute waves for the smallest launches, or split-K
-//                                    through a caller-provided workspace (plan_tiles / plan_splits, fitted to measurements)
+//                                    through a caller-provided workspace (plan_tiles / plan_splits in mx_gemm_plan.h, fitted to measurements)
 #include <stdlib.h>
 
 #include "mx_common.h"

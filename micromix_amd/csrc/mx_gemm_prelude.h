@@ -26,6 +26,7 @@
 #include "mx_direct_convert.h"
 #include "mx_group_convert.h"
 #include "mx_kernels.h"
+#include "mx_gemm_plan.h"    // the tile table and the whole host-side plan (no HIP in it)
 
 namespace mm {
 
@@ -40,21 +41,57 @@ namespace mm {
 #define MM_SPLIT_FENCES 0
 #endif
 
-template <class KernelT>
-static hipError_t launch_tile(KernelT kern, DynamicLdsOnce &attr, int lds_bytes, int tiles, int threads, const GemmArgs &a,
-                              hipStream_t stream) {
-    if (hipError_t e = attr.ensure(reinterpret_cast<const void *>(kern), lds_bytes); e != hipSuccess) return e;
-    if (a.ev_start != nullptr && a.ev_stop != nullptr)
-        hipExtLaunchKernelGGL(kern, dim3(tiles), dim3(threads), lds_bytes, stream, a.ev_start, a.ev_stop, 0, a);
+static_assert(MM_PLAN_MAX_SPLITS == MM_MAX_SPLITS, "the plan's split bound is GemmArgs' (mx_gemm_plan.h)");
+
+// The one launch of a tile kernel: `args` are the kernel's arguments, `ev` the diagnostics events (both null: none).  The kernel's
+// dynamic-LDS limit is raised once per device before its first launch; that state belongs to the kernel -- a static of this
+// instantiation -- so no call site can pair a kernel with another kernel's flag.
+struct LaunchDims { int wgs, threads, lds_bytes; };
+template <auto Kern, class... Args>
+static hipError_t launch_tile(LaunchDims d, hipStream_t stream, DiagEvents ev, const Args &...args) {
+    static DynamicLdsOnce attr;
+    if (hipError_t e = attr.ensure(reinterpret_cast<const void *>(Kern), d.lds_bytes); e != hipSuccess) return e;
+    if (ev.start != nullptr && ev.stop != nullptr)
+        hipExtLaunchKernelGGL(Kern, dim3(d.wgs), dim3(d.threads), d.lds_bytes, stream, ev.start, ev.stop, 0, args...);
     else
-        hipLaunchKernelGGL(kern, dim3(tiles), dim3(threads), lds_bytes, stream, a);
+        hipLaunchKernelGGL(Kern, dim3(d.wgs), dim3(d.threads), d.lds_bytes, stream, args...);
     return hipGetLastError();
 }
 
-// the tiles for launches with few tiles live in mx_gemm_tiles_small.hip (compiled beside mx_gemm256.hip)
-hipError_t launch_small_tile(int kind, bool w4, bool splitk, int wgs, const GemmArgs &a, hipStream_t stream);
-hipError_t launch_small_tile_grouped(int kind, bool w4, int total, const GroupedTileArgs &ga, hipStream_t stream);
-hipError_t launch_small_tile_moe(int kind, bool w4, int total, const GemmArgs &a, const MoeGroups &mg, hipStream_t stream);
-constexpr size_t SMALL_PART_BYTES_64x64 = 16 * 256 * 4, SMALL_PART_BYTES_64x128 = 32 * 256 * 4;   // fp32 accumulators of one workgroup (in-kernel split-K)
+// The kernel table: one row per tile namespace, made where mx_gemm_tile.inc was included for it.  A row names the namespace's kernels by
+// family and weight mode and ties it to its entry of the plan's tile table; the launchers below are written once over a row.
+#define MM_TILE_KERNELS(ns, KIND)                                                                                              \
+    struct ns##_row {                                                                                                          \
+        template <bool W4> static constexpr LaunchDims dims(int wgs) { return LaunchDims{wgs, ns::NTHREADS, ns::Lds<W4>::TOTAL}; } \
+        template <bool W4, bool SPLITK> static constexpr auto gemm = ns::mx_gemm256_kernel<W4, SPLITK>;                        \
+        template <bool W4> static constexpr auto grouped = ns::mx_gemm256_grouped_kernel<W4>;                                  \
+        template <bool W4> static constexpr auto moe = ns::mx_gemm256_moe_kernel<W4>;                                          \
+    };                                                                                                                         \
+    static_assert(ns::BM == tile_shape(KIND).bm && ns::BN == tile_shape(KIND).bn, "the plan's tile table (mx_gemm_plan.h)")
+
+template <class Row, bool SPLITK = false>
+static hipError_t launch_gemm(bool w4, int wgs, const GemmArgs &a, hipStream_t stream) {
+    const DiagEvents ev{a.ev_start, a.ev_stop};
+    return w4 ? launch_tile<Row::template gemm<true, SPLITK>>(Row::template dims<true>(wgs), stream, ev, a)
+              : launch_tile<Row::template gemm<false, SPLITK>>(Row::template dims<false>(wgs), stream, ev, a);
+}
+// grouped launch (launch_mx_gemm256_grouped has filled ga.first_block[]; wgs = all groups' tiles)
+template <class Row>
+static hipError_t launch_grouped(bool w4, int wgs, const GroupedTileArgs &ga, hipStream_t stream) {
+    return w4 ? launch_tile<Row::template grouped<true>>(Row::template dims<true>(wgs), stream, DiagEvents{}, ga)
+              : launch_tile<Row::template grouped<false>>(Row::template dims<false>(wgs), stream, DiagEvents{}, ga);
+}
+// device-sized grouped launch (wgs = the host bound of plan_moe)
+template <class Row>
+static hipError_t launch_moe(bool w4, int wgs, const GemmArgs &a, const MoeGroups &mg, hipStream_t stream) {
+    return w4 ? launch_tile<Row::template moe<true>>(Row::template dims<true>(wgs), stream, DiagEvents{}, a, mg)
+              : launch_tile<Row::template moe<false>>(Row::template dims<false>(wgs), stream, DiagEvents{}, a, mg);
+}
+
+// the tiles for launches with few tiles live in mx_gemm_tiles_small.hip (compiled beside mx_gemm256.hip): tile = TK_G64, TK_G32,
+// TK_G32N or TK_G16 (gemm; splitk, the in-kernel split-K variants, on TK_G32 and TK_G32N only), the first three (grouped, moe)
+hipError_t launch_small_tile(TileKind tile, bool w4, bool splitk, int wgs, const GemmArgs &a, hipStream_t stream);
+hipError_t launch_small_tile_grouped(TileKind tile, bool w4, int total, const GroupedTileArgs &ga, hipStream_t stream);
+hipError_t launch_small_tile_moe(TileKind tile, bool w4, int total, const GemmArgs &a, const MoeGroups &mg, hipStream_t stream);
 
 }  // namespace mm

@@ -1,6 +1,6 @@
 // The tiles for launches that cannot fill the chip with 128-row tiles -- 128 x 128 (8 waves), 64 x 128 / 64 x 64 (4 compute + 4 loader
 // waves), 32 x 64 (2 + 2) -- in a translation unit of their own, so that hipcc compiles them beside mx_gemm256.hip (round 6: one file
-// took 100 s of a 105 s build).  plan_tiles / plan_small_split in mx_gemm256.hip choose; the launchers below are all that file sees.
+// took 100 s of a 105 s build).  plan_tiles / plan_small_split (mx_gemm_plan.h) choose; the launchers below are all that mx_gemm256.hip sees.
 #include "mx_gemm_prelude.h"
 
 namespace mm {
@@ -67,73 +67,38 @@ namespace mm {
 #undef MM_LDS_BUDGET
 
 
+MM_TILE_KERNELS(g64, TK_G64);
+MM_TILE_KERNELS(g32, TK_G32);
+MM_TILE_KERNELS(g32n, TK_G32N);
+MM_TILE_KERNELS(g16, TK_G16);
 static_assert((size_t)g32n::NACC * g32n::NT * 4 == SMALL_PART_BYTES_64x64 && (size_t)g32::NACC * g32::NT * 4 == SMALL_PART_BYTES_64x128,
-              "partial-sum slot sizes of the in-kernel split-K (mx_gemm_prelude.h)");
+              "partial-sum slot sizes of the in-kernel split-K (mx_gemm_plan.h)");
 
-// kind: 64 = 128 x 128 tiles (g64), 32 = 64 x 128 (g32), 33 = 64 x 64 (g32n), 16 = 32 x 64 (g16); splitk: the in-kernel split-K
-// variants (split_tile_reduce; 64 x 128 and 64 x 64 tiles only)
-hipError_t launch_small_tile(int kind, bool w4, bool splitk, int wgs, const GemmArgs &a, hipStream_t stream) {
-    static DynamicLdsOnce done[12];
-    if (splitk) {
-        if (kind == 33)
-            return w4 ? launch_tile(g32n::mx_gemm256_kernel<true, true>, done[8], g32n::Lds<true>::TOTAL, wgs, g32n::NTHREADS, a, stream)
-                      : launch_tile(g32n::mx_gemm256_kernel<false, true>, done[9], g32n::Lds<false>::TOTAL, wgs, g32n::NTHREADS, a, stream);
-        if (kind == 32)
-            return w4 ? launch_tile(g32::mx_gemm256_kernel<true, true>, done[10], g32::Lds<true>::TOTAL, wgs, g32::NTHREADS, a, stream)
-                      : launch_tile(g32::mx_gemm256_kernel<false, true>, done[11], g32::Lds<false>::TOTAL, wgs, g32::NTHREADS, a, stream);
-        return hipErrorInvalidValue;
-    }
-    switch (kind) {
-        case 64:
-            return w4 ? launch_tile(g64::mx_gemm256_kernel<true, false>, done[0], g64::Lds<true>::TOTAL, wgs, g64::NT, a, stream)
-                      : launch_tile(g64::mx_gemm256_kernel<false, false>, done[1], g64::Lds<false>::TOTAL, wgs, g64::NT, a, stream);
-        case 32:
-            return w4 ? launch_tile(g32::mx_gemm256_kernel<true, false>, done[2], g32::Lds<true>::TOTAL, wgs, g32::NTHREADS, a, stream)
-                      : launch_tile(g32::mx_gemm256_kernel<false, false>, done[3], g32::Lds<false>::TOTAL, wgs, g32::NTHREADS, a, stream);
-        case 33:
-            return w4 ? launch_tile(g32n::mx_gemm256_kernel<true, false>, done[4], g32n::Lds<true>::TOTAL, wgs, g32n::NTHREADS, a, stream)
-                      : launch_tile(g32n::mx_gemm256_kernel<false, false>, done[5], g32n::Lds<false>::TOTAL, wgs, g32n::NTHREADS, a, stream);
-        case 16:
-            return w4 ? launch_tile(g16::mx_gemm256_kernel<true, false>, done[6], g16::Lds<true>::TOTAL, wgs, g16::NTHREADS, a, stream)
-                      : launch_tile(g16::mx_gemm256_kernel<false, false>, done[7], g16::Lds<false>::TOTAL, wgs, g16::NTHREADS, a, stream);
+// splitk: the in-kernel split-K variants (split_tile_reduce; 64 x 128 and 64 x 64 tiles only)
+hipError_t launch_small_tile(TileKind tile, bool w4, bool splitk, int wgs, const GemmArgs &a, hipStream_t stream) {
+    switch (tile) {
+        case TK_G32N: return splitk ? launch_gemm<g32n_row, true>(w4, wgs, a, stream) : launch_gemm<g32n_row>(w4, wgs, a, stream);
+        case TK_G32: return splitk ? launch_gemm<g32_row, true>(w4, wgs, a, stream) : launch_gemm<g32_row>(w4, wgs, a, stream);
+        case TK_G64: return splitk ? hipErrorInvalidValue : launch_gemm<g64_row>(w4, wgs, a, stream);
+        case TK_G16: return splitk ? hipErrorInvalidValue : launch_gemm<g16_row>(w4, wgs, a, stream);
         default: return hipErrorInvalidValue;
     }
 }
 
-// grouped launch (launch_mx_gemm256_grouped has filled ga.first_block[]; total = all groups' tiles)
-hipError_t launch_small_tile_grouped(int kind, bool w4, int total, const GroupedTileArgs &ga, hipStream_t stream) {
-    static DynamicLdsOnce done[6];
-    auto go = [&](auto kern, DynamicLdsOnce &d, int lds, int threads) -> hipError_t {
-        if (hipError_t e = d.ensure(reinterpret_cast<const void *>(kern), lds); e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(total), dim3(threads), lds, stream, ga);
-        return hipGetLastError();
-    };
-    switch (kind) {
-        case 33: return w4 ? go(g32n::mx_gemm256_grouped_kernel<true>, done[0], g32n::Lds<true>::TOTAL, g32n::NTHREADS)
-                           : go(g32n::mx_gemm256_grouped_kernel<false>, done[1], g32n::Lds<false>::TOTAL, g32n::NTHREADS);
-        case 32: return w4 ? go(g32::mx_gemm256_grouped_kernel<true>, done[2], g32::Lds<true>::TOTAL, g32::NTHREADS)
-                           : go(g32::mx_gemm256_grouped_kernel<false>, done[3], g32::Lds<false>::TOTAL, g32::NTHREADS);
-        case 64: return w4 ? go(g64::mx_gemm256_grouped_kernel<true>, done[4], g64::Lds<true>::TOTAL, g64::NT)
-                           : go(g64::mx_gemm256_grouped_kernel<false>, done[5], g64::Lds<false>::TOTAL, g64::NT);
+hipError_t launch_small_tile_grouped(TileKind tile, bool w4, int total, const GroupedTileArgs &ga, hipStream_t stream) {
+    switch (tile) {
+        case TK_G32N: return launch_grouped<g32n_row>(w4, total, ga, stream);
+        case TK_G32: return launch_grouped<g32_row>(w4, total, ga, stream);
+        case TK_G64: return launch_grouped<g64_row>(w4, total, ga, stream);
         default: return hipErrorInvalidValue;
     }
 }
 
-// device-sized grouped launch (launch_mx_gemm256_moe has chosen the tile and the grid bound `total`)
-hipError_t launch_small_tile_moe(int kind, bool w4, int total, const GemmArgs &a, const MoeGroups &mg, hipStream_t stream) {
-    static DynamicLdsOnce done[6];
-    auto go = [&](auto kern, DynamicLdsOnce &d, int lds, int threads) -> hipError_t {
-        if (hipError_t e = d.ensure(reinterpret_cast<const void *>(kern), lds); e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(total), dim3(threads), lds, stream, a, mg);
-        return hipGetLastError();
-    };
-    switch (kind) {
-        case 33: return w4 ? go(g32n::mx_gemm256_moe_kernel<true>, done[0], g32n::Lds<true>::TOTAL, g32n::NTHREADS)
-                           : go(g32n::mx_gemm256_moe_kernel<false>, done[1], g32n::Lds<false>::TOTAL, g32n::NTHREADS);
-        case 32: return w4 ? go(g32::mx_gemm256_moe_kernel<true>, done[2], g32::Lds<true>::TOTAL, g32::NTHREADS)
-                           : go(g32::mx_gemm256_moe_kernel<false>, done[3], g32::Lds<false>::TOTAL, g32::NTHREADS);
-        case 64: return w4 ? go(g64::mx_gemm256_moe_kernel<true>, done[4], g64::Lds<true>::TOTAL, g64::NT)
-                           : go(g64::mx_gemm256_moe_kernel<false>, done[5], g64::Lds<false>::TOTAL, g64::NT);
+hipError_t launch_small_tile_moe(TileKind tile, bool w4, int total, const GemmArgs &a, const MoeGroups &mg, hipStream_t stream) {
+    switch (tile) {
+        case TK_G32N: return launch_moe<g32n_row>(w4, total, a, mg, stream);
+        case TK_G32: return launch_moe<g32_row>(w4, total, a, mg, stream);
+        case TK_G64: return launch_moe<g64_row>(w4, total, a, mg, stream);
         default: return hipErrorInvalidValue;
     }
 }
