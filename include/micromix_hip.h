@@ -519,6 +519,52 @@ int mm_kv_move_rows(void *kv_data, void *kv_param, int kv_dtype, int max_pages, 
                     mm_stream_t stream);
 
 /*
+ * Greedy verification of tree and chain drafts on the device (detect the three entries by their symbols; mm_version stays 660): the
+ * vocabulary argmax of the verified rows, the walk that picks the accepted path, and the move table mm_kv_move_rows takes.  None of
+ * the three reads device memory on the host or allocates: capture-safe.
+ * mm_argmax_rows: out_idx[r] = the index of the maximum of row r of logits (bf16, row r at logits + r * ld elements, ld >= vocab)
+ *   under one total order: any NaN, of either sign, is greater than +inf; +0 == -0; among equal maxima the lowest index wins (so the
+ *   first NaN of a row).  This is torch.argmax's order on the CPU.  The answer does not depend on how a row is divided or on the order
+ *   in which workgroups finish.  logits needs 2-byte alignment only and ld may be odd (logits[:, :V] of a padded lm_head output): the
+ *   kernel peels the elements in front of and behind the 16-byte vectors of a row's part itself.
+ *   A row is split into parts of MM_ARGMAX_CHUNK columns, one workgroup each; with more than one part (vocab > MM_ARGMAX_CHUNK) every
+ *   part writes its (key, index) to `workspace` (mm_argmax_rows_workspace_bytes(rows, vocab) bytes, 8-byte aligned, no initialisation
+ *   needed: every word read was written by the same call) and a second small launch reduces them.  vocab <= MM_ARGMAX_CHUNK: one
+ *   launch, no workspace (the size is 0).
+ *   Limits: vocab <= MM_ARGMAX_MAX_VOCAB = 2^20, rows <= MM_ARGMAX_MAX_ROWS = 65535 (a grid dimension): beyond, MM_ERR_UNSUPPORTED.
+ *   Null logits or out_idx with rows > 0, rows < 0, vocab < 1, ld < vocab, an odd logits address, an out_idx that is not 4-byte aligned,
+ *   a workspace that is needed and null, too small or not 8-byte aligned: MM_ERR_BAD_ARG.  rows == 0: MM_OK.  All without device work.
+ * mm_verify_greedy: for sequence b with n = qo_indptr[b + 1] - qo_indptr[b] new tokens (rows t = qo_indptr[b] + i, node i) and
+ *   base = len_b - n (len_b from kv_indptr / last_page_len / page_size as in mm_paged_prefill_tree): draft_tok[t] is node i's token,
+ *   target_tok[t] the token the target model picks after it (mm_argmax_rows of its logits, or any sampler's choice), root_tok[b] the
+ *   token picked after the last committed one.  parent(i) is the highest set bit of tree_mask[t] below bit i, -1 without one (bits at
+ *   i and above are ignored); with a null tree_mask, i - 1 (chains).
+ *   The walk, for 1 <= n <= 64 and root_tok[b] >= 0: cur = -1, want = root_tok[b], k = 0; take the lowest i with parent(i) == cur and
+ *   draft_tok == want; none: stop; else path[k++] = i, want = target_tok[row i], cur = i, again.
+ *   result [batch, MM_VERIFY_STRIDE]: [0] = k, [1] = want (the bonus token; root_tok[b] when nothing matched or n == 0),
+ *   [2 .. 2 + k) the path, the rest -1.  A sequence with n > 64 or root_tok[b] < 0 is no draft but a prompt chunk (which the attention
+ *   kernels treat causally too) and keeps all: [0] = n, [1] = target_tok of its last row (-1 when n == 0), every path entry -1, no moves.
+ *   move_src, move_dst [num_tokens], laid over qo_indptr, to be passed on as mm_kv_move_rows(..., move_indptr = qo_indptr, move_src,
+ *   move_dst, num_moves = num_tokens): row qo_indptr[b] + i of a draft with i < k holds src = base + path[i], dst = base + i; every
+ *   other row holds src = dst = -1.  Every element of result, move_src and move_dst is written by every call.
+ *   qo_indptr entries are clamped to [0, num_tokens] as the attention kernels do.  No workspace.
+ *   Null target_tok / draft_tok / move_src / move_dst with num_tokens > 0, null root_tok / qo_indptr / kv_indptr / last_page_len /
+ *   result with batch > 0, a tree_mask that is not 8-byte aligned, negative num_tokens or batch, page_size < 1: MM_ERR_BAD_ARG;
+ *   batch == 0: MM_OK; all without device work.
+ */
+#define MM_ARGMAX_CHUNK 8192          /* columns of a row that one workgroup reduces */
+#define MM_ARGMAX_MAX_VOCAB (1 << 20)
+#define MM_ARGMAX_MAX_ROWS 65535
+#define MM_VERIFY_STRIDE 66           /* ints per sequence in mm_verify_greedy's result: k, the bonus token, 64 path entries */
+size_t mm_argmax_rows_workspace_bytes(int rows, int vocab);
+int mm_argmax_rows(const void *logits_bf16, int rows, int vocab, long long ld /* elements between rows, >= vocab */,
+                   int32_t *out_idx /* [rows] */, void *workspace, size_t workspace_bytes, mm_stream_t stream);
+int mm_verify_greedy(const int32_t *target_tok /* [T] */, const int32_t *draft_tok /* [T] */, const int32_t *root_tok /* [batch] */,
+                     const uint64_t *tree_mask /* [T] or null: chains */, const int32_t *qo_indptr /* [batch + 1] */, int num_tokens,
+                     const int32_t *kv_indptr, const int32_t *last_page_len, int page_size, int batch,
+                     int32_t *result /* [batch, 66] */, int32_t *move_src /* [T] */, int32_t *move_dst /* [T] */, mm_stream_t stream);
+
+/*
  * Shared-prefix decode over the paged KV cache (detect the two entries by their symbols; mm_version stays 660): mm_paged_decode for a
  * batch in which groups of sequences hold a leading run of pages in common (n samples of one prompt, beams, a system prompt;
  * PagedKVCache.fork).  The result is the same function as mm_paged_decode -- every sequence attends all of its own tokens -- within the

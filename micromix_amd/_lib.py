@@ -25,6 +25,7 @@ EXPORTS = (
     "mm_paged_decode_window_workspace_bytes", "mm_paged_decode_window", "mm_paged_prefill_window_workspace_bytes", "mm_paged_prefill_window",
     "mm_paged_decode_shared_workspace_bytes", "mm_paged_decode_shared",
     "mm_paged_prefill_tree", "mm_kv_move_rows",
+    "mm_argmax_rows_workspace_bytes", "mm_argmax_rows", "mm_verify_greedy",
     "mm_moe_route", "mm_moe_plan", "mm_moe_gather", "mm_moe_combine",
     "mm_moe_sf_bytes", "mm_moe_quantize", "mm_moe_activate_quantize", "mm_moe_matmul_supported", "mm_moe_matmul",
     "mm_moe_gate_up_activate_supported", "mm_moe_gate_up_activate_describe", "mm_moe_gate_up_activate",
@@ -41,6 +42,8 @@ MM_WS_TICKET_BYTES = 4096
 MM_RMS_REFERENCE, MM_RMS_NO_INTEGER_ROUND = 0, 1
 MM_NORM_NO_INTEGER_ROUND = 0x100
 MM_KV_INT4, MM_KV_BF16, MM_KV_FP8_E4M3 = 0, 1, 3      # 2 is unassigned
+MM_ARGMAX_CHUNK, MM_ARGMAX_MAX_VOCAB, MM_ARGMAX_MAX_ROWS = 8192, 1 << 20, 65535
+MM_VERIFY_STRIDE = 66
 
 class MMGroup(ctypes.Structure):
     """mm_group of include/micromix_hip.h"""
@@ -183,6 +186,13 @@ def load():
         lib.mm_paged_prefill_tree.argtypes = lib.mm_paged_prefill.argtypes + [vp]
         lib.mm_kv_move_rows.restype = i
         lib.mm_kv_move_rows.argtypes = [vp, vp] + [i] * 6 + [vp, vp, i] + [vp] * 3 + [i, vp]
+    if hasattr(lib, "mm_verify_greedy"):               # detected by symbol, like the pairs above
+        lib.mm_argmax_rows_workspace_bytes.restype = sz
+        lib.mm_argmax_rows_workspace_bytes.argtypes = [i, i]
+        lib.mm_argmax_rows.restype = i
+        lib.mm_argmax_rows.argtypes = [vp, i, i, ctypes.c_longlong, vp, vp, sz, vp]
+        lib.mm_verify_greedy.restype = i
+        lib.mm_verify_greedy.argtypes = [vp] * 5 + [i, vp, vp, i, i, vp, vp, vp, vp]
     lib.mm_moe_route.restype = i
     lib.mm_moe_route.argtypes = [vp, i, i, i, vp, vp, vp]
     lib.mm_moe_plan.restype = i

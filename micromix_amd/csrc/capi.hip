@@ -692,6 +692,36 @@ int mm_kv_move_rows(void *kv_data, void *kv_param, int kv_dtype, int max_pages, 
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_kv_move_rows");
 }
 
+// ---- greedy verification of drafts (verify.hip)
+size_t mm_argmax_rows_workspace_bytes(int rows, int vocab) {
+    if (rows <= 0 || vocab < 1 || vocab > MM_ARGMAX_MAX_VOCAB || rows > MM_ARGMAX_MAX_ROWS) return 0;
+    return mm::argmax_workspace_bytes(rows, vocab);
+}
+
+int mm_argmax_rows(const void *logits_bf16, int rows, int vocab, long long ld, int32_t *out_idx, void *workspace, size_t workspace_bytes,
+                   mm_stream_t stream) {
+    if (rows < 0 || vocab < 1 || ld < vocab) return MM_ERR_BAD_ARG;
+    if (vocab > MM_ARGMAX_MAX_VOCAB || rows > MM_ARGMAX_MAX_ROWS) return MM_ERR_UNSUPPORTED;
+    if (rows == 0) return MM_OK;
+    if (!logits_bf16 || !out_idx || ((uintptr_t)logits_bf16 & 1) || ((uintptr_t)out_idx & 3)) return MM_ERR_BAD_ARG;
+    const size_t need = mm::argmax_workspace_bytes(rows, vocab);
+    if (need && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7))) return MM_ERR_BAD_ARG;
+    hipError_t e = mm::launch_argmax_rows(logits_bf16, rows, vocab, ld, out_idx, need ? workspace : nullptr, (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_argmax_rows");
+}
+
+int mm_verify_greedy(const int32_t *target_tok, const int32_t *draft_tok, const int32_t *root_tok, const uint64_t *tree_mask,
+                     const int32_t *qo_indptr, int num_tokens, const int32_t *kv_indptr, const int32_t *last_page_len, int page_size, int batch,
+                     int32_t *result, int32_t *move_src, int32_t *move_dst, mm_stream_t stream) {
+    if (num_tokens < 0 || batch < 0 || page_size < 1 || ((uintptr_t)tree_mask & 7)) return MM_ERR_BAD_ARG;
+    if (batch == 0) return MM_OK;
+    if (!root_tok || !qo_indptr || !kv_indptr || !last_page_len || !result) return MM_ERR_BAD_ARG;
+    if (num_tokens > 0 && (!target_tok || !draft_tok || !move_src || !move_dst)) return MM_ERR_BAD_ARG;
+    hipError_t e = mm::launch_verify_greedy(target_tok, draft_tok, root_tok, tree_mask, qo_indptr, num_tokens, kv_indptr, last_page_len,
+                                            page_size, batch, result, move_src, move_dst, (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_verify_greedy");
+}
+
 // the un-windowed entry points are the windowed ones at window = 0
 size_t mm_paged_decode_window_workspace_bytes(int batch, int num_qo_heads, int num_kv_heads, int max_seq_len, int window) {
     if (batch <= 0 || num_kv_heads <= 0 || num_qo_heads <= 0 || max_seq_len < 0 || window < 0 || num_qo_heads % num_kv_heads) return 0;

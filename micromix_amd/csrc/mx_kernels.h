@@ -290,6 +290,13 @@ hipError_t launch_kv_copy_pages(const PagedKV &kv, const int *src_pages, const i
 // every layer, K and V, every head, all sources read before any destination is written (kv_move.hip); kv.layer is 0
 hipError_t launch_kv_move_rows(const PagedKV &kv, const int *move_indptr, const int *src_pos, const int *dst_pos, int num_moves,
                                hipStream_t stream);
+// greedy verification of drafts (verify.hip): the argmax of bf16 rows (ws: argmax_workspace_bytes, 0 when a row is one part), and the walk
+// that picks each sequence's accepted path and writes the move table launch_kv_move_rows takes with move_indptr = qo_indptr
+size_t argmax_workspace_bytes(int rows, int vocab);
+hipError_t launch_argmax_rows(const void *logits, int rows, int vocab, long long ld, int *out, void *ws, hipStream_t stream);
+hipError_t launch_verify_greedy(const int *target_tok, const int *draft_tok, const int *root_tok, const void *tree_mask, const int *qo_indptr,
+                                int T, const int *kv_indptr, const int *last_page_len, int P, int B, int *result, int *move_src,
+                                int *move_dst, hipStream_t stream);
 // sparse MoE block around the grouped GEMMs (moe.hip): n = T * top_k pairs, H a multiple of 8, rows 16-byte aligned
 hipError_t launch_moe_route(const void *logits, int T, int E, int top_k, int *ids, void *w, hipStream_t stream);
 hipError_t launch_moe_plan(const int *ids, int n, int E, int top_k, int *offsets, int *sorted_token, int *slot_of, hipStream_t stream);

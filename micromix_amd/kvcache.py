@@ -89,12 +89,32 @@ chain from the root under the parents given to `tree_mask`.  No window form: a c
 Measured (Llama-3-8B heads): a 21-node tree in one call is 8 to 16 % faster than its 16 paths as forked sequences and holds
 66 pages for 80; with a chain's words the tree kernels are 1.5 to 3 % slower than the causal ones for int4 and bf16, so verify a
 chain without `tree=`.
+
+    logits = lm_head(hidden)                               # bf16 [T, vocab], the rows of the announced nodes
+    paths, nxt = cache.verify(mixedgemm.argmax_rows(logits), draft_tok, root_tok)     # int32 ids; instead of accept(paths)
+
+Verifying a draft.  Greedy (exact-match) verification picks the path on the device: `mixedgemm.argmax_rows` gives the token the target
+model chooses after every node (torch.argmax's order on the CPU: NaN above +inf, the lowest index among equals), and
+`verify(target_tok, draft_tok, root_tok)` walks each sequence's tree from `root_tok[b]` -- the token chosen after the last committed
+one, the previous step's bonus -- taking the lowest-numbered child whose draft token is the one wanted, until there is none.  It is two
+halves.  `verify_launch` runs `mixedgemm.verify_greedy` (one wave per sequence; a node's parent is read from its `tree_mask` word, the
+highest bit below its own) and then `mixedgemm.kv_move_rows` straight from the move table the walk wrote, with no host work between or
+before them, so `argmax_rows` -> `verify_launch` can close the captured graph of a step; it uses the words of the last `tree_mask`
+call, chains without one.  `commit(result)` copies 66 ints per sequence to the host -- the path's length, the bonus token, the path --
+and does `accept`'s validation and bookkeeping without launching moves.  A sequence with more than 64 announced tokens or a negative
+`root_tok` is a prompt chunk and keeps all its tokens; a cache made with `window=` verifies chains, which have no moves.  A path the
+host validation refuses (ValueError) is refused after the rows have moved: the announced rows are then undefined, the committed tokens
+untouched, and `truncate(b, base_b)` recovers.  Token ids are int32 (convert torch.argmax's and a tokenizer's int64).
+Measured (vocabulary 128 256): `argmax_rows` takes 5 to 9 us for 1 to 64 rows and 61 us for 64 x 21 (71 % of 8 TB/s), 2 to
+8 x faster than torch.argmax; `verify_launch` 5 to 6 us for one sequence's 21-node tree in 32 layers, 42 to 48 us for 64.  By the host
+clock the whole `verify` is 14 % shorter than ids to the host + a Python walk + `accept` for 64 sequences and no shorter for one:
+`commit` still pays `accept`'s bookkeeping and table upload.  What it buys is a step whose device work is one graph.
 """
 from __future__ import annotations
 
 import torch
 
-from . import mixedgemm
+from . import _lib, mixedgemm
 
 HEAD_DIM = 128
 
@@ -139,6 +159,10 @@ class PagedKVCache:
         self.num_new_tokens = 0
         self._announced = None                                  # (counts, bases) of the last extend while the tables are still its own
         self._parents = None                                    # what tree_mask was given for them (None: chains)
+        self._tree_words = None                                 # tree_mask's words, kept at one address for verify_launch ...
+        self._tree_words_live = False                           # ... and whether they describe the tokens announced now
+        self._verify_result = torch.zeros((batch, _lib.MM_VERIFY_STRIDE), **i32)
+        self._verify_moves = None                               # move_src | move_dst, two halves of one tensor
         self._workspace = None
         self._shared_workspace = None
         self._prefill_workspace = None
@@ -164,6 +188,7 @@ class PagedKVCache:
         self.append_indptr.copy_(torch.tensor(app, dtype=torch.int32))
         self.num_new_tokens = app[-1]
         self._announced = self._parents = None                  # extend sets them again after its upload
+        self._tree_words_live = False
         groups, shared = self.share_groups()
         gptr = [0]
         for grp in groups:
@@ -370,7 +395,8 @@ class PagedKVCache:
         `attend_new(tree=)`, bit i of word j set when i is j or an ancestor of j.  depths[b][i]: the nodes between i and the committed
         tokens, so node i stands at position base_b + depths[b][i], which is the cos / sin row to give `append_rope` for it.
         ValueError for a parent >= its index or < -1, a list of the wrong length, a tree of more than 64 nodes, and tables changed
-        since the `extend`.  The parents are kept for `accept`."""
+        since the `extend`.  The parents are kept for `accept`, and a copy of the words for `verify_launch`: in a tensor of the cache's
+        own that keeps its address while the token count does not grow, so a captured `verify_launch` replays with the next tree."""
         if self._announced is None:
             raise ValueError("tree_mask: the page tables changed since the last extend (fork, truncate, reset, accept): nothing is announced")
         counts = self._announced[0]
@@ -399,6 +425,12 @@ class PagedKVCache:
             kept.append(par)
         self._parents = kept
         mask = torch.tensor([x - (1 << 64) if x >> 63 else x for x in words], dtype=torch.int64).to(self.device)
+        if self._tree_words is None or self._tree_words.numel() < mask.numel():
+            if self._tree_words is not None:
+                self._retired.append(self._tree_words)           # a graph captured earlier may still point at it
+            self._tree_words = torch.zeros((max(mask.numel(), 64 * self.batch),), dtype=torch.int64, device=self.device)
+        self._tree_words[: mask.numel()].copy_(mask)
+        self._tree_words_live = True
         return mask, depths
 
     def accept(self, paths):
@@ -409,28 +441,10 @@ class PagedKVCache:
         Call it after every layer's `append`, outside graph capture.  A sequence that took its own copy of a shared last page at the
         `extend` keeps it, also when its whole draft is dropped.  ValueError when the tables changed since the `extend`, and for a
         path that is not a chain from the root under the parents of the last `tree_mask` (without one: causal chains, so a prefix
-        0, 1, .. k - 1)."""
-        if self._announced is None:
-            raise ValueError("accept: the page tables changed since the last extend (fork, truncate, reset, accept): nothing to accept")
-        counts, bases = self._announced
-        if len(paths) != self.batch:
-            raise ValueError(f"accept: need {self.batch} paths")
-        parents = self._parents or [None] * self.batch
-        checked = []
-        for b, path in enumerate(paths):
-            if path is None:
-                if counts[b]:
-                    raise ValueError(f"accept: sequence {b} announced {counts[b]} tokens and has no path ([] drops them all)")
-                path = []
-            path = [int(p) for p in path]
-            for i, p in enumerate(path):
-                if not 0 <= p < counts[b]:
-                    raise ValueError(f"accept: token {p} is not one of the {counts[b]} sequence {b} announced")
-                parent = p - 1 if parents[b] is None else parents[b][p]
-                if parent != (path[i - 1] if i else -1):
-                    raise ValueError(f"accept: token {p} of sequence {b} does not continue the path (its parent is {parent})")
-            self._check_length(b, bases[b] + len(path), "accept")
-            checked.append(path)
+        0, 1, .. k - 1).  `verify` picks the paths on the device and does all of this without the host in between (the module
+        docstring, "Verifying a draft")."""
+        checked = self._checked_paths(paths, "accept")
+        bases = self._announced[1]
         indptr, src, dst = [0], [], []
         for b, path in enumerate(checked):
             for i, p in enumerate(path):
@@ -440,9 +454,123 @@ class PagedKVCache:
             indptr.append(len(src))
         if src:
             self._move_rows(indptr, src, dst)
+        self._keep_paths(checked)
+
+    def _checked_paths(self, paths, what):
+        """`paths` as lists of ints, each a chain from the root of what the last `extend` announced; ValueError otherwise"""
+        if self._announced is None:
+            raise ValueError(f"{what}: the page tables changed since the last extend (fork, truncate, reset, accept): nothing to accept")
+        counts, bases = self._announced
+        if len(paths) != self.batch:
+            raise ValueError(f"{what}: need {self.batch} paths")
+        parents = self._parents or [None] * self.batch
+        checked = []
+        for b, path in enumerate(paths):
+            if path is None:
+                if counts[b]:
+                    raise ValueError(f"{what}: sequence {b} announced {counts[b]} tokens and has no path ([] drops them all)")
+                path = []
+            path = [int(p) for p in path]
+            for i, p in enumerate(path):
+                if not 0 <= p < counts[b]:
+                    raise ValueError(f"{what}: token {p} is not one of the {counts[b]} sequence {b} announced")
+                parent = p - 1 if parents[b] is None else parents[b][p]
+                if parent != (path[i - 1] if i else -1):
+                    raise ValueError(f"{what}: token {p} of sequence {b} does not continue the path (its parent is {parent})")
+            self._check_length(b, bases[b] + len(path), what)
+            checked.append(path)
+        return checked
+
+    def _keep_paths(self, checked):
+        """the bookkeeping after the rows of the checked paths were packed down: every sequence ends behind its path, one upload"""
+        bases = self._announced[1]
         for b, path in enumerate(checked):
             self._shorten(b, bases[b] + len(path))
         self._upload([0] * self.batch)
+
+    def verify_launch(self, target_tok, draft_tok, root_tok):
+        """The device half of `verify`: `mixedgemm.verify_greedy` over the tokens the last `extend` announced -- with the cache's own
+        tables, `append_indptr`, and the words of the last `tree_mask` call (chains when it was not called since the `extend`) --
+        and then, on the same stream with nothing in between, `mixedgemm.kv_move_rows` from the move table it wrote.  target_tok,
+        draft_tok: int32 [num_new_tokens], root_tok: int32 [batch], on the cache's device (what they mean: `mixedgemm.verify_greedy`).
+        Returns the result tensor, int32 [batch, 66], the same tensor at every call; give it to `commit`.  Nothing is allocated after
+        the first call with a token count, and nothing is read on the host: capturable, after every layer's `append`.  A graph
+        captured with a tree replays with a tree (`tree_mask` writes the next one where the graph reads it), one captured with
+        chains with chains.  ValueError on a cache made with window= when `tree_mask` was given a tree: chains only there."""
+        if self.device.type == "cpu":
+            raise RuntimeError("verify_launch needs a device cache; a CPU cache verifies with verify()")
+        if self.window and any(p is not None for p in self._parents or ()):
+            raise ValueError(f"verify_launch has no sliding-window form for trees: this cache was made with window={self.window}")
+        T = self.num_new_tokens
+        if self._verify_moves is None or self._verify_moves.size(1) < T:
+            if self._verify_moves is not None:
+                self._retired.append(self._verify_moves)         # a graph captured earlier may still point at it
+            self._verify_moves = torch.full((2, max(T, 64 * self.batch)), -1, dtype=torch.int32, device=self.device)
+        src, dst = self._verify_moves[0, :T], self._verify_moves[1, :T]
+        mixedgemm.verify_greedy(target_tok, draft_tok, root_tok, self.append_indptr, self.kv_indptr, self.last_page_len, self.page_size,
+                                tree_mask=self._tree_words[:T] if self._tree_words_live else None, result=self._verify_result,
+                                move_src=src, move_dst=dst)
+        mixedgemm.kv_move_rows(self.kv_data, self.kv_param, self.kv_indptr, self.kv_indices, self.append_indptr, src, dst)
+        return self._verify_result
+
+    @staticmethod
+    def _paths_of(rows, counts):
+        """(paths, next_tokens) from the rows of a verify result: k path entries, or -- a sequence that keeps all -- every token"""
+        paths, nxt = [], []
+        for row, n in zip(rows, counts):
+            k = row[0]
+            paths.append(list(range(k)) if k and row[2] < 0 else row[2:2 + k])
+            if not n and not k:
+                paths[-1] = None
+            nxt.append(row[1])
+        return paths, nxt
+
+    def commit(self, result):
+        """The host half of `verify`: one device-to-host copy of `result` (what `verify_launch` returned, also after a graph replay),
+        then the validation and the bookkeeping of `accept` for the paths it holds -- no move is launched: the rows were packed by
+        `verify_launch`.  Returns (paths, next_tokens): paths[b] as `accept` takes it (every announced token for a sequence that kept
+        all, None where nothing was announced), next_tokens[b] the bonus token (`mixedgemm.verify_greedy`, result[b][1]).
+        ValueError as `accept` raises it, here AFTER the rows have moved -- a path the parents of `tree_mask` do not allow, which
+        includes a tree sequence that kept all (root_tok < 0): the rows of the announced tokens are then undefined, the committed
+        tokens are untouched, and `truncate(b, base_b)` for every sequence (base_b = seq_lens[b] minus what it announced) recovers."""
+        if self._announced is None:
+            raise ValueError("commit: the page tables changed since the last extend (fork, truncate, reset, accept): nothing to accept")
+        paths, nxt = self._paths_of(result.cpu().tolist(), self._announced[0])
+        self._keep_paths(self._checked_paths(paths, "commit"))
+        return paths, nxt
+
+    def verify(self, target_tok, draft_tok, root_tok):
+        """Greedy verification of the tokens the last `extend` announced, after every layer's `append`: `verify_launch` then `commit`
+        (the module docstring, "Verifying a draft"); returns (paths, next_tokens).  On a CPU cache the walk runs here, in plain
+        Python, and `accept` moves the rows: the rule in words."""
+        if self.device.type != "cpu":
+            return self.commit(self.verify_launch(target_tok, draft_tok, root_tok))
+        if self._announced is None:
+            raise ValueError("verify: the page tables changed since the last extend (fork, truncate, reset, accept): nothing to accept")
+        counts = self._announced[0]
+        parents = self._parents or [None] * self.batch
+        target, draft, roots = (t.tolist() for t in (target_tok, draft_tok, root_tok))
+        if len(target) != self.num_new_tokens or len(draft) != self.num_new_tokens or len(roots) != self.batch:
+            raise RuntimeError(f"verify expects the {self.num_new_tokens} tokens announced by extend() and {self.batch} root tokens")
+        paths, nxt, q0 = [], [], 0
+        for b, n in enumerate(counts):
+            if n > 64 or roots[b] < 0:                           # no draft: a prompt chunk keeps all
+                paths.append(list(range(n)) if n else None)
+                nxt.append(target[q0 + n - 1] if n else -1)
+            else:
+                cur, want, path = -1, roots[b], []
+                while True:
+                    step = [i for i in range(n) if (i - 1 if parents[b] is None else parents[b][i]) == cur and draft[q0 + i] == want]
+                    if not step:
+                        break
+                    cur = step[0]
+                    path.append(cur)
+                    want = target[q0 + cur]
+                paths.append(path if n else None)
+                nxt.append(want)
+            q0 += n
+        self.accept(paths)
+        return paths, nxt
 
     def _move_rows(self, indptr, src, dst):
         """positions src -> dst within each sequence (indptr splits them), every layer: one launch on the current stream"""

@@ -31,6 +31,7 @@ from . import _lib
 __all__ = ["test_function", "matmul", "gate_up_activate", "interleave_gate_up", "reorder_quantize_x", "reorder_quantize_w", "reorder_quantize_w4", "activate_quantize_x",
            "downproj_quantize_w", "downproj_quantize_w4", "rmsnorm_quantize_x", "qlinear_decode", "qlinear_decode_supported", "matmul_grouped", "reorder_quantize_x_grouped",
            "kv_append", "rope_kv_append", "kv_copy_pages", "kv_move_rows", "paged_decode", "paged_decode_workspace_bytes", "paged_decode_shared", "paged_decode_shared_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes",
+           "argmax_rows", "argmax_rows_workspace_bytes", "verify_greedy",
            "moe_route", "moe_plan", "moe_gather", "moe_combine",
            "moe_expert_table", "moe_sf_bytes", "moe_quantize", "moe_activate_quantize", "moe_matmul", "moe_matmul_supported",
            "permute_packed_rows", "moe_gate_up_table", "moe_gate_up_activate", "moe_gate_up_activate_supported"]
@@ -1058,6 +1059,119 @@ def kv_move_rows(kv_data, kv_param, kv_indptr, kv_indices, move_indptr, src_pos,
                                  _stream_ptr(dev))
     if st:
         _lib.check(st, "kv_move_rows")
+
+
+def _verify_lib():
+    lib = _lib.load()
+    if not hasattr(lib, "mm_verify_greedy"):
+        raise _lib.MicroMixLibraryError("libmicromix_hip.so has no mm_argmax_rows / mm_verify_greedy: it was built before draft "
+                                        "verification; rebuild it with `python -m micromix_amd.build --force`")
+    return lib
+
+
+def argmax_rows_workspace_bytes(rows, vocab):
+    """bytes of workspace `argmax_rows` needs for bf16 logits [rows, vocab]; 0 when a row is one part (vocab <= MM_ARGMAX_CHUNK)"""
+    return int(_verify_lib().mm_argmax_rows_workspace_bytes(int(rows), int(vocab)))
+
+
+def argmax_rows(logits, *, out=None, workspace=None):
+    """The index of each row's maximum: logits bf16 [rows, vocab] on the device, last stride 1, any row stride >= vocab (a slice
+    logits[:, :V] of a padded lm_head output, at any 2-byte-aligned offset, is taken as it is: nothing is copied).  Returns int32 [rows]
+    (`out` when given).  The order is torch.argmax's on the CPU: any NaN is greater than +inf, +0 == -0, the lowest index among equal
+    maxima wins.  vocab <= 2^20, rows <= 65535.  workspace: a contiguous device tensor of `argmax_rows_workspace_bytes(rows, vocab)`
+    bytes, uninitialised, allocated when needed and not given (under graph capture pass one).  Runs on the current stream,
+    capture-safe."""
+    lib = _verify_lib()
+    if not isinstance(logits, torch.Tensor):
+        raise TypeError("logits must be a torch.Tensor")
+    if logits.dtype is not torch.bfloat16:
+        raise TypeError(f"logits must be torch.bfloat16, got {logits.dtype}")
+    if not logits.is_cuda:
+        raise RuntimeError("logits must be a device tensor (HIP); the MicroMix ops have no CPU path")
+    if logits.dim() != 2 or logits.size(1) < 1:
+        raise RuntimeError("logits must be [rows, vocab] with vocab >= 1")
+    rows, vocab = logits.shape
+    if vocab > 1 and logits.stride(1) != 1:
+        raise RuntimeError("logits must have unit stride along the vocabulary (the rows may be any distance >= vocab apart)")
+    ld = logits.stride(0) if rows > 1 else vocab
+    if ld < vocab:
+        raise RuntimeError(f"logits rows overlap: row stride {ld} < vocab {vocab}")
+    dev = logits.device
+    if out is None:
+        out = torch.empty((rows,), dtype=torch.int32, device=dev)
+    elif not _ok(out, torch.int32, dev.index) or out.dim() != 1 or out.numel() != rows:
+        _check_tensor(out, "out", torch.int32, dev)
+        raise RuntimeError(f"out must be int32 [{rows}]")
+    workspace, ws_args = _kv_workspace(workspace, argmax_rows_workspace_bytes(rows, vocab), dev)
+    with _on_device(dev.index):
+        st = lib.mm_argmax_rows(_ptr(logits), rows, vocab, ld, _ptr(out), *ws_args, _stream_ptr(dev))
+    if st:
+        _lib.check(st, "argmax_rows")
+    return out
+
+
+def verify_greedy(target_tok, draft_tok, root_tok, qo_indptr, kv_indptr, last_page_len, page_size, *, tree_mask=None, result=None,
+                  move_src=None, move_dst=None):
+    """Greedy (exact-match) verification of tree or chain drafts, one wave per sequence; returns (result, move_src, move_dst).
+
+    Sequence b has the n = qo_indptr[b + 1] - qo_indptr[b] draft nodes of rows qo_indptr[b] .. : draft_tok[t] is a node's token,
+    target_tok[t] the token the target model picks after it (`argmax_rows` of its logits, or any sampler's choice), root_tok[b] the token
+    picked after the last committed one.  tree_mask: the int64 words of `paged_prefill(tree_mask=)` -- a node's parent is the highest set
+    bit below its own -- or None for chains.  Starting from root_tok[b], the walk takes the lowest-numbered child of the node just taken
+    whose token is the one wanted, until there is none.  result int32 [B, 66]: [0] the path's length k, [1] the bonus token (the
+    target's choice after the last node taken; root_tok[b] when nothing matched), [2 : 2 + k] the path, the rest -1.  A sequence with
+    n > 64 or root_tok[b] < 0 is a prompt chunk and keeps all: [0] = n, [1] = target_tok of its last row (-1 for n = 0), path entries -1.
+    move_src, move_dst int32 [T], laid over qo_indptr: pass them on as `kv_move_rows(..., move_indptr=qo_indptr, move_src, move_dst)`
+    to pack each path down to the positions base_b .. base_b + k - 1 (base_b = len_b - n, len_b from kv_indptr / last_page_len /
+    page_size).  Every element of the three outputs is written.  All tensors are int32 on one device (token ids as int64 are refused:
+    convert them with .to(torch.int32)).  Runs on the current stream, capture-safe (include/micromix_hip.h, mm_verify_greedy)."""
+    lib = _verify_lib()
+    ints = (("target_tok", target_tok), ("draft_tok", draft_tok), ("root_tok", root_tok), ("qo_indptr", qo_indptr), ("kv_indptr", kv_indptr),
+            ("last_page_len", last_page_len))
+    for n, t in ints:                                      # what torch.argmax and a tokenizer hand over: say what to do about it
+        if isinstance(t, torch.Tensor) and t.dtype is torch.int64:
+            raise TypeError(f"{n} must be torch.int32, got torch.int64: convert it with {n}.to(torch.int32)")
+    if not (isinstance(target_tok, torch.Tensor) and target_tok.is_cuda):
+        _check_tensor(target_tok, "target_tok", torch.int32)
+    dev = target_tok.device
+    for n, t in ints:
+        if not _ok(t, torch.int32, dev.index):
+            _check_tensor(t, n, torch.int32, dev)
+        if t.dim() != 1:
+            raise RuntimeError(f"{n} must be one-dimensional")
+    T, B = target_tok.numel(), root_tok.numel()
+    if draft_tok.numel() != T:
+        raise RuntimeError("target_tok and draft_tok must be of one length")
+    if qo_indptr.numel() != B + 1 or kv_indptr.numel() != B + 1 or last_page_len.numel() != B:
+        raise RuntimeError("qo_indptr and kv_indptr must have B + 1 entries and last_page_len B (B = root_tok.numel())")
+    page_size = int(page_size)
+    if page_size < 1:
+        raise ValueError("page_size must be positive")
+    if tree_mask is not None:
+        if not _ok(tree_mask, torch.int64, dev.index):
+            _check_tensor(tree_mask, "tree_mask", torch.int64, dev)
+        if tree_mask.dim() != 1 or tree_mask.numel() != T:
+            raise RuntimeError(f"tree_mask must be int64 [{T}], one word per row")
+    if result is None:
+        result = torch.empty((B, _lib.MM_VERIFY_STRIDE), dtype=torch.int32, device=dev)
+    elif not _ok(result, torch.int32, dev.index) or tuple(result.shape) != (B, _lib.MM_VERIFY_STRIDE):
+        _check_tensor(result, "result", torch.int32, dev)
+        raise RuntimeError(f"result must be int32 [{B}, {_lib.MM_VERIFY_STRIDE}]")
+    moves = []
+    for n, t in (("move_src", move_src), ("move_dst", move_dst)):
+        if t is None:
+            t = torch.empty((T,), dtype=torch.int32, device=dev)
+        elif not _ok(t, torch.int32, dev.index) or t.dim() != 1 or t.numel() != T:
+            _check_tensor(t, n, torch.int32, dev)
+            raise RuntimeError(f"{n} must be int32 [{T}]")
+        moves.append(t)
+    with _on_device(dev.index):
+        st = lib.mm_verify_greedy(_ptr(target_tok), _ptr(draft_tok), _ptr(root_tok), _ptr(tree_mask) if tree_mask is not None else None,
+                                  _ptr(qo_indptr), T, _ptr(kv_indptr), _ptr(last_page_len), page_size, B, _ptr(result), _ptr(moves[0]),
+                                  _ptr(moves[1]), _stream_ptr(dev))
+    if st:
+        _lib.check(st, "verify_greedy")
+    return result, moves[0], moves[1]
 
 
 def _token_rows(t, name, heads):
