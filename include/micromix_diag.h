@@ -19,10 +19,17 @@ typedef void *mm_stream_t; /* hipStream_t */
  *     a_regs/b_regs [64 lanes][8] int32; scale_a/scale_b [64] int32; out [64][16|4] float.
  *   mm_diag_hw_convert: v_cvt_scalef32_pk_{fp4,fp8}_bf16 / pk32_bf6_bf16 on n (multiple of 32)
  *     bf16 values with one scale; out_codes gets one element code per byte.
+ *   mm_diag_hw_convert_f32: the same from n fp32 values, through the converters (v_cvt_scalef32_pk_{fp4,fp8}_f32 / 2xpk16_bf6_f32)
+ *     and the element order of the reorder-free quantizers' shared code (csrc/mx_direct_convert.h: convert32).
+ *     saturate = 0: unclamped, as quantize32 calls it (past FMAX * scale the fp8 converter returns the NaN code); 1: convert32's
+ *     saturating form.
+ *   mm_diag_silu_mul: out_f32[i] = silu(a[i]) * b[i] of bf16 a, b as those quantizers evaluate it in fp32 (silu_mul, same header).
  */
 int mm_diag_mfma(int shape, int el_a, int el_b, int opsel, const void *a_regs, const void *b_regs, const void *scale_a,
                  const void *scale_b, void *out, mm_stream_t stream);
 int mm_diag_hw_convert(const void *src_bf16, int n, float scale, int el, uint8_t *out_codes, mm_stream_t stream);
+int mm_diag_hw_convert_f32(const void *src_f32, int n, float scale, int el, int saturate, uint8_t *out_codes, mm_stream_t stream);
+int mm_diag_silu_mul(const void *a_bf16, const void *b_bf16, int n, void *out_f32, mm_stream_t stream);
 /* Issue-rate microbenchmark: `blocks` workgroups of 4 waves, each wave issues iters*8 independent scaled
  * MFMAs on register operands taken from seed_regs ([128][8] int32).  flops = blocks*4*iters*8*2*M*N*K. */
 int mm_diag_mfma_rate(int shape, int el_a, int el_b, int blocks, int iters, const void *seed_regs, void *sink,

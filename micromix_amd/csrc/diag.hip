@@ -7,6 +7,7 @@
 #include "../../include/micromix_diag.h"
 #include "../../include/micromix_hip.h"   // status codes only
 #include "mx_common.h"
+#include "mx_direct_convert.h"
 
 namespace mm {
 
@@ -117,6 +118,37 @@ __global__ void diag_hw_convert(const uint16_t *src, int ngroups, float scale, i
     }
 }
 
+// The fp32-source twin: one thread converts one 32-element group with convert32 (mx_direct_convert.h) -- the three converters and
+// the MM_BF6_LO / MM_BF6_HI element order every quantize32 site uses, unclamped as quantize32 calls it (SAT false) or saturating -- and
+// spreads the packed bytes to one code per byte
+template <int EL, bool SAT>
+__global__ void diag_hw_convert_f32(const float *src, int ngroups, float scale, uint8_t *out) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= ngroups) return;
+    float v[32];
+#pragma unroll
+    for (int i = 0; i < 32; ++i) v[i] = src[(size_t)g * 32 + i];
+    __attribute__((aligned(16))) uint8_t packed[32];
+    convert32<EL, false, SAT>(v, scale, packed);
+    uint8_t *o = out + (size_t)g * 32;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+        if constexpr (EL == EL_FP4) o[i] = (packed[i >> 1] >> (4 * (i & 1))) & 0xF;
+        else if constexpr (EL == EL_FP8) o[i] = packed[i];
+        else {
+            const int bit = 6 * i, at = bit >> 3, off = bit & 7;          // dense little-endian bit stream (oracle: pack_fp6)
+            const unsigned two = packed[at] | ((at + 1 < 24 ? (unsigned)packed[at + 1] : 0u) << 8);
+            o[i] = (two >> off) & 0x3F;
+        }
+    }
+}
+
+// silu_mul (mx_direct_convert.h) of bf16 a, b per element, the fp32 result as the quantizers see it
+__global__ void diag_silu_mul(const uint16_t *a, const uint16_t *b, int n, float *out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = silu_mul(__uint_as_float((uint32_t)a[i] << 16), __uint_as_float((uint32_t)b[i] << 16));
+}
+
 // Register-only issue-rate loop: every wave issues `iters` x 8 independent scaled MFMAs.
 template <int FA, int FB, int SHAPE>
 __global__ void __launch_bounds__(256) diag_mfma_rate(const v8i *seed, int iters, float *sink) {
@@ -207,6 +239,27 @@ int mm_diag_hw_convert(const void *src_bf16, int n, float scale, int el, uint8_t
     const int groups = n / 32;
     hipLaunchKernelGGL(mm::diag_hw_convert, dim3((groups + 63) / 64), dim3(64), 0, (hipStream_t)stream,
                        (const uint16_t *)src_bf16, groups, scale, el, out_codes);
+    return hipGetLastError() == hipSuccess ? MM_OK : MM_ERR_LAUNCH;
+}
+
+int mm_diag_hw_convert_f32(const void *src_f32, int n, float scale, int el, int saturate, uint8_t *out_codes, mm_stream_t stream) {
+    if (n < 0 || (n % 32) || el < 0 || el > 2) return MM_ERR_BAD_ARG;
+    if (n == 0) return MM_OK;
+    const int groups = n / 32;
+    const dim3 grid((groups + 63) / 64), block(64);
+    hipStream_t s = (hipStream_t)stream;
+    auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, 0, s, (const float *)src_f32, groups, scale, out_codes); };
+    if (el == mm::EL_FP4) saturate ? launch(mm::diag_hw_convert_f32<mm::EL_FP4, true>) : launch(mm::diag_hw_convert_f32<mm::EL_FP4, false>);
+    else if (el == mm::EL_FP6) saturate ? launch(mm::diag_hw_convert_f32<mm::EL_FP6, true>) : launch(mm::diag_hw_convert_f32<mm::EL_FP6, false>);
+    else saturate ? launch(mm::diag_hw_convert_f32<mm::EL_FP8, true>) : launch(mm::diag_hw_convert_f32<mm::EL_FP8, false>);
+    return hipGetLastError() == hipSuccess ? MM_OK : MM_ERR_LAUNCH;
+}
+
+int mm_diag_silu_mul(const void *a_bf16, const void *b_bf16, int n, void *out_f32, mm_stream_t stream) {
+    if (n < 0) return MM_ERR_BAD_ARG;
+    if (n == 0) return MM_OK;
+    hipLaunchKernelGGL(mm::diag_silu_mul, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const uint16_t *)a_bf16,
+                       (const uint16_t *)b_bf16, n, (float *)out_f32);
     return hipGetLastError() == hipSuccess ? MM_OK : MM_ERR_LAUNCH;
 }
 }

@@ -30,23 +30,25 @@ __device__ __forceinline__ int scale_exponent_f32(float amax) {
     return e < -127 ? -127 : (e > 127 ? 127 : e);
 }
 
+// 32 fp32 values -> the packed codes of RNE_fmt(v / scale), one rounding (the three fp32-source converters; mm_diag_hw_convert_f32 of
+// diag.hip runs exactly this against the oracle's encoder).  Past FMAX * scale the fp4 / fp6 converters saturate, but the fp8 one returns
+// the e4m3 NaN code for everything that rounds beyond 448 (measured).  quantize32's exponent rule gives amax <= FMAX * scale
+// for every finite block, so it converts unclamped (SAT = false: no instruction for a case it cannot meet); a caller with a scale of
+// its own takes SAT = true, which clamps the fp8 inputs to +-448 * 2^e first (e the scale's exponent field, which is all the converter
+// reads; field 0 means 2^-127) -- the satfinite conversion of the reference and of the oracle's encoder.
 // (GLOBAL_OUT: the fp4 codes leave through a write-through global store; false for destinations in LDS)
-template <int EL, bool GLOBAL_OUT = true>
-__device__ __forceinline__ uint32_t quantize32(const float (&v)[32], uint8_t *__restrict__ out) {
-    float amax = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 32; ++i) amax = fmaxf(amax, fabsf(v[i]));
-    int e = 0;                                   // scale 1.0
-    if (amax > 1e-6f) e = scale_exponent_f32<EL>(amax);
-    const int ec = e < -126 ? -126 : e;          // 2^-127 is not a normal fp32; only reachable for amax < FMAX * 2^-127
-    const float scale = __uint_as_float((uint32_t)(127 + ec) << 23);
+template <int EL, bool GLOBAL_OUT = true, bool SAT = false>
+__device__ __forceinline__ void convert32(const float (&v)[32], float scale, uint8_t *__restrict__ out) {
     if constexpr (EL == EL_FP8) {
+        const uint32_t field = __float_as_uint(scale) & 0x7F800000u;
+        const float lim = field ? 448.0f * __uint_as_float(field) : 0x1.cp-119f;
+        auto in = [&](int i) { return SAT ? fminf(fmaxf(v[i], -lim), lim) : v[i]; };
         uint32_t w[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             ds2 r = {0, 0};
-            r = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(r, v[4 * i], v[4 * i + 1], scale, false);
-            r = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(r, v[4 * i + 2], v[4 * i + 3], scale, true);
+            r = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(r, in(4 * i), in(4 * i + 1), scale, false);
+            r = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(r, in(4 * i + 2), in(4 * i + 3), scale, true);
             __builtin_memcpy(&w[i], &r, 4);
         }
         uint4 *o = reinterpret_cast<uint4 *>(out);
@@ -77,6 +79,17 @@ __device__ __forceinline__ uint32_t quantize32(const float (&v)[32], uint8_t *__
         o[1] = make_uint2(r[2], r[3]);
         o[2] = make_uint2(r[4], r[5]);
     }
+}
+
+template <int EL, bool GLOBAL_OUT = true>
+__device__ __forceinline__ uint32_t quantize32(const float (&v)[32], uint8_t *__restrict__ out) {
+    float amax = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) amax = fmaxf(amax, fabsf(v[i]));
+    int e = 0;                                   // scale 1.0
+    if (amax > 1e-6f) e = scale_exponent_f32<EL>(amax);
+    const int ec = e < -126 ? -126 : e;          // 2^-127 is not a normal fp32; only reachable for amax < FMAX * 2^-127
+    convert32<EL, GLOBAL_OUT>(v, __uint_as_float((uint32_t)(127 + ec) << 23), out);
     return (uint32_t)(e + 127);
 }
 
