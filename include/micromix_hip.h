@@ -565,6 +565,49 @@ int mm_verify_greedy(const int32_t *target_tok /* [T] */, const int32_t *draft_t
                      int32_t *result /* [batch, 66] */, int32_t *move_src /* [T] */, int32_t *move_dst /* [T] */, mm_stream_t stream);
 
 /*
+ * Sampling on the device (detect the two entries by their symbols; mm_version stays 660): out_idx[r] = a token drawn from row r of
+ * bf16 logits under temperature, top-k, top-p and min-p, so that mm_sample_rows -> mm_verify_greedy closes a captured speculative
+ * step as mm_argmax_rows -> mm_verify_greedy does for greedy decoding: sample the target's token at every node, keep the draft path
+ * that matches, emit the target's sample as the bonus token -- distributed as the target model's, whatever the draft.  The library
+ * draws no random numbers: u brings one uniform number per row.  u, temperature, top_k, top_p, min_p are DEVICE arrays of `rows`
+ * entries (fp32; top_k int32), read by the kernels only, so one captured graph serves any mix of requests rewritten in place.  A null
+ * temperature means 1.0, a null filter array means that filter is off; u is required.  Nothing is read on the host, nothing allocated.
+ * The rule, for row r with logits l_i (i < vocab), u = u[r] (NaN -> 0, else clamped to [0, 1 - 2^-24]), T = temperature[r],
+ * k = top_k[r], p = top_p[r], q = min_p[r]:
+ *   1 Greedy cases.  m = the row maximum in mm_argmax_rows' order.  m NaN or +-inf, T <= 0 or T NaN: out_idx[r] is exactly what
+ *     mm_argmax_rows returns for the row.  Every other row has a finite m and no NaN.
+ *   2 Weights.  w_i = exp((l_i - m) / T), -inf -> 0; the maximum has w = 1.
+ *   3 Classes.  Tokens of equal value form one class (+0 and -0 are one class, as in mm_argmax_rows' key); the classes are ordered by
+ *     descending value; each filter keeps a non-empty prefix of that order.
+ *   4 Filters.  top-k: the shortest prefix whose token count is >= k, for 1 <= k < vocab (any other k: off); Z_k is its mass.
+ *     top-p: the shortest prefix whose mass is >= p * Z_k, for p < 1 (p <= 0: the top class only; p >= 1 or NaN: off).
+ *     min-p: the classes with w >= q, for 0 < q <= 1 (any other q: off).
+ *   5 Kept set.  The shortest of the three prefixes.  Whole classes are kept, so equal logits are treated equally: HF's
+ *     TopKLogitsWarper exactly; for top-p a superset of HF's set by at most the rest of one tie class; min-p does not depend on where
+ *     it stands in the chain.
+ *   6 Draw.  Z = the kept mass; out_idx[r] = the first kept index i, in ascending index order, with sum_{kept j <= i} w_j > u * Z; if
+ *     rounding leaves none, the last kept index with w > 0.
+ *   How the kernels realise it: w = exp2((l - m) * (log2e / T)) in fp32 (V_EXP_F32), then W = trunc(w * 2^43) as a 64-bit integer, and
+ *   every mass above is a sum of W's.  Integer sums are exact and do not depend on their order, so the result is a function of the
+ *   inputs alone -- the same bits on every run and however a row is divided -- and "rounding leaves none" cannot occur.  A bf16 row holds
+ *   at most 65 281 classes, named by mm_argmax_rows' 16-bit key: the filters are a radix select on it (two 256-bin histogram levels of
+ *   counts and masses), without a sort.  tests/sample_oracle.py derives the bound on a prefix mass against the rule in exact arithmetic.
+ *   logits, ld, the limits on vocab and rows and the split into parts of MM_ARGMAX_CHUNK columns: as mm_argmax_rows (2-byte alignment,
+ *   any ld >= vocab).  workspace: mm_sample_rows_workspace_bytes(rows, vocab) bytes (0 for arguments mm_sample_rows refuses), 8-byte
+ *   aligned, always needed, no initialisation needed: every word read was written by the same call.  It holds 3 KiB per part of every
+ *   row (the histograms) and 2 KiB per row.  Launches: mm_argmax_rows' one or two, then 2 (no top_k and no top_p array) or 8.
+ *   Null logits, u or out_idx with rows > 0, rows < 0, vocab < 1, ld < vocab, an odd logits address, any other array that is not 4-byte
+ *   aligned, a workspace that is null, too small or not 8-byte aligned: MM_ERR_BAD_ARG.  vocab > MM_ARGMAX_MAX_VOCAB or
+ *   rows > MM_ARGMAX_MAX_ROWS: MM_ERR_UNSUPPORTED.  rows == 0: MM_OK.  All without device work.
+ */
+size_t mm_sample_rows_workspace_bytes(int rows, int vocab);
+int mm_sample_rows(const void *logits_bf16, int rows, int vocab, long long ld /* elements between rows, >= vocab */,
+                   const float *u /* [rows] */, const float *temperature /* [rows] or null: 1.0 */,
+                   const int32_t *top_k /* [rows] or null: off */, const float *top_p /* [rows] or null: off */,
+                   const float *min_p /* [rows] or null: off */, int32_t *out_idx /* [rows] */, void *workspace, size_t workspace_bytes,
+                   mm_stream_t stream);
+
+/*
  * Shared-prefix decode over the paged KV cache (detect the two entries by their symbols; mm_version stays 660): mm_paged_decode for a
  * batch in which groups of sequences hold a leading run of pages in common (n samples of one prompt, beams, a system prompt;
  * PagedKVCache.fork).  The result is the same function as mm_paged_decode -- every sequence attends all of its own tokens -- within the

@@ -26,6 +26,7 @@ EXPORTS = (
     "mm_paged_decode_shared_workspace_bytes", "mm_paged_decode_shared",
     "mm_paged_prefill_tree", "mm_kv_move_rows",
     "mm_argmax_rows_workspace_bytes", "mm_argmax_rows", "mm_verify_greedy",
+    "mm_sample_rows_workspace_bytes", "mm_sample_rows",
     "mm_moe_route", "mm_moe_plan", "mm_moe_gather", "mm_moe_combine",
     "mm_moe_sf_bytes", "mm_moe_quantize", "mm_moe_activate_quantize", "mm_moe_matmul_supported", "mm_moe_matmul",
     "mm_moe_gate_up_activate_supported", "mm_moe_gate_up_activate_describe", "mm_moe_gate_up_activate",
@@ -193,6 +194,11 @@ def load():
         lib.mm_argmax_rows.argtypes = [vp, i, i, ctypes.c_longlong, vp, vp, sz, vp]
         lib.mm_verify_greedy.restype = i
         lib.mm_verify_greedy.argtypes = [vp] * 5 + [i, vp, vp, i, i, vp, vp, vp, vp]
+    if hasattr(lib, "mm_sample_rows"):
+        lib.mm_sample_rows_workspace_bytes.restype = sz
+        lib.mm_sample_rows_workspace_bytes.argtypes = [i, i]
+        lib.mm_sample_rows.restype = i
+        lib.mm_sample_rows.argtypes = [vp, i, i, ctypes.c_longlong] + [vp] * 7 + [sz, vp]
     lib.mm_moe_route.restype = i
     lib.mm_moe_route.argtypes = [vp, i, i, i, vp, vp, vp]
     lib.mm_moe_plan.restype = i

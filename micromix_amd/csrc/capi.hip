@@ -722,6 +722,25 @@ int mm_verify_greedy(const int32_t *target_tok, const int32_t *draft_tok, const 
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_verify_greedy");
 }
 
+// ---- sampling (sample.hip)
+size_t mm_sample_rows_workspace_bytes(int rows, int vocab) {
+    if (rows <= 0 || vocab < 1 || vocab > MM_ARGMAX_MAX_VOCAB || rows > MM_ARGMAX_MAX_ROWS) return 0;
+    return mm::sample_workspace_bytes(rows, vocab);
+}
+
+int mm_sample_rows(const void *logits_bf16, int rows, int vocab, long long ld, const float *u, const float *temperature, const int32_t *top_k,
+                   const float *top_p, const float *min_p, int32_t *out_idx, void *workspace, size_t workspace_bytes, mm_stream_t stream) {
+    if (rows < 0 || vocab < 1 || ld < vocab) return MM_ERR_BAD_ARG;
+    if (vocab > MM_ARGMAX_MAX_VOCAB || rows > MM_ARGMAX_MAX_ROWS) return MM_ERR_UNSUPPORTED;
+    if (rows == 0) return MM_OK;
+    if (!logits_bf16 || !u || !out_idx || ((uintptr_t)logits_bf16 & 1)) return MM_ERR_BAD_ARG;
+    if ((((uintptr_t)u | (uintptr_t)temperature | (uintptr_t)top_k | (uintptr_t)top_p | (uintptr_t)min_p | (uintptr_t)out_idx) & 3)) return MM_ERR_BAD_ARG;
+    const size_t need = mm::sample_workspace_bytes(rows, vocab);
+    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7)) return MM_ERR_BAD_ARG;
+    hipError_t e = mm::launch_sample_rows(logits_bf16, rows, vocab, ld, u, temperature, top_k, top_p, min_p, out_idx, workspace, (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_sample_rows");
+}
+
 // the un-windowed entry points are the windowed ones at window = 0
 size_t mm_paged_decode_window_workspace_bytes(int batch, int num_qo_heads, int num_kv_heads, int max_seq_len, int window) {
     if (batch <= 0 || num_kv_heads <= 0 || num_qo_heads <= 0 || max_seq_len < 0 || window < 0 || num_qo_heads % num_kv_heads) return 0;

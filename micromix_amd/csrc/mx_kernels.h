@@ -292,11 +292,17 @@ hipError_t launch_kv_move_rows(const PagedKV &kv, const int *move_indptr, const 
                                hipStream_t stream);
 // greedy verification of drafts (verify.hip): the argmax of bf16 rows (ws: argmax_workspace_bytes, 0 when a row is one part), and the walk
 // that picks each sequence's accepted path and writes the move table launch_kv_move_rows takes with move_indptr = qo_indptr
+int argmax_parts(int vocab);                              // workgroups a row is divided among: ceil(vocab / MM_ARGMAX_CHUNK)
 size_t argmax_workspace_bytes(int rows, int vocab);
 hipError_t launch_argmax_rows(const void *logits, int rows, int vocab, long long ld, int *out, void *ws, hipStream_t stream);
 hipError_t launch_verify_greedy(const int *target_tok, const int *draft_tok, const int *root_tok, const void *tree_mask, const int *qo_indptr,
                                 int T, const int *kv_indptr, const int *last_page_len, int P, int B, int *result, int *move_src,
                                 int *move_dst, hipStream_t stream);
+// sampling over bf16 rows (sample.hip): temperature, top-k, top-p, min-p, each a device array of `rows` entries or null; ws:
+// sample_workspace_bytes, uninitialised
+size_t sample_workspace_bytes(int rows, int vocab);
+hipError_t launch_sample_rows(const void *logits, int rows, int vocab, long long ld, const float *u, const float *temperature,
+                              const int *top_k, const float *top_p, const float *min_p, int *out, void *ws, hipStream_t stream);
 // sparse MoE block around the grouped GEMMs (moe.hip): n = T * top_k pairs, H a multiple of 8, rows 16-byte aligned
 hipError_t launch_moe_route(const void *logits, int T, int E, int top_k, int *ids, void *w, hipStream_t stream);
 hipError_t launch_moe_plan(const int *ids, int n, int E, int top_k, int *offsets, int *sorted_token, int *slot_of, hipStream_t stream);

@@ -5,13 +5,15 @@
 // -0 == +0 at 0x7F80, the positive ones up to +inf 0xFF00, and every NaN, of either sign, 0xFF01 -- and the answer is the lowest index
 // among the largest keys.  That is a total order on (key, index), so max is associative and commutative over it: the answer cannot depend
 // on how a row is divided among lanes, waves and workgroups, nor on who finishes first.  Nothing is accumulated into memory; every partial
-// a finishing workgroup reads was written by a workgroup of the same call, so the workspace needs no initialisation.
+// a finishing workgroup reads was written by a workgroup of the same call, so the workspace needs no initialisation.  The key and the
+// wave reductions live in mx_argmax_key.h, which sample.hip shares.
 //
 // One workgroup reduces MM_ARGMAX_CHUNK columns of one row: it peels the (up to 7) elements in front of the first 16-byte boundary and
 // behind the last, holds the 16-byte vectors between them in registers (4 per lane), finds the largest key without tracking an index
 // (packed 16-bit min / max / sub: 4 operations an element), and only then looks for the lowest column that holds that key -- in the few
 // lanes whose own maximum equals it.
 #include "../../include/micromix_hip.h"
+#include "mx_argmax_key.h"
 #include "mx_kernels.h"
 
 #include <hip/hip_runtime.h>
@@ -19,40 +21,11 @@
 
 namespace mm {
 
-typedef unsigned short us8 __attribute__((ext_vector_type(8)));
-typedef short ss8 __attribute__((ext_vector_type(8)));
-
 constexpr int ARG_THREADS = 256, ARG_VECS = MM_ARGMAX_CHUNK / 8 / ARG_THREADS;      // lanes per workgroup; 16-byte vectors per lane
 static_assert(ARG_VECS * ARG_THREADS * 8 == MM_ARGMAX_CHUNK && MM_ARGMAX_CHUNK <= 65536, "a part is a whole number of vectors per lane");
-constexpr unsigned KEY_NAN = 0xFF01u, BF16_NEG_INF = 0xFF80u;
-
-// the keys of 8 bf16 values: |x| with every NaN clamped to one value, negated for a set sign bit, shifted to unsigned; -NaN wraps
-// around to 0xFFFF and the last min brings it back to +NaN's key
-__device__ inline us8 argmax_keys(us8 u) {
-    const us8 mag = __builtin_elementwise_min(u & (us8)0x7FFF, (us8)0x7F81);
-    const us8 neg = (us8)((ss8)u >> 15);
-    const us8 s = (mag ^ neg) - neg;
-    return __builtin_elementwise_min(s + (us8)0x7F80, (us8)KEY_NAN);
-}
-
-__device__ inline unsigned argmax_key(unsigned u) {                                  // the same for one value
-    const unsigned mag = min(u & 0x7FFFu, 0x7F81u), neg = (u & 0x8000u) ? 0xFFFFu : 0u;
-    return min((((mag ^ neg) - neg) + 0x7F80u) & 0xFFFFu, KEY_NAN);
-}
 
 // a partial: the key above the bitwise complement of the column, so that the larger word is the larger key, then the lower column
 __device__ inline unsigned long long argmax_pack(unsigned key, unsigned col) { return ((unsigned long long)key << 32) | (0xFFFFFFFFu - col); }
-
-__device__ inline unsigned wave_max(unsigned x) {
-#pragma unroll
-    for (int off = 32; off; off >>= 1) x = max(x, (unsigned)__shfl_xor((int)x, off));
-    return x;
-}
-__device__ inline unsigned wave_min(unsigned x) {
-#pragma unroll
-    for (int off = 32; off; off >>= 1) x = min(x, (unsigned)__shfl_xor((int)x, off));
-    return x;
-}
 
 // grid (parts, rows).  One part: out[row] is written; several: partial[row * parts + part]
 __global__ __launch_bounds__(ARG_THREADS) void argmax_rows_kernel(const uint16_t *__restrict__ logits, int vocab, long long ld,

@@ -493,6 +493,8 @@ class PagedKVCache:
         tables, `append_indptr`, and the words of the last `tree_mask` call (chains when it was not called since the `extend`) --
         and then, on the same stream with nothing in between, `mixedgemm.kv_move_rows` from the move table it wrote.  target_tok,
         draft_tok: int32 [num_new_tokens], root_tok: int32 [batch], on the cache's device (what they mean: `mixedgemm.verify_greedy`).
+        target_tok comes from `mixedgemm.argmax_rows` (greedy decoding) or `mixedgemm.sample_rows` (temperature, top-k, top-p, min-p:
+        the kept path and the bonus token are then distributed as the target model's), either captured in front of this call.
         Returns the result tensor, int32 [batch, 66], the same tensor at every call; give it to `commit`.  Nothing is allocated after
         the first call with a token count, and nothing is read on the host: capturable, after every layer's `append`.  A graph
         captured with a tree replays with a tree (`tree_mask` writes the next one where the graph reads it), one captured with

@@ -31,7 +31,7 @@ from . import _lib
 __all__ = ["test_function", "matmul", "gate_up_activate", "interleave_gate_up", "reorder_quantize_x", "reorder_quantize_w", "reorder_quantize_w4", "activate_quantize_x",
            "downproj_quantize_w", "downproj_quantize_w4", "rmsnorm_quantize_x", "qlinear_decode", "qlinear_decode_supported", "matmul_grouped", "reorder_quantize_x_grouped",
            "kv_append", "rope_kv_append", "kv_copy_pages", "kv_move_rows", "paged_decode", "paged_decode_workspace_bytes", "paged_decode_shared", "paged_decode_shared_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes",
-           "argmax_rows", "argmax_rows_workspace_bytes", "verify_greedy",
+           "argmax_rows", "argmax_rows_workspace_bytes", "verify_greedy", "sample_rows", "sample_rows_workspace_bytes",
            "moe_route", "moe_plan", "moe_gather", "moe_combine",
            "moe_expert_table", "moe_sf_bytes", "moe_quantize", "moe_activate_quantize", "moe_matmul", "moe_matmul_supported",
            "permute_packed_rows", "moe_gate_up_table", "moe_gate_up_activate", "moe_gate_up_activate_supported"]
@@ -1110,12 +1110,101 @@ def argmax_rows(logits, *, out=None, workspace=None):
     return out
 
 
+def _sample_lib():
+    lib = _lib.load()
+    if not hasattr(lib, "mm_sample_rows"):
+        raise _lib.MicroMixLibraryError("libmicromix_hip.so has no mm_sample_rows: it was built before the sampler; rebuild it with "
+                                        "`python -m micromix_amd.build --force`")
+    return lib
+
+
+def sample_rows_workspace_bytes(rows, vocab):
+    """bytes of workspace `sample_rows` needs for bf16 logits [rows, vocab]: 3 KiB per part of MM_ARGMAX_CHUNK columns of every row
+    and 2 KiB per row"""
+    return int(_sample_lib().mm_sample_rows_workspace_bytes(int(rows), int(vocab)))
+
+
+def _row_param(value, name, dtype, rows, dev):
+    """a per-row parameter of `sample_rows`: None, a device tensor [rows] of `dtype`, or -- outside graph capture -- a Python number,
+    broadcast to one"""
+    if value is None:
+        return None
+    if isinstance(value, torch.Tensor):
+        if not _ok(value, dtype, dev.index) or value.dim() != 1 or value.numel() != rows:
+            _check_tensor(value, name, dtype, dev)
+            raise RuntimeError(f"{name} must be {dtype} [{rows}], one entry per row")
+        return value
+    if isinstance(value, bool) or not isinstance(value, (int, float)):
+        raise TypeError(f"{name} must be None, a number or a {dtype} device tensor [{rows}], got {type(value).__name__}")
+    if dtype is torch.int32 and not isinstance(value, int):
+        raise TypeError(f"{name} must be an int or a torch.int32 device tensor [{rows}], got {type(value).__name__}")
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(f"{name}: a Python number would be uploaded during graph capture; pass a {dtype} device tensor [{rows}]")
+    if dtype is torch.int32:
+        value = min(max(value, -(1 << 31)), (1 << 31) - 1)
+    return torch.full((rows,), value, dtype=dtype, device=dev)
+
+
+def sample_rows(logits, u, *, temperature=None, top_k=None, top_p=None, min_p=None, out=None, workspace=None):
+    """One token per row, drawn under temperature, top-k, top-p and min-p: logits bf16 [rows, vocab] on the device as `argmax_rows`
+    takes them (any row stride >= vocab, any 2-byte-aligned offset), u fp32 [rows] uniform in [0, 1) -- `torch.rand`, which captures;
+    the library draws no random numbers.  Returns int32 [rows] (`out` when given), ready for `verify_greedy` / `verify_launch` as
+    target_tok: the accepted path and the bonus token are then distributed as the target model's.
+
+    temperature, top_p, min_p: fp32 [rows], top_k: int32 [rows], device tensors read by the kernels only, so one captured graph serves
+    any mix of requests rewritten in place; None: temperature 1, that filter off; a Python number is broadcast to a tensor (outside
+    capture only).  Per row: temperature <= 0 or NaN, or a row whose maximum is NaN or infinite, gives exactly `argmax_rows`' answer.
+    Otherwise w_i = exp((l_i - max) / T); tokens of equal logit form a class and every filter keeps whole classes in descending
+    order: top_k the shortest prefix with >= k tokens (1 <= k < vocab, else off), top_p the shortest prefix with mass >= p times
+    top-k's (p < 1; p <= 0 keeps the top class), min_p the classes with w >= q (0 < q <= 1); the kept set is the shortest of the
+    three; the answer is the first kept index whose cumulative kept mass exceeds u * Z (include/micromix_hip.h, mm_sample_rows).  The
+    result is a function of the inputs alone: the same bits on every run.  vocab <= 2^20, rows <= 65535.  workspace: a contiguous
+    device tensor of `sample_rows_workspace_bytes(rows, vocab)` bytes, uninitialised, allocated when not given (under graph capture
+    pass one).  Runs on the current stream, capture-safe."""
+    lib = _sample_lib()
+    if not isinstance(logits, torch.Tensor):
+        raise TypeError("logits must be a torch.Tensor")
+    if logits.dtype is not torch.bfloat16:
+        raise TypeError(f"logits must be torch.bfloat16, got {logits.dtype}")
+    if not logits.is_cuda:
+        raise RuntimeError("logits must be a device tensor (HIP); the MicroMix ops have no CPU path")
+    if logits.dim() != 2 or logits.size(1) < 1:
+        raise RuntimeError("logits must be [rows, vocab] with vocab >= 1")
+    rows, vocab = logits.shape
+    if vocab > 1 and logits.stride(1) != 1:
+        raise RuntimeError("logits must have unit stride along the vocabulary (the rows may be any distance >= vocab apart)")
+    ld = logits.stride(0) if rows > 1 else vocab
+    if ld < vocab:
+        raise RuntimeError(f"logits rows overlap: row stride {ld} < vocab {vocab}")
+    dev = logits.device
+    if u is None or not isinstance(u, torch.Tensor):
+        raise TypeError(f"u must be a torch.float32 device tensor [{rows}] (torch.rand), got {type(u).__name__}")
+    u = _row_param(u, "u", torch.float32, rows, dev)
+    temperature = _row_param(temperature, "temperature", torch.float32, rows, dev)
+    top_k = _row_param(top_k, "top_k", torch.int32, rows, dev)
+    top_p = _row_param(top_p, "top_p", torch.float32, rows, dev)
+    min_p = _row_param(min_p, "min_p", torch.float32, rows, dev)
+    if out is None:
+        out = torch.empty((rows,), dtype=torch.int32, device=dev)
+    elif not _ok(out, torch.int32, dev.index) or out.dim() != 1 or out.numel() != rows:
+        _check_tensor(out, "out", torch.int32, dev)
+        raise RuntimeError(f"out must be int32 [{rows}]")
+    workspace, ws_args = _kv_workspace(workspace, sample_rows_workspace_bytes(rows, vocab), dev)
+    opt = lambda t: _ptr(t) if t is not None else None
+    with _on_device(dev.index):
+        st = lib.mm_sample_rows(_ptr(logits), rows, vocab, ld, _ptr(u), opt(temperature), opt(top_k), opt(top_p), opt(min_p), _ptr(out),
+                                *ws_args, _stream_ptr(dev))
+    if st:
+        _lib.check(st, "sample_rows")
+    return out
+
+
 def verify_greedy(target_tok, draft_tok, root_tok, qo_indptr, kv_indptr, last_page_len, page_size, *, tree_mask=None, result=None,
                   move_src=None, move_dst=None):
     """Greedy (exact-match) verification of tree or chain drafts, one wave per sequence; returns (result, move_src, move_dst).
 
     Sequence b has the n = qo_indptr[b + 1] - qo_indptr[b] draft nodes of rows qo_indptr[b] .. : draft_tok[t] is a node's token,
-    target_tok[t] the token the target model picks after it (`argmax_rows` of its logits, or any sampler's choice), root_tok[b] the token
+    target_tok[t] the token the target model picks after it (`argmax_rows` or `sample_rows` of its logits), root_tok[b] the token
     picked after the last committed one.  tree_mask: the int64 words of `paged_prefill(tree_mask=)` -- a node's parent is the highest set
     bit below its own -- or None for chains.  Starting from root_tok[b], the walk takes the lowest-numbered child of the node just taken
     whose token is the one wanted, until there is none.  result int32 [B, 66]: [0] the path's length k, [1] the bonus token (the
