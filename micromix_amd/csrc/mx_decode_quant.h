@@ -6,6 +6,7 @@
 #include "mx_group_convert.h"
 #include "mx_direct_convert.h"
 #include "mx_rms_convert.h"
+#include "mx_decode_quant_sizes.h"   // dq::operand_bytes, rms_bytes, early_fits: plain C++, shared with the host-side plans
 
 #define MM_DQ_SCHED_BARRIER() do { MM_DEVICE_ONLY(__builtin_amdgcn_sched_barrier(0);) } while (0)
 
@@ -43,17 +44,7 @@ struct LdsMap {
     uint8_t *opN, *opS, *opO, *scales;
     int pN, pS, pO, Gt, gN, gS;
 };
-__host__ __device__ inline size_t operand_bytes(int M, const int K[3]) {   // quantized rows + their scale bytes
-    const size_t Kt = (size_t)K[0] + K[1] + K[2];
-    return (size_t)M * (K[0] / 2 + K[1] / 4 * 3 + K[2] + Kt / 32);
-}
-// LDS behind the (16-byte rounded) operands when the norm runs inside the launch: [K bf16 norm weights | M x P partial sums | M rvar]
-__host__ __device__ inline int rms_pow2(int T) { int P = 64; while (P < T) P <<= 1; return P; }
-__host__ __device__ inline size_t rms_bytes(int M, const int K[3]) {
-    const size_t Kt = (size_t)K[0] + K[1] + K[2];
-    return Kt * 2 + (size_t)M * rms_pow2((int)(Kt >> 5)) * 4 + 64;
-}
-constexpr int RMS_MAX_K = 8192;      // the wave-local halving tree covers P <= 256 partial sums
+// (operand_bytes, rms_pow2, rms_bytes, RMS_MAX_K and early_fits -- the sizes the launchers plan with -- are in mx_decode_quant_sizes.h)
 
 // one group with the norm: gather x and w (same byte offsets into the staged row and the staged weight vector), v = bf16((x w) rvar),
 // block exponent, the reference's integer rounding, conversion into LDS; returns the scale byte (rmsnorm_quantize.hip: rms_group)
@@ -407,7 +398,6 @@ __device__ __forceinline__ void wait_vmcnt_range(int n) {
     }
 }
 __device__ __forceinline__ void wait_vmcnt(int n) { wait_vmcnt_range<0, 63>(n < 0 ? 0 : (n > 63 ? 63 : n)); }
-__host__ __device__ inline bool early_fits(int M, int Kt, int NT, int npass) { return 2 * (size_t)M * (size_t)(Kt >> 5) <= (size_t)NT * npass; }
 template <int NT, bool RMS, int NPASS, bool ADD = false, class Request, class Landed>
 __device__ __forceinline__ LdsMap quantize_rows_early(const QuantIn &a, uint8_t *smem, Request request, Landed landed) {
     const int Kt = a.K[0] + a.K[1] + a.K[2], Gt = Kt >> 5;

@@ -43,6 +43,7 @@
 #include "mx_buffer_ops.h"   // make_rsrc, lds_address, dma16: the descriptor and the ring's buffer_load_dwordx4 ... lds
 #include "mx_decode_quant.h"
 #include "mx_kernels.h"
+#include "mx_stream_plan.h"   // every size host and kernel share, the configurations that exist and the whole host-side plan (no HIP in it)
 
 namespace mm {
 namespace stream {
@@ -56,9 +57,6 @@ namespace stream {
 #define MM_STREAM_ACCZERO_EARLY 0
 #endif
 
-
-// launches without the quantization that take their scales from scale images (see stream_body): one token tile, and two with fp4 weights
-__host__ __device__ constexpr bool scale_images_for(int T16, bool W4) { return T16 == 1 || (T16 == 2 && W4); }
 
 // The ring's tiles go global -> LDS by dma16 (mx_buffer_ops.h).  (The same tiles through registers -- buffer_load_dwordx4 into a
 // register ring, ds_write_b128 in lane order when a slab is consumed -- measured the same times at 118 instead of 53 VGPRs:
@@ -133,7 +131,7 @@ __device__ __forceinline__ void static_for(Fn &&fn) {
 template <int F, int T16, bool W4, bool QUANT = false>
 struct Ring {
     static constexpr int WP = W4 ? 1 : 2;
-    static constexpr int W_BYTES = F * WP * 1024, X_BYTES = QUANT ? 0 : T16 * 2048, SLOT = W_BYTES + X_BYTES;
+    static constexpr int W_BYTES = ring_weight_bytes(F, W4), SLOT = ring_slot_bytes(F, T16, W4, QUANT);      // (mx_stream_plan.h)
     // vector-memory instructions of a slab, at least: the second piece of an activation tile is requested only where it holds rows the
     // launch has (fp4 tiles are one piece; M <= 8: rows 0 .. 7 sit in the first piece of every format).  The counted waits use this
     // minimum -- with longer slabs behind it a wait lets at most one instruction fewer stay in flight, never one too many.
@@ -157,22 +155,12 @@ __device__ unsigned long long *g_stream_clock;
 // its first batch of rows is staged it requests its first D slabs of weights, and the activation fragments and scales of a slab come
 // from that LDS copy (rows in the reference's packed layout, as in qlinear_decode.hip).  `qbytes` = the quantization's LDS range in
 // front of the rings.
-// QUANT kernels: the scale image.  A slab's 512-byte scale atom carries the scales of 128 weight rows; a workgroup wants 16 F of them, and
+// QUANT kernels: the scale image (scale_image_bytes, mx_stream_plan.h).  A slab's 512-byte scale atom carries the scales of 128 weight rows; a workgroup wants 16 F of them, and
 // a launch of these kernels is the sum of its vector-memory instructions (30-45 cycles each on a CU, whatever they fetch): with one atom
 // load per slab the scales cost as much as the fp4 weights themselves (down_proj at M = 1, tools/stream_clock.py: loop 5.2 us, without the
 // scale loads 2.8; the whole launch 11.0 -> 8.6).  So a wave gathers the scale dwords of ALL of its slabs in front of everything else --
 // one dword per lane = (slab, weight row), 64 / (16 F) slabs per instruction, global -> LDS directly -- into a private image
 // [instruction k][lane] of dwords, and a step reads its scale bytes from there.
-__host__ __device__ constexpr int scale_image_wave_bytes(int F, int NW, int T) {      // T = 128-deep slabs of the launch
-    const int spi = 4 / F, per_wave = (T + NW - 1) / NW;
-    return (per_wave + spi - 1) / spi * 256;
-}
-__host__ __device__ constexpr int scale_image_bytes(int F, int NW, int T) { return NW * scale_image_wave_bytes(F, NW, T); }
-// both images of a launch without the quantization (weights' rows 16 F, activations' 16 T16): one token tile only, see stream_body
-__host__ __device__ constexpr int scale_images_bytes(int F, int T16, int NW, int T, bool W4) {
-    return scale_images_for(T16, W4) ? scale_image_bytes(F, NW, T) + scale_image_bytes(T16, NW, T) : 0;
-}
-constexpr int STREAM_LDS_MAX = 160 * 1024;      // (the 64-token configuration on 16 features uses all of a CU's LDS)
 // one global_load_lds_dword: lane l's dword at `p` -> LDS byte lds + 4 l (M0 = lds; counted by vmcnt like the ring's DMA)
 // (M0 is saved and restored by the caller, once around its loop: m0_save / m0_restore)
 __device__ __forceinline__ void dma4(const uint8_t *p, unsigned lds) {
@@ -185,8 +173,7 @@ __device__ __forceinline__ unsigned m0_save() {
 }
 __device__ __forceinline__ void m0_restore(unsigned keep) { MM_DEVICE_ONLY(asm volatile("s_mov_b32 m0, %0" : : "s"(keep) : "memory");) }
 
-// slots per thread of dq::quantize_rows_early (see there): 2 on the four-wave kernels, whose register count costs no resident workgroup
-template <int NW> constexpr int EARLY_NPASS = NW <= 4 ? 2 : 1;
+template <int NW> constexpr int EARLY_NPASS = early_npass(NW);      // slots per thread of dq::quantize_rows_early (mx_stream_plan.h)
 // ACT (round 6; F = 4, one token tile, fp4 weights): the fused gate | up weight of mm_gate_up_activate -- 128 gate rows alternating with the
 // 128 up rows of the same indices -- with the activation INSIDE the launch.  Workgroup b takes the 32 gate rows 256 (b / 4) + 32 (b % 4) ..
 // and the 32 up rows 128 further on (its four 16-row tiles: gate, gate, up, up), i.e. both halves of ONE 32-column group of the
@@ -795,48 +782,12 @@ __device__ __forceinline__ void stream_body(const GemmArgs &a, const dq::QuantIn
 template <int F, int T16, int D, int NW, bool W4>
 __global__ void __launch_bounds__(64 * NW) mx_gemm_stream_kernel(GemmArgs a) { stream_body<F, T16, D, NW, W4>(a); }
 
-template <int F, int T16, int D, int NW, bool W4>
-static hipError_t launch_one(const GemmArgs &a, hipStream_t stream) {
-    const int present = (a.K[0] ? 1 : 0) + (a.K[1] ? 1 : 0) + (a.K[2] ? 1 : 0);
-    // [rings | scale images] while the slabs stream, then the reduction image over both
-    const int red_bytes = NW * (F * T16 >= 8 ? 1 : present) * F * T16 * 4 * 64 * (int)sizeof(float);
-    const int stage_bytes = NW * D * Ring<F, T16, W4>::SLOT + scale_images_bytes(F, T16, NW, (a.K[0] + a.K[1] + a.K[2]) >> 7, W4);
-    const int lds = red_bytes > stage_bytes ? red_bytes : stage_bytes;
-    if (lds > STREAM_LDS_MAX) return hipErrorInvalidValue;      // (mx_gemm_stream_supported keeps callers away from this)
-    static DynamicLdsOnce once;
-    if (lds > 65536) {
-        hipError_t e = once.ensure(reinterpret_cast<const void *>(mx_gemm_stream_kernel<F, T16, D, NW, W4>), STREAM_LDS_MAX);
-        if (e != hipSuccess) return e;
-    }
-    const int blocks = (a.N + 16 * F - 1) / (16 * F);
-    MM_LAUNCH((mx_gemm_stream_kernel<F, T16, D, NW, W4>), dim3(blocks), dim3(64 * NW), lds, stream, a);
-    return hipGetLastError();
-}
-
 // Grouped launch (MoE experts): blockIdx.y picks one of up to MM_MAX_GROUPS problems that share N, the K split and the weight mode
 // (as mx_gemm_skinny_grouped_kernel); T16 covers the largest group, a group with M = 0 returns at once.
 template <int F, int T16, int D, int NW, bool W4>
 __global__ void __launch_bounds__(64 * NW) mx_gemm_stream_grouped_kernel(GroupedGemmArgs ga) {
     const GemmArgs &a = ga.g[blockIdx.y];
     if (a.M > 0) stream_body<F, T16, D, NW, W4>(a);
-}
-
-template <int F, int T16, int D, int NW, bool W4>
-static hipError_t launch_grouped_one(const GroupedGemmArgs &ga, hipStream_t stream) {
-    const GemmArgs &a = ga.g[0];
-    const int present = (a.K[0] ? 1 : 0) + (a.K[1] ? 1 : 0) + (a.K[2] ? 1 : 0);
-    const int red_bytes = NW * (F * T16 >= 8 ? 1 : present) * F * T16 * 4 * 64 * (int)sizeof(float);
-    const int stage_bytes = NW * D * Ring<F, T16, W4>::SLOT + scale_images_bytes(F, T16, NW, (a.K[0] + a.K[1] + a.K[2]) >> 7, W4);
-    const int lds = red_bytes > stage_bytes ? red_bytes : stage_bytes;
-    if (lds > STREAM_LDS_MAX) return hipErrorInvalidValue;      // (mx_gemm_stream_grouped_supported keeps callers away from this)
-    static DynamicLdsOnce once;
-    if (lds > 65536) {
-        hipError_t e = once.ensure(reinterpret_cast<const void *>(mx_gemm_stream_grouped_kernel<F, T16, D, NW, W4>), STREAM_LDS_MAX);
-        if (e != hipSuccess) return e;
-    }
-    const int blocks = (a.N + 16 * F - 1) / (16 * F);
-    hipLaunchKernelGGL((mx_gemm_stream_grouped_kernel<F, T16, D, NW, W4>), dim3(blocks, ga.ngroups), dim3(64 * NW), lds, stream, ga);
-    return hipGetLastError();
 }
 
 // Device-sized grouped launch (mm_moe_matmul): blockIdx.y is the expert; its row count and the bases of its rows in the packed buffers
@@ -849,23 +800,6 @@ __global__ void __launch_bounds__(64 * NW) mx_gemm_stream_moe_kernel(GemmArgs a,
     if (lo < 0 || M < 1 || M > 16 * T16 || M > mg.max_rows || M > mg.n - lo) return;
     moe_group_args(a, mg, e, lo, M);
     stream_body<F, T16, D, NW, W4>(a);
-}
-
-template <int F, int T16, int D, int NW, bool W4>
-static hipError_t launch_moe_one(const GemmArgs &a, const MoeGroups &mg, hipStream_t stream) {
-    const int present = (a.K[0] ? 1 : 0) + (a.K[1] ? 1 : 0) + (a.K[2] ? 1 : 0);
-    const int red_bytes = NW * (F * T16 >= 8 ? 1 : present) * F * T16 * 4 * 64 * (int)sizeof(float);
-    const int stage_bytes = NW * D * Ring<F, T16, W4>::SLOT + scale_images_bytes(F, T16, NW, (a.K[0] + a.K[1] + a.K[2]) >> 7, W4);
-    const int lds = red_bytes > stage_bytes ? red_bytes : stage_bytes;
-    if (lds > STREAM_LDS_MAX) return hipErrorInvalidValue;      // (mx_gemm_stream_moe_supported keeps callers away from this)
-    static DynamicLdsOnce once;
-    if (lds > 65536) {
-        hipError_t e = once.ensure(reinterpret_cast<const void *>(mx_gemm_stream_moe_kernel<F, T16, D, NW, W4>), STREAM_LDS_MAX);
-        if (e != hipSuccess) return e;
-    }
-    const int blocks = (a.N + 16 * F - 1) / (16 * F);
-    hipLaunchKernelGGL((mx_gemm_stream_moe_kernel<F, T16, D, NW, W4>), dim3(blocks, mg.E), dim3(64 * NW), lds, stream, a, mg);
-    return hipGetLastError();
 }
 
 // mm_qlinear_decode on the streaming kernel: the workgroup quantizes the M <= 8 rows itself (QUANT)
@@ -900,61 +834,153 @@ __global__ void __launch_bounds__(256) mx_qlinear_stream_act_add_kernel(GemmArgs
 }
 template <int T16>
 __global__ void __launch_bounds__(256) mx_gemm_stream_act_kernel(GemmArgs a) { stream_body<4, T16, 2, 4, true, false, false, true>(a); }
-constexpr int ACT_GROUP_BYTES = 16 * 32 * 4;       // the 32 values of a group for up to 16 tokens, behind the reduction image
 
+// ---- the host side: the plan is mx_stream_plan.h's; what follows reads the environment, picks the instantiation and launches ----
+static_assert(MAX_GROUPS == MM_MAX_GROUPS, "the plan's group bound is GroupedGemmArgs' (mx_stream_plan.h)");
+
+#ifndef MM_STREAM_SWEEP      // kernel-developer build: every (F, D, NW) combination, picked by MICROMIX_STREAM_CFG="F,D,NW"
+#define MM_STREAM_SWEEP 0
+#endif
+
+// the developer overrides of the plan, read from the environment once per process
+static const StreamOverrides &stream_overrides() {
+    static const StreamOverrides ov = [] {
+        auto env_int = [](const char *name, int dflt) {
+            const char *v = getenv(name);
+            return v ? atoi(v) : dflt;
+        };
+        StreamOverrides o;
+        o.stream = env_int("MICROMIX_STREAM", o.stream);
+        o.grouped = env_int("MICROMIX_STREAM_GROUPED", o.grouped);
+        o.grouped_max_m = env_int("MICROMIX_STREAM_GROUPED_MAX_M", o.grouped_max_m);
+        o.decode_stream = env_int("MICROMIX_DECODE_STREAM", o.decode_stream);
+        o.decode_early = env_int("MICROMIX_DECODE_EARLY", o.decode_early);
+        o.decode_f4 = env_int("MICROMIX_DECODE_F4", o.decode_f4);
+        o.decode_depth = env_int("MICROMIX_DECODE_DEPTH", o.decode_depth);
+        o.gate_up_act_stream = env_int("MICROMIX_GATE_UP_ACT_STREAM", o.gate_up_act_stream);
+#if MM_STREAM_SWEEP
+        int f = 0, d = 0, nw = 0;
+        if (const char *v = getenv("MICROMIX_STREAM_CFG"); v && sscanf(v, "%d,%d,%d", &f, &d, &nw) == 3) o.cfg_f = f ? f : -1, o.cfg_d = d, o.cfg_nw = nw;
+#endif
+        return o;
+    }();
+    return ov;
+}
+
+// The one launch of a streaming kernel: `args` are the kernel's arguments.  The kernel's dynamic-LDS limit is raised once per device
+// before the first launch that needs more than 64 KB; that state belongs to the kernel -- a static of this instantiation (compare
+// launch_tile, mx_gemm_prelude.h).  DIAG: the launch attaches the diagnostics events (mm_diag_set_kernel_events) -- the plain, the
+// quantizing and the ACT launches do, the grouped and device-sized ones do not.
+template <auto Kern, bool DIAG, class... Args>
+static hipError_t launch_stream(const StreamLaunch &l, hipStream_t stream, const Args &...args) {
+    static DynamicLdsOnce once;
+    if (l.raise_to) {
+        if (hipError_t e = once.ensure(reinterpret_cast<const void *>(Kern), l.raise_to); e != hipSuccess) return e;
+    }
+    if constexpr (DIAG) MM_LAUNCH(Kern, dim3(l.grid_x, l.grid_y), dim3(l.threads), l.lds_bytes, stream, args...);
+    else hipLaunchKernelGGL(Kern, dim3(l.grid_x, l.grid_y), dim3(l.threads), l.lds_bytes, stream, args...);
+    return hipGetLastError();
+}
+
+// The one place that turns a runtime (configuration, weight mode) into a template instantiation: fn(index) of the matching row of the
+// kind's closed list (mx_stream_plan.h).  A configuration that is not in the list is an error, not a new kernel.
+template <StreamKind KIND, class Fn>
+static hipError_t for_cfg(const StreamCfg &c, bool w4, Fn &&fn) {
+    constexpr CfgList list = cfg_list(KIND);
+    constexpr size_t N = list.n;
+    hipError_t e = hipErrorInvalidValue;
+    // (the rows last to first: hipcc emits what a fold instantiates in reverse, so the kernels stand in the object in list order)
+    [&]<size_t... I>(std::index_sequence<I...>) {
+        (void)((list.rows[N - 1 - I].cfg == c && list.rows[N - 1 - I].w4 == w4 && ((e = fn(std::integral_constant<size_t, N - 1 - I>{})), true)) || ...);
+    }(std::make_index_sequence<N>{});
+    return e;
+}
+
+// a row of the plain / grouped / device-sized / ACT lists is that kind's kernel
+template <StreamKind KIND, int F, int T16, int D, int NW, bool W4, class... Args>
+static hipError_t launch_gemm_row(const StreamLaunch &l, hipStream_t stream, const Args &...args) {
+    constexpr auto kern = [] {
+        if constexpr (KIND == SK_GROUPED) return mx_gemm_stream_grouped_kernel<F, T16, D, NW, W4>;
+        else if constexpr (KIND == SK_MOE) return mx_gemm_stream_moe_kernel<F, T16, D, NW, W4>;
+        else if constexpr (KIND == SK_ACT) return mx_gemm_stream_act_kernel<T16>;
+        else return mx_gemm_stream_kernel<F, T16, D, NW, W4>;
+    }();
+    static_assert(KIND != SK_ACT || (F == 4 && D == 2 && NW == 4 && W4), "mx_gemm_stream_act_kernel");
+    return launch_stream<kern, KIND == SK_PLAIN || KIND == SK_ACT>(l, stream, args...);
+}
+template <StreamKind KIND, class... Args>
+static hipError_t launch_gemm(const GemmPlan &p, bool w4, hipStream_t stream, const Args &...args) {
+    if (!p.ok) return hipErrorInvalidValue;
+    return for_cfg<KIND>(p.cfg, w4, [&](auto i) {
+        constexpr CfgRow r = cfg_list(KIND).rows[decltype(i)::value];
+        return launch_gemm_row<KIND, r.cfg.F, r.cfg.T16, r.cfg.D, r.cfg.NW, r.w4>(p.launch, stream, args...);
+    });
+}
+
+// a row of the quantizing lists: the kernel without the norm, with it, or with the residual add in front of it, as `qi` asks
 template <int F, int D, int NW, bool W4, bool RMS = false, bool ACT = false, bool ADD = false>
 static hipError_t launch_quant(const GemmArgs &a, dq::QuantIn qi, hipStream_t stream) {
     static_assert(!ACT || (F == 4 && D == 2 && NW == 4 && W4), "mx_qlinear_stream_act_kernel");
-    if constexpr (ACT && !RMS) {
-        if (qi.norm_w != nullptr) return launch_quant<F, D, NW, W4, true, true>(a, qi, stream);
-    }
-    if constexpr (!ACT && !RMS && ((F == 4 && D == 2 && NW == 4) || (F == 2 && D == 2 && NW == 8) || (F == 1 && NW == 8 && (D == 3 || D == 4)))) {
-        if (qi.norm_w != nullptr) return launch_quant<F, D, NW, W4, true>(a, qi, stream);      // (the configurations the default dispatch uses)
+    if constexpr (!RMS && has_norm_kernel(StreamCfg{F, 1, D, NW})) {      // (the configurations the default selection uses)
+        if (qi.norm_w != nullptr) return launch_quant<F, D, NW, W4, true, ACT>(a, qi, stream);
     }
     if constexpr (RMS && !ADD) {      // (every norm variant has its variant with the residual add)
         if (qi.R != nullptr) return launch_quant<F, D, NW, W4, true, ACT, true>(a, qi, stream);
     }
-    if (!ADD && qi.R != nullptr) return hipErrorInvalidValue;
-    if (!RMS && qi.norm_w != nullptr) return hipErrorInvalidValue;       // (a kernel-developer override picked a configuration without a norm variant)
-    const int present = (a.K[0] ? 1 : 0) + (a.K[1] ? 1 : 0) + (a.K[2] ? 1 : 0);
-    const size_t Kt = (size_t)a.K[0] + a.K[1] + a.K[2];
-    // [rings | scale image] while the slabs stream, then the reduction image over both
-    const size_t red_bytes = (size_t)NW * present * F * 4 * 64 * sizeof(float);      // (ACT: the group buffer lies in the staged rows' range)
-    const size_t ring_bytes = (size_t)NW * D * Ring<F, 1, W4, true>::SLOT + scale_image_bytes(F, NW, (int)(Kt >> 7));
-    const size_t tail = red_bytes > ring_bytes ? red_bytes : ring_bytes;
-    const size_t ops = ((dq::operand_bytes(a.M, a.K) + 15) & ~(size_t)15) + (qi.norm_w != nullptr ? ((dq::rms_bytes(a.M, a.K) + 15) & ~(size_t)15) : 0);
-    // staged bf16 rows: all M if two workgroups still fit a CU's 160 KB, else as many as one workgroup can hold (at least one)
-    constexpr size_t LDS_CU = 160 * 1024, LDS_WG = 156 * 1024;
-    size_t rows = qi.mode == 1 ? 0 : a.M;       // (mode 1 quantizes straight from global memory: nothing is staged)
-    if (qi.mode != 1 && 2 * (ops + tail + rows * Kt * 2) > LDS_CU) {
-        const size_t two = LDS_CU / 2 > ops + tail ? (LDS_CU / 2 - ops - tail) / (Kt * 2) : 0;
-        const size_t one = LDS_WG > ops + tail ? (LDS_WG - ops - tail) / (Kt * 2) : 0;
-        rows = two >= 1 ? two : one;
-        if (rows > (size_t)a.M) rows = a.M;
-    }
-    if (rows < 1 && qi.mode != 1) return hipErrorInvalidValue;
-    qi.stage_rows = (int)rows;
-    qi.early = (qi.mode != 1 && rows >= (size_t)a.M && dq::early_fits(a.M, (int)Kt, 64 * NW, EARLY_NPASS<NW>)) ? 1 : 0;
-    if (qi.mode == 1) qi.early = (size_t)a.M * (Kt / 32) <= 64u * NW ? 1 : 0;      // activate_rows_early: one pass of the workgroup's threads
-    static const int early_on = getenv("MICROMIX_DECODE_EARLY") ? atoi(getenv("MICROMIX_DECODE_EARLY")) : 1;   // kernel-developer override
-    if (!early_on) qi.early = 0;
-    const size_t qbytes = rows * Kt * 2 + ops, lds = qbytes + tail;
-    if (lds > LDS_WG) return hipErrorInvalidValue;      // (every mode: the supported() predicates keep callers away from this)
-    static DynamicLdsOnce once;
-    auto kern = [] {
+    const QuantKind what = ACT ? QK_GATE_UP_ACT : (qi.mode == 1 ? QK_DOWN_ACTIVATE : QK_QLINEAR);
+    const QuantPlan p = plan_quant(what, StreamCfg{F, 1, D, NW}, W4, a.M, a.N, a.K, qi.norm_w != nullptr, qi.R != nullptr, stream_overrides());
+    if (!p.ok || p.rms != RMS || p.add != ADD) return hipErrorInvalidValue;      // (!RMS with a norm: a kernel-developer override picked a configuration without that variant)
+    qi.stage_rows = p.stage_rows;
+    qi.early = p.early;
+    constexpr auto kern = [] {
         if constexpr (ACT && ADD) return mx_qlinear_stream_act_add_kernel<true>;
         else if constexpr (ADD) return mx_qlinear_stream_add_kernel<F, D, NW, W4>;
         else if constexpr (ACT) return mx_qlinear_stream_act_kernel<RMS>;
         else if constexpr (RMS) return mx_qlinear_stream_rms_kernel<F, D, NW, W4>;
         else return mx_qlinear_stream_kernel<F, D, NW, W4>;
     }();
-    if (lds > 65536) {
-        hipError_t e = once.ensure(reinterpret_cast<const void *>(kern), (int)LDS_WG);
-        if (e != hipSuccess) return e;
+    return launch_stream<kern, true>(p.launch, stream, a, qi, p.qbytes);
+}
+template <StreamKind KIND>
+static hipError_t launch_quant_cfg(const StreamCfg &c, bool w4, const GemmArgs &a, const dq::QuantIn &qi, hipStream_t stream) {
+    return for_cfg<KIND>(c, w4, [&](auto i) {
+        constexpr CfgRow r = cfg_list(KIND).rows[decltype(i)::value];
+        return launch_quant<r.cfg.F, r.cfg.D, r.cfg.NW, r.w4, false, KIND == SK_QUANT_ACT>(a, qi, stream);
+    });
+}
+
+// the arguments of the quantizing launches: the rows to quantize (and the norm in front of that) ...
+static dq::QuantIn quant_in(const void *X, const int16_t *idx, int M, const int K[3], const NormArgs &norm, int mode = 0) {
+    dq::QuantIn qi = {};
+    qi.X = (const uint16_t *)X;
+    qi.idx = idx;
+    qi.M = M;
+    qi.mode = mode;
+    qi.norm_w = (const uint16_t *)norm.weight;
+    qi.eps = norm.eps;
+    qi.int_round = norm.int_round;
+    qi.R = (const uint16_t *)norm.res;
+    qi.S_out = (uint16_t *)norm.s_out;
+    for (int g = 0; g < 3; ++g) qi.K[g] = K[g];
+    return qi;
+}
+// ... and the GEMM behind it, whose activation operands the workgroups make themselves
+static GemmArgs decode_gemm_args(const uint8_t *const W[3], const uint8_t *const SFW[3], int M, int N, const int K[3], int round_per_segment,
+                                 const void *bias, void *D) {
+    GemmArgs a = {};
+    for (int g = 0; g < 3; ++g) {
+        a.W[g] = W[g];
+        a.SFW[g] = SFW[g];
+        a.K[g] = K[g];
     }
-    const int blocks = (a.N + 16 * F - 1) / (16 * F);
-    MM_LAUNCH(kern, dim3(blocks), dim3(64 * NW), lds, stream, a, qi, (int)qbytes);
-    return hipGetLastError();
+    a.M = M;
+    a.N = N;
+    a.sfx_row_tiles = 1;
+    a.sfw_row_tiles = (N + 127) / 128;
+    a.round_per_segment = round_per_segment;
+    a.bias = (const uint16_t *)bias;
+    a.D = (uint16_t *)D;
+    return a;
 }
 
 }  // namespace stream
@@ -965,293 +991,60 @@ extern "C" int mm_diag_set_stream_clock(void *buf) {
 }
 #endif
 
-// the grouped launch on the streaming kernel: every group M <= 64 (one to four token tiles); the workgroups of all groups count towards
-// filling the CUs
-// one token tile: the rings of the (F, D, NW) the dispatch may pick (at most 8 waves x 4 slots x (1 + 2) KB with fp4 weights, (2 + 2) KB
-// without) and both scale images (at most 8 waves, 16 rows per slab: the larger of the two geometries) must fit a workgroup's LDS
-// 16 features x two token tiles x 8 waves with fp4 weights: `depth` slots of 1 + 4 KB and both images
-static bool two_tile_fits(int depth, int T) {
-    return 8 * depth * 5 * 1024 + stream::scale_image_bytes(1, 8, T) + stream::scale_image_bytes(2, 8, T) <= stream::STREAM_LDS_MAX;
-}
-static bool stream_images_fit(int M, const int K[3], bool w4) {
-    if (M > 32 || (M > 16 && !w4)) return true;
-    const int T = (K[0] + K[1] + K[2]) >> 7;
-    if (M > 16) return two_tile_fits(2, T);      // (the 32-feature configuration: 4 waves x 2 slots x 6 KB + smaller images)
-    const int rings = 8 * (T <= 32 ? 4 : 3) * (w4 ? 3 : 4) * 1024;
-    return rings + 2 * stream::scale_image_bytes(1, 8, T) <= stream::STREAM_LDS_MAX;
-}
+// ---- the exported entry points (mx_kernels.h): the plan for the device that is current at the call ----
+using namespace stream;
+
+// the grouped launch: the workgroups of all groups count towards filling the CUs
 bool mx_gemm_stream_grouped_supported(int max_m, int ngroups, int N, const int K[3]) {
-    static const int on = getenv("MICROMIX_STREAM_GROUPED") ? atoi(getenv("MICROMIX_STREAM_GROUPED")) : 1;   // kernel-developer override
-    (void)N;
-    static const int max_tokens = getenv("MICROMIX_STREAM_GROUPED_MAX_M") ? atoi(getenv("MICROMIX_STREAM_GROUPED_MAX_M")) : 64;
-    return on && max_m >= 1 && max_m <= max_tokens && max_m <= 64 && ngroups >= 1 && ngroups <= MM_MAX_GROUPS && stream_images_fit(max_m, K, false) && stream_images_fit(max_m, K, true);      // (either weight mode)
+    return grouped_supported(max_m, ngroups, N, K, device_cus, stream_overrides());
 }
 hipError_t launch_mx_gemm_stream_grouped(const GroupedGemmArgs &ga, int max_m, bool w4, hipStream_t stream) {
-    using namespace stream;
-    const bool wide = (ga.g[0].N + 31) / 32 * ga.ngroups >= device_cus();
-#define MM_STREAM_G(F_, T_, D_, NW_)                                                 \
-    (w4 ? launch_grouped_one<F_, T_, D_, NW_, true>(ga, stream) : launch_grouped_one<F_, T_, D_, NW_, false>(ga, stream))
-    if (max_m <= 16) return wide ? MM_STREAM_G(2, 1, 2, 8) : MM_STREAM_G(1, 1, 3, 8);
-    if (max_m <= 32 && w4) {      // (as launch_mx_gemm_stream: scale images with two token tiles)
-        const int slabs = (ga.g[0].K[0] + ga.g[0].K[1] + ga.g[0].K[2]) >> 7;
-        if (wide) return launch_grouped_one<2, 2, 2, 4, true>(ga, stream);
-        return two_tile_fits(3, slabs) ? launch_grouped_one<1, 2, 3, 8, true>(ga, stream) : launch_grouped_one<1, 2, 2, 8, true>(ga, stream);
-    }
-    if (max_m <= 32) return wide ? MM_STREAM_G(2, 2, 3, 4) : MM_STREAM_G(1, 2, 3, 8);
-    if (max_m <= 48) return wide ? MM_STREAM_G(2, 3, 2, 4) : MM_STREAM_G(1, 3, 2, 8);
-    return wide ? MM_STREAM_G(2, 4, 2, 4) : MM_STREAM_G(1, 4, 2, 8);
-#undef MM_STREAM_G
+    const GemmArgs &a = ga.g[0];
+    return launch_gemm<SK_GROUPED>(plan_grouped(max_m, ga.ngroups, a.N, a.K, w4, device_cus(), stream_overrides()), w4, stream, ga);
 }
 
 // the device-sized grouped launch: the configurations of launch_mx_gemm_stream_grouped, chosen from host values only -- the tier from
-// max_rows, the groups that share the CUs counted as that launch counts them at its fullest, min(E, n, MM_MAX_GROUPS).  The host-sized
-// path takes both from the rows of each launch, so the two may run different configurations on the same rows.  F, T16 and D leave every
-// bit alone; NW does not once a launch has more than four slabs (K > 512): slab j is summed in wave j % NW and the waves in wave order.
-// An expert's rows therefore carry the bits mm_matmul_grouped gives them in a launch of the same NW (4 when `wide` and the tier is
-// above 16 rows, 8 otherwise), and the bits of every launch when K <= 512.
-// Supported where the host-sized path streams whatever its largest group of at most max_m rows is: every tier up to max_m's must fit
-// (a very long K fits the 64-row tier and not the 16-row one), so that no group is on the skinny kernel there and streamed here.
-bool mx_gemm_stream_moe_supported(int max_m, const int K[3]) {
-    max_m = max_m < 64 ? max_m : 64;
-    for (int tier = 16; tier < max_m; tier += 16)
-        if (!mx_gemm_stream_grouped_supported(tier, 1, 0, K)) return false;
-    return mx_gemm_stream_grouped_supported(max_m, 1, 0, K);
-}
+// max_rows, the groups that share the CUs counted as that launch counts them at its fullest (moe_rows, moe_groups).  The host-sized
+// path takes both from the rows of each launch, so the two may run different configurations on the same rows; an expert's rows carry
+// the bits mm_matmul_grouped gives them in a launch of the same NW, and the bits of every launch when K <= 512 (select_gemm).
+bool mx_gemm_stream_moe_supported(int max_m, const int K[3]) { return moe_supported(max_m, K, stream_overrides()); }
 hipError_t launch_mx_gemm_stream_moe(const GemmArgs &a, const MoeGroups &mg, bool w4, hipStream_t stream) {
-    using namespace stream;
-    const int max_m = mg.max_rows < 64 ? mg.max_rows : 64;
-    int groups = mg.E < mg.n ? mg.E : mg.n;
-    groups = groups < MM_MAX_GROUPS ? groups : MM_MAX_GROUPS;
-    const bool wide = (a.N + 31) / 32 * groups >= device_cus();
-#define MM_STREAM_G(F_, T_, D_, NW_)                                                 \
-    (w4 ? launch_moe_one<F_, T_, D_, NW_, true>(a, mg, stream) : launch_moe_one<F_, T_, D_, NW_, false>(a, mg, stream))
-    if (max_m <= 16) return wide ? MM_STREAM_G(2, 1, 2, 8) : MM_STREAM_G(1, 1, 3, 8);
-    if (max_m <= 32 && w4) {
-        const int slabs = (a.K[0] + a.K[1] + a.K[2]) >> 7;
-        if (wide) return launch_moe_one<2, 2, 2, 4, true>(a, mg, stream);
-        return two_tile_fits(3, slabs) ? launch_moe_one<1, 2, 3, 8, true>(a, mg, stream) : launch_moe_one<1, 2, 2, 8, true>(a, mg, stream);
-    }
-    if (max_m <= 32) return wide ? MM_STREAM_G(2, 2, 3, 4) : MM_STREAM_G(1, 2, 3, 8);
-    if (max_m <= 48) return wide ? MM_STREAM_G(2, 3, 2, 4) : MM_STREAM_G(1, 3, 2, 8);
-    return wide ? MM_STREAM_G(2, 4, 2, 4) : MM_STREAM_G(1, 4, 2, 8);
-#undef MM_STREAM_G
+    const GemmPlan p = plan_moe(mg.max_rows, mg.E, mg.n, a.N, a.K, w4, device_cus(), stream_overrides());
+    return launch_gemm<SK_MOE>(p, w4, stream, a, mg);
 }
 
-bool mx_gemm_stream_supported(int M, int N, const int K[3], bool w4) {
-    static const int on = getenv("MICROMIX_STREAM") ? atoi(getenv("MICROMIX_STREAM")) : 1;   // kernel-developer override
-    if (!on || M > 64) return false;
-    // few features, short K, a handful of tokens (q/k/v/o at M <= 8): the launch is all start-up, and the first kernel's is shorter
-    // (q/o at M = 1: 4.65 against 5.0-5.5 us; from M = 16 on the two meet)
-    if (M <= 8 && (N + 15) / 16 <= device_cus() && K[0] + K[1] + K[2] <= 8192) return false;
-    return stream_images_fit(M, K, w4);
-}
-
-// LDS that the ring / reduction tail of the quantizing launches may need beside the quantization's own range: the largest of the
-// instantiations launch_quant is called with -- matching-precision weights, NW * D * SLOT = 8 * 2 * 4096 = 4 * 2 * 8192 = 8 * 4 * 2048
-// = 64 KB (fp4 weights: 48 KB).  The supported() predicates budget this worst case so that a shape they accept always launches
-// (they budgeted 48 KB whatever the weight mode).
-constexpr size_t stream_tail_budget(bool w4) { return (w4 ? 48 : 64) * 1024; }
-// ... with the scale image (stream::scale_image_bytes) of the (F, NW) the dispatch below picks for N output features behind the rings
-// (NW * D * SLOT <= 32 KB with fp4 weights, 64 KB without): under the reduction image where that is the larger one
-static size_t quant_tail_budget(int N, size_t Kt, bool w4) {
-    const int cus = device_cus(), T = (int)(Kt >> 7);
-    const size_t simg = (N + 31) / 32 > 2 * cus ? stream::scale_image_bytes(4, 4, T)
-                                                : ((N + 31) / 32 >= cus ? stream::scale_image_bytes(2, 8, T) : stream::scale_image_bytes(1, 8, T));
-    const size_t rings = (w4 ? 32 : 64) * 1024 + simg;
-    return rings > stream_tail_budget(w4) ? rings : stream_tail_budget(w4);
-}
-
-// 1 if mm_qlinear_decode can run on the streaming kernel (the quantized rows, one staged row and the rings fit a workgroup's LDS)
-bool qlinear_stream_supported(int M, int N, const int K[3], bool rms, bool w4) {
-    static const int on = getenv("MICROMIX_DECODE_STREAM") ? atoi(getenv("MICROMIX_DECODE_STREAM")) : 1;   // kernel-developer override
-    // Measured against the first fused kernel (qlinear_decode.hip; tools/time_decode.py, profiles/r04_stream_ablation.txt section 8):
-    // it wins where N / 32 fills the CUs and one pass quantizes the rows (gate/up at M = 1 / 2 / 4: 12.5 / 11.8 / 14.3 -> 10.2 / 9.2 /
-    // 12.3 us) and loses on q/k/v/o (few workgroups: all start-up) and at M = 8 (two passes per workgroup: quantize + GEMM wins there).
-    const size_t Kt = (size_t)K[0] + K[1] + K[2];
-    const size_t norm = rms ? dq::rms_bytes(M, K) : 0;
-    if (rms && Kt > (size_t)dq::RMS_MAX_K) return false;
-    const size_t need = dq::operand_bytes(M, K) + norm + Kt * 2 + quant_tail_budget(N, Kt, w4) + 64;
-    if (on == 2 && M >= 1 && M <= 8) return need <= 156 * 1024;     // (A/B runs: every shape that fits)
-    if (!on || M < 1 || M > 4 || (N + 31) / 32 < device_cus()) return false;
-    return need <= 156 * 1024;
-}
-
+// mm_*qlinear_decode on the streaming kernel
+bool qlinear_stream_supported(int M, int N, const int K[3], bool rms, bool w4) { return qlinear_supported(M, N, K, rms, w4, device_cus(), stream_overrides()); }
 hipError_t launch_qlinear_stream(const void *X, const int16_t *idx, const uint8_t *const W[3], const uint8_t *const SFW[3], int M, int N,
                                  const int K[3], bool w4, int round_per_segment, const void *bias, void *D, hipStream_t stream,
                                  const NormArgs &norm) {
-    using namespace stream;
-    GemmArgs a = {};
-    dq::QuantIn qi = {};
-    qi.X = (const uint16_t *)X;
-    qi.idx = idx;
-    qi.M = M;
-    qi.norm_w = (const uint16_t *)norm.weight;
-    qi.eps = norm.eps;
-    qi.int_round = norm.int_round;
-    qi.R = (const uint16_t *)norm.res;
-    qi.S_out = (uint16_t *)norm.s_out;
-    for (int g = 0; g < 3; ++g) {
-        a.W[g] = W[g];
-        a.SFW[g] = SFW[g];
-        a.K[g] = qi.K[g] = K[g];
-    }
-    a.M = M;
-    a.N = N;
-    a.sfx_row_tiles = 1;
-    a.sfw_row_tiles = (N + 127) / 128;
-    a.round_per_segment = round_per_segment;
-    a.bias = (const uint16_t *)bias;
-    a.D = (uint16_t *)D;
-    const bool wide = (N + 31) / 32 >= device_cus();
-    // kernel-developer overrides: 64 features x 4 waves with this many slots (-1: never) / ring slots (2, 3, 4).  Ignored with the norm inside
-    // the launch: only the default (F, D, NW) configurations have norm variants (an override made a supported shape fail at launch)
-    static const int qf4_env = getenv("MICROMIX_DECODE_F4") ? atoi(getenv("MICROMIX_DECODE_F4")) : 0;
-    static const int qd_env = getenv("MICROMIX_DECODE_DEPTH") ? atoi(getenv("MICROMIX_DECODE_DEPTH")) : 2;
-    const int qf4 = norm.weight != nullptr ? 0 : qf4_env, qd = norm.weight != nullptr ? 2 : qd_env;
-    if (wide && qf4 == 2) return w4 ? launch_quant<4, 2, 4, true>(a, qi, stream) : launch_quant<4, 2, 4, false>(a, qi, stream);
-    if (wide && qf4 == 3) return w4 ? launch_quant<4, 3, 4, true>(a, qi, stream) : launch_quant<4, 3, 4, false>(a, qi, stream);
-    if (wide && qf4 == 4) return w4 ? launch_quant<4, 4, 4, true>(a, qi, stream) : launch_quant<4, 4, 4, false>(a, qi, stream);
-    // more than one round of 32-feature workgroups (two per CU): 64 features x 4 waves halve the workgroups that repeat the quantization and
-    // run in one round (fused gate + up, N = 28672, M = 1: 17.3 -> 14.2 us, from HBM 18.7 -> 16.1; at N = 14336 it loses 1 us from HBM)
-    if (wide && qf4 == 0 && (N + 31) / 32 > 2 * device_cus()) return w4 ? launch_quant<4, 2, 4, true>(a, qi, stream) : launch_quant<4, 2, 4, false>(a, qi, stream);
-    if (wide && qd == 3) return w4 ? launch_quant<2, 3, 8, true>(a, qi, stream) : launch_quant<2, 3, 8, false>(a, qi, stream);
-    if (wide && qd == 4) return w4 ? launch_quant<2, 4, 8, true>(a, qi, stream) : launch_quant<2, 4, 8, false>(a, qi, stream);
-    if (wide) return w4 ? launch_quant<2, 2, 8, true>(a, qi, stream) : launch_quant<2, 2, 8, false>(a, qi, stream);
-    if (((K[0] + K[1] + K[2]) >> 7) <= 32) return w4 ? launch_quant<1, 4, 8, true>(a, qi, stream) : launch_quant<1, 4, 8, false>(a, qi, stream);
-    return w4 ? launch_quant<1, 3, 8, true>(a, qi, stream) : launch_quant<1, 3, 8, false>(a, qi, stream);
+    const StreamCfg c = select_quant(QK_QLINEAR, N, K, norm.weight != nullptr, device_cus(), stream_overrides());
+    return launch_quant_cfg<SK_QUANT>(c, w4, decode_gemm_args(W, SFW, M, N, K, round_per_segment, bias, D), quant_in(X, idx, M, K, norm), stream);
 }
 
-// The fused gate | up launch with the activation inside (stream_body ACT): N = 2 I rows of weights, 128 gate | 128 up alternating
+// The fused gate | up launch with the activation inside (stream_body ACT): on quantized rows, and from the bf16 rows (M <= 4)
 bool gate_up_act_stream_supported(int M, int N, const int K[3], bool from_bf16, bool rms) {
-    static const int on = getenv("MICROMIX_GATE_UP_ACT_STREAM") ? atoi(getenv("MICROMIX_GATE_UP_ACT_STREAM")) : 1;   // kernel-developer override
-    if (!on || M < 1 || N < 256 || (N % 256) != 0) return false;
-    if ((N + 63) / 64 < device_cus()) return false;          // 64-row workgroups: at least one per CU, else the two-launch form
-    const size_t Kt = (size_t)K[0] + K[1] + K[2];
-    if (!from_bf16) {      // one or two token tiles: 4 waves x 2 slots x (4 + 2 T16) KB and both scale images
-        const int T16 = M <= 16 ? 1 : 2;
-        return M <= 32 && 4 * 2 * (4 + 2 * T16) * 1024 + stream::scale_images_bytes(4, T16, 4, (int)(Kt >> 7), true) <= stream::STREAM_LDS_MAX;
-    }
-    if (M > 4 || (rms && Kt > (size_t)dq::RMS_MAX_K)) return false;
-    const size_t norm = rms ? ((dq::rms_bytes(M, K) + 15) & ~(size_t)15) : 0;
-    const size_t tail = 48 * 1024;      // (three segments' reduction image; the rings + scale image stay below; the group buffer lies in the staged row's range)
-    return Kt * 2 >= (size_t)stream::ACT_GROUP_BYTES && dq::operand_bytes(M, K) + 16 + norm + Kt * 2 + tail + 64 <= 156 * 1024 &&
-           stream::scale_image_bytes(4, 4, (int)(Kt >> 7)) <= 16 * 1024;
+    return gate_up_act_supported(M, N, K, from_bf16, rms, device_cus(), stream_overrides());
 }
-template <int T16>
-static hipError_t launch_gate_up_act_tiles(const GemmArgs &a, hipStream_t stream) {
-    using namespace stream;
-    const int present = (a.K[0] ? 1 : 0) + (a.K[1] ? 1 : 0) + (a.K[2] ? 1 : 0);
-    // (two token tiles: eight tiles per wave reduce one segment at a time through one image; the fp6 group buffer lies inside it)
-    const int red_bytes = 4 * (4 * T16 >= 8 ? 1 : present) * 4 * T16 * 4 * 64 * (int)sizeof(float) + (T16 == 1 ? ACT_GROUP_BYTES : 0);
-    const int stage_bytes = 4 * 2 * Ring<4, T16, true>::SLOT + scale_images_bytes(4, T16, 4, (a.K[0] + a.K[1] + a.K[2]) >> 7, true);
-    const int lds = red_bytes > stage_bytes ? red_bytes : stage_bytes;
-    if (lds > STREAM_LDS_MAX) return hipErrorInvalidValue;
-    static DynamicLdsOnce once;
-    if (lds > 65536) {
-        hipError_t e = once.ensure(reinterpret_cast<const void *>(mx_gemm_stream_act_kernel<T16>), STREAM_LDS_MAX);
-        if (e != hipSuccess) return e;
-    }
-    MM_LAUNCH(mx_gemm_stream_act_kernel<T16>, dim3(a.N / 64), dim3(256), lds, stream, a);
-    return hipGetLastError();
-}
-hipError_t launch_gate_up_act_stream(const GemmArgs &a, hipStream_t stream) {
-    return a.M <= 16 ? launch_gate_up_act_tiles<1>(a, stream) : launch_gate_up_act_tiles<2>(a, stream);
-}
+hipError_t launch_gate_up_act_stream(const GemmArgs &a, hipStream_t stream) { return launch_gemm<SK_ACT>(plan_gate_up_act(a.M, a.N, a.K), true, stream, a); }
 hipError_t launch_gate_up_act_stream_decode(const void *X, const int16_t *idx, const GemmArgs &a, hipStream_t stream, const NormArgs &norm) {
-    using namespace stream;
-    dq::QuantIn qi = {};
-    qi.X = (const uint16_t *)X;
-    qi.idx = idx;
-    qi.M = a.M;
-    qi.norm_w = (const uint16_t *)norm.weight;
-    qi.eps = norm.eps;
-    qi.int_round = norm.int_round;
-    qi.R = (const uint16_t *)norm.res;
-    qi.S_out = (uint16_t *)norm.s_out;
-    for (int g = 0; g < 3; ++g) qi.K[g] = a.K[g];
-    return launch_quant<4, 2, 4, true, false, true>(a, qi, stream);
+    return launch_quant_cfg<SK_QUANT_ACT>(select_quant(QK_GATE_UP_ACT, a.N, a.K, norm.weight != nullptr, device_cus(), stream_overrides()), true, a,
+                                          quant_in(X, idx, a.M, a.K, norm), stream);
 }
 
 // mm_down_activate_decode: down_proj at M <= 4 straight from the bf16 gate | up matrix -- every workgroup computes silu(gate) * up and
 // quantizes it for its own use (the bytes of mm_activate_quantize), K = the intermediate size in natural order
-bool down_activate_stream_supported(int M, int N, const int K[3], bool w4) {
-    const size_t Kt = (size_t)K[0] + K[1] + K[2];
-    return M >= 1 && M <= 4 && dq::operand_bytes(M, K) + quant_tail_budget(N, Kt, w4) + 64 <= 156 * 1024;
-}
+bool down_activate_stream_supported(int M, int N, const int K[3], bool w4) { return down_activate_supported(M, N, K, w4, device_cus()); }
 hipError_t launch_down_activate_stream(const void *GU, const uint8_t *const W[3], const uint8_t *const SFW[3], int M, int N, const int K[3],
                                        bool w4, int round_per_segment, const void *bias, void *D, hipStream_t stream) {
-    using namespace stream;
-    GemmArgs a = {};
-    dq::QuantIn qi = {};
-    qi.X = (const uint16_t *)GU;
-    qi.M = M;
-    qi.mode = 1;
-    for (int g = 0; g < 3; ++g) {
-        a.W[g] = W[g];
-        a.SFW[g] = SFW[g];
-        a.K[g] = qi.K[g] = K[g];
-    }
-    a.M = M;
-    a.N = N;
-    a.sfx_row_tiles = 1;
-    a.sfw_row_tiles = (N + 127) / 128;
-    a.round_per_segment = round_per_segment;
-    a.bias = (const uint16_t *)bias;
-    a.D = (uint16_t *)D;
-    const bool wide = (N + 31) / 32 >= device_cus();
-    if (wide) return w4 ? launch_quant<2, 2, 8, true>(a, qi, stream) : launch_quant<2, 2, 8, false>(a, qi, stream);
-    // (A deeper ring does nothing here -- seven or fourteen slots, a wave's whole share of K = 14336 in flight at once, measured the same
-    // 10.6 us as three, round 6, and with the weights coming from HBM 11.6 against 11.5: the launch is the sum of its vector-memory
-    // instructions, not a chain of round trips.  The scale image is what took 1.6 us off it.)
-    return w4 ? launch_quant<1, 3, 8, true>(a, qi, stream) : launch_quant<1, 3, 8, false>(a, qi, stream);
+    const StreamCfg c = select_quant(QK_DOWN_ACTIVATE, N, K, false, device_cus(), stream_overrides());
+    return launch_quant_cfg<SK_QUANT>(c, w4, decode_gemm_args(W, SFW, M, N, K, round_per_segment, bias, D), quant_in(GU, nullptr, M, K, NormArgs{}, 1), stream);
 }
 
-#ifndef MM_STREAM_SWEEP      // kernel-developer build: every (F, D, NW) combination, picked by MICROMIX_STREAM_CFG="F,D,NW"
-#define MM_STREAM_SWEEP 0
-#endif
-
+// mm_matmul at M <= 64
+bool mx_gemm_stream_supported(int M, int N, const int K[3], bool w4) { return gemm_supported(M, N, K, w4, device_cus, stream_overrides()); }
 hipError_t launch_mx_gemm_stream(const GemmArgs &a, bool w4, hipStream_t stream) {
-    using namespace stream;
-    const int cus = device_cus();
-    // 32 features per workgroup once those fill the CUs, 16 below (q/o at N = 4096: 256 workgroups instead of 128)
-    const bool wide = (a.N + 31) / 32 >= cus;
-#define MM_STREAM(F_, T_, D_, NW_)                                                   \
-    (w4 ? launch_one<F_, T_, D_, NW_, true>(a, stream) : launch_one<F_, T_, D_, NW_, false>(a, stream))
-#if MM_STREAM_SWEEP
-    static int cf = 0, cd = 0, cn = 0;
-    static const bool have = getenv("MICROMIX_STREAM_CFG") && sscanf(getenv("MICROMIX_STREAM_CFG"), "%d,%d,%d", &cf, &cd, &cn) == 3;
-    if (have) {
-#define MM_TRY(F_, D_, NW_)                                                                              \
-    if (cf == F_ && cd == D_ && cn == NW_) return a.M <= 16 ? MM_STREAM(F_, 1, D_, NW_) : (a.M <= 32 ? MM_STREAM(F_, 2, D_, NW_) : MM_STREAM(F_, 4, D_, NW_));
-        if (cf == 4 && cd == 2 && cn == 4) return a.M <= 16 ? MM_STREAM(4, 1, 2, 4) : (a.M <= 32 ? MM_STREAM(4, 2, 2, 4) : MM_STREAM(4, 4, 2, 4));
-        if (cf == 4 && cd == 2 && cn == 8) return a.M <= 16 ? MM_STREAM(4, 1, 2, 8) : (a.M <= 32 ? MM_STREAM(4, 2, 2, 8) : hipErrorInvalidValue);
-        if (cf == 4 && cd == 3 && cn == 4) return a.M <= 16 ? MM_STREAM(4, 1, 3, 4) : (a.M <= 32 ? MM_STREAM(4, 2, 3, 4) : hipErrorInvalidValue);
-        MM_TRY(1, 4, 4) MM_TRY(1, 6, 4) MM_TRY(1, 4, 8) MM_TRY(1, 2, 8) MM_TRY(1, 3, 8) MM_TRY(1, 2, 16)
-        MM_TRY(2, 3, 4) MM_TRY(2, 4, 4) MM_TRY(2, 4, 8) MM_TRY(2, 3, 8) MM_TRY(2, 2, 8) MM_TRY(2, 2, 16) MM_TRY(2, 1, 16)
-#undef MM_TRY
-        return hipErrorInvalidValue;
-    }
-#endif
-    // (slots, waves) from sweeps on three boxes (profiles/r04_stream_ablation.txt, section 7): more waves with a shallow ring beat fewer
-    // with a deep one; 32 tokens x 32 features: four waves, so that two workgroups fit a CU's LDS
-    // more than one round of 32-feature workgroups (fused gate + up, N = 28672): 64 features x 4 waves run in one round -- the same
-    // time with resident weights, 1 us less at M = 16 when they come from HBM (18.2 -> 17.1; section 19 of the record)
-    if (a.M <= 16 && (a.N + 31) / 32 > 2 * cus) return MM_STREAM(4, 1, 2, 4);
-    const int slabs = (a.K[0] + a.K[1] + a.K[2]) >> 7;
-    // (few features: four slots when a wave's slabs are at most four -- K <= 4096: everything is requested at once, no phantom steps)
-    if (a.M <= 16) return wide ? MM_STREAM(2, 1, 2, 8) : (slabs <= 32 ? MM_STREAM(1, 1, 4, 8) : MM_STREAM(1, 1, 3, 8));
-    // 17 .. 32 tokens.  fp4 weights take their scales from images (round 6): on 32 features two slots instead of three keep the second
-    // workgroup's place in the LDS (gate/up 10.1-10.8 -> 9.4-9.8 us); on 16 features (one workgroup per CU) three slots while rings and
-    // images fit, else two (down_proj 12.0 -> 11.1)
-    if (a.M <= 32 && w4) {
-        if (wide) return launch_one<2, 2, 2, 4, true>(a, stream);
-        return two_tile_fits(3, slabs) ? launch_one<1, 2, 3, 8, true>(a, stream) : launch_one<1, 2, 2, 8, true>(a, stream);
-    }
-    if (a.M <= 32) return wide ? MM_STREAM(2, 2, 3, 4) : MM_STREAM(1, 2, 3, 8);
-    // 33 .. 64 tokens: three / four token tiles; two slots of 8 / 10 KB and four waves, so that two workgroups fit a CU's LDS
-    if (a.M <= 48) return wide ? MM_STREAM(2, 3, 2, 4) : MM_STREAM(1, 3, 2, 8);
-    return wide ? MM_STREAM(2, 4, 2, 4) : MM_STREAM(1, 4, 2, 8);
-#undef MM_STREAM
+    return launch_gemm<SK_PLAIN>(plan_plain(a.M, a.N, a.K, w4, device_cus(), stream_overrides()), w4, stream, a);
 }
 
 }  // namespace mm

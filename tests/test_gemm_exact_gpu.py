@@ -25,9 +25,25 @@ WIDE_N, WIDE_M, EDGE_SPLIT = 24608, (1, 8, 16, 17, 32), (128, 128, 128)
 EDGE_M = sorted({m for m, n in _boundary_shapes() if n == 264})
 EDGE_N = (264, 4104)
 SPLIT_K = [(130, 256, (2048, 1024, 1024)), (192, 256, (12288, 1024, 1024)), (128, 1024, (2048, 128, 1920)), (65, 700, (2048, 0, 512))]
+# the streaming configurations a grouped / device-sized launch picks by default (tests/test_stream_dispatch_cpu.py asserts that the
+# tables below reach every one): 32 features per workgroup once N / 32 x groups fills the CUs -- N = 1024 with eight groups -- per
+# tier of the largest group (16 | 32 | 48 | 64 rows); 16 features below, and two ring slots instead of three for two token tiles of
+# fp4 weights once K is too long for three (209 slabs)
+WIDE_TIERS = [(1024, (256, 128, 256), ms) for ms in ((16, 3, 1, 8, 5, 12, 2, 7), (17, 32, 3, 20, 1, 25, 9, 30), (33, 48, 4, 40, 17, 1, 36, 45),
+                                                      (49, 64, 2, 55, 33, 16, 60, 50))]
+NARROW_TIERS = [(256, (256, 128, 256), (17, 32, 5)), (256, (256, 128, 256), (33, 48, 2)), (32, (0, 0, 26752), (17,))]
 GROUPED = [(256, (256, 128, 128), (3, 0, 17, 64, 1, 40, 8, 33, 5, 12)),                 # ten groups, one empty (tests/test_grouped_gpu.py)
-           (512, (128, 0, 128), (128, 200, 65, 512, 300, 96, 1000, 70, 130))]            # nine large groups
+           (512, (128, 0, 128), (128, 200, 65, 512, 300, 96, 1000, 70, 130)),            # nine large groups
+           *WIDE_TIERS, *NARROW_TIERS]
+GROUPED_IDS = ["ten-groups", "nine-large-groups"] + [f"wide-{16 * t}-rows" for t in (1, 2, 3, 4)] + ["narrow-32-rows", "narrow-48-rows", "two-slots-32-rows"]
 MOE = (512, (256, 128, 128), (0, 1, 65, 300))
+MOE_TIERS = [*WIDE_TIERS, (256, (256, 128, 256), (16, 0, 7)), *NARROW_TIERS]             # (one more: the device-sized 16-row tier on 16 features)
+MOE_TABLES = [MOE, *MOE_TIERS]
+
+
+def _group_seed(N, split, ms, g):
+    """the two tables this file began with keep the seeds they had; every later table's seeds also carry its split and row counts"""
+    return _seed(8, N, g) if (N, split, ms) in GROUPED[:2] else _seed(11, N, split, ms, g)
 
 
 def _seed(*key):
@@ -60,9 +76,9 @@ def all_cases():
     cases += [(M, N, EDGE_SPLIT, _seed(6, M, N), ("w4",)) for M in EDGE_M for N in EDGE_N]
     cases += [(M, N, split, _seed(7, M, N, split), BOTH) for M, N, split in SPLIT_K]
     for N, split, ms in GROUPED:
-        cases += [(M, N, split, _seed(8, N, g), BOTH) for g, M in enumerate(ms)]
-    N, split, ms = MOE
-    cases += [(M, N, split, _seed(9, e), BOTH) for e, M in enumerate(ms)]
+        cases += [(M, N, split, _group_seed(N, split, ms, g), BOTH) for g, M in enumerate(ms)]
+    for N, split, ms in MOE_TABLES:
+        cases += [(M, N, split, _seed(9, e) if (N, split, ms) == MOE else _seed(10, N, split, ms, e), BOTH) for e, M in enumerate(ms)]
     return cases
 
 
@@ -208,10 +224,10 @@ def _group_cases(N, split, ms, wmode, seeds):
 
 
 @pytest.mark.parametrize("wmode", BOTH)
-@pytest.mark.parametrize("N,split,ms", GROUPED, ids=["ten-groups", "nine-large-groups"])
+@pytest.mark.parametrize("N,split,ms", GROUPED, ids=GROUPED_IDS)
 def test_grouped_launch(dev, N, split, ms, wmode):
     import torch
-    cases = _group_cases(N, split, ms, wmode, [_seed(8, N, g) for g in range(len(ms))])
+    cases = _group_cases(N, split, ms, wmode, [_group_seed(N, split, ms, g) for g in range(len(ms))])
     As, Bs = [to_dev(dev, c.qx) for c in cases], [to_dev(dev, c.qw) for c in cases]
     biases = [t_from_bits(c.bias, dev) if g % 2 else None for g, c in enumerate(cases)]
     for rounding in ("reference", "fused"):
@@ -226,10 +242,20 @@ def test_grouped_launch(dev, N, split, ms, wmode):
 @pytest.mark.parametrize("with_bias", (False, True), ids=["plain", "bias"])
 @pytest.mark.parametrize("wmode", BOTH)
 def test_moe_matmul(dev, wmode, with_bias):
+    _moe_matmul(dev, *MOE, wmode, with_bias, [_seed(9, e) for e in range(len(MOE[2]))])
+
+
+@pytest.mark.parametrize("wmode", BOTH)
+@pytest.mark.parametrize("N,split,ms", MOE_TIERS, ids=[f"{n}x{sum(s)}-{max(m)}-rows-{len(m)}-experts" for n, s, m in MOE_TIERS])
+def test_moe_matmul_tiers(dev, N, split, ms, wmode):
+    """every streaming configuration a device-sized launch picks (the tier from max_rows, the width from N / 32 x experts)"""
+    _moe_matmul(dev, N, split, ms, wmode, True, [_seed(10, N, split, ms, e) for e in range(len(ms))])
+
+
+def _moe_matmul(dev, N, split, ms, wmode, with_bias, seeds):
     import torch
-    N, split, ms = MOE
     E, n, K = len(ms), sum(ms), sum(split)
-    cases = _group_cases(N, split, ms, wmode, [_seed(9, e) for e in range(len(ms))])
+    cases = _group_cases(N, split, ms, wmode, seeds)
     off = np.concatenate([[0], np.cumsum(ms)]).astype(np.int32)
     idx = [torch.arange(K, dtype=torch.int16, device=dev) for _ in ms]           # the packed operands are in reordered order already
     table = mixedgemm.moe_expert_table(idx, [tuple(to_dev(dev, c.qw)) for c in cases], *split,

@@ -495,6 +495,9 @@ STREAM_CASES = [
     (32, 300, (3072, 896, 128)),           # two token tiles, 32 slabs
     (5, 16640, (256, 128, 256)),           # more than one round of 32-feature workgroups: 64 features x 4 waves (F = 4), half tiles
     (16, 16424, (128, 256, 1024)),         # ... full tiles, ragged last workgroup (16424 = 256 x 64 + 40)
+    (17, 48, (0, 0, 26752)),               # two token tiles, fp4 weights: 209 slabs, too many for three ring slots beside the scale images: two
+    (40, 272, (256, 128, 256)),            # three token tiles where the default dispatch streams them (N / 32 far below the CUs)
+    (64, 200, (128, 128, 128)),            # four token tiles, ragged N
 ]
 # 32 < M <= 64 (three / four token tiles; the dispatch sends only some of these shapes to the streaming kernel, so it is forced through
 # MICROMIX_MID_M_STREAM in a child process: tests/test_stream_mid_m_gpu.py)
