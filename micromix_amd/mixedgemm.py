@@ -19,14 +19,20 @@ Differences from the reference, all deliberate:
   * inputs are validated (dtype/device/contiguity) instead of being reinterpreted blindly;
   * `matmul` takes optional keyword-only `bias` and `rounding` arguments (extensions).
 The remaining exports of the reference module (FlashInfer KV ops) are outside the hot path; they raise
-NotImplementedError.  The paged KV cache itself is `kv_append` / `paged_decode` / `paged_prefill` below (GQA, bf16 q,
+NotImplementedError.  The paged KV cache itself is `kv_append` / `paged_decode` / `paged_prefill` (GQA, bf16 q,
 quantizes K/V itself; micromix_amd/kvcache.py wraps them), on the reference's FlashInfer layout.
+
+This module holds the reference's surface, its quantizers and the fused decode layer.  The paged-cache, attention, verification and
+sampling wrappers live in micromix_amd/paged.py and the `moe_*` wrappers and tables in micromix_amd/moe_ops.py; both are re-exported
+here, so `mixedgemm.<name>` stays the one way to reach every op.  The argument checks and the launch tail that all three share are
+micromix_amd/_args.py.
 """
 from __future__ import annotations
 
 import torch
 
 from . import _lib
+from ._args import _check_split, _check_tensor, _launch, _ok, _on_device, _opt, _ptr, _round_flags, _sf_bytes_w, _stream_ptr
 
 __all__ = ["test_function", "matmul", "gate_up_activate", "interleave_gate_up", "reorder_quantize_x", "reorder_quantize_w", "reorder_quantize_w4", "activate_quantize_x",
            "downproj_quantize_w", "downproj_quantize_w4", "rmsnorm_quantize_x", "qlinear_decode", "qlinear_decode_supported", "matmul_grouped", "reorder_quantize_x_grouped",
@@ -42,52 +48,8 @@ def test_function():
     return _lib.load().mm_test_function().decode()
 
 
-def _stream_ptr(device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
-
-
-def _check_tensor(t, name, dtype, device=None):
-    """Slow path: produces the precise error.  The ops call it only after the cheap combined test failed."""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
-    if t.dtype != dtype:
-        raise TypeError(f"{name} must be {dtype}, got {t.dtype}")
-    if not t.is_cuda:
-        raise RuntimeError(f"{name} must be a device tensor (HIP); the MicroMix ops have no CPU path")
-    if device is not None and t.device != device:
-        raise RuntimeError(f"{name} is on {t.device}, expected {device}")
-    if not t.is_contiguous():
-        raise RuntimeError(f"{name} must be contiguous")
-
-
-def _ok(t, dtype, index) -> bool:
-    # one short-circuit expression per tensor: ~0.3 us instead of ~0.7 us for the descriptive checks
-    return t.dtype is dtype and t.is_cuda and t.get_device() == index and t.is_contiguous()
-
-
-def _ptr(t):
-    return t.data_ptr() if t.numel() else None
-
-
 def _sf_bytes_x(m, k):   # bindings.cpp:120-123
     return (m // 128 + 1) * 128 * (k // 32)
-
-
-def _sf_bytes_w(n, k):   # bindings.cpp:170-172 (rows padded to 128)
-    return (n + 127) // 128 * 128 * (k // 32)
-
-
-def _check_split(KN, KS, KO, K, what):
-    """the reference's "Value error in run_<what>" unless (KN, KS, KO) are non-negative multiples of 128 that add up to K (K None: to
-    anything but 0)"""
-    if KN < 0 or KS < 0 or KO < 0 or KN % 128 or KS % 128 or KO % 128 or (KN + KS + KO != K if K is not None else KN + KS + KO == 0):
-        _lib.check(_lib.MM_ERR_BAD_SPLIT, what)
-
-
-def _round_flags(rounding, integer_round=True):
-    if rounding not in ("reference", "fused"):
-        raise ValueError("rounding must be 'reference' or 'fused'")
-    return (_lib.MM_ROUND_PER_SEGMENT if rounding == "reference" else _lib.MM_ROUND_ONCE) | (0 if integer_round else _lib.MM_NORM_NO_INTEGER_ROUND)
 
 
 def _weight_mode(B, N, KN, KS, KO, split_name="(KN, KS, KO)"):
@@ -106,26 +68,6 @@ def _check_weight_scales(SF, N, KN, KS, KO, names=None):
             if t.numel() < _sf_bytes_w(N, k):
                 raise RuntimeError(f"{n} holds {t.numel()} scale bytes, needs at least {_sf_bytes_w(N, k)}")
         raise RuntimeError("weight scale tensors are too small")
-
-
-class _on_device:
-    """`with torch.cuda.device(d)` only when d is not already current (saves ~2 us per call)."""
-    __slots__ = ("idx", "prev")
-
-    def __init__(self, idx):
-        self.idx = idx
-        self.prev = -1
-
-    def __enter__(self):
-        cur = torch.cuda.current_device()
-        if cur != self.idx:
-            self.prev = cur
-            torch.cuda.set_device(self.idx)
-
-    def __exit__(self, *exc):
-        if self.prev >= 0:
-            torch.cuda.set_device(self.prev)
-        return False
 
 
 def _quantize(src, reorder_index, KN, KS, KO, mode, what, gather_subset=False):
@@ -152,14 +94,9 @@ def _quantize(src, reorder_index, KN, KS, KO, mode, what, gather_subset=False):
     sfN = torch.empty((sf_bytes(rows, KN),), dtype=u8, device=dev)
     sfS = torch.empty((sf_bytes(rows, KS),), dtype=u8, device=dev)
     sfO = torch.empty((sf_bytes(rows, KO),), dtype=u8, device=dev)
-    with _on_device(dev.index):
-        entry = lib.mm_reorder_quantize_gather if gather_subset else lib.mm_reorder_quantize
-        st = entry(
-            _ptr(src), rows, K, _ptr(reorder_index), KN, KS, KO,
-            _lib.MM_QUANT_W4 if w4 else _lib.MM_QUANT_MIXED,
+    _launch(what, dev, lib.mm_reorder_quantize_gather if gather_subset else lib.mm_reorder_quantize,
+            _ptr(src), rows, K, _ptr(reorder_index), KN, KS, KO, _lib.MM_QUANT_W4 if w4 else _lib.MM_QUANT_MIXED,
             _ptr(oN), _ptr(oS), _ptr(oO), _ptr(sfN), _ptr(sfS), _ptr(sfO), _stream_ptr(dev))
-    if st:
-        _lib.check(st, what)
     return oN, oS, oO, sfN, sfS, sfO
 
 
@@ -300,13 +237,8 @@ def matmul(AN, BN, AS, BS, AO, BO, SFAN, SFBN, SFAS, SFBS, SFAO, SFBO, *, bias=N
         if ws_bytes:
             ws = split_workspace(dev, ws_bytes)
             ws_bytes = ws.numel()
-    with _on_device(index):
-        st = lib.mm_matmul_ws(_ptr(AN), _ptr(BN), _ptr(AS), _ptr(BS), _ptr(AO), _ptr(BO), _ptr(SFAN), _ptr(SFBN),
-                              _ptr(SFAS), _ptr(SFBS), _ptr(SFAO), _ptr(SFBO), M, N, KN, KS, KO, wmode, flags,
-                              _ptr(bias) if bias is not None else None, _ptr(out), _ptr(ws) if ws is not None else None,
-                              ws_bytes, _stream_ptr(dev))
-    if st:
-        _lib.check(st, "matmul")
+    _launch("matmul", dev, lib.mm_matmul_ws, _ptr(AN), _ptr(BN), _ptr(AS), _ptr(BS), _ptr(AO), _ptr(BO), _ptr(SFAN), _ptr(SFBN),
+            _ptr(SFAS), _ptr(SFBS), _ptr(SFAO), _ptr(SFBO), M, N, KN, KS, KO, wmode, flags, _opt(bias), _ptr(out), _opt(ws), ws_bytes, _stream_ptr(dev))
     return out
 
 
@@ -392,13 +324,9 @@ def gate_up_activate(A, B, DN, DS, DO, *, rounding="reference"):
     sfO = torch.empty((_sf_bytes_x(M, DO),), dtype=u8, device=dev)
     ws_bytes = lib.mm_gate_up_activate_workspace_bytes(M, I)
     ws = torch.empty((ws_bytes,), dtype=u8, device=dev) if ws_bytes else None      # stream-ordered scratch from the caching allocator
-    with _on_device(index):
-        st = lib.mm_gate_up_activate(_ptr(A[0]), _ptr(B[0]), _ptr(A[1]), _ptr(B[1]), _ptr(A[2]), _ptr(B[2]), _ptr(A[3]), _ptr(B[3]),
-                                     _ptr(A[4]), _ptr(B[4]), _ptr(A[5]), _ptr(B[5]), M, I, KN, KS, KO, DN, DS, DO, flags,
-                                     _ptr(oN), _ptr(oS), _ptr(oO), _ptr(sfN), _ptr(sfS), _ptr(sfO),
-                                     _ptr(ws) if ws is not None else None, ws_bytes, _stream_ptr(dev))
-    if st:
-        _lib.check(st, "gate_up_activate")
+    _launch("gate_up_activate", dev, lib.mm_gate_up_activate, _ptr(A[0]), _ptr(B[0]), _ptr(A[1]), _ptr(B[1]), _ptr(A[2]), _ptr(B[2]), _ptr(A[3]),
+            _ptr(B[3]), _ptr(A[4]), _ptr(B[4]), _ptr(A[5]), _ptr(B[5]), M, I, KN, KS, KO, DN, DS, DO, flags,
+            _ptr(oN), _ptr(oS), _ptr(oO), _ptr(sfN), _ptr(sfS), _ptr(sfO), _opt(ws), ws_bytes, _stream_ptr(dev))
     return oN, oS, oO, sfN, sfS, sfO
 
 
@@ -434,10 +362,7 @@ def reorder_quantize_x_grouped(Xs, reorder_indices, KN, KS, KO):
         e.src_bf16, e.reorder_index = _ptr(X), _ptr(idx)
         e.oN, e.oS, e.oO, e.sfN, e.sfS, e.sfO = (_ptr(t) for t in out)
         e.rows = rows
-    with _on_device(index):
-        st = lib.mm_reorder_quantize_grouped(arr, len(Xs), K, KN, KS, KO, _lib.MM_QUANT_MIXED, _stream_ptr(dev))
-    if st:
-        _lib.check(st, "reorder_quantize_x")
+    _launch("reorder_quantize_x", dev, lib.mm_reorder_quantize_grouped, arr, len(Xs), K, KN, KS, KO, _lib.MM_QUANT_MIXED, _stream_ptr(dev))
     return res
 
 
@@ -495,10 +420,7 @@ def matmul_grouped(As, Bs, *, biases=None, rounding="reference", outs=None):
         e.bias_bf16 = _ptr(bias) if bias is not None else None
         e.D = _ptr(out)
         e.M = M
-    with _on_device(index):
-        st = lib.mm_matmul_grouped(arr, len(As), N, KN, KS, KO, wmode, flags, _stream_ptr(dev))
-    if st:
-        _lib.check(st, "matmul_grouped")
+    _launch("matmul_grouped", dev, lib.mm_matmul_grouped, arr, len(As), N, KN, KS, KO, wmode, flags, _stream_ptr(dev))
     return outs
 
 
@@ -606,17 +528,14 @@ def _gate_up_activate_decode(norm, X, norm_weight, eps, reorder_index, B, DN, DS
     sfO = torch.empty((_sf_bytes_x(M, DO),), dtype=u8, device=dev)
     ws = torch.empty((M * N2 * 2,), dtype=u8, device=dev)      # (scratch of the two-launch form; stream-ordered, from the caching allocator)
     tail = (_ptr(reorder_index), _ptr(B[0]), _ptr(B[1]), _ptr(B[2]), _ptr(B[3]), _ptr(B[4]), _ptr(B[5]), M, I, KN, KS, KO, DN, DS, DO, flags, _ptr(oN),
-            _ptr(oS), _ptr(oO), _ptr(sfN), _ptr(sfS), _ptr(sfO), _ptr(ws), ws.numel(), _stream_ptr(dev))
-    with _on_device(index):
-        if not norm:
-            st, what = lib.mm_gate_up_activate_decode(_ptr(X), *tail), "gate_up_activate_decode"
-        elif residual is None:
-            st, what = lib.mm_rmsnorm_gate_up_activate_decode(_ptr(X), _ptr(norm_weight), float(eps), *tail), "rmsnorm_gate_up_activate_decode"
-        else:
-            st, what = lib.mm_add_rmsnorm_gate_up_activate_decode(_ptr(X), _ptr(residual), _ptr(out_sum), _ptr(norm_weight), float(eps), *tail), \
-                "add_rmsnorm_gate_up_activate_decode"
-    if st:
-        _lib.check(st, what)
+            _ptr(oS), _ptr(oO), _ptr(sfN), _ptr(sfS), _ptr(sfO), _ptr(ws), ws.numel())
+    if not norm:
+        _launch("gate_up_activate_decode", dev, lib.mm_gate_up_activate_decode, _ptr(X), *tail, _stream_ptr(dev))
+    elif residual is None:
+        _launch("rmsnorm_gate_up_activate_decode", dev, lib.mm_rmsnorm_gate_up_activate_decode, _ptr(X), _ptr(norm_weight), float(eps), *tail, _stream_ptr(dev))
+    else:
+        _launch("add_rmsnorm_gate_up_activate_decode", dev, lib.mm_add_rmsnorm_gate_up_activate_decode, _ptr(X), _ptr(residual), _ptr(out_sum),
+                _ptr(norm_weight), float(eps), *tail, _stream_ptr(dev))
     return out_sum, oN, oS, oO, sfN, sfS, sfO
 
 
@@ -657,11 +576,8 @@ def down_activate_decode(GU, B, DN, DS, DO, *, bias=None, rounding="reference"):
         _check_tensor(bias, "bias", torch.bfloat16, dev)
         raise RuntimeError("bias must have N elements")
     out = torch.empty((M, N), dtype=torch.bfloat16, device=dev)
-    with _on_device(index):
-        st = lib.mm_down_activate_decode(_ptr(GU), _ptr(B[0]), _ptr(B[1]), _ptr(B[2]), _ptr(B[3]), _ptr(B[4]), _ptr(B[5]), M, N, DN, DS, DO, wmode,
-                                         flags, _ptr(bias) if bias is not None else None, _ptr(out), _stream_ptr(dev))
-    if st:
-        _lib.check(st, "down_activate_decode")
+    _launch("down_activate_decode", dev, lib.mm_down_activate_decode, _ptr(GU), _ptr(B[0]), _ptr(B[1]), _ptr(B[2]), _ptr(B[3]), _ptr(B[4]), _ptr(B[5]),
+            M, N, DN, DS, DO, wmode, flags, _opt(bias), _ptr(out), _stream_ptr(dev))
     return out
 
 
@@ -734,17 +650,14 @@ def _qlinear_decode(norm, X, norm_weight, eps, reorder_index, BN, BS, BO, SFBN, 
     if out is None:
         out = torch.empty((M, N), dtype=torch.bfloat16, device=dev)
     tail = (_ptr(reorder_index), _ptr(BN), _ptr(BS), _ptr(BO), _ptr(SFBN), _ptr(SFBS), _ptr(SFBO), M, N, KN, KS, KO, wmode, flags,
-            _ptr(bias) if bias is not None else None, _ptr(out), _stream_ptr(dev))
-    with _on_device(index):
-        if not norm:
-            st, what = lib.mm_qlinear_decode(_ptr(X), *tail), "qlinear_decode"
-        elif residual is None:
-            st, what = lib.mm_rmsnorm_qlinear_decode(_ptr(X), _ptr(norm_weight), float(eps), *tail), "rmsnorm_qlinear_decode"
-        else:
-            st, what = lib.mm_add_rmsnorm_qlinear_decode(_ptr(X), _ptr(residual), _ptr(out_sum), _ptr(norm_weight), float(eps), *tail), \
-                "add_rmsnorm_qlinear_decode"
-    if st:
-        _lib.check(st, what)
+            _opt(bias), _ptr(out))
+    if not norm:
+        _launch("qlinear_decode", dev, lib.mm_qlinear_decode, _ptr(X), *tail, _stream_ptr(dev))
+    elif residual is None:
+        _launch("rmsnorm_qlinear_decode", dev, lib.mm_rmsnorm_qlinear_decode, _ptr(X), _ptr(norm_weight), float(eps), *tail, _stream_ptr(dev))
+    else:
+        _launch("add_rmsnorm_qlinear_decode", dev, lib.mm_add_rmsnorm_qlinear_decode, _ptr(X), _ptr(residual), _ptr(out_sum), _ptr(norm_weight),
+                float(eps), *tail, _stream_ptr(dev))
     return out_sum, out
 
 
@@ -770,15 +683,12 @@ def _direct(src_a, src_b, KN, KS, KO, mode, what):
     sfN = torch.empty((_sf_bytes_x(rows, KN),), dtype=u8, device=dev)
     sfS = torch.empty((_sf_bytes_x(rows, KS),), dtype=u8, device=dev)
     sfO = torch.empty((_sf_bytes_x(rows, KO),), dtype=u8, device=dev)
-    with _on_device(dev.index):
-        if src_b is not None:
-            st = lib.mm_activate_quantize(_ptr(src_a), _ptr(src_b), rows, KN, KS, KO, _ptr(oN), _ptr(oS), _ptr(oO), _ptr(sfN),
-                                          _ptr(sfS), _ptr(sfO), _stream_ptr(dev))
-        else:
-            st = lib.mm_downproj_quantize(_ptr(src_a), rows, KN, KS, KO, _lib.MM_QUANT_W4 if w4 else _lib.MM_QUANT_MIXED,
-                                          _ptr(oN), _ptr(oS), _ptr(oO), _ptr(sfN), _ptr(sfS), _ptr(sfO), _stream_ptr(dev))
-    if st:
-        _lib.check(st, what)
+    if src_b is not None:
+        _launch(what, dev, lib.mm_activate_quantize, _ptr(src_a), _ptr(src_b), rows, KN, KS, KO, _ptr(oN), _ptr(oS), _ptr(oO), _ptr(sfN), _ptr(sfS),
+                _ptr(sfO), _stream_ptr(dev))
+    else:
+        _launch(what, dev, lib.mm_downproj_quantize, _ptr(src_a), rows, KN, KS, KO, _lib.MM_QUANT_W4 if w4 else _lib.MM_QUANT_MIXED,
+                _ptr(oN), _ptr(oS), _ptr(oO), _ptr(sfN), _ptr(sfS), _ptr(sfO), _stream_ptr(dev))
     return oN, oS, oO, sfN, sfS, sfO
 
 
@@ -860,14 +770,11 @@ def _rmsnorm_quantize_x(add, X, W, eps, reorder_index, KN, KS, KO, integer_round
     sfS = torch.empty((_sf_bytes_x(rows, KS),), dtype=u8, device=dev)
     sfO = torch.empty((_sf_bytes_x(rows, KO),), dtype=u8, device=dev)
     tail = (float(eps), rows, K, _ptr(reorder_index), KN, KS, KO, _lib.MM_RMS_REFERENCE if integer_round else _lib.MM_RMS_NO_INTEGER_ROUND,
-            _ptr(oN), _ptr(oS), _ptr(oO), _ptr(sfN), _ptr(sfS), _ptr(sfO), _stream_ptr(dev))
-    with _on_device(dev.index):
-        if add:
-            st = lib.mm_add_rmsnorm_quantize(_ptr(X), _ptr(residual), _ptr(out_sum), _ptr(W), *tail)
-        else:
-            st = lib.mm_rmsnorm_quantize(_ptr(X), _ptr(W), *tail)
-    if st:
-        _lib.check(st, "add_rmsnorm_quantize_x" if add else "rmsnorm_bf16_mixed")
+            _ptr(oN), _ptr(oS), _ptr(oO), _ptr(sfN), _ptr(sfS), _ptr(sfO))
+    if add:
+        _launch("add_rmsnorm_quantize_x", dev, lib.mm_add_rmsnorm_quantize, _ptr(X), _ptr(residual), _ptr(out_sum), _ptr(W), *tail, _stream_ptr(dev))
+    else:
+        _launch("rmsnorm_bf16_mixed", dev, lib.mm_rmsnorm_quantize, _ptr(X), _ptr(W), *tail, _stream_ptr(dev))
     return out_sum, oN, oS, oO, sfN, sfS, sfO
 
 
@@ -875,1039 +782,8 @@ for _n in ("batch_decode_i4", "batch_decode_f16", "init_kv_i4", "init_kv_f16", "
     globals()[_n] = _not_on_path(_n)
 
 
-# ---- paged KV cache (include/micromix_hip.h, mm_kv_append / mm_paged_decode; micromix_amd/kvcache.py is the small cache object) ----
-
-def _kv_bytes(kv_data):
-    """an fp8 cache held as torch.float8_e4m3fn, seen as the uint8 tensor the ops take: the same bytes, OCP e4m3fn codes"""
-    return kv_data.view(torch.uint8) if isinstance(kv_data, torch.Tensor) and kv_data.dtype is torch.float8_e4m3fn else kv_data
-
-
-def _kv_geometry(kv_data, kv_param, index):
-    """(dtype code, max_pages, L, Hkv, P, kv_data as the C ABI takes it) of a cache, recognised by its shape; int4: uint8
-    [max_pages, L, 2, Hkv, P, 64] + fp16 params [..., P, 2]; fp8: uint8 (or torch.float8_e4m3fn, viewed as uint8) [max_pages, L, 2, Hkv,
-    P, 128] + the same fp16 params; bf16: bf16 [max_pages, L, 2, Hkv, P, 128] and kv_param None."""
-    if kv_param is None:
-        if not _ok(kv_data, torch.bfloat16, index):
-            _check_tensor(kv_data, "kv_data", torch.bfloat16)
-            raise RuntimeError(f"kv_data must be on cuda:{index}")
-        if kv_data.dim() != 6 or kv_data.size(2) != 2 or kv_data.size(5) != 128:
-            raise RuntimeError("bf16 kv_data (kv_param None) must be [max_pages, L, 2, Hkv, P, 128]; an int4 cache ([..., 64] uint8) and an "
-                               "fp8 cache ([..., 128] uint8 / float8_e4m3fn) need their fp16 kv_param")
-        kind = _lib.MM_KV_BF16
-    else:
-        kv_data = _kv_bytes(kv_data)
-        if not (_ok(kv_data, torch.uint8, index) and _ok(kv_param, torch.float16, index)):
-            _check_tensor(kv_data, "kv_data", torch.uint8)
-            _check_tensor(kv_param, "kv_param", torch.float16, kv_data.device)
-            raise RuntimeError(f"kv_data / kv_param must be on cuda:{index}")
-        if kv_data.dim() != 6 or kv_data.size(2) != 2 or kv_data.size(5) not in (64, 128):
-            raise RuntimeError("kv_data with a kv_param must be [max_pages, L, 2, Hkv, P, 64] uint8 (int4) or [max_pages, L, 2, Hkv, P, 128] "
-                               "uint8 / float8_e4m3fn (fp8); a bf16 cache [max_pages, L, 2, Hkv, P, 128] takes kv_param None")
-        if tuple(kv_param.shape) != tuple(kv_data.shape[:5]) + (2,):
-            raise RuntimeError("kv_param must be [max_pages, L, 2, Hkv, P, 2] fp16, matching kv_data")
-        kind = _lib.MM_KV_INT4 if kv_data.size(5) == 64 else _lib.MM_KV_FP8_E4M3
-    max_pages, L, _, Hkv, P, _ = kv_data.shape
-    return kind, max_pages, L, Hkv, P, kv_data
-
-
-def _page_table(kv_indptr, kv_indices, last_page_len, dev):
-    for n, t in (("kv_indptr", kv_indptr), ("kv_indices", kv_indices), ("last_page_len", last_page_len)):
-        if not _ok(t, torch.int32, dev.index):
-            _check_tensor(t, n, torch.int32, dev)
-    B = last_page_len.numel()
-    if kv_indptr.numel() != B + 1:
-        raise RuntimeError("kv_indptr must have B + 1 entries (B = last_page_len.numel())")
-    return B
-
-
-def _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, q=None):
-    """The common checks of the four cache ops: (device, B, Hkv, the C arguments kv_data .. batch that every entry point takes in this
-    order).  The device is q's (bf16, contiguous); an append has no q and takes the cache's."""
-    if kv_param is not None:
-        kv_data = _kv_bytes(kv_data)
-    if q is None:
-        if not (isinstance(kv_data, torch.Tensor) and kv_data.is_cuda):
-            _check_tensor(kv_data, "kv_data", torch.uint8 if kv_param is not None else torch.bfloat16)
-        dev = kv_data.device
-    else:
-        if not (isinstance(q, torch.Tensor) and q.is_cuda and _ok(q, torch.bfloat16, q.get_device())):
-            _check_tensor(q, "q", torch.bfloat16)
-        dev = q.device
-    kind, max_pages, L, Hkv, P, kv_data = _kv_geometry(kv_data, kv_param, dev.index)
-    B = _page_table(kv_indptr, kv_indices, last_page_len, dev)
-    layer_idx = int(layer_idx)
-    if not 0 <= layer_idx < L:
-        raise RuntimeError(f"layer_idx {layer_idx} outside the cache's {L} layers")
-    return dev, B, Hkv, (_ptr(kv_data), _ptr(kv_param) if kv_param is not None else None, kind, max_pages, L, layer_idx, Hkv, P, 128,
-                         _ptr(kv_indptr), _ptr(kv_indices), _ptr(last_page_len), B)
-
-
-def _kv_workspace(workspace, need, dev):
-    """(the split-KV scratch, which the caller holds across the launch, its two C arguments): allocated when `need` bytes are wanted and
-    none was passed"""
-    if not need:
-        return None, (None, 0)
-    if workspace is None:
-        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
-    if (not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or workspace.device != dev
-            or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need):
-        raise RuntimeError(f"workspace must be a contiguous device tensor of at least {need} bytes on {dev}")
-    return workspace, (_ptr(workspace), workspace.numel() * workspace.element_size())
-
-
-def _sm_scale(sm_scale):
-    scale = float(sm_scale) if sm_scale is not None else 128 ** -0.5
-    if not scale > 0:
-        raise ValueError("sm_scale must be positive")
-    return scale
-
-
-def kv_append(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, k, v, append_indptr, layer_idx):
-    """Write T new tokens' K and V (bf16 [T, Hkv, 128]) into layer `layer_idx` of a paged cache, in place.
-
-    Not an export of the reference module (its append_kv_i4 / _f16 take K/V already quantized and one head count).  The page table
-    (kv_indptr [B + 1], kv_indices, last_page_len [B], int32) already counts the new tokens; append_indptr [B + 1] splits the T tokens
-    among the sequences, each sequence's go to its last positions.  kv_param None: bf16 cache (a copy); otherwise int4 codes + fp16
-    (scale, zero) by the rule of quantize_int_group(x, 4, 128), or -- kv_data [..., 128] uint8 / float8_e4m3fn -- e4m3 codes with a
-    power-of-two scale per row and zero = 0 (include/micromix_hip.h, MM_KV_FP8_E4M3).  Runs on the current stream, capture-safe.
-    """
-    lib = _lib.load()
-    dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx)
-    if not _ok(append_indptr, torch.int32, dev.index):
-        _check_tensor(append_indptr, "append_indptr", torch.int32, dev)
-    for n, t in (("k", k), ("v", v)):
-        if not _ok(t, torch.bfloat16, dev.index):
-            _check_tensor(t, n, torch.bfloat16, dev)
-    if k.dim() != 3 or k.shape != v.shape or k.size(1) != Hkv or k.size(2) != 128:
-        raise RuntimeError(f"k and v must both be [T, {Hkv}, 128] bf16")
-    if append_indptr.numel() != B + 1:
-        raise RuntimeError("append_indptr must have B + 1 entries")
-    with _on_device(dev.index):
-        st = lib.mm_kv_append(*kv_args, _ptr(k), _ptr(v), _ptr(append_indptr), k.size(0), _stream_ptr(dev))
-    if st:
-        _lib.check(st, "kv_append")
-
-
-def kv_copy_pages(kv_data, kv_param, src_pages, dst_pages, rows=None):
-    """Copy token rows [0, rows[i]) of page src_pages[i] to page dst_pages[i] of a paged cache, for every layer, K and V, every head, in
-    place; returns None.  rows None: whole pages.  Bytes only (codes and, for int4 / fp8, the fp16 params): no dequantization.
-
-    src_pages, dst_pages, rows: int32 device tensors of one length.  A pair whose page index lies outside the cache, with src == dst or
-    with rows <= 0 is skipped; rows above the page size count as the page size.  The destination pages must be pairwise distinct and
-    none of them a source of the same call (include/micromix_hip.h, mm_kv_copy_pages).  What PagedKVCache.extend calls before a sequence
-    writes into a partly filled page it shares.  Runs on the current stream, capture-safe."""
-    lib = _lib.load()
-    if kv_param is not None:
-        kv_data = _kv_bytes(kv_data)
-    if not (isinstance(kv_data, torch.Tensor) and kv_data.is_cuda):
-        _check_tensor(kv_data, "kv_data", torch.uint8 if kv_param is not None else torch.bfloat16)
-    dev = kv_data.device
-    kind, max_pages, L, Hkv, P, kv_data = _kv_geometry(kv_data, kv_param, dev.index)
-    index = [("src_pages", src_pages), ("dst_pages", dst_pages)] + ([("rows", rows)] if rows is not None else [])
-    for n, t in index:
-        if not _ok(t, torch.int32, dev.index):
-            _check_tensor(t, n, torch.int32, dev)
-        if t.dim() != 1 or t.numel() != src_pages.numel():
-            raise RuntimeError("src_pages, dst_pages and rows must be one-dimensional and of one length")
-    with _on_device(dev.index):
-        st = lib.mm_kv_copy_pages(_ptr(kv_data), _ptr(kv_param) if kv_param is not None else None, kind, max_pages, L, Hkv, P, 128,
-                                  _ptr(src_pages), _ptr(dst_pages), _ptr(rows) if rows is not None else None, src_pages.numel(),
-                                  _stream_ptr(dev))
-    if st:
-        _lib.check(st, "kv_copy_pages")
-
-
-def _tree_lib():
-    lib = _lib.load()
-    if not hasattr(lib, "mm_paged_prefill_tree"):
-        raise _lib.MicroMixLibraryError("libmicromix_hip.so has no mm_paged_prefill_tree / mm_kv_move_rows: it was built before tree-masked "
-                                        "attention; rebuild it with `python -m micromix_amd.build --force`")
-    return lib
-
-
-def kv_move_rows(kv_data, kv_param, kv_indptr, kv_indices, move_indptr, src_pos, dst_pos):
-    """Within each sequence of a paged cache, move token rows from one logical position to another, for every layer, K and V, every
-    head, in place; returns None.  Bytes only (codes and, for int4 / fp8, the fp16 params): no dequantization.
-
-    Sequence b's moves are m in [move_indptr[b], move_indptr[b + 1]): the row at position src_pos[m] goes to position dst_pos[m], a
-    position being row pos % P of page kv_indices[kv_indptr[b] + pos // P].  All sources of a sequence are read before any of its
-    destinations is written, so a destination may be another move's source -- what packing the accepted path of a tree draft down to
-    contiguous positions needs (PagedKVCache.accept).  At most 64 moves per sequence are performed; a move with src == dst, a position
-    outside the pages the sequence lists or a page index outside the cache is skipped.  The destinations of a sequence must be pairwise
-    distinct, and no page written may be listed by another sequence with moves in the call (include/micromix_hip.h, mm_kv_move_rows).
-    move_indptr [B + 1], src_pos, dst_pos: int32 device tensors.  Runs on the current stream, capture-safe."""
-    lib = _tree_lib()
-    if kv_param is not None:
-        kv_data = _kv_bytes(kv_data)
-    if not (isinstance(kv_data, torch.Tensor) and kv_data.is_cuda):
-        _check_tensor(kv_data, "kv_data", torch.uint8 if kv_param is not None else torch.bfloat16)
-    dev = kv_data.device
-    kind, max_pages, L, Hkv, P, kv_data = _kv_geometry(kv_data, kv_param, dev.index)
-    for n, t in (("kv_indptr", kv_indptr), ("kv_indices", kv_indices), ("move_indptr", move_indptr), ("src_pos", src_pos), ("dst_pos", dst_pos)):
-        if not _ok(t, torch.int32, dev.index):
-            _check_tensor(t, n, torch.int32, dev)
-        if t.dim() != 1:
-            raise RuntimeError(f"{n} must be one-dimensional")
-    B = kv_indptr.numel() - 1
-    if B < 0 or move_indptr.numel() != B + 1:
-        raise RuntimeError("kv_indptr and move_indptr must both have B + 1 entries")
-    if src_pos.numel() != dst_pos.numel():
-        raise RuntimeError("src_pos and dst_pos must be of one length")
-    with _on_device(dev.index):
-        st = lib.mm_kv_move_rows(_ptr(kv_data), _ptr(kv_param) if kv_param is not None else None, kind, max_pages, L, Hkv, P, 128,
-                                 _ptr(kv_indptr), _ptr(kv_indices), B, _ptr(move_indptr), _ptr(src_pos), _ptr(dst_pos), src_pos.numel(),
-                                 _stream_ptr(dev))
-    if st:
-        _lib.check(st, "kv_move_rows")
-
-
-def _verify_lib():
-    lib = _lib.load()
-    if not hasattr(lib, "mm_verify_greedy"):
-        raise _lib.MicroMixLibraryError("libmicromix_hip.so has no mm_argmax_rows / mm_verify_greedy: it was built before draft "
-                                        "verification; rebuild it with `python -m micromix_amd.build --force`")
-    return lib
-
-
-def argmax_rows_workspace_bytes(rows, vocab):
-    """bytes of workspace `argmax_rows` needs for bf16 logits [rows, vocab]; 0 when a row is one part (vocab <= MM_ARGMAX_CHUNK)"""
-    return int(_verify_lib().mm_argmax_rows_workspace_bytes(int(rows), int(vocab)))
-
-
-def argmax_rows(logits, *, out=None, workspace=None):
-    """The index of each row's maximum: logits bf16 [rows, vocab] on the device, last stride 1, any row stride >= vocab (a slice
-    logits[:, :V] of a padded lm_head output, at any 2-byte-aligned offset, is taken as it is: nothing is copied).  Returns int32 [rows]
-    (`out` when given).  The order is torch.argmax's on the CPU: any NaN is greater than +inf, +0 == -0, the lowest index among equal
-    maxima wins.  vocab <= 2^20, rows <= 65535.  workspace: a contiguous device tensor of `argmax_rows_workspace_bytes(rows, vocab)`
-    bytes, uninitialised, allocated when needed and not given (under graph capture pass one).  Runs on the current stream,
-    capture-safe."""
-    lib = _verify_lib()
-    if not isinstance(logits, torch.Tensor):
-        raise TypeError("logits must be a torch.Tensor")
-    if logits.dtype is not torch.bfloat16:
-        raise TypeError(f"logits must be torch.bfloat16, got {logits.dtype}")
-    if not logits.is_cuda:
-        raise RuntimeError("logits must be a device tensor (HIP); the MicroMix ops have no CPU path")
-    if logits.dim() != 2 or logits.size(1) < 1:
-        raise RuntimeError("logits must be [rows, vocab] with vocab >= 1")
-    rows, vocab = logits.shape
-    if vocab > 1 and logits.stride(1) != 1:
-        raise RuntimeError("logits must have unit stride along the vocabulary (the rows may be any distance >= vocab apart)")
-    ld = logits.stride(0) if rows > 1 else vocab
-    if ld < vocab:
-        raise RuntimeError(f"logits rows overlap: row stride {ld} < vocab {vocab}")
-    dev = logits.device
-    if out is None:
-        out = torch.empty((rows,), dtype=torch.int32, device=dev)
-    elif not _ok(out, torch.int32, dev.index) or out.dim() != 1 or out.numel() != rows:
-        _check_tensor(out, "out", torch.int32, dev)
-        raise RuntimeError(f"out must be int32 [{rows}]")
-    workspace, ws_args = _kv_workspace(workspace, argmax_rows_workspace_bytes(rows, vocab), dev)
-    with _on_device(dev.index):
-        st = lib.mm_argmax_rows(_ptr(logits), rows, vocab, ld, _ptr(out), *ws_args, _stream_ptr(dev))
-    if st:
-        _lib.check(st, "argmax_rows")
-    return out
-
-
-def _sample_lib():
-    lib = _lib.load()
-    if not hasattr(lib, "mm_sample_rows"):
-        raise _lib.MicroMixLibraryError("libmicromix_hip.so has no mm_sample_rows: it was built before the sampler; rebuild it with "
-                                        "`python -m micromix_amd.build --force`")
-    return lib
-
-
-def sample_rows_workspace_bytes(rows, vocab):
-    """bytes of workspace `sample_rows` needs for bf16 logits [rows, vocab]: 3 KiB per part of MM_ARGMAX_CHUNK columns of every row
-    and 2 KiB per row"""
-    return int(_sample_lib().mm_sample_rows_workspace_bytes(int(rows), int(vocab)))
-
-
-def _row_param(value, name, dtype, rows, dev):
-    """a per-row parameter of `sample_rows`: None, a device tensor [rows] of `dtype`, or -- outside graph capture -- a Python number,
-    broadcast to one"""
-    if value is None:
-        return None
-    if isinstance(value, torch.Tensor):
-        if not _ok(value, dtype, dev.index) or value.dim() != 1 or value.numel() != rows:
-            _check_tensor(value, name, dtype, dev)
-            raise RuntimeError(f"{name} must be {dtype} [{rows}], one entry per row")
-        return value
-    if isinstance(value, bool) or not isinstance(value, (int, float)):
-        raise TypeError(f"{name} must be None, a number or a {dtype} device tensor [{rows}], got {type(value).__name__}")
-    if dtype is torch.int32 and not isinstance(value, int):
-        raise TypeError(f"{name} must be an int or a torch.int32 device tensor [{rows}], got {type(value).__name__}")
-    if torch.cuda.is_current_stream_capturing():
-        raise RuntimeError(f"{name}: a Python number would be uploaded during graph capture; pass a {dtype} device tensor [{rows}]")
-    if dtype is torch.int32:
-        value = min(max(value, -(1 << 31)), (1 << 31) - 1)
-    return torch.full((rows,), value, dtype=dtype, device=dev)
-
-
-def sample_rows(logits, u, *, temperature=None, top_k=None, top_p=None, min_p=None, out=None, workspace=None):
-    """One token per row, drawn under temperature, top-k, top-p and min-p: logits bf16 [rows, vocab] on the device as `argmax_rows`
-    takes them (any row stride >= vocab, any 2-byte-aligned offset), u fp32 [rows] uniform in [0, 1) -- `torch.rand`, which captures;
-    the library draws no random numbers.  Returns int32 [rows] (`out` when given), ready for `verify_greedy` / `verify_launch` as
-    target_tok: the accepted path and the bonus token are then distributed as the target model's.
-
-    temperature, top_p, min_p: fp32 [rows], top_k: int32 [rows], device tensors read by the kernels only, so one captured graph serves
-    any mix of requests rewritten in place; None: temperature 1, that filter off; a Python number is broadcast to a tensor (outside
-    capture only).  Per row: temperature <= 0 or NaN, or a row whose maximum is NaN or infinite, gives exactly `argmax_rows`' answer.
-    Otherwise w_i = exp((l_i - max) / T); tokens of equal logit form a class and every filter keeps whole classes in descending
-    order: top_k the shortest prefix with >= k tokens (1 <= k < vocab, else off), top_p the shortest prefix with mass >= p times
-    top-k's (p < 1; p <= 0 keeps the top class), min_p the classes with w >= q (0 < q <= 1); the kept set is the shortest of the
-    three; the answer is the first kept index whose cumulative kept mass exceeds u * Z (include/micromix_hip.h, mm_sample_rows).  The
-    result is a function of the inputs alone: the same bits on every run.  vocab <= 2^20, rows <= 65535.  workspace: a contiguous
-    device tensor of `sample_rows_workspace_bytes(rows, vocab)` bytes, uninitialised, allocated when not given (under graph capture
-    pass one).  Runs on the current stream, capture-safe."""
-    lib = _sample_lib()
-    if not isinstance(logits, torch.Tensor):
-        raise TypeError("logits must be a torch.Tensor")
-    if logits.dtype is not torch.bfloat16:
-        raise TypeError(f"logits must be torch.bfloat16, got {logits.dtype}")
-    if not logits.is_cuda:
-        raise RuntimeError("logits must be a device tensor (HIP); the MicroMix ops have no CPU path")
-    if logits.dim() != 2 or logits.size(1) < 1:
-        raise RuntimeError("logits must be [rows, vocab] with vocab >= 1")
-    rows, vocab = logits.shape
-    if vocab > 1 and logits.stride(1) != 1:
-        raise RuntimeError("logits must have unit stride along the vocabulary (the rows may be any distance >= vocab apart)")
-    ld = logits.stride(0) if rows > 1 else vocab
-    if ld < vocab:
-        raise RuntimeError(f"logits rows overlap: row stride {ld} < vocab {vocab}")
-    dev = logits.device
-    if u is None or not isinstance(u, torch.Tensor):
-        raise TypeError(f"u must be a torch.float32 device tensor [{rows}] (torch.rand), got {type(u).__name__}")
-    u = _row_param(u, "u", torch.float32, rows, dev)
-    temperature = _row_param(temperature, "temperature", torch.float32, rows, dev)
-    top_k = _row_param(top_k, "top_k", torch.int32, rows, dev)
-    top_p = _row_param(top_p, "top_p", torch.float32, rows, dev)
-    min_p = _row_param(min_p, "min_p", torch.float32, rows, dev)
-    if out is None:
-        out = torch.empty((rows,), dtype=torch.int32, device=dev)
-    elif not _ok(out, torch.int32, dev.index) or out.dim() != 1 or out.numel() != rows:
-        _check_tensor(out, "out", torch.int32, dev)
-        raise RuntimeError(f"out must be int32 [{rows}]")
-    workspace, ws_args = _kv_workspace(workspace, sample_rows_workspace_bytes(rows, vocab), dev)
-    opt = lambda t: _ptr(t) if t is not None else None
-    with _on_device(dev.index):
-        st = lib.mm_sample_rows(_ptr(logits), rows, vocab, ld, _ptr(u), opt(temperature), opt(top_k), opt(top_p), opt(min_p), _ptr(out),
-                                *ws_args, _stream_ptr(dev))
-    if st:
-        _lib.check(st, "sample_rows")
-    return out
-
-
-def verify_greedy(target_tok, draft_tok, root_tok, qo_indptr, kv_indptr, last_page_len, page_size, *, tree_mask=None, result=None,
-                  move_src=None, move_dst=None):
-    """Greedy (exact-match) verification of tree or chain drafts, one wave per sequence; returns (result, move_src, move_dst).
-
-    Sequence b has the n = qo_indptr[b + 1] - qo_indptr[b] draft nodes of rows qo_indptr[b] .. : draft_tok[t] is a node's token,
-    target_tok[t] the token the target model picks after it (`argmax_rows` or `sample_rows` of its logits), root_tok[b] the token
-    picked after the last committed one.  tree_mask: the int64 words of `paged_prefill(tree_mask=)` -- a node's parent is the highest set
-    bit below its own -- or None for chains.  Starting from root_tok[b], the walk takes the lowest-numbered child of the node just taken
-    whose token is the one wanted, until there is none.  result int32 [B, 66]: [0] the path's length k, [1] the bonus token (the
-    target's choice after the last node taken; root_tok[b] when nothing matched), [2 : 2 + k] the path, the rest -1.  A sequence with
-    n > 64 or root_tok[b] < 0 is a prompt chunk and keeps all: [0] = n, [1] = target_tok of its last row (-1 for n = 0), path entries -1.
-    move_src, move_dst int32 [T], laid over qo_indptr: pass them on as `kv_move_rows(..., move_indptr=qo_indptr, move_src, move_dst)`
-    to pack each path down to the positions base_b .. base_b + k - 1 (base_b = len_b - n, len_b from kv_indptr / last_page_len /
-    page_size).  Every element of the three outputs is written.  All tensors are int32 on one device (token ids as int64 are refused:
-    convert them with .to(torch.int32)).  Runs on the current stream, capture-safe (include/micromix_hip.h, mm_verify_greedy)."""
-    lib = _verify_lib()
-    ints = (("target_tok", target_tok), ("draft_tok", draft_tok), ("root_tok", root_tok), ("qo_indptr", qo_indptr), ("kv_indptr", kv_indptr),
-            ("last_page_len", last_page_len))
-    for n, t in ints:                                      # what torch.argmax and a tokenizer hand over: say what to do about it
-        if isinstance(t, torch.Tensor) and t.dtype is torch.int64:
-            raise TypeError(f"{n} must be torch.int32, got torch.int64: convert it with {n}.to(torch.int32)")
-    if not (isinstance(target_tok, torch.Tensor) and target_tok.is_cuda):
-        _check_tensor(target_tok, "target_tok", torch.int32)
-    dev = target_tok.device
-    for n, t in ints:
-        if not _ok(t, torch.int32, dev.index):
-            _check_tensor(t, n, torch.int32, dev)
-        if t.dim() != 1:
-            raise RuntimeError(f"{n} must be one-dimensional")
-    T, B = target_tok.numel(), root_tok.numel()
-    if draft_tok.numel() != T:
-        raise RuntimeError("target_tok and draft_tok must be of one length")
-    if qo_indptr.numel() != B + 1 or kv_indptr.numel() != B + 1 or last_page_len.numel() != B:
-        raise RuntimeError("qo_indptr and kv_indptr must have B + 1 entries and last_page_len B (B = root_tok.numel())")
-    page_size = int(page_size)
-    if page_size < 1:
-        raise ValueError("page_size must be positive")
-    if tree_mask is not None:
-        if not _ok(tree_mask, torch.int64, dev.index):
-            _check_tensor(tree_mask, "tree_mask", torch.int64, dev)
-        if tree_mask.dim() != 1 or tree_mask.numel() != T:
-            raise RuntimeError(f"tree_mask must be int64 [{T}], one word per row")
-    if result is None:
-        result = torch.empty((B, _lib.MM_VERIFY_STRIDE), dtype=torch.int32, device=dev)
-    elif not _ok(result, torch.int32, dev.index) or tuple(result.shape) != (B, _lib.MM_VERIFY_STRIDE):
-        _check_tensor(result, "result", torch.int32, dev)
-        raise RuntimeError(f"result must be int32 [{B}, {_lib.MM_VERIFY_STRIDE}]")
-    moves = []
-    for n, t in (("move_src", move_src), ("move_dst", move_dst)):
-        if t is None:
-            t = torch.empty((T,), dtype=torch.int32, device=dev)
-        elif not _ok(t, torch.int32, dev.index) or t.dim() != 1 or t.numel() != T:
-            _check_tensor(t, n, torch.int32, dev)
-            raise RuntimeError(f"{n} must be int32 [{T}]")
-        moves.append(t)
-    with _on_device(dev.index):
-        st = lib.mm_verify_greedy(_ptr(target_tok), _ptr(draft_tok), _ptr(root_tok), _ptr(tree_mask) if tree_mask is not None else None,
-                                  _ptr(qo_indptr), T, _ptr(kv_indptr), _ptr(last_page_len), page_size, B, _ptr(result), _ptr(moves[0]),
-                                  _ptr(moves[1]), _stream_ptr(dev))
-    if st:
-        _lib.check(st, "verify_greedy")
-    return result, moves[0], moves[1]
-
-
-def _token_rows(t, name, heads):
-    """(heads, token stride in elements) of q / k / v given as [T, H, 128] or [T, H * 128] whose rows lie contiguous within a token.
-    Stride 0: any stride will do (at most one token); None: the tensor has to be copied (rows not contiguous, an odd stride, a
-    misaligned pointer)"""
-    if t.dim() == 3 and t.size(2) == 128:
-        H, inner = t.size(1), t.stride(2) == 1 and (t.size(1) == 1 or t.stride(1) == 128)
-    elif t.dim() == 2 and t.size(1) % 128 == 0 and t.size(1):
-        H, inner = t.size(1) // 128, t.stride(1) == 1
-    else:
-        raise RuntimeError(f"{name} must be [T, H, 128] or [T, H * 128] bf16")
-    if heads is not None and H != heads:
-        raise RuntimeError(f"{name} has {H} heads, the cache has {heads}")
-    stride = t.stride(0) if t.size(0) > 1 else 0
-    ok = inner and (stride == 0 or stride >= H * 128) and stride % 2 == 0 and t.data_ptr() % 4 == 0
-    return H, (stride if ok else None)
-
-
-def rope_kv_append(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, q, k, v, cos, sin, append_indptr, layer_idx):
-    """RoPE on q and k, then `kv_append` of (rotated k, v), in one launch; returns the rotated q, bf16 [T, Hq, 128] contiguous.
-
-    q, k, v: bf16 [T, H, 128] or [T, H * 128].  Views of one packed [T, (Hq + 2 Hkv) * 128] projection (what FusedQLinear returns) are
-    read in place; so are any three tensors with one common token stride.  Otherwise they are packed into one buffer first (one copy).
-    cos, sin: bf16 [T, 128], or HF's [1, T, 128] / [bsz, q_len, 128] (flattened): row i belongs to flat token i; a row stride is honoured.
-    RoPE is HF's apply_rotary_pos_emb in bf16 arithmetic, q * cos + rotate_half(q) * sin with every op rounded to bf16, bit for bit
-    (include/micromix_hip.h, mm_rope_kv_append).  The cache receives exactly what kv_append(rope(k), v) writes; q is rotated for every
-    token.  Page table, append_indptr and the three cache kinds (int4, fp8 e4m3, bf16) as in `kv_append`.  Runs on the current stream,
-    capture-safe.
-    """
-    lib = _lib.load()
-    dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx)
-    if not _ok(append_indptr, torch.int32, dev.index):
-        _check_tensor(append_indptr, "append_indptr", torch.int32, dev)
-    if append_indptr.numel() != B + 1:
-        raise RuntimeError("append_indptr must have B + 1 entries")
-    for n, t in (("q", q), ("k", k), ("v", v), ("cos", cos), ("sin", sin)):
-        if not (isinstance(t, torch.Tensor) and t.dtype is torch.bfloat16 and t.is_cuda and t.get_device() == dev.index):
-            _check_tensor(t, n, torch.bfloat16, dev)      # contiguity is not asked of these five
-    Hq, sq = _token_rows(q, "q", None)
-    _, sk = _token_rows(k, "k", Hkv)
-    _, sv = _token_rows(v, "v", Hkv)
-    T = q.size(0)
-    if k.size(0) != T or v.size(0) != T:
-        raise RuntimeError("q, k and v must hold the same T tokens")
-    if Hq % Hkv:
-        raise RuntimeError(f"the {Hq} query heads are not a multiple of the cache's {Hkv} kv heads")
-    strides = {sq, sk, sv} - {0}
-    if None in strides or len(strides) > 1 or max(strides, default=Hq * 128) < Hq * 128:
-        packed = torch.cat([q.reshape(T, Hq * 128), k.reshape(T, Hkv * 128), v.reshape(T, Hkv * 128)], dim=1)
-        q, k, v = packed[:, : Hq * 128], packed[:, Hq * 128: (Hq + Hkv) * 128], packed[:, (Hq + Hkv) * 128:]
-        strides = {(Hq + 2 * Hkv) * 128}
-    sq = max(strides, default=Hq * 128)
-    if cos.shape != sin.shape or cos.dim() not in (2, 3) or cos.size(-1) != 128 or cos.numel() != T * 128:
-        raise RuntimeError(f"cos and sin must both be [T = {T}, 128] (or [bsz, q_len, 128] with bsz * q_len = T) bf16")
-    cos, sin = cos.reshape(T, 128), sin.reshape(T, 128)
-    sc = cos.stride(0) if T > 1 else 128
-    if not (cos.stride(1) == 1 and sin.stride(1) == 1 and (T <= 1 or sin.stride(0) == sc) and sc >= 128 and sc % 2 == 0
-            and cos.data_ptr() % 4 == 0 and sin.data_ptr() % 4 == 0):
-        cos, sin, sc = cos.contiguous(), sin.contiguous(), 128
-    q_rot = torch.empty((T, Hq, 128), dtype=torch.bfloat16, device=dev)
-    with _on_device(dev.index):
-        st = lib.mm_rope_kv_append(*kv_args, _ptr(q), _ptr(k), _ptr(v), sq, Hq, _ptr(cos), _ptr(sin), sc, _ptr(append_indptr), T,
-                                   _ptr(q_rot), _stream_ptr(dev))
-    if st:
-        _lib.check(st, "rope_kv_append")
-    return q_rot
-
-
-def _window(window):
-    """HF's sliding_window as the C ABI takes it: None or 0 is no window (the un-windowed entry points), W >= 1 a window of W tokens"""
-    window = 0 if window is None else int(window)
-    if window < 0:
-        raise ValueError("window must be None, 0 (no window) or a positive token count")
-    return window
-
-
-def paged_decode_workspace_bytes(B, Hq, Hkv, max_seq_len, window=None):
-    """bytes of fp32 scratch paged_decode needs for this bound and window (0: one launch, no workspace)"""
-    window = _window(window)
-    if not window:
-        return int(_lib.load().mm_paged_decode_workspace_bytes(int(B), int(Hq), int(Hkv), int(max_seq_len)))
-    return int(_lib.load().mm_paged_decode_window_workspace_bytes(int(B), int(Hq), int(Hkv), int(max_seq_len), window))
-
-
-def paged_decode(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, max_seq_len, sm_scale=None, workspace=None, *,
-                 window=None):
-    """Single-token GQA attention over layer `layer_idx` of a paged cache: q bf16 [B, Hq, 128] -> o bf16 [B, Hq, 128].
-
-    Query head h reads kv head h // (Hq / Hkv) (HF repeat_kv), every cached token, softmax in fp32 with sm_scale (default 1/sqrt(128));
-    a sequence of length 0 gives zeros.  `max_seq_len` bounds the sequence lengths; the split over the tokens depends on it (and B,
-    Hq, Hkv) only, so a captured graph stays valid while the sequences grow up to it.  `workspace` (uint8 / any device tensor of at
-    least paged_decode_workspace_bytes(...) bytes) is allocated here when None -- pass one when capturing a graph.
-    `window` = W (HF's sliding_window; None or 0: none): the query attends the last W tokens of its sequence, its own included.  Only
-    these tokens are read, the split is laid over W tokens, and page-table entries below the window may be -1.
-    The cache is int4, fp8 (e4m3) or bf16, told apart as in `kv_append`; over an fp8 cache the result equals, bit for bit, that over a
-    bf16 cache holding the dequantized values.
-    """
-    lib = _lib.load()
-    window = _window(window)
-    dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, q)
-    if q.dim() != 3 or q.size(0) != B or q.size(2) != 128:
-        raise RuntimeError(f"q must be [B = {B}, Hq, 128] bf16")
-    Hq = q.size(1)
-    if Hq % Hkv:
-        raise RuntimeError(f"the {Hq} query heads are not a multiple of the cache's {Hkv} kv heads")
-    max_seq_len = int(max_seq_len)
-    if max_seq_len < 0:
-        raise RuntimeError("max_seq_len must be >= 0")
-    need = paged_decode_workspace_bytes(B, Hq, Hkv, max_seq_len, window) if B else 0
-    workspace, ws_args = _kv_workspace(workspace, need, dev)
-    o = torch.empty((B, Hq, 128), dtype=torch.bfloat16, device=dev)
-    scale = _sm_scale(sm_scale)
-    with _on_device(dev.index):
-        if window:
-            st = lib.mm_paged_decode_window(_ptr(q), *kv_args, Hq, max_seq_len, scale, *ws_args, _ptr(o), _stream_ptr(dev), window)
-        else:
-            st = lib.mm_paged_decode(_ptr(q), *kv_args, Hq, max_seq_len, scale, *ws_args, _ptr(o), _stream_ptr(dev))
-    if st:
-        _lib.check(st, "paged_decode")
-    return o
-
-
-def _shared_lib():
-    lib = _lib.load()
-    if not hasattr(lib, "mm_paged_decode_shared"):
-        raise _lib.MicroMixLibraryError("libmicromix_hip.so has no mm_paged_decode_shared: it was built before shared-prefix decode; "
-                                        "rebuild it with `python -m micromix_amd.build --force`")
-    return lib
-
-
-def paged_decode_shared_workspace_bytes(B, Hq, Hkv, max_shared_len, max_suffix_len):
-    """bytes of fp32 scratch paged_decode_shared needs for these bounds: the partials of its prefix and tail chunks (never 0 for B > 0
-    and sizes the call takes; 0 for sizes it refuses)"""
-    return int(_shared_lib().mm_paged_decode_shared_workspace_bytes(int(B), int(Hq), int(Hkv), int(max_shared_len), int(max_suffix_len)))
-
-
-def paged_decode_shared(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, group_indptr, group_members, shared_len,
-                        max_shared_len, max_suffix_len, sm_scale=None, workspace=None, *, out=None):
-    """`paged_decode` for a batch in which groups of sequences hold their leading pages in common: q bf16 [B, Hq, 128] -> o bf16
-    [B, Hq, 128], the same function (every sequence attends all of its tokens), within the same budget but not the same bits.
-
-    The shared tokens of a group are walked once per slab of 16 // (Hq // Hkv) members instead of once per member; each sequence's own
-    tail is walked as in `paged_decode`.  group_indptr [B + 1], group_members [B], shared_len [B]: int32 device tensors.  Group j is
-    group_members[group_indptr[j] : group_indptr[j + 1]], trailing unused groups are empty (group_indptr[j] = B), group_members is a
-    permutation of range(B), and shared_len[b] -- the same for every member of a group, at most each member's length, any value, not
-    only multiples of the page size -- counts the leading tokens b has on the same pages as its group (include/micromix_hip.h,
-    mm_paged_decode_shared, also for what happens when the tensors break the rules: wrong results for those sequences, no access outside
-    the tensors).  `PagedKVCache.share_groups()` derives one grouping from a page table; a caller who knows better (a beam tree whose
-    branches share different depths) passes its own.
-    `max_shared_len` bounds the shared counts, `max_suffix_len` the tails; the launches depend on them (and B, Hq, Hkv) only, so a
-    captured graph stays valid while lengths and groups change within them.  `workspace` (at least
-    paged_decode_shared_workspace_bytes(...) bytes; always needed) is allocated here when None -- pass one when capturing a graph.
-    `out`: a bf16 [B, Hq, 128] tensor to write instead of a new one.  No sliding window.
-    """
-    lib = _shared_lib()
-    dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, q)
-    if q.dim() != 3 or q.size(0) != B or q.size(2) != 128:
-        raise RuntimeError(f"q must be [B = {B}, Hq, 128] bf16")
-    Hq = q.size(1)
-    if Hq % Hkv:
-        raise RuntimeError(f"the {Hq} query heads are not a multiple of the cache's {Hkv} kv heads")
-    for n, t, size in (("group_indptr", group_indptr, B + 1), ("group_members", group_members, B), ("shared_len", shared_len, B)):
-        if not _ok(t, torch.int32, dev.index):
-            _check_tensor(t, n, torch.int32, dev)
-        if t.dim() != 1 or t.numel() != size:
-            raise RuntimeError(f"{n} must be a one-dimensional int32 tensor of {size} entries (B = {B})")
-    max_shared_len, max_suffix_len = int(max_shared_len), int(max_suffix_len)
-    if min(max_shared_len, max_suffix_len) < 0 or max(max_shared_len, max_suffix_len) > 1 << 29:
-        raise RuntimeError("max_shared_len and max_suffix_len must lie in [0, 2^29]")
-    need = paged_decode_shared_workspace_bytes(B, Hq, Hkv, max_shared_len, max_suffix_len) if B and Hq // Hkv <= 16 else 0
-    workspace, ws_args = _kv_workspace(workspace, need, dev)
-    if out is None:
-        out = torch.empty((B, Hq, 128), dtype=torch.bfloat16, device=dev)
-    elif not _ok(out, torch.bfloat16, dev.index) or tuple(out.shape) != (B, Hq, 128):
-        _check_tensor(out, "out", torch.bfloat16, dev)
-        raise RuntimeError(f"out must be [{B}, {Hq}, 128] bf16")
-    scale = _sm_scale(sm_scale)
-    with _on_device(dev.index):
-        st = lib.mm_paged_decode_shared(_ptr(q), *kv_args, Hq, _ptr(group_indptr), _ptr(group_members), _ptr(shared_len), max_shared_len,
-                                        max_suffix_len, scale, *ws_args, _ptr(out), _stream_ptr(dev))
-    if st:
-        _lib.check(st, "paged_decode_shared")
-    return out
-
-
-def paged_prefill_workspace_bytes(T, B, Hq, Hkv, max_seq_len, window=None):
-    """bytes of fp32 scratch paged_prefill needs for T query tokens over B sequences within max_seq_len, under `window` (0: one launch,
-    no workspace)"""
-    window = _window(window)
-    if not window:
-        return int(_lib.load().mm_paged_prefill_workspace_bytes(int(T), int(B), int(Hq), int(Hkv), int(max_seq_len)))
-    return int(_lib.load().mm_paged_prefill_window_workspace_bytes(int(T), int(B), int(Hq), int(Hkv), int(max_seq_len), window))
-
-
-def paged_prefill(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, qo_indptr, layer_idx, max_seq_len, sm_scale=None,
-                  workspace=None, *, window=None, tree_mask=None):
-    """Causal GQA attention of T new query tokens over layer `layer_idx` of a paged cache: q bf16 [T, Hq, 128] -> o bf16 [T, Hq, 128].
-
-    qo_indptr (int32 [B + 1], qo_indptr[B] = T) splits the queries among the sequences, as kv_append's append_indptr does; pass the
-    same array.  The page table already counts the new tokens, and the mask is aligned bottom-right: sequence b's j-th new token sits
-    at position len_b - n_b + j and attends positions 0 .. that one.  Softmax in fp32 with sm_scale (default 1/sqrt(128)).
-    `max_seq_len` bounds the sequence lengths; the grid and the split over the tokens depend on it (and T, B, Hq, Hkv) only, so a
-    captured graph stays valid over later steps with the same T.  `workspace` (any contiguous device tensor of at least
-    paged_prefill_workspace_bytes(...) bytes) is allocated here when None -- pass one when capturing a graph.
-    `window` = W (HF's sliding_window; None or 0: none): the token at position p attends positions max(0, p - W + 1) .. p; the kv tiles
-    below a query tile's windows are not read, and page-table entries below every window may be -1.
-    `tree_mask` (int64 [T] device tensor, one word per query token; None: the causal mask): verification of a tree draft.  With
-    base_b = len_b - n_b, sequence b's j-th new token attends every position below base_b and new slot base_b + i exactly when i <= j
-    and bit i of its word is set (bits above j are ignored; set bit j for a token to attend itself).  A sequence with more than 64 new
-    tokens ignores its words and is attended causally.  Words (2 << j) - 1 give the bits of the causal call.  No window form: `window`
-    together with `tree_mask` is a ValueError.  The tensor is read by the kernel only, so a captured graph replays with other trees
-    written into it.  `PagedKVCache.tree_mask` builds the words from parent indices.
-    The cache is int4, fp8 (e4m3) or bf16, told apart as in `kv_append`; fp8 runs p.V on bf16(p * scale_v) times the codes, as int4.
-    """
-    lib = _lib.load() if tree_mask is None else _tree_lib()
-    window = _window(window)
-    if window and tree_mask is not None:
-        raise ValueError("paged_prefill has no sliding-window form of the tree mask: pass window or tree_mask, not both")
-    dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, q)
-    if not _ok(qo_indptr, torch.int32, dev.index):
-        _check_tensor(qo_indptr, "qo_indptr", torch.int32, dev)
-    if qo_indptr.numel() != B + 1:
-        raise RuntimeError("qo_indptr must have B + 1 entries (B = last_page_len.numel())")
-    if q.dim() != 3 or q.size(2) != 128:
-        raise RuntimeError("q must be [T, Hq, 128] bf16, T = qo_indptr[-1]")
-    T, Hq = q.size(0), q.size(1)
-    if Hq % Hkv:
-        raise RuntimeError(f"the {Hq} query heads are not a multiple of the cache's {Hkv} kv heads")
-    if tree_mask is not None:
-        if not _ok(tree_mask, torch.int64, dev.index):
-            _check_tensor(tree_mask, "tree_mask", torch.int64, dev)
-        if tree_mask.dim() != 1 or tree_mask.numel() != T:
-            raise RuntimeError(f"tree_mask must be a one-dimensional int64 tensor of T = {T} words")
-    max_seq_len = int(max_seq_len)
-    if max_seq_len < 0:
-        raise RuntimeError("max_seq_len must be >= 0")
-    need = paged_prefill_workspace_bytes(T, B, Hq, Hkv, max_seq_len, window) if B and T else 0
-    workspace, ws_args = _kv_workspace(workspace, need, dev)
-    o = torch.empty((T, Hq, 128), dtype=torch.bfloat16, device=dev)
-    scale = _sm_scale(sm_scale)
-    with _on_device(dev.index):
-        if tree_mask is not None:
-            st = lib.mm_paged_prefill_tree(_ptr(q), _ptr(qo_indptr), T, *kv_args, Hq, max_seq_len, scale, *ws_args, _ptr(o),
-                                           _stream_ptr(dev), _ptr(tree_mask))
-        elif window:
-            st = lib.mm_paged_prefill_window(_ptr(q), _ptr(qo_indptr), T, *kv_args, Hq, max_seq_len, scale, *ws_args, _ptr(o),
-                                             _stream_ptr(dev), window)
-        else:
-            st = lib.mm_paged_prefill(_ptr(q), _ptr(qo_indptr), T, *kv_args, Hq, max_seq_len, scale, *ws_args, _ptr(o), _stream_ptr(dev))
-    if st:
-        _lib.check(st, "paged_prefill")
-    return o
-
-
-# ---- sparse MoE block (include/micromix_hip.h, mm_moe_*; micromix_amd/moe.py assembles the block) ----
-
-def _moe_tensor(t, name, dtype, dev, shape=None):
-    if not _ok(t, dtype, dev.index):
-        _check_tensor(t, name, dtype, dev)
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise RuntimeError(f"{name} must be {list(shape)}, got {list(t.shape)}")
-    return t
-
-
-def moe_route(logits, top_k, *, topk_ids=None, topk_w=None):
-    """Top-k routing of the gate logits: logits bf16 [T, E] -> (topk_ids int32 [T, top_k], topk_w bf16 [T, top_k]).
-
-    Not an export of the reference module; the same numbers as its softmax(float) -> topk -> renormalise -> cast
-    (qMixtralLayer.py:422-426): the top_k largest logits in descending order, equal logits in ascending expert index (torch.topk
-    leaves ties unspecified), w_j = exp(l_j - max) / sum over the selected, in fp32, rounded to bf16.  1 <= top_k <= 8,
-    top_k <= E <= 64.  Outputs are allocated unless passed in.  Runs on the current stream, capture-safe.
-    """
-    lib = _lib.load()
-    if not (isinstance(logits, torch.Tensor) and logits.is_cuda and _ok(logits, torch.bfloat16, logits.get_device())):
-        _check_tensor(logits, "logits", torch.bfloat16)
-    if logits.dim() != 2:
-        raise RuntimeError("logits must be [T, E] bf16")
-    dev, (T, E), top_k = logits.device, logits.shape, int(top_k)
-    topk_ids = torch.empty((T, top_k), dtype=torch.int32, device=dev) if topk_ids is None else _moe_tensor(topk_ids, "topk_ids", torch.int32, dev, (T, top_k))
-    topk_w = torch.empty((T, top_k), dtype=torch.bfloat16, device=dev) if topk_w is None else _moe_tensor(topk_w, "topk_w", torch.bfloat16, dev, (T, top_k))
-    with _on_device(dev.index):
-        st = lib.mm_moe_route(_ptr(logits), T, E, top_k, _ptr(topk_ids), _ptr(topk_w), _stream_ptr(dev))
-    if st:
-        _lib.check(st, "moe_route")
-    return topk_ids, topk_w
-
-
-def moe_plan(topk_ids, num_experts, *, expert_offsets=None, sorted_token=None, slot_of=None):
-    """The dispatch plan of routed tokens: topk_ids int32 [T, top_k] -> (expert_offsets int32 [E + 1], sorted_token int32 [T * top_k],
-    slot_of int32 [T, top_k]), a stable counting sort of the (token, k-slot) pairs by expert.
-
-    Expert e owns the slots [expert_offsets[e], expert_offsets[e + 1]); within an expert the slots run by ascending token;
-    sorted_token[s] is the token of slot s, slot_of[t, j] the slot of token t's j-th choice.  An id outside [0, E) is not counted and
-    gets slot_of = -1; the slots left over then hold sorted_token = -1.  Deterministic; runs on the current stream, capture-safe.
-    """
-    lib = _lib.load()
-    if not (isinstance(topk_ids, torch.Tensor) and topk_ids.is_cuda and _ok(topk_ids, torch.int32, topk_ids.get_device())):
-        _check_tensor(topk_ids, "topk_ids", torch.int32)
-    if topk_ids.dim() != 2:
-        raise RuntimeError("topk_ids must be [T, top_k] int32")
-    dev, (T, top_k), E = topk_ids.device, topk_ids.shape, int(num_experts)
-    i32 = torch.int32
-    if expert_offsets is None:      # without tokens the entry does no device work: the offsets are all zero then
-        expert_offsets = (torch.empty if T else torch.zeros)((max(E, 0) + 1,), dtype=i32, device=dev)
-    else:
-        _moe_tensor(expert_offsets, "expert_offsets", i32, dev, (E + 1,))
-        if T == 0:
-            expert_offsets.zero_()
-    sorted_token = torch.empty((T * top_k,), dtype=i32, device=dev) if sorted_token is None else _moe_tensor(sorted_token, "sorted_token", i32, dev, (T * top_k,))
-    slot_of = torch.empty((T, top_k), dtype=i32, device=dev) if slot_of is None else _moe_tensor(slot_of, "slot_of", i32, dev, (T, top_k))
-    with _on_device(dev.index):
-        st = lib.mm_moe_plan(_ptr(topk_ids), T, E, top_k, _ptr(expert_offsets), _ptr(sorted_token), _ptr(slot_of), _stream_ptr(dev))
-    if st:
-        _lib.check(st, "moe_plan")
-    return expert_offsets, sorted_token, slot_of
-
-
-def moe_gather(x, sorted_token, *, out=None):
-    """x bf16 [T, H], sorted_token int32 [n_rows] -> x_sorted bf16 [n_rows, H] with x_sorted[s] = x[sorted_token[s]] (H a multiple
-    of 8).  A row whose sorted_token lies outside [0, T) is left as it was (uninitialised in an output allocated here).  Runs on the
-    current stream, capture-safe."""
-    lib = _lib.load()
-    if not (isinstance(x, torch.Tensor) and x.is_cuda and _ok(x, torch.bfloat16, x.get_device())):
-        _check_tensor(x, "x", torch.bfloat16)
-    if x.dim() != 2:
-        raise RuntimeError("x must be [T, H] bf16")
-    dev, (T, H) = x.device, x.shape
-    _moe_tensor(sorted_token, "sorted_token", torch.int32, dev)
-    n_rows = sorted_token.numel()
-    out = torch.empty((n_rows, H), dtype=torch.bfloat16, device=dev) if out is None else _moe_tensor(out, "out", torch.bfloat16, dev, (n_rows, H))
-    with _on_device(dev.index):
-        st = lib.mm_moe_gather(_ptr(x), _ptr(sorted_token), T, n_rows, H, _ptr(out), _stream_ptr(dev))
-    if st:
-        _lib.check(st, "moe_gather")
-    return out
-
-
-def moe_combine(y_sorted, topk_ids, topk_w, slot_of, *, out=None):
-    """The weighted sum of every token's expert outputs: y_sorted bf16 [T * top_k, H] (rows in plan order), topk_ids int32, topk_w bf16,
-    slot_of int32, all [T, top_k] -> out bf16 [T, H].
-
-    Per token its entries are taken in ascending expert id, c = bf16(y * w), acc = bf16(acc + c) from +0.0: bit for bit what the
-    reference's zeros + index_add_ expert by expert leaves (qMixtralLayer.py:428-450), whatever order topk_ids lists the experts in.
-    Entries with slot_of = -1 are skipped; every row of out is written.  Runs on the current stream, capture-safe.
-    """
-    lib = _lib.load()
-    if not (isinstance(y_sorted, torch.Tensor) and y_sorted.is_cuda and _ok(y_sorted, torch.bfloat16, y_sorted.get_device())):
-        _check_tensor(y_sorted, "y_sorted", torch.bfloat16)
-    dev = y_sorted.device
-    _moe_tensor(topk_ids, "topk_ids", torch.int32, dev)
-    if topk_ids.dim() != 2 or y_sorted.dim() != 2 or y_sorted.size(0) != topk_ids.numel():
-        raise RuntimeError("topk_ids must be [T, top_k] and y_sorted [T * top_k, H]")
-    T, top_k = topk_ids.shape
-    H = y_sorted.size(1)
-    _moe_tensor(topk_w, "topk_w", torch.bfloat16, dev, (T, top_k))
-    _moe_tensor(slot_of, "slot_of", torch.int32, dev, (T, top_k))
-    out = torch.empty((T, H), dtype=torch.bfloat16, device=dev) if out is None else _moe_tensor(out, "out", torch.bfloat16, dev, (T, H))
-    with _on_device(dev.index):
-        st = lib.mm_moe_combine(_ptr(y_sorted), _ptr(topk_ids), _ptr(topk_w), _ptr(slot_of), T, top_k, H, _ptr(out), _stream_ptr(dev))
-    if st:
-        _lib.check(st, "moe_combine")
-    return out
-
-
-# ---- device-sized grouped launches: the expert quantizer and GEMM of a capturable MoE block (mm_moe_quantize / mm_moe_matmul) ----
-
-class MoEExpertTable:
-    """`mm_moe_expert[E]` in device memory (include/micromix_hip.h) with the tensors it points to kept alive.  `tensor` int64 [E, 8]:
-    per expert the addresses of (reorder_index, BN, BS, BO, SFBN, SFBS, SFBO, bias or 0).  Built once, by moe_expert_table."""
-    __slots__ = ("tensor", "E", "N", "K", "split", "wmode", "has_bias", "_keep")
-
-
-def moe_expert_table(reorder_indices, Bs, KN, KS, KO, biases=None):
-    """One table per layer of the experts: reorder_indices[e] int16 [K], Bs[e] = (BN, BS, BO, SFBN, SFBS, SFBO) as matmul_grouped takes
-    them, biases[e] bf16 [N] or None.  All experts share N, the (KN, KS, KO) split and the weight mode.  The addresses are copied to the
-    device here -- build the table once (SparseMoEBlock.__init__), never per call."""
-    E = len(Bs)
-    if not (1 <= E <= 64) or len(reorder_indices) != E or (biases is not None and len(biases) != E):
-        raise ValueError("1 <= E <= 64 experts, one reorder index (and bias entry) each")
-    KN, KS, KO = int(KN), int(KS), int(KO)
-    K = KN + KS + KO
-    _check_split(KN, KS, KO, None, "moe_expert_table")
-    dev = Bs[0][0].device
-    index, u8 = dev.index, torch.uint8
-    N = Bs[0][0].size(0)
-    same = Bs[0][1].size(1) == KS // 4 * 3 and Bs[0][2].size(1) == KO          # (as matmul_grouped tells the weight mode)
-    wmode = _lib.MM_W_MATCH if same else _lib.MM_W_FP4
-    wb = (KN // 2, KS // 4 * 3 if same else KS // 2, KO if same else KO // 2)
-    if tuple(tuple(t.shape) for t in Bs[0][:3]) != tuple((N, w) for w in wb):
-        raise RuntimeError("the packed weights of expert 0 do not match the split in either weight mode")
-    shapes = tuple(tuple(t.shape) for t in Bs[0])
-    rows, keep = [], []
-    for e, (idx, B) in enumerate(zip(reorder_indices, Bs)):
-        if not _ok(idx, torch.int16, index) or idx.numel() != K:
-            _check_tensor(idx, f"reorder_index[{e}]", torch.int16, dev)
-            raise RuntimeError(f"expert {e}: the reorder index must have {K} entries")
-        for t in B:
-            if not _ok(t, u8, index):
-                _check_tensor(t, f"expert {e} weight operand", u8, dev)
-        if tuple(tuple(t.shape) for t in B[:3]) != shapes[:3] or any(t.numel() < _sf_bytes_w(N, k) for t, k in zip(B[3:], (KN, KS, KO))):
-            raise RuntimeError(f"expert {e}: packed weights do not match N / split / weight mode of expert 0")
-        bias = biases[e] if biases is not None else None
-        if bias is not None and (not _ok(bias, torch.bfloat16, index) or bias.numel() != N):
-            raise RuntimeError(f"expert {e}: bias must be a bfloat16 tensor with N elements")
-        rows.append([idx.data_ptr()] + [t.data_ptr() if t.numel() else 0 for t in B] + [bias.data_ptr() if bias is not None else 0])
-        keep.append((idx, B, bias))
-    tab = MoEExpertTable()
-    tab.tensor = torch.tensor(rows, dtype=torch.int64).to(dev)
-    tab.E, tab.N, tab.K, tab.split, tab.wmode, tab._keep = E, N, K, (KN, KS, KO), wmode, keep
-    tab.has_bias = biases is not None and any(b is not None for b in biases)
-    return tab
-
-
-def moe_sf_bytes(n, E, Kseg):
-    """bytes of a packed scale tensor for n rows of E experts: n // 128 + E tiles of 128 rows (include/micromix_hip.h)"""
-    return (n // 128 + E) * 128 * (Kseg // 32)
-
-
-def _moe_outputs(out, n, E, widths, split, dev):
-    """the 6-tuple a MoE quantizer fills: allocated, or the caller's `out` checked"""
-    u8 = torch.uint8
-    if out is None:
-        return tuple(torch.empty((n, w), dtype=u8, device=dev) for w in widths) + \
-            tuple(torch.empty((moe_sf_bytes(n, E, k),), dtype=u8, device=dev) for k in split)
-    for t, w in zip(out[:3], widths):
-        _moe_tensor(t, "packed output", u8, dev, (n, w))
-    for t, k in zip(out[3:], split):
-        if _moe_tensor(t, "scale output", u8, dev).numel() < moe_sf_bytes(n, E, k):
-            raise RuntimeError("a scale output is smaller than moe_sf_bytes(n, E, Kseg)")
-    return out
-
-
-def moe_quantize(src, row_of_slot, expert_offsets, table, n=None, *, mode="x", out=None):
-    """The expert quantizer with the row counts read on the device: for every slot s that an expert owns (expert_offsets int32 [E + 1],
-    moe_plan's), row row_of_slot[s] of src bf16 [rows, K] -- row s itself with row_of_slot=None -- quantized with that expert's reorder
-    index (table: moe_expert_table).  Returns ONE 6-tuple (oN, oS, oO, sfN, sfS, sfO) for all experts: packed rows in slot order
-    [n, .], scale tensors of moe_sf_bytes(n, E, Kseg) bytes with expert e's run at tile expert_offsets[e] // 128 + e; bytes of slots and
-    tiles that no expert owns are left as they were.  n defaults to len(row_of_slot) (or src's rows).  mode "x" (mixed) or "w4".
-    Byte for byte reorder_quantize_x_grouped's per-expert tensors laid end to end.  No host sync; capture-safe."""
-    lib = _lib.load()
-    if not (isinstance(src, torch.Tensor) and src.is_cuda and _ok(src, torch.bfloat16, src.get_device())):
-        _check_tensor(src, "src", torch.bfloat16)
-    if src.dim() != 2:
-        raise RuntimeError("src must be [rows, K] bf16")
-    dev, (src_rows, K) = src.device, src.shape
-    if mode not in ("x", "w4"):
-        raise ValueError("mode must be 'x' or 'w4'")
-    w4 = mode == "w4"
-    E, (KN, KS, KO) = table.E, table.split
-    if K != table.K:
-        raise RuntimeError(f"src must be [rows, {table.K}]")
-    _moe_tensor(expert_offsets, "expert_offsets", torch.int32, dev, (E + 1,))
-    if row_of_slot is not None:
-        _moe_tensor(row_of_slot, "row_of_slot", torch.int32, dev)
-        n = row_of_slot.numel() if n is None else int(n)
-        if row_of_slot.numel() < n:
-            raise RuntimeError("row_of_slot must have n entries")
-    else:
-        n = src_rows if n is None else int(n)
-    out = _moe_outputs(out, n, E, (KN // 2, KS // 2 if w4 else KS // 4 * 3, KO // 2 if w4 else KO), (KN, KS, KO), dev)
-    with _on_device(dev.index):
-        st = lib.mm_moe_quantize(_ptr(src), _ptr(row_of_slot) if row_of_slot is not None else None, _ptr(expert_offsets), _ptr(table.tensor), E, n,
-                                 src_rows, K, KN, KS, KO, _lib.MM_QUANT_W4 if w4 else _lib.MM_QUANT_MIXED, *(_ptr(t) for t in out), _stream_ptr(dev))
-    if st:
-        _lib.check(st, "moe_quantize")
-    return tuple(out)
-
-
-def moe_activate_quantize(a, b, expert_offsets, table, *, out=None, h_out=None):
-    """The experts' activation and the quantizer of their down-projection in one launch: a, b bf16 [n, K] in slot order (the outputs of
-    moe_matmul for w1 and w3), and for every slot s that an expert owns h[s] = bf16(bf16(silu(a[s])) * b[s]) -- torch's bf16
-    `F.silu(a) * b` except where the device exp2 / rcp move a value across a bf16 rounding boundary (include/micromix_hip.h) --
-    quantized as moe_quantize(h, None, expert_offsets, table) would.  Returns that 6-tuple, byte for byte; `out=` takes a 6-tuple to
-    fill.  h_out: None, or a bf16 [n, K] tensor (not a or b) that also receives h.  Slots no expert owns are left as they were in
-    every output.  Mixed mode only.  No host sync, no allocation sized by device data; capture-safe."""
-    lib = _lib.load()
-    if not (isinstance(a, torch.Tensor) and a.is_cuda and _ok(a, torch.bfloat16, a.get_device())):
-        _check_tensor(a, "a", torch.bfloat16)
-    if a.dim() != 2:
-        raise RuntimeError("a must be [n, K] bf16")
-    dev, (n, K) = a.device, a.shape
-    _moe_tensor(b, "b", torch.bfloat16, dev, (n, K))
-    E, (KN, KS, KO) = table.E, table.split
-    if K != table.K:
-        raise RuntimeError(f"a and b must be [n, {table.K}]")
-    _moe_tensor(expert_offsets, "expert_offsets", torch.int32, dev, (E + 1,))
-    if h_out is not None:
-        _moe_tensor(h_out, "h_out", torch.bfloat16, dev, (n, K))
-        if h_out.data_ptr() in (a.data_ptr(), b.data_ptr()) and n:
-            raise RuntimeError("h_out must not be a or b")
-    out = _moe_outputs(out, n, E, (KN // 2, KS // 4 * 3, KO), (KN, KS, KO), dev)
-    with _on_device(dev.index):
-        st = lib.mm_moe_activate_quantize(_ptr(a), _ptr(b), _ptr(expert_offsets), _ptr(table.tensor), E, n, K, KN, KS, KO, *(_ptr(t) for t in out),
-                                          _ptr(h_out) if h_out is not None else None, _stream_ptr(dev))
-    if st:
-        _lib.check(st, "moe_activate_quantize")
-    return tuple(out)
-
-
-def moe_matmul_supported(max_rows, table):
-    """False where moe_matmul would answer "unsupported configuration" (very long K: take matmul_grouped there)"""
-    return bool(_lib.load().mm_moe_matmul_supported(int(max_rows), table.N, *table.split, table.wmode))
-
-
-def moe_matmul(A, expert_offsets, table, max_rows, *, rounding="reference", out=None):
-    """The expert GEMM with the row counts read on the device: A = moe_quantize's 6-tuple (mode "x"), out bf16 [n, N] with the rows of
-    expert e = matmul_grouped's output for that expert (bit for bit wherever both split K over the same number of waves, and always when
-    K <= 512: include/micromix_hip.h), weights and biases from `table`.  max_rows: a bound on any expert's
-    rows that the caller vouches for (T in a MoE block); an expert with more rows is skipped, its rows of `out` left as they were, as
-    are the rows from expert_offsets[E] on.  At most two launches, whatever E.  No host sync; capture-safe."""
-    lib = _lib.load()
-    if rounding not in ("reference", "fused"):
-        _round_flags(rounding)
-    flags = _lib.MM_ROUND_PER_SEGMENT if rounding == "reference" else _lib.MM_ROUND_ONCE
-    dev = A[0].device
-    E, N, (KN, KS, KO) = table.E, table.N, table.split
-    n = A[0].size(0)
-    u8 = torch.uint8
-    for t, w in zip(A[:3], (KN // 2, KS // 4 * 3, KO)):
-        _moe_tensor(t, "activation segment", u8, dev, (n, w))
-    for t, k in zip(A[3:], (KN, KS, KO)):
-        if _moe_tensor(t, "activation scales", u8, dev).numel() < moe_sf_bytes(n, E, k):
-            raise RuntimeError("an activation scale tensor is smaller than moe_sf_bytes(n, E, Kseg)")
-    _moe_tensor(expert_offsets, "expert_offsets", torch.int32, dev, (E + 1,))
-    out = torch.empty((n, N), dtype=torch.bfloat16, device=dev) if out is None else _moe_tensor(out, "out", torch.bfloat16, dev, (n, N))
-    with _on_device(dev.index):
-        st = lib.mm_moe_matmul(*(_ptr(t) for t in A), _ptr(expert_offsets), _ptr(table.tensor), E, n, int(max_rows), N, KN, KS, KO, table.wmode,
-                               flags, _ptr(out), _stream_ptr(dev))
-    if st:
-        _lib.check(st, "moe_matmul")
-    return out
-
-
-# ---- w1 | w3, silu * mul and w2's quantizer in one expert launch (mm_moe_gate_up_activate) ----
-
-def permute_packed_rows(packed6, perm):
-    """Rows of a packed weight (BN, BS, BO, SFBN, SFBS, SFBO) in another order: row j of the result is row perm[j] of the input.
-
-    Weights are quantized per output row, so this is a pure byte shuffle, equal byte for byte to quantizing the row-permuted weight:
-    the packed codes move as rows; a scale tensor is tiled per 128 rows, and inside a tile's 512-byte atom of one 128-column slab row
-    r sits at (r & 31) * 16 + ((r >> 5) & 3) * 4 (sf_offset, csrc/mx_common.h).  The row count must be a multiple of 128 (whole scale
-    tiles) and perm a permutation of it.  Plain torch on any device, CPU tensors included; returns new tensors."""
-    n = packed6[0].size(0)
-    perm = torch.as_tensor(perm).to(device=packed6[0].device, dtype=torch.long).reshape(-1)
-    if n % 128 or perm.numel() != n or (n and not torch.equal(torch.sort(perm).values, torch.arange(n, device=perm.device))):
-        raise ValueError("permute_packed_rows: the rows must be a multiple of 128 and perm a permutation of them")
-    out = [t.index_select(0, perm) if t.numel() else t.clone() for t in packed6[:3]]
-    for t in packed6[3:]:
-        if t.numel() == 0:
-            out.append(t.clone())
-            continue
-        if t.numel() % (n * 4):
-            raise ValueError("permute_packed_rows: a scale tensor is not whole 128-row tiles of these rows")
-        atoms = t.numel() // (n * 4)                                  # 128-column slabs of the segment
-        rows = t.reshape(n // 128, atoms, 32, 4, 4).permute(0, 3, 2, 1, 4).reshape(n, atoms * 4)        # [row, its scale bytes]
-        rows = rows.index_select(0, perm)
-        out.append(rows.reshape(n // 128, 4, 32, atoms, 4).permute(0, 3, 2, 1, 4).reshape(-1).contiguous())
-    return tuple(out)
-
-
-def moe_gate_up_table(reorder_indices1, w1s, w3s, reorder_indices2, split1, split2, *, biases1=None, biases3=None):
-    """The device table of `moe_gate_up_activate`: per expert ONE packed fp4 weight of N = 2 I rows made from w1s[e] and w3s[e] (the
-    6-tuples moe_expert_table takes).  Row j of the gate half is w1 row reorder_indices2[e][j], row j of the up half is w3 row
-    reorder_indices2[e][j] -- the expert's w2 reorder index moves into the weight, because the fused epilogue quantizes 128 consecutive
-    features into one segment of w2's K split -- and the halves are interleaved per 128 rows (interleave_gate_up).  reorder_indices1[e]
-    is the index of the first quantizer (w1's), split1 / split2 the (KN, KS, KO) splits of w1 and of w2.  Returns a MoEExpertTable with
-    N = 2 I and no bias whose weights are NEW tensors that it keeps alive: while the originals stay in use elsewhere, the memory held
-    for w1 / w3 doubles.  Raises ValueError for biases on w1 / w3, weights that are not fp4 (MM_W_FP4), I not a multiple of 128 or an
-    entry of split2 that is not a multiple of 128 (or split2 not adding up to I)."""
-    E = len(w1s)
-    if not (1 <= E <= 64) or len(w3s) != E or len(reorder_indices1) != E or len(reorder_indices2) != E:
-        raise ValueError("moe_gate_up_table: 1 <= E <= 64 experts with w1, w3 and both reorder indices each")
-    if any(b is not None for bs in (biases1, biases3) if bs is not None for b in bs):
-        raise ValueError("moe_gate_up_table: w1 / w3 must have no bias (the fused epilogue adds none)")
-    KN, KS, KO = (int(k) for k in split1)
-    split2 = tuple(int(k) for k in split2)
-    I = w1s[0][0].size(0)
-    if I < 128 or I % 128:
-        raise ValueError(f"moe_gate_up_table: I = {I} must be a multiple of 128")
-    if len(split2) != 3 or any(k < 0 or k % 128 for k in split2) or sum(split2) != I:
-        raise ValueError(f"moe_gate_up_table: split2 = {split2} must be three non-negative multiples of 128 that add up to I = {I}")
-    fp4 = ((I, KN // 2), (I, KS // 2), (I, KO // 2))
-    Bs = []
-    for e in range(E):
-        for name, B in (("w1", w1s[e]), ("w3", w3s[e])):
-            if tuple(tuple(t.shape) for t in B[:3]) != fp4:
-                raise ValueError(f"moe_gate_up_table: expert {e}: {name} must be fp4 weights (MM_W_FP4) of [{I}, .] rows matching split1")
-            if any(t.numel() < _sf_bytes_w(I, k) for t, k in zip(B[3:], (KN, KS, KO))):
-                raise ValueError(f"moe_gate_up_table: expert {e}: a scale tensor of {name} holds fewer than _sf_bytes_w(I, Kseg) bytes")
-        idx2 = reorder_indices2[e]
-        if idx2.numel() != I:
-            raise ValueError(f"moe_gate_up_table: expert {e}: w2's reorder index must have I = {I} entries")
-        whole = lambda B: tuple(B[:3]) + tuple(t.reshape(-1)[:_sf_bytes_w(I, k)] for t, k in zip(B[3:], (KN, KS, KO)))
-        Bs.append(interleave_gate_up(permute_packed_rows(whole(w1s[e]), idx2), permute_packed_rows(whole(w3s[e]), idx2)))
-    tab = moe_expert_table(reorder_indices1, Bs, KN, KS, KO)
-    tab.wmode = _lib.MM_W_FP4              # (moe_expert_table cannot tell the modes apart when KS = KO = 0)
-    return tab
-
-
-def _gate_up_split2(table, split2):
-    DN, DS, DO = (int(k) for k in split2)
-    if table.N % 256:
-        raise RuntimeError("table must be a moe_gate_up_table (N = 2 I, I a multiple of 128)")
-    _check_split(DN, DS, DO, table.N // 2, "moe_gate_up_activate")
-    return DN, DS, DO
-
-
-def moe_gate_up_activate_supported(max_rows, table, split2):
-    """False where moe_gate_up_activate would refuse: max_rows < 1, a bad split, or a table whose weights are not fp4"""
-    I = table.N // 2
-    return table.N % 256 == 0 and bool(_lib.load().mm_moe_gate_up_activate_supported(int(max_rows), I, *table.split, *(int(k) for k in split2), table.wmode))
-
-
-def moe_gate_up_activate_describe(table, n, split2=None):
-    """which kernel family and how many workgroups moe_gate_up_activate launches for n rows on the current device"""
-    return _lib.load().mm_moe_gate_up_activate_describe(table.E, int(n), table.N // 2).decode()
-
-
-def moe_gate_up_activate(A, expert_offsets, table, max_rows, split2, *, rounding="reference", out=None):
-    """Both up-projections of the experts, silu * mul and the quantizer of their down-projection in ONE launch: A = moe_quantize's
-    6-tuple (mode "x", w1's split), table = moe_gate_up_table(..), split2 = w2's (KN, KS, KO).  Returns the 6-tuple that moe_matmul
-    takes for w2 -- for every slot an expert of 1 .. max_rows rows owns byte for byte what
-    `moe_activate_quantize(moe_matmul(A, .., w1), moe_matmul(A, .., w3), offsets, w2's table)` gives wherever moe_matmul runs the
-    expert on the tiled kernels (more than 64 rows; below that it may add its fp32 partial sums in another order, include/micromix_hip.h).
-    Scale bytes of rows past an expert's last inside its own 128-row tiles are unspecified; everything else outside the experts' rows
-    and runs, and the rows of an expert above max_rows, are left as they were.  `out=` takes a 6-tuple to fill.  No host sync, no
-    allocation sized by device data; capture-safe."""
-    lib = _lib.load()
-    if rounding not in ("reference", "fused"):
-        _round_flags(rounding)
-    flags = _lib.MM_ROUND_PER_SEGMENT if rounding == "reference" else _lib.MM_ROUND_ONCE
-    dev = A[0].device
-    E, (KN, KS, KO) = table.E, table.split
-    DN, DS, DO = _gate_up_split2(table, split2)
-    n = A[0].size(0)
-    u8 = torch.uint8
-    for t, w in zip(A[:3], (KN // 2, KS // 4 * 3, KO)):
-        _moe_tensor(t, "activation segment", u8, dev, (n, w))
-    for t, k in zip(A[3:], (KN, KS, KO)):
-        if _moe_tensor(t, "activation scales", u8, dev).numel() < moe_sf_bytes(n, E, k):
-            raise RuntimeError("an activation scale tensor is smaller than moe_sf_bytes(n, E, Kseg)")
-    _moe_tensor(expert_offsets, "expert_offsets", torch.int32, dev, (E + 1,))
-    out = _moe_outputs(out, n, E, (DN // 2, DS // 4 * 3, DO), (DN, DS, DO), dev)
-    with _on_device(dev.index):
-        st = lib.mm_moe_gate_up_activate(*(_ptr(t) for t in A), _ptr(expert_offsets), _ptr(table.tensor), E, n, int(max_rows), table.N // 2, KN, KS, KO,
-                                         DN, DS, DO, flags, *(_ptr(t) for t in out), _stream_ptr(dev))
-    if st:
-        _lib.check(st, "moe_gate_up_activate")
-    return tuple(out)
+# ---- the rest of the surface lives with its subsystem; `mixedgemm` stays the one place to import it from ----
+
+from .paged import *  # noqa: E402,F401,F403  (the paged KV cache, attention over it, draft verification and sampling)
+from .paged import _kv_geometry  # noqa: E402,F401
+from .moe_ops import *  # noqa: E402,F401,F403  (the sparse MoE block's ops and tables)

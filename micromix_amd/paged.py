@@ -1,0 +1,537 @@
+"""The paged KV cache and what runs over it, as `mixedgemm` exports it: append (with RoPE), page copy and row moves, decode, shared-prefix
+decode and prefill attention (include/micromix_hip.h, mm_kv_append .. mm_paged_prefill_tree), and the end of a speculative step:
+`argmax_rows` / `sample_rows` -> `verify_greedy`.  None of it is an export of the reference module (its append_kv_i4 / _f16 take K/V
+already quantized and one head count); micromix_amd/kvcache.py is the small cache object on top.  Every wrapper runs on torch's
+current stream and is capture-safe."""
+from __future__ import annotations
+
+import torch
+
+from . import _lib
+from ._args import _check_tensor, _launch, _lead, _lib_with, _ok, _opt, _out, _ptr, _stream_ptr, _tensor
+
+__all__ = ["kv_append", "rope_kv_append", "kv_copy_pages", "kv_move_rows", "paged_decode", "paged_decode_workspace_bytes", "paged_decode_shared",
+           "paged_decode_shared_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes", "argmax_rows", "argmax_rows_workspace_bytes",
+           "verify_greedy", "sample_rows", "sample_rows_workspace_bytes"]
+
+# entries a library built before them lacks: (the symbol looked for, the names and the feature of the rebuild message)
+_TREE = ("mm_paged_prefill_tree", "mm_paged_prefill_tree / mm_kv_move_rows", "tree-masked attention")
+_VERIFY = ("mm_verify_greedy", "mm_argmax_rows / mm_verify_greedy", "draft verification")
+_SAMPLE = ("mm_sample_rows", "mm_sample_rows", "the sampler")
+_SHARED = ("mm_paged_decode_shared", "mm_paged_decode_shared", "shared-prefix decode")
+
+
+def _kv_bytes(kv_data):
+    """an fp8 cache held as torch.float8_e4m3fn, seen as the uint8 tensor the ops take: the same bytes, OCP e4m3fn codes"""
+    return kv_data.view(torch.uint8) if isinstance(kv_data, torch.Tensor) and kv_data.dtype is torch.float8_e4m3fn else kv_data
+
+
+def _kv_geometry(kv_data, kv_param, index):
+    """(dtype code, max_pages, L, Hkv, P, kv_data as the C ABI takes it) of a cache, recognised by its shape; int4: uint8
+    [max_pages, L, 2, Hkv, P, 64] + fp16 params [..., P, 2]; fp8: uint8 (or torch.float8_e4m3fn, viewed as uint8) [max_pages, L, 2, Hkv,
+    P, 128] + the same fp16 params; bf16: bf16 [max_pages, L, 2, Hkv, P, 128] and kv_param None."""
+    if kv_param is None:
+        if not _ok(kv_data, torch.bfloat16, index):
+            _check_tensor(kv_data, "kv_data", torch.bfloat16)
+            raise RuntimeError(f"kv_data must be on cuda:{index}")
+        if kv_data.dim() != 6 or kv_data.size(2) != 2 or kv_data.size(5) != 128:
+            raise RuntimeError("bf16 kv_data (kv_param None) must be [max_pages, L, 2, Hkv, P, 128]; an int4 cache ([..., 64] uint8) and an "
+                               "fp8 cache ([..., 128] uint8 / float8_e4m3fn) need their fp16 kv_param")
+        kind = _lib.MM_KV_BF16
+    else:
+        kv_data = _kv_bytes(kv_data)
+        if not (_ok(kv_data, torch.uint8, index) and _ok(kv_param, torch.float16, index)):
+            _check_tensor(kv_data, "kv_data", torch.uint8)
+            _check_tensor(kv_param, "kv_param", torch.float16, kv_data.device)
+            raise RuntimeError(f"kv_data / kv_param must be on cuda:{index}")
+        if kv_data.dim() != 6 or kv_data.size(2) != 2 or kv_data.size(5) not in (64, 128):
+            raise RuntimeError("kv_data with a kv_param must be [max_pages, L, 2, Hkv, P, 64] uint8 (int4) or [max_pages, L, 2, Hkv, P, 128] "
+                               "uint8 / float8_e4m3fn (fp8); a bf16 cache [max_pages, L, 2, Hkv, P, 128] takes kv_param None")
+        if tuple(kv_param.shape) != tuple(kv_data.shape[:5]) + (2,):
+            raise RuntimeError("kv_param must be [max_pages, L, 2, Hkv, P, 2] fp16, matching kv_data")
+        kind = _lib.MM_KV_INT4 if kv_data.size(5) == 64 else _lib.MM_KV_FP8_E4M3
+    max_pages, L, _, Hkv, P, _ = kv_data.shape
+    return kind, max_pages, L, Hkv, P, kv_data
+
+
+def _cache(kv_data, kv_param, dev=None):
+    """(device, dtype code, max_pages, L, Hkv, P, kv_data as the C ABI takes it) of a cache that has to lie on `dev`; None: on the
+    device it is found on (an op without a query)"""
+    if kv_param is not None:
+        kv_data = _kv_bytes(kv_data)
+    if dev is None:
+        if not (isinstance(kv_data, torch.Tensor) and kv_data.is_cuda):
+            _check_tensor(kv_data, "kv_data", torch.uint8 if kv_param is not None else torch.bfloat16)
+        dev = kv_data.device
+    return (dev, *_kv_geometry(kv_data, kv_param, dev.index))
+
+
+def _page_table(kv_indptr, kv_indices, last_page_len, dev):
+    _tensor(kv_indptr, "kv_indptr", torch.int32, dev)
+    _tensor(kv_indices, "kv_indices", torch.int32, dev)
+    _tensor(last_page_len, "last_page_len", torch.int32, dev)
+    B = last_page_len.numel()
+    if kv_indptr.numel() != B + 1:
+        raise RuntimeError("kv_indptr must have B + 1 entries (B = last_page_len.numel())")
+    return B
+
+
+def _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, q=None):
+    """The common checks of the cache ops that take a page table and a layer: (device, B, Hkv, the C arguments kv_data .. batch that
+    every entry point takes in this order).  The device is q's (bf16, contiguous); an append has no q and takes the cache's."""
+    dev, kind, max_pages, L, Hkv, P, kv_data = _cache(kv_data, kv_param, _lead(q, "q", torch.bfloat16) if q is not None else None)
+    B = _page_table(kv_indptr, kv_indices, last_page_len, dev)
+    layer_idx = int(layer_idx)
+    if not 0 <= layer_idx < L:
+        raise RuntimeError(f"layer_idx {layer_idx} outside the cache's {L} layers")
+    return dev, B, Hkv, (_ptr(kv_data), _opt(kv_param), kind, max_pages, L, layer_idx, Hkv, P, 128,
+                         _ptr(kv_indptr), _ptr(kv_indices), _ptr(last_page_len), B)
+
+
+def _query_heads(q, Hkv, B=None):
+    """Hq of the query an attention wrapper takes: [B, Hq, 128] for decode, [T, Hq, 128] (B None) for prefill, Hq a multiple of Hkv"""
+    if q.dim() != 3 or q.size(2) != 128 or (B is not None and q.size(0) != B):
+        raise RuntimeError(f"q must be [B = {B}, Hq, 128] bf16" if B is not None else "q must be [T, Hq, 128] bf16, T = qo_indptr[-1]")
+    return _head_groups(q.size(1), Hkv)
+
+
+def _head_groups(Hq, Hkv):
+    if Hq % Hkv:
+        raise RuntimeError(f"the {Hq} query heads are not a multiple of the cache's {Hkv} kv heads")
+    return Hq
+
+
+def _kv_workspace(workspace, need, dev):
+    """(the split-KV scratch, which the caller holds across the launch, its two C arguments): allocated when `need` bytes are wanted and
+    none was passed"""
+    if not need:
+        return None, (None, 0)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+    if (not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or workspace.device != dev
+            or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need):
+        raise RuntimeError(f"workspace must be a contiguous device tensor of at least {need} bytes on {dev}")
+    return workspace, (_ptr(workspace), workspace.numel() * workspace.element_size())
+
+
+def _sm_scale(sm_scale):
+    scale = float(sm_scale) if sm_scale is not None else 128 ** -0.5
+    if not scale > 0:
+        raise ValueError("sm_scale must be positive")
+    return scale
+
+
+def kv_append(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, k, v, append_indptr, layer_idx):
+    """Write T new tokens' K and V (bf16 [T, Hkv, 128]) into layer `layer_idx` of a paged cache, in place.
+
+    Not an export of the reference module (its append_kv_i4 / _f16 take K/V already quantized and one head count).  The page table
+    (kv_indptr [B + 1], kv_indices, last_page_len [B], int32) already counts the new tokens; append_indptr [B + 1] splits the T tokens
+    among the sequences, each sequence's go to its last positions.  kv_param None: bf16 cache (a copy); otherwise int4 codes + fp16
+    (scale, zero) by the rule of quantize_int_group(x, 4, 128), or -- kv_data [..., 128] uint8 / float8_e4m3fn -- e4m3 codes with a
+    power-of-two scale per row and zero = 0 (include/micromix_hip.h, MM_KV_FP8_E4M3).  Runs on the current stream, capture-safe.
+    """
+    lib = _lib.load()
+    dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx)
+    _tensor(append_indptr, "append_indptr", torch.int32, dev)
+    _tensor(k, "k", torch.bfloat16, dev)
+    _tensor(v, "v", torch.bfloat16, dev)
+    if k.dim() != 3 or k.shape != v.shape or k.size(1) != Hkv or k.size(2) != 128:
+        raise RuntimeError(f"k and v must both be [T, {Hkv}, 128] bf16")
+    if append_indptr.numel() != B + 1:
+        raise RuntimeError("append_indptr must have B + 1 entries")
+    _launch("kv_append", dev, lib.mm_kv_append, *kv_args, _ptr(k), _ptr(v), _ptr(append_indptr), k.size(0), _stream_ptr(dev))
+
+
+def kv_copy_pages(kv_data, kv_param, src_pages, dst_pages, rows=None):
+    """Copy token rows [0, rows[i]) of page src_pages[i] to page dst_pages[i] of a paged cache, for every layer, K and V, every head, in
+    place; returns None.  rows None: whole pages.  Bytes only (codes and, for int4 / fp8, the fp16 params): no dequantization.
+
+    src_pages, dst_pages, rows: int32 device tensors of one length.  A pair whose page index lies outside the cache, with src == dst or
+    with rows <= 0 is skipped; rows above the page size count as the page size.  The destination pages must be pairwise distinct and
+    none of them a source of the same call (include/micromix_hip.h, mm_kv_copy_pages).  What PagedKVCache.extend calls before a sequence
+    writes into a partly filled page it shares.  Runs on the current stream, capture-safe."""
+    lib = _lib.load()
+    dev, kind, max_pages, L, Hkv, P, kv_data = _cache(kv_data, kv_param)
+    for n, t in (("src_pages", src_pages), ("dst_pages", dst_pages), ("rows", rows)):
+        if t is not None:
+            if _tensor(t, n, torch.int32, dev).dim() != 1 or t.numel() != src_pages.numel():
+                raise RuntimeError("src_pages, dst_pages and rows must be one-dimensional and of one length")
+    _launch("kv_copy_pages", dev, lib.mm_kv_copy_pages, _ptr(kv_data), _opt(kv_param), kind, max_pages, L, Hkv, P, 128, _ptr(src_pages),
+            _ptr(dst_pages), _opt(rows), src_pages.numel(), _stream_ptr(dev))
+
+
+def kv_move_rows(kv_data, kv_param, kv_indptr, kv_indices, move_indptr, src_pos, dst_pos):
+    """Within each sequence of a paged cache, move token rows from one logical position to another, for every layer, K and V, every
+    head, in place; returns None.  Bytes only (codes and, for int4 / fp8, the fp16 params): no dequantization.
+
+    Sequence b's moves are m in [move_indptr[b], move_indptr[b + 1]): the row at position src_pos[m] goes to position dst_pos[m], a
+    position being row pos % P of page kv_indices[kv_indptr[b] + pos // P].  All sources of a sequence are read before any of its
+    destinations is written, so a destination may be another move's source -- what packing the accepted path of a tree draft down to
+    contiguous positions needs (PagedKVCache.accept).  At most 64 moves per sequence are performed; a move with src == dst, a position
+    outside the pages the sequence lists or a page index outside the cache is skipped.  The destinations of a sequence must be pairwise
+    distinct, and no page written may be listed by another sequence with moves in the call (include/micromix_hip.h, mm_kv_move_rows).
+    move_indptr [B + 1], src_pos, dst_pos: int32 device tensors.  Runs on the current stream, capture-safe."""
+    lib = _lib_with(*_TREE)
+    dev, kind, max_pages, L, Hkv, P, kv_data = _cache(kv_data, kv_param)
+    for n, t in (("kv_indptr", kv_indptr), ("kv_indices", kv_indices), ("move_indptr", move_indptr), ("src_pos", src_pos), ("dst_pos", dst_pos)):
+        if _tensor(t, n, torch.int32, dev).dim() != 1:
+            raise RuntimeError(f"{n} must be one-dimensional")
+    B = kv_indptr.numel() - 1
+    if B < 0 or move_indptr.numel() != B + 1:
+        raise RuntimeError("kv_indptr and move_indptr must both have B + 1 entries")
+    if src_pos.numel() != dst_pos.numel():
+        raise RuntimeError("src_pos and dst_pos must be of one length")
+    _launch("kv_move_rows", dev, lib.mm_kv_move_rows, _ptr(kv_data), _opt(kv_param), kind, max_pages, L, Hkv, P, 128, _ptr(kv_indptr),
+            _ptr(kv_indices), B, _ptr(move_indptr), _ptr(src_pos), _ptr(dst_pos), src_pos.numel(), _stream_ptr(dev))
+
+
+def argmax_rows_workspace_bytes(rows, vocab):
+    """bytes of workspace `argmax_rows` needs for bf16 logits [rows, vocab]; 0 when a row is one part (vocab <= MM_ARGMAX_CHUNK)"""
+    return int(_lib_with(*_VERIFY).mm_argmax_rows_workspace_bytes(int(rows), int(vocab)))
+
+
+def _logits(logits):
+    """(rows, vocab, elements between rows, device) of the bf16 logits `argmax_rows` and `sample_rows` take: unit stride along the
+    vocabulary, any row stride >= vocab, nothing copied"""
+    if not isinstance(logits, torch.Tensor):
+        raise TypeError("logits must be a torch.Tensor")
+    if logits.dtype is not torch.bfloat16:
+        raise TypeError(f"logits must be torch.bfloat16, got {logits.dtype}")
+    if not logits.is_cuda:
+        raise RuntimeError("logits must be a device tensor (HIP); the MicroMix ops have no CPU path")
+    if logits.dim() != 2 or logits.size(1) < 1:
+        raise RuntimeError("logits must be [rows, vocab] with vocab >= 1")
+    rows, vocab = logits.shape
+    if vocab > 1 and logits.stride(1) != 1:
+        raise RuntimeError("logits must have unit stride along the vocabulary (the rows may be any distance >= vocab apart)")
+    ld = logits.stride(0) if rows > 1 else vocab
+    if ld < vocab:
+        raise RuntimeError(f"logits rows overlap: row stride {ld} < vocab {vocab}")
+    return rows, vocab, ld, logits.device
+
+
+def argmax_rows(logits, *, out=None, workspace=None):
+    """The index of each row's maximum: logits bf16 [rows, vocab] on the device, last stride 1, any row stride >= vocab (a slice
+    logits[:, :V] of a padded lm_head output, at any 2-byte-aligned offset, is taken as it is: nothing is copied).  Returns int32 [rows]
+    (`out` when given).  The order is torch.argmax's on the CPU: any NaN is greater than +inf, +0 == -0, the lowest index among equal
+    maxima wins.  vocab <= 2^20, rows <= 65535.  workspace: a contiguous device tensor of `argmax_rows_workspace_bytes(rows, vocab)`
+    bytes, uninitialised, allocated when needed and not given (under graph capture pass one).  Runs on the current stream,
+    capture-safe."""
+    lib = _lib_with(*_VERIFY)
+    rows, vocab, ld, dev = _logits(logits)
+    out = _out(out, "out", torch.int32, dev, (rows,), "int32 {0}")
+    workspace, ws_args = _kv_workspace(workspace, argmax_rows_workspace_bytes(rows, vocab), dev)
+    _launch("argmax_rows", dev, lib.mm_argmax_rows, _ptr(logits), rows, vocab, ld, _ptr(out), *ws_args, _stream_ptr(dev))
+    return out
+
+
+def sample_rows_workspace_bytes(rows, vocab):
+    """bytes of workspace `sample_rows` needs for bf16 logits [rows, vocab]: 3 KiB per part of MM_ARGMAX_CHUNK columns of every row
+    and 2 KiB per row"""
+    return int(_lib_with(*_SAMPLE).mm_sample_rows_workspace_bytes(int(rows), int(vocab)))
+
+
+def _row_param(value, name, dtype, rows, dev):
+    """a per-row parameter of `sample_rows`: None, a device tensor [rows] of `dtype`, or -- outside graph capture -- a Python number,
+    broadcast to one"""
+    if value is None:
+        return None
+    if isinstance(value, torch.Tensor):
+        return _tensor(value, name, dtype, dev, (rows,), "{2} {0}, one entry per row")
+    if isinstance(value, bool) or not isinstance(value, (int, float)):
+        raise TypeError(f"{name} must be None, a number or a {dtype} device tensor [{rows}], got {type(value).__name__}")
+    if dtype is torch.int32 and not isinstance(value, int):
+        raise TypeError(f"{name} must be an int or a torch.int32 device tensor [{rows}], got {type(value).__name__}")
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(f"{name}: a Python number would be uploaded during graph capture; pass a {dtype} device tensor [{rows}]")
+    if dtype is torch.int32:
+        value = min(max(value, -(1 << 31)), (1 << 31) - 1)
+    return torch.full((rows,), value, dtype=dtype, device=dev)
+
+
+def sample_rows(logits, u, *, temperature=None, top_k=None, top_p=None, min_p=None, out=None, workspace=None):
+    """One token per row, drawn under temperature, top-k, top-p and min-p: logits bf16 [rows, vocab] on the device as `argmax_rows`
+    takes them (any row stride >= vocab, any 2-byte-aligned offset), u fp32 [rows] uniform in [0, 1) -- `torch.rand`, which captures;
+    the library draws no random numbers.  Returns int32 [rows] (`out` when given), ready for `verify_greedy` / `verify_launch` as
+    target_tok: the accepted path and the bonus token are then distributed as the target model's.
+
+    temperature, top_p, min_p: fp32 [rows], top_k: int32 [rows], device tensors read by the kernels only, so one captured graph serves
+    any mix of requests rewritten in place; None: temperature 1, that filter off; a Python number is broadcast to a tensor (outside
+    capture only).  Per row: temperature <= 0 or NaN, or a row whose maximum is NaN or infinite, gives exactly `argmax_rows`' answer.
+    Otherwise w_i = exp((l_i - max) / T); tokens of equal logit form a class and every filter keeps whole classes in descending
+    order: top_k the shortest prefix with >= k tokens (1 <= k < vocab, else off), top_p the shortest prefix with mass >= p times
+    top-k's (p < 1; p <= 0 keeps the top class), min_p the classes with w >= q (0 < q <= 1); the kept set is the shortest of the
+    three; the answer is the first kept index whose cumulative kept mass exceeds u * Z (include/micromix_hip.h, mm_sample_rows).  The
+    result is a function of the inputs alone: the same bits on every run.  vocab <= 2^20, rows <= 65535.  workspace: a contiguous
+    device tensor of `sample_rows_workspace_bytes(rows, vocab)` bytes, uninitialised, allocated when not given (under graph capture
+    pass one).  Runs on the current stream, capture-safe."""
+    lib = _lib_with(*_SAMPLE)
+    rows, vocab, ld, dev = _logits(logits)
+    if u is None or not isinstance(u, torch.Tensor):
+        raise TypeError(f"u must be a torch.float32 device tensor [{rows}] (torch.rand), got {type(u).__name__}")
+    u = _row_param(u, "u", torch.float32, rows, dev)
+    temperature = _row_param(temperature, "temperature", torch.float32, rows, dev)
+    top_k = _row_param(top_k, "top_k", torch.int32, rows, dev)
+    top_p = _row_param(top_p, "top_p", torch.float32, rows, dev)
+    min_p = _row_param(min_p, "min_p", torch.float32, rows, dev)
+    out = _out(out, "out", torch.int32, dev, (rows,), "int32 {0}")
+    workspace, ws_args = _kv_workspace(workspace, sample_rows_workspace_bytes(rows, vocab), dev)
+    _launch("sample_rows", dev, lib.mm_sample_rows, _ptr(logits), rows, vocab, ld, _ptr(u), _opt(temperature), _opt(top_k), _opt(top_p),
+            _opt(min_p), _ptr(out), *ws_args, _stream_ptr(dev))
+    return out
+
+
+def verify_greedy(target_tok, draft_tok, root_tok, qo_indptr, kv_indptr, last_page_len, page_size, *, tree_mask=None, result=None,
+                  move_src=None, move_dst=None):
+    """Greedy (exact-match) verification of tree or chain drafts, one wave per sequence; returns (result, move_src, move_dst).
+
+    Sequence b has the n = qo_indptr[b + 1] - qo_indptr[b] draft nodes of rows qo_indptr[b] .. : draft_tok[t] is a node's token,
+    target_tok[t] the token the target model picks after it (`argmax_rows` or `sample_rows` of its logits), root_tok[b] the token
+    picked after the last committed one.  tree_mask: the int64 words of `paged_prefill(tree_mask=)` -- a node's parent is the highest set
+    bit below its own -- or None for chains.  Starting from root_tok[b], the walk takes the lowest-numbered child of the node just taken
+    whose token is the one wanted, until there is none.  result int32 [B, 66]: [0] the path's length k, [1] the bonus token (the
+    target's choice after the last node taken; root_tok[b] when nothing matched), [2 : 2 + k] the path, the rest -1.  A sequence with
+    n > 64 or root_tok[b] < 0 is a prompt chunk and keeps all: [0] = n, [1] = target_tok of its last row (-1 for n = 0), path entries -1.
+    move_src, move_dst int32 [T], laid over qo_indptr: pass them on as `kv_move_rows(..., move_indptr=qo_indptr, move_src, move_dst)`
+    to pack each path down to the positions base_b .. base_b + k - 1 (base_b = len_b - n, len_b from kv_indptr / last_page_len /
+    page_size).  Every element of the three outputs is written.  All tensors are int32 on one device (token ids as int64 are refused:
+    convert them with .to(torch.int32)).  Runs on the current stream, capture-safe (include/micromix_hip.h, mm_verify_greedy)."""
+    lib = _lib_with(*_VERIFY)
+    ints = (("target_tok", target_tok), ("draft_tok", draft_tok), ("root_tok", root_tok), ("qo_indptr", qo_indptr), ("kv_indptr", kv_indptr),
+            ("last_page_len", last_page_len))
+    for n, t in ints:                                      # what torch.argmax and a tokenizer hand over: say what to do about it
+        if isinstance(t, torch.Tensor) and t.dtype is torch.int64:
+            raise TypeError(f"{n} must be torch.int32, got torch.int64: convert it with {n}.to(torch.int32)")
+    if not (isinstance(target_tok, torch.Tensor) and target_tok.is_cuda):
+        _check_tensor(target_tok, "target_tok", torch.int32)
+    dev = target_tok.device
+    for n, t in ints:
+        if _tensor(t, n, torch.int32, dev).dim() != 1:
+            raise RuntimeError(f"{n} must be one-dimensional")
+    T, B = target_tok.numel(), root_tok.numel()
+    if draft_tok.numel() != T:
+        raise RuntimeError("target_tok and draft_tok must be of one length")
+    if qo_indptr.numel() != B + 1 or kv_indptr.numel() != B + 1 or last_page_len.numel() != B:
+        raise RuntimeError("qo_indptr and kv_indptr must have B + 1 entries and last_page_len B (B = root_tok.numel())")
+    page_size = int(page_size)
+    if page_size < 1:
+        raise ValueError("page_size must be positive")
+    if tree_mask is not None:
+        _tensor(tree_mask, "tree_mask", torch.int64, dev, (T,), "int64 {0}, one word per row")
+    result = _out(result, "result", torch.int32, dev, (B, _lib.MM_VERIFY_STRIDE), "int32 {0}")
+    move_src = _out(move_src, "move_src", torch.int32, dev, (T,), "int32 {0}")
+    move_dst = _out(move_dst, "move_dst", torch.int32, dev, (T,), "int32 {0}")
+    _launch("verify_greedy", dev, lib.mm_verify_greedy, _ptr(target_tok), _ptr(draft_tok), _ptr(root_tok), _opt(tree_mask), _ptr(qo_indptr), T,
+            _ptr(kv_indptr), _ptr(last_page_len), page_size, B, _ptr(result), _ptr(move_src), _ptr(move_dst), _stream_ptr(dev))
+    return result, move_src, move_dst
+
+
+def _token_rows(t, name, heads):
+    """(heads, token stride in elements) of q / k / v given as [T, H, 128] or [T, H * 128] whose rows lie contiguous within a token.
+    Stride 0: any stride will do (at most one token); None: the tensor has to be copied (rows not contiguous, an odd stride, a
+    misaligned pointer)"""
+    if t.dim() == 3 and t.size(2) == 128:
+        H, inner = t.size(1), t.stride(2) == 1 and (t.size(1) == 1 or t.stride(1) == 128)
+    elif t.dim() == 2 and t.size(1) % 128 == 0 and t.size(1):
+        H, inner = t.size(1) // 128, t.stride(1) == 1
+    else:
+        raise RuntimeError(f"{name} must be [T, H, 128] or [T, H * 128] bf16")
+    if heads is not None and H != heads:
+        raise RuntimeError(f"{name} has {H} heads, the cache has {heads}")
+    stride = t.stride(0) if t.size(0) > 1 else 0
+    ok = inner and (stride == 0 or stride >= H * 128) and stride % 2 == 0 and t.data_ptr() % 4 == 0
+    return H, (stride if ok else None)
+
+
+def rope_kv_append(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, q, k, v, cos, sin, append_indptr, layer_idx):
+    """RoPE on q and k, then `kv_append` of (rotated k, v), in one launch; returns the rotated q, bf16 [T, Hq, 128] contiguous.
+
+    q, k, v: bf16 [T, H, 128] or [T, H * 128].  Views of one packed [T, (Hq + 2 Hkv) * 128] projection (what FusedQLinear returns) are
+    read in place; so are any three tensors with one common token stride.  Otherwise they are packed into one buffer first (one copy).
+    cos, sin: bf16 [T, 128], or HF's [1, T, 128] / [bsz, q_len, 128] (flattened): row i belongs to flat token i; a row stride is honoured.
+    RoPE is HF's apply_rotary_pos_emb in bf16 arithmetic, q * cos + rotate_half(q) * sin with every op rounded to bf16, bit for bit
+    (include/micromix_hip.h, mm_rope_kv_append).  The cache receives exactly what kv_append(rope(k), v) writes; q is rotated for every
+    token.  Page table, append_indptr and the three cache kinds (int4, fp8 e4m3, bf16) as in `kv_append`.  Runs on the current stream,
+    capture-safe.
+    """
+    lib = _lib.load()
+    dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx)
+    _tensor(append_indptr, "append_indptr", torch.int32, dev)
+    if append_indptr.numel() != B + 1:
+        raise RuntimeError("append_indptr must have B + 1 entries")
+    for n, t in (("q", q), ("k", k), ("v", v), ("cos", cos), ("sin", sin)):
+        if not (isinstance(t, torch.Tensor) and t.dtype is torch.bfloat16 and t.is_cuda and t.get_device() == dev.index):
+            _check_tensor(t, n, torch.bfloat16, dev)      # contiguity is not asked of these five
+    Hq, sq = _token_rows(q, "q", None)
+    _, sk = _token_rows(k, "k", Hkv)
+    _, sv = _token_rows(v, "v", Hkv)
+    T = q.size(0)
+    if k.size(0) != T or v.size(0) != T:
+        raise RuntimeError("q, k and v must hold the same T tokens")
+    _head_groups(Hq, Hkv)
+    strides = {sq, sk, sv} - {0}
+    if None in strides or len(strides) > 1 or max(strides, default=Hq * 128) < Hq * 128:
+        packed = torch.cat([q.reshape(T, Hq * 128), k.reshape(T, Hkv * 128), v.reshape(T, Hkv * 128)], dim=1)
+        q, k, v = packed[:, : Hq * 128], packed[:, Hq * 128: (Hq + Hkv) * 128], packed[:, (Hq + Hkv) * 128:]
+        strides = {(Hq + 2 * Hkv) * 128}
+    sq = max(strides, default=Hq * 128)
+    if cos.shape != sin.shape or cos.dim() not in (2, 3) or cos.size(-1) != 128 or cos.numel() != T * 128:
+        raise RuntimeError(f"cos and sin must both be [T = {T}, 128] (or [bsz, q_len, 128] with bsz * q_len = T) bf16")
+    cos, sin = cos.reshape(T, 128), sin.reshape(T, 128)
+    sc = cos.stride(0) if T > 1 else 128
+    if not (cos.stride(1) == 1 and sin.stride(1) == 1 and (T <= 1 or sin.stride(0) == sc) and sc >= 128 and sc % 2 == 0
+            and cos.data_ptr() % 4 == 0 and sin.data_ptr() % 4 == 0):
+        cos, sin, sc = cos.contiguous(), sin.contiguous(), 128
+    q_rot = torch.empty((T, Hq, 128), dtype=torch.bfloat16, device=dev)
+    _launch("rope_kv_append", dev, lib.mm_rope_kv_append, *kv_args, _ptr(q), _ptr(k), _ptr(v), sq, Hq, _ptr(cos), _ptr(sin), sc,
+            _ptr(append_indptr), T, _ptr(q_rot), _stream_ptr(dev))
+    return q_rot
+
+
+def _window(window):
+    """HF's sliding_window as the C ABI takes it: None or 0 is no window (the un-windowed entry points), W >= 1 a window of W tokens"""
+    window = 0 if window is None else int(window)
+    if window < 0:
+        raise ValueError("window must be None, 0 (no window) or a positive token count")
+    return window
+
+
+def paged_decode_workspace_bytes(B, Hq, Hkv, max_seq_len, window=None):
+    """bytes of fp32 scratch paged_decode needs for this bound and window (0: one launch, no workspace)"""
+    window = _window(window)
+    if not window:
+        return int(_lib.load().mm_paged_decode_workspace_bytes(int(B), int(Hq), int(Hkv), int(max_seq_len)))
+    return int(_lib.load().mm_paged_decode_window_workspace_bytes(int(B), int(Hq), int(Hkv), int(max_seq_len), window))
+
+
+def _max_seq_len(max_seq_len):
+    max_seq_len = int(max_seq_len)
+    if max_seq_len < 0:
+        raise RuntimeError("max_seq_len must be >= 0")
+    return max_seq_len
+
+
+def paged_decode(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, max_seq_len, sm_scale=None, workspace=None, *,
+                 window=None):
+    """Single-token GQA attention over layer `layer_idx` of a paged cache: q bf16 [B, Hq, 128] -> o bf16 [B, Hq, 128].
+
+    Query head h reads kv head h // (Hq / Hkv) (HF repeat_kv), every cached token, softmax in fp32 with sm_scale (default 1/sqrt(128));
+    a sequence of length 0 gives zeros.  `max_seq_len` bounds the sequence lengths; the split over the tokens depends on it (and B,
+    Hq, Hkv) only, so a captured graph stays valid while the sequences grow up to it.  `workspace` (uint8 / any device tensor of at
+    least paged_decode_workspace_bytes(...) bytes) is allocated here when None -- pass one when capturing a graph.
+    `window` = W (HF's sliding_window; None or 0: none): the query attends the last W tokens of its sequence, its own included.  Only
+    these tokens are read, the split is laid over W tokens, and page-table entries below the window may be -1.
+    The cache is int4, fp8 (e4m3) or bf16, told apart as in `kv_append`; over an fp8 cache the result equals, bit for bit, that over a
+    bf16 cache holding the dequantized values.
+    """
+    lib = _lib.load()
+    window = _window(window)
+    dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, q)
+    Hq = _query_heads(q, Hkv, B)
+    max_seq_len = _max_seq_len(max_seq_len)
+    need = paged_decode_workspace_bytes(B, Hq, Hkv, max_seq_len, window) if B else 0
+    workspace, ws_args = _kv_workspace(workspace, need, dev)
+    o = torch.empty((B, Hq, 128), dtype=torch.bfloat16, device=dev)
+    args = (_ptr(q), *kv_args, Hq, max_seq_len, _sm_scale(sm_scale), *ws_args, _ptr(o))
+    if window:
+        _launch("paged_decode", dev, lib.mm_paged_decode_window, *args, _stream_ptr(dev), window)
+    else:
+        _launch("paged_decode", dev, lib.mm_paged_decode, *args, _stream_ptr(dev))
+    return o
+
+
+def paged_decode_shared_workspace_bytes(B, Hq, Hkv, max_shared_len, max_suffix_len):
+    """bytes of fp32 scratch paged_decode_shared needs for these bounds: the partials of its prefix and tail chunks (never 0 for B > 0
+    and sizes the call takes; 0 for sizes it refuses)"""
+    return int(_lib_with(*_SHARED).mm_paged_decode_shared_workspace_bytes(int(B), int(Hq), int(Hkv), int(max_shared_len), int(max_suffix_len)))
+
+
+def paged_decode_shared(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, group_indptr, group_members, shared_len,
+                        max_shared_len, max_suffix_len, sm_scale=None, workspace=None, *, out=None):
+    """`paged_decode` for a batch in which groups of sequences hold their leading pages in common: q bf16 [B, Hq, 128] -> o bf16
+    [B, Hq, 128], the same function (every sequence attends all of its tokens), within the same budget but not the same bits.
+
+    The shared tokens of a group are walked once per slab of 16 // (Hq // Hkv) members instead of once per member; each sequence's own
+    tail is walked as in `paged_decode`.  group_indptr [B + 1], group_members [B], shared_len [B]: int32 device tensors.  Group j is
+    group_members[group_indptr[j] : group_indptr[j + 1]], trailing unused groups are empty (group_indptr[j] = B), group_members is a
+    permutation of range(B), and shared_len[b] -- the same for every member of a group, at most each member's length, any value, not
+    only multiples of the page size -- counts the leading tokens b has on the same pages as its group (include/micromix_hip.h,
+    mm_paged_decode_shared, also for what happens when the tensors break the rules: wrong results for those sequences, no access outside
+    the tensors).  `PagedKVCache.share_groups()` derives one grouping from a page table; a caller who knows better (a beam tree whose
+    branches share different depths) passes its own.
+    `max_shared_len` bounds the shared counts, `max_suffix_len` the tails; the launches depend on them (and B, Hq, Hkv) only, so a
+    captured graph stays valid while lengths and groups change within them.  `workspace` (at least
+    paged_decode_shared_workspace_bytes(...) bytes; always needed) is allocated here when None -- pass one when capturing a graph.
+    `out`: a bf16 [B, Hq, 128] tensor to write instead of a new one.  No sliding window.
+    """
+    lib = _lib_with(*_SHARED)
+    dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, q)
+    Hq = _query_heads(q, Hkv, B)
+    for n, t, size in (("group_indptr", group_indptr, B + 1), ("group_members", group_members, B), ("shared_len", shared_len, B)):
+        if _tensor(t, n, torch.int32, dev).dim() != 1 or t.numel() != size:
+            raise RuntimeError(f"{n} must be a one-dimensional int32 tensor of {size} entries (B = {B})")
+    max_shared_len, max_suffix_len = int(max_shared_len), int(max_suffix_len)
+    if min(max_shared_len, max_suffix_len) < 0 or max(max_shared_len, max_suffix_len) > 1 << 29:
+        raise RuntimeError("max_shared_len and max_suffix_len must lie in [0, 2^29]")
+    need = paged_decode_shared_workspace_bytes(B, Hq, Hkv, max_shared_len, max_suffix_len) if B and Hq // Hkv <= 16 else 0
+    workspace, ws_args = _kv_workspace(workspace, need, dev)
+    out = _out(out, "out", torch.bfloat16, dev, (B, Hq, 128), "{0} bf16")
+    _launch("paged_decode_shared", dev, lib.mm_paged_decode_shared, _ptr(q), *kv_args, Hq, _ptr(group_indptr), _ptr(group_members),
+            _ptr(shared_len), max_shared_len, max_suffix_len, _sm_scale(sm_scale), *ws_args, _ptr(out), _stream_ptr(dev))
+    return out
+
+
+def paged_prefill_workspace_bytes(T, B, Hq, Hkv, max_seq_len, window=None):
+    """bytes of fp32 scratch paged_prefill needs for T query tokens over B sequences within max_seq_len, under `window` (0: one launch,
+    no workspace)"""
+    window = _window(window)
+    if not window:
+        return int(_lib.load().mm_paged_prefill_workspace_bytes(int(T), int(B), int(Hq), int(Hkv), int(max_seq_len)))
+    return int(_lib.load().mm_paged_prefill_window_workspace_bytes(int(T), int(B), int(Hq), int(Hkv), int(max_seq_len), window))
+
+
+def paged_prefill(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, qo_indptr, layer_idx, max_seq_len, sm_scale=None,
+                  workspace=None, *, window=None, tree_mask=None):
+    """Causal GQA attention of T new query tokens over layer `layer_idx` of a paged cache: q bf16 [T, Hq, 128] -> o bf16 [T, Hq, 128].
+
+    qo_indptr (int32 [B + 1], qo_indptr[B] = T) splits the queries among the sequences, as kv_append's append_indptr does; pass the
+    same array.  The page table already counts the new tokens, and the mask is aligned bottom-right: sequence b's j-th new token sits
+    at position len_b - n_b + j and attends positions 0 .. that one.  Softmax in fp32 with sm_scale (default 1/sqrt(128)).
+    `max_seq_len` bounds the sequence lengths; the grid and the split over the tokens depend on it (and T, B, Hq, Hkv) only, so a
+    captured graph stays valid over later steps with the same T.  `workspace` (any contiguous device tensor of at least
+    paged_prefill_workspace_bytes(...) bytes) is allocated here when None -- pass one when capturing a graph.
+    `window` = W (HF's sliding_window; None or 0: none): the token at position p attends positions max(0, p - W + 1) .. p; the kv tiles
+    below a query tile's windows are not read, and page-table entries below every window may be -1.
+    `tree_mask` (int64 [T] device tensor, one word per query token; None: the causal mask): verification of a tree draft.  With
+    base_b = len_b - n_b, sequence b's j-th new token attends every position below base_b and new slot base_b + i exactly when i <= j
+    and bit i of its word is set (bits above j are ignored; set bit j for a token to attend itself).  A sequence with more than 64 new
+    tokens ignores its words and is attended causally.  Words (2 << j) - 1 give the bits of the causal call.  No window form: `window`
+    together with `tree_mask` is a ValueError.  The tensor is read by the kernel only, so a captured graph replays with other trees
+    written into it.  `PagedKVCache.tree_mask` builds the words from parent indices.
+    The cache is int4, fp8 (e4m3) or bf16, told apart as in `kv_append`; fp8 runs p.V on bf16(p * scale_v) times the codes, as int4.
+    """
+    lib = _lib.load() if tree_mask is None else _lib_with(*_TREE)
+    window = _window(window)
+    if window and tree_mask is not None:
+        raise ValueError("paged_prefill has no sliding-window form of the tree mask: pass window or tree_mask, not both")
+    dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, q)
+    _tensor(qo_indptr, "qo_indptr", torch.int32, dev)
+    if qo_indptr.numel() != B + 1:
+        raise RuntimeError("qo_indptr must have B + 1 entries (B = last_page_len.numel())")
+    Hq = _query_heads(q, Hkv)
+    T = q.size(0)
+    if tree_mask is not None:
+        if _tensor(tree_mask, "tree_mask", torch.int64, dev).dim() != 1 or tree_mask.numel() != T:
+            raise RuntimeError(f"tree_mask must be a one-dimensional int64 tensor of T = {T} words")
+    max_seq_len = _max_seq_len(max_seq_len)
+    need = paged_prefill_workspace_bytes(T, B, Hq, Hkv, max_seq_len, window) if B and T else 0
+    workspace, ws_args = _kv_workspace(workspace, need, dev)
+    o = torch.empty((T, Hq, 128), dtype=torch.bfloat16, device=dev)
+    args = (_ptr(q), _ptr(qo_indptr), T, *kv_args, Hq, max_seq_len, _sm_scale(sm_scale), *ws_args, _ptr(o))
+    if tree_mask is not None:
+        _launch("paged_prefill", dev, lib.mm_paged_prefill_tree, *args, _stream_ptr(dev), _ptr(tree_mask))
+    elif window:
+        _launch("paged_prefill", dev, lib.mm_paged_prefill_window, *args, _stream_ptr(dev), window)
+    else:
+        _launch("paged_prefill", dev, lib.mm_paged_prefill, *args, _stream_ptr(dev))
+    return o

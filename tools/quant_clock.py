@@ -1,6 +1,6 @@
 """Timeline of reorder_quantize_kernel's workgroups from in-kernel clock stamps (instrumented library:
 tools/build_variant.sh instr -DMM_INSTRUMENT).  python tools/quant_clock.py [KN,KS,KO]"""
-import ctypes, os, sys
+import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 if "MICROMIX_HIP_LIB" not in os.environ:
@@ -18,7 +18,6 @@ f = lambda: lib.mm_reorder_quantize(x.data_ptr(), 4096, 4096, idx.data_ptr(), *s
 for _ in range(300): f()
 torch.cuda.synchronize()
 clk = torch.zeros((8192, 4), dtype=torch.int64, device=dev)
-lib.mm_diag_set_quant_clock_buffer.argtypes = [ctypes.c_void_p]
 assert lib.mm_diag_set_quant_clock_buffer(clk.data_ptr()) == 0
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 e0.record(); f(); e1.record(); torch.cuda.synchronize()
