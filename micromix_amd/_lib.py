@@ -116,6 +116,8 @@ def _bind(lib, protos):
 _PROTOS, EXPORTS, _consts = _read("micromix_hip.h")
 _DIAG_PROTOS, DIAG_EXPORTS, _diag_consts = _read("micromix_diag.h")
 globals().update(_consts, **_diag_consts)
+# CALIB_EXPORTS: the entries of include/micromix_calib.h, exported by the product library next to EXPORTS; the header defines no constant
+_CALIB_PROTOS, CALIB_EXPORTS, _ = _read("micromix_calib.h")
 
 _lib = None
 
@@ -129,7 +131,7 @@ def load():
         raise MicroMixLibraryError(
             f"{LIB_PATH} is missing: build it with `python -m micromix_amd.build` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
-    _lib = _bind(ctypes.CDLL(LIB_PATH), _PROTOS)
+    _lib = _bind(_bind(ctypes.CDLL(LIB_PATH), _PROTOS), _CALIB_PROTOS)
     return _lib
 
 

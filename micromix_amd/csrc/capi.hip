@@ -1,5 +1,6 @@
 // extern "C" surface of libmicromix_hip.so -- see include/micromix_hip.h.
 #include "../../include/micromix_hip.h"
+#include "../../include/micromix_calib.h"
 #include "mx_common.h"
 #include "mx_kernels.h"
 #include "mx_kv_shared_host.h"
@@ -739,6 +740,28 @@ int mm_sample_rows(const void *logits_bf16, int rows, int vocab, long long ld, c
     if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7)) return MM_ERR_BAD_ARG;
     hipError_t e = mm::launch_sample_rows(logits_bf16, rows, vocab, ld, u, temperature, top_k, top_p, min_p, out_idx, workspace, (hipStream_t)stream);
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_sample_rows");
+}
+
+// ---- calibration statistics (calib_stats.hip, include/micromix_calib.h)
+static int calib_refused(int rows, int K) {
+    if (rows < 0 || K < 0) return MM_ERR_BAD_ARG;
+    if (K < 128 || K % 128 || K > 32768 || rows > (1 << 20)) return MM_ERR_UNSUPPORTED;
+    return MM_OK;
+}
+
+size_t mm_calib_workspace_bytes(int rows, int K) { return calib_refused(rows, K) || rows == 0 ? 0 : mm::calib_workspace_bytes(rows, K); }
+
+int mm_calib_accumulate(const void *x, int dtype, int rows, int K, long long ld, float lamda, void *score_f32, void *counts_i64,
+                        void *workspace, size_t workspace_bytes, mm_stream_t stream) {
+    if (rows < 0 || K < 0 || ld < K || !(lamda > 0.0f) || !(lamda < __builtin_inff())) return MM_ERR_BAD_ARG;
+    if (calib_refused(rows, K) || (dtype != 0 && dtype != 1)) return MM_ERR_UNSUPPORTED;
+    if (rows == 0) return MM_OK;
+    if (!x || !score_f32 || !counts_i64 || !workspace) return MM_ERR_BAD_ARG;
+    if (((uintptr_t)x & 15) || (ld & 7) || ((uintptr_t)score_f32 & 3) || ((uintptr_t)counts_i64 & 7) || ((uintptr_t)workspace & 15)) return MM_ERR_BAD_ARG;
+    if (workspace_bytes < mm::calib_workspace_bytes(rows, K)) return MM_ERR_BAD_ARG;
+    hipError_t e = mm::launch_calib_accumulate(x, dtype == 1, rows, K, ld, lamda, (float *)score_f32, (long long *)counts_i64, workspace,
+                                               (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_calib_accumulate");
 }
 
 // the un-windowed entry points are the windowed ones at window = 0

@@ -303,6 +303,11 @@ hipError_t launch_verify_greedy(const int *target_tok, const int *draft_tok, con
 size_t sample_workspace_bytes(int rows, int vocab);
 hipError_t launch_sample_rows(const void *logits, int rows, int vocab, long long ld, const float *u, const float *temperature,
                               const int *top_k, const float *top_p, const float *min_p, int *out, void *ws, hipStream_t stream);
+// calibration statistics of one batch (calib_stats.hip, include/micromix_calib.h): x [rows, K] bf16 or fp16, K a multiple of 128 up to
+// 32768, rows >= 1; ws: calib_workspace_bytes, uninitialised
+size_t calib_workspace_bytes(int rows, int K);
+hipError_t launch_calib_accumulate(const void *x, bool fp16, int rows, int K, long long ld, float lamda, float *score, long long *counts,
+                                   void *ws, hipStream_t stream);
 // sparse MoE block around the grouped GEMMs (moe.hip): n = T * top_k pairs, H a multiple of 8, rows 16-byte aligned
 hipError_t launch_moe_route(const void *logits, int T, int E, int top_k, int *ids, void *w, hipStream_t stream);
 hipError_t launch_moe_plan(const int *ids, int n, int E, int top_k, int *offsets, int *sorted_token, int *slot_of, hipStream_t stream);
