@@ -118,6 +118,8 @@ _DIAG_PROTOS, DIAG_EXPORTS, _diag_consts = _read("micromix_diag.h")
 globals().update(_consts, **_diag_consts)
 # CALIB_EXPORTS: the entries of include/micromix_calib.h, exported by the product library next to EXPORTS; the header defines no constant
 _CALIB_PROTOS, CALIB_EXPORTS, _ = _read("micromix_calib.h")
+# LOGPROB_EXPORTS: the entries of include/micromix_logprob.h, exported and bound the same way; the header defines no constant either
+_LOGPROB_PROTOS, LOGPROB_EXPORTS, _ = _read("micromix_logprob.h")
 
 _lib = None
 
@@ -131,7 +133,7 @@ def load():
         raise MicroMixLibraryError(
             f"{LIB_PATH} is missing: build it with `python -m micromix_amd.build` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
-    _lib = _bind(_bind(ctypes.CDLL(LIB_PATH), _PROTOS), _CALIB_PROTOS)
+    _lib = _bind(_bind(_bind(ctypes.CDLL(LIB_PATH), _PROTOS), _CALIB_PROTOS), _LOGPROB_PROTOS)
     return _lib
 
 

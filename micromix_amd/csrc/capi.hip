@@ -1,6 +1,7 @@
 // extern "C" surface of libmicromix_hip.so -- see include/micromix_hip.h.
 #include "../../include/micromix_hip.h"
 #include "../../include/micromix_calib.h"
+#include "../../include/micromix_logprob.h"
 #include "mx_common.h"
 #include "mx_kernels.h"
 #include "mx_kv_shared_host.h"
@@ -762,6 +763,35 @@ int mm_calib_accumulate(const void *x, int dtype, int rows, int K, long long ld,
     hipError_t e = mm::launch_calib_accumulate(x, dtype == 1, rows, K, ld, lamda, (float *)score_f32, (long long *)counts_i64, workspace,
                                                (hipStream_t)stream);
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_calib_accumulate");
+}
+
+// ---- token log-probabilities (logprob.hip, include/micromix_logprob.h)
+static int logprob_refused(int rows, int vocab, long long ld, int top_n) {
+    if (rows < 0 || vocab < 1 || ld < vocab || top_n < 0 || top_n > 32) return MM_ERR_BAD_ARG;
+    if (vocab > MM_ARGMAX_MAX_VOCAB || rows > MM_ARGMAX_MAX_ROWS) return MM_ERR_UNSUPPORTED;
+    return MM_OK;
+}
+
+size_t mm_logprob_rows_workspace_bytes(int rows, int vocab, int top_n) {
+    return logprob_refused(rows, vocab, vocab, top_n) || rows == 0 ? 0 : mm::logprob_workspace_bytes(rows, vocab, top_n);
+}
+
+int mm_logprob_rows(const void *logits_bf16, int rows, int vocab, long long ld, const int32_t *target, const float *temperature,
+                    float *logprob, int32_t *rank, float *lse, int top_n, int32_t *top_idx, float *top_logprob, void *workspace,
+                    size_t workspace_bytes, mm_stream_t stream) {
+    if (int st = logprob_refused(rows, vocab, ld, top_n)) return st;
+    if (rows == 0) return MM_OK;
+    if (!logits_bf16 || ((uintptr_t)logits_bf16 & 1)) return MM_ERR_BAD_ARG;
+    if ((((uintptr_t)target | (uintptr_t)temperature | (uintptr_t)logprob | (uintptr_t)rank | (uintptr_t)lse | (uintptr_t)top_idx |
+          (uintptr_t)top_logprob) & 3)) return MM_ERR_BAD_ARG;
+    if (!target != !logprob || (rank && !target)) return MM_ERR_BAD_ARG;
+    if (top_n > 0 && (!top_idx || !top_logprob)) return MM_ERR_BAD_ARG;
+    if (!target && !lse && top_n == 0) return MM_ERR_BAD_ARG;                     // nothing asked for
+    const size_t need = mm::logprob_workspace_bytes(rows, vocab, top_n);
+    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7)) return MM_ERR_BAD_ARG;
+    hipError_t e = mm::launch_logprob_rows(logits_bf16, rows, vocab, ld, target, temperature, logprob, rank, lse, top_n, top_idx, top_logprob,
+                                           workspace, (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_logprob_rows");
 }
 
 // the un-windowed entry points are the windowed ones at window = 0

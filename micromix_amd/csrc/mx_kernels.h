@@ -303,6 +303,12 @@ hipError_t launch_verify_greedy(const int *target_tok, const int *draft_tok, con
 size_t sample_workspace_bytes(int rows, int vocab);
 hipError_t launch_sample_rows(const void *logits, int rows, int vocab, long long ld, const float *u, const float *temperature,
                               const int *top_k, const float *top_p, const float *min_p, int *out, void *ws, hipStream_t stream);
+// token log-probabilities over bf16 rows (logprob.hip, include/micromix_logprob.h): target and temperature device arrays of `rows`
+// entries or null, every output null when not wanted, top_n 0 .. 32; ws: logprob_workspace_bytes, uninitialised
+size_t logprob_workspace_bytes(int rows, int vocab, int top_n);
+hipError_t launch_logprob_rows(const void *logits, int rows, int vocab, long long ld, const int *target, const float *temperature,
+                               float *logprob, int *rank, float *lse, int top_n, int *top_idx, float *top_logprob, void *ws,
+                               hipStream_t stream);
 // calibration statistics of one batch (calib_stats.hip, include/micromix_calib.h): x [rows, K] bf16 or fp16, K a multiple of 128 up to
 // 32768, rows >= 1; ws: calib_workspace_bytes, uninitialised
 size_t calib_workspace_bytes(int rows, int K);

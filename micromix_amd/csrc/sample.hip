@@ -24,19 +24,12 @@
 #include "../../include/micromix_hip.h"
 #include "mx_argmax_key.h"
 #include "mx_kernels.h"
+#include "mx_row_weights.h"
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace mm {
-
-typedef unsigned long long u64;
-
-constexpr int SMP_THREADS = 256, SMP_VECS = MM_ARGMAX_CHUNK / 8 / SMP_THREADS;      // lanes per workgroup; 16-byte vectors per lane
-constexpr int SMP_RUN = MM_ARGMAX_CHUNK / SMP_THREADS;                              // consecutive columns per lane in the draw
-static_assert(SMP_VECS * SMP_THREADS * 8 == MM_ARGMAX_CHUNK && SMP_RUN * SMP_THREADS == MM_ARGMAX_CHUNK, "a part divides among the lanes");
-constexpr float SMP_ONE = 0x1p43f;                                                  // W of the maximum: 2^20 tokens stay below 2^64
-constexpr float LOG2E = 1.4426950408889634f;
 
 // what the select launches hand on, one per row
 struct SampleRow {
@@ -82,51 +75,11 @@ __device__ inline RowRule row_rule(const SampleParams &a, int row) {
     return r;
 }
 
-// w of one token.  l == m gives exactly 1 whatever T (0 * inf never forms); -inf gives 0 whatever T (inf * 0 never forms)
-__device__ inline float weight(unsigned bits, unsigned key, const RowRule &r) {
-    const float d = __uint_as_float(bits << 16) - r.m;
-    const float t = d == 0.0f ? 0.0f : d * r.c;
-    return key == 0u ? 0.0f : __builtin_amdgcn_exp2f(t);
-}
-
-__device__ inline u64 fixed(float w) { return (u64)(w * SMP_ONE); }
-
 // W of a token if it is kept, else 0
 __device__ inline u64 kept_mass(unsigned bits, unsigned kt, const RowRule &r) {
     const unsigned key = argmax_key(bits);
     const float w = weight(bits, key, r);
     return key >= kt && (!r.has_q || w >= r.q) ? fixed(w) : 0ull;
-}
-
-// f(bits) for every column of a part, each once, in no particular order: the peel and the vector loads of argmax_rows_kernel
-template <class F>
-__device__ inline void for_each_in_part(const uint16_t *p, int len, int t, F f) {
-    const int head = min(len, (int)((8u - (unsigned)((uintptr_t)p >> 1)) & 7u));    // elements in front of the first 16-byte boundary
-    const int nb = (len - head) >> 3, tail = len - head - 8 * nb;                   // whole vectors; elements behind the last
-    const us8 *body = (const us8 *)(p + head);
-    us8 raw[SMP_VECS];
-#pragma unroll
-    for (int u = 0; u < SMP_VECS; ++u) {
-        const int v = t + u * SMP_THREADS;
-        raw[u] = v < nb ? body[v] : (us8)BF16_NEG_INF;
-    }
-    // lanes 0 .. 7 the head, lanes 8 .. 15 the tail, an element each
-    const int peel = t < head ? t : (t >= 8 && t - 8 < tail) ? head + 8 * nb + t - 8 : -1;
-    const unsigned peeled = peel >= 0 ? p[peel] : 0u;
-#pragma unroll
-    for (int u = 0; u < SMP_VECS; ++u) {
-        if (t + u * SMP_THREADS < nb) {                                             // a filled vector is no token: it is not counted
-#pragma unroll
-            for (int e = 0; e < 8; ++e) f((unsigned)raw[u][e]);
-        }
-    }
-    if (peel >= 0) f(peeled);
-}
-
-__device__ inline u64 wave_sum(u64 x) {
-#pragma unroll
-    for (int off = 32; off; off >>= 1) x += (u64)__shfl_xor((long long)x, off);
-    return x;
 }
 
 // grid (parts, rows).  level 1: bins are the key's high byte; level 2: its low byte, for the keys whose high byte is state[row].bin

@@ -1,9 +1,12 @@
 """The paged KV cache and what runs over it, as `mixedgemm` exports it: append (with RoPE), page copy and row moves, decode, shared-prefix
-decode and prefill attention (include/micromix_hip.h, mm_kv_append .. mm_paged_prefill_tree), and the end of a speculative step:
-`argmax_rows` / `sample_rows` -> `verify_greedy`.  None of it is an export of the reference module (its append_kv_i4 / _f16 take K/V
+decode and prefill attention (include/micromix_hip.h, mm_kv_append .. mm_paged_prefill_tree), the end of a speculative step:
+`argmax_rows` / `sample_rows` -> `verify_greedy`, and what the logits say about a token: `logprob_rows` / `cross_entropy`
+(include/micromix_logprob.h).  None of it is an export of the reference module (its append_kv_i4 / _f16 take K/V
 already quantized and one head count); micromix_amd/kvcache.py is the small cache object on top.  Every wrapper runs on torch's
 current stream and is capture-safe."""
 from __future__ import annotations
+
+from collections import namedtuple
 
 import torch
 
@@ -12,12 +15,13 @@ from ._args import _check_tensor, _launch, _lead, _lib_with, _ok, _opt, _out, _p
 
 __all__ = ["kv_append", "rope_kv_append", "kv_copy_pages", "kv_move_rows", "paged_decode", "paged_decode_workspace_bytes", "paged_decode_shared",
            "paged_decode_shared_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes", "argmax_rows", "argmax_rows_workspace_bytes",
-           "verify_greedy", "sample_rows", "sample_rows_workspace_bytes"]
+           "verify_greedy", "sample_rows", "sample_rows_workspace_bytes", "logprob_rows", "logprob_rows_workspace_bytes", "cross_entropy"]
 
 # entries a library built before them lacks: (the symbol looked for, the names and the feature of the rebuild message)
 _TREE = ("mm_paged_prefill_tree", "mm_paged_prefill_tree / mm_kv_move_rows", "tree-masked attention")
 _VERIFY = ("mm_verify_greedy", "mm_argmax_rows / mm_verify_greedy", "draft verification")
 _SAMPLE = ("mm_sample_rows", "mm_sample_rows", "the sampler")
+_LOGPROB = ("mm_logprob_rows", "mm_logprob_rows", "token log-probabilities")
 _SHARED = ("mm_paged_decode_shared", "mm_paged_decode_shared", "shared-prefix decode")
 
 
@@ -279,6 +283,93 @@ def sample_rows(logits, u, *, temperature=None, top_k=None, top_p=None, min_p=No
     _launch("sample_rows", dev, lib.mm_sample_rows, _ptr(logits), rows, vocab, ld, _ptr(u), _opt(temperature), _opt(top_k), _opt(top_p),
             _opt(min_p), _ptr(out), *ws_args, _stream_ptr(dev))
     return out
+
+
+LogprobRows = namedtuple("LogprobRows", ["logprob", "rank", "lse", "top_idx", "top_logprob"])
+
+
+def logprob_rows_workspace_bytes(rows, vocab, top_n=0):
+    """bytes of workspace `logprob_rows` needs for bf16 logits [rows, vocab]: at most 24 + 8 top_n bytes per part of MM_ARGMAX_CHUNK
+    columns of every row and 8 bytes per row"""
+    return int(_lib_with(*_LOGPROB).mm_logprob_rows_workspace_bytes(int(rows), int(vocab), int(top_n)))
+
+
+def _targets(targets, rows, vocab, dev):
+    """the int32 [rows] targets `mm_logprob_rows` takes; int64 (what a tokenizer and torch hand over) is narrowed on the device, a value
+    outside [0, vocab) becoming -1, which is ignored like every other such value"""
+    if isinstance(targets, torch.Tensor) and targets.dtype is torch.int64:
+        _tensor(targets, "targets", torch.int64, dev, (rows,), "int32 or int64 {0}, one entry per row")
+        return torch.where((targets >= 0) & (targets < vocab), targets, -1).to(torch.int32)
+    if not isinstance(targets, torch.Tensor):
+        raise TypeError(f"targets must be None or an int32 or int64 device tensor [{rows}], got {type(targets).__name__}")
+    return _tensor(targets, "targets", torch.int32, dev, (rows,), "int32 or int64 {0}, one entry per row")
+
+
+def logprob_rows(logits, targets=None, *, temperature=None, top_n=0, workspace=None):
+    """Log-probabilities of tokens under softmax(logits / T): logits bf16 [rows, vocab] on the device as `argmax_rows` takes them (any
+    row stride >= vocab, any 2-byte-aligned offset, nothing copied).  Returns the named tuple (logprob, rank, lse, top_idx,
+    top_logprob), with None for what was not asked for:
+
+    logprob, rank   fp32 / int32 [rows], with `targets` (int32 or int64 [rows] on the device): the log-probability of targets[r] and the
+                    number of tokens whose logit is greater (0: the target is a greedy token, lm-eval's is_greedy).  A target < 0 or
+                    >= vocab is ignored: logprob 0.0, rank -1 (CrossEntropyLoss's ignore_index)
+    lse             fp32 [rows], always: log sum_i exp(l_i / T)
+    top_idx,        int32 / fp32 [rows, top_n], with 1 <= top_n <= 32: the top_n tokens by descending logit, the lower index first
+    top_logprob     among equal ones (column 0 is `argmax_rows`' answer bit for bit), and their log-probabilities; -1 and -inf
+                    beyond the vocabulary
+
+    temperature: fp32 [rows] on the device, a Python number (outside graph capture) or None; None, T <= 0 and NaN all mean 1, so a
+    greedy request reports the unscaled distribution.  The distribution is the unfiltered one `sample_rows` draws from -- the same
+    integer masses, summed exactly -- and the logarithm is taken in fp64 of that sum, so the result is a function of the inputs
+    alone: the same bits on every run.  A row whose maximum is NaN or infinite gives NaN values (torch.log_softmax's answer) and the
+    same integers (include/micromix_logprob.h).  vocab <= 2^20, rows <= 65535.  workspace: a contiguous device tensor of
+    `logprob_rows_workspace_bytes(rows, vocab, top_n)` bytes, uninitialised, allocated when not given (under graph capture pass
+    one).  Runs on the current stream, capture-safe."""
+    lib = _lib_with(*_LOGPROB)
+    rows, vocab, ld, dev = _logits(logits)
+    if isinstance(top_n, bool) or not isinstance(top_n, int) or not 0 <= top_n <= 32:
+        raise ValueError(f"top_n must be an int in 0 .. 32, got {top_n!r}")
+    logprob = rank = top_idx = top_logprob = None
+    if targets is not None:
+        targets = _targets(targets, rows, vocab, dev)
+        logprob = torch.empty((rows,), dtype=torch.float32, device=dev)
+        rank = torch.empty((rows,), dtype=torch.int32, device=dev)
+    temperature = _row_param(temperature, "temperature", torch.float32, rows, dev)
+    lse = torch.empty((rows,), dtype=torch.float32, device=dev)
+    if top_n:
+        top_idx = torch.empty((rows, top_n), dtype=torch.int32, device=dev)
+        top_logprob = torch.empty((rows, top_n), dtype=torch.float32, device=dev)
+    workspace, ws_args = _kv_workspace(workspace, logprob_rows_workspace_bytes(rows, vocab, top_n), dev)
+    _launch("logprob_rows", dev, lib.mm_logprob_rows, _ptr(logits), rows, vocab, ld, _opt(targets), _opt(temperature), _opt(logprob),
+            _opt(rank), _ptr(lse), top_n, _opt(top_idx), _opt(top_logprob), *ws_args, _stream_ptr(dev))
+    return LogprobRows(logprob, rank, lse, top_idx, top_logprob)
+
+
+def cross_entropy(logits, labels, *, ignore_index=-100, reduction="mean"):
+    """nn.CrossEntropyLoss's forward for bf16 logits [rows, vocab] and integer labels [rows] on the device, as an fp32 tensor: a scalar
+    for reduction "mean" (over the rows that are not ignored; NaN when all are, as torch gives) and "sum", [rows] for "none" (0 where
+    ignored).  A label equal to `ignore_index`, negative or >= vocab is ignored.
+
+    The per-row term is -`logprob_rows(logits, labels).logprob`: no [rows, vocab] fp32 tensor is formed.  The reduction over the rows
+    is a torch fp64 sum on the device, rounded to fp32 once.  The reference's evaluation applies nn.CrossEntropyLoss to the bf16
+    logits themselves, which rounds the mean loss to bf16's 8 bits of mantissa; this does not.  More than 65535 rows are taken in
+    slices.  Not capture-safe (it allocates and narrows the labels)."""
+    if reduction not in ("mean", "sum", "none"):
+        raise ValueError(f"reduction must be 'mean', 'sum' or 'none', got {reduction!r}")
+    rows, vocab, ld, dev = _logits(logits)
+    if not isinstance(labels, torch.Tensor) or labels.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"labels must be an int32 or int64 device tensor [{rows}]")
+    _tensor(labels, "labels", labels.dtype, dev, (rows,), "{2} {0}, one entry per row")
+    labels = torch.where(labels == ignore_index, -1, labels)
+    step = _lib.MM_ARGMAX_MAX_ROWS
+    nll = torch.cat([-logprob_rows(logits[i:i + step], labels[i:i + step]).logprob for i in range(0, rows, step)]) if rows else \
+        torch.zeros((0,), dtype=torch.float32, device=dev)
+    if reduction == "none":
+        return nll
+    total = nll.sum(dtype=torch.float64)
+    if reduction == "mean":
+        total = total / ((labels >= 0) & (labels < vocab)).sum()
+    return total.to(torch.float32)
 
 
 def verify_greedy(target_tok, draft_tok, root_tok, qo_indptr, kv_indptr, last_page_len, page_size, *, tree_mask=None, result=None,
