@@ -120,6 +120,8 @@ globals().update(_consts, **_diag_consts)
 _CALIB_PROTOS, CALIB_EXPORTS, _ = _read("micromix_calib.h")
 # LOGPROB_EXPORTS: the entries of include/micromix_logprob.h, exported and bound the same way; the header defines no constant either
 _LOGPROB_PROTOS, LOGPROB_EXPORTS, _ = _read("micromix_logprob.h")
+# LOGITS_EXPORTS: the entry of include/micromix_logits.h, likewise
+_LOGITS_PROTOS, LOGITS_EXPORTS, _ = _read("micromix_logits.h")
 
 _lib = None
 
@@ -133,7 +135,7 @@ def load():
         raise MicroMixLibraryError(
             f"{LIB_PATH} is missing: build it with `python -m micromix_amd.build` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
-    _lib = _bind(_bind(_bind(ctypes.CDLL(LIB_PATH), _PROTOS), _CALIB_PROTOS), _LOGPROB_PROTOS)
+    _lib = _bind(_bind(_bind(_bind(ctypes.CDLL(LIB_PATH), _PROTOS), _CALIB_PROTOS), _LOGPROB_PROTOS), _LOGITS_PROTOS)
     return _lib
 
 

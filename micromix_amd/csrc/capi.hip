@@ -2,6 +2,7 @@
 #include "../../include/micromix_hip.h"
 #include "../../include/micromix_calib.h"
 #include "../../include/micromix_logprob.h"
+#include "../../include/micromix_logits.h"
 #include "mx_common.h"
 #include "mx_kernels.h"
 #include "mx_kv_shared_host.h"
@@ -792,6 +793,37 @@ int mm_logprob_rows(const void *logits_bf16, int rows, int vocab, long long ld, 
     hipError_t e = mm::launch_logprob_rows(logits_bf16, rows, vocab, ld, target, temperature, logprob, rank, lse, top_n, top_idx, top_logprob,
                                            workspace, (hipStream_t)stream);
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_logprob_rows");
+}
+
+// ---- penalties, bias and mask before a token is picked (logits_process.hip, include/micromix_logits.h)
+int mm_process_logits(const void *logits_bf16, int rows, int vocab, long long ld_in, void *out_bf16, long long ld_out, const int32_t *tokens,
+                      long long ld_tok, int n_seq, const int32_t *row_seq, const int32_t *prompt_len, const int32_t *total_len,
+                      const float *repetition_penalty, const float *frequency_penalty, const float *presence_penalty,
+                      const int32_t *bias_idx, const float *bias_val, int n_bias, const int32_t *allowed_mask, long long ld_mask,
+                      mm_stream_t stream) {
+    if (rows < 0 || vocab < 1 || ld_in < vocab || ld_out < vocab || n_bias < 0) return MM_ERR_BAD_ARG;
+    if (tokens && (n_seq < 1 || ld_tok < 1)) return MM_ERR_BAD_ARG;
+    if (allowed_mask && ld_mask < ((long long)vocab + 31) / 32) return MM_ERR_BAD_ARG;
+    if (rows > 0) {                                                                 // every refusal of an argument comes before a limit
+        const uintptr_t in = (uintptr_t)logits_bf16, out = (uintptr_t)out_bf16;
+        if (!in || !out || ((in | out) & 1)) return MM_ERR_BAD_ARG;
+        if (tokens ? !prompt_len || !total_len : prompt_len || total_len || row_seq || repetition_penalty || frequency_penalty || presence_penalty)
+            return MM_ERR_BAD_ARG;
+        if (!bias_idx != !bias_val || (n_bias > 0) != (bias_idx != nullptr)) return MM_ERR_BAD_ARG;
+        if ((((uintptr_t)tokens | (uintptr_t)row_seq | (uintptr_t)prompt_len | (uintptr_t)total_len | (uintptr_t)repetition_penalty |
+              (uintptr_t)frequency_penalty | (uintptr_t)presence_penalty | (uintptr_t)bias_idx | (uintptr_t)bias_val | (uintptr_t)allowed_mask) & 3))
+            return MM_ERR_BAD_ARG;
+        // the in-place form, or spans of (rows - 1) ld + vocab elements that do not meet
+        const uintptr_t in_end = in + 2 * ((uintptr_t)(rows - 1) * (uintptr_t)ld_in + (uintptr_t)vocab);
+        const uintptr_t out_end = out + 2 * ((uintptr_t)(rows - 1) * (uintptr_t)ld_out + (uintptr_t)vocab);
+        if (!(in == out && ld_in == ld_out) && in < out_end && out < in_end) return MM_ERR_BAD_ARG;
+    }
+    if (vocab > MM_ARGMAX_MAX_VOCAB || rows > MM_ARGMAX_MAX_ROWS || n_bias > (1 << 20) || (tokens && ld_tok > (1 << 24))) return MM_ERR_UNSUPPORTED;
+    if (rows == 0) return MM_OK;
+    hipError_t e = mm::launch_process_logits(logits_bf16, rows, vocab, ld_in, out_bf16, ld_out, tokens, ld_tok, n_seq, row_seq, prompt_len,
+                                             total_len, repetition_penalty, frequency_penalty, presence_penalty, bias_idx, bias_val, n_bias,
+                                             allowed_mask, ld_mask, (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_process_logits");
 }
 
 // the un-windowed entry points are the windowed ones at window = 0

@@ -309,6 +309,12 @@ size_t logprob_workspace_bytes(int rows, int vocab, int top_n);
 hipError_t launch_logprob_rows(const void *logits, int rows, int vocab, long long ld, const int *target, const float *temperature,
                                float *logprob, int *rank, float *lse, int top_n, int *top_idx, float *top_logprob, void *ws,
                                hipStream_t stream);
+// penalties, bias and mask over bf16 rows (logits_process.hip, include/micromix_logits.h): every optional array null when off, one launch,
+// no workspace
+hipError_t launch_process_logits(const void *logits, int rows, int vocab, long long ld_in, void *out, long long ld_out, const int *tokens,
+                                 long long ld_tok, int n_seq, const int *row_seq, const int *prompt_len, const int *total_len,
+                                 const float *repetition, const float *frequency, const float *presence, const int *bias_idx,
+                                 const float *bias_val, int n_bias, const int *mask, long long ld_mask, hipStream_t stream);
 // calibration statistics of one batch (calib_stats.hip, include/micromix_calib.h): x [rows, K] bf16 or fp16, K a multiple of 128 up to
 // 32768, rows >= 1; ws: calib_workspace_bytes, uninitialised
 size_t calib_workspace_bytes(int rows, int K);

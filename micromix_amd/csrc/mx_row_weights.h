@@ -4,6 +4,8 @@
 // A weight w = exp2((l - m) * c), c = log2e / T, fp32 in [0, 1], becomes W = trunc(w * 2^43), a 64-bit integer: 2^20 of them cannot
 // overflow and integer addition is associative, so a sum of W's is the same number however a row is divided among lanes, waves and
 // workgroups and whoever finishes first.
+//
+// logits_process.hip (mm_process_logits) uses the walk alone, and the two helpers that write a walked part back: part_head, store_part.
 #pragma once
 
 #include "../../include/micromix_hip.h"
@@ -64,6 +66,34 @@ __device__ inline void for_each_in_part_at(const uint16_t *p, int len, int t, F 
 template <class F>
 __device__ inline void for_each_in_part(const uint16_t *p, int len, int t, F f) {
     for_each_in_part_at(p, len, t, [&](unsigned bits, int, int) { f(bits); });
+}
+
+// the elements the walk finds in front of the first 16-byte boundary of a part read at p: slot 8 u + e of lane t is column
+// part_head + 8 (t + u SMP_THREADS) + e
+__device__ inline int part_head(const uint16_t *p, int len) { return min(len, (int)((8u - (unsigned)((uintptr_t)p >> 1)) & 7u)); }
+
+// The walk's columns written back: v[u][e] is the new value of the column the walk handed out as slot 8 u + e, `peeled` that of slot
+// SMP_RUN, for the lane's columns of the part of `len` columns that was read at p and is written at q (q == p: in place).  Every lane
+// writes exactly the columns it was handed.  Where q is congruent to p mod 16 a vector of p is a vector of q and goes out as one
+// 16-byte store; otherwise its 8 elements go out one by one: the same bits either way
+__device__ inline void store_part(uint16_t *q, const uint16_t *p, int len, int t, const us8 (&v)[SMP_VECS], unsigned peeled) {
+    const int head = part_head(p, len);
+    const int nb = (len - head) >> 3, tail = len - head - 8 * nb;
+    const bool congruent = ((((uintptr_t)q ^ (uintptr_t)p) >> 1) & 7u) == 0;
+#pragma unroll
+    for (int u = 0; u < SMP_VECS; ++u) {
+        const int at = t + u * SMP_THREADS;
+        if (at < nb) {
+            if (congruent) {
+                *(us8 *)(q + head + 8 * at) = v[u];
+            } else {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) q[head + 8 * at + e] = (uint16_t)v[u][e];
+            }
+        }
+    }
+    const int peel = t < head ? t : (t >= 8 && t - 8 < tail) ? head + 8 * nb + t - 8 : -1;
+    if (peel >= 0) q[peel] = (uint16_t)peeled;
 }
 
 __device__ inline u64 wave_sum(u64 x) {

@@ -1,7 +1,7 @@
 """The paged KV cache and what runs over it, as `mixedgemm` exports it: append (with RoPE), page copy and row moves, decode, shared-prefix
 decode and prefill attention (include/micromix_hip.h, mm_kv_append .. mm_paged_prefill_tree), the end of a speculative step:
-`argmax_rows` / `sample_rows` -> `verify_greedy`, and what the logits say about a token: `logprob_rows` / `cross_entropy`
-(include/micromix_logprob.h).  None of it is an export of the reference module (its append_kv_i4 / _f16 take K/V
+`process_logits` (include/micromix_logits.h) -> `argmax_rows` / `sample_rows` -> `verify_greedy`, and what the logits say about a
+token: `logprob_rows` / `cross_entropy` (include/micromix_logprob.h).  None of it is an export of the reference module (its append_kv_i4 / _f16 take K/V
 already quantized and one head count); micromix_amd/kvcache.py is the small cache object on top.  Every wrapper runs on torch's
 current stream and is capture-safe."""
 from __future__ import annotations
@@ -15,13 +15,15 @@ from ._args import _check_tensor, _launch, _lead, _lib_with, _ok, _opt, _out, _p
 
 __all__ = ["kv_append", "rope_kv_append", "kv_copy_pages", "kv_move_rows", "paged_decode", "paged_decode_workspace_bytes", "paged_decode_shared",
            "paged_decode_shared_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes", "argmax_rows", "argmax_rows_workspace_bytes",
-           "verify_greedy", "sample_rows", "sample_rows_workspace_bytes", "logprob_rows", "logprob_rows_workspace_bytes", "cross_entropy"]
+           "verify_greedy", "sample_rows", "sample_rows_workspace_bytes", "logprob_rows", "logprob_rows_workspace_bytes", "cross_entropy",
+           "process_logits"]
 
 # entries a library built before them lacks: (the symbol looked for, the names and the feature of the rebuild message)
 _TREE = ("mm_paged_prefill_tree", "mm_paged_prefill_tree / mm_kv_move_rows", "tree-masked attention")
 _VERIFY = ("mm_verify_greedy", "mm_argmax_rows / mm_verify_greedy", "draft verification")
 _SAMPLE = ("mm_sample_rows", "mm_sample_rows", "the sampler")
 _LOGPROB = ("mm_logprob_rows", "mm_logprob_rows", "token log-probabilities")
+_LOGITS = ("mm_process_logits", "mm_process_logits", "logits processing")
 _SHARED = ("mm_paged_decode_shared", "mm_paged_decode_shared", "shared-prefix decode")
 
 
@@ -370,6 +372,96 @@ def cross_entropy(logits, labels, *, ignore_index=-100, reduction="mean"):
     if reduction == "mean":
         total = total / ((labels >= 0) & (labels < vocab)).sum()
     return total.to(torch.float32)
+
+
+def _rows_of(t, name, dtype, rows, dev, min_cols=0):
+    """an optional [rows, n] array of `process_logits` (n >= min_cols; rows None: one row or more), as _tensor checks it; returns
+    (t, n)"""
+    if t is None:
+        return None, 0
+    lead = "n_seq" if rows is None else rows
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be None or a {dtype} device tensor [{lead}, n], got {type(t).__name__}")
+    _tensor(t, name, dtype, dev)
+    if t.dim() != 2 or (t.size(0) < 1 if rows is None else t.size(0) != rows) or t.size(1) < max(min_cols, 1):
+        raise RuntimeError(f"{name} must be {dtype} [{lead}, n] with n >= {max(min_cols, 1)}, got {list(t.shape)}")
+    return t, t.size(1)
+
+
+def _row_array(t, name, dtype, rows, dev):
+    """an optional per-row device array of `process_logits`: a tensor only, since the kernel is what reads it"""
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be None or a {dtype} device tensor [{rows}], got {type(t).__name__}")
+    return _tensor(t, name, dtype, dev, (rows,), "{2} {0}, one entry per row")
+
+
+def process_logits(logits, *, out=None, tokens=None, prompt_len=None, total_len=None, row_seq=None, repetition_penalty=None,
+                   frequency_penalty=None, presence_penalty=None, bias_idx=None, bias_val=None, allowed_mask=None):
+    """What a request does to the logits before a token is picked, in one launch: repetition, frequency and presence penalties over a
+    token history, a bias list and an allowed-token bitmask.  logits bf16 [rows, vocab] on the device as `argmax_rows` takes them (any
+    row stride >= vocab, any 2-byte-aligned offset).  Returns `out`, bf16 [rows, vocab]: a new tensor for None, `logits` itself for
+    the in-place form, or any tensor or strided view of that shape that does not otherwise overlap the logits; columns beyond vocab
+    of a padded `out` are not written.  `sample_rows`, `argmax_rows` and `logprob_rows` take the result as it is.
+
+    tokens          int32 [n_seq, ld_tok]: the token history of every sequence, prompt first; ids outside [0, vocab) (padding) are
+                    ignored.  With it prompt_len and total_len, int32 [rows]: row r reads tokens[s][0 .. prompt_len[r]) as its prompt
+                    and [prompt_len[r] .. total_len[r]) as its output (both clamped to the buffer), s = row_seq[r] (int32 [rows]) or
+                    r.  The lengths belong to the row and the buffer to the sequence: n samples of one prompt share a buffer, and
+                    the rows of a chain draft read one buffer under total_len = base + i + 1.  s outside [0, n_seq): no history
+    repetition_penalty   fp32 [rows]: a token seen in prompt or output has its logit x divided by it (x < 0: multiplied), HF's rule;
+                    a value that is not finite and > 0 is off
+    frequency_penalty, presence_penalty   fp32 [rows]: a token that occurs c > 0 times in the output loses frequency * c, then
+                    presence (vLLM's and OpenAI's rule); NaN is off
+    bias_idx, bias_val   int32 / fp32 [rows, n]: bias_val[r][j] is added to token bias_idx[r][j]; of several entries for one token
+                    the last (highest j) counts; ids outside [0, vocab) are padding; -inf bans a token
+    allowed_mask    int32 [rows, >= ceil(vocab / 32)]: xgrammar's bitmask; a token whose bit is clear becomes -inf
+    Every one of them is a device tensor that only the kernel reads, so a captured graph serves requests rewritten in place; None
+    is off.  The steps run in the order above, each a correctly rounded fp32 operation on (float)logit, the result rounded to bf16
+    once (include/micromix_logits.h): a function of the inputs alone, the same bits on every run.  vocab <= 2^20, rows <= 65535,
+    ld_tok <= 2^24, n <= 2^20.  No workspace, nothing allocated but a missing `out`.  Runs on the current stream, capture-safe."""
+    lib = _lib_with(*_LOGITS)
+    rows, vocab, ld_in, dev = _logits(logits)
+    if out is None:
+        out = torch.empty((rows, vocab), dtype=torch.bfloat16, device=dev)
+        ld_out = vocab
+    elif out is logits:
+        ld_out = ld_in
+    else:
+        try:
+            orows, ovocab, ld_out, odev = _logits(out)
+        except (TypeError, RuntimeError) as e:
+            raise type(e)(str(e).replace("logits", "out")) from None
+        if (orows, ovocab) != (rows, vocab) or odev != dev:
+            raise RuntimeError(f"out must be bf16 [{rows}, {vocab}] on {dev}, got {list(out.shape)} on {odev}")
+    tokens, ld_tok = _rows_of(tokens, "tokens", torch.int32, None, dev)
+    n_seq = tokens.size(0) if tokens is not None else 0
+    per_row = dict(prompt_len=prompt_len, total_len=total_len, row_seq=row_seq, repetition_penalty=repetition_penalty,
+                   frequency_penalty=frequency_penalty, presence_penalty=presence_penalty)
+    if tokens is None:
+        given = [n for n, v in per_row.items() if v is not None]
+        if given:
+            raise RuntimeError(f"{given[0]} needs tokens: the history it is applied over")
+    elif prompt_len is None or total_len is None:
+        raise RuntimeError(f"{'prompt_len' if prompt_len is None else 'total_len'} is required with tokens (int32 [{rows}])")
+    prompt_len = _row_array(prompt_len, "prompt_len", torch.int32, rows, dev)
+    total_len = _row_array(total_len, "total_len", torch.int32, rows, dev)
+    row_seq = _row_array(row_seq, "row_seq", torch.int32, rows, dev)
+    repetition_penalty = _row_array(repetition_penalty, "repetition_penalty", torch.float32, rows, dev)
+    frequency_penalty = _row_array(frequency_penalty, "frequency_penalty", torch.float32, rows, dev)
+    presence_penalty = _row_array(presence_penalty, "presence_penalty", torch.float32, rows, dev)
+    if (bias_idx is None) != (bias_val is None):
+        raise RuntimeError(f"{'bias_val' if bias_val is None else 'bias_idx'} is missing: bias_idx and bias_val come together")
+    bias_idx, n_bias = _rows_of(bias_idx, "bias_idx", torch.int32, rows, dev)
+    bias_val, n_val = _rows_of(bias_val, "bias_val", torch.float32, rows, dev)
+    if n_val != n_bias:
+        raise RuntimeError(f"bias_val must be fp32 {[rows, n_bias]} like bias_idx, got {list(bias_val.shape)}")
+    allowed_mask, ld_mask = _rows_of(allowed_mask, "allowed_mask", torch.int32, rows, dev, (vocab + 31) // 32)
+    _launch("process_logits", dev, lib.mm_process_logits, _ptr(logits), rows, vocab, ld_in, _ptr(out), ld_out, _opt(tokens), ld_tok, n_seq,
+            _opt(row_seq), _opt(prompt_len), _opt(total_len), _opt(repetition_penalty), _opt(frequency_penalty), _opt(presence_penalty),
+            _opt(bias_idx), _opt(bias_val), n_bias, _opt(allowed_mask), ld_mask, _stream_ptr(dev))
+    return out
 
 
 def verify_greedy(target_tok, draft_tok, root_tok, qo_indptr, kv_indptr, last_page_len, page_size, *, tree_mask=None, result=None,
