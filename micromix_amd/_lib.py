@@ -122,6 +122,8 @@ _CALIB_PROTOS, CALIB_EXPORTS, _ = _read("micromix_calib.h")
 _LOGPROB_PROTOS, LOGPROB_EXPORTS, _ = _read("micromix_logprob.h")
 # LOGITS_EXPORTS: the entry of include/micromix_logits.h, likewise
 _LOGITS_PROTOS, LOGITS_EXPORTS, _ = _read("micromix_logits.h")
+# SPEC_EXPORTS: the entries of include/micromix_spec.h, likewise
+_SPEC_PROTOS, SPEC_EXPORTS, _ = _read("micromix_spec.h")
 
 _lib = None
 
@@ -135,7 +137,10 @@ def load():
         raise MicroMixLibraryError(
             f"{LIB_PATH} is missing: build it with `python -m micromix_amd.build` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
-    _lib = _bind(_bind(_bind(_bind(ctypes.CDLL(LIB_PATH), _PROTOS), _CALIB_PROTOS), _LOGPROB_PROTOS), _LOGITS_PROTOS)
+    lib = ctypes.CDLL(LIB_PATH)
+    for protos in (_PROTOS, _CALIB_PROTOS, _LOGPROB_PROTOS, _LOGITS_PROTOS, _SPEC_PROTOS):
+        _bind(lib, protos)
+    _lib = lib
     return _lib
 
 

@@ -3,6 +3,7 @@
 #include "../../include/micromix_calib.h"
 #include "../../include/micromix_logprob.h"
 #include "../../include/micromix_logits.h"
+#include "../../include/micromix_spec.h"
 #include "mx_common.h"
 #include "mx_kernels.h"
 #include "mx_kv_shared_host.h"
@@ -742,6 +743,30 @@ int mm_sample_rows(const void *logits_bf16, int rows, int vocab, long long ld, c
     if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7)) return MM_ERR_BAD_ARG;
     hipError_t e = mm::launch_sample_rows(logits_bf16, rows, vocab, ld, u, temperature, top_k, top_p, min_p, out_idx, workspace, (hipStream_t)stream);
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_sample_rows");
+}
+
+// ---- speculative sampling of chain drafts (spec_sample.hip, include/micromix_spec.h)
+size_t mm_spec_sample_rows_workspace_bytes(int rows, int vocab) {
+    if (rows <= 0 || vocab < 1 || vocab > MM_ARGMAX_MAX_VOCAB || rows > MM_ARGMAX_MAX_ROWS) return 0;
+    return mm::spec_sample_workspace_bytes(rows, vocab);
+}
+
+int mm_spec_sample_rows(const void *logits_bf16, long long ld, const void *draft_logits_bf16, long long draft_ld, int rows, int vocab,
+                        const int32_t *cand_tok, const float *u_accept, const float *u_resample, const float *temperature,
+                        const int32_t *top_k, const float *top_p, const float *min_p, int32_t *out_idx, int32_t *accepted, void *workspace,
+                        size_t workspace_bytes, mm_stream_t stream) {
+    if (rows < 0 || vocab < 1 || ld < vocab || (draft_logits_bf16 && draft_ld < vocab)) return MM_ERR_BAD_ARG;
+    if (vocab > MM_ARGMAX_MAX_VOCAB || rows > MM_ARGMAX_MAX_ROWS) return MM_ERR_UNSUPPORTED;
+    if (rows == 0) return MM_OK;
+    if (!logits_bf16 || !cand_tok || !u_accept || !u_resample || !out_idx) return MM_ERR_BAD_ARG;
+    if (((uintptr_t)logits_bf16 | (uintptr_t)draft_logits_bf16) & 1) return MM_ERR_BAD_ARG;
+    if ((((uintptr_t)cand_tok | (uintptr_t)u_accept | (uintptr_t)u_resample | (uintptr_t)temperature | (uintptr_t)top_k | (uintptr_t)top_p |
+          (uintptr_t)min_p | (uintptr_t)out_idx | (uintptr_t)accepted) & 3)) return MM_ERR_BAD_ARG;
+    const size_t need = mm::spec_sample_workspace_bytes(rows, vocab);
+    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 7)) return MM_ERR_BAD_ARG;
+    hipError_t e = mm::launch_spec_sample_rows(logits_bf16, ld, draft_logits_bf16, draft_ld, rows, vocab, cand_tok, u_accept, u_resample,
+                                               temperature, top_k, top_p, min_p, out_idx, accepted, workspace, (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_spec_sample_rows");
 }
 
 // ---- calibration statistics (calib_stats.hip, include/micromix_calib.h)

@@ -29,6 +29,9 @@ __device__ inline unsigned argmax_key(unsigned u) {                             
     return min((((mag ^ neg) - neg) + 0x7F80u) & 0xFFFFu, KEY_NAN);
 }
 
+// a token id that names a column of the row (mm_spec_sample_rows' candidates: anything else means "no candidate")
+__device__ inline bool in_vocab(int x, int vocab) { return x >= 0 && x < vocab; }
+
 __device__ inline unsigned wave_max(unsigned x) {
 #pragma unroll
     for (int off = 32; off; off >>= 1) x = max(x, (unsigned)__shfl_xor((int)x, off));

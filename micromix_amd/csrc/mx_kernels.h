@@ -295,6 +295,10 @@ hipError_t launch_kv_move_rows(const PagedKV &kv, const int *move_indptr, const 
 int argmax_parts(int vocab);                              // workgroups a row is divided among: ceil(vocab / MM_ARGMAX_CHUNK)
 size_t argmax_workspace_bytes(int rows, int vocab);
 hipError_t launch_argmax_rows(const void *logits, int rows, int vocab, long long ld, int *out, void *ws, hipStream_t stream);
+// ... of two matrices of one shape in the same launches, each with its row distance, answers and workspace; a row of the second whose
+// cand entry (device, `rows` entries) is outside [0, vocab) is not read and gets no answer
+hipError_t launch_argmax_rows_pair(const void *logits, long long ld, int *out, void *ws, const void *logits2, long long ld2, int *out2, void *ws2,
+                                   const int *cand, int rows, int vocab, hipStream_t stream);
 hipError_t launch_verify_greedy(const int *target_tok, const int *draft_tok, const int *root_tok, const void *tree_mask, const int *qo_indptr,
                                 int T, const int *kv_indptr, const int *last_page_len, int P, int B, int *result, int *move_src,
                                 int *move_dst, hipStream_t stream);
@@ -303,6 +307,13 @@ hipError_t launch_verify_greedy(const int *target_tok, const int *draft_tok, con
 size_t sample_workspace_bytes(int rows, int vocab);
 hipError_t launch_sample_rows(const void *logits, int rows, int vocab, long long ld, const float *u, const float *temperature,
                               const int *top_k, const float *top_p, const float *min_p, int *out, void *ws, hipStream_t stream);
+// speculative sampling of chain drafts over bf16 rows (spec_sample.hip, include/micromix_spec.h): draft_logits null = one-hot drafts,
+// accepted null when not wanted, the per-row parameters as launch_sample_rows takes them; ws: spec_sample_workspace_bytes, uninitialised
+size_t spec_sample_workspace_bytes(int rows, int vocab);
+hipError_t launch_spec_sample_rows(const void *logits, long long ld, const void *draft_logits, long long draft_ld, int rows, int vocab,
+                                   const int *cand_tok, const float *u_accept, const float *u_resample, const float *temperature,
+                                   const int *top_k, const float *top_p, const float *min_p, int *out, int *accepted, void *ws,
+                                   hipStream_t stream);
 // token log-probabilities over bf16 rows (logprob.hip, include/micromix_logprob.h): target and temperature device arrays of `rows`
 // entries or null, every output null when not wanted, top_n 0 .. 32; ws: logprob_workspace_bytes, uninitialised
 size_t logprob_workspace_bytes(int rows, int vocab, int top_n);

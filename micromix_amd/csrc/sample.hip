@@ -21,73 +21,31 @@
 //   mass                         the kept mass of every part: key >= kt and w >= min_p
 //   draw                         Z, the part that holds u * Z, and the column inside it
 // The six select launches are left out when top_k and top_p are both null; a row with neither filter on leaves them at once.
+// What spec_sample.hip (mm_spec_sample_rows) shares -- the row's rule, the kept mass of a token, the select as launch_sample_select --
+// is declared in mx_sample_select.h; a row whose SampleParams::cand entry names no token leaves the select at once, unread.
 #include "../../include/micromix_hip.h"
 #include "mx_argmax_key.h"
 #include "mx_kernels.h"
 #include "mx_row_weights.h"
+#include "mx_sample_select.h"
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace mm {
 
-// what the select launches hand on, one per row
-struct SampleRow {
-    u64 above[256];          // level 1: the mass of bin b and every bin above it
-    u64 base;                // the mass above the bin being refined
-    u64 target;              // top-p: the mass the prefix has to reach
-    unsigned need;           // top-k: the tokens the prefix still lacks above the bin being refined
-    int bin;                 // the level-1 bin the next level-2 sweep refines; -1: the threshold is final
-    int for_p;               // that sweep is top-p's (else top-k's)
-    unsigned kt;             // the threshold key: a token is kept when its key is >= kt (and its weight >= min_p)
-};
-
-struct SampleParams {
-    const uint16_t *logits;
-    long long ld;
-    int vocab;
-    const int *out;          // the argmax of every row, written by argmax_rows before any kernel here
-    const float *temperature, *top_p, *min_p;
-    const int *top_k;
-};
-
-// a row's parameters as the rule reads them
-struct RowRule {
-    float m, c, p, q;        // the maximum, log2e / T, top-p (0 for p <= 0), min-p
-    int k;
-    bool greedy, has_k, has_p, has_q;
-};
-
-__device__ inline RowRule row_rule(const SampleParams &a, int row) {
-    RowRule r;
-    const unsigned mbits = a.logits[(long long)row * a.ld + a.out[row]], mkey = argmax_key(mbits);
-    const float T = a.temperature ? a.temperature[row] : 1.0f;
-    r.greedy = mkey == 0u || mkey >= KEY_POS_INF || !(T > 0.0f);                    // -inf, +inf, NaN; T <= 0 or NaN
-    r.m = __uint_as_float(mbits << 16);
-    r.c = LOG2E / T;
-    r.k = a.top_k ? a.top_k[row] : 0;
-    r.has_k = r.k >= 1 && r.k < a.vocab;
-    const float p = a.top_p ? a.top_p[row] : 1.0f;
-    r.has_p = p < 1.0f;                                                              // NaN: off
-    r.p = p > 0.0f ? p : 0.0f;
-    r.q = a.min_p ? a.min_p[row] : 0.0f;
-    r.has_q = r.q > 0.0f && r.q <= 1.0f;
-    return r;
-}
-
-// W of a token if it is kept, else 0
-__device__ inline u64 kept_mass(unsigned bits, unsigned kt, const RowRule &r) {
-    const unsigned key = argmax_key(bits);
-    const float w = weight(bits, key, r);
-    return key >= kt && (!r.has_q || w >= r.q) ? fixed(w) : 0ull;
-}
-
-// grid (parts, rows).  level 1: bins are the key's high byte; level 2: its low byte, for the keys whose high byte is state[row].bin
-__global__ __launch_bounds__(SMP_THREADS) void sample_hist_kernel(SampleParams a, int level, const SampleRow *__restrict__ state,
-                                                                  u64 *__restrict__ hist_mass, unsigned *__restrict__ hist_cnt) {
+// grid (parts, rows) or (parts, rows, 2): z names the side.  level 1: bins are the key's high byte; level 2: its low byte, for the keys
+// whose high byte is state[row].bin
+__global__ __launch_bounds__(SMP_THREADS) void sample_hist_kernel(SelectSide first, SelectSide second, int level) {
     __shared__ u64 s_mass[256];
     __shared__ unsigned s_cnt[256];
     const int t = threadIdx.x, row = blockIdx.y, lo = blockIdx.x * MM_ARGMAX_CHUNK;
+    const SelectSide &side = blockIdx.z ? second : first;
+    const SampleParams &a = side.a;
+    const SampleRow *state = side.state;
+    u64 *hist_mass = side.hist_mass;
+    unsigned *hist_cnt = side.hist_cnt;
+    if (skipped(a, row)) return;
     const RowRule r = row_rule(a, row);
     if (r.greedy || !(r.has_k || r.has_p)) return;
     const int bin = level == 1 ? -1 : state[row].bin;
@@ -113,14 +71,20 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_hist_kernel(SampleParams a
 // the largest bin b with f(b) >= x, where f does not grow with b and f(0) >= x >= 1: lane b tests itself against f(b + 1)
 #define SMP_CROSSES(f_here, f_next, x) ((f_here) >= (x) && (f_next) < (x))
 
-// grid rows, 256 lanes, lane b the bin b.  stage 1 follows the level-1 sweep, stages 2 and 3 a level-2 sweep each
-__global__ __launch_bounds__(256) void sample_finish_kernel(SampleParams a, int stage, int parts, SampleRow *__restrict__ state,
-                                                            const u64 *__restrict__ hist_mass, const unsigned *__restrict__ hist_cnt) {
+// grid rows or (rows, 2): y names the side; 256 lanes, lane b the bin b.  stage 1 follows the level-1 sweep, stages 2 and 3 a level-2
+// sweep each
+__global__ __launch_bounds__(256) void sample_finish_kernel(SelectSide first, SelectSide second, int stage, int parts) {
     __shared__ u64 s_m[257];
     __shared__ unsigned s_c[257];
     __shared__ u64 s_zk;
     __shared__ int s_bin;
     const int t = threadIdx.x, row = blockIdx.x;
+    const SelectSide &side = blockIdx.y ? second : first;
+    const SampleParams &a = side.a;
+    SampleRow *state = side.state;
+    const u64 *hist_mass = side.hist_mass;
+    const unsigned *hist_cnt = side.hist_cnt;
+    if (skipped(a, row)) return;
     const RowRule r = row_rule(a, row);
     if (r.greedy) return;
     SampleRow &st = state[row];
@@ -250,12 +214,10 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_draw_kernel(SampleParams a
     const RowRule r = row_rule(a, row);
     if (r.greedy) return;                                                           // out[row] holds the argmax already
     const unsigned kt = state ? state[row].kt : 0u;
-    float ur = u[row];
-    ur = ur > 0.0f ? fminf(ur, 1.0f - 0x1p-24f) : 0.0f;                             // NaN -> 0
+    const float ur = clamp_u(u[row]);                                               // NaN -> 0
     u64 Z = 0;
     for (int c = 0; c < parts; ++c) Z += part_mass[(long long)row * parts + c];
-    u64 want = (u64)((double)ur * (double)Z);                                       // < Z: the prefix passes it inside the row
-    want = min(want, Z - 1);                                                        // (the maximum is kept: Z >= 2^43)
+    u64 want = sample_want(ur, Z);                                                  // < Z: the prefix passes it inside the row
     int part = 0;
     for (int c = 0; c < parts; ++c) {
         const u64 s = part_mass[(long long)row * parts + c];
@@ -310,9 +272,18 @@ static SampleWorkspace sample_layout(int rows, int vocab) {
 
 size_t sample_workspace_bytes(int rows, int vocab) { return sample_layout(rows, vocab).total; }
 
+hipError_t launch_sample_select(const SelectSide &first, const SelectSide *second, int rows, int parts, hipStream_t stream) {
+    const int sides = second ? 2 : 1;
+    const SelectSide &other = second ? *second : first;
+    for (int stage = 1; stage <= 3; ++stage) {
+        sample_hist_kernel<<<dim3(parts, rows, sides), SMP_THREADS, 0, stream>>>(first, other, stage == 1 ? 1 : 2);
+        sample_finish_kernel<<<dim3(rows, sides), 256, 0, stream>>>(first, other, stage, parts);
+    }
+    return hipGetLastError();
+}
+
 hipError_t launch_sample_rows(const void *logits, int rows, int vocab, long long ld, const float *u, const float *temperature,
                               const int *top_k, const float *top_p, const float *min_p, int *out, void *ws, hipStream_t stream) {
-    static_assert(sizeof(SampleRow) % 8 == 0, "the arrays behind the row states hold 64-bit words");
     const int parts = argmax_parts(vocab);
     const SampleWorkspace w = sample_layout(rows, vocab);
     char *base = (char *)ws;
@@ -321,13 +292,11 @@ hipError_t launch_sample_rows(const void *logits, int rows, int vocab, long long
     SampleRow *state = top_k || top_p ? (SampleRow *)(base + w.state) : nullptr;
     hipError_t e = launch_argmax_rows(logits, rows, vocab, ld, out, base + w.argmax, stream);
     if (e != hipSuccess) return e;
-    const SampleParams a{(const uint16_t *)logits, ld, vocab, out, temperature, top_p, min_p, top_k};
+    const SampleParams a{(const uint16_t *)logits, ld, vocab, out, temperature, top_p, min_p, top_k, nullptr};
     const dim3 grid(parts, rows);
     if (state) {
-        for (int stage = 1; stage <= 3; ++stage) {
-            sample_hist_kernel<<<grid, SMP_THREADS, 0, stream>>>(a, stage == 1 ? 1 : 2, state, hist_mass, hist_cnt);
-            sample_finish_kernel<<<rows, 256, 0, stream>>>(a, stage, parts, state, hist_mass, hist_cnt);
-        }
+        e = launch_sample_select(SelectSide{a, state, hist_mass, hist_cnt}, nullptr, rows, parts, stream);
+        if (e != hipSuccess) return e;
     }
     sample_mass_kernel<<<grid, SMP_THREADS, 0, stream>>>(a, state, part_mass);
     sample_draw_kernel<<<rows, SMP_THREADS, 0, stream>>>(a, u, parts, state, part_mass, out);

@@ -24,14 +24,30 @@ namespace mm {
 constexpr int ARG_THREADS = 256, ARG_VECS = MM_ARGMAX_CHUNK / 8 / ARG_THREADS;      // lanes per workgroup; 16-byte vectors per lane
 static_assert(ARG_VECS * ARG_THREADS * 8 == MM_ARGMAX_CHUNK && MM_ARGMAX_CHUNK <= 65536, "a part is a whole number of vectors per lane");
 
+// the second matrix of a launch with gridDim.z == 2
+struct ArgmaxSecond {
+    const uint16_t *logits;
+    long long ld;
+    int *out;
+    unsigned long long *partial;
+    const int *cand;
+};
+
 // a partial: the key above the bitwise complement of the column, so that the larger word is the larger key, then the lower column
 __device__ inline unsigned long long argmax_pack(unsigned key, unsigned col) { return ((unsigned long long)key << 32) | (0xFFFFFFFFu - col); }
 
-// grid (parts, rows).  One part: out[row] is written; several: partial[row * parts + part]
+// grid (parts, rows) or (parts, rows, 2).  One part: out[row] is written; several: partial[row * parts + part].  z = 1 is a second
+// matrix with its own row distance and outputs (mm_spec_sample_rows' draft rows); a row of it whose cand entry names no token is
+// not read and gets no answer
 __global__ __launch_bounds__(ARG_THREADS) void argmax_rows_kernel(const uint16_t *__restrict__ logits, int vocab, long long ld,
-                                                                  int *__restrict__ out, unsigned long long *__restrict__ partial) {
+                                                                  int *__restrict__ out, unsigned long long *__restrict__ partial,
+                                                                  ArgmaxSecond second) {
     __shared__ unsigned s_key[ARG_THREADS / 64], s_col[ARG_THREADS / 64];
     const int t = threadIdx.x, row = blockIdx.y, lo = blockIdx.x * MM_ARGMAX_CHUNK;
+    if (blockIdx.z) {
+        if (!in_vocab(second.cand[row], vocab)) return;
+        logits = second.logits, ld = second.ld, out = second.out, partial = second.partial;
+    }
     const int len = min(vocab - lo, MM_ARGMAX_CHUNK);                               // >= 1: the grid holds ceil(vocab / CHUNK) parts
     const uint16_t *p = logits + (long long)row * ld + lo;
     const int head = min(len, (int)((8u - (unsigned)((uintptr_t)p >> 1)) & 7u));    // elements in front of the first 16-byte boundary
@@ -90,9 +106,15 @@ __global__ __launch_bounds__(ARG_THREADS) void argmax_rows_kernel(const uint16_t
     }
 }
 
-// one wave per row: the largest of its `parts` partials (at most 2^20 / MM_ARGMAX_CHUNK of them)
-__global__ __launch_bounds__(64) void argmax_finish_kernel(const unsigned long long *__restrict__ partial, int parts, int *__restrict__ out) {
+// one wave per row: the largest of its `parts` partials (at most 2^20 / MM_ARGMAX_CHUNK of them).  grid rows or (rows, 2), the second
+// matrix as above
+__global__ __launch_bounds__(64) void argmax_finish_kernel(const unsigned long long *__restrict__ partial, int parts, int *__restrict__ out,
+                                                           int vocab, ArgmaxSecond second) {
     const int row = blockIdx.x;
+    if (blockIdx.y) {
+        if (!in_vocab(second.cand[row], vocab)) return;
+        partial = second.partial, out = second.out;
+    }
     unsigned long long best = 0;                                                    // below every partial: a column never reaches 2^32 - 1
     for (int c = threadIdx.x; c < parts; c += 64) best = max(best, partial[(long long)row * parts + c]);
 #pragma unroll
@@ -109,8 +131,17 @@ size_t argmax_workspace_bytes(int rows, int vocab) {
 
 hipError_t launch_argmax_rows(const void *logits, int rows, int vocab, long long ld, int *out, void *ws, hipStream_t stream) {
     const int parts = argmax_parts(vocab);
-    argmax_rows_kernel<<<dim3(parts, rows), ARG_THREADS, 0, stream>>>((const uint16_t *)logits, vocab, ld, out, (unsigned long long *)ws);
-    if (parts > 1) argmax_finish_kernel<<<rows, 64, 0, stream>>>((const unsigned long long *)ws, parts, out);
+    argmax_rows_kernel<<<dim3(parts, rows), ARG_THREADS, 0, stream>>>((const uint16_t *)logits, vocab, ld, out, (unsigned long long *)ws, ArgmaxSecond{});
+    if (parts > 1) argmax_finish_kernel<<<rows, 64, 0, stream>>>((const unsigned long long *)ws, parts, out, vocab, ArgmaxSecond{});
+    return hipGetLastError();
+}
+
+hipError_t launch_argmax_rows_pair(const void *logits, long long ld, int *out, void *ws, const void *logits2, long long ld2, int *out2, void *ws2,
+                                   const int *cand, int rows, int vocab, hipStream_t stream) {
+    const int parts = argmax_parts(vocab);
+    const ArgmaxSecond second{(const uint16_t *)logits2, ld2, out2, (unsigned long long *)ws2, cand};
+    argmax_rows_kernel<<<dim3(parts, rows, 2), ARG_THREADS, 0, stream>>>((const uint16_t *)logits, vocab, ld, out, (unsigned long long *)ws, second);
+    if (parts > 1) argmax_finish_kernel<<<dim3(rows, 2), 64, 0, stream>>>((const unsigned long long *)ws, parts, out, vocab, second);
     return hipGetLastError();
 }
 

@@ -1,6 +1,7 @@
 """The paged KV cache and what runs over it, as `mixedgemm` exports it: append (with RoPE), page copy and row moves, decode, shared-prefix
 decode and prefill attention (include/micromix_hip.h, mm_kv_append .. mm_paged_prefill_tree), the end of a speculative step:
-`process_logits` (include/micromix_logits.h) -> `argmax_rows` / `sample_rows` -> `verify_greedy`, and what the logits say about a
+`process_logits` (include/micromix_logits.h) -> `argmax_rows` / `sample_rows` / `spec_sample_rows` (include/micromix_spec.h) ->
+`verify_greedy`, and what the logits say about a
 token: `logprob_rows` / `cross_entropy` (include/micromix_logprob.h).  None of it is an export of the reference module (its append_kv_i4 / _f16 take K/V
 already quantized and one head count); micromix_amd/kvcache.py is the small cache object on top.  Every wrapper runs on torch's
 current stream and is capture-safe."""
@@ -16,7 +17,7 @@ from ._args import _check_tensor, _launch, _lead, _lib_with, _ok, _opt, _out, _p
 __all__ = ["kv_append", "rope_kv_append", "kv_copy_pages", "kv_move_rows", "paged_decode", "paged_decode_workspace_bytes", "paged_decode_shared",
            "paged_decode_shared_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes", "argmax_rows", "argmax_rows_workspace_bytes",
            "verify_greedy", "sample_rows", "sample_rows_workspace_bytes", "logprob_rows", "logprob_rows_workspace_bytes", "cross_entropy",
-           "process_logits"]
+           "process_logits", "spec_sample_rows", "spec_sample_rows_workspace_bytes", "chain_candidates"]
 
 # entries a library built before them lacks: (the symbol looked for, the names and the feature of the rebuild message)
 _TREE = ("mm_paged_prefill_tree", "mm_paged_prefill_tree / mm_kv_move_rows", "tree-masked attention")
@@ -24,6 +25,7 @@ _VERIFY = ("mm_verify_greedy", "mm_argmax_rows / mm_verify_greedy", "draft verif
 _SAMPLE = ("mm_sample_rows", "mm_sample_rows", "the sampler")
 _LOGPROB = ("mm_logprob_rows", "mm_logprob_rows", "token log-probabilities")
 _LOGITS = ("mm_process_logits", "mm_process_logits", "logits processing")
+_SPEC = ("mm_spec_sample_rows", "mm_spec_sample_rows", "speculative sampling")
 _SHARED = ("mm_paged_decode_shared", "mm_paged_decode_shared", "shared-prefix decode")
 
 
@@ -285,6 +287,95 @@ def sample_rows(logits, u, *, temperature=None, top_k=None, top_p=None, min_p=No
     _launch("sample_rows", dev, lib.mm_sample_rows, _ptr(logits), rows, vocab, ld, _ptr(u), _opt(temperature), _opt(top_k), _opt(top_p),
             _opt(min_p), _ptr(out), *ws_args, _stream_ptr(dev))
     return out
+
+
+def spec_sample_rows_workspace_bytes(rows, vocab):
+    """bytes of workspace `spec_sample_rows` needs for bf16 logits [rows, vocab]: 6 KiB + 48 bytes per part of MM_ARGMAX_CHUNK columns
+    of every row and about 4.1 KiB per row"""
+    return int(_lib_with(*_SPEC).mm_spec_sample_rows_workspace_bytes(int(rows), int(vocab)))
+
+
+def spec_sample_rows(logits, draft_logits, cand_tok, u_accept, u_resample, *, temperature=None, top_k=None, top_p=None, min_p=None,
+                     out=None, accepted=None, workspace=None):
+    """Speculative sampling for chain drafts: per row, accept the draft's candidate token with probability min(1, p / q) or redraw
+    from norm(max(0, p - q)).  Returns (out, accepted), int32 [rows] each (the tensors given as `out` / `accepted` when given).  `out`
+    is ready for `verify_greedy` / `verify_launch` as target_tok: the walk then yields the accepted prefix and, as the bonus token,
+    the redraw at the first rejection or the plain sample after the leaf -- distributed exactly as the target model's, and a draft
+    token survives with probability sum min(p, q) where `sample_rows -> verify_greedy` gives sum p q.
+
+    logits          bf16 [rows, vocab] as `sample_rows` takes them: row r is the target's logits after node r
+    draft_logits    bf16 [rows, vocab] (its own row stride and offset; it may be `logits` itself): row r is the draft model's logits
+                    cand_tok[r] was drawn from.  None: one-hot drafts (n-gram, prompt lookup, greedy drafts), q(x) = 1
+    cand_tok        int32 [rows]: the token the draft proposed for the next position (`chain_candidates`); < 0 or >= vocab: none
+    u_accept, u_resample   fp32 [rows] uniform in [0, 1) (`torch.rand`): the library draws no random numbers
+    temperature, top_k, top_p, min_p   as `sample_rows`; the SAME per-row parameters shape p and q, so the draft must have been
+                    sampled under the request's parameters (by `sample_rows` from `draft_logits`: then q is bit for bit what it was
+                    drawn from)
+    accepted[r]     1 accepted, 0 rejected (out[r] is the redraw, never cand_tok[r]), -1 no candidate (out[r] is bit for bit
+                    `sample_rows(logits, u_resample, ...)`).  A greedy row (temperature <= 0, ...) gives `argmax_rows`' answer and
+                    1 / 0 as it equals the candidate
+    p and q are the kept distributions of `sample_rows` as integer masses; the accept test and the residual are formed exactly in
+    128-bit integers (include/micromix_spec.h), so the result is a function of the inputs alone.  Chains only: a row has one
+    candidate.  For a tree draft `sample_rows` -> `verify_greedy` stays the recommendation.  vocab <= 2^20, rows <= 65535.
+    workspace: a contiguous device tensor of `spec_sample_rows_workspace_bytes(rows, vocab)` bytes, uninitialised, allocated when not
+    given (under graph capture pass one).  Runs on the current stream, capture-safe."""
+    lib = _lib_with(*_SPEC)
+    rows, vocab, ld, dev = _logits(logits)
+    draft_ld = vocab
+    if draft_logits is not None:
+        try:
+            drows, dvocab, draft_ld, ddev = _logits(draft_logits)
+        except (TypeError, RuntimeError) as e:
+            raise type(e)(str(e).replace("logits", "draft_logits")) from None
+        if (drows, dvocab) != (rows, vocab) or ddev != dev:
+            raise RuntimeError(f"draft_logits must be bf16 [{rows}, {vocab}] on {dev}, got {list(draft_logits.shape)} on {ddev}")
+    if isinstance(cand_tok, torch.Tensor) and cand_tok.dtype is torch.int64:
+        raise TypeError("cand_tok must be torch.int32, got torch.int64: convert it with cand_tok.to(torch.int32)")
+    if not isinstance(cand_tok, torch.Tensor):
+        raise TypeError(f"cand_tok must be a torch.int32 device tensor [{rows}], got {type(cand_tok).__name__}")
+    _tensor(cand_tok, "cand_tok", torch.int32, dev, (rows,), "{2} {0}, one entry per row")
+    for name, u in (("u_accept", u_accept), ("u_resample", u_resample)):
+        if not isinstance(u, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.float32 device tensor [{rows}] (torch.rand), got {type(u).__name__}")
+        _tensor(u, name, torch.float32, dev, (rows,), "{2} {0}, one entry per row")
+    temperature = _row_param(temperature, "temperature", torch.float32, rows, dev)
+    top_k = _row_param(top_k, "top_k", torch.int32, rows, dev)
+    top_p = _row_param(top_p, "top_p", torch.float32, rows, dev)
+    min_p = _row_param(min_p, "min_p", torch.float32, rows, dev)
+    out = _out(out, "out", torch.int32, dev, (rows,), "int32 {0}")
+    accepted = _out(accepted, "accepted", torch.int32, dev, (rows,), "int32 {0}")
+    workspace, ws_args = _kv_workspace(workspace, spec_sample_rows_workspace_bytes(rows, vocab), dev)
+    _launch("spec_sample_rows", dev, lib.mm_spec_sample_rows, _ptr(logits), ld, _opt(draft_logits), draft_ld, rows, vocab, _ptr(cand_tok),
+            _ptr(u_accept), _ptr(u_resample), _opt(temperature), _opt(top_k), _opt(top_p), _opt(min_p), _ptr(out), _ptr(accepted), *ws_args,
+            _stream_ptr(dev))
+    return out, accepted
+
+
+def chain_candidates(draft_tok, qo_indptr, *, out=None):
+    """The candidates `spec_sample_rows` takes for chain drafts laid out as `verify_greedy` takes them: cand[t] = draft_tok[t + 1]
+    inside a sequence -- the draft token of node t's child -- and -1 on each sequence's last row (the leaf: its row gives the plain
+    sample).  draft_tok int32 [T], qo_indptr int32 [B + 1] with qo_indptr[0] = 0 and qo_indptr[B] = T; returns int32 [T] (`out`
+    when given).  An empty sequence, the first one included, touches no row.  Torch index arithmetic on the tensors' own device with
+    shapes that depend on T and B alone: nothing is read on the host, so it is capture-safe (under capture pass `out`)."""
+    for n, t in (("draft_tok", draft_tok), ("qo_indptr", qo_indptr)):
+        if not isinstance(t, torch.Tensor) or t.dtype is not torch.int32 or t.dim() != 1:
+            raise TypeError(f"{n} must be a one-dimensional torch.int32 tensor")
+    if qo_indptr.device != draft_tok.device or qo_indptr.numel() < 1:
+        raise RuntimeError("qo_indptr must have B + 1 >= 1 entries on draft_tok's device")
+    T = draft_tok.numel()
+    if out is None:
+        out = torch.empty_like(draft_tok)
+    elif not isinstance(out, torch.Tensor) or out.dtype is not torch.int32 or out.shape != draft_tok.shape or out.device != draft_tok.device:
+        raise RuntimeError(f"out must be int32 [{T}] on {draft_tok.device}")
+    if T == 0:
+        return out
+    ends = qo_indptr[1:].to(torch.int64)
+    # the last row of every non-empty sequence; an empty one points at the spare entry T, which is dropped
+    last = torch.where(ends > qo_indptr[:-1], ends - 1, T).clamp_(0, T)
+    is_last = torch.zeros(T + 1, dtype=torch.bool, device=draft_tok.device).index_fill_(0, last, True)
+    out[:T - 1].copy_(draft_tok[1:])
+    out[T - 1:].fill_(-1)
+    return out.masked_fill_(is_last[:T], -1)
 
 
 LogprobRows = namedtuple("LogprobRows", ["logprob", "rank", "lse", "top_idx", "top_logprob"])
