@@ -124,6 +124,11 @@ _LOGPROB_PROTOS, LOGPROB_EXPORTS, _ = _read("micromix_logprob.h")
 _LOGITS_PROTOS, LOGITS_EXPORTS, _ = _read("micromix_logits.h")
 # SPEC_EXPORTS: the entries of include/micromix_spec.h, likewise
 _SPEC_PROTOS, SPEC_EXPORTS, _ = _read("micromix_spec.h")
+# KVSTEP_EXPORTS: the entries of include/micromix_kvstep.h, likewise.  Its integers stay out of the module's MM_* attributes (those are the
+# two headers' above): KV_STEP holds them by name -- the limits, the state's header size, the statuses of a step -- and KV_STEP_STATUS
+# names a status value
+_KVSTEP_PROTOS, KVSTEP_EXPORTS, KV_STEP = _read("micromix_kvstep.h")
+KV_STEP_STATUS = {v: n for n, v in KV_STEP.items() if n not in ("MM_KV_STEP_MAX_BATCH", "MM_KV_STEP_HEADER_INTS")}
 
 _lib = None
 
@@ -138,7 +143,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -m micromix_amd.build` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for protos in (_PROTOS, _CALIB_PROTOS, _LOGPROB_PROTOS, _LOGITS_PROTOS, _SPEC_PROTOS):
+    for protos in (_PROTOS, _CALIB_PROTOS, _LOGPROB_PROTOS, _LOGITS_PROTOS, _SPEC_PROTOS, _KVSTEP_PROTOS):
         _bind(lib, protos)
     _lib = lib
     return _lib

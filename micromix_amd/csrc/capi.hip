@@ -4,6 +4,7 @@
 #include "../../include/micromix_logprob.h"
 #include "../../include/micromix_logits.h"
 #include "../../include/micromix_spec.h"
+#include "../../include/micromix_kvstep.h"
 #include "mx_common.h"
 #include "mx_kernels.h"
 #include "mx_kv_shared_host.h"
@@ -767,6 +768,36 @@ int mm_spec_sample_rows(const void *logits_bf16, long long ld, const void *draft
     hipError_t e = mm::launch_spec_sample_rows(logits_bf16, ld, draft_logits_bf16, draft_ld, rows, vocab, cand_tok, u_accept, u_resample,
                                                temperature, top_k, top_p, min_p, out_idx, accepted, workspace, (hipStream_t)stream);
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_spec_sample_rows");
+}
+
+// ---- one step of the device allocator (kv_step.hip, include/micromix_kvstep.h)
+static int kv_step_refused(int batch, int max_pages, int pages_per_seq) {
+    if (batch < 0 || max_pages < 1 || pages_per_seq < 1) return MM_ERR_BAD_ARG;
+    if (batch > MM_KV_STEP_MAX_BATCH) return MM_ERR_UNSUPPORTED;
+    if (MM_KV_STEP_HEADER_INTS + 3LL * batch + max_pages + (long long)batch * pages_per_seq > INT32_MAX) return MM_ERR_UNSUPPORTED;
+    return MM_OK;
+}
+
+size_t mm_kv_step_state_ints(int batch, int max_pages, int pages_per_seq) {
+    if (batch <= 0 || kv_step_refused(batch, max_pages, pages_per_seq)) return 0;
+    return (size_t)MM_KV_STEP_HEADER_INTS + 3 * (size_t)batch + (size_t)max_pages + (size_t)batch * pages_per_seq;
+}
+
+int mm_kv_step(int32_t *state, int batch, int max_pages, int pages_per_seq, int page_size, int max_seq_len, const int32_t *keep,
+               int keep_stride, const int32_t *next_new, int num_next_tokens, const int32_t *depths, int32_t *kv_indptr, int32_t *kv_indices,
+               long long kv_indices_capacity, int32_t *last_page_len, int32_t *append_indptr, int32_t *token_pos, mm_stream_t stream) {
+    const int refused = kv_step_refused(batch, max_pages, pages_per_seq);
+    if (refused == MM_ERR_BAD_ARG || page_size < 1 || max_seq_len < 1 || num_next_tokens < 0 || kv_indices_capacity < 0) return MM_ERR_BAD_ARG;
+    if ((keep && keep_stride < 1) || (depths && !token_pos)) return MM_ERR_BAD_ARG;
+    if (refused) return refused;
+    if (batch == 0) return MM_OK;
+    if (!state || !next_new || !kv_indptr || !kv_indices || !last_page_len || !append_indptr) return MM_ERR_BAD_ARG;
+    if (((uintptr_t)state | (uintptr_t)keep | (uintptr_t)next_new | (uintptr_t)depths | (uintptr_t)kv_indptr | (uintptr_t)kv_indices |
+         (uintptr_t)last_page_len | (uintptr_t)append_indptr | (uintptr_t)token_pos) & 3) return MM_ERR_BAD_ARG;
+    const mm::KVStep s{state, batch, max_pages, pages_per_seq, page_size, max_seq_len, keep, keep_stride, next_new, num_next_tokens, depths,
+                       kv_indptr, kv_indices, kv_indices_capacity, last_page_len, append_indptr, token_pos};
+    hipError_t e = mm::launch_kv_step(s, (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_kv_step");
 }
 
 // ---- calibration statistics (calib_stats.hip, include/micromix_calib.h)

@@ -314,6 +314,21 @@ hipError_t launch_spec_sample_rows(const void *logits, long long ld, const void 
                                    const int *cand_tok, const float *u_accept, const float *u_resample, const float *temperature,
                                    const int *top_k, const float *top_p, const float *min_p, int *out, int *accepted, void *ws,
                                    hipStream_t stream);
+// one step of the device allocator (kv_step.hip, include/micromix_kvstep.h): the step kernel, one workgroup, then the launch that rebuilds
+// kv_indices and writes token_pos; keep, depths and token_pos null when absent
+struct KVStep {
+    int *state;
+    int B, max_pages, pps, P, max_seq_len;
+    const int *keep;
+    int keep_stride;
+    const int *next_new;
+    int T;
+    const int *depths;
+    int *kv_indptr, *kv_indices;
+    long long capacity;
+    int *last_page_len, *append_indptr, *token_pos;
+};
+hipError_t launch_kv_step(const KVStep &s, hipStream_t stream);
 // token log-probabilities over bf16 rows (logprob.hip, include/micromix_logprob.h): target and temperature device arrays of `rows`
 // entries or null, every output null when not wanted, top_n 0 .. 32; ws: logprob_workspace_bytes, uninitialised
 size_t logprob_workspace_bytes(int rows, int vocab, int top_n);

@@ -109,6 +109,39 @@ Measured (vocabulary 128 256): `argmax_rows` takes 5 to 9 us for 1 to
 8 x faster than torch.argmax; `verify_launch` 5 to 6 us for one sequence's 21-node tree in 32 layers, 42 to 48 us for 64.  By the host
 clock the whole `verify` is 14 % shorter than ids to the host + a Python walk + `accept` for 64 sequences and no shorter for one:
 `commit` still pays `accept`'s bookkeeping and table upload.  What it buys is a step whose device work is one graph.
+
+    cache.extend(counts); cache.tree_mask(parents)         # the first announce on the host: pages, copy-on-write, the tree
+    for step in range(8):                                  # ... and then no host bookkeeping: capturable, all 8 steps in one graph
+        for layer in range(32):
+            o = cache.attend_new(layer, cache.append_rope(layer, q, k, v, cos, sin), max_seq_len=4096, tree=mask)
+        result = cache.verify_launch(mixedgemm.argmax_rows(lm_head(hidden)), draft_tok, root_tok)
+        token_pos = cache.step_launch(result, counts, max_seq_len=4096, depths=depths)     # commit + the next extend, on the device
+    cache.sync()                                           # the host lists catch up: one copy
+
+Device steps.  `step_launch(result, next_counts, max_seq_len=)` is `commit(result)` + `extend(next_counts)` as one capture-safe call of
+`mixedgemm.kv_step` (include/micromix_kvstep.h): every sequence is shortened behind the tokens `result` says it keeps (None: all of
+them, the plain decode loop), the pages past them go back to a free stack ON THE DEVICE, the next tokens get pages from it, and
+`kv_indptr`, `kv_indices`, `last_page_len` and `append_indptr` are rewritten in place -- the tables the host code produces, entry for
+entry, page numbers included, because every push and pop lands where the host's sequential loops put it (prefix sums over the
+sequences, no atomics).  It returns `token_pos`, the position of every new token: its cos / sin row.  The device state -- lengths, page
+lists, the stack -- is one int32 tensor that the host packs and uploads when its own tables changed since the last upload
+(`upload_state`, or a `step_launch` outside capture) and reads back with `sync()`, which always copies the state that is on the
+device -- a replayed graph moves it without any Python running -- and rebuilds `_pages`, the free list in
+the stack's order, the reference counts and `seq_lens`, and announces the last step's tokens again so that `commit` / `accept` can
+close it on the host.  While the device is ahead -- after a `step_launch`, and, once one was captured, whenever the 16-byte header of the state says
+that a graph has run since the host last looked -- everything that needs the host lists raises RuntimeError naming `sync()`: `extend`,
+`fork`, `truncate`, `reset`, `accept`, `commit`, `share_groups`, `pages_in_use`, `seq_lens`, `steps_guaranteed`, and `attend` /
+`attend_new` without an explicit `max_seq_len`; `append`, `append_rope`, `attend` / `attend_new` with `max_seq_len`, `tree_mask` and
+`verify_launch` work.  `attend(shared=True)` with both bounds keeps working too: a device step never shortens a sequence below the
+tokens that were committed when the groups were formed, so the shared prefixes and the group tables stay valid.
+A step that cannot be taken -- no page left, a sequence past `max_seq_len`, a keep count outside its range -- changes nothing and
+leaves a sticky status; the later steps of a captured graph then do nothing, its appends rewrite slots the sequences already own, and
+`sync()` raises naming the step and the status with the host state that of the last good step.  `steps_guaranteed(next_counts,
+max_seq_len)` says how many steps cannot fail.  No reference counts exist on the device and none are needed: a dropped page holds
+only announced tokens, written by this sequence alone into a page it took for them, so shared pages are never pushed; what has to
+hold on entry is that no sequence's partly filled last page is shared (the host `extend` before the first step sees to it, ValueError
+otherwise), and steps keep that (`step_launch`).  Out of scope: releasing pages below a window (a cache made with `window=` and
+release on refuses), `fork` on the device, counts that change from step to step inside one graph, more than 1 024 sequences.
 """
 from __future__ import annotations
 
@@ -145,7 +178,7 @@ class PagedKVCache:
         self._pages = [[] for _ in range(batch)]                # -1: a page released below the window; its entry keeps its place
         self._released = [0] * batch                            # leading entries of _pages[b] that are -1
         self._ref = [0] * max_pages                             # entries of _pages that name the page; 0: the page is in _free, once
-        self.seq_lens = [0] * batch
+        self._seq_lens = [0] * batch
         i32 = dict(dtype=torch.int32, device=dev)
         self.kv_indptr = torch.zeros((batch + 1,), **i32)
         # capacity: every page, so the tensor never moves -- unless released entries (which keep their place) outgrow it
@@ -167,6 +200,35 @@ class PagedKVCache:
         self._shared_workspace = None
         self._prefill_workspace = None
         self._retired = []
+        # device steps (the module docstring, "Device steps")
+        self._ahead = False                                     # the device took steps the host lists have not seen: sync() reads them
+        self._state_current = False                             # the packed state on the device equals the host lists
+        self._step_state = None                                 # the state of mixedgemm.kv_step, and (max_seq_len, pages_per_seq) it was made for
+        self._step_geometry = None
+        self._step_counts = self._step_depths = None            # what _next_new and _depths_dev hold
+        self._next_new = self._depths_dev = self._token_pos = self._token_pos_view = None    # made by the first step_launch / upload_state
+        self._captured = False                                  # a step_launch was captured: a graph replay moves the device unseen
+        self._steps_seen = 0                                    # steps_done of the state when the host last wrote or read it
+        self._shared_host = [0] * batch                         # shared_len as it was last uploaded
+
+    @property
+    def seq_lens(self):
+        """tokens per sequence, the announced ones included (host bookkeeping; RuntimeError while the device is ahead: `sync()`)"""
+        self._host("seq_lens")
+        return self._seq_lens
+
+    @seq_lens.setter
+    def seq_lens(self, value):
+        self._seq_lens = value
+
+    def _host(self, what):
+        """the host lists are current, or RuntimeError.  The Python of a captured step_launch does not run at a replay, so once one
+        was captured the state's header is read (16 bytes) to see whether a graph has moved the device since sync() or the upload"""
+        if not self._ahead and self._captured and self._state_current:
+            status, steps_done = self._step_state[:2].tolist()
+            self._ahead = bool(status) or steps_done != self._steps_seen
+        if self._ahead:
+            raise RuntimeError(f"{what}: the device has taken steps (step_launch) that the host lists have not seen; call sync() first")
 
     def _upload(self, new):
         indptr, indices, last = [0], [], []
@@ -189,12 +251,14 @@ class PagedKVCache:
         self.num_new_tokens = app[-1]
         self._announced = self._parents = None                  # extend sets them again after its upload
         self._tree_words_live = False
+        self._state_current = False                             # step_launch packs the lists again
         groups, shared = self.share_groups()
         gptr = [0]
         for grp in groups:
             gptr.append(gptr[-1] + len(grp))
         gptr += [self.batch] * (self.batch + 1 - len(gptr))    # the unused trailing groups are empty
         self._group_table.copy_(torch.tensor(gptr + [b for grp in groups for b in grp] + shared, dtype=torch.int32))
+        self._shared_host = shared
         self._max_shared = max(shared)
         self._max_suffix = max(n - c for n, c in zip(self.seq_lens, shared))
 
@@ -204,6 +268,7 @@ class PagedKVCache:
         same pages as the rest of its group.  Sequences are taken in index order; b joins the first group whose leader (its first
         member) lists the same page, a real one (>= 0), in entry 0, and opens a group otherwise.  A group shares
         page_size * (leading entries on which all its members agree), capped at its shortest member's length; a group of one shares 0."""
+        self._host("share_groups")
         groups = []
         for b, pages in enumerate(self._pages):
             for grp in groups:
@@ -227,6 +292,7 @@ class PagedKVCache:
 
     @property
     def pages_in_use(self):
+        self._host("pages_in_use")
         return self.max_pages - len(self._free)
 
     def _unref(self, page):
@@ -255,6 +321,7 @@ class PagedKVCache:
         rewrites the page table in place (host -> device copies; call it outside graph capture).  The following `append` calls of
         every layer take exactly sum(counts) tokens, sequence by sequence.  A sequence whose partly filled last page is shared gets
         its own copy first (the module docstring, "Sharing")."""
+        self._host("extend")
         new = [int(new_tokens_per_seq)] * self.batch if isinstance(new_tokens_per_seq, int) else [int(n) for n in new_tokens_per_seq]
         if len(new) != self.batch or min(new) < 0:
             raise ValueError(f"need {self.batch} non-negative token counts")
@@ -318,6 +385,7 @@ class PagedKVCache:
         then lists the same pages, released entries included, and each page's count goes up.  length 0 is a reset.  ValueError for src == dst,
         a length outside [0, seq_lens[src]] and a length that would put a released page inside the window (the module docstring).
         Rewrites the page table on the device like `extend` (outside graph capture)."""
+        self._host("fork")
         length = self.seq_lens[src] if length is None else int(length)
         if src == dst:
             raise ValueError("fork: src and dst are the same sequence")
@@ -334,6 +402,7 @@ class PagedKVCache:
     def truncate(self, seq, length):
         """Drop the tokens of `seq` at and past `length` (the rejected part of a speculative draft).  Nothing is copied; pages wholly
         past `length` lose a reference.  ValueError as for `fork`.  Outside graph capture."""
+        self._host("truncate")
         length = int(length)
         self._check_length(seq, length, "truncate")
         self._shorten(seq, length)
@@ -341,6 +410,7 @@ class PagedKVCache:
 
     def reset(self, seq):
         """Empty sequence `seq`: its pages lose a reference, and those it owned alone return to the free list (outside graph capture)."""
+        self._host("reset")
         self._shorten(seq, 0)
         self._upload([0] * self.batch)
 
@@ -369,6 +439,8 @@ class PagedKVCache:
             if self.window:
                 raise ValueError("attend(shared=True) has no sliding-window form: this cache was made with window="
                                  f"{self.window}; use attend()")
+            if max_shared_len is None or max_seq_len is None:
+                self._host("attend(shared=True) without max_seq_len and max_shared_len")
             most = self._max_shared if max_shared_len is None else int(max_shared_len)
             tail = self._max_suffix if max_seq_len is None else int(max_seq_len)
             need = mixedgemm.paged_decode_shared_workspace_bytes(self.batch, q.size(1), self.num_kv_heads, most, tail)
@@ -379,6 +451,8 @@ class PagedKVCache:
             return mixedgemm.paged_decode_shared(q, self.kv_data, self.kv_param, self.kv_indptr, self.kv_indices, self.last_page_len, layer,
                                                  self.group_indptr, self.group_members, self.shared_len, most, tail, sm_scale=sm_scale,
                                                  workspace=self._shared_workspace if need else None)
+        if max_seq_len is None:
+            self._host("attend without max_seq_len")
         bound = max(self.seq_lens) if max_seq_len is None else int(max_seq_len)
         need = mixedgemm.paged_decode_workspace_bytes(self.batch, q.size(1), self.num_kv_heads, bound, self.window)
         if need and (self._workspace is None or self._workspace.numel() < need):
@@ -443,6 +517,7 @@ class PagedKVCache:
         path that is not a chain from the root under the parents of the last `tree_mask` (without one: causal chains, so a prefix
         0, 1, .. k - 1).  `verify` picks the paths on the device and does all of this without the host in between (the module
         docstring, "Verifying a draft")."""
+        self._host("accept")
         checked = self._checked_paths(paths, "accept")
         bases = self._announced[1]
         indptr, src, dst = [0], [], []
@@ -535,6 +610,7 @@ class PagedKVCache:
         ValueError as `accept` raises it, here AFTER the rows have moved -- a path the parents of `tree_mask` do not allow, which
         includes a tree sequence that kept all (root_tok < 0): the rows of the announced tokens are then undefined, the committed
         tokens are untouched, and `truncate(b, base_b)` for every sequence (base_b = seq_lens[b] minus what it announced) recovers."""
+        self._host("commit")
         if self._announced is None:
             raise ValueError("commit: the page tables changed since the last extend (fork, truncate, reset, accept): nothing to accept")
         paths, nxt = self._paths_of(result.cpu().tolist(), self._announced[0])
@@ -601,6 +677,8 @@ class PagedKVCache:
             raise ValueError(f"attend_new(tree=) has no sliding-window form: this cache was made with window={self.window}")
         if q.dim() != 3 or q.size(0) != self.num_new_tokens:
             raise RuntimeError(f"attend_new expects the {self.num_new_tokens} tokens announced by extend(), got q of shape {tuple(q.shape)}")
+        if max_seq_len is None:
+            self._host("attend_new without max_seq_len")
         bound = max(self.seq_lens) if max_seq_len is None else int(max_seq_len)
         need = mixedgemm.paged_prefill_workspace_bytes(self.num_new_tokens, self.batch, q.size(1), self.num_kv_heads, bound, self.window)
         if need and (self._prefill_workspace is None or self._prefill_workspace.numel() < need):
@@ -610,3 +688,260 @@ class PagedKVCache:
         return mixedgemm.paged_prefill(q, self.kv_data, self.kv_param, self.kv_indptr, self.kv_indices, self.last_page_len,
                                        self.append_indptr, layer, bound, sm_scale=sm_scale,
                                        workspace=self._prefill_workspace if need else None, window=self.window, tree_mask=tree)
+
+    # ---- device steps ---------------------------------------------------------------------------------------------------------------------
+    def _step_args(self, next_counts, max_seq_len):
+        counts = [int(next_counts)] * self.batch if isinstance(next_counts, int) else [int(n) for n in next_counts]
+        if len(counts) != self.batch or min(counts) < 0:
+            raise ValueError(f"need {self.batch} non-negative token counts")
+        max_seq_len = int(max_seq_len)
+        if max_seq_len < 1:
+            raise ValueError("max_seq_len must be positive")
+        return counts, max_seq_len, -(-max_seq_len // self.page_size)
+
+    def _flat_depths(self, depths, counts):
+        """depths as `tree_mask` returns them (a list per sequence, None: a chain) or one flat list, as one flat list"""
+        if depths is None:
+            return None
+        if len(depths) == self.batch and all(d is None or isinstance(d, (list, tuple)) for d in depths):
+            depths = [x for d, n in zip(depths, counts) for x in (range(n) if d is None else d)]
+        flat = [int(x) for x in depths]
+        if len(flat) != sum(counts) or (flat and min(flat) < 0):
+            raise ValueError(f"depths: need one non-negative depth for each of the {sum(counts)} announced tokens")
+        return flat
+
+    def steps_guaranteed(self, next_counts, max_seq_len):
+        """How many `step_launch(result, next_counts, max_seq_len=max_seq_len)` calls in a row cannot fail, whatever the drafts keep
+        (host only).  The worst case keeps every announced token, since a step that keeps less holds fewer pages and shorter
+        sequences: step s then needs seq_lens[b] + s * n_b <= max_seq_len for every sequence, sum_b ceil((seq_lens[b] + s * n_b) / P)
+        - (pages held now) <= the free pages, and that sum of list entries <= kv_indices.numel().  Exact for that case: this many
+        steps with everything kept succeed and the next one fails.  With no token announced at all every step succeeds: 2^31 - 1."""
+        self._host("steps_guaranteed")
+        counts, max_seq_len, _ = self._step_args(next_counts, max_seq_len)
+        if max(self._seq_lens) > max_seq_len:
+            return 0
+        if not any(counts):
+            return (1 << 31) - 1
+        held, free, P = sum(map(len, self._pages)), len(self._free), self.page_size
+
+        def fits(s):                                             # monotone in s: entries only grow
+            entries = sum(-(-(n + s * c) // P) for n, c in zip(self._seq_lens, counts))
+            return entries - held <= free and entries <= self.kv_indices.numel()
+
+        lo, hi = 0, min((max_seq_len - n) // c for n, c in zip(self._seq_lens, counts) if c)    # by length; then bisect on the pages
+        while lo < hi:
+            mid = (lo + hi + 1) // 2
+            lo, hi = (mid, hi) if fits(mid) else (lo, mid - 1)
+        return lo
+
+    def _check_sole_owner(self, what):
+        for b, n in enumerate(self._seq_lens):
+            if n % self.page_size and self._ref[self._pages[b][-1]] > 1:
+                raise ValueError(f"{what}: sequence {b} shares its partly filled last page; a host extend() that announces tokens for it "
+                                 "takes its own copy first")
+        if any(p < 0 for pages in self._pages for p in pages):
+            raise ValueError(f"{what}: pages were released below a window; device steps keep every page")
+
+    def _pack_state(self, max_seq_len, pps):
+        """the state of mixedgemm.kv_step (include/micromix_kvstep.h) from the host lists, as one list"""
+        announced = self._announced[0] if self._announced is not None else [0] * self.batch
+        for b, pages in enumerate(self._pages):
+            if len(pages) > pps or self._seq_lens[b] > max_seq_len:
+                raise ValueError(f"step_launch: sequence {b} holds {self._seq_lens[b]} tokens, more than max_seq_len = {max_seq_len}")
+        flat = [0, 0, len(self._free), 0] + self._seq_lens + list(announced) + [len(p) for p in self._pages]
+        flat += self._free + [0] * (self.max_pages - len(self._free))
+        for pages in self._pages:
+            flat += pages + [0] * (pps - len(pages))
+        return flat
+
+    def upload_state(self, max_seq_len, next_counts=None, depths=None):
+        """Make the device state of `step_launch` current now (one host-to-device copy, outside capture).  With next_counts (and the
+        depths `step_launch` will be given) it also uploads those and allocates token_pos: everything `step_launch(result, next_counts,
+        max_seq_len=max_seq_len, depths=depths)` would do outside capture, so that the FIRST such call can already be captured.
+        `step_launch` does all of this itself when it is not capturing.  Call it again before replaying a graph of steps whenever
+        host calls (extend, fork, truncate, ...) changed the tables since: the graph reads the state that was uploaded last."""
+        self._host("upload_state")
+        if self.release:
+            raise ValueError("device steps do not release pages below a window: this cache was made with window= and release on")
+        counts, max_seq_len, pps = self._step_args(0 if next_counts is None else next_counts, max_seq_len)
+        self._check_sole_owner("upload_state")
+        flat = self._pack_state(max_seq_len, pps)
+        if self.device.type == "cpu":
+            return
+        if self._step_state is None or self._step_state.numel() != len(flat):
+            if self._step_state is not None:
+                self._retired.append(self._step_state)          # a graph captured earlier may still point at it
+            self._step_state = torch.zeros((len(flat),), dtype=torch.int32, device=self.device)
+        self._step_state.copy_(torch.tensor(flat, dtype=torch.int32))
+        self._step_geometry = (max_seq_len, pps)
+        self._state_current = True
+        self._steps_seen = 0
+        if next_counts is not None:
+            self._step_buffers(counts, depths, False)
+
+    def _step_buffers(self, counts, depths, capturing):
+        """next_counts, depths and token_pos where the kernel reads and writes them; returns the depths tensor or None.  Uploads and
+        allocations happen only when something differs from the last call, and raise under capture"""
+        T = sum(counts)
+        if counts != self._step_counts:
+            if capturing:
+                raise RuntimeError("step_launch under stream capture with new next_counts: they are uploaded outside capture")
+            if self._next_new is None:
+                self._next_new = torch.zeros((self.batch,), dtype=torch.int32, device=self.device)
+            self._next_new.copy_(torch.tensor(counts, dtype=torch.int32))
+            self._step_counts = counts
+        if self._token_pos is None or self._token_pos.numel() < T:
+            if capturing:
+                raise RuntimeError("step_launch under stream capture would allocate token_pos: call it once outside capture")
+            if self._token_pos is not None:
+                self._retired.append(self._token_pos)
+            self._token_pos = torch.zeros((max(T, 64 * self.batch),), dtype=torch.int32, device=self.device)
+            self._token_pos_view = None
+        if self._token_pos_view is None or self._token_pos_view.numel() != T:
+            self._token_pos_view = self._token_pos[:T]
+        if isinstance(depths, torch.Tensor):
+            return depths
+        flat = self._flat_depths(depths, counts)
+        if flat is not None and (flat != self._step_depths or self._depths_dev is None or self._depths_dev.numel() < T):
+            if capturing:
+                raise RuntimeError("step_launch under stream capture with new depths: they are uploaded outside capture")
+            if self._depths_dev is None or self._depths_dev.numel() < T:
+                if self._depths_dev is not None:
+                    self._retired.append(self._depths_dev)
+                self._depths_dev = torch.zeros((max(T, 64 * self.batch),), dtype=torch.int32, device=self.device)
+            self._depths_dev[:T].copy_(torch.tensor(flat, dtype=torch.int32))
+            self._step_depths = flat
+        return None if flat is None or not T else self._depths_dev[:T]
+
+    def step_launch(self, result, next_counts, *, max_seq_len, depths=None):
+        """Commit the announced tokens and announce the next ones ON THE DEVICE: what `commit(result)` + `extend(next_counts)` do, without
+        the host (the module docstring, "Device steps"; the rule: include/micromix_kvstep.h).  Returns token_pos, int32 [T], T =
+        sum(next_counts): the position of every new token, its cos / sin row for `append_rope`; the same tensor at every call.
+        result: what `verify_launch` returned (its column 0 is the number of announced tokens each sequence keeps, already packed down by
+        its moves), or None: every announced token stays, the plain decode loop.  next_counts: an int or one host int per sequence.
+        depths: the depths of the new tokens as `tree_mask` returns them, a flat list, or an int32 device tensor [T] of the caller's
+        that the kernel reads at every replay; None: chains.  max_seq_len: no sequence may grow past it; it sizes the state
+        (ceil(max_seq_len / P) list entries per sequence) and has to stay the same while the device is ahead.
+        Capturable once the device state is current: the counts and depths are uploaded only when they differ from the last call's, the
+        state only when the host tables changed since it was uploaded (any extend, fork, truncate, reset, accept) -- under stream capture
+        either raises RuntimeError; `upload_state(max_seq_len, next_counts, depths)` or one call outside capture prepares all of it.  Nothing is read on the host: a
+        step that cannot be taken (no page left, a sequence past max_seq_len, ...) leaves every table as it was and sets a sticky
+        status that `sync()` raises; `steps_guaranteed` says how many steps cannot fail.
+        On entry with the host current, no sequence's partly filled last page may be shared (ValueError; the host `extend` that announced
+        its tokens made it so).  Device steps keep that: after a step a sequence's last page is the page it wrote before, still its own,
+        or a page popped from the free stack, which no list names; pages below the announced tokens are never touched.
+        ValueError on a cache whose window releases pages: eviction stays on the host.  The announced counts become next_counts, so
+        `tree_mask` (outside capture) and `verify_launch` work for the next step; when next_counts equal the counts announced before,
+        the tree of the last `tree_mask` call stays in force: a fixed topology needs no call between the steps.
+        On a CPU cache the rule runs here in plain Python over the lists, and a step that cannot be taken raises RuntimeError at once."""
+        if self.release:
+            raise ValueError("step_launch does not release pages below a window: this cache was made with window= and release on")
+        counts, max_seq_len, pps = self._step_args(next_counts, max_seq_len)
+        T = sum(counts)
+        if result is not None and self._announced is None:
+            raise ValueError("step_launch: the page tables changed since the last extend (fork, truncate, reset, accept): nothing to keep")
+        same = self._announced is not None and list(self._announced[0]) == counts
+        tree = (self._parents, self._tree_words_live) if same else (None, False)
+        if self.device.type == "cpu":
+            token_pos = self._step_host(result, counts, max_seq_len, pps, self._flat_depths(depths, counts))
+            self._parents, self._tree_words_live = tree
+            return token_pos
+        capturing = torch.cuda.is_current_stream_capturing()
+        if self._ahead and self._step_geometry != (max_seq_len, pps):
+            raise RuntimeError(f"step_launch: max_seq_len was {self._step_geometry[0]} when the device went ahead; call sync() before changing it")
+        if not self._ahead and not (self._state_current and self._step_geometry == (max_seq_len, pps)):
+            if capturing:
+                raise RuntimeError("step_launch under stream capture with a stale device state: the host tables changed since it was "
+                                   "uploaded; call upload_state(max_seq_len, next_counts, depths), or step_launch once, outside capture")
+            self.upload_state(max_seq_len)
+        depths_dev = self._step_buffers(counts, depths, capturing)
+        mixedgemm.kv_step(self._step_state, self.max_pages, pps, self.page_size, max_seq_len, self._next_new, T, self.kv_indptr, self.kv_indices,
+                          self.last_page_len, self.append_indptr, keep=result, depths=depths_dev, token_pos=self._token_pos_view if T else None)
+        self._ahead = True
+        self._captured |= capturing
+        self.num_new_tokens = T
+        self._announced = (counts, None)                        # the bases are the device's until sync()
+        self._parents, self._tree_words_live = tree
+        return self._token_pos_view
+
+    def _step_host(self, result, counts, max_seq_len, pps, depths):
+        """the rule of include/micromix_kvstep.h in plain words, on a CPU cache's own lists"""
+        P, status = self.page_size, _lib.KV_STEP
+        announced = list(self._announced[0]) if self._announced is not None else [0] * self.batch
+        if result is None:
+            keep = announced
+        else:
+            keep = [int(k) for k in (result[:, 0] if isinstance(result, torch.Tensor) and result.dim() == 2 else result)]
+        self._check_sole_owner("step_launch")
+        self._pack_state(max_seq_len, pps)                       # its refusals
+        kept = [n - a + k for n, a, k in zip(self._seq_lens, announced, keep)]
+        final = [n + c for n, c in zip(kept, counts)]
+        keep_pages, final_pages = [-(-n // P) for n in kept], [-(-n // P) for n in final]
+        pushes = sum(len(pages) - kp for pages, kp in zip(self._pages, keep_pages))
+        failed = None
+        if any(not 0 <= k <= a for k, a in zip(keep, announced)):
+            failed = "MM_KV_STEP_BAD_KEEP"
+        elif max(final) > max_seq_len:
+            failed = "MM_KV_STEP_TOO_LONG"
+        elif sum(final_pages) - sum(keep_pages) > len(self._free) + pushes:
+            failed = "MM_KV_STEP_OUT_OF_PAGES"
+        elif sum(final_pages) > self.kv_indices.numel():
+            failed = "MM_KV_STEP_INDICES_CAPACITY"
+        if failed:
+            raise RuntimeError(f"step_launch: the step cannot be taken: {failed} ({status[failed]}); nothing was changed")
+        for b in range(self.batch):                              # 1: shorten; the pages past the kept tokens go back, highest entry first
+            for p in reversed(self._pages[b][keep_pages[b]:]):
+                self._unref(p)
+            del self._pages[b][keep_pages[b]:]
+        for b in range(self.batch):                              # 2: after all are shortened, the new tokens' pages in pop order
+            self._pages[b] += [self._take() for _ in range(final_pages[b] - keep_pages[b])]
+            self._seq_lens[b] = final[b]
+        self._upload(counts)                                     # 3: the tables
+        self._announced = (counts, kept)
+        pos = [kept[b] + i for b, n in enumerate(counts) for i in range(n)] if depths is None else \
+              [kept[b] + d for b, n in enumerate(counts) for d in depths[sum(counts[:b]):sum(counts[:b]) + n]]
+        return torch.tensor(pos, dtype=torch.int32)
+
+    def sync(self):
+        """Bring the host lists up to the device: one device-to-host copy of the state, from which `_pages`, the free list (in the
+        stack's order), the reference counts (recounted from the lists) and `seq_lens` are rebuilt; the tokens of the last announce
+        are announced again on the host, so `commit` / `accept` can close the last step, and `extend` etc. work again.  The
+        copy is made whenever a state is on the device that the host has not replaced since -- also when no `step_launch` ran in
+        Python, because a replayed graph moves the device without it -- and the lists are rebuilt when the state's step count or
+        status says that steps were taken.  Call it after the replays whose result the host wants.  RuntimeError when a step failed, naming its number (from 0, counted from the last upload
+        of the state) and its status; the host state is then that of the last good step, which is also what the device tables hold,
+        and the next `step_launch` uploads the state again."""
+        if self._step_state is None or not self._state_current:
+            return                                               # the host lists are the newer ones
+        flat = self._step_state.cpu().tolist()
+        B, H = self.batch, _lib.KV_STEP["MM_KV_STEP_HEADER_INTS"]
+        status, steps_done, free_count, failed_step = flat[:H]
+        if not self._ahead and not status and steps_done == self._steps_seen:
+            return                                               # nothing ran since the host last looked
+        self._steps_seen = steps_done
+        pps = self._step_geometry[1]
+        lens, announced, num_pages = flat[H:H + B], flat[H + B:H + 2 * B], flat[H + 2 * B:H + 3 * B]
+        stack = flat[H + 3 * B:H + 3 * B + self.max_pages]
+        lists = H + 3 * B + self.max_pages
+        self._pages = [flat[lists + b * pps:lists + b * pps + num_pages[b]] for b in range(B)]
+        self._free = stack[:free_count]
+        self._ref = [0] * self.max_pages
+        for pages in self._pages:
+            for p in pages:
+                self._ref[p] += 1
+        assert all((self._ref[p] == 0) == (n == 1) for p, n in enumerate(self._count_free())), "a page is both listed and free, or neither"
+        self._seq_lens = lens
+        self._ahead = False
+        self._announced = (announced, [n - a for n, a in zip(lens, announced)])
+        self.num_new_tokens = sum(announced)
+        self._max_suffix = max(n - c for n, c in zip(lens, self._shared_host))
+        if status:
+            self._state_current = False
+            raise RuntimeError(f"sync: device step {failed_step} could not be taken: {_lib.KV_STEP_STATUS.get(status, status)} ({status}); "
+                               "the tables and the host state are those of the last good step")
+
+    def _count_free(self):
+        seen = [0] * self.max_pages
+        for p in self._free:
+            seen[p] += 1
+        return seen

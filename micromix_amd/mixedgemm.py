@@ -36,7 +36,7 @@ from ._args import _check_split, _check_tensor, _launch, _ok, _on_device, _opt, 
 
 __all__ = ["test_function", "matmul", "gate_up_activate", "interleave_gate_up", "reorder_quantize_x", "reorder_quantize_w", "reorder_quantize_w4", "activate_quantize_x",
            "downproj_quantize_w", "downproj_quantize_w4", "rmsnorm_quantize_x", "qlinear_decode", "qlinear_decode_supported", "matmul_grouped", "reorder_quantize_x_grouped",
-           "kv_append", "rope_kv_append", "kv_copy_pages", "kv_move_rows", "paged_decode", "paged_decode_workspace_bytes", "paged_decode_shared", "paged_decode_shared_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes",
+           "kv_append", "rope_kv_append", "kv_copy_pages", "kv_move_rows", "kv_step", "kv_step_state_ints", "paged_decode", "paged_decode_workspace_bytes", "paged_decode_shared", "paged_decode_shared_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes",
            "argmax_rows", "argmax_rows_workspace_bytes", "verify_greedy", "sample_rows", "sample_rows_workspace_bytes",
            "logprob_rows", "logprob_rows_workspace_bytes", "cross_entropy", "process_logits",
            "spec_sample_rows", "spec_sample_rows_workspace_bytes", "chain_candidates",

@@ -1,7 +1,7 @@
 """The paged KV cache and what runs over it, as `mixedgemm` exports it: append (with RoPE), page copy and row moves, decode, shared-prefix
 decode and prefill attention (include/micromix_hip.h, mm_kv_append .. mm_paged_prefill_tree), the end of a speculative step:
 `process_logits` (include/micromix_logits.h) -> `argmax_rows` / `sample_rows` / `spec_sample_rows` (include/micromix_spec.h) ->
-`verify_greedy`, and what the logits say about a
+`verify_greedy` -> `kv_step` (include/micromix_kvstep.h: the page table's bookkeeping between two steps), and what the logits say about a
 token: `logprob_rows` / `cross_entropy` (include/micromix_logprob.h).  None of it is an export of the reference module (its append_kv_i4 / _f16 take K/V
 already quantized and one head count); micromix_amd/kvcache.py is the small cache object on top.  Every wrapper runs on torch's
 current stream and is capture-safe."""
@@ -14,7 +14,7 @@ import torch
 from . import _lib
 from ._args import _check_tensor, _launch, _lead, _lib_with, _ok, _opt, _out, _ptr, _stream_ptr, _tensor
 
-__all__ = ["kv_append", "rope_kv_append", "kv_copy_pages", "kv_move_rows", "paged_decode", "paged_decode_workspace_bytes", "paged_decode_shared",
+__all__ = ["kv_append", "rope_kv_append", "kv_copy_pages", "kv_move_rows", "kv_step", "kv_step_state_ints", "paged_decode", "paged_decode_workspace_bytes", "paged_decode_shared",
            "paged_decode_shared_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes", "argmax_rows", "argmax_rows_workspace_bytes",
            "verify_greedy", "sample_rows", "sample_rows_workspace_bytes", "logprob_rows", "logprob_rows_workspace_bytes", "cross_entropy",
            "process_logits", "spec_sample_rows", "spec_sample_rows_workspace_bytes", "chain_candidates"]
@@ -26,6 +26,7 @@ _SAMPLE = ("mm_sample_rows", "mm_sample_rows", "the sampler")
 _LOGPROB = ("mm_logprob_rows", "mm_logprob_rows", "token log-probabilities")
 _LOGITS = ("mm_process_logits", "mm_process_logits", "logits processing")
 _SPEC = ("mm_spec_sample_rows", "mm_spec_sample_rows", "speculative sampling")
+_KVSTEP = ("mm_kv_step", "mm_kv_step", "device steps of the page table")
 _SHARED = ("mm_paged_decode_shared", "mm_paged_decode_shared", "shared-prefix decode")
 
 
@@ -191,6 +192,60 @@ def kv_move_rows(kv_data, kv_param, kv_indptr, kv_indices, move_indptr, src_pos,
         raise RuntimeError("src_pos and dst_pos must be of one length")
     _launch("kv_move_rows", dev, lib.mm_kv_move_rows, _ptr(kv_data), _opt(kv_param), kind, max_pages, L, Hkv, P, 128, _ptr(kv_indptr),
             _ptr(kv_indices), B, _ptr(move_indptr), _ptr(src_pos), _ptr(dst_pos), src_pos.numel(), _stream_ptr(dev))
+
+
+def kv_step_state_ints(batch, max_pages, pages_per_seq):
+    """int32 entries of the state `kv_step` works on (include/micromix_kvstep.h states the layout): MM_KV_STEP_HEADER_INTS + 3 * batch +
+    max_pages + batch * pages_per_seq; 0 for arguments `kv_step` refuses"""
+    return int(_lib_with(*_KVSTEP).mm_kv_step_state_ints(int(batch), int(max_pages), int(pages_per_seq)))
+
+
+def kv_step(state, max_pages, pages_per_seq, page_size, max_seq_len, next_new, num_next_tokens, kv_indptr, kv_indices, last_page_len,
+            append_indptr, *, keep=None, depths=None, token_pos=None):
+    """One step of the paged cache's allocator on the device: every sequence is shortened behind the tokens it keeps of those last
+    announced, the pages past them return to the free stack, next_new[b] tokens are announced and get pages, and kv_indptr, kv_indices,
+    last_page_len, append_indptr (and token_pos) are rewritten in place; returns None.  What PagedKVCache's accept + extend compute on
+    the host, page numbers included (include/micromix_kvstep.h states the rule, the layout of `state` and the MM_KV_STEP_* statuses).
+
+    state: int32 [kv_step_state_ints(B, max_pages, pages_per_seq)], B = next_new.numel() <= MM_KV_STEP_MAX_BATCH.  keep: None (every
+    announced token stays: plain decode), int32 [B], or int32 [B, S] whose column 0 counts -- `verify_greedy`'s result as it is.
+    num_next_tokens: a host int, what next_new has to sum to (the T of the following appends).  depths: int32 [num_next_tokens], a new
+    token's distance from the committed ones (None: chains); token_pos: int32 [num_next_tokens] or None, receives each new token's
+    position, its cos / sin row.  A step that cannot be taken (no page left, a sequence past max_seq_len, a count outside its range, ...)
+    changes nothing but state[0], its status, and state[3]; every later call then does nothing until the host rewrites the state.  The
+    call itself does not fail for that: nothing is read on the host.  All tensors int32 on one device.  Runs on the current stream,
+    capture-safe."""
+    lib = _lib_with(*_KVSTEP)
+    dev = _lead(state, "state", torch.int32)
+    B = _tensor(next_new, "next_new", torch.int32, dev).numel()
+    for n, t in (("state", state), ("next_new", next_new), ("kv_indptr", kv_indptr), ("kv_indices", kv_indices), ("last_page_len", last_page_len),
+                 ("append_indptr", append_indptr), ("depths", depths), ("token_pos", token_pos)):
+        if t is not None and _tensor(t, n, torch.int32, dev).dim() != 1:
+            raise RuntimeError(f"{n} must be one-dimensional")
+    max_pages, pages_per_seq, page_size, max_seq_len, T = int(max_pages), int(pages_per_seq), int(page_size), int(max_seq_len), int(num_next_tokens)
+    if min(max_pages, pages_per_seq, page_size, max_seq_len) < 1 or T < 0:
+        raise ValueError("max_pages, pages_per_seq, page_size and max_seq_len must be positive and num_next_tokens non-negative")
+    most = _lib.KV_STEP["MM_KV_STEP_MAX_BATCH"]
+    if B > most:
+        raise RuntimeError(f"kv_step takes at most {most} sequences, got {B}")
+    if state.numel() < _lib.KV_STEP["MM_KV_STEP_HEADER_INTS"] + 3 * B + max_pages + B * pages_per_seq:
+        raise RuntimeError(f"state must hold kv_step_state_ints({B}, {max_pages}, {pages_per_seq}) entries, got {state.numel()}")
+    if kv_indptr.numel() != B + 1 or append_indptr.numel() != B + 1 or last_page_len.numel() != B:
+        raise RuntimeError("kv_indptr and append_indptr must have B + 1 entries and last_page_len B (B = next_new.numel())")
+    stride = 0
+    if keep is not None:
+        _tensor(keep, "keep", torch.int32, dev)
+        if keep.dim() not in (1, 2) or keep.size(0) != B or keep.numel() == 0 and B:
+            raise RuntimeError(f"keep must be int32 [{B}] or [{B}, S] with the count in column 0")
+        stride = keep.size(1) if keep.dim() == 2 else 1
+    for n, t in (("depths", depths), ("token_pos", token_pos)):
+        if t is not None and t.numel() != T:
+            raise RuntimeError(f"{n} must have num_next_tokens = {T} entries")
+    if depths is not None and token_pos is None:
+        raise RuntimeError("depths without token_pos: the positions have nowhere to go")
+    _launch("kv_step", dev, lib.mm_kv_step, _ptr(state), B, max_pages, pages_per_seq, page_size, max_seq_len, _opt(keep), stride, _ptr(next_new),
+            T, _opt(depths), _ptr(kv_indptr), _ptr(kv_indices), kv_indices.numel(), _ptr(last_page_len), _ptr(append_indptr), _opt(token_pos),
+            _stream_ptr(dev))
 
 
 def argmax_rows_workspace_bytes(rows, vocab):
