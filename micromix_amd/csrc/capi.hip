@@ -5,6 +5,7 @@
 #include "../../include/micromix_logits.h"
 #include "../../include/micromix_spec.h"
 #include "../../include/micromix_kvstep.h"
+#include "../../include/micromix_tokens.h"
 #include "mx_common.h"
 #include "mx_kernels.h"
 #include "mx_kv_shared_host.h"
@@ -798,6 +799,54 @@ int mm_kv_step(int32_t *state, int batch, int max_pages, int pages_per_seq, int 
                        kv_indptr, kv_indices, kv_indices_capacity, last_page_len, append_indptr, token_pos};
     hipError_t e = mm::launch_kv_step(s, (hipStream_t)stream);
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_kv_step");
+}
+
+// ---- the token half of a step (token_step.hip, include/micromix_tokens.h)
+static int tokens_refused(int batch, long long ld_tok, int num_tokens) { return batch < 0 || ld_tok < 1 || num_tokens < 0 ? MM_ERR_BAD_ARG : MM_OK; }
+static int tokens_limits(int batch, long long ld_tok) { return batch > MM_TOKENS_MAX_BATCH || ld_tok > MM_TOKENS_MAX_LD ? MM_ERR_UNSUPPORTED : MM_OK; }
+
+int mm_token_step(int32_t *tokens, long long ld_tok, int batch, int32_t *total_len, int32_t *finished, const int32_t *result, int result_stride,
+                  const int32_t *target_tok, int num_tokens, const int32_t *qo_indptr, const int32_t *root_tok, const int32_t *max_total,
+                  const int32_t *stop_tok, int n_stop, const int32_t *kv_state, int32_t *emitted, mm_stream_t stream) {
+    if (tokens_refused(batch, ld_tok, num_tokens) || result_stride < MM_VERIFY_STRIDE || n_stop < 0 || (stop_tok != nullptr) != (n_stop > 0))
+        return MM_ERR_BAD_ARG;
+    if (batch > 0) {
+        if (!tokens || !total_len || !finished || !result || !qo_indptr || !root_tok || !max_total || (!target_tok && num_tokens > 0))
+            return MM_ERR_BAD_ARG;
+        if (((uintptr_t)tokens | (uintptr_t)total_len | (uintptr_t)finished | (uintptr_t)result | (uintptr_t)target_tok | (uintptr_t)qo_indptr |
+             (uintptr_t)root_tok | (uintptr_t)max_total | (uintptr_t)stop_tok | (uintptr_t)kv_state | (uintptr_t)emitted) & 3) return MM_ERR_BAD_ARG;
+    }
+    if (tokens_limits(batch, ld_tok) || n_stop > MM_TOKENS_MAX_STOP) return MM_ERR_UNSUPPORTED;
+    if (batch == 0) return MM_OK;
+    const mm::TokenStep s{tokens, ld_tok, batch, total_len, finished, result, result_stride, target_tok, num_tokens, qo_indptr, root_tok, max_total,
+                          stop_tok, n_stop, kv_state, emitted};
+    hipError_t e = mm::launch_token_step(s, (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_token_step");
+}
+
+size_t mm_ngram_draft_workspace_bytes(int batch, long long ld_tok) {
+    if (batch <= 0 || tokens_refused(batch, ld_tok, 0) || tokens_limits(batch, ld_tok)) return 0;
+    return mm::ngram_workspace_bytes(batch, ld_tok);
+}
+
+int mm_ngram_draft(int32_t *tokens, long long ld_tok, int batch, const int32_t *total_len, const int32_t *next_indptr, int num_tokens, int min_n,
+                   int max_n, int32_t *draft_tok, int32_t *root_tok, int32_t *cand_tok, int32_t *match_len, int32_t *row_seq, int32_t *row_total_len,
+                   void *workspace, size_t workspace_bytes, mm_stream_t stream) {
+    if (tokens_refused(batch, ld_tok, num_tokens) || min_n < 1 || max_n < min_n) return MM_ERR_BAD_ARG;
+    const bool limits = tokens_limits(batch, ld_tok) || max_n > MM_NGRAM_MAX_N;
+    if (batch > 0) {
+        if (!tokens || !total_len || !next_indptr || !root_tok || (!draft_tok && num_tokens > 0)) return MM_ERR_BAD_ARG;
+        if (((uintptr_t)tokens | (uintptr_t)total_len | (uintptr_t)next_indptr | (uintptr_t)draft_tok | (uintptr_t)root_tok | (uintptr_t)cand_tok |
+             (uintptr_t)match_len | (uintptr_t)row_seq | (uintptr_t)row_total_len | (uintptr_t)workspace) & 3) return MM_ERR_BAD_ARG;
+        const size_t need = limits ? 0 : mm::ngram_workspace_bytes(batch, ld_tok);
+        if (need && (!workspace || workspace_bytes < need)) return MM_ERR_BAD_ARG;
+    }
+    if (limits) return MM_ERR_UNSUPPORTED;
+    if (batch == 0) return MM_OK;
+    const mm::NgramDraft s{tokens, ld_tok, batch, total_len, next_indptr, num_tokens, min_n, max_n, draft_tok, root_tok, cand_tok, match_len,
+                           row_seq, row_total_len, (unsigned *)workspace};
+    hipError_t e = mm::launch_ngram_draft(s, (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_ngram_draft");
 }
 
 // ---- calibration statistics (calib_stats.hip, include/micromix_calib.h)

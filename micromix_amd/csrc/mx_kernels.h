@@ -329,6 +329,35 @@ struct KVStep {
     int *last_page_len, *append_indptr, *token_pos;
 };
 hipError_t launch_kv_step(const KVStep &s, hipStream_t stream);
+// the token half of a step (token_step.hip, include/micromix_tokens.h): commit a verified step into the history; draft the next chain
+// by n-gram lookup over it.  Optional arrays null when absent; ws: ngram_workspace_bytes, uninitialised
+struct TokenStep {
+    int *tokens;
+    long long ld_tok;
+    int B;
+    int *total_len, *finished;
+    const int *result;
+    int result_stride;
+    const int *target_tok;
+    int T;
+    const int *qo_indptr, *root_tok, *max_total, *stop_tok;
+    int n_stop;
+    const int *kv_state;
+    int *emitted;
+};
+hipError_t launch_token_step(const TokenStep &s, hipStream_t stream);
+struct NgramDraft {
+    int *tokens;
+    long long ld_tok;
+    int B;
+    const int *total_len, *next_indptr;
+    int T, min_n, max_n;
+    int *draft_tok, *root_tok, *cand_tok, *match_len, *row_seq, *row_total_len;
+    unsigned *ws;
+};
+int ngram_parts(long long ld_tok);
+size_t ngram_workspace_bytes(int batch, long long ld_tok);
+hipError_t launch_ngram_draft(const NgramDraft &s, hipStream_t stream);
 // token log-probabilities over bf16 rows (logprob.hip, include/micromix_logprob.h): target and temperature device arrays of `rows`
 // entries or null, every output null when not wanted, top_n 0 .. 32; ws: logprob_workspace_bytes, uninitialised
 size_t logprob_workspace_bytes(int rows, int vocab, int top_n);

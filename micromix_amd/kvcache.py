@@ -779,6 +779,12 @@ class PagedKVCache:
         if next_counts is not None:
             self._step_buffers(counts, depths, False)
 
+    @property
+    def step_state(self):
+        """the device state of `step_launch` (include/micromix_kvstep.h), or None before the first upload: what `mixedgemm.token_step`
+        takes as kv_state, so that the token history stops where the page table did.  The same tensor until the geometry changes"""
+        return self._step_state
+
     def _step_buffers(self, counts, depths, capturing):
         """next_counts, depths and token_pos where the kernel reads and writes them; returns the depths tensor or None.  Uploads and
         allocations happen only when something differs from the last call, and raise under capture"""

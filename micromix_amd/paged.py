@@ -1,7 +1,8 @@
 """The paged KV cache and what runs over it, as `mixedgemm` exports it: append (with RoPE), page copy and row moves, decode, shared-prefix
 decode and prefill attention (include/micromix_hip.h, mm_kv_append .. mm_paged_prefill_tree), the end of a speculative step:
 `process_logits` (include/micromix_logits.h) -> `argmax_rows` / `sample_rows` / `spec_sample_rows` (include/micromix_spec.h) ->
-`verify_greedy` -> `kv_step` (include/micromix_kvstep.h: the page table's bookkeeping between two steps), and what the logits say about a
+`verify_greedy` -> `token_step` (include/micromix_tokens.h: the token history's half of a step; `ngram_draft` drafts the next chain from
+it) -> `kv_step` (include/micromix_kvstep.h: the page table's bookkeeping between two steps), and what the logits say about a
 token: `logprob_rows` / `cross_entropy` (include/micromix_logprob.h).  None of it is an export of the reference module (its append_kv_i4 / _f16 take K/V
 already quantized and one head count); micromix_amd/kvcache.py is the small cache object on top.  Every wrapper runs on torch's
 current stream and is capture-safe."""
@@ -17,7 +18,8 @@ from ._args import _check_tensor, _launch, _lead, _lib_with, _ok, _opt, _out, _p
 __all__ = ["kv_append", "rope_kv_append", "kv_copy_pages", "kv_move_rows", "kv_step", "kv_step_state_ints", "paged_decode", "paged_decode_workspace_bytes", "paged_decode_shared",
            "paged_decode_shared_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes", "argmax_rows", "argmax_rows_workspace_bytes",
            "verify_greedy", "sample_rows", "sample_rows_workspace_bytes", "logprob_rows", "logprob_rows_workspace_bytes", "cross_entropy",
-           "process_logits", "spec_sample_rows", "spec_sample_rows_workspace_bytes", "chain_candidates"]
+           "process_logits", "spec_sample_rows", "spec_sample_rows_workspace_bytes", "chain_candidates", "token_step", "ngram_draft",
+           "ngram_draft_workspace_bytes"]
 
 # entries a library built before them lacks: (the symbol looked for, the names and the feature of the rebuild message)
 _TREE = ("mm_paged_prefill_tree", "mm_paged_prefill_tree / mm_kv_move_rows", "tree-masked attention")
@@ -27,6 +29,7 @@ _LOGPROB = ("mm_logprob_rows", "mm_logprob_rows", "token log-probabilities")
 _LOGITS = ("mm_process_logits", "mm_process_logits", "logits processing")
 _SPEC = ("mm_spec_sample_rows", "mm_spec_sample_rows", "speculative sampling")
 _KVSTEP = ("mm_kv_step", "mm_kv_step", "device steps of the page table")
+_TOKENS = ("mm_ngram_draft", "mm_token_step / mm_ngram_draft", "the token history on the device")
 _SHARED = ("mm_paged_decode_shared", "mm_paged_decode_shared", "shared-prefix decode")
 
 
@@ -246,6 +249,193 @@ def kv_step(state, max_pages, pages_per_seq, page_size, max_seq_len, next_new, n
     _launch("kv_step", dev, lib.mm_kv_step, _ptr(state), B, max_pages, pages_per_seq, page_size, max_seq_len, _opt(keep), stride, _ptr(next_new),
             T, _opt(depths), _ptr(kv_indptr), _ptr(kv_indices), kv_indices.numel(), _ptr(last_page_len), _ptr(append_indptr), _opt(token_pos),
             _stream_ptr(dev))
+
+
+NgramDraft = namedtuple("NgramDraft", ["draft_tok", "root_tok", "cand_tok", "match_len", "row_seq", "row_total_len"])
+
+
+def _token_state(tokens, total_len, what):
+    """(device, batch, ld_tok) of the token history `token_step` and `ngram_draft` share; on the CPU the checks the device path makes"""
+    if not isinstance(tokens, torch.Tensor):
+        raise TypeError(f"{what}: tokens must be a torch.int32 tensor [batch, ld_tok]")
+    if tokens.is_cuda:
+        dev = _lead(tokens, "tokens", torch.int32)
+    else:
+        dev = tokens.device
+        if tokens.dtype is not torch.int32 or not tokens.is_contiguous():
+            raise TypeError(f"{what}: tokens must be a contiguous torch.int32 tensor [batch, ld_tok]")
+    if tokens.dim() != 2 or tokens.size(1) < 1:
+        raise RuntimeError(f"tokens must be int32 [batch, ld_tok] with ld_tok >= 1, got {list(tokens.shape)}")
+    B, ld = tokens.shape
+    if ld > _lib.TOKENS["MM_TOKENS_MAX_LD"] or B > _lib.TOKENS["MM_TOKENS_MAX_BATCH"]:
+        raise RuntimeError(f"{what} takes at most {_lib.TOKENS['MM_TOKENS_MAX_BATCH']} sequences of {_lib.TOKENS['MM_TOKENS_MAX_LD']} tokens, got {[B, ld]}")
+    _ints(total_len, "total_len", dev, (B,))
+    return dev, B, ld
+
+
+def _ints(t, name, dev, shape=None, new=None):
+    """an int32 array of the token ops on `dev`, CPU or device: checked as _tensor checks it, or -- None with `new` -- a new one"""
+    if t is None and new is not None:
+        return torch.empty(new, dtype=torch.int32, device=dev)
+    if dev.type != "cpu":
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+        return _tensor(t, name, torch.int32, dev, shape, "int32 {0}, got {1}")
+    if not isinstance(t, torch.Tensor) or t.dtype is not torch.int32 or t.device != dev or not t.is_contiguous():
+        raise TypeError(f"{name} must be a contiguous torch.int32 tensor on {dev}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise RuntimeError(f"{name} must be int32 {list(shape)}, got {list(t.shape)}")
+    return t
+
+
+def _clamp(x, lo, hi):
+    return lo if x < lo else hi if x > hi else x
+
+
+def token_step(tokens, total_len, finished, result, target_tok, qo_indptr, root_tok, max_total, *, stop_tok=None, kv_state=None,
+               emitted=None):
+    """Commit one verified step into the token history, on the device: the tokens the step generated -- target_tok along the accepted
+    path, the bonus last -- are appended to tokens[b] at total_len[b] until a stop token (kept, finished[b] = 1) or the sequence's
+    limit min(max_total[b], ld_tok) (finished[b] = 2); returns `emitted`, int32 [B], how many each sequence committed.
+    include/micromix_tokens.h states the rule.
+
+    tokens int32 [B, ld_tok], total_len and finished int32 [B]: the state, the layout `process_logits` reads, updated in place.
+    result: `verify_greedy`'s, int32 [B, 66]; target_tok int32 [T], qo_indptr int32 [B + 1] and root_tok int32 [B]: what went into it.
+    max_total int32 [B]; stop_tok int32 [B, n <= 64] or None, entries < 0 unused; kv_state: `kv_step`'s state or None -- once its
+    status is non-zero the whole call writes nothing (call this after `verify_greedy` and BEFORE the step's `kv_step` /
+    `step_launch`); emitted: int32 [B] or None (a new one: pass it under capture).  A finished sequence, a prompt chunk (more than
+    64 rows, or root_tok[b] < 0) and a sequence whose path is empty are left alone.  Every array is a device tensor that only the kernel
+    reads: capture-safe, on the current stream.  On CPU tensors the same rule runs in plain Python over lists."""
+    dev, B, ld = _token_state(tokens, total_len, "token_step")
+    _ints(finished, "finished", dev, (B,))
+    stride = _lib.MM_VERIFY_STRIDE
+    _ints(result, "result", dev, (B, stride))
+    if _ints(target_tok, "target_tok", dev).dim() != 1:
+        raise RuntimeError("target_tok must be one-dimensional")
+    T = target_tok.numel()
+    _ints(qo_indptr, "qo_indptr", dev, (B + 1,))
+    _ints(root_tok, "root_tok", dev, (B,))
+    _ints(max_total, "max_total", dev, (B,))
+    n_stop = 0
+    if stop_tok is not None:
+        _ints(stop_tok, "stop_tok", dev)
+        most = _lib.TOKENS["MM_TOKENS_MAX_STOP"]
+        if stop_tok.dim() != 2 or stop_tok.size(0) != B or not 1 <= stop_tok.size(1) <= most:
+            raise RuntimeError(f"stop_tok must be int32 [{B}, n] with 1 <= n <= {most}, got {list(stop_tok.shape)}")
+        n_stop = stop_tok.size(1)
+    if kv_state is not None and _ints(kv_state, "kv_state", dev).numel() < 1:
+        raise RuntimeError("kv_state must be kv_step's state")
+    emitted = _ints(emitted, "emitted", dev, (B,), new=(B,))
+    if dev.type == "cpu":
+        return _token_step_host(tokens, total_len, finished, result, target_tok, qo_indptr, root_tok, max_total, stop_tok, kv_state, emitted)
+    _launch("token_step", dev, _lib_with(*_TOKENS).mm_token_step, _ptr(tokens), ld, B, _ptr(total_len), _ptr(finished), _ptr(result), stride,
+            _ptr(target_tok), T, _ptr(qo_indptr), _ptr(root_tok), _ptr(max_total), _opt(stop_tok), n_stop, _opt(kv_state), _ptr(emitted),
+            _stream_ptr(dev))
+    return emitted
+
+
+def _token_step_host(tokens, total_len, finished, result, target_tok, qo_indptr, root_tok, max_total, stop_tok, kv_state, emitted):
+    """the rule of mm_token_step (include/micromix_tokens.h) in plain words, on CPU tensors"""
+    if kv_state is not None and int(kv_state.reshape(-1)[0]) != 0:
+        return emitted                                           # the sticky failure of kv_step: nothing at all is written
+    B, ld = tokens.shape
+    target, qo, T = target_tok.tolist(), qo_indptr.tolist(), target_tok.numel()
+    for b, row in enumerate(result.tolist()):
+        q0 = _clamp(qo[b], 0, T)
+        n, k, N, m = _clamp(qo[b + 1], 0, T) - q0, row[0], int(total_len[b]), 0
+        path = row[2:2 + max(k, 0)]
+        if (int(finished[b]) == 0 and 1 <= n <= 64 and int(root_tok[b]) >= 0 and 1 <= k <= n and N >= 0
+                and all(0 <= i < n for i in path)):
+            made = [target[q0 + i] for i in path]
+            limit = min(int(max_total[b]), ld)
+            c = min(k, max(0, limit - N))
+            stops = set(t for t in stop_tok[b].tolist() if t >= 0) if stop_tok is not None else set()
+            hit = [i for i in range(c) if made[i] in stops]
+            m = hit[0] + 1 if hit else c
+            if m:
+                tokens[b, N:N + m] = torch.tensor(made[:m], dtype=torch.int32)
+            total_len[b] = N + m
+            if hit:
+                finished[b] = _lib.TOKENS["MM_TOKENS_STOPPED"]
+            elif N + m >= limit:
+                finished[b] = _lib.TOKENS["MM_TOKENS_LENGTH"]
+        emitted[b] = m
+    return emitted
+
+
+def ngram_draft_workspace_bytes(batch, ld_tok):
+    """bytes of workspace `ngram_draft` needs for a history [batch, ld_tok]: 4 per part of MM_NGRAM_CHUNK tokens of every sequence; 0
+    when a history is one part, and for arguments `ngram_draft` refuses"""
+    return int(_lib_with(*_TOKENS).mm_ngram_draft_workspace_bytes(int(batch), int(ld_tok)))
+
+
+def ngram_draft(tokens, total_len, next_indptr, num_tokens, *, min_n=1, max_n=4, draft_tok=None, root_tok=None, cand_tok=None,
+                match_len=None, row_seq=None, row_total_len=None, workspace=None):
+    """Draft the next chain of every sequence by prompt lookup, on the device: the longest n-gram (at most max_n tokens, at least min_n)
+    of the history tokens[b][0 .. total_len[b]) that repeats its end -- the latest among equals -- is continued, periodically where
+    the continuation runs into the end; without one the last token is repeated, so the count per step stays fixed.
+    include/micromix_tokens.h states the rule.  Returns NgramDraft(draft_tok, root_tok, cand_tok, match_len, row_seq, row_total_len).
+
+    tokens int32 [B, ld_tok], total_len int32 [B]: the state `token_step` keeps.  next_indptr int32 [B + 1]: the next step's qo_indptr
+    / append_indptr, at most 64 nodes a sequence; num_tokens: a host int, its last entry (the T of the next step).  1 <= min_n <= max_n
+    <= MM_NGRAM_MAX_N = 16.  draft_tok int32 [T]: node 0 of a sequence is its last token, the root, then the draft -- the model's input
+    ids and `verify_greedy`'s draft_tok; root_tok int32 [B]: `verify_greedy`'s (-1 for an empty history); cand_tok int32 [T]:
+    `chain_candidates`' values, for `spec_sample_rows`' one-hot form; match_len int32 [B]: the n-gram's length, 0 without a match;
+    row_seq, row_total_len int32 [T]: what `process_logits` takes for the chain's rows, whose draft tokens are laid into tokens[b] past
+    total_len[b] (uncommitted slack that the next `token_step` overwrites).  Outputs that are None are allocated, as is the workspace
+    (`ngram_draft_workspace_bytes`, uninitialised): pass them under capture.  Every array is a device tensor that only the kernels
+    read: capture-safe, on the current stream.  On CPU tensors the same rule runs in plain Python over lists."""
+    dev, B, ld = _token_state(tokens, total_len, "ngram_draft")
+    T, min_n, max_n = int(num_tokens), int(min_n), int(max_n)
+    most = _lib.TOKENS["MM_NGRAM_MAX_N"]
+    if T < 0 or not 1 <= min_n <= max_n <= most:
+        raise ValueError(f"ngram_draft needs num_tokens >= 0 and 1 <= min_n <= max_n <= {most}, got {T}, {min_n}, {max_n}")
+    _ints(next_indptr, "next_indptr", dev, (B + 1,))
+    out = NgramDraft(_ints(draft_tok, "draft_tok", dev, (T,), new=(T,)), _ints(root_tok, "root_tok", dev, (B,), new=(B,)),
+                     _ints(cand_tok, "cand_tok", dev, (T,), new=(T,)), _ints(match_len, "match_len", dev, (B,), new=(B,)),
+                     _ints(row_seq, "row_seq", dev, (T,), new=(T,)), _ints(row_total_len, "row_total_len", dev, (T,), new=(T,)))
+    if dev.type == "cpu":
+        return _ngram_draft_host(tokens, total_len, next_indptr, T, min_n, max_n, out)
+    lib = _lib_with(*_TOKENS)
+    need = int(lib.mm_ngram_draft_workspace_bytes(B, ld))
+    workspace, ws_args = _kv_workspace(workspace, need, dev)
+    _launch("ngram_draft", dev, lib.mm_ngram_draft, _ptr(tokens), ld, B, _ptr(total_len), _ptr(next_indptr), T, min_n, max_n, _opt(out.draft_tok),
+            _ptr(out.root_tok), _opt(out.cand_tok), _ptr(out.match_len), _opt(out.row_seq), _opt(out.row_total_len), *ws_args, _stream_ptr(dev))
+    return out
+
+
+def _ngram_draft_host(tokens, total_len, next_indptr, T, min_n, max_n, out):
+    """the rule of mm_ngram_draft (include/micromix_tokens.h) in plain words, on CPU tensors"""
+    B, ld = tokens.shape
+    nxt = next_indptr.tolist()
+    for b in range(B):
+        N = _clamp(int(total_len[b]), 0, ld)
+        h = tokens[b, :N].tolist()
+        best_m, best_e = 0, -1
+        for e in range(N - 1):                                   # end positions 0 .. N - 2; later ones win ties
+            m = 0
+            while m < min(max_n, e + 1) and h[e - m] == h[N - 1 - m]:
+                m += 1
+            if m and m >= best_m:
+                best_m, best_e = m, e
+        hit = best_m >= min_n
+        last = h[N - 1] if N else 0
+        t0 = _clamp(nxt[b], 0, T)
+        n = _clamp(nxt[b + 1], 0, T) - t0
+        out.root_tok[b] = last if N else -1
+        out.match_len[b] = best_m if hit else 0
+        if not 1 <= n <= 64:
+            continue
+        p = N - 1 - best_e
+        chain = [last] + [h[best_e + 1 + i % p] if hit else last for i in range(n - 1)]
+        out.draft_tok[t0:t0 + n] = torch.tensor(chain, dtype=torch.int32)
+        out.cand_tok[t0:t0 + n] = torch.tensor(chain[1:] + [-1], dtype=torch.int32)
+        out.row_seq[t0:t0 + n] = b
+        out.row_total_len[t0:t0 + n] = torch.tensor([min(N + i, ld) for i in range(n)], dtype=torch.int32)
+        slack = chain[1:1 + max(0, min(n - 1, ld - N))]
+        if slack:
+            tokens[b, N:N + len(slack)] = torch.tensor(slack, dtype=torch.int32)
+    return out
 
 
 def argmax_rows_workspace_bytes(rows, vocab):
