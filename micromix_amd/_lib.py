@@ -132,6 +132,8 @@ KV_STEP_STATUS = {v: n for n, v in KV_STEP.items() if n not in ("MM_KV_STEP_MAX_
 # TOKENS_EXPORTS: the entries of include/micromix_tokens.h, likewise; TOKENS holds its integers by name (the limits, the n-gram part, the
 # values of `finished`)
 _TOKENS_PROTOS, TOKENS_EXPORTS, TOKENS = _read("micromix_tokens.h")
+# RANDOM_EXPORTS: the entry of include/micromix_random.h, likewise; RANDOM holds its two limits by name
+_RANDOM_PROTOS, RANDOM_EXPORTS, RANDOM = _read("micromix_random.h")
 
 _lib = None
 
@@ -146,7 +148,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -m micromix_amd.build` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for protos in (_PROTOS, _CALIB_PROTOS, _LOGPROB_PROTOS, _LOGITS_PROTOS, _SPEC_PROTOS, _KVSTEP_PROTOS, _TOKENS_PROTOS):
+    for protos in (_PROTOS, _CALIB_PROTOS, _LOGPROB_PROTOS, _LOGITS_PROTOS, _SPEC_PROTOS, _KVSTEP_PROTOS, _TOKENS_PROTOS, _RANDOM_PROTOS):
         _bind(lib, protos)
     _lib = lib
     return _lib

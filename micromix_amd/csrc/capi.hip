@@ -6,6 +6,7 @@
 #include "../../include/micromix_spec.h"
 #include "../../include/micromix_kvstep.h"
 #include "../../include/micromix_tokens.h"
+#include "../../include/micromix_random.h"
 #include "mx_common.h"
 #include "mx_kernels.h"
 #include "mx_kv_shared_host.h"
@@ -847,6 +848,19 @@ int mm_ngram_draft(int32_t *tokens, long long ld_tok, int batch, const int32_t *
                            row_seq, row_total_len, (unsigned *)workspace};
     hipError_t e = mm::launch_ngram_draft(s, (hipStream_t)stream);
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_ngram_draft");
+}
+
+// ---- uniform numbers keyed by seed and position (random.hip, include/micromix_random.h)
+int mm_uniform_rows(const int64_t *seed, const int32_t *sub, int batch, const int32_t *row_seq, const int32_t *pos, int rows, int n, unsigned domain,
+                    float *out, uint32_t *bits, long long ld_out, mm_stream_t stream) {
+    if (rows < 0 || batch < 0 || n < 1 || ld_out < rows) return MM_ERR_BAD_ARG;
+    if (rows > 0 && ((!out && !bits) || !pos || (!seed && batch > 0))) return MM_ERR_BAD_ARG;
+    if (((uintptr_t)seed & 7) || (((uintptr_t)sub | (uintptr_t)row_seq | (uintptr_t)pos | (uintptr_t)out | (uintptr_t)bits) & 3)) return MM_ERR_BAD_ARG;
+    if (n > MM_UNIFORM_MAX_N || rows > MM_UNIFORM_MAX_ROWS) return MM_ERR_UNSUPPORTED;
+    if (rows == 0) return MM_OK;
+    const mm::UniformRows s{(const long long *)seed, sub, batch, row_seq, pos, rows, n, domain, out, bits, ld_out};
+    hipError_t e = mm::launch_uniform_rows(s, (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_uniform_rows");
 }
 
 // ---- calibration statistics (calib_stats.hip, include/micromix_calib.h)

@@ -358,6 +358,20 @@ struct NgramDraft {
 int ngram_parts(long long ld_tok);
 size_t ngram_workspace_bytes(int batch, long long ld_tok);
 hipError_t launch_ngram_draft(const NgramDraft &s, hipStream_t stream);
+// uniform numbers keyed by seed and position (random.hip, include/micromix_random.h): sub and row_seq null when absent, out or bits
+// null when not wanted; no state, no workspace
+struct UniformRows {
+    const long long *seed;
+    const int *sub;
+    int B;
+    const int *row_seq, *pos;
+    int rows, n;
+    unsigned domain;
+    float *out;
+    unsigned *bits;
+    long long ld_out;
+};
+hipError_t launch_uniform_rows(const UniformRows &s, hipStream_t stream);
 // token log-probabilities over bf16 rows (logprob.hip, include/micromix_logprob.h): target and temperature device arrays of `rows`
 // entries or null, every output null when not wanted, top_n 0 .. 32; ws: logprob_workspace_bytes, uninitialised
 size_t logprob_workspace_bytes(int rows, int vocab, int top_n);

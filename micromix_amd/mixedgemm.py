@@ -39,7 +39,7 @@ __all__ = ["test_function", "matmul", "gate_up_activate", "interleave_gate_up", 
            "kv_append", "rope_kv_append", "kv_copy_pages", "kv_move_rows", "kv_step", "kv_step_state_ints", "paged_decode", "paged_decode_workspace_bytes", "paged_decode_shared", "paged_decode_shared_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes",
            "argmax_rows", "argmax_rows_workspace_bytes", "verify_greedy", "sample_rows", "sample_rows_workspace_bytes",
            "logprob_rows", "logprob_rows_workspace_bytes", "cross_entropy", "process_logits",
-           "spec_sample_rows", "spec_sample_rows_workspace_bytes", "chain_candidates", "token_step", "ngram_draft", "ngram_draft_workspace_bytes",
+           "spec_sample_rows", "spec_sample_rows_workspace_bytes", "chain_candidates", "token_step", "ngram_draft", "ngram_draft_workspace_bytes", "uniform_rows",
            "moe_route", "moe_plan", "moe_gather", "moe_combine",
            "moe_expert_table", "moe_sf_bytes", "moe_quantize", "moe_activate_quantize", "moe_matmul", "moe_matmul_supported",
            "permute_packed_rows", "moe_gate_up_table", "moe_gate_up_activate", "moe_gate_up_activate_supported"]

@@ -1,6 +1,7 @@
 """The paged KV cache and what runs over it, as `mixedgemm` exports it: append (with RoPE), page copy and row moves, decode, shared-prefix
 decode and prefill attention (include/micromix_hip.h, mm_kv_append .. mm_paged_prefill_tree), the end of a speculative step:
-`process_logits` (include/micromix_logits.h) -> `argmax_rows` / `sample_rows` / `spec_sample_rows` (include/micromix_spec.h) ->
+`process_logits` (include/micromix_logits.h) -> `argmax_rows` / `sample_rows` / `spec_sample_rows` (include/micromix_spec.h; `uniform_rows`,
+include/micromix_random.h, makes their uniform numbers from the request's seed and the position) ->
 `verify_greedy` -> `token_step` (include/micromix_tokens.h: the token history's half of a step; `ngram_draft` drafts the next chain from
 it) -> `kv_step` (include/micromix_kvstep.h: the page table's bookkeeping between two steps), and what the logits say about a
 token: `logprob_rows` / `cross_entropy` (include/micromix_logprob.h).  None of it is an export of the reference module (its append_kv_i4 / _f16 take K/V
@@ -19,7 +20,7 @@ __all__ = ["kv_append", "rope_kv_append", "kv_copy_pages", "kv_move_rows", "kv_s
            "paged_decode_shared_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes", "argmax_rows", "argmax_rows_workspace_bytes",
            "verify_greedy", "sample_rows", "sample_rows_workspace_bytes", "logprob_rows", "logprob_rows_workspace_bytes", "cross_entropy",
            "process_logits", "spec_sample_rows", "spec_sample_rows_workspace_bytes", "chain_candidates", "token_step", "ngram_draft",
-           "ngram_draft_workspace_bytes"]
+           "ngram_draft_workspace_bytes", "uniform_rows"]
 
 # entries a library built before them lacks: (the symbol looked for, the names and the feature of the rebuild message)
 _TREE = ("mm_paged_prefill_tree", "mm_paged_prefill_tree / mm_kv_move_rows", "tree-masked attention")
@@ -30,6 +31,7 @@ _LOGITS = ("mm_process_logits", "mm_process_logits", "logits processing")
 _SPEC = ("mm_spec_sample_rows", "mm_spec_sample_rows", "speculative sampling")
 _KVSTEP = ("mm_kv_step", "mm_kv_step", "device steps of the page table")
 _TOKENS = ("mm_ngram_draft", "mm_token_step / mm_ngram_draft", "the token history on the device")
+_RANDOM = ("mm_uniform_rows", "mm_uniform_rows", "seeded uniform numbers")
 _SHARED = ("mm_paged_decode_shared", "mm_paged_decode_shared", "shared-prefix decode")
 
 
@@ -435,6 +437,103 @@ def _ngram_draft_host(tokens, total_len, next_indptr, T, min_n, max_n, out):
         slack = chain[1:1 + max(0, min(n - 1, ld - N))]
         if slack:
             tokens[b, N:N + len(slack)] = torch.tensor(slack, dtype=torch.int32)
+    return out
+
+
+def _vector(t, name, dtype, dev, size=None):
+    """a one-dimensional array of `uniform_rows` on `dev`, CPU or device, checked as _tensor checks it; returns its length"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if dev.type != "cpu":
+        _tensor(t, name, dtype, dev)
+    elif t.dtype is not dtype or t.device != dev or not t.is_contiguous():
+        raise TypeError(f"{name} must be a contiguous {dtype} tensor on {dev}")
+    if t.dim() != 1 or (size is not None and t.numel() != size):
+        raise RuntimeError(f"{name} must be {dtype} [{'n' if size is None else size}], got {list(t.shape)}")
+    return t.numel()
+
+
+def _streams(t, name, dtype, dev, n, rows, ld):
+    """an output of `uniform_rows`, [n, rows] with unit stride along the rows and `ld` elements between two streams (None: whatever
+    this one has, at least rows); a new dense one for None.  Returns (tensor, ld)"""
+    if t is None:
+        ld = rows if ld is None else ld
+        return torch.empty((n, ld), dtype=dtype, device=dev)[:, :rows], ld
+    if not isinstance(t, torch.Tensor) or t.dtype is not dtype or t.device != dev:
+        raise TypeError(f"{name} must be a {dtype} tensor on {dev}")
+    if tuple(t.shape) != (n, rows) or (rows > 1 and t.stride(1) != 1):
+        raise RuntimeError(f"{name} must be {dtype} [{n}, {rows}] with unit stride along the rows, got {list(t.shape)} with strides {list(t.stride())}")
+    have = t.stride(0) if n > 1 and rows > 0 else rows if ld is None else ld           # one stream: its stride says nothing
+    if have < rows or (ld is not None and have != ld):
+        raise RuntimeError(f"{name}: {have} elements between two streams, {'at least ' + str(rows) if ld is None else ld} wanted")
+    return t, have
+
+
+def uniform_rows(seed, pos, *, n=3, sub=None, row_seq=None, domain=0, out=None, bits=False):
+    """Uniform numbers for the rows of a sampled step, keyed by the request's seed and the position of the token a row decides: no
+    generator state, so what a request draws does not depend on the batch it shares, the row it sits in or the calls before.  Returns
+    `out`, fp32 [n, rows]: n streams, each a contiguous [rows] array -- out[0], out[1] (and out[2]) are `spec_sample_rows`' u_accept
+    and u_resample (and `sample_rows`' u) without a copy.  With bits=True returns (out, bits), bits int32 [n, rows] holding the 32-bit
+    words the numbers were made of.  include/micromix_random.h states the rule.
+
+    seed int64 [batch], one per sequence; pos int32 [rows]: the index in the history at which the token the row decides will be
+    committed -- `ngram_draft`'s row_total_len, or total_len for a plain decode step; row_seq int32 [rows]: the row's sequence
+    (`ngram_draft`'s row_seq), None: row r is sequence r.  A row whose sequence is outside [0, batch) gets zeros.  sub int32 [batch]
+    or None (0): separates the samples or beams of one prompt under one seed; domain, a host integer in [0, 2^32): separates
+    consumers (a draft model's sampler from the target's).  1 <= n <= 16, rows <= 2^24.  Row r's words are Philox4x32-10 of counter
+    (pos[r], sub[s], block, domain) under key seed[s]; u = (word >> 8) * 2^-24, on the grid the samplers read without clamping.
+    out: fp32 [n, rows] or None (a new one: pass it under capture); it may be a view with more than `rows` elements between two
+    streams, whose slack is not written.  bits: True, or an int32 [n, rows] tensor with the same distance between two streams.
+    Every array is a device tensor that only the kernel reads: capture-safe, on the current stream, no workspace.  On CPU tensors the
+    same rule runs in plain Python integers."""
+    if not isinstance(seed, torch.Tensor):
+        raise TypeError("seed must be a torch.int64 tensor [batch]")
+    dev = seed.device
+    batch = _vector(seed, "seed", torch.int64, dev)
+    rows = _vector(pos, "pos", torch.int32, dev)
+    if sub is not None:
+        _vector(sub, "sub", torch.int32, dev, batch)
+    if row_seq is not None:
+        _vector(row_seq, "row_seq", torch.int32, dev, rows)
+    most_n, most_rows = _lib.RANDOM["MM_UNIFORM_MAX_N"], _lib.RANDOM["MM_UNIFORM_MAX_ROWS"]
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= most_n:
+        raise ValueError(f"uniform_rows needs 1 <= n <= {most_n}, got {n!r}")
+    if isinstance(domain, bool) or not isinstance(domain, int) or not 0 <= domain < 1 << 32:
+        raise ValueError(f"domain must be an integer in [0, 2^32), got {domain!r}")
+    if rows > most_rows:
+        raise RuntimeError(f"uniform_rows takes at most {most_rows} rows, got {rows}")
+    out, ld = _streams(out, "out", torch.float32, dev, n, rows, None)
+    words = None
+    if bits is not False:
+        words, _ = _streams(None if bits is True else bits, "bits", torch.int32, dev, n, rows, ld)
+    if dev.type == "cpu":
+        _uniform_rows_host(seed, sub, row_seq, pos, n, domain, out, words)
+    else:
+        _launch("uniform_rows", dev, _lib_with(*_RANDOM).mm_uniform_rows, _ptr(seed), _opt(sub), batch, _opt(row_seq), _ptr(pos), rows, n, domain,
+                _ptr(out), _opt(words), ld, _stream_ptr(dev))
+    return out if words is None else (out, words)
+
+
+def _uniform_rows_host(seed, sub, row_seq, pos, n, domain, out, bits):
+    """the rule of mm_uniform_rows (include/micromix_random.h) in plain Python integers, on CPU tensors"""
+    mask = 0xFFFFFFFF
+    seeds, subs = seed.tolist(), sub.tolist() if sub is not None else None
+    seqs = row_seq.tolist() if row_seq is not None else range(pos.numel())
+    for r, (s, p) in enumerate(zip(seqs, pos.tolist())):
+        words = [0] * n
+        if 0 <= s < len(seeds):
+            for j in range((n + 3) // 4):
+                c = [p & mask, (subs[s] if subs is not None else 0) & mask, j, domain]
+                k0, k1 = seeds[s] & mask, seeds[s] >> 32 & mask
+                for _ in range(10):
+                    a, b = 0xD2511F53 * c[0], 0xCD9E8D57 * c[2]
+                    c = [b >> 32 ^ c[1] ^ k0, b & mask, a >> 32 ^ c[3] ^ k1, a & mask]
+                    k0, k1 = k0 + 0x9E3779B9 & mask, k1 + 0xBB67AE85 & mask
+                words[4 * j:4 * j + 4] = c[:n - 4 * j]
+        for i, w in enumerate(words):
+            out[i, r] = (w >> 8) * 2.0 ** -24
+            if bits is not None:
+                bits[i, r] = w - (w >> 31 << 32)
     return out
 
 
