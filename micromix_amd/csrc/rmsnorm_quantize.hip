@@ -217,13 +217,20 @@ rmsnorm_quantize_kernel(const uint16_t *__restrict__ src, const uint16_t *__rest
 #pragma unroll
         for (int u = 0; u < GPT; ++u) sum[u] = stage_and_sum(u, r);
         if constexpr (PREFETCH) fetch(r + gridDim.x);
-        // part[t] for t < T, zeros up to P (P <= 2 * GPT * NTH: group threads past T contribute the zero padding)
+        // part[t] for t < T; group threads past T write the zero padding (their sum is 0), the line after them zeroes one more slot per
+        // thread.  GPT = 1: P <= 2 NTH, so that is every slot up to P, and stride <= NTH: every step of the tree is taken in full.
+        // GPT = 2 with NTH < 512 (320, 384, 448 threads; P = 1024): slots 3 NTH .. 1023 are never written, and the first step of the tree
+        // (stride 512) is taken by g < NTH only, so slots NTH .. 511 never receive slots 512 + NTH .. 1023.  Both are sound because
+        // T <= 512 + NTH (NTH >= T / 2 and T <= 1024): every slot that is not zeroed (>= 3 NTH) or not folded (>= 512 + NTH) lies at or
+        // past T -- its value in the reference's tree is the zero padding, adding it changes nothing -- and is never read: the fold reads
+        // g + 512 < 512 + NTH <= 3 NTH only (NTH >= 256), and every later stride is <= 256 <= NTH.
+        // (tests/test_rms_order_gpu.py: K = 16512, 20480, 24576, 28672)
 #pragma unroll
         for (int u = 0; u < GPT; ++u) part[g + u * NTH] = sum[u];
         if (g + GPT * NTH < P) part[g + GPT * NTH] = 0.0f;
         __syncthreads();
         for (int stride = P >> 1; stride >= 64; stride >>= 1) {
-            if (g < stride) part[g] += part[g + stride];          // (stride <= 512 <= NTH whenever GPT = 2; GPT = 1: P <= 2 NTH)
+            if (g < stride) part[g] += part[g + stride];
             __syncthreads();
         }
         if (g < 64) {

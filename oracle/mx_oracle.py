@@ -335,20 +335,21 @@ def _round_half_away(x: np.ndarray) -> np.ndarray:
 
 
 def rmsnorm_quantize(x_bits: np.ndarray, w_bits: np.ndarray, eps: float, idx: np.ndarray, kn: int, ks: int, ko: int,
-                     integer_round: bool = True, sf_fill: int = 0):
+                     integer_round: bool = True, sf_fill: int = 0, rvar: np.ndarray | None = None):
     """Restates rmsnorm_bf16_mixed_kernel (rmsnorm.cu:95-312).
 
     v[i] = bf16((float(x[idx[i]]) * float(w[idx[i]])) * rvar)   (:190-195); per 32-group amax, scale = amax == 0 ? 0.5 :
     2^ceil(log2(amax / FMAX)) (:216-245, as reorder.cu); then -- and this is what the reference does, rmsnorm.cu:262-267 --
     q = convert(bf16(clamp(round(v / scale), -FMAX, FMAX))): the value is rounded to an INTEGER (half away from zero)
     before the element conversion.  ``integer_round=False`` gives the quantizer without that step (identical to
-    reorder_quantize applied to the normalised row).
+    reorder_quantize applied to the normalised row).  ``rvar`` (fp32, one per row) replaces rmsnorm_rvar(x_bits, eps): the tests
+    use it to show what a sum of squares taken in another order would have produced (tests/rms_order_cases.py).
     """
     x_bits = np.asarray(x_bits)
     rows, k = x_bits.shape
     check_split(k, kn, ks, ko)
     idx = np.asarray(idx).astype(np.int64)
-    rvar = rmsnorm_rvar(x_bits, eps)
+    rvar = rmsnorm_rvar(x_bits, eps) if rvar is None else np.asarray(rvar, np.float32).reshape(rows)
     xv = bf16_to_f32(x_bits)[:, idx]
     wv = bf16_to_f32(np.asarray(w_bits))[idx]
     prod = (xv * wv[None, :]).astype(np.float32)         # exact

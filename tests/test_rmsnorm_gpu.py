@@ -29,25 +29,58 @@ CASES = [(1, 128, (0, 128, 0)), (3, 384, (128, 128, 128)), (130, 4096, (2048, 10
          (4, 8192, (4096, 2048, 2048)),       # the largest K of the 32-bit product row (256 threads, four partial sums per lane)
          (3, 8320, (4096, 128, 4096)),        # the first K of the 16-bit row kernel
          (3, 20480, (8192, 4096, 8192)),      # K > 16384: the 1024-thread variant
-         (3, 32768, (16384, 8192, 8192))]     # the largest K the int16 reorder index allows: 68 KiB of dynamic LDS
+         (3, 32768, (16384, 8192, 8192)),     # the largest K the int16 reorder index allows: 68 KiB of dynamic LDS
+         # rows against the CU count (resolved on the device, see many_rows): the first count that leaves the LDS-DMA ring for the plain
+         # products kernel, and three ragged laps of the prefetching row loop of the 16-bit kernel
+         ("2 CUs + 1", 4096, (2048, 1024, 1024)), ("3 grid + 1", 8320, (4096, 128, 4096))]
+BLOCK = 41                                    # distinct rows of a case whose row count follows the device; prime to every grid
+
+
+def many_rows(rows, k, split):
+    """(the row count of a symbolic case, row r of the launch as a row of a BLOCK-row block) -- the oracle then runs on BLOCK rows"""
+    import torch
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    if isinstance(rows, int):
+        return rows, np.arange(rows)
+    if rows == "2 CUs + 1":
+        rows = 2 * cus + 1
+    else:
+        # an upper bound of the 16-bit kernel's grid (launch_rmsnorm_quantize): 32 wave slots and 160 KB of LDS per CU
+        threads = (k // 32 + 63) // 64 * 64
+        lds = k * 2 + max(threads, 64) * 4 + split[1] // 4 * 3 + split[2]
+        rows = 3 * cus * min(32 // (threads // 64), (160 * 1024) // lds) + 1
+    return rows, np.arange(rows) % BLOCK
+
+
+def repeat_rows(want, of, rows, split):
+    """the oracle's six outputs for len(of) rows whose row r is row of[r] of the rows `want` was computed for"""
+    block = int(of.max()) + 1
+    out = [np.ascontiguousarray(w[of]) for w in want[:3]]
+    for w, kseg in zip(want[3:], split):
+        sf = np.zeros((o.sf_size_x(rows, kseg),), np.uint8)
+        if kseg:
+            sf[o.sf_valid_offsets(rows, kseg)] = w[o.sf_valid_offsets(block, kseg)].reshape(block, -1)[of].reshape(-1)
+        out.append(sf)
+    return out
 
 
 @pytest.mark.parametrize("integer_round", (True, False))
 @pytest.mark.parametrize("rows,k,split", CASES)
 def test_rmsnorm_quantize_matches_oracle(dev, rows, k, split, integer_round):
     import torch
+    rows, of = many_rows(rows, k, split)
     rng = np.random.default_rng(rows * 3 + k)
-    xb = make_inputs(rng, rows, k)
+    xb = make_inputs(rng, int(of.max()) + 1, k)
     xb[0, :64] = 0                                            # an all-zero group after the reorder is unlikely: force one below
     wb = o.f32_to_bf16((1.0 + 0.2 * rng.standard_normal(k)).astype(np.float32))
     idx = rng.permutation(k).astype(np.int16)
     if rows > 1:
         xb[1, :] = 0                                          # zero row: rvar = 1/sqrt(eps), every block is empty -> byte 126
     eps = 1e-5
-    got = mixedgemm.rmsnorm_quantize_x(t_from_bits(xb, dev), t_from_bits(wb, dev), eps,
+    got = mixedgemm.rmsnorm_quantize_x(t_from_bits(xb[of], dev), t_from_bits(wb, dev), eps,
                                        torch.from_numpy(idx).to(dev), *split, integer_round=integer_round)
     torch.cuda.synchronize()
-    want = o.rmsnorm_quantize(xb, wb, eps, idx, *split, integer_round=integer_round)
+    want = repeat_rows(o.rmsnorm_quantize(xb, wb, eps, idx, *split, integer_round=integer_round), of, rows, split)
     check_exact(got, want, rows, split, f"rmsnorm {rows}x{k} {split} integer_round={integer_round}")
 
 
