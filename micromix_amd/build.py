@@ -26,7 +26,7 @@ SOURCES = ["capi.hip", "reorder_quantize.hip", "direct_quantize.hip", "rmsnorm_q
            "kv_cache.hip", "kv_prefill.hip", "rope_append.hip", "kv_copy.hip", "kv_move.hip", "verify.hip", "sample.hip", "moe.hip", "calib_stats.hip", "logprob.hip",
            "logits_process.hip", "spec_sample.hip", "kv_step.hip", "token_step.hip", "random.hip"]
 DIAG_SOURCES = ["diag.hip"]
-HEADERS = ["mx_common.h", "mx_kernels.h", "mx_acc_regs.h", "mx_gemm_tile.inc", "kv_decode_tiles.inc", "mx_group_convert.h", "mx_instrument.h", "mx_direct_convert.h", "mx_decode_quant.h", "mx_rms_convert.h", "mx_gemm_prelude.h", "mx_paged_kv.h", "mx_kv_shared_host.h", "mx_buffer_ops.h", "mx_gemm_plan.h", "mx_stream_plan.h", "mx_decode_quant_sizes.h", "mx_argmax_key.h", "mx_row_weights.h", "mx_sample_select.h", "mx_spec_rule.h",
+HEADERS = ["mx_common.h", "mx_kernels.h", "mx_acc_regs.h", "mx_gemm_tile.inc", "kv_decode_tiles.inc", "mx_group_convert.h", "mx_instrument.h", "mx_direct_convert.h", "mx_decode_quant.h", "mx_rms_convert.h", "mx_gemm_prelude.h", "mx_paged_kv.h", "mx_kv_shared_host.h", "mx_buffer_ops.h", "mx_gemm_plan.h", "mx_stream_plan.h", "mx_quant_plan.h", "mx_launch_shape.h", "mx_decode_quant_sizes.h", "mx_argmax_key.h", "mx_row_weights.h", "mx_sample_select.h", "mx_spec_rule.h",
            os.path.join("..", "..", "include", "micromix_hip.h"), os.path.join("..", "..", "include", "micromix_diag.h"),
            os.path.join("..", "..", "include", "micromix_calib.h"), os.path.join("..", "..", "include", "micromix_logprob.h"),
            os.path.join("..", "..", "include", "micromix_logits.h"), os.path.join("..", "..", "include", "micromix_spec.h"),

@@ -181,11 +181,13 @@ hipError_t launch_direct_quantize(const void *A, const void *B, int rows, int KN
     long long blocks = (total + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
     // mode 3 = mode 0 on the interleaved [rows, 2 K] layout (A = the matrix, B = A + 128 elements; the caller passes both)
-    auto kern = mode == 0 ? direct_quantize_kernel<0> : mode == 1 ? direct_quantize_kernel<1> : mode == 2 ? direct_quantize_kernel<2>
-                                                                                                           : direct_quantize_kernel<0, true>;
-    MM_LAUNCH(kern, dim3((unsigned)blocks), dim3(256), 0, stream, (const uint16_t *)A, (const uint16_t *)B, rows, KN, KS, KO,
-                       oN, oS, oO, sfN, sfS, sfO);
-    return hipGetLastError();
+    auto launch = [&](auto kern_) {
+        return launch_kernel<decltype(kern_)::value>(LaunchShape{(int)blocks, 1, 256, 0, 0}, stream, diag_events(), (const uint16_t *)A, (const uint16_t *)B, rows,
+                                                     KN, KS, KO, oN, oS, oO, sfN, sfS, sfO);
+    };
+    // (modes 0 and 1 last: the kernels stand in the object in the order they are named here, where they have always stood)
+    if (mode != 0 && mode != 1) return mode == 2 ? launch(kernel_c<direct_quantize_kernel<2>>{}) : launch(kernel_c<direct_quantize_kernel<0, true>>{});
+    return mode == 1 ? launch(kernel_c<direct_quantize_kernel<1>>{}) : launch(kernel_c<direct_quantize_kernel<0>>{});
 }
 
 }  // namespace mm

@@ -43,19 +43,12 @@ namespace mm {
 
 static_assert(MM_PLAN_MAX_SPLITS == MM_MAX_SPLITS, "the plan's split bound is GemmArgs' (mx_gemm_plan.h)");
 
-// The one launch of a tile kernel: `args` are the kernel's arguments, `ev` the diagnostics events (both null: none).  The kernel's
-// dynamic-LDS limit is raised once per device before its first launch; that state belongs to the kernel -- a static of this
-// instantiation -- so no call site can pair a kernel with another kernel's flag.
+// The one launch of a tile kernel: launch_kernel (mx_kernels.h; the streaming kernels' launch_stream is the same call), which owns the
+// kernel's dynamic-LDS flag.  A tile kernel's limit is raised to its LDS before its first launch, whatever the size.
 struct LaunchDims { int wgs, threads, lds_bytes; };
 template <auto Kern, class... Args>
 static hipError_t launch_tile(LaunchDims d, hipStream_t stream, DiagEvents ev, const Args &...args) {
-    static DynamicLdsOnce attr;
-    if (hipError_t e = attr.ensure(reinterpret_cast<const void *>(Kern), d.lds_bytes); e != hipSuccess) return e;
-    if (ev.start != nullptr && ev.stop != nullptr)
-        hipExtLaunchKernelGGL(Kern, dim3(d.wgs), dim3(d.threads), d.lds_bytes, stream, ev.start, ev.stop, 0, args...);
-    else
-        hipLaunchKernelGGL(Kern, dim3(d.wgs), dim3(d.threads), d.lds_bytes, stream, args...);
-    return hipGetLastError();
+    return launch_kernel<Kern>(LaunchShape{d.wgs, 1, d.threads, d.lds_bytes, d.lds_bytes}, stream, ev, args...);
 }
 
 // The kernel table: one row per tile namespace, made where mx_gemm_tile.inc was included for it.  A row names the namespace's kernels by

@@ -867,19 +867,12 @@ static const StreamOverrides &stream_overrides() {
     return ov;
 }
 
-// The one launch of a streaming kernel: `args` are the kernel's arguments.  The kernel's dynamic-LDS limit is raised once per device
-// before the first launch that needs more than 64 KB; that state belongs to the kernel -- a static of this instantiation (compare
-// launch_tile, mx_gemm_prelude.h).  DIAG: the launch attaches the diagnostics events (mm_diag_set_kernel_events) -- the plain, the
-// quantizing and the ACT launches do, the grouped and device-sized ones do not.
+// The one launch of a streaming kernel: launch_kernel (mx_kernels.h; the tile kernels' launch_tile is the same call), which owns the
+// kernel's dynamic-LDS flag -- raised before the first launch that needs more than 64 KB.  DIAG: the launch attaches the diagnostics
+// events (mm_diag_set_kernel_events) -- the plain, the quantizing and the ACT launches do, the grouped and device-sized ones do not.
 template <auto Kern, bool DIAG, class... Args>
 static hipError_t launch_stream(const StreamLaunch &l, hipStream_t stream, const Args &...args) {
-    static DynamicLdsOnce once;
-    if (l.raise_to) {
-        if (hipError_t e = once.ensure(reinterpret_cast<const void *>(Kern), l.raise_to); e != hipSuccess) return e;
-    }
-    if constexpr (DIAG) MM_LAUNCH(Kern, dim3(l.grid_x, l.grid_y), dim3(l.threads), l.lds_bytes, stream, args...);
-    else hipLaunchKernelGGL(Kern, dim3(l.grid_x, l.grid_y), dim3(l.threads), l.lds_bytes, stream, args...);
-    return hipGetLastError();
+    return launch_kernel<Kern>(l, stream, DIAG ? diag_events() : DiagEvents{}, args...);
 }
 
 // The one place that turns a runtime (configuration, weight mode) into a template instantiation: fn(index) of the matching row of the

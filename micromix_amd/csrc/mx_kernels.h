@@ -5,6 +5,9 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <type_traits>
+
+#include "mx_launch_shape.h"
 
 namespace mm {
 
@@ -38,35 +41,45 @@ struct DynamicLdsOnce {
     }
 };
 
-// resident workgroups per CU of `kernel` at (threads, dynamic LDS): the occupancy query costs ~1 us of host time per launch, so the
-// last answer is kept per calling thread and kernel slot (a layer stack alternates between a handful of shapes)
-struct OccupancyCache {
-    struct Entry { const void *kernel; int dev, threads; size_t lds; int per_cu; };
-    static int get(int slot, const void *kernel, int threads, size_t lds) {
-        static thread_local Entry last[16] = {};
-        Entry &e = last[slot & 15];
-        const int dev = current_device();
-        if (e.kernel == kernel && e.dev == dev && e.threads == threads && e.lds == lds && e.per_cu > 0) return e.per_cu;
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-        e = Entry{kernel, dev, threads, lds, per_cu};
-        return per_cu;
-    }
-};
-
-// Measurement hook (mm_diag_set_kernel_events): the calling thread's pair of events, both null unless registered.  The quantizer
-// launchers (MM_LAUNCH) and the tiled GEMM (GemmArgs::ev_start / ev_stop) attach them to their dispatch, so that their elapsed time is
-// the kernel's own duration -- what rocprofv3's kernel trace reports -- without the launch gap that events around a call include.
+// Measurement hook (mm_diag_set_kernel_events): the calling thread's pair of events, both null unless registered.  The launches that
+// hand them to launch_kernel -- the quantizers' and, from GemmArgs::ev_start / ev_stop, the GEMMs' -- attach them to their dispatch, so
+// that their elapsed time is the kernel's own duration -- what rocprofv3's kernel trace reports -- without the launch gap that events
+// around a call include.
 struct DiagEvents { hipEvent_t start, stop; };
 DiagEvents &diag_events();     // thread-local, defined in capi.hip
-#define MM_LAUNCH(kern, grid, block, lds, stream, ...)                                                                      \
-    do {                                                                                                                   \
-        const mm::DiagEvents &ev_ = mm::diag_events();                                                                     \
-        if (ev_.start != nullptr && ev_.stop != nullptr)                                                                   \
-            hipExtLaunchKernelGGL(kern, grid, block, lds, stream, ev_.start, ev_.stop, 0, __VA_ARGS__);                    \
-        else                                                                                                               \
-            hipLaunchKernelGGL(kern, grid, block, lds, stream, __VA_ARGS__);                                               \
-    } while (0)
+
+// The one launch of a kernel that keeps state per kernel: `args` are the kernel's arguments, `ev` the diagnostics events (both null:
+// none).  With l.raise_to the kernel's dynamic-LDS limit is raised to it once per device before the first such launch; that state
+// belongs to the kernel -- a static of this instantiation -- so no call site can pair a kernel with another kernel's flag.
+template <auto Kern, class... Args>
+hipError_t launch_kernel(const LaunchShape &l, hipStream_t stream, DiagEvents ev, const Args &...args) {
+    static DynamicLdsOnce once;
+    if (l.raise_to) {
+        if (hipError_t e = once.ensure(reinterpret_cast<const void *>(Kern), l.raise_to); e != hipSuccess) return e;
+    }
+    if (ev.start != nullptr && ev.stop != nullptr)
+        hipExtLaunchKernelGGL(Kern, dim3(l.grid_x, l.grid_y), dim3(l.threads), l.lds_bytes, stream, ev.start, ev.stop, 0, args...);
+    else
+        hipLaunchKernelGGL(Kern, dim3(l.grid_x, l.grid_y), dim3(l.threads), l.lds_bytes, stream, args...);
+    return hipGetLastError();
+}
+
+// a kernel as a value that a generic lambda can take: decltype(k)::value is the kernel
+template <auto Kern> using kernel_c = std::integral_constant<decltype(Kern), Kern>;
+
+// resident workgroups per CU of Kern at (threads, dynamic LDS): the occupancy query costs ~1 us of host time per launch, so the last
+// answer is kept per calling thread and kernel -- a static of this instantiation (a layer stack alternates between a handful of shapes)
+template <auto Kern>
+int resident_per_cu(int threads, size_t lds) {
+    struct Entry { int dev, threads; size_t lds; int per_cu; };
+    static thread_local Entry last = {};
+    const int dev = current_device();
+    if (last.dev == dev && last.threads == threads && last.lds == lds && last.per_cu > 0) return last.per_cu;
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(Kern), threads, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+    last = Entry{dev, threads, lds, per_cu};
+    return per_cu;
+}
 
 constexpr int MM_MAX_SPLITS = 16;   // in-kernel split-K: splits per tile
 

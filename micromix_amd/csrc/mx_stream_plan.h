@@ -10,6 +10,7 @@
 #include <initializer_list>
 
 #include "mx_decode_quant_sizes.h"   // dq::operand_bytes, rms_bytes, early_fits: the LDS range of the quantization in front of the rings
+#include "mx_launch_shape.h"
 
 namespace mm {
 
@@ -133,7 +134,7 @@ constexpr bool has_norm_kernel(const StreamCfg &c) {
 }
 
 // what a launcher needs: the grid, the workgroup, the dynamic LDS and the limit to raise the kernel's to (0: the default 64 KB holds)
-struct StreamLaunch { int grid_x, grid_y, threads, lds_bytes, raise_to; };
+using StreamLaunch = LaunchShape;      // {grid_x, grid_y, threads, lds_bytes, raise_to}
 struct GemmPlan { bool ok; StreamCfg cfg; StreamLaunch launch; };
 struct QuantPlan {
     bool ok;

@@ -21,6 +21,7 @@
 #include "mx_buffer_ops.h"   // make_brsrc / make_rsrc, slab_bytes, load_frag / load_frag16 (the weights' fragments), wait_vmcnt
 #include "mx_decode_quant.h"
 #include "mx_kernels.h"
+#include "mx_quant_plan.h"
 
 namespace mm {
 namespace decode {
@@ -496,14 +497,8 @@ __global__ void __launch_bounds__(NT) qlinear_decode16_kernel(Args a) {
 
 }  // namespace decode
 
-// dynamic LDS: the quantized rows and scales of all M rows + as many staged bf16 rows as fit next to the 32 KB reduction buffer
-constexpr size_t DECODE_LDS_MAX = 126 * 1024;
-static size_t decode_operand_bytes(int M, const int K[3], bool rms = false) {
-    return rms ? ((dq::operand_bytes(M, K) + 15) & ~(size_t)15) + dq::rms_bytes(M, K) : dq::operand_bytes(M, K);
-}
-
-// features per workgroup: 16 while 32 would leave half of the CUs without a workgroup
-static int decode_features(int N) { return 2 * ((N + 31) / 32) <= device_cus() ? 16 : 32; }
+// ---- the host side: the plan is mx_quant_plan.h's (LDS, staged rows, lane pairs, feature width, grid) ----
+static_assert(quant::DECODE_THREADS == decode::NT && decode::BN == 32 && decode::BN16 == 16, "the plan's workgroup (mx_quant_plan.h)");
 
 // 0: cannot run; 1: can run; 2: can run and is expected to beat quantize + GEMM.  Every workgroup repeats the quantization, in
 // ceil(M * K/32 / 512) passes of ~1.4 us, and the workgroups take ceil(N/features / CUs) rounds; measured on MI355X the fused
@@ -511,7 +506,7 @@ static int decode_features(int N) { return 2 * ((N + 31) / 32) <= device_cus() ?
 int qlinear_decode_supported(int M, int N, const int K[3], bool rms, bool w4) {
     const size_t Kt = (size_t)K[0] + K[1] + K[2];
     if (rms && Kt > (size_t)dq::RMS_MAX_K) return 0;
-    if (M < 1 || M > 8 || Kt * 2 + decode_operand_bytes(M, K, rms) > DECODE_LDS_MAX) return 0;   // at least one staged row must fit
+    if (!quant::decode_fits(M, K, rms)) return 0;   // M <= 8, and at least one staged row must fit
     // layers wide enough for the streaming kernel's workgroup-local quantization (mx_gemm_stream.hip): it beats quantize + GEMM at
     // M = 1 and 2 (gate/up 10.6-12.7 -> 8.5-9.3 us, fused gate + up 18.3-19.0 -> 16.2-17.7) and ties or loses from M = 4 on
     // (every workgroup repeats the quantization: beyond ~4 rounds of workgroups -- not measured, N > 32768 -- one separate quantize launch is cheaper)
@@ -528,7 +523,7 @@ int qlinear_decode_supported(int M, int N, const int K[3], bool rms, bool w4) {
         if (rms) return (M <= 2 && N <= 32768 && 2 * (size_t)M * (Kt / 32) <= 512 && (Kt <= 4096 || (N + 31) / 32 <= device_cus())) ? 2 : 1;
         return (M <= 2 && N <= 32768) ? 2 : 1;
     }
-    const int feat = decode_features(N), cus = device_cus();
+    const int cus = device_cus(), feat = quant::decode_features(N, cus);
     const int rounds = ((N + feat - 1) / feat + cus - 1) / cus;
     const int passes = (int)((M * (Kt / 32) + decode::NT - 1) / decode::NT);
     if (rms) return (rounds == 1 && M <= 2) ? 2 : 1;
@@ -562,40 +557,23 @@ hipError_t launch_qlinear_decode(const void *X, const int16_t *idx, const uint8_
     a.round_per_segment = round_per_segment;
     a.bias = (const uint16_t *)bias;
     a.D = (uint16_t *)D;
-    const size_t Kt = (size_t)K[0] + K[1] + K[2], ops = decode_operand_bytes(M, K, rms);
-    int stage_rows = (int)((DECODE_LDS_MAX - ops) / (Kt * 2));
-    stage_rows = stage_rows > M ? M : stage_rows;
-    a.stage_rows = stage_rows;
-    const size_t lds = (size_t)stage_rows * Kt * 2 + ops;
-    const bool f16 = decode_features(N) == 16;
-    // lane pairs in the quantization phase when one pass of the workgroup covers every (row, group, half) slot (see the kernels)
-    const bool pairs = 2 * (size_t)stage_rows * (Kt / 32) <= (size_t)NT;
+    // MICROMIX_DECODE_PERSIST=0, read once per process: one workgroup per feature block on the 32-feature kernel too (A/B runs)
+    static const bool persist = [] { const char *e = getenv("MICROMIX_DECODE_PERSIST"); return !(e && e[0] == '0'); }();
+    const quant::DecodePlan p = quant::plan_qlinear_decode(M, N, K, rms, add, w4, device_cus(), persist);
+    a.stage_rows = p.stage_rows;
+    // the one place that turns the plan into an instantiation: the 16- or the 32-feature kernel <fp4 weights, norm, lanes per group, add>
+    const bool f16 = p.features == 16;
     auto pick = [&](auto lpg_) {
         constexpr int L = decltype(lpg_)::value;
-        if (add) return f16 ? (w4 ? qlinear_decode16_kernel<true, true, L, true> : qlinear_decode16_kernel<false, true, L, true>)
-                            : (w4 ? qlinear_decode_kernel<true, true, L, true> : qlinear_decode_kernel<false, true, L, true>);
-        return rms ? (f16 ? (w4 ? qlinear_decode16_kernel<true, true, L> : qlinear_decode16_kernel<false, true, L>)
-                          : (w4 ? qlinear_decode_kernel<true, true, L> : qlinear_decode_kernel<false, true, L>))
-                   : (f16 ? (w4 ? qlinear_decode16_kernel<true, false, L> : qlinear_decode16_kernel<false, false, L>)
-                          : (w4 ? qlinear_decode_kernel<true, false, L> : qlinear_decode_kernel<false, false, L>));
+        if (add) return f16 ? (w4 ? launch_kernel<qlinear_decode16_kernel<true, true, L, true>, Args> : launch_kernel<qlinear_decode16_kernel<false, true, L, true>, Args>)
+                            : (w4 ? launch_kernel<qlinear_decode_kernel<true, true, L, true>, Args> : launch_kernel<qlinear_decode_kernel<false, true, L, true>, Args>);
+        return rms ? (f16 ? (w4 ? launch_kernel<qlinear_decode16_kernel<true, true, L>, Args> : launch_kernel<qlinear_decode16_kernel<false, true, L>, Args>)
+                          : (w4 ? launch_kernel<qlinear_decode_kernel<true, true, L>, Args> : launch_kernel<qlinear_decode_kernel<false, true, L>, Args>))
+                   : (f16 ? (w4 ? launch_kernel<qlinear_decode16_kernel<true, false, L>, Args> : launch_kernel<qlinear_decode16_kernel<false, false, L>, Args>)
+                          : (w4 ? launch_kernel<qlinear_decode_kernel<true, false, L>, Args> : launch_kernel<qlinear_decode_kernel<false, false, L>, Args>));
     };
-    auto kern = pairs ? pick(std::integral_constant<int, 2>{}) : pick(std::integral_constant<int, 1>{});
-    static DynamicLdsOnce done[32];
-    if (hipError_t e = done[(add ? 16 : 0) + (pairs ? 8 : 0) + (rms ? 4 : 0) + (f16 ? 2 : 0) + (w4 ? 0 : 1)].ensure(reinterpret_cast<const void *>(kern), (int)DECODE_LDS_MAX); e != hipSuccess)
-        return e;
-    const int feat = f16 ? BN16 : BN;
-    int blocks = (N + feat - 1) / feat;
-    if (!f16) {
-        // The 32-feature kernel walks its feature blocks (see its phase 2): one workgroup per CU.  Measured (tools/time_decode.py,
-        // K = 4096, (2048,128,1920), one box, us at M = 1 / 4 / 8): gate/up N = 14336 one workgroup per block 13.0 / 16.0 / 20.2,
-        // one per CU 11.4 / 13.4 / 15.8, two per CU 13.1 / 16.1 / 20.2; fused gate + up N = 28672: 26.1 / 32.3 / 40.2 against
-        // 20.9 / 23.1 / 25.4 (two per CU 22.7 / 26.6 / 31.3).  MICROMIX_DECODE_PERSIST=0 restores one workgroup per block (A/B runs).
-        static const bool persist = [] { const char *e = getenv("MICROMIX_DECODE_PERSIST"); return !(e && e[0] == '0'); }();
-        const int resident = device_cus();
-        if (persist && blocks > resident) blocks = resident;
-    }
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(NT), lds, stream, a);
-    return hipGetLastError();
+    auto launch = p.pairs ? pick(std::integral_constant<int, 2>{}) : pick(std::integral_constant<int, 1>{});
+    return launch(p.shape(), stream, DiagEvents{}, a);
 }
 
 }  // namespace mm

@@ -20,6 +20,7 @@
 #include "mx_group_convert.h"
 #include "mx_instrument.h"
 #include "mx_kernels.h"
+#include "mx_quant_plan.h"
 
 namespace mm {
 
@@ -266,81 +267,63 @@ moe_activate_quantize_kernel(const uint16_t *__restrict__ a, const uint16_t *__r
 hipError_t set_quant_clock_buffer(unsigned long long *buf) { return hipMemcpyToSymbol(HIP_SYMBOL(g_quant_clock), &buf, sizeof(buf)); }
 #endif
 
+// ---- the host side: the plan is mx_quant_plan.h's; what follows picks the instantiation and launches ----
+// The one place that turns a plan into template arguments: fn(fp4 weights, the kernel's launch bound)
+template <class Fn>
+static hipError_t for_variant(bool w4, const quant::ReorderPlan &p, Fn &&fn) {
+    using std::bool_constant, std::integral_constant;
+    if (p.max_threads == 256) return w4 ? fn(bool_constant<true>{}, integral_constant<int, 256>{}) : fn(bool_constant<false>{}, integral_constant<int, 256>{});
+    return w4 ? fn(bool_constant<true>{}, integral_constant<int, 1024>{}) : fn(bool_constant<false>{}, integral_constant<int, 1024>{});
+}
+
 hipError_t launch_reorder_quantize(const void *src, int rows, int K, const int16_t *idx, int KN, int KS, int KO, bool w4,
                                    uint8_t *oN, uint8_t *oS, uint8_t *oO, uint8_t *sfN, uint8_t *sfS, uint8_t *sfO,
                                    hipStream_t stream) {
     if (rows == 0) return hipSuccess;
-    const int G = (KN + KS + KO) / 32;
-    const int stagers = K / 32;  // a row of K bf16 is staged as K/8 16-byte chunks, at most 4 per thread
-    const int threads = ((G > stagers ? G : stagers) + 63) / 64 * 64;
-    const size_t lds = (size_t)K * 2 + (w4 ? 0 : (size_t)KS / 4 * 3 + KO);   // the staged row + the image of its fp6 / fp8 codes
-    auto kern = threads <= 256 ? (w4 ? reorder_quantize_kernel<true, 256> : reorder_quantize_kernel<false, 256>)
-                               : (w4 ? reorder_quantize_kernel<true, 1024> : reorder_quantize_kernel<false, 1024>);
-    // K > 21845: the row and the image together pass the default 64 KiB limit of dynamic LDS (at most 96 KiB, K = 32768)
-    static DynamicLdsOnce big_lds;
-    if (lds > 48 * 1024)
-        if (hipError_t e = big_lds.ensure(reinterpret_cast<const void *>(reorder_quantize_kernel<false, 1024>), 96 * 1024); e != hipSuccess) return e;
-    // one resident wave of workgroups (no tail), each striding over the rows
-    const int per_cu = OccupancyCache::get(w4 ? 0 : 1, reinterpret_cast<const void *>(kern), threads, lds);
-    const int cus = device_cus();
-    int blocks = cus * per_cu;
-    // (fewer, fatter workgroups that keep their reorder indices for 2 / 4 / 8 rows were measured: 11.1 -> 11.7 / 15.6 / 23.9 us;
-    // one row per workgroup with the occupancy limited to 12 / 8 / 4 workgroups per CU, so that rounds of workgroups overlap
-    // their load / gather / store phases: 11.3 / 11.4 / 13.7 us)
-    blocks = rows < blocks ? rows : blocks;
-    MM_LAUNCH(kern, dim3(blocks), dim3(threads), lds, stream, (const uint16_t *)src, rows, K, idx, KN, KS, KO, oN,
-                       oS, oO, sfN, sfS, sfO);
-    return hipGetLastError();
+    const quant::ReorderPlan p = quant::plan_reorder_quantize(K, KN, KS, KO, w4);
+    return for_variant(w4, p, [&](auto w4_, auto maxt_) {
+        constexpr auto kern = reorder_quantize_kernel<decltype(w4_)::value, decltype(maxt_)::value>;
+        // one resident wave of workgroups (no tail), each striding over the rows
+        // (fewer, fatter workgroups that keep their reorder indices for 2 / 4 / 8 rows were measured: 11.1 -> 11.7 / 15.6 / 23.9 us;
+        // one row per workgroup with the occupancy limited to 12 / 8 / 4 workgroups per CU, so that rounds of workgroups overlap
+        // their load / gather / store phases: 11.3 / 11.4 / 13.7 us)
+        const int blocks = quant::resident_grid(rows, device_cus(), resident_per_cu<kern>(p.threads, p.lds_bytes));
+        return launch_kernel<kern>(p.shape(blocks), stream, diag_events(), (const uint16_t *)src, rows, K, idx, KN, KS, KO, oN, oS, oO, sfN, sfS, sfO);
+    });
 }
 
 hipError_t launch_reorder_quantize_grouped(const GroupedQuantArgs &ga, int max_rows, bool w4, hipStream_t stream) {
     if (ga.ngroups < 1 || ga.ngroups > MM_MAX_GROUPS || max_rows < 1) return hipErrorInvalidValue;
-    const int G = (ga.KN + ga.KS + ga.KO) / 32, stagers = ga.K / 32;
-    const int threads = ((G > stagers ? G : stagers) + 63) / 64 * 64;
-    const size_t lds = (size_t)ga.K * 2 + (w4 ? 0 : (size_t)ga.KS / 4 * 3 + ga.KO);
-    auto kern = threads <= 256 ? (w4 ? reorder_quantize_grouped_kernel<true, 256> : reorder_quantize_grouped_kernel<false, 256>)
-                               : (w4 ? reorder_quantize_grouped_kernel<true, 1024> : reorder_quantize_grouped_kernel<false, 1024>);
-    static DynamicLdsOnce big_lds;
-    if (lds > 48 * 1024)
-        if (hipError_t e = big_lds.ensure(reinterpret_cast<const void *>(reorder_quantize_grouped_kernel<false, 1024>), 96 * 1024); e != hipSuccess) return e;
-    const int per_cu = OccupancyCache::get(w4 ? 2 : 3, reinterpret_cast<const void *>(kern), threads, lds);
-    const int cus = device_cus();
-    int bx = cus * per_cu / ga.ngroups;   // one resident wave of workgroups shared by the groups
-    bx = bx < 1 ? 1 : bx;
-    bx = max_rows < bx ? max_rows : bx;
-    hipLaunchKernelGGL(kern, dim3(bx, ga.ngroups), dim3(threads), lds, stream, ga);
-    return hipGetLastError();
+    const quant::ReorderPlan p = quant::plan_reorder_quantize(ga.K, ga.KN, ga.KS, ga.KO, w4);
+    return for_variant(w4, p, [&](auto w4_, auto maxt_) {
+        constexpr auto kern = reorder_quantize_grouped_kernel<decltype(w4_)::value, decltype(maxt_)::value>;
+        // one resident wave of workgroups shared by the groups
+        const int bx = quant::resident_grid(max_rows, device_cus(), resident_per_cu<kern>(p.threads, p.lds_bytes), ga.ngroups);
+        return launch_kernel<kern>(p.shape(bx, ga.ngroups), stream, DiagEvents{}, ga);
+    });
 }
 
 hipError_t launch_moe_quantize(const void *src, const int *row_of_slot, const MoeGroups &mg, int src_rows, int K, int KN, int KS, int KO,
                                bool w4, uint8_t *oN, uint8_t *oS, uint8_t *oO, uint8_t *sfN, uint8_t *sfS, uint8_t *sfO, hipStream_t stream) {
     if (mg.n == 0) return hipSuccess;
-    const int G = (KN + KS + KO) / 32, stagers = K / 32;
-    const int threads = ((G > stagers ? G : stagers) + 63) / 64 * 64;
-    const size_t lds = (size_t)K * 2 + (w4 ? 0 : (size_t)KS / 4 * 3 + KO);
-    auto kern = threads <= 256 ? (w4 ? moe_quantize_kernel<true, 256> : moe_quantize_kernel<false, 256>)
-                               : (w4 ? moe_quantize_kernel<true, 1024> : moe_quantize_kernel<false, 1024>);
-    static DynamicLdsOnce big_lds;
-    if (lds > 48 * 1024)
-        if (hipError_t e = big_lds.ensure(reinterpret_cast<const void *>(moe_quantize_kernel<false, 1024>), 96 * 1024); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(mg.n), dim3(threads), lds, stream, (const uint16_t *)src, row_of_slot, mg, src_rows, K, KN, KS, KO, oN, oS,
-                       oO, sfN, sfS, sfO);
-    return hipGetLastError();
+    const quant::ReorderPlan p = quant::plan_reorder_quantize(K, KN, KS, KO, w4);
+    return for_variant(w4, p, [&](auto w4_, auto maxt_) {
+        constexpr auto kern = moe_quantize_kernel<decltype(w4_)::value, decltype(maxt_)::value>;
+        return launch_kernel<kern>(p.shape(mg.n), stream, DiagEvents{}, (const uint16_t *)src, row_of_slot, mg, src_rows, K, KN, KS, KO, oN, oS, oO, sfN,
+                                   sfS, sfO);
+    });
 }
 
 hipError_t launch_moe_activate_quantize(const void *a, const void *b, void *h_out, const MoeGroups &mg, int K, int KN, int KS, int KO, uint8_t *oN,
                                         uint8_t *oS, uint8_t *oO, uint8_t *sfN, uint8_t *sfS, uint8_t *sfO, hipStream_t stream) {
     if (mg.n == 0) return hipSuccess;
-    const int G = (KN + KS + KO) / 32, stagers = K / 32;
-    const int threads = ((G > stagers ? G : stagers) + 63) / 64 * 64;
-    const size_t lds = (size_t)K * 2 + (size_t)KS / 4 * 3 + KO;
-    auto kern = threads <= 256 ? moe_activate_quantize_kernel<256> : moe_activate_quantize_kernel<1024>;
-    static DynamicLdsOnce big_lds;
-    if (lds > 48 * 1024)
-        if (hipError_t e = big_lds.ensure(reinterpret_cast<const void *>(moe_activate_quantize_kernel<1024>), 96 * 1024); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(mg.n), dim3(threads), lds, stream, (const uint16_t *)a, (const uint16_t *)b, (uint16_t *)h_out, mg, K, KN, KS, KO,
-                       oN, oS, oO, sfN, sfS, sfO);
-    return hipGetLastError();
+    const quant::ReorderPlan p = quant::plan_reorder_quantize(K, KN, KS, KO, false);
+    auto launch = [&](auto maxt_) {
+        constexpr auto kern = moe_activate_quantize_kernel<decltype(maxt_)::value>;
+        return launch_kernel<kern>(p.shape(mg.n), stream, DiagEvents{}, (const uint16_t *)a, (const uint16_t *)b, (uint16_t *)h_out, mg, K, KN, KS, KO, oN,
+                                   oS, oO, sfN, sfS, sfO);
+    };
+    return p.max_threads == 256 ? launch(std::integral_constant<int, 256>{}) : launch(std::integral_constant<int, 1024>{});
 }
 
 }  // namespace mm

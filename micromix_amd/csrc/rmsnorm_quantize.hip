@@ -31,6 +31,7 @@
 #include "mx_group_convert.h"
 #include "mx_rms_convert.h"
 #include "mx_kernels.h"
+#include "mx_quant_plan.h"
 
 #define MM_RMS_SCHED_BARRIER() do { MM_DEVICE_ONLY(__builtin_amdgcn_sched_barrier(0);) } while (0)
 
@@ -224,7 +225,8 @@ rmsnorm_quantize_kernel(const uint16_t *__restrict__ src, const uint16_t *__rest
         // T <= 512 + NTH (NTH >= T / 2 and T <= 1024): every slot that is not zeroed (>= 3 NTH) or not folded (>= 512 + NTH) lies at or
         // past T -- its value in the reference's tree is the zero padding, adding it changes nothing -- and is never read: the fold reads
         // g + 512 < 512 + NTH <= 3 NTH only (NTH >= 256), and every later stride is <= 256 <= NTH.
-        // (tests/test_rms_order_gpu.py: K = 16512, 20480, 24576, 28672)
+        // (tests/test_rms_order_gpu.py: K = 16512, 20480, 24576, 28672.  The conditions argued from -- NTH >= 256, 2 NTH >= T, T <= 1024,
+        // 512 + NTH >= T, 3 NTH >= 512 + NTH -- are checked for every plan of this kernel by tools/quant_plan_host_check.cpp.)
 #pragma unroll
         for (int u = 0; u < GPT; ++u) part[g + u * NTH] = sum[u];
         if (g + GPT * NTH < P) part[g + GPT * NTH] = 0.0f;
@@ -545,92 +547,65 @@ rmsnorm_quantize_ring_kernel(const uint16_t *__restrict__ src, const uint16_t *_
     if (prev >= 0) store_code_image(image, bytesS, KO, oS, oO, prev);
 }
 
+// ---- the host side: the plan is mx_quant_plan.h's; what follows reads the environment, picks the instantiation and launches ----
+// MICROMIX_RMS_RING, read once per process: 0 never the ring kernel, 3 / 4 always with that depth (K <= 8192); unset: the plan's rule
+static int rms_ring_pin() {
+    static const int pin = getenv("MICROMIX_RMS_RING") ? atoi(getenv("MICROMIX_RMS_RING")) : -1;
+    return pin;
+}
+
+// what every kernel of the file takes in front of its last argument (the staging hook; the ring kernels: the slot size)
+struct RowArgs {
+    const uint16_t *src, *weight;
+    float eps;
+    int rows, K;
+    const int16_t *idx;
+    int KN, KS, KO;
+    uint8_t *oN, *oS, *oO, *sfN, *sfS, *sfO;
+};
+// The one launch of a planned kernel: CUs x occupancy workgroups striding over the rows, with the diagnostics events
+template <auto Kern, class Last>
+static hipError_t launch_rows(const quant::RmsPlan &p, const RowArgs &a, hipStream_t stream, const Last &last) {
+    const int blocks = quant::resident_grid(a.rows, device_cus(), resident_per_cu<Kern>(p.threads, p.lds_bytes));
+    return launch_kernel<Kern>(p.shape(blocks), stream, diag_events(), a.src, a.weight, a.eps, a.rows, a.K, a.idx, a.KN, a.KS, a.KO, a.oN, a.oS, a.oO, a.sfN,
+                               a.sfS, a.sfO, last);
+}
+// The plans that stage the row through registers, with either hook: 256 / 512 / 512 threads, K <= 8192 / 16384 / 32768 (beyond 16384 a
+// thread plays two of the reference's group threads)
+template <class Stage>
+static hipError_t launch_staged(const quant::RmsPlan &p, bool integer_round, const RowArgs &a, hipStream_t stream, const Stage &hook) {
+    auto launch = p.kernel == quant::RMS_PRODUCTS ? (integer_round ? launch_rows<rmsnorm_quantize_products_kernel<true, Stage>, Stage>
+                                                                   : launch_rows<rmsnorm_quantize_products_kernel<false, Stage>, Stage>)
+                : p.kernel == quant::RMS_STAGED1 ? (integer_round ? launch_rows<rmsnorm_quantize_kernel<true, 1, Stage>, Stage>
+                                                                  : launch_rows<rmsnorm_quantize_kernel<false, 1, Stage>, Stage>)
+                                                 : (integer_round ? launch_rows<rmsnorm_quantize_kernel<true, 2, Stage>, Stage>
+                                                                  : launch_rows<rmsnorm_quantize_kernel<false, 2, Stage>, Stage>);
+    return launch(p, a, stream, hook);
+}
+
 hipError_t launch_rmsnorm_quantize(const void *src, const void *weight, float eps, int rows, int K, const int16_t *idx, int KN,
                                    int KS, int KO, bool integer_round, uint8_t *oN, uint8_t *oS, uint8_t *oO, uint8_t *sfN,
                                    uint8_t *sfS, uint8_t *sfO, hipStream_t stream) {
     if (rows == 0) return hipSuccess;
-    const int T = K / 32;
-    const int groups_per_thread = T > 512 ? 2 : 1;     // K > 16384: rmsnorm_quantize_kernel<*, 2>, 512 threads
-    // (the ring kernel's counted vmcnt needs exactly roundup64(K / 32) threads -- every wave's lane 0 owns a group; it traps otherwise)
-    const int threads = ((T + groups_per_thread - 1) / groups_per_thread + 63) / 64 * 64;
-    int P = 64;
-    while (P < T) P <<= 1;
-    const bool products = threads <= 256;   // K <= 8192: the 32-bit product row (see the header)
-    // K <= 8192, round 5: the LDS-DMA row ring (MICROMIX_RMS_RING=0: the products kernel; =3 / 4: ring depth)
-    // Measured (round 5, tools/time_rmsnorm.py, K = 4096, us, products / ring of 3): 256 rows 7.5 / 5.8 -- the ring kernel's prologue
-    // requests its first rows before anything else -- but 4096 rows 11.6 / 14.7: with several rows per workgroup the launch is bound by
-    // the per-row instruction stream (the integer rounding alone is 1.5 us of it), not by bytes in flight, and the ring kernel reads its
-    // row back from LDS for the sum of squares.  So: the ring while a workgroup sees at most ~2 rows (rows <= 2 x CUs), the products
-    // kernel beyond.  MICROMIX_RMS_RING=0 never, =3 / =4 always with that depth.
-    static const int ring_pin = getenv("MICROMIX_RMS_RING") ? atoi(getenv("MICROMIX_RMS_RING")) : -1;
-    const int ring = ring_pin >= 0 ? ring_pin : (rows <= 2 * device_cus() ? 3 : 0);
-    if (products && ring >= 3) {
-        const int slot = ((K * 2 + 1023) / 1024) * 1024;
-        const int R = ring >= 4 ? 4 : 3;
-        const size_t lds_r = (size_t)R * slot + 1024 + (size_t)(P > threads ? P : threads) * 4 + (size_t)KS / 4 * 3 + KO;
-        auto kr = R == 4 ? (integer_round ? rmsnorm_quantize_ring_kernel<true, 4> : rmsnorm_quantize_ring_kernel<false, 4>)
-                         : (integer_round ? rmsnorm_quantize_ring_kernel<true, 3> : rmsnorm_quantize_ring_kernel<false, 3>);
-        static DynamicLdsOnce rattr[4];
-        if (lds_r > 48 * 1024)
-            if (hipError_t e = rattr[(R == 4 ? 2 : 0) + (integer_round ? 1 : 0)].ensure(reinterpret_cast<const void *>(kr), 104 * 1024); e != hipSuccess) return e;
-        const int per_cu = OccupancyCache::get(integer_round ? 6 : 7, reinterpret_cast<const void *>(kr), threads, lds_r);
-        int blocks = device_cus() * per_cu;
-        blocks = rows < blocks ? rows : blocks;
-        MM_LAUNCH(kr, dim3(blocks), dim3(threads), lds_r, stream, (const uint16_t *)src, (const uint16_t *)weight, eps, rows, K, idx, KN, KS, KO,
-                  oN, oS, oO, sfN, sfS, sfO, slot);
-        return hipGetLastError();
+    const quant::RmsPlan p = quant::plan_rmsnorm_quantize(rows, K, KS, KO, false, device_cus(), rms_ring_pin());
+    const RowArgs a = {(const uint16_t *)src, (const uint16_t *)weight, eps, rows, K, idx, KN, KS, KO, oN, oS, oO, sfN, sfS, sfO};
+    if (const int R = quant::rms_ring_depth(p.kernel)) {
+        auto launch = R == 4 ? (integer_round ? launch_rows<rmsnorm_quantize_ring_kernel<true, 4>, int> : launch_rows<rmsnorm_quantize_ring_kernel<false, 4>, int>)
+                             : (integer_round ? launch_rows<rmsnorm_quantize_ring_kernel<true, 3>, int> : launch_rows<rmsnorm_quantize_ring_kernel<false, 3>, int>);
+        return launch(p, a, stream, p.slot_bytes);
     }
-    const int pslots = P > groups_per_thread * threads ? P : groups_per_thread * threads;
-    const size_t lds = (size_t)K * (products ? 4 : 2) + (size_t)pslots * 4 + (size_t)KS / 4 * 3 + KO;
-    // 256 / 512 / 512 threads: K <= 8192 / 16384 / 32768 (beyond 16384 a thread plays two of the reference's group threads)
-    auto kern = products ? (integer_round ? rmsnorm_quantize_products_kernel<true> : rmsnorm_quantize_products_kernel<false>)
-              : groups_per_thread == 1 ? (integer_round ? rmsnorm_quantize_kernel<true, 1> : rmsnorm_quantize_kernel<false, 1>)
-                               : (integer_round ? rmsnorm_quantize_kernel<true, 2> : rmsnorm_quantize_kernel<false, 2>);
-    // K > ~21000: row + partial sums + the image of the fp6 / fp8 codes pass the default 64 KiB limit of dynamic LDS (K = 32768: 100 KiB)
-    static DynamicLdsOnce attr[6];
-    if (lds > 48 * 1024) {
-        const int which = (products ? 0 : groups_per_thread == 1 ? 1 : 2) * 2 + (integer_round ? 1 : 0);
-        if (hipError_t e = attr[which].ensure(reinterpret_cast<const void *>(kern), 104 * 1024); e != hipSuccess) return e;
-    }
-    const int per_cu = OccupancyCache::get(integer_round ? 4 : 5, reinterpret_cast<const void *>(kern), threads, lds);
-    const int cus = device_cus();
-    int blocks = cus * per_cu;
-    blocks = rows < blocks ? rows : blocks;
-    MM_LAUNCH(kern, dim3(blocks), dim3(threads), lds, stream, (const uint16_t *)src, (const uint16_t *)weight, eps, rows,
-                       K, idx, KN, KS, KO, oN, oS, oO, sfN, sfS, sfO, RowLoad());
-    return hipGetLastError();
+    return launch_staged(p, integer_round, a, stream, RowLoad());
 }
 
-// mm_add_rmsnorm_quantize: the two kernels that stage the row through registers, at every row count -- the LDS-DMA ring moves global
-// memory straight to LDS and cannot add on the way.  Grid as above: CUs x occupancy workgroups striding over the rows.
+// mm_add_rmsnorm_quantize: the kernels that stage the row through registers, at every row count -- the LDS-DMA ring moves global memory
+// straight to LDS and cannot add on the way, so the plan of a launch with the residual never names it
 hipError_t launch_add_rmsnorm_quantize(const void *src, const void *res, void *s_out, const void *weight, float eps, int rows, int K,
                                        const int16_t *idx, int KN, int KS, int KO, bool integer_round, uint8_t *oN, uint8_t *oS, uint8_t *oO,
                                        uint8_t *sfN, uint8_t *sfS, uint8_t *sfO, hipStream_t stream) {
     if (rows == 0) return hipSuccess;
-    const int T = K / 32;
-    const int groups_per_thread = T > 512 ? 2 : 1;
-    const int threads = ((T + groups_per_thread - 1) / groups_per_thread + 63) / 64 * 64;
-    int P = 64;
-    while (P < T) P <<= 1;
-    const bool products = threads <= 256;
-    const int pslots = P > groups_per_thread * threads ? P : groups_per_thread * threads;
-    const size_t lds = (size_t)K * (products ? 4 : 2) + (size_t)pslots * 4 + (size_t)KS / 4 * 3 + KO;
-    using Add = RowAddResidual;
-    auto kern = products ? (integer_round ? rmsnorm_quantize_products_kernel<true, Add> : rmsnorm_quantize_products_kernel<false, Add>)
-              : groups_per_thread == 1 ? (integer_round ? rmsnorm_quantize_kernel<true, 1, Add> : rmsnorm_quantize_kernel<false, 1, Add>)
-                               : (integer_round ? rmsnorm_quantize_kernel<true, 2, Add> : rmsnorm_quantize_kernel<false, 2, Add>);
-    static DynamicLdsOnce attr[6];
-    if (lds > 48 * 1024) {
-        const int which = (products ? 0 : groups_per_thread == 1 ? 1 : 2) * 2 + (integer_round ? 1 : 0);
-        if (hipError_t e = attr[which].ensure(reinterpret_cast<const void *>(kern), 104 * 1024); e != hipSuccess) return e;
-    }
-    // (slots of its own: a layer stack alternates this launch with mm_rmsnorm_quantize's)
-    const int per_cu = OccupancyCache::get(integer_round ? 8 : 9, reinterpret_cast<const void *>(kern), threads, lds);
-    int blocks = device_cus() * per_cu;
-    blocks = rows < blocks ? rows : blocks;
-    MM_LAUNCH(kern, dim3(blocks), dim3(threads), lds, stream, (const uint16_t *)src, (const uint16_t *)weight, eps, rows, K, idx, KN, KS, KO,
-              oN, oS, oO, sfN, sfS, sfO, Add{(const uint16_t *)res, (uint16_t *)s_out});
-    return hipGetLastError();
+    const quant::RmsPlan p = quant::plan_rmsnorm_quantize(rows, K, KS, KO, true, device_cus(), rms_ring_pin());
+    const RowArgs a = {(const uint16_t *)src, (const uint16_t *)weight, eps, rows, K, idx, KN, KS, KO, oN, oS, oO, sfN, sfS, sfO};
+    return launch_staged(p, integer_round, a, stream, RowAddResidual{(const uint16_t *)res, (uint16_t *)s_out});
 }
 
 }  // namespace mm
