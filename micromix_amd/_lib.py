@@ -134,6 +134,8 @@ KV_STEP_STATUS = {v: n for n, v in KV_STEP.items() if n not in ("MM_KV_STEP_MAX_
 _TOKENS_PROTOS, TOKENS_EXPORTS, TOKENS = _read("micromix_tokens.h")
 # RANDOM_EXPORTS: the entry of include/micromix_random.h, likewise; RANDOM holds its two limits by name
 _RANDOM_PROTOS, RANDOM_EXPORTS, RANDOM = _read("micromix_random.h")
+# ATTENTION_EXPORTS: the entry of include/micromix_attention.h, likewise; ATTENTION holds the kernel's two tile sizes and the stride limit by name
+_ATTENTION_PROTOS, ATTENTION_EXPORTS, ATTENTION = _read("micromix_attention.h")
 
 _lib = None
 
@@ -148,7 +150,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -m micromix_amd.build` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for protos in (_PROTOS, _CALIB_PROTOS, _LOGPROB_PROTOS, _LOGITS_PROTOS, _SPEC_PROTOS, _KVSTEP_PROTOS, _TOKENS_PROTOS, _RANDOM_PROTOS):
+    for protos in (_PROTOS, _CALIB_PROTOS, _LOGPROB_PROTOS, _LOGITS_PROTOS, _SPEC_PROTOS, _KVSTEP_PROTOS, _TOKENS_PROTOS, _RANDOM_PROTOS, _ATTENTION_PROTOS):
         _bind(lib, protos)
     _lib = lib
     return _lib

@@ -7,6 +7,7 @@
 #include "../../include/micromix_kvstep.h"
 #include "../../include/micromix_tokens.h"
 #include "../../include/micromix_random.h"
+#include "../../include/micromix_attention.h"
 #include "mx_common.h"
 #include "mx_kernels.h"
 #include "mx_kv_shared_host.h"
@@ -861,6 +862,32 @@ int mm_uniform_rows(const int64_t *seed, const int32_t *sub, int batch, const in
     const mm::UniformRows s{(const long long *)seed, sub, batch, row_seq, pos, rows, n, domain, out, bits, ld_out};
     hipError_t e = mm::launch_uniform_rows(s, (hipStream_t)stream);
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_uniform_rows");
+}
+
+// ---- dense causal attention over contiguous q, k, v (dense_attention.hip, include/micromix_attention.h)
+int mm_dense_attention(const void *q, const void *k, const void *v, long long q_stride, long long k_stride, long long v_stride,
+                       const int32_t *seq_indptr, int batch, int total_tokens, int num_q_heads, int num_kv_heads, int head_dim, float sm_scale,
+                       void *o, mm_stream_t stream) {
+    if (total_tokens < 0 || batch < 0 || num_q_heads < 1 || num_kv_heads < 1) return MM_ERR_BAD_ARG;
+    const bool work = total_tokens > 0 && batch > 0;
+    if (work) {
+        if (!q || !k || !v || !o || !seq_indptr) return MM_ERR_BAD_ARG;
+        if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) & 15) || ((uintptr_t)seq_indptr & 3)) return MM_ERR_BAD_ARG;
+        if (((q_stride | k_stride | v_stride) & 7) || q_stride < (long long)num_q_heads * 128 || k_stride < (long long)num_kv_heads * 128 ||
+            v_stride < (long long)num_kv_heads * 128)
+            return MM_ERR_BAD_ARG;
+    }
+    if (head_dim != 128 || num_q_heads % num_kv_heads) return MM_ERR_UNSUPPORTED;
+    if (!work) return MM_OK;
+    if (q_stride > MM_DENSE_ATTN_MAX_STRIDE || k_stride > MM_DENSE_ATTN_MAX_STRIDE || v_stride > MM_DENSE_ATTN_MAX_STRIDE) return MM_ERR_UNSUPPORTED;
+    if (((long long)total_tokens / MM_DENSE_ATTN_BQ + batch) * num_q_heads >= (1LL << 31)) return MM_ERR_UNSUPPORTED;
+    mm::DenseAttention a{};
+    a.q = (const uint16_t *)q, a.k = (const uint16_t *)k, a.v = (const uint16_t *)v;
+    a.sq = q_stride, a.sk = k_stride, a.sv = v_stride;
+    a.indptr = seq_indptr, a.B = batch, a.T = total_tokens, a.Hq = num_q_heads, a.Hkv = num_kv_heads;
+    a.o = (uint16_t *)o;
+    hipError_t e = mm::launch_dense_attention(a, sm_scale, (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_dense_attention");
 }
 
 // ---- calibration statistics (calib_stats.hip, include/micromix_calib.h)

@@ -1,0 +1,252 @@
+// Dense causal GQA attention over contiguous bf16 q, k, v (mm_dense_attention, include/micromix_attention.h, which states the function).
+// No cache and no page table: K and V rows of a sequence lie stride apart, so every address is affine in the tile index.
+//
+// One workgroup (4 waves) per (128-token query tile of one sequence, query head); wave w owns rows 32 w .. 32 w + 31 of the tile as two
+// blocks of 16, with q (B fragments, 32 VGPRs) and the fp32 O^T accumulators (64 VGPRs) in registers for the whole walk.  The kv tokens
+// are walked 64 at a time, tiles above the diagonal are not visited, a wave skips the tiles above its own rows, and the compare runs
+// only on the tiles that cross a wave's diagonal.
+//   staging  K and V tiles go global -> LDS with the LDS-DMA (dma16: 64 lanes x 16 B per instruction, 8 per wave per tile), both AS
+//            STORED ([token][128 dims], 256 B rows), double buffered (2 x 32 KB).  The DMA writes LDS in lane order, so the layout is
+//            chosen by which 16-byte chunk of the row a lane FETCHES: position p of row r holds chunk p ^ (r & 15) of K and chunk
+//            p ^ ((r & 7) << 1) of V, which makes the reads below free of bank conflicts without padding.  Rows past the last token the
+//            tile's queries attend are fetched from that last token (finite, masked), so nothing outside the sequence is ever read.
+//   pipeline per tile: wait_vmcnt<0> (this wave's part of tile t has landed), ONE barrier (everybody's has, and everybody is done with
+//            tile t - 1), issue tile t + 1 into the other buffer, then the math of tile t.  No load depends on another load.
+//   scores   S^T = K q^T on v_mfma_f32_16x16x32_bf16, A = K rows from LDS (one ds_read_b128 serves both row blocks), B = q: a lane
+//            holds 16 scores of one query row per block, the row max crosses 4 lanes.  Online softmax in fp32, log2 domain.
+//   p.V      O^T += V^T P^T, B = bf16(p) straight from the score registers, A = V read TRANSPOSED from the as-stored tile with
+//            ds_read_b64_tr_b16: the 16 lanes of a group fetch 4 tokens x 16 dims and each receives its dim's 4 tokens (again one read
+//            for both row blocks).
+// GQA: blockIdx.x = tile * Hq + head with the head fastest, so the g workgroups that share a kv head's K/V tiles are dispatched next
+// to each other and all but the first find them in L2.  The last tiles (the longest walks) come first.
+// Sequence b owns tiles [seq_indptr[b] / 128 + b, seq_indptr[b + 1] / 128 + b + 1), which hold its ceil(n_b / 128) tiles, so the grid
+// (T / 128 + B) * Hq needs no host copy of seq_indptr; the surplus workgroups exit.
+#include "../../include/micromix_attention.h"
+#include "mx_buffer_ops.h"
+#include "mx_kernels.h"
+#include "mx_paged_kv.h"      // v8bf, v4u, v2u, pack_bf, HD
+
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+namespace {
+
+using mm::DenseAttention;
+using mm::kv::HD;
+using mm::kv::pack_bf;
+using mm::kv::v2u;
+using mm::kv::v4u;
+using mm::kv::v8bf;
+using mm::rsrc_t;
+using mm::v4f;
+
+constexpr int BQ = MM_DENSE_ATTN_BQ, BK = MM_DENSE_ATTN_BK, NT = 256;
+constexpr int ROWB = HD * 2;                 // bytes of a K / V row in LDS
+constexpr int TILEB = BK * ROWB;             // one K or V tile
+constexpr int BUFB = 2 * TILEB;              // K | V of one kv tile
+constexpr int LDS_BYTES = 2 * BUFB;          // double buffered
+static_assert(BQ == 128 && BK == 64 && HD == 128 && LDS_BYTES == 65536, "the lane maps below are written for these tiles");
+
+typedef __bf16 bf16x4 __attribute__((__vector_size__(8)));
+typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+
+// (sequence, tile of it, first token, token count) of workgroup tile index i; false for a surplus tile
+__device__ inline bool tile_of(const DenseAttention &a, int i, int &j, int &q0, int &n) {
+    int lo = 0, hi = a.B;                            // the largest b with start(b) = seq_indptr[b] / BQ + b <= i
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (min(max(a.indptr[mid], 0), a.T) / BQ + mid <= i) lo = mid; else hi = mid;
+    }
+    q0 = min(max(a.indptr[lo], 0), a.T);
+    n = min(max(a.indptr[lo + 1], 0), a.T) - q0;
+    j = i - (q0 / BQ + lo);
+    return n > 0 && j >= 0 && j * BQ < n;
+}
+
+// V^T fragment of 4 tokens: lane c of a 16-lane group passes the address of token (c >> 2), dims 4 (c & 3) .. + 3 of a 4 x 16 block and
+// receives the block's 4 tokens of dim c
+__device__ __forceinline__ v2u read_tr(const uint8_t *p) {
+    v2u r = {0u, 0u};
+    MM_DEVICE_ONLY(r = __builtin_bit_cast(v2u, __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4 *)p));)
+    return r;
+}
+
+__global__ __launch_bounds__(NT) void dense_attention_kernel(const DenseAttention a) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];   // [2][K tile | V tile], written by the LDS-DMA only
+
+    const int x = blockIdx.x, h = x % a.Hq, kvh = h / a.g;
+    const int tile = a.tiles - 1 - x / a.Hq;              // the last tiles of a sequence carry the most work: they start first
+    int j, q0, n;
+    if (!tile_of(a, tile, j, q0, n)) return;
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l = tid & 63, c = l & 15, kq = l >> 4;
+    const int i0 = j * BQ;                                // first token (of the sequence) of this query tile
+    const int kend = min(n, i0 + BQ);                     // tokens 0 .. kend - 1 are attended by some row
+    const int nt = (kend + BK - 1) / BK;
+    const int wr0 = i0 + 32 * wave;                       // this wave's first row; its last valid one
+    const bool wactive = wr0 < n;
+    const int wmax = min(wr0 + 31, n - 1);
+
+    // ---- q as the MFMA B operand: row block rb, lane (c, kq) holds row wr0 + 16 rb + c, dims 32 kq + 8 s + e in step s
+    v8bf qb[2][4];
+    int irow[2];
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb) {
+        irow[rb] = wr0 + 16 * rb + c;
+        const bool valid = irow[rb] < n;
+        const v4u *qp = (const v4u *)(a.q + (int64_t)(q0 + (valid ? irow[rb] : i0)) * a.sq + (int64_t)h * HD + 32 * kq);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) qb[rb][s] = __builtin_bit_cast(v8bf, valid ? qp[s] : v4u{0, 0, 0, 0});
+    }
+
+    // ---- staging: DMA instruction i of wave w fills LDS rows 16 w + 4 i .. + 3 of a tile, lane (kq, c) position c of row 16 w + 4 i + kq
+    const uint8_t *kseq = (const uint8_t *)(a.k + (int64_t)q0 * a.sk + (int64_t)kvh * HD);
+    const uint8_t *vseq = (const uint8_t *)(a.v + (int64_t)q0 * a.sv + (int64_t)kvh * HD);
+    const int skb = (int)a.sk * 2, svb = (int)a.sv * 2;   // bytes between two tokens (<= 2^23)
+    const unsigned lds0 = __builtin_amdgcn_readfirstlane(mm::lds_address(smem));
+    auto issue = [&](int t) {
+        const int kt = t * BK, nrows = min(kend - kt, BK);           // >= 1
+        const rsrc_t rk = mm::make_rsrc(kseq + (int64_t)kt * skb, (unsigned)((nrows - 1) * skb + ROWB));
+        const rsrc_t rv = mm::make_rsrc(vseq + (int64_t)kt * svb, (unsigned)((nrows - 1) * svb + ROWB));
+        const unsigned base = lds0 + (t & 1) * BUFB + wave * 4096;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int rr = 16 * wave + 4 * i + kq, rc = min(rr, nrows - 1);
+            mm::dma16(rk, rc * skb + ((c ^ (rr & 15)) << 4), 0, base + i * 1024);
+            mm::dma16(rv, rc * svb + ((c ^ ((rr & 7) << 1)) << 4), 0, base + TILEB + i * 1024);
+        }
+    };
+
+    // ---- LDS read offsets of this lane.  K: row 16 blk + c, chunk 4 kq + s.  V (transposed read): token 32 ks + 16 u + 4 kq + (c >> 2),
+    // dims 16 dt + 4 (c & 3) .. + 3, that is chunk 2 dt + ((c >> 1) & 1), its half c & 1
+    int koff[4], voff[2];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) koff[s] = c * ROWB + (((4 * kq + s) ^ c) << 4);
+    const int vtok = 4 * kq + (c >> 2), vsw = (vtok & 7) << 1, vx = (c >> 1) & 1, vhalf = (c & 1) << 3;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) voff[u] = (16 * u + vtok) * ROWB + vhalf;
+
+    float m[2] = {-INFINITY, -INFINITY}, lsum[2] = {0.0f, 0.0f};
+    v4f o[2][8];
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int dt = 0; dt < 8; ++dt) o[rb][dt] = v4f{0.0f, 0.0f, 0.0f, 0.0f};
+
+    issue(0);
+    for (int t = 0; t < nt; ++t) {
+        mm::wait_vmcnt<0>();                               // this wave's share of tile t is in LDS
+        __syncthreads();                                   // ... everybody's is, and nobody still reads tile t - 1
+        if (t + 1 < nt) issue(t + 1);                      // in flight during this tile's math
+        const int kt = t * BK;
+        if (!wactive || kt > wmax) continue;               // every row of this wave is masked on this tile
+        const uint8_t *sk = smem + (t & 1) * BUFB, *sv = sk + TILEB;
+
+        // ---- scores S^T: lane (c, kq) holds, for its row of each block, tokens kt + 16 blk + 4 kq + r
+        float sc[2][4][4];
+#pragma unroll
+        for (int blk = 0; blk < 4; ++blk) {
+            v4f d0 = {0.0f, 0.0f, 0.0f, 0.0f}, d1 = d0;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const v8bf kf = __builtin_bit_cast(v8bf, *(const v4u *)(sk + blk * 16 * ROWB + koff[s]));
+                d0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qb[0][s], d0, 0, 0, 0);
+                d1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qb[1][s], d1, 0, 0, 0);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                sc[0][blk][r] = d0[r] * a.scale_log2;
+                sc[1][blk][r] = d1[r] * a.scale_log2;
+            }
+        }
+        if (kt + BK - 1 > wr0) {                           // the tile crosses the diagonal of some row of this wave
+#pragma unroll
+            for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+                for (int blk = 0; blk < 4; ++blk)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (kt + 16 * blk + 4 * kq + r > irow[rb]) sc[rb][blk][r] = -INFINITY;
+        }
+        // ---- online softmax (log2 domain), P as the B operand of p.V: k step ks covers tokens 32 ks + {4 kq + e, 16 + 4 kq + e}
+        v8bf pb[2][2];
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb) {
+            float mt = -INFINITY;
+#pragma unroll
+            for (int blk = 0; blk < 4; ++blk)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) mt = fmaxf(mt, sc[rb][blk][r]);
+            mt = fmaxf(mt, __shfl_xor(mt, 16));
+            mt = fmaxf(mt, __shfl_xor(mt, 32));
+            const float mn = fmaxf(m[rb], mt), mb = mn == -INFINITY ? 0.0f : mn, alpha = __builtin_amdgcn_exp2f(m[rb] - mb);
+            m[rb] = mn;
+            float ps = 0.0f;
+#pragma unroll
+            for (int blk = 0; blk < 4; ++blk)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    sc[rb][blk][r] = __builtin_amdgcn_exp2f(sc[rb][blk][r] - mb);
+                    ps += sc[rb][blk][r];
+                }
+            lsum[rb] = lsum[rb] * alpha + ps;
+#pragma unroll
+            for (int dt = 0; dt < 8; ++dt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) o[rb][dt][r] *= alpha;
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                v4u w;
+                w.x = pack_bf(sc[rb][2 * ks][0], sc[rb][2 * ks][1]);
+                w.y = pack_bf(sc[rb][2 * ks][2], sc[rb][2 * ks][3]);
+                w.z = pack_bf(sc[rb][2 * ks + 1][0], sc[rb][2 * ks + 1][1]);
+                w.w = pack_bf(sc[rb][2 * ks + 1][2], sc[rb][2 * ks + 1][3]);
+                pb[rb][ks] = __builtin_bit_cast(v8bf, w);
+            }
+        }
+        // ---- p.V: O^T lane (c, kq) holds row c of each block, dims 16 dt + 4 kq + r
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+#pragma unroll
+            for (int dt = 0; dt < 8; ++dt) {
+                const int chunk = (((2 * dt) ^ vsw) | vx) << 4;
+                const v2u a0 = read_tr(sv + ks * 32 * ROWB + voff[0] + chunk), a1 = read_tr(sv + ks * 32 * ROWB + voff[1] + chunk);
+                const v8bf va = __builtin_bit_cast(v8bf, v4u{a0.x, a0.y, a1.x, a1.y});
+                o[0][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(va, pb[0][ks], o[0][dt], 0, 0, 0);
+                o[1][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(va, pb[1][ks], o[1][dt], 0, 0, 0);
+            }
+        }
+    }
+
+    // ---- row totals over the 4 lanes of a row, then o = O / l, rounded to bf16 once
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb) {
+        float ls = lsum[rb];
+        ls += __shfl_xor(ls, 16);
+        ls += __shfl_xor(ls, 32);
+        if (irow[rb] >= n) continue;
+        const float inv = ls > 0.0f ? 1.0f / ls : 0.0f;
+        uint16_t *orow = a.o + ((int64_t)(q0 + irow[rb]) * a.Hq + h) * HD + 4 * kq;
+#pragma unroll
+        for (int dt = 0; dt < 8; ++dt) {
+            v2u w;
+            w.x = pack_bf(o[rb][dt][0] * inv, o[rb][dt][1] * inv);
+            w.y = pack_bf(o[rb][dt][2] * inv, o[rb][dt][3] * inv);
+            *(v2u *)(orow + 16 * dt) = w;
+        }
+    }
+}
+
+}  // namespace
+
+namespace mm {
+
+hipError_t launch_dense_attention(DenseAttention a, float sm_scale, hipStream_t stream) {
+    a.g = a.Hq / a.Hkv;
+    a.tiles = a.T / BQ + a.B;
+    a.scale_log2 = kv_scale_log2(sm_scale);
+    dense_attention_kernel<<<(unsigned)((long long)a.tiles * a.Hq), NT, LDS_BYTES, stream>>>(a);
+    return hipGetLastError();
+}
+
+}  // namespace mm

@@ -385,6 +385,18 @@ struct UniformRows {
     long long ld_out;
 };
 hipError_t launch_uniform_rows(const UniformRows &s, hipStream_t stream);
+// dense causal GQA attention over contiguous bf16 q, k, v (dense_attention.hip, include/micromix_attention.h): sq, sk, sv are the
+// elements between two tokens; g, tiles and scale_log2 are filled in by the launch
+struct DenseAttention {
+    const uint16_t *q, *k, *v;
+    long long sq, sk, sv;
+    const int *indptr;
+    int B, T, Hq, Hkv;
+    uint16_t *o;
+    int g, tiles;
+    float scale_log2;
+};
+hipError_t launch_dense_attention(DenseAttention a, float sm_scale, hipStream_t stream);
 // token log-probabilities over bf16 rows (logprob.hip, include/micromix_logprob.h): target and temperature device arrays of `rows`
 // entries or null, every output null when not wanted, top_n 0 .. 32; ws: logprob_workspace_bytes, uninitialised
 size_t logprob_workspace_bytes(int rows, int vocab, int top_n);

@@ -1,5 +1,6 @@
 """The paged KV cache and what runs over it, as `mixedgemm` exports it: append (with RoPE), page copy and row moves, decode, shared-prefix
-decode and prefill attention (include/micromix_hip.h, mm_kv_append .. mm_paged_prefill_tree), the end of a speculative step:
+decode and prefill attention (include/micromix_hip.h, mm_kv_append .. mm_paged_prefill_tree), `dense_attention` over contiguous q, k, v
+without a cache (include/micromix_attention.h), the end of a speculative step:
 `process_logits` (include/micromix_logits.h) -> `argmax_rows` / `sample_rows` / `spec_sample_rows` (include/micromix_spec.h; `uniform_rows`,
 include/micromix_random.h, makes their uniform numbers from the request's seed and the position) ->
 `verify_greedy` -> `token_step` (include/micromix_tokens.h: the token history's half of a step; `ngram_draft` drafts the next chain from
@@ -20,7 +21,7 @@ __all__ = ["kv_append", "rope_kv_append", "kv_copy_pages", "kv_move_rows", "kv_s
            "paged_decode_shared_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes", "argmax_rows", "argmax_rows_workspace_bytes",
            "verify_greedy", "sample_rows", "sample_rows_workspace_bytes", "logprob_rows", "logprob_rows_workspace_bytes", "cross_entropy",
            "process_logits", "spec_sample_rows", "spec_sample_rows_workspace_bytes", "chain_candidates", "token_step", "ngram_draft",
-           "ngram_draft_workspace_bytes", "uniform_rows"]
+           "ngram_draft_workspace_bytes", "uniform_rows", "dense_attention"]
 
 # entries a library built before them lacks: (the symbol looked for, the names and the feature of the rebuild message)
 _TREE = ("mm_paged_prefill_tree", "mm_paged_prefill_tree / mm_kv_move_rows", "tree-masked attention")
@@ -32,6 +33,7 @@ _SPEC = ("mm_spec_sample_rows", "mm_spec_sample_rows", "speculative sampling")
 _KVSTEP = ("mm_kv_step", "mm_kv_step", "device steps of the page table")
 _TOKENS = ("mm_ngram_draft", "mm_token_step / mm_ngram_draft", "the token history on the device")
 _RANDOM = ("mm_uniform_rows", "mm_uniform_rows", "seeded uniform numbers")
+_DENSE = ("mm_dense_attention", "mm_dense_attention", "dense attention over contiguous q, k, v")
 _SHARED = ("mm_paged_decode_shared", "mm_paged_decode_shared", "shared-prefix decode")
 
 
@@ -1152,4 +1154,53 @@ def paged_prefill(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, qo
         _launch("paged_prefill", dev, lib.mm_paged_prefill_window, *args, _stream_ptr(dev), window)
     else:
         _launch("paged_prefill", dev, lib.mm_paged_prefill, *args, _stream_ptr(dev))
+    return o
+
+
+def dense_attention(q, k, v, seq_indptr=None, sm_scale=None):
+    """Causal GQA attention over contiguous bf16 q, k, v, without a cache: what scaled_dot_product_attention(q, repeat_kv(k),
+    repeat_kv(v), is_causal=True) computes for every sequence of a flattened batch; returns o, bf16 [T, Hq, 128].
+
+    q, k, v: bf16 [T, H, 128] or [T, H * 128], the same T tokens, Hq a multiple of Hkv; query head h reads kv head h // (Hq // Hkv).
+    A tensor whose rows lie contiguous within a token is read in place whatever its token stride (a multiple of 8 elements, the pointer
+    16-byte aligned): the three views of one packed [T, (Hq + 2 Hkv) * 128] projection (what FusedQLinear returns) are not copied
+    apart, and K / V are not repeated.  Anything else is copied with .contiguous() first.
+    seq_indptr: int32 [B + 1] device tensor, sequence b owns tokens seq_indptr[b] .. seq_indptr[b + 1]; None: one sequence of T tokens.
+    A [bsz, q_len] batch is seq_indptr = arange(bsz + 1) * q_len over the flattened tokens.  Token i of a sequence attends tokens 0 .. i
+    of that sequence; a sequence of length 0 writes nothing, and rows of o that no sequence owns are left as allocated.
+    Softmax in fp32 with sm_scale (default 1/sqrt(128)).  The launch depends on (T, B, Hq, Hkv) only and seq_indptr is read by the kernel:
+    capture-safe, no workspace, and a captured graph replays with another split of the same T.
+    """
+    for name, t in (("q", q), ("k", k), ("v", v)):             # what the tensors are first, where they are after: the order of _check_tensor
+        if not (isinstance(t, torch.Tensor) and t.dtype is torch.bfloat16):
+            _check_tensor(t, name, torch.bfloat16)
+    Hq, sq = _token_rows(q, "q", None)
+    Hkv, sk = _token_rows(k, "k", None)
+    _, sv = _token_rows(v, "v", Hkv)
+    T = q.size(0)
+    if k.size(0) != T or v.size(0) != T:
+        raise RuntimeError("q, k and v must hold the same T tokens")
+    _head_groups(Hq, Hkv)
+    if seq_indptr is not None and not (isinstance(seq_indptr, torch.Tensor) and seq_indptr.dtype is torch.int32 and seq_indptr.dim() == 1
+                                       and seq_indptr.numel() >= 1):
+        raise RuntimeError("seq_indptr must be a one-dimensional int32 tensor of B + 1 entries (B >= 0), or None for one sequence")
+    dev = q.device
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if not (t.is_cuda and t.device == dev):
+            _check_tensor(t, name, torch.bfloat16, dev)
+    if seq_indptr is None:
+        seq_indptr = torch.arange(2, dtype=torch.int32, device=dev) * T
+    B = _tensor(seq_indptr, "seq_indptr", torch.int32, dev).numel() - 1
+    lib = _lib_with(*_DENSE)
+
+    def rows(t, H, stride):
+        """the tensor and its token stride as the C ABI takes them: in place when _token_rows' rule and the 16-byte rule allow"""
+        if stride is None or stride % 8 or t.data_ptr() % 16:
+            return t.contiguous(), H * 128
+        return t, stride or H * 128
+
+    (q, sq), (k, sk), (v, sv) = rows(q, Hq, sq), rows(k, Hkv, sk), rows(v, Hkv, sv)
+    o = torch.empty((T, Hq, 128), dtype=torch.bfloat16, device=dev)
+    _launch("dense_attention", dev, lib.mm_dense_attention, _ptr(q), _ptr(k), _ptr(v), sq, sk, sv, _ptr(seq_indptr), B, T, Hq, Hkv, 128,
+            _sm_scale(sm_scale), _ptr(o), _stream_ptr(dev))
     return o
