@@ -136,6 +136,8 @@ _TOKENS_PROTOS, TOKENS_EXPORTS, TOKENS = _read("micromix_tokens.h")
 _RANDOM_PROTOS, RANDOM_EXPORTS, RANDOM = _read("micromix_random.h")
 # ATTENTION_EXPORTS: the entry of include/micromix_attention.h, likewise; ATTENTION holds the kernel's two tile sizes and the stride limit by name
 _ATTENTION_PROTOS, ATTENTION_EXPORTS, ATTENTION = _read("micromix_attention.h")
+# ROPE_EXPORTS: the entry of include/micromix_rope.h, likewise; ROPE holds the tokens a workgroup owns by name
+_ROPE_PROTOS, ROPE_EXPORTS, ROPE = _read("micromix_rope.h")
 
 _lib = None
 
@@ -150,7 +152,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -m micromix_amd.build` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for protos in (_PROTOS, _CALIB_PROTOS, _LOGPROB_PROTOS, _LOGITS_PROTOS, _SPEC_PROTOS, _KVSTEP_PROTOS, _TOKENS_PROTOS, _RANDOM_PROTOS, _ATTENTION_PROTOS):
+    for protos in (_PROTOS, _CALIB_PROTOS, _LOGPROB_PROTOS, _LOGITS_PROTOS, _SPEC_PROTOS, _KVSTEP_PROTOS, _TOKENS_PROTOS, _RANDOM_PROTOS, _ATTENTION_PROTOS, _ROPE_PROTOS):
         _bind(lib, protos)
     _lib = lib
     return _lib

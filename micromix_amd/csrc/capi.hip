@@ -8,6 +8,7 @@
 #include "../../include/micromix_tokens.h"
 #include "../../include/micromix_random.h"
 #include "../../include/micromix_attention.h"
+#include "../../include/micromix_rope.h"
 #include "mx_common.h"
 #include "mx_kernels.h"
 #include "mx_kv_shared_host.h"
@@ -668,6 +669,41 @@ int mm_rope_kv_append(void *kv_data, void *kv_param, int kv_dtype, int max_pages
     hipError_t e = mm::launch_rope_kv_append(kv, q_bf16, k_bf16, v_bf16, qkv_token_stride, num_qo_heads, cos_bf16, sin_bf16, cs_token_stride,
                                              append_indptr, num_tokens, q_out_bf16, (hipStream_t)stream);
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_rope_kv_append");
+}
+
+// the prefill shape of the above, with or without a cache (rope_prefill.hip, include/micromix_rope.h)
+int mm_rope_prefill(void *kv_data, void *kv_param, int kv_dtype, int max_pages, int num_layers, int layer, int num_kv_heads, int page_size,
+                    int head_dim, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_len, int batch,
+                    const void *q_bf16, const void *k_bf16, const void *v_bf16, int64_t qkv_token_stride, int num_qo_heads,
+                    const void *cos_bf16, const void *sin_bf16, int64_t cs_token_stride, const int32_t *append_indptr, int num_tokens,
+                    void *q_out_bf16, void *k_out_bf16, void *v_out_bf16, mm_stream_t stream) {
+    mm::PagedKV kv;
+    const bool cache = kv_data != nullptr;
+    if (cache) {
+        if (int st = kv_geometry(kv_data, kv_param, kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size, head_dim, kv_indptr,
+                                 kv_indices, last_page_len, batch, &kv)) return st;
+    } else if (num_kv_heads < 1 || head_dim <= 0) {
+        return MM_ERR_BAD_ARG;
+    }
+    if (num_tokens < 0 || num_qo_heads < 1 || num_qo_heads % num_kv_heads) return MM_ERR_BAD_ARG;
+    // a row of a token's q (the widest of the three) and of cos / sin must fit its stride; the kernel moves 16-byte vectors
+    if (qkv_token_stride < (int64_t)num_qo_heads * 128 || cs_token_stride < 128 || ((qkv_token_stride | cs_token_stride) & 7)) return MM_ERR_BAD_ARG;
+    if (head_dim != 128) return MM_ERR_UNSUPPORTED;
+    if (num_tokens == 0) return MM_OK;
+    if (!q_bf16 || !k_bf16 || !v_bf16 || !cos_bf16 || !sin_bf16 || !q_out_bf16) return MM_ERR_BAD_ARG;
+    if (((uintptr_t)q_bf16 | (uintptr_t)k_bf16 | (uintptr_t)v_bf16 | (uintptr_t)cos_bf16 | (uintptr_t)sin_bf16 | (uintptr_t)q_out_bf16 |
+         (uintptr_t)k_out_bf16 | (uintptr_t)v_out_bf16) & 15)
+        return MM_ERR_BAD_ARG;
+    if (cache) {
+        if (batch == 0 || !kv_pointers(kv) || !append_indptr) return MM_ERR_BAD_ARG;     // batch 0: tokens that belong to no sequence
+        if (((uintptr_t)kv_data & 15) || (((uintptr_t)kv_param | (uintptr_t)kv_indptr | (uintptr_t)kv_indices | (uintptr_t)last_page_len |
+                                           (uintptr_t)append_indptr) & 3))
+            return MM_ERR_BAD_ARG;
+    }
+    hipError_t e = mm::launch_rope_prefill(cache ? &kv : nullptr, q_bf16, k_bf16, v_bf16, qkv_token_stride, num_qo_heads, num_kv_heads, cos_bf16,
+                                           sin_bf16, cs_token_stride, append_indptr, num_tokens, q_out_bf16, k_out_bf16, v_out_bf16,
+                                           (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_rope_prefill");
 }
 
 int mm_kv_copy_pages(void *kv_data, void *kv_param, int kv_dtype, int max_pages, int num_layers, int num_kv_heads, int page_size,

@@ -296,6 +296,11 @@ hipError_t launch_paged_decode_shared(const PagedKV &kv, const void *q, int Hq, 
 // RoPE + append in one launch (rope_append.hip): q | k | v share the token stride qkv_stride, cos | sin the stride cs_stride (elements)
 hipError_t launch_rope_kv_append(const PagedKV &kv, const void *q, const void *k, const void *v, int64_t qkv_stride, int Hq, const void *cos,
                                  const void *sin, int64_t cs_stride, const int *append_indptr, int T, void *q_out, hipStream_t stream);
+// the same for a prompt's worth of tokens (rope_prefill.hip, include/micromix_rope.h): kv may be null (no cache, Hkv from the argument);
+// k_out / v_out, each optional, receive what a reader of the slot gets back
+hipError_t launch_rope_prefill(const PagedKV *kv, const void *q, const void *k, const void *v, int64_t qkv_stride, int Hq, int Hkv,
+                               const void *cos, const void *sin, int64_t cs_stride, const int *append_indptr, int T, void *q_out, void *k_out,
+                               void *v_out, hipStream_t stream);
 // rows [0, rows[i]) of page src_pages[i] -> page dst_pages[i], every layer, K and V, every head (kv_copy.hip); kv.layer is 0
 hipError_t launch_kv_copy_pages(const PagedKV &kv, const int *src_pages, const int *dst_pages, const int *rows, int num_pairs,
                                 hipStream_t stream);

@@ -15,6 +15,7 @@
 
 #include "mx_kernels.h"
 #include "mx_paged_kv.h"
+#include "mx_rope.h"              // rope_one: the element rule, shared with rope_prefill.hip
 
 namespace {
 
@@ -30,12 +31,6 @@ struct RopeArgs {
     int64_t qkv_stride, cs_stride;     // elements per token
     int Hq, g;
 };
-
-// bf16(bf16(x * c) + bf16(r * s)) for one element
-__device__ inline uint32_t rope_one(uint32_t x, uint32_t r, uint32_t c, uint32_t s) {
-    const uint32_t a = f2bf_rne(bf16f(x) * bf16f(c)), b = f2bf_rne(bf16f(r) * bf16f(s));
-    return f2bf_rne(bf16f(a) + bf16f(b));
-}
 
 // the rotated elements 2 lane, 2 lane + 1 of a row; the whole wave calls it
 __device__ inline uint32_t rope_pair(uint32_t x, uint32_t cs, uint32_t sn, int lane) {

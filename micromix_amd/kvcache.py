@@ -420,14 +420,40 @@ class PagedKVCache:
             raise RuntimeError(f"append expects the {self.num_new_tokens} tokens announced by extend(), got k of shape {tuple(k.shape)}")
         mixedgemm.kv_append(self.kv_data, self.kv_param, self.kv_indptr, self.kv_indices, self.last_page_len, k, v, self.append_indptr, layer)
 
-    def append_rope(self, layer, q, k, v, cos, sin):
+    def append_rope(self, layer, q, k, v, cos, sin, dense=False):
         """RoPE + `append` in one launch: rotates q and k (bf16 [T, H, 128] or [T, H * 128], e.g. the views FusedQLinear returns) by the
         bf16 cos / sin rows of the announced tokens ([T, 128] or HF's [bsz, q_len, 128]), writes the rotated K and V of `layer` and returns
-        the rotated q, bf16 [T, Hq, 128], for `attend` / `attend_new`.  Bit-equal to HF's bf16 apply_rotary_pos_emb followed by `append`."""
+        the rotated q, bf16 [T, Hq, 128], for `attend` / `attend_new`.  Bit-equal to HF's bf16 apply_rotary_pos_emb followed by `append`.
+        dense=True: the same cache bytes and the same q from the prefill-shaped kernel (`mixedgemm.rope_kv_append_dense`), which returns
+        (q_rot, k_seen, v_seen): with them the K and V of the announced tokens as the cache now holds them, for `dense_attention`."""
         if q.dim() not in (2, 3) or q.size(0) != self.num_new_tokens:
             raise RuntimeError(f"append_rope expects the {self.num_new_tokens} tokens announced by extend(), got q of shape {tuple(q.shape)}")
-        return mixedgemm.rope_kv_append(self.kv_data, self.kv_param, self.kv_indptr, self.kv_indices, self.last_page_len, q, k, v, cos, sin,
-                                        self.append_indptr, layer)
+        op = mixedgemm.rope_kv_append_dense if dense else mixedgemm.rope_kv_append
+        return op(self.kv_data, self.kv_param, self.kv_indptr, self.kv_indices, self.last_page_len, q, k, v, cos, sin, self.append_indptr, layer)
+
+    def prefill_fresh(self, layer, q, k, v, cos, sin, sm_scale=None):
+        """`append_rope` + `attend_new` for prompts that start their sequences, on the dense kernel: after `extend`, when every sequence
+        with announced tokens consists of exactly those tokens, the attention of the new tokens over the cache is square causal
+        attention over the new tokens themselves.  Runs `append_rope(dense=True)` and `mixedgemm.dense_attention(q_rot, k_seen, v_seen,
+        seq_indptr=append_indptr)`: two launches, both capture-safe (the check below reads the host lists only); returns o, bf16
+        [T, Hq, 128].  The cache afterwards is `append_rope`'s, byte for byte.
+        Opt-in, because the bits are not `attend_new`'s: K and V are the cache's values rounded to bf16 -- exact for a bf16 and an
+        fp8 cache, one more rounding for int4 (bf16(code * scale - zero), the tensor the reference's quantize_int_group hands its
+        attention) -- and the dense kernel sums in another order than `paged_prefill`.
+        ValueError when a sequence with announced tokens already held tokens, when the tables changed since the `extend`, and on a
+        cache made with window=: use `attend_new` there."""
+        if self.window:
+            raise ValueError(f"prefill_fresh has no sliding-window form: this cache was made with window={self.window}; use "
+                             "append_rope() and attend_new()")
+        if self._announced is None or self._announced[1] is None:
+            raise ValueError("prefill_fresh: the host lists do not describe the announced tokens (the tables changed since the last "
+                             "extend, or a device step announced them); use append_rope() and attend_new()")
+        held = [b for b, (n, base) in enumerate(zip(*self._announced)) if n and base]
+        if held:
+            raise ValueError(f"prefill_fresh: sequences {held} held tokens before the announced ones, which dense attention would not "
+                             "see; use append_rope() and attend_new()")
+        q_rot, k_seen, v_seen = self.append_rope(layer, q, k, v, cos, sin, dense=True)
+        return mixedgemm.dense_attention(q_rot, k_seen, v_seen, seq_indptr=self.append_indptr, sm_scale=sm_scale)
 
     def attend(self, layer, q, max_seq_len=None, sm_scale=None, *, shared=False, max_shared_len=None):
         """Decode attention of q (bf16 [B, Hq, 128]) over `layer`.  max_seq_len defaults to the longest sequence now (host

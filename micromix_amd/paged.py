@@ -17,7 +17,7 @@ import torch
 from . import _lib
 from ._args import _check_tensor, _launch, _lead, _lib_with, _ok, _opt, _out, _ptr, _stream_ptr, _tensor
 
-__all__ = ["kv_append", "rope_kv_append", "kv_copy_pages", "kv_move_rows", "kv_step", "kv_step_state_ints", "paged_decode", "paged_decode_workspace_bytes", "paged_decode_shared",
+__all__ = ["kv_append", "rope_kv_append", "rope_kv_append_dense", "rope_qk", "kv_copy_pages", "kv_move_rows", "kv_step", "kv_step_state_ints", "paged_decode", "paged_decode_workspace_bytes", "paged_decode_shared",
            "paged_decode_shared_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes", "argmax_rows", "argmax_rows_workspace_bytes",
            "verify_greedy", "sample_rows", "sample_rows_workspace_bytes", "logprob_rows", "logprob_rows_workspace_bytes", "cross_entropy",
            "process_logits", "spec_sample_rows", "spec_sample_rows_workspace_bytes", "chain_candidates", "token_step", "ngram_draft",
@@ -34,6 +34,7 @@ _KVSTEP = ("mm_kv_step", "mm_kv_step", "device steps of the page table")
 _TOKENS = ("mm_ngram_draft", "mm_token_step / mm_ngram_draft", "the token history on the device")
 _RANDOM = ("mm_uniform_rows", "mm_uniform_rows", "seeded uniform numbers")
 _DENSE = ("mm_dense_attention", "mm_dense_attention", "dense attention over contiguous q, k, v")
+_ROPE = ("mm_rope_prefill", "mm_rope_prefill", "the prefill shape of RoPE + KV append")
 _SHARED = ("mm_paged_decode_shared", "mm_paged_decode_shared", "shared-prefix decode")
 
 
@@ -963,6 +964,37 @@ def _token_rows(t, name, heads):
     return H, (stride if ok else None)
 
 
+def _rope_operands(dev, Hkv, q, k, v, cos, sin, vec):
+    """(T, Hq, Hkv, q, k, v, their token stride, cos, sin, their row stride) as the RoPE entries take them, accesses of `vec` elements:
+    q, k, v read in place when they share one token stride that is a multiple of `vec` and at least Hq * 128 and their pointers are
+    2 * vec-byte aligned, packed into one buffer (one copy) otherwise; cos / sin likewise, made contiguous otherwise.  Hkv None: k says"""
+    for n, t in (("q", q), ("k", k), ("v", v), ("cos", cos), ("sin", sin)):
+        if not (isinstance(t, torch.Tensor) and t.dtype is torch.bfloat16 and t.is_cuda and t.get_device() == dev.index):
+            _check_tensor(t, n, torch.bfloat16, dev)      # contiguity is not asked of these five
+    Hq, sq = _token_rows(q, "q", None)
+    Hkv, sk = _token_rows(k, "k", Hkv)
+    _, sv = _token_rows(v, "v", Hkv)
+    T = q.size(0)
+    if k.size(0) != T or v.size(0) != T:
+        raise RuntimeError("q, k and v must hold the same T tokens")
+    _head_groups(Hq, Hkv)
+    strides = {sq, sk, sv} - {0}
+    if (None in strides or len(strides) > 1 or max(strides, default=Hq * 128) < Hq * 128 or max(strides, default=0) % vec
+            or any(t.data_ptr() % (2 * vec) for t in (q, k, v))):
+        packed = torch.cat([q.reshape(T, Hq * 128), k.reshape(T, Hkv * 128), v.reshape(T, Hkv * 128)], dim=1)
+        q, k, v = packed[:, : Hq * 128], packed[:, Hq * 128: (Hq + Hkv) * 128], packed[:, (Hq + Hkv) * 128:]
+        strides = {(Hq + 2 * Hkv) * 128}
+    sq = max(strides, default=Hq * 128)
+    if cos.shape != sin.shape or cos.dim() not in (2, 3) or cos.size(-1) != 128 or cos.numel() != T * 128:
+        raise RuntimeError(f"cos and sin must both be [T = {T}, 128] (or [bsz, q_len, 128] with bsz * q_len = T) bf16")
+    cos, sin = cos.reshape(T, 128), sin.reshape(T, 128)
+    sc = cos.stride(0) if T > 1 else 128
+    if not (cos.stride(1) == 1 and sin.stride(1) == 1 and (T <= 1 or sin.stride(0) == sc) and sc >= 128 and sc % vec == 0
+            and cos.data_ptr() % (2 * vec) == 0 and sin.data_ptr() % (2 * vec) == 0):
+        cos, sin, sc = cos.contiguous(), sin.contiguous(), 128
+    return T, Hq, Hkv, q, k, v, sq, cos, sin, sc
+
+
 def rope_kv_append(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, q, k, v, cos, sin, append_indptr, layer_idx):
     """RoPE on q and k, then `kv_append` of (rotated k, v), in one launch; returns the rotated q, bf16 [T, Hq, 128] contiguous.
 
@@ -979,33 +1011,56 @@ def rope_kv_append(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, q, k
     _tensor(append_indptr, "append_indptr", torch.int32, dev)
     if append_indptr.numel() != B + 1:
         raise RuntimeError("append_indptr must have B + 1 entries")
-    for n, t in (("q", q), ("k", k), ("v", v), ("cos", cos), ("sin", sin)):
-        if not (isinstance(t, torch.Tensor) and t.dtype is torch.bfloat16 and t.is_cuda and t.get_device() == dev.index):
-            _check_tensor(t, n, torch.bfloat16, dev)      # contiguity is not asked of these five
-    Hq, sq = _token_rows(q, "q", None)
-    _, sk = _token_rows(k, "k", Hkv)
-    _, sv = _token_rows(v, "v", Hkv)
-    T = q.size(0)
-    if k.size(0) != T or v.size(0) != T:
-        raise RuntimeError("q, k and v must hold the same T tokens")
-    _head_groups(Hq, Hkv)
-    strides = {sq, sk, sv} - {0}
-    if None in strides or len(strides) > 1 or max(strides, default=Hq * 128) < Hq * 128:
-        packed = torch.cat([q.reshape(T, Hq * 128), k.reshape(T, Hkv * 128), v.reshape(T, Hkv * 128)], dim=1)
-        q, k, v = packed[:, : Hq * 128], packed[:, Hq * 128: (Hq + Hkv) * 128], packed[:, (Hq + Hkv) * 128:]
-        strides = {(Hq + 2 * Hkv) * 128}
-    sq = max(strides, default=Hq * 128)
-    if cos.shape != sin.shape or cos.dim() not in (2, 3) or cos.size(-1) != 128 or cos.numel() != T * 128:
-        raise RuntimeError(f"cos and sin must both be [T = {T}, 128] (or [bsz, q_len, 128] with bsz * q_len = T) bf16")
-    cos, sin = cos.reshape(T, 128), sin.reshape(T, 128)
-    sc = cos.stride(0) if T > 1 else 128
-    if not (cos.stride(1) == 1 and sin.stride(1) == 1 and (T <= 1 or sin.stride(0) == sc) and sc >= 128 and sc % 2 == 0
-            and cos.data_ptr() % 4 == 0 and sin.data_ptr() % 4 == 0):
-        cos, sin, sc = cos.contiguous(), sin.contiguous(), 128
+    T, Hq, _, q, k, v, sq, cos, sin, sc = _rope_operands(dev, Hkv, q, k, v, cos, sin, 2)
     q_rot = torch.empty((T, Hq, 128), dtype=torch.bfloat16, device=dev)
     _launch("rope_kv_append", dev, lib.mm_rope_kv_append, *kv_args, _ptr(q), _ptr(k), _ptr(v), sq, Hq, _ptr(cos), _ptr(sin), sc,
             _ptr(append_indptr), T, _ptr(q_rot), _stream_ptr(dev))
     return q_rot
+
+
+def rope_kv_append_dense(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, q, k, v, cos, sin, append_indptr, layer_idx):
+    """`rope_kv_append` in the shape of a prompt (include/micromix_rope.h, mm_rope_prefill: several tokens per workgroup, 16-byte accesses),
+    returning what `dense_attention` over a fresh prompt needs: (q_rot [T, Hq, 128], k_seen [T, Hkv, 128], v_seen [T, Hkv, 128]), bf16.
+
+    Arguments as `rope_kv_append`; the cache receives the same bytes and q_rot has the same bits.  k_seen / v_seen hold what a reader of
+    each token's slot gets back: for a bf16 cache rope(k) and v -- v_seen is then the `v` argument itself, nothing is copied --, for
+    fp8 code * 2^e, for int4 bf16(code * scale - zero), computed in fp32: the bf16 tensor the reference's quantize_int_group returns.
+    Inputs are read in place when their strides are multiples of 8 elements and their pointers 16-byte aligned, and copied once
+    otherwise.  Runs on the current stream, capture-safe."""
+    lib = _lib_with(*_ROPE)
+    dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx)
+    _tensor(append_indptr, "append_indptr", torch.int32, dev)
+    if append_indptr.numel() != B + 1:
+        raise RuntimeError("append_indptr must have B + 1 entries")
+    v_given = v
+    T, Hq, _, q, k, v, sq, cos, sin, sc = _rope_operands(dev, Hkv, q, k, v, cos, sin, 8)
+    q_rot = torch.empty((T, Hq, 128), dtype=torch.bfloat16, device=dev)
+    k_seen = torch.empty((T, Hkv, 128), dtype=torch.bfloat16, device=dev)
+    v_seen = torch.empty((T, Hkv, 128), dtype=torch.bfloat16, device=dev) if kv_param is not None else None
+    _launch("rope_kv_append_dense", dev, lib.mm_rope_prefill, *kv_args, _ptr(q), _ptr(k), _ptr(v), sq, Hq, _ptr(cos), _ptr(sin), sc,
+            _ptr(append_indptr), T, _ptr(q_rot), _ptr(k_seen), _opt(v_seen), _stream_ptr(dev))
+    return q_rot, k_seen, v_seen if v_seen is not None else v_given
+
+
+def rope_qk(q, k, cos, sin):
+    """RoPE on q and k without a cache, in one launch: (q_rot [T, Hq, 128], k_rot [T, Hkv, 128]), bf16 contiguous -- HF's bf16
+    apply_rotary_pos_emb, q * cos + rotate_half(q) * sin with every op rounded to bf16, bit for bit (include/micromix_rope.h,
+    mm_rope_prefill without a cache), ready for `dense_attention(q_rot, k_rot, v)`.
+
+    q, k: bf16 [T, H, 128] or [T, H * 128], Hq a multiple of Hkv.  Views of one packed projection (what FusedQLinear returns) are read in
+    place when their common token stride is a multiple of 8 elements and their pointers are 16-byte aligned; otherwise they are copied
+    once.  cos, sin: bf16 [T, 128] or HF's [1, T, 128] / [bsz, q_len, 128] (flattened); a row stride is honoured.  Runs on the current
+    stream, capture-safe."""
+    lib = _lib_with(*_ROPE)
+    if not (isinstance(q, torch.Tensor) and q.dtype is torch.bfloat16 and q.is_cuda):
+        _check_tensor(q, "q", torch.bfloat16)
+    dev = q.device
+    T, Hq, Hkv, q, k, _, sq, cos, sin, sc = _rope_operands(dev, None, q, k, k, cos, sin, 8)
+    q_rot = torch.empty((T, Hq, 128), dtype=torch.bfloat16, device=dev)
+    k_rot = torch.empty((T, Hkv, 128), dtype=torch.bfloat16, device=dev)
+    _launch("rope_qk", dev, lib.mm_rope_prefill, None, None, 0, 0, 0, 0, Hkv, 0, 128, None, None, None, 0, _ptr(q), _ptr(k), _ptr(k), sq, Hq,
+            _ptr(cos), _ptr(sin), sc, None, T, _ptr(q_rot), _ptr(k_rot), None, _stream_ptr(dev))
+    return q_rot, k_rot
 
 
 def _window(window):
