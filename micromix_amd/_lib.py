@@ -138,6 +138,8 @@ _RANDOM_PROTOS, RANDOM_EXPORTS, RANDOM = _read("micromix_random.h")
 _ATTENTION_PROTOS, ATTENTION_EXPORTS, ATTENTION = _read("micromix_attention.h")
 # ROPE_EXPORTS: the entry of include/micromix_rope.h, likewise; ROPE holds the tokens a workgroup owns by name
 _ROPE_PROTOS, ROPE_EXPORTS, ROPE = _read("micromix_rope.h")
+# ATTENTION_WINDOW_EXPORTS: the entry of include/micromix_attention_window.h, likewise; the header defines no constant
+_ATTENTION_WINDOW_PROTOS, ATTENTION_WINDOW_EXPORTS, _ = _read("micromix_attention_window.h")
 
 _lib = None
 
@@ -152,7 +154,8 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -m micromix_amd.build` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for protos in (_PROTOS, _CALIB_PROTOS, _LOGPROB_PROTOS, _LOGITS_PROTOS, _SPEC_PROTOS, _KVSTEP_PROTOS, _TOKENS_PROTOS, _RANDOM_PROTOS, _ATTENTION_PROTOS, _ROPE_PROTOS):
+    for protos in (_PROTOS, _CALIB_PROTOS, _LOGPROB_PROTOS, _LOGITS_PROTOS, _SPEC_PROTOS, _KVSTEP_PROTOS, _TOKENS_PROTOS, _RANDOM_PROTOS, _ATTENTION_PROTOS, _ROPE_PROTOS,
+                   _ATTENTION_WINDOW_PROTOS):
         _bind(lib, protos)
     _lib = lib
     return _lib

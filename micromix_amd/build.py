@@ -32,7 +32,7 @@ HEADERS = ["mx_common.h", "mx_kernels.h", "mx_acc_regs.h", "mx_gemm_tile.inc", "
            os.path.join("..", "..", "include", "micromix_logits.h"), os.path.join("..", "..", "include", "micromix_spec.h"),
            os.path.join("..", "..", "include", "micromix_kvstep.h"), os.path.join("..", "..", "include", "micromix_tokens.h"),
            os.path.join("..", "..", "include", "micromix_random.h"), os.path.join("..", "..", "include", "micromix_attention.h"),
-           os.path.join("..", "..", "include", "micromix_rope.h")]
+           os.path.join("..", "..", "include", "micromix_rope.h"), os.path.join("..", "..", "include", "micromix_attention_window.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 # flags of single sources, after FLAGS.  dense_attention.hip: its fp32 softmax and rescaling stay one operation per lane and instruction;
 # the compiler does not pair them into packed fp32 instructions (the host pass does not know the feature and says that it ignores it).

@@ -8,6 +8,7 @@
 #include "../../include/micromix_tokens.h"
 #include "../../include/micromix_random.h"
 #include "../../include/micromix_attention.h"
+#include "../../include/micromix_attention_window.h"
 #include "../../include/micromix_rope.h"
 #include "mx_common.h"
 #include "mx_kernels.h"
@@ -900,11 +901,12 @@ int mm_uniform_rows(const int64_t *seed, const int32_t *sub, int batch, const in
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_uniform_rows");
 }
 
-// ---- dense causal attention over contiguous q, k, v (dense_attention.hip, include/micromix_attention.h)
-int mm_dense_attention(const void *q, const void *k, const void *v, long long q_stride, long long k_stride, long long v_stride,
-                       const int32_t *seq_indptr, int batch, int total_tokens, int num_q_heads, int num_kv_heads, int head_dim, float sm_scale,
-                       void *o, mm_stream_t stream) {
-    if (total_tokens < 0 || batch < 0 || num_q_heads < 1 || num_kv_heads < 1) return MM_ERR_BAD_ARG;
+// ---- dense causal attention over contiguous q, k, v (dense_attention.hip, include/micromix_attention.h), and its sliding-window form
+// (include/micromix_attention_window.h): window 0 is the former, which has none
+static int dense_attention(const void *q, const void *k, const void *v, long long q_stride, long long k_stride, long long v_stride,
+                           const int32_t *seq_indptr, int batch, int total_tokens, int num_q_heads, int num_kv_heads, int head_dim,
+                           float sm_scale, void *o, mm_stream_t stream, bool windowed, int window, const char *what) {
+    if (total_tokens < 0 || batch < 0 || num_q_heads < 1 || num_kv_heads < 1 || (windowed && window < 1)) return MM_ERR_BAD_ARG;
     const bool work = total_tokens > 0 && batch > 0;
     if (work) {
         if (!q || !k || !v || !o || !seq_indptr) return MM_ERR_BAD_ARG;
@@ -922,8 +924,23 @@ int mm_dense_attention(const void *q, const void *k, const void *v, long long q_
     a.sq = q_stride, a.sk = k_stride, a.sv = v_stride;
     a.indptr = seq_indptr, a.B = batch, a.T = total_tokens, a.Hq = num_q_heads, a.Hkv = num_kv_heads;
     a.o = (uint16_t *)o;
-    hipError_t e = mm::launch_dense_attention(a, sm_scale, (hipStream_t)stream);
-    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_dense_attention");
+    hipError_t e = windowed ? mm::launch_dense_attention_window(a, sm_scale, window, (hipStream_t)stream)
+                            : mm::launch_dense_attention(a, sm_scale, (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, what);
+}
+
+int mm_dense_attention(const void *q, const void *k, const void *v, long long q_stride, long long k_stride, long long v_stride,
+                       const int32_t *seq_indptr, int batch, int total_tokens, int num_q_heads, int num_kv_heads, int head_dim, float sm_scale,
+                       void *o, mm_stream_t stream) {
+    return dense_attention(q, k, v, q_stride, k_stride, v_stride, seq_indptr, batch, total_tokens, num_q_heads, num_kv_heads, head_dim,
+                           sm_scale, o, stream, false, 0, "mm_dense_attention");
+}
+
+int mm_dense_attention_window(const void *q, const void *k, const void *v, long long q_stride, long long k_stride, long long v_stride,
+                              const int32_t *seq_indptr, int batch, int total_tokens, int num_q_heads, int num_kv_heads, int head_dim,
+                              float sm_scale, void *o, mm_stream_t stream, int window) {
+    return dense_attention(q, k, v, q_stride, k_stride, v_stride, seq_indptr, batch, total_tokens, num_q_heads, num_kv_heads, head_dim,
+                           sm_scale, o, stream, true, window, "mm_dense_attention_window");
 }
 
 // ---- calibration statistics (calib_stats.hip, include/micromix_calib.h)

@@ -21,6 +21,8 @@
 // to each other and all but the first find them in L2.  The last tiles (the longest walks) come first.
 // Sequence b owns tiles [seq_indptr[b] / 128 + b, seq_indptr[b + 1] / 128 + b + 1), which hold its ceil(n_b / 128) tiles, so the grid
 // (T / 128 + B) * Hq needs no host copy of seq_indptr; the surplus workgroups exit.
+// The sliding-window form (mm_dense_attention_window, include/micromix_attention_window.h) is the kernel's second instantiation: the same
+// tiles, staging and pipeline over a walk that starts at the window's lower edge, stated at the template below.
 #include "../../include/micromix_attention.h"
 #include "mx_buffer_ops.h"
 #include "mx_kernels.h"
@@ -29,10 +31,12 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <type_traits>
 
 namespace {
 
 using mm::DenseAttention;
+using mm::DenseAttentionWindow;
 using mm::kv::HD;
 using mm::kv::pack_bf;
 using mm::kv::v2u;
@@ -72,7 +76,12 @@ __device__ __forceinline__ v2u read_tr(const uint8_t *p) {
     return r;
 }
 
-__global__ __launch_bounds__(NT) void dense_attention_kernel(const DenseAttention a) {
+// WIN: the sliding-window form (mm_dense_attention_window, include/micromix_attention_window.h): row i attends tokens i - W + 1 .. i, so
+// the walk starts at the tile that holds the lower edge of the query tile's first row, a wave also skips the tiles wholly below the
+// window of its first row, and a second compare runs on the tiles that cross the lower edge of some row of the wave.  With WIN false
+// t0 and W are constants and every added line folds away: the un-windowed kernel's instructions are what they were without them.
+template <bool WIN>
+__global__ __launch_bounds__(NT) void dense_attention_kernel(const std::conditional_t<WIN, DenseAttentionWindow, DenseAttention> a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];   // [2][K tile | V tile], written by the LDS-DMA only
 
     const int x = blockIdx.x, h = x % a.Hq, kvh = h / a.g;
@@ -86,6 +95,8 @@ __global__ __launch_bounds__(NT) void dense_attention_kernel(const DenseAttentio
     const int wr0 = i0 + 32 * wave;                       // this wave's first row; its last valid one
     const bool wactive = wr0 < n;
     const int wmax = min(wr0 + 31, n - 1);
+    int W = 0, t0 = 0;                                    // the window (1 <= W < T, the launch sees to it) and the first kv tile of the walk
+    if constexpr (WIN) W = a.W, t0 = max(i0 - W + 1, 0) / BK;
 
     // ---- q as the MFMA B operand: row block rb, lane (c, kq) holds row wr0 + 16 rb + c, dims 32 kq + 8 s + e in step s
     v8bf qb[2][4];
@@ -108,7 +119,7 @@ __global__ __launch_bounds__(NT) void dense_attention_kernel(const DenseAttentio
         const int kt = t * BK, nrows = min(kend - kt, BK);           // >= 1
         const rsrc_t rk = mm::make_rsrc(kseq + (int64_t)kt * skb, (unsigned)((nrows - 1) * skb + ROWB));
         const rsrc_t rv = mm::make_rsrc(vseq + (int64_t)kt * svb, (unsigned)((nrows - 1) * svb + ROWB));
-        const unsigned base = lds0 + (t & 1) * BUFB + wave * 4096;
+        const unsigned base = lds0 + ((t - t0) & 1) * BUFB + wave * 4096;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int rr = 16 * wave + 4 * i + kq, rc = min(rr, nrows - 1);
@@ -133,14 +144,15 @@ __global__ __launch_bounds__(NT) void dense_attention_kernel(const DenseAttentio
 #pragma unroll
         for (int dt = 0; dt < 8; ++dt) o[rb][dt] = v4f{0.0f, 0.0f, 0.0f, 0.0f};
 
-    issue(0);
-    for (int t = 0; t < nt; ++t) {
+    if constexpr (WIN) issue(t0); else issue(0);           // the literal: with issue(t0) the un-windowed prologue is scheduled differently
+    for (int t = t0; t < nt; ++t) {
         mm::wait_vmcnt<0>();                               // this wave's share of tile t is in LDS
         __syncthreads();                                   // ... everybody's is, and nobody still reads tile t - 1
         if (t + 1 < nt) issue(t + 1);                      // in flight during this tile's math
         const int kt = t * BK;
         if (!wactive || kt > wmax) continue;               // every row of this wave is masked on this tile
-        const uint8_t *sk = smem + (t & 1) * BUFB, *sv = sk + TILEB;
+        if (WIN && kt + BK - 1 < wr0 - W + 1) continue;    // ... here too: the tile ends below the window of the wave's first row
+        const uint8_t *sk = smem + ((t - t0) & 1) * BUFB, *sv = sk + TILEB;
 
         // ---- scores S^T: lane (c, kq) holds, for its row of each block, tokens kt + 16 blk + 4 kq + r
         float sc[2][4][4];
@@ -167,6 +179,16 @@ __global__ __launch_bounds__(NT) void dense_attention_kernel(const DenseAttentio
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
                         if (kt + 16 * blk + 4 * kq + r > irow[rb]) sc[rb][blk][r] = -INFINITY;
+        }
+        if (WIN && kt < wmax - W + 1) {                    // the tile crosses the lower edge of some row of this wave: token j of it is
+            const int kw = kt - wr0 + W;                   // masked for row wr0 + x when j + W <= wr0 + x; kw is uniform and small
+#pragma unroll
+            for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+                for (int blk = 0; blk < 4; ++blk)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (kw + 16 * blk + 4 * kq + r <= 16 * rb + c) sc[rb][blk][r] = -INFINITY;
         }
         // ---- online softmax (log2 domain), P as the B operand of p.V: k step ks covers tokens 32 ks + {4 kq + e, 16 + 4 kq + e}
         v8bf pb[2][2];
@@ -245,7 +267,21 @@ hipError_t launch_dense_attention(DenseAttention a, float sm_scale, hipStream_t 
     a.g = a.Hq / a.Hkv;
     a.tiles = a.T / BQ + a.B;
     a.scale_log2 = kv_scale_log2(sm_scale);
-    dense_attention_kernel<<<(unsigned)((long long)a.tiles * a.Hq), NT, LDS_BYTES, stream>>>(a);
+    dense_attention_kernel<false><<<(unsigned)((long long)a.tiles * a.Hq), NT, LDS_BYTES, stream>>>(a);
+    return hipGetLastError();
+}
+
+// window >= 1.  A window that no row of T tokens can feel is the un-windowed kernel, which gives the same bits by construction; below
+// that W < T, so no i - W + 1 of the kernel overflows.  The grid is the same, from host values alone.
+hipError_t launch_dense_attention_window(DenseAttention a, float sm_scale, int window, hipStream_t stream) {
+    if (window >= a.T) return launch_dense_attention(a, sm_scale, stream);
+    DenseAttentionWindow w{};
+    static_cast<DenseAttention &>(w) = a;
+    w.g = a.Hq / a.Hkv;
+    w.tiles = a.T / BQ + a.B;
+    w.scale_log2 = kv_scale_log2(sm_scale);
+    w.W = window;
+    dense_attention_kernel<true><<<(unsigned)((long long)w.tiles * w.Hq), NT, LDS_BYTES, stream>>>(w);
     return hipGetLastError();
 }
 

@@ -402,6 +402,12 @@ struct DenseAttention {
     float scale_log2;
 };
 hipError_t launch_dense_attention(DenseAttention a, float sm_scale, hipStream_t stream);
+// its sliding-window form (include/micromix_attention_window.h): what the window kernel takes, W filled in by the launch (1 <= W < T;
+// a window of T or more launches the un-windowed kernel)
+struct DenseAttentionWindow : DenseAttention {
+    int W;
+};
+hipError_t launch_dense_attention_window(DenseAttention a, float sm_scale, int window, hipStream_t stream);
 // token log-probabilities over bf16 rows (logprob.hip, include/micromix_logprob.h): target and temperature device arrays of `rows`
 // entries or null, every output null when not wanted, top_n 0 .. 32; ws: logprob_workspace_bytes, uninitialised
 size_t logprob_workspace_bytes(int rows, int vocab, int top_n);

@@ -431,7 +431,7 @@ class PagedKVCache:
         op = mixedgemm.rope_kv_append_dense if dense else mixedgemm.rope_kv_append
         return op(self.kv_data, self.kv_param, self.kv_indptr, self.kv_indices, self.last_page_len, q, k, v, cos, sin, self.append_indptr, layer)
 
-    def prefill_fresh(self, layer, q, k, v, cos, sin, sm_scale=None):
+    def prefill_fresh(self, layer, q, k, v, cos, sin, sm_scale=None, *, windowed=False):
         """`append_rope` + `attend_new` for prompts that start their sequences, on the dense kernel: after `extend`, when every sequence
         with announced tokens consists of exactly those tokens, the attention of the new tokens over the cache is square causal
         attention over the new tokens themselves.  Runs `append_rope(dense=True)` and `mixedgemm.dense_attention(q_rot, k_seen, v_seen,
@@ -441,8 +441,13 @@ class PagedKVCache:
         fp8 cache, one more rounding for int4 (bf16(code * scale - zero), the tensor the reference's quantize_int_group hands its
         attention) -- and the dense kernel sums in another order than `paged_prefill`.
         ValueError when a sequence with announced tokens already held tokens, when the tables changed since the `extend`, and on a
-        cache made with window=: use `attend_new` there."""
-        if self.window:
+        cache made with window=: use `attend_new` there, or pass windowed=True.
+        windowed=True: on a cache made with window=W the same checks and the same append, then `mixedgemm.dense_attention_window(q_rot,
+        k_seen, v_seen, W, seq_indptr=append_indptr)`: every new token attends the last W tokens, its own included, as `attend_new`
+        has it there.  It rests on this: `extend` releases no page of a sequence whose announced tokens start at position 0 -- the
+        first of them has a window that begins at 0 -- so every slot the append writes exists; the pages below the window of the
+        last token go at the next `extend`, as they do after `attend_new`.  On a cache without a window it is the plain route."""
+        if self.window and not windowed:
             raise ValueError(f"prefill_fresh has no sliding-window form: this cache was made with window={self.window}; use "
                              "append_rope() and attend_new()")
         if self._announced is None or self._announced[1] is None:
@@ -453,6 +458,8 @@ class PagedKVCache:
             raise ValueError(f"prefill_fresh: sequences {held} held tokens before the announced ones, which dense attention would not "
                              "see; use append_rope() and attend_new()")
         q_rot, k_seen, v_seen = self.append_rope(layer, q, k, v, cos, sin, dense=True)
+        if self.window:
+            return mixedgemm.dense_attention_window(q_rot, k_seen, v_seen, self.window, seq_indptr=self.append_indptr, sm_scale=sm_scale)
         return mixedgemm.dense_attention(q_rot, k_seen, v_seen, seq_indptr=self.append_indptr, sm_scale=sm_scale)
 
     def attend(self, layer, q, max_seq_len=None, sm_scale=None, *, shared=False, max_shared_len=None):

@@ -21,7 +21,7 @@ __all__ = ["kv_append", "rope_kv_append", "rope_kv_append_dense", "rope_qk", "kv
            "paged_decode_shared_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes", "argmax_rows", "argmax_rows_workspace_bytes",
            "verify_greedy", "sample_rows", "sample_rows_workspace_bytes", "logprob_rows", "logprob_rows_workspace_bytes", "cross_entropy",
            "process_logits", "spec_sample_rows", "spec_sample_rows_workspace_bytes", "chain_candidates", "token_step", "ngram_draft",
-           "ngram_draft_workspace_bytes", "uniform_rows", "dense_attention"]
+           "ngram_draft_workspace_bytes", "uniform_rows", "dense_attention", "dense_attention_window"]
 
 # entries a library built before them lacks: (the symbol looked for, the names and the feature of the rebuild message)
 _TREE = ("mm_paged_prefill_tree", "mm_paged_prefill_tree / mm_kv_move_rows", "tree-masked attention")
@@ -34,6 +34,7 @@ _KVSTEP = ("mm_kv_step", "mm_kv_step", "device steps of the page table")
 _TOKENS = ("mm_ngram_draft", "mm_token_step / mm_ngram_draft", "the token history on the device")
 _RANDOM = ("mm_uniform_rows", "mm_uniform_rows", "seeded uniform numbers")
 _DENSE = ("mm_dense_attention", "mm_dense_attention", "dense attention over contiguous q, k, v")
+_DENSE_WINDOW = ("mm_dense_attention_window", "mm_dense_attention_window", "sliding-window dense attention over contiguous q, k, v")
 _ROPE = ("mm_rope_prefill", "mm_rope_prefill", "the prefill shape of RoPE + KV append")
 _SHARED = ("mm_paged_decode_shared", "mm_paged_decode_shared", "shared-prefix decode")
 
@@ -1212,20 +1213,9 @@ def paged_prefill(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, qo
     return o
 
 
-def dense_attention(q, k, v, seq_indptr=None, sm_scale=None):
-    """Causal GQA attention over contiguous bf16 q, k, v, without a cache: what scaled_dot_product_attention(q, repeat_kv(k),
-    repeat_kv(v), is_causal=True) computes for every sequence of a flattened batch; returns o, bf16 [T, Hq, 128].
-
-    q, k, v: bf16 [T, H, 128] or [T, H * 128], the same T tokens, Hq a multiple of Hkv; query head h reads kv head h // (Hq // Hkv).
-    A tensor whose rows lie contiguous within a token is read in place whatever its token stride (a multiple of 8 elements, the pointer
-    16-byte aligned): the three views of one packed [T, (Hq + 2 Hkv) * 128] projection (what FusedQLinear returns) are not copied
-    apart, and K / V are not repeated.  Anything else is copied with .contiguous() first.
-    seq_indptr: int32 [B + 1] device tensor, sequence b owns tokens seq_indptr[b] .. seq_indptr[b + 1]; None: one sequence of T tokens.
-    A [bsz, q_len] batch is seq_indptr = arange(bsz + 1) * q_len over the flattened tokens.  Token i of a sequence attends tokens 0 .. i
-    of that sequence; a sequence of length 0 writes nothing, and rows of o that no sequence owns are left as allocated.
-    Softmax in fp32 with sm_scale (default 1/sqrt(128)).  The launch depends on (T, B, Hq, Hkv) only and seq_indptr is read by the kernel:
-    capture-safe, no workspace, and a captured graph replays with another split of the same T.
-    """
+def _dense_attention(entry, q, k, v, seq_indptr, sm_scale, *window):
+    """the argument handling and the launch that `dense_attention` and `dense_attention_window` share: `entry` is the _lib_with triple of
+    the C entry, `window` what it takes after the stream"""
     for name, t in (("q", q), ("k", k), ("v", v)):             # what the tensors are first, where they are after: the order of _check_tensor
         if not (isinstance(t, torch.Tensor) and t.dtype is torch.bfloat16):
             _check_tensor(t, name, torch.bfloat16)
@@ -1246,7 +1236,7 @@ def dense_attention(q, k, v, seq_indptr=None, sm_scale=None):
     if seq_indptr is None:
         seq_indptr = torch.arange(2, dtype=torch.int32, device=dev) * T
     B = _tensor(seq_indptr, "seq_indptr", torch.int32, dev).numel() - 1
-    lib = _lib_with(*_DENSE)
+    lib = _lib_with(*entry)
 
     def rows(t, H, stride):
         """the tensor and its token stride as the C ABI takes them: in place when _token_rows' rule and the 16-byte rule allow"""
@@ -1256,6 +1246,34 @@ def dense_attention(q, k, v, seq_indptr=None, sm_scale=None):
 
     (q, sq), (k, sk), (v, sv) = rows(q, Hq, sq), rows(k, Hkv, sk), rows(v, Hkv, sv)
     o = torch.empty((T, Hq, 128), dtype=torch.bfloat16, device=dev)
-    _launch("dense_attention", dev, lib.mm_dense_attention, _ptr(q), _ptr(k), _ptr(v), sq, sk, sv, _ptr(seq_indptr), B, T, Hq, Hkv, 128,
-            _sm_scale(sm_scale), _ptr(o), _stream_ptr(dev))
+    _launch(entry[0][3:], dev, getattr(lib, entry[0]), _ptr(q), _ptr(k), _ptr(v), sq, sk, sv, _ptr(seq_indptr), B, T, Hq, Hkv, 128,
+            _sm_scale(sm_scale), _ptr(o), _stream_ptr(dev), *window)
     return o
+
+
+def dense_attention(q, k, v, seq_indptr=None, sm_scale=None):
+    """Causal GQA attention over contiguous bf16 q, k, v, without a cache: what scaled_dot_product_attention(q, repeat_kv(k),
+    repeat_kv(v), is_causal=True) computes for every sequence of a flattened batch; returns o, bf16 [T, Hq, 128].
+
+    q, k, v: bf16 [T, H, 128] or [T, H * 128], the same T tokens, Hq a multiple of Hkv; query head h reads kv head h // (Hq // Hkv).
+    A tensor whose rows lie contiguous within a token is read in place whatever its token stride (a multiple of 8 elements, the pointer
+    16-byte aligned): the three views of one packed [T, (Hq + 2 Hkv) * 128] projection (what FusedQLinear returns) are not copied
+    apart, and K / V are not repeated.  Anything else is copied with .contiguous() first.
+    seq_indptr: int32 [B + 1] device tensor, sequence b owns tokens seq_indptr[b] .. seq_indptr[b + 1]; None: one sequence of T tokens.
+    A [bsz, q_len] batch is seq_indptr = arange(bsz + 1) * q_len over the flattened tokens.  Token i of a sequence attends tokens 0 .. i
+    of that sequence; a sequence of length 0 writes nothing, and rows of o that no sequence owns are left as allocated.
+    Softmax in fp32 with sm_scale (default 1/sqrt(128)).  The launch depends on (T, B, Hq, Hkv) only and seq_indptr is read by the kernel:
+    capture-safe, no workspace, and a captured graph replays with another split of the same T.
+    """
+    return _dense_attention(_DENSE, q, k, v, seq_indptr, sm_scale)
+
+
+def dense_attention_window(q, k, v, window, seq_indptr=None, sm_scale=None):
+    """`dense_attention` with HF's sliding_window (include/micromix_attention_window.h, mm_dense_attention_window): token i of a sequence
+    attends tokens max(0, i - window + 1) .. i of that sequence, what SDPA computes under a causal band mask.  q, k, v, seq_indptr,
+    sm_scale, the in-place reading of views, the errors and the capture rules are `dense_attention`'s; window is an int >= 1.
+    A query tile past the window walks about (window + 128) / 64 kv tiles however long its sequence is.  window >= T runs
+    `dense_attention`'s kernel, and inside a windowed launch a sequence no longer than window gets `dense_attention`'s bits."""
+    if isinstance(window, bool) or not isinstance(window, int) or window < 1:
+        raise ValueError(f"window must be an int >= 1, got {window!r}")
+    return _dense_attention(_DENSE_WINDOW, q, k, v, seq_indptr, sm_scale, min(window, 2 ** 31 - 1))
