@@ -140,6 +140,11 @@ _ATTENTION_PROTOS, ATTENTION_EXPORTS, ATTENTION = _read("micromix_attention.h")
 _ROPE_PROTOS, ROPE_EXPORTS, ROPE = _read("micromix_rope.h")
 # ATTENTION_WINDOW_EXPORTS: the entry of include/micromix_attention_window.h, likewise; the header defines no constant
 _ATTENTION_WINDOW_PROTOS, ATTENTION_WINDOW_EXPORTS, _ = _read("micromix_attention_window.h")
+# ATTENTION_PREFIX_EXPORTS: the entries of include/micromix_attention_prefix.h, likewise; ATTENTION_PREFIX holds its header's integers by
+# name (micromix_attention.h's, which it includes by reference only, are ATTENTION's)
+_ATTENTION_PREFIX_PROTOS, ATTENTION_PREFIX_EXPORTS, ATTENTION_PREFIX = _read("micromix_attention_prefix.h")
+# KVGATHER_EXPORTS: the entry of include/micromix_kvgather.h, likewise; KVGATHER holds the output rows a workgroup owns by name
+_KVGATHER_PROTOS, KVGATHER_EXPORTS, KVGATHER = _read("micromix_kvgather.h")
 
 _lib = None
 
@@ -155,7 +160,7 @@ def load():
             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
     for protos in (_PROTOS, _CALIB_PROTOS, _LOGPROB_PROTOS, _LOGITS_PROTOS, _SPEC_PROTOS, _KVSTEP_PROTOS, _TOKENS_PROTOS, _RANDOM_PROTOS, _ATTENTION_PROTOS, _ROPE_PROTOS,
-                   _ATTENTION_WINDOW_PROTOS):
+                   _ATTENTION_WINDOW_PROTOS, _ATTENTION_PREFIX_PROTOS, _KVGATHER_PROTOS):
         _bind(lib, protos)
     _lib = lib
     return _lib

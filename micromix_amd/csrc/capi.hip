@@ -9,6 +9,8 @@
 #include "../../include/micromix_random.h"
 #include "../../include/micromix_attention.h"
 #include "../../include/micromix_attention_window.h"
+#include "../../include/micromix_attention_prefix.h"
+#include "../../include/micromix_kvgather.h"
 #include "../../include/micromix_rope.h"
 #include "mx_common.h"
 #include "mx_kernels.h"
@@ -901,16 +903,21 @@ int mm_uniform_rows(const int64_t *seed, const int32_t *sub, int batch, const in
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_uniform_rows");
 }
 
-// ---- dense causal attention over contiguous q, k, v (dense_attention.hip, include/micromix_attention.h), and its sliding-window form
-// (include/micromix_attention_window.h): window 0 is the former, which has none
+// ---- dense causal attention over contiguous q, k, v (dense_attention.hip, include/micromix_attention.h), its sliding-window form
+// (include/micromix_attention_window.h): window 0 is the former, which has none; and its rectangular split-KV form
+// (include/micromix_attention_prefix.h): `prefix` holds what that one takes besides, total_tokens being its query tokens
+struct DensePrefix { const int32_t *kv_indptr; int total_kv, max_kv_len; void *ws; size_t ws_bytes; };
 static int dense_attention(const void *q, const void *k, const void *v, long long q_stride, long long k_stride, long long v_stride,
                            const int32_t *seq_indptr, int batch, int total_tokens, int num_q_heads, int num_kv_heads, int head_dim,
-                           float sm_scale, void *o, mm_stream_t stream, bool windowed, int window, const char *what) {
+                           float sm_scale, void *o, mm_stream_t stream, bool windowed, int window, const char *what,
+                           const DensePrefix *prefix = nullptr) {
     if (total_tokens < 0 || batch < 0 || num_q_heads < 1 || num_kv_heads < 1 || (windowed && window < 1)) return MM_ERR_BAD_ARG;
+    if (prefix && (prefix->total_kv < 0 || prefix->max_kv_len < 0)) return MM_ERR_BAD_ARG;
     const bool work = total_tokens > 0 && batch > 0;
     if (work) {
-        if (!q || !k || !v || !o || !seq_indptr) return MM_ERR_BAD_ARG;
+        if (!q || !k || !v || !o || !seq_indptr || (prefix && !prefix->kv_indptr)) return MM_ERR_BAD_ARG;
         if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) & 15) || ((uintptr_t)seq_indptr & 3)) return MM_ERR_BAD_ARG;
+        if (prefix && ((uintptr_t)prefix->kv_indptr & 3)) return MM_ERR_BAD_ARG;
         if (((q_stride | k_stride | v_stride) & 7) || q_stride < (long long)num_q_heads * 128 || k_stride < (long long)num_kv_heads * 128 ||
             v_stride < (long long)num_kv_heads * 128)
             return MM_ERR_BAD_ARG;
@@ -924,6 +931,16 @@ static int dense_attention(const void *q, const void *k, const void *v, long lon
     a.sq = q_stride, a.sk = k_stride, a.sv = v_stride;
     a.indptr = seq_indptr, a.B = batch, a.T = total_tokens, a.Hq = num_q_heads, a.Hkv = num_kv_heads;
     a.o = (uint16_t *)o;
+    if (prefix) {
+        int nc, chunk;
+        mm::dense_prefix_split(total_tokens, batch, num_q_heads, prefix->max_kv_len, &nc, &chunk);
+        if (((long long)total_tokens / MM_DENSE_ATTN_BQ + batch) * num_q_heads * nc >= (1LL << 31)) return MM_ERR_UNSUPPORTED;
+        const size_t need = mm::dense_prefix_workspace_bytes(total_tokens, batch, num_q_heads, prefix->max_kv_len);
+        if (need && (!prefix->ws || prefix->ws_bytes < need || ((uintptr_t)prefix->ws & 15))) return MM_ERR_BAD_ARG;
+        hipError_t e = mm::launch_dense_attention_prefix(a, prefix->kv_indptr, prefix->total_kv, prefix->max_kv_len, sm_scale, prefix->ws,
+                                                         (hipStream_t)stream);
+        return e == hipSuccess ? MM_OK : fail_hip(e, what);
+    }
     hipError_t e = windowed ? mm::launch_dense_attention_window(a, sm_scale, window, (hipStream_t)stream)
                             : mm::launch_dense_attention(a, sm_scale, (hipStream_t)stream);
     return e == hipSuccess ? MM_OK : fail_hip(e, what);
@@ -941,6 +958,47 @@ int mm_dense_attention_window(const void *q, const void *k, const void *v, long 
                               float sm_scale, void *o, mm_stream_t stream, int window) {
     return dense_attention(q, k, v, q_stride, k_stride, v_stride, seq_indptr, batch, total_tokens, num_q_heads, num_kv_heads, head_dim,
                            sm_scale, o, stream, true, window, "mm_dense_attention_window");
+}
+
+int mm_dense_attention_prefix_plan(int total_q_tokens, int batch, int num_q_heads, int max_kv_len, int *num_chunks, int *chunk_tokens) {
+    int nc, chunk;
+    mm::dense_prefix_split(total_q_tokens, batch, num_q_heads, max_kv_len, &nc, &chunk);
+    if (num_chunks) *num_chunks = nc;
+    if (chunk_tokens) *chunk_tokens = chunk;
+    return nc;
+}
+
+size_t mm_dense_attention_prefix_workspace_bytes(int total_q_tokens, int batch, int num_q_heads, int max_kv_len) {
+    return mm::dense_prefix_workspace_bytes(total_q_tokens, batch, num_q_heads, max_kv_len);
+}
+
+int mm_dense_attention_prefix(const void *q, const void *k, const void *v, long long q_stride, long long k_stride, long long v_stride,
+                              const int32_t *qo_indptr, const int32_t *kv_indptr, int batch, int total_q_tokens, int total_kv_tokens,
+                              int num_q_heads, int num_kv_heads, int head_dim, int max_kv_len, float sm_scale, void *workspace,
+                              size_t workspace_bytes, void *o, mm_stream_t stream) {
+    const DensePrefix prefix{kv_indptr, total_kv_tokens, max_kv_len, workspace, workspace_bytes};
+    return dense_attention(q, k, v, q_stride, k_stride, v_stride, qo_indptr, batch, total_q_tokens, num_q_heads, num_kv_heads, head_dim,
+                           sm_scale, o, stream, false, 0, "mm_dense_attention_prefix", &prefix);
+}
+
+// ---- a layer's cache rows as contiguous bf16 (kv_gather.hip, include/micromix_kvgather.h)
+int mm_kv_gather_dense(void *kv_data, void *kv_param, int kv_dtype, int max_pages, int num_layers, int layer, int num_kv_heads, int page_size,
+                       int head_dim, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_len, int batch,
+                       const int32_t *out_indptr, int total_kv_tokens, void *k_out, void *v_out, long long k_stride, long long v_stride,
+                       mm_stream_t stream) {
+    mm::PagedKV kv;
+    if (int st = kv_geometry(kv_data, kv_param, kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size, head_dim, kv_indptr, kv_indices,
+                             last_page_len, batch, &kv)) return st;
+    if (total_kv_tokens < 0 || ((k_stride | v_stride) & 7) || k_stride < (long long)num_kv_heads * 128 || v_stride < (long long)num_kv_heads * 128)
+        return MM_ERR_BAD_ARG;
+    if (total_kv_tokens == 0 || batch == 0) return MM_OK;
+    if (!kv_pointers(kv) || !out_indptr || !k_out || !v_out) return MM_ERR_BAD_ARG;
+    if ((((uintptr_t)kv_data | (uintptr_t)k_out | (uintptr_t)v_out) & 15) ||
+        (((uintptr_t)kv_param | (uintptr_t)kv_indptr | (uintptr_t)kv_indices | (uintptr_t)last_page_len | (uintptr_t)out_indptr) & 3))
+        return MM_ERR_BAD_ARG;
+    const mm::KVGather g{kv, out_indptr, (uint16_t *)k_out, (uint16_t *)v_out, k_stride, v_stride, total_kv_tokens, 0};
+    hipError_t e = mm::launch_kv_gather(g, (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_kv_gather_dense");
 }
 
 // ---- calibration statistics (calib_stats.hip, include/micromix_calib.h)

@@ -23,7 +23,11 @@
 // (T / 128 + B) * Hq needs no host copy of seq_indptr; the surplus workgroups exit.
 // The sliding-window form (mm_dense_attention_window, include/micromix_attention_window.h) is the kernel's second instantiation: the same
 // tiles, staging and pipeline over a walk that starts at the window's lower edge, stated at the template below.
+// The rectangular split-KV form (mm_dense_attention_prefix, include/micromix_attention_prefix.h) is the third: new query tokens over K / V
+// that also hold the tokens in front of them, the diagonal moved nk - nq to the right, blockIdx also carrying a chunk of the kv tokens,
+// and a small merge launch behind it; stated at the template too.
 #include "../../include/micromix_attention.h"
+#include "../../include/micromix_attention_prefix.h"
 #include "mx_buffer_ops.h"
 #include "mx_kernels.h"
 #include "mx_paged_kv.h"      // v8bf, v4u, v2u, pack_bf, HD
@@ -36,6 +40,7 @@
 namespace {
 
 using mm::DenseAttention;
+using mm::DenseAttentionPrefix;
 using mm::DenseAttentionWindow;
 using mm::kv::HD;
 using mm::kv::pack_bf;
@@ -56,12 +61,13 @@ typedef __bf16 bf16x4 __attribute__((__vector_size__(8)));
 typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
 
 // (sequence, tile of it, first token, token count) of workgroup tile index i; false for a surplus tile
-__device__ inline bool tile_of(const DenseAttention &a, int i, int &j, int &q0, int &n) {
+__device__ inline bool tile_of(const DenseAttention &a, int i, int &b, int &j, int &q0, int &n) {
     int lo = 0, hi = a.B;                            // the largest b with start(b) = seq_indptr[b] / BQ + b <= i
     while (hi - lo > 1) {
         const int mid = (lo + hi) >> 1;
         if (min(max(a.indptr[mid], 0), a.T) / BQ + mid <= i) lo = mid; else hi = mid;
     }
+    b = lo;
     q0 = min(max(a.indptr[lo], 0), a.T);
     n = min(max(a.indptr[lo + 1], 0), a.T) - q0;
     j = i - (q0 / BQ + lo);
@@ -80,23 +86,44 @@ __device__ __forceinline__ v2u read_tr(const uint8_t *p) {
 // the walk starts at the tile that holds the lower edge of the query tile's first row, a wave also skips the tiles wholly below the
 // window of its first row, and a second compare runs on the tiles that cross the lower edge of some row of the wave.  With WIN false
 // t0 and W are constants and every added line folds away: the un-windowed kernel's instructions are what they were without them.
-template <bool WIN>
-__global__ __launch_bounds__(NT) void dense_attention_kernel(const std::conditional_t<WIN, DenseAttentionWindow, DenseAttention> a) {
+// PFX: the rectangular split-KV form (mm_dense_attention_prefix, include/micromix_attention_prefix.h): the sequence's n = nq query rows
+// lie at q0 and its nk kv tokens at k0 of their own split, row i attends tokens 0 .. off + i with off = nk - nq (uniform, any sign), so
+// off moves kend, the wave skip and the compare; blockIdx.x = (tile * nc + chunk) * Hq + head, and the workgroup walks the kv tiles of
+// tokens [chunk * a.chunk, (chunk + 1) * a.chunk) below kend, leaving at once when there are none.  With nc > 1 the epilogue stores
+// the accumulators as they lie, unnormalised, and (m, l) per row for dense_prefix_merge_kernel; with nc == 1 it is the other forms'.
+// With PFX false off is 0, k0 is q0, nk is n and t1 is nt: the two instantiations above keep their instructions.
+template <bool WIN, bool PFX = false>
+__global__ __launch_bounds__(NT) void dense_attention_kernel(
+    const std::conditional_t<PFX, DenseAttentionPrefix, std::conditional_t<WIN, DenseAttentionWindow, DenseAttention>> a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];   // [2][K tile | V tile], written by the LDS-DMA only
 
     const int x = blockIdx.x, h = x % a.Hq, kvh = h / a.g;
-    const int tile = a.tiles - 1 - x / a.Hq;              // the last tiles of a sequence carry the most work: they start first
-    int j, q0, n;
-    if (!tile_of(a, tile, j, q0, n)) return;
+    int xt = x / a.Hq, ck = 0;                            // PFX: the head is fastest, then the chunk
+    if constexpr (PFX) ck = xt % a.nc, xt /= a.nc;
+    const int tile = a.tiles - 1 - xt;                    // the last tiles of a sequence carry the most work: they start first
+    int b, j, q0, n;
+    if (!tile_of(a, tile, b, j, q0, n)) return;
+    int k0 = q0, nk = n, off = 0;                         // where the sequence's kv tokens lie, and how far right the diagonal sits
+    if constexpr (PFX) {
+        k0 = min(max(a.kv_indptr[b], 0), a.Tk);
+        nk = max(min(max(a.kv_indptr[b + 1], 0), a.Tk) - k0, 0);
+        off = nk - n;
+    }
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l = tid & 63, c = l & 15, kq = l >> 4;
     const int i0 = j * BQ;                                // first token (of the sequence) of this query tile
-    const int kend = min(n, i0 + BQ);                     // tokens 0 .. kend - 1 are attended by some row
-    const int nt = (kend + BK - 1) / BK;
+    const int kend = min(nk, off + i0 + BQ);              // tokens 0 .. kend - 1 are attended by some row (PFX: none when kend <= 0)
+    const int nt = PFX && kend <= 0 ? 0 : (kend + BK - 1) / BK;
     const int wr0 = i0 + 32 * wave;                       // this wave's first row; its last valid one
     const bool wactive = wr0 < n;
     const int wmax = min(wr0 + 31, n - 1);
     int W = 0, t0 = 0;                                    // the window (1 <= W < T, the launch sees to it) and the first kv tile of the walk
     if constexpr (WIN) W = a.W, t0 = max(i0 - W + 1, 0) / BK;
+    int t1 = nt;                                          // the end of the walk
+    if constexpr (PFX) {
+        t0 = ck * (a.chunk / BK);
+        t1 = min(nt, t0 + a.chunk / BK);
+        if (t0 >= t1 && a.nc > 1) return;                 // nothing of this chunk lies below the tile's diagonal: the merge knows
+    }
 
     // ---- q as the MFMA B operand: row block rb, lane (c, kq) holds row wr0 + 16 rb + c, dims 32 kq + 8 s + e in step s
     v8bf qb[2][4];
@@ -111,8 +138,8 @@ __global__ __launch_bounds__(NT) void dense_attention_kernel(const std::conditio
     }
 
     // ---- staging: DMA instruction i of wave w fills LDS rows 16 w + 4 i .. + 3 of a tile, lane (kq, c) position c of row 16 w + 4 i + kq
-    const uint8_t *kseq = (const uint8_t *)(a.k + (int64_t)q0 * a.sk + (int64_t)kvh * HD);
-    const uint8_t *vseq = (const uint8_t *)(a.v + (int64_t)q0 * a.sv + (int64_t)kvh * HD);
+    const uint8_t *kseq = (const uint8_t *)(a.k + (int64_t)k0 * a.sk + (int64_t)kvh * HD);
+    const uint8_t *vseq = (const uint8_t *)(a.v + (int64_t)k0 * a.sv + (int64_t)kvh * HD);
     const int skb = (int)a.sk * 2, svb = (int)a.sv * 2;   // bytes between two tokens (<= 2^23)
     const unsigned lds0 = __builtin_amdgcn_readfirstlane(mm::lds_address(smem));
     auto issue = [&](int t) {
@@ -144,13 +171,14 @@ __global__ __launch_bounds__(NT) void dense_attention_kernel(const std::conditio
 #pragma unroll
         for (int dt = 0; dt < 8; ++dt) o[rb][dt] = v4f{0.0f, 0.0f, 0.0f, 0.0f};
 
-    if constexpr (WIN) issue(t0); else issue(0);           // the literal: with issue(t0) the un-windowed prologue is scheduled differently
-    for (int t = t0; t < nt; ++t) {
+    if constexpr (PFX) { if (t0 < t1) issue(t0); }         // nc == 1 and no token attended: no walk, the epilogue writes zeros
+    else if constexpr (WIN) issue(t0); else issue(0);      // the literal: with issue(t0) the un-windowed prologue is scheduled differently
+    for (int t = t0; t < t1; ++t) {
         mm::wait_vmcnt<0>();                               // this wave's share of tile t is in LDS
         __syncthreads();                                   // ... everybody's is, and nobody still reads tile t - 1
-        if (t + 1 < nt) issue(t + 1);                      // in flight during this tile's math
-        const int kt = t * BK;
-        if (!wactive || kt > wmax) continue;               // every row of this wave is masked on this tile
+        if (t + 1 < t1) issue(t + 1);                      // in flight during this tile's math
+        const int kt = t * BK, ko = kt - off;              // ko: the tile's first token seen from the diagonal, uniform
+        if (!wactive || ko > wmax) continue;               // every row of this wave is masked on this tile
         if (WIN && kt + BK - 1 < wr0 - W + 1) continue;    // ... here too: the tile ends below the window of the wave's first row
         const uint8_t *sk = smem + ((t - t0) & 1) * BUFB, *sv = sk + TILEB;
 
@@ -171,14 +199,14 @@ __global__ __launch_bounds__(NT) void dense_attention_kernel(const std::conditio
                 sc[1][blk][r] = d1[r] * a.scale_log2;
             }
         }
-        if (kt + BK - 1 > wr0) {                           // the tile crosses the diagonal of some row of this wave
+        if (ko + BK - 1 > wr0) {                           // the tile crosses the diagonal of some row of this wave
 #pragma unroll
             for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
                 for (int blk = 0; blk < 4; ++blk)
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
-                        if (kt + 16 * blk + 4 * kq + r > irow[rb]) sc[rb][blk][r] = -INFINITY;
+                        if (ko + 16 * blk + 4 * kq + r > irow[rb]) sc[rb][blk][r] = -INFINITY;
         }
         if (WIN && kt < wmax - W + 1) {                    // the tile crosses the lower edge of some row of this wave: token j of it is
             const int kw = kt - wr0 + W;                   // masked for row wr0 + x when j + W <= wr0 + x; kw is uniform and small
@@ -240,6 +268,27 @@ __global__ __launch_bounds__(NT) void dense_attention_kernel(const std::conditio
         }
     }
 
+    // ---- PFX, split: the partial rows as the accumulators hold them (lane (c, kq): row c of a block, dims 16 dt + 4 kq .. + 3, 16 bytes)
+    // and (m, l) per row, at part index ((tile * Hq + h) * nc + chunk) * BQ + row, the layout kv::merge_chunks reads with stride BQ
+    if constexpr (PFX) {
+        if (a.nc > 1) {
+            const int64_t part0 = (((int64_t)tile * a.Hq + h) * a.nc + ck) * BQ;
+            float *ml = a.ws + (int64_t)a.tiles * a.Hq * a.nc * BQ * HD;
+#pragma unroll
+            for (int rb = 0; rb < 2; ++rb) {
+                float ls = lsum[rb];
+                ls += __shfl_xor(ls, 16);
+                ls += __shfl_xor(ls, 32);
+                if (irow[rb] >= n) continue;
+                const int64_t part = part0 + (irow[rb] - i0);
+                float *op = a.ws + part * HD + 4 * kq;
+#pragma unroll
+                for (int dt = 0; dt < 8; ++dt) *(v4f *)(op + 16 * dt) = o[rb][dt];
+                if (kq == 0) *(float2 *)(ml + part * 2) = make_float2(m[rb], ls);
+            }
+            return;
+        }
+    }
     // ---- row totals over the 4 lanes of a row, then o = O / l, rounded to bf16 once
 #pragma unroll
     for (int rb = 0; rb < 2; ++rb) {
@@ -256,6 +305,28 @@ __global__ __launch_bounds__(NT) void dense_attention_kernel(const std::conditio
             w.y = pack_bf(o[rb][dt][2] * inv, o[rb][dt][3] * inv);
             *(v2u *)(orow + 16 * dt) = w;
         }
+    }
+}
+
+// combines the chunk partials of the rows of one (query tile, head): only the chunks that hold tokens below the tile's diagonal were
+// written, the first ceil(nt / tiles per chunk) of them, by the same kend as the kernel's; none: the rows attend nothing and get zeros
+__global__ __launch_bounds__(NT) void dense_prefix_merge_kernel(const DenseAttentionPrefix a) {
+    const int x = blockIdx.x, h = x % a.Hq, tile = a.tiles - 1 - x / a.Hq;
+    int b, j, q0, n;
+    if (!tile_of(a, tile, b, j, q0, n)) return;
+    const int k0 = min(max(a.kv_indptr[b], 0), a.Tk), nk = max(min(max(a.kv_indptr[b + 1], 0), a.Tk) - k0, 0);
+    const int i0 = j * BQ, kend = min(nk, nk - n + i0 + BQ), nt = kend <= 0 ? 0 : (kend + BK - 1) / BK, cpt = a.chunk / BK;
+    const int live = min(a.nc, (nt + cpt - 1) / cpt), rows = min(BQ, n - i0);
+    const int64_t first = ((int64_t)tile * a.Hq + h) * a.nc * BQ;       // part index of chunk 0, row 0; chunk stride BQ
+    const float *ml = a.ws + (int64_t)a.tiles * a.Hq * a.nc * BQ * HD;
+    for (int idx = threadIdx.x; idx < rows * (HD / 4); idx += NT) {
+        const int row = idx / (HD / 4), d = 4 * (idx % (HD / 4));
+        float o[4];
+        mm::kv::merge_chunks<4>(ml, a.ws + d, first + row, BQ, live, o);
+        v2u w;
+        w.x = pack_bf(o[0], o[1]);
+        w.y = pack_bf(o[2], o[3]);
+        *(v2u *)(a.o + ((int64_t)(q0 + i0 + row) * a.Hq + h) * HD + d) = w;
     }
 }
 
@@ -282,6 +353,40 @@ hipError_t launch_dense_attention_window(DenseAttention a, float sm_scale, int w
     w.scale_log2 = kv_scale_log2(sm_scale);
     w.W = window;
     dense_attention_kernel<true><<<(unsigned)((long long)w.tiles * w.Hq), NT, LDS_BYTES, stream>>>(w);
+    return hipGetLastError();
+}
+
+// nc chunks of `chunk` tokens from host values alone (kv_chunks, as the paged kernels get theirs): `tiles * Hq` workgroups per chunk
+// against MM_DENSE_PREFIX_TARGET = 512, the workgroups of 64 KB LDS an MI355X holds at once (2 per CU, 256 CUs) -- a second round of
+// them would wait for the first -- and kv_chunks' 256-token minimum, four kv tiles, below which the prologue and the partial rows
+// outweigh the walk
+void dense_prefix_split(int total_q, int B, int Hq, int max_kv_len, int *nc, int *chunk) {
+    *nc = 1, *chunk = BK;
+    if (total_q <= 0 || B <= 0 || Hq < 1 || max_kv_len <= 0) return;
+    kv_chunks(((long long)total_q / BQ + B) * Hq, MM_DENSE_PREFIX_TARGET, max_kv_len, BK, nc, chunk);
+}
+
+size_t dense_prefix_workspace_bytes(int total_q, int B, int Hq, int max_kv_len) {
+    int nc, chunk;
+    dense_prefix_split(total_q, B, Hq, max_kv_len, &nc, &chunk);
+    return nc > 1 ? (size_t)((long long)total_q / BQ + B) * Hq * nc * BQ * (HD + 2) * sizeof(float) : 0;    // DenseAttentionPrefix::ws
+}
+
+hipError_t launch_dense_attention_prefix(DenseAttention a, const int *kv_indptr, int total_kv, int max_kv_len, float sm_scale, void *ws,
+                                         hipStream_t stream) {
+    DenseAttentionPrefix p{};
+    static_cast<DenseAttention &>(p) = a;
+    p.g = a.Hq / a.Hkv;
+    p.tiles = a.T / BQ + a.B;
+    p.scale_log2 = kv_scale_log2(sm_scale);
+    p.kv_indptr = kv_indptr;
+    p.Tk = total_kv;
+    p.ws = (float *)ws;
+    dense_prefix_split(a.T, a.B, a.Hq, max_kv_len, &p.nc, &p.chunk);
+    dense_attention_kernel<false, true><<<(unsigned)((long long)p.tiles * p.Hq * p.nc), NT, LDS_BYTES, stream>>>(p);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || p.nc == 1) return e;
+    dense_prefix_merge_kernel<<<(unsigned)((long long)p.tiles * p.Hq), NT, 0, stream>>>(p);
     return hipGetLastError();
 }
 

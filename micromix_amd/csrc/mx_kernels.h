@@ -408,6 +408,28 @@ struct DenseAttentionWindow : DenseAttention {
     int W;
 };
 hipError_t launch_dense_attention_window(DenseAttention a, float sm_scale, int window, hipStream_t stream);
+// its rectangular split-KV form (include/micromix_attention_prefix.h): indptr / T are the query tokens' (qo_indptr, total_q_tokens),
+// kv_indptr / Tk the kv tokens'; nc and chunk come from dense_prefix_split, ws (dense_prefix_workspace_bytes, uninitialised; nc > 1 only)
+// holds the partial rows [tile][head][chunk][BQ][128] fp32, then (m, l) per row in the same order
+struct DenseAttentionPrefix : DenseAttention {
+    const int *kv_indptr;
+    int Tk, nc, chunk;
+    float *ws;
+};
+void dense_prefix_split(int total_q, int B, int Hq, int max_kv_len, int *nc, int *chunk);
+size_t dense_prefix_workspace_bytes(int total_q, int B, int Hq, int max_kv_len);
+hipError_t launch_dense_attention_prefix(DenseAttention a, const int *kv_indptr, int total_kv, int max_kv_len, float sm_scale, void *ws,
+                                         hipStream_t stream);
+// a layer's cache rows as contiguous bf16 (kv_gather.hip, include/micromix_kvgather.h): T output rows, sk / sv elements between two;
+// G is filled in by the launch
+struct KVGather {
+    PagedKV kv;
+    const int *out_indptr;
+    uint16_t *k_out, *v_out;
+    long long sk, sv;
+    int T, G;
+};
+hipError_t launch_kv_gather(KVGather a, hipStream_t stream);
 // token log-probabilities over bf16 rows (logprob.hip, include/micromix_logprob.h): target and temperature device arrays of `rows`
 // entries or null, every output null when not wanted, top_n 0 .. 32; ws: logprob_workspace_bytes, uninitialised
 size_t logprob_workspace_bytes(int rows, int vocab, int top_n);

@@ -1,4 +1,4 @@
-// Device side of the paged KV cache (PagedKV, mx_kernels.h), shared by kv_cache.hip, kv_prefill.hip, rope_append.hip and rope_prefill.hip: the page-table
+// Device side of the paged KV cache (PagedKV, mx_kernels.h), shared by kv_cache.hip, kv_prefill.hip, rope_append.hip, rope_prefill.hip and kv_gather.hip: the page-table
 // walk (seq_len, kv_row, k_row), where an appended token's row lies and what is written there (append_row, store_row: the int4 rule or
 // the fp8 rule of include/micromix_hip.h, or a bf16 copy), the decoding (int4: codes_to_bf16; fp8: fp8x4_to_bf16, fp8x4_to_f32; both:
 // scale_of, zero_of) and the split-KV merge (merge_chunks).
@@ -191,6 +191,19 @@ __device__ inline uint32_t dpp(uint32_t x) { return (uint32_t)__builtin_amdgcn_u
          x = f(x, __builtin_bit_cast(decltype(x), dpp<0x4e>(__builtin_bit_cast(uint32_t, x)))); \
          x = f(x, __builtin_bit_cast(decltype(x), dpp<0x141>(__builtin_bit_cast(uint32_t, x)))); } while (0)
 
+// ---- what a reader of a slot gets back, as bf16 bits: the one copy of the rule, for the rows store_row8 has just written and for the
+// rows kv_gather.hip finds stored.  fp8: 4 codes (one dword) times scale = 2^e, exact, so the high halves of the fp32 products are the
+// values.  int4: two codes as floats 0 .. 15 with the row's fp16 (scale, zero) as stored: the product is exact, so one fp32 and one
+// bf16 rounding
+__device__ inline v2u fp8_seen(uint32_t codes, float scale) {
+    const v2u back = fp8x4_to_bf16(codes);
+    v2u r;
+    r.x = (__float_as_uint(bf16f(back.x & 0xffffu) * scale) >> 16) | (__float_as_uint(bf16f(back.x >> 16) * scale) & 0xffff0000u);
+    r.y = (__float_as_uint(bf16f(back.y & 0xffffu) * scale) >> 16) | (__float_as_uint(bf16f(back.y >> 16) * scale) & 0xffff0000u);
+    return r;
+}
+__device__ inline uint32_t int4_seen(float c0, float c1, float sf, float zf) { return pack_bf(c0 * sf - zf, c1 * sf - zf); }
+
 // the K (which = 0) or V (which = 1) row of head h, given the K row of head 0 of the same page and slot (kv_row)
 __device__ inline int64_t row_of(const PagedKV &kv, int64_t k_row0, int which, int h) { return k_row0 + ((int64_t)which * kv.Hkv + h) * kv.P; }
 
@@ -225,9 +238,9 @@ __device__ inline void store_row8(const PagedKV &kv, int64_t row, int j, v4u &lo
                 v2s r = fp8_codes<false>(v2s{0, 0}, fp8_clamp(x[2 * m], top), e);
                 r = fp8_codes<true>(r, fp8_clamp(x[2 * m + 1], top), e);
                 code[half][m] = __builtin_bit_cast(uint32_t, r);
-                const v2u back = fp8x4_to_bf16(code[half][m]);               // exact, and so is the product with 2^e: the high halves
-                x[2 * m] = (__float_as_uint(bf16f(back.x & 0xffffu) * scale) >> 16) | (__float_as_uint(bf16f(back.x >> 16) * scale) & 0xffff0000u);
-                x[2 * m + 1] = (__float_as_uint(bf16f(back.y & 0xffffu) * scale) >> 16) | (__float_as_uint(bf16f(back.y >> 16) * scale) & 0xffff0000u);
+                const v2u seen = fp8_seen(code[half][m], scale);
+                x[2 * m] = seen.x;
+                x[2 * m + 1] = seen.y;
             }
         }
         if (row >= 0) {
@@ -258,7 +271,7 @@ __device__ inline void store_row8(const PagedKV &kv, int64_t row, int j, v4u &lo
         for (int m = 0; m < 4; ++m) {
             const float c0 = int4_code(bf16f(x[m] & 0xffffu), s, base), c1 = int4_code(bf16f(x[m] >> 16), s, base);
             code[half] |= ((unsigned)c0 | ((unsigned)c1 << 4)) << (8 * m);
-            x[m] = pack_bf(c0 * sf - zf, c1 * sf - zf);
+            x[m] = int4_seen(c0, c1, sf, zf);
         }
     }
     if (row >= 0) {

@@ -185,6 +185,7 @@ class PagedKVCache:
         self.kv_indices = torch.zeros((max(max_pages, batch * -(-int(max_seq_len or 0) // page_size)),), **i32)
         self.last_page_len = torch.zeros((batch,), **i32)
         self.append_indptr = torch.zeros((batch + 1,), **i32)
+        self.gather_indptr = torch.zeros((batch + 1,), **i32)  # running sums of the sequence lengths: where attend_new_dense gathers them
         # the groups of attend(shared=True), one tensor so that a table change costs one more copy: views of fixed size and address
         self._group_table = torch.tensor(list(range(batch + 1)) + list(range(batch)) + [0] * batch, **i32)   # nobody shares yet
         self.group_indptr, self.group_members, self.shared_len = self._group_table.split([batch + 1, batch, batch])
@@ -199,6 +200,7 @@ class PagedKVCache:
         self._workspace = None
         self._shared_workspace = None
         self._prefill_workspace = None
+        self._gathered = self._dense_workspace = None           # attend_new_dense: the layer as contiguous bf16 (k, v), the split's partials
         self._retired = []
         # device steps (the module docstring, "Device steps")
         self._ahead = False                                     # the device took steps the host lists have not seen: sync() reads them
@@ -210,6 +212,13 @@ class PagedKVCache:
         self._captured = False                                  # a step_launch was captured: a graph replay moves the device unseen
         self._steps_seen = 0                                    # steps_done of the state when the host last wrote or read it
         self._shared_host = [0] * batch                         # shared_len as it was last uploaded
+
+    def _upload_gather_indptr(self):
+        """gather_indptr from the host lengths: the one table no device step writes, so whoever renews the lengths (_upload, sync) calls this"""
+        sums = [0]
+        for n in self._seq_lens:
+            sums.append(sums[-1] + n)
+        self.gather_indptr.copy_(torch.tensor(sums, dtype=torch.int32))
 
     @property
     def seq_lens(self):
@@ -248,6 +257,7 @@ class PagedKVCache:
             self.kv_indices[: len(indices)].copy_(torch.tensor(indices, dtype=torch.int32))
         self.last_page_len.copy_(torch.tensor(last, dtype=torch.int32))
         self.append_indptr.copy_(torch.tensor(app, dtype=torch.int32))
+        self._upload_gather_indptr()
         self.num_new_tokens = app[-1]
         self._announced = self._parents = None                  # extend sets them again after its upload
         self._tree_words_live = False
@@ -722,6 +732,53 @@ class PagedKVCache:
                                        self.append_indptr, layer, bound, sm_scale=sm_scale,
                                        workspace=self._prefill_workspace if need else None, window=self.window, tree_mask=tree)
 
+    def attend_new_dense(self, layer, q, max_seq_len=None, sm_scale=None):
+        """`attend_new` on the dense kernels, for many new tokens over a cache that already holds tokens (a later chunk of a chunked
+        prefill, a new turn, a prompt behind a forked prefix): called after `append` / `append_rope` of the same layer, it gathers the
+        layer into two bf16 buffers the cache owns (`mixedgemm.kv_gather_dense`, every sequence at `gather_indptr`, the running sums
+        of the lengths) and runs `mixedgemm.dense_attention_prefix(q, K, V, append_indptr, gather_indptr, bound)`: three launches --
+        gather, attention, merge -- all capture-safe under max_seq_len, which bounds every sequence as in `attend`; the buffers hold
+        batch * bound tokens, grow like the workspaces do, and the retired ones are kept for graphs captured earlier.
+        Opt-in, because the bits are not `attend_new`'s: K and V are the cache's values rounded to bf16 -- exact for a bf16 and an fp8
+        cache, one more rounding for int4, as in `prefill_fresh` -- and the dense kernel sums in another order.  It pays when the new
+        tokens fill query tiles of 128; a few tokens per sequence are `attend_new`'s.
+        ValueError on a cache made with window=, when the host lists do not describe the announced tokens (the tables changed since
+        the last `extend`, or a device step announced them, in Python or by a replayed graph: `gather_indptr` is written by the host
+        only, by `extend` and its kin and again by `sync()`, after which the call works), and when max_seq_len is below a sequence's
+        length (tokens past the bound would be left out without a word).
+        Out of scope: a sliding-window form, tree masks, reading the pages inside the attention kernel without the gather, and
+        gathering only the tokens that changed since the last call."""
+        if self.window:
+            raise ValueError(f"attend_new_dense has no sliding-window form: this cache was made with window={self.window}; use attend_new()")
+        stale = self._ahead or self._announced is None or self._announced[1] is None
+        if not stale and not torch.cuda.is_current_stream_capturing():
+            try:
+                self._host("attend_new_dense")                  # a replayed graph may have taken steps no Python saw
+            except RuntimeError:
+                stale = True
+        if stale:
+            raise ValueError("attend_new_dense: the host lists do not describe the announced tokens (the tables changed since the last "
+                             "extend, or a device step announced them: call sync() first); or use attend_new()")
+        if q.dim() != 3 or q.size(0) != self.num_new_tokens:
+            raise RuntimeError(f"attend_new_dense expects the {self.num_new_tokens} tokens announced by extend(), got q of shape {tuple(q.shape)}")
+        bound = max(self._seq_lens) if max_seq_len is None else int(max_seq_len)
+        if bound < max(self._seq_lens):
+            raise ValueError(f"attend_new_dense: max_seq_len {bound} is below the longest sequence, {max(self._seq_lens)} tokens")
+        rows = max(self.batch * bound, 1)
+        if self._gathered is None or self._gathered[0].size(0) < rows:
+            if self._gathered is not None:
+                self._retired.append(self._gathered)            # a graph captured earlier may still point at them
+            self._gathered = tuple(torch.empty((rows, self.num_kv_heads, HEAD_DIM), dtype=torch.bfloat16, device=self.device) for _ in "kv")
+        need = mixedgemm.dense_attention_prefix_workspace_bytes(self.num_new_tokens, self.batch, q.size(1), bound)
+        if need and (self._dense_workspace is None or self._dense_workspace.numel() < need):
+            if self._dense_workspace is not None:
+                self._retired.append(self._dense_workspace)     # a graph captured earlier may still point at it
+            self._dense_workspace = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        k, v = mixedgemm.kv_gather_dense(self.kv_data, self.kv_param, self.kv_indptr, self.kv_indices, self.last_page_len, self.gather_indptr,
+                                         layer, self._gathered[0].size(0), *self._gathered)
+        return mixedgemm.dense_attention_prefix(q, k, v, self.append_indptr, self.gather_indptr, bound, sm_scale=sm_scale,
+                                                workspace=self._dense_workspace if need else None)
+
     # ---- device steps ---------------------------------------------------------------------------------------------------------------------
     def _step_args(self, next_counts, max_seq_len):
         counts = [int(next_counts)] * self.batch if isinstance(next_counts, int) else [int(n) for n in next_counts]
@@ -970,6 +1027,7 @@ class PagedKVCache:
                 self._ref[p] += 1
         assert all((self._ref[p] == 0) == (n == 1) for p, n in enumerate(self._count_free())), "a page is both listed and free, or neither"
         self._seq_lens = lens
+        self._upload_gather_indptr()                            # kv_step does not know this table
         self._ahead = False
         self._announced = (announced, [n - a for n, a in zip(lens, announced)])
         self.num_new_tokens = sum(announced)

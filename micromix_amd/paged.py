@@ -10,6 +10,7 @@ already quantized and one head count); micromix_amd/kvcache.py is the small cach
 current stream and is capture-safe."""
 from __future__ import annotations
 
+import ctypes
 from collections import namedtuple
 
 import torch
@@ -21,7 +22,8 @@ __all__ = ["kv_append", "rope_kv_append", "rope_kv_append_dense", "rope_qk", "kv
            "paged_decode_shared_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes", "argmax_rows", "argmax_rows_workspace_bytes",
            "verify_greedy", "sample_rows", "sample_rows_workspace_bytes", "logprob_rows", "logprob_rows_workspace_bytes", "cross_entropy",
            "process_logits", "spec_sample_rows", "spec_sample_rows_workspace_bytes", "chain_candidates", "token_step", "ngram_draft",
-           "ngram_draft_workspace_bytes", "uniform_rows", "dense_attention", "dense_attention_window"]
+           "ngram_draft_workspace_bytes", "uniform_rows", "dense_attention", "dense_attention_window", "dense_attention_prefix",
+           "dense_attention_prefix_workspace_bytes", "dense_attention_prefix_plan", "kv_gather_dense"]
 
 # entries a library built before them lacks: (the symbol looked for, the names and the feature of the rebuild message)
 _TREE = ("mm_paged_prefill_tree", "mm_paged_prefill_tree / mm_kv_move_rows", "tree-masked attention")
@@ -35,6 +37,8 @@ _TOKENS = ("mm_ngram_draft", "mm_token_step / mm_ngram_draft", "the token histor
 _RANDOM = ("mm_uniform_rows", "mm_uniform_rows", "seeded uniform numbers")
 _DENSE = ("mm_dense_attention", "mm_dense_attention", "dense attention over contiguous q, k, v")
 _DENSE_WINDOW = ("mm_dense_attention_window", "mm_dense_attention_window", "sliding-window dense attention over contiguous q, k, v")
+_DENSE_PREFIX = ("mm_dense_attention_prefix", "mm_dense_attention_prefix", "dense attention of new tokens over a gathered prefix")
+_GATHER = ("mm_kv_gather_dense", "mm_kv_gather_dense", "the gather of a layer's cache into contiguous bf16")
 _ROPE = ("mm_rope_prefill", "mm_rope_prefill", "the prefill shape of RoPE + KV append")
 _SHARED = ("mm_paged_decode_shared", "mm_paged_decode_shared", "shared-prefix decode")
 
@@ -1213,18 +1217,19 @@ def paged_prefill(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, qo
     return o
 
 
-def _dense_attention(entry, q, k, v, seq_indptr, sm_scale, *window):
-    """the argument handling and the launch that `dense_attention` and `dense_attention_window` share: `entry` is the _lib_with triple of
-    the C entry, `window` what it takes after the stream"""
+def _dense_attention(entry, q, k, v, seq_indptr, sm_scale, *window, prefix=None):
+    """the argument handling and the launch that `dense_attention`, `dense_attention_window` and `dense_attention_prefix` share: `entry`
+    is the _lib_with triple of the C entry, `window` what it takes after the stream; `prefix`: (kv_indptr, max_kv_len, workspace) of the
+    rectangular form, whose k and v hold their own token count and whose seq_indptr splits the queries"""
     for name, t in (("q", q), ("k", k), ("v", v)):             # what the tensors are first, where they are after: the order of _check_tensor
         if not (isinstance(t, torch.Tensor) and t.dtype is torch.bfloat16):
             _check_tensor(t, name, torch.bfloat16)
     Hq, sq = _token_rows(q, "q", None)
     Hkv, sk = _token_rows(k, "k", None)
     _, sv = _token_rows(v, "v", Hkv)
-    T = q.size(0)
-    if k.size(0) != T or v.size(0) != T:
-        raise RuntimeError("q, k and v must hold the same T tokens")
+    T, Tk = q.size(0), k.size(0)
+    if v.size(0) != Tk or (prefix is None and Tk != T):
+        raise RuntimeError("q, k and v must hold the same T tokens" if prefix is None else "k and v must hold the same tokens")
     _head_groups(Hq, Hkv)
     if seq_indptr is not None and not (isinstance(seq_indptr, torch.Tensor) and seq_indptr.dtype is torch.int32 and seq_indptr.dim() == 1
                                        and seq_indptr.numel() >= 1):
@@ -1237,6 +1242,14 @@ def _dense_attention(entry, q, k, v, seq_indptr, sm_scale, *window):
         seq_indptr = torch.arange(2, dtype=torch.int32, device=dev) * T
     B = _tensor(seq_indptr, "seq_indptr", torch.int32, dev).numel() - 1
     lib = _lib_with(*entry)
+    if prefix is not None:
+        kv_indptr, max_kv_len, workspace = prefix
+        if kv_indptr is None:
+            kv_indptr = torch.arange(2, dtype=torch.int32, device=dev) * Tk
+        if _tensor(kv_indptr, "kv_indptr", torch.int32, dev).dim() != 1 or kv_indptr.numel() != B + 1:
+            raise RuntimeError(f"kv_indptr must be a one-dimensional int32 tensor of B + 1 = {B + 1} entries, as qo_indptr")
+        max_kv_len = _max_seq_len(max_kv_len)
+        workspace, ws_args = _kv_workspace(workspace, dense_attention_prefix_workspace_bytes(T, B, Hq, max_kv_len), dev)
 
     def rows(t, H, stride):
         """the tensor and its token stride as the C ABI takes them: in place when _token_rows' rule and the 16-byte rule allow"""
@@ -1246,6 +1259,10 @@ def _dense_attention(entry, q, k, v, seq_indptr, sm_scale, *window):
 
     (q, sq), (k, sk), (v, sv) = rows(q, Hq, sq), rows(k, Hkv, sk), rows(v, Hkv, sv)
     o = torch.empty((T, Hq, 128), dtype=torch.bfloat16, device=dev)
+    if prefix is not None:
+        _launch(entry[0][3:], dev, getattr(lib, entry[0]), _ptr(q), _ptr(k), _ptr(v), sq, sk, sv, _ptr(seq_indptr), _ptr(kv_indptr), B, T, Tk,
+                Hq, Hkv, 128, max_kv_len, _sm_scale(sm_scale), *ws_args, _ptr(o), _stream_ptr(dev))
+        return o
     _launch(entry[0][3:], dev, getattr(lib, entry[0]), _ptr(q), _ptr(k), _ptr(v), sq, sk, sv, _ptr(seq_indptr), B, T, Hq, Hkv, 128,
             _sm_scale(sm_scale), _ptr(o), _stream_ptr(dev), *window)
     return o
@@ -1277,3 +1294,58 @@ def dense_attention_window(q, k, v, window, seq_indptr=None, sm_scale=None):
     if isinstance(window, bool) or not isinstance(window, int) or window < 1:
         raise ValueError(f"window must be an int >= 1, got {window!r}")
     return _dense_attention(_DENSE_WINDOW, q, k, v, seq_indptr, sm_scale, min(window, 2 ** 31 - 1))
+
+
+def dense_attention_prefix_plan(total_q_tokens, batch, Hq, max_kv_len):
+    """(nc, chunk) of `dense_attention_prefix` for these host values (include/micromix_attention_prefix.h, Split): nc chunks of `chunk` kv
+    tokens, chunk a multiple of 64; nc == 1: one launch, no workspace"""
+    nc, chunk = ctypes.c_int(), ctypes.c_int()
+    _lib_with(*_DENSE_PREFIX).mm_dense_attention_prefix_plan(int(total_q_tokens), int(batch), int(Hq), int(max_kv_len), ctypes.byref(nc),
+                                                             ctypes.byref(chunk))
+    return nc.value, chunk.value
+
+
+def dense_attention_prefix_workspace_bytes(total_q_tokens, batch, Hq, max_kv_len):
+    """bytes of fp32 scratch `dense_attention_prefix` needs for these host values (0: one chunk, no workspace)"""
+    return int(_lib_with(*_DENSE_PREFIX).mm_dense_attention_prefix_workspace_bytes(int(total_q_tokens), int(batch), int(Hq), int(max_kv_len)))
+
+
+def dense_attention_prefix(q, k, v, qo_indptr, kv_indptr, max_kv_len, sm_scale=None, workspace=None):
+    """`dense_attention` of new query tokens over K / V that also hold the tokens in front of them (include/micromix_attention_prefix.h,
+    mm_dense_attention_prefix): q bf16 [Tq, Hq, 128] or [Tq, Hq * 128], k and v bf16 [Tk, Hkv, 128] or [Tk, Hkv * 128] -> o bf16 [Tq, Hq, 128].
+
+    qo_indptr and kv_indptr (int32 [B + 1] device tensors; both None: one sequence) split the query and the kv tokens among the
+    sequences.  With nq and nk a sequence's two counts, its query i attends its keys 0 .. nk - nq + i: the mask of `paged_prefill`,
+    aligned bottom-right; a query whose range is empty (nk < nq) gives zeros.  Nothing of another sequence is read.
+    `max_kv_len` bounds every nk.  The split of the kv tokens into chunks depends on it (and Tq, B, Hq) only, as does the grid, so a
+    captured graph stays valid while the sequences grow up to it with the same Tq; `dense_attention_prefix_plan` tells the split.
+    `workspace` (any contiguous device tensor of at least dense_attention_prefix_workspace_bytes(Tq, B, Hq, max_kv_len) bytes, not
+    initialised) is allocated here when None -- pass one when capturing a graph.  With one chunk there is one launch and none is
+    needed, and with nq == nk everywhere the result has `dense_attention`'s bits; otherwise a second launch merges the chunks.
+    sm_scale, the in-place reading of views and the errors are `dense_attention`'s.  `kv_gather_dense` makes k and v from a paged
+    cache; `PagedKVCache.attend_new_dense` is the route from a cache."""
+    return _dense_attention(_DENSE_PREFIX, q, k, v, qo_indptr, sm_scale, prefix=(kv_indptr, max_kv_len, workspace))
+
+
+def kv_gather_dense(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, out_indptr, layer, total_kv_tokens, k_out=None, v_out=None):
+    """Layer `layer` of a paged cache as contiguous bf16 (include/micromix_kvgather.h, mm_kv_gather_dense): returns (k, v), bf16
+    [total_kv_tokens, Hkv, 128] each, the operands of `dense_attention_prefix`.
+
+    out_indptr (int32 [B + 1] device tensor): token p of sequence b goes to row out_indptr[b] + p; rows that belong to no token -- between
+    two sequences' ranges, past a sequence's length, at or past out_indptr[b + 1], on a released page -- are left as they were.  The
+    values are what a reader of the slot gets back, as `rope_kv_append_dense` returns them for the tokens it appends: the bf16 bits, fp8
+    code * 2^e, int4 bf16(code * scale - zero) in fp32.  The cache is int4, fp8 or bf16, told apart as in `kv_append`.
+    k_out / v_out: bf16 [total_kv_tokens, Hkv, 128] tensors to write instead of new ones (new ones are not cleared).  The launch
+    depends on total_kv_tokens and Hkv only and the tables are read by the kernel: capture-safe while the sequences grow within it."""
+    lib = _lib_with(*_GATHER)
+    dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer)
+    if _tensor(out_indptr, "out_indptr", torch.int32, dev).dim() != 1 or out_indptr.numel() != B + 1:
+        raise RuntimeError(f"out_indptr must be a one-dimensional int32 tensor of B + 1 = {B + 1} entries")
+    T = int(total_kv_tokens)
+    if T < 0:
+        raise RuntimeError("total_kv_tokens must be >= 0")
+    k_out = _out(k_out, "k_out", torch.bfloat16, dev, (T, Hkv, 128), "{0} bf16")
+    v_out = _out(v_out, "v_out", torch.bfloat16, dev, (T, Hkv, 128), "{0} bf16")
+    _launch("kv_gather_dense", dev, lib.mm_kv_gather_dense, *kv_args, _ptr(out_indptr), T, _ptr(k_out), _ptr(v_out), Hkv * 128, Hkv * 128,
+            _stream_ptr(dev))
+    return k_out, v_out
