@@ -145,6 +145,9 @@ _ATTENTION_WINDOW_PROTOS, ATTENTION_WINDOW_EXPORTS, _ = _read("micromix_attentio
 _ATTENTION_PREFIX_PROTOS, ATTENTION_PREFIX_EXPORTS, ATTENTION_PREFIX = _read("micromix_attention_prefix.h")
 # KVGATHER_EXPORTS: the entry of include/micromix_kvgather.h, likewise; KVGATHER holds the output rows a workgroup owns by name
 _KVGATHER_PROTOS, KVGATHER_EXPORTS, KVGATHER = _read("micromix_kvgather.h")
+# ATTENTION_HD64_EXPORTS: the entries of include/micromix_attention_hd64.h, likewise; ATTENTION_HD64 holds the tile sizes of its attention
+# kernel, the stride limit and the tokens a RoPE workgroup owns by name
+_ATTENTION_HD64_PROTOS, ATTENTION_HD64_EXPORTS, ATTENTION_HD64 = _read("micromix_attention_hd64.h")
 
 _lib = None
 
@@ -160,7 +163,7 @@ def load():
             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
     for protos in (_PROTOS, _CALIB_PROTOS, _LOGPROB_PROTOS, _LOGITS_PROTOS, _SPEC_PROTOS, _KVSTEP_PROTOS, _TOKENS_PROTOS, _RANDOM_PROTOS, _ATTENTION_PROTOS, _ROPE_PROTOS,
-                   _ATTENTION_WINDOW_PROTOS, _ATTENTION_PREFIX_PROTOS, _KVGATHER_PROTOS):
+                   _ATTENTION_WINDOW_PROTOS, _ATTENTION_PREFIX_PROTOS, _KVGATHER_PROTOS, _ATTENTION_HD64_PROTOS):
         _bind(lib, protos)
     _lib = lib
     return _lib

@@ -10,6 +10,7 @@
 #include "../../include/micromix_attention.h"
 #include "../../include/micromix_attention_window.h"
 #include "../../include/micromix_attention_prefix.h"
+#include "../../include/micromix_attention_hd64.h"
 #include "../../include/micromix_kvgather.h"
 #include "../../include/micromix_rope.h"
 #include "mx_common.h"
@@ -979,6 +980,49 @@ int mm_dense_attention_prefix(const void *q, const void *k, const void *v, long 
     const DensePrefix prefix{kv_indptr, total_kv_tokens, max_kv_len, workspace, workspace_bytes};
     return dense_attention(q, k, v, q_stride, k_stride, v_stride, qo_indptr, batch, total_q_tokens, num_q_heads, num_kv_heads, head_dim,
                            sm_scale, o, stream, false, 0, "mm_dense_attention_prefix", &prefix);
+}
+
+// ---- the cache-less route for 64-wide heads (dense_attention_hd64.hip, include/micromix_attention_hd64.h): the statuses in the order
+// of dense_attention above, with rows of 64 elements
+int mm_dense_attention_hd64(const void *q, const void *k, const void *v, long long q_stride, long long k_stride, long long v_stride,
+                            const int32_t *seq_indptr, int batch, int total_tokens, int num_q_heads, int num_kv_heads, int window,
+                            float sm_scale, void *o, mm_stream_t stream) {
+    if (total_tokens < 0 || batch < 0 || num_q_heads < 1 || num_kv_heads < 1 || window < 0) return MM_ERR_BAD_ARG;
+    const bool work = total_tokens > 0 && batch > 0;
+    if (work) {
+        if (!q || !k || !v || !o || !seq_indptr) return MM_ERR_BAD_ARG;
+        if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) & 15) || ((uintptr_t)seq_indptr & 3)) return MM_ERR_BAD_ARG;
+        if (((q_stride | k_stride | v_stride) & 7) || q_stride < (long long)num_q_heads * 64 || k_stride < (long long)num_kv_heads * 64 ||
+            v_stride < (long long)num_kv_heads * 64)
+            return MM_ERR_BAD_ARG;
+    }
+    if (num_q_heads % num_kv_heads) return MM_ERR_UNSUPPORTED;
+    if (!work) return MM_OK;
+    if (q_stride > MM_DENSE_ATTN_HD64_MAX_STRIDE || k_stride > MM_DENSE_ATTN_HD64_MAX_STRIDE || v_stride > MM_DENSE_ATTN_HD64_MAX_STRIDE)
+        return MM_ERR_UNSUPPORTED;
+    if (((long long)total_tokens / MM_DENSE_ATTN_HD64_BQ + batch) * num_q_heads >= (1LL << 31)) return MM_ERR_UNSUPPORTED;
+    mm::DenseAttention a{};
+    a.q = (const uint16_t *)q, a.k = (const uint16_t *)k, a.v = (const uint16_t *)v;
+    a.sq = q_stride, a.sk = k_stride, a.sv = v_stride;
+    a.indptr = seq_indptr, a.B = batch, a.T = total_tokens, a.Hq = num_q_heads, a.Hkv = num_kv_heads;
+    a.o = (uint16_t *)o;
+    hipError_t e = mm::launch_dense_attention_hd64(a, sm_scale, window, (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_dense_attention_hd64");
+}
+
+int mm_rope_qk_hd64(const void *q_bf16, const void *k_bf16, int64_t qkv_token_stride, int num_qo_heads, int num_kv_heads,
+                    const void *cos_bf16, const void *sin_bf16, int64_t cs_token_stride, int num_tokens, void *q_out_bf16,
+                    void *k_out_bf16, mm_stream_t stream) {
+    if (num_tokens < 0 || num_qo_heads < 1 || num_kv_heads < 1 || num_qo_heads % num_kv_heads) return MM_ERR_BAD_ARG;
+    // a row of a token's q (the wider of the two) and of cos / sin must fit its stride; the kernel moves 16-byte vectors
+    if (qkv_token_stride < (int64_t)num_qo_heads * 64 || cs_token_stride < 64 || ((qkv_token_stride | cs_token_stride) & 7)) return MM_ERR_BAD_ARG;
+    if (num_tokens == 0) return MM_OK;
+    if (!q_bf16 || !k_bf16 || !cos_bf16 || !sin_bf16 || !q_out_bf16 || !k_out_bf16) return MM_ERR_BAD_ARG;
+    if (((uintptr_t)q_bf16 | (uintptr_t)k_bf16 | (uintptr_t)cos_bf16 | (uintptr_t)sin_bf16 | (uintptr_t)q_out_bf16 | (uintptr_t)k_out_bf16) & 15)
+        return MM_ERR_BAD_ARG;
+    hipError_t e = mm::launch_rope_qk_hd64(q_bf16, k_bf16, qkv_token_stride, num_qo_heads, num_kv_heads, cos_bf16, sin_bf16, cs_token_stride,
+                                           num_tokens, q_out_bf16, k_out_bf16, (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_rope_qk_hd64");
 }
 
 // ---- a layer's cache rows as contiguous bf16 (kv_gather.hip, include/micromix_kvgather.h)

@@ -420,6 +420,11 @@ void dense_prefix_split(int total_q, int B, int Hq, int max_kv_len, int *nc, int
 size_t dense_prefix_workspace_bytes(int total_q, int B, int Hq, int max_kv_len);
 hipError_t launch_dense_attention_prefix(DenseAttention a, const int *kv_indptr, int total_kv, int max_kv_len, float sm_scale, void *ws,
                                          hipStream_t stream);
+// the same route for 64-wide heads (dense_attention_hd64.hip, include/micromix_attention_hd64.h): `a` as launch_dense_attention takes
+// it with rows of 64 elements, window 0 for none; and plain RoPE of q and k, as launch_rope_prefill without a cache
+hipError_t launch_dense_attention_hd64(DenseAttention a, float sm_scale, int window, hipStream_t stream);
+hipError_t launch_rope_qk_hd64(const void *q, const void *k, int64_t qkv_stride, int Hq, int Hkv, const void *cos, const void *sin,
+                               int64_t cs_stride, int T, void *q_out, void *k_out, hipStream_t stream);
 // a layer's cache rows as contiguous bf16 (kv_gather.hip, include/micromix_kvgather.h): T output rows, sk / sv elements between two;
 // G is filled in by the launch
 struct KVGather {

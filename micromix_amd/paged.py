@@ -40,6 +40,7 @@ _DENSE_WINDOW = ("mm_dense_attention_window", "mm_dense_attention_window", "slid
 _DENSE_PREFIX = ("mm_dense_attention_prefix", "mm_dense_attention_prefix", "dense attention of new tokens over a gathered prefix")
 _GATHER = ("mm_kv_gather_dense", "mm_kv_gather_dense", "the gather of a layer's cache into contiguous bf16")
 _ROPE = ("mm_rope_prefill", "mm_rope_prefill", "the prefill shape of RoPE + KV append")
+_DENSE_HD64 = ("mm_dense_attention_hd64", "mm_dense_attention_hd64 / mm_rope_qk_hd64", "dense attention and RoPE for 64-wide heads")
 _SHARED = ("mm_paged_decode_shared", "mm_paged_decode_shared", "shared-prefix decode")
 
 
@@ -136,8 +137,8 @@ def _kv_workspace(workspace, need, dev):
     return workspace, (_ptr(workspace), workspace.numel() * workspace.element_size())
 
 
-def _sm_scale(sm_scale):
-    scale = float(sm_scale) if sm_scale is not None else 128 ** -0.5
+def _sm_scale(sm_scale, hd=128):
+    scale = float(sm_scale) if sm_scale is not None else hd ** -0.5
     if not scale > 0:
         raise ValueError("sm_scale must be positive")
     return scale
@@ -952,51 +953,66 @@ def verify_greedy(target_tok, draft_tok, root_tok, qo_indptr, kv_indptr, last_pa
     return result, move_src, move_dst
 
 
-def _token_rows(t, name, heads):
+def _head_dim(**operands):
+    """64 when an operand is [T, H, 64] -- then every one has to be: the entries of include/micromix_attention_hd64.h --, else 128,
+    whose shapes _token_rows checks.  Shapes only: no device is looked at"""
+    if not any(isinstance(t, torch.Tensor) and t.dim() == 3 and t.size(2) == 64 for t in operands.values()):
+        return 128
+    for name, t in operands.items():
+        if not (isinstance(t, torch.Tensor) and t.dim() == 3 and t.size(2) == 64):
+            raise RuntimeError(f"{name} must be [T, H, 64] bf16 as the other operands are: q, k and v agree on the head dimension, and a "
+                               "2-D tensor always means 128-wide heads")
+    return 64
+
+
+def _token_rows(t, name, heads, hd=128):
     """(heads, token stride in elements) of q / k / v given as [T, H, 128] or [T, H * 128] whose rows lie contiguous within a token.
     Stride 0: any stride will do (at most one token); None: the tensor has to be copied (rows not contiguous, an odd stride, a
-    misaligned pointer)"""
-    if t.dim() == 3 and t.size(2) == 128:
-        H, inner = t.size(1), t.stride(2) == 1 and (t.size(1) == 1 or t.stride(1) == 128)
-    elif t.dim() == 2 and t.size(1) % 128 == 0 and t.size(1):
+    misaligned pointer).  hd = 64 (the entries of include/micromix_attention_hd64.h): [T, H, 64] only, a 2-D tensor always means 128"""
+    if t.dim() == 3 and t.size(2) == hd:
+        H, inner = t.size(1), t.stride(2) == 1 and (t.size(1) == 1 or t.stride(1) == hd)
+    elif t.dim() == 2 and hd == 128 and t.size(1) % 128 == 0 and t.size(1):
         H, inner = t.size(1) // 128, t.stride(1) == 1
-    else:
+    elif hd == 128:
         raise RuntimeError(f"{name} must be [T, H, 128] or [T, H * 128] bf16")
+    else:
+        raise RuntimeError(f"{name} must be [T, H, {hd}] bf16 as the other operands are: q, k and v agree on the head dimension")
     if heads is not None and H != heads:
         raise RuntimeError(f"{name} has {H} heads, the cache has {heads}")
     stride = t.stride(0) if t.size(0) > 1 else 0
-    ok = inner and (stride == 0 or stride >= H * 128) and stride % 2 == 0 and t.data_ptr() % 4 == 0
+    ok = inner and (stride == 0 or stride >= H * hd) and stride % 2 == 0 and t.data_ptr() % 4 == 0
     return H, (stride if ok else None)
 
 
-def _rope_operands(dev, Hkv, q, k, v, cos, sin, vec):
+def _rope_operands(dev, Hkv, q, k, v, cos, sin, vec, hd=128):
     """(T, Hq, Hkv, q, k, v, their token stride, cos, sin, their row stride) as the RoPE entries take them, accesses of `vec` elements:
-    q, k, v read in place when they share one token stride that is a multiple of `vec` and at least Hq * 128 and their pointers are
-    2 * vec-byte aligned, packed into one buffer (one copy) otherwise; cos / sin likewise, made contiguous otherwise.  Hkv None: k says"""
+    q, k, v read in place when they share one token stride that is a multiple of `vec` and at least Hq * hd and their pointers are
+    2 * vec-byte aligned, packed into one buffer (one copy) otherwise; cos / sin likewise, made contiguous otherwise.  Hkv None: k says.
+    hd = 64: the same with rows of 64 elements, for the entries of include/micromix_attention_hd64.h"""
     for n, t in (("q", q), ("k", k), ("v", v), ("cos", cos), ("sin", sin)):
         if not (isinstance(t, torch.Tensor) and t.dtype is torch.bfloat16 and t.is_cuda and t.get_device() == dev.index):
             _check_tensor(t, n, torch.bfloat16, dev)      # contiguity is not asked of these five
-    Hq, sq = _token_rows(q, "q", None)
-    Hkv, sk = _token_rows(k, "k", Hkv)
-    _, sv = _token_rows(v, "v", Hkv)
+    Hq, sq = _token_rows(q, "q", None, hd)
+    Hkv, sk = _token_rows(k, "k", Hkv, hd)
+    _, sv = _token_rows(v, "v", Hkv, hd)
     T = q.size(0)
     if k.size(0) != T or v.size(0) != T:
         raise RuntimeError("q, k and v must hold the same T tokens")
     _head_groups(Hq, Hkv)
     strides = {sq, sk, sv} - {0}
-    if (None in strides or len(strides) > 1 or max(strides, default=Hq * 128) < Hq * 128 or max(strides, default=0) % vec
+    if (None in strides or len(strides) > 1 or max(strides, default=Hq * hd) < Hq * hd or max(strides, default=0) % vec
             or any(t.data_ptr() % (2 * vec) for t in (q, k, v))):
-        packed = torch.cat([q.reshape(T, Hq * 128), k.reshape(T, Hkv * 128), v.reshape(T, Hkv * 128)], dim=1)
-        q, k, v = packed[:, : Hq * 128], packed[:, Hq * 128: (Hq + Hkv) * 128], packed[:, (Hq + Hkv) * 128:]
-        strides = {(Hq + 2 * Hkv) * 128}
-    sq = max(strides, default=Hq * 128)
-    if cos.shape != sin.shape or cos.dim() not in (2, 3) or cos.size(-1) != 128 or cos.numel() != T * 128:
-        raise RuntimeError(f"cos and sin must both be [T = {T}, 128] (or [bsz, q_len, 128] with bsz * q_len = T) bf16")
-    cos, sin = cos.reshape(T, 128), sin.reshape(T, 128)
-    sc = cos.stride(0) if T > 1 else 128
-    if not (cos.stride(1) == 1 and sin.stride(1) == 1 and (T <= 1 or sin.stride(0) == sc) and sc >= 128 and sc % vec == 0
+        packed = torch.cat([q.reshape(T, Hq * hd), k.reshape(T, Hkv * hd), v.reshape(T, Hkv * hd)], dim=1)
+        q, k, v = packed[:, : Hq * hd], packed[:, Hq * hd: (Hq + Hkv) * hd], packed[:, (Hq + Hkv) * hd:]
+        strides = {(Hq + 2 * Hkv) * hd}
+    sq = max(strides, default=Hq * hd)
+    if cos.shape != sin.shape or cos.dim() not in (2, 3) or cos.size(-1) != hd or cos.numel() != T * hd:
+        raise RuntimeError(f"cos and sin must both be [T = {T}, {hd}] (or [bsz, q_len, {hd}] with bsz * q_len = T) bf16")
+    cos, sin = cos.reshape(T, hd), sin.reshape(T, hd)
+    sc = cos.stride(0) if T > 1 else hd
+    if not (cos.stride(1) == 1 and sin.stride(1) == 1 and (T <= 1 or sin.stride(0) == sc) and sc >= hd and sc % vec == 0
             and cos.data_ptr() % (2 * vec) == 0 and sin.data_ptr() % (2 * vec) == 0):
-        cos, sin, sc = cos.contiguous(), sin.contiguous(), 128
+        cos, sin, sc = cos.contiguous(), sin.contiguous(), hd
     return T, Hq, Hkv, q, k, v, sq, cos, sin, sc
 
 
@@ -1055,14 +1071,23 @@ def rope_qk(q, k, cos, sin):
     q, k: bf16 [T, H, 128] or [T, H * 128], Hq a multiple of Hkv.  Views of one packed projection (what FusedQLinear returns) are read in
     place when their common token stride is a multiple of 8 elements and their pointers are 16-byte aligned; otherwise they are copied
     once.  cos, sin: bf16 [T, 128] or HF's [1, T, 128] / [bsz, q_len, 128] (flattened); a row stride is honoured.  Runs on the current
-    stream, capture-safe."""
-    lib = _lib_with(*_ROPE)
+    stream, capture-safe.
+    64-wide heads (include/micromix_attention_hd64.h, mm_rope_qk_hd64): q and k given as [T, H, 64] -- both, and 3-D: a 2-D tensor
+    always means 128 -- with cos, sin [T, 64] return (q_rot [T, Hq, 64], k_rot [T, Hkv, 64]) by the same rule with the partner at d +- 32."""
+    hd = _head_dim(q=q, k=k)
+    if hd == 64 and not all(isinstance(t, torch.Tensor) and t.size(-1) == 64 for t in (cos, sin)):
+        raise RuntimeError("cos and sin must be [T, 64] bf16 for 64-wide heads")
+    lib = _lib_with(*(_ROPE if hd == 128 else _DENSE_HD64))
     if not (isinstance(q, torch.Tensor) and q.dtype is torch.bfloat16 and q.is_cuda):
         _check_tensor(q, "q", torch.bfloat16)
     dev = q.device
-    T, Hq, Hkv, q, k, _, sq, cos, sin, sc = _rope_operands(dev, None, q, k, k, cos, sin, 8)
-    q_rot = torch.empty((T, Hq, 128), dtype=torch.bfloat16, device=dev)
-    k_rot = torch.empty((T, Hkv, 128), dtype=torch.bfloat16, device=dev)
+    T, Hq, Hkv, q, k, _, sq, cos, sin, sc = _rope_operands(dev, None, q, k, k, cos, sin, 8, hd)
+    q_rot = torch.empty((T, Hq, hd), dtype=torch.bfloat16, device=dev)
+    k_rot = torch.empty((T, Hkv, hd), dtype=torch.bfloat16, device=dev)
+    if hd == 64:
+        _launch("rope_qk", dev, lib.mm_rope_qk_hd64, _ptr(q), _ptr(k), sq, Hq, Hkv, _ptr(cos), _ptr(sin), sc, T, _ptr(q_rot), _ptr(k_rot),
+                _stream_ptr(dev))
+        return q_rot, k_rot
     _launch("rope_qk", dev, lib.mm_rope_prefill, None, None, 0, 0, 0, 0, Hkv, 0, 128, None, None, None, 0, _ptr(q), _ptr(k), _ptr(k), sq, Hq,
             _ptr(cos), _ptr(sin), sc, None, T, _ptr(q_rot), _ptr(k_rot), None, _stream_ptr(dev))
     return q_rot, k_rot
@@ -1224,9 +1249,14 @@ def _dense_attention(entry, q, k, v, seq_indptr, sm_scale, *window, prefix=None)
     for name, t in (("q", q), ("k", k), ("v", v)):             # what the tensors are first, where they are after: the order of _check_tensor
         if not (isinstance(t, torch.Tensor) and t.dtype is torch.bfloat16):
             _check_tensor(t, name, torch.bfloat16)
-    Hq, sq = _token_rows(q, "q", None)
-    Hkv, sk = _token_rows(k, "k", None)
-    _, sv = _token_rows(v, "v", Hkv)
+    hd = _head_dim(q=q, k=k, v=v)
+    if hd == 64:
+        if prefix is not None:
+            raise RuntimeError("dense_attention_prefix takes 128-wide heads only: the paged cache it reads from has no 64-wide rows")
+        entry = _DENSE_HD64
+    Hq, sq = _token_rows(q, "q", None, hd)
+    Hkv, sk = _token_rows(k, "k", None, hd)
+    _, sv = _token_rows(v, "v", Hkv, hd)
     T, Tk = q.size(0), k.size(0)
     if v.size(0) != Tk or (prefix is None and Tk != T):
         raise RuntimeError("q, k and v must hold the same T tokens" if prefix is None else "k and v must hold the same tokens")
@@ -1254,11 +1284,15 @@ def _dense_attention(entry, q, k, v, seq_indptr, sm_scale, *window, prefix=None)
     def rows(t, H, stride):
         """the tensor and its token stride as the C ABI takes them: in place when _token_rows' rule and the 16-byte rule allow"""
         if stride is None or stride % 8 or t.data_ptr() % 16:
-            return t.contiguous(), H * 128
-        return t, stride or H * 128
+            return t.contiguous(), H * hd
+        return t, stride or H * hd
 
     (q, sq), (k, sk), (v, sv) = rows(q, Hq, sq), rows(k, Hkv, sk), rows(v, Hkv, sv)
-    o = torch.empty((T, Hq, 128), dtype=torch.bfloat16, device=dev)
+    o = torch.empty((T, Hq, hd), dtype=torch.bfloat16, device=dev)
+    if hd == 64:                                               # one entry for both forms: window 0 is none
+        _launch("dense_attention_hd64", dev, lib.mm_dense_attention_hd64, _ptr(q), _ptr(k), _ptr(v), sq, sk, sv, _ptr(seq_indptr), B, T, Hq,
+                Hkv, *(window or (0,)), _sm_scale(sm_scale, 64), _ptr(o), _stream_ptr(dev))
+        return o
     if prefix is not None:
         _launch(entry[0][3:], dev, getattr(lib, entry[0]), _ptr(q), _ptr(k), _ptr(v), sq, sk, sv, _ptr(seq_indptr), _ptr(kv_indptr), B, T, Tk,
                 Hq, Hkv, 128, max_kv_len, _sm_scale(sm_scale), *ws_args, _ptr(o), _stream_ptr(dev))
@@ -1281,6 +1315,8 @@ def dense_attention(q, k, v, seq_indptr=None, sm_scale=None):
     of that sequence; a sequence of length 0 writes nothing, and rows of o that no sequence owns are left as allocated.
     Softmax in fp32 with sm_scale (default 1/sqrt(128)).  The launch depends on (T, B, Hq, Hkv) only and seq_indptr is read by the kernel:
     capture-safe, no workspace, and a captured graph replays with another split of the same T.
+    64-wide heads (include/micromix_attention_hd64.h, mm_dense_attention_hd64, a kernel of its own): q, k, v given as [T, H, 64] -- all
+    three, and 3-D: a 2-D tensor always means 128 -- return o [T, Hq, 64], sm_scale defaulting to 1/sqrt(64); everything else as above.
     """
     return _dense_attention(_DENSE, q, k, v, seq_indptr, sm_scale)
 
@@ -1290,7 +1326,8 @@ def dense_attention_window(q, k, v, window, seq_indptr=None, sm_scale=None):
     attends tokens max(0, i - window + 1) .. i of that sequence, what SDPA computes under a causal band mask.  q, k, v, seq_indptr,
     sm_scale, the in-place reading of views, the errors and the capture rules are `dense_attention`'s; window is an int >= 1.
     A query tile past the window walks about (window + 128) / 64 kv tiles however long its sequence is.  window >= T runs
-    `dense_attention`'s kernel, and inside a windowed launch a sequence no longer than window gets `dense_attention`'s bits."""
+    `dense_attention`'s kernel, and inside a windowed launch a sequence no longer than window gets `dense_attention`'s bits.
+    [T, H, 64] operands run mm_dense_attention_hd64 with this window, as `dense_attention` states."""
     if isinstance(window, bool) or not isinstance(window, int) or window < 1:
         raise ValueError(f"window must be an int >= 1, got {window!r}")
     return _dense_attention(_DENSE_WINDOW, q, k, v, seq_indptr, sm_scale, min(window, 2 ** 31 - 1))
