@@ -8,8 +8,8 @@
  * codes are micromix_hip.h's.  micromix_amd/paged.py (dense_attention, dense_attention_window and rope_qk given [T, H, 64] tensors) is the
  * Python side; csrc/dense_attention_hd64.hip holds both kernels.
  *
- * Out of scope: the paged cache stays 128-only -- its rows, its int4 / fp8 groups of 128 values and its decode / prefill / tree kernels --
- * and so do mm_dense_attention_prefix, mm_kv_gather_dense and everything else that reads or writes a cache.
+ * Out of scope here: the paged cache.  Its append and decode for 64-wide rows are micromix_kv_hd64.h's; its prefill / tree / window
+ * kernels, mm_dense_attention_prefix and mm_kv_gather_dense stay 128-only.
  *
  * mm_dense_attention_hd64.  q, k, v are bf16; token t, head h, element e of q lies at q[t * q_stride + h * 64 + e], and k, v likewise with
  * their strides and num_kv_heads heads: the strides are ELEMENTS BETWEEN TWO TOKENS, so q, k and v may be three views of one packed

@@ -148,6 +148,9 @@ _KVGATHER_PROTOS, KVGATHER_EXPORTS, KVGATHER = _read("micromix_kvgather.h")
 # ATTENTION_HD64_EXPORTS: the entries of include/micromix_attention_hd64.h, likewise; ATTENTION_HD64 holds the tile sizes of its attention
 # kernel, the stride limit and the tokens a RoPE workgroup owns by name
 _ATTENTION_HD64_PROTOS, ATTENTION_HD64_EXPORTS, ATTENTION_HD64 = _read("micromix_attention_hd64.h")
+# KV_HD64_EXPORTS: the entries of include/micromix_kv_hd64.h, likewise; KV_HD64 holds the tokens an append workgroup owns and the decode
+# kernel's tile and wave counts by name
+_KV_HD64_PROTOS, KV_HD64_EXPORTS, KV_HD64 = _read("micromix_kv_hd64.h")
 
 _lib = None
 
@@ -163,7 +166,7 @@ def load():
             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
     for protos in (_PROTOS, _CALIB_PROTOS, _LOGPROB_PROTOS, _LOGITS_PROTOS, _SPEC_PROTOS, _KVSTEP_PROTOS, _TOKENS_PROTOS, _RANDOM_PROTOS, _ATTENTION_PROTOS, _ROPE_PROTOS,
-                   _ATTENTION_WINDOW_PROTOS, _ATTENTION_PREFIX_PROTOS, _KVGATHER_PROTOS, _ATTENTION_HD64_PROTOS):
+                   _ATTENTION_WINDOW_PROTOS, _ATTENTION_PREFIX_PROTOS, _KVGATHER_PROTOS, _ATTENTION_HD64_PROTOS, _KV_HD64_PROTOS):
         _bind(lib, protos)
     _lib = lib
     return _lib

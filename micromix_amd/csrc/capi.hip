@@ -11,10 +11,12 @@
 #include "../../include/micromix_attention_window.h"
 #include "../../include/micromix_attention_prefix.h"
 #include "../../include/micromix_attention_hd64.h"
+#include "../../include/micromix_kv_hd64.h"
 #include "../../include/micromix_kvgather.h"
 #include "../../include/micromix_rope.h"
 #include "mx_common.h"
 #include "mx_kernels.h"
+#include "mx_kv_hd64.h"
 #include "mx_kv_shared_host.h"
 
 #include <stdio.h>
@@ -1023,6 +1025,77 @@ int mm_rope_qk_hd64(const void *q_bf16, const void *k_bf16, int64_t qkv_token_st
     hipError_t e = mm::launch_rope_qk_hd64(q_bf16, k_bf16, qkv_token_stride, num_qo_heads, num_kv_heads, cos_bf16, sin_bf16, cs_token_stride,
                                            num_tokens, q_out_bf16, k_out_bf16, (hipStream_t)stream);
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_rope_qk_hd64");
+}
+
+// ---- the paged cache for 64-wide heads (kv_hd64.hip, include/micromix_kv_hd64.h): the statuses in the order the header gives them
+static int kv_geometry_hd64(const void *kv_data, const void *kv_param, int kv_dtype, int max_pages, int L, int layer, int Hkv, int P,
+                            const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_len, int B, mm::PagedKV *kv) {
+    const int st = kv_geometry(kv_data, kv_param, kv_dtype, max_pages, L, layer, Hkv, P, 128, kv_indptr, kv_indices, last_page_len, B, kv);
+    return st ? st : kv_dtype == MM_KV_INT4 ? MM_ERR_UNSUPPORTED : MM_OK;
+}
+// what the kernels read of a cache, where they need it: kv_data in 16-byte vectors, the rest as dwords
+static bool kv_aligned_hd64(const mm::PagedKV &kv) {
+    return !((uintptr_t)kv.data & 15) && !(((uintptr_t)kv.param | (uintptr_t)kv.indptr | (uintptr_t)kv.indices | (uintptr_t)kv.last_page_len) & 3);
+}
+
+int mm_rope_kv_append_hd64(void *kv_data, void *kv_param, int kv_dtype, int max_pages, int num_layers, int layer, int num_kv_heads,
+                           int page_size, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_len, int batch,
+                           const void *q_bf16, const void *k_bf16, const void *v_bf16, int64_t qkv_token_stride, int num_qo_heads,
+                           const void *cos_bf16, const void *sin_bf16, int64_t cs_token_stride, const int32_t *append_indptr,
+                           int num_tokens, void *q_out_bf16, void *k_out_bf16, void *v_out_bf16, mm_stream_t stream) {
+    mm::PagedKV kv;
+    const bool rot = cos_bf16 || sin_bf16;
+    if (num_kv_heads >= 1 && (num_tokens < 0 || num_qo_heads < 1 || num_qo_heads % num_kv_heads)) return MM_ERR_BAD_ARG;
+    const int st = kv_geometry_hd64(kv_data, kv_param, kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size, kv_indptr, kv_indices,
+                                    last_page_len, batch, &kv);
+    if (st == MM_ERR_BAD_ARG) return st;
+    // a row of a token's q | k | v and of cos / sin must fit its stride; the kernel moves 16-byte vectors
+    if (qkv_token_stride < (int64_t)(num_qo_heads > num_kv_heads ? num_qo_heads : num_kv_heads) * 64 || (qkv_token_stride & 7)) return MM_ERR_BAD_ARG;
+    if (rot && (cs_token_stride < 64 || (cs_token_stride & 7))) return MM_ERR_BAD_ARG;
+    if (st) return st;
+    if (num_tokens == 0) return MM_OK;
+    if (batch == 0 || !kv_pointers(kv) || !append_indptr || !k_bf16 || !v_bf16) return MM_ERR_BAD_ARG;   // batch 0: tokens of no sequence
+    if (rot ? !cos_bf16 || !sin_bf16 || !q_bf16 || !q_out_bf16 : !q_bf16 != !q_out_bf16) return MM_ERR_BAD_ARG;
+    if (((uintptr_t)q_bf16 | (uintptr_t)k_bf16 | (uintptr_t)v_bf16 | (uintptr_t)cos_bf16 | (uintptr_t)sin_bf16 | (uintptr_t)q_out_bf16 |
+         (uintptr_t)k_out_bf16 | (uintptr_t)v_out_bf16) & 15)
+        return MM_ERR_BAD_ARG;
+    if (!kv_aligned_hd64(kv) || ((uintptr_t)append_indptr & 3)) return MM_ERR_BAD_ARG;
+    hipError_t e = mm::launch_rope_kv_append_hd64(kv, q_bf16, k_bf16, v_bf16, qkv_token_stride, num_qo_heads, cos_bf16, sin_bf16,
+                                                  cs_token_stride, append_indptr, num_tokens, q_out_bf16, k_out_bf16, v_out_bf16,
+                                                  (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_rope_kv_append_hd64");
+}
+
+size_t mm_paged_decode_hd64_workspace_bytes(int batch, int num_qo_heads, int num_kv_heads, int max_seq_len) {
+    if (batch <= 0 || num_kv_heads <= 0 || num_qo_heads <= 0 || max_seq_len < 0 || num_qo_heads % num_kv_heads || num_qo_heads / num_kv_heads > 16)
+        return 0;
+    return mm::kv_decode_hd64_workspace_bytes(batch, num_qo_heads, num_kv_heads, max_seq_len);
+}
+
+int mm_paged_decode_hd64_split(int batch, int num_kv_heads, int max_seq_len, int *chunks, int *chunk_len) {
+    if (batch < 1 || num_kv_heads < 1 || max_seq_len < 0 || !chunks || !chunk_len) return MM_ERR_BAD_ARG;
+    mm::kv_decode_hd64_split(batch, num_kv_heads, max_seq_len, chunks, chunk_len);
+    return MM_OK;
+}
+
+int mm_paged_decode_hd64(const void *q_bf16, const void *kv_data, const void *kv_param, int kv_dtype, int max_pages, int num_layers,
+                         int layer, int num_kv_heads, int page_size, const int32_t *kv_indptr, const int32_t *kv_indices,
+                         const int32_t *last_page_len, int batch, int num_qo_heads, int max_seq_len, float sm_scale, void *workspace,
+                         size_t workspace_bytes, void *o_bf16, mm_stream_t stream) {
+    mm::PagedKV kv;
+    const int st = kv_geometry_hd64(kv_data, kv_param, kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size, kv_indptr, kv_indices,
+                                    last_page_len, batch, &kv);
+    if (st == MM_ERR_BAD_ARG) return st;
+    if (num_qo_heads < 1 || num_qo_heads % num_kv_heads || max_seq_len < 0) return MM_ERR_BAD_ARG;
+    if (st) return st;
+    if (num_qo_heads / num_kv_heads > 16) return MM_ERR_UNSUPPORTED;
+    if (batch == 0) return MM_OK;
+    if (!q_bf16 || !kv_pointers(kv) || !o_bf16) return MM_ERR_BAD_ARG;
+    if ((((uintptr_t)q_bf16 | (uintptr_t)o_bf16) & 15) || !kv_aligned_hd64(kv)) return MM_ERR_BAD_ARG;
+    const size_t need = mm::kv_decode_hd64_workspace_bytes(batch, num_qo_heads, num_kv_heads, max_seq_len);
+    if (need && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15))) return MM_ERR_BAD_ARG;
+    hipError_t e = mm::launch_paged_decode_hd64(kv, q_bf16, num_qo_heads, max_seq_len, sm_scale, workspace, o_bf16, (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_paged_decode_hd64");
 }
 
 // ---- a layer's cache rows as contiguous bf16 (kv_gather.hip, include/micromix_kvgather.h)

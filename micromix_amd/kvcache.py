@@ -17,6 +17,12 @@
 "fp8_e4m3" (OCP e4m3fn codes with a power-of-two scale per row: half the bytes of bf16, relative error at most 2^-4 per value, and
 attention that equals, bit for bit, attention over a bf16 cache of the dequantized values).  Nothing else in the class depends on it.
 
+    cache = PagedKVCache(..., kind="bf16", head_dim=64)   # Llama-3.2-1B / Qwen2.5-0.5B: rows of 64 (include/micromix_kv_hd64.h)
+
+With `head_dim=64` (kinds "bf16" and "fp8_e4m3"; q, k, v [.., H, 64], cos / sin [T, 64]) `extend`, `append`, `append_rope`,
+`prefill_fresh`, `attend`, `truncate` and `reset` work; everything that needs a 128-only kernel -- a window, `fork`, `attend(shared=True)`,
+`attend_new`, `attend_new_dense`, `tree_mask`, `accept`, the verify and step family -- raises ValueError naming head_dim 64.
+
 The page table lives in device tensors of fixed capacity that `extend` rewrites in place, so `append` + `attend` (or `attend_new`) captured once into a
 hipGraph replay correctly after later `extend` calls, as long as T stays the same and the sequences stay within the captured
 `max_seq_len`.  The allocator is a free list with a reference count per page, so sequences can share pages (below).
@@ -153,9 +159,19 @@ HEAD_DIM = 128
 
 
 class PagedKVCache:
-    def __init__(self, num_layers, num_kv_heads, page_size, max_pages, batch, kind="int4", device="cuda", window=None, release=True, max_seq_len=None):
+    def __init__(self, num_layers, num_kv_heads, page_size, max_pages, batch, kind="int4", device="cuda", window=None, release=True, max_seq_len=None,
+                 head_dim=HEAD_DIM):
         if kind not in ("int4", "bf16", "fp8_e4m3"):
             raise ValueError("kind must be 'int4', 'bf16' or 'fp8_e4m3'")
+        if head_dim not in (HEAD_DIM, 64):
+            raise ValueError(f"head_dim must be {HEAD_DIM} or 64, got {head_dim}")
+        self.head_dim = head_dim
+        if head_dim == 64:
+            if kind == "int4":
+                raise ValueError("head_dim 64 has no int4 kind: the int4 rule is one (scale, zero) group per 128 values and a 64-value row "
+                                 "has no such group; use kind='bf16' or 'fp8_e4m3'")
+            if window:
+                raise ValueError(f"head_dim 64 has no sliding-window form (window={window}): its decode kernel attends every token")
         self.window = 0 if window is None else int(window)
         if self.window < 0:
             raise ValueError("window must be None, 0 (no window) or a positive token count")
@@ -168,7 +184,14 @@ class PagedKVCache:
         self.num_layers, self.num_kv_heads, self.page_size, self.max_pages, self.batch = num_layers, num_kv_heads, page_size, max_pages, batch
         self.kind, self.device = kind, dev
         shape = (max_pages, num_layers, 2, num_kv_heads, page_size)
-        if kind in ("int4", "fp8_e4m3"):      # int4: two codes per byte; fp8 (OCP e4m3fn): one; both with fp16 (scale, zero) per row
+        if head_dim == 64:                    # rows of 64 (include/micromix_kv_hd64.h); the fp8 codes as float8_e4m3fn: that is how the ops
+            if kind == "fp8_e4m3":            # tell them from the int4 cache of 128-wide heads, which is uint8 [.., 64] too
+                self.kv_data = torch.zeros(shape + (64,), dtype=torch.uint8, device=dev).view(torch.float8_e4m3fn)
+                self.kv_param = torch.zeros(shape + (2,), dtype=torch.float16, device=dev)
+            else:
+                self.kv_data = torch.zeros(shape + (64,), dtype=torch.bfloat16, device=dev)
+                self.kv_param = None
+        elif kind in ("int4", "fp8_e4m3"):      # int4: two codes per byte; fp8 (OCP e4m3fn): one; both with fp16 (scale, zero) per row
             self.kv_data = torch.zeros(shape + (HEAD_DIM // 2 if kind == "int4" else HEAD_DIM,), dtype=torch.uint8, device=dev)
             self.kv_param = torch.zeros(shape + (2,), dtype=torch.float16, device=dev)
         else:
@@ -212,6 +235,12 @@ class PagedKVCache:
         self._captured = False                                  # a step_launch was captured: a graph replay moves the device unseen
         self._steps_seen = 0                                    # steps_done of the state when the host last wrote or read it
         self._shared_host = [0] * batch                         # shared_len as it was last uploaded
+
+    def _only_128(self, what):
+        """the methods whose kernels exist for 128-wide heads only refuse a head_dim 64 cache here, before any device work"""
+        if self.head_dim == 64:
+            raise ValueError(f"{what} has no form for head_dim 64: its kernel is 128-only (extend, append, append_rope, prefill_fresh, "
+                             "attend, truncate and reset work)")
 
     def _upload_gather_indptr(self):
         """gather_indptr from the host lengths: the one table no device step writes, so whoever renews the lengths (_upload, sync) calls this"""
@@ -395,6 +424,7 @@ class PagedKVCache:
         then lists the same pages, released entries included, and each page's count goes up.  length 0 is a reset.  ValueError for src == dst,
         a length outside [0, seq_lens[src]] and a length that would put a released page inside the window (the module docstring).
         Rewrites the page table on the device like `extend` (outside graph capture)."""
+        self._only_128("fork")
         self._host("fork")
         length = self.seq_lens[src] if length is None else int(length)
         if src == dst:
@@ -457,6 +487,8 @@ class PagedKVCache:
         has it there.  It rests on this: `extend` releases no page of a sequence whose announced tokens start at position 0 -- the
         first of them has a window that begins at 0 -- so every slot the append writes exists; the pages below the window of the
         last token go at the next `extend`, as they do after `attend_new`.  On a cache without a window it is the plain route."""
+        if windowed:
+            self._only_128("prefill_fresh(windowed=True)")
         if self.window and not windowed:
             raise ValueError(f"prefill_fresh has no sliding-window form: this cache was made with window={self.window}; use "
                              "append_rope() and attend_new()")
@@ -479,6 +511,7 @@ class PagedKVCache:
         docstring, "Shared-prefix decode"), always, whether or not anything is shared.  Its two bounds default to host bookkeeping, the
         largest shared count and the longest tail now; under capture pass max_seq_len, which then bounds the tails, and max_shared_len."""
         if shared:
+            self._only_128("attend(shared=True)")
             if self.window:
                 raise ValueError("attend(shared=True) has no sliding-window form: this cache was made with window="
                                  f"{self.window}; use attend()")
@@ -497,7 +530,10 @@ class PagedKVCache:
         if max_seq_len is None:
             self._host("attend without max_seq_len")
         bound = max(self.seq_lens) if max_seq_len is None else int(max_seq_len)
-        need = mixedgemm.paged_decode_workspace_bytes(self.batch, q.size(1), self.num_kv_heads, bound, self.window)
+        if self.head_dim == 64:
+            need = mixedgemm.paged_decode_hd64_workspace_bytes(self.batch, q.size(1), self.num_kv_heads, bound)
+        else:
+            need = mixedgemm.paged_decode_workspace_bytes(self.batch, q.size(1), self.num_kv_heads, bound, self.window)
         if need and (self._workspace is None or self._workspace.numel() < need):
             if self._workspace is not None:
                 self._retired.append(self._workspace)      # a graph captured earlier may still point at it
@@ -514,6 +550,7 @@ class PagedKVCache:
         ValueError for a parent >= its index or < -1, a list of the wrong length, a tree of more than 64 nodes, and tables changed
         since the `extend`.  The parents are kept for `accept`, and a copy of the words for `verify_launch`: in a tensor of the cache's
         own that keeps its address while the token count does not grow, so a captured `verify_launch` replays with the next tree."""
+        self._only_128("tree_mask")
         if self._announced is None:
             raise ValueError("tree_mask: the page tables changed since the last extend (fork, truncate, reset, accept): nothing is announced")
         counts = self._announced[0]
@@ -560,6 +597,7 @@ class PagedKVCache:
         path that is not a chain from the root under the parents of the last `tree_mask` (without one: causal chains, so a prefix
         0, 1, .. k - 1).  `verify` picks the paths on the device and does all of this without the host in between (the module
         docstring, "Verifying a draft")."""
+        self._only_128("accept")
         self._host("accept")
         checked = self._checked_paths(paths, "accept")
         bases = self._announced[1]
@@ -617,6 +655,7 @@ class PagedKVCache:
         the first call with a token count, and nothing is read on the host: capturable, after every layer's `append`.  A graph
         captured with a tree replays with a tree (`tree_mask` writes the next one where the graph reads it), one captured with
         chains with chains.  ValueError on a cache made with window= when `tree_mask` was given a tree: chains only there."""
+        self._only_128("verify_launch")
         if self.device.type == "cpu":
             raise RuntimeError("verify_launch needs a device cache; a CPU cache verifies with verify()")
         if self.window and any(p is not None for p in self._parents or ()):
@@ -653,6 +692,7 @@ class PagedKVCache:
         ValueError as `accept` raises it, here AFTER the rows have moved -- a path the parents of `tree_mask` do not allow, which
         includes a tree sequence that kept all (root_tok < 0): the rows of the announced tokens are then undefined, the committed
         tokens are untouched, and `truncate(b, base_b)` for every sequence (base_b = seq_lens[b] minus what it announced) recovers."""
+        self._only_128("commit")
         self._host("commit")
         if self._announced is None:
             raise ValueError("commit: the page tables changed since the last extend (fork, truncate, reset, accept): nothing to accept")
@@ -664,6 +704,7 @@ class PagedKVCache:
         """Greedy verification of the tokens the last `extend` announced, after every layer's `append`: `verify_launch` then `commit`
         (the module docstring, "Verifying a draft"); returns (paths, next_tokens).  On a CPU cache the walk runs here, in plain
         Python, and `accept` moves the rows: the rule in words."""
+        self._only_128("verify")
         if self.device.type != "cpu":
             return self.commit(self.verify_launch(target_tok, draft_tok, root_tok))
         if self._announced is None:
@@ -716,6 +757,7 @@ class PagedKVCache:
         tree: the mask `tree_mask()` returned (int64 [num_new_tokens]): the new tokens are tree drafts, and a token attends the
         committed tokens, its ancestors among the new ones and itself (the module docstring, "Tree drafts").  ValueError on a cache
         made with window=."""
+        self._only_128("attend_new")
         if tree is not None and self.window:
             raise ValueError(f"attend_new(tree=) has no sliding-window form: this cache was made with window={self.window}")
         if q.dim() != 3 or q.size(0) != self.num_new_tokens:
@@ -748,6 +790,7 @@ class PagedKVCache:
         length (tokens past the bound would be left out without a word).
         Out of scope: a sliding-window form, tree masks, reading the pages inside the attention kernel without the gather, and
         gathering only the tokens that changed since the last call."""
+        self._only_128("attend_new_dense")
         if self.window:
             raise ValueError(f"attend_new_dense has no sliding-window form: this cache was made with window={self.window}; use attend_new()")
         stale = self._ahead or self._announced is None or self._announced[1] is None
@@ -850,6 +893,7 @@ class PagedKVCache:
         max_seq_len=max_seq_len, depths=depths)` would do outside capture, so that the FIRST such call can already be captured.
         `step_launch` does all of this itself when it is not capturing.  Call it again before replaying a graph of steps whenever
         host calls (extend, fork, truncate, ...) changed the tables since: the graph reads the state that was uploaded last."""
+        self._only_128("upload_state")
         self._host("upload_state")
         if self.release:
             raise ValueError("device steps do not release pages below a window: this cache was made with window= and release on")
@@ -930,6 +974,7 @@ class PagedKVCache:
         `tree_mask` (outside capture) and `verify_launch` work for the next step; when next_counts equal the counts announced before,
         the tree of the last `tree_mask` call stays in force: a fixed topology needs no call between the steps.
         On a CPU cache the rule runs here in plain Python over the lists, and a step that cannot be taken raises RuntimeError at once."""
+        self._only_128("step_launch")
         if self.release:
             raise ValueError("step_launch does not release pages below a window: this cache was made with window= and release on")
         counts, max_seq_len, pps = self._step_args(next_counts, max_seq_len)

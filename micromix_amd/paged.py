@@ -18,7 +18,7 @@ import torch
 from . import _lib
 from ._args import _check_tensor, _launch, _lead, _lib_with, _ok, _opt, _out, _ptr, _stream_ptr, _tensor
 
-__all__ = ["kv_append", "rope_kv_append", "rope_kv_append_dense", "rope_qk", "kv_copy_pages", "kv_move_rows", "kv_step", "kv_step_state_ints", "paged_decode", "paged_decode_workspace_bytes", "paged_decode_shared",
+__all__ = ["kv_append", "rope_kv_append", "rope_kv_append_dense", "rope_qk", "kv_copy_pages", "kv_move_rows", "kv_step", "kv_step_state_ints", "paged_decode", "paged_decode_workspace_bytes", "paged_decode_hd64_plan", "paged_decode_hd64_workspace_bytes", "paged_decode_shared",
            "paged_decode_shared_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes", "argmax_rows", "argmax_rows_workspace_bytes",
            "verify_greedy", "sample_rows", "sample_rows_workspace_bytes", "logprob_rows", "logprob_rows_workspace_bytes", "cross_entropy",
            "process_logits", "spec_sample_rows", "spec_sample_rows_workspace_bytes", "chain_candidates", "token_step", "ngram_draft",
@@ -42,11 +42,48 @@ _GATHER = ("mm_kv_gather_dense", "mm_kv_gather_dense", "the gather of a layer's 
 _ROPE = ("mm_rope_prefill", "mm_rope_prefill", "the prefill shape of RoPE + KV append")
 _DENSE_HD64 = ("mm_dense_attention_hd64", "mm_dense_attention_hd64 / mm_rope_qk_hd64", "dense attention and RoPE for 64-wide heads")
 _SHARED = ("mm_paged_decode_shared", "mm_paged_decode_shared", "shared-prefix decode")
+_KV_HD64 = ("mm_paged_decode_hd64", "mm_rope_kv_append_hd64 / mm_paged_decode_hd64", "the paged cache for 64-wide heads")
 
 
 def _kv_bytes(kv_data):
     """an fp8 cache held as torch.float8_e4m3fn, seen as the uint8 tensor the ops take: the same bytes, OCP e4m3fn codes"""
     return kv_data.view(torch.uint8) if isinstance(kv_data, torch.Tensor) and kv_data.dtype is torch.float8_e4m3fn else kv_data
+
+
+_BF16_SHAPE = ("bf16 kv_data (kv_param None) must be [max_pages, L, 2, Hkv, P, 128]; an int4 cache ([..., 64] uint8) and an "
+               "fp8 cache ([..., 128] uint8 / float8_e4m3fn) need their fp16 kv_param")
+
+
+def _cache_head_dim(kv_data, kv_param):
+    """64 for a cache with 64-wide rows (include/micromix_kv_hd64.h), by its last dimension: bf16 [.., 64] with kv_param None, or
+    torch.float8_e4m3fn [.., 64] with its fp16 kv_param -- the dtype has to say fp8 there, because uint8 [.., 64] with a kv_param is the
+    int4 cache of 128-wide heads and stays that.  Otherwise 128.  Shapes and dtypes only: no device is looked at"""
+    if isinstance(kv_data, torch.Tensor) and kv_data.dim() == 6 and kv_data.size(5) == 64:
+        if kv_data.dtype is torch.bfloat16 if kv_param is None else kv_data.dtype is torch.float8_e4m3fn:
+            return 64
+    return 128
+
+
+def _geometry_hd64(kv_data, kv_param, index):
+    """_kv_geometry for a cache _cache_head_dim found 64 wide"""
+    if kv_param is None:
+        if not _ok(kv_data, torch.bfloat16, index):
+            _check_tensor(kv_data, "kv_data", torch.bfloat16)
+            raise RuntimeError(f"kv_data must be on cuda:{index}")
+        kind = _lib.MM_KV_BF16
+    else:
+        kv_data = kv_data.view(torch.uint8)
+        if not (_ok(kv_data, torch.uint8, index) and _ok(kv_param, torch.float16, index)):
+            _check_tensor(kv_data, "kv_data", torch.uint8)
+            _check_tensor(kv_param, "kv_param", torch.float16, kv_data.device)
+            raise RuntimeError(f"kv_data / kv_param must be on cuda:{index}")
+        if tuple(kv_param.shape) != tuple(kv_data.shape[:5]) + (2,):
+            raise RuntimeError("kv_param must be [max_pages, L, 2, Hkv, P, 2] fp16, matching kv_data")
+        kind = _lib.MM_KV_FP8_E4M3
+    if kv_data.size(2) != 2:
+        raise RuntimeError("kv_data for 64-wide heads must be [max_pages, L, 2, Hkv, P, 64] bf16 or float8_e4m3fn")
+    max_pages, L, _, Hkv, P, _ = kv_data.shape
+    return kind, max_pages, L, Hkv, P, kv_data
 
 
 def _kv_geometry(kv_data, kv_param, index):
@@ -58,8 +95,7 @@ def _kv_geometry(kv_data, kv_param, index):
             _check_tensor(kv_data, "kv_data", torch.bfloat16)
             raise RuntimeError(f"kv_data must be on cuda:{index}")
         if kv_data.dim() != 6 or kv_data.size(2) != 2 or kv_data.size(5) != 128:
-            raise RuntimeError("bf16 kv_data (kv_param None) must be [max_pages, L, 2, Hkv, P, 128]; an int4 cache ([..., 64] uint8) and an "
-                               "fp8 cache ([..., 128] uint8 / float8_e4m3fn) need their fp16 kv_param")
+            raise RuntimeError(_BF16_SHAPE)
         kind = _lib.MM_KV_BF16
     else:
         kv_data = _kv_bytes(kv_data)
@@ -77,16 +113,19 @@ def _kv_geometry(kv_data, kv_param, index):
     return kind, max_pages, L, Hkv, P, kv_data
 
 
-def _cache(kv_data, kv_param, dev=None):
+def _cache(kv_data, kv_param, dev=None, hd=128):
     """(device, dtype code, max_pages, L, Hkv, P, kv_data as the C ABI takes it) of a cache that has to lie on `dev`; None: on the
-    device it is found on (an op without a query)"""
+    device it is found on (an op without a query).  hd: what _cache_head_dim said, for the ops that have a 64-wide form; the others
+    refuse such a cache here"""
+    if hd == 128 and kv_param is not None and _cache_head_dim(kv_data, kv_param) == 64:    # bf16 [.., 64]: _kv_geometry's own message
+        raise RuntimeError("this op has no form for a cache with head_dim 64 (kv_data [.., 64] float8_e4m3fn): 128-wide heads only")
     if kv_param is not None:
         kv_data = _kv_bytes(kv_data)
     if dev is None:
         if not (isinstance(kv_data, torch.Tensor) and kv_data.is_cuda):
             _check_tensor(kv_data, "kv_data", torch.uint8 if kv_param is not None else torch.bfloat16)
         dev = kv_data.device
-    return (dev, *_kv_geometry(kv_data, kv_param, dev.index))
+    return (dev, *(_kv_geometry if hd == 128 else _geometry_hd64)(kv_data, kv_param, dev.index))
 
 
 def _page_table(kv_indptr, kv_indices, last_page_len, dev):
@@ -99,15 +138,16 @@ def _page_table(kv_indptr, kv_indices, last_page_len, dev):
     return B
 
 
-def _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, q=None):
+def _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, q=None, hd=128):
     """The common checks of the cache ops that take a page table and a layer: (device, B, Hkv, the C arguments kv_data .. batch that
-    every entry point takes in this order).  The device is q's (bf16, contiguous); an append has no q and takes the cache's."""
-    dev, kind, max_pages, L, Hkv, P, kv_data = _cache(kv_data, kv_param, _lead(q, "q", torch.bfloat16) if q is not None else None)
+    every entry point takes in this order).  The device is q's (bf16, contiguous); an append has no q and takes the cache's.
+    hd = 64: the same for the entries of include/micromix_kv_hd64.h, which take no head_dim"""
+    dev, kind, max_pages, L, Hkv, P, kv_data = _cache(kv_data, kv_param, _lead(q, "q", torch.bfloat16) if q is not None else None, hd)
     B = _page_table(kv_indptr, kv_indices, last_page_len, dev)
     layer_idx = int(layer_idx)
     if not 0 <= layer_idx < L:
         raise RuntimeError(f"layer_idx {layer_idx} outside the cache's {L} layers")
-    return dev, B, Hkv, (_ptr(kv_data), _opt(kv_param), kind, max_pages, L, layer_idx, Hkv, P, 128,
+    return dev, B, Hkv, (_ptr(kv_data), _opt(kv_param), kind, max_pages, L, layer_idx, Hkv, P, *((128,) if hd == 128 else ()),
                          _ptr(kv_indptr), _ptr(kv_indices), _ptr(last_page_len), B)
 
 
@@ -153,15 +193,22 @@ def kv_append(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, k, v, app
     (scale, zero) by the rule of quantize_int_group(x, 4, 128), or -- kv_data [..., 128] uint8 / float8_e4m3fn -- e4m3 codes with a
     power-of-two scale per row and zero = 0 (include/micromix_hip.h, MM_KV_FP8_E4M3).  Runs on the current stream, capture-safe.
     """
-    lib = _lib.load()
-    dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx)
+    hd = _cache_head_dim(kv_data, kv_param)
+    lib = _lib.load() if hd == 128 else _lib_with(*_KV_HD64)
+    dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, hd=hd)
     _tensor(append_indptr, "append_indptr", torch.int32, dev)
     _tensor(k, "k", torch.bfloat16, dev)
     _tensor(v, "v", torch.bfloat16, dev)
-    if k.dim() != 3 or k.shape != v.shape or k.size(1) != Hkv or k.size(2) != 128:
-        raise RuntimeError(f"k and v must both be [T, {Hkv}, 128] bf16")
+    if hd == 64:
+        _head_dim_is_64(kv_param, k=k, v=v)
+    if k.dim() != 3 or k.shape != v.shape or k.size(1) != Hkv or k.size(2) != hd:
+        raise RuntimeError(f"k and v must both be [T, {Hkv}, {hd}] bf16")
     if append_indptr.numel() != B + 1:
         raise RuntimeError("append_indptr must have B + 1 entries")
+    if hd == 64:                                             # the copy form of mm_rope_kv_append_hd64: no cos / sin, no q
+        k, v = (t if t.data_ptr() % 16 == 0 else t.clone() for t in (k, v))
+        return _launch("kv_append", dev, lib.mm_rope_kv_append_hd64, *kv_args, None, _ptr(k), _ptr(v), Hkv * 64, Hkv, None, None, 0,
+                       _ptr(append_indptr), k.size(0), None, None, None, _stream_ptr(dev))
     _launch("kv_append", dev, lib.mm_kv_append, *kv_args, _ptr(k), _ptr(v), _ptr(append_indptr), k.size(0), _stream_ptr(dev))
 
 
@@ -1027,6 +1074,8 @@ def rope_kv_append(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, q, k
     token.  Page table, append_indptr and the three cache kinds (int4, fp8 e4m3, bf16) as in `kv_append`.  Runs on the current stream,
     capture-safe.
     """
+    if _cache_head_dim(kv_data, kv_param) == 64:
+        return _rope_kv_append_hd64(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, q, k, v, cos, sin, append_indptr, layer_idx, False)
     lib = _lib.load()
     dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx)
     _tensor(append_indptr, "append_indptr", torch.int32, dev)
@@ -1048,6 +1097,8 @@ def rope_kv_append_dense(kv_data, kv_param, kv_indptr, kv_indices, last_page_len
     fp8 code * 2^e, for int4 bf16(code * scale - zero), computed in fp32: the bf16 tensor the reference's quantize_int_group returns.
     Inputs are read in place when their strides are multiples of 8 elements and their pointers 16-byte aligned, and copied once
     otherwise.  Runs on the current stream, capture-safe."""
+    if _cache_head_dim(kv_data, kv_param) == 64:
+        return _rope_kv_append_hd64(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, q, k, v, cos, sin, append_indptr, layer_idx, True)
     lib = _lib_with(*_ROPE)
     dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx)
     _tensor(append_indptr, "append_indptr", torch.int32, dev)
@@ -1061,6 +1112,38 @@ def rope_kv_append_dense(kv_data, kv_param, kv_indptr, kv_indices, last_page_len
     _launch("rope_kv_append_dense", dev, lib.mm_rope_prefill, *kv_args, _ptr(q), _ptr(k), _ptr(v), sq, Hq, _ptr(cos), _ptr(sin), sc,
             _ptr(append_indptr), T, _ptr(q_rot), _ptr(k_seen), _opt(v_seen), _stream_ptr(dev))
     return q_rot, k_seen, v_seen if v_seen is not None else v_given
+
+
+def _rope_kv_append_hd64(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, q, k, v, cos, sin, append_indptr, layer_idx, dense):
+    """`rope_kv_append` (dense False: returns q_rot) and `rope_kv_append_dense` (True: (q_rot, k_seen, v_seen)) over a cache with 64-wide
+    rows: one kernel, mm_rope_kv_append_hd64 (include/micromix_kv_hd64.h), serves both.  q, k, v [T, H, 64], cos, sin [T, 64]: a 2-D
+    tensor always means 128, and the operands agree with the cache"""
+    _head_dim_is_64(kv_param, q=q, k=k, v=v)
+    if not all(isinstance(t, torch.Tensor) and t.size(-1) == 64 for t in (cos, sin)):
+        raise RuntimeError("cos and sin must be [T, 64] bf16 for a cache with head_dim 64")
+    lib = _lib_with(*_KV_HD64)
+    dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, hd=64)
+    _tensor(append_indptr, "append_indptr", torch.int32, dev)
+    if append_indptr.numel() != B + 1:
+        raise RuntimeError("append_indptr must have B + 1 entries")
+    v_given = v
+    T, Hq, _, q, k, v, sq, cos, sin, sc = _rope_operands(dev, Hkv, q, k, v, cos, sin, 8, 64)
+    q_rot = torch.empty((T, Hq, 64), dtype=torch.bfloat16, device=dev)
+    k_seen = torch.empty((T, Hkv, 64), dtype=torch.bfloat16, device=dev) if dense else None
+    v_seen = torch.empty((T, Hkv, 64), dtype=torch.bfloat16, device=dev) if dense and kv_param is not None else None
+    _launch("rope_kv_append", dev, lib.mm_rope_kv_append_hd64, *kv_args, _ptr(q), _ptr(k), _ptr(v), sq, Hq, _ptr(cos), _ptr(sin), sc,
+            _ptr(append_indptr), T, _ptr(q_rot), _opt(k_seen), _opt(v_seen), _stream_ptr(dev))
+    return (q_rot, k_seen, v_seen if v_seen is not None else v_given) if dense else q_rot
+
+
+def _head_dim_is_64(kv_param, **operands):
+    """the operands of a call on a cache with head_dim 64 are [.., H, 64]; a bf16 cache [.., 64] met with other operands may as well be
+    a mistaken 128 cache, and the message says both"""
+    for name, t in operands.items():
+        if not (isinstance(t, torch.Tensor) and t.dim() == 3 and t.size(2) == 64):
+            raise RuntimeError((_BF16_SHAPE + " -- or, for 64-wide heads, [max_pages, L, 2, Hkv, P, 64]: then " if kv_param is None else "") +
+                               f"{name} must be [.., H, 64] bf16: the cache has head_dim 64, the operands agree with it, and a 2-D tensor "
+                               "always means 128-wide heads")
 
 
 def rope_qk(q, k, cos, sin):
@@ -1101,12 +1184,29 @@ def _window(window):
     return window
 
 
+def paged_decode_hd64_workspace_bytes(B, Hq, Hkv, max_seq_len):
+    """`paged_decode_workspace_bytes` for a cache with head_dim 64 (include/micromix_kv_hd64.h), which has no window form: that
+    function takes no cache to tell the two apart by"""
+    return int(_lib_with(*_KV_HD64).mm_paged_decode_hd64_workspace_bytes(int(B), int(Hq), int(Hkv), int(max_seq_len)))
+
+
 def paged_decode_workspace_bytes(B, Hq, Hkv, max_seq_len, window=None):
-    """bytes of fp32 scratch paged_decode needs for this bound and window (0: one launch, no workspace)"""
+    """bytes of fp32 scratch paged_decode needs for this bound and window (0: one launch, no workspace); over a cache with head_dim 64:
+    `paged_decode_hd64_workspace_bytes`"""
     window = _window(window)
     if not window:
         return int(_lib.load().mm_paged_decode_workspace_bytes(int(B), int(Hq), int(Hkv), int(max_seq_len)))
     return int(_lib.load().mm_paged_decode_window_workspace_bytes(int(B), int(Hq), int(Hkv), int(max_seq_len), window))
+
+
+def paged_decode_hd64_plan(B, Hkv, max_seq_len):
+    """(chunks, chunk_len) of `paged_decode` over a cache with head_dim 64 for these host values (include/micromix_kv_hd64.h,
+    mm_paged_decode_hd64_split): chunk c of a sequence is its tokens [c * chunk_len, (c + 1) * chunk_len), the last chunk to the end"""
+    nc, cl = ctypes.c_int(0), ctypes.c_int(0)
+    st = _lib_with(*_KV_HD64).mm_paged_decode_hd64_split(int(B), int(Hkv), int(max_seq_len), ctypes.byref(nc), ctypes.byref(cl))
+    if st:
+        _lib.check(st, "paged_decode_hd64_plan")
+    return nc.value, cl.value
 
 
 def _max_seq_len(max_seq_len):
@@ -1129,8 +1229,24 @@ def paged_decode(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, lay
     The cache is int4, fp8 (e4m3) or bf16, told apart as in `kv_append`; over an fp8 cache the result equals, bit for bit, that over a
     bf16 cache holding the dequantized values.
     """
-    lib = _lib.load()
     window = _window(window)
+    if _cache_head_dim(kv_data, kv_param) == 64:
+        if window:
+            raise ValueError(f"paged_decode has no sliding-window form for head_dim 64 (window={window})")
+        _head_dim_is_64(kv_param, q=q)
+        lib = _lib_with(*_KV_HD64)
+        dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, q, 64)
+        if q.size(0) != B:
+            raise RuntimeError(f"q must be [B = {B}, Hq, 64] bf16")
+        Hq = _head_groups(q.size(1), Hkv)
+        max_seq_len = _max_seq_len(max_seq_len)
+        need = paged_decode_hd64_workspace_bytes(B, Hq, Hkv, max_seq_len) if B else 0
+        workspace, ws_args = _kv_workspace(workspace, need, dev)
+        o = torch.empty((B, Hq, 64), dtype=torch.bfloat16, device=dev)
+        _launch("paged_decode", dev, lib.mm_paged_decode_hd64, _ptr(q), *kv_args, Hq, max_seq_len, _sm_scale(sm_scale, 64), *ws_args, _ptr(o),
+                _stream_ptr(dev))
+        return o
+    lib = _lib.load()
     dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, q)
     Hq = _query_heads(q, Hkv, B)
     max_seq_len = _max_seq_len(max_seq_len)
