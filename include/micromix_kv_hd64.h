@@ -68,8 +68,8 @@
  * kv_param (fp8) or page-table array; q, o or kv_data not 16-byte aligned; kv_param or an int32 array not 4-byte aligned; a workspace
  * that is needed and null, smaller than mm_paged_decode_hd64_workspace_bytes or not 16-byte aligned.
  *
- * Out of scope: int4 for 64-wide rows; the sliding-window, shared-prefix, tree and multi-token (mm_paged_prefill) forms;
- * mm_dense_attention_prefix / mm_kv_gather_dense, mm_kv_copy_pages and mm_kv_move_rows for 64-wide rows.
+ * Out of scope: int4 for 64-wide rows; the sliding-window, shared-prefix and tree forms (the causal multi-token form is
+ * micromix_kv_prefill_hd64.h's); mm_dense_attention_prefix / mm_kv_gather_dense, mm_kv_copy_pages and mm_kv_move_rows for 64-wide rows.
  */
 #ifndef MICROMIX_KV_HD64_H
 #define MICROMIX_KV_HD64_H

@@ -25,7 +25,7 @@ SOURCES = ["capi.hip", "reorder_quantize.hip", "direct_quantize.hip", "rmsnorm_q
            "mx_gemm_tiles_small.hip", "mx_gemm_skinny.hip", "mx_gemm_stream.hip", "qlinear_decode.hip",
            "kv_cache.hip", "kv_prefill.hip", "rope_append.hip", "kv_copy.hip", "kv_move.hip", "verify.hip", "sample.hip", "moe.hip", "calib_stats.hip", "logprob.hip",
            "logits_process.hip", "spec_sample.hip", "kv_step.hip", "token_step.hip", "random.hip", "dense_attention.hip", "rope_prefill.hip", "kv_gather.hip",
-           "dense_attention_hd64.hip", "kv_hd64.hip"]
+           "dense_attention_hd64.hip", "kv_hd64.hip", "kv_prefill_hd64.hip"]
 DIAG_SOURCES = ["diag.hip"]
 HEADERS = ["mx_common.h", "mx_kernels.h", "mx_acc_regs.h", "mx_gemm_tile.inc", "kv_decode_tiles.inc", "mx_group_convert.h", "mx_instrument.h", "mx_direct_convert.h", "mx_decode_quant.h", "mx_rms_convert.h", "mx_gemm_prelude.h", "mx_paged_kv.h", "mx_kv_shared_host.h", "mx_buffer_ops.h", "mx_gemm_plan.h", "mx_stream_plan.h", "mx_quant_plan.h", "mx_launch_shape.h", "mx_decode_quant_sizes.h", "mx_argmax_key.h", "mx_row_weights.h", "mx_sample_select.h", "mx_spec_rule.h", "mx_rope.h", "mx_kv_hd64.h",
            os.path.join("..", "..", "include", "micromix_hip.h"), os.path.join("..", "..", "include", "micromix_diag.h"),
@@ -35,14 +35,16 @@ HEADERS = ["mx_common.h", "mx_kernels.h", "mx_acc_regs.h", "mx_gemm_tile.inc", "
            os.path.join("..", "..", "include", "micromix_random.h"), os.path.join("..", "..", "include", "micromix_attention.h"),
            os.path.join("..", "..", "include", "micromix_rope.h"), os.path.join("..", "..", "include", "micromix_attention_window.h"),
            os.path.join("..", "..", "include", "micromix_attention_prefix.h"), os.path.join("..", "..", "include", "micromix_kvgather.h"),
-           os.path.join("..", "..", "include", "micromix_attention_hd64.h"), os.path.join("..", "..", "include", "micromix_kv_hd64.h")]
+           os.path.join("..", "..", "include", "micromix_attention_hd64.h"), os.path.join("..", "..", "include", "micromix_kv_hd64.h"),
+           os.path.join("..", "..", "include", "micromix_kv_prefill_hd64.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 # flags of single sources, after FLAGS.  dense_attention.hip: its fp32 softmax and rescaling stay one operation per lane and instruction;
 # the compiler does not pair them into packed fp32 instructions (the host pass does not know the feature and says that it ignores it).
 # rope_prefill.hip: the same for its bf16-rounded products and sums, sixteen elements to a lane; kv_gather.hip: for its code * scale - zero
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SOURCE_FLAGS = {"dense_attention.hip": _NO_PACKED_FP32, "rope_prefill.hip": _NO_PACKED_FP32, "kv_gather.hip": _NO_PACKED_FP32,
-                "dense_attention_hd64.hip": _NO_PACKED_FP32}       # both of the first two reasons: its softmax and its RoPE
+                "dense_attention_hd64.hip": _NO_PACKED_FP32,       # both of the first two reasons: its softmax and its RoPE
+                "kv_prefill_hd64.hip": _NO_PACKED_FP32}            # the first: paired, its 128-row bf16 kernel spills at four waves per SIMD
 
 
 def hipcc() -> str:

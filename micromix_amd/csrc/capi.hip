@@ -12,6 +12,7 @@
 #include "../../include/micromix_attention_prefix.h"
 #include "../../include/micromix_attention_hd64.h"
 #include "../../include/micromix_kv_hd64.h"
+#include "../../include/micromix_kv_prefill_hd64.h"
 #include "../../include/micromix_kvgather.h"
 #include "../../include/micromix_rope.h"
 #include "mx_common.h"
@@ -1096,6 +1097,45 @@ int mm_paged_decode_hd64(const void *q_bf16, const void *kv_data, const void *kv
     if (need && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15))) return MM_ERR_BAD_ARG;
     hipError_t e = mm::launch_paged_decode_hd64(kv, q_bf16, num_qo_heads, max_seq_len, sm_scale, workspace, o_bf16, (hipStream_t)stream);
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_paged_decode_hd64");
+}
+
+// ---- causal multi-token attention over that cache (kv_prefill_hd64.hip, include/micromix_kv_prefill_hd64.h)
+size_t mm_paged_prefill_hd64_workspace_bytes(int num_tokens, int batch, int num_qo_heads, int num_kv_heads, int max_seq_len) {
+    if (num_tokens <= 0 || batch <= 0 || batch > 65535 || num_kv_heads <= 0 || num_kv_heads > 65535 || num_qo_heads <= 0 || max_seq_len < 0 ||
+        num_qo_heads % num_kv_heads || num_qo_heads / num_kv_heads > 16)
+        return 0;
+    return mm::kv_prefill_hd64_workspace_bytes(num_tokens, batch, num_qo_heads, num_kv_heads, max_seq_len);
+}
+
+int mm_paged_prefill_hd64_plan(int num_tokens, int batch, int num_qo_heads, int num_kv_heads, int max_seq_len, int *rows,
+                               int *tile_tokens, int *tiles, int *chunks, int *chunk_len) {
+    if (num_tokens < 0 || batch < 1 || num_kv_heads < 1 || num_qo_heads < 1 || num_qo_heads % num_kv_heads || max_seq_len < 0 || !rows ||
+        !tile_tokens || !tiles || !chunks || !chunk_len)
+        return MM_ERR_BAD_ARG;
+    if (num_qo_heads / num_kv_heads > 16) return MM_ERR_UNSUPPORTED;
+    mm::kv_prefill_hd64_plan(num_tokens, batch, num_qo_heads, num_kv_heads, max_seq_len, rows, tile_tokens, tiles, chunks, chunk_len);
+    return MM_OK;
+}
+
+int mm_paged_prefill_hd64(const void *q_bf16, const int32_t *qo_indptr, int num_tokens, const void *kv_data, const void *kv_param,
+                          int kv_dtype, int max_pages, int num_layers, int layer, int num_kv_heads, int page_size,
+                          const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_len, int batch, int num_qo_heads,
+                          int max_seq_len, float sm_scale, void *workspace, size_t workspace_bytes, void *o_bf16, mm_stream_t stream) {
+    mm::PagedKV kv;
+    const int st = kv_geometry_hd64(kv_data, kv_param, kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size, kv_indptr, kv_indices,
+                                    last_page_len, batch, &kv);
+    if (st == MM_ERR_BAD_ARG) return st;
+    if (num_qo_heads < 1 || num_qo_heads % num_kv_heads || max_seq_len < 0 || num_tokens < 0) return MM_ERR_BAD_ARG;
+    if (st) return st;
+    if (num_qo_heads / num_kv_heads > 16) return MM_ERR_UNSUPPORTED;
+    if (num_tokens == 0 || batch == 0) return MM_OK;
+    if (!q_bf16 || !qo_indptr || !kv_pointers(kv) || !o_bf16) return MM_ERR_BAD_ARG;
+    if ((((uintptr_t)q_bf16 | (uintptr_t)o_bf16) & 15) || !kv_aligned_hd64(kv) || ((uintptr_t)qo_indptr & 3)) return MM_ERR_BAD_ARG;
+    const size_t need = mm::kv_prefill_hd64_workspace_bytes(num_tokens, batch, num_qo_heads, num_kv_heads, max_seq_len);
+    if (need && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15))) return MM_ERR_BAD_ARG;
+    hipError_t e = mm::launch_paged_prefill_hd64(kv, q_bf16, qo_indptr, num_tokens, num_qo_heads, max_seq_len, sm_scale, workspace, o_bf16,
+                                                 (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_paged_prefill_hd64");
 }
 
 // ---- a layer's cache rows as contiguous bf16 (kv_gather.hip, include/micromix_kvgather.h)

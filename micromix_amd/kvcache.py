@@ -20,8 +20,8 @@ attention that equals, bit for bit, attention over a bf16 cache of the dequantiz
     cache = PagedKVCache(..., kind="bf16", head_dim=64)   # Llama-3.2-1B / Qwen2.5-0.5B: rows of 64 (include/micromix_kv_hd64.h)
 
 With `head_dim=64` (kinds "bf16" and "fp8_e4m3"; q, k, v [.., H, 64], cos / sin [T, 64]) `extend`, `append`, `append_rope`,
-`prefill_fresh`, `attend`, `truncate` and `reset` work; everything that needs a 128-only kernel -- a window, `fork`, `attend(shared=True)`,
-`attend_new`, `attend_new_dense`, `tree_mask`, `accept`, the verify and step family -- raises ValueError naming head_dim 64.
+`prefill_fresh`, `attend`, `attend_new` (include/micromix_kv_prefill_hd64.h; without `tree=`), `truncate` and `reset` work; everything that
+needs a 128-only kernel -- a window, `fork`, `attend(shared=True)`, `attend_new(tree=)`, `attend_new_dense`, `tree_mask`, `accept`, the verify and step family -- raises ValueError naming head_dim 64.
 
 The page table lives in device tensors of fixed capacity that `extend` rewrites in place, so `append` + `attend` (or `attend_new`) captured once into a
 hipGraph replay correctly after later `extend` calls, as long as T stays the same and the sequences stay within the captured
@@ -240,7 +240,7 @@ class PagedKVCache:
         """the methods whose kernels exist for 128-wide heads only refuse a head_dim 64 cache here, before any device work"""
         if self.head_dim == 64:
             raise ValueError(f"{what} has no form for head_dim 64: its kernel is 128-only (extend, append, append_rope, prefill_fresh, "
-                             "attend, truncate and reset work)")
+                             "attend, attend_new, truncate and reset work)")
 
     def _upload_gather_indptr(self):
         """gather_indptr from the host lengths: the one table no device step writes, so whoever renews the lengths (_upload, sync) calls this"""
@@ -756,8 +756,13 @@ class PagedKVCache:
         max_seq_len as in `attend`.
         tree: the mask `tree_mask()` returned (int64 [num_new_tokens]): the new tokens are tree drafts, and a token attends the
         committed tokens, its ancestors among the new ones and itself (the module docstring, "Tree drafts").  ValueError on a cache
-        made with window=."""
-        self._only_128("attend_new")
+        made with window=.
+        head_dim 64: q bf16 [num_new_tokens, Hq, 64]; tree= stays refused."""
+        if self.head_dim == 64:
+            if tree is not None:
+                self._only_128("attend_new(tree=)")
+            if not (isinstance(q, torch.Tensor) and q.dim() == 3 and q.dtype is torch.bfloat16 and q.size(2) == 64):
+                raise ValueError("attend_new on a cache with head_dim 64 takes q as a bf16 tensor [num_new_tokens, Hq, 64]")
         if tree is not None and self.window:
             raise ValueError(f"attend_new(tree=) has no sliding-window form: this cache was made with window={self.window}")
         if q.dim() != 3 or q.size(0) != self.num_new_tokens:
@@ -765,7 +770,10 @@ class PagedKVCache:
         if max_seq_len is None:
             self._host("attend_new without max_seq_len")
         bound = max(self.seq_lens) if max_seq_len is None else int(max_seq_len)
-        need = mixedgemm.paged_prefill_workspace_bytes(self.num_new_tokens, self.batch, q.size(1), self.num_kv_heads, bound, self.window)
+        if self.head_dim == 64:
+            need = mixedgemm.paged_prefill_hd64_workspace_bytes(self.num_new_tokens, self.batch, q.size(1), self.num_kv_heads, bound)
+        else:
+            need = mixedgemm.paged_prefill_workspace_bytes(self.num_new_tokens, self.batch, q.size(1), self.num_kv_heads, bound, self.window)
         if need and (self._prefill_workspace is None or self._prefill_workspace.numel() < need):
             if self._prefill_workspace is not None:
                 self._retired.append(self._prefill_workspace)      # a graph captured earlier may still point at it

@@ -1,5 +1,6 @@
 """The paged KV cache and what runs over it, as `mixedgemm` exports it: append (with RoPE), page copy and row moves, decode, shared-prefix
-decode and prefill attention (include/micromix_hip.h, mm_kv_append .. mm_paged_prefill_tree), `dense_attention` over contiguous q, k, v
+decode and prefill attention (include/micromix_hip.h, mm_kv_append .. mm_paged_prefill_tree; over a cache with 64-wide rows
+include/micromix_kv_hd64.h and micromix_kv_prefill_hd64.h: append, decode, prefill), `dense_attention` over contiguous q, k, v
 without a cache (include/micromix_attention.h), the end of a speculative step:
 `process_logits` (include/micromix_logits.h) -> `argmax_rows` / `sample_rows` / `spec_sample_rows` (include/micromix_spec.h; `uniform_rows`,
 include/micromix_random.h, makes their uniform numbers from the request's seed and the position) ->
@@ -19,7 +20,7 @@ from . import _lib
 from ._args import _check_tensor, _launch, _lead, _lib_with, _ok, _opt, _out, _ptr, _stream_ptr, _tensor
 
 __all__ = ["kv_append", "rope_kv_append", "rope_kv_append_dense", "rope_qk", "kv_copy_pages", "kv_move_rows", "kv_step", "kv_step_state_ints", "paged_decode", "paged_decode_workspace_bytes", "paged_decode_hd64_plan", "paged_decode_hd64_workspace_bytes", "paged_decode_shared",
-           "paged_decode_shared_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes", "argmax_rows", "argmax_rows_workspace_bytes",
+           "paged_decode_shared_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes", "paged_prefill_hd64_plan", "paged_prefill_hd64_workspace_bytes", "argmax_rows", "argmax_rows_workspace_bytes",
            "verify_greedy", "sample_rows", "sample_rows_workspace_bytes", "logprob_rows", "logprob_rows_workspace_bytes", "cross_entropy",
            "process_logits", "spec_sample_rows", "spec_sample_rows_workspace_bytes", "chain_candidates", "token_step", "ngram_draft",
            "ngram_draft_workspace_bytes", "uniform_rows", "dense_attention", "dense_attention_window", "dense_attention_prefix",
@@ -43,6 +44,7 @@ _ROPE = ("mm_rope_prefill", "mm_rope_prefill", "the prefill shape of RoPE + KV a
 _DENSE_HD64 = ("mm_dense_attention_hd64", "mm_dense_attention_hd64 / mm_rope_qk_hd64", "dense attention and RoPE for 64-wide heads")
 _SHARED = ("mm_paged_decode_shared", "mm_paged_decode_shared", "shared-prefix decode")
 _KV_HD64 = ("mm_paged_decode_hd64", "mm_rope_kv_append_hd64 / mm_paged_decode_hd64", "the paged cache for 64-wide heads")
+_KV_PREFILL_HD64 = ("mm_paged_prefill_hd64", "mm_paged_prefill_hd64", "multi-token attention over the paged cache for 64-wide heads")
 
 
 def _kv_bytes(kv_data):
@@ -1311,6 +1313,26 @@ def paged_prefill_workspace_bytes(T, B, Hq, Hkv, max_seq_len, window=None):
     return int(_lib.load().mm_paged_prefill_window_workspace_bytes(int(T), int(B), int(Hq), int(Hkv), int(max_seq_len), window))
 
 
+def paged_prefill_hd64_workspace_bytes(T, B, Hq, Hkv, max_seq_len):
+    """`paged_prefill_workspace_bytes` for a cache with head_dim 64 (include/micromix_kv_prefill_hd64.h), which has no window form: that
+    function takes no cache to tell the two apart by"""
+    return int(_lib_with(*_KV_PREFILL_HD64).mm_paged_prefill_hd64_workspace_bytes(int(T), int(B), int(Hq), int(Hkv), int(max_seq_len)))
+
+
+PrefillHd64Plan = namedtuple("PrefillHd64Plan", "rows tile_tokens tiles chunks chunk_len")
+
+
+def paged_prefill_hd64_plan(T, B, Hq, Hkv, max_seq_len):
+    """(rows, tile_tokens, tiles, chunks, chunk_len) of `paged_prefill` over a cache with head_dim 64 for these host values
+    (include/micromix_kv_prefill_hd64.h, mm_paged_prefill_hd64_plan): the (token, head) rows of a workgroup (128, or 64 for few tokens
+    per sequence), the query tokens of one sequence in a tile, the tile count, and the split of the positions into chunks"""
+    out = [ctypes.c_int(0) for _ in range(5)]
+    st = _lib_with(*_KV_PREFILL_HD64).mm_paged_prefill_hd64_plan(int(T), int(B), int(Hq), int(Hkv), int(max_seq_len), *map(ctypes.byref, out))
+    if st:
+        _lib.check(st, "paged_prefill_hd64_plan")
+    return PrefillHd64Plan(*(v.value for v in out))
+
+
 def paged_prefill(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, qo_indptr, layer_idx, max_seq_len, sm_scale=None,
                   workspace=None, *, window=None, tree_mask=None):
     """Causal GQA attention of T new query tokens over layer `layer_idx` of a paged cache: q bf16 [T, Hq, 128] -> o bf16 [T, Hq, 128].
@@ -1330,9 +1352,30 @@ def paged_prefill(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, qo
     together with `tree_mask` is a ValueError.  The tensor is read by the kernel only, so a captured graph replays with other trees
     written into it.  `PagedKVCache.tree_mask` builds the words from parent indices.
     The cache is int4, fp8 (e4m3) or bf16, told apart as in `kv_append`; fp8 runs p.V on bf16(p * scale_v) times the codes, as int4.
+    A cache with head_dim 64 (include/micromix_kv_prefill_hd64.h, a kernel of its own): q [T, Hq, 64] -> o [T, Hq, 64], sm_scale
+    defaults to 1/sqrt(64), the workspace is paged_prefill_hd64_workspace_bytes(...), over an fp8 cache the result equals, bit for bit,
+    that over a bf16 cache of the dequantized values, and `window` or `tree_mask` is a ValueError.
     """
-    lib = _lib.load() if tree_mask is None else _lib_with(*_TREE)
     window = _window(window)
+    if _cache_head_dim(kv_data, kv_param) == 64:
+        if window or tree_mask is not None:
+            raise ValueError("paged_prefill has no sliding-window and no tree-mask form for head_dim 64 "
+                             f"(window={window}, tree_mask {'given' if tree_mask is not None else 'None'})")
+        _head_dim_is_64(kv_param, q=q)
+        lib = _lib_with(*_KV_PREFILL_HD64)
+        dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, q, 64)
+        _tensor(qo_indptr, "qo_indptr", torch.int32, dev)
+        if qo_indptr.numel() != B + 1:
+            raise RuntimeError("qo_indptr must have B + 1 entries (B = last_page_len.numel())")
+        T, Hq = q.size(0), _head_groups(q.size(1), Hkv)
+        max_seq_len = _max_seq_len(max_seq_len)
+        need = paged_prefill_hd64_workspace_bytes(T, B, Hq, Hkv, max_seq_len) if B and T else 0
+        workspace, ws_args = _kv_workspace(workspace, need, dev)
+        o = torch.empty((T, Hq, 64), dtype=torch.bfloat16, device=dev)
+        _launch("paged_prefill", dev, lib.mm_paged_prefill_hd64, _ptr(q), _ptr(qo_indptr), T, *kv_args, Hq, max_seq_len,
+                _sm_scale(sm_scale, 64), *ws_args, _ptr(o), _stream_ptr(dev))
+        return o
+    lib = _lib.load() if tree_mask is None else _lib_with(*_TREE)
     if window and tree_mask is not None:
         raise ValueError("paged_prefill has no sliding-window form of the tree mask: pass window or tree_mask, not both")
     dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx, q)
