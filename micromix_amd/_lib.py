@@ -154,6 +154,8 @@ _KV_HD64_PROTOS, KV_HD64_EXPORTS, KV_HD64 = _read("micromix_kv_hd64.h")
 # KV_PREFILL_HD64_EXPORTS: the entries of include/micromix_kv_prefill_hd64.h, likewise; KV_PREFILL_HD64 holds the rows of its two
 # instantiations and its kv tile by name
 _KV_PREFILL_HD64_PROTOS, KV_PREFILL_HD64_EXPORTS, KV_PREFILL_HD64 = _read("micromix_kv_prefill_hd64.h")
+# DECODE_STEP_EXPORTS: the entries of include/micromix_decode_step.h, likewise; the header defines no constant
+_DECODE_STEP_PROTOS, DECODE_STEP_EXPORTS, _ = _read("micromix_decode_step.h")
 
 _lib = None
 
@@ -169,7 +171,8 @@ def load():
             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
     for protos in (_PROTOS, _CALIB_PROTOS, _LOGPROB_PROTOS, _LOGITS_PROTOS, _SPEC_PROTOS, _KVSTEP_PROTOS, _TOKENS_PROTOS, _RANDOM_PROTOS, _ATTENTION_PROTOS, _ROPE_PROTOS,
-                   _ATTENTION_WINDOW_PROTOS, _ATTENTION_PREFIX_PROTOS, _KVGATHER_PROTOS, _ATTENTION_HD64_PROTOS, _KV_HD64_PROTOS, _KV_PREFILL_HD64_PROTOS):
+                   _ATTENTION_WINDOW_PROTOS, _ATTENTION_PREFIX_PROTOS, _KVGATHER_PROTOS, _ATTENTION_HD64_PROTOS, _KV_HD64_PROTOS, _KV_PREFILL_HD64_PROTOS,
+                   _DECODE_STEP_PROTOS):
         _bind(lib, protos)
     _lib = lib
     return _lib

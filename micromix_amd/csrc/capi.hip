@@ -15,6 +15,7 @@
 #include "../../include/micromix_kv_prefill_hd64.h"
 #include "../../include/micromix_kvgather.h"
 #include "../../include/micromix_rope.h"
+#include "../../include/micromix_decode_step.h"
 #include "mx_common.h"
 #include "mx_kernels.h"
 #include "mx_kv_hd64.h"
@@ -1273,6 +1274,36 @@ int mm_paged_decode(const void *q_bf16, const void *kv_data, const void *kv_para
                     size_t workspace_bytes, void *o_bf16, mm_stream_t stream) {
     return mm_paged_decode_window(q_bf16, kv_data, kv_param, kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size, head_dim, kv_indptr,
                                   kv_indices, last_page_len, batch, num_qo_heads, max_seq_len, sm_scale, workspace, workspace_bytes, o_bf16, stream, 0);
+}
+
+// one decode step in one launch (decode_step.hip, include/micromix_decode_step.h): the statuses of mm_rope_kv_append and mm_paged_decode,
+// the workspace of the latter
+size_t mm_rope_append_decode_workspace_bytes(int batch, int num_qo_heads, int num_kv_heads, int max_seq_len) {
+    return mm_paged_decode_workspace_bytes(batch, num_qo_heads, num_kv_heads, max_seq_len);
+}
+
+int mm_rope_append_decode(void *kv_data, void *kv_param, int kv_dtype, int max_pages, int num_layers, int layer, int num_kv_heads,
+                          int page_size, int head_dim, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_len,
+                          int batch, const void *q_bf16, const void *k_bf16, const void *v_bf16, int64_t qkv_token_stride,
+                          int num_qo_heads, const void *cos_bf16, const void *sin_bf16, int64_t cs_token_stride, int max_seq_len,
+                          float sm_scale, void *workspace, size_t workspace_bytes, void *q_out_bf16, void *o_bf16, mm_stream_t stream) {
+    mm::PagedKV kv;
+    if (int st = kv_geometry(kv_data, kv_param, kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size, head_dim, kv_indptr, kv_indices,
+                             last_page_len, batch, &kv)) return st;
+    if (num_qo_heads <= 0 || num_qo_heads % num_kv_heads || max_seq_len < 0) return MM_ERR_BAD_ARG;
+    if (qkv_token_stride < (int64_t)num_qo_heads * 128 || cs_token_stride < 128 || (qkv_token_stride & 1) || (cs_token_stride & 1))
+        return MM_ERR_BAD_ARG;
+    if (num_qo_heads / num_kv_heads > 16) return MM_ERR_UNSUPPORTED;
+    if (batch == 0) return MM_OK;
+    if (!kv_pointers(kv) || !q_bf16 || !k_bf16 || !v_bf16 || !cos_bf16 || !sin_bf16 || !o_bf16) return MM_ERR_BAD_ARG;
+    if (((uintptr_t)q_bf16 | (uintptr_t)k_bf16 | (uintptr_t)v_bf16 | (uintptr_t)cos_bf16 | (uintptr_t)sin_bf16 | (uintptr_t)q_out_bf16 |
+         (uintptr_t)o_bf16) & 3)
+        return MM_ERR_BAD_ARG;
+    const size_t need = mm_rope_append_decode_workspace_bytes(batch, num_qo_heads, num_kv_heads, max_seq_len);
+    if (need && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15))) return MM_ERR_BAD_ARG;
+    hipError_t e = mm::launch_rope_append_decode(kv, q_bf16, k_bf16, v_bf16, qkv_token_stride, num_qo_heads, cos_bf16, sin_bf16, cs_token_stride,
+                                                 max_seq_len, sm_scale, workspace, q_out_bf16, o_bf16, (hipStream_t)stream);
+    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_rope_append_decode");
 }
 
 // shared-prefix decode: the sizes, the split and the workspace rules are mx_kv_shared_host.h's

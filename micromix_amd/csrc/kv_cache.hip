@@ -31,6 +31,7 @@
 #include <stdint.h>
 
 #include "mx_kernels.h"
+#include "mx_kv_decode.h"
 #include "mx_kv_shared_host.h"
 #include "mx_paged_kv.h"
 
@@ -38,11 +39,6 @@ namespace {
 
 using namespace mm::kv;       // the page-table walk, the append rule, the int4 decoding and the chunk merge
 using mm::PagedKV;
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-constexpr int DEC_WAVES = 4;
-constexpr int TILE = 32;           // tokens per wave iteration
 
 // One workgroup per appended token and kv head; wave 0 writes K, wave 1 writes V (the slot and the int4 rule: mx_paged_kv.h).
 template <int KIND>
@@ -55,42 +51,11 @@ __global__ __launch_bounds__(128) void kv_append_kernel(const PagedKV kv, const 
     store_row<KIND>(kv, row, lane, two);
 }
 
-struct DecodeArgs {
-    PagedKV kv;
-    const uint16_t *q;
-    float *ws;                 // partials: o [B, Hkv, nc, g, 128], then (m, l) [B, Hkv, nc, g, 2]
-    uint16_t *o;
-    int Hq, g, nc, chunk;
-    float scale_log2;          // sm_scale * log2(e)
-    int window;                // WINDOW kernels: the query attends its last `window` >= 1 tokens (itself included)
-};
-
-// mm_paged_decode_shared: d is what the tile loop and the merge kernel take, with d.nc = ncA + ncB, the partials of a (sequence, query
-// head) -- prefix chunks first, then tail chunks, one stride; d.chunk and d.window are unused
-struct SharedArgs {
-    DecodeArgs d;
-    const int *group_indptr, *group_members, *shared_len;
-    int ncA, chunkA, ncB, chunkB;
-};
-
-// What a workgroup walks, and for whom:
-//   WALK_ALL     sequence b = blockIdx.z, tokens [0, len_b), its g heads
-//   WALK_WINDOW  sequence b, tokens [lo_b, len_b), lo_b = max(0, len_b - window), chunk c from lo_b + c * chunk on.  The tiles start at
-//                lo_b itself -- a lane addresses its token's row on its own, so a tile need not start on a multiple of 32 -- and no token
-//                below the window is ever looked at: no compare, no page-table read, the span exactly min(len_b, window) tokens
-//   WALK_PREFIX  slot s = blockIdx.z of group_members: live when it is the first of a slab, i.e. a multiple of per = 16 / g positions
-//                into its group; the slab is the group's members from s on, at most per.  Row c of the A operand is member c / g,
-//                head c % g; the walk is [0, min(shared_len, len)) of the slab's first member, over that member's page list.  Always
-//                partials, every row's to its own (sequence, query head, chunk).  A dead slot returns having read the group table only
-//   WALK_SUFFIX  sequence b, tokens [min(shared_len[b], len_b), len_b), the WINDOW shape with the begin read from shared_len.  Always
-//                partials, behind the ncA prefix chunks
-// A member index outside [0, B) is a row without a query and without an output; a bad first member makes the slab's walk empty.
-enum { WALK_ALL = 0, WALK_WINDOW = 1, WALK_PREFIX = 2, WALK_SUFFIX = 3 };
-
 template <int KIND, int GP, bool WINDOW>
 __global__ __launch_bounds__(256) void paged_decode_kernel(const DecodeArgs a) {
     constexpr int WALK = WINDOW ? WALK_WINDOW : WALK_ALL;
     const SharedArgs sh = {};                          // no shared walk here: the branches that read it are discarded
+    const v4u *const step_q = nullptr;                 // nor a q rotated in the launch (WALK_STEP), here and below
 #include "kv_decode_tiles.inc"
 }
 
@@ -99,6 +64,7 @@ template <int KIND>
 __global__ __launch_bounds__(256) void paged_decode_prefix_kernel(const SharedArgs sh) {
     constexpr int WALK = WALK_PREFIX, GP = 16;
     const DecodeArgs &a = sh.d;
+    const v4u *const step_q = nullptr;
 #include "kv_decode_tiles.inc"
 }
 
@@ -106,6 +72,7 @@ template <int KIND, int GP>
 __global__ __launch_bounds__(256) void paged_decode_suffix_kernel(const SharedArgs sh) {
     constexpr int WALK = WALK_SUFFIX;
     const DecodeArgs &a = sh.d;
+    const v4u *const step_q = nullptr;
 #include "kv_decode_tiles.inc"
 }
 
@@ -179,6 +146,11 @@ hipError_t launch_kv_append(const PagedKV &kv, const void *k, const void *v, con
     return hipGetLastError();
 }
 
+hipError_t launch_paged_decode_merge(const kv::DecodeArgs &a, hipStream_t stream) {
+    paged_decode_merge_kernel<<<dim3(a.Hq, a.kv.B), 64, 0, stream>>>(a);
+    return hipGetLastError();
+}
+
 hipError_t launch_paged_decode(const PagedKV &kv, const void *q, int Hq, int max_seq_len, int window, float sm_scale, void *ws, void *o,
                                hipStream_t stream) {
     DecodeArgs a;
@@ -196,8 +168,7 @@ hipError_t launch_paged_decode(const PagedKV &kv, const void *q, int Hq, int max
     else if (kv.kind == KV_FP8) e = window > 0 ? launch_decode_g<KV_FP8, true>(a, stream) : launch_decode_g<KV_FP8, false>(a, stream);
     else e = window > 0 ? launch_decode_g<KV_BF16, true>(a, stream) : launch_decode_g<KV_BF16, false>(a, stream);
     if (e != hipSuccess || a.nc == 1) return e;
-    paged_decode_merge_kernel<<<dim3(Hq, kv.B), 64, 0, stream>>>(a);
-    return hipGetLastError();
+    return launch_paged_decode_merge(a, stream);
 }
 
 hipError_t launch_paged_decode_shared(const PagedKV &kv, const void *q, int Hq, const int *group_indptr, const int *group_members,
@@ -226,9 +197,7 @@ hipError_t launch_paged_decode_shared(const PagedKV &kv, const void *q, int Hq, 
     if (kv.kind == KV_INT4) e = launch_shared_g<KV_INT4>(s, stream);
     else if (kv.kind == KV_FP8) e = launch_shared_g<KV_FP8>(s, stream);
     else e = launch_shared_g<KV_BF16>(s, stream);
-    if (e != hipSuccess) return e;
-    paged_decode_merge_kernel<<<dim3(Hq, kv.B), 64, 0, stream>>>(s.d);
-    return hipGetLastError();
+    return e != hipSuccess ? e : launch_paged_decode_merge(s.d, stream);
 }
 
 }  // namespace mm

@@ -1,5 +1,7 @@
-// The tile loop of the four decode walks (kv_cache.hip: WALK_ALL, WALK_WINDOW, WALK_PREFIX, WALK_SUFFIX), the body of each of its kernels.
-// The including kernel provides: the constants KIND, GP and WALK, `a` (DecodeArgs) and `sh` (SharedArgs; read by the shared walks only).
+// The tile loop of the decode walks (mx_kv_decode.h: WALK_ALL, WALK_WINDOW, WALK_PREFIX, WALK_SUFFIX of kv_cache.hip, WALK_STEP of
+// decode_step.hip), the body of each of their kernels.
+// The including kernel provides: the constants KIND, GP and WALK, `a` (DecodeArgs), `sh` (SharedArgs; read by the shared walks only) and
+// `step_q` (v4u[4], this lane's part of the A operand; read by WALK_STEP only).
 // A textual include rather than a device function: the un-shared kernels then compile to the instructions they had before the shared
 // walks existed, which an inlined function did not give (DESIGN 7i).
     __shared__ float s_p[DEC_WAVES][TILE][16];        // (p * scale) of the tile, [token][head]
@@ -55,7 +57,9 @@
         const v4u *qrow = (const v4u *)(a.q + ((int64_t)qb * a.Hq + (int64_t)kvh * g + qh) * HD + 32 * kq);
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-            v4u w = (WALK == WALK_PREFIX ? live : c < g) ? qrow[s] : v4u{0, 0, 0, 0};
+            v4u w;
+            if constexpr (WALK == WALK_STEP) w = step_q[s];
+            else w = (WALK == WALK_PREFIX ? live : c < g) ? qrow[s] : v4u{0, 0, 0, 0};
             qa[s] = __builtin_bit_cast(v8bf, w);
 #pragma unroll
             for (int j = 0; j < 4; ++j) qsum += bf16f(w[j] & 0xffffu) + bf16f(w[j] >> 16);
@@ -254,7 +258,7 @@
     __syncthreads();
 
     // ---- merge the four waves: thread -> (head, 128 / 2 dims pair)
-    const bool single = WALK <= WALK_WINDOW && a.nc == 1;
+    const bool single = (WALK <= WALK_WINDOW || WALK == WALK_STEP) && a.nc == 1;
     int rows = g;                                      // the rows with an output
     if constexpr (WALK == WALK_PREFIX) rows = members * g;
     for (int idx = threadIdx.x; idx < rows * (HD / 2); idx += 256) {

@@ -296,6 +296,11 @@ hipError_t launch_paged_decode_shared(const PagedKV &kv, const void *q, int Hq, 
 // RoPE + append in one launch (rope_append.hip): q | k | v share the token stride qkv_stride, cos | sin the stride cs_stride (elements)
 hipError_t launch_rope_kv_append(const PagedKV &kv, const void *q, const void *k, const void *v, int64_t qkv_stride, int Hq, const void *cos,
                                  const void *sin, int64_t cs_stride, const int *append_indptr, int T, void *q_out, hipStream_t stream);
+// that launch with one token per sequence and launch_paged_decode (window 0) over the result as one launch (decode_step.hip,
+// include/micromix_decode_step.h); q_out may be null, ws as launch_paged_decode takes it
+hipError_t launch_rope_append_decode(const PagedKV &kv, const void *q, const void *k, const void *v, int64_t qkv_stride, int Hq, const void *cos,
+                                     const void *sin, int64_t cs_stride, int max_seq_len, float sm_scale, void *ws, void *q_out, void *o,
+                                     hipStream_t stream);
 // the same for a prompt's worth of tokens (rope_prefill.hip, include/micromix_rope.h): kv may be null (no cache, Hkv from the argument);
 // k_out / v_out, each optional, receive what a reader of the slot gets back
 hipError_t launch_rope_prefill(const PagedKV *kv, const void *q, const void *k, const void *v, int64_t qkv_stride, int Hq, int Hkv,

@@ -104,15 +104,20 @@ __device__ inline bool k_row(const PagedKV &kv, const int *pages, int t, int end
 // the first position of a window of W >= 1 tokens that ends at position p (HF's sliding_window: max(0, p - W + 1)); p >= -1
 __device__ inline int window_begin(int p, int W) { return p >= W ? p - W + 1 : 0; }
 
+// the K or V row of head h that a token appended at position pos of sequence b (length len) is written to; -1: nothing is written
+__device__ inline int64_t append_row_at(const PagedKV &kv, int b, int pos, int len, int which, int h) {
+    if (pos < 0 || pos >= len) return -1;                     // a table that does not count the appended tokens: nothing written
+    const int page = kv.indices[kv.indptr[b] + pos / kv.P];
+    if (page < 0 || page >= kv.max_pages) return -1;
+    return kv_row(kv, page, which, h, pos % kv.P);
+}
+
 // the K (which = 0) or V (which = 1) row of appended token i, head h; -1: nothing is written for this token
 __device__ inline int64_t append_row(const PagedKV &kv, const int *append_indptr, int i, int which, int h) {
     const int b = find_seq(append_indptr, kv.B, i);
     const int len = seq_len(kv, b);
     const int pos = len - (append_indptr[b + 1] - append_indptr[b]) + (i - append_indptr[b]);
-    if (pos < 0 || pos >= len) return -1;                     // a table that does not count the appended tokens: nothing written
-    const int page = kv.indices[kv.indptr[b] + pos / kv.P];
-    if (page < 0 || page >= kv.max_pages) return -1;
-    return kv_row(kv, page, which, h, pos % kv.P);
+    return append_row_at(kv, b, pos, len, which, h);
 }
 
 // ---- the two quantizing rules, element by element: what store_row (a wave per row) and store_row8 (eight lanes per row) are made of

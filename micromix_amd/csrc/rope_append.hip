@@ -15,7 +15,7 @@
 
 #include "mx_kernels.h"
 #include "mx_paged_kv.h"
-#include "mx_rope.h"              // rope_one: the element rule, shared with rope_prefill.hip
+#include "mx_rope.h"              // rope_one: the element rule, shared with rope_prefill.hip; rope_pair: a wave's row, with decode_step.hip
 
 namespace {
 
@@ -31,15 +31,6 @@ struct RopeArgs {
     int64_t qkv_stride, cs_stride;     // elements per token
     int Hq, g;
 };
-
-// the rotated elements 2 lane, 2 lane + 1 of a row; the whole wave calls it
-__device__ inline uint32_t rope_pair(uint32_t x, uint32_t cs, uint32_t sn, int lane) {
-    // lanes 32..63 of the first operand change places with lanes 0..31 of the second, so in every lane one of the two results is the
-    // dword of lane ^ 32 and the other the lane's own: the xor of the three is the partner's
-    const auto sw = __builtin_amdgcn_permlane32_swap(x, x, false, false);
-    const uint32_t r = sw[0] ^ sw[1] ^ x ^ (lane < 32 ? 0x80008000u : 0u);     // rotate_half: -x[d + 64] below 64, x[d - 64] above
-    return rope_one(x & 0xffffu, r & 0xffffu, cs & 0xffffu, sn & 0xffffu) | (rope_one(x >> 16, r >> 16, cs >> 16, sn >> 16) << 16);
-}
 
 template <int KIND>
 __global__ __launch_bounds__(64 * (2 + MAX_Q_WAVES)) void rope_kv_append_kernel(const RopeArgs a) {

@@ -7,8 +7,10 @@
         o = cache.attend(layer, q)         # q bf16 [B, Hq, 128] -> o bf16 [B, Hq, 128]
         # or, from the q | k | v projection before RoPE, with HF's bf16 cos / sin rows [T, 128]: one launch instead of RoPE + append
         o = cache.attend(layer, cache.append_rope(layer, q, k, v, cos, sin))
+        # or both of those as one launch, the same cache bytes and the same o (include/micromix_decode_step.h; no window, 128-wide heads)
+        o = cache.decode_step(layer, q, k, v, cos, sin)
 
-    cache.extend([300, 512, 5])            # several tokens per sequence: a prompt, a chunk of one, a speculative draft
+    cache.extend([300, 512, 5])           # several tokens per sequence: a prompt, a chunk of one, a speculative draft
     for layer in range(32):
         cache.append(layer, k, v)          # k, v bf16 [T, Hkv, 128], T = 817
         o = cache.attend_new(layer, q)     # q bf16 [T, Hq, 128] -> o bf16 [T, Hq, 128], causal over each sequence's cache
@@ -540,6 +542,36 @@ class PagedKVCache:
             self._workspace = torch.empty((need,), dtype=torch.uint8, device=self.device)
         return mixedgemm.paged_decode(q, self.kv_data, self.kv_param, self.kv_indptr, self.kv_indices, self.last_page_len, layer, bound,
                                       sm_scale=sm_scale, workspace=self._workspace if need else None, window=self.window)
+
+    def decode_step(self, layer, q, k, v, cos, sin, max_seq_len=None, sm_scale=None):
+        """`append_rope` + `attend` of a decode step -- `extend(1)`: one new token per sequence -- in one launch
+        (`mixedgemm.rope_append_decode`): q, k, v, cos, sin as `append_rope` takes them, returns o, bf16 [B, Hq, 128].  The cache bytes
+        and o are the pair's, bit for bit; max_seq_len and sm_scale as in `attend`.  A sequence that has forked is fine: `extend` has
+        given it its own last page.
+        Captured in a hipGraph it took 0.3 to 1.75 us less per layer than the pair at every shape timed (Llama-3-8B heads, int4 / fp8 /
+        bf16, 1 x 4 096 to 64 x 1 024 and 1 x 32 768), most at 64 sequences and bf16 rows, within the spread of the repeats
+        at fp8 1 x 4 096: use it for plain decode steps; the pair stays as it is and remains the way for everything else.
+        ValueError, before any device work, on a cache made with window= or head_dim=64, and when the last `extend` did not announce
+        exactly one token for every sequence."""
+        if self.head_dim == 64:
+            raise ValueError("decode_step has no form for head_dim 64: its kernel is 128-only; use append_rope() and attend()")
+        if self.window:
+            raise ValueError(f"decode_step has no sliding-window form: this cache was made with window={self.window}; use append_rope() "
+                             "and attend()")
+        if self.num_new_tokens != self.batch:
+            raise ValueError(f"decode_step takes one new token for each of the {self.batch} sequences (extend(1)); the last extend "
+                             f"announced {self.num_new_tokens} tokens")
+        if max_seq_len is None:
+            self._host("decode_step without max_seq_len")
+        bound = max(self.seq_lens) if max_seq_len is None else int(max_seq_len)
+        Hq = q.size(1) if q.dim() == 3 else q.size(-1) // HEAD_DIM
+        need = mixedgemm.rope_append_decode_workspace_bytes(self.batch, Hq, self.num_kv_heads, bound)
+        if need and (self._workspace is None or self._workspace.numel() < need):
+            if self._workspace is not None:
+                self._retired.append(self._workspace)      # a graph captured earlier may still point at it
+            self._workspace = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        return mixedgemm.rope_append_decode(self.kv_data, self.kv_param, self.kv_indptr, self.kv_indices, self.last_page_len, q, k, v, cos, sin,
+                                            layer, bound, sm_scale=sm_scale, workspace=self._workspace if need else None)
 
     def tree_mask(self, parents):
         """(mask, depths) of the tokens the last `extend` announced, taken as tree drafts (host work and one upload; a CPU cache works).

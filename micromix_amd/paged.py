@@ -19,7 +19,7 @@ import torch
 from . import _lib
 from ._args import _check_tensor, _launch, _lead, _lib_with, _ok, _opt, _out, _ptr, _stream_ptr, _tensor
 
-__all__ = ["kv_append", "rope_kv_append", "rope_kv_append_dense", "rope_qk", "kv_copy_pages", "kv_move_rows", "kv_step", "kv_step_state_ints", "paged_decode", "paged_decode_workspace_bytes", "paged_decode_hd64_plan", "paged_decode_hd64_workspace_bytes", "paged_decode_shared",
+__all__ = ["kv_append", "rope_kv_append", "rope_kv_append_dense", "rope_append_decode", "rope_append_decode_workspace_bytes", "rope_qk", "kv_copy_pages", "kv_move_rows", "kv_step", "kv_step_state_ints", "paged_decode", "paged_decode_workspace_bytes", "paged_decode_hd64_plan", "paged_decode_hd64_workspace_bytes", "paged_decode_shared",
            "paged_decode_shared_workspace_bytes", "paged_prefill", "paged_prefill_workspace_bytes", "paged_prefill_hd64_plan", "paged_prefill_hd64_workspace_bytes", "argmax_rows", "argmax_rows_workspace_bytes",
            "verify_greedy", "sample_rows", "sample_rows_workspace_bytes", "logprob_rows", "logprob_rows_workspace_bytes", "cross_entropy",
            "process_logits", "spec_sample_rows", "spec_sample_rows_workspace_bytes", "chain_candidates", "token_step", "ngram_draft",
@@ -44,6 +44,7 @@ _ROPE = ("mm_rope_prefill", "mm_rope_prefill", "the prefill shape of RoPE + KV a
 _DENSE_HD64 = ("mm_dense_attention_hd64", "mm_dense_attention_hd64 / mm_rope_qk_hd64", "dense attention and RoPE for 64-wide heads")
 _SHARED = ("mm_paged_decode_shared", "mm_paged_decode_shared", "shared-prefix decode")
 _KV_HD64 = ("mm_paged_decode_hd64", "mm_rope_kv_append_hd64 / mm_paged_decode_hd64", "the paged cache for 64-wide heads")
+_DECODE_STEP = ("mm_rope_append_decode", "mm_rope_append_decode", "the one-launch decode step")
 _KV_PREFILL_HD64 = ("mm_paged_prefill_hd64", "mm_paged_prefill_hd64", "multi-token attention over the paged cache for 64-wide heads")
 
 
@@ -1260,6 +1261,43 @@ def paged_decode(q, kv_data, kv_param, kv_indptr, kv_indices, last_page_len, lay
         _launch("paged_decode", dev, lib.mm_paged_decode_window, *args, _stream_ptr(dev), window)
     else:
         _launch("paged_decode", dev, lib.mm_paged_decode, *args, _stream_ptr(dev))
+    return o
+
+
+def rope_append_decode_workspace_bytes(B, Hq, Hkv, max_seq_len):
+    """bytes of fp32 scratch rope_append_decode needs for this bound: `paged_decode_workspace_bytes` of the same arguments, whatever
+    they are (include/micromix_decode_step.h)"""
+    return int(_lib_with(*_DECODE_STEP).mm_rope_append_decode_workspace_bytes(int(B), int(Hq), int(Hkv), int(max_seq_len)))
+
+
+def rope_append_decode(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, q, k, v, cos, sin, layer_idx, max_seq_len, sm_scale=None,
+                       workspace=None, *, q_out=None):
+    """One decode step of layer `layer_idx` in one launch: `rope_kv_append` with one new token per sequence (append_indptr = 0, 1, .., B)
+    and `paged_decode` of the rotated q over the sequences that now hold it; returns o, bf16 [B, Hq, 128].
+
+    The cache afterwards is `rope_kv_append`'s byte for byte and o is `paged_decode`'s bit for bit, for the same max_seq_len and
+    sm_scale (include/micromix_decode_step.h, mm_rope_append_decode): the workgroup whose chunk holds a sequence's last position writes
+    the row and then walks it as the chain's decode kernel would.  q, k, v, cos, sin as `rope_kv_append` takes them with T = B tokens,
+    token b for sequence b; the page table already counts the token.  `workspace` as in `paged_decode` (the same size:
+    rope_append_decode_workspace_bytes) -- pass one when capturing a graph.  q_out: bf16 [B, Hq, 128] contiguous, receives the rotated
+    q when given.  The three 128-wide cache kinds; no sliding-window, shared-prefix or tree form, one token per sequence, and a cache
+    with head_dim 64 raises ValueError.  Runs on the current stream, capture-safe.
+    """
+    if _cache_head_dim(kv_data, kv_param) == 64:
+        raise ValueError("rope_append_decode has no form for head_dim 64: its kernel is 128-only; use rope_kv_append and paged_decode")
+    lib = _lib_with(*_DECODE_STEP)
+    dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx)
+    T, Hq, _, q, k, v, sq, cos, sin, sc = _rope_operands(dev, Hkv, q, k, v, cos, sin, 2)
+    if T != B:
+        raise RuntimeError(f"rope_append_decode takes one new token per sequence: q, k, v must hold B = {B} tokens, got {T}")
+    max_seq_len = _max_seq_len(max_seq_len)
+    need = rope_append_decode_workspace_bytes(B, Hq, Hkv, max_seq_len) if B else 0
+    workspace, ws_args = _kv_workspace(workspace, need, dev)
+    if q_out is not None:
+        _tensor(q_out, "q_out", torch.bfloat16, dev, (B, Hq, 128))
+    o = torch.empty((B, Hq, 128), dtype=torch.bfloat16, device=dev)
+    _launch("rope_append_decode", dev, lib.mm_rope_append_decode, *kv_args, _ptr(q), _ptr(k), _ptr(v), sq, Hq, _ptr(cos), _ptr(sin), sc,
+            max_seq_len, _sm_scale(sm_scale), *ws_args, _opt(q_out), _ptr(o), _stream_ptr(dev))
     return o
 
 
