@@ -20,7 +20,8 @@
 //   pipeline per tile: wait for the own DMA of tile n, ONE barrier, load the page-table entries of tile n + 2, issue tile n + 1 from
 //            the entries loaded a tile earlier, then the arithmetic of tile n: no load waits on another load.
 //   scores   S^T = K q^T on v_mfma_f32_16x16x32_bf16, A = K by ds_read_b128, B = q in registers for the whole walk
-//   softmax  fp32, log2 domain, the scale folded into the one fma per score, lane-local state, the row max across 4 lanes.  Each row
+//   softmax  fp32, log2 domain, the scores scaled before the max is taken (the largest gives p = 1 exactly), lane-local state, the row
+//            max across 4 lanes.  Each row
 //            has its own diagonal: tiles wholly above the tile's last position are not visited, the compare runs only on tiles that
 //            cross the diagonal of some row of the wave, and a wave whose rows are all masked on a tile skips its arithmetic
 //   p.V      O^T += V^T P^T, A = V by ds_read_b64_tr_b16, B = bf16(p) straight from the score registers
@@ -98,6 +99,15 @@ __device__ __forceinline__ void dma16_global(const uint8_t *src, unsigned lds_ad
 __device__ __forceinline__ v2u read_tr(const uint8_t *p) {
     v2u r = {0u, 0u};
     MM_DEVICE_ONLY(r = __builtin_bit_cast(v2u, __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4 *)p));)
+    return r;
+}
+
+// x * y rounded to fp32 on its own: a product whose use the compiler sees (`x * y`, __fmul_rn) is contracted with a later subtraction into
+// one fma, whose exponent then differs from the rounded product the row max was taken of.  The empty statement makes the product opaque;
+// the multiply itself stays the compiler's to select and schedule
+__device__ __forceinline__ float mul_rounded(float x, float y) {
+    float r = x * y;
+    MM_DEVICE_ONLY(asm("" : "+v"(r));)
     return r;
 }
 
@@ -287,21 +297,28 @@ void paged_prefill_hd64_kernel(const Prefill64 a) {
             v8bf pb[RB][2];
 #pragma unroll
             for (int rb = 0; rb < RB; ++rb) {
+                // The scores are scaled first and the max is taken of the scaled values (7c's order), so the row's largest score gives
+                // p = exp2(0) = 1 exactly, whatever its size.  exp2(fma(score, scale, -max)) with max = fl(score * scale) leaves the
+                // product's rounding error in the exponent of that token: at scores of 2^18 its p is up to 1 +- 0.011, bf16(p) then
+                // differs from the p that went into l, and a row that attends one token returns V (1 +- 2^-8), not V
                 float mt = -INFINITY;
 #pragma unroll
                 for (int blk = 0; blk < 4; ++blk)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) mt = fmaxf(mt, sc[rb][blk][r]);
+                    for (int r = 0; r < 4; ++r) {
+                        sc[rb][blk][r] = mul_rounded(sc[rb][blk][r], a.scale_log2);    // scale_log2 > 0: -inf stays -inf
+                        mt = fmaxf(mt, sc[rb][blk][r]);
+                    }
                 mt = fmaxf(mt, __shfl_xor(mt, 16));
                 mt = fmaxf(mt, __shfl_xor(mt, 32));
-                const float mn = fmaxf(m[rb], mt * a.scale_log2), mb = mn == -INFINITY ? 0.0f : mn, alpha = __builtin_amdgcn_exp2f(m[rb] - mb);
+                const float mn = fmaxf(m[rb], mt), mb = mn == -INFINITY ? 0.0f : mn, alpha = __builtin_amdgcn_exp2f(m[rb] - mb);
                 m[rb] = mn;
                 float ps = 0.0f;
 #pragma unroll
                 for (int blk = 0; blk < 4; ++blk)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        sc[rb][blk][r] = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[rb][blk][r], a.scale_log2, -mb));
+                        sc[rb][blk][r] = __builtin_amdgcn_exp2f(sc[rb][blk][r] - mb);
                         ps += sc[rb][blk][r];
                     }
                 lsum[rb] = lsum[rb] * alpha + ps;

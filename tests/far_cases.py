@@ -137,13 +137,16 @@ KV_MAX_B = 65535
 
 # ---- paged KV pools just over 4 GiB ------------------------------------------------------------------------------------------------
 class FarPool:
-    """a paged cache [max_pages, L, 2, Hkv, P, row_bytes of data] whose data tensor is just over 4 GiB"""
+    """a paged cache [max_pages, L, 2, Hkv, P, row_bytes of data] whose data tensor is just over 4 GiB; hd: the row width in
+    elements, 128, or 64 for the cache of include/micromix_kv_hd64.h (fp8 and bf16 only: 64 and 128 bytes a row)"""
     ROW_BYTES = {"int4": 64, "fp8": 128, "bf16": 256}
 
-    def __init__(self, kind, L=2, Hkv=2, P=16):
-        self.kind, self.L, self.Hkv, self.P = kind, L, Hkv, P
+    def __init__(self, kind, L=2, Hkv=2, P=16, hd=128):
+        assert hd == 128 or (hd == 64 and kind != "int4")
+        self.kind, self.L, self.Hkv, self.P, self.hd = kind, L, Hkv, P, hd
         self.itemsize = 2 if kind == "bf16" else 1
-        self.page_bytes = L * 2 * Hkv * P * self.ROW_BYTES[kind]
+        self.row_bytes = self.ROW_BYTES[kind] * hd // 128
+        self.page_bytes = L * 2 * Hkv * P * self.row_bytes
         self.param_page_bytes = 0 if kind == "bf16" else L * 2 * Hkv * P * 4
         self.first_past_b31 = -(-B31 // self.page_bytes)     # the first page wholly past B31 (it starts there)
         self.first_past_b32 = -(-B32 // self.page_bytes)
@@ -197,6 +200,7 @@ class FarPool:
 
 
 POOLS = {kind: FarPool(kind) for kind in ("int4", "fp8", "bf16")}
+POOLS_HD64 = {kind: FarPool(kind, hd=64) for kind in ("fp8", "bf16")}      # tests/test_far_kv_hd64_gpu.py
 
 
 def param_past_b31_pool_bytes(kind="int4"):

@@ -100,9 +100,11 @@ def v_decode(row):
     return f"seq {vals['seq']} pos {vals['pos']} head {vals['head']}"
 
 
-def describe_mismatch(got, want, labels, bound, grid=True):
+def describe_mismatch(got, want, labels, bound, grid=True, decode=None):
     """None if |got - want| <= bound everywhere, else a message naming the first bad row and (grid: V rows of v_grid) the token its
-    output holds, otherwise its worst dimension; got, want [rows, 128], bound a scalar or an array that broadcasts, labels(i) -> str"""
+    output holds, otherwise its worst dimension; got, want [rows, 128], bound a scalar or an array that broadcasts, labels(i) -> str;
+    decode: what reads a grid row back (v_decode; tests/kv_exact_cases_hd64.py passes the one of its 64-wide grid)"""
+    decode = decode or v_decode
     err = np.abs(np.asarray(got, dtype=np.float64) - want)
     bad = np.flatnonzero(((err > bound) | ~np.isfinite(err)).any(-1))
     if bad.size == 0:
@@ -113,7 +115,7 @@ def describe_mismatch(got, want, labels, bound, grid=True):
         return (f"{bad.size} of {err.shape[0]} rows outside the bound; first: {labels(i)} dim {d} expects {want[i, d]!r}, got "
                 f"{got[i, d]!r} (bound {np.broadcast_to(bound, err.shape)[i, d]:.3e})")
     return (f"{bad.size} of {err.shape[0]} rows outside the bound, worst err {np.nanmax(err):.3e}; first: {labels(i)} expects "
-            f"{v_decode(want[i])}, got {v_decode(got[i])} (err {np.nanmax(err[i]):.3e})")
+            f"{decode(want[i])}, got {decode(got[i])} (err {np.nanmax(err[i]):.3e})")
 
 
 # ---- needle ----------------------------------------------------------------------------------------------------------------

@@ -119,6 +119,36 @@ def test_kv_pools_cross_b31_and_b32_and_wrap_onto_pages_of_the_case():
     table("paged KV pools", lines)
 
 
+def test_kv_pools_of_64_wide_rows_cross_b31_and_b32_and_wrap_onto_pages_of_the_case():
+    """the same proofs for the pools of tests/test_far_kv_hd64_gpu.py: rows of 64 elements, 128 bytes in bf16 and 64 in fp8"""
+    lines = []
+    assert set(fc.POOLS_HD64) == {"fp8", "bf16"}
+    for kind, pool in fc.POOLS_HD64.items():
+        assert pool.hd == 64 and pool.row_bytes == {"bf16": 128, "fp8": 64}[kind] and 2 * pool.page_bytes == fc.POOLS[kind].page_bytes
+        assert pool.page_bytes == pool.L * 2 * pool.Hkv * pool.P * pool.row_bytes
+        far = pool.far_pages()
+        assert far[0] == 0 and far[3] == pool.max_pages - 1 and len(set(pool.pages())) == len(pool.pages())
+        assert fc.B32 < pool.data_bytes() <= fc.B32 + 4 * pool.page_bytes                       # just over 4 GiB
+        assert pool.crossed(far[1]) >= {"B31"} and not pool.crossed(far[1] - 1) >= {"B31"}       # the first page wholly past B31
+        assert pool.crossed(far[2]) >= {"B31", "B32"} and "B32" not in pool.crossed(far[2] - 1)
+        assert pool.crossed(far[3]) >= {"B31", "B32"} and far[3] > far[2]
+        assert "E31" in pool.crossed(far[2]) and ("E32" in pool.crossed(far[3])) == (kind != "bf16")
+        for p in far:
+            for what, w in pool.wraps(p).items():
+                assert w in pool.pages() and w != p, (kind, p, what)
+        assert pool.pages() == far + [1] and all(0 <= p < pool.max_pages for p in pool.pages() + pool.spare_pages())
+        assert not set(pool.spare_pages()) & set(pool.pages()) and pool.spare_pages()[0] * pool.page_bytes < fc.B31 <= pool.spare_pages()[1] * pool.page_bytes
+        assert pool.param_bytes() < fc.B31 and (pool.param_bytes() == 0) == (kind == "bf16")
+        assert 4 * fc.GIB < pool.need_bytes() < fc.MEMORY_CAP
+        lines.append(f"{kind}, rows of 64: {pool.max_pages} pages of {pool.page_bytes} bytes, data {pool.data_bytes() / fc.GIB:.4f} GiB, params "
+                     f"{pool.param_bytes() / fc.GIB:.4f} GiB; pages {pool.pages()}; "
+                     + "; ".join(f"page {p} crosses {sorted(pool.crossed(p)) or '-'} wraps {pool.wraps(p) or '-'}" for p in far))
+    # the default width is the 128 pools' own: nothing about them moved
+    assert all(p.hd == 128 and p.row_bytes == fc.FarPool.ROW_BYTES[k] for k, p in fc.POOLS.items())
+    assert [fc.POOLS[k].page_bytes for k in ("int4", "fp8", "bf16")] == [8192, 16384, 32768]
+    table("paged KV pools, rows of 64", lines)
+
+
 def test_a_pool_whose_params_pass_b31_does_not_fit_the_memory_cap():
     """a pool whose fp16 param tensor itself passes B31 cannot be built within MEMORY_CAP: whatever L, Hkv and P are, int4 data is 16 times
     its params and fp8 data 32 times"""
@@ -133,9 +163,12 @@ def test_every_case_fits_the_memory_cap():
     needs = {"test_far_logits_gpu": fc.logits_need_bytes(), "test_far_logits_gpu, bias lists": fc.bias_need_bytes(),
              "test_limits_gpu": fc.limits_need_bytes()}
     needs.update({f"test_far_kv_gpu[{k}]": p.need_bytes() for k, p in fc.POOLS.items()})
+    needs.update({f"test_far_kv_hd64_gpu[{k}]": p.need_bytes() for k, p in fc.POOLS_HD64.items()})
+    assert len(needs) == 8
     table("device memory needed", [f"{k}: {v / fc.GIB:.2f} GiB" for k, v in needs.items()])
     assert all(v < fc.MEMORY_CAP for v in needs.values())
     assert fc.logits_need_bytes() > 8 * fc.GIB and all(p.need_bytes() > 4 * fc.GIB for p in fc.POOLS.values())
+    assert all(p.need_bytes() > 4 * fc.GIB for p in fc.POOLS_HD64.values())
 
 
 def test_gemm_quantizer_and_moe_matrices_cross_their_thresholds():

@@ -10,6 +10,7 @@ the oracles as the existing tests do (bytes exactly; attention within the bounds
 tests/test_kvprefill_gpu.py).
 
 kv_append and rope_kv_append; paged_decode with the window off and on; paged_decode_shared; paged_prefill causal and tree-masked;
+rope_append_decode (the one-launch decode step);
 kv_copy_pages far -> near, near -> far and far -> far; kv_move_rows between far pages, with the neighbours of every far page compared."""
 import numpy as np
 import pytest
@@ -292,3 +293,33 @@ def test_kv_move_rows(case):
     c.assert_far_equals_twin("kv_move_rows")
     c.assert_twin_is(want_d, want_p, "kv_move_rows")
     assert all(np.array_equal(a, b) for a, b in zip(before, snapshot(c, sel))), "kv_move_rows wrote a page next to a named one"
+
+
+def test_rope_append_decode(case):
+    """the one-launch decode step (include/micromix_decode_step.h) over the far pool against its twin: o, the rotated q and the
+    cache bytes.  The lengths put the new row of sequence 0 on the last page, past 2^32 bytes, and the walk reads it back from there
+    after the first page past 2^32 and page 0; sequence 1's lands on page 1, where a 32-bit offset of the last page would.  Neither
+    new row lies on a page the other sequence reads (they share their first two pages: a row written there would race with the other
+    walk).  Runs last: it rewrites two rows the other tests have filled"""
+    c = filled(case)
+    lens = [2 * c.g.P + 9, 2 * c.g.P + 9]
+    new_pages = [c.seq_pages[s][(n - 1) // c.g.P] for s, n in enumerate(lens)]
+    assert new_pages == [c.g.far_pages()[3], 1] and "B32" in c.g.crossed(new_pages[0]) and c.g.wraps(new_pages[0])["byte mod 2^32"] == 1
+    assert not set(new_pages) & (set(c.seq_pages[0][:2]) | set(c.seq_pages[1][:2]))
+    rng = np.random.default_rng(7)
+    qb, kb, vb = rows(rng, 2, HQ, 2.0), rows(rng, 2, c.g.Hkv, 2.0), rows(rng, 2, c.g.Hkv, 0.5)
+    cos, sin = ro.llama3_tables(np.array([n - 1 for n in lens]))
+    for layer in range(c.g.L):
+        outs, q_outs = [], []
+        for data, param, tbl in c.both((0, 1), lens):
+            q_outs.append(torch.empty((2, HQ, 128), dtype=torch.bfloat16, device=c.dev))
+            outs.append(mixedgemm.rope_append_decode(data, param, *tbl, bf16(qb, c.dev), bf16(kb, c.dev), bf16(vb, c.dev), bf16(cos, c.dev),
+                                                     bf16(sin, c.dev), layer, 64, q_out=q_outs[-1]))
+        same(outs, f"rope_append_decode, layer {layer}")
+        same(q_outs, f"rope_append_decode, layer {layer}, q_out")
+        assert np.array_equal(bits_of(q_outs[0]), ro.rope(qb, cos, sin)), "the rotated q"
+        # the chain it fuses, on the twin, which by now holds the new rows: the same o bit for bit
+        d, p, tbl = c.both((0, 1), lens)[1]
+        assert torch.equal(mixedgemm.paged_decode(q_outs[1], d, p, *tbl, layer, 64).view(torch.int16), outs[1].view(torch.int16))
+    torch.cuda.synchronize()
+    c.assert_far_equals_twin("rope_append_decode")
