@@ -156,6 +156,8 @@ _KV_HD64_PROTOS, KV_HD64_EXPORTS, KV_HD64 = _read("micromix_kv_hd64.h")
 _KV_PREFILL_HD64_PROTOS, KV_PREFILL_HD64_EXPORTS, KV_PREFILL_HD64 = _read("micromix_kv_prefill_hd64.h")
 # DECODE_STEP_EXPORTS: the entries of include/micromix_decode_step.h, likewise; the header defines no constant
 _DECODE_STEP_PROTOS, DECODE_STEP_EXPORTS, _ = _read("micromix_decode_step.h")
+# QKNORM_EXPORTS: the entries of include/micromix_qknorm.h, likewise; the header defines no constant, so QKNORM is empty
+_QKNORM_PROTOS, QKNORM_EXPORTS, QKNORM = _read("micromix_qknorm.h")
 
 _lib = None
 
@@ -172,7 +174,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for protos in (_PROTOS, _CALIB_PROTOS, _LOGPROB_PROTOS, _LOGITS_PROTOS, _SPEC_PROTOS, _KVSTEP_PROTOS, _TOKENS_PROTOS, _RANDOM_PROTOS, _ATTENTION_PROTOS, _ROPE_PROTOS,
                    _ATTENTION_WINDOW_PROTOS, _ATTENTION_PREFIX_PROTOS, _KVGATHER_PROTOS, _ATTENTION_HD64_PROTOS, _KV_HD64_PROTOS, _KV_PREFILL_HD64_PROTOS,
-                   _DECODE_STEP_PROTOS):
+                   _DECODE_STEP_PROTOS, _QKNORM_PROTOS):
         _bind(lib, protos)
     _lib = lib
     return _lib

@@ -27,7 +27,7 @@ SOURCES = ["capi.hip", "reorder_quantize.hip", "direct_quantize.hip", "rmsnorm_q
            "logits_process.hip", "spec_sample.hip", "kv_step.hip", "token_step.hip", "random.hip", "dense_attention.hip", "rope_prefill.hip", "kv_gather.hip",
            "dense_attention_hd64.hip", "kv_hd64.hip", "kv_prefill_hd64.hip", "decode_step.hip"]
 DIAG_SOURCES = ["diag.hip"]
-HEADERS = ["mx_common.h", "mx_kernels.h", "mx_acc_regs.h", "mx_gemm_tile.inc", "kv_decode_tiles.inc", "mx_group_convert.h", "mx_instrument.h", "mx_direct_convert.h", "mx_decode_quant.h", "mx_rms_convert.h", "mx_gemm_prelude.h", "mx_paged_kv.h", "mx_kv_shared_host.h", "mx_buffer_ops.h", "mx_gemm_plan.h", "mx_stream_plan.h", "mx_quant_plan.h", "mx_launch_shape.h", "mx_decode_quant_sizes.h", "mx_argmax_key.h", "mx_row_weights.h", "mx_sample_select.h", "mx_spec_rule.h", "mx_rope.h", "mx_kv_hd64.h", "mx_kv_decode.h",
+HEADERS = ["mx_common.h", "mx_kernels.h", "mx_acc_regs.h", "mx_gemm_tile.inc", "kv_decode_tiles.inc", "mx_group_convert.h", "mx_instrument.h", "mx_direct_convert.h", "mx_decode_quant.h", "mx_rms_convert.h", "mx_gemm_prelude.h", "mx_paged_kv.h", "mx_kv_shared_host.h", "mx_buffer_ops.h", "mx_gemm_plan.h", "mx_stream_plan.h", "mx_quant_plan.h", "mx_launch_shape.h", "mx_decode_quant_sizes.h", "mx_argmax_key.h", "mx_row_weights.h", "mx_sample_select.h", "mx_spec_rule.h", "mx_rope.h", "mx_kv_hd64.h", "mx_kv_decode.h", "mx_qknorm.h",
            os.path.join("..", "..", "include", "micromix_hip.h"), os.path.join("..", "..", "include", "micromix_diag.h"),
            os.path.join("..", "..", "include", "micromix_calib.h"), os.path.join("..", "..", "include", "micromix_logprob.h"),
            os.path.join("..", "..", "include", "micromix_logits.h"), os.path.join("..", "..", "include", "micromix_spec.h"),
@@ -36,7 +36,8 @@ HEADERS = ["mx_common.h", "mx_kernels.h", "mx_acc_regs.h", "mx_gemm_tile.inc", "
            os.path.join("..", "..", "include", "micromix_rope.h"), os.path.join("..", "..", "include", "micromix_attention_window.h"),
            os.path.join("..", "..", "include", "micromix_attention_prefix.h"), os.path.join("..", "..", "include", "micromix_kvgather.h"),
            os.path.join("..", "..", "include", "micromix_attention_hd64.h"), os.path.join("..", "..", "include", "micromix_kv_hd64.h"),
-           os.path.join("..", "..", "include", "micromix_kv_prefill_hd64.h"), os.path.join("..", "..", "include", "micromix_decode_step.h")]
+           os.path.join("..", "..", "include", "micromix_kv_prefill_hd64.h"), os.path.join("..", "..", "include", "micromix_decode_step.h"),
+           os.path.join("..", "..", "include", "micromix_qknorm.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 # flags of single sources, after FLAGS.  dense_attention.hip: its fp32 softmax and rescaling stay one operation per lane and instruction;
 # the compiler does not pair them into packed fp32 instructions (the host pass does not know the feature and says that it ignores it).

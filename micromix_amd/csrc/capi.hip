@@ -16,11 +16,13 @@
 #include "../../include/micromix_kvgather.h"
 #include "../../include/micromix_rope.h"
 #include "../../include/micromix_decode_step.h"
+#include "../../include/micromix_qknorm.h"
 #include "mx_common.h"
 #include "mx_kernels.h"
 #include "mx_kv_hd64.h"
 #include "mx_kv_shared_host.h"
 
+#include <math.h>
 #include <stdio.h>
 #include <string.h>
 
@@ -657,11 +659,22 @@ int mm_kv_append(void *kv_data, void *kv_param, int kv_dtype, int max_pages, int
     return e == hipSuccess ? MM_OK : fail_hip(e, "mm_kv_append");
 }
 
-int mm_rope_kv_append(void *kv_data, void *kv_param, int kv_dtype, int max_pages, int num_layers, int layer, int num_kv_heads, int page_size,
-                      int head_dim, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_len, int batch,
-                      const void *q_bf16, const void *k_bf16, const void *v_bf16, int64_t qkv_token_stride, int num_qo_heads,
-                      const void *cos_bf16, const void *sin_bf16, int64_t cs_token_stride, const int32_t *append_indptr, int num_tokens,
-                      void *q_out_bf16, mm_stream_t stream) {
+// Qwen3's QK-norm (include/micromix_qknorm.h): the three RoPE entries below are one body each for the plain and the normed form.  What
+// the normed form adds to its parent's statuses: eps with the numbers, the two weights with the pointers
+struct QKNorm {
+    const void *q_weight, *k_weight;
+    float eps;
+};
+static bool qknorm_eps_ok(const QKNorm *n) { return !n || (std::isfinite(n->eps) && n->eps > 0.0f); }
+static bool qknorm_weights_ok(const QKNorm *n) {
+    return !n || (n->q_weight && n->k_weight && !(((uintptr_t)n->q_weight | (uintptr_t)n->k_weight) & 15));
+}
+
+static int rope_kv_append(const char *what, const QKNorm *norm, void *kv_data, void *kv_param, int kv_dtype, int max_pages, int num_layers,
+                          int layer, int num_kv_heads, int page_size, int head_dim, const int32_t *kv_indptr, const int32_t *kv_indices,
+                          const int32_t *last_page_len, int batch, const void *q_bf16, const void *k_bf16, const void *v_bf16,
+                          int64_t qkv_token_stride, int num_qo_heads, const void *cos_bf16, const void *sin_bf16, int64_t cs_token_stride,
+                          const int32_t *append_indptr, int num_tokens, void *q_out_bf16, mm_stream_t stream) {
     mm::PagedKV kv;
     if (int st = kv_geometry(kv_data, kv_param, kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size, head_dim, kv_indptr, kv_indices,
                              last_page_len, batch, &kv)) return st;
@@ -669,22 +682,48 @@ int mm_rope_kv_append(void *kv_data, void *kv_param, int kv_dtype, int max_pages
     // a row of a token's q (the widest of the three) and of cos / sin must fit its stride; the kernel moves dwords
     if (qkv_token_stride < (int64_t)num_qo_heads * 128 || cs_token_stride < 128 || (qkv_token_stride & 1) || (cs_token_stride & 1))
         return MM_ERR_BAD_ARG;
+    if (!qknorm_eps_ok(norm)) return MM_ERR_BAD_ARG;
     if (num_tokens == 0) return MM_OK;
     if (batch == 0) return MM_ERR_BAD_ARG;                    // tokens that belong to no sequence
     if (!kv_pointers(kv) || !q_bf16 || !k_bf16 || !v_bf16 || !cos_bf16 || !sin_bf16 || !append_indptr || !q_out_bf16) return MM_ERR_BAD_ARG;
     if (((uintptr_t)q_bf16 | (uintptr_t)k_bf16 | (uintptr_t)v_bf16 | (uintptr_t)cos_bf16 | (uintptr_t)sin_bf16 | (uintptr_t)q_out_bf16) & 3)
         return MM_ERR_BAD_ARG;
+    if (!qknorm_weights_ok(norm)) return MM_ERR_BAD_ARG;
     hipError_t e = mm::launch_rope_kv_append(kv, q_bf16, k_bf16, v_bf16, qkv_token_stride, num_qo_heads, cos_bf16, sin_bf16, cs_token_stride,
-                                             append_indptr, num_tokens, q_out_bf16, (hipStream_t)stream);
-    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_rope_kv_append");
+                                             append_indptr, num_tokens, q_out_bf16, (hipStream_t)stream, norm ? norm->q_weight : nullptr,
+                                             norm ? norm->k_weight : nullptr, norm ? norm->eps : 0.0f);
+    return e == hipSuccess ? MM_OK : fail_hip(e, what);
+}
+
+int mm_rope_kv_append(void *kv_data, void *kv_param, int kv_dtype, int max_pages, int num_layers, int layer, int num_kv_heads, int page_size,
+                      int head_dim, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_len, int batch,
+                      const void *q_bf16, const void *k_bf16, const void *v_bf16, int64_t qkv_token_stride, int num_qo_heads,
+                      const void *cos_bf16, const void *sin_bf16, int64_t cs_token_stride, const int32_t *append_indptr, int num_tokens,
+                      void *q_out_bf16, mm_stream_t stream) {
+    return rope_kv_append("mm_rope_kv_append", nullptr, kv_data, kv_param, kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size, head_dim,
+                          kv_indptr, kv_indices, last_page_len, batch, q_bf16, k_bf16, v_bf16, qkv_token_stride, num_qo_heads, cos_bf16, sin_bf16,
+                          cs_token_stride, append_indptr, num_tokens, q_out_bf16, stream);
+}
+
+int mm_rope_kv_append_qknorm(void *kv_data, void *kv_param, int kv_dtype, int max_pages, int num_layers, int layer, int num_kv_heads,
+                             int page_size, int head_dim, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_len,
+                             int batch, const void *q_bf16, const void *k_bf16, const void *v_bf16, int64_t qkv_token_stride,
+                             int num_qo_heads, const void *cos_bf16, const void *sin_bf16, int64_t cs_token_stride,
+                             const int32_t *append_indptr, int num_tokens, void *q_out_bf16, const void *q_norm_weight_bf16,
+                             const void *k_norm_weight_bf16, float norm_eps, mm_stream_t stream) {
+    const QKNorm norm = {q_norm_weight_bf16, k_norm_weight_bf16, norm_eps};
+    return rope_kv_append("mm_rope_kv_append_qknorm", &norm, kv_data, kv_param, kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size,
+                          head_dim, kv_indptr, kv_indices, last_page_len, batch, q_bf16, k_bf16, v_bf16, qkv_token_stride, num_qo_heads, cos_bf16,
+                          sin_bf16, cs_token_stride, append_indptr, num_tokens, q_out_bf16, stream);
 }
 
 // the prefill shape of the above, with or without a cache (rope_prefill.hip, include/micromix_rope.h)
-int mm_rope_prefill(void *kv_data, void *kv_param, int kv_dtype, int max_pages, int num_layers, int layer, int num_kv_heads, int page_size,
-                    int head_dim, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_len, int batch,
-                    const void *q_bf16, const void *k_bf16, const void *v_bf16, int64_t qkv_token_stride, int num_qo_heads,
-                    const void *cos_bf16, const void *sin_bf16, int64_t cs_token_stride, const int32_t *append_indptr, int num_tokens,
-                    void *q_out_bf16, void *k_out_bf16, void *v_out_bf16, mm_stream_t stream) {
+static int rope_prefill(const char *what, const QKNorm *norm, void *kv_data, void *kv_param, int kv_dtype, int max_pages, int num_layers, int layer,
+                        int num_kv_heads, int page_size, int head_dim, const int32_t *kv_indptr, const int32_t *kv_indices,
+                        const int32_t *last_page_len, int batch, const void *q_bf16, const void *k_bf16, const void *v_bf16,
+                        int64_t qkv_token_stride, int num_qo_heads, const void *cos_bf16, const void *sin_bf16, int64_t cs_token_stride,
+                        const int32_t *append_indptr, int num_tokens, void *q_out_bf16, void *k_out_bf16, void *v_out_bf16,
+                        mm_stream_t stream) {
     mm::PagedKV kv;
     const bool cache = kv_data != nullptr;
     if (cache) {
@@ -696,9 +735,10 @@ int mm_rope_prefill(void *kv_data, void *kv_param, int kv_dtype, int max_pages, 
     if (num_tokens < 0 || num_qo_heads < 1 || num_qo_heads % num_kv_heads) return MM_ERR_BAD_ARG;
     // a row of a token's q (the widest of the three) and of cos / sin must fit its stride; the kernel moves 16-byte vectors
     if (qkv_token_stride < (int64_t)num_qo_heads * 128 || cs_token_stride < 128 || ((qkv_token_stride | cs_token_stride) & 7)) return MM_ERR_BAD_ARG;
+    if (!qknorm_eps_ok(norm)) return MM_ERR_BAD_ARG;
     if (head_dim != 128) return MM_ERR_UNSUPPORTED;
     if (num_tokens == 0) return MM_OK;
-    if (!q_bf16 || !k_bf16 || !v_bf16 || !cos_bf16 || !sin_bf16 || !q_out_bf16) return MM_ERR_BAD_ARG;
+    if (!q_bf16 || !k_bf16 || !v_bf16 || !cos_bf16 || !sin_bf16 || !q_out_bf16 || !qknorm_weights_ok(norm)) return MM_ERR_BAD_ARG;
     if (((uintptr_t)q_bf16 | (uintptr_t)k_bf16 | (uintptr_t)v_bf16 | (uintptr_t)cos_bf16 | (uintptr_t)sin_bf16 | (uintptr_t)q_out_bf16 |
          (uintptr_t)k_out_bf16 | (uintptr_t)v_out_bf16) & 15)
         return MM_ERR_BAD_ARG;
@@ -710,8 +750,31 @@ int mm_rope_prefill(void *kv_data, void *kv_param, int kv_dtype, int max_pages, 
     }
     hipError_t e = mm::launch_rope_prefill(cache ? &kv : nullptr, q_bf16, k_bf16, v_bf16, qkv_token_stride, num_qo_heads, num_kv_heads, cos_bf16,
                                            sin_bf16, cs_token_stride, append_indptr, num_tokens, q_out_bf16, k_out_bf16, v_out_bf16,
-                                           (hipStream_t)stream);
-    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_rope_prefill");
+                                           (hipStream_t)stream, norm ? norm->q_weight : nullptr, norm ? norm->k_weight : nullptr,
+                                           norm ? norm->eps : 0.0f);
+    return e == hipSuccess ? MM_OK : fail_hip(e, what);
+}
+
+int mm_rope_prefill(void *kv_data, void *kv_param, int kv_dtype, int max_pages, int num_layers, int layer, int num_kv_heads, int page_size,
+                    int head_dim, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_len, int batch,
+                    const void *q_bf16, const void *k_bf16, const void *v_bf16, int64_t qkv_token_stride, int num_qo_heads,
+                    const void *cos_bf16, const void *sin_bf16, int64_t cs_token_stride, const int32_t *append_indptr, int num_tokens,
+                    void *q_out_bf16, void *k_out_bf16, void *v_out_bf16, mm_stream_t stream) {
+    return rope_prefill("mm_rope_prefill", nullptr, kv_data, kv_param, kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size, head_dim,
+                        kv_indptr, kv_indices, last_page_len, batch, q_bf16, k_bf16, v_bf16, qkv_token_stride, num_qo_heads, cos_bf16, sin_bf16,
+                        cs_token_stride, append_indptr, num_tokens, q_out_bf16, k_out_bf16, v_out_bf16, stream);
+}
+
+int mm_rope_prefill_qknorm(void *kv_data, void *kv_param, int kv_dtype, int max_pages, int num_layers, int layer, int num_kv_heads,
+                           int page_size, int head_dim, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_len,
+                           int batch, const void *q_bf16, const void *k_bf16, const void *v_bf16, int64_t qkv_token_stride, int num_qo_heads,
+                           const void *cos_bf16, const void *sin_bf16, int64_t cs_token_stride, const int32_t *append_indptr, int num_tokens,
+                           void *q_out_bf16, void *k_out_bf16, void *v_out_bf16, const void *q_norm_weight_bf16,
+                           const void *k_norm_weight_bf16, float norm_eps, mm_stream_t stream) {
+    const QKNorm norm = {q_norm_weight_bf16, k_norm_weight_bf16, norm_eps};
+    return rope_prefill("mm_rope_prefill_qknorm", &norm, kv_data, kv_param, kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size,
+                        head_dim, kv_indptr, kv_indices, last_page_len, batch, q_bf16, k_bf16, v_bf16, qkv_token_stride, num_qo_heads, cos_bf16,
+                        sin_bf16, cs_token_stride, append_indptr, num_tokens, q_out_bf16, k_out_bf16, v_out_bf16, stream);
 }
 
 int mm_kv_copy_pages(void *kv_data, void *kv_param, int kv_dtype, int max_pages, int num_layers, int num_kv_heads, int page_size,
@@ -1282,28 +1345,55 @@ size_t mm_rope_append_decode_workspace_bytes(int batch, int num_qo_heads, int nu
     return mm_paged_decode_workspace_bytes(batch, num_qo_heads, num_kv_heads, max_seq_len);
 }
 
-int mm_rope_append_decode(void *kv_data, void *kv_param, int kv_dtype, int max_pages, int num_layers, int layer, int num_kv_heads,
-                          int page_size, int head_dim, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_len,
-                          int batch, const void *q_bf16, const void *k_bf16, const void *v_bf16, int64_t qkv_token_stride,
-                          int num_qo_heads, const void *cos_bf16, const void *sin_bf16, int64_t cs_token_stride, int max_seq_len,
-                          float sm_scale, void *workspace, size_t workspace_bytes, void *q_out_bf16, void *o_bf16, mm_stream_t stream) {
+static int rope_append_decode(const char *what, const QKNorm *norm, void *kv_data, void *kv_param, int kv_dtype, int max_pages, int num_layers,
+                              int layer, int num_kv_heads, int page_size, int head_dim, const int32_t *kv_indptr, const int32_t *kv_indices,
+                              const int32_t *last_page_len, int batch, const void *q_bf16, const void *k_bf16, const void *v_bf16,
+                              int64_t qkv_token_stride, int num_qo_heads, const void *cos_bf16, const void *sin_bf16, int64_t cs_token_stride,
+                              int max_seq_len, float sm_scale, void *workspace, size_t workspace_bytes, void *q_out_bf16, void *o_bf16,
+                              mm_stream_t stream) {
     mm::PagedKV kv;
     if (int st = kv_geometry(kv_data, kv_param, kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size, head_dim, kv_indptr, kv_indices,
                              last_page_len, batch, &kv)) return st;
     if (num_qo_heads <= 0 || num_qo_heads % num_kv_heads || max_seq_len < 0) return MM_ERR_BAD_ARG;
     if (qkv_token_stride < (int64_t)num_qo_heads * 128 || cs_token_stride < 128 || (qkv_token_stride & 1) || (cs_token_stride & 1))
         return MM_ERR_BAD_ARG;
+    if (!qknorm_eps_ok(norm)) return MM_ERR_BAD_ARG;
     if (num_qo_heads / num_kv_heads > 16) return MM_ERR_UNSUPPORTED;
     if (batch == 0) return MM_OK;
-    if (!kv_pointers(kv) || !q_bf16 || !k_bf16 || !v_bf16 || !cos_bf16 || !sin_bf16 || !o_bf16) return MM_ERR_BAD_ARG;
+    if (!kv_pointers(kv) || !q_bf16 || !k_bf16 || !v_bf16 || !cos_bf16 || !sin_bf16 || !o_bf16 || !qknorm_weights_ok(norm)) return MM_ERR_BAD_ARG;
     if (((uintptr_t)q_bf16 | (uintptr_t)k_bf16 | (uintptr_t)v_bf16 | (uintptr_t)cos_bf16 | (uintptr_t)sin_bf16 | (uintptr_t)q_out_bf16 |
          (uintptr_t)o_bf16) & 3)
         return MM_ERR_BAD_ARG;
     const size_t need = mm_rope_append_decode_workspace_bytes(batch, num_qo_heads, num_kv_heads, max_seq_len);
     if (need && (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15))) return MM_ERR_BAD_ARG;
     hipError_t e = mm::launch_rope_append_decode(kv, q_bf16, k_bf16, v_bf16, qkv_token_stride, num_qo_heads, cos_bf16, sin_bf16, cs_token_stride,
-                                                 max_seq_len, sm_scale, workspace, q_out_bf16, o_bf16, (hipStream_t)stream);
-    return e == hipSuccess ? MM_OK : fail_hip(e, "mm_rope_append_decode");
+                                                 max_seq_len, sm_scale, workspace, q_out_bf16, o_bf16, (hipStream_t)stream,
+                                                 norm ? norm->q_weight : nullptr, norm ? norm->k_weight : nullptr, norm ? norm->eps : 0.0f);
+    return e == hipSuccess ? MM_OK : fail_hip(e, what);
+}
+
+int mm_rope_append_decode(void *kv_data, void *kv_param, int kv_dtype, int max_pages, int num_layers, int layer, int num_kv_heads,
+                          int page_size, int head_dim, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_len,
+                          int batch, const void *q_bf16, const void *k_bf16, const void *v_bf16, int64_t qkv_token_stride,
+                          int num_qo_heads, const void *cos_bf16, const void *sin_bf16, int64_t cs_token_stride, int max_seq_len,
+                          float sm_scale, void *workspace, size_t workspace_bytes, void *q_out_bf16, void *o_bf16, mm_stream_t stream) {
+    return rope_append_decode("mm_rope_append_decode", nullptr, kv_data, kv_param, kv_dtype, max_pages, num_layers, layer, num_kv_heads, page_size,
+                              head_dim, kv_indptr, kv_indices, last_page_len, batch, q_bf16, k_bf16, v_bf16, qkv_token_stride, num_qo_heads,
+                              cos_bf16, sin_bf16, cs_token_stride, max_seq_len, sm_scale, workspace, workspace_bytes, q_out_bf16, o_bf16, stream);
+}
+
+int mm_rope_append_decode_qknorm(void *kv_data, void *kv_param, int kv_dtype, int max_pages, int num_layers, int layer, int num_kv_heads,
+                                 int page_size, int head_dim, const int32_t *kv_indptr, const int32_t *kv_indices,
+                                 const int32_t *last_page_len, int batch, const void *q_bf16, const void *k_bf16, const void *v_bf16,
+                                 int64_t qkv_token_stride, int num_qo_heads, const void *cos_bf16, const void *sin_bf16,
+                                 int64_t cs_token_stride, int max_seq_len, float sm_scale, void *workspace, size_t workspace_bytes,
+                                 void *q_out_bf16, void *o_bf16, const void *q_norm_weight_bf16, const void *k_norm_weight_bf16,
+                                 float norm_eps, mm_stream_t stream) {
+    const QKNorm norm = {q_norm_weight_bf16, k_norm_weight_bf16, norm_eps};
+    return rope_append_decode("mm_rope_append_decode_qknorm", &norm, kv_data, kv_param, kv_dtype, max_pages, num_layers, layer, num_kv_heads,
+                              page_size, head_dim, kv_indptr, kv_indices, last_page_len, batch, q_bf16, k_bf16, v_bf16, qkv_token_stride,
+                              num_qo_heads, cos_bf16, sin_bf16, cs_token_stride, max_seq_len, sm_scale, workspace, workspace_bytes, q_out_bf16,
+                              o_bf16, stream);
 }
 
 // shared-prefix decode: the sizes, the split and the workspace rules are mx_kv_shared_host.h's

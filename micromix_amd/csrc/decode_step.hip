@@ -25,9 +25,12 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "mx_kernels.h"
 #include "mx_kv_decode.h"
 #include "mx_paged_kv.h"
+#include "mx_qknorm.h"
 #include "mx_rope.h"
 
 namespace {
@@ -46,8 +49,17 @@ struct StepArgs {
     int64_t qkv_stride, cs_stride;     // elements per token
 };
 
-template <int KIND, int GP>
-__global__ __launch_bounds__(256) void rope_append_decode_kernel(const StepArgs st) {
+struct StepNormArgs : StepArgs {
+    const uint16_t *q_weight, *k_weight;   // bf16 [128] each
+    float eps;
+};
+
+// NORM (mm_rope_append_decode_qknorm): q and k pass mx_qknorm.h's rule before their rotation.  q: a lane norms the block it holds and
+// the block of its rotate_half partners (qknorm_blocks: the row's sum needs one exchange, with lane ^ 16), with the two blocks of the
+// weight loaded next to its cos / sin block; the four waves repeat the norm as they repeat the rotation.  k: wave 0 of the owning
+// workgroup, in rope_pair's layout (qknorm_pair).  No LDS and no barrier beyond the one below.
+template <int KIND, int GP, bool NORM>
+__global__ __launch_bounds__(256) void rope_append_decode_kernel(const std::conditional_t<NORM, StepNormArgs, StepArgs> st) {
     constexpr int WALK = WALK_STEP;
     const DecodeArgs &a = st.d;
     const SharedArgs sh = {};
@@ -65,14 +77,38 @@ __global__ __launch_bounds__(256) void rope_append_decode_kernel(const StepArgs 
             const v4u_dw *cs = (const v4u_dw *)(st.cos + (int64_t)b * st.cs_stride + 32 * kq);
             const v4u_dw *sn = (const v4u_dw *)(st.sin + (int64_t)b * st.cs_stride + 32 * kq);
             const uint32_t flip = kq < 2 ? 0x80008000u : 0u;                   // rotate_half: -x[d + 64] below 64, x[d - 64] above
+            if constexpr (NORM) {
+                const v4u_dw *gx = (const v4u_dw *)(st.q_weight + 32 * kq), *gp = (const v4u_dw *)(st.q_weight + 32 * (kq ^ 2));
+                v4u xn[4], pn[4];
 #pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const v4u xs = x[s], rs = r[s], cc = cs[s], ss = sn[s];
+                for (int s = 0; s < 4; ++s) xn[s] = x[s], pn[s] = r[s];
+                const float rscale = qknorm_blocks_rscale(xn, pn, st.eps);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const uint32_t p = rs[j] ^ flip;
-                    step_q[s][j] = rope_one(xs[j] & 0xffffu, p & 0xffffu, cc[j] & 0xffffu, ss[j] & 0xffffu) |
-                                   (rope_one(xs[j] >> 16, p >> 16, cc[j] >> 16, ss[j] >> 16) << 16);
+                for (int s = 0; s < 4; ++s) {
+                    const v4u wx = gx[s], wp = gp[s];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) xn[s][j] = qkn_scale(xn[s][j], rscale, wx[j]), pn[s][j] = qkn_scale(pn[s][j], rscale, wp[j]);
+                }
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    const v4u cc = cs[s], ss = sn[s];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const uint32_t xv = xn[s][j], p = pn[s][j] ^ flip;
+                        step_q[s][j] = rope_one(xv & 0xffffu, p & 0xffffu, cc[j] & 0xffffu, ss[j] & 0xffffu) |
+                                       (rope_one(xv >> 16, p >> 16, cc[j] >> 16, ss[j] >> 16) << 16);
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    const v4u xs = x[s], rs = r[s], cc = cs[s], ss = sn[s];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const uint32_t p = rs[j] ^ flip;
+                        step_q[s][j] = rope_one(xs[j] & 0xffffu, p & 0xffffu, cc[j] & 0xffffu, ss[j] & 0xffffu) |
+                                       (rope_one(xs[j] >> 16, p >> 16, cc[j] >> 16, ss[j] >> 16) << 16);
+                    }
                 }
             }
             if (st.q_out && chunk == 0 && wave == 0) {
@@ -91,6 +127,7 @@ __global__ __launch_bounds__(256) void rope_append_decode_kernel(const StepArgs 
                 if (wave == 0) {
                     const uint32_t cs = ((const uint32_t *)(st.cos + (int64_t)b * st.cs_stride))[l];
                     const uint32_t sn = ((const uint32_t *)(st.sin + (int64_t)b * st.cs_stride))[l];
+                    if constexpr (NORM) two = qknorm_pair(two, ((const uint32_t *)st.k_weight)[l], st.eps);
                     two = rope_pair(two, cs, sn, l);
                 }
                 const int64_t row = append_row_at(a.kv, b, len - 1, len, wave, kvh);
@@ -102,13 +139,20 @@ __global__ __launch_bounds__(256) void rope_append_decode_kernel(const StepArgs 
 #include "kv_decode_tiles.inc"
 }
 
-template <int KIND>
-hipError_t launch_step_g(const StepArgs &st, hipStream_t stream) {
+template <int KIND, bool NORM>
+hipError_t launch_step_g(const std::conditional_t<NORM, StepNormArgs, StepArgs> &st, hipStream_t stream) {
     const dim3 grid(st.d.nc, st.d.kv.Hkv, st.d.kv.B);
-    if (st.d.g <= 4) rope_append_decode_kernel<KIND, 4><<<grid, 256, 0, stream>>>(st);
-    else if (st.d.g <= 8) rope_append_decode_kernel<KIND, 8><<<grid, 256, 0, stream>>>(st);
-    else rope_append_decode_kernel<KIND, 16><<<grid, 256, 0, stream>>>(st);
+    if (st.d.g <= 4) rope_append_decode_kernel<KIND, 4, NORM><<<grid, 256, 0, stream>>>(st);
+    else if (st.d.g <= 8) rope_append_decode_kernel<KIND, 8, NORM><<<grid, 256, 0, stream>>>(st);
+    else rope_append_decode_kernel<KIND, 16, NORM><<<grid, 256, 0, stream>>>(st);
     return hipGetLastError();
+}
+
+template <bool NORM>
+hipError_t launch_step_kind(const std::conditional_t<NORM, StepNormArgs, StepArgs> &st, hipStream_t stream) {
+    if (st.d.kv.kind == KV_INT4) return launch_step_g<KV_INT4, NORM>(st, stream);
+    if (st.d.kv.kind == KV_FP8) return launch_step_g<KV_FP8, NORM>(st, stream);
+    return launch_step_g<KV_BF16, NORM>(st, stream);
 }
 
 }  // namespace
@@ -117,8 +161,8 @@ namespace mm {
 
 hipError_t launch_rope_append_decode(const PagedKV &kv, const void *q, const void *k, const void *v, int64_t qkv_stride, int Hq, const void *cos,
                                      const void *sin, int64_t cs_stride, int max_seq_len, float sm_scale, void *ws, void *q_out, void *o,
-                                     hipStream_t stream) {
-    StepArgs st;
+                                     hipStream_t stream, const void *q_weight, const void *k_weight, float eps) {
+    StepNormArgs st;                                                           // q_weight != nullptr: the QK-norm form, both weights given
     st.d.kv = kv;
     st.d.q = nullptr;
     st.d.ws = (float *)ws;
@@ -136,10 +180,10 @@ hipError_t launch_rope_append_decode(const PagedKV &kv, const void *q, const voi
     st.q_out = (uint16_t *)q_out;
     st.qkv_stride = qkv_stride;
     st.cs_stride = cs_stride;
-    hipError_t e;
-    if (kv.kind == KV_INT4) e = launch_step_g<KV_INT4>(st, stream);
-    else if (kv.kind == KV_FP8) e = launch_step_g<KV_FP8>(st, stream);
-    else e = launch_step_g<KV_BF16>(st, stream);
+    st.q_weight = (const uint16_t *)q_weight;
+    st.k_weight = (const uint16_t *)k_weight;
+    st.eps = eps;
+    const hipError_t e = q_weight ? launch_step_kind<true>(st, stream) : launch_step_kind<false>(st, stream);
     if (e != hipSuccess || st.d.nc == 1) return e;
     return launch_paged_decode_merge(st.d, stream);
 }

@@ -293,19 +293,23 @@ hipError_t launch_paged_decode(const PagedKV &kv, const void *q, int Hq, int max
 hipError_t launch_paged_decode_shared(const PagedKV &kv, const void *q, int Hq, const int *group_indptr, const int *group_members,
                                       const int *shared_len, int max_shared_len, int max_suffix_len, float sm_scale, void *ws, void *o,
                                       hipStream_t stream);
-// RoPE + append in one launch (rope_append.hip): q | k | v share the token stride qkv_stride, cos | sin the stride cs_stride (elements)
+// RoPE + append in one launch (rope_append.hip): q | k | v share the token stride qkv_stride, cos | sin the stride cs_stride (elements).
+// This launch and the two below take Qwen3's QK-norm as their last three arguments (mx_qknorm.h, include/micromix_qknorm.h): with
+// q_weight the rows of q and k are normed by q_weight / k_weight (bf16 [128], both given) and eps before they are rotated
 hipError_t launch_rope_kv_append(const PagedKV &kv, const void *q, const void *k, const void *v, int64_t qkv_stride, int Hq, const void *cos,
-                                 const void *sin, int64_t cs_stride, const int *append_indptr, int T, void *q_out, hipStream_t stream);
+                                 const void *sin, int64_t cs_stride, const int *append_indptr, int T, void *q_out, hipStream_t stream,
+                                 const void *q_weight = nullptr, const void *k_weight = nullptr, float eps = 0.0f);
 // that launch with one token per sequence and launch_paged_decode (window 0) over the result as one launch (decode_step.hip,
 // include/micromix_decode_step.h); q_out may be null, ws as launch_paged_decode takes it
 hipError_t launch_rope_append_decode(const PagedKV &kv, const void *q, const void *k, const void *v, int64_t qkv_stride, int Hq, const void *cos,
                                      const void *sin, int64_t cs_stride, int max_seq_len, float sm_scale, void *ws, void *q_out, void *o,
-                                     hipStream_t stream);
+                                     hipStream_t stream, const void *q_weight = nullptr, const void *k_weight = nullptr, float eps = 0.0f);
 // the same for a prompt's worth of tokens (rope_prefill.hip, include/micromix_rope.h): kv may be null (no cache, Hkv from the argument);
 // k_out / v_out, each optional, receive what a reader of the slot gets back
 hipError_t launch_rope_prefill(const PagedKV *kv, const void *q, const void *k, const void *v, int64_t qkv_stride, int Hq, int Hkv,
                                const void *cos, const void *sin, int64_t cs_stride, const int *append_indptr, int T, void *q_out, void *k_out,
-                               void *v_out, hipStream_t stream);
+                               void *v_out, hipStream_t stream, const void *q_weight = nullptr, const void *k_weight = nullptr,
+                               float eps = 0.0f);
 // rows [0, rows[i]) of page src_pages[i] -> page dst_pages[i], every layer, K and V, every head (kv_copy.hip); kv.layer is 0
 hipError_t launch_kv_copy_pages(const PagedKV &kv, const int *src_pages, const int *dst_pages, const int *rows, int num_pairs,
                                 hipStream_t stream);

@@ -13,8 +13,11 @@
 #include <hip/hip_fp16.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "mx_kernels.h"
 #include "mx_paged_kv.h"
+#include "mx_qknorm.h"            // qknorm_pair: QK-norm of a wave's row ahead of its rotation (NORM, mm_rope_kv_append_qknorm)
 #include "mx_rope.h"              // rope_one: the element rule, shared with rope_prefill.hip; rope_pair: a wave's row, with decode_step.hip
 
 namespace {
@@ -32,8 +35,14 @@ struct RopeArgs {
     int Hq, g;
 };
 
-template <int KIND>
-__global__ __launch_bounds__(64 * (2 + MAX_Q_WAVES)) void rope_kv_append_kernel(const RopeArgs a) {
+struct RopeNormArgs : RopeArgs {
+    const uint16_t *q_weight, *k_weight;       // bf16 [128] each
+    float eps;
+};
+
+// NORM: q and k rows pass mx_qknorm.h's rule before the rotation; a wave loads its dword of the weight once, next to cos / sin
+template <int KIND, bool NORM>
+__global__ __launch_bounds__(64 * (2 + MAX_Q_WAVES)) void rope_kv_append_kernel(const std::conditional_t<NORM, RopeNormArgs, RopeArgs> a) {
     const int i = blockIdx.x, h = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t in = (int64_t)i * a.qkv_stride;
     if (wave == 1) {                                          // V: as mm_kv_append
@@ -44,8 +53,12 @@ __global__ __launch_bounds__(64 * (2 + MAX_Q_WAVES)) void rope_kv_append_kernel(
     }
     const uint32_t cs = ((const uint32_t *)(a.cos + (int64_t)i * a.cs_stride))[lane];
     const uint32_t sn = ((const uint32_t *)(a.sin + (int64_t)i * a.cs_stride))[lane];
+    [[maybe_unused]] uint32_t w = 0;
+    if constexpr (NORM) w = ((const uint32_t *)(wave == 0 ? a.k_weight : a.q_weight))[lane];
     if (wave == 0) {                                          // K
-        const uint32_t two = rope_pair(((const uint32_t *)(a.k + in + (int64_t)h * HD))[lane], cs, sn, lane);
+        uint32_t two = ((const uint32_t *)(a.k + in + (int64_t)h * HD))[lane];
+        if constexpr (NORM) two = qknorm_pair(two, w, a.eps);
+        two = rope_pair(two, cs, sn, lane);
         const int64_t row = append_row(a.kv, a.append_indptr, i, 0, h);
         if (row >= 0) store_row<KIND>(a.kv, row, lane, two);
         return;
@@ -54,7 +67,8 @@ __global__ __launch_bounds__(64 * (2 + MAX_Q_WAVES)) void rope_kv_append_kernel(
     const int nq = (int)(blockDim.x >> 6) - 2;
     for (int j = wave - 2; j < a.g; j += nq) {
         const int hq = h * a.g + j;
-        const uint32_t two = ((const uint32_t *)(a.q + in + (int64_t)hq * HD))[lane];
+        uint32_t two = ((const uint32_t *)(a.q + in + (int64_t)hq * HD))[lane];
+        if constexpr (NORM) two = qknorm_pair(two, w, a.eps);
         // stored as a float: a store of an integer type here may alias the page table for all the compiler knows, and then wave 0 and
         // wave 1 read the table (append_row) with vector loads instead of scalar ones (7 % of the launch at T = 4096)
         ((float *)(a.q_out + ((int64_t)i * a.Hq + hq) * HD))[lane] = __uint_as_float(rope_pair(two, cs, sn, lane));
@@ -65,9 +79,11 @@ __global__ __launch_bounds__(64 * (2 + MAX_Q_WAVES)) void rope_kv_append_kernel(
 
 namespace mm {
 
+// q_weight != nullptr: the QK-norm form, both weights given
 hipError_t launch_rope_kv_append(const PagedKV &kv, const void *q, const void *k, const void *v, int64_t qkv_stride, int Hq, const void *cos,
-                                 const void *sin, int64_t cs_stride, const int *append_indptr, int T, void *q_out, hipStream_t stream) {
-    RopeArgs a;
+                                 const void *sin, int64_t cs_stride, const int *append_indptr, int T, void *q_out, hipStream_t stream,
+                                 const void *q_weight, const void *k_weight, float eps) {
+    RopeNormArgs a;
     a.kv = kv;
     a.append_indptr = append_indptr;
     a.q = (const uint16_t *)q;
@@ -80,11 +96,19 @@ hipError_t launch_rope_kv_append(const PagedKV &kv, const void *q, const void *k
     a.cs_stride = cs_stride;
     a.Hq = Hq;
     a.g = Hq / kv.Hkv;
+    a.q_weight = (const uint16_t *)q_weight;
+    a.k_weight = (const uint16_t *)k_weight;
+    a.eps = eps;
     const dim3 grid(T, kv.Hkv);
     const int threads = 64 * (2 + (a.g < MAX_Q_WAVES ? a.g : MAX_Q_WAVES));
-    if (kv.kind == KV_INT4) rope_kv_append_kernel<KV_INT4><<<grid, threads, 0, stream>>>(a);
-    else if (kv.kind == KV_FP8) rope_kv_append_kernel<KV_FP8><<<grid, threads, 0, stream>>>(a);
-    else rope_kv_append_kernel<KV_BF16><<<grid, threads, 0, stream>>>(a);
+    const RopeArgs &plain = a;
+    if (q_weight) {
+        if (kv.kind == KV_INT4) rope_kv_append_kernel<KV_INT4, true><<<grid, threads, 0, stream>>>(a);
+        else if (kv.kind == KV_FP8) rope_kv_append_kernel<KV_FP8, true><<<grid, threads, 0, stream>>>(a);
+        else rope_kv_append_kernel<KV_BF16, true><<<grid, threads, 0, stream>>>(a);
+    } else if (kv.kind == KV_INT4) rope_kv_append_kernel<KV_INT4, false><<<grid, threads, 0, stream>>>(plain);
+    else if (kv.kind == KV_FP8) rope_kv_append_kernel<KV_FP8, false><<<grid, threads, 0, stream>>>(plain);
+    else rope_kv_append_kernel<KV_BF16, false><<<grid, threads, 0, stream>>>(plain);
     return hipGetLastError();
 }
 

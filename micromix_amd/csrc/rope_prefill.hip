@@ -28,9 +28,12 @@
 #include <hip/hip_fp16.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/micromix_rope.h"
 #include "mx_kernels.h"
 #include "mx_paged_kv.h"
+#include "mx_qknorm.h"
 #include "mx_rope.h"
 
 namespace {
@@ -62,8 +65,16 @@ __device__ inline void rope_row(v4u &lo, v4u &hi, const v4u (&cs)[2], const v4u 
     }
 }
 
-template <int KIND>
-__global__ __launch_bounds__(64 * MAX_WAVES) void rope_prefill_kernel(const RopePrefillArgs a) {
+struct RopePrefillNormArgs : RopePrefillArgs {
+    const uint16_t *q_weight, *k_weight;       // bf16 [128] each
+    float eps;
+};
+
+// NORM: q and k rows pass mx_qknorm.h's rule (qknorm_row8) before the rotation.  A group loads its two chunks of the q weight next to
+// its cos / sin chunks and keeps them over its q rows; a wave's rows ascend, q before K, so the chunks of the k weight replace them
+// once, at the wave's first K row.
+template <int KIND, bool NORM>
+__global__ __launch_bounds__(64 * MAX_WAVES) void rope_prefill_kernel(const std::conditional_t<NORM, RopePrefillNormArgs, RopePrefillArgs> a) {
     const int j = threadIdx.x & 7, wave = threadIdx.x >> 6;
     const int64_t i = (int64_t)blockIdx.x * TPW + ((threadIdx.x >> 3) & (TPW - 1));
     if (i >= a.T) return;                                     // whole row groups leave: the eight lanes of a group stay together
@@ -76,11 +87,26 @@ __global__ __launch_bounds__(64 * MAX_WAVES) void rope_prefill_kernel(const Rope
         const v4u *c = (const v4u *)(a.cos + i * a.cs_stride), *s = (const v4u *)(a.sin + i * a.cs_stride);
         cs[0] = c[j], cs[1] = c[HD / 16 + j], sn[0] = s[j], sn[1] = s[HD / 16 + j];
     }
+    [[maybe_unused]] v4u w[2] = {};
+    [[maybe_unused]] bool w_is_k = wave >= a.Hq;
+    if constexpr (NORM) {
+        if (wave < rot_rows) {
+            const v4u *g = (const v4u *)(w_is_k ? a.k_weight : a.q_weight);
+            w[0] = g[j], w[1] = g[HD / 16 + j];
+        }
+    }
     for (int r = wave; r < a.R; r += a.G) {
         const bool isq = r < a.Hq, isk = !isq && r < rot_rows;
         const int h = isq ? r : isk ? r - a.Hq : r - rot_rows;
         const v4u *src = (const v4u *)((isq ? a.q : isk ? a.k : a.v) + i * a.qkv_stride + (int64_t)h * HD);
         v4u lo = src[j], hi = src[HD / 16 + j];
+        if constexpr (NORM) {
+            if (isk && !w_is_k) {
+                const v4u *g = (const v4u *)a.k_weight;
+                w[0] = g[j], w[1] = g[HD / 16 + j], w_is_k = true;
+            }
+            if (r < rot_rows) qknorm_row8(lo, hi, w, a.eps);
+        }
         if (r < rot_rows) rope_row(lo, hi, cs, sn);
         v4u *dst;
         if (isq) {                                            // q: every token, whatever its cache slot
@@ -102,8 +128,8 @@ namespace mm {
 
 hipError_t launch_rope_prefill(const PagedKV *kv, const void *q, const void *k, const void *v, int64_t qkv_stride, int Hq, int Hkv,
                                const void *cos, const void *sin, int64_t cs_stride, const int *append_indptr, int T, void *q_out, void *k_out,
-                               void *v_out, hipStream_t stream) {
-    RopePrefillArgs a{};
+                               void *v_out, hipStream_t stream, const void *q_weight, const void *k_weight, float eps) {
+    RopePrefillNormArgs a{};                                  // q_weight != nullptr: the QK-norm form, both weights given
     if (kv) a.kv = *kv;
     a.cache = kv != nullptr;
     a.append_indptr = append_indptr;
@@ -124,9 +150,17 @@ hipError_t launch_rope_prefill(const PagedKV *kv, const void *q, const void *k, 
     a.G = (a.R + 3) / 4 < MAX_WAVES ? (a.R + 3) / 4 : MAX_WAVES;
     const unsigned grid = (unsigned)(((int64_t)T + TPW - 1) / TPW);
     const int kind = kv ? kv->kind : KV_BF16;                 // without a cache K and V are handed on as they are: the bf16 kind's values
-    if (kind == KV_INT4) rope_prefill_kernel<KV_INT4><<<grid, 64 * a.G, 0, stream>>>(a);
-    else if (kind == KV_FP8) rope_prefill_kernel<KV_FP8><<<grid, 64 * a.G, 0, stream>>>(a);
-    else rope_prefill_kernel<KV_BF16><<<grid, 64 * a.G, 0, stream>>>(a);
+    a.q_weight = (const uint16_t *)q_weight;
+    a.k_weight = (const uint16_t *)k_weight;
+    a.eps = eps;
+    const RopePrefillArgs &plain = a;
+    if (q_weight) {
+        if (kind == KV_INT4) rope_prefill_kernel<KV_INT4, true><<<grid, 64 * a.G, 0, stream>>>(a);
+        else if (kind == KV_FP8) rope_prefill_kernel<KV_FP8, true><<<grid, 64 * a.G, 0, stream>>>(a);
+        else rope_prefill_kernel<KV_BF16, true><<<grid, 64 * a.G, 0, stream>>>(a);
+    } else if (kind == KV_INT4) rope_prefill_kernel<KV_INT4, false><<<grid, 64 * a.G, 0, stream>>>(plain);
+    else if (kind == KV_FP8) rope_prefill_kernel<KV_FP8, false><<<grid, 64 * a.G, 0, stream>>>(plain);
+    else rope_prefill_kernel<KV_BF16, false><<<grid, 64 * a.G, 0, stream>>>(plain);
     return hipGetLastError();
 }
 

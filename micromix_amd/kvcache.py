@@ -462,18 +462,25 @@ class PagedKVCache:
             raise RuntimeError(f"append expects the {self.num_new_tokens} tokens announced by extend(), got k of shape {tuple(k.shape)}")
         mixedgemm.kv_append(self.kv_data, self.kv_param, self.kv_indptr, self.kv_indices, self.last_page_len, k, v, self.append_indptr, layer)
 
-    def append_rope(self, layer, q, k, v, cos, sin, dense=False):
+    def append_rope(self, layer, q, k, v, cos, sin, dense=False, *, qk_norm=None):
         """RoPE + `append` in one launch: rotates q and k (bf16 [T, H, 128] or [T, H * 128], e.g. the views FusedQLinear returns) by the
         bf16 cos / sin rows of the announced tokens ([T, 128] or HF's [bsz, q_len, 128]), writes the rotated K and V of `layer` and returns
         the rotated q, bf16 [T, Hq, 128], for `attend` / `attend_new`.  Bit-equal to HF's bf16 apply_rotary_pos_emb followed by `append`.
         dense=True: the same cache bytes and the same q from the prefill-shaped kernel (`mixedgemm.rope_kv_append_dense`), which returns
-        (q_rot, k_seen, v_seen): with them the K and V of the announced tokens as the cache now holds them, for `dense_attention`."""
+        (q_rot, k_seen, v_seen): with them the K and V of the announced tokens as the cache now holds them, for `dense_attention`.
+        qk_norm = (q_weight, k_weight, eps): Qwen3's q_norm / k_norm (bf16 [128] each) on every q and k head row ahead of the rotation,
+        in the same launch, HF's Qwen3RMSNorm (include/micromix_qknorm.h); head_dim 128 only, ValueError on a cache with head_dim 64."""
+        if qk_norm is not None and self.head_dim == 64:
+            raise ValueError("append_rope(qk_norm=) has no form for head_dim 64: the QK-norm kernels are 128-only")
         if q.dim() not in (2, 3) or q.size(0) != self.num_new_tokens:
             raise RuntimeError(f"append_rope expects the {self.num_new_tokens} tokens announced by extend(), got q of shape {tuple(q.shape)}")
         op = mixedgemm.rope_kv_append_dense if dense else mixedgemm.rope_kv_append
+        if qk_norm is not None:
+            return op(self.kv_data, self.kv_param, self.kv_indptr, self.kv_indices, self.last_page_len, q, k, v, cos, sin, self.append_indptr,
+                      layer, qk_norm=qk_norm)
         return op(self.kv_data, self.kv_param, self.kv_indptr, self.kv_indices, self.last_page_len, q, k, v, cos, sin, self.append_indptr, layer)
 
-    def prefill_fresh(self, layer, q, k, v, cos, sin, sm_scale=None, *, windowed=False):
+    def prefill_fresh(self, layer, q, k, v, cos, sin, sm_scale=None, *, windowed=False, qk_norm=None):
         """`append_rope` + `attend_new` for prompts that start their sequences, on the dense kernel: after `extend`, when every sequence
         with announced tokens consists of exactly those tokens, the attention of the new tokens over the cache is square causal
         attention over the new tokens themselves.  Runs `append_rope(dense=True)` and `mixedgemm.dense_attention(q_rot, k_seen, v_seen,
@@ -488,7 +495,10 @@ class PagedKVCache:
         k_seen, v_seen, W, seq_indptr=append_indptr)`: every new token attends the last W tokens, its own included, as `attend_new`
         has it there.  It rests on this: `extend` releases no page of a sequence whose announced tokens start at position 0 -- the
         first of them has a window that begins at 0 -- so every slot the append writes exists; the pages below the window of the
-        last token go at the next `extend`, as they do after `attend_new`.  On a cache without a window it is the plain route."""
+        last token go at the next `extend`, as they do after `attend_new`.  On a cache without a window it is the plain route.
+        qk_norm as `append_rope` takes it."""
+        if qk_norm is not None and self.head_dim == 64:
+            raise ValueError("prefill_fresh(qk_norm=) has no form for head_dim 64: the QK-norm kernels are 128-only")
         if windowed:
             self._only_128("prefill_fresh(windowed=True)")
         if self.window and not windowed:
@@ -501,7 +511,7 @@ class PagedKVCache:
         if held:
             raise ValueError(f"prefill_fresh: sequences {held} held tokens before the announced ones, which dense attention would not "
                              "see; use append_rope() and attend_new()")
-        q_rot, k_seen, v_seen = self.append_rope(layer, q, k, v, cos, sin, dense=True)
+        q_rot, k_seen, v_seen = self.append_rope(layer, q, k, v, cos, sin, dense=True, qk_norm=qk_norm)
         if self.window:
             return mixedgemm.dense_attention_window(q_rot, k_seen, v_seen, self.window, seq_indptr=self.append_indptr, sm_scale=sm_scale)
         return mixedgemm.dense_attention(q_rot, k_seen, v_seen, seq_indptr=self.append_indptr, sm_scale=sm_scale)
@@ -543,7 +553,7 @@ class PagedKVCache:
         return mixedgemm.paged_decode(q, self.kv_data, self.kv_param, self.kv_indptr, self.kv_indices, self.last_page_len, layer, bound,
                                       sm_scale=sm_scale, workspace=self._workspace if need else None, window=self.window)
 
-    def decode_step(self, layer, q, k, v, cos, sin, max_seq_len=None, sm_scale=None):
+    def decode_step(self, layer, q, k, v, cos, sin, max_seq_len=None, sm_scale=None, *, qk_norm=None):
         """`append_rope` + `attend` of a decode step -- `extend(1)`: one new token per sequence -- in one launch
         (`mixedgemm.rope_append_decode`): q, k, v, cos, sin as `append_rope` takes them, returns o, bf16 [B, Hq, 128].  The cache bytes
         and o are the pair's, bit for bit; max_seq_len and sm_scale as in `attend`.  A sequence that has forked is fine: `extend` has
@@ -552,7 +562,8 @@ class PagedKVCache:
         bf16, 1 x 4 096 to 64 x 1 024 and 1 x 32 768), most at 64 sequences and bf16 rows, within the spread of the repeats
         at fp8 1 x 4 096: use it for plain decode steps; the pair stays as it is and remains the way for everything else.
         ValueError, before any device work, on a cache made with window= or head_dim=64, and when the last `extend` did not announce
-        exactly one token for every sequence."""
+        exactly one token for every sequence.
+        qk_norm as `append_rope` takes it: the step of a Qwen3 layer stays one launch."""
         if self.head_dim == 64:
             raise ValueError("decode_step has no form for head_dim 64: its kernel is 128-only; use append_rope() and attend()")
         if self.window:
@@ -570,6 +581,10 @@ class PagedKVCache:
             if self._workspace is not None:
                 self._retired.append(self._workspace)      # a graph captured earlier may still point at it
             self._workspace = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        if qk_norm is not None:
+            return mixedgemm.rope_append_decode(self.kv_data, self.kv_param, self.kv_indptr, self.kv_indices, self.last_page_len, q, k, v, cos,
+                                                sin, layer, bound, sm_scale=sm_scale, workspace=self._workspace if need else None,
+                                                qk_norm=qk_norm)
         return mixedgemm.rope_append_decode(self.kv_data, self.kv_param, self.kv_indptr, self.kv_indices, self.last_page_len, q, k, v, cos, sin,
                                             layer, bound, sm_scale=sm_scale, workspace=self._workspace if need else None)
 

@@ -45,6 +45,7 @@ _DENSE_HD64 = ("mm_dense_attention_hd64", "mm_dense_attention_hd64 / mm_rope_qk_
 _SHARED = ("mm_paged_decode_shared", "mm_paged_decode_shared", "shared-prefix decode")
 _KV_HD64 = ("mm_paged_decode_hd64", "mm_rope_kv_append_hd64 / mm_paged_decode_hd64", "the paged cache for 64-wide heads")
 _DECODE_STEP = ("mm_rope_append_decode", "mm_rope_append_decode", "the one-launch decode step")
+_QKNORM = ("mm_rope_kv_append_qknorm", "mm_rope_kv_append_qknorm / mm_rope_prefill_qknorm / mm_rope_append_decode_qknorm", "QK-norm in the RoPE kernels")
 _KV_PREFILL_HD64 = ("mm_paged_prefill_hd64", "mm_paged_prefill_hd64", "multi-token attention over the paged cache for 64-wide heads")
 
 
@@ -1066,7 +1067,26 @@ def _rope_operands(dev, Hkv, q, k, v, cos, sin, vec, hd=128):
     return T, Hq, Hkv, q, k, v, sq, cos, sin, sc
 
 
-def rope_kv_append(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, q, k, v, cos, sin, append_indptr, layer_idx):
+def _qk_norm(qk_norm, what, dev, hd64):
+    """qk_norm = (q_weight, k_weight, eps) of Qwen3's q_norm / k_norm as the *_qknorm entries take it (include/micromix_qknorm.h): the
+    two pointers and the float.  `hd64`: the call is one over 64-wide rows, which have no normed kernel"""
+    if hd64:
+        raise ValueError(f"{what}(qk_norm=) has no form for head_dim 64: the QK-norm kernels are 128-only")
+    try:
+        q_weight, k_weight, eps = qk_norm
+    except (TypeError, ValueError):
+        raise TypeError("qk_norm must be (q_weight, k_weight, eps): the two bf16 [128] weights of q_norm and k_norm and their eps") from None
+    q_weight = _tensor(q_weight, "qk_norm's q_weight", torch.bfloat16, dev, (128,))
+    k_weight = _tensor(k_weight, "qk_norm's k_weight", torch.bfloat16, dev, (128,))
+    eps = float(eps)
+    if not (0.0 < eps < float("inf")):
+        raise ValueError(f"qk_norm's eps must be finite and > 0, got {eps}")
+    if q_weight.data_ptr() % 16 or k_weight.data_ptr() % 16:
+        raise RuntimeError("qk_norm's weights must be 16-byte aligned")
+    return _ptr(q_weight), _ptr(k_weight), eps
+
+
+def rope_kv_append(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, q, k, v, cos, sin, append_indptr, layer_idx, *, qk_norm=None):
     """RoPE on q and k, then `kv_append` of (rotated k, v), in one launch; returns the rotated q, bf16 [T, Hq, 128] contiguous.
 
     q, k, v: bf16 [T, H, 128] or [T, H * 128].  Views of one packed [T, (Hq + 2 Hkv) * 128] projection (what FusedQLinear returns) are
@@ -1076,22 +1096,31 @@ def rope_kv_append(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, q, k
     (include/micromix_hip.h, mm_rope_kv_append).  The cache receives exactly what kv_append(rope(k), v) writes; q is rotated for every
     token.  Page table, append_indptr and the three cache kinds (int4, fp8 e4m3, bf16) as in `kv_append`.  Runs on the current stream,
     capture-safe.
+    qk_norm = (q_weight, k_weight, eps): Qwen3's q_norm / k_norm, HF's Qwen3RMSNorm of every q and k head row (bf16 [128] weights, one
+    per side, shared by its heads) ahead of the rotation, in the same launch (include/micromix_qknorm.h, which states the rule and the
+    order of its sum).  128-wide heads only: ValueError over a cache with head_dim 64.
     """
     if _cache_head_dim(kv_data, kv_param) == 64:
+        if qk_norm is not None:
+            _qk_norm(qk_norm, "rope_kv_append", None, True)
         return _rope_kv_append_hd64(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, q, k, v, cos, sin, append_indptr, layer_idx, False)
-    lib = _lib.load()
+    lib = _lib.load() if qk_norm is None else _lib_with(*_QKNORM)
     dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx)
     _tensor(append_indptr, "append_indptr", torch.int32, dev)
     if append_indptr.numel() != B + 1:
         raise RuntimeError("append_indptr must have B + 1 entries")
     T, Hq, _, q, k, v, sq, cos, sin, sc = _rope_operands(dev, Hkv, q, k, v, cos, sin, 2)
     q_rot = torch.empty((T, Hq, 128), dtype=torch.bfloat16, device=dev)
+    if qk_norm is not None:
+        _launch("rope_kv_append", dev, lib.mm_rope_kv_append_qknorm, *kv_args, _ptr(q), _ptr(k), _ptr(v), sq, Hq, _ptr(cos), _ptr(sin), sc,
+                _ptr(append_indptr), T, _ptr(q_rot), *_qk_norm(qk_norm, "rope_kv_append", dev, False), _stream_ptr(dev))
+        return q_rot
     _launch("rope_kv_append", dev, lib.mm_rope_kv_append, *kv_args, _ptr(q), _ptr(k), _ptr(v), sq, Hq, _ptr(cos), _ptr(sin), sc,
             _ptr(append_indptr), T, _ptr(q_rot), _stream_ptr(dev))
     return q_rot
 
 
-def rope_kv_append_dense(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, q, k, v, cos, sin, append_indptr, layer_idx):
+def rope_kv_append_dense(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, q, k, v, cos, sin, append_indptr, layer_idx, *, qk_norm=None):
     """`rope_kv_append` in the shape of a prompt (include/micromix_rope.h, mm_rope_prefill: several tokens per workgroup, 16-byte accesses),
     returning what `dense_attention` over a fresh prompt needs: (q_rot [T, Hq, 128], k_seen [T, Hkv, 128], v_seen [T, Hkv, 128]), bf16.
 
@@ -1099,10 +1128,12 @@ def rope_kv_append_dense(kv_data, kv_param, kv_indptr, kv_indices, last_page_len
     each token's slot gets back: for a bf16 cache rope(k) and v -- v_seen is then the `v` argument itself, nothing is copied --, for
     fp8 code * 2^e, for int4 bf16(code * scale - zero), computed in fp32: the bf16 tensor the reference's quantize_int_group returns.
     Inputs are read in place when their strides are multiples of 8 elements and their pointers 16-byte aligned, and copied once
-    otherwise.  Runs on the current stream, capture-safe."""
+    otherwise.  Runs on the current stream, capture-safe.  qk_norm as in `rope_kv_append`: the same bits from this kernel."""
     if _cache_head_dim(kv_data, kv_param) == 64:
+        if qk_norm is not None:
+            _qk_norm(qk_norm, "rope_kv_append_dense", None, True)
         return _rope_kv_append_hd64(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, q, k, v, cos, sin, append_indptr, layer_idx, True)
-    lib = _lib_with(*_ROPE)
+    lib = _lib_with(*(_ROPE if qk_norm is None else _QKNORM))
     dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx)
     _tensor(append_indptr, "append_indptr", torch.int32, dev)
     if append_indptr.numel() != B + 1:
@@ -1112,8 +1143,13 @@ def rope_kv_append_dense(kv_data, kv_param, kv_indptr, kv_indices, last_page_len
     q_rot = torch.empty((T, Hq, 128), dtype=torch.bfloat16, device=dev)
     k_seen = torch.empty((T, Hkv, 128), dtype=torch.bfloat16, device=dev)
     v_seen = torch.empty((T, Hkv, 128), dtype=torch.bfloat16, device=dev) if kv_param is not None else None
-    _launch("rope_kv_append_dense", dev, lib.mm_rope_prefill, *kv_args, _ptr(q), _ptr(k), _ptr(v), sq, Hq, _ptr(cos), _ptr(sin), sc,
-            _ptr(append_indptr), T, _ptr(q_rot), _ptr(k_seen), _opt(v_seen), _stream_ptr(dev))
+    if qk_norm is not None:
+        _launch("rope_kv_append_dense", dev, lib.mm_rope_prefill_qknorm, *kv_args, _ptr(q), _ptr(k), _ptr(v), sq, Hq, _ptr(cos), _ptr(sin), sc,
+                _ptr(append_indptr), T, _ptr(q_rot), _ptr(k_seen), _opt(v_seen), *_qk_norm(qk_norm, "rope_kv_append_dense", dev, False),
+                _stream_ptr(dev))
+    else:
+        _launch("rope_kv_append_dense", dev, lib.mm_rope_prefill, *kv_args, _ptr(q), _ptr(k), _ptr(v), sq, Hq, _ptr(cos), _ptr(sin), sc,
+                _ptr(append_indptr), T, _ptr(q_rot), _ptr(k_seen), _opt(v_seen), _stream_ptr(dev))
     return q_rot, k_seen, v_seen if v_seen is not None else v_given
 
 
@@ -1149,7 +1185,7 @@ def _head_dim_is_64(kv_param, **operands):
                                "always means 128-wide heads")
 
 
-def rope_qk(q, k, cos, sin):
+def rope_qk(q, k, cos, sin, *, qk_norm=None):
     """RoPE on q and k without a cache, in one launch: (q_rot [T, Hq, 128], k_rot [T, Hkv, 128]), bf16 contiguous -- HF's bf16
     apply_rotary_pos_emb, q * cos + rotate_half(q) * sin with every op rounded to bf16, bit for bit (include/micromix_rope.h,
     mm_rope_prefill without a cache), ready for `dense_attention(q_rot, k_rot, v)`.
@@ -1159,11 +1195,14 @@ def rope_qk(q, k, cos, sin):
     once.  cos, sin: bf16 [T, 128] or HF's [1, T, 128] / [bsz, q_len, 128] (flattened); a row stride is honoured.  Runs on the current
     stream, capture-safe.
     64-wide heads (include/micromix_attention_hd64.h, mm_rope_qk_hd64): q and k given as [T, H, 64] -- both, and 3-D: a 2-D tensor
-    always means 128 -- with cos, sin [T, 64] return (q_rot [T, Hq, 64], k_rot [T, Hkv, 64]) by the same rule with the partner at d +- 32."""
+    always means 128 -- with cos, sin [T, 64] return (q_rot [T, Hq, 64], k_rot [T, Hkv, 64]) by the same rule with the partner at d +- 32.
+    qk_norm as in `rope_kv_append` (128-wide heads only: ValueError with 64-wide q and k)."""
     hd = _head_dim(q=q, k=k)
+    if qk_norm is not None and hd == 64:
+        _qk_norm(qk_norm, "rope_qk", None, True)
     if hd == 64 and not all(isinstance(t, torch.Tensor) and t.size(-1) == 64 for t in (cos, sin)):
         raise RuntimeError("cos and sin must be [T, 64] bf16 for 64-wide heads")
-    lib = _lib_with(*(_ROPE if hd == 128 else _DENSE_HD64))
+    lib = _lib_with(*(_QKNORM if qk_norm is not None else _ROPE if hd == 128 else _DENSE_HD64))
     if not (isinstance(q, torch.Tensor) and q.dtype is torch.bfloat16 and q.is_cuda):
         _check_tensor(q, "q", torch.bfloat16)
     dev = q.device
@@ -1172,6 +1211,11 @@ def rope_qk(q, k, cos, sin):
     k_rot = torch.empty((T, Hkv, hd), dtype=torch.bfloat16, device=dev)
     if hd == 64:
         _launch("rope_qk", dev, lib.mm_rope_qk_hd64, _ptr(q), _ptr(k), sq, Hq, Hkv, _ptr(cos), _ptr(sin), sc, T, _ptr(q_rot), _ptr(k_rot),
+                _stream_ptr(dev))
+        return q_rot, k_rot
+    if qk_norm is not None:
+        _launch("rope_qk", dev, lib.mm_rope_prefill_qknorm, None, None, 0, 0, 0, 0, Hkv, 0, 128, None, None, None, 0, _ptr(q), _ptr(k), _ptr(k),
+                sq, Hq, _ptr(cos), _ptr(sin), sc, None, T, _ptr(q_rot), _ptr(k_rot), None, *_qk_norm(qk_norm, "rope_qk", dev, False),
                 _stream_ptr(dev))
         return q_rot, k_rot
     _launch("rope_qk", dev, lib.mm_rope_prefill, None, None, 0, 0, 0, 0, Hkv, 0, 128, None, None, None, 0, _ptr(q), _ptr(k), _ptr(k), sq, Hq,
@@ -1271,7 +1315,7 @@ def rope_append_decode_workspace_bytes(B, Hq, Hkv, max_seq_len):
 
 
 def rope_append_decode(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, q, k, v, cos, sin, layer_idx, max_seq_len, sm_scale=None,
-                       workspace=None, *, q_out=None):
+                       workspace=None, *, q_out=None, qk_norm=None):
     """One decode step of layer `layer_idx` in one launch: `rope_kv_append` with one new token per sequence (append_indptr = 0, 1, .., B)
     and `paged_decode` of the rotated q over the sequences that now hold it; returns o, bf16 [B, Hq, 128].
 
@@ -1282,10 +1326,11 @@ def rope_append_decode(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, 
     rope_append_decode_workspace_bytes) -- pass one when capturing a graph.  q_out: bf16 [B, Hq, 128] contiguous, receives the rotated
     q when given.  The three 128-wide cache kinds; no sliding-window, shared-prefix or tree form, one token per sequence, and a cache
     with head_dim 64 raises ValueError.  Runs on the current stream, capture-safe.
+    qk_norm as in `rope_kv_append`: then the cache, q_out and o are those of `rope_kv_append(qk_norm=)` followed by `paged_decode`.
     """
     if _cache_head_dim(kv_data, kv_param) == 64:
         raise ValueError("rope_append_decode has no form for head_dim 64: its kernel is 128-only; use rope_kv_append and paged_decode")
-    lib = _lib_with(*_DECODE_STEP)
+    lib = _lib_with(*(_DECODE_STEP if qk_norm is None else _QKNORM))
     dev, B, Hkv, kv_args = _kv_args(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, layer_idx)
     T, Hq, _, q, k, v, sq, cos, sin, sc = _rope_operands(dev, Hkv, q, k, v, cos, sin, 2)
     if T != B:
@@ -1296,6 +1341,11 @@ def rope_append_decode(kv_data, kv_param, kv_indptr, kv_indices, last_page_len, 
     if q_out is not None:
         _tensor(q_out, "q_out", torch.bfloat16, dev, (B, Hq, 128))
     o = torch.empty((B, Hq, 128), dtype=torch.bfloat16, device=dev)
+    if qk_norm is not None:
+        _launch("rope_append_decode", dev, lib.mm_rope_append_decode_qknorm, *kv_args, _ptr(q), _ptr(k), _ptr(v), sq, Hq, _ptr(cos), _ptr(sin),
+                sc, max_seq_len, _sm_scale(sm_scale), *ws_args, _opt(q_out), _ptr(o), *_qk_norm(qk_norm, "rope_append_decode", dev, False),
+                _stream_ptr(dev))
+        return o
     _launch("rope_append_decode", dev, lib.mm_rope_append_decode, *kv_args, _ptr(q), _ptr(k), _ptr(v), sq, Hq, _ptr(cos), _ptr(sin), sc,
             max_seq_len, _sm_scale(sm_scale), *ws_args, _opt(q_out), _ptr(o), _stream_ptr(dev))
     return o

@@ -6,6 +6,13 @@
 Per product source: the SHA-256 of its gfx950 assembly (<stem>-hip-amdgcn-amd-amdhsa-gfx950.s) in both builds after every
 __hip_cuid_<hash> -- a hash of the translation unit, the one symbol that follows the source text -- is replaced by one token, and
 the compiler's .ident line.  Exit status 1 if a source differs; its first differing lines are printed.
+
+    python tools/compare_isa.py --kernels PARENT/micromix_amd/lib/obj BRANCH/micromix_amd/lib/obj rope_append.hip [...]
+
+For a source that gained instantiations (a new template parameter) and must keep its old ones: every kernel of the parent is looked
+up in the branch by its name up to the template arguments the branch appended with the value `false`, and the two bodies -- the
+instructions and labels between .globl and the end of the function, the kernel's own symbol and the function index of its local
+labels replaced -- must be equal.  Exit status 1 if a kernel differs or is missing.
 """
 import hashlib
 import os
@@ -40,5 +47,40 @@ def main(parent, branch):
     return 1 if differ else 0
 
 
+def kernel_bodies(objdir, src):
+    """{kernel symbol: its instructions and labels} of a source's device assembly"""
+    out, name = {}, None
+    for line in normalised(objdir, src):
+        m = re.match(r"\s*\.globl\s+(\S+)", line)
+        if m:
+            name = None if m.group(1).startswith("__hip_cuid") else m.group(1)      # the translation unit's hash is data, not a kernel
+            if name:
+                out[name] = []
+        elif name and "-- End function" in line:
+            name = None
+        elif name:
+            t = line.split(";")[0].rstrip()
+            if t.strip() and not t.strip().startswith("."):
+                out[name].append(re.sub(r"\.LBB\d+_", ".LBB_", t.replace(name, "SELF")))
+    return out
+
+
+def template_key(symbol):
+    """the kernel's name and template arguments without trailing `false` arguments and without its parameter types"""
+    m = re.search(r"(\d+[A-Za-z_]\w*?)I((?:L[a-z]\d+E)+)E", symbol)
+    return (m.group(1), re.sub(r"(Lb0E)+$", "", m.group(2))) if m else (symbol, "")
+
+
+def main_kernels(parent, branch, sources):
+    bad = 0
+    for src in sources:
+        theirs = {template_key(n): b for n, b in kernel_bodies(branch, src).items() if "Lb1E" not in template_key(n)[1]}
+        for name, body in sorted(kernel_bodies(parent, src).items()):
+            same = theirs.get(template_key(name)) == body
+            bad += not same
+            print(f"{src:20s} {'.'.join(template_key(name)):48s} {len(body):6d} lines  {'identical' if same else 'DIFFERENT or missing'}")
+    return 1 if bad else 0
+
+
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    sys.exit(main_kernels(sys.argv[2], sys.argv[3], sys.argv[4:]) if sys.argv[1] == "--kernels" else main(sys.argv[1], sys.argv[2]))
